@@ -14,11 +14,21 @@ ends.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   roofline      - dominant kernel's algorithmic work / measured HIP-event time
+                  (events recorded inside the timed steps: no run of its own)
+and, with --full only:
   cpu_baseline  - the CPU oracle timed on a bounded sample (rank 0, N=1 only)
   extra_configs - at N=1: BASELINE configs[1] (step) and configs[2] (step+obs)
                   and the two reference-faithful policy workloads (one policy
                   ship per arena; destroyed ships skipped), each with its own
                   roofline - labelled secondary lines, never `value`
+A plain run sets up, warms up, times --steps lock-steps and prints the line.
+
+--dump-outputs DIR writes what the timed path computed in its last lock-step
+(rank 0's shard) as DIR/<name>.npy, float32 (laser positions and the last
+episode's all-reduced scores float64): the
+ships' state, the actions that step consumed, the policy's act values / action
+/ pointer, the laser lists and the u8 maps of a fixed, seeded sample of arenas.
+The inputs depend only on the arguments (seeded spawns, bots and weights).
 """
 import argparse
 import json
@@ -33,6 +43,8 @@ SEED = 0x0F160001
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 FP32_PEAK_TF = 157.3    # fp32 vector = f32-input MFMA peak
 METRIC = "arena-steps/sec (env.step+obs+policy fwd) at 4096 arenas, 1/2/4/8 MI355X"
+DUMP_ARENAS = 32        # --dump-outputs: arenas whose laser lists and maps are written (2 x 20 MB of f32 maps at 32)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def pmc_files():
@@ -277,11 +289,46 @@ def scratch_feed_line(N, M, device, base, fence):
     return rec
 
 
+def dump_outputs(path, wl, torch, nat):
+    """--dump-outputs: the arrays a caller of the timed path receives after its last lock-step, as path/<name>.npy.
+    Per-ship arrays cover every arena; the laser lists (slots past n_lasers zeroed) and the 400 x 400 maps cover
+    DUMP_ARENAS arenas drawn with a fixed seed (sample_arenas.npy).  Called after the timed region's final fence."""
+    import numpy as np
+    b = wl.b
+    pick = np.sort(np.random.RandomState(SEED).choice(b.N, min(b.N, DUMP_ARENAS), replace=False))
+    out = {"sample_arenas": pick.astype(np.float32)}
+    s = b.snapshot()
+    for k in ("x", "y", "px", "py", "alive", "hull", "reward", "score"):
+        out["ship_" + k] = s[k].astype(np.float32)
+    out["n_lasers"] = s["n_lasers"].astype(np.float32)
+    live = np.arange(b.L)[None, :] < s["n_lasers"][pick, None]
+    for k, dt in (("lx", np.float64), ("ly", np.float64), ("lowner", np.float32), ("ldead", np.float32)):
+        out["laser_" + k[1:]] = np.where(live, s[k][pick], 0).astype(dt)
+    if wl.do_policy:     # the headless workloads draw the bots' actions inside k_step: no action array is written
+        a = b.actions_host()
+        out["actions"] = np.stack([a[k] for k in ("valid", "shoot", "thrust", "px", "py")], axis=-1).astype(np.float32)
+    if wl.capture is not None:
+        for k, t in zip(("act_values", "iaction", "ipointer"), wl.capture):
+            out[k] = t.cpu().numpy().astype(np.float32)
+    if wl.do_obs:
+        for k, m in zip(("ship_map", "laser_map"), b.maps_tensor(nat.MAP_U8)):
+            out[k] = m.index_select(0, torch.from_numpy(pick).to(m.device)).cpu().numpy().astype(np.float32)
+    if wl.roll.score_log:
+        out["last_episode_scores"] = np.asarray(wl.roll.score_log[-1], np.float64)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (at most %d MB): fewer ships per arena"
+                         % (total / 2**20, DUMP_MAX_BYTES >> 20))
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+
+
 class Workload:
     """One timed configuration on an ArenaBatch: ShardedRollout + the policy hook + HIP-event bracketing of the
     dominant kernel."""
 
-    def __init__(self, b, workload, n_pol, alive_only, w_dev, dist, torch, nat, ep_ticks, start_tick=0):
+    def __init__(self, b, workload, n_pol, alive_only, w_dev, dist, torch, nat, ep_ticks, start_tick=0, capture=False):
         import numpy as np
         from ofighters_amd.rollout import ShardedRollout
         self.b, self.workload, self.n_pol, self.alive_only = b, workload, n_pol, alive_only
@@ -290,6 +337,14 @@ class Workload:
         self.nat, self.np = nat, np
         self.ev = 0
         self.timed = False
+        self.timed_steps = self.steps = 0
+        # capture (--dump-outputs): the LAST timed forward writes act values / iaction / ipointer into these buffers
+        # instead of the handle's workspace (same kernels; act values are only stored when a buffer is given)
+        self.capture = None
+        if capture and self.do_policy:
+            self.capture = (torch.zeros((b.N, b.M, 2), dtype=torch.float32, device="cuda"),
+                            torch.zeros((b.N, b.M), dtype=torch.int32, device="cuda"),
+                            torch.zeros((b.N, b.M, 2), dtype=torch.int32, device="cuda"))
         N, M = b.N, b.M
         self.mask_ptr = None
         self._keep = None
@@ -314,10 +369,15 @@ class Workload:
         # request_actions: the policy ships' actions overwrite the scripted ones
         if self.timed and self.ev == 0:
             e.policy_profile(0)          # the library brackets its dominant kernel with event pairs from here on
-        e.policy_forward(self.w_ptr, self.mask_ptr)
+        out = (None, None, None)
+        if self.timed:
+            self.timed_steps += 1
+            if self.capture is not None and self.timed_steps == self.steps:
+                out = tuple(t.data_ptr() for t in self.capture)
+        e.policy_forward(self.w_ptr, self.mask_ptr, *out)
         if self.timed:
             self.ev += 2
-        e.policy_actions(ship_mask_ptr=self.mask_ptr)
+        e.policy_actions(iaction_ptr=out[1], ipointer_ptr=out[2], ship_mask_ptr=self.mask_ptr)
 
     def _probe(self, stage, begin, n=1):
         # headless workloads (no policy): K lock-steps per ofx_rollout call; the library itself brackets the call's
@@ -332,6 +392,7 @@ class Workload:
         self.roll.run(warmup)
         fence()
         self.episodes_before = len(self.roll.score_log)
+        self.steps = steps
         self.timed = True
         t0 = time.perf_counter()
         self.roll.run(steps)
@@ -447,10 +508,16 @@ def main():
     ap.add_argument("--trunk-sparse", action="store_true",
                     help="OFX_OPT_TRUNK_SPARSE for the main line (exact, bit-identical, opt-in: NOT the headline "
                          "configuration - for profiling the secondary lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline and, at N=1 on the "
+                         "headline configuration, the secondary configurations (other workloads, precisions, the "
+                         "training tick) - each timed in runs of their own")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last lock-step as DIR/<name>.npy (rank 0's shard)")
     ap.add_argument("--no-bf16-accuracy", dest="bf16_accuracy", action="store_false",
-                    help="skip the float64 evaluation behind the bf16 lines' accuracy numbers (~20 s of CPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary configurations at N=1")
+                    help="with --full: skip the float64 evaluation behind the bf16 lines' accuracy numbers (~20 s of CPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary configurations at N=1")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -508,7 +575,7 @@ def main():
     base, _ = shard_range(rank, world, N)
     n_pol = M if args.policy_ships < 0 else min(M, args.policy_ships)
     w_host = w_dev = None
-    if args.workload == "step+obs+policy" or not args.no_extra:
+    if args.workload == "step+obs+policy" or (args.full and not args.no_extra):
         # synthetic he_uniform / glorot_uniform weights of the pointer_model architecture (no checkpoint
         # ships with the reference); seed 0x0F160002
         from ofighters_amd.agents.policy_weights import synthetic
@@ -521,7 +588,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(workload, n_pol_, alive_only, warmup, steps, full_config, bf16=False, sparse=False):
+    def measure(workload, n_pol_, alive_only, warmup, steps, full_config, bf16=False, sparse=False, dump=None):
         b = ArenaBatch(N, M, device=local_rank, arena_base=base)
         if args.trunk_form:
             b.set_option(nat.OPT_TRUNK_FUSE, args.trunk_form)
@@ -532,8 +599,10 @@ def main():
         ep = b.cfg.episode_ticks
         # an episode end (restart + score all-reduce) falls into the middle of the timed region whatever --steps is
         start = (ep - warmup - max(1, steps // 2)) % ep
-        wl = Workload(b, workload, n_pol_, alive_only, w_dev, dist, torch, nat, ep, start_tick=start)
+        wl = Workload(b, workload, n_pol_, alive_only, w_dev, dist, torch, nat, ep, start_tick=start, capture=dump is not None)
         dt, k_ms = wl.run(warmup, steps, fence, torch, dist)
+        if dump is not None and rank == 0:
+            dump_outputs(dump, wl, torch, nat)
         rec = {"workload": wl.describe(), "value": world * N * steps / dt, "unit": "arena-steps/s", "steps": steps,
                "warmup": warmup, "ms_per_step": dt / steps * 1e3, "roofline": wl.roofline(k_ms, dt, steps, full_config),
                "laser_overflow": b.overflow_count(), "laser_cap": b.L, "episode_ticks": ep,
@@ -558,7 +627,8 @@ def main():
 
     headline_full = N == 4096 and M == 8 and n_pol == M and not args.policy_alive_only and not args.policy_bf16 and not args.trunk_sparse
     head = measure(args.workload, n_pol, args.policy_alive_only, args.warmup, args.steps,
-                   headline_full or args.workload != "step+obs+policy", bf16=args.policy_bf16, sparse=args.trunk_sparse)
+                   headline_full or args.workload != "step+obs+policy", bf16=args.policy_bf16, sparse=args.trunk_sparse,
+                   dump=args.dump_outputs)
     do_policy = args.workload == "step+obs+policy"
     out = {
         "metric": METRIC,
@@ -586,7 +656,7 @@ def main():
         if k in head:
             out["config"][k] = head[k]
 
-    if world == 1 and not args.no_extra and do_policy and headline_full:
+    if args.full and world == 1 and not args.no_extra and do_policy and headline_full:
         # secondary lines (never `value`): BASELINE configs[1] / [2], and the two reference-faithful policy workloads -
         # the stock line-up has ONE QlearnIA ship (lib/ofighters.py:53: bound 1.01 M arena-steps/s), and
         # QlearnIA.play returns None once the ship is destroyed (agents/qlearnIA_V2.py:372-377)
@@ -675,7 +745,7 @@ def main():
                     "bf16 = opt-in OFX_OPT_POLICY_BF16 (no parity credit)",
         }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.workload, M, n_pol, w_host, head["episode_ticks"])
     if rank == 0:
         print(json.dumps(out))

@@ -40,7 +40,7 @@ def test_two_rank_launch_line():
 
 @gpu
 def test_single_rank_line_has_the_contract_fields():
-    d = _bench(["--arenas", "128", "--steps", "12", "--warmup", "3", "--no-extra"])
+    d = _bench(["--arenas", "128", "--steps", "12", "--warmup", "3", "--no-extra", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -49,6 +49,28 @@ def test_single_rank_line_has_the_contract_fields():
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1
     assert d["cpu_baseline"]["all_cores"]["cores"] >= 1 and d["cpu_baseline"]["cpu_model"]
     assert d["config"]["episodes_in_timed_region"] >= 1
+
+
+@gpu
+def test_plain_line_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """Without --full the line carries the headline only (no CPU baseline, no secondary lines); --steps sets the timed
+    lock-steps; --dump-outputs writes the last timed lock-step's arrays (f32 / f64, within 64 MB), the same bits on a
+    second run with the same arguments."""
+    import numpy as np
+    args = ["--arenas", "64", "--steps", "7", "--warmup", "2"]
+    dumps = []
+    for i in range(2):
+        d = _bench(args + ["--dump-outputs", str(tmp_path / str(i))])
+        assert "cpu_baseline" not in d and "extra_configs" not in d and "secondary" not in d["config"]
+        assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["roofline"]["kernel"] == "k_head_stream"
+        dumps.append({p.stem: np.load(p) for p in sorted((tmp_path / str(i)).glob("*.npy"))})
+    a, b = dumps
+    assert {"act_values", "iaction", "ipointer", "actions", "ship_x", "ship_map", "laser_map", "laser_x"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["act_values"].shape == (64, 8, 2) and np.abs(a["act_values"]).max() > 0
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
 
 
 @gpu

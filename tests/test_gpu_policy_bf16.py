@@ -1,7 +1,7 @@
 """OFX_OPT_POLICY_BF16 - the OPT-IN reduced-precision forward (value 1: bf16, value 2: fp16 operands in conv2-4 and
 upconv3 / upconv4, fp32 sums; never the default, never the headline number).  Measured against the float64 graph like the fp32 path (tests/policy_ref64.py):
 the error of the heat map and how often its arg-max is the float64 map's are REPORTED (gpurun_out/policy_fp64_report.json,
-bench.py repeats the measurement in its bf16 lines); asserted is only that the switch gives a reduced-precision version
+bench.py --full repeats the measurement in its bf16 lines); asserted is only that the switch gives a reduced-precision version
 of the same function - act_values within 2e-2 of their scale (conv2 / conv3 of the streaming trunk run on bf16 operands
 too), the heat map within 3e-2 of its scale, the fused arg-max equal to the arg-max of the map the kernel wrote, every
 pointer a near-maximum of the float64 map - and that the fp32 path is untouched by the switch having been used."""
