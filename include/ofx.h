@@ -426,6 +426,46 @@ int ofx_replay_gather_valid(ofx_handle *h, const int32_t *slot, const int32_t *n
                             int32_t max_rows, ofx_transition *rows, void *bits_prev, void *bits_next,
                             int32_t *n_rows_host);
 
+/* ---- prioritized experience replay (opt-in) -----------------------------
+ * Schaul et al. 2016, proportional variant, per arena like the memories.  Off unless ofx_replay_prioritize is called;
+ * then nothing of the uniform path above changes either.
+ *  - Masses: float32 m = p^alpha per row, [N][C] in the ring positions of the rows (an append that overwrites a row
+ *    overwrites its mass).  A new row gets the arena's running maximum mmax[a] (starts at 1.0); rows already in the
+ *    memory when PER is enabled get 1.0.  An update sets p = |e1| + |e2| + eps (float32; e1, e2 = the row's signed TD
+ *    errors on the two heads), m = powf(p, alpha) and raises mmax[a] if needed; a non-finite error leaves the mass as it was.
+ *  - Sampling: stratified proportional, with replacement, within each arena over its ELIGIBLE rows (those
+ *    ofx_replay_sample uses: the oldest rows whose `state` frame has left the ring are skipped).  n = min(batch, valid)
+ *    draws.  Draw j: Philox counter (global arena, j, draw, stream 4), U = rr[0] * 2^-32,
+ *    u = ((double)j + U) / n * total; the row drawn is the first eligible row whose inclusive prefix mass is > u (none,
+ *    through rounding: the last eligible row).  Summation order, part of the contract: all sums in float64; the eligible
+ *    rows form 64 contiguous chunks of ceil(valid / 64) rows, each summed sequentially; the chunk totals are chained
+ *    sequentially in chunk order (excl[k] = chain before chunk k, total = the whole chain); the prefix of a row of chunk
+ *    k is excl[k] + (the sequential sum of chunk k's rows up to it).
+ *  - IS weights: raw w = (valid * m / total)^(-beta) in float64, stored as float32 (total = 0: 1); they correct back to
+ *    the uniform sampler's distribution (uniform within each arena, equal rows per arena).  alpha = 0 gives w = 1.
+ *  - Loss: Keras sample_weight semantics, sum w e1^2 / (2 n) + sum w e2^2 / (160000 n) (divided by n, not by sum w).
+ *  - Write-back: one thread per arena walks the window's entries in packed order, so a row drawn twice keeps the later
+ *    entry's priority.  An entry is skipped when the ring row its slot names (oldest-first, as ofx_replay_gather_valid
+ *    reads it NOW) no longer holds the gathered (tick_prev, ship): overwritten, or shifted by captures since sampling.
+ * ofx_replay_create / ofx_replay_destroy drop the priorities with the memory.                                        */
+/* Allocate mass [N][C] and mmax [N] and enable PER (OFX_ERR_STATE without ofx_replay_create; alpha < 0 or eps <= 0:
+ * OFX_ERR_INVALID).  Called again: new alpha / eps, every mass and mmax back to 1.0.  Synchronises.                */
+int ofx_replay_prioritize(ofx_handle *h, float alpha, float eps);
+/* The sampler above: slot[N][batch] / n_sampled[N] with ofx_replay_sample's layout and meaning (oldest-first indices,
+ * -1 pads), is_weight[N][batch] the raw IS weights (0 in pads).  Device pointers; n_sampled may be NULL.          */
+int ofx_replay_sample_prioritized(ofx_handle *h, uint64_t seed, uint32_t draw, int32_t batch, double beta, int32_t *slot,
+                                  int32_t *n_sampled, float *is_weight);
+/* The IS weights of the window ofx_replay_gather_valid gathers with the same (n_sampled, batch, first, max_rows):
+ * packed in its (arena, j) order into out[max_rows] (device) and divided by the window's maximum.                 */
+int ofx_replay_window_weights(ofx_handle *h, const float *is_weight, const int32_t *n_sampled, int32_t batch,
+                              int32_t first, int32_t max_rows, float *out);
+/* Write-back for the n_rows rows of that window: rows[n_rows] as ofx_replay_gather_valid wrote them, td[n_rows][2]
+ * = (e1, e2) (from ofx_dqn_fit_weighted's td_out or from the caller).  Device pointers.                           */
+int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, const int32_t *n_sampled, int32_t batch,
+                                 int32_t first, int32_t n_rows, const ofx_transition *rows, const float *td);
+/* Masses of one arena, oldest first (the order of ofx_replay_rows_host); mass_host holds `capacity` floats.        */
+int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *mass_host, int32_t *n_host);
+
 /* ---- forward on stored observations, TD targets -------------------------
  * The predictions Trainer.replay makes on a minibatch (agents/qlearnIA_V2.py:251-268): n_obs observations given as
  * 1-bit map pairs bits[n_obs][2 (ship, laser)][W*H/32] uint32 (the layout ofx_replay_gather writes) + their toVector
@@ -463,6 +503,13 @@ int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, const ofx_tr
 int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                 const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
                 float *grad_out, float *loss_host);
+/* ofx_dqn_fit with per-row loss weights (Keras sample_weight: sum w e1^2 / (2 n) + sum w e2^2 / (160000 n)) and the rows'
+ * errors from its own training-mode forward: row_weight [n] / td_out [n][2] = (e1, e2) = (prediction - target) on the
+ * two heads before the update, device pointers, either may be NULL.  The weight is the first factor of every seed, so
+ * a NULL row_weight or weights of 1.0 give ofx_dqn_fit bit for bit (lean and OFX_OPT_FIT_PLAIN forms).           */
+int ofx_dqn_fit_weighted(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
+                         const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
+                         float *grad_out, float *loss_host, const float *row_weight, float *td_out);
 /* The same step with Trainer.replay's quirks reproduced as written (agents/qlearnIA_V2.py:251-285), for a user who
  * wants the reference's training dynamics rather than the textbook DQN step above:
  *   - targets are whole predictions of `state` ([target, ptr_target] = predict(state), inference-mode BatchNorm) with

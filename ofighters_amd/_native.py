@@ -117,6 +117,7 @@ SIGNATURES = {
     "ofx_policy_forward_obs": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_targets": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "ofx_dqn_fit": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofx_dqn_fit_weighted": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_fit_reference": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "ofx_replay_create": (_i, [_vp, C.c_int32, C.c_int32]),
     "ofx_replay_destroy": (_i, [_vp]),
@@ -128,6 +129,11 @@ SIGNATURES = {
     "ofx_replay_sample": (_i, [_vp, _u64, _u32, C.c_int32, _vp, _vp]),
     "ofx_replay_gather": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp]),
     "ofx_replay_gather_valid": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ofx_replay_prioritize": (_i, [_vp, C.c_float, C.c_float]),
+    "ofx_replay_sample_prioritized": (_i, [_vp, _u64, _u32, C.c_int32, C.c_double, _vp, _vp, _vp]),
+    "ofx_replay_window_weights": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "ofx_replay_update_priorities": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "ofx_replay_priorities_host": (_i, [_vp, C.c_int32, _vp, _vp]),
     "ofx_timer_start": (_i, [_vp]),
     "ofx_timer_stop": (_i, [_vp, C.POINTER(C.c_float)]),
     "ofx_event_record": (_i, [_vp, C.c_int32]),

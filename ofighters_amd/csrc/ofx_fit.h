@@ -77,4 +77,5 @@ int ofx_fit_out_bw(hipStream_t st, int n, const ofx_fit_src &src, const float *d
 size_t ofx_fit_point_doubles(int n);
 int ofx_fit_top_point(hipStream_t st, int n, const ofx_transition *rows, const ofx_fit_src &src, const float *w, const float *b,
                       const float *o1, const float *y_act, const float *y_ptr, const float *stat, float *o2p, float *do1,
-                      float *d2p, float *lpart, float *gpatch, double *scratch, double *sums, float *dw, float *db);
+                      float *d2p, float *lpart, float *gpatch, double *scratch, double *sums, float *dw, float *db,
+                      const float *row_weight = nullptr, float *td_out = nullptr);

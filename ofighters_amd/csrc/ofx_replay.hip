@@ -12,6 +12,7 @@
 //   per ship [N][M]                  previous_obs / previous_action / previous_pointer (+ the toVector head) and the
 //                                    agent's `done` latch
 #include "ofx_internal.h"
+#include <float.h>
 #include <string.h>
 
 struct ofx_replay {
@@ -29,6 +30,10 @@ struct ofx_replay {
   int32_t *prev_iaction, *prev_px, *prev_py, *prev_tick, *prev_slot;
   float *prev_head;        // [N][M][8]
   int32_t *scan_off;       // [N + 1] prefix sums of ofx_replay_gather_valid (kept: no allocation per replay)
+  // prioritized replay (ofx_replay_prioritize), null = off
+  float *mass;             // [N][C] p^alpha, same ring positions as rows
+  float *mmax;             // [N] running maximum mass: what a new row gets
+  float alpha, eps;
 };
 
 void ofx_replay_free(ofx_handle *h) {
@@ -36,7 +41,7 @@ void ofx_replay_free(ofx_handle *h) {
   if (!r) return;
   void *ptrs[] = {r->frame_bits, r->frame_tick, r->rows, r->head, r->count, r->appended, r->has_prev, r->latched,
                   r->prev_iaction, r->prev_px, r->prev_py, r->prev_tick, r->prev_head, r->frame_head, r->cur_slot,
-                  r->prev_slot, r->scan_off};
+                  r->prev_slot, r->scan_off, r->mass, r->mmax};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   delete r;
   h->replay = nullptr;
@@ -175,6 +180,7 @@ __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
 #pragma unroll
     for (int k = 0; k < 8; k++) { row.head_prev[k] = p.r.prev_head[(size_t)t * 8 + k]; row.head_next[k] = hd[k]; }
     p.r.rows[(size_t)a * p.C + (head + pos) % p.C] = row;
+    if (p.r.mass) p.r.mass[(size_t)a * p.C + (head + pos) % p.C] = p.r.mmax[a];  // PER: a new row gets the running max
   }
   if (plays) {
     if (done) p.r.latched[t] = 1;
@@ -484,5 +490,257 @@ extern "C" int ofx_replay_gather_valid(ofx_handle *h, const int32_t *slot, const
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) { ofx_set_error("ofx_replay_gather_valid: %s", hipGetErrorString(e)); return OFX_ERR_HIP; }
   *n_rows_host = total - first < 0 ? 0 : (total - first > max_rows ? max_rows : total - first);
+  return OFX_OK;
+}
+
+// ---- prioritized experience replay (Schaul et al. 2016, proportional variant; include/ofx.h states the contract) ------
+// mass[a][ring position] = p^alpha beside every row; sampling is stratified proportional over the arena's eligible rows,
+// with a summation order fixed so that a CPU restatement (tests/per_oracle.py) picks the same slots: float64 sums, 64
+// chunks of ceil(valid / 64) consecutive rows each summed in row order, chunk totals chained in chunk order.
+#define OFX_STREAM_PER 4u
+__global__ void k_fill_f32(size_t count, float v, float *out) {
+  const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i < count) out[i] = v;
+}
+
+extern "C" int ofx_replay_prioritize(ofx_handle *h, float alpha, float eps) {
+  if (!h) { ofx_set_error("ofx_replay_prioritize: null handle"); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  if (!r) { ofx_set_error("ofx_replay_prioritize before ofx_replay_create"); return OFX_ERR_STATE; }
+  if (!(alpha >= 0.f && alpha <= FLT_MAX) || !(eps > 0.f && eps <= FLT_MAX)) {  // (NaN fails both)
+    ofx_set_error("ofx_replay_prioritize: alpha must be >= 0 and eps > 0, got %g, %g", (double)alpha, (double)eps);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  const size_t N = h->cfg.n_arenas, NC = N * (size_t)r->capacity;
+  if (!r->mass) {
+    OFX_HIP(hipMalloc((void **)&r->mass, sizeof(float) * NC));
+    OFX_HIP(hipMalloc((void **)&r->mmax, sizeof(float) * N));
+  }
+  r->alpha = alpha;
+  r->eps = eps;
+  // every row already in the memory, and every new one until the first update, has mass 1
+  hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, h->stream, NC, 1.f, r->mass);
+  hipLaunchKernelGGL(k_fill_f32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, N, 1.f, r->mmax);
+  OFX_HIP(hipGetLastError());
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  return OFX_OK;
+}
+
+static int per_ready(ofx_handle *h, const char *who) {
+  if (!h || !h->replay) { ofx_set_error("%s: no replay memory", who); return OFX_ERR_STATE; }
+  if (!h->replay->mass) { ofx_set_error("%s: prioritized replay is off (ofx_replay_prioritize)", who); return OFX_ERR_STATE; }
+  return OFX_OK;
+}
+
+struct PerSampleParams {
+  int N, C, F, batch, arena_base;
+  uint32_t k0, k1, draw;
+  double beta;
+  ofx_replay r;
+  int32_t *slot, *n_out;
+  float *is_weight;
+};
+
+// One 64-lane wave per arena.  Lane L sums chunk L; every lane then runs the same sequential chain over the 64 chunk
+// totals and keeps its own inclusive prefix.  Draw j belongs to lane j % 64: binary search for the first chunk whose
+// inclusive prefix exceeds u (the prefixes are monotone), then a sequential walk inside it that rebuilds the chunk's
+// running sum - prefix(row) = excl(chunk) + running sum, which reaches the chunk's inclusive prefix exactly at its last row.
+__global__ __launch_bounds__(256) void k_replay_sample_per(PerSampleParams p) {
+  const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (a >= p.N) return;  // wave-uniform
+  const int C = p.C;
+  const int count = p.r.count[a], head = p.r.head[a];
+  const int first = ((head - count) % C + C) % C;
+  const ofx_transition *rows = p.r.rows + (size_t)a * C;
+  int skip = 0;  // the same eligibility as k_replay_sample: the oldest rows whose `state` frame has left the ring
+  while (skip < count) {
+    const ofx_transition &o = rows[(first + skip) % C];
+    if (p.r.frame_tick[(size_t)a * p.F + o.frame_prev] == o.tick_prev) break;
+    skip++;
+  }
+  const int valid = count - skip, n = min(p.batch, valid);
+  const float *mass = p.r.mass + (size_t)a * C;
+  const int base = first + skip;  // eligible row i sits at ring position (base + i) % C
+  const int cs = (valid + 63) / 64, nchunks = cs ? (valid + cs - 1) / cs : 0;
+  const int lo = min(lane * cs, valid), hi = min(lo + cs, valid);
+  double t = 0.0;
+  for (int i = lo; i < hi; i++) t += (double)mass[(base + i) % C];
+  double total = 0.0, incl = 0.0;
+  for (int k = 0; k < 64; k++) {
+    total += __shfl(t, k);
+    if (k == lane) incl = total;
+  }
+  int32_t *out = p.slot + (size_t)a * p.batch;
+  float *wout = p.is_weight + (size_t)a * p.batch;
+  for (int j0 = 0; j0 < n; j0 += 64) {  // wave-uniform trip count: the shuffles below see every lane
+    const int j = j0 + lane;
+    double u = 0.0;
+    if (j < n) {
+      uint32_t rr[4];
+      ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)j, p.draw, OFX_STREAM_PER, p.k0, p.k1, rr);
+      const double U = (double)rr[0] * 0x1p-32;
+      u = ((double)j + U) / n * total;
+    }
+    int klo = 0, khi = nchunks;  // first chunk with incl > u lies in [klo, khi]; khi == nchunks: none
+    for (int it = 0; it < 7; it++) {
+      const int mid = (klo + khi) >> 1;
+      const double v = __shfl(incl, min(mid, 63));
+      if (klo < khi) {
+        if (v > u) khi = mid;
+        else klo = mid + 1;
+      }
+    }
+    double ex = __shfl(incl, max(klo - 1, 0));
+    if (klo == 0) ex = 0.0;
+    if (j < n) {
+      int pick = valid - 1;  // rounding left no row above u: the last eligible row
+      if (klo < nchunks) {
+        const int r0 = klo * cs, r1 = min(r0 + cs, valid);
+        double run = 0.0;
+        pick = r1 - 1;
+        for (int i = r0; i < r1; i++) {
+          run += (double)mass[(base + i) % C];
+          if (ex + run > u) { pick = i; break; }
+        }
+      }
+      const double m = (double)mass[(base + pick) % C];
+      out[j] = skip + pick;
+      wout[j] = total > 0.0 ? (float)pow((double)valid * m / total, -p.beta) : 1.f;
+    }
+  }
+  for (int j = n + lane; j < p.batch; j += 64) { out[j] = -1; wout[j] = 0.f; }
+  if (p.n_out && lane == 0) p.n_out[a] = n;
+}
+
+extern "C" int ofx_replay_sample_prioritized(ofx_handle *h, uint64_t seed, uint32_t draw, int32_t batch, double beta,
+                                             int32_t *slot, int32_t *n_sampled, float *is_weight) {
+  int rc;
+  if ((rc = per_ready(h, "ofx_replay_sample_prioritized"))) return rc;
+  if (!slot || !is_weight || batch <= 0 || !(beta >= -DBL_MAX && beta <= DBL_MAX)) {
+    ofx_set_error("ofx_replay_sample_prioritized: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  PerSampleParams p;
+  p.N = h->cfg.n_arenas; p.C = h->replay->capacity; p.F = h->replay->frames; p.batch = batch;
+  p.arena_base = h->cfg.arena_base; p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.draw = draw; p.beta = beta;
+  p.r = *h->replay; p.slot = slot; p.n_out = n_sampled; p.is_weight = is_weight;
+  hipLaunchKernelGGL(k_replay_sample_per, dim3((unsigned)((p.N + 3) / 4)), dim3(256), 0, h->stream, p);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// packed entry d = off[a] + j - first of the window (ofx_replay_gather_valid's order) <- is_weight[a][j]
+__global__ __launch_bounds__(256) void k_replay_window_pack(int N, int batch, const float *is_weight, const int32_t *n_sampled,
+                                                            const int32_t *off, int first, int max_rows, float *out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= N * batch) return;
+  const int a = t / batch, j = t - a * batch;
+  if (j >= n_sampled[a]) return;
+  const int d = off[a] + j - first;
+  if (d < 0 || d >= max_rows) return;
+  out[d] = is_weight[t];
+}
+// the window's weights over their maximum (the max is exact in any order)
+__global__ __launch_bounds__(1024) void k_replay_window_norm(int N, const int32_t *off, int first, int max_rows, float *out) {
+  __shared__ float red[1024];
+  const int tid = threadIdx.x, n = min(max(off[N] - first, 0), max_rows);
+  float m = 0.f;
+  for (int d = tid; d < n; d += 1024) m = fmaxf(m, out[d]);
+  red[tid] = m;
+  __syncthreads();
+  for (int k = 512; k > 0; k >>= 1) {
+    if (tid < k) red[tid] = fmaxf(red[tid], red[tid + k]);
+    __syncthreads();
+  }
+  const float mx = red[0];
+  if (mx > 0.f)
+    for (int d = tid; d < n; d += 1024) out[d] = out[d] / mx;
+}
+
+extern "C" int ofx_replay_window_weights(ofx_handle *h, const float *is_weight, const int32_t *n_sampled, int32_t batch,
+                                         int32_t first, int32_t max_rows, float *out) {
+  int rc;
+  if ((rc = per_ready(h, "ofx_replay_window_weights"))) return rc;
+  if (!is_weight || !n_sampled || !out || batch <= 0 || first < 0 || max_rows <= 0) {
+    ofx_set_error("ofx_replay_window_weights: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const int N = h->cfg.n_arenas;
+  int32_t *off = h->replay->scan_off;
+  hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
+  hipLaunchKernelGGL(k_replay_window_pack, dim3((unsigned)((N * batch + 255) / 256)), dim3(256), 0, h->stream, N, batch,
+                     is_weight, n_sampled, (const int32_t *)off, first, max_rows, out);
+  hipLaunchKernelGGL(k_replay_window_norm, dim3(1), dim3(1024), 0, h->stream, N, (const int32_t *)off, first, max_rows, out);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// one thread per arena, j in order: a duplicate row takes the later packed position's priority
+__global__ void k_replay_update_per(int N, int C, int batch, const int32_t *slot, const int32_t *n_sampled, const int32_t *off,
+                                    int first, int n_rows, const ofx_transition *rows, const float *td, ofx_replay r) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= N) return;
+  const int count = r.count[a], head = r.head[a];
+  const int first_row = ((head - count) % C + C) % C;
+  const int j0 = max(0, first - off[a]), j1 = min(n_sampled[a], first + n_rows - off[a]);
+  float mx = r.mmax[a];
+  for (int j = j0; j < j1; j++) {
+    const int d = off[a] + j - first;
+    const int s = slot[(size_t)a * batch + j];
+    if (s < 0 || s >= count) continue;
+    const size_t pos = (size_t)a * C + (first_row + s) % C;
+    const ofx_transition &g = rows[d];
+    if (r.rows[pos].tick_prev != g.tick_prev || r.rows[pos].ship != g.ship) continue;  // overwritten since sampling
+    const float e1 = td[2 * (size_t)d], e2 = td[2 * (size_t)d + 1];
+    if (!isfinite(e1) || !isfinite(e2)) continue;
+    const float m = powf(fabsf(e1) + fabsf(e2) + r.eps, r.alpha);
+    r.mass[pos] = m;
+    mx = fmaxf(mx, m);
+  }
+  r.mmax[a] = mx;
+}
+
+extern "C" int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, const int32_t *n_sampled, int32_t batch,
+                                            int32_t first, int32_t n_rows, const ofx_transition *rows, const float *td) {
+  int rc;
+  if ((rc = per_ready(h, "ofx_replay_update_priorities"))) return rc;
+  if (!slot || !n_sampled || !rows || !td || batch <= 0 || first < 0 || n_rows < 0) {
+    ofx_set_error("ofx_replay_update_priorities: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  if (n_rows == 0) return OFX_OK;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const int N = h->cfg.n_arenas;
+  int32_t *off = h->replay->scan_off;  // recomputed here: never the offsets an earlier call left behind
+  hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
+  hipLaunchKernelGGL(k_replay_update_per, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, h->replay->capacity, batch, slot,
+                     n_sampled, (const int32_t *)off, first, n_rows, rows, td, *h->replay);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// masses of one arena, oldest first (the order of ofx_replay_rows_host)
+extern "C" int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *mass_host, int32_t *n_host) {
+  int rc;
+  if ((rc = per_ready(h, "ofx_replay_priorities_host"))) return rc;
+  if (!mass_host || !n_host) { ofx_set_error("ofx_replay_priorities_host: bad argument"); return OFX_ERR_INVALID; }
+  if (arena < 0 || arena >= h->cfg.n_arenas) { ofx_set_error("ofx_replay_priorities_host: arena out of range"); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  int32_t head, count;
+  OFX_HIP(hipMemcpy(&head, r->head + arena, 4, hipMemcpyDeviceToHost));
+  OFX_HIP(hipMemcpy(&count, r->count + arena, 4, hipMemcpyDeviceToHost));
+  const int C = r->capacity;
+  const int first = ((head - count) % C + C) % C;
+  const float *base = r->mass + (size_t)arena * C;
+  const int n1 = min(count, C - first);
+  if (n1 > 0) OFX_HIP(hipMemcpy(mass_host, base + first, sizeof(float) * n1, hipMemcpyDeviceToHost));
+  if (count > n1) OFX_HIP(hipMemcpy(mass_host + n1, base, sizeof(float) * (count - n1), hipMemcpyDeviceToHost));
+  *n_host = count;
   return OFX_OK;
 }

@@ -437,9 +437,10 @@ __global__ void t_concat_bwd(int n, const float *df, float *dx4) {
   }
 }
 
-// loss seeds: one non-zero error per head and sample; loss[0] += mse(out1) share, loss[1] += mse(out2) share
+// loss seeds: one non-zero error per head and sample; loss[0] += mse(out1) share, loss[1] += mse(out2) share.
+// rw (may be null = 1): per-row loss weights, the first factor of every term; td (may be null): the errors (e1, e2)
 __global__ void t_loss_seed(int n, const ofx_transition *rows, const float *o1, const float *o2, const float *y_act,
-                            const float *y_ptr, float *do1, float *do2, float *lpart) {
+                            const float *y_ptr, float *do1, float *do2, float *lpart, const float *rw, float *td) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const ofx_transition r = rows[s];
@@ -448,10 +449,12 @@ __global__ void t_loss_seed(int n, const ofx_transition *rows, const float *o1, 
   const float e1 = o1[2 * s + a] - y_act[s];
   const size_t k = (size_t)s * TPS * TPS + (size_t)py * TPS + px;
   const float e2 = o2[k] - y_ptr[s];
-  do1[2 * s + a] = 2.f * e1 / (2.f * n);
-  do2[k] = 2.f * e2 / ((float)(TPS * TPS) * n);
-  lpart[2 * s] = e1 * e1 / (2.f * n);          // summed in sample order by t_sum_ordered
-  lpart[2 * s + 1] = e2 * e2 / ((float)(TPS * TPS) * n);
+  const float w = rw ? rw[s] : 1.f;
+  do1[2 * s + a] = w * 2.f * e1 / (2.f * n);
+  do2[k] = w * 2.f * e2 / ((float)(TPS * TPS) * n);
+  lpart[2 * s] = w * e1 * e1 / (2.f * n);      // summed in sample order by t_sum_ordered
+  lpart[2 * s + 1] = w * e2 * e2 / ((float)(TPS * TPS) * n);
+  if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
 }
 // out[j] = sum_i part[i * stride + j] for j < stride, in index order (one thread per j: tiny)
 __global__ void t_sum_ordered(int count, int stride, const float *part, float *out) {
@@ -622,7 +625,8 @@ static int refuse_pads(ofx_handle *h, int n, const ofx_transition *rows, const c
 // z of every convolution in HBM.  The dense layers, the loss and Adam are the plain form's kernels.
 static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                         const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
-                        const float *t1, const float *t2, float *grad_out, float *loss_host) {
+                        const float *t1, const float *t2, float *grad_out, float *loss_host, const float *row_weight,
+                        float *td_out) {
   const bool dense = t1 != nullptr;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
@@ -710,7 +714,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
     // layer's g from that one pixel (ofx_fit.hip, "the top of head 2 for the textbook targets")
     float *o2p = o2, *d2p = o2 + N;                          // [n] each: the dense planes are not used on this path
     if ((rc = ofx_fit_top_point(st, n, rows, head_src(3), T(50), T(51), o1, y_act, y_ptr, ustat[2], o2p, do1, d2p, lpart, gpatch,
-                                pscratch, sums, G(50), G(51)))) return rc;
+                                pscratch, sums, G(50), G(51), row_weight, td_out))) return rc;
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
     OFX_HIP(hipGetLastError());
   } else if (dense) {
@@ -797,11 +801,14 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
 // One fit step.  Two forms of the targets: the sparse one of ofx_dqn_fit (one error per head and sample: y_act / y_ptr,
 // inputs = `state`) and the dense one of ofx_dqn_fit_reference (t1 [n][2] / t2 [n][400][400] whole target tensors,
 // inputs = bits_in + the rows' next_state head).
+// row_weight / td_out (sparse form only, either may be null): per-row loss weights and the rows' errors (ofx_dqn_fit_weighted).
 static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                         const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
-                        const float *t1, const float *t2, float *grad_out, float *loss_host) {
+                        const float *t1, const float *t2, float *grad_out, float *loss_host,
+                        const float *row_weight = nullptr, float *td_out = nullptr) {
   if (!h->opt_fit_plain)
-    return dqn_fit_lean(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, t1, t2, grad_out, loss_host);
+    return dqn_fit_lean(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, t1, t2, grad_out, loss_host,
+                        row_weight, td_out);
   const bool dense = t1 != nullptr;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
@@ -893,7 +900,7 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
       OFX_HIP(hipGetLastError());
     }
   } else {
-    K(t_loss_seed, N, n, rows, o1, o2, y_act, y_ptr, do1, do2, lpart);
+    K(t_loss_seed, N, n, rows, o1, o2, y_act, y_ptr, do1, do2, lpart, row_weight, td_out);
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
   }
 
@@ -992,6 +999,20 @@ extern "C" int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *
   }
   return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
                       loss_host);
+}
+
+// ofx_dqn_fit with Keras sample_weight semantics (prioritized replay's importance-sampling weights): the loss is
+// sum w e1^2 / (2 n) + sum w e2^2 / (160000 n); row_weight null = ofx_dqn_fit bit for bit (so is a weight of 1.0).
+extern "C" int ofx_dqn_fit_weighted(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr,
+                                    int32_t n, const ofx_transition *rows, const void *bits_prev, const float *y_act,
+                                    const float *y_ptr, float *grad_out, float *loss_host, const float *row_weight,
+                                    float *td_out) {
+  if (!h || !weights || !adam_m || !adam_v || !rows || !bits_prev || !y_act || !y_ptr || n < 1 || step < 1) {
+    ofx_set_error("ofx_dqn_fit_weighted: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
+                      loss_host, row_weight, td_out);
 }
 
 // Trainer.replay's loop body and fit exactly as written (agents/qlearnIA_V2.py:251-285), quirks included:

@@ -493,6 +493,41 @@ class ArenaBatch:
                                                      rows.ptr, bits_prev.ptr, bits_next.ptr, C.byref(n)))
         return n.value
 
+    # ------------------------------------------------------------ prioritized replay (include/ofx.h: the contract)
+    def replay_prioritize(self, alpha=0.6, eps=1e-3):
+        """Enable prioritized experience replay on the memory: masses p^alpha per row, new rows at the running max."""
+        nat.check(nat.lib().ofx_replay_prioritize(self._h, float(alpha), float(eps)))
+
+    def replay_sample_prioritized(self, seed, draw, batch, beta, slot=None, n=None, is_weight=None):
+        """Stratified proportional sample per arena -> (slot [N][batch], n [N], is_weight [N][batch]) DeviceBuffers;
+        slot / n as replay_sample, is_weight the raw importance-sampling weights."""
+        if slot is None:
+            slot = DeviceBuffer(4 * self.N * batch)
+        if n is None:
+            n = DeviceBuffer(4 * self.N)
+        if is_weight is None:
+            is_weight = DeviceBuffer(4 * self.N * batch)
+        nat.check(nat.lib().ofx_replay_sample_prioritized(self._h, seed, int(draw), int(batch), float(beta), slot.ptr, n.ptr,
+                                                           is_weight.ptr))
+        return slot, n, is_weight
+
+    def replay_window_weights_into(self, is_weight, n_sampled, batch, first, max_rows, out):
+        """The IS weights of replay_gather_valid's window (same arguments), packed and max-normalised into `out`."""
+        nat.check(nat.lib().ofx_replay_window_weights(self._h, is_weight.ptr, n_sampled.ptr, int(batch), int(first),
+                                                       int(max_rows), out.ptr))
+
+    def replay_update_priorities(self, slot, n_sampled, batch, first, n_rows, rows_ptr, td_ptr):
+        """Priority write-back for the n_rows gathered rows of that window from td [n_rows][2] = (e1, e2)."""
+        nat.check(nat.lib().ofx_replay_update_priorities(self._h, slot.ptr, n_sampled.ptr, int(batch), int(first),
+                                                          int(n_rows), rows_ptr, td_ptr))
+
+    def replay_priorities(self, arena):
+        """Masses (p^alpha) of one arena's rows, oldest first (the order of replay_rows)."""
+        m = np.zeros(self.replay_capacity, np.float32)
+        n = C.c_int32()
+        nat.check(nat.lib().ofx_replay_priorities_host(self._h, int(arena), m.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return m[:n.value]
+
     def policy_forward_obs(self, weights_ptr, n_obs, bits_ptr, vec8_ptr, want_probe_ptr=None):
         """Forward on stored observations (Trainer.replay's predictions): host dict of act / iaction / ipointer /
         ptr_max (+ ptr_probe when want_probe_ptr, an int32 [n_obs][2] device array of (x, y), is given)."""
@@ -526,6 +561,16 @@ class ArenaBatch:
         nat.check(nat.lib().ofx_dqn_fit(self._h, weights_buf.ptr, adam_m_buf.ptr, adam_v_buf.ptr, int(step), float(lr),
                                          int(n), rows_ptr, bits_prev_ptr, y_act_ptr, y_ptr_ptr,
                                          grad_buf.ptr if grad_buf else None, loss))
+        return float(loss[0]), float(loss[1])
+
+    def dqn_fit_weighted(self, weights_buf, adam_m_buf, adam_v_buf, step, lr, n, rows_ptr, bits_prev_ptr, y_act_ptr,
+                         y_ptr_ptr, row_weight_ptr=None, td_ptr=None, grad_buf=None):
+        """dqn_fit with per-row loss weights (Keras sample_weight) and the rows' (e1, e2) into td_ptr [n][2]; either may
+        be None (no weights == dqn_fit).  Returns (loss1, loss2)."""
+        loss = (C.c_float * 2)()
+        nat.check(nat.lib().ofx_dqn_fit_weighted(self._h, weights_buf.ptr, adam_m_buf.ptr, adam_v_buf.ptr, int(step),
+                                                  float(lr), int(n), rows_ptr, bits_prev_ptr, y_act_ptr, y_ptr_ptr,
+                                                  grad_buf.ptr if grad_buf else None, loss, row_weight_ptr, td_ptr))
         return float(loss[0]), float(loss[1])
 
     def dqn_fit_reference(self, weights_buf, adam_m_buf, adam_v_buf, step, lr, n, rows_ptr, bits_prev_ptr, bits_next_ptr,

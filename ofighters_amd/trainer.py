@@ -3,7 +3,12 @@ for an ArenaBatch: weights, Adam state and the replay memory live in HBM; `get_b
 ArenaBatch.policy_forward + policy_explore, `remember` is ArenaBatch.replay_capture, and `replay(batch_size)`
 (:240-285) is sample -> gather -> targets -> one fit step, all through the C-ABI (ofx_replay_sample, ofx_replay_gather,
 ofx_dqn_targets, ofx_dqn_fit - or ofx_dqn_fit_reference with `reference_quirks=True`: the reference's step as written,
-ptr_target[x][y] and the fit on next_state's inputs included, :280-283)."""
+ptr_target[x][y] and the fit on next_state's inputs included, :280-283).
+
+`prioritized=True` (opt-in, not in the reference) turns on proportional prioritized experience replay (Schaul et al.
+2016): ofx_replay_sample_prioritized draws the minibatch by priority, ofx_dqn_fit_weighted takes the window's
+importance-sampling weights (beta annealed linearly from per_beta to 1 over per_beta_steps fit steps) and returns the
+rows' TD errors, which ofx_replay_update_priorities writes back."""
 import numpy as np
 
 from .engine import DeviceBuffer
@@ -12,7 +17,10 @@ from .lib.epsilon import Epsilon_cos
 
 class DeviceTrainer:
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
-                 seed=0x0F160003, fit_batch=256, reference_quirks=False):
+                 seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
+                 per_beta_steps=50_000, per_eps=1e-3):
+        if prioritized and reference_quirks:
+            raise ValueError("DeviceTrainer: prioritized replay needs the textbook fit (reference_quirks=False)")
         self.batch = batch                                  # the ArenaBatch this trainer plays and learns on
         w = np.ascontiguousarray(weights, np.float32)
         self.n_floats = w.size
@@ -29,11 +37,15 @@ class DeviceTrainer:
                                                             # replay takes 3.6 ms at 64 rows, 5.8 at 256 - about one
                                                             # lock-step of a 4096-arena batch -, 42 ms at 4096
         self.reference_quirks = bool(reference_quirks)      # Trainer.replay as written instead of the textbook DQN step
+        self.prioritized = bool(prioritized)                # PER: priority exponent alpha, IS exponent beta -> 1, eps
+        self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = per_alpha, per_beta, per_beta_steps, per_eps
         self.fit_steps = 0
         self.draws = 0
         self.losses = []
         self._buf = {}                                       # replay scratch kept between calls (grow-only)
         batch.replay_create(memory_size, frames)
+        if self.prioritized:
+            batch.replay_prioritize(per_alpha, per_eps)
 
     def _scratch(self, name, nbytes):
         """A device buffer of at least nbytes that lives as long as the trainer: no hipMalloc / hipFree per replay."""
@@ -74,6 +86,8 @@ class DeviceTrainer:
         cnt, _ = b.replay_count()
         if int(cnt.max()) == 0:
             return None
+        if self.prioritized:
+            return self._replay_prioritized(bs)
         slot, n_s = b.replay_sample(self.seed, self.draws, bs, self._scratch("slot", 4 * b.N * bs), self._scratch("n_s", 4 * b.N))
         self.draws += 1
         # the sampled transitions of all arenas, WITHOUT the -1 pads of arenas that hold fewer than bs (a pad would enter
@@ -108,5 +122,43 @@ class DeviceTrainer:
         self.fit_steps += 1
         loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
                          y_act.ptr, y_ptr.ptr)
+        self.losses.append(loss)
+        return loss
+
+    def beta(self):
+        """The IS exponent of the next fit step: per_beta -> 1.0 linearly over per_beta_steps fit steps."""
+        f = min(1.0, self.fit_steps / float(self.per_beta_steps)) if self.per_beta_steps > 0 else 1.0
+        return self.per_beta + (1.0 - self.per_beta) * f
+
+    def _replay_prioritized(self, bs):
+        """replay() under PER: the same moving window of the sampled rows as the uniform path, weighted by the window's
+        max-normalised IS weights; the fit's pre-update errors become the rows' new priorities."""
+        b = self.batch
+        N = b.N
+        slot, n_s, isw = b.replay_sample_prioritized(self.seed, self.draws, bs, self.beta(), self._scratch("slot", 4 * N * bs),
+                                                     self._scratch("n_s", 4 * N), self._scratch("is_w", 4 * N * bs))
+        self.draws += 1
+        b.sync()
+        n_valid = int(n_s.download(np.int32, (N,)).sum())
+        if n_valid == 0:
+            return None
+        n = min(n_valid, int(self.fit_batch))
+        start = ((self.draws - 1) * n) % (n_valid - n + 1)
+        words = b.W * b.H // 32
+        rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
+        bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
+        got = b.replay_gather_valid_into(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
+        if got != n:
+            raise Exception("DeviceTrainer.replay: gathered %d of %d rows" % (got, n))
+        row_w, td = self._scratch("row_w", 4 * n), self._scratch("td", 8 * n)
+        b.replay_window_weights_into(isw, n_s, bs, start, n, row_w)
+        y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
+        from . import _native as nat
+        nat.check(nat.lib().ofx_dqn_targets(b.handle, self.weights.ptr, n, rows.ptr, bits_prev.ptr, bits_next.ptr,
+                                             float(self.gamma), None, None, y_act.ptr, y_ptr.ptr))
+        self.fit_steps += 1
+        loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows.ptr,
+                                  bits_prev.ptr, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
+        b.replay_update_priorities(slot, n_s, bs, start, n, rows.ptr, td.ptr)
         self.losses.append(loss)
         return loss

@@ -1,0 +1,486 @@
+"""Prioritized experience replay (include/ofx.h, "prioritized experience replay"): the CPU restatement's properties, and
+on the GPU the sampler, the priority write-back, the weighted fit and the trainer against it."""
+import ctypes as C
+
+import numpy as np
+import pytest
+from scipy import stats
+
+from tests import per_oracle
+
+PER_SYMBOLS = ["ofx_replay_prioritize", "ofx_replay_sample_prioritized", "ofx_replay_window_weights",
+               "ofx_replay_update_priorities", "ofx_replay_priorities_host", "ofx_dqn_fit_weighted"]
+
+
+# ------------------------------------------------------------------------------------------------------ CPU
+def test_per_symbols_exported_declared_and_bound():
+    from ofighters_amd import _native as nat
+    from tests.test_abi import header_symbols
+    L = C.CDLL(nat.LIB_PATH)
+    declared = header_symbols()
+    for s in PER_SYMBOLS:
+        assert s in declared and s in nat.SIGNATURES and hasattr(L, s), s
+
+
+def _draw_counts(mass, batch, draws, seed=0x0F160005, arena=3):
+    counts = np.zeros(len(mass), np.int64)
+    for d in range(draws):
+        picks, _ = per_oracle.sample(mass, batch, 0.4, seed, arena, d)
+        np.add.at(counts, picks, 1)
+    return counts
+
+
+def test_restatement_frequencies_follow_the_masses():
+    rs = np.random.RandomState(11)
+    mass = (10.0 ** rs.uniform(-1, 1, 40)).astype(np.float32)
+    counts = _draw_counts(mass, 8, 2500)                     # 20 000 draws
+    assert counts.sum() == 20000
+    expect = 20000 * mass.astype(np.float64) / mass.astype(np.float64).sum()
+    assert stats.chisquare(counts, expect).pvalue > 1e-3
+
+
+def test_restatement_alpha_zero_is_uniform_with_unit_weights():
+    mass = np.ones(30, np.float32)                           # alpha = 0: every mass is p^0 = 1
+    counts = _draw_counts(mass, 8, 2500)
+    assert stats.chisquare(counts, np.full(30, 20000 / 30)).pvalue > 1e-3
+    for d in range(50):
+        _, w = per_oracle.sample(mass, 8, 0.7, 5, 1, d)
+        assert (w == 1.0).all()
+    picks, w = per_oracle.sample(mass, 30, 0.7, 5, 1, 0)    # one draw per stratum of equal rows: each row once
+    assert sorted(picks) == list(range(30)) and (w == 1.0).all()
+
+
+def test_restatement_each_stratum_lands_in_its_own_segment():
+    rs = np.random.RandomState(5)
+    for valid in (1, 7, 63, 64, 65, 200, 400):
+        mass = (10.0 ** rs.uniform(-3, 3, valid)).astype(np.float32)
+        incl = per_oracle.row_prefixes(mass)
+        total = per_oracle.prefix_chain(mass)[1]
+        for batch in (1, 8, 32):
+            for d in range(5):
+                picks, _ = per_oracle.sample(mass, batch, 0.4, 9, valid, d)
+                n = len(picks)
+                assert n == min(batch, valid)
+                for j, i in enumerate(picks):
+                    lo = incl[i - 1] if i else 0.0
+                    # the row's mass segment [lo, incl[i]) meets the stratum [j, j + 1) * total / n
+                    assert lo <= (j + 1) / n * total and incl[i] > j / n * total, (valid, batch, j, i)
+
+
+def test_restatement_never_draws_expired_rows():
+    rs = np.random.RandomState(2)
+    for skip in (0, 1, 5, 12):
+        mass = (10.0 ** rs.uniform(-2, 2, 20)).astype(np.float32)
+        for d in range(200):
+            slot, n, iw = per_oracle.sample_arena(mass, skip, 8, 0.5, 77, 4, d)
+            assert n == min(8, 20 - skip)
+            assert (slot[:n] >= skip).all() and (slot[n:] == -1).all() and (iw[n:] == 0).all()
+    slot, n, _ = per_oracle.sample_arena(np.ones(3, np.float32), 3, 8, 0.5, 77, 4, 0)
+    assert n == 0 and (slot == -1).all()
+
+
+# ------------------------------------------------------------------------------------------------------ GPU
+def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_base=0, prioritize=True, alpha=0.6,
+             masks=None):
+    """A seeded collecting rollout with capture; masks(t) -> uint8 [N_global][M] of the capturing ships at tick t."""
+    from ofighters_amd import ArenaBatch, DeviceBuffer
+    b = ArenaBatch(N, M, arena_base=arena_base)
+    b.replay_create(capacity, frames)
+    if prioritize:
+        b.replay_prioritize(alpha, 1e-3)
+    b.spawn_random(seed)
+    ia_d, ip_d = DeviceBuffer(4 * N * M), DeviceBuffer(8 * N * M)
+    mask_d = DeviceBuffer(N * M)
+    for t in range(ticks):
+        mk = np.ones((N, M), np.uint8) if masks is None else masks(t)[arena_base:arena_base + N]
+        b.sync()
+        mask_d.upload(np.ascontiguousarray(mk))
+        b.bot_actions(["random"] * M, seed, tick=t)
+        b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+        b.policy_actions(out_ptr=b._actions.ptr, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+        b.replay_capture(t, mask_d.ptr, ia_d.ptr, ip_d.ptr)
+        b.step(actions_ptr=b._actions.ptr)
+    b.sync()
+    return b
+
+
+def _varied_masks(NG, M):
+    """arena 0 never captures (0 rows), arena 1 captures at ticks 0-1 (1 row), arena 2 with one ship (11 rows at 12
+    ticks), arena 3 one ship at ticks 0-4 (4 rows), the others every ship."""
+    def masks(t):
+        mk = np.ones((NG, M), np.uint8)
+        mk[0] = 0
+        mk[1] = 0
+        mk[1, 0] = t < 2
+        mk[2] = 0
+        mk[2, 0] = 1
+        mk[3] = 0
+        mk[3, 0] = t < 5
+        return mk
+    return masks
+
+
+def _gather_rows(b, slot, n_s, batch, first, max_rows):
+    """gather_valid without the maps -> (rows DeviceBuffer, n_rows)."""
+    from ofighters_amd import DeviceBuffer, _native as nat
+    rows = DeviceBuffer(max(1, max_rows) * b.TRANSITION_DTYPE.itemsize)
+    n = C.c_int32()
+    nat.check(nat.lib().ofx_replay_gather_valid(b.handle, slot.ptr, n_s.ptr, int(batch), int(first), int(max_rows), rows.ptr,
+                                                 None, None, C.byref(n)))
+    return rows, n.value
+
+
+def _all_rows_window(b):
+    """slot / n_sampled naming every row of every arena (oldest first), and those rows gathered."""
+    from ofighters_amd import DeviceBuffer
+    cnt, _ = b.replay_count()
+    Cap = b.replay_capacity
+    slot = np.full((b.N, Cap), -1, np.int32)
+    for a in range(b.N):
+        slot[a, :cnt[a]] = np.arange(cnt[a])
+    slot_d, n_d = DeviceBuffer(slot.nbytes).upload(slot), DeviceBuffer(4 * b.N).upload(cnt.astype(np.int32))
+    total = int(cnt.sum())
+    rows, got = _gather_rows(b, slot_d, n_d, Cap, 0, total)
+    assert got == total
+    return slot_d, n_d, Cap, rows, total, cnt
+
+
+def _set_masses(b, td_fn):
+    """Hand-set masses: one write-back over every row with td = td_fn(rows) [n][2]."""
+    from ofighters_amd import DeviceBuffer
+    slot_d, n_d, Cap, rows, total, cnt = _all_rows_window(b)
+    b.sync()
+    r = rows.download(b.TRANSITION_DTYPE, (total,))
+    td = np.ascontiguousarray(td_fn(r), np.float32)
+    td_d = DeviceBuffer(td.nbytes).upload(td)
+    b.replay_update_priorities(slot_d, n_d, Cap, 0, total, rows.ptr, td_d.ptr)
+    b.sync()
+    return r, td
+
+
+def _skip(b, a):
+    """How many of the arena's oldest rows have lost their `state` frame (not eligible)."""
+    from ofighters_amd import OfxError
+    rows = b.replay_rows(a)
+    for k, r in enumerate(rows):
+        try:
+            b.replay_frame(a, int(r["tick_prev"]))
+            return k
+        except OfxError:
+            pass
+    return len(rows)
+
+
+def _device_sample(b, seed, draw, batch, beta):
+    slot, n, iw = b.replay_sample_prioritized(seed, draw, batch, beta)
+    b.sync()
+    return (slot.download(np.int32, (b.N, batch)), n.download(np.int32, (b.N,)), iw.download(np.float32, (b.N, batch)),
+            (slot, n, iw))
+
+
+def _check_sampler(b, batch, beta, seed, draws, arena_base=0):
+    masses = [b.replay_priorities(a) for a in range(b.N)]
+    skips = [_skip(b, a) for a in range(b.N)]
+    for d in draws:
+        slot, n, iw, _ = _device_sample(b, seed, d, batch, beta)
+        for a in range(b.N):
+            rs, rn, riw = per_oracle.sample_arena(masses[a], skips[a], batch, beta, seed, arena_base + a, d)
+            assert n[a] == rn and np.array_equal(slot[a], rs), (a, d, slot[a], rs)
+            np.testing.assert_allclose(iw[a], riw, rtol=1e-6, atol=0, err_msg="arena %d draw %d" % (a, d))
+    return skips
+
+
+@pytest.mark.gpu
+def test_capture_writes_the_running_max():
+    b = _rollout(16, ticks=8)
+    cnt, _ = b.replay_count()
+    assert cnt.min() > 0
+    for a in range(b.N):
+        assert (b.replay_priorities(a) == 1.0).all()
+    # a synthetic write-back raises mmax; the rows captured afterwards carry it
+    _, td = _set_masses(b, lambda r: np.stack([r["ship"] * 3.0 + 1.0, np.full(len(r), -2.0)], 1))
+    before = [b.replay_priorities(a) for a in range(b.N)]
+    mmax = max(per_oracle.new_mass(3.0 * 3 + 1.0, -2.0, 0.6, 1e-3), 1.0)
+    from ofighters_amd import DeviceBuffer
+    M = b.M
+    ia_d, ip_d = DeviceBuffer(4 * b.N * M), DeviceBuffer(8 * b.N * M)
+    b.bot_actions(["random"] * M, 1, tick=8)
+    b.policy_explore(1.0, 1, tick=8, collecting=True, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+    b.replay_capture(8, None, ia_d.ptr, ip_d.ptr)
+    b.sync()
+    cnt2, _ = b.replay_count()
+    for a in range(b.N):
+        m = b.replay_priorities(a)
+        assert np.array_equal(m[:cnt[a]], before[a])
+        assert (np.abs(m[cnt[a]:] - mmax) <= 2 * np.spacing(np.float32(mmax))).all()
+        assert (m[cnt[a]:] == before[a].max()).all()      # the arena's running max is the largest mass written
+    assert (cnt2 > cnt).sum() > b.N // 2
+    # enabling PER on a memory that holds rows gives them mass 1.0 again
+    b.replay_prioritize(0.5, 1e-2)
+    assert all((b.replay_priorities(a) == 1.0).all() for a in range(b.N))
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("frames,batch", [(0, 8), (0, 32), (4, 8), (4, 32)])
+def test_sampler_equals_restatement(frames, batch):
+    N, M = 64, 4
+    b = _rollout(N, M, capacity=40, frames=frames, masks=_varied_masks(N, M))
+    cnt, _ = b.replay_count()
+    assert cnt[0] == 0 and cnt[1] == 1 and 0 < cnt[3] <= 4 < cnt[2] <= 11 and (cnt == 40).sum() > 32   # rings wrapped
+    rs = np.random.RandomState(frames + batch)
+    spread = 10.0 ** rs.uniform(-3, 3, 400 * 64)
+    _set_masses(b, lambda r: np.stack([spread[:len(r)], np.zeros(len(r))], 1))
+    m4 = b.replay_priorities(4)
+    assert m4.max() / m4.min() > 1e2
+    skips = _check_sampler(b, batch, 0.4, 0x0F160021, range(3))
+    if frames:
+        assert max(skips) > 0, "no row expired"
+    b.close()
+
+
+@pytest.mark.gpu
+def test_sampler_slices_equal_one_batch():
+    N, M = 64, 4
+    masks = _varied_masks(N, M)
+    td = lambda r: np.stack([(r["tick_prev"] % 7) * 0.9 - 2.0, r["ship"] * 0.25], 1)
+    full = _rollout(N, M, masks=masks)
+    _set_masses(full, td)
+    fs, fn, fw, _ = _device_sample(full, 99, 1, 8, 0.6)
+    for base in (0, N // 2):
+        part = _rollout(N // 2, M, masks=masks, arena_base=base)
+        _set_masses(part, td)
+        ps, pn, pw, _ = _device_sample(part, 99, 1, 8, 0.6)
+        sl = slice(base, base + N // 2)
+        assert np.array_equal(ps, fs[sl]) and np.array_equal(pn, fn[sl]) and np.array_equal(pw, fw[sl])
+        _check_sampler(part, 8, 0.6, 99, [1], arena_base=base)
+        part.close()
+    full.close()
+
+
+@pytest.mark.gpu
+def test_window_weights_and_update():
+    from ofighters_amd import DeviceBuffer
+    N, M, batch, alpha, eps = 16, 4, 8, 0.6, 1e-3
+    b = _rollout(N, M, capacity=40, masks=_varied_masks(N, M))
+    rs = np.random.RandomState(4)
+    spread = 10.0 ** rs.uniform(-2, 2, 4000)
+    _set_masses(b, lambda r: np.stack([spread[:len(r)], np.zeros(len(r))], 1))
+    before = [b.replay_priorities(a).astype(np.float64) for a in range(N)]
+    slot_h, n_h, iw_h, (slot, n_s, iw) = _device_sample(b, 5, 0, batch, 0.4)
+    total = int(n_h.sum())
+    first, max_rows = 3, total - 5
+    rows, got = _gather_rows(b, slot, n_s, batch, first, max_rows)
+    assert got == max_rows
+    out = DeviceBuffer(4 * max_rows)
+    b.replay_window_weights_into(iw, n_s, batch, first, max_rows, out)
+    b.sync()
+    np.testing.assert_array_equal(out.download(np.float32, (max_rows,)),
+                                  per_oracle.window_weights(iw_h, n_h, first, max_rows))
+    td = rs.normal(0, 3, (max_rows, 2)).astype(np.float32)
+    td[7, 0], td[11, 1], td[12, 0] = np.nan, np.inf, -np.inf
+    td_d = DeviceBuffer(td.nbytes).upload(td)
+    b.replay_update_priorities(slot, n_s, batch, first, max_rows, rows.ptr, td_d.ptr)
+    b.sync()
+    # restatement: packed entry d is (arena, j); later entries of a duplicated row win; non-finite errors are skipped
+    want = [m.copy() for m in before]
+    written = [set() for _ in range(N)]
+    d = -first
+    dup = 0
+    for a in range(N):
+        for j in range(n_h[a]):
+            if 0 <= d < max_rows and np.isfinite(td[d]).all():
+                s = slot_h[a, j]
+                dup += s in written[a]
+                written[a].add(s)
+                want[a][s] = per_oracle.new_mass(td[d, 0], td[d, 1], alpha, eps)
+            d += 1
+    assert dup > 0, "no duplicate draw to test the last-write rule"
+    for a in range(N):
+        got_m = b.replay_priorities(a).astype(np.float64)
+        ulp = np.spacing(want[a].astype(np.float32)).astype(np.float64)
+        assert (np.abs(got_m - want[a]) <= 2 * ulp).all(), (a, got_m, want[a])
+        unchanged = [i for i in range(len(got_m)) if i not in written[a]]
+        assert np.array_equal(got_m[unchanged], before[a][unchanged])
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full", [False, True])
+def test_update_skips_rows_overwritten_since_sampling(full):
+    """full: the memory is full, so the captures between sample and update shift every slot (and overwrite the oldest
+    rows): no priority may land on another row.  not full: the slots still name the same rows, the update lands."""
+    from ofighters_amd import DeviceBuffer
+    N, M, batch = 8, 4, 8
+    Cap = 24 if full else 200
+    b = _rollout(N, M, capacity=Cap, ticks=8)
+    cnt0, app0 = b.replay_count()
+    slot_h, n_h, _, (slot, n_s, _) = _device_sample(b, 3, 0, batch, 0.4)
+    total = int(n_h.sum())
+    rows, got = _gather_rows(b, slot, n_s, batch, 0, total)
+    key = lambda r: (int(r["tick_prev"]), int(r["ship"]))
+    before = {a: dict(zip(map(key, b.replay_rows(a)), b.replay_priorities(a))) for a in range(N)}
+    ia_d, ip_d = DeviceBuffer(4 * N * M), DeviceBuffer(8 * N * M)
+    for t in (8, 9):                                        # two more lock-steps of capture
+        b.bot_actions(["random"] * M, 3, tick=t)
+        b.policy_explore(1.0, 3, tick=t, collecting=True, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+        b.replay_capture(t, None, ia_d.ptr, ip_d.ptr)
+        b.policy_actions(out_ptr=b._actions.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+        b.step(actions_ptr=b._actions.ptr)
+    b.sync()
+    cnt1, app1 = b.replay_count()
+    shifted = (cnt0 == Cap) & (app1 > app0)             # full memories that took new rows: every slot has moved
+    assert shifted.any() == full
+    td = np.full((total, 2), 50.0, np.float32)             # a mass no row had
+    b.replay_update_priorities(slot, n_s, batch, 0, total, rows.ptr, DeviceBuffer(td.nbytes).upload(td).ptr)
+    b.sync()
+    big = per_oracle.new_mass(50.0, 50.0, 0.6, 1e-3)
+    g = rows.download(b.TRANSITION_DTYPE, (total,))
+    sampled = [set() for _ in range(N)]
+    d = 0
+    for a in range(N):
+        for j in range(n_h[a]):
+            sampled[a].add(key(g[d]))
+            d += 1
+    landed = np.zeros(N, int)
+    for a in range(N):
+        for r, m in zip(b.replay_rows(a), b.replay_priorities(a)):
+            k = key(r)
+            if m != 1.0:
+                assert k in sampled[a], "a priority landed on a row that was not sampled"
+                assert abs(m - big) <= 2 * np.spacing(np.float32(big))
+                landed[a] += 1
+            assert k not in before[a] or k in sampled[a] or m == before[a][k]
+    assert (landed[shifted] == 0).all()
+    if not full:
+        assert list(landed) == [len(s) for s in sampled]
+    b.close()
+
+
+# ---- the weighted fit -------------------------------------------------------------------------------------------------
+def _fit_inputs(n):
+    rs = np.random.RandomState(1)
+    return rs.uniform(-1, 2, n).astype(np.float32), rs.uniform(-1, 2, n).astype(np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["lean", "plain"])
+def test_weighted_fit_with_unit_weights_is_dqn_fit(form):
+    from ofighters_amd import DeviceBuffer, _native as nat
+    from oracle import pyoracle
+    from tests.test_train import _collect_minibatch
+    b, n, rows_d, bp_d, _ = _collect_minibatch(4)
+    b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
+    w, _ = pyoracle.policy_init(5, trained_like=True)
+    y, y2 = _fit_inputs(n)
+    y_d, y2_d = DeviceBuffer(4 * n).upload(y), DeviceBuffer(4 * n).upload(y2)
+    ones = DeviceBuffer(4 * n).upload(np.ones(n, np.float32))
+    td = DeviceBuffer(8 * n)
+    res = []
+    for weighted in (False, True):
+        bufs = [DeviceBuffer(w.nbytes) for _ in range(4)]
+        bufs[0].upload(w); bufs[1].upload(np.zeros_like(w)); bufs[2].upload(np.zeros_like(w))
+        args = (bufs[0], bufs[1], bufs[2], 1, 1e-4, n, rows_d.ptr, bp_d.ptr, y_d.ptr, y2_d.ptr)
+        if weighted:
+            l = b.dqn_fit_weighted(*args, row_weight_ptr=ones.ptr, td_ptr=td.ptr, grad_buf=bufs[3])
+        else:
+            l = b.dqn_fit(*args, grad_buf=bufs[3])
+        b.sync()
+        res.append((l, [x.download(np.float32, w.shape) for x in bufs]))
+    (la, xa), (lb, xb) = res
+    assert la == lb
+    for k in range(4):                                      # weights, adam m, adam v, gradient
+        assert np.array_equal(xa[k], xb[k]), k
+    b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["lean", "plain"])
+def test_weighted_fit_vs_torch_autograd(form):
+    from ofighters_amd import DeviceBuffer, _native as nat
+    from oracle import pyoracle
+    from tests.per_torch_ref import weighted_reference
+    from tests.test_train import _collect_minibatch, _compare_gradients
+    b, n, rows_d, bp_d, _ = _collect_minibatch(1)           # 4 rows
+    assert n == 4
+    b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
+    w, shapes = pyoracle.policy_init(9, trained_like=True)
+    y, y2 = _fit_inputs(n)
+    rw = np.random.RandomState(8).uniform(0.05, 1.0, n).astype(np.float32)
+    y_d, y2_d, rw_d = (DeviceBuffer(4 * n).upload(v) for v in (y, y2, rw))
+    td_d = DeviceBuffer(8 * n)
+    zeros = np.zeros_like(w)
+    w_d, m_d, v_d, g_d = DeviceBuffer(w.nbytes).upload(w), DeviceBuffer(w.nbytes).upload(zeros), \
+        DeviceBuffer(w.nbytes).upload(zeros), DeviceBuffer(w.nbytes)
+    l1, l2 = b.dqn_fit_weighted(w_d, m_d, v_d, 1, 1e-4, n, rows_d.ptr, bp_d.ptr, y_d.ptr, y2_d.ptr, rw_d.ptr, td_d.ptr, g_d)
+    b.sync()
+    g = g_d.download(np.float32, w.shape).astype(np.float64)
+    td = td_d.download(np.float32, (n, 2)).astype(np.float64)
+    rows = rows_d.download(b.TRANSITION_DTYPE, (n,))
+    bits = bp_d.download(np.uint32, (n, 2, 5000))
+    x0 = np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(n, 2, 400, 400).astype(np.float64)
+    rl1, rl2, rg, e1, e2 = weighted_reference(w.astype(np.float64), shapes, x0, rows["head_prev"],
+                                              rows["iaction"].astype(np.int64), rows["px"].astype(np.int64),
+                                              rows["py"].astype(np.int64), y, y2, rw)
+    assert abs(l1 - rl1) <= 1e-4 * max(1.0, abs(rl1)) and abs(l2 - rl2) <= 1e-4 * max(1e-9, abs(rl2)) + 1e-12
+    _compare_gradients(shapes, rg, g)
+    np.testing.assert_allclose(td[:, 0], e1, rtol=0, atol=1e-4 * max(1.0, np.abs(e1).max()))
+    np.testing.assert_allclose(td[:, 1], e2, rtol=0, atol=1e-4 * max(1.0, np.abs(e2).max()))
+    b.close()
+
+
+@pytest.mark.gpu
+def test_weighted_lean_fit_equals_plain_fit_at_128_rows():
+    """the bounds of test_lean_fit_equals_plain_fit_large_batches (its checker, reused) with random row weights in the
+    textbook fit"""
+    from ofighters_amd import DeviceBuffer
+    from tests.test_train import _check_lean_equals_plain, _collect_minibatch
+    b, n, rows_d, bp_d, bn_d = _collect_minibatch(32)
+    assert n == 128
+    rw = DeviceBuffer(4 * n).upload(np.random.RandomState(6).uniform(0.05, 1.0, n).astype(np.float32))
+    plain_fit = b.dqn_fit
+    b.dqn_fit = lambda *a, grad_buf=None: b.dqn_fit_weighted(*a[:10], row_weight_ptr=rw.ptr,
+                                                             grad_buf=grad_buf if grad_buf is not None else a[10])
+    try:
+        _check_lean_equals_plain(b, n, rows_d, bp_d, bn_d)
+    finally:
+        b.dqn_fit = plain_fit
+    b.close()
+
+
+# ---- end to end ------------------------------------------------------------------------------------------------------
+def _train(seed):
+    from ofighters_amd import ArenaBatch
+    from ofighters_amd.agents.policy_weights import synthetic
+    from ofighters_amd.lib.epsilon import Epsilon_decay
+    from ofighters_amd.rollout import TrainingRollout
+    from ofighters_amd.trainer import DeviceTrainer
+    N, M = 64, 8
+    b = ArenaBatch(N, M)
+    eps = Epsilon_decay()
+    eps.set(0.3)
+    tr = DeviceTrainer(b, synthetic(7), learning_rate=1e-3, epsilon=eps, batch_size=8, memory_size=100, fit_batch=64,
+                       seed=seed, prioritized=True, per_beta_steps=40)
+    roll = TrainingRollout(b, tr, ["idle"] * M, seed, policy_ships=(0,), episode_ticks=60, replay_every=5)
+    roll.run(300)
+    masses = np.concatenate([b.replay_priorities(a) for a in range(N)])
+    w = tr.weights_host()
+    out = (w, np.array(roll.losses), masses, tr.beta())
+    b.close()
+    return out
+
+
+@pytest.mark.gpu
+def test_training_rollout_with_prioritized_replay():
+    w, L, masses, beta = _train(0x0F160031)
+    assert len(L) >= 50 and np.isfinite(L).all()
+    assert np.isfinite(masses).all() and (masses > 0).all() and (masses != 1.0).sum() >= 64
+    assert abs(beta - 1.0) < 1e-12
+    w2, L2, masses2, _ = _train(0x0F160031)
+    assert np.array_equal(w, w2) and np.array_equal(L, L2) and np.array_equal(masses, masses2)
+
+
+def test_prioritized_trainer_refuses_reference_quirks():
+    from ofighters_amd.trainer import DeviceTrainer
+    with pytest.raises(ValueError):
+        DeviceTrainer(None, np.zeros(4, np.float32), prioritized=True, reference_quirks=True)
