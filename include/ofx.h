@@ -466,6 +466,37 @@ int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, const int32
 /* Masses of one arena, oldest first (the order of ofx_replay_rows_host); mass_host holds `capacity` floats.        */
 int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *mass_host, int32_t *n_host);
 
+/* ---- n-step returns (opt-in) --------------------------------------------
+ * Not in the reference.  Off unless these two calls are used; nothing above changes.
+ *  - Window: ofx_replay_gather_nstep gathers the window ofx_replay_gather_valid gathers for the same (slot, n_sampled,
+ *    batch, first, max_rows): the same packed (arena, j) order, the same *n_rows_host, the same synchronisation.
+ *  - Chain: from the sampled row r0, r_{k+1} is the row of the same arena and ship with tick_prev == r_k.tick_next
+ *    (unique: a ship appends at most one row per capture tick, and the capture tick never restarts).  The chain stops
+ *    after L = nstep rows, after a row with done != 0, or when no such row is in the memory (an episode restart cleared
+ *    previous_*, so the ticks do not chain, or the successor is not captured yet); a truncated chain is no error and
+ *    bootstraps from its last row with gamma^L.  The walk only reads the memory.
+ *  - Composite row: r0 with tick_next, frame_next, head_next and done of r_{L-1} (ship, tick_prev, frame_prev, iaction,
+ *    px, py, head_prev and reward stay r0's, so ofx_replay_update_priorities writes PER priorities back unchanged).
+ *    bits_prev[d] = r0's state maps, bits_next[d] = r_{L-1}'s next-state maps (newer than r0's state frame, so still in
+ *    the ring whenever r0 is eligible).
+ *  - Return and discount, float64 with every operation rounded on its own (no FMA): g = (double)gamma, acc = 0, p = 1;
+ *    for k = 0 .. L-1: acc += p * r_k.reward, then p *= g.  ret[d] = (float)acc, disc[d] = r_{L-1}.done ? 0 : (float)p.
+ *  - Targets: ofx_dqn_targets_nstep is ofx_dqn_targets with y_act = ret + disc * max(act_values(next_state)) and
+ *    y_ptr = ret + disc * max(heat(next_state)) in float32, the product rounded, then the sum (no FMA).  q_sa / p_sp,
+ *    their NULL rule and padding rows as in ofx_dqn_targets.
+ *  - nstep = 1 gives ofx_replay_gather_valid's rows and maps bit for bit with ret = reward, disc = gamma * (not done),
+ *    and those fed to ofx_dqn_targets_nstep give ofx_dqn_targets' y_act / y_ptr bit for bit.
+ * Errors: OFX_ERR_INVALID where ofx_replay_gather_valid fails so, for nstep outside 1 .. 64, for gamma not finite or
+ * outside [0, 1], and (both calls) for a NULL ret or disc.                                                          */
+/* ret[max_rows] / disc[max_rows] float32, device pointers like the rest; maps may be NULL.  Synchronises.          */
+int ofx_replay_gather_nstep(ofx_handle *h, const int32_t *slot, const int32_t *n_sampled, int32_t batch, int32_t first,
+                            int32_t max_rows, int32_t nstep, float gamma, ofx_transition *rows, void *bits_prev,
+                            void *bits_next, float *ret, float *disc, int32_t *n_rows_host);
+/* ret[n] / disc[n] as ofx_replay_gather_nstep wrote them, for the n rows it gathered.                              */
+int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                          const void *bits_prev, const void *bits_next, const float *ret, const float *disc,
+                          float *q_sa, float *p_sp, float *y_act, float *y_ptr);
+
 /* ---- forward on stored observations, TD targets -------------------------
  * The predictions Trainer.replay makes on a minibatch (agents/qlearnIA_V2.py:251-268): n_obs observations given as
  * 1-bit map pairs bits[n_obs][2 (ship, laser)][W*H/32] uint32 (the layout ofx_replay_gather writes) + their toVector

@@ -1923,25 +1923,10 @@ __global__ void k_dqn_unpack(int n, const ofx_transition *rows, float *vec_prev,
   probe[2 * i + 1] = pad ? 0 : min(max(r.py, 0), PS - 1);
 }
 
-__global__ void k_dqn_targets(int n, const ofx_transition *rows, float gamma, const float *act_prev, const float *probe_prev,
-                              const float *act_next, const float *max_next, float *q_sa, float *p_sp, float *y_act,
-                              float *y_ptr) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ofx_transition r = rows[i];
-  if (r.ship < 0) {
-    if (q_sa) q_sa[i] = p_sp[i] = 0.f;
-    y_act[i] = y_ptr[i] = 0.f;
-    return;
-  }
-  const float live = r.done ? 0.f : 1.f;  // int(not done)
-  if (q_sa) {   // the forward on `state` was run
-    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
-    p_sp[i] = probe_prev[i];
-  }
-  y_act[i] = (float)r.reward + gamma * fmaxf(act_next[2 * i], act_next[2 * i + 1]) * live;  // np.max(prediction)
-  y_ptr[i] = (float)r.reward + gamma * max_next[i] * live;                                    // np.max(ptr_prediction)
-}
+// k_dqn_targets, the TD arithmetic (ofx_train.hip: a -ffp-contract=off file, see there)
+int ofx_launch_dqn_targets(ofx_handle *h, int n, const ofx_transition *rows, float gamma, const float *act_prev,
+                           const float *probe_prev, const float *act_next, const float *max_next, float *q_sa, float *p_sp,
+                           float *y_act, float *y_ptr, const float *ret, const float *disc);
 
 static int ensure_aux(ofx_handle *h, size_t bytes) {
   if (h->aux_bytes >= bytes) return OFX_OK;
@@ -1957,11 +1942,12 @@ extern "C" int ofx_policy_forward_obs(ofx_handle *h, const float *weights, int32
                                       const float *vec8, float *act_values, int32_t *iaction, int32_t *ipointer,
                                       float *ptr_max, const int32_t *probe, float *ptr_probe);
 
-extern "C" int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
-                               const void *bits_prev, const void *bits_next, float gamma, float *q_sa, float *p_sp,
-                               float *y_act, float *y_ptr) {
+// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch
+static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, int32_t n, const ofx_transition *rows,
+                            const void *bits_prev, const void *bits_next, float gamma, const float *ret, const float *disc,
+                            float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
   if (!h || !weights || !rows || !bits_prev || !bits_next || (!q_sa) != (!p_sp) || !y_act || !y_ptr || n < 1) {
-    ofx_set_error("ofx_dqn_targets: bad argument");
+    ofx_set_error("%s: bad argument", who);
     return OFX_ERR_INVALID;
   }
   OFX_HIP(hipSetDevice(h->cfg.device));
@@ -1984,10 +1970,23 @@ extern "C" int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, c
     return rc;
   if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, nullptr, max_next, nullptr, nullptr)))
     return rc;
-  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev, probe_prev,
-                     act_next, max_next, q_sa, p_sp, y_act, y_ptr);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
+  return ofx_launch_dqn_targets(h, n, rows, gamma, act_prev, probe_prev, act_next, max_next, q_sa, p_sp, y_act, y_ptr, ret,
+                                disc);
+}
+
+extern "C" int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                               const void *bits_prev, const void *bits_next, float gamma, float *q_sa, float *p_sp,
+                               float *y_act, float *y_ptr) {
+  return dqn_targets_impl(h, "ofx_dqn_targets", weights, n, rows, bits_prev, bits_next, gamma, nullptr, nullptr, q_sa,
+                          p_sp, y_act, y_ptr);
+}
+
+extern "C" int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                                     const void *bits_prev, const void *bits_next, const float *ret, const float *disc,
+                                     float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
+  if (!ret || !disc) { ofx_set_error("ofx_dqn_targets_nstep: ret and disc must be given"); return OFX_ERR_INVALID; }
+  return dqn_targets_impl(h, "ofx_dqn_targets_nstep", weights, n, rows, bits_prev, bits_next, 0.f, ret, disc, q_sa, p_sp,
+                          y_act, y_ptr);
 }
 
 // (iaction, ipointer) of the last forward / explore, for the other translation units (ofx_replay.hip)

@@ -443,10 +443,59 @@ __global__ __launch_bounds__(1024) void k_replay_scan(int N, const int32_t *n_sa
   if (tid == 1023) off[N] = part[1023];
 }
 
+// n-step returns (ofx_replay_gather_nstep; include/ofx.h states the contract): chain length, discount and outputs
+struct NstepParams {
+  int nstep;
+  double gamma;
+  float *ret, *disc;  // [max_rows]
+};
+
+// Wave 0 of the workgroup: the n-step chain from oldest-first row s.  Per step the 64 lanes test 64 consecutive rows
+// after the current one; the lowest row of the same ship is the ship's next row in append order, and it is the
+// successor iff its tick_prev is the current row's tick_next (a ship's tick_prev values increase strictly; a restart
+// in between leaves a gap).  Lane 0 writes ret / disc; returns the oldest-first index of the chain's last row.
+__device__ int nstep_chain(const ofx_transition *ring, int C, int first_row, int count, int s, int lane, int d,
+                           const NstepParams &q) {
+  int cur = s, L = 0;
+  double acc = 0.0, pw = 1.0;
+  for (;;) {
+    const ofx_transition *r = ring + (first_row + cur) % C;
+    const int done = r->done, ship = r->ship, tick = r->tick_next;
+    acc += pw * (double)r->reward;  // -ffp-contract=off: the product and the sum round on their own
+    pw *= q.gamma;
+    if (done || ++L == q.nstep) break;
+    int next = -1;
+    for (int base = cur + 1; base < count; base += 64) {  // wave-uniform trip count
+      const int i = base + lane;
+      bool same = false;
+      int tp = 0;
+      if (i < count) {
+        const ofx_transition *c = ring + (first_row + i) % C;
+        same = c->ship == ship;
+        tp = c->tick_prev;
+      }
+      const unsigned long long hit = __ballot(same);
+      if (hit) {
+        const int l = __ffsll((long long)hit) - 1;
+        if (__shfl(tp, l) == tick) next = base + l;
+        break;
+      }
+    }
+    if (next < 0) break;  // restart (the ship's next row does not chain) or ring head (no next row yet)
+    cur = next;
+  }
+  if (lane == 0) {
+    q.ret[d] = (float)acc;
+    q.disc[d] = ring[(first_row + cur) % C].done ? 0.f : (float)pw;
+  }
+  return cur;
+}
+
 // one workgroup per (arena, j): sampled entry j of arena a is packed row off[a] + j - first, when it falls into
-// [0, max_rows)
+// [0, max_rows).  NSTEP: the row is the composite of the n-step chain from it (wave 0 walks the chain first).
+template <bool NSTEP>
 __global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, const int32_t *n_sampled, const int32_t *off, int first,
-                                                             int max_rows) {
+                                                             int max_rows, NstepParams q) {
   const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
   if (j >= n_sampled[a]) return;
   const int d = off[a] + j - first;
@@ -454,10 +503,25 @@ __global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, con
   const int s = p.slot[(size_t)a * p.batch + j];
   const int count = p.r.count[a], head = p.r.head[a];
   const int first_row = ((head - count) % p.C + p.C) % p.C;
-  const ofx_transition *src = p.r.rows + (size_t)a * p.C + (first_row + s) % p.C;
+  const ofx_transition *ring = p.r.rows + (size_t)a * p.C;
+  const ofx_transition *src = ring + (first_row + s) % p.C;
+  const ofx_transition *end = src;  // the row whose next state is gathered
+  if constexpr (NSTEP) {
+    __shared__ int end_s;
+    if (threadIdx.x < 64) {
+      const int e = nstep_chain(ring, p.C, first_row, count, s, threadIdx.x, d, q);
+      if (threadIdx.x == 0) end_s = e;
+    }
+    __syncthreads();
+    end = ring + (first_row + end_s) % p.C;
+  }
   ofx_transition *dst = p.rows + d;
-  if (threadIdx.x < sizeof(ofx_transition) / 4) ((int32_t *)dst)[threadIdx.x] = ((const int32_t *)src)[threadIdx.x];
-  const int slots[2] = {src->frame_prev, src->frame_next};
+  if (threadIdx.x < sizeof(ofx_transition) / 4) {
+    const int w = threadIdx.x;  // tick_next, frame_next, done and head_next come from the chain's last row
+    const bool from_end = w == 1 || w == 3 || w == 9 || w >= (int)(offsetof(ofx_transition, head_next) / 4);
+    ((int32_t *)dst)[w] = ((const int32_t *)(from_end ? end : src))[w];
+  }
+  const int slots[2] = {src->frame_prev, end->frame_next};
   uint32_t *outs[2] = {p.bits_prev, p.bits_next};
   for (int w = 0; w < 2; w++) {
     if (!outs[w]) continue;
@@ -467,11 +531,12 @@ __global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, con
   }
 }
 
-extern "C" int ofx_replay_gather_valid(ofx_handle *h, const int32_t *slot, const int32_t *n_sampled, int32_t batch,
-                                       int32_t first, int32_t max_rows, ofx_transition *rows, void *bits_prev,
-                                       void *bits_next, int32_t *n_rows_host) {
+// ofx_replay_gather_valid (q == null) and ofx_replay_gather_nstep: the same window, scan and synchronisation
+static int gather_window(ofx_handle *h, const char *who, const int32_t *slot, const int32_t *n_sampled, int32_t batch,
+                         int32_t first, int32_t max_rows, ofx_transition *rows, void *bits_prev, void *bits_next,
+                         int32_t *n_rows_host, const NstepParams *q) {
   if (!h || !h->replay || !slot || !n_sampled || !rows || !n_rows_host || batch <= 0 || first < 0 || max_rows <= 0) {
-    ofx_set_error("ofx_replay_gather_valid: bad argument");
+    ofx_set_error("%s: bad argument", who);
     return OFX_ERR_INVALID;
   }
   ofx_replay *r = h->replay;
@@ -482,15 +547,39 @@ extern "C" int ofx_replay_gather_valid(ofx_handle *h, const int32_t *slot, const
   GatherParams p;
   p.N = N; p.C = r->capacity; p.F = r->frames; p.batch = batch; p.words = r->words;
   p.r = *r; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
-  hipLaunchKernelGGL(k_replay_gather_valid, dim3((unsigned)(N * batch)), dim3(256), 0, h->stream, p, n_sampled, (const int32_t *)off,
-                     first, max_rows);
+  if (q)
+    hipLaunchKernelGGL(k_replay_gather_valid<true>, dim3((unsigned)(N * batch)), dim3(256), 0, h->stream, p, n_sampled,
+                       (const int32_t *)off, first, max_rows, *q);
+  else
+    hipLaunchKernelGGL(k_replay_gather_valid<false>, dim3((unsigned)(N * batch)), dim3(256), 0, h->stream, p, n_sampled,
+                       (const int32_t *)off, first, max_rows, NstepParams{});
   hipError_t e = hipGetLastError();
   int32_t total = 0;
   if (e == hipSuccess) e = hipMemcpyAsync(&total, off + N, sizeof(total), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { ofx_set_error("ofx_replay_gather_valid: %s", hipGetErrorString(e)); return OFX_ERR_HIP; }
+  if (e != hipSuccess) { ofx_set_error("%s: %s", who, hipGetErrorString(e)); return OFX_ERR_HIP; }
   *n_rows_host = total - first < 0 ? 0 : (total - first > max_rows ? max_rows : total - first);
   return OFX_OK;
+}
+
+extern "C" int ofx_replay_gather_valid(ofx_handle *h, const int32_t *slot, const int32_t *n_sampled, int32_t batch,
+                                       int32_t first, int32_t max_rows, ofx_transition *rows, void *bits_prev,
+                                       void *bits_next, int32_t *n_rows_host) {
+  return gather_window(h, "ofx_replay_gather_valid", slot, n_sampled, batch, first, max_rows, rows, bits_prev, bits_next,
+                       n_rows_host, nullptr);
+}
+
+extern "C" int ofx_replay_gather_nstep(ofx_handle *h, const int32_t *slot, const int32_t *n_sampled, int32_t batch,
+                                       int32_t first, int32_t max_rows, int32_t nstep, float gamma, ofx_transition *rows,
+                                       void *bits_prev, void *bits_next, float *ret, float *disc, int32_t *n_rows_host) {
+  if (!ret || !disc || nstep < 1 || nstep > 64 || !(gamma >= 0.f && gamma <= 1.f)) {  // (NaN fails the gamma test)
+    ofx_set_error("ofx_replay_gather_nstep: ret and disc must be given, nstep in 1..64 and gamma in [0, 1], got %d, %g",
+                  nstep, (double)gamma);
+    return OFX_ERR_INVALID;
+  }
+  const NstepParams q{nstep, (double)gamma, ret, disc};
+  return gather_window(h, "ofx_replay_gather_nstep", slot, n_sampled, batch, first, max_rows, rows, bits_prev, bits_next,
+                       n_rows_host, &q);
 }
 
 // ---- prioritized experience replay (Schaul et al. 2016, proportional variant; include/ofx.h states the contract) ------

@@ -478,6 +478,47 @@ __global__ void t_reference_targets(int n, const ofx_transition *rows, float gam
   // ptr_target[ipointer] with ipointer = (x, y) on the (400, 400, 1) prediction = [row][col][0]: row x, column y (:280)
   t2[(size_t)s * TPS * TPS + (size_t)px * TPS + py] = (float)r.reward + gamma * max_next[s] * live;
 }
+
+// The TD arithmetic of ofx_dqn_targets / ofx_dqn_targets_nstep (their forwards run in ofx_policy.hip).  It lives in this
+// -ffp-contract=off file because the n-step form must round the product and the sum on their own, and under
+// -ffp-contract=fast the backend fuses them whatever `#pragma clang fp contract` says.  The one-step form gives the
+// bits it gave there as fma(live, gamma * m, reward): live is 0 or 1, so that fma rounds once, like the add here.
+// ret / disc null: the one-step targets of Trainer.replay.
+__global__ void k_dqn_targets(int n, const ofx_transition *rows, float gamma, const float *act_prev, const float *probe_prev,
+                              const float *act_next, const float *max_next, float *q_sa, float *p_sp, float *y_act,
+                              float *y_ptr, const float *ret, const float *disc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ofx_transition r = rows[i];
+  if (r.ship < 0) {
+    if (q_sa) q_sa[i] = p_sp[i] = 0.f;
+    y_act[i] = y_ptr[i] = 0.f;
+    return;
+  }
+  if (q_sa) {   // the forward on `state` was run
+    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
+    p_sp[i] = probe_prev[i];
+  }
+  const float m_act = fmaxf(act_next[2 * i], act_next[2 * i + 1]);  // np.max(prediction)
+  if (ret) {                                                          // n-step: ret + disc * max
+    y_act[i] = ret[i] + disc[i] * m_act;
+    y_ptr[i] = ret[i] + disc[i] * max_next[i];
+    return;
+  }
+  const float live = r.done ? 0.f : 1.f;  // int(not done)
+  y_act[i] = (float)r.reward + gamma * m_act * live;
+  y_ptr[i] = (float)r.reward + gamma * max_next[i] * live;  // np.max(ptr_prediction)
+}
+
+int ofx_launch_dqn_targets(ofx_handle *h, int n, const ofx_transition *rows, float gamma, const float *act_prev,
+                           const float *probe_prev, const float *act_next, const float *max_next, float *q_sa, float *p_sp,
+                           float *y_act, float *y_ptr, const float *ret, const float *disc) {
+  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev, probe_prev,
+                     act_next, max_next, q_sa, p_sp, y_act, y_ptr, ret, disc);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
 __global__ void t_unpack_heads(int n, const ofx_transition *rows, float *vec_prev, float *vec_next) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;

@@ -528,6 +528,27 @@ class ArenaBatch:
         nat.check(nat.lib().ofx_replay_priorities_host(self._h, int(arena), m.ctypes.data_as(C.c_void_p), C.byref(n)))
         return m[:n.value]
 
+    # ------------------------------------------------------------ n-step returns (include/ofx.h: the contract)
+    def replay_gather_nstep_into(self, slot, n_sampled, batch, first, max_rows, nstep, gamma, rows, bits_prev, bits_next,
+                                 ret, disc):
+        """replay_gather_valid_into's window with every row the composite of its n-step chain: ret / disc [max_rows]
+        float32 DeviceBuffers receive the discounted return and the bootstrap discount; returns n_rows."""
+        n = C.c_int32()
+        nat.check(nat.lib().ofx_replay_gather_nstep(self._h, slot.ptr, n_sampled.ptr, int(batch), int(first), int(max_rows),
+                                                     int(nstep), float(gamma), rows.ptr, bits_prev.ptr if bits_prev else None,
+                                                     bits_next.ptr if bits_next else None, ret.ptr, disc.ptr, C.byref(n)))
+        return n.value
+
+    def dqn_targets_nstep(self, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr, ret_ptr, disc_ptr, current=True):
+        """dqn_targets with y = ret + disc * max(next_state) (ret / disc from replay_gather_nstep_into): host arrays q_sa,
+        p_sp, y_act, y_ptr; current=False: only y_act, y_ptr."""
+        n = int(n)
+        bufs = [DeviceBuffer(4 * n) if (current or k >= 2) else None for k in range(4)]
+        nat.check(nat.lib().ofx_dqn_targets_nstep(self._h, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr, ret_ptr,
+                                                   disc_ptr, *[b.ptr if b else None for b in bufs]))
+        self.sync()
+        return tuple(b.download(np.float32, (n,)) if b else None for b in bufs)
+
     def policy_forward_obs(self, weights_ptr, n_obs, bits_ptr, vec8_ptr, want_probe_ptr=None):
         """Forward on stored observations (Trainer.replay's predictions): host dict of act / iaction / ipointer /
         ptr_max (+ ptr_probe when want_probe_ptr, an int32 [n_obs][2] device array of (x, y), is given)."""

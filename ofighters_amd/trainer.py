@@ -8,7 +8,14 @@ ptr_target[x][y] and the fit on next_state's inputs included, :280-283).
 `prioritized=True` (opt-in, not in the reference) turns on proportional prioritized experience replay (Schaul et al.
 2016): ofx_replay_sample_prioritized draws the minibatch by priority, ofx_dqn_fit_weighted takes the window's
 importance-sampling weights (beta annealed linearly from per_beta to 1 over per_beta_steps fit steps) and returns the
-rows' TD errors, which ofx_replay_update_priorities writes back."""
+rows' TD errors, which ofx_replay_update_priorities writes back.
+
+`n_step=n` (opt-in, not in the reference; 1 = the one-step targets above) bootstraps every target n lock-steps ahead:
+ofx_replay_gather_nstep follows each sampled row's ship through its following rows (until n rows, its death, an episode
+restart or the newest row), gathers the chain's last next-state maps and the discounted return ret = sum gamma^k r_k with
+the discount disc = gamma^L (0 after a death), and ofx_dqn_targets_nstep forms y = ret + disc * max(next_state).  Works
+with `prioritized` (the priorities become n-step TD errors); the return is not corrected for the off-policy actions
+inside the chain (as in Rainbow)."""
 import numpy as np
 
 from .engine import DeviceBuffer
@@ -18,9 +25,14 @@ from .lib.epsilon import Epsilon_cos
 class DeviceTrainer:
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
-                 per_beta_steps=50_000, per_eps=1e-3):
+                 per_beta_steps=50_000, per_eps=1e-3, n_step=1):
         if prioritized and reference_quirks:
             raise ValueError("DeviceTrainer: prioritized replay needs the textbook fit (reference_quirks=False)")
+        if int(n_step) != n_step or n_step < 1:
+            raise ValueError("DeviceTrainer: n_step must be an integer >= 1, got %r" % (n_step,))
+        if n_step > 1 and reference_quirks:
+            raise ValueError("DeviceTrainer: n-step returns need the textbook fit (reference_quirks=False computes its own "
+                             "one-step targets)")
         self.batch = batch                                  # the ArenaBatch this trainer plays and learns on
         w = np.ascontiguousarray(weights, np.float32)
         self.n_floats = w.size
@@ -39,6 +51,7 @@ class DeviceTrainer:
         self.reference_quirks = bool(reference_quirks)      # Trainer.replay as written instead of the textbook DQN step
         self.prioritized = bool(prioritized)                # PER: priority exponent alpha, IS exponent beta -> 1, eps
         self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = per_alpha, per_beta, per_beta_steps, per_eps
+        self.n_step = int(n_step)                           # TD targets bootstrap n_step lock-steps ahead (1: one-step)
         self.fit_steps = 0
         self.draws = 0
         self.losses = []
@@ -103,7 +116,7 @@ class DeviceTrainer:
         words = b.W * b.H // 32
         rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
         bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
-        got = b.replay_gather_valid_into(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
+        got = self._gather(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
         if got != n:
             raise Exception("DeviceTrainer.replay: gathered %d of %d rows" % (got, n))
         rows_p, prev_p, next_p = rows.ptr, bits_prev.ptr, bits_next.ptr
@@ -114,16 +127,34 @@ class DeviceTrainer:
             self.losses.append(loss)
             return loss
         y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
-        from . import _native as nat
-        # q_sa / p_sp (the current values at the chosen action / pointer) are not asked for: the fit's own training-mode
-        # forward produces them, so the targets need the forward on next_state only
-        nat.check(nat.lib().ofx_dqn_targets(b.handle, self.weights.ptr, n, rows_p, prev_p, next_p, float(self.gamma),
-                                             None, None, y_act.ptr, y_ptr.ptr))
+        self._targets(n, rows_p, prev_p, next_p, y_act, y_ptr)
         self.fit_steps += 1
         loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
                          y_act.ptr, y_ptr.ptr)
         self.losses.append(loss)
         return loss
+
+    def _gather(self, slot, n_s, bs, start, n, rows, bits_prev, bits_next):
+        """The window of sampled rows: ofx_replay_gather_valid, or with n_step > 1 the rows' n-step composites and their
+        ret / disc (two more grow-only scratch buffers, read by _targets)."""
+        b = self.batch
+        if self.n_step == 1:
+            return b.replay_gather_valid_into(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
+        ret, disc = self._scratch("ret", 4 * n), self._scratch("disc", 4 * n)
+        return b.replay_gather_nstep_into(slot, n_s, bs, start, n, self.n_step, self.gamma, rows, bits_prev, bits_next,
+                                          ret, disc)
+
+    def _targets(self, n, rows_p, prev_p, next_p, y_act, y_ptr):
+        """y_act / y_ptr of the gathered window.  q_sa / p_sp (the current values at the chosen action / pointer) are not
+        asked for: the fit's own training-mode forward produces them, so the targets need the forward on next_state only."""
+        from . import _native as nat
+        h, w = self.batch.handle, self.weights.ptr
+        if self.n_step == 1:
+            nat.check(nat.lib().ofx_dqn_targets(h, w, n, rows_p, prev_p, next_p, float(self.gamma), None, None, y_act.ptr,
+                                                 y_ptr.ptr))
+        else:
+            nat.check(nat.lib().ofx_dqn_targets_nstep(h, w, n, rows_p, prev_p, next_p, self._buf["ret"].ptr,
+                                                       self._buf["disc"].ptr, None, None, y_act.ptr, y_ptr.ptr))
 
     def beta(self):
         """The IS exponent of the next fit step: per_beta -> 1.0 linearly over per_beta_steps fit steps."""
@@ -147,15 +178,13 @@ class DeviceTrainer:
         words = b.W * b.H // 32
         rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
         bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
-        got = b.replay_gather_valid_into(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
+        got = self._gather(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
         if got != n:
             raise Exception("DeviceTrainer.replay: gathered %d of %d rows" % (got, n))
         row_w, td = self._scratch("row_w", 4 * n), self._scratch("td", 8 * n)
         b.replay_window_weights_into(isw, n_s, bs, start, n, row_w)
         y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
-        from . import _native as nat
-        nat.check(nat.lib().ofx_dqn_targets(b.handle, self.weights.ptr, n, rows.ptr, bits_prev.ptr, bits_next.ptr,
-                                             float(self.gamma), None, None, y_act.ptr, y_ptr.ptr))
+        self._targets(n, rows.ptr, bits_prev.ptr, bits_next.ptr, y_act, y_ptr)
         self.fit_steps += 1
         loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows.ptr,
                                   bits_prev.ptr, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
