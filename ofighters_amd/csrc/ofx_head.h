@@ -16,7 +16,8 @@ struct HeadParams2 {
   const float *efr;             // frame phase weights of upconv4 [line h|v][side][parity 2][3][8] (PrepLayout::efr)
   float *u2fr;                  // [S][4][100][4] exact frame lines of uprelu2: row 0, row 99, col 0, col 99
   float *vfr;                   // [S][4][200][9] exact frame lines of the tap planes V_t = sum_c w4[t][c] uprelu3_c (top, bottom, left, right)
-  float *c4;                    // [S][4][400]   zero-padding corrections of the heat-map frame pixels
+  float *c4;                    // [S][1664]     zero-padding corrections of the heat-map frame pixels: four lines of 400, the
+                                //               column lines padded with zeros (HC4_*, ofx_head.hip)
   const uint8_t *mask;          // [S] or null
   int32_t *live;                // with a mask: scratch [1 + S], filled here with the count and the ordered list of the
                                 // selected ships - workgroup i works on live[1 + i], so the live workgroups are the

@@ -36,6 +36,24 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define HD_PS 400
+// c4 of one ship (floats): the two row lines (top, bottom), 16 zeros, the two column lines (left, right), each followed
+// by 16 zeros.  k_head_stream's consumers read a column line at heat-map rows -16 .. 413 (the passes in front of the
+// first and behind the last row, whose results are dropped) and read the zeros wherever a lane has no frame pixel.
+// Behind the S ships' blocks stands one block of HC4_STRIDE zeros: the "other strip's" column line of every workgroup.
+constexpr int HC4_ZERO = 800;
+constexpr int HC4_COL = 816, HC4_CPITCH = 416;
+constexpr int HC4_STRIDE = HC4_COL + 2 * HC4_CPITCH + 16;   // 1664
+// line ln (row 0, row 399, column 0, column 399), pixel t along it
+__device__ __forceinline__ int hc4_at(int ln, int t) { return ln < 2 ? ln * 400 + t : HC4_COL + (ln - 2) * HC4_CPITCH + t; }
+// the zeros: 800 .. 815, 1216 .. 1231, 1632 .. 1663 (64 cells, k = 0 .. 63)
+__device__ __forceinline__ int hc4_pad(int k) { return k < 16 ? HC4_ZERO + k : k < 32 ? HC4_COL + 400 + k - 16 : HC4_COL + HC4_CPITCH + 400 + k - 32; }
+
+// the block of zeros behind the ships' c4 lines (the scratch is shared with other layouts: written by the first
+// workgroup of every launch of the frame kernel)
+__device__ __forceinline__ void hc4_zero_block(const HeadParams2 &p, int tid, int threads) {
+  if (blockIdx.x == 0)
+    for (int e = tid; e < HC4_STRIDE; e += threads) p.c4[(size_t)p.S * HC4_STRIDE + e] = 0.f;
+}
 
 // max without the canonicalising v_max(x, x) of fmaxf(); compiler-visible (never feed an MFMA result to inline asm:
 // the hazard recogniser does not look inside an asm statement)
@@ -124,6 +142,7 @@ __global__ __launch_bounds__(HF_THREADS) void k_head_frames_ref(HeadParams2 p) {
   __shared__ __align__(16) float sm[HF_TOTAL];
   const int tid = threadIdx.x;
   const int s = hd_ship(p, (int)blockIdx.x);
+  hc4_zero_block(p, tid, HF_THREADS);
   if (s < 0) return;  // block-uniform
   float *l1 = sm + HF_L1, *U1r = sm + HF_U1R, *U1c = sm + HF_U1C, *U2r = sm + HF_U2R, *U2c = sm + HF_U2C;
   float *u2rb = sm + HF_B2R, *u2cb = sm + HF_B2C, *u3l = sm + HF_U3L;
@@ -272,8 +291,9 @@ __global__ __launch_bounds__(HF_THREADS) void k_head_frames_ref(HeadParams2 p) {
         }
       }
     }
-    p.c4[(size_t)s * 1600 + e] = acc;
+    p.c4[(size_t)s * HC4_STRIDE + hc4_at(ln, t)] = acc;
   }
+  if (tid < 64) p.c4[(size_t)s * HC4_STRIDE + hc4_pad(tid)] = 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -327,6 +347,7 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
   // must not leave all the live workgroups on one of them)
   const int s = hd_ship(p, (int)((blockIdx.x & ~7u) | ((blockIdx.x + (blockIdx.x >> 3)) & 7u)));
   const int tid = threadIdx.x, lane = tid & 63;
+  hc4_zero_block(p, tid, HG_THREADS);
   if (s < 0) return;  // block-uniform
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n16 = lane & 15, kq = lane >> 4;
@@ -521,8 +542,9 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
         for (int ci = 0; ci < 8; ci++) acc -= p.w4raw[tap * 8 + ci] * Lc[ci];
       }
     }
-    p.c4[(size_t)s * 1600 + e] = acc;
+    p.c4[(size_t)s * HC4_STRIDE + hc4_at(ln, t)] = acc;
   }
+  if (tid < 64) p.c4[(size_t)s * HC4_STRIDE + hc4_pad(tid)] = 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -544,7 +566,7 @@ static_assert(HS_PL2 % 32 == 16, "uprelu2 plane stride");
 constexpr int HS_TABP = 16 * HS_GPR;
 static_assert(HS_TABP == 4 * 52, "table period in tiles");
 // LDS of a workgroup: two of them per CU (160 KB)
-static_assert(4 * (HS_NV * HS_PL3 + 4 * HS_PL2 + HS_TABP) <= 80 * 1024, "two workgroups per CU");
+static_assert(4 * (HS_NV * HS_PL3 + 4 * HS_PL2 + HS_TABP + 400) <= 80 * 1024, "two workgroups per CU");
 // uprelu2 row pairs finished by the end of sub-step s - 1 (0 = by the prologue): the table of tools/head_schedule.py,
 // 2, 3, 5, 6, 7, 8, 10, ...: min(50, s + 2 + ((s + 2) >> 2)) (hs_pairs_done_c below)
 // Stage-A tile of consumer wave cw in sub-step st (uprelu2 rows for the M-tiles of st + 1): tile id 2 pair + half belongs
@@ -613,6 +635,8 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
   // lo 16 bits: float offset of the group's first quad in the uprelu2 ring (row slot of quad row - 1); hi: in a tap
   // plane (row slot of uprelu3 row 2 * quad row), bit 31: the group holds the strip's frame column
   __shared__ unsigned tabG[HS_TABP];
+  // the strip's halves of c4's two row lines (heat-map rows 0 and 399): read in two of the 42 sub-steps
+  __shared__ __align__(16) float crs[2 * 200];
   // blocks b and b + 8 (same XCD under round-robin placement) are the two halves of one ship; the ship of a block
   // rotates with the group of 16 blocks, so that a regular ship mask (say the first ship of every arena: the
   // reference's own line-up has one policy ship) does not put all the live workgroups on one XCD
@@ -955,7 +979,7 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
 #pragma unroll
         for (int t = 0; t < 3; t++) cy[a][k][t] = p.legacy ? HS_CL[a][k][t] : HS_CH[a][k][t];
     const bool fcol = task_ok && (side ? jx == 49 : jx == 0);  // the lane owns pixels of the strip's frame column
-    const float *c4s = p.c4 + (size_t)s * 1600;
+    const float *c4s = p.c4 + (size_t)s * HC4_STRIDE;
     const int x0 = 100 * side + 2 * jx;              // uprelu3 column of the lane's first pixel
     // running per-lane state: R = uprelu3 row of the lane's pixels in this sub-step (+5 per sub-step); q[dy] = byte
     // offset of ring row R + dy - 1 at the lane's column (+5 rows per sub-step, wrapped at 16 rows)
@@ -966,7 +990,23 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
 #pragma unroll
     for (int dy = 0; dy < 3; dy++) q[dy] = (unsigned)((R + dy - 1) & (HS_NR3 - 1)) * PB + lcol;
     const unsigned qlim = RING + lcol;
-    int coff = (side ? 3 : 2) * 400 + 2 * R;         // frame-column correction of the lane's two heat-map rows
+    // zero-padding corrections of the frame pixels (global memory), requested a sub-step ahead like stage A's operands:
+    // unconditional loads, so that no wait in the pass has to drain the counter.  Column: a frame-column lane walks its
+    // line of c4 (+ 2 heat-map rows x 5 per sub-step, the line is padded for the passes outside the plane), every
+    // other lane re-reads a zero word (x - (+0) = x, every bit).  The frame pixel is the lane's first pixel, column
+    // parity 0, in the left strip and its second pixel, parity 1, in the right one: both pairs are loaded with the
+    // lane's offset, the one the strip does not have from the block of zeros (a scalar base chosen once), and both are
+    // subtracted - no select or branch on `side` in the pass.  Row: the pixels of row 0 are met in sub-step 1 by the
+    // lanes with r_in = 3, those of row 199 in the last sub-step by the lanes with r_in = 2: the strip's part of the two
+    // lines waits in LDS (visible behind the prologue's barrier).
+    const char *const c4z = reinterpret_cast<const char *>(p.c4 + (size_t)p.S * HC4_STRIDE);
+    const char *const c4l = side ? c4z : reinterpret_cast<const char *>(c4s);
+    const char *const c4r = side ? reinterpret_cast<const char *>(c4s) : c4z;
+    unsigned coff = 4u * (fcol ? (unsigned)(HC4_COL + side * HC4_CPITCH + 2 * R) : (unsigned)HC4_ZERO);   // bytes
+    const unsigned cstep = fcol ? 40u : 0u;
+    static_assert(HC4_COL - 16 >= HC4_ZERO && HC4_COL + HC4_CPITCH + 2 * (4 - 8 + 5 * HS_NS) + 1 < HC4_STRIDE, "c4 padding");
+    f32x2 ccl = *reinterpret_cast<const f32x2 *>(c4l + coff), ccr = *reinterpret_cast<const f32x2 *>(c4r + coff);
+    if (task < 100) *reinterpret_cast<f32x4 *>(crs + 4 * task) = *reinterpret_cast<const f32x4 *>(c4s + r_in * 400 + 2 * x0);
     float tv = -INFINITY;
     int tst = 0;
     f32x4 snap[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // the 8 values of the pass that holds the lane's maximum
@@ -1004,12 +1044,6 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
       stageA_pick(min(st + 1, HS_NS - 1));
       HS_STAMP(3);
       if (__builtin_amdgcn_ballot_w64(ok) != 0) {    // wave-uniform
-        // zero-padding corrections of frame pixels (global memory: requested up front, zero for the other lanes)
-        f32x2 ccol = {0.f, 0.f};
-        f32x4 crow = {0.f, 0.f, 0.f, 0.f};
-        if (fcol && ok) ccol = *reinterpret_cast<const f32x2 *>(c4s + coff);
-        const bool edge = st < 3 || st > 38;         // wave-uniform: the block may hold row 0 or row 199
-        if (edge && ok && (R == 0 || R == 199)) crow = *reinterpret_cast<const f32x4 *>(c4s + (R ? 1 : 0) * 400 + 2 * x0);
         // ---- the stencil.  Vertical first: Z[a][kx] = sum_(ky, ty) cy[a][ky][ty] V_(ky, kx)[R + ty - 1] on the four
         // columns x0 - 1 .. x0 + 2 the lane reads (two pairs); one (tap column, column pair) at a time, the 7 reads of the
         // next one requested in front of the 12 packed FMAs of this one
@@ -1065,11 +1099,17 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
           }
         }
         // frame pixels: phase (a, b) of pixel px is heat-map pixel (2 R + a, 2 x + b); the corrections are zero elsewhere
-        if (side) { o[1][1] -= ccol[0]; o[1][3] -= ccol[1]; }  // block-uniform
-        else { o[0][0] -= ccol[0]; o[0][2] -= ccol[1]; }
-        if (edge) {
-          if (st < 3) { o[0][0] -= crow[0]; o[0][1] -= crow[1]; o[1][0] -= crow[2]; o[1][1] -= crow[3]; }
-          else { o[0][2] -= crow[0]; o[0][3] -= crow[1]; o[1][2] -= crow[2]; o[1][3] -= crow[3]; }
+        o[0][0] -= ccl[0]; o[0][2] -= ccl[1];
+        o[1][1] -= ccr[0]; o[1][3] -= ccr[1];
+        // wave-uniform: the sub-steps that hold row 0 / row 199.  A bit test: written as comparisons the condition becomes
+        // a chain of scalar branches behind the stencil, and the compiler moves the stencil's FMAs behind it and all 42
+        // LDS reads in front (40 registers spilled)
+        if ((((1ull << 1) | (1ull << (HS_NS - 1))) >> st) & 1) {
+          const f32x4 cr = *reinterpret_cast<const f32x4 *>(crs + (st == 1 ? 0 : 200) + 4 * jx);
+          if (ok && (R == 0 || R == 199)) {
+            if (st == 1) { o[0][0] -= cr[0]; o[0][1] -= cr[1]; o[1][0] -= cr[2]; o[1][1] -= cr[3]; }
+            else { o[0][2] -= cr[0]; o[0][3] -= cr[1]; o[1][2] -= cr[2]; o[1][3] -= cr[3]; }
+          }
         }
         if (EXTRA && p.heat && ok) {
           float *hp = p.heat + (size_t)s * HD_PS * HD_PS + (size_t)(2 * R) * HD_PS + 2 * x0;
@@ -1098,7 +1138,9 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
       }
       HS_STAMP(2);
       R += 5;
-      coff += 10;
+      coff += cstep;
+      ccl = *reinterpret_cast<const f32x2 *>(c4l + coff);
+      ccr = *reinterpret_cast<const f32x2 *>(c4r + coff);
 #pragma unroll
       for (int dy = 0; dy < 3; dy++) {  // + 5 rows, wrapped at the ring size
         const unsigned n = q[dy] + 5 * PB;
@@ -1139,7 +1181,7 @@ int ofx_head_compact(ofx_handle *h, int S, const uint8_t *mask, int32_t *live) {
 size_t ofx_head_frame_bytes(size_t S, size_t *u2fr, size_t *vfr, size_t *c4) {
   *u2fr = 4 * S * 1600;
   *vfr = 4 * S * 7200;
-  *c4 = 4 * S * 1600;
+  *c4 = 4 * (S + 1) * HC4_STRIDE;   // + the block of zeros
   return *u2fr + *vfr + *c4;
 }
 
