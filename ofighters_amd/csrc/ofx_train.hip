@@ -545,10 +545,13 @@ __global__ __launch_bounds__(256) void t_loss_dense(size_t total, float scale, c
   if (threadIdx.x == 0) lpart[blockIdx.x] = red[0];
 }
 
-__global__ void t_adam(size_t cnt, float *w, const float *g, float *m, float *v, float lr_t, float b1, float b2, float eps) {
+// c1 = 1 - beta1 and c2 = 1 - beta2 arrive rounded from their decimal values (0.1, 0.001): formed in fp32 from the rounded
+// betas, 1.f - 0.999f is 0.000999987 - 1.3e-5 off the constant of the recurrence, 27 times what the format asks for
+__global__ void t_adam(size_t cnt, float *w, const float *g, float *m, float *v, float lr_t, float b1, float b2, float c1,
+                       float c2, float eps) {
   for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
     const float gi = g[e];
-    const float mi = b1 * m[e] + (1.f - b1) * gi, vi = b2 * v[e] + (1.f - b2) * gi * gi;
+    const float mi = b1 * m[e] + c1 * gi, vi = b2 * v[e] + c2 * gi * gi;
     m[e] = mi; v[e] = vi;
     w[e] -= lr_t * mi / (sqrtf(vi) + eps);
   }
@@ -826,7 +829,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
     const int k = conv_bn ? (t < 24 ? t % 6 : (t - 32) % 6) : -1;
     if (k == 4 || k == 5) continue;  // moving mean / variance: not trained
     K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
-      adam_v + L.offset[t], lr_t, b1, b2, 1e-7f);
+      adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
   }
   for (int i = 0; i < 4; i++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[6 * i + 4], weights + L.offset[6 * i + 5], tstat[i]);
   for (int j = 0; j < 3; j++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUO[j], weights + L.offset[32 + 6 * j + 4], weights + L.offset[32 + 6 * j + 5], ustat[j]);
@@ -1017,7 +1020,7 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
     const int k = conv_bn ? (t < 24 ? t % 6 : (t - 32) % 6) : -1;
     if (k == 4 || k == 5) continue;  // moving mean / variance: not trained
     K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
-      adam_v + L.offset[t], lr_t, b1, b2, 1e-7f);
+      adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
   }
   for (int i = 0; i < 4; i++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[6 * i + 4], weights + L.offset[6 * i + 5], tstat[i]);
   for (int j = 0; j < 3; j++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUO[j], weights + L.offset[32 + 6 * j + 4], weights + L.offset[32 + 6 * j + 5], ustat[j]);

@@ -403,6 +403,58 @@ def test_short_memories_are_not_padded_into_the_fit():
     b.close()
 
 
+@pytest.mark.parametrize("form", ["lean", "plain"])
+def test_adam_recurrence_after_the_first_step(form):
+    """Three consecutive ofx_dqn_fit calls (step = 1, 2, 3) on one small minibatch: from the second step on the decay terms
+    b1 * m and b2 * v and the bias correction of t_adam (ofx_train.hip) carry values a step-1 comparison from zero moments
+    cannot tell apart.  After every step the recurrence is evaluated in float64 from the device's OWN gradient and the
+    previous device m, v, w:
+        m = 0.9 m + 0.1 g      v = 0.999 v + 0.001 g^2      w -= lr sqrt(1 - 0.999^t) / (1 - 0.9^t) m / (sqrt(v) + 1e-7)
+    m and v are two fp32 products and a sum with rounded constants: 8 * 2^-24 of the sum of the two terms' magnitudes.
+    w: the allowance of the step-1 check of test_dqn_fit_vs_torch_autograd.  The moving BatchNorm statistics are not
+    Adam's (excluded, as there)."""
+    from ofighters_amd import DeviceBuffer, _native as nat
+    b, n, rows_d, bp_d, bn_d = _collect_minibatch(3)
+    b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
+    w0, shapes = pyoracle.policy_init(9, trained_like=True)
+    rs = np.random.RandomState(5)
+    y = DeviceBuffer(4 * n).upload(rs.uniform(-1, 2, n).astype(np.float32))
+    y2 = DeviceBuffer(4 * n).upload(rs.uniform(-1, 2, n).astype(np.float32))
+    zeros = np.zeros_like(w0)
+    w_d, m_d, v_d, g_d = (DeviceBuffer(w0.nbytes) for _ in range(4))
+    w_d.upload(w0); m_d.upload(zeros); v_d.upload(zeros)
+    lr, ulp = 1e-3, 8 * 2.0 ** -24
+    w, m, v = (a.astype(np.float64) for a in (w0, zeros, zeros))
+    for t in (1, 2, 3):
+        loss = b.dqn_fit(w_d, m_d, v_d, t, lr, n, rows_d.ptr, bp_d.ptr, y.ptr, y2.ptr, g_d)
+        assert np.isfinite(loss).all()
+        g = g_d.download(np.float32, w0.shape).astype(np.float64)
+        w1, m1, v1 = (buf.download(np.float32, w0.shape).astype(np.float64) for buf in (w_d, m_d, v_d))
+        m_ref, v_ref = 0.9 * m + 0.1 * g, 0.999 * v + 0.001 * g * g
+        w_ref = w - lr * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t) * m_ref / (np.sqrt(v_ref) + 1e-7)
+        # (+ 2^-148: below 2^-126 fp32 rounds to a fixed spacing of 2^-149, not to 2^-24 of the value - g * g underflows
+        # for the smallest gradients - and each of the three operations may lose half of that spacing)
+        m_tol = ulp * (np.abs(0.9 * m) + np.abs(0.1 * g)) + 2.0 ** -148
+        v_tol = ulp * (0.999 * v + 0.001 * g * g) + 2.0 ** -148
+        for name, (o, shp) in shapes.items():
+            c = int(np.prod(shp))
+            if name.split(".")[1] in ("mean", "var"):
+                continue
+            s = slice(o, o + c)
+            em = float((np.abs(m1[s] - m_ref[s]) / m_tol[s]).max())          # worst error, in units of its bound
+            ev = float((np.abs(v1[s] - v_ref[s]) / v_tol[s]).max())
+            ew = float(np.abs(w1[s] - w_ref[s]).max())
+            print("step %d %-5s %-18s m %.3f of its bound, v %.3f of its bound, w err %.2e" % (t, form, name, em, ev, ew))
+            assert em <= 1.0, (t, name, "adam_m: worst error, in bounds", em)
+            assert ev <= 1.0, (t, name, "adam_v: worst error, in bounds", ev)
+            assert ew <= 2e-7 + 1e-6 * float(np.abs(w[s]).max()), (t, name, "w", ew)
+        assert np.abs(g).max() > 0
+        if t > 1:                                # the decay terms are there: the moments are not a function of g alone
+            assert np.abs(m).max() > 0 and np.abs(v).max() > 0
+        w, m, v = w1, m1, v1
+    b.close()
+
+
 # ---- the lean fit in the regime it is USED in (r04): minibatches of 128 - 4096 rows -------------------------------
 # Every persistent kernel of ofx_fit.hip loops over several tiles per block there (OFX_FIT_MAX_BLOCKS = 2048, 1024 for
 # the weight-gradient kernels), the reductions go through their two-level ordered combines and f_bits_corr through its
