@@ -291,7 +291,9 @@ int ofx_policy_layout(const ofx_handle *h, ofx_policy_desc *desc_host);
  * forward; act_values float32 [N][M][2]; iaction int32 [N][M];
  * ipointer int32 [N][M][2] = (x, y) of the heat-map arg-max
  * (unravel_index(order='F'), qlearnIA_V2.py:218-220); heatmap float32
- * [N][M][W][H] or NULL (never materialised when NULL).                       */
+ * [N][M][W][H] or NULL (never materialised when NULL).  NULL iaction /
+ * ipointer: the handle keeps them for ofx_policy_explore / ofx_policy_actions /
+ * ofx_replay_capture, whatever else is called in between.                    */
 int ofx_policy_forward(ofx_handle *h, const float *weights, const uint8_t *ship_mask,
                        float *act_values, int32_t *iaction, int32_t *ipointer,
                        float *heatmap);
@@ -342,11 +344,13 @@ int ofx_set_option(ofx_handle *h, int32_t option, int32_t value);
  * and the collecting phase :393-395): for every selected ship, with probability `epsilon` - or always when
  * `collecting` != 0 - replace (iaction, ipointer) by random_play() (:317-321): iaction = randint(0, 1),
  * ipointer = (randint(0, W-1), randint(0, H-1)).  Draws: Philox4x32-10 keyed by `seed`, counter
- * (global arena, ship, tick, stream 2).  NULL iaction / ipointer = the handle's workspace results.             */
+ * (global arena, ship, tick, stream 2).  NULL iaction / ipointer = the handle's results of the last
+ * ofx_policy_forward / ofx_policy_explore.                                                                     */
 int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, uint32_t tick, int32_t collecting,
                        const uint8_t *ship_mask, int32_t *iaction, int32_t *ipointer);
 /* QlearnIA.play action packing (qlearnIA_V2.py:447-454): exactly one of
- * shoot/thrust set, pointer always set.                                      */
+ * shoot/thrust set, pointer always set.  NULL iaction / ipointer = the handle's
+ * results of the last ofx_policy_forward / ofx_policy_explore.               */
 int ofx_policy_actions(ofx_handle *h, const int32_t *iaction, const int32_t *ipointer,
                        const uint8_t *ship_mask, ofx_action *actions);
 
@@ -385,8 +389,8 @@ int ofx_replay_destroy(ofx_handle *h); /* also done by ofx_destroy            */
 /* Call once per lock-step after the action choice and BEFORE ofx_step: stores
  * the current observation maps as frame `tick` of every arena with a playing
  * agent and runs the play() bookkeeping for every ship selected by ship_mask
- * (NULL = all) with its chosen (iaction, ipointer) (NULL = the workspace
- * results of ofx_policy_forward / ofx_policy_explore).  `tick` must increase by
+ * (NULL = all) with its chosen (iaction, ipointer) (NULL = the handle's results
+ * of the last ofx_policy_forward / ofx_policy_explore).  `tick` must increase by
  * one per call and not restart at episode boundaries.                         */
 int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
                        const int32_t *ipointer);
@@ -502,8 +506,7 @@ int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const 
  * 1-bit map pairs bits[n_obs][2 (ship, laser)][W*H/32] uint32 (the layout ofx_replay_gather writes) + their toVector
  * heads vec8[n_obs][8]; every observation gets its own trunk run.  Outputs (device, any may be NULL): act_values
  * [n_obs][2], iaction [n_obs], ipointer [n_obs][2], ptr_max [n_obs] = np.max of the heat map; with probe [n_obs][2]
- * (x, y) also ptr_probe [n_obs] = the heat-map value at that pointer.  Uses the policy workspace: the (iaction,
- * ipointer) a previous ofx_policy_forward left there are gone afterwards.                                        */
+ * (x, y) also ptr_probe [n_obs] = the heat-map value at that pointer.                                            */
 int ofx_policy_forward_obs(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits, const float *vec8,
                            float *act_values, int32_t *iaction, int32_t *ipointer, float *ptr_max,
                            const int32_t *probe, float *ptr_probe);

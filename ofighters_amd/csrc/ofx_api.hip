@@ -165,7 +165,7 @@ extern "C" int ofx_destroy(ofx_handle *h) {
   ofx_state &s = h->st;
   void *ptrs[] = {s.ship_x, s.ship_y, s.ship_px, s.ship_py, s.hull, s.reward, s.score, s.obs_reward, s.last_score,
                   s.alive, s.killer, s.time, s.n_lasers, s.laser_x, s.laser_y, s.laser_dx, s.laser_dy,
-                  s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->fitws, h->fitws2, h->trunk_stat};
+                  s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->res_iaction, h->fitws, h->fitws2, h->trunk_stat};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (int t = 0; t < 5; t++) for (int w = 0; w < 2; w++) if (h->maps[t][w]) (void)hipFree(h->maps[t][w]);
   if (h->events) { (void)hipEventDestroy(h->ev0); (void)hipEventDestroy(h->ev1); }
@@ -195,14 +195,33 @@ extern "C" int ofx_set_stream(ofx_handle *h, void *stream) {
   return OFX_OK;
 }
 
-int ofx_ensure_scratch(ofx_handle *h, size_t bytes) {
-  if (h->scratch_bytes >= bytes) return OFX_OK;
+int ofx_ensure_buffer(ofx_handle *h, void **buf, size_t *have, size_t bytes) {
+  if (*have >= bytes) return OFX_OK;
   OFX_HIP(hipStreamSynchronize(h->stream));
-  if (h->scratch) (void)hipFree(h->scratch);
-  h->scratch = nullptr;
-  h->scratch_bytes = 0;
-  OFX_HIP(hipMalloc(&h->scratch, bytes));
-  h->scratch_bytes = bytes;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *have = 0;
+  OFX_HIP(hipMalloc(buf, bytes));
+  *have = bytes;
+  return OFX_OK;
+}
+int ofx_ensure_scratch(ofx_handle *h, size_t bytes) { return ofx_ensure_buffer(h, &h->scratch, &h->scratch_bytes, bytes); }
+
+int ofx_counter(ofx_handle *h, int slot, int32_t **counter) {
+  if (!h->counter) OFX_HIP(hipMalloc((void **)&h->counter, 4 * sizeof(int32_t)));
+  *counter = h->counter + slot;
+  return OFX_OK;
+}
+
+int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer) {
+  const size_t S = (size_t)h->cfg.n_arenas * h->cfg.n_ships;
+  if (!h->res_iaction) {  // one block for both; zeros until the first forward: an action packed too early is in range
+    OFX_HIP(hipMalloc((void **)&h->res_iaction, 3 * S * sizeof(int32_t)));
+    OFX_HIP(hipMemsetAsync(h->res_iaction, 0, 3 * S * sizeof(int32_t), h->stream));
+    h->res_ipointer = h->res_iaction + S;
+  }
+  *iaction = h->res_iaction;
+  *ipointer = h->res_ipointer;
   return OFX_OK;
 }
 

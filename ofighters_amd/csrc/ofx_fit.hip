@@ -29,6 +29,7 @@
 // contraction; checked against torch autograd in float64 and against the plain form (tests/test_train.py).  Per row of
 // the minibatch 9.4 MB of workspace instead of 61 MB; 4096 rows in 42 ms (r03: 66).
 #include "ofx_internal.h"
+#include "ofx_trunk.h"
 #include "ofx_fit.h"
 #include "ofx_diag.h"
 
@@ -1250,7 +1251,7 @@ __global__ __launch_bounds__(384) void f_bits_corr(int n, const uint32_t *__rest
 // z0 = conv3x3(1-bit maps) takes one of 512 values per channel and input map, so (1) its batch statistics follow from the
 // autocorrelation Cc of the shifted bit maps: sum z = M b + sum_u w_u B_u, sum z^2 = M b^2 + 2 b sum_u w_u B_u + sum_uu'
 // w_u w_u' Cc[u][u'] (exact integers times weights, in doubles); (2) pool(relu(bn(z0))) - all the second layer reads - is the
-// forward's table kernel (k_conv1_lut, ofx_policy.hip) on a table that folds the BATCH statistics; (3) the backward
+// forward's table kernel (k_conv1_lut, ofx_trunk.hip) on a table that folds the BATCH statistics; (3) the backward
 // through the pooling looks x-hat up in a second table.  The 5.12 MB per row of z0 are neither written nor read.
 // lut_y[ci][pattern][co] = scale_co sum of the set taps' weights (+ scale b + shift for ci = 0): relu(bn(z0)) = max(y, 0)
 // lut_x: the same with rs instead of scale and rs (b - mean) for ci = 0: x-hat

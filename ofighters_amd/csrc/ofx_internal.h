@@ -64,7 +64,9 @@ struct ofx_handle {
   size_t fitws_bytes;              // hipMalloc per replay cost ~60 ms of mapping: r03), grown on demand
   void *fitws2;                    // the reference form's dense targets, kept likewise
   size_t fitws2_bytes;
-  int32_t *counter;                // [4] small device counter of the fit's argument checks (allocated on first use)
+  int32_t *counter;                // [4] small device counters, one slot per user (ofx_counter; allocated on first use)
+  int32_t *res_iaction;            // [N*M]    (iaction, ipointer) of the last ofx_policy_forward / ofx_policy_explore that
+  int32_t *res_ipointer;           // [N*M][2] was given null result pointers (ofx_policy_results: one block, allocated on first use)
   float *prep;                     // prepared policy weights (BN folded, phase weights, tables): ofx_policy.hip
   float *prep_tmp;                 // the same for a blob that is not the pinned one (rebuilt per forward)
   const float *prep_pinned;        // the blob `prep` was built from while it is pinned (ofx_policy_pin_weights)
@@ -81,13 +83,18 @@ struct ofx_handle {
 // kernels / launchers implemented in the other translation units
 int ofx_launch_step(ofx_handle *h, const ofx_action *actions);
 int ofx_launch_raster(ofx_handle *h, int map_type, void *ship_map, void *laser_map);
-int ofx_ensure_scratch(ofx_handle *h, size_t bytes);
+int ofx_ensure_buffer(ofx_handle *h, void **buf, size_t *have, size_t bytes);  // a handle-kept block, grown on demand
+int ofx_ensure_scratch(ofx_handle *h, size_t bytes);   // h->scratch; transient: the next caller may overwrite or re-allocate it
+enum { OFX_COUNTER_PADS, OFX_COUNTER_FIRST_DONE };      // slots of the handle's counter block
+int ofx_counter(ofx_handle *h, int slot, int32_t **counter);
+// the handle's own (iaction [N*M], ipointer [N*M][2]): what a null result pointer of ofx_policy_forward /
+// ofx_policy_explore / ofx_policy_actions / ofx_replay_capture stands for
+int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer);
 void ofx_replay_free(ofx_handle *h);
 int ofx_replay_episode_reset(ofx_handle *h, const uint8_t *arena_mask);
 // C[M][N] = act(A[M][K] (lda) x B[K][N] (ldb) + bias[N]) on the f32 MFMA (k_gemm_f32, ofx_policy.hip)
 int ofx_launch_gemm(ofx_handle *h, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,
                     int M, int N, int K, int relu, const int32_t *live = nullptr);
-int ofx_launch_conv1_lut(ofx_handle *h, const void *bits, int n, const float *lut, float *out);  // k_conv1_lut, caller's table
 int ofx_policy_weights_updated(ofx_handle *h, const float *weights);  // the blob was changed in place (ofx_dqn_fit)
 // model.predict on n stored observations: act_values [n][2], heatmap [n][H][W], ptr_max [n] (any may be null)
 int ofx_policy_predict_obs(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits, const float *vec8,

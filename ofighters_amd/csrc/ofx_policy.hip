@@ -6,54 +6,29 @@
 // (keras/tensorflow and weights are absent), it is checked against that
 // restatement with an fp32 tolerance.
 //
+//
 // Work split (what is shared per arena):
-//   trunk   4 x [conv3x3 + BN + ReLU + maxpool2]   once per ARENA  (image is the same for its ships)
+//   trunk   4 x [conv3x3 + BN + ReLU + maxpool2]   once per ARENA  (image is the same for its ships): ofx_trunk.hip
 //   dense1  [5008 -> 100]: the 5000 trunk features once per arena on MFMA
 //           (v_mfma_f32_32x32x2_f32, exact fp32), the 8-scalar head per ship
 //   head-1  dense2 + output1 per ship (VALU, tiny)
 //   head-2  updense1 [100 -> 625] on MFMA, then 4 x [bilinear x2 + conv3x3]
-//           per ship: upconv2-4 + arg-max in the row-streaming kernel of ofx_head.hip (4-phase
-//           low-resolution form, the (400,400) heat-map is only materialised on request).
+//           per ship: upconv1 here (1 -> 2 @ 50x50, bilinear up-sampling fused into its LDS staging), upconv2-4 + arg-max
+//           in the row-streaming kernel of ofx_head.hip (4-phase low-resolution form, the (400,400) heat-map is only
+//           materialised on request).
 //
-// The convolutions run on the matrix cores (k_convm: banded GEMM; ofx_head.hip: phase-form GEMMs); conv1 reads the
-// 1-bit maps through a 512-entry table (k_conv1_lut).  k_conv is the plain VALU convolution: upconv1 (1 -> 2 @ 50x50,
-// bilinear up-sampling fused into its LDS staging) and, under OFX_OPT_TRUNK_PLAIN, the reference trunk of the
-// agreement test.  BatchNorm is folded into the conv weights by k_policy_prepare.
-#include <stdlib.h>
+// This unit: the blob and prepared-weight layouts (BatchNorm is folded into the conv weights by k_policy_prepare, for
+// the trunk and the head alike), the dense-layer kernels, the forward's driver, explore and action packing.
 #include <string.h>
-#include <type_traits>
-#include <utility>
 
 #include "ofx_internal.h"
+#include "ofx_blob.h"
+#include "ofx_trunk.h"
 #include "ofx_head.h"
-#include "ofx_diag.h"
-#include "ofx_lowp.h"
 
-#define PS 400 /* the model's fixed input side: Input((DEFAULT_WIDTH, DEFAULT_HEIGHT, 2)) */
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-static const int kTrunkCin[4] = {2, 8, 8, 8};
-static const int kUpCin[4] = {1, 2, 4, 8};
-static const int kUpCout[4] = {2, 4, 8, 1};
-
-// ---- user blob layout (identical to oracle/policy_oracle.c) -------------------
-static int policy_layout(int32_t *offset, int32_t *count) {
-  int n = 0, off = 0;
-#define T(c) do { offset[n] = off; count[n] = (c); off += (c); n++; } while (0)
-  for (int i = 0; i < 4; i++) { T(9 * kTrunkCin[i] * 8); T(8); T(8); T(8); T(8); T(8); }
-  T(5008 * 100); T(100);
-  T(100 * 50); T(50);
-  T(50 * 2); T(2);
-  T(100 * 625); T(625);
-  for (int i = 0; i < 3; i++) { int co = kUpCout[i]; T(9 * kUpCin[i] * co); T(co); T(co); T(co); T(co); T(co); }
-  T(9 * 8 * 1); T(1);
-#undef T
-  offset[n] = off;
-  return n;
-}
+// ---- user blob layout (ofx_blob.h) -------------------------------------------------
 
 extern "C" int ofx_policy_layout(const ofx_handle *h, ofx_policy_desc *desc) {
   (void)h;
@@ -265,458 +240,6 @@ __global__ void k_policy_prepare(PrepParams p) {
   }
 }
 
-// ---- generic direct 3x3 convolution ------------------------------------------------
-struct ConvParams {
-  const float *in;                 // MODE 0: planar [img][CIN][H][W]; k_upconv1: [img][625]
-  const unsigned *bits[2];         // MODE 1: word bits[ci][img * bits_stride + w], LSB-first (ch0 ship, ch1 laser)
-  size_t bits_stride;              // words between consecutive images (PS*PS/32, or twice that for interleaved maps)
-  const float *w, *b;              // folded [9][CIN][COUT], [COUT]
-  float *out;                      // planar [img][COUT][Ho][Wo] or HWC [img][Ho][Wo][COUT]
-  const uint8_t *mask;             // per image, may be null
-  const float *wbm;                // k_convm, CIN = 8: per-lane B operand [24][64] (PrepLayout::wbm)
-  int H, W;                        // conv domain (input after any upsampling) = conv output size
-  int tiles_x, tiles;              // tiles per row / per image
-  int legacy;                      // k_upconv1: TF1 legacy source mapping (src = dst / 2) instead of half-pixel centres
-  int images;                      // k_convm: number of images (the grid is padded to a multiple of 8 of them)
-  const int32_t *live;             // k_upconv1 with a mask: ordered list of the selected images (live[0] = count), else null
-  unsigned long long *stat;        // k_trunk12<0, true>: [4] M-tiles executed / all, table waves executed / all (may be null)
-};
-
-// MODE: 0 planar f32 input, 1 two 1-bit maps
-template <int CIN, int COUT, int TH, int TW, int MODE, bool POOL, bool OUT_HWC>
-__global__ __launch_bounds__(((TH / 2) * (TW / 2) + 63) / 64 * 64) void k_conv(ConvParams p) {
-  constexpr int NT = (TH / 2) * (TW / 2);
-  constexpr int NTB = (NT + 63) / 64 * 64;
-  constexpr int TWP = TW + 2;
-  __shared__ __align__(16) float tile[CIN][TH + 2][TWP];
-  const int img = blockIdx.x / p.tiles, t = blockIdx.x - img * p.tiles;
-  if (p.mask && !p.mask[img]) return;  // block-uniform
-  const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
-  const int tid = threadIdx.x;
-  const int H = p.H, W = p.W;
-
-  // ---- stage the (TH+2) x (TW+2) x CIN input patch (zero outside the image: padding 'same').
-  // Loads are issued in batches of SU before any LDS store so one memory latency covers SU elements.
-  constexpr int TOTAL = CIN * (TH + 2) * TWP;
-  constexpr int SU = 8;
-  for (int base = 0; base < TOTAL; base += NTB * SU) {
-    float vals[SU];
-#pragma unroll
-    for (int u = 0; u < SU; u++) {
-      const int e = base + u * NTB + tid;
-      float v = 0.f;
-      if (e < TOTAL) {
-        const int c = e % TWP, r = (e / TWP) % (TH + 2), ci = e / (TWP * (TH + 2));
-        const int gy = ty0 - 1 + r, gx = tx0 - 1 + c;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-          if (MODE == 0) {
-            v = p.in[(((size_t)img * CIN + ci) * H + gy) * W + gx];
-          } else if (MODE == 1) {
-            const int cell = gy * W + gx;
-            v = (float)((p.bits[ci][(size_t)img * p.bits_stride + (cell >> 5)] >> (cell & 31)) & 1u);
-          }
-        }
-      }
-      vals[u] = v;
-    }
-#pragma unroll
-    for (int u = 0; u < SU; u++) {
-      const int e = base + u * NTB + tid;
-      if (e < TOTAL) (&tile[0][0][0])[e] = vals[u];
-    }
-  }
-  __syncthreads();
-  if (tid >= NT) return;
-  const int tr = tid / (TW / 2), tc = tid - tr * (TW / 2);
-
-  float acc[2][2][COUT];
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int co = 0; co < COUT; co++) acc[i][j][co] = 0.f;
-
-#pragma unroll
-  for (int ci = 0; ci < CIN; ci++) {
-    float v[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const float2 lo = *reinterpret_cast<const float2 *>(&tile[ci][2 * tr + r][2 * tc]);
-      const float2 hi = *reinterpret_cast<const float2 *>(&tile[ci][2 * tr + r][2 * tc + 2]);
-      v[r][0] = lo.x; v[r][1] = lo.y; v[r][2] = hi.x; v[r][3] = hi.y;
-    }
-#pragma unroll
-    for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-      for (int dx = 0; dx < 3; dx++)
-#pragma unroll
-        for (int co = 0; co < COUT; co++) {
-          const float wv = p.w[((dy * 3 + dx) * CIN + ci) * COUT + co];  // wave-uniform -> scalar load
-#pragma unroll
-          for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) acc[i][j][co] = __builtin_fmaf(v[i + dy][j + dx], wv, acc[i][j][co]);
-        }
-  }
-
-  // ---- epilogue: folded bias, ReLU, optional 2x2 max-pool ----
-  const int oy = ty0 + 2 * tr, ox = tx0 + 2 * tc;
-#pragma unroll
-  for (int co = 0; co < COUT; co++) {
-    const float bias = p.b[co];
-    float o00 = fmaxf(acc[0][0][co] + bias, 0.f), o01 = fmaxf(acc[0][1][co] + bias, 0.f);
-    float o10 = fmaxf(acc[1][0][co] + bias, 0.f), o11 = fmaxf(acc[1][1][co] + bias, 0.f);
-    if (POOL) {
-      const float m = fmaxf(fmaxf(o00, o01), fmaxf(o10, o11));
-      const int Ho = H >> 1, Wo = W >> 1, py = oy >> 1, px = ox >> 1;
-      if (OUT_HWC) p.out[(((size_t)img * Ho + py) * Wo + px) * COUT + co] = m;
-      else p.out[(((size_t)img * COUT + co) * Ho + py) * Wo + px] = m;
-    } else {
-      float *o = p.out + (((size_t)img * COUT + co) * H + oy) * W + ox;
-      *reinterpret_cast<float2 *>(o) = make_float2(o00, o01);
-      *reinterpret_cast<float2 *>(o + W) = make_float2(o10, o11);
-    }
-  }
-}
-
-// max without the canonicalising v_max(x, x) the compiler puts in front of fmaxf() in IEEE mode (x is an MFMA
-// result here, never a signalling NaN): med3(x, floor, +inf).  NOT inline assembly: the compiler's hazard recogniser
-// does not look inside an asm statement, so an asm v_max placed right behind the MFMA that produces x reads the
-// register before the matrix pipe has written it (seen as wrong cells under one scheduling variant).
-// The +inf comes out of an opaque scalar move: with a literal the optimiser folds med3 back into the canonicalising max.
-__device__ __forceinline__ float max_raw(float x, float floor) {
-  float pinf;
-  asm("s_mov_b32 %0, 0x7f800000" : "=s"(pinf));
-  return __builtin_amdgcn_fmed3f(x, floor, pinf);
-}
-
-// ---- trunk convolution on the matrix cores ---------------------------------------------------------------------
-// conv3x3 (zero padding) + folded BN + ReLU + 2x2 max-pool as a GEMM whose N dimension is 8 output channels x 2
-// adjacent output rows:  D[pixel x][(co, r)] = sum_k A[x][k] B[k][(co, r)],  k = (input row 0..3, dx, ci),
-// B[k][(co, r)] = w[row - r][dx][ci][co] when 0 <= row - r <= 2, else 0  -> K = 12 CIN, 3/4 of the MACs useful, but a
-// v_mfma_f32_16x16x4_f32 retires 32 MAC/cycle against 16 for v_fmac_f32 (both share the SIMD's issue slots on gfx950,
-// tools/ubench_mix.hip), and the whole epilogue of an M-tile (2x2 pool, ReLU, store) is ~10 VALU instructions.
-// A[x][k] is gathered from an LDS copy of the input tile (one ds_read_b32 per lane per MFMA, immediate offsets);
-// the row pair of a column group shares one accumulator quad: lane (n = (co, r), kq) holds pixels 4 kq .. 4 kq + 3,
-// so the x-pool is in-lane and the y-pool is one DPP quad swap.
-// bf16 operand helpers of the opt-in OFX_OPT_POLICY_BF16 forms (k_convm, ts_gemm_phase_bf16)
-// the lane's six B operands from wbm [24][64] (value for MFMA j of the fp32 form, lane l: k = l >> 4 -> ci = (l >> 4) + 4 (j & 1), tap j >> 1)
-template <int LP>
-__device__ __forceinline__ void ts_bw_lp(const float *wbm, int n16, int kq, lp_x4 (&bwb)[6]) {
-#pragma unroll
-  for (int J = 0; J < 6; J++) {
-    const int j = 2 * (2 * J + (kq >> 1)) + (kq & 1);
-    const float *q = wbm + j * 64 + n16;
-    bwb[J] = lp_pk4<LP>(q[0], q[16], q[32], q[48]);
-  }
-}
-// MODE 0: planar f32 input [img][CIN][H][W] (the only mode left; conv1 reads the bit maps through k_conv1_lut).  Output: planar [img][8][H/2][W/2] or
-// (OUT_HWC) [img][H/2][W/2][8].  TH rows x 16 NG columns per workgroup, TH even, H % TH == 0; W is masked.
-// A workgroup walks TPW consecutive tiles of one image: the weights are fetched once, the global loads of tile i+1 are
-// in flight (in registers) while tile i computes, and the grid stays small (the dispatcher needs ~5 ns per workgroup:
-// one workgroup per tile cost 1.6 ms of launch floor for conv2 alone).
-template <int CIN, int TH, int NG, int MODE, bool OUT_HWC, int TPW, int LP = 0>
-__global__ __launch_bounds__(256) void k_convm(ConvParams p) {
-  constexpr bool BF16 = LP != 0;
-  static_assert(!BF16 || CIN == 8, "the bf16 form packs the four channels of a k-quarter");
-  constexpr int TW = 16 * NG, LS = TW + 8;  // LDS row: image column tx0 + c sits at index c + 4 (16-byte aligned interior),
-                                            // the left / right halo columns at 3 and TW + 4
-  constexpr int PLS = ((TH + 2) * LS + 63) / 64 * 64 + 16;  // plane stride = 16 mod 64: the 4 k-quarters hit different banks
-  constexpr int NK = 3 * CIN;                                // MFMAs per M-tile (K = 12 CIN)
-  constexpr int JOBS = NG * (TH / 2);
-  constexpr int ROWS = CIN * (TH + 2);
-  constexpr bool VEC = MODE == 0 && !OUT_HWC;                // rows of W floats are 16-byte aligned (W % 4 == 0)
-  __shared__ __align__(16) float tile[CIN * PLS];
-  const unsigned bid = blockIdx.x;
-  // XCD-aware order: workgroups go round-robin over the 8 XCDs (each with its own L2), so workgroup b works on image
-  // 8 (b / 8 / wpi) + b % 8: the tiles of one image run back to back on ONE XCD and the halo rows a tile shares with
-  // its vertical neighbour come out of that L2 (conv2: FETCH_SIZE 10.6 -> 5.1 GB for a 5.24 GB input; same time - the
-  // kernel is bound by its compute phase, 2.45 ms with the staging ablated, 1.19 ms with only the staging)
-  const int wpi = p.tiles / TPW, j = (int)(bid >> 3);        // p.tiles % TPW == 0: all tiles of a workgroup share the image
-  const int img = (j / wpi) * 8 + (int)(bid & 7u), t_first = (j % wpi) * TPW;
-  if (img >= p.images) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int H = p.H, W = p.W;
-  const int n16 = lane & 15, kq = lane >> 4, co = n16 >> 1, r = n16 & 1;
-
-  // B operand: the lane's column (co, r) of the banded weight matrix, rows k = 4 j + kq
-  float bw[NK];
-  int aoff[NK];  // LDS offset of A[.][4 j + kq] relative to the M-tile origin (compile-time + kq * PLS when CIN == 8)
-#pragma unroll
-  for (int j = 0; j < NK; j++) {
-    const int k = 4 * j + kq, rd = k / CIN, ci = k - rd * CIN, row = rd / 3, dx = rd - row * 3, tr = row - r;
-    if constexpr (CIN == 8) bw[j] = p.wbm[j * 64 + lane];  // pre-arranged by k_policy_prepare: one coalesced load
-    else bw[j] = (tr >= 0 && tr < 3) ? p.w[((tr * 3 + dx) * CIN + ci) * 8 + co] : 0.f;
-    aoff[j] = ci * PLS + row * LS + dx;
-  }
-  const float bias = p.b[co];
-  const f32x4 binit = {bias, bias, bias, bias};
-  // OFX_OPT_POLICY_BF16: see ts_gemm_phase_bf16 - MFMA J, element i: tap 2 J + (kq >> 1), channel 4 (kq & 1) + i
-  lp_x4 bwb[6];
-  int toff[6];
-  if constexpr (BF16) {
-    ts_bw_lp<LP ? LP : 1>(p.wbm, n16, kq, bwb);
-#pragma unroll
-    for (int J = 0; J < 6; J++) {
-      const int tap = 2 * J + (kq >> 1);
-      toff[J] = (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-    }
-  }
-  const int H2 = H >> 1, W2 = W >> 1;
-
-  // ---- staging, split into fetch (global -> registers) and commit (registers -> LDS) ----
-  constexpr int V4 = TW / 4, RPW = VEC ? (ROWS + 3) / 4 : 1;       // VEC: float4 per row, rows per wave
-  static_assert(!VEC || V4 + 2 <= 64, "tile row wider than one wave");
-  f32x4 vpre[RPW];  // native vectors: a float4 select is lowered to a pointer select + flat loads
-  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-
-  auto fetch = [&](int t) {
-    const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
-    if constexpr (VEC) {
-      // a wave moves one tile row per step: lane i < V4 the i-th float4 of the interior, lanes V4 / V4+1 the float4
-      // that holds the left / right halo column
-      const int gxl = lane < V4 ? tx0 + 4 * lane : (lane == V4 ? tx0 - 4 : tx0 + TW);
-      const bool colok = lane < V4 + 2 && gxl >= 0 && gxl < W;
-      const float *imgbase = p.in + (size_t)img * CIN * H * W;
-#pragma unroll
-      for (int u = 0; u < RPW; u++) {
-        const int rr = wv + 4 * u;
-        const int ci = rr / (TH + 2), r_ = rr - ci * (TH + 2), gy = ty0 - 1 + r_;
-        const bool rowok = rr < ROWS && gy >= 0 && gy < H;  // wave-uniform
-        // 32-bit offset from the image's base (scalar base + vector offset addressing; an image is < 4 GB)
-        const unsigned off = (unsigned)((rowok ? ci * H + gy : 0) * W + gxl);
-        vpre[u] = z4;
-        if (rowok && colok) vpre[u] = *reinterpret_cast<const f32x4 *>(imgbase + off);  // exec-masked global load
-      }
-    }
-  };
-
-  auto commit = [&](int t) {
-    const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
-    if constexpr (VEC) {
-#pragma unroll
-      for (int u = 0; u < RPW; u++) {
-        const int rr = wv + 4 * u;
-        if (rr >= ROWS) break;  // wave-uniform
-        const int ci = rr / (TH + 2), r_ = rr - ci * (TH + 2);
-        float *trow = &tile[ci * PLS + r_ * LS];
-        if (lane < V4) *reinterpret_cast<f32x4 *>(trow + 4 + 4 * lane) = vpre[u];
-        else if (lane == V4) trow[3] = vpre[u][3];
-        else if (lane == V4 + 1) trow[TW + 4] = vpre[u][0];
-      }
-    } else {  // rows that are not a multiple of 16 bytes (the 50x50 layer: W even, W <= TW): 8-byte pieces, every load of
-              // a thread in flight before the first LDS store; the halo columns are zeroed once (see below)
-      constexpr int TOTAL = CIN * (TH + 2) * (TW / 2), SU = (TOTAL + 255) / 256;
-      (void)tx0;  // one tile per image row (launch_convm checks)
-      f32x2 vals[SU];
-      const int W2c = W >> 1;
-#pragma unroll
-      for (int u = 0; u < SU; u++) {
-        const int e = u * 256 + tid;
-        const int j = e % (TW / 2), rr = (e / (TW / 2)) % (TH + 2), ci = e / ((TW / 2) * (TH + 2));
-        const int gy = ty0 - 1 + rr;
-        vals[u] = (f32x2){0.f, 0.f};
-        if (e < TOTAL && j < W2c && gy >= 0 && gy < H)
-          vals[u] = *reinterpret_cast<const f32x2 *>(p.in + (((size_t)img * CIN + ci) * H + gy) * W + 2 * j);
-      }
-#pragma unroll
-      for (int u = 0; u < SU; u++) {
-        const int e = u * 256 + tid;
-        const int j = e % (TW / 2), rr = (e / (TW / 2)) % (TH + 2), ci = e / ((TW / 2) * (TH + 2));
-        if (e < TOTAL && j <= W2c) *reinterpret_cast<f32x2 *>(&tile[ci * PLS + rr * LS + 4 + 2 * j]) = vals[u];
-      }
-    }
-  };
-
-  // A[.][4 j + kq]: with 8 input channels the (row, dx) of step j is a compile-time constant and the channel is
-  // 4 (j & 1) + kq, so every LDS read is base + immediate; with 2 channels the per-lane offsets live in registers
-  const float *abase = &tile[(CIN == 8 ? kq * PLS : 0) + n16 + 3];
-  auto aof = [&](int j) -> int {
-    if (CIN == 8) return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3);
-    return aoff[j];
-  };
-
-  auto lda = [&](const float *a, int j) -> float { return a[aof(j)]; };
-  if constexpr (!VEC) {  // left halo column (image column -1): never written by the staging above
-    for (int e = tid; e < CIN * (TH + 2); e += 256) tile[(e / (TH + 2)) * PLS + (e % (TH + 2)) * LS + 3] = 0.f;
-  }
-  fetch(t_first);
-#pragma unroll 1
-  for (int i = 0; i < TPW; i++) {
-    const int t = t_first + i;
-    const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
-    commit(t);
-    __syncthreads();
-    if (i + 1 < TPW) fetch(t + 1);
-
-    // epilogue of an M-tile: x-pool + ReLU (two v_med3), y-pool = max with the DPP quad swap [1,0,3,2] (rows r = 0 / 1
-    // sit in lanes n, n ^ 1), one 8-byte store from the r = 0 lanes
-    float *const obase = OUT_HWC ? p.out + (((size_t)img * H2 + (ty0 >> 1)) * W2 + (tx0 >> 1) + 2 * kq) * 8 + co
-                                 : p.out + (((size_t)img * 8 + co) * H2 + (ty0 >> 1)) * W2 + (tx0 >> 1) + 2 * kq;
-    auto finish = [&](const f32x4 d, int g, int tt) {
-      float q0, q1;
-      q0 = max_raw(max_raw(d[0], 0.f), d[1]);  // compiler-visible reads of the MFMA result (see max_raw)
-      q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-      q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-      q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-      const int px = ((tx0 + 16 * g) >> 1) + 2 * kq;
-      if (r == 0 && px < W2) {
-        if (OUT_HWC) {
-          float *op = obase + ((size_t)tt * W2 + 8 * g) * 8;
-          op[0] = q0;
-          if (px + 1 < W2) op[8] = q1;
-        } else {  // W2 is even here: px < W2 implies px + 1 < W2
-          *reinterpret_cast<float2 *>(obase + tt * W2 + 8 * g) = make_float2(q0, q1);
-        }
-      }
-    };
-    // two M-tiles per iteration (independent accumulator chains keep the matrix pipe busy); a trailing odd one alone
-#pragma unroll 1
-    for (int job = wv; job < JOBS; job += 8) {
-      const int job1 = job + 4;
-      const int g0 = job % NG, t0 = job / NG;
-      const float *a0 = abase + (2 * t0) * LS + 16 * g0;
-      if (job1 < JOBS) {  // wave-uniform
-        const int g1 = job1 % NG, t1 = job1 / NG;
-        const float *a1 = abase + (2 * t1) * LS + 16 * g1;
-        f32x4 d0 = binit, d1 = binit;
-        if constexpr (BF16) {
-#pragma unroll
-          for (int J = 0; J < 6; J++) {
-            const float *q0 = a0 + toff[J], *q1 = a1 + toff[J];
-            const lp_x4 A0 = lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]);
-            const lp_x4 A1 = lp_pk4<LP ? LP : 1>(q1[0], q1[PLS], q1[2 * PLS], q1[3 * PLS]);
-            d0 = lp_mfma16<LP ? LP : 1>(A0, bwb[J], d0);
-            d1 = lp_mfma16<LP ? LP : 1>(A1, bwb[J], d1);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < NK; j++) {
-            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(lda(a0, j), bw[j], d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(lda(a1, j), bw[j], d1, 0, 0, 0);
-          }
-        }
-        finish(d0, g0, t0);
-        finish(d1, g1, t1);
-      } else {
-        f32x4 d0 = binit;
-        if constexpr (BF16) {
-#pragma unroll
-          for (int J = 0; J < 6; J++) {
-            const float *q0 = a0 + toff[J];
-            d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(lda(a0, j), bw[j], d0, 0, 0, 0);
-        }
-        finish(d0, g0, t0);
-      }
-    }
-    if (i + 1 < TPW) __syncthreads();  // the next commit overwrites the tile
-  }
-}
-
-template <int CIN, int TH, int NG, int MODE, bool OUT_HWC, int TPW, int LP = 0>
-static int launch_convm(ofx_handle *h, ConvParams p, int images, int H) {
-  p.H = H; p.W = H;
-  p.tiles_x = (H + 16 * NG - 1) / (16 * NG);
-  p.tiles = p.tiles_x * (H / TH);
-  if (p.tiles % TPW) { ofx_set_error("launch_convm: %d tiles per image not divisible by %d", p.tiles, TPW); return OFX_ERR_INVALID; }
-  if (OUT_HWC && (H % 2 || H > 16 * NG)) { ofx_set_error("launch_convm: the 8-byte staging takes even rows of one tile width"); return OFX_ERR_INVALID; }
-  p.images = images;
-  hipLaunchKernelGGL((k_convm<CIN, TH, NG, MODE, OUT_HWC, TPW, LP>), dim3((unsigned)((images + 7) / 8 * 8 * (p.tiles / TPW))), dim3(256), 0,
-                     h->stream, p);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
-}
-
-// ---- conv1 on the binary observation maps as a table lookup ------------------------------------------------------
-// The two input channels are 1-bit maps, so conv3x3 of one channel at one pixel takes one of 512 values per output
-// channel: out[co] = b[co] + LUT[0][pattern0][co] + LUT[1][pattern1][co] (PrepLayout::lut1, 32 KB, staged in LDS).
-// Every pixel is evaluated (no sparsity shortcut); a thread owns one pooled output pixel = 2x2 conv outputs = a
-// 4x4 bit window per channel: 8 aligned word pairs + funnel shifts give the windows, 16 ds_read_b128 the table rows,
-// then 2x2 max-pool + ReLU and 8 coalesced stores (planar [img][8][200][200]).  ~170 VALU instructions per pooled
-// pixel against 6 MFMAs + epilogue per 16 in the GEMM form (3.4 ms): the kernel is bound by its 5.2 GB of output.
-// Input rows are re-aligned while staging: bit x + 1 of LDS row r <-> image column x of row ty0 - 1 + r (bit 0 and
-// the bits past column W-1 are the zero padding).
-template <int TH>
-__global__ __launch_bounds__(256) void k_conv1_lut(ConvParams p, const float *lut) {
-  constexpr int W = PS, H = PS, WR = 14;                       // words per staged row (402 bits)
-  constexpr int W2 = W / 2, NPX = (TH / 2) * W2;
-  __shared__ __align__(16) float slut[2 * 512 * 8];
-  __shared__ unsigned rows[2][TH + 2][WR];
-  const int tiles = H / TH;
-  const int img = blockIdx.x / tiles, ty0 = (blockIdx.x - img * tiles) * TH;
-  const int tid = threadIdx.x;
-  for (int e = tid; e < 2 * 512 * 8 / 4; e += 256)
-    reinterpret_cast<float4 *>(slut)[e] = reinterpret_cast<const float4 *>(lut)[e];
-  for (int e = tid; e < 2 * (TH + 2) * WR; e += 256) {
-    const int w = e % WR, r = (e / WR) % (TH + 2), ci = e / (WR * (TH + 2));
-    const int gy = ty0 - 1 + r;
-    unsigned out = 0u;
-    if (gy >= 0 && gy < H) {
-      // output bits b = 0..31 <-> column x = 32 w - 1 + b <-> cell gy * W + x
-      const long long s0 = (long long)gy * W + 32 * w - 1;        // cell of output bit 0 (-1 only for gy = 0, w = 0)
-      const unsigned *bits = p.bits[ci] + (size_t)img * p.bits_stride;
-      const long long sw = s0 >> 5;                               // arithmetic shift: -1 -> word -1
-      const unsigned lo = (sw >= 0 && sw < (PS * PS) >> 5) ? bits[sw] : 0u;
-      const unsigned hi = (sw + 1 < (PS * PS) >> 5) ? bits[sw + 1] : 0u;
-      out = __funnelshift_r(lo, hi, (unsigned)(s0 & 31));
-      // keep only columns 0 <= x < W of THIS row
-      const int xlo = 32 * w - 1;
-      if (xlo < 0) out &= ~1u;
-      const int over = xlo + 32 - W;                              // bits past the last column
-      if (over > 0) out = over >= 32 ? 0u : (out & (0xFFFFFFFFu >> over));
-    }
-    rows[ci][r][w] = out;
-  }
-  __syncthreads();
-  float *const obase = p.out + ((size_t)img * 8 * (H / 2) + (ty0 >> 1)) * W2;  // wave-uniform: scalar base + 32-bit offsets
-  // a thread owns FOUR horizontally adjacent pooled pixels: the kernel is bound by its 5.2 GB of output, and 16-byte
-  // stores (1 KB contiguous per wave and channel plane) use the write path better than 4-byte ones (256 B)
-  constexpr int NQ = NPX / 4, QR = W2 / 4;                       // quads of the tile, quads per pooled row
-  for (int qd = tid; qd < NQ; qd += 256) {
-    const int py = qd / QR, pq = qd - py * QR;
-    const int x0 = 8 * pq;                                        // window = staged bits x0 .. x0 + 9 of rows 2 py .. 2 py + 3
-    unsigned f[2][4];
-#pragma unroll
-    for (int ci = 0; ci < 2; ci++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const unsigned *rw = &rows[ci][2 * py + r][x0 >> 5];
-        f[ci][r] = __funnelshift_r(rw[0], rw[1], (unsigned)(x0 & 31)) & 1023u;
-      }
-    f32x4 m4[8];                                                  // [channel] = the 4 pixels
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      f32x4 acc[4][2];                                            // [2x2 pixel][channels 0-3 | 4-7]
-#pragma unroll
-      for (int ci = 0; ci < 2; ci++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const int dy = q >> 1, sh = 2 * j + (q & 1);
-          const unsigned pat = ((f[ci][dy] >> sh) & 7u) | (((f[ci][dy + 1] >> sh) & 7u) << 3) | (((f[ci][dy + 2] >> sh) & 7u) << 6);
-          const f32x4 *e = reinterpret_cast<const f32x4 *>(&slut[(ci * 512 + pat) * 8]);
-          if (ci == 0) { acc[q][0] = e[0]; acc[q][1] = e[1]; }    // the table of channel 0 carries the bias
-          else { acc[q][0] += e[0]; acc[q][1] += e[1]; }
-        }
-#pragma unroll
-      for (int co = 0; co < 8; co++) {
-        float m;  // the operands are ordinary VALU results (interlocked), not MFMA results: asm is safe here
-        asm("v_max3_f32 %0, %1, %2, 0" : "=v"(m) : "v"(acc[0][co >> 2][co & 3]), "v"(acc[1][co >> 2][co & 3]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(acc[2][co >> 2][co & 3]), "v"(acc[3][co >> 2][co & 3]), "v"(m));
-        m4[co][j] = m;
-      }
-    }
-    const unsigned off = (unsigned)(py * W2 + 4 * pq);
-#pragma unroll
-    for (int co = 0; co < 8; co++) *reinterpret_cast<f32x4 *>(obase + (size_t)co * (H / 2) * W2 + off) = m4[co];
-  }
-}
-
 // ---- upconv1 (1 -> 2 channels @ 50x50 behind a x2 bilinear up-sampling of the 25x25 dense output) --------------------
 // One workgroup per policy sample: the 625 inputs and the zero-padded up-sampled plane live in LDS (the generic k_conv
 // gathered every staged cell from global memory with four loads: 0.26 ms for 32768 ships; this form 0.22, bound by its
@@ -783,614 +306,6 @@ __global__ __launch_bounds__(256) void k_upconv1(ConvParams p) {
   }
   }  // tid < 250
   }  // work items
-}
-
-// ---- streaming trunk kernel (k_trunk12): the GEMM phase ---------------------------------------------
-// k_convm's banded GEMM over an LDS tile of RP row pairs x WD columns (planes PLS apart, rows LS apart; abase = the
-// lane's k-quarter plane at column -1 of tile row 0).  M-tiles of 16 pixels are enumerated FLAT over (row pair, column):
-// RP * WD / 16 of them, no masked columns; wave w takes tiles w, w + 16, w + 32, w + 48 as four interleaved accumulator
-// chains (a wave with three: a pair and a single).  Epilogue as k_convm: 2x2 pool + ReLU, one 8-byte store per lane to
-// orow = the lane's channel plane at the step's first pooled row (planar [.][WD/2]).
-template <int WD, int RP, int LS, int PLS>
-__device__ __forceinline__ void ts_gemm_phase(const float *abase, const float (&bw)[24], const f32x4 binit, int wv, int n16,
-                                              int kq, int r, float *orow) {
-  constexpr int NK = 24, NPX = RP * WD, NT = (NPX + 15) / 16;
-  static_assert(WD % 4 == 0 && NT <= 64, "four M-tiles per wave at most");
-  auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3); };
-  auto finish = [&](const f32x4 d, int T) {
-    float q0, q1;
-    q0 = max_raw(max_raw(d[0], 0.f), d[1]);  // compiler-visible reads of the MFMA result (see max_raw)
-    q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-    q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-    q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-    const int P = 16 * T + 4 * kq;                                 // the lane's four pixels P .. P + 3 of one row pair
-    const int rp = P / WD, x = P - rp * WD;
-    if (r == 0 && P < NPX) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(q0, q1);
-  };
-  auto a_of_tile = [&](int T) -> const float * {                   // the lane's A row: pixel 16 T + n16 (clamped past the end)
-    const int P = min(16 * T + n16, NPX - 1);
-    const int rp = P / WD, x = P - rp * WD;
-    return abase + 2 * rp * LS + x;
-  };
-  if (wv + 48 < NT) {  // all four M-tiles of the wave at once (k_trunk12: 3.0 -> 2.84 ms against two pairs)
-    const float *a0 = a_of_tile(wv), *a1 = a_of_tile(wv + 16), *a2 = a_of_tile(wv + 32), *a3 = a_of_tile(wv + 48);
-    f32x4 d0 = binit, d1 = binit, d2 = binit, d3 = binit;
-#pragma unroll
-    for (int j = 0; j < NK; j++) {
-      d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[j], d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[aof(j)], bw[j], d1, 0, 0, 0);
-      d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[aof(j)], bw[j], d2, 0, 0, 0);
-      d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[aof(j)], bw[j], d3, 0, 0, 0);
-    }
-    finish(d0, wv); finish(d1, wv + 16); finish(d2, wv + 32); finish(d3, wv + 48);
-  } else {
-#pragma unroll 1
-    for (int T = wv; T < NT; T += 32) {
-      const int T1 = T + 16;
-      const float *a0 = a_of_tile(T);
-      if (T1 < NT) {  // wave-uniform
-        const float *a1 = a_of_tile(T1);
-        f32x4 d0 = binit, d1 = binit;
-#pragma unroll
-        for (int j = 0; j < NK; j++) {
-          d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[j], d0, 0, 0, 0);
-          d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[aof(j)], bw[j], d1, 0, 0, 0);
-        }
-        finish(d0, T);
-        finish(d1, T1);
-      } else {
-        f32x4 d0 = binit;
-#pragma unroll
-        for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[j], d0, 0, 0, 0);
-        finish(d0, T);
-      }
-    }
-  }
-}
-
-// OFX_OPT_TRUNK_SPARSE (opt-in, exact): the same GEMM phase, but an M-tile whose whole input window - 4 tile rows x 18
-// columns - holds the layer's CONSTANT input (conv1 of an empty neighbourhood: every channel plane at K1[ci]) and touches
-// no zero padding stores the constant K2[co] the dense MFMA sequence gives for such a window (computed by that very
-// sequence once per workgroup: the same bits) instead of running its 24 MFMAs.  nz: per tile row 8 words, bit x set
-// <-> column x of that row is NOT known to be constant (phase A).  An M-tile that crosses from one row pair into the
-// next contains columns 199 and 0, i.e. touches the padding: only tiles inside one row pair with 1 <= x, x + 15 <= 198
-// can be constant.  top / bottom: tile row 0 / the last tile row is a padding row of the image.
-// LP != 0: the same with the 16-bit operand sequence of ts_gemm_phase_bf16 (K2 then comes from THAT sequence).
-template <int WD, int RP, int LS, int PLS, int LP>
-__device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const float (&bw)[LP ? 1 : 24], const lp_x4 (&bwb)[6],
-                                                     const f32x4 binit, int wv, int lane,
-                                                     int n16, int kq, int r, float *orow, const unsigned *nz, float k2,
-                                                     bool top, bool bottom, unsigned &n_exec, unsigned &n_all,
-                                                     unsigned long long *dbg = nullptr) {
-#if OFX_TRUNK_STAMPS
-  unsigned long long g_last = __builtin_amdgcn_s_memtime();
-#define TSG_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); dbg[i] += t_ - g_last; g_last = t_; } while (0)
-#else
-#define TSG_STAMP(i) do { } while (0)
-#endif
-  constexpr int NK = 24, NPX = RP * WD, NT = (NPX + 15) / 16;
-  auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3); };
-  int toff[6];  // LP: abase carries the fp32 form's + kq * PLS: taken out again (ts_gemm_phase_bf16)
-#pragma unroll
-  for (int J = 0; J < 6; J++) {
-    const int tap = 2 * J + (kq >> 1);
-    toff[J] = (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-  }
-  // the M-tile's matrix sequence: one or two accumulator chains
-  auto mm1 = [&](const float *a0, f32x4 &d0) {
-    if constexpr (LP != 0) {
-#pragma unroll
-      for (int J = 0; J < 6; J++) {
-        const float *q0 = a0 + toff[J];
-        d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[LP ? 0 : j], d0, 0, 0, 0);
-    }
-  };
-  auto mm2 = [&](const float *a0, const float *a1, f32x4 &d0, f32x4 &d1) {
-    if constexpr (LP != 0) {
-#pragma unroll
-      for (int J = 0; J < 6; J++) {
-        const float *q0 = a0 + toff[J], *q1 = a1 + toff[J];
-        const lp_x4 A0 = lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]);
-        const lp_x4 A1 = lp_pk4<LP ? LP : 1>(q1[0], q1[PLS], q1[2 * PLS], q1[3 * PLS]);
-        d0 = lp_mfma16<LP ? LP : 1>(A0, bwb[J], d0);
-        d1 = lp_mfma16<LP ? LP : 1>(A1, bwb[J], d1);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NK; j++) {
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[LP ? 0 : j], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[aof(j)], bw[LP ? 0 : j], d1, 0, 0, 0);
-      }
-    }
-  };
-  auto finish = [&](const f32x4 d, int T) {
-    float q0, q1;
-    q0 = max_raw(max_raw(d[0], 0.f), d[1]);
-    q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-    q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-    q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-    const int P = 16 * T + 4 * kq;
-    const int rp = P / WD, x = P - rp * WD;
-    if (r == 0 && P < NPX) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(q0, q1);
-  };
-  auto a_of_tile = [&](int T) -> const float * {
-    const int P = min(16 * T + n16, NPX - 1);
-    const int rp = P / WD, x = P - rp * WD;
-    return abase + 2 * rp * LS + x;
-  };
-  // Every wave classifies ALL the step's M-tiles by itself, lane T tile T: no list to build, no barrier.  Bit T of the
-  // mask: tile T has to run.  (A first version let a wave test its own four tiles one after the other with eight lanes each
-  // and appended to a shared list behind a barrier: 4 500 cycles per step for the classification alone, stamps.)
-  unsigned long long run_mask;
-  {
-    const int T = lane, P = 16 * T, rp = P / WD, x = P - rp * WD;
-    bool run = T < NT;
-    if (run && !(x < 1 || x + 15 > WD - 2 || P + 15 >= NPX || (top && rp == 0) || (bottom && rp == RP - 1))) {
-      // window = bits x - 1 .. x + 16 of tile rows 2 rp .. 2 rp + 3: two words per row
-      const int w0 = (x - 1) >> 5, lo = (x - 1) & 31;
-      const unsigned m0 = 0x3FFFFu << lo, m1 = lo + 18 > 32 ? (1u << (lo + 18 - 32)) - 1u : 0u;
-      unsigned any = 0u;
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) {
-        const unsigned *rw = nz + (2 * rp + rr) * 8 + w0;
-        any |= (rw[0] & m0) | (rw[1] & m1);
-      }
-      run = any != 0u;
-    }
-    run_mask = __builtin_amdgcn_ballot_w64(run);
-  }
-  auto store_const = [&](int T) {                                          // the constant tile: the dense result, stored
-    const int P = 16 * T + 4 * kq, rp = P / WD, x = P - rp * WD;
-    if (r == 0) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(k2, k2);
-  };
-  auto run1 = [&](int T0) {
-    f32x4 d0 = binit;
-    mm1(a_of_tile(T0), d0);
-    finish(d0, T0);
-  };
-  // the wave's own four tiles: the constant ones are stored; then the RUN tiles are dealt out over all 16 waves - wave w
-  // takes the w-th, (w + 16)-th, ... set bit of the mask (a tile's result does not depend on who computes it)
-#pragma unroll 1
-  for (int T = wv; T < NT; T += 16)
-    if (!((run_mask >> T) & 1ull)) store_const(T);
-  if (wv == 0) { n_all += (unsigned)NT; n_exec += (unsigned)__builtin_popcountll(run_mask); }
-  TSG_STAMP(0);
-  unsigned long long m = run_mask;
-  for (int i = 0; i < wv && m; i++) m &= m - 1;                             // skip the bits of the waves in front
-#pragma unroll 1
-  while (m) {
-    const int T0 = __builtin_ctzll(m);
-    unsigned long long m2 = m;
-    for (int i = 0; i < 16 && m2; i++) m2 &= m2 - 1;                        // 16 set bits further on: this wave's next tile
-    if (m2) {                                                               // two accumulator chains
-      const int T1 = __builtin_ctzll(m2);
-      f32x4 d0 = binit, d1 = binit;
-      mm2(a_of_tile(T0), a_of_tile(T1), d0, d1);
-      finish(d0, T0);
-      finish(d1, T1);
-      for (int i = 0; i < 16 && m2; i++) m2 &= m2 - 1;
-    } else run1(T0);
-    m = m2;
-  }
-  TSG_STAMP(2);
-}
-
-// OFX_OPT_POLICY_BF16 (opt-in): the same banded GEMM on v_mfma_f32_16x16x16_bf16 - K = 96 as 6 MFMAs of K = 16 instead
-// of 24 of K = 4.  MFMA J, lane (pixel n16, k-quarter kq), element i: k <-> (tap = 2 J + (kq >> 1), ci = 4 (kq & 1) + i):
-// the A operand is the four channel planes 4 (kq & 1) .. + 3 at the tap's (row, dx) of the fp32 LDS tile, rounded to
-// bf16 on the way in (one address per J: lane-constant tap offset, planes by immediate); the B operand is packed once
-// from the same PrepLayout::wbm the fp32 kernel uses.  fp32 accumulation, same epilogue.
-template <int WD, int RP, int LS, int PLS, int LP>
-__device__ __forceinline__ void ts_gemm_phase_bf16(const float *abase, const lp_x4 (&bwb)[6], const f32x4 binit, int wv, int n16,
-                                                   int kq, int r, float *orow) {
-  constexpr int NPX = RP * WD, NT = (NPX + 15) / 16;
-  static_assert(WD % 4 == 0 && NT <= 64, "four M-tiles per wave at most");
-  int toff[6];  // abase carries the fp32 form's + kq * PLS: taken out again
-#pragma unroll
-  for (int J = 0; J < 6; J++) {
-    const int tap = 2 * J + (kq >> 1);
-    toff[J] = (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-  }
-  auto finish = [&](const f32x4 d, int T) {
-    float q0, q1;
-    q0 = max_raw(max_raw(d[0], 0.f), d[1]);
-    q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-    q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-    q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-    const int P = 16 * T + 4 * kq;
-    const int rp = P / WD, x = P - rp * WD;
-    if (r == 0 && P < NPX) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(q0, q1);
-  };
-  auto a_of_tile = [&](int T) -> const float * {
-    const int P = min(16 * T + n16, NPX - 1);
-    const int rp = P / WD, x = P - rp * WD;
-    return abase + 2 * rp * LS + x;
-  };
-#pragma unroll 1
-  for (int T = wv; T < NT; T += 32) {  // two M-tiles at a time: two accumulator chains
-    const int T1 = T + 16;
-    const bool two = T1 < NT;          // wave-uniform
-    const float *a0 = a_of_tile(T), *a1 = a_of_tile(two ? T1 : T);
-    f32x4 d0 = binit, d1 = binit;
-#pragma unroll
-    for (int J = 0; J < 6; J++) {
-      const float *q0 = a0 + toff[J], *q1 = a1 + toff[J];
-      const lp_x4 A0 = lp_pk4<LP>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]);
-      const lp_x4 A1 = lp_pk4<LP>(q1[0], q1[PLS], q1[2 * PLS], q1[3 * PLS]);
-      d0 = lp_mfma16<LP>(A0, bwb[J], d0);
-      d1 = lp_mfma16<LP>(A1, bwb[J], d1);
-    }
-    finish(d0, T);
-    if (two) finish(d1, T1);
-  }
-}
-
-// ---- conv1 -> conv2 fused: the 5.2 GB pooled conv1 activation never exists -----------------------------------------
-// One 1024-thread workgroup walks ONE image top to bottom in 20 steps of F12_TH = 10 conv2 rows.  Per step:
-//   phase A (all threads, VALU + LDS): the table form of conv1 (see k_conv1_lut) for the 10 NEW rows of p1 = pool(relu(
-//            bn(conv1))) - a thread owns two adjacent p1 pixels, 1000 of the 1024 threads busy - written straight into
-//            the planar LDS tile the GEMM reads (rows R0 - 1 .. R0 + 10 of p1, zero outside the image);
-//   phase B (MFMA): conv2 as k_convm's banded GEMM on that tile, M-tiles of 16 pixels enumerated FLAT over the 5 row
-//            pairs x 200 columns (62.5 M-tiles: no masked columns), 4 per wave as four accumulator chains; the global loads of
-//            the next step's bit rows are in flight meanwhile;
-//            (the step's last two p1 rows are also kept aside: they are the first two tile rows of the next step).
-// Separating the phases in time costs little as long as each phase has its four waves per SIMD busy; one workgroup per CU.
-// (r03: a form with two half-workgroups in anti-phase, 8 table waves beside 8 GEMM waves on two images, took 3.19 ms
-// against 2.83 ms - measured on the chip and removed again, DESIGN.md section 3.  MFMA and VALU instructions share one
-// issue port per SIMD and a matrix wave with MFMAs queued starves the vector instructions of the waves beside it
-// (tools/ubench_coexec.hip, fixed-window form); the table phase is also one chain of LDS latencies of ~8 400 cycles
-// per WAVE whatever the number of waves, so halving the table waves halves the table throughput.)
-// Output = k_convm's: planar [img][8][100][100].
-constexpr int F12_TH = 10, F12_LS = 216, F12_ROWS = F12_TH + 2;
-constexpr int F12_PLS = (F12_ROWS * F12_LS + 63) / 64 * 64 + 16;  // plane stride = 16 mod 64, as k_convm
-constexpr int F12_WR = 14, F12_BR = 2 * (F12_TH + 1) + 2;         // words per staged bit row; bit rows of the first step
-constexpr int F12_THREADS = 1024;
-static_assert(F12_PLS % 64 == 16 && F12_PLS % 4 == 0 && F12_LS % 4 == 0, "tile layout");
-static_assert(2 * F12_BR * F12_WR <= F12_THREADS, "one staged word per thread");
-static_assert((F12_TH + 1) * 100 <= 2 * F12_THREADS && F12_TH * 100 <= F12_THREADS, "pixel pairs per step");
-
-// SPARSE (OFX_OPT_TRUNK_SPARSE, opt-in, fp32 only): the two input planes are ~1 % set bits (lib/observation.py:79-95), so
-// most of conv1's output is ONE value per channel - K1[c] = relu(bn(conv1(empty window))), table pattern 0 - and most
-// of conv2's M-tiles multiply that constant.  Exact: a wave whose 64 pixel pairs all see empty 4 x 6 bit windows writes
-// K1 instead of reading its 16 table rows per pixel (the same sum of the same two table entries), every other pixel
-// pair marks its two columns in a per-row bit map, and the GEMM phase skips M-tiles whose whole window is unmarked and
-// away from the padding (ts_gemm_phase_sparse).  Bit-identical to the dense kernel (tests/test_gpu_policy.py).
-template <int LP, bool SPARSE = false>
-__global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const float *lut) {
-  constexpr bool BF16 = LP != 0;
-  constexpr int W = PS, H = PS, H1 = PS / 2, H2 = PS / 4, LS = F12_LS, PLS = F12_PLS, NK = 24;
-  __shared__ __align__(16) float slut[2 * 512 * 8];
-  __shared__ __align__(16) float tile[8 * F12_PLS];
-  __shared__ unsigned rows[2][2][F12_BR][F12_WR];  // [buffer][channel][bit row][word]
-  __shared__ __align__(16) float halo[2][8][2][F12_LS];  // the last two p1 rows of a step = the first two of the next
-  __shared__ unsigned nz[SPARSE ? 2 : 1][F12_ROWS][8];   // SPARSE: [buffer][tile row]: bit x <-> column x may differ from K1
-  __shared__ __align__(16) float k1s[8], k2s[8];         // SPARSE: the constants of an empty neighbourhood
-  // SPARSE (fp32): the 24 B operands of a lane are re-read from here in every phase B instead of living in registers
-  // through phase A - with them the loop spilled, and every spill reload is an s_waitcnt vmcnt(0), i.e. a wait for the bit
-  // rows in flight and for the stores' acknowledgements (stamps: 3 400 of a step's 13 700 cycles in front of phase A's
-  // barrier, 5 000 behind the last M-tile)
-  __shared__ float wbs[(SPARSE && !BF16) ? 24 * 64 : 1];
-  unsigned n_exec = 0, n_all = 0, t_exec = 0, t_all = 0; // SPARSE: the wave's counts (M-tiles run / all, table passes run / all)
-#if OFX_TRUNK_STAMPS
-  unsigned long long st_a = 0, st_b = 0, st_last = __builtin_amdgcn_s_memtime(), st_begin = st_last, st_g[3] = {0, 0, 0};
-#define T12_STAMP(acc) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc += t_ - st_last; st_last = t_; } while (0)
-#else
-#define T12_STAMP(acc) do { } while (0)
-#endif
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n16 = lane & 15, kq = lane >> 4, co = n16 >> 1, r = n16 & 1;
-
-  // bit rows of the p1 rows [pa, pb): image rows 2 pa - 1 .. 2 pb, re-aligned like k_conv1_lut (bit x + 1 of a staged
-  // row <-> image column x; bit 0 and the bits past column W - 1 are the zero padding).  One word per thread.
-  auto bits_fetch = [&](int img, int pa, int pb) -> unsigned {
-    const int nrows = 2 * (pb - pa) + 2;
-    unsigned out = 0u;
-    if (tid < 2 * nrows * F12_WR) {
-      const int w = tid % F12_WR, rr = (tid / F12_WR) % nrows, ci = tid / (F12_WR * nrows);
-      const int gy = 2 * pa - 1 + rr;
-      if (gy >= 0 && gy < H) {
-        const long long s0 = (long long)gy * W + 32 * w - 1;      // cell of output bit 0 (-1 only for gy = 0, w = 0)
-        const unsigned *bits = p.bits[ci] + (size_t)img * p.bits_stride;
-        const long long sw = s0 >> 5;                             // arithmetic shift: -1 -> word -1
-        const unsigned lo = (sw >= 0 && sw < (PS * PS) >> 5) ? bits[sw] : 0u;
-        const unsigned hi = (sw + 1 < (PS * PS) >> 5) ? bits[sw + 1] : 0u;
-        out = __funnelshift_r(lo, hi, (unsigned)(s0 & 31));
-        const int xlo = 32 * w - 1;
-        if (xlo < 0) out &= ~1u;
-        const int over = xlo + 32 - W;                            // bits past the last column
-        if (over > 0) out = over >= 32 ? 0u : (out & (0xFFFFFFFFu >> over));
-      }
-    }
-    return out;
-  };
-  auto bits_commit = [&](int buf, int pa, int pb, unsigned word) {
-    const int nrows = 2 * (pb - pa) + 2;
-    if (tid < 2 * nrows * F12_WR) {
-      const int w = tid % F12_WR, rr = (tid / F12_WR) % nrows, ci = tid / (F12_WR * nrows);
-      rows[buf][ci][rr][w] = word;
-    }
-  };
-
-  // ---- prologue: table, weights, zeroed tile (halo columns and the row above the image stay zero), first bit rows ----
-  for (int e = tid; e < 2 * 512 * 8 / 4; e += F12_THREADS)
-    reinterpret_cast<f32x4 *>(slut)[e] = reinterpret_cast<const f32x4 *>(lut)[e];
-  for (int e = tid; e < 8 * PLS / 4; e += F12_THREADS) reinterpret_cast<f32x4 *>(tile)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int e = tid; e < 2 * 8 * 2 * LS / 4; e += F12_THREADS) reinterpret_cast<f32x4 *>(&halo[0][0][0][0])[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bw[(BF16 || SPARSE) ? 1 : NK];
-  lp_x4 bwb[6];
-  if constexpr (BF16) ts_bw_lp<LP ? LP : 1>(p.wbm, n16, kq, bwb);
-  else if constexpr (SPARSE) {
-    for (int e = tid; e < NK * 64; e += F12_THREADS) wbs[e] = p.wbm[e];
-  } else {
-#pragma unroll
-    for (int j = 0; j < NK; j++) bw[j] = p.wbm[j * 64 + lane];   // per-lane B operand of k_convm (PrepLayout::wbm)
-  }
-  const float bias = p.b[co];
-  const f32x4 binit = {bias, bias, bias, bias};
-  const float *abase = &tile[kq * PLS + 3];
-  if constexpr (SPARSE) {
-    // K1: the table form's value for pattern 0 in both channels (the max of four equal sums and 0); K2: conv2 + pool + ReLU
-    // of a window of K1 planes, through the kernel's own MFMA sequence on a tile filled with them
-    __syncthreads();                                               // slut stands
-    if (tid < 8) k1s[tid] = fmaxf(slut[tid] + slut[512 * 8 + tid], 0.f);
-    for (int e = tid; e < 2 * F12_ROWS * 8; e += F12_THREADS) (&nz[0][0][0])[e] = 0u;
-    __syncthreads();
-    for (int e = tid; e < 8 * PLS; e += F12_THREADS) tile[e] = k1s[min(e / PLS, 7)];
-    __syncthreads();
-    if (wv == 0) {
-      const float *a0 = abase + 2 * LS + 16 + n16;                 // any interior M-tile: row pair 1, columns 16 .. 31
-      f32x4 d0 = binit;
-      if constexpr (BF16) {
-#pragma unroll
-        for (int J = 0; J < 6; J++) {
-          const int tap = 2 * J + (kq >> 1);
-          const float *q0 = a0 + (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-          d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-        }
-      } else {
-        auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3); };
-#pragma unroll
-        for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], wbs[(BF16 ? 0 : j) * 64 + lane], d0, 0, 0, 0);
-      }
-      float q0 = max_raw(max_raw(d0[0], 0.f), d0[1]);
-      q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-      if (r == 0 && kq == 0) k2s[co] = q0;
-    }
-    __syncthreads();
-    for (int e = tid; e < 8 * PLS / 4; e += F12_THREADS) reinterpret_cast<f32x4 *>(tile)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  bits_commit(0, 0, F12_TH + 1, bits_fetch((int)blockIdx.x, 0, F12_TH + 1));
-  unsigned w_ahead = 0u;                                // SPARSE: the bit rows of the step after next, in flight
-  if constexpr (SPARSE) { if ((int)blockIdx.x < p.images) w_ahead = bits_fetch((int)blockIdx.x, F12_TH + 1, 2 * F12_TH + 1); }
-  __syncthreads();
-  const float k2 = SPARSE ? k2s[co] : 0.f;
-
-  // persistent: a workgroup takes images blockIdx.x, blockIdx.x + gridDim.x, ... (table, weights and the zero frame of
-  // the tile are set up once; the first bit rows of the next image are fetched under the last step of this one)
-#pragma unroll 1
-  for (int img = (int)blockIdx.x; img < p.images; img += (int)gridDim.x)
-#pragma unroll 1
-  for (int step = 0; step < H1 / F12_TH; step++) {
-    const int R0 = step * F12_TH;                                  // first conv2 row of the step
-    // new p1 rows [pa, pb) -> tile rows pa - (R0 - 1) ..; the first step also makes row 0 (its row -1 is the zero row),
-    // the last one leaves row 200 zero
-    const int pa = step ? R0 + 1 : 0, pb = min(R0 + F12_TH + 1, H1);
-    const int buf = step & 1;
-    // the next step's bit rows (of the workgroup's next image behind the last step)
-    const bool last = step + 1 == H1 / F12_TH;
-    const int nimg = last ? img + (int)gridDim.x : img;
-    const bool more = nimg < p.images;
-    const int na = last ? 0 : R0 + F12_TH + 1, nb = last ? F12_TH + 1 : min(R0 + 2 * F12_TH + 1, H1);
-    unsigned nextw = 0u;
-    T12_STAMP(st_b);
-    // ---- phase A: conv1 table look-up + pool + ReLU, two adjacent p1 pixels per thread ----
-    if (step && pb - pa < F12_TH)  // last step: p1 row 200 does not exist - the tile row behind the image is zero
-      for (int e = tid; e < 8 * LS; e += F12_THREADS) tile[(e / LS) * PLS + (F12_TH + 1) * LS + e % LS] = 0.f;
-    if (!step)  // the row above the image
-      for (int e = tid; e < 8 * LS; e += F12_THREADS) tile[(e / LS) * PLS + e % LS] = 0.f;
-    if (step && tid < 8 * 2 * (LS / 4)) {  // rows R0 - 1, R0: kept by the previous step (nobody reads the tile in phase A)
-      const int c4 = tid % (LS / 4), rr = (tid / (LS / 4)) & 1, ci = tid / (2 * (LS / 4));
-      reinterpret_cast<f32x4 *>(&tile[ci * PLS + rr * LS])[c4] = reinterpret_cast<const f32x4 *>(&halo[buf][ci][rr][0])[c4];
-    }
-    if constexpr (SPARSE) {  // ... and their column marks (the rows this step writes start at tile row 2: no overlap)
-      if (step && tid < 16) nz[buf][tid >> 3][tid & 7] = nz[buf ^ 1][F12_TH + (tid >> 3)][tid & 7];
-    }
-    for (int q = tid; q < (pb - pa) * 100; q += F12_THREADS) {
-      const int py = q / 100, pp = q - py * 100;
-      const int x0 = 4 * pp;                                       // window = staged bits x0 .. x0 + 5 of rows 2 py .. 2 py + 3
-      unsigned f[2][4];
-#pragma unroll
-      for (int ci = 0; ci < 2; ci++)
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-          const unsigned *rw = &rows[buf][ci][2 * py + rr][x0 >> 5];
-          f[ci][rr] = __funnelshift_r(rw[0], rw[1], (unsigned)(x0 & 31)) & 63u;
-        }
-      float m2[8][2];
-      bool dense_pass = true;
-      if constexpr (SPARSE) {
-        const unsigned any = (f[0][0] | f[0][1] | f[0][2] | f[0][3]) | (f[1][0] | f[1][1] | f[1][2] | f[1][3]);
-        dense_pass = __builtin_amdgcn_ballot_w64(any != 0u) != 0;  // wave-uniform
-        t_all++;
-        if (dense_pass) {
-          t_exec++;
-          if (any != 0u) atomicOr(&nz[buf][pa + py - (R0 - 1)][(2 * pp) >> 5], 3u << ((2 * pp) & 31));  // columns 2 pp, 2 pp + 1: an even bit and its neighbour
-        } else {
-          const f32x4 ka = *reinterpret_cast<const f32x4 *>(&k1s[0]), kb = *reinterpret_cast<const f32x4 *>(&k1s[4]);
-#pragma unroll
-          for (int c = 0; c < 8; c++) m2[c][0] = m2[c][1] = c < 4 ? ka[c & 3] : kb[c & 3];
-        }
-      }
-      if (dense_pass) {
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        f32x4 acc[4][2];                                           // [2x2 pixel][channels 0-3 | 4-7]
-#pragma unroll
-        for (int ci = 0; ci < 2; ci++)
-#pragma unroll
-          for (int qq = 0; qq < 4; qq++) {
-            const int dy = qq >> 1, sh = 2 * j + (qq & 1);
-            const unsigned pat = ((f[ci][dy] >> sh) & 7u) | (((f[ci][dy + 1] >> sh) & 7u) << 3) | (((f[ci][dy + 2] >> sh) & 7u) << 6);
-            const f32x4 *e = reinterpret_cast<const f32x4 *>(&slut[(ci * 512 + pat) * 8]);
-            if (ci == 0) { acc[qq][0] = e[0]; acc[qq][1] = e[1]; }  // the table of channel 0 carries the bias
-            else { acc[qq][0] += e[0]; acc[qq][1] += e[1]; }
-          }
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-          float m;  // the operands are ordinary VALU results (interlocked), not MFMA results: asm is safe here
-          asm("v_max3_f32 %0, %1, %2, 0" : "=v"(m) : "v"(acc[0][c >> 2][c & 3]), "v"(acc[1][c >> 2][c & 3]));
-          asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(acc[2][c >> 2][c & 3]), "v"(acc[3][c >> 2][c & 3]), "v"(m));
-          m2[c][j] = m;
-        }
-      }
-      }  // dense_pass
-      const int trow = pa + py - (R0 - 1);
-      float *dst = &tile[trow * LS + 4 + 2 * pp];
-#pragma unroll
-      for (int c = 0; c < 8; c++) *reinterpret_cast<float2 *>(dst + c * PLS) = make_float2(m2[c][0], m2[c][1]);
-      if (trow >= F12_TH) {  // also the next step's first two rows
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-          *reinterpret_cast<float2 *>(&halo[buf ^ 1][c][trow - F12_TH][4 + 2 * pp]) = make_float2(m2[c][0], m2[c][1]);
-      }
-    }
-    __syncthreads();
-
-    T12_STAMP(st_a);
-    // ---- phase B: conv2 on the tile; the next step's bit rows are fetched meanwhile ----
-    if constexpr (!SPARSE) { if (more) nextw = bits_fetch(nimg, na, nb); }
-    // SPARSE: the bit rows travel TWO steps ahead.  The dense GEMM phase hides the ~2 us of a fetch issued at its start;
-    // the sparse step is over before the word lands.  Here, BETWEEN the two phases, the word fetched a whole step ago is
-    // committed (the next step's rows) and the step after that is requested: the wait for the word is a vmcnt(0), which
-    // also waits for every p2 store in flight - at the top of the step those are the stores the previous GEMM phase has
-    // just issued (stamps: 5 000 of a step's 12 700 cycles went there), behind phase A they are a table phase old.
-    if constexpr (SPARSE) {
-      if (more) bits_commit(buf ^ 1, na, nb, w_ahead);
-      int i2 = nimg, s2 = last ? 0 : step + 1;
-      if (++s2 == H1 / F12_TH) { s2 = 0; i2 += (int)gridDim.x; }
-      const int r2 = s2 * F12_TH;
-      w_ahead = i2 < p.images ? bits_fetch(i2, s2 ? r2 + 1 : 0, min(r2 + F12_TH + 1, H1)) : 0u;
-    }
-
-    if constexpr (SPARSE) {
-      float bwl[BF16 ? 1 : NK];
-      if constexpr (!BF16) {
-        int zoff;                                   // an offset the compiler cannot see through: the reads stay in the loop
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zoff));
-#pragma unroll
-        for (int j = 0; j < NK; j++) bwl[j] = wbs[j * 64 + lane + zoff];
-      }
-      ts_gemm_phase_sparse<200, F12_TH / 2, F12_LS, F12_PLS, LP>(abase, bwl, bwb, binit, wv, lane, n16, kq, r,
-                                                                  p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2,
-                                                                  &nz[buf][0][0], k2, step == 0, last, n_exec, n_all
-#if OFX_TRUNK_STAMPS
-                                                                  , st_g
-#endif
-                                                                  );
-      // the other buffer's marks are last step's: cleared for the next step (its first two rows are copied in there)
-      for (int e = tid; e < F12_ROWS * 8; e += F12_THREADS) (&nz[buf ^ 1][0][0])[e] = 0u;
-    } else if constexpr (BF16)
-      ts_gemm_phase_bf16<200, F12_TH / 2, F12_LS, F12_PLS, LP ? LP : 1>(abase, bwb, binit, wv, n16, kq, r,
-                                                            p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
-    else
-      ts_gemm_phase<200, F12_TH / 2, F12_LS, F12_PLS>(abase, bw, binit, wv, n16, kq, r,
-                                                       p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
-    if constexpr (!SPARSE) { if (more) bits_commit(buf ^ 1, na, nb, nextw); }  // the other buffer: phase A of this step is behind every wave
-    __syncthreads();
-  }
-  if constexpr (SPARSE) {
-#if OFX_TRUNK_STAMPS
-    T12_STAMP(st_b);
-    if (p.stat && tid == 0) {   // diagnostic: cycles of wave 0 in phase A (up to its barrier) / phase B / whole kernel / blocks
-      atomicAdd(&p.stat[0], st_a); atomicAdd(&p.stat[1], st_b);          // phase A (with its barrier) / the rest of the step
-      atomicAdd(&p.stat[2], st_g[0]); atomicAdd(&p.stat[3], st_g[2]);    // of that: classification + constant stores / the run tiles
-    }
-#else
-    if (p.stat && lane == 0) {
-      atomicAdd(&p.stat[0], (unsigned long long)n_exec); atomicAdd(&p.stat[1], (unsigned long long)n_all);
-      atomicAdd(&p.stat[2], (unsigned long long)t_exec); atomicAdd(&p.stat[3], (unsigned long long)t_all);
-    }
-#endif
-  }
-}
-
-// ---- conv3 as a streaming kernel: k_trunk12's GEMM phase on tiles that arrive by LDS-direct loads --------------------
-// Planar f32 input [img][8][100][100] -> planar [img][8][50][50].  One persistent 1024-thread workgroup per CU walks an
-// image in 5 steps of 20 rows over TWO tiles (8 planes x 22 rows x 108 floats each, 157 KB): while the GEMM phase
-// (ts_gemm_phase: 10 row pairs x 100 columns = 62.5 M-tiles, four chains per wave) runs on one, the 22 rows of the next
-// step land in the other by global_load_lds_dwordx4 - no staging registers (a register prefetch of 20 rows spills next
-// to four accumulator chains), no LDS store instructions.  An LDS-direct load writes lane l's 16 bytes at base + 16 l, so a
-// plane is filled front to back in pieces of 64 float4: lane q of a plane -> (row q / 27, float4 q % 27); float4 0 and
-// 26 of a row (the halo columns) and the rows outside the image read 16 zero bytes instead (PrepLayout::zero16).
-constexpr int C3_W = 100, C3_TH = 20, C3_LS = 108, C3_ROWS = C3_TH + 2, C3_F4 = C3_LS / 4;
-constexpr int C3_PLS = (C3_ROWS * C3_LS + 63) / 64 * 64 + 16;
-constexpr int C3_PF4 = C3_ROWS * C3_F4, C3_NI = (C3_PF4 + 63) / 64;  // float4 of a plane, wave-instructions per plane
-static_assert(C3_PLS % 64 == 16 && C3_W % C3_TH == 0 && C3_W / 4 + 2 == C3_F4 && 64 * C3_NI * 4 <= C3_PLS + 64 * 4, "tile layout");
-static_assert(2 * 8 * C3_PLS * 4 <= 160 * 1024, "two tiles in LDS");
-
-template <int LP>
-__global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, const float *zero16) {
-  constexpr bool BF16 = LP != 0;
-  constexpr int W = C3_W, H = C3_W, H2 = C3_W / 2, PLS = C3_PLS, NK = 24, STEPS = H / C3_TH;
-  __shared__ __align__(16) float tiles[2][8 * C3_PLS];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n16 = lane & 15, kq = lane >> 4, co = n16 >> 1, r = n16 & 1;
-
-  // rows R0 - 1 .. R0 + C3_TH of image img -> tiles[buf]; 80 wave-instructions spread over the 16 waves
-  auto stage = [&](int buf, int img, int R0) {
-#pragma unroll 1
-    for (int i = wv; i < 8 * C3_NI; i += F12_THREADS / 64) {
-      const int ci = i / C3_NI, k = i - ci * C3_NI;
-      const int q = 64 * k + lane;
-      if (q < C3_PF4) {
-        const int row = q / C3_F4, c4 = q - row * C3_F4, gy = R0 - 1 + row;
-        const float *src = zero16;
-        if (c4 >= 1 && c4 <= W / 4 && gy >= 0 && gy < H) src = p.in + (((size_t)img * 8 + ci) * H + gy) * W + 4 * (c4 - 1);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                         (__attribute__((address_space(3))) void *)&tiles[buf][ci * PLS + 256 * k], 16, 0, 0);
-      }
-    }
-  };
-
-  float bw[BF16 ? 1 : NK];
-  lp_x4 bwb[6];
-  if constexpr (BF16) ts_bw_lp<LP ? LP : 1>(p.wbm, n16, kq, bwb);
-  else {
-#pragma unroll
-    for (int j = 0; j < NK; j++) bw[j] = p.wbm[j * 64 + lane];
-  }
-  const float bias = p.b[co];
-  const f32x4 binit = {bias, bias, bias, bias};
-  if ((int)blockIdx.x < p.images) stage(0, (int)blockIdx.x, 0);
-  // the LDS-direct loads are published to the other waves by vmcnt(0) BEFORE the barrier: the memory model only
-  // promises lgkmcnt(0) at a workgroup fence, so the wait is written out rather than left to the compiler
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-  __syncthreads();
-  int buf = 0;
-#pragma unroll 1
-  for (int img = (int)blockIdx.x; img < p.images; img += (int)gridDim.x)
-#pragma unroll 1
-  for (int step = 0; step < STEPS; step++) {
-    const int R0 = step * C3_TH;
-    const bool last = step + 1 == STEPS;
-    const int nimg = last ? img + (int)gridDim.x : img;
-    if (nimg < p.images) stage(buf ^ 1, nimg, last ? 0 : R0 + C3_TH);
-    if constexpr (BF16)
-      ts_gemm_phase_bf16<W, C3_TH / 2, C3_LS, C3_PLS, LP ? LP : 1>(&tiles[buf][kq * PLS + 3], bwb, binit, wv, n16, kq, r,
-                                                      p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
-    else
-      ts_gemm_phase<W, C3_TH / 2, C3_LS, C3_PLS>(&tiles[buf][kq * PLS + 3], bw, binit, wv, n16, kq, r,
-                                                 p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's LDS-direct loads have landed (see above)
-    __syncthreads();
-    buf ^= 1;
-  }
 }
 
 // ---- fp32 MFMA GEMM for the dense layers -------------------------------------------
@@ -1584,20 +499,15 @@ struct PolicyWs {
 static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int kDense1Chunks = 25;  // split-K of dense1: 5000 = 25 x 200
 
-// N images (trunk runs), S policy samples (heads); the layout depends on both, so a forward with other sizes
-// (ofx_policy_forward_obs) invalidates the results a previous forward left in the workspace
-// conv1 -> conv2 fused (k_trunk12, one persistent workgroup per CU) once the images fill the CUs a few times over;
-// below that the two-kernel form has the shorter critical path (OFX_OPT_TRUNK_FUSE: 1 always, 2 never)
-static bool trunk_fused(const ofx_handle *h, size_t N) {
-  if (h->opt_trunk_plain) return false;
-  return h->opt_trunk_fuse == 1 || (h->opt_trunk_fuse == 0 && N >= 4 * (size_t)h->n_cus);
-}
-
+// N images (trunk runs), S policy samples (heads).  Everything here is transient: a later forward with other sizes or
+// any other user of the handle's scratch block may overwrite or re-allocate it.  The (iaction, ipointer) slots only
+// take results nobody asked for (ofx_policy_forward_obs with null outputs); the results that ofx_policy_forward keeps
+// for ofx_policy_explore / ofx_policy_actions / ofx_replay_capture live in the handle (ofx_policy_results).
 static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S) {
   size_t f2, f3, f4;
   ofx_head_frame_bytes(S, &f2, &f3, &f4);
   // p1 (5.2 GB at 4096 arenas) exists only in the two-kernel form of the trunk
-  const size_t sz[] = {trunk_fused(h, N) ? 0 : al(4ull * N * 8 * 200 * 200), al(4ull * N * 8 * 100 * 100), al(4ull * N * 8 * 50 * 50),
+  const size_t sz[] = {ofx_trunk_fused(h, N) ? 0 : al(4ull * N * 8 * 200 * 200), al(4ull * N * 8 * 100 * 100), al(4ull * N * 8 * 50 * 50),
                        al(4ull * N * 5000),          al(4ull * N * 100 * kDense1Chunks), al(4ull * S * 100),
                        al(4ull * S * 625),           al(4ull * S * 2 * 50 * 50),   al(f2), al(f3), al(f4),
                        al(8ull * S),                 al(4ull * S),                 al(8ull * S),
@@ -1615,32 +525,6 @@ static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S) {
   return OFX_OK;
 }
 
-template <int CIN, int COUT, int TH, int TW, int MODE, bool POOL, bool OUT_HWC>
-static int launch_conv(ofx_handle *h, ConvParams p, int images, int H) {
-  p.H = H; p.W = H;
-  p.tiles_x = H / TW;
-  p.tiles = p.tiles_x * (H / TH);
-  constexpr int NTB = ((TH / 2) * (TW / 2) + 63) / 64 * 64;
-  hipLaunchKernelGGL((k_conv<CIN, COUT, TH, TW, MODE, POOL, OUT_HWC>), dim3((unsigned)(images * p.tiles)), dim3(NTB), 0,
-                     h->stream, p);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
-}
-
-// conv1 + BatchNorm + ReLU + pool of n stored observations (bits [n][2][5000]) through a caller-built table
-// [2][512][8] (channel 0 carries the bias): out [n][8][200][200].  The fit's first layer (ofx_fit.hip): its table folds
-// the BATCH statistics.
-int ofx_launch_conv1_lut(ofx_handle *h, const void *bits, int n, const float *lut, float *out) {
-  ConvParams cp{};
-  cp.bits[0] = reinterpret_cast<const unsigned *>(bits);
-  cp.bits[1] = cp.bits[0] + (PS * PS) / 32;
-  cp.bits_stride = 2 * (size_t)((PS * PS) / 32);
-  cp.out = out; cp.H = PS; cp.W = PS; cp.images = n;
-  hipLaunchKernelGGL(k_conv1_lut<40>, dim3((unsigned)(n * (PS / 40))), dim3(256), 0, h->stream, cp, lut);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
-}
-
 // (also the dense layers of the fit's forward, ofx_train.hip)
 int ofx_launch_gemm(ofx_handle *h, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,
                     int M, int N, int K, int relu, const int32_t *live) {
@@ -1650,8 +534,6 @@ int ofx_launch_gemm(ofx_handle *h, const float *A, int lda, const float *B, int 
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
-
-static const int t_d1 = 24, t_d2 = 26, t_o1 = 28, t_ud = 30, t_up = 32, t_u4 = 50;  // tensor indices of the blob
 
 // BN folding, phase weights, tables: `weights` -> the handle's prepared-weights buffer (two small launches)
 // `slot`: &h->prep (the pinned blob's buffer) or &h->prep_tmp (any other blob: a target network or a one-off forward
@@ -1667,14 +549,14 @@ static int policy_prepare(ofx_handle *h, const float *weights, float **slot) {
   PrepParams pp;
   pp.w = weights; pp.prep = *slot;
   for (int i = 0; i < 4; i++) {
-    pp.src_k[i] = off[6 * i]; pp.src_b[i] = off[6 * i + 1]; pp.src_g[i] = off[6 * i + 2];
+    pp.src_k[i] = off[ofx_t_trunk(i)]; pp.src_b[i] = off[ofx_t_trunk(i, OFX_T_BIAS)]; pp.src_g[i] = off[ofx_t_trunk(i, OFX_T_GAMMA)];
     pp.cin[i] = kTrunkCin[i]; pp.cout[i] = 8; pp.dst_w[i] = L.tw[i]; pp.dst_b[i] = L.tb[i];
   }
   for (int i = 0; i < 3; i++) {
-    pp.src_k[4 + i] = off[t_up + 6 * i]; pp.src_b[4 + i] = off[t_up + 6 * i + 1]; pp.src_g[4 + i] = off[t_up + 6 * i + 2];
+    pp.src_k[4 + i] = off[ofx_t_up(i)]; pp.src_b[4 + i] = off[ofx_t_up(i, OFX_T_BIAS)]; pp.src_g[4 + i] = off[ofx_t_up(i, OFX_T_GAMMA)];
     pp.cin[4 + i] = kUpCin[i]; pp.cout[4 + i] = kUpCout[i]; pp.dst_w[4 + i] = L.uw[i]; pp.dst_b[4 + i] = L.ub[i];
   }
-  pp.src_k4 = off[t_u4]; pp.src_b4 = off[t_u4 + 1];
+  pp.src_k4 = off[OFX_T_OUT2]; pp.src_b4 = off[OFX_T_OUT2 + 1];
   pp.dst_w4raw = L.w4raw; pp.dst_b4 = L.b4; pp.dst_efr = L.efr;
   pp.dst_w4eff_c = L.w4eff_c; pp.dst_w3mf = L.w3mf; pp.dst_w2mf = L.w2mf; pp.dst_w2fr = L.w2fr; pp.dst_w3fr = L.w3fr; pp.dst_lut1 = L.lut1;
   for (int i = 0; i < 3; i++) pp.dst_wbm[i] = L.wbm[i];
@@ -1702,17 +584,6 @@ extern "C" int ofx_policy_pin_weights(ofx_handle *h, const float *weights) {
 
 int ofx_policy_weights_updated(ofx_handle *h, const float *weights) {  // ofx_train.hip: the blob changed in place
   if (h->prep_pinned && h->prep_pinned == weights) return policy_prepare(h, weights, &h->prep);
-  return OFX_OK;
-}
-
-extern "C" int ofx_policy_trunk_stats(ofx_handle *h, int64_t *counts_host) {
-  if (!h || !counts_host) { ofx_set_error("ofx_policy_trunk_stats: null argument"); return OFX_ERR_INVALID; }
-  for (int i = 0; i < 4; i++) counts_host[i] = 0;
-  if (!h->trunk_stat) return OFX_OK;
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipMemcpyAsync(counts_host, h->trunk_stat, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-  OFX_HIP(hipMemsetAsync(h->trunk_stat, 0, 4 * sizeof(unsigned long long), h->stream));
-  OFX_HIP(hipStreamSynchronize(h->stream));
   return OFX_OK;
 }
 
@@ -1744,13 +615,23 @@ extern "C" int ofx_set_option(ofx_handle *h, int32_t option, int32_t value) {
   }
 }
 
-// The forward proper: N images (two 1-bit maps each: word bits?[img * bits_stride + w]) with M policy samples per
-// image; vec8 = explicit observation heads [N*M][8] or null (the live state of the handle's arenas).
-static int policy_forward_impl(ofx_handle *h, const float *weights, int N, int M, const unsigned *bits0,
-                               const unsigned *bits1, size_t bits_stride, const float *vec8, const uint8_t *ship_mask,
-                               float *act_values, int32_t *iaction, int32_t *ipointer, float *heatmap, float *ptr_max,
-                               const int32_t *probe, float *ptr_probe) {
-  const int S = N * M;
+// One forward: N images (two 1-bit maps each: word bits[ci][img * bits_stride + w]) with M policy samples per image.
+struct ForwardArgs {
+  const float *weights;
+  int N, M;
+  const unsigned *bits[2];
+  size_t bits_stride;
+  const float *vec8;               // explicit observation heads [N*M][8] or null (the live state of the handle's arenas)
+  const uint8_t *ship_mask;        // [N*M] or null
+  // results as in include/ofx.h, each may be null; null iaction / ipointer go to a throw-away slot of the workspace
+  float *act_values, *heatmap, *ptr_max, *ptr_probe;
+  int32_t *iaction, *ipointer;
+  const int32_t *probe;
+};
+
+static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
+  const int N = a.N, S = a.N * a.M;
+  const float *weights = a.weights;
   PolicyWs ws;
   int rc = policy_workspace(h, &ws, N, S);
   if (rc) return rc;
@@ -1764,60 +645,21 @@ static int policy_forward_impl(ofx_handle *h, const float *weights, int N, int M
   if (!pinned && (rc = policy_prepare(h, weights, &h->prep_tmp))) return rc;
   const float *prep = pinned ? h->prep : h->prep_tmp;
 
-  // 1. trunk, once per arena
-  ConvParams cp;
-  memset(&cp, 0, sizeof(cp));
-  cp.bits[0] = bits0;
-  cp.bits[1] = bits1;
-  cp.bits_stride = bits_stride;
-  cp.w = prep + L.tw[0]; cp.b = prep + L.tb[0]; cp.out = ws.p1;
-  const int lowp = vec8 == nullptr ? h->opt_policy_lowp : 0;  // opt-in (1 bf16, 2 fp16 operands), the rollout's forward only
-  const bool plain = h->opt_trunk_plain;  // OFX_OPT_TRUNK_PLAIN: every trunk layer through the plain VALU kernel
-  const bool fused12 = trunk_fused(h, (size_t)N);
-  if (plain) rc = launch_conv<2, 8, 10, 100, 1, true, false>(h, cp, N, 400);
-  else if (fused12) {
-    cp.out = ws.p2; cp.b = prep + L.tb[1]; cp.wbm = prep + L.wbm[0]; cp.images = N;
-    const dim3 g12((unsigned)(N < h->n_cus ? N : h->n_cus));
-    const bool sparse = h->opt_trunk_sparse || vec8 != nullptr;   // exact either way: the forwards on stored observations (DQN targets) always take it
-    cp.stat = h->opt_trunk_sparse ? h->trunk_stat : nullptr;
-    const float *lut1 = prep + L.lut1;
-#define T12(LP_) do { if (sparse) hipLaunchKernelGGL((k_trunk12<LP_, true>), g12, dim3(F12_THREADS), 0, h->stream, cp, lut1); \
-                      else hipLaunchKernelGGL((k_trunk12<LP_, false>), g12, dim3(F12_THREADS), 0, h->stream, cp, lut1); } while (0)
-    if (lowp == 1) T12(1); else if (lowp == 2) T12(2); else T12(0);
-#undef T12
-    OFX_HIP(hipGetLastError());
-  } else {
-    cp.H = 400; cp.W = 400;
-    hipLaunchKernelGGL(k_conv1_lut<40>, dim3((unsigned)(N * (400 / 40))), dim3(256), 0, h->stream, cp,
-                       (const float *)(prep + L.lut1));
-    OFX_HIP(hipGetLastError());
-  }
-  if (rc) return rc;
-  // k_convm tile shapes from an A/B on the chip (conv2: 2 row pairs x 208 columns, 29 KB of LDS, five workgroups per CU)
-  cp.in = ws.p1; cp.w = prep + L.tw[1]; cp.b = prep + L.tb[1]; cp.out = ws.p2; cp.wbm = prep + L.wbm[0];
-  if (plain) rc = launch_conv<8, 8, 10, 100, 0, true, false>(h, cp, N, 200);
-  else if (!fused12) rc = launch_convm<8, 2, 13, 0, false, 1>(h, cp, N, 200);
-  if (rc) return rc;
-  cp.in = ws.p2; cp.w = prep + L.tw[2]; cp.b = prep + L.tb[2]; cp.out = ws.p3; cp.wbm = prep + L.wbm[1];
-  if (plain) rc = launch_conv<8, 8, 10, 100, 0, true, false>(h, cp, N, 100);
-  else if (fused12) {  // large batches: the streaming form, like conv1 -> conv2
-    cp.images = N;
-    const dim3 g3((unsigned)(N < h->n_cus ? N : h->n_cus));
-    if (lowp == 1) hipLaunchKernelGGL(k_conv3_stream<1>, g3, dim3(F12_THREADS), 0, h->stream, cp, (const float *)(prep + L.zero16));
-    else if (lowp == 2) hipLaunchKernelGGL(k_conv3_stream<2>, g3, dim3(F12_THREADS), 0, h->stream, cp, (const float *)(prep + L.zero16));
-    else hipLaunchKernelGGL(k_conv3_stream<0>, g3, dim3(F12_THREADS), 0, h->stream, cp, (const float *)(prep + L.zero16));
-    OFX_HIP(hipGetLastError());
-  } else rc = launch_convm<8, 4, 7, 0, false, 1>(h, cp, N, 100);
-  if (rc) return rc;
-  cp.in = ws.p3; cp.w = prep + L.tw[3]; cp.b = prep + L.tb[3]; cp.out = ws.p4; cp.wbm = prep + L.wbm[2];
-  if (plain) rc = launch_conv<8, 8, 10, 50, 0, true, true>(h, cp, N, 50);  // (h,w,c) = Flatten order
-  else if (lowp == 1 && fused12) rc = launch_convm<8, 10, 4, 0, true, 1, 1>(h, cp, N, 50);
-  else if (lowp == 2 && fused12) rc = launch_convm<8, 10, 4, 0, true, 1, 2>(h, cp, N, 50);
-  else rc = launch_convm<8, 10, 4, 0, true, 1>(h, cp, N, 50);
-  if (rc) return rc;
+  // 1. trunk, once per arena (ofx_trunk.hip)
+  const int lowp = a.vec8 == nullptr ? h->opt_policy_lowp : 0;  // opt-in (1 bf16, 2 fp16 operands), the rollout's forward only
+  TrunkParams tp;
+  memset(&tp, 0, sizeof(tp));
+  tp.bits[0] = a.bits[0]; tp.bits[1] = a.bits[1]; tp.bits_stride = a.bits_stride; tp.images = N;
+  for (int i = 0; i < 4; i++) { tp.tw[i] = prep + L.tw[i]; tp.tb[i] = prep + L.tb[i]; }
+  for (int i = 0; i < 3; i++) tp.wbm[i] = prep + L.wbm[i];
+  tp.lut1 = prep + L.lut1; tp.zero16 = prep + L.zero16;
+  tp.p1 = ws.p1; tp.p2 = ws.p2; tp.p3 = ws.p3; tp.p4 = ws.p4;
+  tp.lowp = lowp; tp.sparse = h->opt_trunk_sparse || a.vec8 != nullptr;   // exact either way: the forwards on stored observations (DQN targets) always take it
+  tp.stat = h->opt_trunk_sparse ? h->trunk_stat : nullptr;
+  if ((rc = ofx_launch_trunk(h, tp))) return rc;
 
   // 2. dense1: trunk features on MFMA once per arena; head + head-1 per ship
-  const float *k1 = weights + off[t_d1];
+  const float *k1 = weights + off[OFX_T_DENSE1];
   {
     const int tiles = ((N + 31) / 32) * 4, jobs = tiles * kDense1Chunks;
     hipLaunchKernelGGL(k_gemm_f32_splitk, dim3((jobs + 3) / 4), dim3(256), 0, h->stream, ws.p4, 5000, k1 + 8 * 100, 100,
@@ -1825,22 +667,22 @@ static int policy_forward_impl(ofx_handle *h, const float *weights, int N, int M
     OFX_HIP(hipGetLastError());
   }
   HeadParams hp;
-  hp.N = N; hp.M = M; hp.st = h->st; hp.vec8 = vec8; hp.g1 = ws.g1; hp.g1_chunks = kDense1Chunks;
-  hp.k1 = k1; hp.b1 = weights + off[t_d1 + 1];
-  hp.k2 = weights + off[t_d2]; hp.b2 = weights + off[t_d2 + 1];
-  hp.k3 = weights + off[t_o1]; hp.b3 = weights + off[t_o1 + 1];
+  hp.N = N; hp.M = a.M; hp.st = h->st; hp.vec8 = a.vec8; hp.g1 = ws.g1; hp.g1_chunks = kDense1Chunks;
+  hp.k1 = k1; hp.b1 = weights + off[OFX_T_DENSE1 + 1];
+  hp.k2 = weights + off[OFX_T_DENSE2]; hp.b2 = weights + off[OFX_T_DENSE2 + 1];
+  hp.k3 = weights + off[OFX_T_OUT1]; hp.b3 = weights + off[OFX_T_OUT1 + 1];
   // a masked forward works on the ordered list of the selected ships from here on (one scan of the mask)
   const int32_t *live = nullptr;
-  if (ship_mask) {
-    if ((rc = ofx_head_compact(h, S, ship_mask, ws.live))) return rc;
+  if (a.ship_mask) {
+    if ((rc = ofx_head_compact(h, S, a.ship_mask, ws.live))) return rc;
     live = ws.live;
   }
-  hp.mask = ship_mask; hp.live = live; hp.d1 = ws.d1; hp.act = act_values; hp.iaction = iaction ? iaction : ws.iaction;
+  hp.mask = a.ship_mask; hp.live = live; hp.d1 = ws.d1; hp.act = a.act_values; hp.iaction = a.iaction ? a.iaction : ws.iaction;
   hipLaunchKernelGGL(k_head_dense, dim3((S + 3) / 4), dim3(256), 0, h->stream, hp);
   OFX_HIP(hipGetLastError());
 
   // 3. head-2: updense1 on MFMA, upconv1 (1 -> 2 @ 50x50), then upconv2-4 + arg-max in the streaming kernel (ofx_head.hip)
-  if ((rc = ofx_launch_gemm(h, ws.d1, 100, weights + off[t_ud], 625, weights + off[t_ud + 1], ws.u0, 625, S, 625, 100, 1, live)))
+  if ((rc = ofx_launch_gemm(h, ws.d1, 100, weights + off[OFX_T_UPDENSE], 625, weights + off[OFX_T_UPDENSE + 1], ws.u0, 625, S, 625, 100, 1, live)))
     return rc;
   ConvParams up;
   memset(&up, 0, sizeof(up));
@@ -1860,13 +702,14 @@ static int policy_forward_impl(ofx_handle *h, const float *weights, int N, int M
   hp2.u2fr = ws.u2fr; hp2.vfr = ws.vfr; hp2.c4 = ws.c4;
   hp2.frames_ref = h->opt_frames_ref; hp2.legacy = h->opt_bilinear_legacy;
   hp2.bf16 = lowp;  // the rollout's forward only: targets and fit stay fp32
-  hp2.mask = ship_mask; hp2.live = ws.live; hp2.live_ready = ship_mask != nullptr; hp2.best = ws.best; hp2.heat = heatmap; hp2.probe = probe; hp2.ptr_probe = probe ? ptr_probe : nullptr;
+  hp2.mask = a.ship_mask; hp2.live = ws.live; hp2.live_ready = a.ship_mask != nullptr; hp2.best = ws.best; hp2.heat = a.heatmap;
+  hp2.probe = a.probe; hp2.ptr_probe = a.probe ? a.ptr_probe : nullptr;
   const int pb = h->prof_base;  // ofx_policy_profile: events around the dominant kernel, until the ring is full
   hp2.event_base = pb;
   if ((rc = ofx_launch_head(h, hp2))) return rc;
   if (pb >= 0) h->prof_base = pb + 3 < OFX_RING_MAX ? pb + 2 : -1;
-  hipLaunchKernelGGL(k_policy_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, ship_mask, ws.best,
-                     ipointer ? ipointer : ws.ipointer, ptr_max);
+  hipLaunchKernelGGL(k_policy_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, a.ship_mask, ws.best,
+                     a.ipointer ? a.ipointer : ws.ipointer, a.ptr_max);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -1884,9 +727,26 @@ extern "C" int ofx_policy_forward(ofx_handle *h, const float *weights, const uin
   OFX_HIP(hipSetDevice(c.device));
   int rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr);  // the observation as 1-bit maps
   if (rc) return rc;
-  return policy_forward_impl(h, weights, c.n_arenas, c.n_ships, (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0],
-                             (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1], (size_t)(PS * PS) >> 5, nullptr, ship_mask,
-                             act_values, iaction, ipointer, heatmap, nullptr, nullptr, nullptr);
+  int32_t *ria, *rip;  // null = the handle's results
+  if ((rc = ofx_policy_results(h, &ria, &rip))) return rc;
+  if (!iaction) iaction = ria;
+  if (!ipointer) ipointer = rip;
+  ForwardArgs a{};
+  a.weights = weights; a.N = c.n_arenas; a.M = c.n_ships;
+  a.bits[0] = (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0]; a.bits[1] = (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1];
+  a.bits_stride = (size_t)(PS * PS) >> 5;
+  a.ship_mask = ship_mask; a.act_values = act_values; a.iaction = iaction; a.ipointer = ipointer; a.heatmap = heatmap;
+  return policy_forward_impl(h, a);
+}
+
+// n stored observations (bits [n][2][5000], vec8 [n][8]), one policy sample each
+static ForwardArgs obs_args(const float *weights, int32_t n_obs, const void *bits, const float *vec8) {
+  const size_t words = (size_t)(PS * PS) >> 5;
+  ForwardArgs a{};
+  a.weights = weights; a.N = n_obs; a.M = 1;
+  a.bits[0] = (const unsigned *)bits; a.bits[1] = a.bits[0] + words; a.bits_stride = 2 * words;
+  a.vec8 = vec8;
+  return a;
 }
 
 extern "C" int ofx_policy_forward_obs(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits,
@@ -1895,108 +755,17 @@ extern "C" int ofx_policy_forward_obs(ofx_handle *h, const float *weights, int32
   if (!h || !weights || !bits || !vec8 || n_obs < 1) { ofx_set_error("ofx_policy_forward_obs: bad argument"); return OFX_ERR_INVALID; }
   if ((probe == nullptr) != (ptr_probe == nullptr)) { ofx_set_error("ofx_policy_forward_obs: pass probe and ptr_probe together"); return OFX_ERR_INVALID; }
   OFX_HIP(hipSetDevice(h->cfg.device));
-  const size_t words = (size_t)(PS * PS) >> 5;
-  return policy_forward_impl(h, weights, n_obs, 1, (const unsigned *)bits, (const unsigned *)bits + words, 2 * words, vec8,
-                             nullptr, act_values, iaction, ipointer, nullptr, ptr_max, probe, ptr_probe);
+  ForwardArgs a = obs_args(weights, n_obs, bits, vec8);
+  a.act_values = act_values; a.iaction = iaction; a.ipointer = ipointer; a.ptr_max = ptr_max; a.probe = probe; a.ptr_probe = ptr_probe;
+  return policy_forward_impl(h, a);
 }
 
 // model.predict on stored observations with the whole heat map written out (ofx_dqn_fit_reference, ofx_train.hip)
 int ofx_policy_predict_obs(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits, const float *vec8,
                            float *act_values, float *heatmap, float *ptr_max) {
-  const size_t words = (size_t)(PS * PS) >> 5;
-  return policy_forward_impl(h, weights, n_obs, 1, (const unsigned *)bits, (const unsigned *)bits + words, 2 * words, vec8,
-                             nullptr, act_values, nullptr, nullptr, heatmap, ptr_max, nullptr, nullptr);
-}
-
-// ---- TD targets of Trainer.replay (agents/qlearnIA_V2.py:251-270) -------------------------------------------------
-__global__ void k_dqn_unpack(int n, const ofx_transition *rows, float *vec_prev, float *vec_next, int32_t *probe) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ofx_transition r = rows[i];
-  const bool pad = r.ship < 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    vec_prev[(size_t)i * 8 + k] = pad ? 0.f : r.head_prev[k];
-    vec_next[(size_t)i * 8 + k] = pad ? 0.f : r.head_next[k];
-  }
-  probe[2 * i] = pad ? 0 : min(max(r.px, 0), PS - 1);
-  probe[2 * i + 1] = pad ? 0 : min(max(r.py, 0), PS - 1);
-}
-
-// k_dqn_targets, the TD arithmetic (ofx_train.hip: a -ffp-contract=off file, see there)
-int ofx_launch_dqn_targets(ofx_handle *h, int n, const ofx_transition *rows, float gamma, const float *act_prev,
-                           const float *probe_prev, const float *act_next, const float *max_next, float *q_sa, float *p_sp,
-                           float *y_act, float *y_ptr, const float *ret, const float *disc);
-
-static int ensure_aux(ofx_handle *h, size_t bytes) {
-  if (h->aux_bytes >= bytes) return OFX_OK;
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  if (h->aux) (void)hipFree(h->aux);
-  h->aux = nullptr; h->aux_bytes = 0;
-  OFX_HIP(hipMalloc(&h->aux, bytes));
-  h->aux_bytes = bytes;
-  return OFX_OK;
-}
-
-extern "C" int ofx_policy_forward_obs(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits,
-                                      const float *vec8, float *act_values, int32_t *iaction, int32_t *ipointer,
-                                      float *ptr_max, const int32_t *probe, float *ptr_probe);
-
-// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch
-static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, int32_t n, const ofx_transition *rows,
-                            const void *bits_prev, const void *bits_next, float gamma, const float *ret, const float *disc,
-                            float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
-  if (!h || !weights || !rows || !bits_prev || !bits_next || (!q_sa) != (!p_sp) || !y_act || !y_ptr || n < 1) {
-    ofx_set_error("%s: bad argument", who);
-    return OFX_ERR_INVALID;
-  }
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  const size_t nn = (size_t)n;
-  int rc = ensure_aux(h, al(32 * nn) * 2 + al(8 * nn) * 3 + al(4 * nn) * 2);
-  if (rc) return rc;
-  char *b = (char *)h->aux;
-  float *vec_prev = (float *)b; b += al(32 * nn);
-  float *vec_next = (float *)b; b += al(32 * nn);
-  int32_t *probe = (int32_t *)b; b += al(8 * nn);
-  float *act_prev = (float *)b; b += al(8 * nn);
-  float *act_next = (float *)b; b += al(8 * nn);
-  float *probe_prev = (float *)b; b += al(4 * nn);
-  float *max_next = (float *)b;
-  hipLaunchKernelGGL(k_dqn_unpack, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, vec_prev, vec_next, probe);
-  OFX_HIP(hipGetLastError());
-  // q_sa = p_sp = NULL: the caller only wants the targets (ofx_dqn_fit's own forward gives the current values) - the forward
-  // on `state` is skipped
-  if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, vec_prev, act_prev, nullptr, nullptr, nullptr, probe, probe_prev)))
-    return rc;
-  if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, nullptr, max_next, nullptr, nullptr)))
-    return rc;
-  return ofx_launch_dqn_targets(h, n, rows, gamma, act_prev, probe_prev, act_next, max_next, q_sa, p_sp, y_act, y_ptr, ret,
-                                disc);
-}
-
-extern "C" int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
-                               const void *bits_prev, const void *bits_next, float gamma, float *q_sa, float *p_sp,
-                               float *y_act, float *y_ptr) {
-  return dqn_targets_impl(h, "ofx_dqn_targets", weights, n, rows, bits_prev, bits_next, gamma, nullptr, nullptr, q_sa,
-                          p_sp, y_act, y_ptr);
-}
-
-extern "C" int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
-                                     const void *bits_prev, const void *bits_next, const float *ret, const float *disc,
-                                     float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
-  if (!ret || !disc) { ofx_set_error("ofx_dqn_targets_nstep: ret and disc must be given"); return OFX_ERR_INVALID; }
-  return dqn_targets_impl(h, "ofx_dqn_targets_nstep", weights, n, rows, bits_prev, bits_next, 0.f, ret, disc, q_sa, p_sp,
-                          y_act, y_ptr);
-}
-
-// (iaction, ipointer) of the last forward / explore, for the other translation units (ofx_replay.hip)
-int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer) {
-  PolicyWs ws;
-  int rc = policy_workspace(h, &ws, h->cfg.n_arenas, (size_t)h->cfg.n_arenas * h->cfg.n_ships);
-  if (rc) return rc;
-  *iaction = ws.iaction;
-  *ipointer = ws.ipointer;
-  return OFX_OK;
+  ForwardArgs a = obs_args(weights, n_obs, bits, vec8);
+  a.act_values = act_values; a.heatmap = heatmap; a.ptr_max = ptr_max;
+  return policy_forward_impl(h, a);
 }
 
 #define OFX_STREAM_EXPLORE 2u
@@ -2021,13 +790,11 @@ extern "C" int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, 
   if (!h->spawned) { ofx_set_error("ofx_policy_explore before ofx_spawn"); return OFX_ERR_STATE; }
   if (epsilon < 0.0 || epsilon > 1.0) { ofx_set_error("Value must me in range [0,1]"); return OFX_ERR_INVALID; }  // epsilon.py:56
   OFX_HIP(hipSetDevice(h->cfg.device));
-  if (!iaction || !ipointer) {
-    PolicyWs ws;
-    int rc = policy_workspace(h, &ws, h->cfg.n_arenas, (size_t)h->cfg.n_arenas * h->cfg.n_ships);
-    if (rc) return rc;
-    if (!iaction) iaction = ws.iaction;
-    if (!ipointer) ipointer = ws.ipointer;
-  }
+  int rc;
+  int32_t *ria, *rip;  // null = the handle's results
+  if ((rc = ofx_policy_results(h, &ria, &rip))) return rc;
+  if (!iaction) iaction = ria;
+  if (!ipointer) ipointer = rip;
   const int S = h->cfg.n_arenas * h->cfg.n_ships;
   hipLaunchKernelGGL(k_policy_explore, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
                      h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), tick,
@@ -2042,13 +809,11 @@ extern "C" int ofx_policy_actions(ofx_handle *h, const int32_t *iaction, const i
   if (!h->spawned) { ofx_set_error("ofx_policy_actions before ofx_spawn"); return OFX_ERR_STATE; }
   OFX_HIP(hipSetDevice(h->cfg.device));
   const int S = h->cfg.n_arenas * h->cfg.n_ships;
-  if (!iaction || !ipointer) {  // use the results the last ofx_policy_forward kept in the workspace
-    PolicyWs ws;
-    int rc = policy_workspace(h, &ws, h->cfg.n_arenas, (size_t)h->cfg.n_arenas * h->cfg.n_ships);
-    if (rc) return rc;
-    if (!iaction) iaction = ws.iaction;
-    if (!ipointer) ipointer = ws.ipointer;
-  }
+  int rc;
+  int32_t *ria, *rip;  // null = the handle's results
+  if ((rc = ofx_policy_results(h, &ria, &rip))) return rc;
+  if (!iaction) iaction = ria;
+  if (!ipointer) ipointer = rip;
   hipLaunchKernelGGL(k_policy_actions, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, h->st, iaction, ipointer,
                      ship_mask, actions);
   OFX_HIP(hipGetLastError());

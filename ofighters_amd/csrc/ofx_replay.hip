@@ -213,8 +213,6 @@ __global__ __launch_bounds__(256) void k_replay_frames(int N, int F, int words, 
   for (int k = threadIdx.x; k < q; k += 256) { dst[k] = s0[k]; dst[q + k] = s1[k]; }
 }
 
-int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer);  // ofx_policy.hip
-
 extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
                                   const int32_t *ipointer) {
   if (!h) { ofx_set_error("ofx_replay_capture: null handle"); return OFX_ERR_INVALID; }
@@ -225,12 +223,10 @@ extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *s
   if (h->cfg.n_ships > OFX_WAVE) { ofx_set_error("ofx_replay_capture: n_ships > 64"); return OFX_ERR_INVALID; }
   OFX_HIP(hipSetDevice(h->cfg.device));
   int rc;
-  if (!iaction || !ipointer) {  // the results the last ofx_policy_forward / ofx_policy_explore left in the workspace
-    int32_t *ia, *ip;
-    if ((rc = ofx_policy_results(h, &ia, &ip))) return rc;
-    if (!iaction) iaction = ia;
-    if (!ipointer) ipointer = ip;
-  }
+  int32_t *ria, *rip;  // null = the handle's results
+  if ((rc = ofx_policy_results(h, &ria, &rip))) return rc;
+  if (!iaction) iaction = ria;
+  if (!ipointer) ipointer = rip;
   // the observation maps of this lock-step (the same 1-bit maps the policy trunk reads)
   if ((rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr))) return rc;
   CaptureParams p;
@@ -261,9 +257,9 @@ extern "C" int ofx_agents_first_done(ofx_handle *h, const uint8_t *ship_mask, ui
   if (!h || !seen || !count_host) { ofx_set_error("ofx_agents_first_done: null argument"); return OFX_ERR_INVALID; }
   if (!h->spawned) { ofx_set_error("ofx_agents_first_done before ofx_spawn"); return OFX_ERR_STATE; }
   OFX_HIP(hipSetDevice(h->cfg.device));
-  int rc;
-  if ((rc = ofx_ensure_scratch(h, 256))) return rc;
-  int *cnt = (int *)h->scratch;
+  int32_t *cnt;
+  int rc = ofx_counter(h, OFX_COUNTER_FIRST_DONE, &cnt);
+  if (rc) return rc;
   OFX_HIP(hipMemsetAsync(cnt, 0, sizeof(int), h->stream));
   const int n = h->cfg.n_arenas * h->cfg.n_ships;
   hipLaunchKernelGGL(k_first_done, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->st.alive, ship_mask, seen, cnt);

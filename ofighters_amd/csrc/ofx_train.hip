@@ -17,6 +17,7 @@
 //     next_state as input, :280-283, are stated in include/ofx.h, not reproduced);
 //   * Adam: beta1 0.9, beta2 0.999, eps 1e-7, bias-corrected step size.
 #include "ofx_internal.h"
+#include "ofx_blob.h"
 #include "ofx_fit.h"
 #include <string.h>
 
@@ -479,7 +480,8 @@ __global__ void t_reference_targets(int n, const ofx_transition *rows, float gam
   t2[(size_t)s * TPS * TPS + (size_t)px * TPS + py] = (float)r.reward + gamma * max_next[s] * live;
 }
 
-// The TD arithmetic of ofx_dqn_targets / ofx_dqn_targets_nstep (their forwards run in ofx_policy.hip).  It lives in this
+// ---- TD targets of Trainer.replay (agents/qlearnIA_V2.py:251-270): ofx_dqn_targets / ofx_dqn_targets_nstep below ----
+// The TD arithmetic (the forwards run in ofx_policy.hip).  It lives in this
 // -ffp-contract=off file because the n-step form must round the product and the sum on their own, and under
 // -ffp-contract=fast the backend fuses them whatever `#pragma clang fp contract` says.  The one-step form gives the
 // bits it gave there as fma(live, gamma * m, reward): live is 0 or 1, so that fma rounds once, like the add here.
@@ -510,23 +512,22 @@ __global__ void k_dqn_targets(int n, const ofx_transition *rows, float gamma, co
   y_ptr[i] = (float)r.reward + gamma * max_next[i] * live;  // np.max(ptr_prediction)
 }
 
-int ofx_launch_dqn_targets(ofx_handle *h, int n, const ofx_transition *rows, float gamma, const float *act_prev,
-                           const float *probe_prev, const float *act_next, const float *max_next, float *q_sa, float *p_sp,
-                           float *y_act, float *y_ptr, const float *ret, const float *disc) {
-  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev, probe_prev,
-                     act_next, max_next, q_sa, p_sp, y_act, y_ptr, ret, disc);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
+// the rows' observation heads [n][8] and (probe, may be null) clamped pointers [n][2]; zeros for a padding row
+__global__ void k_dqn_unpack(int n, const ofx_transition *rows, float *vec_prev, float *vec_next, int32_t *probe) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ofx_transition r = rows[i];
+  const bool pad = r.ship < 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    vec_prev[(size_t)i * 8 + k] = pad ? 0.f : r.head_prev[k];
+    vec_next[(size_t)i * 8 + k] = pad ? 0.f : r.head_next[k];
+  }
+  if (!probe) return;
+  probe[2 * i] = pad ? 0 : min(max(r.px, 0), TPS - 1);
+  probe[2 * i + 1] = pad ? 0 : min(max(r.py, 0), TPS - 1);
 }
 
-__global__ void t_unpack_heads(int n, const ofx_transition *rows, float *vec_prev, float *vec_next) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
-  for (int k = 0; k < 8; k++) {
-    vec_prev[(size_t)s * 8 + k] = rows[s].head_prev[k];
-    vec_next[(size_t)s * 8 + k] = rows[s].head_next[k];
-  }
-}
 // dense targets: d = 2 (o - t) scale; block b's share of the loss goes to lpart[b] (summed in block order afterwards)
 __global__ __launch_bounds__(256) void t_loss_dense(size_t total, float scale, const float *o, const float *t, float *d, float *lpart) {
   __shared__ float red[256];
@@ -579,8 +580,6 @@ struct Arena {  // bump allocator over one hipMalloc
   float *f(size_t n) { return (float *)take(n * 4); }
   double *d(size_t n) { return (double *)take(n * 8); }
 };
-
-static const int kTI[4] = {2, 8, 8, 8}, kUI[4] = {1, 2, 4, 8}, kUO[4] = {2, 4, 8, 1};
 
 static const int kWSlices = 128;
 
@@ -640,29 +639,98 @@ __global__ void t_count_pads(int n, const ofx_transition *rows, int32_t *out) {
 // a workspace the handle keeps between calls: grown on demand, given back when a call needs less than a quarter of it (one
 // 4096-row fit leaves 40 GB behind - a handle that then trains on 256 rows should not hold them), freed by ofx_destroy
 static int keep_workspace(ofx_handle *h, void **buf, size_t *have, size_t need) {
-  if (*have >= need && *have / 4 <= need) return OFX_OK;
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr; *have = 0;
-  OFX_HIP(hipMalloc(buf, need));
-  *have = need;
-  return OFX_OK;
+  if (*have / 4 > need) *have = 0;   // given back: allocated anew at `need`
+  return ofx_ensure_buffer(h, buf, have, need);
 }
 
 // padding rows (ship < 0) would enter the BatchNorm batch statistics and the loss scale: refused before any work is done
 static int refuse_pads(ofx_handle *h, int n, const ofx_transition *rows, const char *who) {
   hipStream_t st = h->stream;
-  if (!h->counter) OFX_HIP(hipMalloc((void **)&h->counter, 4 * sizeof(int32_t)));
-  int32_t pads = 0;
-  OFX_HIP(hipMemsetAsync(h->counter, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(t_count_pads, dim3((n + 255) / 256), dim3(256), 0, st, n, rows, h->counter);
-  OFX_HIP(hipMemcpyAsync(&pads, h->counter, sizeof(pads), hipMemcpyDeviceToHost, st));
+  int32_t *counter, pads = 0;
+  int rc = ofx_counter(h, OFX_COUNTER_PADS, &counter);
+  if (rc) return rc;
+  OFX_HIP(hipMemsetAsync(counter, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(t_count_pads, dim3((n + 255) / 256), dim3(256), 0, st, n, rows, counter);
+  OFX_HIP(hipMemcpyAsync(&pads, counter, sizeof(pads), hipMemcpyDeviceToHost, st));
   OFX_HIP(hipStreamSynchronize(st));
   if (pads) {
     ofx_set_error("%s: %d of %d rows are padding (ship < 0); gather with ofx_replay_gather_valid", who, pads, n);
     return OFX_ERR_INVALID;
   }
   return OFX_OK;
+}
+
+// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch
+static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, int32_t n, const ofx_transition *rows,
+                            const void *bits_prev, const void *bits_next, float gamma, const float *ret, const float *disc,
+                            float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
+  if (!h || !weights || !rows || !bits_prev || !bits_next || (!q_sa) != (!p_sp) || !y_act || !y_ptr || n < 1) {
+    ofx_set_error("%s: bad argument", who);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const size_t nn = (size_t)n;
+  const size_t need = 7 * 256 + 4 * nn * (8 + 8 + 2 + 2 + 2 + 1 + 1);   // seven arrays, each rounded up to 256 bytes
+  int rc = ofx_ensure_buffer(h, &h->aux, &h->aux_bytes, need);
+  if (rc) return rc;
+  Arena A{(char *)h->aux, 0, need};
+  float *vec_prev = A.f(8 * nn), *vec_next = A.f(8 * nn);
+  int32_t *probe = (int32_t *)A.f(2 * nn);
+  float *act_prev = A.f(2 * nn), *act_next = A.f(2 * nn), *probe_prev = A.f(nn), *max_next = A.f(nn);
+  hipLaunchKernelGGL(k_dqn_unpack, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, vec_prev, vec_next, probe);
+  OFX_HIP(hipGetLastError());
+  // q_sa = p_sp = NULL: the caller only wants the targets (ofx_dqn_fit's own forward gives the current values) - the forward
+  // on `state` is skipped
+  if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, vec_prev, act_prev, nullptr, nullptr, nullptr, probe, probe_prev)))
+    return rc;
+  if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, nullptr, max_next, nullptr, nullptr)))
+    return rc;
+  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev, probe_prev,
+                     act_next, max_next, q_sa, p_sp, y_act, y_ptr, ret, disc);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+extern "C" int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                               const void *bits_prev, const void *bits_next, float gamma, float *q_sa, float *p_sp,
+                               float *y_act, float *y_ptr) {
+  return dqn_targets_impl(h, "ofx_dqn_targets", weights, n, rows, bits_prev, bits_next, gamma, nullptr, nullptr, q_sa,
+                          p_sp, y_act, y_ptr);
+}
+
+extern "C" int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                                     const void *bits_prev, const void *bits_next, const float *ret, const float *disc,
+                                     float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
+  if (!ret || !disc) { ofx_set_error("ofx_dqn_targets_nstep: ret and disc must be given"); return OFX_ERR_INVALID; }
+  return dqn_targets_impl(h, "ofx_dqn_targets_nstep", weights, n, rows, bits_prev, bits_next, 0.f, ret, disc, q_sa, p_sp,
+                          y_act, y_ptr);
+}
+
+// The tail of a fit step, after the gradients: Adam on the trained tensors, the moving BatchNorm statistics from the batch
+// statistics (tstat / ustat: trunk / head-2 layers), the loss read back (a synchronisation), a pinned blob prepared again.
+static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weights, const float *grad, float *adam_m,
+                            float *adam_v, int32_t step, float lr, float *const *tstat, float *const *ustat,
+                            const float *loss, float *loss_host) {
+  hipStream_t st = h->stream;
+  const float b1 = 0.9f, b2 = 0.999f;
+  const float lr_t = lr * sqrtf(1.f - powf(b2, (float)step)) / (1.f - powf(b1, (float)step));
+  for (int t = 0; t < L.n_tensors; t++) {
+    if (!ofx_blob_trained(t)) continue;  // moving mean / variance
+    K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
+      adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
+  }
+  for (int i = 0; i < 4; i++)
+    hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
+                       weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i]);
+  for (int j = 0; j < 3; j++)
+    hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
+                       weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j]);
+  OFX_HIP(hipGetLastError());
+  float lh[2] = {0.f, 0.f};
+  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(lh), hipMemcpyDeviceToHost, st));
+  OFX_HIP(hipStreamSynchronize(st));
+  if (loss_host) { loss_host[0] = lh[0]; loss_host[1] = lh[1]; }
+  return ofx_policy_weights_updated(h, weights);
 }
 
 // The lean form of one fit step (default; ofx_fit.hip): the same graph, loss and update as dqn_fit_impl below with only
@@ -687,7 +755,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
   sz(4 * ofx_fit_first_floats()); sz(4 * 5008 * 100);
   sz(8 * ofx_fit_first_doubles(n)); sz(8 * ofx_fit_first_part_doubles(n));                                 // correlation, first-layers backward
   for (int i = 0; i < 3; i++) sz(4 * N * 8 * tS[i + 1] * tS[i + 1]);                                       // pooled activation
-  for (int j = 0; j < 3; j++) { sz(4 * N * kUO[j] * uS[j] * uS[j]); sz(4 * N * kUO[j] * uS[j] * uS[j]); }
+  for (int j = 0; j < 3; j++) { sz(4 * N * kUpCout[j] * uS[j] * uS[j]); sz(4 * N * kUpCout[j] * uS[j] * uS[j]); }
   sz(4 * N * 160000); sz(4 * N * 160000);                                                                  // o2, do2
   sz(4 * N * 5000); sz(4 * N * 5008); sz(4 * N * 100); sz(4 * N * 50); sz(4 * N * 2); sz(4 * N * 625);      // p3 f d1 d2 o1 u0
   sz(4 * N * 625); sz(4 * N * 2); sz(4 * N * 100); sz(4 * N * 50); sz(4 * N * 5008); sz(4 * N * 5000);      // gu0 do1 dd1 dd2 df dp3
@@ -712,7 +780,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
   for (int i = 0; i < 4; i++) { tz[i] = i ? A.f(N * 8 * tS[i] * tS[i]) : nullptr; tg[i] = i ? A.f(N * 8 * tS[i] * tS[i]) : nullptr; tstat[i] = A.f(32); tact[i] = A.f(16); }
   float *luts = A.f(ofx_fit_first_floats()), *w1t = A.f(5008 * 100);
   double *cpart = A.d(ofx_fit_first_doubles(n)), *fpart2 = A.d(ofx_fit_first_part_doubles(n));
-  for (int j = 0; j < 3; j++) { uz[j] = A.f(N * kUO[j] * uS[j] * uS[j]); ug[j] = A.f(N * kUO[j] * uS[j] * uS[j]); ustat[j] = A.f(32); uact[j] = A.f(16); }
+  for (int j = 0; j < 3; j++) { uz[j] = A.f(N * kUpCout[j] * uS[j] * uS[j]); ug[j] = A.f(N * kUpCout[j] * uS[j] * uS[j]); ustat[j] = A.f(32); uact[j] = A.f(16); }
   float *o2 = A.f(N * 160000), *do2 = A.f(N * 160000);
   float *p3 = A.f(N * 5000), *f = A.f(N * 5008), *d1 = A.f(N * 100), *d2 = A.f(N * 50), *o1 = A.f(N * 2), *u0 = A.f(N * 625);
   float *gu0 = A.f(N * 625), *do1 = A.f(N * 2), *dd1 = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008), *dp3 = A.f(N * 5000);
@@ -732,24 +800,24 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
 
   // ---- forward (training mode) ----
   // the first layer is never materialised: statistics from the autocorrelation of the bit maps, p0 through the table kernel
-  if ((rc = ofx_fit_first_fwd(h, n, bits_prev, T(0), T(1), T(2), T(3), cpart, tstat[0], tact[0], luts, tp[0]))) return rc;
+  if ((rc = ofx_fit_first_fwd(h, n, bits_prev, T(ofx_t_trunk(0)), T(ofx_t_trunk(0, OFX_T_BIAS)), T(ofx_t_trunk(0, OFX_T_GAMMA)), T(ofx_t_trunk(0, OFX_T_BETA)), cpart, tstat[0], tact[0], luts, tp[0]))) return rc;
   for (int i = 1; i < 4; i++) {
     const int s = tS[i];
-    if ((rc = ofx_fit_conv_fwd(st, n, kTI[i], 8, s, s, trunk_src(i, false), T(6 * i), T(6 * i + 1), tz[i], part, &nb))) return rc;
-    if ((rc = ofx_fit_finish(st, nb, 8, (double)N * s * s, part, T(6 * i + 2), T(6 * i + 3), nullptr, tstat[i], tact[i]))) return rc;
+    if ((rc = ofx_fit_conv_fwd(st, n, kTrunkCin[i], 8, s, s, trunk_src(i, false), T(ofx_t_trunk(i)), T(ofx_t_trunk(i, OFX_T_BIAS)), tz[i], part, &nb))) return rc;
+    if ((rc = ofx_fit_finish(st, nb, 8, (double)N * s * s, part, T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), nullptr, tstat[i], tact[i]))) return rc;
   }
   if ((rc = ofx_fit_pool_act(st, n, 8, 50, 50, tz[3], tact[3], p3))) return rc;
   K(t_concat_fwd, N * 5008, n, rows, p3, f, dense ? 1 : 0);
-  if ((rc = ofx_launch_gemm(h, f, 5008, T(24), 100, T(25), d1, 100, n, 100, 5008, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(26), 50, T(27), d2, 50, n, 50, 100, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d2, 50, T(28), 2, T(29), o1, 2, n, 2, 50, 0))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(30), 625, T(31), u0, 625, n, 625, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), d1, 100, n, 100, 5008, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), d2, 50, n, 50, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), o1, 2, n, 2, 50, 0))) return rc;
+  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), u0, 625, n, 625, 100, 1))) return rc;
   for (int j = 0; j < 3; j++) {
     const int s = uS[j];
-    if ((rc = ofx_fit_conv_fwd(st, n, kUI[j], kUO[j], s, s, head_src(j), T(32 + 6 * j), T(33 + 6 * j), uz[j], part, &nb))) return rc;
-    if ((rc = ofx_fit_finish(st, nb, kUO[j], (double)N * s * s, part, T(34 + 6 * j), T(35 + 6 * j), nullptr, ustat[j], uact[j]))) return rc;
+    if ((rc = ofx_fit_conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), uz[j], part, &nb))) return rc;
+    if ((rc = ofx_fit_finish(st, nb, kUpCout[j], (double)N * s * s, part, T(ofx_t_up(j, OFX_T_GAMMA)), T(ofx_t_up(j, OFX_T_BETA)), nullptr, ustat[j], uact[j]))) return rc;
   }
-  if (dense && (rc = ofx_fit_out_fwd(st, n, head_src(3), T(50), T(51), o2, weff))) return rc;
+  if (dense && (rc = ofx_fit_out_fwd(st, n, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o2, weff))) return rc;
 
   // ---- loss seeds ----
   OFX_HIP(hipMemsetAsync(do1, 0, N * 2 * 4, st));
@@ -757,8 +825,8 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
     // one error per sample on the heat map: the output convolution at the pointer only, its gradients and the last head
     // layer's g from that one pixel (ofx_fit.hip, "the top of head 2 for the textbook targets")
     float *o2p = o2, *d2p = o2 + N;                          // [n] each: the dense planes are not used on this path
-    if ((rc = ofx_fit_top_point(st, n, rows, head_src(3), T(50), T(51), o1, y_act, y_ptr, ustat[2], o2p, do1, d2p, lpart, gpatch,
-                                pscratch, sums, G(50), G(51), row_weight, td_out))) return rc;
+    if ((rc = ofx_fit_top_point(st, n, rows, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o1, y_act, y_ptr, ustat[2], o2p, do1, d2p, lpart, gpatch,
+                                pscratch, sums, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1), row_weight, td_out))) return rc;
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
     OFX_HIP(hipGetLastError());
   } else if (dense) {
@@ -771,75 +839,57 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
   }
 
   // ---- backward: head 2 ----
-  if (dense && (rc = ofx_fit_out_bw(st, n, head_src(3), do2, part, fpart, G(50), G(51)))) return rc;
+  if (dense && (rc = ofx_fit_out_bw(st, n, head_src(3), do2, part, fpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1)))) return rc;
   const float *dzn = do2;
   for (int j = 2; j >= 0; j--) {
     const int s = uS[j];
     if (j < 2 || dense) {   // (the textbook path has the last layer's g and its sums already)
-      if ((rc = ofx_fit_b1_up(st, n, kUO[j], kUO[j + 1], s, s, 1, dzn, T(32 + 6 * (j + 1)), uz[j], ustat[j], uact[j], legacy, ug[j], part, &nb, zero, wtr))) return rc;
-      if ((rc = ofx_fit_finish(st, nb, kUO[j], 1.0, part, nullptr, nullptr, sums, nullptr, nullptr))) return rc;
+      if ((rc = ofx_fit_b1_up(st, n, kUpCout[j], kUpCout[j + 1], s, s, 1, dzn, T(ofx_t_up(j + 1)), uz[j], ustat[j], uact[j], legacy, ug[j], part, &nb, zero, wtr))) return rc;
+      if ((rc = ofx_fit_finish(st, nb, kUpCout[j], 1.0, part, nullptr, nullptr, sums, nullptr, nullptr))) return rc;
     }
     const bool patch = j == 2 && !dense;   // (g of the last layer is a 4 x 4 patch per sample there: not read, dz written)
-    if ((rc = ofx_fit_bw(st, n, kUI[j], kUO[j], s, s, head_src(j), 1, ug[j], uz[j], ustat[j], T(34 + 6 * j), sums, part,
-                         G(32 + 6 * j), G(33 + 6 * j), G(34 + 6 * j), G(35 + 6 * j), patch ? gpatch : nullptr,
+    if ((rc = ofx_fit_bw(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), 1, ug[j], uz[j], ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), sums, part,
+                         G(ofx_t_up(j)), G(ofx_t_up(j, OFX_T_BIAS)), G(ofx_t_up(j, OFX_T_GAMMA)), G(ofx_t_up(j, OFX_T_BETA)), patch ? gpatch : nullptr,
                          patch ? rows : nullptr))) return rc;
     dzn = ug[j];
   }
-  if ((rc = ofx_fit_b1_up(st, n, 1, 2, 25, 25, 0, dzn, T(32), u0, nullptr, nullptr, legacy, gu0, part, &nb, zero, wtr))) return rc;
+  if ((rc = ofx_fit_b1_up(st, n, 1, 2, 25, 25, 0, dzn, T(ofx_t_up(0)), u0, nullptr, nullptr, legacy, gu0, part, &nb, zero, wtr))) return rc;
   // gu0 = d u0 [n][625], already behind u0's ReLU mask
-  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, gu0, G(30), G(31));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, gu0, T(30), dd1, 0);
+  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, gu0, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, gu0, T(OFX_T_UPDENSE), dd1, 0);
   // ---- backward: head 1 ----
-  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(28), G(29));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(28), dd2, 0);
+  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(OFX_T_OUT1), dd2, 0);
   K(t_relu_mask, N * 50, N * 50, d2, dd2);
-  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(26), G(27));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(26), dd1, 1);
+  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(OFX_T_DENSE2), dd1, 1);
   // ---- dense1 + trunk ----
   K(t_relu_mask, N * 100, N * 100, d1, dd1);
-  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(24), G(25));
+  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
   // d f = dd1 x W1^T on the f32 MFMA GEMM (the 5008 x 100 kernel transposed first): 2 x 5008 x 100 FLOP per row
-  hipLaunchKernelGGL(t_transpose, dim3((100 + 31) / 32, (5008 + 31) / 32), dim3(256), 0, st, 5008, 100, T(24), w1t);
+  hipLaunchKernelGGL(t_transpose, dim3((100 + 31) / 32, (5008 + 31) / 32), dim3(256), 0, st, 5008, 100, T(OFX_T_DENSE1), w1t);
   OFX_HIP(hipGetLastError());
   if ((rc = ofx_launch_gemm(h, dd1, 100, w1t, 5008, nullptr, df, 5008, n, 5008, 100, 0))) return rc;
   K(t_concat_bwd, N * 5000, n, df, dp3);
   dzn = dp3;
   for (int i = 3; i >= 0; i--) {
     const int s = tS[i];
-    if ((rc = ofx_fit_b1_pool(st, n, s, s, i < 3, dzn, i < 3 ? T(6 * (i + 1)) : nullptr, tz[i], tstat[i], tact[i], tg[i], part, &nb, wtr, zero))) return rc;
+    if ((rc = ofx_fit_b1_pool(st, n, s, s, i < 3, dzn, i < 3 ? T(ofx_t_trunk(i + 1)) : nullptr, tz[i], tstat[i], tact[i], tg[i], part, &nb, wtr, zero))) return rc;
     if ((rc = ofx_fit_finish(st, nb, 8, 1.0, part, nullptr, nullptr, sums, nullptr, nullptr))) return rc;
     if (i == 1) {
       // the first two layers: the first has neither z, g nor dz, the second's dz is never stored - only the windows that see
       // a set bit are visited (ofx_fit.hip, f_first_bwd)
-      if ((rc = ofx_fit_first_bwd(st, n, bits_prev, tg[1], tz[1], tstat[1], T(8), sums, T(6), tp[0], luts, T(0), T(1), tstat[0],
-                                  T(2), T(3), fpart2, cpart, G(0), G(1), G(2), G(3), G(6), G(7), G(8), G(9)))) return rc;
+      if ((rc = ofx_fit_first_bwd(st, n, bits_prev, tg[1], tz[1], tstat[1], T(ofx_t_trunk(1, OFX_T_GAMMA)), sums, T(ofx_t_trunk(1)), tp[0], luts, T(ofx_t_trunk(0)), T(ofx_t_trunk(0, OFX_T_BIAS)), tstat[0],
+                                  T(ofx_t_trunk(0, OFX_T_GAMMA)), T(ofx_t_trunk(0, OFX_T_BETA)), fpart2, cpart, G(ofx_t_trunk(0)), G(ofx_t_trunk(0, OFX_T_BIAS)), G(ofx_t_trunk(0, OFX_T_GAMMA)), G(ofx_t_trunk(0, OFX_T_BETA)), G(ofx_t_trunk(1)), G(ofx_t_trunk(1, OFX_T_BIAS)), G(ofx_t_trunk(1, OFX_T_GAMMA)), G(ofx_t_trunk(1, OFX_T_BETA))))) return rc;
       break;
     }
-    if ((rc = ofx_fit_bw(st, n, kTI[i], 8, s, s, trunk_src(i, true), 1, tg[i], tz[i], tstat[i], T(6 * i + 2), sums, part,
-                         G(6 * i), G(6 * i + 1), G(6 * i + 2), G(6 * i + 3)))) return rc;
+    if ((rc = ofx_fit_bw(st, n, kTrunkCin[i], 8, s, s, trunk_src(i, true), 1, tg[i], tz[i], tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), sums, part,
+                         G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)), G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA))))) return rc;
     dzn = tg[i];
   }
   if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
-  // ---- Adam + moving statistics ----
-  const float b1 = 0.9f, b2 = 0.999f;
-  const float lr_t = lr * sqrtf(1.f - powf(b2, (float)step)) / (1.f - powf(b1, (float)step));
-  for (int t = 0; t < L.n_tensors; t++) {
-    const bool conv_bn = t < 24 || (t >= 32 && t < 50);
-    const int k = conv_bn ? (t < 24 ? t % 6 : (t - 32) % 6) : -1;
-    if (k == 4 || k == 5) continue;  // moving mean / variance: not trained
-    K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
-      adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
-  }
-  for (int i = 0; i < 4; i++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[6 * i + 4], weights + L.offset[6 * i + 5], tstat[i]);
-  for (int j = 0; j < 3; j++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUO[j], weights + L.offset[32 + 6 * j + 4], weights + L.offset[32 + 6 * j + 5], ustat[j]);
-  OFX_HIP(hipGetLastError());
-  float lh[2] = {0.f, 0.f};
-  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(lh), hipMemcpyDeviceToHost, st));
-  OFX_HIP(hipStreamSynchronize(st));
-  if (loss_host) { loss_host[0] = lh[0]; loss_host[1] = lh[1]; }
-  if ((rc = ofx_policy_weights_updated(h, weights))) return rc;  // a pinned blob is prepared again
-  return OFX_OK;
+  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host);
 }
 
 // One fit step.  Two forms of the targets: the sparse one of ofx_dqn_fit (one error per head and sample: y_act / y_ptr,
@@ -865,20 +915,17 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
   // activations: trunk sizes 400,200,100,50 (z, a per layer + pooled), head-2 sizes 50,100,200 (+ upsampled inputs)
   size_t need = 0;
   auto sz = [&](size_t fl) { need += (fl * 4 + 255) & ~(size_t)255; };
-  for (int pass = 0; pass < 1; pass++) {
-    sz(N * 2 * 160000);
-    for (int i = 0, s = 400; i < 4; i++, s /= 2) { sz(N * 8 * s * s); sz(N * 8 * s * s); sz(N * 8 * (s / 2) * (s / 2)); sz(N * 8 * s * s); sz(N * 8 * s * s); }
-    sz(N * 5008); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625);
-    for (int j = 0, s = 50; j < 3; j++, s *= 2) { sz(N * kUI[j] * s * s); sz(N * kUO[j] * s * s); sz(N * kUO[j] * s * s); sz(N * kUO[j] * s * s); sz(N * kUO[j] * s * s); }
-    sz(N * 8 * 160000); sz(N * 160000);               // up4, o2
-    sz(N * 8 * 160000); sz(N * 8 * 160000);           // two gradient scratch planes of the largest size
-    sz(N * 5008); sz(N * 100); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625); sz(N * 160000);
-    sz(L.n_floats); sz(64); sz(2 * N + 4096); need += 65536 + 16 * 64 * 8 + 16 * 64 * 2 * 8 + (size_t)kWSlices * 600 * 8;
-  }
+  sz(N * 2 * 160000);
+  for (int i = 0, s = 400; i < 4; i++, s /= 2) { sz(N * 8 * s * s); sz(N * 8 * s * s); sz(N * 8 * (s / 2) * (s / 2)); sz(N * 8 * s * s); sz(N * 8 * s * s); }
+  sz(N * 5008); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625);
+  for (int j = 0, s = 50; j < 3; j++, s *= 2) { sz(N * kUpCin[j] * s * s); sz(N * kUpCout[j] * s * s); sz(N * kUpCout[j] * s * s); sz(N * kUpCout[j] * s * s); sz(N * kUpCout[j] * s * s); }
+  sz(N * 8 * 160000); sz(N * 160000);               // up4, o2
+  sz(N * 8 * 160000); sz(N * 8 * 160000);           // two gradient scratch planes of the largest size
+  sz(N * 5008); sz(N * 100); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625); sz(N * 160000);
+  sz(L.n_floats); sz(64); sz(2 * N + 4096); need += 65536 + 16 * 64 * 8 + 16 * 64 * 2 * 8 + (size_t)kWSlices * 600 * 8;
   if ((rc = keep_workspace(h, &h->fitws, &h->fitws_bytes, need))) return rc;
   void *raw = h->fitws;
   Arena A{(char *)raw, 0, need};
-  const float *W_ = weights;
   auto T = [&](int t) { return weights + L.offset[t]; };
   float *grad = A.f(L.n_floats);
   OFX_HIP(hipMemsetAsync(grad, 0, sizeof(float) * L.n_floats, st));
@@ -898,37 +945,37 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
   for (int i = 0, s = 400; i < 4; i++, s /= 2) {
     const size_t per = (size_t)s * s;
     tz[i] = A.f(N * 8 * per); ta[i] = A.f(N * 8 * per); tp[i] = A.f(N * 8 * per / 4); tstat[i] = A.f(16);
-    if ((rc = conv_fwd(st, n, kTI[i], 8, s, s, tin, T(6 * i), T(6 * i + 1), tz[i]))) return rc;
+    if ((rc = conv_fwd(st, n, kTrunkCin[i], 8, s, s, tin, T(ofx_t_trunk(i)), T(ofx_t_trunk(i, OFX_T_BIAS)), tz[i]))) return rc;
     hipLaunchKernelGGL(t_chan_sums, dim3(8, 64), dim3(256), 0, st, n, 8, per, tz[i], (const float *)nullptr, spart);
     hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, 8, 64, spart, sums);
     hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, 8, (double)N * (double)per, sums, tstat[i]);
-    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * 8), 0, st, 8, per, tz[i], tstat[i], T(6 * i + 2), T(6 * i + 3), ta[i]);
+    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * 8), 0, st, 8, per, tz[i], tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), ta[i]);
     K(t_pool_fwd, N * 8 * per / 4, n * 8, s, s, ta[i], tp[i]);
     tin = tp[i];
   }
   float *f = A.f(N * 5008), *d1 = A.f(N * 100), *d2 = A.f(N * 50), *o1 = A.f(N * 2), *u0 = A.f(N * 625);
   K(t_concat_fwd, N * 5008, n, rows, tp[3], f, dense ? 1 : 0);
   // the four dense layers on the f32 MFMA (k_gemm_f32: exact fp32 products, fp32 accumulation in MFMA order)
-  if ((rc = ofx_launch_gemm(h, f, 5008, T(24), 100, T(25), d1, 100, n, 100, 5008, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(26), 50, T(27), d2, 50, n, 50, 100, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d2, 50, T(28), 2, T(29), o1, 2, n, 2, 50, 0))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(30), 625, T(31), u0, 625, n, 625, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), d1, 100, n, 100, 5008, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), d2, 50, n, 50, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), o1, 2, n, 2, 50, 0))) return rc;
+  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), u0, 625, n, 625, 100, 1))) return rc;
   float *uu[3], *uz[3], *ua[3], *ustat[3];
   const float *uin = u0;
   for (int j = 0, s = 50; j < 3; j++, s *= 2) {
     const size_t per = (size_t)s * s;
-    uu[j] = A.f(N * kUI[j] * per); uz[j] = A.f(N * kUO[j] * per); ua[j] = A.f(N * kUO[j] * per); ustat[j] = A.f(16);
-    K(t_up_fwd, N * kUI[j] * per, n * kUI[j], s / 2, s / 2, uin, uu[j], legacy);
-    if ((rc = conv_fwd(st, n, kUI[j], kUO[j], s, s, uu[j], T(32 + 6 * j), T(33 + 6 * j), uz[j]))) return rc;
-    hipLaunchKernelGGL(t_chan_sums, dim3(kUO[j], 64), dim3(256), 0, st, n, kUO[j], per, uz[j], (const float *)nullptr, spart);
-    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUO[j], 64, spart, sums);
-    hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, kUO[j], (double)N * (double)per, sums, ustat[j]);
-    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * kUO[j]), 0, st, kUO[j], per, uz[j], ustat[j], T(34 + 6 * j), T(35 + 6 * j), ua[j]);
+    uu[j] = A.f(N * kUpCin[j] * per); uz[j] = A.f(N * kUpCout[j] * per); ua[j] = A.f(N * kUpCout[j] * per); ustat[j] = A.f(16);
+    K(t_up_fwd, N * kUpCin[j] * per, n * kUpCin[j], s / 2, s / 2, uin, uu[j], legacy);
+    if ((rc = conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, uu[j], T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), uz[j]))) return rc;
+    hipLaunchKernelGGL(t_chan_sums, dim3(kUpCout[j], 64), dim3(256), 0, st, n, kUpCout[j], per, uz[j], (const float *)nullptr, spart);
+    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUpCout[j], 64, spart, sums);
+    hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, kUpCout[j], (double)N * (double)per, sums, ustat[j]);
+    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, uz[j], ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), T(ofx_t_up(j, OFX_T_BETA)), ua[j]);
     uin = ua[j];
   }
   float *up4 = A.f(N * 8 * 160000), *o2 = A.f(N * 160000);
   K(t_up_fwd, N * 8 * 160000, n * 8, 200, 200, ua[2], up4, legacy);
-  if ((rc = conv_fwd(st, n, 8, 1, 400, 400, up4, T(50), T(51), o2))) return rc;
+  if ((rc = conv_fwd(st, n, 8, 1, 400, 400, up4, T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o2))) return rc;
 
   // ---- loss seeds ----
   float *do1 = A.f(N * 2), *do2 = A.f(N * 160000);
@@ -950,60 +997,58 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
 
   // ---- backward: head 2 ----
   float *gA = A.f(N * 8 * 160000), *gB = A.f(N * 8 * 160000);  // gradient scratch (largest tensors)
-  conv_bwd_weight(st, n, 8, 1, 400, 400, up4, do2, wpart, G(50), G(51));
-  if ((rc = conv_bwd_data(st, n, 8, 1, 400, 400, do2, T(50), gA))) return rc;   // d up4
+  conv_bwd_weight(st, n, 8, 1, 400, 400, up4, do2, wpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1));
+  if ((rc = conv_bwd_data(st, n, 8, 1, 400, 400, do2, T(OFX_T_OUT2), gA))) return rc;   // d up4
   float *dcur = gB;                                                          // d ua[2]
   K(t_up_bwd, N * 8 * 40000, n * 8, 200, 200, gA, dcur, legacy);
   for (int j = 2, s = 200; j >= 0; j--, s /= 2) {
     const size_t per = (size_t)s * s;
     float *xh = gA;                                                          // reuse as xhat
-    hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * kUO[j]), 0, st, kUO[j], per, uz[j], ua[j], ustat[j], dcur, xh);
-    hipLaunchKernelGGL(t_chan_sums, dim3(kUO[j], 64), dim3(256), 0, st, n, kUO[j], per, dcur, xh, spart);
-    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUO[j], 64, spart, sums);
+    hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, uz[j], ua[j], ustat[j], dcur, xh);
+    hipLaunchKernelGGL(t_chan_sums, dim3(kUpCout[j], 64), dim3(256), 0, st, n, kUpCout[j], per, dcur, xh, spart);
+    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUpCout[j], 64, spart, sums);
     float *dz = ua[j];                                                       // the activation is dead now: holds dz
-    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * kUO[j]), 0, st, kUO[j], per, (double)N * (double)per, dcur, xh, ustat[j], T(34 + 6 * j), sums, dz, G(34 + 6 * j), G(35 + 6 * j));
-    conv_bwd_weight(st, n, kUI[j], kUO[j], s, s, uu[j], dz, wpart, G(32 + 6 * j), G(33 + 6 * j));
+    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, (double)N * (double)per, dcur, xh, ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), sums, dz, G(ofx_t_up(j, OFX_T_GAMMA)), G(ofx_t_up(j, OFX_T_BETA)));
+    conv_bwd_weight(st, n, kUpCin[j], kUpCout[j], s, s, uu[j], dz, wpart, G(ofx_t_up(j)), G(ofx_t_up(j, OFX_T_BIAS)));
     float *duu = gA;                                                         // d (upsampled input)
-    if ((rc = conv_bwd_data(st, n, kUI[j], kUO[j], s, s, dz, T(32 + 6 * j), duu))) return rc;
+    if ((rc = conv_bwd_data(st, n, kUpCin[j], kUpCout[j], s, s, dz, T(ofx_t_up(j)), duu))) return rc;
     float *dprev = gB;                                                       // d (previous activation / u0)
-    K(t_up_bwd, N * kUI[j] * per / 4, n * kUI[j], s / 2, s / 2, duu, dprev, legacy);
+    K(t_up_bwd, N * kUpCin[j] * per / 4, n * kUpCin[j], s / 2, s / 2, duu, dprev, legacy);
     dcur = dprev;
   }
   // dcur = d u0 [n][625] (pre-mask)
-  float *dd1 = A.f(N * 100), *dd1b = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008);
+  float *dd1 = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008);
   K(t_relu_mask, N * 625, N * 625, u0, dcur);
-  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, dcur, G(30), G(31));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, dcur, T(30), dd1, 0);
+  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, dcur, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, dcur, T(OFX_T_UPDENSE), dd1, 0);
   // ---- backward: head 1 ----
-  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(28), G(29));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(28), dd2, 0);
+  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(OFX_T_OUT1), dd2, 0);
   K(t_relu_mask, N * 50, N * 50, d2, dd2);
-  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(26), G(27));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(26), dd1, 1);
-  (void)dd1b;
+  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(OFX_T_DENSE2), dd1, 1);
   // ---- dense1 + trunk ----
   K(t_relu_mask, N * 100, N * 100, d1, dd1);
-  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(24), G(25));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 1252, n, 5008, 100, dd1, T(24), df, 0);
+  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 1252, n, 5008, 100, dd1, T(OFX_T_DENSE1), df, 0);
   float *dp = gB;
   K(t_concat_bwd, N * 5000, n, df, dp);                                      // d tp[3] [n][8][25][25]
   for (int i = 3, s = 50; i >= 0; i--, s *= 2) {
     const size_t per = (size_t)s * s, tot = N * 8 * per;
     float *da = gA;
     K(t_pool_bwd, tot / 4, n * 8, s, s, ta[i], dp, da);
-    float *xh = tp[i];                                                       // pooled output is dead: reuse? too small -> use gB tail
-    xh = gB + N * 8 * 40000;                                                 // second half of gB (>= N*8*per for s <= 200)
+    float *xh = gB + N * 8 * 40000;                                          // second half of gB (>= N*8*per for s <= 200)
     if (s == 400) xh = up4;                                                  // the 400^2 layer: up4 (8 x 400^2) is dead by now
     hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * 8), 0, st, 8, per, tz[i], ta[i], tstat[i], da, xh);
     hipLaunchKernelGGL(t_chan_sums, dim3(8, 64), dim3(256), 0, st, n, 8, per, da, xh, spart);
     hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, 8, 64, spart, sums);
     float *dz = ta[i];
-    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * 8), 0, st, 8, per, (double)N * (double)per, da, xh, tstat[i], T(6 * i + 2), sums, dz, G(6 * i + 2), G(6 * i + 3));
+    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * 8), 0, st, 8, per, (double)N * (double)per, da, xh, tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), sums, dz, G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA)));
     const float *xin = i == 0 ? x0 : tp[i - 1];
-    conv_bwd_weight(st, n, kTI[i], 8, s, s, xin, dz, wpart, G(6 * i), G(6 * i + 1));
+    conv_bwd_weight(st, n, kTrunkCin[i], 8, s, s, xin, dz, wpart, G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)));
     if (i > 0) {
       dp = gB;                                                               // d tp[i-1] [n][8][s][s]
-      if ((rc = conv_bwd_data(st, n, 8, 8, s, s, dz, T(6 * i), dp))) return rc;
+      if ((rc = conv_bwd_data(st, n, 8, 8, s, s, dz, T(ofx_t_trunk(i)), dp))) return rc;
     }
   }
   if (A.over) {  // sizing bug guard: nothing has touched the weights yet
@@ -1012,26 +1057,7 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
   }
   if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
-  // ---- Adam + moving statistics ----
-  const float b1 = 0.9f, b2 = 0.999f;
-  const float lr_t = lr * sqrtf(1.f - powf(b2, (float)step)) / (1.f - powf(b1, (float)step));
-  for (int t = 0; t < L.n_tensors; t++) {
-    const bool conv_bn = t < 24 || (t >= 32 && t < 50);
-    const int k = conv_bn ? (t < 24 ? t % 6 : (t - 32) % 6) : -1;
-    if (k == 4 || k == 5) continue;  // moving mean / variance: not trained
-    K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
-      adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
-  }
-  for (int i = 0; i < 4; i++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[6 * i + 4], weights + L.offset[6 * i + 5], tstat[i]);
-  for (int j = 0; j < 3; j++) hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUO[j], weights + L.offset[32 + 6 * j + 4], weights + L.offset[32 + 6 * j + 5], ustat[j]);
-  OFX_HIP(hipGetLastError());
-  float lh[2] = {0.f, 0.f};
-  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(lh), hipMemcpyDeviceToHost, st));
-  OFX_HIP(hipStreamSynchronize(st));
-  if (loss_host) { loss_host[0] = lh[0]; loss_host[1] = lh[1]; }
-  (void)W_;
-  if ((rc = ofx_policy_weights_updated(h, weights))) return rc;  // a pinned blob is prepared again
-  return OFX_OK;
+  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host);
 }
 
 extern "C" int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
@@ -1086,7 +1112,7 @@ extern "C" int ofx_dqn_fit_reference(ofx_handle *h, float *weights, float *adam_
   float *buf = (float *)h->fitws2;
   float *vec_prev = buf, *vec_next = vec_prev + 8 * N, *act_next = vec_next + 8 * N, *max_next = act_next + 2 * N;
   float *t1 = max_next + N, *t2 = t1 + 2 * N;
-  K(t_unpack_heads, N, n, rows, vec_prev, vec_next);
+  K(k_dqn_unpack, N, n, rows, vec_prev, vec_next, (int32_t *)nullptr);   // (padding rows were refused above)
   if ((rc = ofx_policy_predict_obs(h, weights, n, bits_prev, vec_prev, t1, t2, nullptr))) return rc;
   if ((rc = ofx_policy_predict_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, max_next))) return rc;
   K(t_reference_targets, N, n, rows, gamma, act_next, max_next, t1, t2);

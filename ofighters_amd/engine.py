@@ -334,7 +334,7 @@ class ArenaBatch:
     def policy_forward(self, weights_ptr, ship_mask_ptr=None, act_ptr=None, iaction_ptr=None, ipointer_ptr=None,
                        heat_ptr=None):
         """Bi-head forward for every (arena, ship) on the CURRENT state (device pointers;
-        None outputs stay inside the handle's workspace for policy_actions)."""
+        None iaction / ipointer are kept by the handle for policy_explore / policy_actions / replay_capture)."""
         nat.check(nat.lib().ofx_policy_forward(self._h, weights_ptr, ship_mask_ptr, act_ptr, iaction_ptr,
                                                ipointer_ptr, heat_ptr))
 

@@ -52,3 +52,25 @@ def test_trainer_save_load(tmp_path):
     u = Trainer()
     u.load(path)
     assert np.array_equal(u.weights, t.weights)
+
+
+def test_layout_matches_the_library():
+    """The blob is described three times: layout() here, csrc/ofx_blob.h (ofx_policy_layout reports it; no device
+    needed) and the named tensor indices of that header, restated below.  52 tensors, the same offsets and counts."""
+    import ctypes as C
+    from ofighters_amd import _native as nat
+    off, cnt, total = pw.layout()
+    assert len(off) == len(cnt) == 52
+    d = nat.OfxPolicyDesc()
+    nat.check(nat.lib().ofx_policy_layout(None, C.byref(d)))
+    assert d.n_tensors == 52 and d.n_floats == total
+    assert list(d.offset[:52]) == off and list(d.count[:52]) == cnt
+    # OFX_T_DENSE1 / DENSE2 / OUT1 / UPDENSE / OUT2: kernel, then bias
+    for t, (fi, fo) in zip((24, 26, 28, 30), pw.DENSE):
+        assert (d.count[t], d.count[t + 1]) == (fi * fo, fo)
+    assert (d.count[50], d.count[51]) == (72, 1)
+    # ofx_t_trunk(i, part) = 6 i + part, ofx_t_up(j, part) = 32 + 6 j + part: kernel, bias, gamma, beta, mean, variance
+    for i, cin in enumerate(pw.TRUNK_CIN):
+        assert [d.count[6 * i + k] for k in range(6)] == [9 * cin * 8] + [8] * 5
+    for j, (ci, co) in enumerate(pw.UPCONV):
+        assert [d.count[32 + 6 * j + k] for k in range(6)] == [9 * ci * co] + [co] * 5
