@@ -501,6 +501,40 @@ int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const 
                           const void *bits_prev, const void *bits_next, const float *ret, const float *disc,
                           float *q_sa, float *p_sp, float *y_act, float *y_ptr);
 
+/* ---- target network and Double DQN (opt-in) -----------------------------
+ * Not in the reference.  Off unless these two calls are used; nothing above changes.  A target network is a second
+ * weight blob in the ofx_policy_layout order that the caller keeps and moves towards the trained one with
+ * ofx_policy_blend_weights; the plain targets bootstrap from it when ofx_dqn_targets / ofx_dqn_targets_nstep are given
+ * that blob.  Double DQN (van Hasselt et al. 2016) selects with the online blob and evaluates with the target blob:
+ *  - Selection, per real row i: a* = iaction and p* = ipointer that ofx_policy_forward_obs(online, next_state) returns
+ *    (the first maximum, as np.argmax).
+ *  - Evaluation: v_act = act_values(target, next_state)[a*]; v_ptr = ptr_probe of
+ *    ofx_policy_forward_obs(target, next_state, probe = p*), the value the target's arg-max pass holds at that pixel.
+ *  - One-step form (ret == disc == NULL): y_act = (float)reward + gamma * v_act * live and
+ *    y_ptr = (float)reward + gamma * v_ptr * live with live = done ? 0 : 1 - the expression and the rounding of
+ *    ofx_dqn_targets, every operation rounded on its own.
+ *  - n-step form (ret and disc given, as ofx_replay_gather_nstep wrote them): y = ret + disc * v in float32, the product
+ *    rounded, then the sum (no FMA); gamma is ignored.  Exactly one of ret / disc NULL is OFX_ERR_INVALID.
+ *  - Everything else as ofx_dqn_targets: q_sa / p_sp come from `online` on `state`, both NULL or both given (NULL skips
+ *    that forward); padding rows (ship < 0) give zeros; the same argument checks (a NULL target is OFX_ERR_INVALID).
+ *  - target == online (the same pointer) is allowed: the value at the arg-max is the maximum, so the results are
+ *    ofx_dqn_targets' / ofx_dqn_targets_nstep's bit for bit (NaN outputs excepted: max() skips a NaN, a selection does
+ *    not).
+ *  - Order on the handle's stream: online on `state` (when asked for), online on next_state, target on next_state, one
+ *    kernel for the selection and the TD arithmetic.  A pinned online blob uses its prepared weights; the target blob is
+ *    prepared per call in the handle's second slot, so the pinned preparation survives.  Does not synchronise.
+ *  - Blend: ofx_policy_blend_weights moves the whole blob (ofx_policy_layout n_floats, every tensor, the BatchNorm
+ *    moving statistics included): dst[i] = c * dst[i] + tau * src[i] with c = 1.0f - tau formed once in float32, both
+ *    products rounded, then the sum (no FMA).  tau == 1 is a plain device copy (a dst that has become NaN recovers on
+ *    a hard sync), tau == 0 changes nothing.  Runs on the handle's stream, does not synchronise.  When dst is the
+ *    handle's pinned blob its preparation is redone, as after a fit.  dst and src must not overlap.
+ * Errors (nothing is written): ofx_policy_blend_weights gives OFX_ERR_INVALID for a NULL handle or blob, for
+ * dst == src and for tau not finite or outside [0, 1].                                                             */
+int ofx_dqn_targets_double(ofx_handle *h, const float *online, const float *target, int32_t n,
+                           const ofx_transition *rows, const void *bits_prev, const void *bits_next, float gamma,
+                           const float *ret, const float *disc, float *q_sa, float *p_sp, float *y_act, float *y_ptr);
+int ofx_policy_blend_weights(ofx_handle *h, float *dst, const float *src, float tau);
+
 /* ---- forward on stored observations, TD targets -------------------------
  * The predictions Trainer.replay makes on a minibatch (agents/qlearnIA_V2.py:251-268): n_obs observations given as
  * 1-bit map pairs bits[n_obs][2 (ship, laser)][W*H/32] uint32 (the layout ofx_replay_gather writes) + their toVector

@@ -137,6 +137,8 @@ SIGNATURES = {
     "ofx_replay_gather_nstep": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp,
                                      _vp, _vp, _vp]),
     "ofx_dqn_targets_nstep": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofx_dqn_targets_double": (_i, [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofx_policy_blend_weights": (_i, [_vp, _vp, _vp, C.c_float]),
     "ofx_timer_start": (_i, [_vp]),
     "ofx_timer_stop": (_i, [_vp, C.POINTER(C.c_float)]),
     "ofx_event_record": (_i, [_vp, C.c_int32]),

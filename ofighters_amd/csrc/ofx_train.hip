@@ -512,6 +512,44 @@ __global__ void k_dqn_targets(int n, const ofx_transition *rows, float gamma, co
   y_ptr[i] = (float)r.reward + gamma * max_next[i] * live;  // np.max(ptr_prediction)
 }
 
+// Double DQN (ofx_dqn_targets_double): the online network selects, the target network evaluates.  sel_action [n] is the
+// online forward's iaction on next_state (the first maximum), act_tgt [n][2] the target network's action values there
+// and probe_tgt [n] its heat map probed at the online forward's ipointer.  The TD arithmetic is k_dqn_targets' with
+// the two maxima replaced by the selected values: the same expressions, every operation rounded on its own.
+__global__ void k_dqn_targets_double(int n, const ofx_transition *rows, float gamma, const float *act_prev,
+                                     const float *probe_prev, const int32_t *sel_action, const float *act_tgt,
+                                     const float *probe_tgt, float *q_sa, float *p_sp, float *y_act, float *y_ptr,
+                                     const float *ret, const float *disc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ofx_transition r = rows[i];
+  if (r.ship < 0) {
+    if (q_sa) q_sa[i] = p_sp[i] = 0.f;
+    y_act[i] = y_ptr[i] = 0.f;
+    return;
+  }
+  if (q_sa) {   // the online forward on `state` was run
+    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
+    p_sp[i] = probe_prev[i];
+  }
+  const float v_act = act_tgt[2 * i + (sel_action[i] ? 1 : 0)], v_ptr = probe_tgt[i];
+  if (ret) {                                                          // n-step: ret + disc * v
+    y_act[i] = ret[i] + disc[i] * v_act;
+    y_ptr[i] = ret[i] + disc[i] * v_ptr;
+    return;
+  }
+  const float live = r.done ? 0.f : 1.f;  // int(not done)
+  y_act[i] = (float)r.reward + gamma * v_act * live;
+  y_ptr[i] = (float)r.reward + gamma * v_ptr * live;
+}
+
+// ofx_policy_blend_weights: dst = c * dst + tau * src with c = 1 - tau formed once by the caller; both products are
+// rounded, then the sum (this file is compiled with -ffp-contract=off)
+__global__ void k_blend_weights(size_t cnt, float *dst, const float *src, float c, float tau) {
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x)
+    dst[e] = c * dst[e] + tau * src[e];
+}
+
 // the rows' observation heads [n][8] and (probe, may be null) clamped pointers [n][2]; zeros for a padding row
 __global__ void k_dqn_unpack(int n, const ofx_transition *rows, float *vec_prev, float *vec_next, int32_t *probe) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -660,17 +698,22 @@ static int refuse_pads(ofx_handle *h, int n, const ofx_transition *rows, const c
   return OFX_OK;
 }
 
-// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch
-static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, int32_t n, const ofx_transition *rows,
-                            const void *bits_prev, const void *bits_next, float gamma, const float *ret, const float *disc,
-                            float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
-  if (!h || !weights || !rows || !bits_prev || !bits_next || (!q_sa) != (!p_sp) || !y_act || !y_ptr || n < 1) {
+// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch.
+// ofx_dqn_targets_double (dbl; `weights` is the online blob): the forward on next_state runs twice - online for
+// (iaction, ipointer), then `target` probed at that pointer - and k_dqn_targets_double takes the place of k_dqn_targets.
+// What one forward hands to the next lives in the aux arena: the forward's scratch block is laid out anew by each.
+static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, const float *target, bool dbl, int32_t n,
+                            const ofx_transition *rows, const void *bits_prev, const void *bits_next, float gamma,
+                            const float *ret, const float *disc, float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
+  if (!h || !weights || (dbl && !target) || !rows || !bits_prev || !bits_next || (!q_sa) != (!p_sp) || !y_act || !y_ptr ||
+      n < 1) {
     ofx_set_error("%s: bad argument", who);
     return OFX_ERR_INVALID;
   }
   OFX_HIP(hipSetDevice(h->cfg.device));
   const size_t nn = (size_t)n;
-  const size_t need = 7 * 256 + 4 * nn * (8 + 8 + 2 + 2 + 2 + 1 + 1);   // seven arrays, each rounded up to 256 bytes
+  // seven arrays (four more for the double form), each rounded up to 256 bytes
+  const size_t need = 7 * 256 + 4 * nn * (8 + 8 + 2 + 2 + 2 + 1 + 1) + (dbl ? 4 * 256 + 4 * nn * (1 + 2 + 2 + 1) : 0);
   int rc = ofx_ensure_buffer(h, &h->aux, &h->aux_bytes, need);
   if (rc) return rc;
   Arena A{(char *)h->aux, 0, need};
@@ -683,6 +726,19 @@ static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights
   // on `state` is skipped
   if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, vec_prev, act_prev, nullptr, nullptr, nullptr, probe, probe_prev)))
     return rc;
+  if (dbl) {
+    int32_t *sel_action = (int32_t *)A.f(nn), *sel_pointer = (int32_t *)A.f(2 * nn);
+    float *act_tgt = A.f(2 * nn), *probe_tgt = A.f(nn);
+    // online first (the pinned slot when `weights` is the pinned blob), then the target through prep_tmp
+    if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, nullptr, sel_action, sel_pointer, nullptr, nullptr, nullptr)))
+      return rc;
+    if ((rc = ofx_policy_forward_obs(h, target, n, bits_next, vec_next, act_tgt, nullptr, nullptr, nullptr, sel_pointer, probe_tgt)))
+      return rc;
+    hipLaunchKernelGGL(k_dqn_targets_double, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev,
+                       probe_prev, sel_action, act_tgt, probe_tgt, q_sa, p_sp, y_act, y_ptr, ret, disc);
+    OFX_HIP(hipGetLastError());
+    return OFX_OK;
+  }
   if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, nullptr, max_next, nullptr, nullptr)))
     return rc;
   hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev, probe_prev,
@@ -694,16 +750,48 @@ static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights
 extern "C" int ofx_dqn_targets(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
                                const void *bits_prev, const void *bits_next, float gamma, float *q_sa, float *p_sp,
                                float *y_act, float *y_ptr) {
-  return dqn_targets_impl(h, "ofx_dqn_targets", weights, n, rows, bits_prev, bits_next, gamma, nullptr, nullptr, q_sa,
-                          p_sp, y_act, y_ptr);
+  return dqn_targets_impl(h, "ofx_dqn_targets", weights, nullptr, false, n, rows, bits_prev, bits_next, gamma, nullptr,
+                          nullptr, q_sa, p_sp, y_act, y_ptr);
 }
 
 extern "C" int ofx_dqn_targets_nstep(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
                                      const void *bits_prev, const void *bits_next, const float *ret, const float *disc,
                                      float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
   if (!ret || !disc) { ofx_set_error("ofx_dqn_targets_nstep: ret and disc must be given"); return OFX_ERR_INVALID; }
-  return dqn_targets_impl(h, "ofx_dqn_targets_nstep", weights, n, rows, bits_prev, bits_next, 0.f, ret, disc, q_sa, p_sp,
-                          y_act, y_ptr);
+  return dqn_targets_impl(h, "ofx_dqn_targets_nstep", weights, nullptr, false, n, rows, bits_prev, bits_next, 0.f, ret,
+                          disc, q_sa, p_sp, y_act, y_ptr);
+}
+
+extern "C" int ofx_dqn_targets_double(ofx_handle *h, const float *online, const float *target, int32_t n,
+                                      const ofx_transition *rows, const void *bits_prev, const void *bits_next,
+                                      float gamma, const float *ret, const float *disc, float *q_sa, float *p_sp,
+                                      float *y_act, float *y_ptr) {
+  if ((!ret) != (!disc)) { ofx_set_error("ofx_dqn_targets_double: pass ret and disc together"); return OFX_ERR_INVALID; }
+  return dqn_targets_impl(h, "ofx_dqn_targets_double", online, target, true, n, rows, bits_prev, bits_next,
+                          ret ? 0.f : gamma, ret, disc, q_sa, p_sp, y_act, y_ptr);
+}
+
+// Soft / hard update of a target network: the whole blob, BatchNorm moving statistics included.  tau == 1 is a copy (a
+// NaN in dst must not survive 0 * NaN), tau == 0 is nothing at all.
+extern "C" int ofx_policy_blend_weights(ofx_handle *h, float *dst, const float *src, float tau) {
+  if (!h || !dst || !src || dst == src) {
+    ofx_set_error("ofx_policy_blend_weights: bad argument (null, or dst == src)");
+    return OFX_ERR_INVALID;
+  }
+  if (!(tau >= 0.f && tau <= 1.f)) {   // NaN fails both comparisons
+    ofx_set_error("ofx_policy_blend_weights: tau must lie in [0, 1], got %g", (double)tau);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  hipStream_t st = h->stream;
+  ofx_policy_desc L;
+  int rc = ofx_policy_layout(h, &L);
+  if (rc) return rc;
+  if (tau == 0.f) return OFX_OK;
+  const size_t cnt = (size_t)L.n_floats;
+  if (tau == 1.f) OFX_HIP(hipMemcpyAsync(dst, src, sizeof(float) * cnt, hipMemcpyDeviceToDevice, st));
+  else K(k_blend_weights, cnt, cnt, dst, src, 1.0f - tau, tau);
+  return ofx_policy_weights_updated(h, dst);
 }
 
 // The tail of a fit step, after the gradients: Adam on the trained tensors, the moving BatchNorm statistics from the batch

@@ -549,6 +549,21 @@ class ArenaBatch:
         self.sync()
         return tuple(b.download(np.float32, (n,)) if b else None for b in bufs)
 
+    # ------------------------------------------- target network and Double DQN (include/ofx.h: the contract)
+    def dqn_targets_double_into(self, online_ptr, target_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr, gamma, y_act_ptr,
+                                y_ptr_ptr, ret_ptr=None, disc_ptr=None, q_sa_ptr=None, p_sp_ptr=None):
+        """Double DQN targets into the caller's device arrays: the online blob selects (iaction, ipointer) on next_state,
+        the target blob evaluates them.  ret / disc (replay_gather_nstep_into) select the n-step form.  Does not
+        synchronise."""
+        nat.check(nat.lib().ofx_dqn_targets_double(self._h, online_ptr, target_ptr, int(n), rows_ptr, bits_prev_ptr,
+                                                    bits_next_ptr, float(gamma), ret_ptr, disc_ptr, q_sa_ptr, p_sp_ptr,
+                                                    y_act_ptr, y_ptr_ptr))
+
+    def policy_blend_weights(self, dst_buf, src_buf, tau):
+        """dst = (1 - tau) * dst + tau * src over the whole weight blob (DeviceBuffers; tau = 1: a device copy) on the
+        handle's stream: the soft / hard update of a target network.  Does not synchronise."""
+        nat.check(nat.lib().ofx_policy_blend_weights(self._h, dst_buf.ptr, src_buf.ptr, float(tau)))
+
     def policy_forward_obs(self, weights_ptr, n_obs, bits_ptr, vec8_ptr, want_probe_ptr=None):
         """Forward on stored observations (Trainer.replay's predictions): host dict of act / iaction / ipointer /
         ptr_max (+ ptr_probe when want_probe_ptr, an int32 [n_obs][2] device array of (x, y), is given)."""

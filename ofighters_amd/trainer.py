@@ -15,7 +15,16 @@ ofx_replay_gather_nstep follows each sampled row's ship through its following ro
 restart or the newest row), gathers the chain's last next-state maps and the discounted return ret = sum gamma^k r_k with
 the discount disc = gamma^L (0 after a death), and ofx_dqn_targets_nstep forms y = ret + disc * max(next_state).  Works
 with `prioritized` (the priorities become n-step TD errors); the return is not corrected for the off-policy actions
-inside the chain (as in Rainbow)."""
+inside the chain (as in Rainbow).
+
+`target_sync=K` or `target_tau=tau` (opt-in, not in the reference; one of them) keeps a target network: a second device
+blob that starts as a copy of the initial weights and that the targets bootstrap from instead of the blob being fitted.
+After every fit step ofx_policy_blend_weights moves it: a hard copy of the online weights after every K-th step
+(fit_steps % K == 0), or target = (1 - tau) * target + tau * online after each one.  `double_dqn=True` forms the targets
+with ofx_dqn_targets_double (van Hasselt et al. 2016): the online blob selects the next action and pointer, the target
+blob evaluates them (without a target network both are the online blob, which gives the plain targets).  All of it works
+with `prioritized` and `n_step`; the fit's current values and TD errors always come from the online blob, and save()
+stores the online blob only."""
 import numpy as np
 
 from .engine import DeviceBuffer
@@ -25,7 +34,7 @@ from .lib.epsilon import Epsilon_cos
 class DeviceTrainer:
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
-                 per_beta_steps=50_000, per_eps=1e-3, n_step=1):
+                 per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False):
         if prioritized and reference_quirks:
             raise ValueError("DeviceTrainer: prioritized replay needs the textbook fit (reference_quirks=False)")
         if int(n_step) != n_step or n_step < 1:
@@ -33,6 +42,15 @@ class DeviceTrainer:
         if n_step > 1 and reference_quirks:
             raise ValueError("DeviceTrainer: n-step returns need the textbook fit (reference_quirks=False computes its own "
                              "one-step targets)")
+        if isinstance(target_sync, bool) or not isinstance(target_sync, (int, np.integer)) or target_sync < 0:
+            raise ValueError("DeviceTrainer: target_sync must be an integer >= 0, got %r" % (target_sync,))
+        if target_tau is not None and not (0.0 < float(target_tau) <= 1.0):      # NaN fails the comparison
+            raise ValueError("DeviceTrainer: target_tau must lie in (0, 1], got %r" % (target_tau,))
+        if target_sync and target_tau is not None:
+            raise ValueError("DeviceTrainer: give target_sync (hard copies) or target_tau (soft updates), not both")
+        if (target_sync or target_tau is not None or double_dqn) and reference_quirks:
+            raise ValueError("DeviceTrainer: a target network / Double DQN needs the textbook fit (reference_quirks=False "
+                             "computes its own targets)")
         self.batch = batch                                  # the ArenaBatch this trainer plays and learns on
         w = np.ascontiguousarray(weights, np.float32)
         self.n_floats = w.size
@@ -40,6 +58,11 @@ class DeviceTrainer:
         zeros = np.zeros_like(w)
         self.adam_m = DeviceBuffer(w.nbytes).upload(zeros)
         self.adam_v = DeviceBuffer(w.nbytes).upload(zeros)
+        self.target_sync = int(target_sync)                 # K > 0: target <- online after every K-th fit step
+        self.target_tau = None if target_tau is None else float(target_tau)   # target <- (1 - tau) target + tau online
+        self.double_dqn = bool(double_dqn)                  # select with the online blob, evaluate with the target blob
+        # the target network: a device copy of the initial weights, or None (the targets bootstrap from self.weights)
+        self.target = DeviceBuffer(w.nbytes).upload(w) if (self.target_sync or self.target_tau is not None) else None
         self.learning_rate = learning_rate                  # lr = 0.0001 (qlearnIA_V2.py:306)
         self.gamma = 0.9                                    # :51
         self.epsilon = epsilon if epsilon is not None else Epsilon_cos(period=110 * 400)
@@ -76,6 +99,13 @@ class DeviceTrainer:
     def weights_host(self):
         self.batch.sync()
         return self.weights.download(np.float32, (self.n_floats,))
+
+    def target_host(self):
+        """The target network's blob like weights_host(), or None without a target network."""
+        if self.target is None:
+            return None
+        self.batch.sync()
+        return self.target.download(np.float32, (self.n_floats,))
 
     def save(self, id=None, overwrite=False, folder="networks", name="bi_head_pointer"):
         """Trainer.save (qlearnIA_V2.py:289-298): `keras-model-<name>[-<id>]` under the networks folder, as the .npz
@@ -131,6 +161,7 @@ class DeviceTrainer:
         self.fit_steps += 1
         loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
                          y_act.ptr, y_ptr.ptr)
+        self._move_target()
         self.losses.append(loss)
         return loss
 
@@ -146,15 +177,32 @@ class DeviceTrainer:
 
     def _targets(self, n, rows_p, prev_p, next_p, y_act, y_ptr):
         """y_act / y_ptr of the gathered window.  q_sa / p_sp (the current values at the chosen action / pointer) are not
-        asked for: the fit's own training-mode forward produces them, so the targets need the forward on next_state only."""
+        asked for: the fit's own training-mode forward produces them, so the targets need the forward on next_state only.
+        They bootstrap from the target network when there is one; with double_dqn the online blob selects what it
+        evaluates."""
         from . import _native as nat
-        h, w = self.batch.handle, self.weights.ptr
-        if self.n_step == 1:
+        h = self.batch.handle
+        w = self.target.ptr if self.target is not None else self.weights.ptr
+        nstep = self.n_step > 1
+        if self.double_dqn:
+            self.batch.dqn_targets_double_into(self.weights.ptr, w, n, rows_p, prev_p, next_p, self.gamma, y_act.ptr,
+                                               y_ptr.ptr, self._buf["ret"].ptr if nstep else None,
+                                               self._buf["disc"].ptr if nstep else None)
+        elif not nstep:
             nat.check(nat.lib().ofx_dqn_targets(h, w, n, rows_p, prev_p, next_p, float(self.gamma), None, None, y_act.ptr,
                                                  y_ptr.ptr))
         else:
             nat.check(nat.lib().ofx_dqn_targets_nstep(h, w, n, rows_p, prev_p, next_p, self._buf["ret"].ptr,
                                                        self._buf["disc"].ptr, None, None, y_act.ptr, y_ptr.ptr))
+
+    def _move_target(self):
+        """After a fit step: the hard copy of every target_sync-th step or the soft update of each one (on the stream)."""
+        if self.target is None:
+            return
+        if self.target_tau is not None:
+            self.batch.policy_blend_weights(self.target, self.weights, self.target_tau)
+        elif self.fit_steps % self.target_sync == 0:
+            self.batch.policy_blend_weights(self.target, self.weights, 1.0)
 
     def beta(self):
         """The IS exponent of the next fit step: per_beta -> 1.0 linearly over per_beta_steps fit steps."""
@@ -189,5 +237,6 @@ class DeviceTrainer:
         loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows.ptr,
                                   bits_prev.ptr, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
         b.replay_update_priorities(slot, n_s, bs, start, n, rows.ptr, td.ptr)
+        self._move_target()
         self.losses.append(loss)
         return loss
