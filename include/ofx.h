@@ -578,6 +578,24 @@ int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int
 int ofx_dqn_fit_weighted(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                          const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
                          float *grad_out, float *loss_host, const float *row_weight, float *td_out);
+/* ofx_dqn_fit_weighted with the two error bounds every DQN since Mnih et al. 2015 carries, both opt-in (0 = off):
+ *   huber_delta > 0: Keras Huber(delta) in place of the squared error, h(e) = 0.5 e^2 for |e| <= delta, else
+ *     delta |e| - 0.5 delta^2; loss1 = sum w h(e1) / (2 n), loss2 = sum w h(e2) / (160000 n), seeds
+ *     w clamp(e, -delta, delta) over the same denominators.  Inside the quadratic zone that is HALF the gradient of the
+ *     'mse' fit (0.5 e^2 against e^2), as in Keras: a delta above every error is not the squared-error fit but that fit at
+ *     half the learning signal.  td_out keeps the raw (e1, e2) - priorities stay |TD error| - and loss_host returns the
+ *     Huber losses.
+ *   clip_norm > 0: torch.nn.utils.clip_grad_norm_ over the whole gradient blob: norm = sqrt(sum g^2) (summed in double
+ *     in a fixed order: the step stays reproducible to the bit), Adam consumes min(1, clip_norm / (norm + 1e-6)) g.
+ *     grad_out receives the gradient BEFORE scaling.
+ * grad_norm_host (may be NULL) receives the norm before clipping; it is computed when it is asked for or clip_norm > 0
+ * and read back with the loss (no further synchronisation).  Textbook (sparse-target) form only, lean and
+ * OFX_OPT_FIT_PLAIN.  A negative or non-finite huber_delta / clip_norm fails with OFX_ERR_INVALID before anything is
+ * launched.  huber_delta == 0, clip_norm == 0 and grad_norm_host == NULL launch exactly what ofx_dqn_fit_weighted does. */
+int ofx_dqn_fit_robust(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
+                       const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
+                       float *grad_out, float *loss_host, const float *row_weight, float *td_out, float huber_delta,
+                       float clip_norm, float *grad_norm_host);
 /* The same step with Trainer.replay's quirks reproduced as written (agents/qlearnIA_V2.py:251-285), for a user who
  * wants the reference's training dynamics rather than the textbook DQN step above:
  *   - targets are whole predictions of `state` ([target, ptr_target] = predict(state), inference-mode BatchNorm) with

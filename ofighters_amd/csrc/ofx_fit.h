@@ -74,8 +74,20 @@ int ofx_fit_out_fwd(hipStream_t st, int n, const ofx_fit_src &src, const float *
 int ofx_fit_out_bw(hipStream_t st, int n, const ofx_fit_src &src, const float *d2, double *part, double *fpart, float *dw,
                    float *db);
 // the top of head 2 when d o2 has one non-zero per sample (ofx_dqn_fit's targets): see ofx_fit.hip
+// huber_delta > 0 (ofx_dqn_fit_robust): the seeds and loss shares of Huber(delta); 0 launches the squared-error seed kernel
 size_t ofx_fit_point_doubles(int n);
 int ofx_fit_top_point(hipStream_t st, int n, const ofx_transition *rows, const ofx_fit_src &src, const float *w, const float *b,
                       const float *o1, const float *y_act, const float *y_ptr, const float *stat, float *o2p, float *do1,
                       float *d2p, float *lpart, float *gpatch, double *scratch, double *sums, float *dw, float *db,
-                      const float *row_weight = nullptr, float *td_out = nullptr);
+                      const float *row_weight = nullptr, float *td_out = nullptr, float huber_delta = 0.f);
+
+// Keras Huber(delta) on one error: returns h(e) = 0.5 e^2 for |e| <= delta, else delta (|e| - 0.5 delta), and leaves
+// h'(e) = clamp(e, -delta, delta) in *slope.  Shared by the seed kernels of both forms of the fit (ofx_train.hip and
+// ofx_fit.hip are built with different -ffp-contract settings): no product here feeds a sum, so neither setting can fuse
+// anything and both forms seed the backward pass with the same bits.
+__device__ __forceinline__ float ofx_huber(float e, float delta, float *slope) {
+  const float a = fabsf(e);
+  if (a <= delta) { *slope = e; return 0.5f * e * e; }
+  *slope = e > 0.f ? delta : -delta;
+  return delta * (a - 0.5f * delta);
+}

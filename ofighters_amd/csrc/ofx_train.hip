@@ -19,6 +19,7 @@
 #include "ofx_internal.h"
 #include "ofx_blob.h"
 #include "ofx_fit.h"
+#include <float.h>
 #include <string.h>
 
 #define TPS 400
@@ -457,6 +458,28 @@ __global__ void t_loss_seed(int n, const ofx_transition *rows, const float *o1, 
   lpart[2 * s + 1] = w * e2 * e2 / ((float)(TPS * TPS) * n);
   if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
 }
+// t_loss_seed under Huber(delta) (ofx_dqn_fit_robust, delta > 0): seeds w clamp(e, -delta, delta) and loss shares w h(e)
+// over the same denominators - half the squared-error seed inside the quadratic zone, as in Keras; td keeps the raw errors
+__global__ void t_loss_seed_huber(int n, const ofx_transition *rows, const float *o1, const float *o2, const float *y_act,
+                                  const float *y_ptr, float *do1, float *do2, float *lpart, const float *rw, float *td,
+                                  float delta) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const ofx_transition r = rows[s];
+  if (r.ship < 0) { lpart[2 * s] = lpart[2 * s + 1] = 0.f; return; }  // padding row: no error
+  const int a = r.iaction ? 1 : 0, px = min(max(r.px, 0), TPS - 1), py = min(max(r.py, 0), TPS - 1);
+  const float e1 = o1[2 * s + a] - y_act[s];
+  const size_t k = (size_t)s * TPS * TPS + (size_t)py * TPS + px;
+  const float e2 = o2[k] - y_ptr[s];
+  const float w = rw ? rw[s] : 1.f;
+  float c1, c2;
+  const float h1 = ofx_huber(e1, delta, &c1), h2 = ofx_huber(e2, delta, &c2);
+  do1[2 * s + a] = w * c1 / (2.f * n);
+  do2[k] = w * c2 / ((float)(TPS * TPS) * n);
+  lpart[2 * s] = w * h1 / (2.f * n);      // summed in sample order by t_sum_ordered
+  lpart[2 * s + 1] = w * h2 / ((float)(TPS * TPS) * n);
+  if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
+}
 // out[j] = sum_i part[i * stride + j] for j < stride, in index order (one thread per j: tiny)
 __global__ void t_sum_ordered(int count, int stride, const float *part, float *out) {
   const int j = threadIdx.x;
@@ -464,6 +487,36 @@ __global__ void t_sum_ordered(int count, int stride, const float *part, float *o
   double acc = 0.0;
   for (int i = 0; i < count; i++) acc += (double)part[(size_t)i * stride + j];
   out[j] = (float)acc;
+}
+
+// ---- global gradient norm (ofx_dqn_fit_robust): sum g^2 over the whole blob, the same bits on every run ----
+// A fixed grid of kNormBlocks x 256; each thread sums its grid-stride share in double, the four wave64s of a block
+// combine in LDS by a fixed tree, part[block] goes to t_clip_scale.
+static const int kNormBlocks = 256;
+__global__ __launch_bounds__(256) void t_sqnorm_part(size_t cnt, const float *g, double *part) {
+  __shared__ double red[256];
+  double acc = 0.0;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
+    const double v = (double)g[e];
+    acc += v * v;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int k = 128; k > 0; k >>= 1) {
+    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+// one thread, like t_sum_ordered: the block partials in index order, then out[0] = norm and out[1] = the factor of
+// torch.nn.utils.clip_grad_norm_, min(1, clip / (norm + 1e-6)) in fp32 (clip == 0: no clipping, 1)
+__global__ void t_clip_scale(int count, const double *part, float clip, float *out) {
+  if (threadIdx.x || blockIdx.x) return;
+  double acc = 0.0;
+  for (int i = 0; i < count; i++) acc += part[i];
+  const float norm = (float)sqrt(acc);
+  out[0] = norm;
+  out[1] = clip > 0.f ? fminf(1.f, clip / (norm + 1e-6f)) : 1.f;
 }
 
 // Trainer.replay as written (ofx_dqn_fit_reference): the targets are whole predictions of `state` with one entry
@@ -590,6 +643,18 @@ __global__ void t_adam(size_t cnt, float *w, const float *g, float *m, float *v,
                        float c2, float eps) {
   for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
     const float gi = g[e];
+    const float mi = b1 * m[e] + c1 * gi, vi = b2 * v[e] + c2 * gi * gi;
+    m[e] = mi; v[e] = vi;
+    w[e] -= lr_t * mi / (sqrtf(vi) + eps);
+  }
+}
+// t_adam on scale[0] * g, the factor t_clip_scale left in device memory (no host round trip between the gradient and the
+// update); a factor of exactly 1 - the clip inactive - gives t_adam's bits
+__global__ void t_adam_scaled(size_t cnt, float *w, const float *g, float *m, float *v, float lr_t, float b1, float b2,
+                              float c1, float c2, float eps, const float *scale) {
+  const float sc = scale[0];
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
+    const float gi = sc * g[e];
     const float mi = b1 * m[e] + c1 * gi, vi = b2 * v[e] + c2 * gi * gi;
     m[e] = mi; v[e] = vi;
     w[e] -= lr_t * mi / (sqrtf(vi) + eps);
@@ -796,16 +861,33 @@ extern "C" int ofx_policy_blend_weights(ofx_handle *h, float *dst, const float *
 
 // The tail of a fit step, after the gradients: Adam on the trained tensors, the moving BatchNorm statistics from the batch
 // statistics (tstat / ustat: trunk / head-2 layers), the loss read back (a synchronisation), a pinned blob prepared again.
+// ofx_dqn_fit_robust (R.clip_norm > 0 or R.grad_norm_host given): the gradient's global norm and the clip factor go to
+// loss[2] / loss[3] - the slot is 64 floats - so the copy that fetches the loss fetches the norm too; with a clip, Adam
+// reads the factor from there.  npart: kNormBlocks doubles.
+struct FitRobust {
+  float huber_delta = 0.f, clip_norm = 0.f;
+  float *grad_norm_host = nullptr;
+  bool norm() const { return clip_norm > 0.f || grad_norm_host; }
+};
 static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weights, const float *grad, float *adam_m,
                             float *adam_v, int32_t step, float lr, float *const *tstat, float *const *ustat,
-                            const float *loss, float *loss_host) {
+                            float *loss, float *loss_host, const FitRobust &R, double *npart) {
   hipStream_t st = h->stream;
   const float b1 = 0.9f, b2 = 0.999f;
   const float lr_t = lr * sqrtf(1.f - powf(b2, (float)step)) / (1.f - powf(b1, (float)step));
+  if (R.norm()) {   // untrained slots of the gradient blob are zero: one pass over all of it
+    hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
+    hipLaunchKernelGGL(t_clip_scale, dim3(1), dim3(64), 0, st, kNormBlocks, npart, R.clip_norm, loss + 2);
+    OFX_HIP(hipGetLastError());
+  }
   for (int t = 0; t < L.n_tensors; t++) {
     if (!ofx_blob_trained(t)) continue;  // moving mean / variance
-    K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
-      adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
+    if (R.clip_norm > 0.f)
+      K(t_adam_scaled, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t],
+        adam_m + L.offset[t], adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f, loss + 3);
+    else
+      K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
+        adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
   }
   for (int i = 0; i < 4; i++)
     hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
@@ -814,10 +896,11 @@ static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weig
     hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
                        weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j]);
   OFX_HIP(hipGetLastError());
-  float lh[2] = {0.f, 0.f};
-  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(lh), hipMemcpyDeviceToHost, st));
+  float lh[4] = {0.f, 0.f, 0.f, 0.f};   // {loss1, loss2, norm, clip factor}
+  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(float) * (R.norm() ? 4 : 2), hipMemcpyDeviceToHost, st));
   OFX_HIP(hipStreamSynchronize(st));
   if (loss_host) { loss_host[0] = lh[0]; loss_host[1] = lh[1]; }
+  if (R.grad_norm_host) *R.grad_norm_host = lh[2];
   return ofx_policy_weights_updated(h, weights);
 }
 
@@ -826,7 +909,7 @@ static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weig
 static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                         const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
                         const float *t1, const float *t2, float *grad_out, float *loss_host, const float *row_weight,
-                        float *td_out) {
+                        float *td_out, const FitRobust &R) {
   const bool dense = t1 != nullptr;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
@@ -849,6 +932,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
   sz(4 * N * 625); sz(4 * N * 2); sz(4 * N * 100); sz(4 * N * 50); sz(4 * N * 5008); sz(4 * N * 5000);      // gu0 do1 dd1 dd2 df dp3
   sz(4 * (size_t)L.n_floats); sz(4 * 64); sz(4 * 64); sz(4 * 576); sz(4 * (2 * N + 4096)); sz(8 * ofx_fit_part_doubles()); sz(8 * 32);
   sz(4 * ofx_fit_out_floats()); sz(8 * ofx_fit_out_doubles(n)); sz(8 * ofx_fit_point_doubles(n)); sz(4 * N * 128);
+  sz(8 * kNormBlocks);                                                                                     // gradient-norm partials
   for (int k = 0; k < 7; k++) { sz(4 * 32); sz(4 * 16); }   // stat (+ the mean's low parts), act
   if ((rc = keep_workspace(h, &h->fitws, &h->fitws_bytes, need))) return rc;
   Arena A{(char *)h->fitws, 0, need};
@@ -872,6 +956,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
   float *o2 = A.f(N * 160000), *do2 = A.f(N * 160000);
   float *p3 = A.f(N * 5000), *f = A.f(N * 5008), *d1 = A.f(N * 100), *d2 = A.f(N * 50), *o1 = A.f(N * 2), *u0 = A.f(N * 625);
   float *gu0 = A.f(N * 625), *do1 = A.f(N * 2), *dd1 = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008), *dp3 = A.f(N * 5000);
+  double *npart = A.d(kNormBlocks);
   if (A.over) { ofx_set_error("ofx_dqn_fit: internal workspace sized too small"); return OFX_ERR_STATE; }
   int nb = 0;
   // input of trunk layer i: the forward pools the previous layer's z on the fly and KEEPS the pooled activation (a quarter
@@ -914,7 +999,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
     // layer's g from that one pixel (ofx_fit.hip, "the top of head 2 for the textbook targets")
     float *o2p = o2, *d2p = o2 + N;                          // [n] each: the dense planes are not used on this path
     if ((rc = ofx_fit_top_point(st, n, rows, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o1, y_act, y_ptr, ustat[2], o2p, do1, d2p, lpart, gpatch,
-                                pscratch, sums, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1), row_weight, td_out))) return rc;
+                                pscratch, sums, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1), row_weight, td_out, R.huber_delta))) return rc;
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
     OFX_HIP(hipGetLastError());
   } else if (dense) {
@@ -977,20 +1062,21 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
   }
   if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
-  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host);
+  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
 }
 
 // One fit step.  Two forms of the targets: the sparse one of ofx_dqn_fit (one error per head and sample: y_act / y_ptr,
 // inputs = `state`) and the dense one of ofx_dqn_fit_reference (t1 [n][2] / t2 [n][400][400] whole target tensors,
 // inputs = bits_in + the rows' next_state head).
 // row_weight / td_out (sparse form only, either may be null): per-row loss weights and the rows' errors (ofx_dqn_fit_weighted).
+// R (sparse form only): the Huber loss, the gradient-norm clip and the norm's read-back (ofx_dqn_fit_robust); all off by default.
 static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                         const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
                         const float *t1, const float *t2, float *grad_out, float *loss_host,
-                        const float *row_weight = nullptr, float *td_out = nullptr) {
+                        const float *row_weight = nullptr, float *td_out = nullptr, const FitRobust &R = FitRobust()) {
   if (!h->opt_fit_plain)
     return dqn_fit_lean(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, t1, t2, grad_out, loss_host,
-                        row_weight, td_out);
+                        row_weight, td_out, R);
   const bool dense = t1 != nullptr;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
@@ -1010,7 +1096,8 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
   sz(N * 8 * 160000); sz(N * 160000);               // up4, o2
   sz(N * 8 * 160000); sz(N * 8 * 160000);           // two gradient scratch planes of the largest size
   sz(N * 5008); sz(N * 100); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625); sz(N * 160000);
-  sz(L.n_floats); sz(64); sz(2 * N + 4096); need += 65536 + 16 * 64 * 8 + 16 * 64 * 2 * 8 + (size_t)kWSlices * 600 * 8;
+  sz(L.n_floats); sz(64); sz(2 * N + 4096); sz(2 * kNormBlocks);   // (the last: gradient-norm partials, doubles)
+  need += 65536 + 16 * 64 * 8 + 16 * 64 * 2 * 8 + (size_t)kWSlices * 600 * 8;
   if ((rc = keep_workspace(h, &h->fitws, &h->fitws_bytes, need))) return rc;
   void *raw = h->fitws;
   Arena A{(char *)raw, 0, need};
@@ -1078,6 +1165,9 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
       hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, lpart + 2048, loss + 1);
       OFX_HIP(hipGetLastError());
     }
+  } else if (R.huber_delta > 0.f) {
+    K(t_loss_seed_huber, N, n, rows, o1, o2, y_act, y_ptr, do1, do2, lpart, row_weight, td_out, R.huber_delta);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
   } else {
     K(t_loss_seed, N, n, rows, o1, o2, y_act, y_ptr, do1, do2, lpart, row_weight, td_out);
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
@@ -1106,6 +1196,7 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
   }
   // dcur = d u0 [n][625] (pre-mask)
   float *dd1 = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008);
+  double *npart = A.d(kNormBlocks);
   K(t_relu_mask, N * 625, N * 625, u0, dcur);
   K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, dcur, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
   K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, dcur, T(OFX_T_UPDENSE), dd1, 0);
@@ -1145,7 +1236,7 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
   }
   if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
-  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host);
+  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
 }
 
 extern "C" int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
@@ -1171,6 +1262,30 @@ extern "C" int ofx_dqn_fit_weighted(ofx_handle *h, float *weights, float *adam_m
   }
   return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
                       loss_host, row_weight, td_out);
+}
+
+// ofx_dqn_fit_weighted with the error bounded by Huber(huber_delta) and the gradient clipped to a global norm of
+// clip_norm before Adam; 0 switches either off, and with both off and no grad_norm_host this is ofx_dqn_fit_weighted.
+extern "C" int ofx_dqn_fit_robust(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr,
+                                  int32_t n, const ofx_transition *rows, const void *bits_prev, const float *y_act,
+                                  const float *y_ptr, float *grad_out, float *loss_host, const float *row_weight,
+                                  float *td_out, float huber_delta, float clip_norm, float *grad_norm_host) {
+  if (!h || !weights || !adam_m || !adam_v || !rows || !bits_prev || !y_act || !y_ptr || n < 1 || step < 1) {
+    ofx_set_error("ofx_dqn_fit_robust: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  // NaN fails the first comparison, infinity the second
+  if (!(huber_delta >= 0.f && huber_delta <= FLT_MAX) || !(clip_norm >= 0.f && clip_norm <= FLT_MAX)) {
+    ofx_set_error("ofx_dqn_fit_robust: huber_delta and clip_norm must be finite and >= 0 (0 = off), got %g and %g",
+                  (double)huber_delta, (double)clip_norm);
+    return OFX_ERR_INVALID;
+  }
+  FitRobust R;
+  R.huber_delta = huber_delta;
+  R.clip_norm = clip_norm;
+  R.grad_norm_host = grad_norm_host;
+  return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
+                      loss_host, row_weight, td_out, R);
 }
 
 // Trainer.replay's loop body and fit exactly as written (agents/qlearnIA_V2.py:251-285), quirks included:

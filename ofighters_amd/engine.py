@@ -609,6 +609,21 @@ class ArenaBatch:
                                                   grad_buf.ptr if grad_buf else None, loss, row_weight_ptr, td_ptr))
         return float(loss[0]), float(loss[1])
 
+    def dqn_fit_robust(self, weights_buf, adam_m_buf, adam_v_buf, step, lr, n, rows_ptr, bits_prev_ptr, y_act_ptr,
+                       y_ptr_ptr, huber_delta=0.0, clip_norm=0.0, row_weight_ptr=None, td_ptr=None, grad_buf=None):
+        """dqn_fit_weighted under the Huber loss (huber_delta > 0: Keras Huber(delta), half the mse gradient inside the
+        quadratic zone) and / or with the gradient clipped to a global norm of clip_norm before Adam (> 0:
+        torch.nn.utils.clip_grad_norm_); 0 switches either off.  td_ptr receives the raw errors, grad_buf the gradient
+        before scaling.  Returns (loss1, loss2, grad_norm): the Huber losses and the norm before clipping - None with both
+        options off, where the call launches exactly what dqn_fit_weighted does."""
+        loss, norm = (C.c_float * 2)(), C.c_float(0.0)
+        on = bool(huber_delta) or bool(clip_norm)          # (NaN is true: it reaches the entry and is refused there)
+        nat.check(nat.lib().ofx_dqn_fit_robust(self._h, weights_buf.ptr, adam_m_buf.ptr, adam_v_buf.ptr, int(step),
+                                                float(lr), int(n), rows_ptr, bits_prev_ptr, y_act_ptr, y_ptr_ptr,
+                                                grad_buf.ptr if grad_buf else None, loss, row_weight_ptr, td_ptr,
+                                                float(huber_delta), float(clip_norm), C.byref(norm) if on else None))
+        return float(loss[0]), float(loss[1]), (float(norm.value) if on else None)
+
     def dqn_fit_reference(self, weights_buf, adam_m_buf, adam_v_buf, step, lr, n, rows_ptr, bits_prev_ptr, bits_next_ptr,
                           gamma=0.9, grad_buf=None):
         """The fit step with Trainer.replay's quirks as written (qlearnIA_V2.py:251-285: whole-prediction targets,

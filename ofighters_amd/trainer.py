@@ -24,7 +24,16 @@ After every fit step ofx_policy_blend_weights moves it: a hard copy of the onlin
 with ofx_dqn_targets_double (van Hasselt et al. 2016): the online blob selects the next action and pointer, the target
 blob evaluates them (without a target network both are the online blob, which gives the plain targets).  All of it works
 with `prioritized` and `n_step`; the fit's current values and TD errors always come from the online blob, and save()
-stores the online blob only."""
+stores the online blob only.
+
+`huber_delta=d` and `clip_norm=c` (opt-in, not in the reference; each None or a finite value > 0) bound how an error
+becomes a weight update, the fit step going through ofx_dqn_fit_robust on both replay paths.  huber_delta replaces the
+squared error of both heads by Keras's Huber(d) (Mnih et al. 2015's error clip): quadratic up to |e| = d, linear beyond,
+so a row's seed is clamp(e, -d, d) - inside the quadratic zone HALF the mse gradient, as in Keras - while the
+priorities of `prioritized` stay the raw |TD error|.  clip_norm scales the whole gradient by
+min(1, c / (norm + 1e-6)) before Adam (torch.nn.utils.clip_grad_norm_).  With either set, `grad_norms` collects the
+gradient's norm before clipping of every fit step, next to `losses` (which then holds the Huber losses).  Both work with
+`prioritized`, `n_step`, the target network and `double_dqn`, which only change targets and sampling."""
 import numpy as np
 
 from .engine import DeviceBuffer
@@ -34,7 +43,8 @@ from .lib.epsilon import Epsilon_cos
 class DeviceTrainer:
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
-                 per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False):
+                 per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
+                 huber_delta=None, clip_norm=None):
         if prioritized and reference_quirks:
             raise ValueError("DeviceTrainer: prioritized replay needs the textbook fit (reference_quirks=False)")
         if int(n_step) != n_step or n_step < 1:
@@ -51,6 +61,14 @@ class DeviceTrainer:
         if (target_sync or target_tau is not None or double_dqn) and reference_quirks:
             raise ValueError("DeviceTrainer: a target network / Double DQN needs the textbook fit (reference_quirks=False "
                              "computes its own targets)")
+        for name, val in (("huber_delta", huber_delta), ("clip_norm", clip_norm)):
+            if val is None:
+                continue
+            if isinstance(val, bool) or not (0.0 < float(val) < float("inf")):       # NaN fails the comparison
+                raise ValueError("DeviceTrainer: %s must be None or a finite value > 0, got %r" % (name, val))
+            if reference_quirks:
+                raise ValueError("DeviceTrainer: %s needs the textbook fit (reference_quirks=False is the reference's "
+                                 "mse into plain Adam as written)" % name)
         self.batch = batch                                  # the ArenaBatch this trainer plays and learns on
         w = np.ascontiguousarray(weights, np.float32)
         self.n_floats = w.size
@@ -75,9 +93,12 @@ class DeviceTrainer:
         self.prioritized = bool(prioritized)                # PER: priority exponent alpha, IS exponent beta -> 1, eps
         self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = per_alpha, per_beta, per_beta_steps, per_eps
         self.n_step = int(n_step)                           # TD targets bootstrap n_step lock-steps ahead (1: one-step)
+        self.huber_delta = None if huber_delta is None else float(huber_delta)   # Huber(delta) in place of the mse
+        self.clip_norm = None if clip_norm is None else float(clip_norm)         # global gradient-norm clip before Adam
         self.fit_steps = 0
         self.draws = 0
         self.losses = []
+        self.grad_norms = []                                 # with huber_delta / clip_norm: every fit step's pre-clip norm
         self._buf = {}                                       # replay scratch kept between calls (grow-only)
         batch.replay_create(memory_size, frames)
         if self.prioritized:
@@ -159,11 +180,25 @@ class DeviceTrainer:
         y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
         self._targets(n, rows_p, prev_p, next_p, y_act, y_ptr)
         self.fit_steps += 1
-        loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
-                         y_act.ptr, y_ptr.ptr)
+        if self._robust():
+            loss = self._fit_robust(n, rows_p, prev_p, y_act, y_ptr)
+        else:
+            loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
+                             y_act.ptr, y_ptr.ptr)
         self._move_target()
         self.losses.append(loss)
         return loss
+
+    def _robust(self):
+        return self.huber_delta is not None or self.clip_norm is not None
+
+    def _fit_robust(self, n, rows_p, prev_p, y_act, y_ptr, row_w_p=None, td_p=None):
+        """The fit step through ofx_dqn_fit_robust; the pre-clip gradient norm goes to grad_norms."""
+        l1, l2, norm = self.batch.dqn_fit_robust(self.weights, self.adam_m, self.adam_v, self.fit_steps,
+                                                 self.learning_rate, n, rows_p, prev_p, y_act.ptr, y_ptr.ptr,
+                                                 self.huber_delta or 0.0, self.clip_norm or 0.0, row_w_p, td_p)
+        self.grad_norms.append(norm)
+        return l1, l2
 
     def _gather(self, slot, n_s, bs, start, n, rows, bits_prev, bits_next):
         """The window of sampled rows: ofx_replay_gather_valid, or with n_step > 1 the rows' n-step composites and their
@@ -234,8 +269,11 @@ class DeviceTrainer:
         y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
         self._targets(n, rows.ptr, bits_prev.ptr, bits_next.ptr, y_act, y_ptr)
         self.fit_steps += 1
-        loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows.ptr,
-                                  bits_prev.ptr, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
+        if self._robust():
+            loss = self._fit_robust(n, rows.ptr, bits_prev.ptr, y_act, y_ptr, row_w.ptr, td.ptr)
+        else:
+            loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n,
+                                      rows.ptr, bits_prev.ptr, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
         b.replay_update_priorities(slot, n_s, bs, start, n, rows.ptr, td.ptr)
         self._move_target()
         self.losses.append(loss)
