@@ -243,7 +243,8 @@ int ofx_field_desc(ofx_handle *h, int field, ofx_tensor_desc *out);
 int ofx_map_desc(ofx_handle *h, int map_type, int which, ofx_tensor_desc *out);
 
 /* number of lasers dropped because an arena's list was full since the last
- * call (never silent truncation); resets the counter.                        */
+ * call (never silent truncation); resets the counter.  "Since the last call"
+ * is per process: a checkpoint does not carry the counter over.              */
 int ofx_overflow_count(ofx_handle *h, int64_t *count_host);
 
 /* ---- episodic scores (the only cross-GPU quantity) ----------------------
@@ -469,6 +470,69 @@ int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, const int32
                                  int32_t first, int32_t n_rows, const ofx_transition *rows, const float *td);
 /* Masses of one arena, oldest first (the order of ofx_replay_rows_host); mass_host holds `capacity` floats.        */
 int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *mass_host, int32_t *n_host);
+
+/* ---- checkpoint: export / import of the replay memory --------------------
+ * What a training run must carry across processes besides the weights (checkpoints).  A CHUNK is the
+ * whole memory of local arenas [arena0, arena0 + n_arenas): the caller bounds host memory by choosing the chunk.  The
+ * frame ring is packed on the device - its maps are 1-bit discs, nearly every word is zero - and only the packed
+ * result crosses to the host.  A chunk is one self-describing little-endian blob of four sections, back to back:
+ *
+ *  1. Header, 80 bytes:
+ *       offset  0 uint32 magic 0x5258464F (the bytes "OFXR")     offset  4 uint32 format version, 1
+ *       offset  8 int32 width W    12 int32 height H    16 int32 n_ships M    20 int32 capacity C
+ *       offset 24 int32 frames F (the ring's real length, never 0)     28 int32 words = W * H / 32
+ *       offset 32 int32 n_arenas n of the chunk      36 int32 prioritized (0 / 1)
+ *       offset 40 float32 alpha    44 float32 eps    (of ofx_replay_prioritize; 0 without PER)
+ *       offset 48 uint64 raw_bytes    56 uint64 count_bytes    64 uint64 pair_bytes    72 uint64 zero
+ *  2. Raw section (raw_bytes): every per-arena and per-ship array of the memory that is state, in this order, each the
+ *     chunk's slice [n]... of the device array as it lies there, each padded with zero bytes to a multiple of 8:
+ *       frame_tick int32 [n][F]      lock-step held by each ring slot, -1 = empty
+ *       frame_head int32 [n]         next slot to write, in [0, F)
+ *       cur_slot   int32 [n]         slot written by the last capture, -1 = none, in [-1, F)
+ *       rows       ofx_transition [n][C]   the whole ring of rows in ring position order, stale ones included; the
+ *                                    live rows are the `count` positions before `head`: (head - count + i) mod C,
+ *                                    i = 0 (oldest) .. count - 1
+ *       head       int32 [n]         next ring position to write, in [0, C)
+ *       count      int32 [n]         min(appended, C)
+ *       appended   int64 [n]
+ *       has_prev   uint8 [n][M]      the ship has previous_* (QlearnIA.play)
+ *       latched    uint8 [n][M]      the agent's `done` latch
+ *       prev_iaction, prev_px, prev_py, prev_tick, prev_slot   int32 [n][M] each (five arrays, in this order)
+ *       prev_head  float32 [n][M][8]
+ *       mass       float32 [n][C]    only with prioritized = 1: p^alpha in the ring positions of `rows`
+ *       mmax       float32 [n]       only with prioritized = 1
+ *     raw_bytes is the sum of the padded sizes.  The offsets scratch of the gathers is not state and not saved.
+ *  3. Count section (count_bytes = 4 * n * F * 2): uint32 count[n][F][2] - for every (arena, slot, map: 0 ship,
+ *     1 laser) the number of nonzero 32-bit words of that stored map (pixel p -> bit (p & 31) of word p >> 5).  A slot
+ *     with frame_tick == -1 has count 0.
+ *  4. Pair section (pair_bytes = 8 * the sum of the counts): for every map in the same (arena, slot, map) order its
+ *     count pairs (uint32 word index, uint32 word), ascending in word index, all concatenated.
+ * The blob is exactly 80 + raw_bytes + count_bytes + pair_bytes long.  Two exports of the same state are
+ * byte-identical.
+ *
+ * ofx_replay_export_bytes runs the count pass and returns the exact size of the chunk's blob.  ofx_replay_export
+ * counts again and writes the blob to dst_host (*written_host = its size); with `bytes` too small it fails with
+ * OFX_ERR_INVALID and touches nothing.  Both synchronise.
+ * ofx_replay_import replaces the memory of the chunk's arenas by the blob's: the handle must have a replay memory of
+ * the blob's capacity, frames and PER state (alpha and eps bit for bit) on arenas of the blob's M, W, H, and n_arenas
+ * must be the blob's - otherwise OFX_ERR_STATE (no memory) or OFX_ERR_INVALID with a message naming the field.  The
+ * blob goes through ofx_replay_blob_check before anything on the device is written: a refused blob leaves the handle
+ * as it was.  Then the chunk's part of the ring is cleared, the raw arrays are uploaded and the pairs are scattered.
+ * Synchronises.
+ * ofx_replay_blob_check needs no handle and no device.  It is the single place that decides whether a blob may reach
+ * the kernels; `frames` is the ring's real length.  OFX_ERR_INVALID with a message naming the fault for: a wrong magic
+ * or version; any header dimension that differs from the arguments; section sizes that differ from what the dimensions
+ * give, or that do not add up to `bytes`; a count above `words`, a nonzero count in an empty slot, counts that do not sum
+ * to the pair section; a word index >= words, indices that do not ascend strictly within a map, a zero word;
+ * frame_tick < -1, frame_head / cur_slot / head / count outside the ranges above, appended < count; a live row with
+ * frame_prev / frame_next outside [0, F), ship outside [0, M), iaction outside [0, 2), px outside [0, W) or py outside
+ * [0, H); a ship with has_prev whose prev_slot / prev_iaction / prev_px / prev_py are outside those ranges; with PER a
+ * mass or mmax that is not finite and >= 0.                                                                        */
+int ofx_replay_export_bytes(ofx_handle *h, int32_t arena0, int32_t n_arenas, size_t *bytes_host);
+int ofx_replay_export(ofx_handle *h, int32_t arena0, int32_t n_arenas, void *dst_host, size_t bytes, size_t *written_host);
+int ofx_replay_import(ofx_handle *h, int32_t arena0, int32_t n_arenas, const void *src_host, size_t bytes);
+int ofx_replay_blob_check(const void *src_host, size_t bytes, int32_t n_ships, int32_t width, int32_t height,
+                          int32_t capacity, int32_t frames, int32_t prioritized, int32_t n_arenas);
 
 /* ---- n-step returns (opt-in) --------------------------------------------
  * Not in the reference.  Off unless these two calls are used; nothing above changes.

@@ -2,7 +2,8 @@
 // (agents/qlearnIA_V2.py:58), Trainer.remember (:237-238) and the bookkeeping of QlearnIA.play (:370-403) /
 // QlearnIA.reset (:360-368).  Every arena owns one memory (the reference has one arena and one shared TRAINER).
 //
-// Layout in HBM (288 GB per GPU: the whole memory stays resident, nothing goes to the host):
+// Layout in HBM (288 GB per GPU: the whole memory stays resident; only a checkpoint takes it to the host, the frame ring
+// packed to its nonzero words - ofx_replay_export at the end of this file):
 //   frames  [N][F][2][W*H/32] u32   1-bit observation maps (20 KB per map): a ring of F frames per arena.  An arena
 //                                    stores a frame only on lock-steps where one of its agents plays; the maps are
 //                                    shared by every ship of the arena and by the two transitions that touch them
@@ -420,21 +421,23 @@ extern "C" int ofx_replay_gather(ofx_handle *h, const int32_t *slot, int32_t bat
 
 // ---- the same minibatch without padding: only the rows that exist, packed (Trainer.replay never pads: its batch is
 // min(batch_size, len(memory)) real transitions, qlearnIA_V2.py:241-243) ------------------------------------------------
-// exclusive scan of n_sampled[N] by one workgroup -> off[N], total in off[N]
-__global__ __launch_bounds__(1024) void k_replay_scan(int N, const int32_t *n_sampled, int32_t *off) {
-  __shared__ int part[1024];
+// exclusive scan of n_sampled[N] by one workgroup -> off[N], total in off[N] (int32 for the gathers' windows, 64-bit
+// sums for the checkpoint's pair offsets)
+template <typename In, typename Out>
+__global__ __launch_bounds__(1024) void k_replay_scan(int N, const In *n_sampled, Out *off) {
+  __shared__ Out part[1024];
   const int tid = threadIdx.x, per = (N + 1023) / 1024, lo = min(tid * per, N), hi = min(lo + per, N);
-  int sum = 0;
+  Out sum = 0;
   for (int i = lo; i < hi; i++) sum += n_sampled[i];
   part[tid] = sum;
   __syncthreads();
   for (int d = 1; d < 1024; d <<= 1) {  // Hillis-Steele inclusive scan of the partial sums
-    const int v = tid >= d ? part[tid - d] : 0;
+    const Out v = tid >= d ? part[tid - d] : 0;
     __syncthreads();
     part[tid] += v;
     __syncthreads();
   }
-  int run = tid ? part[tid - 1] : 0;
+  Out run = tid ? part[tid - 1] : 0;
   for (int i = lo; i < hi; i++) { off[i] = run; run += n_sampled[i]; }
   if (tid == 1023) off[N] = part[1023];
 }
@@ -539,7 +542,7 @@ static int gather_window(ofx_handle *h, const char *who, const int32_t *slot, co
   OFX_HIP(hipSetDevice(h->cfg.device));
   const int N = h->cfg.n_arenas;
   int32_t *off = r->scan_off;
-  hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
+  hipLaunchKernelGGL((k_replay_scan<int32_t, int32_t>), dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
   GatherParams p;
   p.N = N; p.C = r->capacity; p.F = r->frames; p.batch = batch; p.words = r->words;
   p.r = *r; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
@@ -756,7 +759,7 @@ extern "C" int ofx_replay_window_weights(ofx_handle *h, const float *is_weight, 
   OFX_HIP(hipSetDevice(h->cfg.device));
   const int N = h->cfg.n_arenas;
   int32_t *off = h->replay->scan_off;
-  hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
+  hipLaunchKernelGGL((k_replay_scan<int32_t, int32_t>), dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
   hipLaunchKernelGGL(k_replay_window_pack, dim3((unsigned)((N * batch + 255) / 256)), dim3(256), 0, h->stream, N, batch,
                      is_weight, n_sampled, (const int32_t *)off, first, max_rows, out);
   hipLaunchKernelGGL(k_replay_window_norm, dim3(1), dim3(1024), 0, h->stream, N, (const int32_t *)off, first, max_rows, out);
@@ -801,7 +804,7 @@ extern "C" int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, 
   OFX_HIP(hipSetDevice(h->cfg.device));
   const int N = h->cfg.n_arenas;
   int32_t *off = h->replay->scan_off;  // recomputed here: never the offsets an earlier call left behind
-  hipLaunchKernelGGL(k_replay_scan, dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
+  hipLaunchKernelGGL((k_replay_scan<int32_t, int32_t>), dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
   hipLaunchKernelGGL(k_replay_update_per, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, h->replay->capacity, batch, slot,
                      n_sampled, (const int32_t *)off, first, n_rows, rows, td, *h->replay);
   OFX_HIP(hipGetLastError());
@@ -827,5 +830,450 @@ extern "C" int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *m
   if (n1 > 0) OFX_HIP(hipMemcpy(mass_host, base + first, sizeof(float) * n1, hipMemcpyDeviceToHost));
   if (count > n1) OFX_HIP(hipMemcpy(mass_host + n1, base, sizeof(float) * (count - n1), hipMemcpyDeviceToHost));
   *n_host = count;
+  return OFX_OK;
+}
+
+// ---- checkpoint: export / import of the memory of a chunk of arenas (include/ofx.h states the blob's layout) --------
+// The frame ring is 1-bit discs of a few ships and lasers: nearly every word is zero.  It crosses to the host as
+// (word index, word) pairs of its nonzero words, packed on the device: a count pass (one wave per (arena, slot, map),
+// 16-byte loads, a ballot of the nonzero words per component), an exclusive scan of the counts, and a write pass that
+// repeats the traversal - a lane's position is the map's base + the popcount of the ballots below it, so the pairs land
+// in ascending word order without atomics and two exports of one state give the same bytes.
+#define OFX_BLOB_MAGIC 0x5258464Fu /* "OFXR" */
+#define OFX_BLOB_VERSION 1u
+#define OFX_BLOB_HEADER 80
+
+struct BlobDims {
+  int32_t W, H, M, C, F, words, n, per;
+};
+// the raw arrays in struct order: bytes per arena, and where each array starts inside the raw section
+enum { RAW_FRAME_TICK, RAW_FRAME_HEAD, RAW_CUR_SLOT, RAW_ROWS, RAW_HEAD, RAW_COUNT, RAW_APPENDED, RAW_HAS_PREV,
+       RAW_LATCHED, RAW_PREV_IACTION, RAW_PREV_PX, RAW_PREV_PY, RAW_PREV_TICK, RAW_PREV_SLOT, RAW_PREV_HEAD, RAW_MASS,
+       RAW_MMAX, RAW_N };
+static size_t pad8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+static void raw_layout(const BlobDims &d, size_t per_arena[RAW_N], size_t off[RAW_N + 1]) {
+  const size_t M = d.M, C = d.C, F = d.F;
+  const size_t sz[RAW_N] = {4 * F, 4, 4, sizeof(ofx_transition) * C, 4, 4, 8, M, M, 4 * M, 4 * M, 4 * M, 4 * M, 4 * M,
+                            32 * M, d.per ? 4 * C : 0, d.per ? (size_t)4 : 0};
+  off[0] = 0;
+  for (int i = 0; i < RAW_N; i++) {
+    per_arena[i] = sz[i];
+    off[i + 1] = off[i] + pad8(sz[i] * (size_t)d.n);
+  }
+}
+
+static void raw_device(const ofx_replay *r, void *ptrs[RAW_N]) {
+  void *p[RAW_N] = {r->frame_tick, r->frame_head, r->cur_slot, r->rows, r->head, r->count, r->appended, r->has_prev,
+                    r->latched, r->prev_iaction, r->prev_px, r->prev_py, r->prev_tick, r->prev_slot, r->prev_head,
+                    r->mass, r->mmax};
+  memcpy(ptrs, p, sizeof(p));
+}
+
+template <typename T>
+static T rd(const uint8_t *p) {  // a blob read from a file sits at any alignment
+  T v;
+  memcpy(&v, p, sizeof(T));
+  return v;
+}
+template <typename T>
+static void wr(uint8_t *p, T v) { memcpy(p, &v, sizeof(T)); }
+
+// One wave per map m = (arena * F + slot) * 2 + which of the chunk.  WRITE = false: counts[m] = nonzero words;
+// WRITE = true: the map's pairs at pairs[off[m] ...] in ascending word index.  Lane l of iteration k0 holds words
+// 4 (k0 + l) .. + 3, so ascending order is lane-major, then component: position = the nonzero words of all four
+// components in the lanes below + the lane's own lower components.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_replay_pack(int n_maps, int words, const uint32_t *bits, const int32_t *frame_tick,
+                                                     uint32_t *counts, const unsigned long long *off, uint2 *pairs) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= n_maps) return;  // wave-uniform
+  if (frame_tick[m >> 1] < 0) {  // an empty slot (its words are zero since ofx_replay_create / the import's clear)
+    if (!WRITE && lane == 0) counts[m] = 0u;
+    return;
+  }
+  const uint4 *src = reinterpret_cast<const uint4 *>(bits + (size_t)m * words);
+  const int q = words >> 2;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  unsigned long long run = 0ull;
+  if constexpr (WRITE) run = off[m];
+  for (int k0 = 0; k0 < q; k0 += 64) {  // wave-uniform trip count: the ballots see every lane
+    const int k = k0 + lane;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (k < q) v = src[k];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    unsigned long long pos = run;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const unsigned long long bal = __ballot(w[c] != 0u);
+      pos += (unsigned long long)__popcll(bal & below);
+      run += (unsigned long long)__popcll(bal);
+    }
+    if constexpr (WRITE) {
+#pragma unroll
+      for (int c = 0; c < 4; c++)
+        if (w[c] != 0u) pairs[pos++] = make_uint2((uint32_t)(4 * k + c), w[c]);
+    }
+  }
+  if (!WRITE && lane == 0) counts[m] = (uint32_t)run;
+}
+
+// Exclusive scan of counts[n] in 64 bits -> off[n], total in off[n], in three launches: a chunk of 4096 arenas has 4 M
+// maps, which one workgroup takes longer to walk than the count pass takes to produce (profiles/r08_checkpoint_4096.txt).
+// The sums of segments of PACK_SEG counts, their scan by one workgroup (k_replay_scan), then every segment's own scan on
+// top of its offset.  Every sum is an integer: any order gives the same bytes.
+#define PACK_SEG 2048
+__device__ inline unsigned long long wave_incl_scan(unsigned long long v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long u = __shfl_up(v, d);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_replay_pack_segsum(int n, const uint32_t *counts, unsigned long long *seg) {
+  __shared__ unsigned long long part[4];
+  const int lo = blockIdx.x * PACK_SEG, hi = min(lo + PACK_SEG, n), lane = threadIdx.x & 63;
+  unsigned long long sum = 0ull;
+  for (int i = lo + threadIdx.x; i < hi; i += 256) sum += counts[i];
+  sum = wave_incl_scan(sum, lane);
+  if (lane == 63) part[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) seg[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+__global__ __launch_bounds__(256) void k_replay_pack_offsets(int n, int n_seg, const uint32_t *counts,
+                                                             const unsigned long long *seg_off, unsigned long long *off) {
+  __shared__ unsigned long long part[4];
+  const int lo = blockIdx.x * PACK_SEG, hi = min(lo + PACK_SEG, n), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long carry = seg_off[blockIdx.x];
+  for (int base = lo; base < hi; base += 256) {  // block-uniform trip count
+    const int i = base + threadIdx.x;
+    const unsigned long long c = i < hi ? counts[i] : 0u;
+    const unsigned long long incl = wave_incl_scan(c, lane);
+    if (lane == 63) part[wave] = incl;
+    __syncthreads();
+    unsigned long long before = carry;
+    for (int w = 0; w < wave; w++) before += part[w];
+    if (i < hi) off[i] = before + incl - c;
+    carry += part[0] + part[1] + part[2] + part[3];
+    __syncthreads();
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) off[n] = seg_off[n_seg];
+}
+
+// off[n + 1] <- the scan of counts[n]; off has room for pack_scan_words(n) entries (the segment arrays follow off[n])
+static size_t pack_scan_words(int n) { return (size_t)n + 1 + 2 * (size_t)((n + PACK_SEG - 1) / PACK_SEG) + 1; }
+static void launch_pack_scan(ofx_handle *h, int n, const uint32_t *counts, unsigned long long *off) {
+  const int n_seg = (n + PACK_SEG - 1) / PACK_SEG;
+  unsigned long long *seg = off + n + 1, *seg_off = seg + n_seg;
+  hipLaunchKernelGGL(k_replay_pack_segsum, dim3((unsigned)n_seg), dim3(256), 0, h->stream, n, counts, seg);
+  hipLaunchKernelGGL((k_replay_scan<unsigned long long, unsigned long long>), dim3(1), dim3(1024), 0, h->stream, n_seg,
+                     (const unsigned long long *)seg, seg_off);
+  hipLaunchKernelGGL(k_replay_pack_offsets, dim3((unsigned)n_seg), dim3(256), 0, h->stream, n, n_seg, counts,
+                     (const unsigned long long *)seg_off, off);
+}
+
+// the import's scatter: one wave per map walks its pair range (indices checked on the host by ofx_replay_blob_check)
+__global__ __launch_bounds__(256) void k_replay_unpack(int n_maps, int words, const unsigned long long *off, const uint2 *pairs,
+                                                       uint32_t *bits) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= n_maps) return;
+  uint32_t *dst = bits + (size_t)m * words;
+  const unsigned long long lo = off[m], hi = off[m + 1];
+  for (unsigned long long i = lo + lane; i < hi; i += 64) {
+    const uint2 p = pairs[i];
+    if (p.x < (uint32_t)words) dst[p.x] = p.y;
+  }
+}
+
+// handle, memory and chunk of an export / import call
+static int chunk_ready(ofx_handle *h, const char *who, int32_t arena0, int32_t n_arenas, BlobDims *d) {
+  if (!h) { ofx_set_error("%s: null handle", who); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  if (!r) { ofx_set_error("%s before ofx_replay_create", who); return OFX_ERR_STATE; }
+  if (arena0 < 0 || n_arenas <= 0 || (long long)arena0 + n_arenas > h->cfg.n_arenas) {
+    ofx_set_error("%s: arenas [%d, %d + %d) outside the handle's %d", who, arena0, arena0, n_arenas, h->cfg.n_arenas);
+    return OFX_ERR_INVALID;
+  }
+  if ((long long)n_arenas * r->frames * 2 > 0x7FFFFFFFll) {
+    ofx_set_error("%s: %d arenas x %d frames is more than one chunk can hold: split the chunk", who, n_arenas, r->frames);
+    return OFX_ERR_INVALID;
+  }
+  d->W = h->cfg.width; d->H = h->cfg.height; d->M = h->cfg.n_ships; d->C = r->capacity; d->F = r->frames;
+  d->words = r->words; d->n = n_arenas; d->per = r->mass ? 1 : 0;
+  return OFX_OK;
+}
+
+// counts and offsets of the chunk's maps in two fresh device arrays (the caller frees them); synchronises
+static int pack_count(ofx_handle *h, const BlobDims &d, int32_t arena0, uint32_t **counts, unsigned long long **off,
+                      unsigned long long *total) {
+  ofx_replay *r = h->replay;
+  const int n_maps = d.n * d.F * 2;
+  *counts = nullptr;
+  *off = nullptr;
+  OFX_HIP(hipMalloc((void **)counts, sizeof(uint32_t) * (size_t)n_maps));
+  hipError_t e = hipMalloc((void **)off, sizeof(unsigned long long) * pack_scan_words(n_maps));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_replay_pack<false>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
+                       r->frame_bits + (size_t)arena0 * d.F * 2 * d.words, r->frame_tick + (size_t)arena0 * d.F, *counts,
+                       (const unsigned long long *)nullptr, (uint2 *)nullptr);
+    launch_pack_scan(h, n_maps, *counts, *off);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(total, *off + n_maps, sizeof(*total), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(*counts);
+    if (*off) (void)hipFree(*off);
+    *counts = nullptr;
+    *off = nullptr;
+    ofx_set_error("ofx_replay_export: %s", hipGetErrorString(e));
+    return OFX_ERR_HIP;
+  }
+  return OFX_OK;
+}
+
+static size_t blob_bytes(const BlobDims &d, unsigned long long total_pairs) {
+  size_t per_arena[RAW_N], off[RAW_N + 1];
+  raw_layout(d, per_arena, off);
+  return OFX_BLOB_HEADER + off[RAW_N] + sizeof(uint32_t) * (size_t)d.n * d.F * 2 + 8 * (size_t)total_pairs;
+}
+
+extern "C" int ofx_replay_export_bytes(ofx_handle *h, int32_t arena0, int32_t n_arenas, size_t *bytes_host) {
+  BlobDims d;
+  int rc;
+  if ((rc = chunk_ready(h, "ofx_replay_export_bytes", arena0, n_arenas, &d))) return rc;
+  if (!bytes_host) { ofx_set_error("ofx_replay_export_bytes: null bytes_host"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  uint32_t *counts;
+  unsigned long long *off, total = 0;
+  if ((rc = pack_count(h, d, arena0, &counts, &off, &total))) return rc;
+  (void)hipFree(counts);
+  (void)hipFree(off);
+  *bytes_host = blob_bytes(d, total);
+  return OFX_OK;
+}
+
+extern "C" int ofx_replay_export(ofx_handle *h, int32_t arena0, int32_t n_arenas, void *dst_host, size_t bytes,
+                                 size_t *written_host) {
+  BlobDims d;
+  int rc;
+  if ((rc = chunk_ready(h, "ofx_replay_export", arena0, n_arenas, &d))) return rc;
+  if (!dst_host || !written_host) { ofx_set_error("ofx_replay_export: null argument"); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  uint32_t *counts;
+  unsigned long long *off, total = 0;
+  if ((rc = pack_count(h, d, arena0, &counts, &off, &total))) return rc;
+  const size_t need = blob_bytes(d, total);
+  uint2 *pairs = nullptr;
+  hipError_t e = hipSuccess;
+  rc = OFX_OK;
+  if (bytes < need) {
+    ofx_set_error("ofx_replay_export: the chunk needs %zu bytes, the destination has %zu", need, bytes);
+    rc = OFX_ERR_INVALID;
+  }
+  const int n_maps = d.n * d.F * 2;
+  if (rc == OFX_OK && total) {
+    e = hipMalloc((void **)&pairs, 8 * (size_t)total);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_replay_pack<true>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
+                         r->frame_bits + (size_t)arena0 * d.F * 2 * d.words, r->frame_tick + (size_t)arena0 * d.F,
+                         (uint32_t *)nullptr, (const unsigned long long *)off, pairs);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  }
+  if (rc == OFX_OK && e == hipSuccess) {
+    uint8_t *dst = (uint8_t *)dst_host;
+    size_t per_arena[RAW_N], roff[RAW_N + 1];
+    raw_layout(d, per_arena, roff);
+    memset(dst, 0, OFX_BLOB_HEADER);
+    wr<uint32_t>(dst + 0, OFX_BLOB_MAGIC); wr<uint32_t>(dst + 4, OFX_BLOB_VERSION);
+    wr<int32_t>(dst + 8, d.W); wr<int32_t>(dst + 12, d.H); wr<int32_t>(dst + 16, d.M); wr<int32_t>(dst + 20, d.C);
+    wr<int32_t>(dst + 24, d.F); wr<int32_t>(dst + 28, d.words); wr<int32_t>(dst + 32, d.n); wr<int32_t>(dst + 36, d.per);
+    wr<float>(dst + 40, d.per ? r->alpha : 0.f); wr<float>(dst + 44, d.per ? r->eps : 0.f);
+    wr<uint64_t>(dst + 48, (uint64_t)roff[RAW_N]); wr<uint64_t>(dst + 56, (uint64_t)4 * n_maps);
+    wr<uint64_t>(dst + 64, (uint64_t)8 * total);
+    void *dev[RAW_N];
+    raw_device(r, dev);
+    uint8_t *raw = dst + OFX_BLOB_HEADER;
+    for (int i = 0; i < RAW_N && e == hipSuccess; i++) {
+      const size_t nb = per_arena[i] * (size_t)d.n;
+      if (!nb) continue;
+      e = hipMemcpy(raw + roff[i], (const uint8_t *)dev[i] + per_arena[i] * (size_t)arena0, nb, hipMemcpyDeviceToHost);
+      memset(raw + roff[i] + nb, 0, roff[i + 1] - roff[i] - nb);  // padding is zero: equal states give equal bytes
+    }
+    uint8_t *cnt = raw + roff[RAW_N];
+    if (e == hipSuccess) e = hipMemcpy(cnt, counts, (size_t)4 * n_maps, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && total) e = hipMemcpy(cnt + (size_t)4 * n_maps, pairs, 8 * (size_t)total, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) *written_host = need;
+  }
+  (void)hipFree(counts);
+  (void)hipFree(off);
+  if (pairs) (void)hipFree(pairs);
+  if (e != hipSuccess) { ofx_set_error("ofx_replay_export: %s", hipGetErrorString(e)); return OFX_ERR_HIP; }
+  return rc;
+}
+
+#define BLOB_FAIL(...) do { ofx_set_error("ofx_replay_blob_check: " __VA_ARGS__); return OFX_ERR_INVALID; } while (0)
+
+// Host only: the one place that decides whether a blob may reach the kernels (no handle, no device).
+extern "C" int ofx_replay_blob_check(const void *src_host, size_t bytes, int32_t n_ships, int32_t width, int32_t height,
+                                     int32_t capacity, int32_t frames, int32_t prioritized, int32_t n_arenas) {
+  if (!src_host) BLOB_FAIL("null blob");
+  if (n_ships <= 0 || width <= 0 || height <= 0 || capacity <= 0 || frames < 2 || n_arenas <= 0 ||
+      ((size_t)width * height) % 128 || (long long)n_arenas * frames * 2 > 0x7FFFFFFFll)
+    BLOB_FAIL("bad dimensions to check against (n_ships %d, %d x %d, capacity %d, frames %d, n_arenas %d)", n_ships, width,
+              height, capacity, frames, n_arenas);
+  const uint8_t *p = (const uint8_t *)src_host;
+  if (bytes < OFX_BLOB_HEADER) BLOB_FAIL("truncated: %zu bytes do not hold the %d-byte header", bytes, OFX_BLOB_HEADER);
+  if (rd<uint32_t>(p) != OFX_BLOB_MAGIC) BLOB_FAIL("wrong magic 0x%08x", rd<uint32_t>(p));
+  if (rd<uint32_t>(p + 4) != OFX_BLOB_VERSION) BLOB_FAIL("unknown format version %u", rd<uint32_t>(p + 4));
+  BlobDims d;
+  d.W = width; d.H = height; d.M = n_ships; d.C = capacity; d.F = frames;
+  d.words = (int32_t)(((size_t)width * height) >> 5); d.n = n_arenas; d.per = prioritized ? 1 : 0;
+  const struct { const char *name; int off; int32_t want; } dims[] = {
+      {"width", 8, d.W}, {"height", 12, d.H}, {"n_ships", 16, d.M}, {"capacity", 20, d.C}, {"frames", 24, d.F},
+      {"words", 28, d.words}, {"n_arenas", 32, d.n}, {"prioritized", 36, d.per}};
+  for (const auto &q : dims)
+    if (rd<int32_t>(p + q.off) != q.want) BLOB_FAIL("%s is %d in the blob, expected %d", q.name, rd<int32_t>(p + q.off), q.want);
+  size_t per_arena[RAW_N], roff[RAW_N + 1];
+  raw_layout(d, per_arena, roff);
+  const size_t n_maps = (size_t)d.n * d.F * 2;
+  const uint64_t raw_bytes = rd<uint64_t>(p + 48), count_bytes = rd<uint64_t>(p + 56), pair_bytes = rd<uint64_t>(p + 64);
+  if (raw_bytes != roff[RAW_N]) BLOB_FAIL("raw section size is %llu, expected %zu", (unsigned long long)raw_bytes, roff[RAW_N]);
+  if (count_bytes != 4 * n_maps) BLOB_FAIL("count section size is %llu, expected %zu", (unsigned long long)count_bytes, 4 * n_maps);
+  if (pair_bytes % 8 || pair_bytes > 8 * n_maps * (uint64_t)d.words)
+    BLOB_FAIL("pair section size %llu is impossible", (unsigned long long)pair_bytes);
+  const size_t raw_at = OFX_BLOB_HEADER, cnt_at = raw_at + roff[RAW_N], pair_at = cnt_at + 4 * n_maps;
+  const size_t end = pair_at + (size_t)pair_bytes;
+  if (bytes < cnt_at) BLOB_FAIL("truncated inside the raw section (%zu bytes, the section ends at %zu)", bytes, cnt_at);
+  if (bytes < pair_at) BLOB_FAIL("truncated inside the count section (%zu bytes, the section ends at %zu)", bytes, pair_at);
+  if (bytes < end) BLOB_FAIL("truncated inside the pair section (%zu bytes, the section ends at %zu)", bytes, end);
+  if (bytes > end) BLOB_FAIL("%zu bytes, the sections end at %zu", bytes, end);
+  const uint8_t *raw = p + raw_at, *cnt = p + cnt_at, *pr = p + pair_at;
+  // the raw arrays
+  const uint8_t *ft = raw + roff[RAW_FRAME_TICK];
+  for (size_t i = 0; i < (size_t)d.n * d.F; i++)
+    if (rd<int32_t>(ft + 4 * i) < -1) BLOB_FAIL("frame_tick %d of arena %zu slot %zu is below -1", rd<int32_t>(ft + 4 * i), i / d.F, i % d.F);
+  for (int a = 0; a < d.n; a++) {
+    const int32_t fh = rd<int32_t>(raw + roff[RAW_FRAME_HEAD] + 4 * (size_t)a), cs = rd<int32_t>(raw + roff[RAW_CUR_SLOT] + 4 * (size_t)a);
+    const int32_t head = rd<int32_t>(raw + roff[RAW_HEAD] + 4 * (size_t)a), count = rd<int32_t>(raw + roff[RAW_COUNT] + 4 * (size_t)a);
+    const int64_t app = rd<int64_t>(raw + roff[RAW_APPENDED] + 8 * (size_t)a);
+    if (fh < 0 || fh >= d.F) BLOB_FAIL("frame_head %d of arena %d outside [0, %d)", fh, a, d.F);
+    if (cs < -1 || cs >= d.F) BLOB_FAIL("cur_slot %d of arena %d outside [-1, %d)", cs, a, d.F);
+    if (head < 0 || head >= d.C) BLOB_FAIL("head %d of arena %d outside [0, %d)", head, a, d.C);
+    if (count < 0 || count > d.C) BLOB_FAIL("count %d of arena %d outside [0, %d]", count, a, d.C);
+    if (app < count) BLOB_FAIL("appended %lld of arena %d below its count %d", (long long)app, a, count);
+    const uint8_t *rows = raw + roff[RAW_ROWS] + sizeof(ofx_transition) * (size_t)a * d.C;
+    const int first = ((head - count) % d.C + d.C) % d.C;
+    for (int i = 0; i < count; i++) {  // the live rows: the sampler and the fit index with these
+      const ofx_transition t = rd<ofx_transition>(rows + sizeof(ofx_transition) * (size_t)((first + i) % d.C));
+      if (t.frame_prev < 0 || t.frame_prev >= d.F) BLOB_FAIL("row %d of arena %d: frame_prev %d outside [0, %d)", i, a, t.frame_prev, d.F);
+      if (t.frame_next < 0 || t.frame_next >= d.F) BLOB_FAIL("row %d of arena %d: frame_next %d outside [0, %d)", i, a, t.frame_next, d.F);
+      if (t.ship < 0 || t.ship >= d.M) BLOB_FAIL("row %d of arena %d: ship %d outside [0, %d)", i, a, t.ship, d.M);
+      if (t.iaction < 0 || t.iaction > 1) BLOB_FAIL("row %d of arena %d: iaction %d outside [0, 2)", i, a, t.iaction);
+      if (t.px < 0 || t.px >= d.W) BLOB_FAIL("row %d of arena %d: px %d outside [0, %d)", i, a, t.px, d.W);
+      if (t.py < 0 || t.py >= d.H) BLOB_FAIL("row %d of arena %d: py %d outside [0, %d)", i, a, t.py, d.H);
+    }
+    for (int s = 0; s < d.M; s++) {  // previous_* of a ship become the indices of its next row
+      const size_t t = (size_t)a * d.M + s;
+      if (!raw[roff[RAW_HAS_PREV] + t]) continue;
+      const int32_t ps = rd<int32_t>(raw + roff[RAW_PREV_SLOT] + 4 * t), ia = rd<int32_t>(raw + roff[RAW_PREV_IACTION] + 4 * t);
+      const int32_t px = rd<int32_t>(raw + roff[RAW_PREV_PX] + 4 * t), py = rd<int32_t>(raw + roff[RAW_PREV_PY] + 4 * t);
+      if (ps < 0 || ps >= d.F) BLOB_FAIL("prev_slot %d of arena %d ship %d outside [0, %d)", ps, a, s, d.F);
+      if (ia < 0 || ia > 1) BLOB_FAIL("prev_iaction %d of arena %d ship %d outside [0, 2)", ia, a, s);
+      if (px < 0 || px >= d.W || py < 0 || py >= d.H) BLOB_FAIL("prev_px / prev_py (%d, %d) of arena %d ship %d outside the map", px, py, a, s);
+    }
+    if (d.per) {
+      const uint8_t *mass = raw + roff[RAW_MASS] + 4 * (size_t)a * d.C;
+      for (int i = 0; i < d.C; i++) {
+        const float m = rd<float>(mass + 4 * (size_t)i);
+        if (!(m >= 0.f && m <= FLT_MAX)) BLOB_FAIL("mass %g at ring position %d of arena %d is not finite and >= 0", (double)m, i, a);
+      }
+      const float mm = rd<float>(raw + roff[RAW_MMAX] + 4 * (size_t)a);
+      if (!(mm >= 0.f && mm <= FLT_MAX)) BLOB_FAIL("mmax %g of arena %d is not finite and >= 0", (double)mm, a);
+    }
+  }
+  // the packed frames
+  uint64_t total = 0;
+  for (size_t m = 0; m < n_maps; m++) {
+    const uint32_t c = rd<uint32_t>(cnt + 4 * m);
+    if (c > (uint32_t)d.words) BLOB_FAIL("count %u of map %zu exceeds the %d words of a map", c, m, d.words);
+    if (c && rd<int32_t>(ft + 4 * (m >> 1)) < 0) BLOB_FAIL("map %zu of an empty slot has count %u", m, c);
+    total += c;
+  }
+  if (total * 8 != pair_bytes) BLOB_FAIL("the counts sum to %llu pairs, the pair section holds %llu", (unsigned long long)total, (unsigned long long)(pair_bytes / 8));
+  const uint8_t *q = pr;
+  for (size_t m = 0; m < n_maps; m++) {
+    const uint32_t c = rd<uint32_t>(cnt + 4 * m);
+    int64_t last = -1;
+    for (uint32_t i = 0; i < c; i++, q += 8) {
+      const uint32_t idx = rd<uint32_t>(q), word = rd<uint32_t>(q + 4);
+      if (idx >= (uint32_t)d.words) BLOB_FAIL("word index %u of map %zu is outside the %d words of a map", idx, m, d.words);
+      if ((int64_t)idx <= last) BLOB_FAIL("word indices of map %zu do not ascend strictly (%u after %lld)", m, idx, (long long)last);
+      if (!word) BLOB_FAIL("zero word at index %u of map %zu", idx, m);
+      last = idx;
+    }
+  }
+  return OFX_OK;
+}
+#undef BLOB_FAIL
+
+extern "C" int ofx_replay_import(ofx_handle *h, int32_t arena0, int32_t n_arenas, const void *src_host, size_t bytes) {
+  BlobDims d;
+  int rc;
+  if ((rc = chunk_ready(h, "ofx_replay_import", arena0, n_arenas, &d))) return rc;
+  if (!src_host) { ofx_set_error("ofx_replay_import: null blob"); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  if ((rc = ofx_replay_blob_check(src_host, bytes, d.M, d.W, d.H, d.C, d.F, d.per, d.n))) return rc;
+  const uint8_t *p = (const uint8_t *)src_host;
+  if (d.per && (memcmp(p + 40, &r->alpha, 4) || memcmp(p + 44, &r->eps, 4))) {
+    ofx_set_error("ofx_replay_import: alpha / eps are %g / %g in the blob, %g / %g in the handle (ofx_replay_prioritize)",
+                  (double)rd<float>(p + 40), (double)rd<float>(p + 44), (double)r->alpha, (double)r->eps);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  size_t per_arena[RAW_N], roff[RAW_N + 1];
+  raw_layout(d, per_arena, roff);
+  const int n_maps = d.n * d.F * 2;
+  const uint8_t *raw = p + OFX_BLOB_HEADER, *cnt = raw + roff[RAW_N], *pr = cnt + (size_t)4 * n_maps;
+  const size_t pair_bytes = (size_t)rd<uint64_t>(p + 64);
+  // staging first: a failed allocation leaves the memory as it was
+  uint32_t *counts = nullptr;
+  unsigned long long *off = nullptr;
+  uint2 *pairs = nullptr;
+  hipError_t e = hipMalloc((void **)&counts, (size_t)4 * n_maps);
+  if (e == hipSuccess) e = hipMalloc((void **)&off, sizeof(unsigned long long) * pack_scan_words(n_maps));
+  if (e == hipSuccess && pair_bytes) e = hipMalloc((void **)&pairs, pair_bytes);
+  if (e == hipSuccess) e = hipMemcpy(counts, cnt, (size_t)4 * n_maps, hipMemcpyHostToDevice);
+  if (e == hipSuccess && pair_bytes) e = hipMemcpy(pairs, pr, pair_bytes, hipMemcpyHostToDevice);
+  void *dev[RAW_N];
+  raw_device(r, dev);
+  for (int i = 0; i < RAW_N && e == hipSuccess; i++) {
+    const size_t nb = per_arena[i] * (size_t)d.n;
+    if (nb) e = hipMemcpy((uint8_t *)dev[i] + per_arena[i] * (size_t)arena0, raw + roff[i], nb, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {
+    uint32_t *bits = r->frame_bits + (size_t)arena0 * d.F * 2 * d.words;
+    e = hipMemsetAsync(bits, 0, sizeof(uint32_t) * (size_t)n_maps * d.words, h->stream);
+    if (e == hipSuccess) {
+      launch_pack_scan(h, n_maps, counts, off);
+      if (pair_bytes)
+        hipLaunchKernelGGL(k_replay_unpack, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
+                           (const unsigned long long *)off, (const uint2 *)pairs, bits);
+      e = hipGetLastError();
+    }
+  }
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = es;
+  if (counts) (void)hipFree(counts);
+  if (off) (void)hipFree(off);
+  if (pairs) (void)hipFree(pairs);
+  if (e != hipSuccess) { ofx_set_error("ofx_replay_import: %s", hipGetErrorString(e)); return OFX_ERR_HIP; }
   return OFX_OK;
 }

@@ -94,6 +94,7 @@ class ArenaBatch:
         self._h = h.value
         self.N, self.M, self.L = self.cfg.n_arenas, self.cfg.n_ships, self.cfg.laser_cap
         self.W, self.H = self.cfg.width, self.cfg.height
+        self.arena_base = self.cfg.arena_base
         self._actions = DeviceBuffer(self.N * self.M * ACTION_DTYPE.itemsize)
         self._draws = None
         self._head = None
@@ -409,6 +410,8 @@ class ArenaBatch:
         """Trainer.memory = deque(maxlen=memory_size) per arena (qlearnIA_V2.py:58)."""
         nat.check(nat.lib().ofx_replay_create(self._h, int(capacity), int(frames)))
         self.replay_capacity = int(capacity)
+        self.replay_frames = int(frames) if frames else int(capacity) + int(capacity) // 4 + 2   # include/ofx.h
+        self.replay_prioritized = False
 
     def replay_capture(self, tick, ship_mask_ptr=None, iaction_ptr=None, ipointer_ptr=None):
         """QlearnIA.play bookkeeping + Trainer.remember for this lock-step; call before step()."""
@@ -497,6 +500,7 @@ class ArenaBatch:
     def replay_prioritize(self, alpha=0.6, eps=1e-3):
         """Enable prioritized experience replay on the memory: masses p^alpha per row, new rows at the running max."""
         nat.check(nat.lib().ofx_replay_prioritize(self._h, float(alpha), float(eps)))
+        self.replay_prioritized = True
 
     def replay_sample_prioritized(self, seed, draw, batch, beta, slot=None, n=None, is_weight=None):
         """Stratified proportional sample per arena -> (slot [N][batch], n [N], is_weight [N][batch]) DeviceBuffers;
@@ -527,6 +531,64 @@ class ArenaBatch:
         n = C.c_int32()
         nat.check(nat.lib().ofx_replay_priorities_host(self._h, int(arena), m.ctypes.data_as(C.c_void_p), C.byref(n)))
         return m[:n.value]
+
+    # ------------------------------------------------------------ checkpoint (include/ofx.h: the blob's layout)
+    def replay_export_bytes(self, arena0, n):
+        """The exact size of the blob replay_export(arena0, n) returns (runs the device's count pass)."""
+        v = C.c_size_t(0)
+        nat.check(nat.lib().ofx_replay_export_bytes(self._h, int(arena0), int(n), C.byref(v)))
+        return int(v.value)
+
+    def replay_export(self, arena0, n):
+        """The replay memory of local arenas [arena0, arena0 + n) as one self-describing blob (uint8 array): every
+        state array raw, the frame ring packed on the device to (word index, word) pairs of its nonzero words."""
+        blob = np.empty(self.replay_export_bytes(arena0, n), np.uint8)
+        w = C.c_size_t(0)
+        nat.check(nat.lib().ofx_replay_export(self._h, int(arena0), int(n), blob.ctypes.data_as(C.c_void_p), blob.nbytes,
+                                               C.byref(w)))
+        if w.value != blob.nbytes:
+            raise Exception("replay_export: wrote %d of %d bytes" % (w.value, blob.nbytes))
+        return blob
+
+    def replay_import(self, arena0, n, blob):
+        """Replace the memory of arenas [arena0, arena0 + n) by a replay_export blob; checked on the host
+        (ofx_replay_blob_check) before anything is written, so a refused blob leaves the memory as it was."""
+        blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview))
+                                    else blob, np.uint8)
+        nat.check(nat.lib().ofx_replay_import(self._h, int(arena0), int(n), blob.ctypes.data_as(C.c_void_p), blob.nbytes))
+
+    STATE_FIELDS = ("ship_x", "ship_y", "ship_px", "ship_py", "ship_alive", "reward", "score", "n_lasers", "laser_x",
+                    "laser_y", "laser_owner", "laser_dead", "killer", "time", "last_scores", "hull", "laser_dx", "laser_dy",
+                    "obs_reward")          # the OFX_F_* fields by number: all of the arena state that outlives a lock-step
+
+    def state_dict(self):
+        """The arena state a resumed run needs: the 19 state fields as get() returns them, plus the episode and tick
+        counters.  Not carried: the overflow counter (it counts "since the last call"), the episode sums (every restart
+        rewrites them before they are read) and the observation maps (a pure function of the state)."""
+        d = {name: self.get(f) for f, name in enumerate(self.STATE_FIELDS)}
+        d["episode"], d["tick"] = int(self.episode), int(self.tick)
+        return d
+
+    def load_state_dict(self, d):
+        """Upload state_dict()'s arrays into a spawned handle of the same shape and rasterise.  Every shape and dtype is
+        checked before the first upload."""
+        arrs = []
+        for f, name in enumerate(self.STATE_FIELDS):
+            if name not in d:
+                raise ValueError("ArenaBatch.load_state_dict: field %r is missing" % name)
+            a, dt = np.asarray(d[name]), np.dtype(_FIELD_DTYPE[f])
+            nbytes = nat.lib().ofx_field_bytes(self._h, f)
+            shape = (self.N,) if f in (nat.F_N_LASERS, nat.F_TIME) else (self.N, nbytes // dt.itemsize // self.N)
+            if a.dtype != dt or a.shape != shape:
+                raise ValueError("ArenaBatch.load_state_dict: field %r is %s %s, this batch holds %s %s"
+                                 % (name, a.dtype, a.shape, dt, shape))
+            arrs.append(np.ascontiguousarray(a))
+        episode, tick = int(d["episode"]), int(d["tick"])
+        self.sync()
+        for f, a in enumerate(arrs):
+            nat.check(nat.lib().ofx_memcpy_h2d(self.device_ptr(f), a.ctypes.data_as(C.c_void_p), a.nbytes))
+        self.episode, self.tick = episode, tick
+        self.rasterise()
 
     # ------------------------------------------------------------ n-step returns (include/ofx.h: the contract)
     def replay_gather_nstep_into(self, slot, n_sampled, batch, first, max_rows, nstep, gamma, rows, bits_prev, bits_next,

@@ -119,6 +119,14 @@ class TrainingRollout(ShardedRollout):
         `trainer.replay(batch_size)` every `replay_every` total steps          :414-415  (total_steps % 50 == 0)
           and on the lock-steps where a learning agent first sees its death    :376-378
         a snapshot every `snapshot_every` episodes                             :416-417
+        a checkpoint every `checkpoint_every` episodes (not in the reference; off by default)
+
+    A snapshot is the trainer's weights alone (DeviceTrainer.save, the Keras-compatible .npz).  `checkpoint(path)` writes
+    everything the run needs to go on in another process - arenas, replay memory, optimiser, counters
+    (ofighters_amd/checkpoint.py) - and `restore(path)`, called on a freshly constructed TrainingRollout built with the
+    same arguments on a fresh ArenaBatch + DeviceTrainer, continues it bit for bit.  With `checkpoint_every=K` and a
+    `checkpoint_folder`, the lock-step that completes every K-th episode ends by writing `<folder>/checkpoint-latest`,
+    replacing the previous one (the episode's restart is then the first thing the restored run does).
 
     The reference calls replay once per dying agent; the batched form does at most ONE replay per lock-step (its
     minibatch already draws from every arena's memory), on `DeviceTrainer.fit_batch` rows of what it sampled.  After a fit the trainer's blob has changed in place and
@@ -132,7 +140,8 @@ class TrainingRollout(ShardedRollout):
     """
 
     def __init__(self, engine, trainer, behaviours, seed, policy_ships=(0,), is_learning=True, collecting_steps=20,
-                 replay_every=50, replay_on_death=True, snapshot_every=50, snapshot_folder=None, **kw):
+                 replay_every=50, replay_on_death=True, snapshot_every=50, snapshot_folder=None, checkpoint_every=0,
+                 checkpoint_folder=None, **kw):
         super().__init__(engine, behaviours, seed, **kw)
         self.trainer = trainer
         self.is_learning = bool(is_learning)
@@ -141,6 +150,8 @@ class TrainingRollout(ShardedRollout):
         self.replay_on_death = bool(replay_on_death)
         self.snapshot_every = snapshot_every
         self.snapshot_folder = snapshot_folder     # None: no files are written
+        self.checkpoint_every = checkpoint_every   # 0: no checkpoints
+        self.checkpoint_folder = checkpoint_folder
         self.total_steps = 0                       # Agent.total_steps of the learning agents (agent.py:68)
         self.episode = 0
         self.losses = []                           # QlearnIA.losses: history['loss'][0] = mse(output1) + mse(output2)
@@ -169,6 +180,25 @@ class TrainingRollout(ShardedRollout):
             self.snapshots.append(self.trainer.save(id="iteration-%s" % self.episode, overwrite=True,
                                                     folder=self.snapshot_folder))
         return total
+
+    def lockstep(self):
+        super().lockstep()
+        if (self.checkpoint_every and self.checkpoint_folder is not None and self.tick % self.episode_ticks == 0
+                and (self.episode + 1) % self.checkpoint_every == 0):   # this lock-step completed episode number episode + 1
+            import os
+            os.makedirs(self.checkpoint_folder, exist_ok=True)
+            self.checkpoint(os.path.join(self.checkpoint_folder, "checkpoint-latest"))
+
+    def checkpoint(self, path):
+        """Write the whole run - arenas, replay memory, trainer, counters - to `path`, between two lock-steps."""
+        from . import checkpoint
+        return checkpoint.save(self, path)
+
+    def restore(self, path):
+        """Continue the run `checkpoint(path)` wrote.  ValueError, with nothing touched, when the checkpoint's dimensions
+        or fingerprints differ from this rollout's; returns the checkpoint's manifest."""
+        from . import checkpoint
+        return checkpoint.load(self, path)
 
     def _replay(self):
         loss = self.trainer.replay()

@@ -33,11 +33,39 @@ so a row's seed is clamp(e, -d, d) - inside the quadratic zone HALF the mse grad
 priorities of `prioritized` stay the raw |TD error|.  clip_norm scales the whole gradient by
 min(1, c / (norm + 1e-6)) before Adam (torch.nn.utils.clip_grad_norm_).  With either set, `grad_norms` collects the
 gradient's norm before clipping of every fit step, next to `losses` (which then holds the Huber losses).  Both work with
-`prioritized`, `n_step`, the target network and `double_dqn`, which only change targets and sampling."""
+`prioritized`, `n_step`, the target network and `double_dqn`, which only change targets and sampling.
+
+save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
+(`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
+cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
+needs to go on as if it had never stopped - weights, both Adam moments, the target blob, the fit / draw counters that key
+the sampler's Philox streams and the Adam bias correction, the loss lists and the epsilon schedule's position - guarded by
+a fingerprint of the hyperparameters that must match.  TrainingRollout.checkpoint() adds the replay memory, the arenas
+and its own counters (ofighters_amd/checkpoint.py); a run restored from it continues bit for bit."""
 import numpy as np
 
 from .engine import DeviceBuffer
 from .lib.epsilon import Epsilon_cos
+
+
+def epsilon_state(eps):
+    """An exploration schedule's position: its class name and scalar attributes (lib/epsilon.py keeps the reference's
+    API, so the state is read and set from here)."""
+    return {"class": type(eps).__name__,
+            "attrs": {k: v for k, v in sorted(vars(eps).items())
+                      if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)}}
+
+
+def set_epsilon_state(eps, state):
+    if type(eps).__name__ != state["class"]:
+        raise ValueError("epsilon schedule: the state is a %s's, the trainer has a %s" % (state["class"], type(eps).__name__))
+    for k, v in state["attrs"].items():
+        setattr(eps, k, v.item() if isinstance(v, np.generic) else v)
+
+
+def fingerprint_diff(have, want):
+    """The keys on which two fingerprints differ (missing keys included), sorted."""
+    return sorted(k for k in set(have) | set(want) if k not in have or k not in want or have[k] != want[k])
 
 
 class DeviceTrainer:
@@ -141,6 +169,57 @@ class DeviceTrainer:
             raise Exception("%s exists (overwrite=False)" % path)
         save_npz(path, self.weights_host())
         return path
+
+    def fingerprint(self):
+        """The hyperparameters a state must have been taken under to be loaded here."""
+        b = self.batch
+        return {"n_floats": int(self.n_floats), "learning_rate": float(self.learning_rate), "gamma": float(self.gamma),
+                "batch_size": int(self.batch_size), "fit_batch": int(self.fit_batch), "seed": int(self.seed),
+                "reference_quirks": self.reference_quirks, "prioritized": self.prioritized,
+                "per_alpha": float(self.per_alpha), "per_beta": float(self.per_beta),
+                "per_beta_steps": int(self.per_beta_steps), "per_eps": float(self.per_eps), "n_step": self.n_step,
+                "target_sync": self.target_sync, "target_tau": self.target_tau, "double_dqn": self.double_dqn,
+                "huber_delta": self.huber_delta, "clip_norm": self.clip_norm,
+                "memory_capacity": int(b.replay_capacity), "memory_frames": int(b.replay_frames)}
+
+    def state_dict(self):
+        """Everything of the trainer that a resumed run needs (host copies; the replay memory belongs to the batch)."""
+        self.batch.sync()
+        blob = lambda buf: buf.download(np.float32, (self.n_floats,))
+        return {"fingerprint": self.fingerprint(), "weights": blob(self.weights), "adam_m": blob(self.adam_m),
+                "adam_v": blob(self.adam_v), "target": None if self.target is None else blob(self.target),
+                "fit_steps": int(self.fit_steps), "draws": int(self.draws),
+                "losses": np.array(self.losses, np.float64).reshape(-1, 2), "grad_norms": np.array(self.grad_norms, np.float64),
+                "epsilon": epsilon_state(self.epsilon)}
+
+    def load_state_dict(self, d):
+        """Take over a state_dict().  The fingerprint is compared first: any difference raises ValueError listing every
+        differing key before a device write.  The blobs go into the existing device buffers, so pointers held elsewhere
+        (a pinned policy) stay valid; pin the weights again to have them prepared."""
+        diff = fingerprint_diff(self.fingerprint(), d["fingerprint"])
+        if diff:
+            raise ValueError("DeviceTrainer.load_state_dict: the state was taken under other hyperparameters: "
+                             + ", ".join("%s (%r here, %r there)" % (k, self.fingerprint().get(k), d["fingerprint"].get(k))
+                                         for k in diff))
+        blobs = {}
+        for k in ("weights", "adam_m", "adam_v", "target"):
+            if k == "target" and self.target is None:
+                if d.get("target") is not None:
+                    raise ValueError("DeviceTrainer.load_state_dict: the state has a target network, this trainer none")
+                continue
+            a = d.get(k)
+            if a is None or np.asarray(a).dtype != np.float32 or np.asarray(a).shape != (self.n_floats,):
+                raise ValueError("DeviceTrainer.load_state_dict: %s must be float32 [%d]" % (k, self.n_floats))
+            blobs[k] = np.ascontiguousarray(a)
+        if type(self.epsilon).__name__ != d["epsilon"]["class"]:
+            set_epsilon_state(self.epsilon, d["epsilon"])       # raises
+        self.batch.sync()
+        for k, a in blobs.items():
+            getattr(self, k).upload(a)
+        self.fit_steps, self.draws = int(d["fit_steps"]), int(d["draws"])
+        self.losses = [(float(a), float(b)) for a, b in np.asarray(d["losses"], np.float64).reshape(-1, 2)]
+        self.grad_norms = [float(x) for x in np.asarray(d["grad_norms"], np.float64).reshape(-1)]
+        set_epsilon_state(self.epsilon, d["epsilon"])
 
     def replay(self, batch_size=None):
         """One Trainer.replay: a minibatch of min(batch_size, len(memory)) rows per arena, targets, one fit step.
