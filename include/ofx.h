@@ -534,6 +534,54 @@ int ofx_replay_import(ofx_handle *h, int32_t arena0, int32_t n_arenas, const voi
 int ofx_replay_blob_check(const void *src_host, size_t bytes, int32_t n_ships, int32_t width, int32_t height,
                           int32_t capacity, int32_t frames, int32_t prioritized, int32_t n_arenas);
 
+/* ---- packed frame store (opt-in, exact) ----------------------------------
+ * The frame ring of ofx_replay_create is frame_bits [N][F][2][W*H/32]: 40 KB per stored lock-step and arena at 400x400,
+ * 82 GB at 4096 arenas with capacity 400.  Its maps are 1-bit discs, nearly every word zero.  ofx_replay_create_packed
+ * builds the same memory - capacity, frames (0 = capacity + capacity/4 + 2), the same checks - that KEEPS its frames as
+ * the (word index, word) pairs of their nonzero words, the form the checkpoint blob already has.  Nothing else differs:
+ * every entry point above that reads the memory returns the bytes it returns from the dense ring holding the same
+ * frames, the blob format stays version 1, and a blob exported from either form imports into the other.
+ *  - Storage per arena: a POOL of pool_pairs uint2 (word index, word), a cyclic buffer (position i means i mod
+ *    pool_pairs), and
+ *       frame_off [N][F] uint32      pool position of the slot's first pair
+ *       frame_cnt [N][F][2] uint32   pairs of the slot's ship map and of its laser map; 0 in a slot without a live frame
+ *       pool_head [N] uint32, live [N] uint32 (pairs of all live frames), evicted [N] int64
+ *    A slot's pairs are its ship map's, then its laser map's; within a map the word index ascends strictly, a zero word
+ *    is never stored, and pixel p is bit (p & 31) of word p >> 5 - the order of the blob's pair section.
+ *  - Sizing: pool_pairs = 0 selects max(512 * frames, 4 * words), words = W*H/32.  512 pairs per slot is about twice the
+ *    mean of the densest run on record (245 pairs per frame, every ship capturing, profiles/r08_checkpoint_4096.txt) and
+ *    8.2 GB instead of 82 GB at the size above; it rests on that one profile, and profiles/r09_packed_replay.txt has what
+ *    a training run needs.  Any other value must lie in [4 * words, 2^31): a frame has at most 2 * words pairs, so the
+ *    newest frame and its predecessor - the two a transition needs - always fit together.  Otherwise OFX_ERR_INVALID
+ *    naming the bound; also when the two maps of a frame (8 * words bytes) exceed the 64 KB of LDS in which the
+ *    readers rebuild them, i.e. for arenas above W*H = 262 144 (the dense ring serves those).
+ *  - Storing a frame of k = k_ship + k_laser pairs into slot s = frame_head (ofx_replay_capture), the rule:
+ *      1. If slot s still holds a live frame (the slot ring has wrapped), release it: live -= its pairs.  It is the
+ *         oldest frame.
+ *      2. While live + k > pool_pairs, release the oldest live frame - the first slot with frame_tick >= 0 walking
+ *         cyclically from s + 1: frame_tick = -1, both counts 0, live -= its pairs, evicted[a] += 1.  EARLY EVICTION.
+ *      3. frame_off[s] = pool_head; the k pairs go to pool_head .. pool_head + k - 1 (mod pool_pairs); pool_head =
+ *         (pool_head + k) mod pool_pairs, live += k, frame_tick[s] = tick.
+ *    So frames leave oldest-first under both mechanisms; the live frames are a cyclic run of slots ending at
+ *    frame_head - 1 and their pairs a cyclic run of the pool ending at pool_head; live depends on the live frames'
+ *    counts only, never on where they lie.  An early-evicted frame is to every reader what an overwritten frame is:
+ *    ofx_replay_frame_host answers OFX_ERR_STATE, and the rows whose `state` frame is gone stay in the row ring and are
+ *    skipped by both samplers (frame_tick[frame_prev] != tick_prev).  Nothing is truncated silently: a pool that is
+ *    too small shows as fewer eligible rows and in ofx_replay_store_stats.
+ *  - Checkpoint: the export's count section is frame_cnt and its pair section the slots' pair ranges, un-wrapped -
+ *    byte for byte the dense ring's blob of the same frames (an early-evicted slot is an empty slot).  The import runs
+ *    ofx_replay_blob_check, then places every arena's live frames in chronological order (the slots walked from
+ *    frame_head, oldest first) from pool position 0 and sets frame_off, frame_cnt, pool_head and live accordingly; the
+ *    memory behaves from then on as the one that was exported.  If an arena's live pairs exceed pool_pairs the import
+ *    fails with OFX_ERR_INVALID naming the arena and both numbers before anything on the device is written.  evicted is
+ *    a per-process counter like ofx_overflow_count and not carried.
+ * ofx_replay_store_stats synchronises and fills stats_host[6]: [0] 1 packed / 0 dense, [1] pool_pairs per arena,
+ * [2] max over arenas of live, [3] sum over arenas of live, [4] sum of evicted since create, [5] bytes of HBM the frame
+ * store holds (dense: frame_bits; packed: pool + frame_off + frame_cnt + pool_head + live + evicted).  A dense memory
+ * reports [1] .. [4] as 0.  OFX_ERR_STATE without a replay memory.                                                  */
+int ofx_replay_create_packed(ofx_handle *h, int32_t capacity, int32_t frames, int64_t pool_pairs);
+int ofx_replay_store_stats(ofx_handle *h, int64_t *stats_host /* [6] */);
+
 /* ---- n-step returns (opt-in) --------------------------------------------
  * Not in the reference.  Off unless these two calls are used; nothing above changes.
  *  - Window: ofx_replay_gather_nstep gathers the window ofx_replay_gather_valid gathers for the same (slot, n_sampled,

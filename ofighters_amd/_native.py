@@ -122,6 +122,8 @@ SIGNATURES = {
                                 C.c_float, C.c_float, _vp]),
     "ofx_dqn_fit_reference": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "ofx_replay_create": (_i, [_vp, C.c_int32, C.c_int32]),
+    "ofx_replay_create_packed": (_i, [_vp, C.c_int32, C.c_int32, C.c_int64]),
+    "ofx_replay_store_stats": (_i, [_vp, C.POINTER(C.c_int64)]),
     "ofx_replay_destroy": (_i, [_vp]),
     "ofx_replay_capture": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "ofx_agents_first_done": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

@@ -12,7 +12,12 @@
 //                                    index: the order of request_actions, battleground.py:146-150)
 //   per ship [N][M]                  previous_obs / previous_action / previous_pointer (+ the toVector head) and the
 //                                    agent's `done` latch
+// Packed form of the frame ring (ofx_replay_create_packed; include/ofx.h, "packed frame store", states the contract):
+//   pool      [N][pool_pairs] uint2   cyclic buffer of (word index, word) pairs of the nonzero words of the live frames
+//   frame_off [N][F] u32, frame_cnt [N][F][2] u32, pool_head [N] u32, live [N] u32, evicted [N] i64
+// Every reader of a frame goes through frame_read below; the dense form is the plain 16-byte copy it always was.
 #include "ofx_internal.h"
+#include "ofx_packed.h"
 #include <float.h>
 #include <string.h>
 
@@ -35,6 +40,15 @@ struct ofx_replay {
   float *mass;             // [N][C] p^alpha, same ring positions as rows
   float *mmax;             // [N] running maximum mass: what a new row gets
   float alpha, eps;
+  // packed frame store (ofx_replay_create_packed), frame_bits is null then
+  int32_t packed;
+  uint32_t pool_pairs;     // per arena
+  uint2 *pool;             // [N][pool_pairs]
+  uint32_t *frame_off;     // [N][F]    pool position of the slot's first pair
+  uint32_t *frame_cnt;     // [N][F][2] pairs of the ship map / of the laser map; 0 in slots that hold no live frame
+  uint32_t *pool_head;     // [N]
+  uint32_t *live;          // [N] pairs of all live frames
+  long long *evicted;      // [N] frames released early, since create
 };
 
 void ofx_replay_free(ofx_handle *h) {
@@ -42,7 +56,8 @@ void ofx_replay_free(ofx_handle *h) {
   if (!r) return;
   void *ptrs[] = {r->frame_bits, r->frame_tick, r->rows, r->head, r->count, r->appended, r->has_prev, r->latched,
                   r->prev_iaction, r->prev_px, r->prev_py, r->prev_tick, r->prev_head, r->frame_head, r->cur_slot,
-                  r->prev_slot, r->scan_off, r->mass, r->mmax};
+                  r->prev_slot, r->scan_off, r->mass, r->mmax, r->pool, r->frame_off, r->frame_cnt, r->pool_head, r->live,
+                  r->evicted};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   delete r;
   h->replay = nullptr;
@@ -55,16 +70,36 @@ static int zalloc(T **p, size_t count, int fill = 0) {
   return OFX_OK;
 }
 
-extern "C" int ofx_replay_create(ofx_handle *h, int32_t capacity, int32_t frames) {
-  if (!h) { ofx_set_error("ofx_replay_create: null handle"); return OFX_ERR_INVALID; }
+#define OFX_LDS_LIMIT (64 * 1024) /* dynamic LDS a launch may ask for: the packed readers build a frame's two maps there */
+
+// ofx_replay_create (pool_pairs < 0: the dense ring) and ofx_replay_create_packed (pool_pairs >= 0)
+static int replay_create(ofx_handle *h, const char *who, int32_t capacity, int32_t frames, int64_t pool_pairs) {
+  if (!h) { ofx_set_error("%s: null handle", who); return OFX_ERR_INVALID; }
   if (capacity <= 0 || frames < 0 || frames == 1) {
-    ofx_set_error("ofx_replay_create: capacity must be > 0 and frames >= 2 (or 0 = capacity + capacity / 4 + 2), got %d, %d",
+    ofx_set_error("%s: capacity must be > 0 and frames >= 2 (or 0 = capacity + capacity / 4 + 2), got %d, %d", who,
                   capacity, frames);
     return OFX_ERR_INVALID;
   }
   if (((size_t)h->cfg.width * h->cfg.height) % 128) {
-    ofx_set_error("ofx_replay_create: width*height must be a multiple of 128");
+    ofx_set_error("%s: width*height must be a multiple of 128", who);
     return OFX_ERR_INVALID;
+  }
+  const bool packed = pool_pairs >= 0;
+  if (packed) {
+    const int32_t F = frames ? frames : capacity + capacity / 4 + 2, words = (int32_t)(((size_t)h->cfg.width * h->cfg.height) >> 5);
+    int64_t low, high;
+    const int64_t want = pool_pairs;
+    pool_pairs = ofx_packed_pool_pairs(want, F, words, &low, &high);
+    if (!pool_pairs) {
+      ofx_set_error("%s: pool_pairs must be 0 (= max(512 * frames, 4 * words)) or lie in [4 * words, 2^31) = [%lld, %lld), got %lld",
+                    who, (long long)low, (long long)high, (long long)(want ? want : 512 * (int64_t)F));
+      return OFX_ERR_INVALID;
+    }
+    if ((size_t)words * 8 > OFX_LDS_LIMIT) {
+      ofx_set_error("%s: the two maps of a frame (%zu bytes) exceed the %d bytes of LDS the packed gather builds them in", who,
+                    (size_t)words * 8, OFX_LDS_LIMIT);
+      return OFX_ERR_INVALID;
+    }
   }
   OFX_HIP(hipSetDevice(h->cfg.device));
   OFX_HIP(hipStreamSynchronize(h->stream));
@@ -79,7 +114,15 @@ extern "C" int ofx_replay_create(ofx_handle *h, int32_t capacity, int32_t frames
   r->words = (int32_t)(((size_t)h->cfg.width * h->cfg.height) >> 5);
   int rc;
 #define A(field, count, fill) if ((rc = zalloc(&r->field, (count), (fill)))) { ofx_replay_free(h); return rc; }
-  A(frame_bits, (size_t)r->frames * 2 * N * r->words, 0)
+  if (packed) {
+    r->packed = 1;
+    r->pool_pairs = (uint32_t)pool_pairs;
+    A(pool, N * (size_t)pool_pairs, 0)
+    A(frame_off, N * (size_t)r->frames, 0) A(frame_cnt, N * (size_t)r->frames * 2, 0)
+    A(pool_head, N, 0) A(live, N, 0) A(evicted, N, 0)
+  } else {
+    A(frame_bits, (size_t)r->frames * 2 * N * r->words, 0)
+  }
   A(frame_tick, N * (size_t)r->frames, 0xFF)
   A(frame_head, N, 0) A(cur_slot, N, 0xFF) A(prev_slot, N * M, 0)
   A(rows, N * (size_t)capacity, 0)
@@ -90,6 +133,51 @@ extern "C" int ofx_replay_create(ofx_handle *h, int32_t capacity, int32_t frames
   A(scan_off, N + 1, 0)
 #undef A
   OFX_HIP(hipDeviceSynchronize());  // null-stream fills vs the handle's non-blocking stream
+  return OFX_OK;
+}
+
+extern "C" int ofx_replay_create(ofx_handle *h, int32_t capacity, int32_t frames) {
+  return replay_create(h, "ofx_replay_create", capacity, frames, -1);
+}
+
+extern "C" int ofx_replay_create_packed(ofx_handle *h, int32_t capacity, int32_t frames, int64_t pool_pairs) {
+  if (pool_pairs < 0) {
+    ofx_set_error("ofx_replay_create_packed: pool_pairs must be 0 (the default) or lie in [4 * words, 2^31), got %lld",
+                  (long long)pool_pairs);
+    return OFX_ERR_INVALID;
+  }
+  return replay_create(h, "ofx_replay_create_packed", capacity, frames, pool_pairs);
+}
+
+extern "C" int ofx_replay_store_stats(ofx_handle *h, int64_t *stats_host) {
+  if (!h || !stats_host) { ofx_set_error("ofx_replay_store_stats: null argument"); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  if (!r) { ofx_set_error("ofx_replay_store_stats: no replay memory"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  const size_t N = h->cfg.n_arenas;
+  for (int i = 0; i < 6; i++) stats_host[i] = 0;
+  if (!r->packed) {
+    stats_host[5] = (int64_t)(sizeof(uint32_t) * N * (size_t)r->frames * 2 * r->words);
+    return OFX_OK;
+  }
+  uint32_t *live = (uint32_t *)malloc(sizeof(uint32_t) * N);
+  long long *ev = (long long *)malloc(sizeof(long long) * N);
+  hipError_t e = (live && ev) ? hipMemcpy(live, r->live, sizeof(uint32_t) * N, hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
+  if (e == hipSuccess) e = hipMemcpy(ev, r->evicted, sizeof(long long) * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) {
+    stats_host[0] = 1;
+    stats_host[1] = r->pool_pairs;
+    for (size_t a = 0; a < N; a++) {
+      if ((int64_t)live[a] > stats_host[2]) stats_host[2] = live[a];
+      stats_host[3] += live[a];
+      stats_host[4] += ev[a];
+    }
+    stats_host[5] = ofx_packed_store_bytes((int64_t)N, r->frames, r->pool_pairs);
+  }
+  free(live);
+  free(ev);
+  OFX_HIP(e);
   return OFX_OK;
 }
 
@@ -214,6 +302,93 @@ __global__ __launch_bounds__(256) void k_replay_frames(int N, int F, int words, 
   for (int k = threadIdx.x; k < q; k += 256) { dst[k] = s0[k]; dst[q + k] = s1[k]; }
 }
 
+// The packed form of k_replay_frames: one workgroup per arena that stores a frame, four waves.  A map is q = words / 4
+// uint4s = P = ceil(q / 64) passes of 64 lanes; wave w takes the passes [w * per, (w + 1) * per) of BOTH maps, so within a
+// map the waves' pairs follow each other in wave order.  Count pass (ballots of the nonzero components), the waves' counts
+// through LDS, lane 0 runs steps 1 and 2 of the storing rule (include/ofx.h) and publishes the base, then the write pass
+// repeats the walk: a lane's position is its wave's base + the nonzero words in the lanes and components below it.
+// k_replay_capture has already written frame_tick of the new slot s: step 1 reads the slot's old counts (0 unless it
+// held a live frame) and the eviction walk covers the F - 1 other slots only.
+__global__ __launch_bounds__(256) void k_replay_frames_packed(int N, int F, int words, const uint32_t *ship_bits,
+                                                              const uint32_t *laser_bits, ofx_replay r) {
+  __shared__ uint32_t wcnt[2][4];
+  __shared__ uint32_t base_s;
+  const int a = blockIdx.x;
+  const int s = r.cur_slot[a];
+  if (s < 0) return;  // block-uniform
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint4 *src[2] = {reinterpret_cast<const uint4 *>(ship_bits + (size_t)a * words),
+                         reinterpret_cast<const uint4 *>(laser_bits + (size_t)a * words)};
+  const int q = words >> 2, P = (q + 63) >> 6, per = (P + 3) >> 2;
+  const int p0 = min(wave * per, P), p1 = min(p0 + per, P);  // wave-uniform
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int m = 0; m < 2; m++) {
+    uint32_t run = 0;
+    for (int pass = p0; pass < p1; pass++) {  // wave-uniform trip count: the ballots see every lane
+      const int k = pass * 64 + lane;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (k < q) v = src[m][k];
+      run += (uint32_t)__popcll(__ballot(v.x != 0u)) + (uint32_t)__popcll(__ballot(v.y != 0u)) +
+             (uint32_t)__popcll(__ballot(v.z != 0u)) + (uint32_t)__popcll(__ballot(v.w != 0u));
+    }
+    if (lane == 0) wcnt[m][wave] = run;
+  }
+  __syncthreads();
+  const uint32_t k_ship = wcnt[0][0] + wcnt[0][1] + wcnt[0][2] + wcnt[0][3];
+  const uint32_t k_laser = wcnt[1][0] + wcnt[1][1] + wcnt[1][2] + wcnt[1][3];
+  const uint32_t pool_pairs = r.pool_pairs;
+  if (threadIdx.x == 0) {
+    const uint32_t k = k_ship + k_laser;  // <= 2 * words <= pool_pairs / 2
+    uint32_t *cnt = r.frame_cnt + (size_t)a * F * 2;
+    int32_t *tick = r.frame_tick + (size_t)a * F;
+    uint32_t live = r.live[a] - (cnt[2 * s] + cnt[2 * s + 1]);  // step 1: the slot ring has wrapped onto its oldest frame
+    long long ev = 0;
+    for (int i = 1, j = s + 1; i < F && live + k > pool_pairs; i++, j++) {  // step 2: early eviction, oldest first
+      if (j >= F) j -= F;
+      if (tick[j] < 0) continue;
+      live -= cnt[2 * j] + cnt[2 * j + 1];
+      tick[j] = -1;
+      cnt[2 * j] = 0u;
+      cnt[2 * j + 1] = 0u;
+      ev++;
+    }
+    const uint32_t head = r.pool_head[a];
+    r.frame_off[(size_t)a * F + s] = head;  // step 3
+    cnt[2 * s] = k_ship;
+    cnt[2 * s + 1] = k_laser;
+    r.pool_head[a] = (head + k) % pool_pairs;
+    r.live[a] = live + k;
+    if (ev) r.evicted[a] += ev;
+    base_s = head;
+  }
+  __syncthreads();
+  uint2 *pool = r.pool + (size_t)a * pool_pairs;
+  for (int m = 0; m < 2; m++) {
+    uint32_t run = base_s + (m ? k_ship : 0u);
+    for (int w = 0; w < wave; w++) run += wcnt[m][w];
+    for (int pass = p0; pass < p1; pass++) {
+      const int k = pass * 64 + lane;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (k < q) v = src[m][k];
+      const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+      uint32_t pos = run;
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const unsigned long long bal = __ballot(w4[c] != 0u);
+        pos += (uint32_t)__popcll(bal & below);
+        run += (uint32_t)__popcll(bal);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; c++)
+        if (w4[c] != 0u) {  // base < pool_pairs and at most 2 * words pairs follow it: one wrap at the most, then < pool_pairs
+          const uint32_t at = pos >= pool_pairs ? pos - pool_pairs : pos;
+          pool[at] = make_uint2((uint32_t)(4 * k + c), w4[c]);
+          pos++;
+        }
+    }
+  }
+}
+
 extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
                                   const int32_t *ipointer) {
   if (!h) { ofx_set_error("ofx_replay_capture: null handle"); return OFX_ERR_INVALID; }
@@ -236,8 +411,12 @@ extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *s
   p.tick = (int)tick; p.st = h->st; p.mask = ship_mask; p.iaction = iaction; p.ipointer = ipointer; p.r = *r;
   hipLaunchKernelGGL(k_replay_capture, dim3((p.N + 3) / 4), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_replay_frames, dim3((unsigned)p.N), dim3(256), 0, h->stream, p.N, r->frames, r->words,
-                     (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][0], (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][1], *r);
+  if (r->packed)
+    hipLaunchKernelGGL(k_replay_frames_packed, dim3((unsigned)p.N), dim3(256), 0, h->stream, p.N, r->frames, r->words,
+                       (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][0], (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][1], *r);
+  else
+    hipLaunchKernelGGL(k_replay_frames, dim3((unsigned)p.N), dim3(256), 0, h->stream, p.N, r->frames, r->words,
+                       (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][0], (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][1], *r);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -300,6 +479,43 @@ extern "C" int ofx_replay_rows_host(ofx_handle *h, int32_t arena, ofx_transition
   return OFX_OK;
 }
 
+// ---- the one reader of a stored frame: slot `slot` of arena a -> out[2][words] (16-byte aligned), every word written ----
+// Dense: the 16-byte copy.  Packed: the workgroup (256 threads, all of them must call) builds the two maps in LDS - zero,
+// barrier, scatter the slot's pairs, barrier - and streams them out with 16-byte stores; the launch gives 8 * words bytes
+// of dynamic LDS.  A slot without a live frame has counts 0 and reads as two empty maps.
+template <bool PACKED>
+__device__ __forceinline__ void frame_read(const ofx_replay &r, int a, int F, int words, int slot, uint32_t *out) {
+  uint4 *out4 = reinterpret_cast<uint4 *>(out);
+  const int n4 = 2 * words / 4;
+  if constexpr (!PACKED) {
+    const uint4 *in = reinterpret_cast<const uint4 *>(r.frame_bits + ((size_t)a * F + slot) * 2 * words);
+    for (int k = threadIdx.x; k < n4; k += 256) out4[k] = in[k];
+  } else {
+    extern __shared__ uint4 frame_lds[];
+    uint32_t *lds = reinterpret_cast<uint32_t *>(frame_lds);
+    for (int k = threadIdx.x; k < n4; k += 256) frame_lds[k] = make_uint4(0u, 0u, 0u, 0u);
+    const size_t fs = (size_t)a * F + slot;
+    const uint32_t c0 = r.frame_cnt[2 * fs], n = c0 + r.frame_cnt[2 * fs + 1], off = r.frame_off[fs];
+    const uint32_t pool_pairs = r.pool_pairs;
+    const uint2 *pool = r.pool + (size_t)a * pool_pairs;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n; i += 256) {
+      uint32_t at = off + i;  // off < pool_pairs, i < 2 * words <= pool_pairs / 2
+      if (at >= pool_pairs) at -= pool_pairs;
+      const uint2 pr = pool[at];
+      if (pr.x < (uint32_t)words) lds[(i < c0 ? 0u : (uint32_t)words) + pr.x] = pr.y;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < n4; k += 256) out4[k] = frame_lds[k];
+    __syncthreads();  // the next frame_read of this workgroup zeroes the LDS again
+  }
+}
+
+// ofx_replay_frame_host on a packed memory: the frame through frame_read into a device buffer
+__global__ __launch_bounds__(256) void k_replay_frame_read(int a, int F, int words, int slot, ofx_replay r, uint32_t *out) {
+  frame_read<true>(r, a, F, words, slot, out);
+}
+
 // the 1-bit maps of one stored lock-step of one arena (pixel p -> bit (p & 7) of byte p >> 3, i.e.
 // numpy.unpackbits(..., bitorder='little')); OFX_ERR_STATE when the frame has left the ring
 extern "C" int ofx_replay_frame_host(ofx_handle *h, int32_t arena, int32_t tick, void *ship_bits_host,
@@ -318,7 +534,18 @@ extern "C" int ofx_replay_frame_host(ofx_handle *h, int32_t arena, int32_t tick,
   OFX_HIP(e);
   if (f < 0) { ofx_set_error("ofx_replay_frame_host: lock-step %d is not in the frame ring of arena %d", tick, arena); return OFX_ERR_STATE; }
   const size_t wb = (size_t)r->words * 4;
-  const uint32_t *slot = r->frame_bits + ((size_t)arena * r->frames + f) * 2 * r->words;
+  const uint32_t *slot;
+  if (r->packed) {
+    int rc;
+    if ((rc = ofx_ensure_scratch(h, 2 * wb))) return rc;
+    hipLaunchKernelGGL(k_replay_frame_read, dim3(1), dim3(256), 2 * wb, h->stream, arena, r->frames, r->words, f, *r,
+                       (uint32_t *)h->scratch);
+    OFX_HIP(hipGetLastError());
+    OFX_HIP(hipStreamSynchronize(h->stream));
+    slot = (const uint32_t *)h->scratch;
+  } else {
+    slot = r->frame_bits + ((size_t)arena * r->frames + f) * 2 * r->words;
+  }
   OFX_HIP(hipMemcpy(ship_bits_host, slot, wb, hipMemcpyDeviceToHost));
   OFX_HIP(hipMemcpy(laser_bits_host, slot + r->words, wb, hipMemcpyDeviceToHost));
   return OFX_OK;
@@ -378,6 +605,7 @@ struct GatherParams {
 };
 
 // one workgroup per (arena, j): row copy + the two frames' bit maps (16-byte loads/stores)
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_replay_gather(GatherParams p) {
   const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
   const int s = p.slot[(size_t)a * p.batch + j];
@@ -399,10 +627,8 @@ __global__ __launch_bounds__(256) void k_replay_gather(GatherParams p) {
   const int slots[2] = {src->frame_prev, src->frame_next};
   uint32_t *outs[2] = {p.bits_prev, p.bits_next};
   for (int w = 0; w < 2; w++) {
-    if (!outs[w]) continue;
-    const uint4 *in = reinterpret_cast<const uint4 *>(p.r.frame_bits + ((size_t)a * p.F + slots[w]) * 2 * p.words);
-    uint4 *out = reinterpret_cast<uint4 *>(outs[w] + ((size_t)a * p.batch + j) * 2 * p.words);
-    for (int k = threadIdx.x; k < 2 * p.words / 4; k += 256) out[k] = in[k];
+    if (!outs[w]) continue;  // block-uniform
+    frame_read<PACKED>(p.r, a, p.F, p.words, slots[w], outs[w] + ((size_t)a * p.batch + j) * 2 * p.words);
   }
 }
 
@@ -414,7 +640,10 @@ extern "C" int ofx_replay_gather(ofx_handle *h, const int32_t *slot, int32_t bat
   GatherParams p;
   p.N = h->cfg.n_arenas; p.C = r->capacity; p.F = r->frames; p.batch = batch; p.words = r->words;
   p.r = *r; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
-  hipLaunchKernelGGL(k_replay_gather, dim3((unsigned)(p.N * batch)), dim3(256), 0, h->stream, p);
+  if (r->packed)
+    hipLaunchKernelGGL(k_replay_gather<true>, dim3((unsigned)(p.N * batch)), dim3(256), (size_t)r->words * 8, h->stream, p);
+  else
+    hipLaunchKernelGGL(k_replay_gather<false>, dim3((unsigned)(p.N * batch)), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -492,7 +721,7 @@ __device__ int nstep_chain(const ofx_transition *ring, int C, int first_row, int
 
 // one workgroup per (arena, j): sampled entry j of arena a is packed row off[a] + j - first, when it falls into
 // [0, max_rows).  NSTEP: the row is the composite of the n-step chain from it (wave 0 walks the chain first).
-template <bool NSTEP>
+template <bool NSTEP, bool PACKED>
 __global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, const int32_t *n_sampled, const int32_t *off, int first,
                                                              int max_rows, NstepParams q) {
   const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
@@ -523,10 +752,8 @@ __global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, con
   const int slots[2] = {src->frame_prev, end->frame_next};
   uint32_t *outs[2] = {p.bits_prev, p.bits_next};
   for (int w = 0; w < 2; w++) {
-    if (!outs[w]) continue;
-    const uint4 *in = reinterpret_cast<const uint4 *>(p.r.frame_bits + ((size_t)a * p.F + slots[w]) * 2 * p.words);
-    uint4 *out = reinterpret_cast<uint4 *>(outs[w] + (size_t)d * 2 * p.words);
-    for (int k = threadIdx.x; k < 2 * p.words / 4; k += 256) out[k] = in[k];
+    if (!outs[w]) continue;  // block-uniform
+    frame_read<PACKED>(p.r, a, p.F, p.words, slots[w], outs[w] + (size_t)d * 2 * p.words);
   }
 }
 
@@ -546,11 +773,19 @@ static int gather_window(ofx_handle *h, const char *who, const int32_t *slot, co
   GatherParams p;
   p.N = N; p.C = r->capacity; p.F = r->frames; p.batch = batch; p.words = r->words;
   p.r = *r; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
-  if (q)
-    hipLaunchKernelGGL(k_replay_gather_valid<true>, dim3((unsigned)(N * batch)), dim3(256), 0, h->stream, p, n_sampled,
+  const dim3 grid((unsigned)(N * batch));
+  const size_t lds = (size_t)r->words * 8;  // packed: the two maps of a frame
+  if (q && r->packed)
+    hipLaunchKernelGGL((k_replay_gather_valid<true, true>), grid, dim3(256), lds, h->stream, p, n_sampled,
                        (const int32_t *)off, first, max_rows, *q);
+  else if (q)
+    hipLaunchKernelGGL((k_replay_gather_valid<true, false>), grid, dim3(256), 0, h->stream, p, n_sampled,
+                       (const int32_t *)off, first, max_rows, *q);
+  else if (r->packed)
+    hipLaunchKernelGGL((k_replay_gather_valid<false, true>), grid, dim3(256), lds, h->stream, p, n_sampled,
+                       (const int32_t *)off, first, max_rows, NstepParams{});
   else
-    hipLaunchKernelGGL(k_replay_gather_valid<false>, dim3((unsigned)(N * batch)), dim3(256), 0, h->stream, p, n_sampled,
+    hipLaunchKernelGGL((k_replay_gather_valid<false, false>), grid, dim3(256), 0, h->stream, p, n_sampled,
                        (const int32_t *)off, first, max_rows, NstepParams{});
   hipError_t e = hipGetLastError();
   int32_t total = 0;
@@ -988,6 +1223,30 @@ __global__ __launch_bounds__(256) void k_replay_unpack(int n_maps, int words, co
   }
 }
 
+// The packed store's side of the blob.  One wave per map m = (arena * F + slot) * 2 + which of the chunk; the map's pairs
+// lie in the arena's pool at frame_off (+ the ship map's count for the laser map), cyclically.  TO_POOL = false: the
+// export un-wraps them into the blob's pair section at off[m]; TO_POOL = true: the import writes them to where
+// ofx_packed_place put the frame.  frame_off / frame_cnt point at the chunk's first arena, pool likewise.
+template <bool TO_POOL>
+__global__ __launch_bounds__(256) void k_replay_pool_copy(int n_maps, int F, uint32_t pool_pairs, const uint32_t *frame_off,
+                                                          const uint32_t *frame_cnt, const unsigned long long *off, uint2 *pool,
+                                                          uint2 *pairs) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (m >= n_maps) return;
+  const int fs = m >> 1;
+  const uint32_t cnt = frame_cnt[m];
+  uint32_t start = frame_off[fs] + ((m & 1) ? frame_cnt[m - 1] : 0u);  // < 2 * pool_pairs
+  if (start >= pool_pairs) start -= pool_pairs;
+  uint2 *arena_pool = pool + (size_t)(fs / F) * pool_pairs;
+  const unsigned long long lo = off[m];
+  for (uint32_t i = lane; i < cnt; i += 64) {
+    uint32_t at = start + i;  // cnt <= words <= pool_pairs / 4
+    if (at >= pool_pairs) at -= pool_pairs;
+    if constexpr (TO_POOL) arena_pool[at] = pairs[lo + i];
+    else pairs[lo + i] = arena_pool[at];
+  }
+}
+
 // handle, memory and chunk of an export / import call
 static int chunk_ready(ofx_handle *h, const char *who, int32_t arena0, int32_t n_arenas, BlobDims *d) {
   if (!h) { ofx_set_error("%s: null handle", who); return OFX_ERR_INVALID; }
@@ -1015,10 +1274,14 @@ static int pack_count(ofx_handle *h, const BlobDims &d, int32_t arena0, uint32_t
   *off = nullptr;
   OFX_HIP(hipMalloc((void **)counts, sizeof(uint32_t) * (size_t)n_maps));
   hipError_t e = hipMalloc((void **)off, sizeof(unsigned long long) * pack_scan_words(n_maps));
+  if (e == hipSuccess && r->packed)  // the store keeps the counts
+    e = hipMemcpyAsync(*counts, r->frame_cnt + (size_t)arena0 * d.F * 2, sizeof(uint32_t) * (size_t)n_maps,
+                       hipMemcpyDeviceToDevice, h->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_replay_pack<false>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
-                       r->frame_bits + (size_t)arena0 * d.F * 2 * d.words, r->frame_tick + (size_t)arena0 * d.F, *counts,
-                       (const unsigned long long *)nullptr, (uint2 *)nullptr);
+    if (!r->packed)
+      hipLaunchKernelGGL(k_replay_pack<false>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
+                         r->frame_bits + (size_t)arena0 * d.F * 2 * d.words, r->frame_tick + (size_t)arena0 * d.F, *counts,
+                         (const unsigned long long *)nullptr, (uint2 *)nullptr);
     launch_pack_scan(h, n_maps, *counts, *off);
     e = hipGetLastError();
   }
@@ -1079,9 +1342,15 @@ extern "C" int ofx_replay_export(ofx_handle *h, int32_t arena0, int32_t n_arenas
   if (rc == OFX_OK && total) {
     e = hipMalloc((void **)&pairs, 8 * (size_t)total);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_replay_pack<true>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
-                         r->frame_bits + (size_t)arena0 * d.F * 2 * d.words, r->frame_tick + (size_t)arena0 * d.F,
-                         (uint32_t *)nullptr, (const unsigned long long *)off, pairs);
+      if (r->packed)
+        hipLaunchKernelGGL(k_replay_pool_copy<false>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.F,
+                           r->pool_pairs, (const uint32_t *)r->frame_off + (size_t)arena0 * d.F,
+                           (const uint32_t *)r->frame_cnt + (size_t)arena0 * d.F * 2, (const unsigned long long *)off,
+                           r->pool + (size_t)arena0 * r->pool_pairs, pairs);
+      else
+        hipLaunchKernelGGL(k_replay_pack<true>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.words,
+                           r->frame_bits + (size_t)arena0 * d.F * 2 * d.words, r->frame_tick + (size_t)arena0 * d.F,
+                           (uint32_t *)nullptr, (const unsigned long long *)off, pairs);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1236,13 +1505,31 @@ extern "C" int ofx_replay_import(ofx_handle *h, int32_t arena0, int32_t n_arenas
                   (double)rd<float>(p + 40), (double)rd<float>(p + 44), (double)r->alpha, (double)r->eps);
     return OFX_ERR_INVALID;
   }
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipStreamSynchronize(h->stream));
   size_t per_arena[RAW_N], roff[RAW_N + 1];
   raw_layout(d, per_arena, roff);
   const int n_maps = d.n * d.F * 2;
   const uint8_t *raw = p + OFX_BLOB_HEADER, *cnt = raw + roff[RAW_N], *pr = cnt + (size_t)4 * n_maps;
   const size_t pair_bytes = (size_t)rd<uint64_t>(p + 64);
+  // a packed store: where every live frame goes, and whether every arena's pool can hold its frames - before any write
+  uint32_t *place = nullptr, *place_off = nullptr, *place_head = nullptr, *place_live = nullptr;
+  if (r->packed) {
+    const size_t nf = (size_t)d.n * d.F;
+    place = (uint32_t *)malloc(sizeof(uint32_t) * (nf + 2 * (size_t)d.n));
+    if (!place) { ofx_set_error("ofx_replay_import: out of host memory"); return OFX_ERR_INVALID; }
+    place_off = place; place_head = place + nf; place_live = place_head + d.n;
+    int64_t need = 0;
+    const int bad = ofx_packed_place(d.n, d.F, r->pool_pairs, raw + roff[RAW_FRAME_TICK], raw + roff[RAW_FRAME_HEAD], cnt,
+                                     place_off, place_head, place_live, &need);
+    if (bad >= 0) {
+      free(place);
+      ofx_set_error("ofx_replay_import: the live frames of arena %d of the chunk hold %lld pairs, the pool %u (pool_pairs of "
+                    "ofx_replay_create_packed)", bad, (long long)need, r->pool_pairs);
+      return OFX_ERR_INVALID;
+    }
+  }
+  hipError_t e0 = hipSetDevice(h->cfg.device);
+  if (e0 == hipSuccess) e0 = hipStreamSynchronize(h->stream);
+  if (e0 != hipSuccess) { free(place); OFX_HIP(e0); }
   // staging first: a failed allocation leaves the memory as it was
   uint32_t *counts = nullptr;
   unsigned long long *off = nullptr;
@@ -1258,7 +1545,24 @@ extern "C" int ofx_replay_import(ofx_handle *h, int32_t arena0, int32_t n_arenas
     const size_t nb = per_arena[i] * (size_t)d.n;
     if (nb) e = hipMemcpy((uint8_t *)dev[i] + per_arena[i] * (size_t)arena0, raw + roff[i], nb, hipMemcpyHostToDevice);
   }
-  if (e == hipSuccess) {
+  if (r->packed) {
+    const size_t nf = (size_t)d.n * d.F;
+    if (e == hipSuccess) e = hipMemcpy(r->frame_off + (size_t)arena0 * d.F, place_off, 4 * nf, hipMemcpyHostToDevice);
+    if (e == hipSuccess)  // on the stream: the scatter below reads it
+      e = hipMemcpyAsync(r->frame_cnt + (size_t)arena0 * d.F * 2, counts, (size_t)4 * n_maps, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpy(r->pool_head + arena0, place_head, 4 * (size_t)d.n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->live + arena0, place_live, 4 * (size_t)d.n, hipMemcpyHostToDevice);
+    free(place);
+    if (e == hipSuccess) {
+      launch_pack_scan(h, n_maps, counts, off);
+      if (pair_bytes)
+        hipLaunchKernelGGL(k_replay_pool_copy<true>, dim3((unsigned)((n_maps + 3) / 4)), dim3(256), 0, h->stream, n_maps, d.F,
+                           r->pool_pairs, (const uint32_t *)r->frame_off + (size_t)arena0 * d.F,
+                           (const uint32_t *)r->frame_cnt + (size_t)arena0 * d.F * 2, (const unsigned long long *)off,
+                           r->pool + (size_t)arena0 * r->pool_pairs, pairs);
+      e = hipGetLastError();
+    }
+  } else if (e == hipSuccess) {
     uint32_t *bits = r->frame_bits + (size_t)arena0 * d.F * 2 * d.words;
     e = hipMemsetAsync(bits, 0, sizeof(uint32_t) * (size_t)n_maps * d.words, h->stream);
     if (e == hipSuccess) {

@@ -86,6 +86,16 @@ def pack_actions(valid, shoot, thrust, px, py):
     return a
 
 
+def check_pool_pairs(what, packed, pool_pairs):
+    """The size argument of the packed frame store (replay_create's pool_pairs, DeviceTrainer's memory_pool_pairs): an
+    integer >= 0 and no bool, and 0 unless the packed store is asked for.  ValueError otherwise; returns it as int."""
+    if isinstance(pool_pairs, bool) or not isinstance(pool_pairs, (int, np.integer)) or pool_pairs < 0:
+        raise ValueError("%s must be an integer >= 0 (0 = the library's default), got %r" % (what, pool_pairs))
+    if pool_pairs and not packed:
+        raise ValueError("%s = %d sizes the packed frame store, which is off (packed / packed_memory)" % (what, pool_pairs))
+    return int(pool_pairs)
+
+
 class ArenaBatch:
     def __init__(self, n_arenas, n_ships=8, **cfg):
         self.cfg = nat.default_config(n_arenas=n_arenas, n_ships=n_ships, **cfg)
@@ -406,12 +416,34 @@ class ArenaBatch:
                                  ("iaction", np.int32), ("px", np.int32), ("py", np.int32), ("reward", np.int32),
                                  ("done", np.int32), ("head_prev", np.float32, 8), ("head_next", np.float32, 8)])
 
-    def replay_create(self, capacity=400, frames=0):
-        """Trainer.memory = deque(maxlen=memory_size) per arena (qlearnIA_V2.py:58)."""
-        nat.check(nat.lib().ofx_replay_create(self._h, int(capacity), int(frames)))
+    STORE_STATS = ("packed", "pool_pairs", "live_max", "live_sum", "evicted", "store_bytes")
+
+    def replay_create(self, capacity=400, frames=0, packed=False, pool_pairs=0):
+        """Trainer.memory = deque(maxlen=memory_size) per arena (qlearnIA_V2.py:58).
+
+        packed=True (opt-in, exact) keeps the stored observation maps as the (word index, word) pairs of their nonzero
+        words in a cyclic pool of `pool_pairs` pairs per arena instead of the dense frame ring - a tenth of its HBM at the
+        default pool_pairs = 0 (max(512 * frames, 4 * W*H/32)); any other value must be >= 4 * W*H/32 and < 2^31.  Every
+        reader returns the same bytes as from the dense ring; when an arena's live frames outgrow its pool the oldest are
+        released early and the rows that need them stop being eligible, exactly like rows whose frame was overwritten
+        (replay_store_stats()["evicted"] counts them).  include/ofx.h, "packed frame store", has the rule."""
+        pool_pairs = check_pool_pairs("replay_create: pool_pairs", packed, pool_pairs)
+        if packed:
+            nat.check(nat.lib().ofx_replay_create_packed(self._h, int(capacity), int(frames), pool_pairs))
+        else:
+            nat.check(nat.lib().ofx_replay_create(self._h, int(capacity), int(frames)))
         self.replay_capacity = int(capacity)
         self.replay_frames = int(frames) if frames else int(capacity) + int(capacity) // 4 + 2   # include/ofx.h
         self.replay_prioritized = False
+
+    def replay_store_stats(self):
+        """The frame store of the replay memory (ofx_replay_store_stats; synchronises): packed (1 / 0), pool_pairs per
+        arena, live_max / live_sum (pairs of the live frames: the fullest arena, all arenas), evicted (frames released
+        early since replay_create; per process, not carried by a checkpoint) and store_bytes (HBM held).  A dense memory
+        reports 0 for all but store_bytes."""
+        v = (C.c_int64 * 6)()
+        nat.check(nat.lib().ofx_replay_store_stats(self._h, v))
+        return dict(zip(self.STORE_STATS, (int(x) for x in v)))
 
     def replay_capture(self, tick, ship_mask_ptr=None, iaction_ptr=None, ipointer_ptr=None):
         """QlearnIA.play bookkeeping + Trainer.remember for this lock-step; call before step()."""

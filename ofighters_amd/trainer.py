@@ -35,6 +35,17 @@ min(1, c / (norm + 1e-6)) before Adam (torch.nn.utils.clip_grad_norm_).  With ei
 gradient's norm before clipping of every fit step, next to `losses` (which then holds the Huber losses).  Both work with
 `prioritized`, `n_step`, the target network and `double_dqn`, which only change targets and sampling.
 
+`packed_memory=True` (opt-in, exact) builds the replay memory with ArenaBatch.replay_create(packed=True): the stored
+observation maps are kept as the pairs of their nonzero words in a pool of `memory_pool_pairs` pairs per arena (0 = the
+library's default, about a tenth of the dense ring's HBM) instead of the dense frame ring, which is what lets a trainer
+exist at 32 768 arenas on one card.  Sampling, gathering, targets and the fit see the same bytes, so a run fits the same
+bits as with the dense ring as long as no arena's pool overflows (batch.replay_store_stats()["evicted"] == 0); a pool that
+is too small releases the oldest frames early and their rows stop being sampled.  memory_pool_pairs must be an integer
+>= 0 (no bool) and 0 without packed_memory: ValueError before anything is allocated.  Neither argument enters
+fingerprint() or a checkpoint's manifest: a checkpoint is form-agnostic (the blob carries frame_tick, early evictions
+included), a run restored under the same memory_pool_pairs continues bit for bit, and restoring into a pool that cannot
+hold the blob's frames is refused by the import.
+
 save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
 (`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
 cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
@@ -44,7 +55,7 @@ a fingerprint of the hyperparameters that must match.  TrainingRollout.checkpoin
 and its own counters (ofighters_amd/checkpoint.py); a run restored from it continues bit for bit."""
 import numpy as np
 
-from .engine import DeviceBuffer
+from .engine import DeviceBuffer, check_pool_pairs
 from .lib.epsilon import Epsilon_cos
 
 
@@ -72,7 +83,8 @@ class DeviceTrainer:
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
                  per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
-                 huber_delta=None, clip_norm=None):
+                 huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0):
+        memory_pool_pairs = check_pool_pairs("DeviceTrainer: memory_pool_pairs", packed_memory, memory_pool_pairs)
         if prioritized and reference_quirks:
             raise ValueError("DeviceTrainer: prioritized replay needs the textbook fit (reference_quirks=False)")
         if int(n_step) != n_step or n_step < 1:
@@ -128,7 +140,12 @@ class DeviceTrainer:
         self.losses = []
         self.grad_norms = []                                 # with huber_delta / clip_norm: every fit step's pre-clip norm
         self._buf = {}                                       # replay scratch kept between calls (grow-only)
-        batch.replay_create(memory_size, frames)
+        self.packed_memory = bool(packed_memory)             # the replay memory's frame store: packed pairs or dense ring
+        self.memory_pool_pairs = memory_pool_pairs           # pairs per arena of the packed store (0: the library's default)
+        if self.packed_memory:
+            batch.replay_create(memory_size, frames, packed=True, pool_pairs=memory_pool_pairs)
+        else:
+            batch.replay_create(memory_size, frames)
         if self.prioritized:
             batch.replay_prioritize(per_alpha, per_eps)
 
