@@ -471,6 +471,65 @@ int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, const int32
 /* Masses of one arena, oldest first (the order of ofx_replay_rows_host); mass_host holds `capacity` floats.        */
 int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *mass_host, int32_t *n_host);
 
+/* ---- global minibatch sampling (opt-in) ----------------------------------
+ * The samplers above draw `batch` rows in EVERY arena.  ofx_replay_sample_global draws n_rows rows from the union of all
+ * arenas' memories instead - uniform over rows, or proportional to priority ACROSS arenas - and writes them as a list of
+ * (arena, slot) pairs, which ofx_replay_gather_list materialises and ofx_replay_update_priorities_list writes back.
+ * Nothing of the per-arena calls changes.
+ *  - Eligibility is ofx_replay_sample's: the oldest skip[a] rows of arena a whose `state` frame has left the ring (dense
+ *    or packed store) are out, v[a] = count[a] - skip[a], R = sum of v.  slot keeps its meaning: the oldest-first index
+ *    into the arena's rows, expired rows included (slot = skip[a] + index among the eligible rows).
+ *  - n = min(n_rows, R) rows are drawn into arena[j] / slot[j] / is_weight[j], j < n; entries n .. n_rows - 1 receive
+ *    -1 / -1 / 0.  *n_drawn_host = n, *eligible_host = R (may be NULL): the call's one synchronisation.
+ *  - Draw j uses Philox counter (arena_base, j, draw, stream 5), key = seed, rr = its four words: two shards with
+ *    different arena_base draw different rows.
+ *  - Uniform (prioritized == 0; needs no ofx_replay_prioritize), without replacement: the eligible rows of all arenas
+ *    form one sequence in (arena, oldest-first) order; stratum j is the integer range [j * R / n, (j + 1) * R / n)
+ *    (64-bit integer arithmetic, floor); the row drawn is lo + ofx_draw_int(rr[0], hi - lo - 1) = lo + (rr[0] * (hi -
+ *    lo)) >> 32, mapped back to (arena, slot) through the exclusive scan of v.  The strata are disjoint: the output is
+ *    strictly ascending in (arena, slot), and n_rows >= R returns every eligible row exactly once.  A row is drawn
+ *    with probability 1 / (hi - lo) of its stratum: n / R exactly when n divides R, otherwise n / R up to the rounding of
+ *    the strata's bounds (a relative n / R at the most).  is_weight, when given, receives 1.
+ *  - Prioritized (prioritized != 0; OFX_ERR_STATE without ofx_replay_prioritize), stratified proportional with
+ *    replacement over all eligible rows.  Arena masses: the total T[a] and the inclusive prefix of a row inside its arena
+ *    are ofx_replay_sample_prioritized's (float64, 64 chunks of ceil(v / 64) rows summed in row order, chunk totals
+ *    chained in order).  Cross-arena prefix, a fixed order: groups of 256 consecutive arenas; s_a = the sequential float64
+ *    running sum of T inside the group in arena order (starting from 0.0 at the group's first arena); X_0 = 0,
+ *    X_{k+1} = X_k + s_last(k); arena a of group k has inclusive prefix G[a] = X_k + s_a and exclusive prefix E[a] =
+ *    G[a - 1] (0 for arena 0); total = G[N - 1].  G is monotone by construction.  Draw j: U = rr[0] * 2^-32,
+ *    u = ((double)j + U) / n * total; the arena is the first with G[a] > u (none: the last arena with an eligible row);
+ *    inside it u' = u - E[a] and the row is the first eligible row whose per-arena inclusive prefix is > u' (none: the
+ *    arena's last eligible row).  Draws come out non-decreasing in (arena, slot); duplicates are adjacent.
+ *  - IS weights: raw w = ((double)R * m / total)^(-beta) in float64 (total == 0: 1), rounded to float32, then divided
+ *    in float32 by the maximum over the n drawn rows.  They correct to UNIFORM OVER ROWS of the whole memory - the
+ *    distribution of the uniform mode above - not to the per-arena sampler's "equal rows per arena".
+ * Errors: OFX_ERR_STATE without a replay memory (or without PER when prioritized); OFX_ERR_INVALID for a NULL arena /
+ * slot / n_drawn_host, a NULL is_weight when prioritized, n_rows <= 0, a non-finite beta, or n_arenas * capacity >= 2^31.
+ * The [N]-sized workspace (skip, v, their scan, T, G) belongs to the handle: allocated at the first call, freed by
+ * ofx_replay_destroy / ofx_replay_create, not part of a checkpoint.                                                  */
+int ofx_replay_sample_global(ofx_handle *h, uint64_t seed, uint32_t draw, int32_t n_rows, int32_t prioritized, double beta,
+                             int32_t *arena, int32_t *slot, float *is_weight, int32_t *n_drawn_host,
+                             int64_t *eligible_host);
+/* Output d of the n listed rows is what ofx_replay_gather_valid (ret and disc NULL) or ofx_replay_gather_nstep (ret and
+ * disc given: the composite row of the n-step chain, ret[d], disc[d]) writes for the same (arena, slot): the row and
+ * both maps [n][2][W*H/32] in the trunk's layout (maps may be NULL).  One workgroup per listed row.  An entry whose
+ * arena is outside [0, N) or whose slot is outside [0, count[arena]) cannot be checked on the host (device pointers): it
+ * receives ofx_replay_gather's padding row (ship = -1, zero maps, ret = disc = 0) and nothing is read for it.
+ * OFX_ERR_INVALID for n <= 0, nstep outside 1 .. 64, gamma outside [0, 1] (NaN included), or nstep > 1 without ret and
+ * disc.  Does not synchronise.                                                                                      */
+int ofx_replay_gather_list(ofx_handle *h, const int32_t *arena, const int32_t *slot, int32_t n, int32_t nstep, float gamma,
+                           ofx_transition *rows, void *bits_prev, void *bits_next, float *ret, float *disc);
+/* Write-back for a gathered list: rows[n] as ofx_replay_gather_list wrote them, td[n][2] = (e1, e2).  Mass formula,
+ * finiteness test and staleness test are ofx_replay_update_priorities': entry j LANDS when its (arena, slot) names a row,
+ * that ring row still holds the gathered (tick_prev, ship) and both errors are finite.  Every entry that lands raises
+ * mmax[arena]; of a run of ADJACENT entries naming the same (arena, slot) the last one that lands sets the mass (a row
+ * drawn twice keeps the later entry's priority; the sampler's lists have their duplicates adjacent).  Precondition:
+ * duplicates that are not adjacent are not ordered - one of them sets the mass.  Then every arena's mmax is raised to
+ * the maximum over all arenas, so that a row captured next enters at the global maximum, as global competition needs
+ * (ofx_replay_capture itself is unchanged).  OFX_ERR_STATE without PER.  Does not synchronise.                        */
+int ofx_replay_update_priorities_list(ofx_handle *h, const int32_t *arena, const int32_t *slot, int32_t n,
+                                      const ofx_transition *rows, const float *td);
+
 /* ---- checkpoint: export / import of the replay memory --------------------
  * What a training run must carry across processes besides the weights (checkpoints).  A CHUNK is the
  * whole memory of local arenas [arena0, arena0 + n_arenas): the caller bounds host memory by choosing the chunk.  The

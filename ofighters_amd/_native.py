@@ -138,6 +138,10 @@ SIGNATURES = {
     "ofx_replay_window_weights": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "ofx_replay_update_priorities": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "ofx_replay_priorities_host": (_i, [_vp, C.c_int32, _vp, _vp]),
+    "ofx_replay_sample_global": (_i, [_vp, _u64, _u32, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ofx_replay_gather_list": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "ofx_replay_update_priorities_list": (_i, [_vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "ofx_replay_export_bytes": (_i, [_vp, C.c_int32, C.c_int32, C.POINTER(_sz)]),
     "ofx_replay_export": (_i, [_vp, C.c_int32, C.c_int32, _vp, _sz, C.POINTER(_sz)]),
     "ofx_replay_import": (_i, [_vp, C.c_int32, C.c_int32, _vp, _sz]),

@@ -49,6 +49,11 @@ struct ofx_replay {
   uint32_t *pool_head;     // [N]
   uint32_t *live;          // [N] pairs of all live frames
   long long *evicted;      // [N] frames released early, since create
+  // workspace of the global sampler (ofx_replay_sample_global), allocated at its first call; not part of a checkpoint
+  int32_t *g_skip, *g_v;   // [N] expired oldest rows / eligible rows
+  long long *g_voff;       // [N + 1] exclusive scan of g_v, R in [N]
+  double *g_T, *g_G;       // [N] arena mass totals / their inclusive cross-arena prefix
+  double *g_gs;            // [ceil(N / 256)] the groups' last running sums
 };
 
 void ofx_replay_free(ofx_handle *h) {
@@ -57,7 +62,7 @@ void ofx_replay_free(ofx_handle *h) {
   void *ptrs[] = {r->frame_bits, r->frame_tick, r->rows, r->head, r->count, r->appended, r->has_prev, r->latched,
                   r->prev_iaction, r->prev_px, r->prev_py, r->prev_tick, r->prev_head, r->frame_head, r->cur_slot,
                   r->prev_slot, r->scan_off, r->mass, r->mmax, r->pool, r->frame_off, r->frame_cnt, r->pool_head, r->live,
-                  r->evicted};
+                  r->evicted, r->g_skip, r->g_v, r->g_voff, r->g_T, r->g_G, r->g_gs};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   delete r;
   h->replay = nullptr;
@@ -1065,6 +1070,393 @@ extern "C" int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *m
   if (n1 > 0) OFX_HIP(hipMemcpy(mass_host, base + first, sizeof(float) * n1, hipMemcpyDeviceToHost));
   if (count > n1) OFX_HIP(hipMemcpy(mass_host + n1, base, sizeof(float) * (count - n1), hipMemcpyDeviceToHost));
   *n_host = count;
+  return OFX_OK;
+}
+
+// ---- global minibatch sampling: n rows from the union of all arenas' memories (include/ofx.h states the contract) -----
+// Per-arena pass (skip, v, T) -> integer scan of v -> float64 group scan of T (PER) -> one wave per draw -> the weights
+// over their maximum.  The list gather and the list write-back take the (arena, slot) pairs the sampler wrote.
+#define OFX_STREAM_GLOBAL 5u
+#define OFX_GLOBAL_GROUP 256
+
+// lane L of the wave sums chunk L of the arena's `valid` eligible rows; every lane runs the same chain over the 64 chunk
+// totals (the summation order of k_replay_sample_per).  Returns the total, *incl = the lane's inclusive chunk prefix.
+__device__ __forceinline__ double arena_chunk_chain(const float *mass, int C, int base, int valid, int lane, double *incl) {
+  const int cs = (valid + 63) / 64;
+  const int lo = min(lane * cs, valid), hi = min(lo + cs, valid);
+  double t = 0.0;
+  for (int i = lo; i < hi; i++) t += (double)mass[(base + i) % C];
+  double total = 0.0, in = 0.0;
+  for (int k = 0; k < 64; k++) {
+    total += __shfl(t, k);
+    if (k == lane) in = total;
+  }
+  *incl = in;
+  return total;
+}
+
+// One wave per arena.  The expiry walk of k_replay_sample, 64 rows per ballot: the first row whose `state` frame is
+// still in the ring ends it.  PER: T[a] by the chunk scheme.
+template <bool PER>
+__global__ __launch_bounds__(256) void k_global_arena(int N, int C, int F, ofx_replay r) {
+  const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (a >= N) return;  // wave-uniform
+  const int count = r.count[a], head = r.head[a];
+  const int first = ((head - count) % C + C) % C;
+  const ofx_transition *rows = r.rows + (size_t)a * C;
+  int skip = count;
+  for (int base = 0; base < count; base += 64) {  // wave-uniform trip count
+    const int i = base + lane;
+    bool live = false;
+    if (i < count) {
+      const ofx_transition &o = rows[(first + i) % C];
+      const int f = o.frame_prev;
+      live = (unsigned)f < (unsigned)F && r.frame_tick[(size_t)a * F + f] == o.tick_prev;
+    }
+    const unsigned long long hit = __ballot(live);
+    if (hit) { skip = base + __ffsll((long long)hit) - 1; break; }
+  }
+  const int valid = count - skip;
+  if constexpr (PER) {
+    double incl;
+    const double total = arena_chunk_chain(r.mass + (size_t)a * C, C, first + skip, valid, lane, &incl);
+    if (lane == 0) r.g_T[a] = total;
+  }
+  if (lane == 0) { r.g_skip[a] = skip; r.g_v[a] = valid; }
+}
+
+// one workgroup per group of 256 consecutive arenas: s = the sequential running sum of T in arena order
+__global__ __launch_bounds__(OFX_GLOBAL_GROUP) void k_global_group_sum(int N, ofx_replay r) {
+  __shared__ double s[OFX_GLOBAL_GROUP];
+  const int a0 = blockIdx.x * OFX_GLOBAL_GROUP, a = a0 + threadIdx.x, cnt = min(OFX_GLOBAL_GROUP, N - a0);
+  s[threadIdx.x] = a < N ? r.g_T[a] : 0.0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double run = 0.0;
+    for (int i = 0; i < cnt; i++) { run += s[i]; s[i] = run; }
+    r.g_gs[blockIdx.x] = run;
+  }
+  __syncthreads();
+  if (a < N) r.g_G[a] = s[threadIdx.x];
+}
+
+// G[a] = X_k + s_a with X_k the chain of the group totals before group k
+__global__ __launch_bounds__(256) void k_global_group_chain(int N, ofx_replay r) {
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= N) return;
+  const int k = a / OFX_GLOBAL_GROUP;
+  double X = 0.0;
+  for (int i = 0; i < k; i++) X += r.g_gs[i];
+  r.g_G[a] = X + r.g_G[a];
+}
+
+struct GlobalDrawParams {
+  int N, C, n_rows, arena_base;
+  uint32_t k0, k1, draw;
+  double beta;
+  ofx_replay r;
+  int32_t *arena, *slot;
+  float *is_weight;
+};
+
+// the arena that holds eligible row idx of the (arena, oldest-first) sequence: the last a with voff[a] <= idx
+__device__ __forceinline__ int global_arena_of(const long long *voff, int N, long long idx) {
+  int lo = 0, hi = N - 1;  // voff[0] = 0 <= idx
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (voff[mid] <= idx) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// One wave per draw j; every lane runs the searches on the same values, the lanes share the in-arena chunk sums.
+template <bool PER>
+__global__ __launch_bounds__(256) void k_global_draw(GlobalDrawParams p) {
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (j >= p.n_rows) return;  // wave-uniform
+  const long long R = p.r.g_voff[p.N];
+  const long long n = R < (long long)p.n_rows ? R : (long long)p.n_rows;
+  if (j >= n) {  // wave-uniform: padding
+    if (lane == 0) {
+      p.arena[j] = -1;
+      p.slot[j] = -1;
+      if (p.is_weight) p.is_weight[j] = 0.f;
+    }
+    return;
+  }
+  uint32_t rr[4];
+  ofx_philox4x32_10((uint32_t)p.arena_base, (uint32_t)j, p.draw, OFX_STREAM_GLOBAL, p.k0, p.k1, rr);
+  if constexpr (!PER) {
+    const long long lo = (long long)j * R / n, hi = ((long long)j + 1) * R / n;
+    const long long idx = lo + ofx_draw_int(rr[0], (int32_t)(hi - lo - 1));
+    const int a = global_arena_of(p.r.g_voff, p.N, idx);
+    if (lane == 0) {
+      p.arena[j] = a;
+      p.slot[j] = p.r.g_skip[a] + (int)(idx - p.r.g_voff[a]);
+      if (p.is_weight) p.is_weight[j] = 1.f;
+    }
+  } else {
+    const double total = p.r.g_G[p.N - 1];
+    const double U = (double)rr[0] * 0x1p-32;
+    const double u = ((double)j + U) / (double)n * total;
+    int lo = 0, hi = p.N;  // the first arena with G > u lies in [lo, hi]; hi == N: none
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (p.r.g_G[mid] > u) hi = mid;
+      else lo = mid + 1;
+    }
+    const int a = lo < p.N ? lo : global_arena_of(p.r.g_voff, p.N, R - 1);
+    const double up = u - (a ? p.r.g_G[a - 1] : 0.0);
+    const int C = p.C, count = p.r.count[a], head = p.r.head[a], skip = p.r.g_skip[a], valid = p.r.g_v[a];
+    const int base = ((head - count) % C + C) % C + skip;
+    const float *mass = p.r.mass + (size_t)a * C;
+    int pick = valid - 1;  // rounding left no row above u': the arena's last eligible row
+    if (valid > 0) {       // wave-uniform (an arena with G > G[a - 1] has rows; the fallback arena has one too)
+      double incl;
+      arena_chunk_chain(mass, C, base, valid, lane, &incl);
+      const int cs = (valid + 63) / 64, nchunks = (valid + cs - 1) / cs;
+      const unsigned long long hit = __ballot(lane < nchunks && incl > up);
+      if (hit) {
+        const int k = __ffsll((long long)hit) - 1;
+        double ex = __shfl(incl, max(k - 1, 0));
+        if (k == 0) ex = 0.0;
+        const int r0 = k * cs, r1 = min(r0 + cs, valid);
+        double run = 0.0;
+        pick = r1 - 1;
+        for (int i = r0; i < r1; i++) {
+          run += (double)mass[(base + i) % C];
+          if (ex + run > up) { pick = i; break; }
+        }
+      }
+    }
+    if (lane == 0) {
+      const double m = valid > 0 ? (double)mass[(base + pick) % C] : 0.0;
+      p.arena[j] = a;
+      p.slot[j] = skip + pick;
+      p.is_weight[j] = total > 0.0 ? (float)pow((double)R * m / total, -p.beta) : 1.f;
+    }
+  }
+}
+
+// the n = min(n_rows, R) raw weights over their maximum (the max is exact in any order)
+__global__ __launch_bounds__(1024) void k_global_norm(int N, int n_rows, const long long *voff, float *w) {
+  __shared__ float red[1024];
+  const int tid = threadIdx.x, n = (int)(voff[N] < (long long)n_rows ? voff[N] : (long long)n_rows);
+  float m = 0.f;
+  for (int d = tid; d < n; d += 1024) m = fmaxf(m, w[d]);
+  red[tid] = m;
+  __syncthreads();
+  for (int k = 512; k > 0; k >>= 1) {
+    if (tid < k) red[tid] = fmaxf(red[tid], red[tid + k]);
+    __syncthreads();
+  }
+  const float mx = red[0];
+  if (mx > 0.f)
+    for (int d = tid; d < n; d += 1024) w[d] = w[d] / mx;
+}
+
+static int global_workspace(ofx_handle *h) {
+  ofx_replay *r = h->replay;
+  if (r->g_skip) return OFX_OK;
+  const size_t N = h->cfg.n_arenas, groups = (N + OFX_GLOBAL_GROUP - 1) / OFX_GLOBAL_GROUP;
+  OFX_HIP(hipMalloc((void **)&r->g_skip, sizeof(int32_t) * N));
+  OFX_HIP(hipMalloc((void **)&r->g_v, sizeof(int32_t) * N));
+  OFX_HIP(hipMalloc((void **)&r->g_voff, sizeof(long long) * (N + 1)));
+  OFX_HIP(hipMalloc((void **)&r->g_T, sizeof(double) * N));
+  OFX_HIP(hipMalloc((void **)&r->g_G, sizeof(double) * N));
+  OFX_HIP(hipMalloc((void **)&r->g_gs, sizeof(double) * groups));
+  return OFX_OK;
+}
+
+extern "C" int ofx_replay_sample_global(ofx_handle *h, uint64_t seed, uint32_t draw, int32_t n_rows, int32_t prioritized,
+                                        double beta, int32_t *arena, int32_t *slot, float *is_weight,
+                                        int32_t *n_drawn_host, int64_t *eligible_host) {
+  if (!h || !h->replay) { ofx_set_error("ofx_replay_sample_global: no replay memory"); return OFX_ERR_STATE; }
+  int rc;
+  if (prioritized && (rc = per_ready(h, "ofx_replay_sample_global"))) return rc;
+  if (!arena || !slot || !n_drawn_host || n_rows <= 0 || (prioritized && !is_weight) ||
+      !(beta >= -DBL_MAX && beta <= DBL_MAX)) {
+    ofx_set_error("ofx_replay_sample_global: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  ofx_replay *r = h->replay;
+  const int N = h->cfg.n_arenas;
+  if ((long long)N * r->capacity > 0x7fffffffLL) {
+    ofx_set_error("ofx_replay_sample_global: n_arenas * capacity must be < 2^31");
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if ((rc = global_workspace(h))) return rc;
+  const dim3 waves((unsigned)((N + 3) / 4));
+  if (prioritized)
+    hipLaunchKernelGGL(k_global_arena<true>, waves, dim3(256), 0, h->stream, N, r->capacity, r->frames, *r);
+  else
+    hipLaunchKernelGGL(k_global_arena<false>, waves, dim3(256), 0, h->stream, N, r->capacity, r->frames, *r);
+  hipLaunchKernelGGL((k_replay_scan<int32_t, long long>), dim3(1), dim3(1024), 0, h->stream, N, (const int32_t *)r->g_v,
+                     r->g_voff);
+  GlobalDrawParams p;
+  p.N = N; p.C = r->capacity; p.n_rows = n_rows; p.arena_base = h->cfg.arena_base;
+  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.draw = draw; p.beta = beta;
+  p.r = *r; p.arena = arena; p.slot = slot; p.is_weight = is_weight;
+  const dim3 draws((unsigned)((n_rows + 3) / 4));
+  if (prioritized) {
+    hipLaunchKernelGGL(k_global_group_sum, dim3((unsigned)((N + OFX_GLOBAL_GROUP - 1) / OFX_GLOBAL_GROUP)),
+                       dim3(OFX_GLOBAL_GROUP), 0, h->stream, N, *r);
+    hipLaunchKernelGGL(k_global_group_chain, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, N, *r);
+    hipLaunchKernelGGL(k_global_draw<true>, draws, dim3(256), 0, h->stream, p);
+    hipLaunchKernelGGL(k_global_norm, dim3(1), dim3(1024), 0, h->stream, N, n_rows, (const long long *)r->g_voff, is_weight);
+  } else {
+    hipLaunchKernelGGL(k_global_draw<false>, draws, dim3(256), 0, h->stream, p);
+  }
+  hipError_t e = hipGetLastError();
+  long long R = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&R, r->g_voff + N, sizeof(R), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { ofx_set_error("ofx_replay_sample_global: %s", hipGetErrorString(e)); return OFX_ERR_HIP; }
+  *n_drawn_host = (int32_t)(R < (long long)n_rows ? R : (long long)n_rows);
+  if (eligible_host) *eligible_host = (int64_t)R;
+  return OFX_OK;
+}
+
+struct GatherListParams {
+  int N, C, F, words, n;
+  ofx_replay r;
+  const int32_t *arena, *slot;
+  ofx_transition *rows;             // [n]
+  uint32_t *bits_prev, *bits_next;  // [n][2][words] or null
+};
+
+// one workgroup per listed row d: what k_replay_gather_valid writes for the same (arena, slot); an entry that names no
+// row gets k_replay_gather's padding row and empty maps
+template <bool NSTEP, bool PACKED>
+__global__ __launch_bounds__(256) void k_replay_gather_list(GatherListParams p, NstepParams q) {
+  const int d = blockIdx.x;
+  const int a = p.arena[d], s = p.slot[d];
+  ofx_transition *dst = p.rows + d;
+  uint32_t *outs[2] = {p.bits_prev, p.bits_next};
+  const int count = (a >= 0 && a < p.N) ? p.r.count[a] : 0;
+  if (s < 0 || s >= count) {  // block-uniform
+    if (threadIdx.x < sizeof(ofx_transition) / 4) ((int32_t *)dst)[threadIdx.x] = threadIdx.x == 4 ? -1 : 0;
+    for (int w = 0; w < 2; w++) {
+      if (!outs[w]) continue;
+      uint4 *out = reinterpret_cast<uint4 *>(outs[w] + (size_t)d * 2 * p.words);
+      for (int k = threadIdx.x; k < 2 * p.words / 4; k += 256) out[k] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (NSTEP && threadIdx.x == 0) { q.ret[d] = 0.f; q.disc[d] = 0.f; }
+    return;
+  }
+  const int head = p.r.head[a];
+  const int first_row = ((head - count) % p.C + p.C) % p.C;
+  const ofx_transition *ring = p.r.rows + (size_t)a * p.C;
+  const ofx_transition *src = ring + (first_row + s) % p.C;
+  const ofx_transition *end = src;  // the row whose next state is gathered
+  if constexpr (NSTEP) {
+    __shared__ int end_s;
+    if (threadIdx.x < 64) {
+      const int e = nstep_chain(ring, p.C, first_row, count, s, threadIdx.x, d, q);
+      if (threadIdx.x == 0) end_s = e;
+    }
+    __syncthreads();
+    end = ring + (first_row + end_s) % p.C;
+  }
+  if (threadIdx.x < sizeof(ofx_transition) / 4) {
+    const int w = threadIdx.x;  // tick_next, frame_next, done and head_next come from the chain's last row
+    const bool from_end = w == 1 || w == 3 || w == 9 || w >= (int)(offsetof(ofx_transition, head_next) / 4);
+    ((int32_t *)dst)[w] = ((const int32_t *)(from_end ? end : src))[w];
+  }
+  const int slots[2] = {src->frame_prev, end->frame_next};
+  for (int w = 0; w < 2; w++) {
+    if (!outs[w]) continue;  // block-uniform
+    frame_read<PACKED>(p.r, a, p.F, p.words, slots[w], outs[w] + (size_t)d * 2 * p.words);
+  }
+}
+
+extern "C" int ofx_replay_gather_list(ofx_handle *h, const int32_t *arena, const int32_t *slot, int32_t n, int32_t nstep,
+                                      float gamma, ofx_transition *rows, void *bits_prev, void *bits_next, float *ret,
+                                      float *disc) {
+  if (!h || !h->replay || !arena || !slot || !rows || n <= 0) { ofx_set_error("ofx_replay_gather_list: bad argument"); return OFX_ERR_INVALID; }
+  if (nstep < 1 || nstep > 64 || !(gamma >= 0.f && gamma <= 1.f) || (nstep > 1 && (!ret || !disc))) {  // (NaN fails the gamma test)
+    ofx_set_error("ofx_replay_gather_list: nstep in 1..64, gamma in [0, 1] and, with nstep > 1, ret and disc must be given, got %d, %g",
+                  nstep, (double)gamma);
+    return OFX_ERR_INVALID;
+  }
+  ofx_replay *r = h->replay;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  GatherListParams p;
+  p.N = h->cfg.n_arenas; p.C = r->capacity; p.F = r->frames; p.words = r->words; p.n = n;
+  p.r = *r; p.arena = arena; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
+  const bool chain = ret && disc;  // nstep == 1 with both given: ret = reward, disc = gamma * (not done), as the window form
+  const NstepParams q{nstep, (double)gamma, ret, disc};
+  const dim3 grid((unsigned)n);
+  const size_t lds = (size_t)r->words * 8;  // packed: the two maps of a frame
+  if (chain && r->packed) hipLaunchKernelGGL((k_replay_gather_list<true, true>), grid, dim3(256), lds, h->stream, p, q);
+  else if (chain) hipLaunchKernelGGL((k_replay_gather_list<true, false>), grid, dim3(256), 0, h->stream, p, q);
+  else if (r->packed) hipLaunchKernelGGL((k_replay_gather_list<false, true>), grid, dim3(256), lds, h->stream, p, NstepParams{});
+  else hipLaunchKernelGGL((k_replay_gather_list<false, false>), grid, dim3(256), 0, h->stream, p, NstepParams{});
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// entry j may write: in range, the ring row still holds the gathered (tick_prev, ship), both errors finite
+__device__ __forceinline__ bool list_entry_lands(const ofx_replay &r, int N, int C, int a, int s, const ofx_transition &g,
+                                                 const float *td, int j, size_t *pos_out) {
+  if (a < 0 || a >= N) return false;
+  const int count = r.count[a], head = r.head[a];
+  if (s < 0 || s >= count) return false;
+  const size_t pos = (size_t)a * C + (((head - count) % C + C) % C + s) % C;
+  if (r.rows[pos].tick_prev != g.tick_prev || r.rows[pos].ship != g.ship) return false;  // overwritten since sampling
+  if (!isfinite(td[2 * (size_t)j]) || !isfinite(td[2 * (size_t)j + 1])) return false;
+  *pos_out = pos;
+  return true;
+}
+
+// One thread per entry.  Every entry that lands raises mmax; of a run of adjacent entries naming one (arena, slot) the
+// last one that lands writes the mass (k_replay_update_per's serial walk, without the walk).
+__global__ __launch_bounds__(256) void k_replay_update_list(int N, int C, int n, const int32_t *arena, const int32_t *slot,
+                                                            const ofx_transition *rows, const float *td, ofx_replay r) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int a = arena[j], s = slot[j];
+  size_t pos;
+  if (!list_entry_lands(r, N, C, a, s, rows[j], td, j, &pos)) return;
+  const float m = powf(fabsf(td[2 * (size_t)j]) + fabsf(td[2 * (size_t)j + 1]) + r.eps, r.alpha);
+  atomicMax(reinterpret_cast<unsigned int *>(r.mmax + a), __float_as_uint(m));  // masses are >= 0: the bit patterns order like the values
+  for (int k = j + 1; k < n && arena[k] == a && slot[k] == s; k++) {
+    size_t other;
+    if (list_entry_lands(r, N, C, a, s, rows[k], td, k, &other)) return;  // a later entry of the run wins
+  }
+  r.mass[pos] = m;
+}
+
+// every arena's mmax <- the maximum over the arenas: under global competition a new row enters at the global maximum
+__global__ __launch_bounds__(1024) void k_replay_level_mmax(int N, float *mmax) {
+  __shared__ float red[1024];
+  const int tid = threadIdx.x;
+  float m = 0.f;
+  for (int a = tid; a < N; a += 1024) m = fmaxf(m, mmax[a]);
+  red[tid] = m;
+  __syncthreads();
+  for (int k = 512; k > 0; k >>= 1) {
+    if (tid < k) red[tid] = fmaxf(red[tid], red[tid + k]);
+    __syncthreads();
+  }
+  const float mx = red[0];
+  for (int a = tid; a < N; a += 1024) mmax[a] = mx;
+}
+
+extern "C" int ofx_replay_update_priorities_list(ofx_handle *h, const int32_t *arena, const int32_t *slot, int32_t n,
+                                                 const ofx_transition *rows, const float *td) {
+  int rc;
+  if ((rc = per_ready(h, "ofx_replay_update_priorities_list"))) return rc;
+  if (!arena || !slot || !rows || !td || n < 0) { ofx_set_error("ofx_replay_update_priorities_list: bad argument"); return OFX_ERR_INVALID; }
+  if (n == 0) return OFX_OK;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const int N = h->cfg.n_arenas;
+  hipLaunchKernelGGL(k_replay_update_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, N, h->replay->capacity,
+                     n, arena, slot, rows, td, *h->replay);
+  hipLaunchKernelGGL(k_replay_level_mmax, dim3(1), dim3(1024), 0, h->stream, N, h->replay->mmax);
+  OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
 

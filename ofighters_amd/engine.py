@@ -564,6 +564,40 @@ class ArenaBatch:
         nat.check(nat.lib().ofx_replay_priorities_host(self._h, int(arena), m.ctypes.data_as(C.c_void_p), C.byref(n)))
         return m[:n.value]
 
+    # ------------------------------------------------------------ global minibatch sampling (include/ofx.h: the contract)
+    def replay_sample_global(self, seed, draw, n_rows, prioritized=False, beta=0.0, arena=None, slot=None, is_weight=None):
+        """n_rows rows from the union of all arenas' memories: uniform over rows without replacement, or (prioritized)
+        stratified proportional to the masses across arenas -> (arena [n_rows], slot [n_rows], is_weight [n_rows] or
+        None, n_drawn, eligible).  The first three are DeviceBuffers (the caller may hand them in), sorted by (arena,
+        slot) with -1 / -1 / 0 after the n_drawn = min(n_rows, eligible) rows drawn; is_weight holds the IS weights
+        over their maximum (uniform: 1.0 when a buffer is given, None otherwise).  Synchronises (two host integers)."""
+        n_rows = int(n_rows)
+        if arena is None:
+            arena = DeviceBuffer(4 * n_rows)
+        if slot is None:
+            slot = DeviceBuffer(4 * n_rows)
+        if is_weight is None and prioritized:
+            is_weight = DeviceBuffer(4 * n_rows)
+        n, elig = C.c_int32(0), C.c_int64(0)
+        nat.check(nat.lib().ofx_replay_sample_global(self._h, seed, int(draw), n_rows, 1 if prioritized else 0, float(beta),
+                                                      arena.ptr, slot.ptr, is_weight.ptr if is_weight is not None else None,
+                                                      C.byref(n), C.byref(elig)))
+        return arena, slot, is_weight, n.value, elig.value
+
+    def replay_gather_list_into(self, arena, slot, n, rows, bits_prev, bits_next, nstep=1, gamma=0.0, ret=None, disc=None):
+        """The n listed (arena, slot) rows into the caller's DeviceBuffers, one workgroup per row: what
+        replay_gather_valid_into writes for them, or with ret / disc (float32 [n] DeviceBuffers) the n-step composites
+        of replay_gather_nstep_into.  An entry that names no row becomes a padding row (ship = -1, zero maps).  Does not
+        synchronise."""
+        nat.check(nat.lib().ofx_replay_gather_list(self._h, arena.ptr, slot.ptr, int(n), int(nstep), float(gamma), rows.ptr,
+                                                    bits_prev.ptr if bits_prev else None, bits_next.ptr if bits_next else None,
+                                                    ret.ptr if ret else None, disc.ptr if disc else None))
+
+    def replay_update_priorities_list(self, arena, slot, n, rows_ptr, td_ptr):
+        """Priority write-back for the n rows of a gathered list from td [n][2] = (e1, e2); afterwards every arena's
+        running maximum is the maximum over all arenas."""
+        nat.check(nat.lib().ofx_replay_update_priorities_list(self._h, arena.ptr, slot.ptr, int(n), rows_ptr, td_ptr))
+
     # ------------------------------------------------------------ checkpoint (include/ofx.h: the blob's layout)
     def replay_export_bytes(self, arena0, n):
         """The exact size of the blob replay_export(arena0, n) returns (runs the device's count pass)."""

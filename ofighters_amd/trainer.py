@@ -46,6 +46,17 @@ fingerprint() or a checkpoint's manifest: a checkpoint is form-agnostic (the blo
 included), a run restored under the same memory_pool_pairs continues bit for bit, and restoring into a pool that cannot
 hold the blob's frames is refused by the import.
 
+`global_sampling=True` (opt-in, not in the reference) draws ONE minibatch of `fit_batch` rows per replay from the union of
+all arenas' memories instead of `batch_size` rows in every arena of which a moving window of fit_batch is fitted:
+ofx_replay_sample_global picks the rows uniformly over rows or, with `prioritized`, proportionally to their priorities
+across arenas (the IS weights then correct to uniform over rows and arrive max-normalised), ofx_replay_gather_list
+materialises exactly those rows and ofx_replay_update_priorities_list writes the TD errors back and levels every arena's
+running maximum to the global one.  replay() then costs no [N]-sized download and fits min(fit_batch, eligible rows);
+`batch_size` is unused.  Works with `prioritized`, `n_step`, the target network, `double_dqn`, `huber_delta`, `clip_norm`
+and `packed_memory`; refused with reference_quirks (ValueError); the value must be a bool.  fingerprint() carries
+"global_sampling": True only when it is on, so a state taken under one sampler is refused under the other, and `draws`
+keys the sampler's Philox stream as before: a checkpoint needs nothing new.
+
 save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
 (`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
 cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
@@ -80,11 +91,18 @@ def fingerprint_diff(have, want):
 
 
 class DeviceTrainer:
+    global_sampling = False                                  # the opt-in of __init__; off on any trainer that never set it
+
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
                  per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
-                 huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0):
+                 huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0, global_sampling=False):
         memory_pool_pairs = check_pool_pairs("DeviceTrainer: memory_pool_pairs", packed_memory, memory_pool_pairs)
+        if not isinstance(global_sampling, (bool, np.bool_)):
+            raise ValueError("DeviceTrainer: global_sampling must be a bool, got %r" % (global_sampling,))
+        if global_sampling and reference_quirks:
+            raise ValueError("DeviceTrainer: global sampling needs the textbook fit (reference_quirks=False is the "
+                             "reference's replay over its own memory as written)")
         if prioritized and reference_quirks:
             raise ValueError("DeviceTrainer: prioritized replay needs the textbook fit (reference_quirks=False)")
         if int(n_step) != n_step or n_step < 1:
@@ -142,6 +160,7 @@ class DeviceTrainer:
         self._buf = {}                                       # replay scratch kept between calls (grow-only)
         self.packed_memory = bool(packed_memory)             # the replay memory's frame store: packed pairs or dense ring
         self.memory_pool_pairs = memory_pool_pairs           # pairs per arena of the packed store (0: the library's default)
+        self.global_sampling = bool(global_sampling)         # one minibatch of fit_batch rows from all arenas' memories
         if self.packed_memory:
             batch.replay_create(memory_size, frames, packed=True, pool_pairs=memory_pool_pairs)
         else:
@@ -190,14 +209,17 @@ class DeviceTrainer:
     def fingerprint(self):
         """The hyperparameters a state must have been taken under to be loaded here."""
         b = self.batch
-        return {"n_floats": int(self.n_floats), "learning_rate": float(self.learning_rate), "gamma": float(self.gamma),
-                "batch_size": int(self.batch_size), "fit_batch": int(self.fit_batch), "seed": int(self.seed),
+        fp = {"n_floats": int(self.n_floats), "learning_rate": float(self.learning_rate), "gamma": float(self.gamma),
+              "batch_size": int(self.batch_size), "fit_batch": int(self.fit_batch), "seed": int(self.seed),
                 "reference_quirks": self.reference_quirks, "prioritized": self.prioritized,
                 "per_alpha": float(self.per_alpha), "per_beta": float(self.per_beta),
                 "per_beta_steps": int(self.per_beta_steps), "per_eps": float(self.per_eps), "n_step": self.n_step,
                 "target_sync": self.target_sync, "target_tau": self.target_tau, "double_dqn": self.double_dqn,
                 "huber_delta": self.huber_delta, "clip_norm": self.clip_norm,
                 "memory_capacity": int(b.replay_capacity), "memory_frames": int(b.replay_frames)}
+        if self.global_sampling:                             # only when on: a default trainer's key set stays as it was,
+            fp["global_sampling"] = True                     # and fingerprint_diff counts the missing key as a difference
+        return fp
 
     def state_dict(self):
         """Everything of the trainer that a resumed run needs (host copies; the replay memory belongs to the batch)."""
@@ -242,6 +264,8 @@ class DeviceTrainer:
         """One Trainer.replay: a minibatch of min(batch_size, len(memory)) rows per arena, targets, one fit step.
         Returns (mse(output1), mse(output2)) or None while every memory is still empty."""
         b = self.batch
+        if self.global_sampling:
+            return self._replay_global()
         bs = int(batch_size or self.batch_size)
         cnt, _ = b.replay_count()
         if int(cnt.max()) == 0:
@@ -281,6 +305,46 @@ class DeviceTrainer:
         else:
             loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
                              y_act.ptr, y_ptr.ptr)
+        self._move_target()
+        self.losses.append(loss)
+        return loss
+
+    def _replay_global(self):
+        """replay() under global_sampling: fit_batch rows drawn from the union of all arenas' memories (uniform over
+        rows, or by priority across arenas), the list gather, the same targets and fit calls, the list write-back.  The
+        sampler's two host integers are the only synchronisation before the fit."""
+        b = self.batch
+        nb = int(self.fit_batch)
+        per = self.prioritized
+        arena, slot, row_w, n, _ = b.replay_sample_global(self.seed, self.draws, nb, per, self.beta() if per else 0.0,
+                                                          self._scratch("g_arena", 4 * nb), self._scratch("g_slot", 4 * nb),
+                                                          self._scratch("row_w", 4 * nb) if per else None)
+        self.draws += 1
+        if n == 0:
+            return None
+        words = b.W * b.H // 32
+        rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
+        bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
+        if self.n_step == 1:
+            b.replay_gather_list_into(arena, slot, n, rows, bits_prev, bits_next)
+        else:
+            b.replay_gather_list_into(arena, slot, n, rows, bits_prev, bits_next, self.n_step, self.gamma,
+                                      self._scratch("ret", 4 * n), self._scratch("disc", 4 * n))
+        rows_p, prev_p = rows.ptr, bits_prev.ptr
+        y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
+        self._targets(n, rows_p, prev_p, bits_next.ptr, y_act, y_ptr)
+        self.fit_steps += 1
+        td = self._scratch("td", 8 * n) if per else None
+        if self._robust():
+            loss = self._fit_robust(n, rows_p, prev_p, y_act, y_ptr, row_w.ptr if per else None, td.ptr if per else None)
+        elif per:
+            loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p,
+                                      prev_p, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
+        else:
+            loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
+                             y_act.ptr, y_ptr.ptr)
+        if per:
+            b.replay_update_priorities_list(arena, slot, n, rows_p, td.ptr)
         self._move_target()
         self.losses.append(loss)
         return loss
