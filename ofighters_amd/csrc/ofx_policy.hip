@@ -601,7 +601,7 @@ extern "C" int ofx_set_option(ofx_handle *h, int32_t option, int32_t value) {
         OFX_HIP(hipMalloc((void **)&h->trunk_stat, 4 * sizeof(unsigned long long)));
         OFX_HIP(hipMemsetAsync(h->trunk_stat, 0, 4 * sizeof(unsigned long long), h->stream));
       }
-      h->opt_trunk_sparse = value != 0; return OFX_OK;
+      h->opt_trunk_dense = value == 0; h->opt_trunk_count = value != 0; return OFX_OK;
     case OFX_OPT_FIT_PLAIN: h->opt_fit_plain = value != 0; return OFX_OK;
     case OFX_OPT_POLICY_BF16:
       if (value < 0 || value > 2) { ofx_set_error("ofx_set_option: OFX_OPT_POLICY_BF16 takes 0 (fp32), 1 (bf16 operands), 2 (fp16 operands)"); return OFX_ERR_INVALID; }
@@ -654,8 +654,10 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   for (int i = 0; i < 3; i++) tp.wbm[i] = prep + L.wbm[i];
   tp.lut1 = prep + L.lut1; tp.zero16 = prep + L.zero16;
   tp.p1 = ws.p1; tp.p2 = ws.p2; tp.p3 = ws.p3; tp.p4 = ws.p4;
-  tp.lowp = lowp; tp.sparse = h->opt_trunk_sparse || a.vec8 != nullptr;   // exact either way: the forwards on stored observations (DQN targets) always take it
-  tp.stat = h->opt_trunk_sparse ? h->trunk_stat : nullptr;
+  // the sparse kernel is exact, so it is the default; OFX_OPT_TRUNK_SPARSE = 0 asks for the dense one (live forward only:
+  // the forwards on stored observations, i.e. the DQN targets, always take the sparse one), = 1 for the counters
+  tp.lowp = lowp; tp.sparse = !h->opt_trunk_dense || a.vec8 != nullptr;
+  tp.stat = h->opt_trunk_count ? h->trunk_stat : nullptr;
   if ((rc = ofx_launch_trunk(h, tp))) return rc;
 
   // 2. dense1: trunk features on MFMA once per arena; head + head-1 per ship

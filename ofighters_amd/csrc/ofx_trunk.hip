@@ -509,7 +509,7 @@ __device__ __forceinline__ void ts_gemm_phase(const float *abase, const float (&
   }
 }
 
-// OFX_OPT_TRUNK_SPARSE (opt-in, exact): the same GEMM phase, but an M-tile whose whole input window - 4 tile rows x 18
+// OFX_OPT_TRUNK_SPARSE (exact; the default): the same GEMM phase, but an M-tile whose whole input window - 4 tile rows x 18
 // columns - holds the layer's CONSTANT input (conv1 of an empty neighbourhood: every channel plane at K1[ci]) and touches
 // no zero padding stores the constant K2[co] the dense MFMA sequence gives for such a window (computed by that very
 // sequence once per workgroup: the same bits) instead of running its 24 MFMAs.  nz: per tile row 8 words, bit x set
@@ -715,7 +715,7 @@ static_assert(F12_PLS % 64 == 16 && F12_PLS % 4 == 0 && F12_LS % 4 == 0, "tile l
 static_assert(2 * F12_BR * F12_WR <= F12_THREADS, "one staged word per thread");
 static_assert((F12_TH + 1) * 100 <= 2 * F12_THREADS && F12_TH * 100 <= F12_THREADS, "pixel pairs per step");
 
-// SPARSE (OFX_OPT_TRUNK_SPARSE, opt-in, fp32 only): the two input planes are ~1 % set bits (lib/observation.py:79-95), so
+// SPARSE (OFX_OPT_TRUNK_SPARSE: exact, the default): the two input planes are ~1 % set bits (lib/observation.py:79-95), so
 // most of conv1's output is ONE value per channel - K1[c] = relu(bn(conv1(empty window))), table pattern 0 - and most
 // of conv2's M-tiles multiply that constant.  Exact: a wave whose 64 pixel pairs all see empty 4 x 6 bit windows writes
 // K1 instead of reading its 16 table rows per pixel (the same sum of the same two table entries), every other pixel
