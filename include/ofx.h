@@ -787,6 +787,53 @@ int ofx_dqn_fit_reference(ofx_handle *h, float *weights, float *adam_m, float *a
                           const ofx_transition *rows, const void *bits_prev, const void *bits_next, float gamma,
                           float *grad_out, float *loss_host);
 
+/* ---- the fit step in two halves: gradient, then apply (gradient accumulation; the seam for a data-parallel sum) ----
+ * ofx_dqn_fit_robust split where its gradient is complete, with a device buffer between the halves, for the textbook
+ * (sparse-target) fit in both forms (lean and OFX_OPT_FIT_PLAIN).  The three fused entries above are untouched.
+ *
+ * The accumulator `acc` is ONE contiguous device float32 buffer of ofx_dqn_acc_floats(h) = n_floats + OFX_ACC_TAIL
+ * floats (a data-parallel caller needs one SUM all-reduce over it):
+ *   [0, n_floats)                         the gradient in the ofx_policy_layout order, untrained slots zero (grad_out)
+ *   tail + OFX_ACC_STAT_FLOATS * k, k < 7  BatchNorm batch statistics of trunk layers 0-3 (k = 0-3) and head-2 layers
+ *                                         0-2 (k = 4-6): {mean, var} pairs, [2 * c] / [2 * c + 1] of channel c, zeros
+ *                                         after the layer's channels
+ *   tail + OFX_ACC_LOSS, + 1              loss1, loss2
+ *   tail + OFX_ACC_COUNT                  how many micro-batches were summed in (a float count)
+ *   the rest                              zero
+ * with tail = n_floats.                                                                                            */
+#define OFX_ACC_TAIL 256
+#define OFX_ACC_STAT_FLOATS 32
+#define OFX_ACC_LOSS (7 * OFX_ACC_STAT_FLOATS)
+#define OFX_ACC_COUNT (OFX_ACC_LOSS + 2)
+int32_t ofx_dqn_acc_floats(const ofx_handle *h);      /* n_floats + OFX_ACC_TAIL; negative on a NULL handle */
+/* The gradient half.  For the n rows exactly the gradient, losses, batch statistics and td_out that
+ * ofx_dqn_fit_robust(..., row_weight, td_out, huber_delta, clip_norm = 0) computes: the same kernels in the same order,
+ * so acc[0, n_floats) after reset holds the bits of that call's grad_out.  Neither `weights` nor any Adam moment is
+ * written and a pinned blob is not prepared again.  Then the accumulator is updated in one pass of fixed order:
+ *   reset != 0:  acc = this micro-batch's values, the whole buffer, count = 1
+ *   reset == 0:  acc[e] += value[e], a plain fp32 add per element (no scale, no fma), count += 1
+ * loss_host may be NULL: the call then synchronises no further than the padding check does; with it the call
+ * synchronises and loss_host[2] = this micro-batch's two losses.  Padding rows are refused as in ofx_dqn_fit; a NULL
+ * acc, n < 1 or a negative or non-finite huber_delta give OFX_ERR_INVALID before anything is launched.  The workspace is
+ * that of a fit of n rows (kept by the handle like ofx_dqn_fit's): k micro-batches of n rows cost the memory of one.  */
+int ofx_dqn_grad(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows, const void *bits_prev,
+                 const float *y_act, const float *y_ptr, const float *row_weight, float *td_out, float huber_delta,
+                 float *acc, int32_t reset, float *loss_host);
+/* The apply half: the tail of a fit step on an accumulator, the effective gradient being scale * acc (scale = 1 / the
+ * count for the mean over micro-batches of equal size).
+ *   clip_norm > 0 or grad_norm_host: the norm over acc[0, n_floats) in ofx_dqn_fit_robust's grid and order, times scale;
+ *     Adam consumes (min(1, clip_norm / (norm + 1e-6)) * scale) * acc, the two factors multiplied once in fp32 into one
+ *     factor kept in device memory.  scale == 1 gives the fused call's norm and update bit for bit, and scale == 1 with
+ *     clip_norm == 0 runs the unscaled Adam kernel.
+ *   moving statistics: 0.99 * moving + 0.01 * (scale * stat);  loss_host[2] = scale * (loss1, loss2) of the tail;
+ *   grad_norm_host = the scaled norm before clipping.
+ * Adam's constants, the bias correction and `step` (1-based) are ofx_dqn_fit's.  Synchronises once (the read-back), then
+ * a pinned blob is prepared again.  OFX_ERR_INVALID for a NULL pointer (loss_host / grad_norm_host may be NULL),
+ * step < 1, a scale that is not finite and > 0 or a clip_norm that is negative or non-finite, before anything is
+ * launched.  ofx_dqn_grad(reset = 1) + ofx_dqn_apply(scale = 1) on n rows is ofx_dqn_fit_robust on them, bit for bit. */
+int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, const float *acc,
+                  float scale, float clip_norm, float *loss_host, float *grad_norm_host);
+
 /* ---- timing helpers (HIP events on the handle's stream) ---------------- */
 int ofx_timer_start(ofx_handle *h);
 int ofx_timer_stop(ofx_handle *h, float *ms_host); /* synchronises */

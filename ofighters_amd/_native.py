@@ -120,6 +120,9 @@ SIGNATURES = {
     "ofx_dqn_fit_weighted": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_fit_robust": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 C.c_float, C.c_float, _vp]),
+    "ofx_dqn_acc_floats": (C.c_int32, [_vp]),
+    "ofx_dqn_grad": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_int32, _vp]),
+    "ofx_dqn_apply": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, _vp, C.c_float, C.c_float, _vp, _vp]),
     "ofx_dqn_fit_reference": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "ofx_replay_create": (_i, [_vp, C.c_int32, C.c_int32]),
     "ofx_replay_create_packed": (_i, [_vp, C.c_int32, C.c_int32, C.c_int64]),

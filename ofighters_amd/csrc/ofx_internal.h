@@ -64,6 +64,8 @@ struct ofx_handle {
   size_t fitws_bytes;              // hipMalloc per replay cost ~60 ms of mapping: r03), grown on demand
   void *fitws2;                    // the reference form's dense targets, kept likewise
   size_t fitws2_bytes;
+  void *applyws;                   // ofx_dqn_apply's {loss, norm, factor} slot and norm partials (2.3 KB), kept likewise
+  size_t applyws_bytes;
   int32_t *counter;                // [4] small device counters, one slot per user (ofx_counter; allocated on first use)
   int32_t *res_iaction;            // [N*M]    (iaction, ipointer) of the last ofx_policy_forward / ofx_policy_explore that
   int32_t *res_ipointer;           // [N*M][2] was given null result pointers (ofx_policy_results: one block, allocated on first use)

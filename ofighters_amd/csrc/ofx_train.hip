@@ -667,6 +667,51 @@ __global__ void t_moving(int c_n, float *mean, float *var, const float *stat) {
   var[c] = 0.99f * var[c] + 0.01f * stat[2 * c + 1];
 }
 
+// ---- the split fit (ofx_dqn_grad / ofx_dqn_apply): the accumulator is [n_floats gradient][OFX_ACC_TAIL] (include/ofx.h) ----
+// One micro-batch into the accumulator, element by element in a fixed order: the gradient blob, the {mean, var} pairs
+// t_moving reads from the 7 stat slots, the two losses, a count of 1 and zeros.  reset: acc = value, else acc += value - a
+// plain fp32 add (this file is compiled with -ffp-contract=off), no scale.
+struct AccSrc {
+  const float *stat[7];   // trunk 0-3, head-2 0-2
+  int stat_n[7];          // floats that hold data in each slot: 2 x channels
+  const float *loss;      // {loss1, loss2}
+};
+__global__ void t_accumulate(size_t n_floats, const float *grad, AccSrc S, float *acc, int reset) {
+  const size_t total = n_floats + OFX_ACC_TAIL;
+  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    float v = 0.f;
+    if (e < n_floats) v = grad[e];
+    else {
+      const int k = (int)(e - n_floats), slot = k / OFX_ACC_STAT_FLOATS, i = k % OFX_ACC_STAT_FLOATS;
+      if (slot < 7) v = i < S.stat_n[slot] ? S.stat[slot][i] : 0.f;
+      else if (k == OFX_ACC_LOSS) v = S.loss[0];
+      else if (k == OFX_ACC_LOSS + 1) v = S.loss[1];
+      else if (k == OFX_ACC_COUNT) v = 1.f;
+    }
+    acc[e] = reset ? v : acc[e] + v;
+  }
+}
+// ofx_dqn_apply's one thread: t_clip_scale's norm of the accumulator (count == 0: none asked for) times scale, and the
+// one factor Adam multiplies the accumulator by, min(1, clip / (norm + 1e-6)) * scale - the two multiplied once, in fp32.
+// out = {scale * loss1, scale * loss2, scaled norm, factor}; scale == 1 leaves t_clip_scale's bits in out[2] / out[3].
+__global__ void t_apply_factor(int count, const double *part, float clip, float scale, const float *tail, float *out) {
+  if (threadIdx.x || blockIdx.x) return;
+  double acc = 0.0;
+  for (int i = 0; i < count; i++) acc += part[i];
+  const float norm = (float)sqrt(acc) * scale;
+  out[0] = scale * tail[OFX_ACC_LOSS];
+  out[1] = scale * tail[OFX_ACC_LOSS + 1];
+  out[2] = norm;
+  out[3] = (clip > 0.f ? fminf(1.f, clip / (norm + 1e-6f)) : 1.f) * scale;
+}
+// t_moving on scale * stat (the accumulator's summed batch statistics); a scale of exactly 1 gives t_moving's bits
+__global__ void t_moving_scaled(int c_n, float *mean, float *var, const float *stat, float scale) {
+  const int c = threadIdx.x;
+  if (c >= c_n) return;
+  mean[c] = 0.99f * mean[c] + 0.01f * (scale * stat[2 * c]);
+  var[c] = 0.99f * var[c] + 0.01f * (scale * stat[2 * c + 1]);
+}
+
 // ---------------------------------------------------------------- host orchestration
 #define GRID(total) dim3((unsigned)(((total) + 255) / 256 > 65535 * 16 ? 65535 * 16 : ((total) + 255) / 256)), dim3(256)
 #define K(kern, total, ...) do { hipLaunchKernelGGL(kern, GRID(total), 0, st, __VA_ARGS__); OFX_HIP(hipGetLastError()); } while (0)
@@ -867,34 +912,55 @@ extern "C" int ofx_policy_blend_weights(ofx_handle *h, float *dst, const float *
 struct FitRobust {
   float huber_delta = 0.f, clip_norm = 0.f;
   float *grad_norm_host = nullptr;
+  // the split fit.  acc (ofx_dqn_grad): the drivers stop after the gradient and hand it to fit_accumulate instead of the
+  // update.  tail (ofx_dqn_apply): `grad` is an accumulator, tail its last OFX_ACC_TAIL floats, scale its factor.
+  float *acc = nullptr;
+  int acc_reset = 0;
+  const float *tail = nullptr;
+  float scale = 1.f;
   bool norm() const { return clip_norm > 0.f || grad_norm_host; }
 };
 static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weights, const float *grad, float *adam_m,
-                            float *adam_v, int32_t step, float lr, float *const *tstat, float *const *ustat,
+                            float *adam_v, int32_t step, float lr, const float *const *tstat, const float *const *ustat,
                             float *loss, float *loss_host, const FitRobust &R, double *npart) {
   hipStream_t st = h->stream;
   const float b1 = 0.9f, b2 = 0.999f;
   const float lr_t = lr * sqrtf(1.f - powf(b2, (float)step)) / (1.f - powf(b1, (float)step));
-  if (R.norm()) {   // untrained slots of the gradient blob are zero: one pass over all of it
+  const bool scaled = R.clip_norm > 0.f || (R.tail && R.scale != 1.f);   // Adam reads its factor from loss[3]
+  if (R.tail) {     // the same norm pass, then the norm, the factor and the losses times scale (t_apply_factor)
+    if (R.norm()) hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
+    hipLaunchKernelGGL(t_apply_factor, dim3(1), dim3(64), 0, st, R.norm() ? kNormBlocks : 0, npart, R.clip_norm, R.scale,
+                       R.tail, loss);
+    OFX_HIP(hipGetLastError());
+  } else if (R.norm()) {   // untrained slots of the gradient blob are zero: one pass over all of it
     hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
     hipLaunchKernelGGL(t_clip_scale, dim3(1), dim3(64), 0, st, kNormBlocks, npart, R.clip_norm, loss + 2);
     OFX_HIP(hipGetLastError());
   }
   for (int t = 0; t < L.n_tensors; t++) {
     if (!ofx_blob_trained(t)) continue;  // moving mean / variance
-    if (R.clip_norm > 0.f)
+    if (scaled)
       K(t_adam_scaled, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t],
         adam_m + L.offset[t], adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f, loss + 3);
     else
       K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
         adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
   }
-  for (int i = 0; i < 4; i++)
-    hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
-                       weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i]);
-  for (int j = 0; j < 3; j++)
-    hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
-                       weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j]);
+  if (R.tail) {
+    for (int i = 0; i < 4; i++)
+      hipLaunchKernelGGL(t_moving_scaled, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
+                         weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i], R.scale);
+    for (int j = 0; j < 3; j++)
+      hipLaunchKernelGGL(t_moving_scaled, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
+                         weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j], R.scale);
+  } else {
+    for (int i = 0; i < 4; i++)
+      hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
+                         weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i]);
+    for (int j = 0; j < 3; j++)
+      hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
+                         weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j]);
+  }
   OFX_HIP(hipGetLastError());
   float lh[4] = {0.f, 0.f, 0.f, 0.f};   // {loss1, loss2, norm, clip factor}
   OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(float) * (R.norm() ? 4 : 2), hipMemcpyDeviceToHost, st));
@@ -902,6 +968,24 @@ static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weig
   if (loss_host) { loss_host[0] = lh[0]; loss_host[1] = lh[1]; }
   if (R.grad_norm_host) *R.grad_norm_host = lh[2];
   return ofx_policy_weights_updated(h, weights);
+}
+
+// The tail of ofx_dqn_grad, in place of fit_apply_update: this micro-batch's gradient, batch statistics and losses into
+// the accumulator (t_accumulate).  Nothing of the weights, the Adam moments or a pinned blob's preparation is touched.
+static int fit_accumulate(ofx_handle *h, const ofx_policy_desc &L, const float *grad, const float *const *tstat,
+                          const float *const *ustat, const float *loss, float *loss_host, const FitRobust &R) {
+  hipStream_t st = h->stream;
+  AccSrc S;
+  for (int i = 0; i < 4; i++) { S.stat[i] = tstat[i]; S.stat_n[i] = 2 * 8; }
+  for (int j = 0; j < 3; j++) { S.stat[4 + j] = ustat[j]; S.stat_n[4 + j] = 2 * kUpCout[j]; }
+  S.loss = loss;
+  const size_t total = (size_t)L.n_floats + OFX_ACC_TAIL;
+  K(t_accumulate, total, (size_t)L.n_floats, grad, S, R.acc, R.acc_reset);
+  if (loss_host) {
+    OFX_HIP(hipMemcpyAsync(loss_host, loss, sizeof(float) * 2, hipMemcpyDeviceToHost, st));
+    OFX_HIP(hipStreamSynchronize(st));
+  }
+  return OFX_OK;
 }
 
 // The lean form of one fit step (default; ofx_fit.hip): the same graph, loss and update as dqn_fit_impl below with only
@@ -1060,6 +1144,7 @@ static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *ada
                          G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)), G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA))))) return rc;
     dzn = tg[i];
   }
+  if (R.acc) return fit_accumulate(h, L, grad, tstat, ustat, loss, loss_host, R);   // ofx_dqn_grad: gradient only
   if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
   return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
@@ -1234,6 +1319,7 @@ static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *ada
     ofx_set_error("ofx_dqn_fit: internal workspace sized too small");
     return OFX_ERR_STATE;
   }
+  if (R.acc) return fit_accumulate(h, L, grad, tstat, ustat, loss, loss_host, R);   // ofx_dqn_grad: gradient only
   if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
   return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
@@ -1286,6 +1372,65 @@ extern "C" int ofx_dqn_fit_robust(ofx_handle *h, float *weights, float *adam_m, 
   R.grad_norm_host = grad_norm_host;
   return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
                       loss_host, row_weight, td_out, R);
+}
+
+// The split fit.  ofx_dqn_grad is ofx_dqn_fit_robust up to and including the backward pass - the same driver in its
+// gradient-only mode (R.acc) - and ofx_dqn_apply is fit_apply_update on an accumulator (R.tail): include/ofx.h.
+extern "C" int32_t ofx_dqn_acc_floats(const ofx_handle *h) {
+  ofx_policy_desc L;
+  if (!h || ofx_policy_layout(h, &L)) return -1;
+  return L.n_floats + OFX_ACC_TAIL;
+}
+
+extern "C" int ofx_dqn_grad(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                            const void *bits_prev, const float *y_act, const float *y_ptr, const float *row_weight,
+                            float *td_out, float huber_delta, float *acc, int32_t reset, float *loss_host) {
+  if (!h || !weights || !rows || !bits_prev || !y_act || !y_ptr || !acc || n < 1) {
+    ofx_set_error("ofx_dqn_grad: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  if (!(huber_delta >= 0.f && huber_delta <= FLT_MAX)) {   // NaN fails the first comparison, infinity the second
+    ofx_set_error("ofx_dqn_grad: huber_delta must be finite and >= 0 (0 = off), got %g", (double)huber_delta);
+    return OFX_ERR_INVALID;
+  }
+  FitRobust R;
+  R.huber_delta = huber_delta;
+  R.acc = acc;
+  R.acc_reset = reset != 0;
+  // (the drivers read the blob and hand it on to fit_apply_update alone, which this mode never reaches)
+  return dqn_fit_impl(h, const_cast<float *>(weights), nullptr, nullptr, 1, 0.f, n, rows, bits_prev, y_act, y_ptr, nullptr,
+                      nullptr, nullptr, loss_host, row_weight, td_out, R);
+}
+
+extern "C" int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr,
+                             const float *acc, float scale, float clip_norm, float *loss_host, float *grad_norm_host) {
+  if (!h || !weights || !adam_m || !adam_v || !acc || step < 1) {
+    ofx_set_error("ofx_dqn_apply: bad argument");
+    return OFX_ERR_INVALID;
+  }
+  if (!(scale > 0.f && scale <= FLT_MAX) || !(clip_norm >= 0.f && clip_norm <= FLT_MAX)) {
+    ofx_set_error("ofx_dqn_apply: scale must be finite and > 0, clip_norm finite and >= 0 (0 = off), got %g and %g",
+                  (double)scale, (double)clip_norm);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  ofx_policy_desc L;
+  int rc = ofx_policy_layout(h, &L);
+  if (rc) return rc;
+  // {loss1, loss2, norm, factor} and the norm's block partials: a block of its own, so the fit's workspace stays as the
+  // last ofx_dqn_grad sized it
+  if ((rc = ofx_ensure_buffer(h, &h->applyws, &h->applyws_bytes, 256 + sizeof(double) * kNormBlocks))) return rc;
+  float *loss = (float *)h->applyws;
+  double *npart = (double *)((char *)h->applyws + 256);
+  const float *tail = acc + L.n_floats, *tstat[4], *ustat[3];
+  for (int i = 0; i < 4; i++) tstat[i] = tail + OFX_ACC_STAT_FLOATS * i;
+  for (int j = 0; j < 3; j++) ustat[j] = tail + OFX_ACC_STAT_FLOATS * (4 + j);
+  FitRobust R;
+  R.clip_norm = clip_norm;
+  R.grad_norm_host = grad_norm_host;
+  R.tail = tail;
+  R.scale = scale;
+  return fit_apply_update(h, L, weights, acc, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
 }
 
 // Trainer.replay's loop body and fit exactly as written (agents/qlearnIA_V2.py:251-285), quirks included:

@@ -752,6 +752,36 @@ class ArenaBatch:
                                                 float(huber_delta), float(clip_norm), C.byref(norm) if on else None))
         return float(loss[0]), float(loss[1]), (float(norm.value) if on else None)
 
+    def dqn_acc_floats(self):
+        """Floats of the accumulator between dqn_grad and dqn_apply: the weight blob's n_floats + the 256-float tail of
+        batch statistics, losses and the micro-batch count (include/ofx.h, OFX_ACC_*)."""
+        v = int(nat.lib().ofx_dqn_acc_floats(self._h))
+        if v < 0:
+            raise Exception("dqn_acc_floats: no policy layout")
+        return v
+
+    def dqn_grad(self, weights_buf, n, rows_ptr, bits_prev_ptr, y_act_ptr, y_ptr_ptr, acc_buf, reset, huber_delta=0.0,
+                 row_weight_ptr=None, td_ptr=None, want_loss=False):
+        """The gradient half of dqn_fit_robust: the n rows' gradient, batch statistics and losses go into acc_buf (a
+        DeviceBuffer of 4 * dqn_acc_floats() bytes) - written with reset, added to it (plain fp32 adds, the count + 1)
+        without.  Nothing of the weights or the Adam state is written.  td_ptr receives the raw errors.  Returns None and
+        does not synchronise beyond the padding check, or with want_loss this micro-batch's (loss1, loss2)."""
+        loss = (C.c_float * 2)() if want_loss else None
+        nat.check(nat.lib().ofx_dqn_grad(self._h, weights_buf.ptr, int(n), rows_ptr, bits_prev_ptr, y_act_ptr, y_ptr_ptr,
+                                          row_weight_ptr, td_ptr, float(huber_delta), acc_buf.ptr, 1 if reset else 0, loss))
+        return (float(loss[0]), float(loss[1])) if want_loss else None
+
+    def dqn_apply(self, weights_buf, adam_m_buf, adam_v_buf, step, lr, acc_buf, scale=1.0, clip_norm=0.0, want_norm=None):
+        """The apply half: Adam, the moving statistics and the loss read-back on scale * acc_buf, the gradient clipped to a
+        global norm of clip_norm (> 0) after scaling; DeviceBuffers are updated in place.  Returns (loss1, loss2,
+        grad_norm): scale times the accumulated losses and the scaled norm before clipping - None unless clip_norm is set
+        or want_norm asks for it.  dqn_grad(reset=True) + dqn_apply(scale=1) is dqn_fit_robust bit for bit."""
+        loss, norm = (C.c_float * 2)(), C.c_float(0.0)
+        on = bool(clip_norm) if want_norm is None else bool(want_norm)   # (NaN is true: refused at the entry)
+        nat.check(nat.lib().ofx_dqn_apply(self._h, weights_buf.ptr, adam_m_buf.ptr, adam_v_buf.ptr, int(step), float(lr),
+                                           acc_buf.ptr, float(scale), float(clip_norm), loss, C.byref(norm) if on else None))
+        return float(loss[0]), float(loss[1]), (float(norm.value) if on else None)
+
     def dqn_fit_reference(self, weights_buf, adam_m_buf, adam_v_buf, step, lr, n, rows_ptr, bits_prev_ptr, bits_next_ptr,
                           gamma=0.9, grad_buf=None):
         """The fit step with Trainer.replay's quirks as written (qlearnIA_V2.py:251-285: whole-prediction targets,

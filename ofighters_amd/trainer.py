@@ -57,6 +57,24 @@ and `packed_memory`; refused with reference_quirks (ValueError); the value must 
 "global_sampling": True only when it is on, so a state taken under one sampler is refused under the other, and `draws`
 keys the sampler's Philox stream as before: a checkpoint needs nothing new.
 
+`accumulate=k` (opt-in, not in the reference; an integer >= 1 and no bool, 1 = off; k > 1 needs global_sampling and is
+refused with reference_quirks: ValueError naming accumulate before anything is allocated) makes one fit step out of k
+micro-batches: replay() draws k * fit_batch rows in ONE ofx_replay_sample_global call (with `prioritized` the IS weights
+are max-normalised over the whole draw), cuts the n rows drawn into c = max(1, n // fit_batch) chunks of fit_batch rows
+(one chunk of n rows while n < fit_batch; rows beyond c * fit_batch are not fitted), and runs gather, targets and
+ofx_dqn_grad per chunk - the chunks are pointer offsets into the draw's sorted list - summing gradient, batch statistics
+and losses into one device accumulator; one ofx_dqn_apply then applies their mean (scale = 1 / c; clip_norm acts on
+that mean), the priorities of all fitted rows are written back and the target network moves.  The fit's workspace is
+that of ONE chunk, which is the point: the step's batch is no longer bounded by it.  BatchNorm normalises every chunk by
+its own batch statistics and the moving statistics take their mean, so k chunks are not bit for bit one fit of k *
+fit_batch rows.  One replay is still one draw and one fit step.  `grad_hook` (an attribute, None by default) is called as
+hook(trainer, acc_buffer) between the last ofx_dqn_grad and ofx_dqn_apply with the accumulator's DeviceBuffer
+(batch.dqn_acc_floats() floats: include/ofx.h) and returns how many accumulators it summed into the buffer (None or 1: it
+is untouched); the scale becomes 1 / (c * that count).  It is the place for a data-parallel caller's SUM all-reduce.  With
+a hook set the step goes through ofx_dqn_grad + ofx_dqn_apply also at accumulate=1 (one chunk: the fused step's bits) on
+every textbook replay path.  fingerprint() carries "accumulate": k only when k > 1; the accumulator is scratch inside
+one replay(), so a checkpoint needs nothing new.
+
 save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
 (`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
 cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
@@ -90,16 +108,34 @@ def fingerprint_diff(have, want):
     return sorted(k for k in set(have) | set(want) if k not in have or k not in want or have[k] != want[k])
 
 
+class _At:
+    """A position inside a DeviceBuffer for the engine calls that take one (they read .ptr alone); owns nothing."""
+
+    def __init__(self, buf, offset):
+        self.ptr = buf.ptr + int(offset)
+
+
 class DeviceTrainer:
     global_sampling = False                                  # the opt-in of __init__; off on any trainer that never set it
+    accumulate = 1                                           # likewise: micro-batches per fit step
+    grad_hook = None                                         # hook(trainer, acc_buffer) before ofx_dqn_apply; see above
 
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
                  per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
-                 huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0, global_sampling=False):
+                 huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0, global_sampling=False,
+                 accumulate=1):
         memory_pool_pairs = check_pool_pairs("DeviceTrainer: memory_pool_pairs", packed_memory, memory_pool_pairs)
         if not isinstance(global_sampling, (bool, np.bool_)):
             raise ValueError("DeviceTrainer: global_sampling must be a bool, got %r" % (global_sampling,))
+        if isinstance(accumulate, (bool, np.bool_)) or not isinstance(accumulate, (int, np.integer)) or accumulate < 1:
+            raise ValueError("DeviceTrainer: accumulate must be an integer >= 1, got %r" % (accumulate,))
+        if accumulate > 1 and reference_quirks:
+            raise ValueError("DeviceTrainer: accumulate > 1 needs the textbook fit (reference_quirks=False is the "
+                             "reference's one fit per replay as written)")
+        if accumulate > 1 and not global_sampling:
+            raise ValueError("DeviceTrainer: accumulate > 1 needs global_sampling=True (the k * fit_batch rows of a step "
+                             "are one draw from all arenas' memories)")
         if global_sampling and reference_quirks:
             raise ValueError("DeviceTrainer: global sampling needs the textbook fit (reference_quirks=False is the "
                              "reference's replay over its own memory as written)")
@@ -161,6 +197,7 @@ class DeviceTrainer:
         self.packed_memory = bool(packed_memory)             # the replay memory's frame store: packed pairs or dense ring
         self.memory_pool_pairs = memory_pool_pairs           # pairs per arena of the packed store (0: the library's default)
         self.global_sampling = bool(global_sampling)         # one minibatch of fit_batch rows from all arenas' memories
+        self.accumulate = int(accumulate)                    # micro-batches of fit_batch rows per fit step
         if self.packed_memory:
             batch.replay_create(memory_size, frames, packed=True, pool_pairs=memory_pool_pairs)
         else:
@@ -219,6 +256,8 @@ class DeviceTrainer:
                 "memory_capacity": int(b.replay_capacity), "memory_frames": int(b.replay_frames)}
         if self.global_sampling:                             # only when on: a default trainer's key set stays as it was,
             fp["global_sampling"] = True                     # and fingerprint_diff counts the missing key as a difference
+        if self.accumulate > 1:                              # the same pattern
+            fp["accumulate"] = self.accumulate
         return fp
 
     def state_dict(self):
@@ -300,7 +339,9 @@ class DeviceTrainer:
         y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
         self._targets(n, rows_p, prev_p, next_p, y_act, y_ptr)
         self.fit_steps += 1
-        if self._robust():
+        if self.grad_hook is not None:
+            loss = self._fit_split(n, rows_p, prev_p, y_act, y_ptr)
+        elif self._robust():
             loss = self._fit_robust(n, rows_p, prev_p, y_act, y_ptr)
         else:
             loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
@@ -313,6 +354,8 @@ class DeviceTrainer:
         """replay() under global_sampling: fit_batch rows drawn from the union of all arenas' memories (uniform over
         rows, or by priority across arenas), the list gather, the same targets and fit calls, the list write-back.  The
         sampler's two host integers are the only synchronisation before the fit."""
+        if self.accumulate > 1 or self.grad_hook is not None:
+            return self._replay_accumulate()
         b = self.batch
         nb = int(self.fit_batch)
         per = self.prioritized
@@ -348,6 +391,72 @@ class DeviceTrainer:
         self._move_target()
         self.losses.append(loss)
         return loss
+
+    def _replay_accumulate(self):
+        """replay() under global_sampling with accumulate > 1 or a grad_hook: accumulate * fit_batch rows in one draw, cut
+        into c = max(1, n // fit_batch) chunks of fit_batch rows (one chunk of all n rows while n < fit_batch; the rows
+        beyond c * fit_batch are drawn but NOT fitted); gather, targets and ofx_dqn_grad per chunk at pointer offsets into
+        the draw's list, the hook, one ofx_dqn_apply with scale = 1 / (c * the hook's count), then the write-back over all
+        fitted rows and the target network's move.  Buffers that hold maps are sized for one chunk."""
+        b = self.batch
+        fb = int(self.fit_batch)
+        nb = self.accumulate * fb
+        per = self.prioritized
+        arena, slot, row_w, n, _ = b.replay_sample_global(self.seed, self.draws, nb, per, self.beta() if per else 0.0,
+                                                          self._scratch("g_arena", 4 * nb), self._scratch("g_slot", 4 * nb),
+                                                          self._scratch("row_w", 4 * nb) if per else None)
+        self.draws += 1
+        if n == 0:
+            return None
+        c = max(1, n // fb)
+        m = fb if n >= fb else n                             # rows per chunk
+        words = b.W * b.H // 32
+        row_bytes = b.TRANSITION_DTYPE.itemsize
+        rows = self._scratch("rows", c * m * row_bytes)      # of every chunk: the write-back reads them
+        bits_prev, bits_next = self._scratch("bits_prev", 4 * m * 2 * words), self._scratch("bits_next", 4 * m * 2 * words)
+        y_act, y_ptr = self._scratch("y_act", 4 * m), self._scratch("y_ptr", 4 * m)
+        td = self._scratch("td", 8 * c * m) if per else None
+        acc = self._scratch("acc", 4 * b.dqn_acc_floats())
+        prev_p = bits_prev.ptr
+        self.fit_steps += 1
+        for i in range(c):
+            o = i * m
+            arena_i, slot_i, rows_i = _At(arena, 4 * o), _At(slot, 4 * o), _At(rows, o * row_bytes)
+            if self.n_step == 1:
+                b.replay_gather_list_into(arena_i, slot_i, m, rows_i, bits_prev, bits_next)
+            else:
+                b.replay_gather_list_into(arena_i, slot_i, m, rows_i, bits_prev, bits_next, self.n_step, self.gamma,
+                                          self._scratch("ret", 4 * m), self._scratch("disc", 4 * m))
+            self._targets(m, rows_i.ptr, prev_p, bits_next.ptr, y_act, y_ptr)
+            b.dqn_grad(self.weights, m, rows_i.ptr, prev_p, y_act.ptr, y_ptr.ptr, acc, i == 0, self.huber_delta or 0.0,
+                       row_w.ptr + 4 * o if per else None, td.ptr + 8 * o if per else None)
+        loss = self._apply(acc, c)
+        if per:
+            b.replay_update_priorities_list(arena, slot, c * m, rows.ptr, td.ptr)
+        self._move_target()
+        self.losses.append(loss)
+        return loss
+
+    def _fit_split(self, n, rows_p, prev_p, y_act, y_ptr, row_w_p=None, td_p=None):
+        """The fit step as ofx_dqn_grad + the hook + ofx_dqn_apply on one chunk (a grad_hook at accumulate=1)."""
+        acc = self._scratch("acc", 4 * self.batch.dqn_acc_floats())
+        self.batch.dqn_grad(self.weights, n, rows_p, prev_p, y_act.ptr, y_ptr.ptr, acc, True, self.huber_delta or 0.0,
+                            row_w_p, td_p)
+        return self._apply(acc, 1)
+
+    def _apply(self, acc, chunks):
+        """The hook, then ofx_dqn_apply on the mean of `chunks` x (the hook's count) accumulated micro-batches; the norm
+        before clipping goes to grad_norms where the fused step reports it (huber_delta / clip_norm)."""
+        count = self.grad_hook(self, acc) if self.grad_hook is not None else None
+        count = 1 if count is None else count
+        if isinstance(count, bool) or int(count) != count or count < 1:
+            raise ValueError("DeviceTrainer: grad_hook must return None or the integer count >= 1 of accumulators it "
+                             "summed, got %r" % (count,))
+        l1, l2, norm = self.batch.dqn_apply(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, acc,
+                                            1.0 / (chunks * int(count)), self.clip_norm or 0.0, want_norm=self._robust())
+        if self._robust():
+            self.grad_norms.append(norm)
+        return l1, l2
 
     def _robust(self):
         return self.huber_delta is not None or self.clip_norm is not None
@@ -429,7 +538,9 @@ class DeviceTrainer:
         y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
         self._targets(n, rows.ptr, bits_prev.ptr, bits_next.ptr, y_act, y_ptr)
         self.fit_steps += 1
-        if self._robust():
+        if self.grad_hook is not None:
+            loss = self._fit_split(n, rows.ptr, bits_prev.ptr, y_act, y_ptr, row_w.ptr, td.ptr)
+        elif self._robust():
             loss = self._fit_robust(n, rows.ptr, bits_prev.ptr, y_act, y_ptr, row_w.ptr, td.ptr)
         else:
             loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n,
