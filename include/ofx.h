@@ -354,6 +354,22 @@ int ofx_set_option(ofx_handle *h, int32_t option, int32_t value);
  * ofx_policy_forward / ofx_policy_explore.                                                                     */
 int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, uint32_t tick, int32_t collecting,
                        const uint8_t *ship_mask, int32_t *iaction, int32_t *ipointer);
+/* ofx_policy_forward and ofx_policy_explore in one call, with the values of what was chosen (opt-in; the input of the
+ * actor-side initial priorities below).  Afterwards the handle-kept (iaction, ipointer) are bit for bit those of
+ * ofx_policy_forward(h, weights, ship_mask, NULL, NULL, NULL, NULL) followed by ofx_policy_explore(h, epsilon, seed,
+ * tick, collecting, ship_mask, NULL, NULL); pinning, the OFX_OPT_* switches and the argument checks are those of the two
+ * calls.  The exploration draw depends on (arena, ship, tick) alone, so it is made before the forward and handed to the
+ * head kernel as a probe: the heat map's value at an exploratory pointer leaves the pass that finds the maximum.  For
+ * every selected ship (device float32 [N][M] each; ships outside ship_mask are not written):
+ *   q_sa   act_values[chosen iaction]
+ *   p_sp   the heat map's value at the chosen pointer: its maximum for a greedy ship, the probed value for an exploring one
+ *   v_act  max(act_values)
+ *   v_ptr  the heat map's maximum
+ * A NULL output goes to a handle-owned [N][M] array (allocated at the first call, freed by ofx_destroy).  A call with
+ * ALL FOUR outputs NULL makes those arrays what ofx_replay_capture_valued reads when it is given no values; a call
+ * with any explicit output withdraws that again (the handle's arrays would be partly stale).  Does not synchronise.   */
+int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t *ship_mask, double epsilon, uint64_t seed,
+                   uint32_t tick, int32_t collecting, float *q_sa, float *p_sp, float *v_act, float *v_ptr);
 /* QlearnIA.play action packing (qlearnIA_V2.py:447-454): exactly one of
  * shoot/thrust set, pointer always set.  NULL iaction / ipointer = the handle's
  * results of the last ofx_policy_forward / ofx_policy_explore.               */
@@ -475,6 +491,38 @@ int ofx_replay_update_priorities(ofx_handle *h, const int32_t *slot, const int32
                                  int32_t first, int32_t n_rows, const ofx_transition *rows, const float *td);
 /* Masses of one arena, oldest first (the order of ofx_replay_rows_host); mass_host holds `capacity` floats.        */
 int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *mass_host, int32_t *n_host);
+
+/* ---- actor-side initial priorities (opt-in) --------------------------------
+ * Horgan et al. 2018 (Ape-X): with many actors per learner nearly every row leaves the memory before it is ever fitted,
+ * so the priority it ENTERS with decides what is sampled - and under the rule above that is the same mmax for all of
+ * them.  Here the actor and the learner share a device: the forward of lock-step t + 1 has max act_values(s') and
+ * max heat(s'), the one of lock-step t had Q(s, a) and heat(s) at the chosen pointer (ofx_policy_act), so the row's
+ * one-step TD errors exist the moment it is captured.  Off unless ofx_replay_actor_priorities is called; then
+ * ofx_replay_capture still works as before (mass = mmax[a], prev_q untouched).
+ *  - prev_q: float32 [N][M][2] = (q_sa, p_sp) of each ship's previous_*, zeros at first; dropped with the memory.
+ *  - ofx_replay_capture_valued does everything ofx_replay_capture does - rows and frames come out byte-identical - and
+ *    every playing ship stores this lock-step's (q_sa, p_sp) into prev_q.  A ship whose row completes forms, in float32
+ *    and in the operation order of ofx_dqn_targets (the actor and the learner agree on equal inputs),
+ *      y1 = reward + gamma * v_act * (1 - done), e1 = prev_q_sa - y1;  y2 = reward + gamma * v_ptr * (1 - done),
+ *      e2 = prev_p_sp - y2   (a done row never reads v_*),
+ *    and its row's mass is the write-back's p = |e1| + |e2| + eps, m = powf(p, alpha) (one device function for both).
+ *    A non-finite e1 or e2: the row takes mmax[a] as it was BEFORE this lock-step, the old rule.  Afterwards
+ *    mmax[a] = max(old, the new masses of this arena formed from finite errors) - one wave reduction, no atomics.
+ *  - The initial priority is the ONE-STEP error of the blob the forward ran on, in inference mode, whatever targets the
+ *    learner forms (n-step, a target network, Double DQN); the first write-back replaces it with the learner's error.
+ * The replay blob (below) does not carry prev_q and keeps its format: a checkpoint moves it with the host pair.        */
+/* Enable (OFX_ERR_STATE without ofx_replay_prioritize; gamma outside [0, 1] or NaN: OFX_ERR_INVALID).  Called again:
+ * the new gamma, prev_q back to zeros.  Synchronises.                                                                */
+int ofx_replay_actor_priorities(ofx_handle *h, float gamma);
+/* Device float32 [N][M] each: all four NULL = the handle's arrays of the last ofx_policy_act (OFX_ERR_STATE before its
+ * first call, or when the last one was given an explicit output), else all four given (OFX_ERR_INVALID otherwise).  tick, ship_mask, iaction, ipointer: ofx_replay_capture's.
+ * OFX_ERR_STATE unless actor priorities are enabled.                                                                 */
+int ofx_replay_capture_valued(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
+                              const int32_t *ipointer, const float *q_sa, const float *p_sp, const float *v_act,
+                              const float *v_ptr);
+/* prev_q to / from the host, float32 [N][M][2].  OFX_ERR_STATE unless actor priorities are enabled.  Synchronise.    */
+int ofx_replay_actor_values_host(ofx_handle *h, float *dst_host);
+int ofx_replay_set_actor_values(ofx_handle *h, const float *src_host);
 
 /* ---- global minibatch sampling (opt-in) ----------------------------------
  * The samplers above draw `batch` rows in EVERY arena.  ofx_replay_sample_global draws n_rows rows from the union of all

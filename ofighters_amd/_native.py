@@ -114,6 +114,7 @@ SIGNATURES = {
     "ofx_policy_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_actions": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_explore": (_i, [_vp, C.c_double, _u64, _u32, C.c_int32, _vp, _vp, _vp]),
+    "ofx_policy_act": (_i, [_vp, _vp, _vp, C.c_double, _u64, _u32, C.c_int32, _vp, _vp, _vp, _vp]),
     "ofx_policy_forward_obs": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_targets": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "ofx_dqn_fit": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -141,6 +142,10 @@ SIGNATURES = {
     "ofx_replay_window_weights": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "ofx_replay_update_priorities": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "ofx_replay_priorities_host": (_i, [_vp, C.c_int32, _vp, _vp]),
+    "ofx_replay_actor_priorities": (_i, [_vp, C.c_float]),
+    "ofx_replay_capture_valued": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofx_replay_actor_values_host": (_i, [_vp, _vp]),
+    "ofx_replay_set_actor_values": (_i, [_vp, _vp]),
     "ofx_replay_sample_global": (_i, [_vp, _u64, _u32, C.c_int32, C.c_int32, C.c_double, _vp, _vp, _vp,
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ofx_replay_gather_list": (_i, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, _vp]),

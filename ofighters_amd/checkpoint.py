@@ -11,6 +11,8 @@ counter, and a fit is reproducible to the bit, so nothing else is hidden):
     trainer/*        weights, Adam m and v, the target blob, the loss and gradient-norm lists (DeviceTrainer.state_dict)
     replay/<k>       the replay memory as ofx_replay_export blobs of consecutive arena chunks, each chosen from
                      ofx_replay_export_bytes to stay under CHUNK_BYTES of host memory
+    replay_actor_values   only with the trainer's actor_priorities: (q_sa, p_sp) of every ship's previous_*, float32
+                     [N][M][2] (the replay blob keeps its format and does not carry them)
 
 Layout: the 8 bytes b"OFXCKPT1"; the sections' raw little-endian bytes, each starting at a multiple of 8; the manifest
 as UTF-8 JSON; a 24-byte trailer = uint64 manifest offset, uint64 manifest length, b"OFXCKPT1" again.  The manifest comes
@@ -175,6 +177,8 @@ def save(rollout, path, chunk_bytes=None):
             w.add("replay/%d" % len(chunks), blob)
             chunks.append([int(a), int(k)])
         manifest["replay_chunks"] = chunks
+        if getattr(t, "actor_priorities", False):
+            w.add("replay_actor_values", e.replay_actor_values())
         w.finish(manifest)
     except BaseException:
         w.abort()
@@ -205,6 +209,8 @@ def load(rollout, path):
     e.sync()
     for i, (a, k) in enumerate(m["replay_chunks"]):
         e.replay_import(a, k, rd.array("replay/%d" % i))
+    if getattr(t, "actor_priorities", False):                          # (the fingerprints agree: the section is there)
+        e.set_replay_actor_values(rd.array("replay_actor_values"))
     es = {name[len("arena/"):]: rd.array(name) for name in rd.sections if name.startswith("arena/")}
     es["episode"], es["tick"] = m["counters"]["engine_episode"], m["counters"]["engine_tick"]
     e.load_state_dict(es)

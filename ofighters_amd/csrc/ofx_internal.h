@@ -82,6 +82,10 @@ struct ofx_handle {
   // (diagnostic, the reference of the == tests); the forwards on stored observations stay sparse.
   bool opt_trunk_dense, opt_trunk_count;
   unsigned long long *trunk_stat;  // [4] device counters of the sparse trunk (allocated with value 1 of the option)
+  // ofx_policy_act (one block, allocated at its first call): the four value arrays a null output stands for, then the
+  // forward's results they are selected from and the pre-drawn exploration
+  float *act_vals;                 // [4][N*M] q_sa, p_sp, v_act, v_ptr, then act [N*M][2], ptr_max [N*M], ptr_probe [N*M]
+  bool act_called;                 // the LAST ofx_policy_act wrote all four of the handle's arrays (all outputs NULL)
 };
 #define OFX_RING_MAX 65536         /* numbered events of ofx_event_record */
 
@@ -95,6 +99,8 @@ int ofx_counter(ofx_handle *h, int slot, int32_t **counter);
 // the handle's own (iaction [N*M], ipointer [N*M][2]): what a null result pointer of ofx_policy_forward /
 // ofx_policy_explore / ofx_policy_actions / ofx_replay_capture stands for
 int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer);
+// the handle's (q_sa, p_sp, v_act, v_ptr) [N*M] of ofx_policy_act; OFX_ERR_STATE unless the last one wrote all four
+int ofx_policy_act_values(ofx_handle *h, const float **q_sa, const float **p_sp, const float **v_act, const float **v_ptr);
 void ofx_replay_free(ofx_handle *h);
 int ofx_replay_episode_reset(ofx_handle *h, const uint8_t *arena_mask);
 // C[M][N] = act(A[M][K] (lda) x B[K][N] (ldb) + bias[N]) on the f32 MFMA (k_gemm_f32, ofx_policy.hip)

@@ -716,29 +716,43 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   return OFX_OK;
 }
 
-extern "C" int ofx_policy_forward(ofx_handle *h, const float *weights, const uint8_t *ship_mask, float *act_values,
-                                  int32_t *iaction, int32_t *ipointer, float *heatmap) {
-  if (!h || !weights) { ofx_set_error("ofx_policy_forward: null argument"); return OFX_ERR_INVALID; }
+// the argument checks of a forward on the live state, and the forward itself: `a` carries the results wanted, the
+// weights and the mask; the images are the handle's arenas
+static int live_forward_check(ofx_handle *h, const float *weights, const char *who) {
+  if (!h || !weights) { ofx_set_error("%s: null argument", who); return OFX_ERR_INVALID; }
   if (!h->spawned) { ofx_set_error("You must execute analyse_battleground first."); return OFX_ERR_STATE; }
   const ofx_config &c = h->cfg;
   if (c.width != PS || c.height != PS) {
     // Input((DEFAULT_WIDTH, DEFAULT_HEIGHT, 2)) is fixed at 400x400 (qlearnIA_V2.py:125)
-    ofx_set_error("ofx_policy_forward: the pointer_model takes 400x400 maps (got %d x %d)", c.width, c.height);
+    ofx_set_error("%s: the pointer_model takes 400x400 maps (got %d x %d)", who, c.width, c.height);
     return OFX_ERR_INVALID;
   }
-  OFX_HIP(hipSetDevice(c.device));
+  return OFX_OK;
+}
+
+static int live_forward(ofx_handle *h, ForwardArgs &a) {
+  const ofx_config &c = h->cfg;
   int rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr);  // the observation as 1-bit maps
   if (rc) return rc;
   int32_t *ria, *rip;  // null = the handle's results
   if ((rc = ofx_policy_results(h, &ria, &rip))) return rc;
-  if (!iaction) iaction = ria;
-  if (!ipointer) ipointer = rip;
-  ForwardArgs a{};
-  a.weights = weights; a.N = c.n_arenas; a.M = c.n_ships;
+  if (!a.iaction) a.iaction = ria;
+  if (!a.ipointer) a.ipointer = rip;
+  a.N = c.n_arenas; a.M = c.n_ships;
   a.bits[0] = (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0]; a.bits[1] = (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1];
   a.bits_stride = (size_t)(PS * PS) >> 5;
-  a.ship_mask = ship_mask; a.act_values = act_values; a.iaction = iaction; a.ipointer = ipointer; a.heatmap = heatmap;
   return policy_forward_impl(h, a);
+}
+
+extern "C" int ofx_policy_forward(ofx_handle *h, const float *weights, const uint8_t *ship_mask, float *act_values,
+                                  int32_t *iaction, int32_t *ipointer, float *heatmap) {
+  int rc = live_forward_check(h, weights, "ofx_policy_forward");
+  if (rc) return rc;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  ForwardArgs a{};
+  a.weights = weights;
+  a.ship_mask = ship_mask; a.act_values = act_values; a.iaction = iaction; a.ipointer = ipointer; a.heatmap = heatmap;
+  return live_forward(h, a);
 }
 
 // n stored observations (bits [n][2][5000], vec8 [n][8]), one policy sample each
@@ -771,18 +785,30 @@ int ofx_policy_predict_obs(ofx_handle *h, const float *weights, int32_t n_obs, c
 }
 
 #define OFX_STREAM_EXPLORE 2u
+// The draw of ship i of arena a at `tick`: true when the ship explores, i.e. random_play() replaces its greedy choice
+// (np.random.rand() <= epsilon, qlearnIA_V2.py:201, or the collecting phase).  The Philox words exist either way, so
+// (*ia, *px, *py) is a valid random choice for every ship - ofx_policy_act probes the heat map there before it knows.
+__device__ __forceinline__ bool explore_draw(int a, int i, int W, int H, int arena_base, double eps, uint32_t k0, uint32_t k1,
+                                             uint32_t tick, int collecting, int32_t *ia, int32_t *px, int32_t *py) {
+  uint32_t r[4];
+  ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_EXPLORE, k0, k1, r);
+  const double u = (double)r[0] * (1.0 / 4294967296.0);
+  *ia = ofx_draw_int(r[1], 1);
+  *px = ofx_draw_int(r[2], W - 1);
+  *py = ofx_draw_int(r[3], H - 1);
+  return collecting || u <= eps;
+}
+
 __global__ void k_policy_explore(int N, int M, int W, int H, int arena_base, double eps, uint32_t k0, uint32_t k1,
                                  uint32_t tick, int collecting, const uint8_t *mask, int32_t *iaction, int32_t *ipointer) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N * M || (mask && !mask[s])) return;
   const int a = s / M, i = s - a * M;
-  uint32_t r[4];
-  ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_EXPLORE, k0, k1, r);
-  const double u = (double)r[0] * (1.0 / 4294967296.0);
-  if (collecting || u <= eps) {  // np.random.rand() <= epsilon (qlearnIA_V2.py:201)
-    iaction[s] = ofx_draw_int(r[1], 1);
-    ipointer[2 * s] = ofx_draw_int(r[2], W - 1);
-    ipointer[2 * s + 1] = ofx_draw_int(r[3], H - 1);
+  int32_t ia, px, py;
+  if (explore_draw(a, i, W, H, arena_base, eps, k0, k1, tick, collecting, &ia, &px, &py)) {
+    iaction[s] = ia;
+    ipointer[2 * s] = px;
+    ipointer[2 * s + 1] = py;
   }
 }
 
@@ -802,6 +828,98 @@ extern "C" int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, 
                      h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), tick,
                      collecting, ship_mask, iaction, ipointer);
   OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ---- ofx_policy_act: forward + exploration in one call, with the values of what was chosen --------------------------
+// The exploration draw depends on (arena, ship, tick) alone, so it is made BEFORE the forward and handed to the head
+// kernel as its probe: the heat map's value at an exploratory pointer leaves the same pass that finds the maximum.
+// Everything is addressed by ship index s = a * M + i (a masked forward walks the compacted list, but hd_ship maps
+// every work item back to s before it reads the probe or writes a result).
+__global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, double eps, uint32_t k0, uint32_t k1,
+                                 uint32_t tick, int collecting, const uint8_t *mask, uint8_t *explores, int32_t *draw_ia,
+                                 int32_t *probe) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= N * M) return;
+  if (mask && !mask[s]) {  // never read by the head, but never left uninitialised either
+    explores[s] = 0; draw_ia[s] = 0; probe[2 * s] = probe[2 * s + 1] = 0;
+    return;
+  }
+  const int a = s / M, i = s - a * M;
+  int32_t ia, px, py;
+  explores[s] = explore_draw(a, i, W, H, arena_base, eps, k0, k1, tick, collecting, &ia, &px, &py) ? 1 : 0;
+  draw_ia[s] = ia;
+  probe[2 * s] = px;
+  probe[2 * s + 1] = py;
+}
+
+__global__ void k_policy_act_finish(int S, const uint8_t *mask, const uint8_t *explores, const int32_t *draw_ia,
+                                    const int32_t *probe, const float *act, const float *ptr_max, const float *ptr_probe,
+                                    int32_t *iaction, int32_t *ipointer, float *q_sa, float *p_sp, float *v_act,
+                                    float *v_ptr) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S || (mask && !mask[s])) return;
+  const bool ex = explores[s] != 0;
+  if (ex) {
+    iaction[s] = draw_ia[s];
+    ipointer[2 * s] = probe[2 * s];
+    ipointer[2 * s + 1] = probe[2 * s + 1];
+  }
+  const float a0 = act[2 * s], a1 = act[2 * s + 1];
+  q_sa[s] = iaction[s] ? a1 : a0;
+  v_act[s] = fmaxf(a0, a1);                   // np.max(prediction), as k_dqn_targets forms it
+  v_ptr[s] = ptr_max[s];
+  p_sp[s] = ex ? ptr_probe[s] : ptr_max[s];   // the greedy pointer is the arg-max: its value is the maximum
+}
+
+// the handle's block of ofx_policy_act: floats q_sa, p_sp, v_act, v_ptr [S] each, act [S][2], ptr_max [S], ptr_probe [S];
+// then int32 draw_ia [S], probe [S][2]; then uint8 explores [S]
+static int policy_act_block(ofx_handle *h) {
+  if (h->act_vals) return OFX_OK;
+  const size_t S = (size_t)h->cfg.n_arenas * h->cfg.n_ships;
+  OFX_HIP(hipMalloc((void **)&h->act_vals, S * (8 * sizeof(float) + 3 * sizeof(int32_t) + 1)));
+  OFX_HIP(hipMemsetAsync(h->act_vals, 0, S * (8 * sizeof(float) + 3 * sizeof(int32_t) + 1), h->stream));
+  return OFX_OK;
+}
+
+int ofx_policy_act_values(ofx_handle *h, const float **q_sa, const float **p_sp, const float **v_act, const float **v_ptr) {
+  if (!h->act_called) return OFX_ERR_STATE;
+  const size_t S = (size_t)h->cfg.n_arenas * h->cfg.n_ships;
+  *q_sa = h->act_vals; *p_sp = h->act_vals + S; *v_act = h->act_vals + 2 * S; *v_ptr = h->act_vals + 3 * S;
+  return OFX_OK;
+}
+
+extern "C" int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t *ship_mask, double epsilon, uint64_t seed,
+                              uint32_t tick, int32_t collecting, float *q_sa, float *p_sp, float *v_act, float *v_ptr) {
+  int rc = live_forward_check(h, weights, "ofx_policy_act");
+  if (rc) return rc;
+  if (epsilon < 0.0 || epsilon > 1.0) { ofx_set_error("Value must me in range [0,1]"); return OFX_ERR_INVALID; }  // epsilon.py:56
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if ((rc = policy_act_block(h))) return rc;
+  const int S = h->cfg.n_arenas * h->cfg.n_ships;
+  float *f = h->act_vals;
+  float *act = f + 4 * (size_t)S, *ptr_max = f + 6 * (size_t)S, *ptr_probe = f + 7 * (size_t)S;
+  int32_t *draw_ia = (int32_t *)(f + 8 * (size_t)S), *probe = draw_ia + S;
+  uint8_t *explores = (uint8_t *)(probe + 2 * (size_t)S);
+  // the handle's four arrays stand for "the last ofx_policy_act" only when that call wrote all four of them
+  const bool kept = !q_sa && !p_sp && !v_act && !v_ptr;
+  if (!q_sa) q_sa = f;
+  if (!p_sp) p_sp = f + S;
+  if (!v_act) v_act = f + 2 * (size_t)S;
+  if (!v_ptr) v_ptr = f + 3 * (size_t)S;
+  hipLaunchKernelGGL(k_policy_predraw, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
+                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), tick,
+                     collecting, ship_mask, explores, draw_ia, probe);
+  OFX_HIP(hipGetLastError());
+  ForwardArgs a{};
+  a.weights = weights; a.ship_mask = ship_mask;
+  a.act_values = act; a.ptr_max = ptr_max; a.probe = probe; a.ptr_probe = ptr_probe;
+  h->act_called = false;
+  if ((rc = live_forward(h, a))) return rc;   // (iaction, ipointer): the handle's results
+  hipLaunchKernelGGL(k_policy_act_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, ship_mask, explores, draw_ia,
+                     probe, act, ptr_max, ptr_probe, a.iaction, a.ipointer, q_sa, p_sp, v_act, v_ptr);
+  OFX_HIP(hipGetLastError());
+  h->act_called = kept;
   return OFX_OK;
 }
 

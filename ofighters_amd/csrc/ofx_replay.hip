@@ -40,6 +40,9 @@ struct ofx_replay {
   float *mass;             // [N][C] p^alpha, same ring positions as rows
   float *mmax;             // [N] running maximum mass: what a new row gets
   float alpha, eps;
+  // actor-side initial priorities (ofx_replay_actor_priorities), null = off
+  float *prev_q;           // [N][M][2] (q_sa, p_sp) of each ship's previous_*, next to prev_iaction
+  float actor_gamma;
   // packed frame store (ofx_replay_create_packed), frame_bits is null then
   int32_t packed;
   uint32_t pool_pairs;     // per arena
@@ -62,7 +65,7 @@ void ofx_replay_free(ofx_handle *h) {
   void *ptrs[] = {r->frame_bits, r->frame_tick, r->rows, r->head, r->count, r->appended, r->has_prev, r->latched,
                   r->prev_iaction, r->prev_px, r->prev_py, r->prev_tick, r->prev_head, r->frame_head, r->cur_slot,
                   r->prev_slot, r->scan_off, r->mass, r->mmax, r->pool, r->frame_off, r->frame_cnt, r->pool_head, r->live,
-                  r->evicted, r->g_skip, r->g_v, r->g_voff, r->g_T, r->g_G, r->g_gs};
+                  r->evicted, r->g_skip, r->g_v, r->g_voff, r->g_T, r->g_G, r->g_gs, r->prev_q};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   delete r;
   h->replay = nullptr;
@@ -219,8 +222,14 @@ struct CaptureParams {
   ofx_state st;
   const uint8_t *mask;
   const int32_t *iaction, *ipointer;
+  const float *q_sa, *p_sp, *v_act, *v_ptr;  // [N][M] of ofx_replay_capture_valued, unread by the plain form
   ofx_replay r;
 };
+
+// PER mass of a row from its two signed TD errors (both finite): the write-backs and the valued capture share it
+__device__ __forceinline__ float per_mass(float e1, float e2, float eps, float alpha) {
+  return powf(fabsf(e1) + fabsf(e2) + eps, alpha);
+}
 
 // One 64-lane wave per arena, lane = ship.  QlearnIA.play (qlearnIA_V2.py:370-403) per capturing ship:
 //   if self.done: return                      -> nothing, not even previous_* changes
@@ -228,6 +237,10 @@ struct CaptureParams {
 //   if previous_*: remember(previous_obs, previous_action, previous_pointer, obs.reward, obs, obs.done)
 //   previous_* = obs, iaction, ipointer
 // Rows are appended in ship-index order (ballot prefix), exactly the deque's append order.
+// VALUED (ofx_replay_capture_valued): the same rows and frames; a completed row's mass comes from the actor's one-step TD
+// errors - k_dqn_targets' float32 arithmetic on (prev_q, this lock-step's maxima) - instead of the running maximum, which
+// stays the fallback for a non-finite error and is raised by one wave reduction (an arena is one wave: no atomics).
+template <bool VALUED>
 __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
   const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (a >= p.N) return;  // wave-uniform
@@ -259,6 +272,8 @@ __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
   const int n_new = __popcll(bal);
   const int pos = __popcll(bal & ((1ull << lane) - 1ull));
   const int head = p.r.head[a];
+  const float mm = VALUED ? p.r.mmax[a] : 0.f;  // as read before this lock-step's raises
+  float raised = 0.f;                           // masses are >= 0
   if (trans) {
     ofx_transition row;
     row.tick_prev = p.r.prev_tick[t];
@@ -274,7 +289,23 @@ __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
 #pragma unroll
     for (int k = 0; k < 8; k++) { row.head_prev[k] = p.r.prev_head[(size_t)t * 8 + k]; row.head_next[k] = hd[k]; }
     p.r.rows[(size_t)a * p.C + (head + pos) % p.C] = row;
-    if (p.r.mass) p.r.mass[(size_t)a * p.C + (head + pos) % p.C] = p.r.mmax[a];  // PER: a new row gets the running max
+    if (VALUED) {
+      float y1 = (float)reward, y2 = (float)reward;  // a done row never reads v_*
+      if (!done) {
+        y1 = (float)reward + p.r.actor_gamma * p.v_act[t];
+        y2 = (float)reward + p.r.actor_gamma * p.v_ptr[t];
+      }
+      const float e1 = p.r.prev_q[2 * (size_t)t] - y1, e2 = p.r.prev_q[2 * (size_t)t + 1] - y2;
+      float m = mm;
+      if (isfinite(e1) && isfinite(e2)) raised = m = per_mass(e1, e2, p.r.eps, p.r.alpha);
+      p.r.mass[(size_t)a * p.C + (head + pos) % p.C] = m;
+    } else if (p.r.mass) {
+      p.r.mass[(size_t)a * p.C + (head + pos) % p.C] = p.r.mmax[a];  // PER: a new row gets the running max
+    }
+  }
+  if (VALUED) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) raised = fmaxf(raised, __shfl_xor(raised, o));
   }
   if (plays) {
     if (done) p.r.latched[t] = 1;
@@ -286,8 +317,13 @@ __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
     p.r.prev_py[t] = p.ipointer[2 * t + 1];
 #pragma unroll
     for (int k = 0; k < 8; k++) p.r.prev_head[(size_t)t * 8 + k] = hd[k];
+    if (VALUED) {
+      p.r.prev_q[2 * (size_t)t] = p.q_sa[t];
+      p.r.prev_q[2 * (size_t)t + 1] = p.p_sp[t];
+    }
   }
   if (lane == 0 && n_new) {
+    if (VALUED) p.r.mmax[a] = fmaxf(mm, raised);
     p.r.head[a] = (head + n_new) % p.C;
     p.r.count[a] = min(p.r.count[a] + n_new, p.C);
     p.r.appended[a] += n_new;
@@ -394,14 +430,14 @@ __global__ __launch_bounds__(256) void k_replay_frames_packed(int N, int F, int 
   }
 }
 
-extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
-                                  const int32_t *ipointer) {
-  if (!h) { ofx_set_error("ofx_replay_capture: null handle"); return OFX_ERR_INVALID; }
+// ofx_replay_capture (q_sa null) and ofx_replay_capture_valued (the four value arrays given)
+static int replay_capture(ofx_handle *h, const char *who, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
+                          const int32_t *ipointer, const float *q_sa, const float *p_sp, const float *v_act,
+                          const float *v_ptr) {
   ofx_replay *r = h->replay;
-  if (!r) { ofx_set_error("ofx_replay_capture before ofx_replay_create"); return OFX_ERR_STATE; }
   if (!h->spawned) { ofx_set_error("You must execute analyse_battleground first."); return OFX_ERR_STATE; }
-  if ((int32_t)tick < 0) { ofx_set_error("ofx_replay_capture: tick must be < 2^31"); return OFX_ERR_INVALID; }
-  if (h->cfg.n_ships > OFX_WAVE) { ofx_set_error("ofx_replay_capture: n_ships > 64"); return OFX_ERR_INVALID; }
+  if ((int32_t)tick < 0) { ofx_set_error("%s: tick must be < 2^31", who); return OFX_ERR_INVALID; }
+  if (h->cfg.n_ships > OFX_WAVE) { ofx_set_error("%s: n_ships > 64", who); return OFX_ERR_INVALID; }
   OFX_HIP(hipSetDevice(h->cfg.device));
   int rc;
   int32_t *ria, *rip;  // null = the handle's results
@@ -414,7 +450,9 @@ extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *s
   p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height; p.C = r->capacity;
   p.F = r->frames;
   p.tick = (int)tick; p.st = h->st; p.mask = ship_mask; p.iaction = iaction; p.ipointer = ipointer; p.r = *r;
-  hipLaunchKernelGGL(k_replay_capture, dim3((p.N + 3) / 4), dim3(256), 0, h->stream, p);
+  p.q_sa = q_sa; p.p_sp = p_sp; p.v_act = v_act; p.v_ptr = v_ptr;
+  if (q_sa) hipLaunchKernelGGL(k_replay_capture<true>, dim3((p.N + 3) / 4), dim3(256), 0, h->stream, p);
+  else hipLaunchKernelGGL(k_replay_capture<false>, dim3((p.N + 3) / 4), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   if (r->packed)
     hipLaunchKernelGGL(k_replay_frames_packed, dim3((unsigned)p.N), dim3(256), 0, h->stream, p.N, r->frames, r->words,
@@ -424,6 +462,13 @@ extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *s
                        (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][0], (const uint32_t *)h->maps[OFX_MAP_BITS_LSB][1], *r);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
+}
+
+extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
+                                  const int32_t *ipointer) {
+  if (!h) { ofx_set_error("ofx_replay_capture: null handle"); return OFX_ERR_INVALID; }
+  if (!h->replay) { ofx_set_error("ofx_replay_capture before ofx_replay_create"); return OFX_ERR_STATE; }
+  return replay_capture(h, "ofx_replay_capture", tick, ship_mask, iaction, ipointer, nullptr, nullptr, nullptr, nullptr);
 }
 
 // first-seen deaths of the selected ships (QlearnIA.play's done latch, agents/qlearnIA_V2.py:376-384)
@@ -1025,7 +1070,7 @@ __global__ void k_replay_update_per(int N, int C, int batch, const int32_t *slot
     if (r.rows[pos].tick_prev != g.tick_prev || r.rows[pos].ship != g.ship) continue;  // overwritten since sampling
     const float e1 = td[2 * (size_t)d], e2 = td[2 * (size_t)d + 1];
     if (!isfinite(e1) || !isfinite(e2)) continue;
-    const float m = powf(fabsf(e1) + fabsf(e2) + r.eps, r.alpha);
+    const float m = per_mass(e1, e2, r.eps, r.alpha);
     r.mass[pos] = m;
     mx = fmaxf(mx, m);
   }
@@ -1070,6 +1115,71 @@ extern "C" int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *m
   if (n1 > 0) OFX_HIP(hipMemcpy(mass_host, base + first, sizeof(float) * n1, hipMemcpyDeviceToHost));
   if (count > n1) OFX_HIP(hipMemcpy(mass_host + n1, base, sizeof(float) * (count - n1), hipMemcpyDeviceToHost));
   *n_host = count;
+  return OFX_OK;
+}
+
+// ---- actor-side initial priorities (Horgan et al. 2018; include/ofx.h states the contract) ---------------------------
+static int actor_ready(ofx_handle *h, const char *who) {
+  int rc;
+  if ((rc = per_ready(h, who))) return rc;
+  if (!h->replay->prev_q) { ofx_set_error("%s: actor priorities are off (ofx_replay_actor_priorities)", who); return OFX_ERR_STATE; }
+  return OFX_OK;
+}
+
+extern "C" int ofx_replay_actor_priorities(ofx_handle *h, float gamma) {
+  int rc;
+  if ((rc = per_ready(h, "ofx_replay_actor_priorities"))) return rc;
+  if (!(gamma >= 0.f && gamma <= 1.f)) {  // (NaN fails both)
+    ofx_set_error("ofx_replay_actor_priorities: gamma must lie in [0, 1], got %g", (double)gamma);
+    return OFX_ERR_INVALID;
+  }
+  ofx_replay *r = h->replay;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  const size_t T = (size_t)h->cfg.n_arenas * h->cfg.n_ships;
+  if (!r->prev_q) OFX_HIP(hipMalloc((void **)&r->prev_q, sizeof(float) * 2 * T));
+  OFX_HIP(hipMemset(r->prev_q, 0, sizeof(float) * 2 * T));
+  OFX_HIP(hipDeviceSynchronize());  // null-stream fill vs the handle's non-blocking stream
+  r->actor_gamma = gamma;
+  return OFX_OK;
+}
+
+extern "C" int ofx_replay_capture_valued(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
+                                         const int32_t *ipointer, const float *q_sa, const float *p_sp, const float *v_act,
+                                         const float *v_ptr) {
+  if (!h) { ofx_set_error("ofx_replay_capture_valued: null handle"); return OFX_ERR_INVALID; }
+  int rc;
+  if ((rc = actor_ready(h, "ofx_replay_capture_valued"))) return rc;
+  const int given = (q_sa != nullptr) + (p_sp != nullptr) + (v_act != nullptr) + (v_ptr != nullptr);
+  if (given != 0 && given != 4) {
+    ofx_set_error("ofx_replay_capture_valued: pass all of q_sa, p_sp, v_act, v_ptr or none (the last ofx_policy_act's)");
+    return OFX_ERR_INVALID;
+  }
+  if (!given && ofx_policy_act_values(h, &q_sa, &p_sp, &v_act, &v_ptr)) {
+    ofx_set_error("ofx_replay_capture_valued: no values given and the handle holds none (the last ofx_policy_act must have had all four outputs NULL)");
+    return OFX_ERR_STATE;
+  }
+  return replay_capture(h, "ofx_replay_capture_valued", tick, ship_mask, iaction, ipointer, q_sa, p_sp, v_act, v_ptr);
+}
+
+// prev_q crosses to the host on its own, so that the replay blob keeps its format
+extern "C" int ofx_replay_actor_values_host(ofx_handle *h, float *dst_host) {
+  int rc;
+  if ((rc = actor_ready(h, "ofx_replay_actor_values_host"))) return rc;
+  if (!dst_host) { ofx_set_error("ofx_replay_actor_values_host: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  OFX_HIP(hipMemcpy(dst_host, h->replay->prev_q, sizeof(float) * 2 * (size_t)h->cfg.n_arenas * h->cfg.n_ships, hipMemcpyDeviceToHost));
+  return OFX_OK;
+}
+
+extern "C" int ofx_replay_set_actor_values(ofx_handle *h, const float *src_host) {
+  int rc;
+  if ((rc = actor_ready(h, "ofx_replay_set_actor_values"))) return rc;
+  if (!src_host) { ofx_set_error("ofx_replay_set_actor_values: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  OFX_HIP(hipMemcpy(h->replay->prev_q, src_host, sizeof(float) * 2 * (size_t)h->cfg.n_arenas * h->cfg.n_ships, hipMemcpyHostToDevice));
   return OFX_OK;
 }
 
@@ -1420,7 +1530,7 @@ __global__ __launch_bounds__(256) void k_replay_update_list(int N, int C, int n,
   const int a = arena[j], s = slot[j];
   size_t pos;
   if (!list_entry_lands(r, N, C, a, s, rows[j], td, j, &pos)) return;
-  const float m = powf(fabsf(td[2 * (size_t)j]) + fabsf(td[2 * (size_t)j + 1]) + r.eps, r.alpha);
+  const float m = per_mass(td[2 * (size_t)j], td[2 * (size_t)j + 1], r.eps, r.alpha);
   atomicMax(reinterpret_cast<unsigned int *>(r.mmax + a), __float_as_uint(m));  // masses are >= 0: the bit patterns order like the values
   for (int k = j + 1; k < n && arena[k] == a && slot[k] == s; k++) {
     size_t other;

@@ -564,6 +564,43 @@ class ArenaBatch:
         nat.check(nat.lib().ofx_replay_priorities_host(self._h, int(arena), m.ctypes.data_as(C.c_void_p), C.byref(n)))
         return m[:n.value]
 
+    # ------------------------------------------------------------ actor-side initial priorities (include/ofx.h: the contract)
+    def policy_act(self, weights_ptr, epsilon, seed, tick=None, collecting=False, ship_mask_ptr=None, q_sa_ptr=None,
+                   p_sp_ptr=None, v_act_ptr=None, v_ptr_ptr=None):
+        """policy_forward + policy_explore in one call (the handle keeps iaction / ipointer, bit for bit those of the
+        two calls), with the values of what was chosen into float32 [N][M] device arrays: q_sa = act_values[iaction],
+        p_sp = the heat map at the chosen pointer, v_act = max(act_values), v_ptr = max(heat map).  None: kept by the
+        handle for replay_capture_valued.  Does not synchronise."""
+        nat.check(nat.lib().ofx_policy_act(self._h, weights_ptr, ship_mask_ptr, float(epsilon), seed,
+                                           self.tick if tick is None else tick, int(bool(collecting)), q_sa_ptr, p_sp_ptr,
+                                           v_act_ptr, v_ptr_ptr))
+
+    def replay_actor_priorities(self, gamma):
+        """Enable actor-side initial priorities on a prioritized memory: replay_capture_valued then gives every new
+        row the mass of its one-step TD error under `gamma` instead of the arena's running maximum."""
+        nat.check(nat.lib().ofx_replay_actor_priorities(self._h, float(gamma)))
+
+    def replay_capture_valued(self, tick, ship_mask_ptr=None, iaction_ptr=None, ipointer_ptr=None, q_sa_ptr=None,
+                              p_sp_ptr=None, v_act_ptr=None, v_ptr_ptr=None):
+        """replay_capture with the values of this lock-step's choice (all four None: the handle's from the last
+        policy_act, else all four given); call before step()."""
+        nat.check(nat.lib().ofx_replay_capture_valued(self._h, int(tick), ship_mask_ptr, iaction_ptr, ipointer_ptr, q_sa_ptr,
+                                                      p_sp_ptr, v_act_ptr, v_ptr_ptr))
+
+    def replay_actor_values(self):
+        """(q_sa, p_sp) of every ship's previous_*, float32 [N][M][2]: what a checkpoint carries next to the replay blob."""
+        v = np.empty((self.N, self.M, 2), np.float32)
+        nat.check(nat.lib().ofx_replay_actor_values_host(self._h, v.ctypes.data_as(C.c_void_p)))
+        return v
+
+    def set_replay_actor_values(self, values):
+        a = np.asarray(values)
+        if a.dtype != np.float32 or a.shape != (self.N, self.M, 2):
+            raise ValueError("ArenaBatch.set_replay_actor_values: float32 [%d][%d][2] expected, got %s %s"
+                             % (self.N, self.M, a.dtype, a.shape))
+        a = np.ascontiguousarray(a)
+        nat.check(nat.lib().ofx_replay_set_actor_values(self._h, a.ctypes.data_as(C.c_void_p)))
+
     # ------------------------------------------------------------ global minibatch sampling (include/ofx.h: the contract)
     def replay_sample_global(self, seed, draw, n_rows, prioritized=False, beta=0.0, arena=None, slot=None, is_weight=None):
         """n_rows rows from the union of all arenas' memories: uniform over rows without replacement, or (prioritized)

@@ -113,6 +113,8 @@ class TrainingRollout(ShardedRollout):
         scripted bots for the other ships                                      agent.py:99-155
         forward on the trainer's (pinned) weights -> epsilon-greedy / the      :397, :199-235
           collecting phase's random play (first `collecting_steps` steps)      :393-395
+          (trainer.actor_priorities: one call that also returns the values of the choice; the capture below
+          turns them into the new rows' priorities - same actions, same rows)
         transition capture (remember previous_obs ... obs, done latch)         :388-391, :401-403
         action packing, step, rasterise                                        :447-454, battleground.py:153-166
         epsilon decay (once per lock-step: "all bots share the same trainer")  :398-400
@@ -217,9 +219,15 @@ class TrainingRollout(ShardedRollout):
             if e.agents_first_done(m, self._seen_done) > 0:
                 self._replay()
                 replayed = True
-        e.policy_forward(t.weights.ptr, m)
-        e.policy_explore(t.epsilon.get(), self.seed, tick=self.capture_tick, collecting=collecting, ship_mask_ptr=m)
-        e.replay_capture(self.capture_tick, ship_mask_ptr=m)
+        if getattr(t, "actor_priorities", False):      # (a duck-typed trainer that predates the option has none)
+            # the same choice in one call, with its values; the capture turns them into the new rows' priorities
+            e.policy_act(t.weights.ptr, t.epsilon.get(), self.seed, tick=self.capture_tick, collecting=collecting,
+                         ship_mask_ptr=m)
+            e.replay_capture_valued(self.capture_tick, ship_mask_ptr=m)
+        else:
+            e.policy_forward(t.weights.ptr, m)
+            e.policy_explore(t.epsilon.get(), self.seed, tick=self.capture_tick, collecting=collecting, ship_mask_ptr=m)
+            e.replay_capture(self.capture_tick, ship_mask_ptr=m)
         e.policy_actions(ship_mask_ptr=m)
         self.capture_tick += 1
         if not collecting and self.is_learning:

@@ -75,6 +75,19 @@ a hook set the step goes through ofx_dqn_grad + ofx_dqn_apply also at accumulate
 every textbook replay path.  fingerprint() carries "accumulate": k only when k > 1; the accumulator is scratch inside
 one replay(), so a checkpoint needs nothing new.
 
+`actor_priorities=True` (opt-in, not in the reference; Horgan et al. 2018, Ape-X; needs `prioritized`, refused with
+reference_quirks, the value must be a bool: ValueError naming actor_priorities before anything is allocated) gives every
+new row the priority of the TD error the actor can form itself instead of the arena's running maximum.  At training sizes
+(thousands of arenas, one replay per lock-step at the most) nearly every row leaves the memory without ever being fitted,
+so under the running-maximum rule the sampler draws almost uniformly over rows that all carry the same mass.
+TrainingRollout then plays through ofx_policy_act, which returns Q(s, a) and the heat map's value at the chosen pointer
+next to both heads' maxima, and captures through ofx_replay_capture_valued, which forms the two errors of a row the
+moment its next state is seen.  Three things to know: the initial priority is the ONE-STEP error, also with n_step > 1;
+it is formed with the ONLINE blob in inference mode - a target network and double_dqn do not enter; and the first
+write-back replaces it with the learner's error, as before.  The actions played and the rows stored do not change.
+fingerprint() carries "actor_priorities": True only when it is on; a checkpoint gains the section
+`replay_actor_values` (the ships' previous values), the replay blob keeps its format.
+
 save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
 (`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
 cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
@@ -118,14 +131,22 @@ class _At:
 class DeviceTrainer:
     global_sampling = False                                  # the opt-in of __init__; off on any trainer that never set it
     accumulate = 1                                           # likewise: micro-batches per fit step
+    actor_priorities = False                                 # likewise: new rows enter at the actor's own TD error
     grad_hook = None                                         # hook(trainer, acc_buffer) before ofx_dqn_apply; see above
 
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
                  per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
                  huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0, global_sampling=False,
-                 accumulate=1):
+                 accumulate=1, actor_priorities=False):
         memory_pool_pairs = check_pool_pairs("DeviceTrainer: memory_pool_pairs", packed_memory, memory_pool_pairs)
+        if not isinstance(actor_priorities, (bool, np.bool_)):
+            raise ValueError("DeviceTrainer: actor_priorities must be a bool, got %r" % (actor_priorities,))
+        if actor_priorities and not prioritized:
+            raise ValueError("DeviceTrainer: actor_priorities needs prioritized=True (it sets the priority a new row "
+                             "enters the memory with)")
+        if actor_priorities and reference_quirks:
+            raise ValueError("DeviceTrainer: actor_priorities needs the textbook fit (reference_quirks=False)")
         if not isinstance(global_sampling, (bool, np.bool_)):
             raise ValueError("DeviceTrainer: global_sampling must be a bool, got %r" % (global_sampling,))
         if isinstance(accumulate, (bool, np.bool_)) or not isinstance(accumulate, (int, np.integer)) or accumulate < 1:
@@ -198,12 +219,15 @@ class DeviceTrainer:
         self.memory_pool_pairs = memory_pool_pairs           # pairs per arena of the packed store (0: the library's default)
         self.global_sampling = bool(global_sampling)         # one minibatch of fit_batch rows from all arenas' memories
         self.accumulate = int(accumulate)                    # micro-batches of fit_batch rows per fit step
+        self.actor_priorities = bool(actor_priorities)       # a new row's mass: the actor's one-step TD error
         if self.packed_memory:
             batch.replay_create(memory_size, frames, packed=True, pool_pairs=memory_pool_pairs)
         else:
             batch.replay_create(memory_size, frames)
         if self.prioritized:
             batch.replay_prioritize(per_alpha, per_eps)
+        if self.actor_priorities:
+            batch.replay_actor_priorities(self.gamma)
 
     def _scratch(self, name, nbytes):
         """A device buffer of at least nbytes that lives as long as the trainer: no hipMalloc / hipFree per replay."""
@@ -258,6 +282,8 @@ class DeviceTrainer:
             fp["global_sampling"] = True                     # and fingerprint_diff counts the missing key as a difference
         if self.accumulate > 1:                              # the same pattern
             fp["accumulate"] = self.accumulate
+        if self.actor_priorities:
+            fp["actor_priorities"] = True
         return fp
 
     def state_dict(self):
