@@ -253,6 +253,14 @@ int ofx_overflow_count(ofx_handle *h, int64_t *count_host);
  * scores.append(score), agents/agent.py:61-63) and, last, the arena count.
  * The caller all-reduces it (RCCL via torch.distributed).                    */
 int ofx_episode_scores(ofx_handle *h, int64_t *sums);
+/* The same per group of arenas (opt-in: the score of each rung of an exploration ladder, or of the greedy evaluation
+ * arenas, next to the shard's total).  group: DEVICE int32 [N], the group of every local arena; sums: DEVICE int64
+ * [n_groups][M+1]: sums[g][i] = the sum of OFX_F_LAST_SCORES[a][i] over the local arenas with group[a] == g, and
+ * sums[g][M] = the number of those arenas.  group[a] == -1 leaves arena a out; a value outside [-1, n_groups) is
+ * ignored like -1.  Integer sums: exact in any summation order, so with every arena in a group the sum over g equals
+ * ofx_episode_scores.  Enqueued on the handle's stream, does not synchronise.  OFX_ERR_INVALID: a NULL pointer,
+ * n_groups < 1 or n_groups > N.                                                                                    */
+int ofx_episode_scores_grouped(ofx_handle *h, const int32_t *group, int32_t n_groups, int64_t *sums);
 /* The same followed by the all-reduce itself, for a host that is not torch: ncclAllReduce(sum, int64, in place) of the
  * [M+1] vector over the ranks of `nccl_comm` - an ncclComm_t the caller made with ncclCommInitRank, one rank per GPU
  * (RCCL over xGMI) - enqueued on the handle's stream.  libofx.so does not link RCCL; the symbol is resolved in the
@@ -354,6 +362,21 @@ int ofx_set_option(ofx_handle *h, int32_t option, int32_t value);
  * ofx_policy_forward / ofx_policy_explore.                                                                     */
 int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, uint32_t tick, int32_t collecting,
                        const uint8_t *ship_mask, int32_t *iaction, int32_t *ipointer);
+/* Opt-in exploration ladder (Horgan et al. 2018, Ape-X: every actor explores at its own rate; here an arena is an
+ * actor).  expo_host: HOST double [N], one exponent per local arena, copied into a handle-owned device array
+ * (ofx_destroy frees it); NULL removes the ladder and the behaviour is exactly that without one.  Each value must be
+ * >= 0 or +INFINITY: a NaN or a negative value returns OFX_ERR_INVALID and changes nothing.  A set-up call: it
+ * synchronises.  While a ladder is set, a ship of local arena a explores in ofx_policy_explore / ofx_policy_act iff
+ * `collecting || u <= eps_a` with
+ *   expo[a] == +inf   never - a greedy (evaluation) arena; `collecting` is ignored for it, and in ofx_policy_act its
+ *                     ships get p_sp = v_ptr
+ *   expo[a] == 1      eps_a = epsilon, bit for bit (no pow)
+ *   otherwise         eps_a = pow(epsilon, expo[a]) in float64; pow(x, 0) = 1, so exponent 0 always explores
+ * The Philox words, u and the random play (iaction, ipointer) drawn from them are those of the scalar rule: only
+ * WHETHER a ship explores changes.  The checks of `epsilon` stay as they are.
+ * ofx_policy_epsilon_ladder_host reads the exponents back into HOST double [N]; OFX_ERR_STATE while no ladder is set. */
+int ofx_policy_epsilon_ladder(ofx_handle *h, const double *expo_host);
+int ofx_policy_epsilon_ladder_host(ofx_handle *h, double *dst_host);
 /* ofx_policy_forward and ofx_policy_explore in one call, with the values of what was chosen (opt-in; the input of the
  * actor-side initial priorities below).  Afterwards the handle-kept (iaction, ipointer) are bit for bit those of
  * ofx_policy_forward(h, weights, ship_mask, NULL, NULL, NULL, NULL) followed by ofx_policy_explore(h, epsilon, seed,

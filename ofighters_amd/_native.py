@@ -107,6 +107,7 @@ SIGNATURES = {
     "ofx_map_desc": (_i, [_vp, _i, _i, C.POINTER(OfxTensorDesc)]),
     "ofx_overflow_count": (_i, [_vp, C.POINTER(C.c_int64)]),
     "ofx_episode_scores": (_i, [_vp, _vp]),
+    "ofx_episode_scores_grouped": (_i, [_vp, _vp, C.c_int32, _vp]),
     "ofx_scores_allreduce": (_i, [_vp, _vp, _vp]),
     "ofx_scratch_feed": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "ofx_scratch_feed_obs": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
@@ -114,6 +115,8 @@ SIGNATURES = {
     "ofx_policy_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_actions": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_explore": (_i, [_vp, C.c_double, _u64, _u32, C.c_int32, _vp, _vp, _vp]),
+    "ofx_policy_epsilon_ladder": (_i, [_vp, _vp]),
+    "ofx_policy_epsilon_ladder_host": (_i, [_vp, _vp]),
     "ofx_policy_act": (_i, [_vp, _vp, _vp, C.c_double, _u64, _u32, C.c_int32, _vp, _vp, _vp, _vp]),
     "ofx_policy_forward_obs": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_targets": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),

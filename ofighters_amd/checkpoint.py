@@ -6,7 +6,8 @@ counter, and a fit is reproducible to the bit, so nothing else is hidden):
 
     the manifest     format version; N, M, W, H, arena_base; the trainer's and the rollout's fingerprints (the arguments
                      that must match at restore); the rollout's counters; the index of the sections
-    rollout/*        losses, epsilons, score_log, the `_seen_done` latch
+    rollout/*        losses, epsilons, score_log, the `_seen_done` latch; rung_log only under an exploration ladder or
+                     evaluation arenas (the ladder itself is re-derived by the constructor from the fingerprint's arguments)
     arena/<field>    the 19 state fields of the arenas (ArenaBatch.state_dict)
     trainer/*        weights, Adam m and v, the target blob, the loss and gradient-norm lists (DeviceTrainer.state_dict)
     replay/<k>       the replay memory as ofx_replay_export blobs of consecutive arena chunks, each chosen from
@@ -122,10 +123,14 @@ def _plain(v):
 
 def rollout_fingerprint(r):
     """The TrainingRollout arguments a restored run must have been built with."""
-    return {"policy_ships": sorted(int(i) for i in np.flatnonzero(np.asarray(r.policy_mask)[0])),
-            "behaviours": _plain(r.behaviours), "seed": int(r.seed), "episode_ticks": int(r.episode_ticks),
-            "collecting_steps": _plain(r.collecting_steps), "replay_every": _plain(r.replay_every),
-            "replay_on_death": bool(r.replay_on_death), "is_learning": bool(r.is_learning)}
+    fp = {"policy_ships": sorted(int(i) for i in np.flatnonzero(np.asarray(r.policy_mask)[0])),
+          "behaviours": _plain(r.behaviours), "seed": int(r.seed), "episode_ticks": int(r.episode_ticks),
+          "collecting_steps": _plain(r.collecting_steps), "replay_every": _plain(r.replay_every),
+          "replay_on_death": bool(r.replay_on_death), "is_learning": bool(r.is_learning)}
+    if getattr(r, "ladder_on", False):                   # only when on: a default rollout's key set stays as it was
+        fp.update(epsilon_ladder=r.epsilon_ladder, eval_arenas=int(r.eval_arenas), total_arenas=int(r.total_arenas),
+                  score_bands=int(r.score_bands))
+    return fp
 
 
 def dims(engine):
@@ -166,6 +171,9 @@ def save(rollout, path, chunk_bytes=None):
         w.add("rollout/epsilons", np.array(rollout.epsilons, np.float64))
         w.add("rollout/score_log", np.array(rollout.score_log, np.int64).reshape(len(rollout.score_log), e.M + 1))
         w.add("rollout/seen_done", rollout._seen_done.download(np.uint8, (e.N, e.M)))
+        if getattr(rollout, "ladder_on", False):
+            w.add("rollout/rung_log", np.array(rollout.rung_log, np.int64).reshape(len(rollout.rung_log), rollout.n_groups,
+                                                                                   e.M + 1))
         for name, a in es.items():
             if name not in ("episode", "tick"):
                 w.add("arena/" + name, a)
@@ -225,6 +233,8 @@ def load(rollout, path):
     rollout.losses = [float(x) for x in rd.array("rollout/losses")]
     rollout.epsilons = [float(x) for x in rd.array("rollout/epsilons")]
     rollout.score_log = [row.copy() for row in rd.array("rollout/score_log")]
+    if getattr(rollout, "ladder_on", False):                           # (the fingerprints agree: the section is there)
+        rollout.rung_log = [g.copy() for g in rd.array("rollout/rung_log")]
     e.sync()
     rollout._seen_done.upload(rd.array("rollout/seen_done"))
     e.policy_pin_weights(t.weights.ptr)             # the blob changed under the pin: prepare it again

@@ -165,7 +165,7 @@ extern "C" int ofx_destroy(ofx_handle *h) {
   ofx_state &s = h->st;
   void *ptrs[] = {s.ship_x, s.ship_y, s.ship_px, s.ship_py, s.hull, s.reward, s.score, s.obs_reward, s.last_score,
                   s.alive, s.killer, s.time, s.n_lasers, s.laser_x, s.laser_y, s.laser_dx, s.laser_dy,
-                  s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->res_iaction, h->fitws, h->fitws2, h->applyws, h->trunk_stat, h->act_vals};
+                  s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->res_iaction, h->fitws, h->fitws2, h->applyws, h->trunk_stat, h->act_vals, h->eps_expo};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (int t = 0; t < 5; t++) for (int w = 0; w < 2; w++) if (h->maps[t][w]) (void)hipFree(h->maps[t][w]);
   if (h->events) { (void)hipEventDestroy(h->ev0); (void)hipEventDestroy(h->ev1); }
@@ -652,6 +652,41 @@ extern "C" int ofx_episode_scores(ofx_handle *h, int64_t *sums) {
   OFX_HIP(hipSetDevice(h->cfg.device));
   OFX_HIP(hipMemcpyAsync(sums, h->st.episode_sums, sizeof(int64_t) * (h->cfg.n_ships + 1), hipMemcpyDeviceToDevice,
                          h->stream));
+  return OFX_OK;
+}
+
+// Per-group sums of the banked scores: block g walks the arenas, a thread per arena, and adds the rows of the arenas
+// with group[a] == g into the block's LDS accumulators (integers: exact in any order).  No global atomics and no
+// zero fill: every block writes its whole row of `sums`.  A group value no block stands for is never matched.
+__global__ void k_scores_grouped(int N, int M, const int32_t *last_score, const int32_t *group, long long *sums) {
+  __shared__ unsigned long long acc[65];  // n_ships <= 64 (ofx_create), then the arena count
+  const int g = blockIdx.x;
+  for (int i = threadIdx.x; i <= M; i += blockDim.x) acc[i] = 0ull;
+  __syncthreads();
+  for (int a = threadIdx.x; a < N; a += blockDim.x) {
+    if (group[a] != g) continue;
+    const int32_t *row = last_score + (size_t)a * M;
+    for (int k = 0; k < M; k++) {
+      int i = k + (int)(threadIdx.x & 63);  // lanes of a wave start at different slots: fewer same-address adds
+      i %= M;
+      atomicAdd(&acc[i], (unsigned long long)(long long)row[i]);
+    }
+    atomicAdd(&acc[M], 1ull);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i <= M; i += blockDim.x) sums[(size_t)g * (M + 1) + i] = (long long)acc[i];
+}
+
+extern "C" int ofx_episode_scores_grouped(ofx_handle *h, const int32_t *group, int32_t n_groups, int64_t *sums) {
+  if (!h || !group || !sums) { ofx_set_error("ofx_episode_scores_grouped: null argument"); return OFX_ERR_INVALID; }
+  if (n_groups < 1 || n_groups > h->cfg.n_arenas) {
+    ofx_set_error("ofx_episode_scores_grouped: n_groups must be in [1, %d] (got %d)", h->cfg.n_arenas, n_groups);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  hipLaunchKernelGGL(k_scores_grouped, dim3(n_groups), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
+                     h->st.last_score, group, (long long *)sums);
+  OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
 

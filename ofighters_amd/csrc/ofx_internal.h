@@ -86,6 +86,7 @@ struct ofx_handle {
   // forward's results they are selected from and the pre-drawn exploration
   float *act_vals;                 // [4][N*M] q_sa, p_sp, v_act, v_ptr, then act [N*M][2], ptr_max [N*M], ptr_probe [N*M]
   bool act_called;                 // the LAST ofx_policy_act wrote all four of the handle's arrays (all outputs NULL)
+  double *eps_expo;                // [N] ofx_policy_epsilon_ladder: arena a explores at epsilon^eps_expo[a] (+inf: never); null = no ladder
 };
 #define OFX_RING_MAX 65536         /* numbered events of ofx_event_record */
 

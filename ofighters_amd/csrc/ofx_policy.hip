@@ -788,24 +788,33 @@ int ofx_policy_predict_obs(ofx_handle *h, const float *weights, int32_t n_obs, c
 // The draw of ship i of arena a at `tick`: true when the ship explores, i.e. random_play() replaces its greedy choice
 // (np.random.rand() <= epsilon, qlearnIA_V2.py:201, or the collecting phase).  The Philox words exist either way, so
 // (*ia, *px, *py) is a valid random choice for every ship - ofx_policy_act probes the heat map there before it knows.
-__device__ __forceinline__ bool explore_draw(int a, int i, int W, int H, int arena_base, double eps, uint32_t k0, uint32_t k1,
-                                             uint32_t tick, int collecting, int32_t *ia, int32_t *px, int32_t *py) {
+// `expo` (ofx_policy_epsilon_ladder, null = none) changes only WHETHER the ship explores: arena a explores at
+// epsilon^expo[a]; exponent 1 leaves epsilon as it is (no pow), +inf is a greedy arena that not even `collecting` moves.
+__device__ __forceinline__ bool explore_draw(int a, int i, int W, int H, int arena_base, double eps, const double *expo,
+                                             uint32_t k0, uint32_t k1, uint32_t tick, int collecting, int32_t *ia,
+                                             int32_t *px, int32_t *py) {
   uint32_t r[4];
   ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_EXPLORE, k0, k1, r);
   const double u = (double)r[0] * (1.0 / 4294967296.0);
   *ia = ofx_draw_int(r[1], 1);
   *px = ofx_draw_int(r[2], W - 1);
   *py = ofx_draw_int(r[3], H - 1);
+  if (expo) {
+    const double x = expo[a];
+    if (x == (double)INFINITY) return false;
+    if (x != 1.0) eps = pow(eps, x);   // float64; pow(x, 0) = 1: exponent 0 always explores
+  }
   return collecting || u <= eps;
 }
 
-__global__ void k_policy_explore(int N, int M, int W, int H, int arena_base, double eps, uint32_t k0, uint32_t k1,
-                                 uint32_t tick, int collecting, const uint8_t *mask, int32_t *iaction, int32_t *ipointer) {
+__global__ void k_policy_explore(int N, int M, int W, int H, int arena_base, double eps, const double *expo, uint32_t k0,
+                                 uint32_t k1, uint32_t tick, int collecting, const uint8_t *mask, int32_t *iaction,
+                                 int32_t *ipointer) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N * M || (mask && !mask[s])) return;
   const int a = s / M, i = s - a * M;
   int32_t ia, px, py;
-  if (explore_draw(a, i, W, H, arena_base, eps, k0, k1, tick, collecting, &ia, &px, &py)) {
+  if (explore_draw(a, i, W, H, arena_base, eps, expo, k0, k1, tick, collecting, &ia, &px, &py)) {
     iaction[s] = ia;
     ipointer[2 * s] = px;
     ipointer[2 * s + 1] = py;
@@ -825,9 +834,41 @@ extern "C" int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, 
   if (!ipointer) ipointer = rip;
   const int S = h->cfg.n_arenas * h->cfg.n_ships;
   hipLaunchKernelGGL(k_policy_explore, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
-                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), tick,
-                     collecting, ship_mask, iaction, ipointer);
+                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     tick, collecting, ship_mask, iaction, ipointer);
   OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ---- the exploration ladder: one exponent per local arena, kept by the handle (set-up calls: both synchronise)
+extern "C" int ofx_policy_epsilon_ladder(ofx_handle *h, const double *expo_host) {
+  if (!h) { ofx_set_error("ofx_policy_epsilon_ladder: null handle"); return OFX_ERR_INVALID; }
+  const int N = h->cfg.n_arenas;
+  if (expo_host)
+    for (int a = 0; a < N; a++)
+      if (!(expo_host[a] >= 0.0)) {  // NaN fails the comparison too; +inf passes
+        ofx_set_error("ofx_policy_epsilon_ladder: exponent %d is %g; each must be >= 0 (+inf = a greedy arena)", a, expo_host[a]);
+        return OFX_ERR_INVALID;
+      }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));  // a kernel in flight may still read the old ladder
+  if (!expo_host) {
+    if (h->eps_expo) OFX_HIP(hipFree(h->eps_expo));
+    h->eps_expo = nullptr;
+    return OFX_OK;
+  }
+  if (!h->eps_expo) OFX_HIP(hipMalloc((void **)&h->eps_expo, sizeof(double) * N));
+  OFX_HIP(hipMemcpy(h->eps_expo, expo_host, sizeof(double) * N, hipMemcpyHostToDevice));
+  OFX_HIP(hipDeviceSynchronize());  // the copy from pageable memory is not ordered with the handle's non-blocking stream
+  return OFX_OK;
+}
+
+extern "C" int ofx_policy_epsilon_ladder_host(ofx_handle *h, double *dst_host) {
+  if (!h || !dst_host) { ofx_set_error("ofx_policy_epsilon_ladder_host: null argument"); return OFX_ERR_INVALID; }
+  if (!h->eps_expo) { ofx_set_error("ofx_policy_epsilon_ladder_host: no ladder is set"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  OFX_HIP(hipMemcpy(dst_host, h->eps_expo, sizeof(double) * h->cfg.n_arenas, hipMemcpyDeviceToHost));
   return OFX_OK;
 }
 
@@ -836,9 +877,9 @@ extern "C" int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, 
 // kernel as its probe: the heat map's value at an exploratory pointer leaves the same pass that finds the maximum.
 // Everything is addressed by ship index s = a * M + i (a masked forward walks the compacted list, but hd_ship maps
 // every work item back to s before it reads the probe or writes a result).
-__global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, double eps, uint32_t k0, uint32_t k1,
-                                 uint32_t tick, int collecting, const uint8_t *mask, uint8_t *explores, int32_t *draw_ia,
-                                 int32_t *probe) {
+__global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, double eps, const double *expo, uint32_t k0,
+                                 uint32_t k1, uint32_t tick, int collecting, const uint8_t *mask, uint8_t *explores,
+                                 int32_t *draw_ia, int32_t *probe) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N * M) return;
   if (mask && !mask[s]) {  // never read by the head, but never left uninitialised either
@@ -847,7 +888,7 @@ __global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, dou
   }
   const int a = s / M, i = s - a * M;
   int32_t ia, px, py;
-  explores[s] = explore_draw(a, i, W, H, arena_base, eps, k0, k1, tick, collecting, &ia, &px, &py) ? 1 : 0;
+  explores[s] = explore_draw(a, i, W, H, arena_base, eps, expo, k0, k1, tick, collecting, &ia, &px, &py) ? 1 : 0;
   draw_ia[s] = ia;
   probe[2 * s] = px;
   probe[2 * s + 1] = py;
@@ -908,8 +949,8 @@ extern "C" int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t
   if (!v_act) v_act = f + 2 * (size_t)S;
   if (!v_ptr) v_ptr = f + 3 * (size_t)S;
   hipLaunchKernelGGL(k_policy_predraw, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
-                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, (uint32_t)seed, (uint32_t)(seed >> 32), tick,
-                     collecting, ship_mask, explores, draw_ia, probe);
+                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     tick, collecting, ship_mask, explores, draw_ia, probe);
   OFX_HIP(hipGetLastError());
   ForwardArgs a{};
   a.weights = weights; a.ship_mask = ship_mask;

@@ -318,6 +318,15 @@ class ArenaBatch:
     def episode_scores_into(self, dev_ptr):
         nat.check(nat.lib().ofx_episode_scores(self._h, dev_ptr))
 
+    def episode_scores_grouped(self, group_buf, n_groups):
+        """int64 [n_groups][M+1]: episode_scores per group of arenas.  group_buf: DeviceBuffer, int32 [N], the group of
+        every local arena (-1, or any value outside [0, n_groups): not counted); the last column counts the arenas."""
+        n_groups = int(n_groups)
+        buf = DeviceBuffer(8 * max(1, n_groups) * (self.M + 1))
+        nat.check(nat.lib().ofx_episode_scores_grouped(self._h, group_buf.ptr, n_groups, buf.ptr))
+        self.sync()
+        return buf.download(np.int64, (n_groups, self.M + 1))
+
     # ------------------------------------------------------------------ timing
     def timer_start(self):
         nat.check(nat.lib().ofx_timer_start(self._h))
@@ -828,6 +837,25 @@ class ArenaBatch:
                                                    float(lr), int(n), rows_ptr, bits_prev_ptr, bits_next_ptr, float(gamma),
                                                    grad_buf.ptr if grad_buf else None, loss))
         return float(loss[0]), float(loss[1])
+
+    # ------------------------------------------------------------ exploration ladder (include/ofx.h: the contract)
+    def policy_epsilon_ladder(self, expo):
+        """One exploration exponent per local arena (float64 [N]; ofighters_amd.exploration.apex_exponents): arena a then
+        explores at epsilon ** expo[a] in policy_explore / policy_act, +inf = a greedy arena that never explores.  None
+        removes the ladder.  Synchronises."""
+        if expo is None:
+            nat.check(nat.lib().ofx_policy_epsilon_ladder(self._h, None))
+            return
+        a = np.ascontiguousarray(expo, dtype=np.float64)
+        if a.shape != (self.N,):
+            raise ValueError("ArenaBatch.policy_epsilon_ladder: float64 [%d] expected, got shape %s" % (self.N, a.shape))
+        nat.check(nat.lib().ofx_policy_epsilon_ladder(self._h, a.ctypes.data_as(C.c_void_p)))
+
+    def policy_epsilon_ladder_host(self):
+        """The exponents policy_epsilon_ladder set, float64 [N]; OfxError (OFX_ERR_STATE) while there is no ladder."""
+        a = np.empty(self.N, np.float64)
+        nat.check(nat.lib().ofx_policy_epsilon_ladder_host(self._h, a.ctypes.data_as(C.c_void_p)))
+        return a
 
     def policy_explore(self, epsilon, seed, tick=None, collecting=False, ship_mask_ptr=None, iaction_ptr=None,
                        ipointer_ptr=None):

@@ -135,6 +135,20 @@ class TrainingRollout(ShardedRollout):
     libofx re-prepares the pinned copy itself (ofx_dqn_fit -> ofx_policy_weights_updated), so the next forward plays
     with the new weights like Keras' shared model does.
 
+    Opt-in, not in the reference (ofighters_amd/exploration.py; Horgan et al. 2018, Ape-X): `epsilon_ladder=alpha` gives
+    every arena its own exploration rate, global arena g of the L learning arenas playing at
+    epsilon ** (1 + alpha * g / (L - 1)), and `eval_arenas=k` makes the last k global arenas of the run greedy: the forward
+    still plays them (under the full policy mask) on the current weights, but they never explore, and a second device
+    mask - the policy mask with those arenas zeroed - keeps them out of the capture (their memories stay empty: greedy
+    play is not the behaviour policy the learner samples) and out of the death count that triggers a replay.
+    `total_arenas` is the run's number of arenas over all shards (default: engine.N; a sharded run passes the world's
+    total, the ladder is keyed by engine.arena_base + a).  With either option on, every episode end also appends the
+    int64 [G][M+1] of engine.episode_scores_grouped to `rung_log` (all-reduced like score_log): the learning arenas in
+    `score_bands` contiguous bands by global id - clipped to the learning arenas and to the n_groups <= N one shard can
+    count - then, with eval_arenas, the evaluation group; `eval_scores` lists per episode the mean banked score of a
+    policy ship of an evaluation arena - the one number that shows whether the current weights play better.  eval_arenas
+    alone leaves every learning arena at exponent 1.  With both off, _play makes exactly the calls it always made.
+
     engine    ArenaBatch
     trainer   DeviceTrainer built on that engine (owns weights, Adam state, epsilon, the replay memory)
     policy_ships  ship slots driven by the policy (the stock line-up has ONE, lib/ofighters.py:53); the others
@@ -143,7 +157,23 @@ class TrainingRollout(ShardedRollout):
 
     def __init__(self, engine, trainer, behaviours, seed, policy_ships=(0,), is_learning=True, collecting_steps=20,
                  replay_every=50, replay_on_death=True, snapshot_every=50, snapshot_folder=None, checkpoint_every=0,
-                 checkpoint_folder=None, **kw):
+                 checkpoint_folder=None, epsilon_ladder=None, eval_arenas=0, total_arenas=None, score_bands=8, **kw):
+        from . import exploration
+        self.ladder_on = epsilon_ladder is not None or isinstance(eval_arenas, bool) or eval_arenas != 0
+        self.epsilon_ladder, self.eval_arenas = None, 0
+        if self.ladder_on:                         # every argument is checked before the first device call
+            total = engine.N if total_arenas is None else total_arenas
+            expo = exploration.apex_exponents(total, 0.0 if epsilon_ladder is None else epsilon_ladder, engine.arena_base,
+                                              engine.N, eval_arenas)
+            learning = int(total) - int(eval_arenas)
+            exploration._integer("score_bands", score_bands, 1)
+            bands = min(int(score_bands), learning, engine.N - (1 if eval_arenas else 0))
+            if bands < 1:
+                raise ValueError("eval_arenas needs at least 2 arenas per shard for the grouped scores, got %d" % engine.N)
+            groups = exploration.score_groups(total, engine.arena_base, engine.N, bands, eval_arenas)
+            self.epsilon_ladder = None if epsilon_ladder is None else float(epsilon_ladder)
+            self.eval_arenas, self.total_arenas, self.score_bands = int(eval_arenas), int(total), bands
+            self.n_groups = exploration.n_groups(bands, eval_arenas)
         super().__init__(engine, behaviours, seed, **kw)
         self.trainer = trainer
         self.is_learning = bool(is_learning)
@@ -165,6 +195,15 @@ class TrainingRollout(ShardedRollout):
         self.policy_mask = mk
         engine.sync()
         self._mask = DeviceBuffer(mk.nbytes).upload(mk)
+        self._learn_mask = self._mask              # what captures and counts deaths: the policy ships of learning arenas
+        self.rung_log = []                         # all-reduced [G][M+1] per finished episode (ladder / eval arenas only)
+        if self.ladder_on:
+            if self.eval_arenas:
+                lm = mk.copy()
+                lm[np.isinf(expo)] = 0
+                self._learn_mask = DeviceBuffer(lm.nbytes).upload(lm)
+            self._groups = DeviceBuffer(groups.nbytes).upload(groups)
+            engine.policy_epsilon_ladder(expo)
         self._zeros = np.zeros((engine.N, engine.M), np.uint8)
         self._seen_done = DeviceBuffer(mk.nbytes).upload(self._zeros)   # the agents' `done` latches, on the device
         engine.policy_pin_weights(trainer.weights.ptr)
@@ -175,6 +214,13 @@ class TrainingRollout(ShardedRollout):
         total = super()._episode_end()
         self.episode += 1
         self.epsilons.append(self.trainer.epsilon.get())
+        if self.ladder_on:
+            grouped = np.asarray(self.e.episode_scores_grouped(self._groups, self.n_groups), dtype=np.int64)
+            if self.dist is not None:
+                t = self.to_tensor(grouped.reshape(-1))
+                self.dist.all_reduce(t)
+                grouped = np.asarray(t.cpu().numpy() if hasattr(t, "cpu") else t, dtype=np.int64)
+            self.rung_log.append(grouped.reshape(self.n_groups, self.e.M + 1).copy())
         self.e.sync()
         self._seen_done.upload(self._zeros)         # QlearnIA.reset: done = False (:360-368)
         if (self.is_learning and self.snapshot_folder is not None and self.snapshot_every
@@ -202,6 +248,14 @@ class TrainingRollout(ShardedRollout):
         from . import checkpoint
         return checkpoint.load(self, path)
 
+    @property
+    def eval_scores(self):
+        """Per finished episode: the mean score a policy ship of an evaluation arena banked (empty without eval_arenas)."""
+        if not (self.ladder_on and self.eval_arenas):
+            return []
+        ships = np.flatnonzero(self.policy_mask[0])
+        return [float(g[-1][ships].sum()) / float(g[-1][-1] * len(ships)) for g in self.rung_log]
+
     def _replay(self):
         loss = self.trainer.replay()
         if loss is not None:
@@ -211,23 +265,23 @@ class TrainingRollout(ShardedRollout):
     def _play(self, e):
         """QlearnIA.play for every policy ship (the device keeps each agent's done latch and previous_*)."""
         self.total_steps += 1                      # Agent.step increments before bot_play (agent.py:67-68)
-        t, m = self.trainer, self._mask.ptr
+        t, m, lm = self.trainer, self._mask.ptr, self._learn_mask.ptr   # lm is m unless there are evaluation arenas
         collecting = self.total_steps < self.collecting_steps
         replayed = False
         if self.is_learning and self.replay_on_death:
             # obs.done seen for the first time this lock-step (:375-378): counted on the device, one int comes back
-            if e.agents_first_done(m, self._seen_done) > 0:
+            if e.agents_first_done(lm, self._seen_done) > 0:
                 self._replay()
                 replayed = True
         if getattr(t, "actor_priorities", False):      # (a duck-typed trainer that predates the option has none)
             # the same choice in one call, with its values; the capture turns them into the new rows' priorities
             e.policy_act(t.weights.ptr, t.epsilon.get(), self.seed, tick=self.capture_tick, collecting=collecting,
                          ship_mask_ptr=m)
-            e.replay_capture_valued(self.capture_tick, ship_mask_ptr=m)
+            e.replay_capture_valued(self.capture_tick, ship_mask_ptr=lm)
         else:
             e.policy_forward(t.weights.ptr, m)
             e.policy_explore(t.epsilon.get(), self.seed, tick=self.capture_tick, collecting=collecting, ship_mask_ptr=m)
-            e.replay_capture(self.capture_tick, ship_mask_ptr=m)
+            e.replay_capture(self.capture_tick, ship_mask_ptr=lm)
         e.policy_actions(ship_mask_ptr=m)
         self.capture_tick += 1
         if not collecting and self.is_learning:

@@ -50,7 +50,8 @@ def cost():
     dw = DeviceBuffer(w.nbytes).upload(w)
     mk = np.zeros((ARENAS, M), np.uint8)
     mk[:, 0] = 1
-    m = DeviceBuffer(mk.nbytes).upload(mk).ptr
+    m_buf = DeviceBuffer(mk.nbytes).upload(mk)               # kept: the pointer alone would outlive its buffer
+    m = m_buf.ptr
     b.policy_pin_weights(dw.ptr)
     tick = [0]
 
