@@ -654,20 +654,35 @@ struct GatherParams {
   uint32_t *bits_prev, *bits_next;  // [N][batch][2][words] or null
 };
 
+// n-step returns (ofx_replay_gather_nstep; include/ofx.h states the contract): chain length, discount and outputs
+struct NstepParams {
+  int nstep;
+  double gamma;
+  float *ret, *disc;  // [max_rows]
+};
+
+// The padding row of a gather (P: GatherParams or GatherListParams) at destination d: an all-zero row with ship = -1 and
+// empty maps (never uninitialised memory); NSTEP: ret = disc = 0 as well.  The whole workgroup calls it.
+template <bool NSTEP, typename P>
+__device__ __forceinline__ void gather_pad_row(const P &p, size_t d, const NstepParams &q) {
+  if (threadIdx.x < sizeof(ofx_transition) / 4) ((int32_t *)(p.rows + d))[threadIdx.x] = threadIdx.x == 4 ? -1 : 0;
+  uint32_t *pads[2] = {p.bits_prev, p.bits_next};
+  for (int w = 0; w < 2; w++) {
+    if (!pads[w]) continue;
+    uint4 *out = reinterpret_cast<uint4 *>(pads[w] + d * 2 * p.words);
+    for (int k = threadIdx.x; k < 2 * p.words / 4; k += 256) out[k] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  if (NSTEP && threadIdx.x == 0) { q.ret[d] = 0.f; q.disc[d] = 0.f; }
+}
+
 // one workgroup per (arena, j): row copy + the two frames' bit maps (16-byte loads/stores)
 template <bool PACKED>
 __global__ __launch_bounds__(256) void k_replay_gather(GatherParams p) {
   const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
   const int s = p.slot[(size_t)a * p.batch + j];
   ofx_transition *dst = p.rows + (size_t)a * p.batch + j;
-  if (s < 0) {  // padding: an all-zero row with ship = -1 and empty maps (never uninitialised memory)
-    if (threadIdx.x < sizeof(ofx_transition) / 4) ((int32_t *)dst)[threadIdx.x] = threadIdx.x == 4 ? -1 : 0;
-    uint32_t *pads[2] = {p.bits_prev, p.bits_next};
-    for (int w = 0; w < 2; w++) {
-      if (!pads[w]) continue;
-      uint4 *out = reinterpret_cast<uint4 *>(pads[w] + ((size_t)a * p.batch + j) * 2 * p.words);
-      for (int k = threadIdx.x; k < 2 * p.words / 4; k += 256) out[k] = make_uint4(0u, 0u, 0u, 0u);
-    }
+  if (s < 0) {
+    gather_pad_row<false>(p, (size_t)a * p.batch + j, NstepParams{});
     return;
   }
   const int count = p.r.count[a], head = p.r.head[a];
@@ -721,13 +736,6 @@ __global__ __launch_bounds__(1024) void k_replay_scan(int N, const In *n_sampled
   if (tid == 1023) off[N] = part[1023];
 }
 
-// n-step returns (ofx_replay_gather_nstep; include/ofx.h states the contract): chain length, discount and outputs
-struct NstepParams {
-  int nstep;
-  double gamma;
-  float *ret, *disc;  // [max_rows]
-};
-
 // Wave 0 of the workgroup: the n-step chain from oldest-first row s.  Per step the 64 lanes test 64 consecutive rows
 // after the current one; the lowest row of the same ship is the ship's next row in append order, and it is the
 // successor iff its tick_prev is the current row's tick_next (a ship's tick_prev values increase strictly; a restart
@@ -769,17 +777,12 @@ __device__ int nstep_chain(const ofx_transition *ring, int C, int first_row, int
   return cur;
 }
 
-// one workgroup per (arena, j): sampled entry j of arena a is packed row off[a] + j - first, when it falls into
-// [0, max_rows).  NSTEP: the row is the composite of the n-step chain from it (wave 0 walks the chain first).
-template <bool NSTEP, bool PACKED>
-__global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, const int32_t *n_sampled, const int32_t *off, int first,
-                                                             int max_rows, NstepParams q) {
-  const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
-  if (j >= n_sampled[a]) return;
-  const int d = off[a] + j - first;
-  if (d < 0 || d >= max_rows) return;
-  const int s = p.slot[(size_t)a * p.batch + j];
-  const int count = p.r.count[a], head = p.r.head[a];
+// One gathered row (P: GatherParams or GatherListParams), by the whole workgroup: oldest-first row s of arena a, which
+// holds count rows, becomes row d of the output with its two frames' maps.  NSTEP: the row is the composite of the
+// n-step chain from it (wave 0 walks the chain first; one LDS word carries its end to the other waves).
+template <bool NSTEP, bool PACKED, typename P>
+__device__ __forceinline__ void gather_row(const P &p, int a, int s, int count, int d, const NstepParams &q) {
+  const int head = p.r.head[a];
   const int first_row = ((head - count) % p.C + p.C) % p.C;
   const ofx_transition *ring = p.r.rows + (size_t)a * p.C;
   const ofx_transition *src = ring + (first_row + s) % p.C;
@@ -805,6 +808,18 @@ __global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, con
     if (!outs[w]) continue;  // block-uniform
     frame_read<PACKED>(p.r, a, p.F, p.words, slots[w], outs[w] + (size_t)d * 2 * p.words);
   }
+}
+
+// one workgroup per (arena, j): sampled entry j of arena a is packed row off[a] + j - first, when it falls into
+// [0, max_rows)
+template <bool NSTEP, bool PACKED>
+__global__ __launch_bounds__(256) void k_replay_gather_valid(GatherParams p, const int32_t *n_sampled, const int32_t *off, int first,
+                                                             int max_rows, NstepParams q) {
+  const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
+  if (j >= n_sampled[a]) return;
+  const int d = off[a] + j - first;
+  if (d < 0 || d >= max_rows) return;
+  gather_row<NSTEP, PACKED>(p, a, p.slot[(size_t)a * p.batch + j], p.r.count[a], d, q);
 }
 
 // ofx_replay_gather_valid (q == null) and ofx_replay_gather_nstep: the same window, scan and synchronisation
@@ -1443,43 +1458,12 @@ template <bool NSTEP, bool PACKED>
 __global__ __launch_bounds__(256) void k_replay_gather_list(GatherListParams p, NstepParams q) {
   const int d = blockIdx.x;
   const int a = p.arena[d], s = p.slot[d];
-  ofx_transition *dst = p.rows + d;
-  uint32_t *outs[2] = {p.bits_prev, p.bits_next};
   const int count = (a >= 0 && a < p.N) ? p.r.count[a] : 0;
   if (s < 0 || s >= count) {  // block-uniform
-    if (threadIdx.x < sizeof(ofx_transition) / 4) ((int32_t *)dst)[threadIdx.x] = threadIdx.x == 4 ? -1 : 0;
-    for (int w = 0; w < 2; w++) {
-      if (!outs[w]) continue;
-      uint4 *out = reinterpret_cast<uint4 *>(outs[w] + (size_t)d * 2 * p.words);
-      for (int k = threadIdx.x; k < 2 * p.words / 4; k += 256) out[k] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    if (NSTEP && threadIdx.x == 0) { q.ret[d] = 0.f; q.disc[d] = 0.f; }
+    gather_pad_row<NSTEP>(p, (size_t)d, q);
     return;
   }
-  const int head = p.r.head[a];
-  const int first_row = ((head - count) % p.C + p.C) % p.C;
-  const ofx_transition *ring = p.r.rows + (size_t)a * p.C;
-  const ofx_transition *src = ring + (first_row + s) % p.C;
-  const ofx_transition *end = src;  // the row whose next state is gathered
-  if constexpr (NSTEP) {
-    __shared__ int end_s;
-    if (threadIdx.x < 64) {
-      const int e = nstep_chain(ring, p.C, first_row, count, s, threadIdx.x, d, q);
-      if (threadIdx.x == 0) end_s = e;
-    }
-    __syncthreads();
-    end = ring + (first_row + end_s) % p.C;
-  }
-  if (threadIdx.x < sizeof(ofx_transition) / 4) {
-    const int w = threadIdx.x;  // tick_next, frame_next, done and head_next come from the chain's last row
-    const bool from_end = w == 1 || w == 3 || w == 9 || w >= (int)(offsetof(ofx_transition, head_next) / 4);
-    ((int32_t *)dst)[w] = ((const int32_t *)(from_end ? end : src))[w];
-  }
-  const int slots[2] = {src->frame_prev, end->frame_next};
-  for (int w = 0; w < 2; w++) {
-    if (!outs[w]) continue;  // block-uniform
-    frame_read<PACKED>(p.r, a, p.F, p.words, slots[w], outs[w] + (size_t)d * 2 * p.words);
-  }
+  gather_row<NSTEP, PACKED>(p, a, s, count, d, q);
 }
 
 extern "C" int ofx_replay_gather_list(ofx_handle *h, const int32_t *arena, const int32_t *slot, int32_t n, int32_t nstep,

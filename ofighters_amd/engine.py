@@ -733,6 +733,18 @@ class ArenaBatch:
                                                     bits_next_ptr, float(gamma), ret_ptr, disc_ptr, q_sa_ptr, p_sp_ptr,
                                                     y_act_ptr, y_ptr_ptr))
 
+    def dqn_targets_into(self, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr, gamma, y_act_ptr, y_ptr_ptr,
+                         ret_ptr=None, disc_ptr=None):
+        """The plain targets into the caller's device arrays, bootstrapped from the blob at weights_ptr: y = r + gamma *
+        max(next_state), or with ret / disc (replay_gather_nstep_into) y = ret + disc * max(next_state).  The current
+        values q_sa / p_sp are not asked for.  Does not synchronise."""
+        if ret_ptr is None:
+            nat.check(nat.lib().ofx_dqn_targets(self._h, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr,
+                                                 float(gamma), None, None, y_act_ptr, y_ptr_ptr))
+        else:
+            nat.check(nat.lib().ofx_dqn_targets_nstep(self._h, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr,
+                                                       ret_ptr, disc_ptr, None, None, y_act_ptr, y_ptr_ptr))
+
     def policy_blend_weights(self, dst_buf, src_buf, tau):
         """dst = (1 - tau) * dst + tau * src over the whole weight blob (DeviceBuffers; tau = 1: a device copy) on the
         handle's stream: the soft / hard update of a target network.  Does not synchronise."""

@@ -1,7 +1,8 @@
 """DeviceTrainer - the batched, device-resident counterpart of the reference's `Trainer` (agents/qlearnIA_V2.py:46-298)
 for an ArenaBatch: weights, Adam state and the replay memory live in HBM; `get_best_action` is
 ArenaBatch.policy_forward + policy_explore, `remember` is ArenaBatch.replay_capture, and `replay(batch_size)`
-(:240-285) is sample -> gather -> targets -> one fit step, all through the C-ABI (ofx_replay_sample, ofx_replay_gather,
+(:240-285) is sample -> gather -> targets -> one fit step - one draw (`_draw_window` or, under global_sampling,
+`_draw_list`) that `_fit` consumes, whatever the options below -, all through the C-ABI (ofx_replay_sample, ofx_replay_gather,
 ofx_dqn_targets, ofx_dqn_fit - or ofx_dqn_fit_reference with `reference_quirks=True`: the reference's step as written,
 ptr_target[x][y] and the fit on next_state's inputs included, :280-283).
 
@@ -27,7 +28,7 @@ with `prioritized` and `n_step`; the fit's current values and TD errors always c
 stores the online blob only.
 
 `huber_delta=d` and `clip_norm=c` (opt-in, not in the reference; each None or a finite value > 0) bound how an error
-becomes a weight update, the fit step going through ofx_dqn_fit_robust on both replay paths.  huber_delta replaces the
+becomes a weight update, the fit step going through ofx_dqn_fit_robust under every sampler.  huber_delta replaces the
 squared error of both heads by Keras's Huber(d) (Mnih et al. 2015's error clip): quadratic up to |e| = d, linear beyond,
 so a row's seed is clamp(e, -d, d) - inside the quadratic zone HALF the mse gradient, as in Keras - while the
 priorities of `prioritized` stay the raw |TD error|.  clip_norm scales the whole gradient by
@@ -71,8 +72,8 @@ fit_batch rows.  One replay is still one draw and one fit step.  `grad_hook` (an
 hook(trainer, acc_buffer) between the last ofx_dqn_grad and ofx_dqn_apply with the accumulator's DeviceBuffer
 (batch.dqn_acc_floats() floats: include/ofx.h) and returns how many accumulators it summed into the buffer (None or 1: it
 is untouched); the scale becomes 1 / (c * that count).  It is the place for a data-parallel caller's SUM all-reduce.  With
-a hook set the step goes through ofx_dqn_grad + ofx_dqn_apply also at accumulate=1 (one chunk: the fused step's bits) on
-every textbook replay path.  fingerprint() carries "accumulate": k only when k > 1; the accumulator is scratch inside
+a hook set the step goes through ofx_dqn_grad + ofx_dqn_apply also at accumulate=1 (one chunk: the fused step's bits)
+under every sampler of the textbook fit.  fingerprint() carries "accumulate": k only when k > 1; the accumulator is scratch inside
 one replay(), so a checkpoint needs nothing new.
 
 `actor_priorities=True` (opt-in, not in the reference; Horgan et al. 2018, Ape-X; needs `prioritized`, refused with
@@ -326,18 +327,29 @@ class DeviceTrainer:
         set_epsilon_state(self.epsilon, d["epsilon"])
 
     def replay(self, batch_size=None):
-        """One Trainer.replay: a minibatch of min(batch_size, len(memory)) rows per arena, targets, one fit step.
-        Returns (mse(output1), mse(output2)) or None while every memory is still empty."""
+        """One Trainer.replay: draw a minibatch - min(batch_size, len(memory)) rows per arena of which a moving window is
+        fitted, or under global_sampling one list of rows from all arenas' memories -, then targets and one fit step on it.
+        Returns (mse(output1), mse(output2)) or None while there is nothing to fit."""
+        draw = self._draw_list() if self.global_sampling else self._draw_window(int(batch_size or self.batch_size))
+        return None if draw is None else self._fit(*draw)
+
+    # A draw is (n, gather, row_w, write_back): n rows to fit; gather(o, m, rows, bits_prev, bits_next, ret, disc)
+    # materialises rows o .. o + m - 1 of them (ret / disc None: one-step) and, where the weights are per window, fills
+    # row_w; row_w the rows' IS weights (None without PER); write_back(k, rows_ptr, td_ptr) the first k rows' priorities.
+    def _draw_window(self, bs):
+        """The default sampler: bs rows per arena, of which a window of fit_batch that moves with the draw counter is
+        fitted; under PER drawn by priority and weighted by the window's max-normalised IS weights."""
         b = self.batch
-        if self.global_sampling:
-            return self._replay_global()
-        bs = int(batch_size or self.batch_size)
         cnt, _ = b.replay_count()
         if int(cnt.max()) == 0:
             return None
-        if self.prioritized:
-            return self._replay_prioritized(bs)
-        slot, n_s = b.replay_sample(self.seed, self.draws, bs, self._scratch("slot", 4 * b.N * bs), self._scratch("n_s", 4 * b.N))
+        per = self.prioritized
+        slot, n_s = self._scratch("slot", 4 * b.N * bs), self._scratch("n_s", 4 * b.N)
+        if per:
+            isw = self._scratch("is_w", 4 * b.N * bs)
+            b.replay_sample_prioritized(self.seed, self.draws, bs, self.beta(), slot, n_s, isw)
+        else:
+            b.replay_sample(self.seed, self.draws, bs, slot, n_s)
         self.draws += 1
         # the sampled transitions of all arenas, WITHOUT the -1 pads of arenas that hold fewer than bs (a pad would enter
         # the BatchNorm batch statistics and the loss scale of the fit; the reference's batch is min(bs, len(memory)) real
@@ -347,43 +359,29 @@ class DeviceTrainer:
         n_valid = int(n_s.download(np.int32, (b.N,)).sum())
         if n_valid == 0:
             return None
-        n = min(n_valid, int(self.fit_batch))
+        n = min(n_valid, int(self.fit_batch))                # at most fit_batch: a window is always one chunk
         start = ((self.draws - 1) * n) % (n_valid - n + 1)
-        words = b.W * b.H // 32
-        rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
-        bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
-        got = self._gather(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
-        if got != n:
-            raise Exception("DeviceTrainer.replay: gathered %d of %d rows" % (got, n))
-        rows_p, prev_p, next_p = rows.ptr, bits_prev.ptr, bits_next.ptr
-        if self.reference_quirks:
-            self.fit_steps += 1
-            loss = b.dqn_fit_reference(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n,
-                                       rows_p, prev_p, next_p, self.gamma)
-            self.losses.append(loss)
-            return loss
-        y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
-        self._targets(n, rows_p, prev_p, next_p, y_act, y_ptr)
-        self.fit_steps += 1
-        if self.grad_hook is not None:
-            loss = self._fit_split(n, rows_p, prev_p, y_act, y_ptr)
-        elif self._robust():
-            loss = self._fit_robust(n, rows_p, prev_p, y_act, y_ptr)
-        else:
-            loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
-                             y_act.ptr, y_ptr.ptr)
-        self._move_target()
-        self.losses.append(loss)
-        return loss
+        row_w = self._scratch("row_w", 4 * n) if per else None
 
-    def _replay_global(self):
-        """replay() under global_sampling: fit_batch rows drawn from the union of all arenas' memories (uniform over
-        rows, or by priority across arenas), the list gather, the same targets and fit calls, the list write-back.  The
-        sampler's two host integers are the only synchronisation before the fit."""
-        if self.accumulate > 1 or self.grad_hook is not None:
-            return self._replay_accumulate()
+        def gather(o, m, rows, bits_prev, bits_next, ret, disc):
+            if ret is None:
+                got = b.replay_gather_valid_into(slot, n_s, bs, start, m, rows, bits_prev, bits_next)
+            else:
+                got = b.replay_gather_nstep_into(slot, n_s, bs, start, m, self.n_step, self.gamma, rows, bits_prev,
+                                                 bits_next, ret, disc)
+            if got != m:
+                raise Exception("DeviceTrainer.replay: gathered %d of %d rows" % (got, m))
+            if per:
+                b.replay_window_weights_into(isw, n_s, bs, start, m, row_w)
+
+        return n, gather, row_w, lambda k, rows_p, td_p: b.replay_update_priorities(slot, n_s, bs, start, k, rows_p, td_p)
+
+    def _draw_list(self):
+        """global_sampling: accumulate * fit_batch rows in one draw from the union of all arenas' memories (uniform over
+        rows, or by priority across arenas); a chunk is a pointer offset into the draw's sorted list.  The sampler's two
+        host integers are the only synchronisation before the fit."""
         b = self.batch
-        nb = int(self.fit_batch)
+        nb = self.accumulate * int(self.fit_batch)
         per = self.prioritized
         arena, slot, row_w, n, _ = b.replay_sample_global(self.seed, self.draws, nb, per, self.beta() if per else 0.0,
                                                           self._scratch("g_arena", 4 * nb), self._scratch("g_slot", 4 * nb),
@@ -391,84 +389,72 @@ class DeviceTrainer:
         self.draws += 1
         if n == 0:
             return None
-        words = b.W * b.H // 32
-        rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
-        bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
-        if self.n_step == 1:
-            b.replay_gather_list_into(arena, slot, n, rows, bits_prev, bits_next)
-        else:
-            b.replay_gather_list_into(arena, slot, n, rows, bits_prev, bits_next, self.n_step, self.gamma,
-                                      self._scratch("ret", 4 * n), self._scratch("disc", 4 * n))
-        rows_p, prev_p = rows.ptr, bits_prev.ptr
-        y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
-        self._targets(n, rows_p, prev_p, bits_next.ptr, y_act, y_ptr)
-        self.fit_steps += 1
-        td = self._scratch("td", 8 * n) if per else None
-        if self._robust():
-            loss = self._fit_robust(n, rows_p, prev_p, y_act, y_ptr, row_w.ptr if per else None, td.ptr if per else None)
-        elif per:
-            loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p,
-                                      prev_p, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
-        else:
-            loss = b.dqn_fit(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n, rows_p, prev_p,
-                             y_act.ptr, y_ptr.ptr)
-        if per:
-            b.replay_update_priorities_list(arena, slot, n, rows_p, td.ptr)
-        self._move_target()
-        self.losses.append(loss)
-        return loss
 
-    def _replay_accumulate(self):
-        """replay() under global_sampling with accumulate > 1 or a grad_hook: accumulate * fit_batch rows in one draw, cut
-        into c = max(1, n // fit_batch) chunks of fit_batch rows (one chunk of all n rows while n < fit_batch; the rows
-        beyond c * fit_batch are drawn but NOT fitted); gather, targets and ofx_dqn_grad per chunk at pointer offsets into
-        the draw's list, the hook, one ofx_dqn_apply with scale = 1 / (c * the hook's count), then the write-back over all
-        fitted rows and the target network's move.  Buffers that hold maps are sized for one chunk."""
+        def gather(o, m, rows, bits_prev, bits_next, ret, disc):
+            nstep = () if ret is None else (self.n_step, self.gamma, ret, disc)
+            b.replay_gather_list_into(_At(arena, 4 * o), _At(slot, 4 * o), m, rows, bits_prev, bits_next, *nstep)
+
+        return n, gather, row_w, lambda k, rows_p, td_p: b.replay_update_priorities_list(arena, slot, k, rows_p, td_p)
+
+    def _fit(self, n, gather, row_w, write_back):
+        """One fit step on a draw of n rows, cut into c = max(1, n // fit_batch) chunks of fit_batch rows (one chunk of
+        all n rows while n < fit_batch; rows beyond c * fit_batch are drawn but NOT fitted): gather and targets per
+        chunk, then the fused fit - or, with accumulate > 1 or a grad_hook, ofx_dqn_grad per chunk, the hook and one
+        ofx_dqn_apply with scale = 1 / (c * the hook's count) -, the write-back over all fitted rows and the target
+        network's move.  `rows` holds every chunk (the write-back reads them); the maps, targets and returns one chunk.
+        The step is counted before the first gather, so a window gather that raises leaves fit_steps one higher."""
         b = self.batch
         fb = int(self.fit_batch)
-        nb = self.accumulate * fb
-        per = self.prioritized
-        arena, slot, row_w, n, _ = b.replay_sample_global(self.seed, self.draws, nb, per, self.beta() if per else 0.0,
-                                                          self._scratch("g_arena", 4 * nb), self._scratch("g_slot", 4 * nb),
-                                                          self._scratch("row_w", 4 * nb) if per else None)
-        self.draws += 1
-        if n == 0:
-            return None
         c = max(1, n // fb)
         m = fb if n >= fb else n                             # rows per chunk
+        per = self.prioritized
+        quirks = self.reference_quirks                       # (window draws only) the reference's own targets and fit
+        split = (self.accumulate > 1 or self.grad_hook is not None) and not quirks
         words = b.W * b.H // 32
         row_bytes = b.TRANSITION_DTYPE.itemsize
-        rows = self._scratch("rows", c * m * row_bytes)      # of every chunk: the write-back reads them
+        rows = self._scratch("rows", c * m * row_bytes)
         bits_prev, bits_next = self._scratch("bits_prev", 4 * m * 2 * words), self._scratch("bits_next", 4 * m * 2 * words)
-        y_act, y_ptr = self._scratch("y_act", 4 * m), self._scratch("y_ptr", 4 * m)
+        ret, disc = (self._scratch("ret", 4 * m), self._scratch("disc", 4 * m)) if self.n_step > 1 else (None, None)
+        if not quirks:
+            y_act, y_ptr = self._scratch("y_act", 4 * m), self._scratch("y_ptr", 4 * m)
         td = self._scratch("td", 8 * c * m) if per else None
-        acc = self._scratch("acc", 4 * b.dqn_acc_floats())
-        prev_p = bits_prev.ptr
+        acc = self._scratch("acc", 4 * b.dqn_acc_floats()) if split else None
         self.fit_steps += 1
         for i in range(c):
             o = i * m
-            arena_i, slot_i, rows_i = _At(arena, 4 * o), _At(slot, 4 * o), _At(rows, o * row_bytes)
-            if self.n_step == 1:
-                b.replay_gather_list_into(arena_i, slot_i, m, rows_i, bits_prev, bits_next)
+            rows_i = _At(rows, o * row_bytes)
+            gather(o, m, rows_i, bits_prev, bits_next, ret, disc)
+            if quirks:                                       # as written: no hook, no split, its targets inside the fit
+                loss = b.dqn_fit_reference(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, m,
+                                           rows_i.ptr, bits_prev.ptr, bits_next.ptr, self.gamma)
+                continue
+            self._targets(m, rows_i.ptr, bits_prev.ptr, bits_next.ptr, y_act, y_ptr)
+            chunk = (m, rows_i.ptr, bits_prev.ptr, y_act.ptr, y_ptr.ptr)
+            w_p, td_p = (row_w.ptr + 4 * o, td.ptr + 8 * o) if per else (None, None)
+            if split:
+                b.dqn_grad(self.weights, *chunk, acc, i == 0, self.huber_delta or 0.0, w_p, td_p)
             else:
-                b.replay_gather_list_into(arena_i, slot_i, m, rows_i, bits_prev, bits_next, self.n_step, self.gamma,
-                                          self._scratch("ret", 4 * m), self._scratch("disc", 4 * m))
-            self._targets(m, rows_i.ptr, prev_p, bits_next.ptr, y_act, y_ptr)
-            b.dqn_grad(self.weights, m, rows_i.ptr, prev_p, y_act.ptr, y_ptr.ptr, acc, i == 0, self.huber_delta or 0.0,
-                       row_w.ptr + 4 * o if per else None, td.ptr + 8 * o if per else None)
-        loss = self._apply(acc, c)
+                loss = self._fit_fused(*chunk, w_p, td_p)
+        if split:
+            loss = self._apply(acc, c)
         if per:
-            b.replay_update_priorities_list(arena, slot, c * m, rows.ptr, td.ptr)
+            write_back(c * m, rows.ptr, td.ptr)
         self._move_target()
         self.losses.append(loss)
         return loss
 
-    def _fit_split(self, n, rows_p, prev_p, y_act, y_ptr, row_w_p=None, td_p=None):
-        """The fit step as ofx_dqn_grad + the hook + ofx_dqn_apply on one chunk (a grad_hook at accumulate=1)."""
-        acc = self._scratch("acc", 4 * self.batch.dqn_acc_floats())
-        self.batch.dqn_grad(self.weights, n, rows_p, prev_p, y_act.ptr, y_ptr.ptr, acc, True, self.huber_delta or 0.0,
-                            row_w_p, td_p)
-        return self._apply(acc, 1)
+    def _fit_fused(self, m, rows_p, prev_p, y_act_p, y_ptr_p, w_p, td_p):
+        """The fit step in one call: ofx_dqn_fit_robust with huber_delta / clip_norm (the pre-clip gradient norm goes to
+        grad_norms), else ofx_dqn_fit_weighted under PER, else ofx_dqn_fit."""
+        b = self.batch
+        step = (self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, m, rows_p, prev_p, y_act_p, y_ptr_p)
+        if self._robust():
+            l1, l2, norm = b.dqn_fit_robust(*step, self.huber_delta or 0.0, self.clip_norm or 0.0, w_p, td_p)
+            self.grad_norms.append(norm)
+            return l1, l2
+        if self.prioritized:
+            return b.dqn_fit_weighted(*step, w_p, td_p)
+        return b.dqn_fit(*step)
 
     def _apply(self, acc, chunks):
         """The hook, then ofx_dqn_apply on the mean of `chunks` x (the hook's count) accumulated micro-batches; the norm
@@ -487,43 +473,19 @@ class DeviceTrainer:
     def _robust(self):
         return self.huber_delta is not None or self.clip_norm is not None
 
-    def _fit_robust(self, n, rows_p, prev_p, y_act, y_ptr, row_w_p=None, td_p=None):
-        """The fit step through ofx_dqn_fit_robust; the pre-clip gradient norm goes to grad_norms."""
-        l1, l2, norm = self.batch.dqn_fit_robust(self.weights, self.adam_m, self.adam_v, self.fit_steps,
-                                                 self.learning_rate, n, rows_p, prev_p, y_act.ptr, y_ptr.ptr,
-                                                 self.huber_delta or 0.0, self.clip_norm or 0.0, row_w_p, td_p)
-        self.grad_norms.append(norm)
-        return l1, l2
-
-    def _gather(self, slot, n_s, bs, start, n, rows, bits_prev, bits_next):
-        """The window of sampled rows: ofx_replay_gather_valid, or with n_step > 1 the rows' n-step composites and their
-        ret / disc (two more grow-only scratch buffers, read by _targets)."""
-        b = self.batch
-        if self.n_step == 1:
-            return b.replay_gather_valid_into(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
-        ret, disc = self._scratch("ret", 4 * n), self._scratch("disc", 4 * n)
-        return b.replay_gather_nstep_into(slot, n_s, bs, start, n, self.n_step, self.gamma, rows, bits_prev, bits_next,
-                                          ret, disc)
-
     def _targets(self, n, rows_p, prev_p, next_p, y_act, y_ptr):
         """y_act / y_ptr of the gathered window.  q_sa / p_sp (the current values at the chosen action / pointer) are not
         asked for: the fit's own training-mode forward produces them, so the targets need the forward on next_state only.
         They bootstrap from the target network when there is one; with double_dqn the online blob selects what it
         evaluates."""
-        from . import _native as nat
-        h = self.batch.handle
         w = self.target.ptr if self.target is not None else self.weights.ptr
         nstep = self.n_step > 1
+        ret_p, disc_p = (self._buf["ret"].ptr, self._buf["disc"].ptr) if nstep else (None, None)
         if self.double_dqn:
             self.batch.dqn_targets_double_into(self.weights.ptr, w, n, rows_p, prev_p, next_p, self.gamma, y_act.ptr,
-                                               y_ptr.ptr, self._buf["ret"].ptr if nstep else None,
-                                               self._buf["disc"].ptr if nstep else None)
-        elif not nstep:
-            nat.check(nat.lib().ofx_dqn_targets(h, w, n, rows_p, prev_p, next_p, float(self.gamma), None, None, y_act.ptr,
-                                                 y_ptr.ptr))
+                                               y_ptr.ptr, ret_p, disc_p)
         else:
-            nat.check(nat.lib().ofx_dqn_targets_nstep(h, w, n, rows_p, prev_p, next_p, self._buf["ret"].ptr,
-                                                       self._buf["disc"].ptr, None, None, y_act.ptr, y_ptr.ptr))
+            self.batch.dqn_targets_into(w, n, rows_p, prev_p, next_p, self.gamma, y_act.ptr, y_ptr.ptr, ret_p, disc_p)
 
     def _move_target(self):
         """After a fit step: the hard copy of every target_sync-th step or the soft update of each one (on the stream)."""
@@ -538,40 +500,3 @@ class DeviceTrainer:
         """The IS exponent of the next fit step: per_beta -> 1.0 linearly over per_beta_steps fit steps."""
         f = min(1.0, self.fit_steps / float(self.per_beta_steps)) if self.per_beta_steps > 0 else 1.0
         return self.per_beta + (1.0 - self.per_beta) * f
-
-    def _replay_prioritized(self, bs):
-        """replay() under PER: the same moving window of the sampled rows as the uniform path, weighted by the window's
-        max-normalised IS weights; the fit's pre-update errors become the rows' new priorities."""
-        b = self.batch
-        N = b.N
-        slot, n_s, isw = b.replay_sample_prioritized(self.seed, self.draws, bs, self.beta(), self._scratch("slot", 4 * N * bs),
-                                                     self._scratch("n_s", 4 * N), self._scratch("is_w", 4 * N * bs))
-        self.draws += 1
-        b.sync()
-        n_valid = int(n_s.download(np.int32, (N,)).sum())
-        if n_valid == 0:
-            return None
-        n = min(n_valid, int(self.fit_batch))
-        start = ((self.draws - 1) * n) % (n_valid - n + 1)
-        words = b.W * b.H // 32
-        rows = self._scratch("rows", n * b.TRANSITION_DTYPE.itemsize)
-        bits_prev, bits_next = self._scratch("bits_prev", 4 * n * 2 * words), self._scratch("bits_next", 4 * n * 2 * words)
-        got = self._gather(slot, n_s, bs, start, n, rows, bits_prev, bits_next)
-        if got != n:
-            raise Exception("DeviceTrainer.replay: gathered %d of %d rows" % (got, n))
-        row_w, td = self._scratch("row_w", 4 * n), self._scratch("td", 8 * n)
-        b.replay_window_weights_into(isw, n_s, bs, start, n, row_w)
-        y_act, y_ptr = self._scratch("y_act", 4 * n), self._scratch("y_ptr", 4 * n)
-        self._targets(n, rows.ptr, bits_prev.ptr, bits_next.ptr, y_act, y_ptr)
-        self.fit_steps += 1
-        if self.grad_hook is not None:
-            loss = self._fit_split(n, rows.ptr, bits_prev.ptr, y_act, y_ptr, row_w.ptr, td.ptr)
-        elif self._robust():
-            loss = self._fit_robust(n, rows.ptr, bits_prev.ptr, y_act, y_ptr, row_w.ptr, td.ptr)
-        else:
-            loss = b.dqn_fit_weighted(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, n,
-                                      rows.ptr, bits_prev.ptr, y_act.ptr, y_ptr.ptr, row_w.ptr, td.ptr)
-        b.replay_update_priorities(slot, n_s, bs, start, n, rows.ptr, td.ptr)
-        self._move_target()
-        self.losses.append(loss)
-        return loss
