@@ -780,6 +780,9 @@ __global__ __launch_bounds__(NT, NT == 512 ? 4 : 2) void f_bw(int n, int H, int 
   // mean): their rounding error is the SAME at every pixel of the batch, so it does not average out in the weight
   // gradient sum in * dz - at 1024 rows fp32 coefficients left conv2's kernel gradient 7e-4 of its scale away from the
   // float64 graph, 1e-3 for conv1's gamma (r04, tools/fit_check64.py; the plain form computes them per element in doubles).
+  // (That attribution is OPEN: with the pairs in place the same 7e-4 / 1e-3 are still there on that minibatch, torch's
+  // float32 autograd shows them too, and a float64 evaluation with the statistics and these per-channel sums rounded to
+  // float32 does not - profiles/r16_fit_fp64.txt.  The pairs stay: they cost nothing measurable.)
   __shared__ float cf[BN ? CO : 1][7];
   if constexpr (BN)
     if (threadIdx.x < CO) {

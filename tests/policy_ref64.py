@@ -33,7 +33,7 @@ def upsample2(u, legacy=False):
     if not legacy:
         return F.interpolate(u, scale_factor=2, mode="bilinear", align_corners=False)
     n = u.shape[-1]
-    k = torch.arange(2 * n)
+    k = torch.arange(2 * n, device=u.device)
     i0, i1 = k // 2, torch.clamp(k // 2 + 1, max=n - 1)
     w1 = ((k % 2) * 0.5).to(u.dtype)
     u = u[..., i0, :] * (1 - w1)[:, None] + u[..., i1, :] * w1[:, None]
