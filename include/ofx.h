@@ -210,6 +210,27 @@ int ofx_bot_actions(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed
 int ofx_rollout(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0, int32_t n_ticks,
                 int32_t observe_map_type);
 
+/* ---- action repeat (opt-in): K lock-steps per decision in one launch ---------
+ * Mnih et al. 2015's frame skip for a learning agent: n_ticks >= 1 lock-steps in ONE launch of the step kernel's third
+ * form (wave per arena, no block barrier, the wavefront fence of ofx_rollout between lock-steps).
+ *  - hold_mask: DEVICE uint8 [N][M] or NULL (nobody).  A ship with hold_mask[a][i] != 0 plays actions[a][i] (DEVICE
+ *    [N][M] ofx_action, e.g. what ofx_policy_actions wrote; loaded once, before the first lock-step) on EVERY lock-step
+ *    of the launch under ofx_step's own rule `valid && alive`, alive being the ship's CURRENT state: a ship destroyed
+ *    inside the span stops acting, an action with valid = 0 never acts.  Its behaviours entry is not used (it must still
+ *    be an OFX_BOT_* value).  Every other ship follows the ofx_bot_actions law of lock-step tick0 + j, as in ofx_rollout.
+ *  - span_reward: DEVICE int32 [N][M] or NULL; receives for EVERY ship, held or not, dead or not, the sum over the
+ *    launch's lock-steps of the reward earned in that lock-step (the value each lock-step leaves in OFX_F_REWARD; the
+ *    state keeps only the last one, the earlier ones are in OFX_F_SCORE).  Undiscounted.  See ofx_replay_reward_source.
+ *  - observe_map_type: as in ofx_rollout, but the maps are rasterised ONCE, after the last lock-step; -1 = none.
+ * The state afterwards - every field, the lasers - is bit-identical to n_ticks x (ofx_bot_actions(tick0 + j), the held
+ * ships' entries overwritten by `actions`, ofx_step); span_reward is the sum of OFX_F_REWARD read after each of those
+ * steps, the maps are the last step's ofx_rasterise.  With hold_mask == NULL the state is that of ofx_rollout(...,
+ * n_ticks, -1).  OFX_ERR_INVALID: NULL handle or behaviours, n_ticks < 1, hold_mask without actions; OFX_ERR_STATE
+ * before ofx_spawn.  Keeps the behaviours on the device like ofx_rollout.  Does not synchronise.                    */
+int ofx_step_repeat(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0, int32_t n_ticks,
+                    const uint8_t *hold_mask, const ofx_action *actions, int32_t *span_reward,
+                    int32_t observe_map_type);
+
 /* ---- state access ------------------------------------------------------ */
 int ofx_get_host(ofx_handle *h, int field, void *dst_host, size_t bytes);
 void *ofx_device_ptr(ofx_handle *h, int field);
@@ -439,6 +460,16 @@ int ofx_replay_destroy(ofx_handle *h); /* also done by ofx_destroy            */
  * one per call and not restart at episode boundaries.                         */
 int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *ship_mask, const int32_t *iaction,
                        const int32_t *ipointer);
+/* Where a completed row's `reward` comes from (opt-in; for ofx_step_repeat's span_reward, when one capture stands for
+ * K lock-steps).  reward: DEVICE int32 [N][M], caller-owned, read by every following capture; NULL, the default, is
+ * the state's reward field - today's behaviour, bit for bit.  While it is set:
+ *  - both capture forms (ofx_replay_capture, ofx_replay_capture_valued) take row.reward from reward[a][i], and the
+ *    valued form's y1 / y2 (its initial priorities) are formed with the same value;
+ *  - element 0 of the observation head (head_prev[0] / head_next[0]) STAYS the state's reward: it is what the live
+ *    forward feeds the network (vec[0] = OFX_F_REWARD), and the forward on stored observations must reproduce it.
+ * Dropped with the memory (ofx_replay_create* / ofx_replay_destroy); not part of the replay blob.  Does not
+ * synchronise.  OFX_ERR_INVALID for a NULL handle, OFX_ERR_STATE without a replay memory.                          */
+int ofx_replay_reward_source(ofx_handle *h, const int32_t *reward);
 /* QlearnIA.play's `if obs.done: ... self.done = True` (agents/qlearnIA_V2.py:376-384) for a caller that drives the
  * learning schedule: counts the selected ships (ship_mask [N][M] uint8, NULL = all) that are destroyed now and were
  * not yet marked in seen[N][M] (device uint8, caller-owned, zeroed by the caller at episode starts), marks them, and

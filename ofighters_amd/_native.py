@@ -100,6 +100,7 @@ SIGNATURES = {
     "ofx_observe_head": (_i, [_vp, _vp, _vp]),
     "ofx_bot_actions": (_i, [_vp, _vp, _u64, _u32, _vp]),
     "ofx_rollout": (_i, [_vp, _vp, _u64, _u32, C.c_int32, C.c_int32]),
+    "ofx_step_repeat": (_i, [_vp, _vp, _u64, _u32, C.c_int32, _vp, _vp, _vp, C.c_int32]),
     "ofx_get_host": (_i, [_vp, _i, _vp, _sz]),
     "ofx_device_ptr": (_vp, [_vp, _i]),
     "ofx_field_bytes": (_sz, [_vp, _i]),
@@ -133,6 +134,7 @@ SIGNATURES = {
     "ofx_replay_store_stats": (_i, [_vp, C.POINTER(C.c_int64)]),
     "ofx_replay_destroy": (_i, [_vp]),
     "ofx_replay_capture": (_i, [_vp, _u32, _vp, _vp, _vp]),
+    "ofx_replay_reward_source": (_i, [_vp, _vp]),
     "ofx_agents_first_done": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "ofx_replay_count": (_i, [_vp, _vp, _vp]),
     "ofx_replay_rows_host": (_i, [_vp, C.c_int32, _vp, _vp]),

@@ -7,7 +7,8 @@ counter, and a fit is reproducible to the bit, so nothing else is hidden):
     the manifest     format version; N, M, W, H, arena_base; the trainer's and the rollout's fingerprints (the arguments
                      that must match at restore); the rollout's counters; the index of the sections
     rollout/*        losses, epsilons, score_log, the `_seen_done` latch; rung_log only under an exploration ladder or
-                     evaluation arenas (the ladder itself is re-derived by the constructor from the fingerprint's arguments)
+                     evaluation arenas (the ladder itself is re-derived by the constructor from the fingerprint's arguments);
+                     span_reward (int32 [N][M], the last span's summed rewards) only under action_repeat > 1
     arena/<field>    the 19 state fields of the arenas (ArenaBatch.state_dict)
     trainer/*        weights, Adam m and v, the target blob, the loss and gradient-norm lists (DeviceTrainer.state_dict)
     replay/<k>       the replay memory as ofx_replay_export blobs of consecutive arena chunks, each chosen from
@@ -130,6 +131,8 @@ def rollout_fingerprint(r):
     if getattr(r, "ladder_on", False):                   # only when on: a default rollout's key set stays as it was
         fp.update(epsilon_ladder=r.epsilon_ladder, eval_arenas=int(r.eval_arenas), total_arenas=int(r.total_arenas),
                   score_bands=int(r.score_bands))
+    if getattr(r, "action_repeat", 1) > 1:
+        fp["action_repeat"] = int(r.action_repeat)
     return fp
 
 
@@ -174,6 +177,8 @@ def save(rollout, path, chunk_bytes=None):
         if getattr(rollout, "ladder_on", False):
             w.add("rollout/rung_log", np.array(rollout.rung_log, np.int64).reshape(len(rollout.rung_log), rollout.n_groups,
                                                                                    e.M + 1))
+        if getattr(rollout, "action_repeat", 1) > 1:
+            w.add("rollout/span_reward", rollout._span.download(np.int32, (e.N, e.M)))
         for name, a in es.items():
             if name not in ("episode", "tick"):
                 w.add("arena/" + name, a)
@@ -237,5 +242,7 @@ def load(rollout, path):
         rollout.rung_log = [g.copy() for g in rd.array("rollout/rung_log")]
     e.sync()
     rollout._seen_done.upload(rd.array("rollout/seen_done"))
+    if getattr(rollout, "action_repeat", 1) > 1:                       # (the fingerprints agree: the section is there)
+        rollout._span.upload(rd.array("rollout/span_reward"))          # the next capture's completed rows read it
     e.policy_pin_weights(t.weights.ptr)             # the blob changed under the pin: prepare it again
     return m

@@ -456,6 +456,37 @@ extern "C" int ofx_rollout(ofx_handle *h, const int32_t *behaviours_host, uint64
   return OFX_OK;
 }
 
+// ------------------------------------------------ action repeat: K lock-steps per decision in one launch
+// The held ships (the learning agents, say) keep the action of their last decision for the whole span while the others
+// follow the bots' law lock-step by lock-step; the span's rewards are summed per ship for the replay memory
+// (ofx_replay_reward_source) and the maps are rasterised once, for the next decision.
+int ofx_launch_step_repeat(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks, const uint8_t *hold_mask,
+                           const ofx_action *actions, int32_t *span_reward);  // ofx_step.hip
+
+extern "C" int ofx_step_repeat(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0,
+                               int32_t n_ticks, const uint8_t *hold_mask, const ofx_action *actions, int32_t *span_reward,
+                               int32_t observe_map_type) {
+  if (!h || !behaviours_host) { ofx_set_error("ofx_step_repeat: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_step_repeat before ofx_spawn"); return OFX_ERR_STATE; }
+  if (n_ticks < 1 || observe_map_type < -1 || observe_map_type > OFX_MAP_BITS) {
+    ofx_set_error("ofx_step_repeat: n_ticks must be >= 1 and observe_map_type -1 (none) or an OFX_MAP_* type");
+    return OFX_ERR_INVALID;
+  }
+  if (hold_mask && !actions) { ofx_set_error("ofx_step_repeat: hold_mask given without actions"); return OFX_ERR_INVALID; }
+  for (int i = 0; i < h->cfg.n_ships; i++)
+    if (behaviours_host[i] < OFX_BOT_IDLE || behaviours_host[i] > OFX_BOT_SHOOT) {
+      ofx_set_error("You must give a bot in parameter or select an existing behavior.");  // agents/agent.py:51
+      return OFX_ERR_INVALID;
+    }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipMemcpyAsync(h->bot_behaviours, behaviours_host, sizeof(int32_t) * h->cfg.n_ships, hipMemcpyHostToDevice,
+                         h->stream));
+  int rc;
+  if ((rc = ofx_launch_step_repeat(h, seed, tick0, n_ticks, hold_mask, actions, span_reward))) return rc;
+  if (observe_map_type >= 0 && (rc = ofx_launch_raster(h, observe_map_type, nullptr, nullptr))) return rc;
+  return OFX_OK;
+}
+
 // ------------------------------------------------------------------ obs head
 // Observation.analyse_ship + toVector head (observation.py:101-123)
 __global__ void k_obs_head(int N, int M, int W, int H, ofx_state st, double *head, uint8_t *done) {

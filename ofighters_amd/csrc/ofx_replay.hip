@@ -57,6 +57,8 @@ struct ofx_replay {
   long long *g_voff;       // [N + 1] exclusive scan of g_v, R in [N]
   double *g_T, *g_G;       // [N] arena mass totals / their inclusive cross-arena prefix
   double *g_gs;            // [ceil(N / 256)] the groups' last running sums
+  // ofx_replay_reward_source: caller-owned device [N][M] a completed row's reward comes from, null = the state's field
+  const int32_t *reward_src;
 };
 
 void ofx_replay_free(ofx_handle *h) {
@@ -256,6 +258,9 @@ __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
     hd[2] = (float)p.st.ship_px[t]; hd[3] = (float)p.st.ship_py[t];
     hd[4] = (float)p.W; hd[5] = (float)p.H;
     hd[6] = (float)p.st.ship_x[t]; hd[7] = (float)p.st.ship_y[t];
+    // the row's reward (and the valued form's targets) may come from a span's sum; hd[0] above stays the state's
+    // reward, which is what the live forward feeds (ofx_policy.hip: vec[0] = st.reward)
+    if (p.r.reward_src) reward = p.r.reward_src[t];
   }
   // the arena keeps this lock-step's maps iff one of its agents plays (k_replay_frames copies them afterwards)
   int slot = -1;
@@ -469,6 +474,13 @@ extern "C" int ofx_replay_capture(ofx_handle *h, uint32_t tick, const uint8_t *s
   if (!h) { ofx_set_error("ofx_replay_capture: null handle"); return OFX_ERR_INVALID; }
   if (!h->replay) { ofx_set_error("ofx_replay_capture before ofx_replay_create"); return OFX_ERR_STATE; }
   return replay_capture(h, "ofx_replay_capture", tick, ship_mask, iaction, ipointer, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ofx_replay_reward_source(ofx_handle *h, const int32_t *reward) {
+  if (!h) { ofx_set_error("ofx_replay_reward_source: null handle"); return OFX_ERR_INVALID; }
+  if (!h->replay) { ofx_set_error("ofx_replay_reward_source before ofx_replay_create"); return OFX_ERR_STATE; }
+  h->replay->reward_src = reward;  // read by the captures enqueued from now on
+  return OFX_OK;
 }
 
 // first-seen deaths of the selected ships (QlearnIA.play's done latch, agents/qlearnIA_V2.py:376-384)

@@ -19,6 +19,9 @@
 // bit; the ship leaves the wave-uniform alive mask before later chunks of 64
 // lasers are tested.  Laser compaction is a ballot + popcount prefix, stable,
 // in place (a chunk's stores land at or below its own load indices).
+// Three forms of the one kernel: k_step<false> (the caller's actions, one lock-step), k_step<true> (the bots' law, n
+// lock-steps per launch: ofx_rollout) and k_step<true, true> (the same loop with held actions for the ships of a mask
+// and the span's rewards summed: ofx_step_repeat).
 //
 // Arithmetic is fp64 with contraction off (build flag -ffp-contract=off):
 // positions are bit-identical to CPython's.  The collide test
@@ -39,6 +42,9 @@ struct StepParams {
   const int32_t *beh;          // device [M] OFX_BOT_*
   uint32_t k0, k1, tick0;
   int n_ticks, arena_base;
+  // HOLD = true (ofx_step_repeat): BOTS' loop in which the ships marked in hold_mask play `actions` on every lock-step
+  const uint8_t *hold_mask;    // device [N][M] or null = nobody holds
+  int32_t *span_reward;        // device [N][M] or null: every ship's rewards summed over the launch's lock-steps
 };
 
 // CPython float_rem: fmod, then the result takes the divisor's sign (b > 0 here)
@@ -84,8 +90,9 @@ __device__ inline ofx_action bot_action(int beh, uint32_t ga, uint32_t i, uint32
   return act;
 }
 
-template <bool BOTS>
+template <bool BOTS, bool HOLD = false>
 __global__ __launch_bounds__(256) void k_step(StepParams p) {
+  static_assert(BOTS || !HOLD, "the held form is a form of the bots' loop");
   const int lane = threadIdx.x & 63;
   const int a = blockIdx.x * OFX_ARENAS_PER_BLOCK + (threadIdx.x >> 6);
   if (a >= p.N) return;  // wave-uniform; the kernel has no block-level barrier
@@ -95,6 +102,15 @@ __global__ __launch_bounds__(256) void k_step(StepParams p) {
   const size_t si = (size_t)a * M + (is_ship ? lane : 0);
   const int my_beh = BOTS && is_ship ? p.beh[lane] : 0;
   const int n_ticks = BOTS ? p.n_ticks : 1;
+  // HOLD: the held action is loaded once; `act.valid && alive` below is still evaluated on every lock-step
+  bool held = false;
+  ofx_action held_act;
+  held_act.px = held_act.py = 0; held_act.shoot = held_act.thrust = held_act.valid = held_act._pad = 0;
+  int span = 0;
+  if (HOLD && is_ship && p.hold_mask && p.hold_mask[si]) {
+    held = true;
+    held_act = p.actions[si];
+  }
 #pragma unroll 1
   for (int tk = 0; tk < n_ticks; tk++) {
   // An arena belongs to ONE wave for the whole launch, so the lock-steps of a K-tick launch only need this wave's own
@@ -185,7 +201,7 @@ __global__ __launch_bounds__(256) void k_step(StepParams p) {
   int ex = 0, ey = 0;
   double ndx = 0, ndy = 0;
   if (is_ship) {
-    const ofx_action act = BOTS ? bot_act : p.actions[si];
+    const ofx_action act = BOTS ? (HOLD && held ? held_act : bot_act) : p.actions[si];
     if (act.valid && alive) {  // ship.py:308
       ptx = act.px;
       pty = act.py;
@@ -302,12 +318,14 @@ __global__ __launch_bounds__(256) void k_step(StepParams p) {
     p.st.score[si] = sc;
     p.st.alive[si] = alive ? 1 : 0;
     p.st.killer[si] = (int16_t)killer;
+    if (HOLD) span += rew;
   }
   if (lane == 0) {
     p.st.n_lasers[a] = out;
     p.st.time[a] += 1;
   }
   }  // lock-steps of this launch
+  if (HOLD && is_ship && p.span_reward) p.span_reward[si] = span;
 }
 
 static StepParams step_params(ofx_handle *h) {
@@ -320,6 +338,7 @@ static StepParams step_params(ofx_handle *h) {
   p.hit_thresh = h->hit_thresh;
   p.st = h->st;
   p.actions = nullptr; p.beh = nullptr; p.k0 = p.k1 = p.tick0 = 0; p.n_ticks = 1; p.arena_base = c.arena_base;
+  p.hold_mask = nullptr; p.span_reward = nullptr;
   return p;
 }
 
@@ -339,6 +358,19 @@ int ofx_launch_step_bots(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_tic
   p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.tick0 = tick0; p.n_ticks = n_ticks;
   const int blocks = (h->cfg.n_arenas + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK;
   hipLaunchKernelGGL(k_step<true>, dim3(blocks), dim3(256), 0, h->stream, p);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ofx_step_repeat: n_ticks lock-steps in ONE launch, the ships of hold_mask on `actions`, the others on the bots' law
+int ofx_launch_step_repeat(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks, const uint8_t *hold_mask,
+                           const ofx_action *actions, int32_t *span_reward) {
+  StepParams p = step_params(h);
+  p.beh = h->bot_behaviours;
+  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.tick0 = tick0; p.n_ticks = n_ticks;
+  p.hold_mask = hold_mask; p.actions = actions; p.span_reward = span_reward;
+  const int blocks = (h->cfg.n_arenas + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK;
+  hipLaunchKernelGGL((k_step<true, true>), dim3(blocks), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }

@@ -207,6 +207,25 @@ class ArenaBatch:
                                         -1 if observe is None else int(observe)))
         self.tick += int(n_ticks)
 
+    def step_repeat(self, behaviours, seed, tick0, n_ticks, hold_mask_ptr=None, actions_ptr=None, span_reward_ptr=None,
+                    observe=None):
+        """Action repeat (ofx_step_repeat): n_ticks lock-steps in ONE kernel launch.  The ships marked in the device
+        uint8 [N][M] at hold_mask_ptr hold their entry of the device action array for the whole span (actions_ptr=None
+        with a mask: the batch's own buffer, the one policy_actions wrote), the others follow `behaviours` lock-step by
+        lock-step; span_reward_ptr (device int32 [N][M]) receives every ship's rewards summed over the span; `observe`
+        = a nat.MAP_* type rasterised once after the last lock-step.  Bit-identical to n_ticks x (bot_actions, the
+        held entries overwritten, step).  Advances `tick` by n_ticks; does not synchronise."""
+        b = np.array([nat.BEHAVIOURS[x] if not isinstance(x, (int, np.integer)) else int(x) for x in behaviours],
+                     dtype=np.int32)
+        if b.shape != (self.M,):
+            raise Exception("behaviours must have one entry per ship")
+        if hold_mask_ptr is not None and actions_ptr is None:
+            actions_ptr = self._actions.ptr
+        nat.check(nat.lib().ofx_step_repeat(self._h, b.ctypes.data_as(C.c_void_p), seed, int(tick0), int(n_ticks),
+                                            hold_mask_ptr, actions_ptr, span_reward_ptr,
+                                            -1 if observe is None else int(observe)))
+        self.tick += int(n_ticks)
+
     def actions_host(self):
         self.sync()
         return self._actions.download(ACTION_DTYPE, (self.N, self.M))
@@ -457,6 +476,12 @@ class ArenaBatch:
     def replay_capture(self, tick, ship_mask_ptr=None, iaction_ptr=None, ipointer_ptr=None):
         """QlearnIA.play bookkeeping + Trainer.remember for this lock-step; call before step()."""
         nat.check(nat.lib().ofx_replay_capture(self._h, int(tick), ship_mask_ptr, iaction_ptr, ipointer_ptr))
+
+    def replay_reward_source(self, reward_ptr):
+        """Where the captures take a completed row's reward from: a device int32 [N][M] the caller owns (step_repeat's
+        span_reward), None = the state's reward field, the default.  Element 0 of the stored observation head stays the
+        state's reward either way.  Does not synchronise."""
+        nat.check(nat.lib().ofx_replay_reward_source(self._h, reward_ptr))
 
     def agents_first_done(self, ship_mask_ptr, seen_buf):
         """How many selected ships are destroyed now and not yet marked in `seen_buf` (DeviceBuffer, uint8 [N][M]); marks

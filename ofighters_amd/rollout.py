@@ -149,6 +149,19 @@ class TrainingRollout(ShardedRollout):
     policy ship of an evaluation arena - the one number that shows whether the current weights play better.  eval_arenas
     alone leaves every learning arena at exponent 1.  With both off, _play makes exactly the calls it always made.
 
+    Opt-in, not in the reference (Mnih et al. 2015, "frame skip"): `action_repeat=K` (an integer >= 1, 1 = off) makes one
+    `lockstep()` one DECISION that is held for K lock-steps.  The episode-end check and `_play` run as they are, then ONE
+    engine.step_repeat (ofx_step_repeat: K lock-steps inside one kernel launch, the policy ships on the action just
+    packed, the others on the bots' law lock-step by lock-step, the maps rasterised once at the end) stands where
+    bot_actions + step + rasterise stood, and `tick` advances by K.  The rollout owns an int32 [N][M] device buffer that
+    receives every ship's rewards summed over the span (undiscounted) and registers it with engine.replay_reward_source:
+    the row the next capture completes carries the whole span's reward, while element 0 of the stored observation head
+    stays the state's reward, as the live forward sees it.  Under action_repeat `total_steps`, `collecting_steps`,
+    `replay_every`, the epsilon schedule, `capture_tick` and the argument of run() all count DECISIONS, not lock-steps;
+    `episode_ticks`, `tick` and the bots' counter ticks stay lock-steps.  K must divide `episode_ticks` and `start_tick`
+    (a span never crosses an episode end): ValueError before the first device call otherwise.  With K == 1 none of this
+    exists and lockstep() / _play make exactly the calls they always made.
+
     engine    ArenaBatch
     trainer   DeviceTrainer built on that engine (owns weights, Adam state, epsilon, the replay memory)
     policy_ships  ship slots driven by the policy (the stock line-up has ONE, lib/ofighters.py:53); the others
@@ -157,8 +170,16 @@ class TrainingRollout(ShardedRollout):
 
     def __init__(self, engine, trainer, behaviours, seed, policy_ships=(0,), is_learning=True, collecting_steps=20,
                  replay_every=50, replay_on_death=True, snapshot_every=50, snapshot_folder=None, checkpoint_every=0,
-                 checkpoint_folder=None, epsilon_ladder=None, eval_arenas=0, total_arenas=None, score_bands=8, **kw):
+                 checkpoint_folder=None, epsilon_ladder=None, eval_arenas=0, total_arenas=None, score_bands=8,
+                 action_repeat=1, **kw):
         from . import exploration
+        self.action_repeat = exploration._integer("action_repeat", action_repeat, 1)
+        if self.action_repeat > 1:                 # every argument is checked before the first device call
+            for name, default in (("episode_ticks", 200), ("start_tick", 0)):
+                v = exploration._integer(name, kw.get(name, default), 0)
+                if v % self.action_repeat:
+                    raise ValueError("action_repeat = %d must divide %s = %d (a span never crosses an episode end)"
+                                     % (self.action_repeat, name, v))
         self.ladder_on = epsilon_ladder is not None or isinstance(eval_arenas, bool) or eval_arenas != 0
         self.epsilon_ladder, self.eval_arenas = None, 0
         if self.ladder_on:                         # every argument is checked before the first device call
@@ -209,6 +230,11 @@ class TrainingRollout(ShardedRollout):
         engine.policy_pin_weights(trainer.weights.ptr)
         self.policy = self._play
         self.capture_tick = 0                      # ofx_replay_capture's clock: never restarts at episode ends
+        if self.action_repeat > 1:
+            # every ship's rewards summed over the last span: what the next capture's completed rows carry
+            span = np.zeros((engine.N, engine.M), np.int32)
+            self._span = DeviceBuffer(span.nbytes).upload(span)
+            engine.replay_reward_source(self._span.ptr)
 
     def _episode_end(self):
         total = super()._episode_end()
@@ -229,8 +255,24 @@ class TrainingRollout(ShardedRollout):
                                                     folder=self.snapshot_folder))
         return total
 
+    def _decision(self):
+        """lockstep() under action_repeat = K > 1: one decision, held for K lock-steps in one launch."""
+        from . import _native as nat
+        if self.tick > 0 and self.tick % self.episode_ticks == 0:
+            self._episode_end()
+        self._play(self.e)
+        K, p = self.action_repeat, self.probe
+        if p: p("step", True, K)       # K lock-steps go down in this one call
+        self.e.step_repeat(self.behaviours, self.seed, self.tick, K, hold_mask_ptr=self._mask.ptr,
+                           span_reward_ptr=self._span.ptr, observe=nat.MAP_U8 if self.observe else None)
+        if p: p("step", False, K)
+        self.tick += K
+
     def lockstep(self):
-        super().lockstep()
+        if self.action_repeat > 1:
+            self._decision()
+        else:
+            super().lockstep()
         if (self.checkpoint_every and self.checkpoint_folder is not None and self.tick % self.episode_ticks == 0
                 and (self.episode + 1) % self.checkpoint_every == 0):   # this lock-step completed episode number episode + 1
             import os
