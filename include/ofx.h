@@ -160,6 +160,41 @@ int ofx_restart(ofx_handle *h, const int32_t *draws, const uint8_t *arena_mask);
 int ofx_spawn_random(ofx_handle *h, uint64_t seed);
 int ofx_restart_random(ofx_handle *h, uint64_t seed, uint32_t episode);
 
+/* ---- per-arena episodes (opt-in): restart an arena when its own episode is over ---------
+ * Every vectorised RL environment restarts a sub-environment when ITS episode ends; ofx_restart* restart on a clock the
+ * caller keeps for all arenas.  ofx_restart_finished is the device-side rule, called once per decision at the head of
+ * the lock-step - where the caller's episode-end check stands, before ofx_bot_actions and the forward.  One kernel (wave
+ * per arena, lane = ship, the decision one ballot, no block barrier), enqueued on the handle's stream; does not
+ * synchronise.  All pointers are DEVICE pointers.
+ * Handle-owned state, allocated and zeroed by the first call (or by ofx_autoreset_set_state), freed by ofx_destroy:
+ *   arena_episode uint32 [N], dead_once uint8 [N][M], restarted uint8 [N] (the arenas the LAST call restarted).
+ * The rule, per arena a:
+ *  - ship i is selected when ship_mask[a][i] != 0 (uint8 [N][M]); ship_mask == NULL selects every ship.
+ *  - a selected ship that is not alive is FINISHED iff dead_once[a][i] was already set; otherwise the call sets
+ *    dead_once[a][i] and the ship is not finished yet.  A destroyed ship is therefore finished on the SECOND call that
+ *    sees it dead: between the two the caller's one lock-step captured the losing frame (done = 1) and latched the agent,
+ *    the reference's order (agents/qlearnIA_V2.py:376-391).
+ *  - the arena restarts iff at least one ship is selected and every selected ship is finished, or
+ *    max_ticks > 0 && OFX_F_TIME[a] >= max_ticks (max_ticks == 0: no clock).
+ * A restart: arena_episode[a] += 1; every ship of the arena gets exactly ofx_restart's treatment, quirks included, on
+ * the draws of ofx_restart_random(seed, arena_episode[a]) for that arena - Philox counter (global arena, ship,
+ * arena_episode[a]), the reset stream; with sums != NULL and g = group ? group[a] : 0 inside [0, n_groups):
+ * sums[g][i] += the score banked, sums[g][M] += 1, sums[g][M+1] += OFX_F_TIME[a] before it is zeroed (the episode's
+ * length in lock-steps) - sums is the caller's int64 [n_groups][M+2], added to with 64-bit atomics and zeroed by the
+ * caller, ofx_episode_scores' sums are not touched; dead_once[a][*] = 0; seen[a][*] = 0 when seen (uint8 [N][M], the
+ * latch array of ofx_agents_first_done) is given; and, while a replay memory exists, the arena's agents forget
+ * previous_* and their done latch as at ofx_restart.  An arena that does not restart changes in dead_once alone.
+ * ofx_spawn* zero arena_episode and dead_once; ofx_restart* clear dead_once of the arenas they restart and leave
+ * arena_episode alone.
+ * OFX_ERR_INVALID: NULL handle, max_ticks < 0, n_groups < 1 or > N, group without sums; OFX_ERR_STATE before ofx_spawn.
+ * ofx_autoreset_state_host reads the state (any pointer may be NULL; synchronises), ofx_autoreset_set_state writes
+ * arena_episode and dead_once from the host for a checkpoint (NULL: that array stays; allocates; synchronises).  The
+ * reader returns OFX_ERR_STATE while nothing is allocated, the setter before ofx_spawn.                              */
+int ofx_restart_finished(ofx_handle *h, uint64_t seed, const uint8_t *ship_mask, int32_t max_ticks, uint8_t *seen,
+                         const int32_t *group, int32_t n_groups, int64_t *sums);
+int ofx_autoreset_state_host(ofx_handle *h, uint32_t *episode_host, uint8_t *dead_once_host, uint8_t *restarted_host);
+int ofx_autoreset_set_state(ofx_handle *h, const uint32_t *episode_host, const uint8_t *dead_once_host);
+
 /* ---- the tick ----------------------------------------------------------
  * ofx_step = Agent.step bookkeeping for every ship, dead included
  *            (score += reward; reward = 0: agents/agent.py:66-74, ship.py:260-262)

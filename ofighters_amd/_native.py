@@ -93,6 +93,9 @@ SIGNATURES = {
     "ofx_restart": (_i, [_vp, _vp, _vp]),
     "ofx_spawn_random": (_i, [_vp, _u64]),
     "ofx_restart_random": (_i, [_vp, _u64, _u32]),
+    "ofx_restart_finished": (_i, [_vp, _u64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp]),
+    "ofx_autoreset_state_host": (_i, [_vp, _vp, _vp, _vp]),
+    "ofx_autoreset_set_state": (_i, [_vp, _vp, _vp]),
     "ofx_step": (_i, [_vp, _vp]),
     "ofx_rasterise": (_i, [_vp, _i, _vp, _vp]),
     "ofx_map_bytes": (_sz, [_vp, _i]),

@@ -8,7 +8,11 @@ counter, and a fit is reproducible to the bit, so nothing else is hidden):
                      that must match at restore); the rollout's counters; the index of the sections
     rollout/*        losses, epsilons, score_log, the `_seen_done` latch; rung_log only under an exploration ladder or
                      evaluation arenas (the ladder itself is re-derived by the constructor from the fingerprint's arguments);
-                     span_reward (int32 [N][M], the last span's summed rewards) only under action_repeat > 1
+                     span_reward (int32 [N][M], the last span's summed rewards) only under action_repeat > 1;
+                     auto_sums (int64 [G][M+2], what the running reporting period has banked) and length_log only under
+                     auto_reset
+    autoreset/*      only under auto_reset: arena_episode (uint32 [N]) and dead_once (uint8 [N][M]) of
+                     ofx_restart_finished
     arena/<field>    the 19 state fields of the arenas (ArenaBatch.state_dict)
     trainer/*        weights, Adam m and v, the target blob, the loss and gradient-norm lists (DeviceTrainer.state_dict)
     replay/<k>       the replay memory as ofx_replay_export blobs of consecutive arena chunks, each chosen from
@@ -133,6 +137,8 @@ def rollout_fingerprint(r):
                   score_bands=int(r.score_bands))
     if getattr(r, "action_repeat", 1) > 1:
         fp["action_repeat"] = int(r.action_repeat)
+    if getattr(r, "auto_reset", False):
+        fp["auto_reset"] = True
     return fp
 
 
@@ -179,6 +185,13 @@ def save(rollout, path, chunk_bytes=None):
                                                                                    e.M + 1))
         if getattr(rollout, "action_repeat", 1) > 1:
             w.add("rollout/span_reward", rollout._span.download(np.int32, (e.N, e.M)))
+        if getattr(rollout, "auto_reset", False):
+            ar = e.autoreset_state()
+            w.add("autoreset/arena_episode", ar["arena_episode"])
+            w.add("autoreset/dead_once", ar["dead_once"])
+            w.add("rollout/auto_sums", rollout._auto_sums.download(np.int64, (rollout._auto_groups, e.M + 2)))
+            w.add("rollout/length_log", np.array(rollout.length_log, np.int64).reshape(len(rollout.length_log),
+                                                                                       rollout._auto_groups))
         for name, a in es.items():
             if name not in ("episode", "tick"):
                 w.add("arena/" + name, a)
@@ -244,5 +257,11 @@ def load(rollout, path):
     rollout._seen_done.upload(rd.array("rollout/seen_done"))
     if getattr(rollout, "action_repeat", 1) > 1:                       # (the fingerprints agree: the section is there)
         rollout._span.upload(rd.array("rollout/span_reward"))          # the next capture's completed rows read it
+    if getattr(rollout, "auto_reset", False):                          # (the fingerprints agree: the sections are there)
+        e.load_autoreset_state({"arena_episode": rd.array("autoreset/arena_episode"),
+                                "dead_once": rd.array("autoreset/dead_once")})
+        e.sync()
+        rollout._auto_sums.upload(rd.array("rollout/auto_sums"))       # the running reporting period goes on
+        rollout.length_log = [g.copy() for g in rd.array("rollout/length_log")]
     e.policy_pin_weights(t.weights.ptr)             # the blob changed under the pin: prepare it again
     return m

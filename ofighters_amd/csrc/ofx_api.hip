@@ -165,7 +165,8 @@ extern "C" int ofx_destroy(ofx_handle *h) {
   ofx_state &s = h->st;
   void *ptrs[] = {s.ship_x, s.ship_y, s.ship_px, s.ship_py, s.hull, s.reward, s.score, s.obs_reward, s.last_score,
                   s.alive, s.killer, s.time, s.n_lasers, s.laser_x, s.laser_y, s.laser_dx, s.laser_dy,
-                  s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->res_iaction, h->fitws, h->fitws2, h->applyws, h->trunk_stat, h->act_vals, h->eps_expo};
+                  s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->res_iaction, h->fitws, h->fitws2, h->applyws, h->trunk_stat, h->act_vals, h->eps_expo,
+                  h->ar_episode, h->ar_dead_once, h->ar_restarted};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (int t = 0; t < 5; t++) for (int w = 0; w < 2; w++) if (h->maps[t][w]) (void)hipFree(h->maps[t][w]);
   if (h->events) { (void)hipEventDestroy(h->ev0); (void)hipEventDestroy(h->ev1); }
@@ -231,6 +232,7 @@ struct ResetParams {
   ofx_state st;
   const int32_t *draws;      // [N][M][2] or null -> counter RNG
   const uint8_t *mask;       // [N] or null
+  uint8_t *dead_once;        // [N][M] of ofx_restart_finished or null: cleared for the arenas that restart
   uint32_t k0, k1, episode;
 };
 
@@ -258,8 +260,32 @@ __global__ void k_spawn(ResetParams p) {
   if (i == 0) { p.st.time[a] = 0; p.st.n_lasers[a] = 0; }
 }
 
-// Battleground.restart -> Ship.reset -> Agent.reset
-// (battleground.py:108-117, ship.py:92-106, agent.py:59-64)
+// Battleground.restart -> Ship.reset -> Agent.reset for ONE ship on the draws (dx, dy)
+// (battleground.py:108-117, ship.py:92-106, agent.py:59-64): the one place the quirks live, shared by k_restart and
+// k_restart_finished.  The banked score goes to sums[i] and the arena count to sums[M]; with `lengths` the arena's
+// clock, as it stood, is added there too before it is zeroed.  sums == null: nothing is counted.
+__device__ __forceinline__ void restart_ship(const ofx_state &st, int M, int a, int i, int dx, int dy, long long *sums,
+                                             long long *lengths) {
+  const int t = a * M + i;
+  const int sc = st.score[t];
+  st.last_score[t] = sc;                         // scores.append(score)
+  if (sums) atomicAdd((unsigned long long *)&sums[i], (unsigned long long)(long long)sc);
+  st.score[t] = 0;                               // reward is NOT cleared (agent.py:59-64)
+  const int ox = st.ship_x[t], oy = st.ship_y[t];
+  st.ship_px[t] = ox;                            // pointing = Point(old x, old y)  ship.py:99
+  st.ship_py[t] = oy;
+  st.ship_x[t] = dx ? dx : ox;                   // `x or self.body.x`            ship.py:100-101
+  st.ship_y[t] = dy ? dy : oy;
+  st.alive[t] = 1;                               // state = "flying"; hull NOT restored
+  st.killer[t] = -1;
+  if (i == 0) {
+    if (sums && lengths) atomicAdd((unsigned long long *)lengths, (unsigned long long)(long long)st.time[a]);
+    st.time[a] = 0;
+    st.n_lasers[a] = 0;                          // self.lasers = []
+    if (sums) atomicAdd((unsigned long long *)&sums[M], 1ull);
+  }
+}
+
 __global__ void k_restart(ResetParams p) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.N * p.M) return;
@@ -275,22 +301,55 @@ __global__ void k_restart(ResetParams p) {
     dx = ofx_draw_int(r[0], p.W);
     dy = ofx_draw_int(r[1], p.H);
   }
-  const int sc = p.st.score[t];
-  p.st.last_score[t] = sc;                       // scores.append(score)
-  atomicAdd((unsigned long long *)&p.st.episode_sums[i], (unsigned long long)(long long)sc);
-  p.st.score[t] = 0;                             // reward is NOT cleared (agent.py:59-64)
-  const int ox = p.st.ship_x[t], oy = p.st.ship_y[t];
-  p.st.ship_px[t] = ox;                          // pointing = Point(old x, old y)  ship.py:99
-  p.st.ship_py[t] = oy;
-  p.st.ship_x[t] = dx ? dx : ox;                 // `x or self.body.x`            ship.py:100-101
-  p.st.ship_y[t] = dy ? dy : oy;
-  p.st.alive[t] = 1;                             // state = "flying"; hull NOT restored
-  p.st.killer[t] = -1;
-  if (i == 0) {
-    p.st.time[a] = 0;
-    p.st.n_lasers[a] = 0;                        // self.lasers = []
-    atomicAdd((unsigned long long *)&p.st.episode_sums[p.M], 1ull);
+  restart_ship(p.st, p.M, a, i, dx, dy, p.st.episode_sums, nullptr);
+  if (p.dead_once) p.dead_once[t] = 0;
+}
+
+// ofx_restart_finished (include/ofx.h has the rule).  One 64-lane wave per arena, lane = ship, four arenas per block
+// as in k_replay_capture; the decision is a ballot over the selected lanes, so every branch below it is wave-uniform.
+// No block barrier; lanes >= M take part in no ballot and touch no memory.
+struct FinishedParams {
+  int N, M, W, H, arena_base, max_ticks, n_groups;
+  ofx_state st;
+  const uint8_t *ship_mask;  // [N][M] or null = every ship
+  uint8_t *seen;             // [N][M] or null
+  const int32_t *group;      // [N] or null = group 0
+  long long *sums;           // [n_groups][M+2] or null
+  uint32_t *arena_episode;   // [N]
+  uint8_t *dead_once;        // [N][M]
+  uint8_t *restarted;        // [N]
+  uint32_t k0, k1;
+};
+
+__global__ __launch_bounds__(256) void k_restart_finished(FinishedParams p) {
+  const int a = blockIdx.x * OFX_ARENAS_PER_BLOCK + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (a >= p.N) return;  // wave-uniform
+  const bool ship = lane < p.M;
+  const int t = a * p.M + lane;  // used under `ship` only
+  const bool selected = ship && (!p.ship_mask || p.ship_mask[t]);
+  bool finished = false;
+  if (selected && !p.st.alive[t]) {
+    if (p.dead_once[t]) finished = true;
+    else p.dead_once[t] = 1;   // seen dead once: the lock-step that follows captures the losing frame
   }
+  const unsigned long long sel = __ballot(selected), fin = __ballot(finished);
+  const int time = p.st.time[a];
+  const bool go = (sel != 0ull && fin == sel) || (p.max_ticks > 0 && time >= p.max_ticks);
+  if (lane == 0) p.restarted[a] = go ? 1 : 0;
+  if (!go) return;  // wave-uniform
+  const uint32_t episode = p.arena_episode[a] + 1u;
+  if (lane == 0) p.arena_episode[a] = episode;
+  if (!ship) return;
+  uint32_t r[4];
+  ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)lane, episode, OFX_STREAM_RESET, p.k0, p.k1, r);
+  long long *row = nullptr;
+  if (p.sums) {
+    const int g = p.group ? p.group[a] : 0;
+    if (g >= 0 && g < p.n_groups) row = p.sums + (size_t)g * (p.M + 2);
+  }
+  restart_ship(p.st, p.M, a, lane, ofx_draw_int(r[0], p.W), ofx_draw_int(r[1], p.H), row, row ? row + p.M + 1 : nullptr);
+  p.dead_once[t] = 0;
+  if (p.seen) p.seen[t] = 0;
 }
 
 static ResetParams reset_params(ofx_handle *h, const int32_t *draws, const uint8_t *mask, uint64_t seed,
@@ -298,7 +357,7 @@ static ResetParams reset_params(ofx_handle *h, const int32_t *draws, const uint8
   ResetParams p;
   p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height;
   p.arena_base = h->cfg.arena_base;
-  p.st = h->st; p.draws = draws; p.mask = mask;
+  p.st = h->st; p.draws = draws; p.mask = mask; p.dead_once = h->ar_dead_once;
   p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.episode = episode;
   return p;
 }
@@ -311,6 +370,10 @@ static int do_spawn(ofx_handle *h, const int32_t *draws, uint64_t seed) {
   OFX_HIP(hipMemsetAsync(h->st.episode_sums, 0, sizeof(long long) * (p.M + 1), h->stream));
   hipLaunchKernelGGL(k_spawn, dim3((T + 255) / 256), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
+  if (h->ar_episode) {  // ofx_restart_finished's counters start again with the arenas
+    OFX_HIP(hipMemsetAsync(h->ar_episode, 0, sizeof(uint32_t) * p.N, h->stream));
+    OFX_HIP(hipMemsetAsync(h->ar_dead_once, 0, (size_t)T, h->stream));
+  }
   h->spawned = true;
   return ofx_replay_episode_reset(h, nullptr);  // fresh agents: previous_* = None
 }
@@ -338,6 +401,76 @@ extern "C" int ofx_restart(ofx_handle *h, const int32_t *draws, const uint8_t *a
 }
 extern "C" int ofx_restart_random(ofx_handle *h, uint64_t seed, uint32_t episode) {
   return do_restart(h, nullptr, nullptr, seed, episode);
+}
+
+// ------------------------------------------------ per-arena episodes: restart the arenas whose own episode is over
+// one block for the three arrays, zeroed on the handle's stream (in order with whatever is enqueued next)
+static int autoreset_alloc(ofx_handle *h) {
+  if (h->ar_episode) return OFX_OK;
+  const size_t N = (size_t)h->cfg.n_arenas, NM = N * h->cfg.n_ships;
+  OFX_HIP(hipMalloc((void **)&h->ar_episode, N * sizeof(uint32_t)));
+  if (hipMalloc((void **)&h->ar_dead_once, NM) != hipSuccess || hipMalloc((void **)&h->ar_restarted, N) != hipSuccess) {
+    if (h->ar_dead_once) (void)hipFree(h->ar_dead_once);
+    (void)hipFree(h->ar_episode);
+    h->ar_episode = nullptr; h->ar_dead_once = nullptr; h->ar_restarted = nullptr;
+    ofx_set_error("ofx_restart_finished: out of device memory");
+    return OFX_ERR_HIP;
+  }
+  OFX_HIP(hipMemsetAsync(h->ar_episode, 0, N * sizeof(uint32_t), h->stream));
+  OFX_HIP(hipMemsetAsync(h->ar_dead_once, 0, NM, h->stream));
+  OFX_HIP(hipMemsetAsync(h->ar_restarted, 0, N, h->stream));
+  return OFX_OK;
+}
+
+extern "C" int ofx_restart_finished(ofx_handle *h, uint64_t seed, const uint8_t *ship_mask, int32_t max_ticks,
+                                    uint8_t *seen, const int32_t *group, int32_t n_groups, int64_t *sums) {
+  if (!h) { ofx_set_error("null handle"); return OFX_ERR_INVALID; }
+  if (max_ticks < 0) { ofx_set_error("ofx_restart_finished: max_ticks must be >= 0 (0 = no clock), got %d", max_ticks); return OFX_ERR_INVALID; }
+  if (n_groups < 1 || n_groups > h->cfg.n_arenas) {
+    ofx_set_error("ofx_restart_finished: n_groups must be in [1, %d] (got %d)", h->cfg.n_arenas, n_groups);
+    return OFX_ERR_INVALID;
+  }
+  if (group && !sums) { ofx_set_error("ofx_restart_finished: group given without sums"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_restart_finished before ofx_spawn"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  int rc = autoreset_alloc(h);
+  if (rc) return rc;
+  FinishedParams p;
+  p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height;
+  p.arena_base = h->cfg.arena_base; p.max_ticks = max_ticks; p.n_groups = n_groups;
+  p.st = h->st; p.ship_mask = ship_mask; p.seen = seen; p.group = group; p.sums = (long long *)sums;
+  p.arena_episode = h->ar_episode; p.dead_once = h->ar_dead_once; p.restarted = h->ar_restarted;
+  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32);
+  hipLaunchKernelGGL(k_restart_finished, dim3((p.N + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK), dim3(256), 0,
+                     h->stream, p);
+  OFX_HIP(hipGetLastError());
+  return ofx_replay_episode_reset(h, h->ar_restarted);  // QlearnIA.reset of the restarted arenas' agents
+}
+
+extern "C" int ofx_autoreset_state_host(ofx_handle *h, uint32_t *episode_host, uint8_t *dead_once_host,
+                                        uint8_t *restarted_host) {
+  if (!h) { ofx_set_error("null handle"); return OFX_ERR_INVALID; }
+  if (!h->ar_episode) { ofx_set_error("ofx_autoreset_state_host before ofx_restart_finished"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const size_t N = (size_t)h->cfg.n_arenas, NM = N * h->cfg.n_ships;
+  if (episode_host) OFX_HIP(hipMemcpyAsync(episode_host, h->ar_episode, N * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  if (dead_once_host) OFX_HIP(hipMemcpyAsync(dead_once_host, h->ar_dead_once, NM, hipMemcpyDeviceToHost, h->stream));
+  if (restarted_host) OFX_HIP(hipMemcpyAsync(restarted_host, h->ar_restarted, N, hipMemcpyDeviceToHost, h->stream));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  return OFX_OK;
+}
+
+extern "C" int ofx_autoreset_set_state(ofx_handle *h, const uint32_t *episode_host, const uint8_t *dead_once_host) {
+  if (!h) { ofx_set_error("null handle"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_autoreset_set_state before ofx_spawn"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  int rc = autoreset_alloc(h);
+  if (rc) return rc;
+  const size_t N = (size_t)h->cfg.n_arenas, NM = N * h->cfg.n_ships;
+  if (episode_host) OFX_HIP(hipMemcpyAsync(h->ar_episode, episode_host, N * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  if (dead_once_host) OFX_HIP(hipMemcpyAsync(h->ar_dead_once, dead_once_host, NM, hipMemcpyHostToDevice, h->stream));
+  OFX_HIP(hipStreamSynchronize(h->stream));  // the host arrays are the caller's again
+  return OFX_OK;
 }
 
 // --------------------------------------------------------------------- tick

@@ -87,6 +87,11 @@ struct ofx_handle {
   float *act_vals;                 // [4][N*M] q_sa, p_sp, v_act, v_ptr, then act [N*M][2], ptr_max [N*M], ptr_probe [N*M]
   bool act_called;                 // the LAST ofx_policy_act wrote all four of the handle's arrays (all outputs NULL)
   double *eps_expo;                // [N] ofx_policy_epsilon_ladder: arena a explores at epsilon^eps_expo[a] (+inf: never); null = no ladder
+  // ofx_restart_finished (one allocation at its first call, null before): per-arena episode counter, the ships seen
+  // dead by one call already, and the arenas the last call restarted
+  uint32_t *ar_episode;            // [N]
+  uint8_t *ar_dead_once;           // [N][M]
+  uint8_t *ar_restarted;           // [N]
 };
 #define OFX_RING_MAX 65536         /* numbered events of ofx_event_record */
 

@@ -162,6 +162,41 @@ class ArenaBatch:
         self.episode += 1
         nat.check(nat.lib().ofx_restart_random(self._h, seed, self.episode))
 
+    # ------------------------------------------- per-arena episodes (include/ofx.h: the contract)
+    def restart_finished(self, seed, ship_mask_ptr=None, max_ticks=0, seen_buf=None, group_buf=None, n_groups=1,
+                         sums_buf=None):
+        """Restart, on the device, the arenas whose own episode is over (ofx_restart_finished): every ship selected by
+        the device uint8 [N][M] at ship_mask_ptr (None = all) was seen destroyed by an earlier call already, or the
+        arena's clock F_TIME has reached max_ticks (0 = no clock).  Call it once per decision, before bot_actions and
+        the forward.  seen_buf (DeviceBuffer, uint8 [N][M], agents_first_done's latches) is cleared for the restarted
+        arenas; sums_buf (DeviceBuffer, int64 [n_groups][M+2], zeroed by the caller) accumulates per group of group_buf
+        (DeviceBuffer, int32 [N]; None = one group) the banked scores, the episodes and their lock-steps.  `episode` is
+        not advanced: every arena counts its own (autoreset_state).  Does not synchronise."""
+        nat.check(nat.lib().ofx_restart_finished(self._h, seed, ship_mask_ptr, int(max_ticks),
+                                                 seen_buf.ptr if seen_buf is not None else None,
+                                                 group_buf.ptr if group_buf is not None else None, int(n_groups),
+                                                 sums_buf.ptr if sums_buf is not None else None))
+
+    def autoreset_state(self):
+        """restart_finished's state on the host: arena_episode uint32 [N], dead_once uint8 [N][M] and restarted uint8
+        [N], the arenas the last call restarted.  OfxError (OFX_ERR_STATE) before the first call.  Synchronises."""
+        ep, dead, res = np.empty(self.N, np.uint32), np.empty((self.N, self.M), np.uint8), np.empty(self.N, np.uint8)
+        nat.check(nat.lib().ofx_autoreset_state_host(self._h, *[a.ctypes.data_as(C.c_void_p) for a in (ep, dead, res)]))
+        return {"arena_episode": ep, "dead_once": dead, "restarted": res}
+
+    def load_autoreset_state(self, d):
+        """Upload autoreset_state()'s arena_episode and dead_once (a checkpoint's); shapes and dtypes are checked first."""
+        arrs = []
+        for name, dt, shape in (("arena_episode", np.uint32, (self.N,)), ("dead_once", np.uint8, (self.N, self.M))):
+            if name not in d:
+                raise ValueError("ArenaBatch.load_autoreset_state: %r is missing" % name)
+            a = np.asarray(d[name])
+            if a.dtype != dt or a.shape != shape:
+                raise ValueError("ArenaBatch.load_autoreset_state: %r is %s %s, this batch holds %s %s"
+                                 % (name, a.dtype, a.shape, np.dtype(dt), shape))
+            arrs.append(np.ascontiguousarray(a))
+        nat.check(nat.lib().ofx_autoreset_set_state(self._h, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+
     def set_ships(self, x=None, y=None, px=None, py=None):
         """Crafted starts (test / fixture use): overwrite ship fields [N,M]."""
         for f, v in ((nat.F_SHIP_X, x), (nat.F_SHIP_Y, y), (nat.F_SHIP_PX, px), (nat.F_SHIP_PY, py)):

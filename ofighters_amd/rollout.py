@@ -162,6 +162,30 @@ class TrainingRollout(ShardedRollout):
     (a span never crosses an episode end): ValueError before the first device call otherwise.  With K == 1 none of this
     exists and lockstep() / _play make exactly the calls they always made.
 
+    Opt-in, not in the reference (every vectorised RL environment restarts a sub-environment when ITS episode ends):
+    `auto_reset=True` (a bool; anything else is a ValueError before the first device call) gives every arena its own
+    episodes.  Without it all arenas restart together every `episode_ticks` lock-steps, and an arena whose learning ship
+    was destroyed early pays the forward for the rest of the episode without capturing a row.  With it every lockstep()
+    - every decision under action_repeat - STARTS with engine.restart_finished (ofx_restart_finished: one kernel, nothing
+    comes back to the host) on the full policy mask, so evaluation arenas restart on their ships' deaths too: an arena
+    restarts when all its policy ships are finished or its own clock has reached `episode_ticks`, on the draws of its own
+    episode counter; its `_seen_done` latches and its agents' previous_* / done latch are cleared on the device
+    (`_seen_done` is never zeroed from the host, restart_random is never called after the spawn).  A destroyed ship is
+    finished on the SECOND call that sees it dead: the lock-step in between is the one in which _play counts the death,
+    replays and captures the losing frame (done = 1), the reference's order (agents/qlearnIA_V2.py:376-391) - so an arena
+    restarts one lock-step after its last learner's death was seen, not on that lock-step.  What the restarts bank - per
+    group under the ladder / evaluation options, else in one row - accumulates on the device in a rollout-owned int64
+    [G][M+2]: M scores, the episodes, their lock-steps.  `tick % episode_ticks == 0` (tick > 0) is then the end of a
+    REPORTING PERIOD, nothing restarts because of it: the sums are downloaded, zeroed and all-reduced like score_log, and
+    appended - columns 0..M summed over the groups to `score_log` (index M: the episodes that ended in the period, no
+    longer the arena count), the [G][M+1] block to `rung_log` under the ladder options, column M+1 as [G] to `length_log`
+    (lock-steps of the finished episodes; over the episodes = the mean episode length).  `episode`, `epsilons`,
+    `snapshot_every` and `checkpoint_every` count reporting periods; `eval_scores` keeps its formula (index M is still
+    the episode count).  engine.episode stays 0: the arenas' counters are engine.autoreset_state()["arena_episode"].
+    Under action_repeat = K an arena's clock advances by K per decision and K divides episode_ticks, so the clock still
+    ends an episode exactly there.  The trainer does not change: n-step chains stop at the cleared previous_*.  With
+    auto_reset=False none of this exists and lockstep() makes exactly the calls it always made.
+
     engine    ArenaBatch
     trainer   DeviceTrainer built on that engine (owns weights, Adam state, epsilon, the replay memory)
     policy_ships  ship slots driven by the policy (the stock line-up has ONE, lib/ofighters.py:53); the others
@@ -171,8 +195,11 @@ class TrainingRollout(ShardedRollout):
     def __init__(self, engine, trainer, behaviours, seed, policy_ships=(0,), is_learning=True, collecting_steps=20,
                  replay_every=50, replay_on_death=True, snapshot_every=50, snapshot_folder=None, checkpoint_every=0,
                  checkpoint_folder=None, epsilon_ladder=None, eval_arenas=0, total_arenas=None, score_bands=8,
-                 action_repeat=1, **kw):
+                 action_repeat=1, auto_reset=False, **kw):
         from . import exploration
+        if not isinstance(auto_reset, (bool, np.bool_)):   # every argument is checked before the first device call
+            raise ValueError("auto_reset must be a bool, got %r" % (auto_reset,))
+        self.auto_reset = bool(auto_reset)
         self.action_repeat = exploration._integer("action_repeat", action_repeat, 1)
         if self.action_repeat > 1:                 # every argument is checked before the first device call
             for name, default in (("episode_ticks", 200), ("start_tick", 0)):
@@ -235,8 +262,49 @@ class TrainingRollout(ShardedRollout):
             span = np.zeros((engine.N, engine.M), np.int32)
             self._span = DeviceBuffer(span.nbytes).upload(span)
             engine.replay_reward_source(self._span.ptr)
+        self.length_log = []                       # all-reduced [G] per reporting period: lock-steps of finished episodes
+        if self.auto_reset:
+            # what the restarts of a reporting period bank, per group: M scores, the episodes, their lock-steps
+            self._auto_groups = self.n_groups if self.ladder_on else 1
+            self._auto_zero = np.zeros((self._auto_groups, engine.M + 2), np.int64)
+            self._auto_sums = DeviceBuffer(self._auto_zero.nbytes).upload(self._auto_zero)
+            # the engine's counters exist from here on: a checkpoint may be written before the first lock-step
+            engine.load_autoreset_state({"arena_episode": np.zeros(engine.N, np.uint32),
+                                         "dead_once": np.zeros((engine.N, engine.M), np.uint8)})
+
+    def _restart_finished(self):
+        """The head of a lock-step under auto_reset: the arenas whose policy ships are all finished, or whose clock
+        has reached episode_ticks, restart on the device."""
+        self.e.restart_finished(self.seed, self._mask.ptr, max_ticks=self.episode_ticks, seen_buf=self._seen_done,
+                                group_buf=self._groups if self.ladder_on else None, n_groups=self._auto_groups,
+                                sums_buf=self._auto_sums)
+
+    def _period_end(self):
+        """auto_reset: `tick` reached a multiple of episode_ticks - report what the restarts since the last one banked."""
+        G, M = self._auto_groups, self.e.M
+        self.e.sync()
+        sums = self._auto_sums.download(np.int64, (G, M + 2))
+        self._auto_sums.upload(self._auto_zero)     # (after the sync: the next restart_finished adds to zeros)
+        if self.dist is not None:
+            t = self.to_tensor(sums.reshape(-1))
+            self.dist.all_reduce(t)
+            sums = np.asarray(t.cpu().numpy() if hasattr(t, "cpu") else t, dtype=np.int64).reshape(G, M + 2)
+        total = sums[:, :M + 1].sum(axis=0)
+        self.score_log.append(total.copy())
+        if self.ladder_on:
+            self.rung_log.append(sums[:, :M + 1].copy())
+        self.length_log.append(sums[:, M + 1].copy())
+        self.episode += 1
+        self.epsilons.append(self.trainer.epsilon.get())
+        if (self.is_learning and self.snapshot_folder is not None and self.snapshot_every
+                and self.episode % self.snapshot_every == 0):
+            self.snapshots.append(self.trainer.save(id="iteration-%s" % self.episode, overwrite=True,
+                                                    folder=self.snapshot_folder))
+        return total
 
     def _episode_end(self):
+        if self.auto_reset:
+            return self._period_end()
         total = super()._episode_end()
         self.episode += 1
         self.epsilons.append(self.trainer.epsilon.get())
@@ -269,6 +337,8 @@ class TrainingRollout(ShardedRollout):
         self.tick += K
 
     def lockstep(self):
+        if self.auto_reset:
+            self._restart_finished()
         if self.action_repeat > 1:
             self._decision()
         else:
