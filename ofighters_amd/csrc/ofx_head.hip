@@ -317,28 +317,61 @@ static_assert(2 * 52 * 52 <= 6400, "l1p fits under u3l");
 
 // zero-padded conv output at a plane corner from the definition: cell (yc, xc) in {0, n2 - 1}^2 of the up-sampled
 // (n2 = 2 n) plane of `get(y, x, ci)` (low-res, n x n)
-template <int CIN, int COUT, class G>
-__device__ __forceinline__ float hg_corner(G get, int n, int yc, int xc, const float *w, float bias, int co, int legacy) {
+// The taps inside the image are dy = dy0 + a, dx = dx0 + b with a, b in {0, 1} (dy0 = 1 on the first row, 0 on the last).
+// Their weights are fetched by hg_corner_w at the top of the kernel: read where they are used, each (tap, ci) was a
+// global load of its own in front of a dependent fma, 8 (uprelu2) and 16 (uprelu3) round trips in a row with the whole
+// workgroup waiting at the next barrier.
+template <int CIN, int COUT>
+__device__ __forceinline__ void hg_corner_w(const float *w, int yc, int xc, int co, float (&wr)[4 * CIN]) {
+  const int dy0 = yc == 0 ? 1 : 0, dx0 = xc == 0 ? 1 : 0;
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+#pragma unroll
+    for (int ci = 0; ci < CIN; ci++) wr[t * CIN + ci] = w[(((dy0 + (t >> 1)) * 3 + dx0 + (t & 1)) * CIN + ci) * COUT + co];
+}
+template <int CIN, class G>
+__device__ __forceinline__ float hg_corner(G get, int n, int yc, int xc, const float (&wr)[4 * CIN], float bias, int legacy) {
   float acc = bias;
-  for (int dy = 0; dy < 3; dy++) {
-    const int uy = yc + dy - 1;
-    if (uy < 0 || uy >= 2 * n) continue;
+  const int dy0 = yc == 0 ? 1 : 0, dx0 = xc == 0 ? 1 : 0;
+#pragma unroll
+  for (int a2 = 0; a2 < 2; a2++) {      // dy ascending, then dx, then ci: the order of the definition
     int ya, yb; float wy;
-    hf_taps(uy, n, ya, yb, wy, legacy);
-    for (int dx = 0; dx < 3; dx++) {
-      const int ux = xc + dx - 1;
-      if (ux < 0 || ux >= 2 * n) continue;
+    hf_taps(yc + dy0 + a2 - 1, n, ya, yb, wy, legacy);
+#pragma unroll
+    for (int b2 = 0; b2 < 2; b2++) {
       int xa, xb; float wx;
-      hf_taps(ux, n, xa, xb, wx, legacy);
+      hf_taps(xc + dx0 + b2 - 1, n, xa, xb, wx, legacy);
+#pragma unroll
       for (int ci = 0; ci < CIN; ci++) {
         const float a = get(ya, xa, ci), b = get(ya, xb, ci), d = get(yb, xa, ci), g = get(yb, xb, ci);
         const float top = a + (b - a) * wx, bot = d + (g - d) * wx;
-        acc += w[((dy * 3 + dx) * CIN + ci) * COUT + co] * (top + (bot - top) * wy);
+        acc += wr[(a2 * 2 + b2) * CIN + ci] * (top + (bot - top) * wy);
       }
     }
   }
   return fmaxf(acc, 0.f);
 }
+
+// Staging of uprelu1: only the three outer rows / columns on each side of the clamp-extended 52 x 52 plane are ever
+// read (the frame bands and the corner cells): 588 of the 2704 cells of a channel, 5 per thread.  Cell e of the list ->
+// (destination in l1p) | (source in the ship's up1 block) << 16, a compile-time table in constant memory (like kHsPick):
+// one coalesced load per cell instead of the / 588, / 52, / 6, % 6 and clamp chain (~30 vector instructions per cell).
+constexpr int HG_NB = 6 * 52 + 46 * 6, HG_NE = 2 * HG_NB, HG_PER = (HG_NE + HG_THREADS - 1) / HG_THREADS;
+struct alignas(16) HgStage { unsigned v[HG_PER * HG_THREADS]; };
+constexpr HgStage hg_make_stage() {
+  HgStage t{};
+  for (int e0 = 0; e0 < HG_PER * HG_THREADS; e0++) {
+    const int e = e0 < HG_NE ? e0 : HG_NE - 1;   // behind the list: the last cell again (loaded, never stored)
+    const int ci = e / HG_NB, k = e - ci * HG_NB;
+    int r = 0, c = 0;
+    if (k < 6 * 52) { const int rr = k / 52; r = rr < 3 ? rr : rr + 46; c = k - rr * 52; }
+    else { const int k2 = k - 6 * 52, cc = k2 % 6; r = 3 + k2 / 6; c = cc < 3 ? cc : cc + 46; }
+    const int rs = r - 1 < 0 ? 0 : r - 1 > 49 ? 49 : r - 1, cs = c - 1 < 0 ? 0 : c - 1 > 49 ? 49 : c - 1;
+    t.v[e0] = (unsigned)((ci * 52 + r) * 52 + c) | (unsigned)((ci * 50 + rs) * 50 + cs) << 16;
+  }
+  return t;
+}
+__constant__ HgStage kHgStage = hg_make_stage();
 
 __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
   __shared__ __align__(16) float sm[HG_TOTAL];
@@ -353,44 +386,49 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
   const int n16 = lane & 15, kq = lane >> 4;
   float *l1p = sm + HG_L1, *u2rb = sm + HG_RB, *u2cb = sm + HG_CB, *u3l = sm + HG_U3;
 
-  {  // uprelu1 -> LDS, clamp-extended by one cell.  Only the three outer rows / columns on each side are ever read (the
-     // frame bands and the corner cells): 588 of the 2704 cells of a channel; all loads of a thread in flight before
-     // the first store
-    constexpr int NB = 6 * 52 + 46 * 6, NE = 2 * NB, PER = (NE + HG_THREADS - 1) / HG_THREADS;  // 588 per channel, 5 per thread
-    float v[PER];
-    int at[PER];
+  // Every global load of the kernel is issued here, in front of the first LDS store and the first barrier, so that one
+  // round trip covers them all (plus one for uprelu1, whose addresses come from kHgStage): the staging list, efr and w4,
+  // the B operands of both MFMA stages (wave = band = line: loaded once), the biases, the corner cells' taps of wave 0.
+  // Nothing below waits for global memory.
+  constexpr int NE = HG_NE, PER = HG_PER;  // 588 cells per channel, 5 per thread (kHgStage)
+  unsigned at[PER];
 #pragma unroll
-    for (int u = 0; u < PER; u++) {
-      const int e = min(u * HG_THREADS + tid, NE - 1);
-      const int ci = e / NB, k = e - ci * NB;
-      int r, c;
-      if (k < 6 * 52) { const int rr = k / 52; r = rr < 3 ? rr : rr + 46; c = k - rr * 52; }
-      else { const int k2 = k - 6 * 52, cc = k2 % 6; r = 3 + k2 / 6; c = cc < 3 ? cc : cc + 46; }
-      at[u] = (ci * 52 + r) * 52 + c;
-      v[u] = p.up1[(size_t)s * 5000 + (ci * 50 + min(max(r - 1, 0), 49)) * 50 + min(max(c - 1, 0), 49)];
-    }
-#pragma unroll
-    for (int u = 0; u < PER; u++)
-      if (u * HG_THREADS + tid < NE) l1p[at[u]] = v[u];
-  }
-  if (tid < 192) efr_s[tid] = p.efr[tid];
-  if (tid < 72) w4s[tid] = p.w4raw[tid];
-  __syncthreads();
-
-  // ---- uprelu2 bands: band v, M-tile m: pixels 16 m + n16 along the band (50), all four phases ----
-  // wave = band: its B operands are loaded once
+  for (int u = 0; u < PER; u++) at[u] = kHgStage.v[u * HG_THREADS + tid];
+  const float efr_v = p.efr[min(tid, 191)], w4_v = p.w4raw[min(tid, 71)];
   float bw2[5];
 #pragma unroll
   for (int jj = 0; jj < 5; jj++) bw2[jj] = p.w2fr[(wv * 20 + 4 * jj + kq) * 16 + n16];
   float bw3[9];
 #pragma unroll
   for (int jj = 0; jj < 9; jj++) bw3[jj] = p.w3fr[(wv * 36 + 4 * jj + kq) * 16 + n16];
+  const float b2v = p.b2[n16 & 3], b3v = p.b3[n16 & 7];
+  float wc2[8], wc3[16];
+  if (wv == 0) {  // (lane & 3 = n16 & 3 and lane & 7 = n16 & 7 are the corner threads' channels: their biases are b2v, b3v)
+    hg_corner_w<2, 4>(p.w2raw, (lane >> 5) ? 99 : 0, ((lane >> 4) & 1) ? 99 : 0, lane & 3, wc2);
+    hg_corner_w<4, 8>(p.w3raw, ((lane >> 3) & 1) ? 199 : 0, ((lane >> 3) & 2) ? 199 : 0, lane & 7, wc3);
+  }
+  {  // uprelu1 -> LDS, clamp-extended by one cell.  Only the three outer rows / columns on each side are ever read (the
+     // frame bands and the corner cells): 588 of the 2704 cells of a channel; all loads of a thread in flight before
+     // the first store
+    float v[PER];
+    const float *src = p.up1 + (size_t)s * 5000;
+#pragma unroll
+    for (int u = 0; u < PER; u++) v[u] = src[at[u] >> 16];
+#pragma unroll
+    for (int u = 0; u < PER; u++)
+      if (u * HG_THREADS + tid < NE) l1p[at[u] & 0xFFFFu] = v[u];
+  }
+  if (tid < 192) efr_s[tid] = efr_v;
+  if (tid < 72) w4s[tid] = w4_v;
+  __syncthreads();
+
+  // ---- uprelu2 bands: band v, M-tile m: pixels 16 m + n16 along the band (50), all four phases ----
 #pragma unroll 1
   for (int m = 0; m < 4; m++) {
     const int v = wv;
     const int pp = min(16 * m + n16, 49);
     const int i = v == 0 ? 0 : v == 1 ? 49 : pp, j = v == 2 ? 0 : v == 3 ? 49 : pp;  // low-res pixel of the A row
-    const float bias = p.b2[n16 & 3];
+    const float bias = b2v;
     f32x4 d = {bias, bias, bias, bias};
 #pragma unroll
     for (int jj = 0; jj < 5; jj++) {  // k = 4 jj + kq: tap = 2 jj + (kq >> 1), ci = kq & 1 (k >= 18: zero weights)
@@ -424,7 +462,7 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
     float val;
     if (fy && fx) {
       auto get = [&](int yy, int xx, int ci) { return l1p[(ci * 52 + yy + 1) * 52 + xx + 1]; };
-      val = hg_corner<2, 4>(get, 50, y, x, p.w2raw, p.b2[co], co, p.legacy);
+      val = hg_corner<2>(get, 50, y, x, wc2, b2v, p.legacy);
     } else if (fx) {
       val = u2cb[(cb * 102 + y + 1) * 4 + co];
     } else {
@@ -444,10 +482,14 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
       ln[(hi ? 101 : 0) * 4 + co] = ln[(hi ? 100 : 1) * 4 + co];
     }
   }
-  for (int e = tid; e < 4 * 100 * 4; e += HG_THREADS) {  // lines: row 0, row 99, col 0, col 99
-    const int ln = e / 400, r = e - ln * 400;
-    const float *src = ln < 2 ? u2rb + (ln ? 3 : 0) * 408 : u2cb + (ln == 3 ? 3 : 0) * 408;
-    p.u2fr[(size_t)s * 1600 + e] = src[4 + r];
+  {  // lines: row 0, row 99, col 0, col 99.  Wave = line: the source band is wave-uniform, a lane walks its floats
+    const float *src = (wv < 2 ? u2rb : u2cb) + ((wv & 1) ? 3 : 0) * 408 + 4;
+    float *dst = p.u2fr + (size_t)s * 1600 + wv * 400;
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+      const int r = lane + 64 * k;
+      if (r < 400) dst[r] = src[r];
+    }
   }
   __syncthreads();
 
@@ -458,7 +500,7 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
     const int qq = min(16 * m + n16, 99);
     const float *band = (v < 2 ? u2rb : u2cb);
     const int b0 = (v & 1) ? 2 : 0;              // the band pair {0,1} or {98,99}
-    const float bias = p.b3[n16 & 7];
+    const float bias = b3v;
     f32x4 d = {bias, bias, bias, bias};
 #pragma unroll
     for (int jj = 0; jj < 9; jj++) {            // k = 4 jj + kq: tap jj, ci = kq
@@ -483,7 +525,7 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
     auto get = [&](int yy, int xx, int ci) {  // uprelu2 near the corner: rows {0,1} / {98,99} of the row bands
       return u2rb[((yy < 50 ? yy : yy - 96) * 102 + xx + 1) * 4 + ci];
     };
-    const float val = hg_corner<4, 8>(get, 100, y, x, p.w3raw, p.b3[co], co, p.legacy);
+    const float val = hg_corner<4>(get, 100, y, x, wc3, b3v, p.legacy);
     u3l[(((c & 1) ? 1 : 0) * 200 + x) * 8 + co] = val;
     u3l[(((c & 2) ? 3 : 2) * 200 + y) * 8 + co] = val;
   }
@@ -514,18 +556,30 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
 
   // ---- corrections of the heat-map frame pixels (PrepLayout::efr: the conv taps of the row / column outside the
   // image in phase form along the line): pixel 2 j + b of a line gets sum_o E[b][o] L[j + o - 1] ----
-  for (int e = tid; e < 4 * 400; e += HG_THREADS) {
-    const int ln = e / 400, t = e - ln * 400, isc = ln >> 1, side = ln & 1, jq = t >> 1, b = t & 1;
-    float acc = 0.f;
-    if (!isc || (t > 0 && t < 399)) {  // the corner pixels are counted with the row lines
-      const float *E = efr_s + ((isc * 2 + side) * 2 + b) * 24;
-      const float *L = u3l + ln * 1600;
+  // Wave = line, pixel t = lane + 64 k: the line, its side and the parity b = lane & 1 never change for a lane, so its
+  // 24 coefficients stay in registers and a cell's 8 channels arrive as two 16-byte LDS reads (the accumulation order
+  // - o, then ci - is the one of the definition above)
+  {
+    const int ln = wv, isc = ln >> 1, side = ln & 1;
+    const float *L = u3l + ln * 1600;
+    float E[24];
+#pragma unroll
+    for (int i = 0; i < 24; i++) E[i] = efr_s[(ln * 2 + (lane & 1)) * 24 + i];
+    float *dst = p.c4 + (size_t)s * HC4_STRIDE + hc4_at(ln, 0);
+#pragma unroll 1
+    for (int k = 0; k < 7; k++) {
+      const int t = lane + 64 * k, jq = t >> 1;
+      float acc = 0.f;   // (lanes behind the line's 400 pixels compute on clamped cells and store nothing)
 #pragma unroll
       for (int o = 0; o < 3; o++) {
         const float *Lp = L + min(max(jq + o - 1, 0), 199) * 8;
+        const f32x4 la = *reinterpret_cast<const f32x4 *>(Lp), lb = *reinterpret_cast<const f32x4 *>(Lp + 4);
 #pragma unroll
-        for (int ci = 0; ci < 8; ci++) acc += E[o * 8 + ci] * Lp[ci];
+        for (int ci = 0; ci < 4; ci++) acc += E[o * 8 + ci] * la[ci];
+#pragma unroll
+        for (int ci = 0; ci < 4; ci++) acc += E[o * 8 + 4 + ci] * lb[ci];
       }
+      if (isc && (t == 0 || t == 399)) acc = 0.f;  // the corner pixels are counted with the row lines
       if (!isc && (t == 0 || t == 399)) {
         // corner pixel: + the column line's sum at this row, minus the tap (outside row, outside column) it shares
         // with the row line
@@ -539,10 +593,10 @@ __global__ __launch_bounds__(HG_THREADS) void k_head_frames(HeadParams2 p) {
         }
         const int tap = (side ? 2 : 0) * 3 + (cs ? 2 : 0);
         const float *Lc = L + (t ? 199 : 0) * 8;        // the corner cell of uprelu3
-        for (int ci = 0; ci < 8; ci++) acc -= p.w4raw[tap * 8 + ci] * Lc[ci];
+        for (int ci = 0; ci < 8; ci++) acc -= w4s[tap * 8 + ci] * Lc[ci];
       }
+      if (t < 400) dst[t] = acc;
     }
-    p.c4[(size_t)s * HC4_STRIDE + hc4_at(ln, t)] = acc;
   }
   if (tid < 64) p.c4[(size_t)s * HC4_STRIDE + hc4_pad(tid)] = 0.f;
 }

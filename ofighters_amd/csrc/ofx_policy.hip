@@ -27,6 +27,7 @@
 #include "ofx_head.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- user blob layout (ofx_blob.h) -------------------------------------------------
 
@@ -241,38 +242,68 @@ __global__ void k_policy_prepare(PrepParams p) {
 }
 
 // ---- upconv1 (1 -> 2 channels @ 50x50 behind a x2 bilinear up-sampling of the 25x25 dense output) --------------------
-// One workgroup per policy sample: the 625 inputs and the zero-padded up-sampled plane live in LDS (the generic k_conv
-// gathered every staged cell from global memory with four loads: 0.26 ms for 32768 ships; this form 0.22, bound by its
-// 0.66 GB of output).  Up-sample x first, then y (the restatement's order), taps in (dy, dx) order with fma, bias
-// behind the sum, ReLU.  A thread owns 10 adjacent pixels of a row.
+// One workgroup per policy sample: the zero-padded up-sampled plane lives in LDS (the generic k_conv gathered every
+// staged cell from global memory with four loads: 0.26 ms for 32768 ships; this form 0.19 for 0.66 GB of output,
+// profiles/r19_head_front.txt).  Up-sample x first, then y (the restatement's order), taps in (dy, dx) order with fma,
+// bias behind the sum, ReLU.  A thread owns 10 adjacent pixels of a row.
+//
+// The up-sampling pass has no index arithmetic per cell: the source indices and the weight of an up-res coordinate
+// g = 2 k + odd are a closed form of (k, odd) - half-pixel centres: odd -> (k, k + 1, .25), even -> (k - 1, k, .75);
+// legacy (src = g / 2): (k, k + 1, odd ? .5 : 0), both clamped to 0 .. 24 - and a thread keeps its column: thread
+// (seg, c) of the first 208 owns column c of the padded plane on the rows R .. R + n - 1 of segment seg (R = 0, 14, 26,
+// 40, n = 14, 12, 14, 12).  Every R is even, so the row pair (R + 2 m, R + 2 m + 1) = up-res rows 2 (K + m) - 1 and
+// 2 (K + m), K = R / 2, takes the same two x-interpolated source rows K + m - 1, K + m (legacy: the second row of the
+// pair takes K + m, K + m + 1) and all row indices are compile-time offsets from K.  The x-interpolated values of the
+// thread's column on its 8 (9) source rows come straight from global memory - 16 (18) loads in flight, no staging of
+// the 625 inputs, one barrier less - and each is used by up to four rows.  Per cell that leaves the two lerps, written
+// as before: top = a + (b - a) lx (the same value for every row that uses it), v = top + (bot - top) ly.
+template <bool LEGACY>
 __global__ __launch_bounds__(256) void k_upconv1(ConvParams p) {
-  __shared__ float u0s[625];
   __shared__ float up[52][53];   // up-sampled plane with its zero frame; pitch 53: the 5 segments of a row start on different banks
+  __shared__ __align__(16) float outs[5000];   // the ship's output block, stored with 16-byte lines (below)
   const int tid = threadIdx.x;
+  const int seg = tid / 52, c = tid - 52 * seg;             // seg 4 (tid >= 208): no up-sampling work
+  const int R = 13 * seg + (seg & 1), K = R >> 1, nrow = 14 - 2 * (seg & 1);
+  const int gx = c - 1, kx = gx >> 1, oddx = gx & 1;        // gx = -1, 50: the zero frame
+  const bool colv = gx >= 0 && gx < 50;
+  const int xa = min(max(LEGACY ? kx : kx - 1 + oddx, 0), 24), xb = min(max(LEGACY ? kx + 1 : kx + oddx, 0), 24);
+  const float lx = LEGACY ? (oddx ? 0.5f : 0.f) : (oddx ? 0.25f : 0.75f);
+  constexpr int nt = LEGACY ? 9 : 8;                       // source rows K - 1 .. K + nt - 2 (clamped)
   // work item it = the it-th ship (of the ordered list `live` with a mask): a bounded grid walks the items, so a
   // masked launch pays for its selected ships only (32768 workgroups that exit at once cost 0.13 ms)
   const int n_items = p.live ? p.live[0] : p.images;
 #pragma unroll 1
   for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
   const int img = p.live ? p.live[1 + it] : it;
-  __syncthreads();  // the previous item's readers of u0s / up are done
-  for (int e = tid; e < 625; e += 256) u0s[e] = p.in[(size_t)img * 625 + e];
-  __syncthreads();
-  for (int e = tid; e < 52 * 52; e += 256) {
-    const int c = e % 52, r = e / 52, gy = r - 1, gx = c - 1;
-    float v = 0.f;
-    if (gy >= 0 && gy < 50 && gx >= 0 && gx < 50) {
-      const float sy = p.legacy ? (float)gy * 0.5f : ((float)gy + 0.5f) * 0.5f - 0.5f;
-      const float sx = p.legacy ? (float)gx * 0.5f : ((float)gx + 0.5f) * 0.5f - 0.5f;
-      const float fy = floorf(sy), fx = floorf(sx);
-      const float ly = sy - fy, lx = sx - fx;
-      int y0 = (int)fy, x0 = (int)fx, y1 = y0 + 1, x1 = x0 + 1;
-      y0 = max(y0, 0); x0 = max(x0, 0); y1 = min(y1, 24); x1 = min(x1, 24);
-      const float a = u0s[y0 * 25 + x0], b = u0s[y0 * 25 + x1], d = u0s[y1 * 25 + x0], g = u0s[y1 * 25 + x1];
-      const float top = a + (b - a) * lx, bot = d + (g - d) * lx;
-      v = top + (bot - top) * ly;
+  float t[9];
+  if (tid < 208) {
+    const float *src = p.in + (size_t)img * 625;
+    float a[9], b[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+      if (i < nt) {
+        const unsigned y25 = 25u * (unsigned)min(max(K - 1 + i, 0), 24);   // uniform base + 32-bit lane offset
+        a[i] = src[y25 + (unsigned)xa];
+        b[i] = src[y25 + (unsigned)xb];
+      }
+#pragma unroll
+    for (int i = 0; i < 9; i++) t[i] = i < nt ? a[i] + (b[i] - a[i]) * lx : 0.f;
+  }
+  __syncthreads();  // the previous item's readers of up are done
+  if (tid < 208) {
+#pragma unroll
+    for (int j = 0; j < 14; j++) {
+      const int m = j >> 1, r = R + j;
+      float v;
+      if constexpr (LEGACY) {
+        const float top = t[m + (j & 1)], bot = t[m + (j & 1) + 1];
+        v = top + (bot - top) * ((j & 1) ? 0.f : 0.5f);
+      } else {
+        const float top = t[m], bot = t[m + 1];
+        v = top + (bot - top) * ((j & 1) ? 0.75f : 0.25f);
+      }
+      if (j < nrow) up[r][c] = (colv && r >= 1 && r <= 50) ? v : 0.f;
     }
-    up[r][c] = v;
   }
   __syncthreads();
   if (tid < 250) {
@@ -299,12 +330,18 @@ __global__ __launch_bounds__(256) void k_upconv1(ConvParams p) {
 #pragma unroll
   for (int co = 0; co < 2; co++) {
     const float bias = p.b[co];
-    float *o = p.out + (((size_t)img * 2 + co) * 50 + row) * 50 + x0;
+    float *o = outs + (co * 50 + row) * 50 + x0;
 #pragma unroll
     for (int i = 0; i < 10; i += 2)
       *reinterpret_cast<float2 *>(o + i) = make_float2(fmaxf(acc[co][i] + bias, 0.f), fmaxf(acc[co][i + 1] + bias, 0.f));
   }
   }  // tid < 250
+  // a thread's 10 pixels are 40 bytes apart from its neighbour's: stored from the registers, every store instruction
+  // touched each 128-byte line of the block with 8 bytes per lane (0.211 ms for 32768 ships).  Through LDS the block
+  // leaves as 1250 consecutive float4 (0.183 ms).  The next item writes `outs` behind its two barriers.
+  __syncthreads();
+  for (int e = tid; e < 1250; e += 256)
+    *reinterpret_cast<float4 *>(p.out + (size_t)img * 5000 + 4 * e) = *reinterpret_cast<const float4 *>(outs + 4 * e);
   }  // work items
 }
 
@@ -351,33 +388,140 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const float *A, int lda, const
   }
 }
 
-// Split-K form for the tall-K dense1 (M = arenas, N = 100, K = 5000): one wave per (32x32 tile, K chunk), partial
-// sums P[chunk][M][N] reduced in a fixed order by the consumer (k_head_dense) - no atomics, bit-reproducible.
-// K is walked 8 at a time with the k-slots permuted (slot kh of step j <-> k = k0 + 4 kh + j) so that a lane
-// fetches its A operands with one 16-byte load per 4 MFMAs; Kc % 8 == 0, lda % 4 == 0, A 16-byte aligned.
-__global__ __launch_bounds__(256) void k_gemm_f32_splitk(const float *A, int lda, const float *B, int ldb, float *P,
-                                                         int M, int N, int Kc, int tiles, int jobs) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int tiles_n = (N + 31) / 32;
-  const int job = blockIdx.x * 4 + wv;
-  const int chunk = job / tiles, tile = job - chunk * tiles;
-  if (job >= jobs) return;  // wave-uniform
-  const int m0 = (tile / tiles_n) * 32, n0 = (tile % tiles_n) * 32;
-  const int r = m0 + (lane & 31), c = n0 + (lane & 31), kh = lane >> 5;
-  const bool rv = r < M, cv = c < N;
+// The same GEMM for K = 100 (updense1 and dense2: A = d1 [.][100], 16-byte aligned rows): a workgroup = one N tile and
+// four M tiles, one per wave.  The 100 x 32 weight tile is staged in LDS once, in the order lane (column, kh) walks it -
+// B[2 t + kh][column], t = 0 .. 49, as 13 groups of four t: one 16-byte LDS read per four MFMAs - and an A row arrives as
+// 25 16-byte loads in three batches: float4 u of the row holds the lane's operand of MFMA 2 u (.x | .y by kh) and of
+// MFMA 2 u + 1 (.z | .w).  MFMA t still multiplies k = 2 t, 2 t + 1: every output keeps k_gemm_f32's k order, bit for
+// bit.  Rows / columns outside the matrix compute on clamped addresses and are not stored.
+__global__ __launch_bounds__(256) void k_gemm_f32_k100(const float *A, int lda, const float *B, int ldb, const float *bias,
+                                                       float *C, int ldc, int M, int N, int relu, const int32_t *live,
+                                                       int tiles_n) {
+  constexpr int K = 100, NT = K / 2, NQ = (NT + 3) / 4;   // 50 MFMAs, 13 groups of four
+  __shared__ __align__(16) float bs[NQ * 2 * 32 * 4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nt = blockIdx.x % tiles_n, mg = blockIdx.x / tiles_n;
+  if (live) M = live[0];
+  if (mg * 128 >= M) return;  // block-uniform (a masked launch is sized for every ship)
+  const int m0 = (mg * 4 + wv) * 32, n0 = nt * 32;
+  const int r0 = m0 + (lane & 31), c = n0 + (lane & 31), kh = lane >> 5;
+  const bool rv = r0 < M, cv = c < N;
+  {  // thread (column tid & 31, (group, kh) = tid >> 5 + 8 i): its four rows -> one float4
+    const float *bp = B + (n0 + (tid & 31) < N ? n0 + (tid & 31) : 0);
+    f32x4 w[(2 * NQ + 7) / 8];
+#pragma unroll
+    for (int i = 0; i < (2 * NQ + 7) / 8; i++) {
+      const int gk = min((tid >> 5) + 8 * i, 2 * NQ - 1), q = gk >> 1, h = gk & 1;
+#pragma unroll
+      for (int j = 0; j < 4; j++) w[i][j] = bp[(size_t)(2 * min(4 * q + j, NT - 1) + h) * ldb];
+    }
+#pragma unroll
+    for (int i = 0; i < (2 * NQ + 7) / 8; i++) {
+      const int gk = (tid >> 5) + 8 * i;
+      if (gk < 2 * NQ) *reinterpret_cast<f32x4 *>(bs + (gk * 32 + (tid & 31)) * 4) = w[i];
+    }
+  }
+  const int r = live ? live[1 + (rv ? r0 : 0)] : (rv ? r0 : 0);
+  const float *ap = A + (size_t)r * lda;
+  constexpr int NU = K / 4, NB0 = 9, NB1 = 8;   // batches of the row's 25 float4: 9, 8, 8
+  f32x4 a[NU];
+#pragma unroll
+  for (int u = 0; u < NB0; u++) a[u] = *reinterpret_cast<const f32x4 *>(ap + 4 * u);
+  __syncthreads();
+  if (m0 >= M) return;  // wave-uniform; behind the workgroup's only barrier
   f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; i++) acc[i] = 0.f;
+  const float *bl = bs + (kh * 32 + (lane & 31)) * 4;
+  f32x4 b4[NQ];
+#pragma unroll
+  for (int u = 0; u < NU; u++) {  // float4 u of the row: MFMAs t = 2 u, 2 u + 1
+    if (u == 0) {
+#pragma unroll
+      for (int i = NB0; i < NB0 + NB1; i++) a[i] = *reinterpret_cast<const f32x4 *>(ap + 4 * i);
+    }
+    if (u == NB0) {
+#pragma unroll
+      for (int i = NB0 + NB1; i < NU; i++) a[i] = *reinterpret_cast<const f32x4 *>(ap + 4 * i);
+    }
+    if ((u & 1) == 0) b4[u >> 1] = *reinterpret_cast<const f32x4 *>(bl + (u >> 1) * 2 * 32 * 4);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kh ? a[u][1] : a[u][0], b4[u >> 1][(2 * u) & 3], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kh ? a[u][3] : a[u][2], b4[u >> 1][(2 * u + 1) & 3], acc, 0, 0, 0);
+  }
+  if (cv) {
+    const float bv = bias ? bias[c] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int row = m0 + (i & 3) + 8 * (i >> 2) + 4 * kh;
+      if (row < M) {
+        float v = acc[i] + bv;
+        if (relu) v = fmaxf(v, 0.f);
+        C[(size_t)(live ? live[1 + row] : row) * ldc + c] = v;
+      }
+    }
+  }
+}
+
+// Split-K form for the tall-K dense1 (M = arenas, N = 100, K = 5000): one wave per (32x32 tile, K chunk of 200), partial
+// sums P[chunk][M][N] reduced in a fixed order by the consumer (k_head_dense) - no atomics, bit-reproducible.
+// K is walked 8 at a time with the k-slots permuted (slot kh of step j <-> k = k0 + 4 kh + j) so that a lane
+// fetches its A operands with one 16-byte load per 4 MFMAs; Kc % 8 == 0, lda % 4 == 0, A 16-byte aligned.
+//
+// A workgroup = one (K chunk, N tile) and four M tiles, one per wave: the chunk's 200 x 32 weight tile is staged in LDS
+// once ([k / 4][column][k % 4]: the four B operands of a k-step are one 16-byte LDS read) instead of being fetched by
+// every lane with four scalar-indexed global loads per k-step, and the A rows arrive in three batches of 16-byte loads,
+// a batch in flight while the one before feeds the MFMAs.  A lane's operands of a row (column) outside the matrix
+// are whatever the clamped address holds: an MFMA row (column) depends on its own operands only and those outputs are
+// not stored.  Blocks that follow each other share their four A tiles (the N tile runs fastest).
+constexpr int kSplitKc = 200;
+__global__ __launch_bounds__(256) void k_gemm_f32_splitk(const float *A, int lda, const float *B, int ldb, float *P,
+                                                         int M, int N, int tiles_n, int groups_m) {
+  constexpr int Kc = kSplitKc, KG = Kc / 4, STEPS = Kc / 8;   // 50 k-groups of 4, 25 k-steps of 8
+  __shared__ __align__(16) float bs[KG * 32 * 4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nt = blockIdx.x % tiles_n, rest = blockIdx.x / tiles_n, mg = rest % groups_m, chunk = rest / groups_m;
+  const int m0 = (mg * 4 + wv) * 32, n0 = nt * 32;
+  const int r = m0 + (lane & 31), c = n0 + (lane & 31), kh = lane >> 5;
+  const bool rv = r < M, cv = c < N;
+  {  // the weight tile: thread (column tid & 31, k-group tid >> 5 + 8 i) loads its four rows and stores them as one float4
+    const float *bp = B + (size_t)chunk * Kc * ldb + (n0 + (tid & 31) < N ? n0 + (tid & 31) : 0);
+    f32x4 w[(KG + 7) / 8];
+#pragma unroll
+    for (int i = 0; i < (KG + 7) / 8; i++) {
+      const int g = min((tid >> 5) + 8 * i, KG - 1);
+#pragma unroll
+      for (int j = 0; j < 4; j++) w[i][j] = bp[(size_t)(4 * g + j) * ldb];
+    }
+#pragma unroll
+    for (int i = 0; i < (KG + 7) / 8; i++) {
+      const int g = (tid >> 5) + 8 * i;
+      if (g < KG) *reinterpret_cast<f32x4 *>(bs + (g * 32 + (tid & 31)) * 4) = w[i];
+    }
+  }
   const float *ap = A + (size_t)(rv ? r : 0) * lda + (size_t)chunk * Kc + 4 * kh;
-  const float *bp = B + ((size_t)chunk * Kc + 4 * kh) * ldb + (cv ? c : 0);
-  for (int k0 = 0; k0 < Kc; k0 += 8) {
-    const float4 a4 = *reinterpret_cast<const float4 *>(ap + k0);
-    const float b0 = bp[(size_t)(k0 + 0) * ldb], b1 = bp[(size_t)(k0 + 1) * ldb], b2 = bp[(size_t)(k0 + 2) * ldb],
-                b3 = bp[(size_t)(k0 + 3) * ldb];
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(rv ? a4.x : 0.f, cv ? b0 : 0.f, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(rv ? a4.y : 0.f, cv ? b1 : 0.f, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(rv ? a4.z : 0.f, cv ? b2 : 0.f, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(rv ? a4.w : 0.f, cv ? b3 : 0.f, acc, 0, 0, 0);
+  constexpr int NB0 = 9, NB1 = 8;   // batches of the 25 k-steps: 9, 8, 8
+  f32x4 a[STEPS];
+#pragma unroll
+  for (int i = 0; i < NB0; i++) a[i] = *reinterpret_cast<const f32x4 *>(ap + 8 * i);
+  __syncthreads();
+  if (m0 >= M) return;  // wave-uniform; behind the workgroup's only barrier
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; i++) acc[i] = 0.f;
+  const float *bl = bs + (kh * 32 + (lane & 31)) * 4;
+#pragma unroll
+  for (int s = 0; s < STEPS; s++) {  // k-step s: k = 8 s + 4 kh + j in MFMA j
+    if (s == 0) {
+#pragma unroll
+      for (int i = NB0; i < NB0 + NB1; i++) a[i] = *reinterpret_cast<const f32x4 *>(ap + 8 * i);
+    }
+    if (s == NB0) {
+#pragma unroll
+      for (int i = NB0 + NB1; i < STEPS; i++) a[i] = *reinterpret_cast<const f32x4 *>(ap + 8 * i);
+    }
+    const f32x4 b4 = *reinterpret_cast<const f32x4 *>(bl + s * 2 * 32 * 4);
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][j], b4[j], acc, 0, 0, 0);
   }
   if (cv) {
     float *out = P + (size_t)chunk * M * N;
@@ -528,9 +672,13 @@ static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S) {
 // (also the dense layers of the fit's forward, ofx_train.hip)
 int ofx_launch_gemm(ofx_handle *h, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,
                     int M, int N, int K, int relu, const int32_t *live) {
-  const int tiles = ((M + 31) / 32) * ((N + 31) / 32);
-  hipLaunchKernelGGL(k_gemm_f32, dim3((tiles + 3) / 4), dim3(256), 0, h->stream, A, lda, B, ldb, bias, C, ldc, M, N, K,
-                     relu, live);
+  const int tiles_m = (M + 31) / 32, tiles_n = (N + 31) / 32, tiles = tiles_m * tiles_n;
+  if (K == 100 && lda % 4 == 0 && ((uintptr_t)A & 15) == 0)  // the layers behind d1: the same sums, operands through LDS
+    hipLaunchKernelGGL(k_gemm_f32_k100, dim3((unsigned)(((tiles_m + 3) / 4) * tiles_n)), dim3(256), 0, h->stream, A, lda, B, ldb,
+                       bias, C, ldc, M, N, relu, live, tiles_n);
+  else
+    hipLaunchKernelGGL(k_gemm_f32, dim3((tiles + 3) / 4), dim3(256), 0, h->stream, A, lda, B, ldb, bias, C, ldc, M, N, K,
+                       relu, live);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -663,9 +811,10 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   // 2. dense1: trunk features on MFMA once per arena; head + head-1 per ship
   const float *k1 = weights + off[OFX_T_DENSE1];
   {
-    const int tiles = ((N + 31) / 32) * 4, jobs = tiles * kDense1Chunks;
-    hipLaunchKernelGGL(k_gemm_f32_splitk, dim3((jobs + 3) / 4), dim3(256), 0, h->stream, ws.p4, 5000, k1 + 8 * 100, 100,
-                       ws.g1, N, 100, 5000 / kDense1Chunks, tiles, jobs);
+    static_assert(5000 == kDense1Chunks * kSplitKc, "k_gemm_f32_splitk's chunk");
+    const int tiles_n = (100 + 31) / 32, groups_m = ((N + 31) / 32 + 3) / 4;
+    hipLaunchKernelGGL(k_gemm_f32_splitk, dim3((unsigned)(tiles_n * groups_m * kDense1Chunks)), dim3(256), 0, h->stream, ws.p4,
+                       5000, k1 + 8 * 100, 100, ws.g1, N, 100, tiles_n, groups_m);
     OFX_HIP(hipGetLastError());
   }
   HeadParams hp;
@@ -691,7 +840,8 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   up.live = live; up.images = S; up.legacy = h->opt_bilinear_legacy;
   up.in = ws.u0; up.w = prep + L.uw[0]; up.b = prep + L.ub[0]; up.out = ws.up1;
   // every ship: one workgroup each (0.22 ms; a bounded grid that loops is 0.02 ms slower); with a mask: a bounded grid over the list
-  hipLaunchKernelGGL(k_upconv1, dim3((unsigned)(live && S > 4096 ? 4096 : S)), dim3(256), 0, h->stream, up);
+  if (up.legacy) hipLaunchKernelGGL(k_upconv1<true>, dim3((unsigned)(live && S > 4096 ? 4096 : S)), dim3(256), 0, h->stream, up);
+  else hipLaunchKernelGGL(k_upconv1<false>, dim3((unsigned)(live && S > 4096 ? 4096 : S)), dim3(256), 0, h->stream, up);
   OFX_HIP(hipGetLastError());
   OFX_HIP(hipMemsetAsync(ws.best, 0, sizeof(unsigned long long) * S, h->stream));
   HeadParams2 hp2;
