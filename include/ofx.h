@@ -380,12 +380,23 @@ int ofx_policy_pin_weights(ofx_handle *h, const float *weights);
  * heat map under the other.  Applies to the forward, the DQN targets and ofx_dqn_fit; a pinned blob is re-prepared. */
 #define OFX_OPT_BILINEAR_LEGACY 3
 /* OPT-IN reduced precision, never the default and never the headline number: ofx_policy_forward (the rollout's forward
- * on the live state; ofx_policy_forward_obs, the DQN targets and the fit stay fp32) feeds conv2-4 (streaming trunk) and
- * upconv3-4 - 97 % of the per-ship work - to the 16-bit matrix instructions: operands rounded to nearest even, sums in
- * fp32.  value 1: bf16 operands (8 significant bits); value 2: fp16 operands (11 significant bits; operands beyond
+ * on the live state; ofx_policy_forward_obs, the DQN targets and the fit stay fp32) feeds conv2, conv3, conv4 of the
+ * STREAMING trunk (OFX_OPT_TRUNK_FUSE; the unfused trunk has no 16-bit form and stays fp32) and upconv3 to the 16-bit
+ * matrix instructions: operands rounded to nearest even, sums in fp32.  The operands are, and nothing else is:
+ *   conv2-4  the layer's input activations and its BatchNorm-folded kernel (the fold itself is fp32); the folded bias,
+ *            ReLU and max-pool are fp32, conv4's output enters dense1 unrounded;
+ *   upconv3  the uprelu2 values and the PHASE weights (rounded after the fp32 combination of the folded kernel with the
+ *            bilinear coefficients, not before); bias fp32; the frame lines (rows / columns 0 and 199) exact fp32.
+ * conv1, the dense layers, upconv1, upconv2 and upconv4 (its up-sampling included) are the fp32 path's.
+ * tests/policy_lowp_ref.py is this contract as a float64 graph.  Against it (tests/test_gpu_policy_lowp.py) the kernels
+ * stay at the fp32 path's own bounds - act_values within 1.5e-5, the heat map within 8e-6 of its maximum - on all but the
+ * pixels behind an operand that sits within fp32 error of a 16-bit rounding boundary, which fp32 and float64 round to
+ * different neighbours: measured at most 0.31 % of a ship's pixels, up to 9e-4 (bf16) / 2.6e-4 (fp16) there.
+ * value 1: bf16 operands (8 significant bits); value 2: fp16 operands (11 significant bits; operands beyond
  * 65504 would overflow - activations behind BatchNorm + ReLU and folded weights are far below); value 0: fp32.  The
- * reference's Keras model is fp32 (agents/qlearnIA_V2.py:123-190): with this switch the heat map differs from the fp32
- * path at the 3e-3 (bf16) / 4e-4 (fp16) level and near-ties of its arg-max can resolve differently; bench.py reports the
+ * reference's Keras model is fp32 (agents/qlearnIA_V2.py:123-190): with this switch the heat map differs from the
+ * UNROUNDED graph by 3.9e-3 (bf16) / 4.6e-4 (fp16) of its maximum on the tests' trained-like weights (3.3e-3 / 4.2e-4
+ * on bench.py's) and near-ties of its arg-max can resolve differently; bench.py reports the
  * measured error against the float64 graph and the arg-max agreement next to the speed.                              */
 #define OFX_OPT_POLICY_BF16 5
 /* Diagnostic: ofx_dqn_fit / ofx_dqn_fit_reference in their PLAIN form (value 1): one kernel per layer and pass, every

@@ -33,10 +33,3 @@ __device__ __forceinline__ lp_f32x4 lp_mfma16(lp_x4 a, lp_x4 b, lp_f32x4 c) {
   if constexpr (LP == 1) return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(lp_h16x4, a), __builtin_bit_cast(lp_h16x4, b), c, 0, 0, 0);
 }
-
-// 16 blocks of D[4][4] += A[4][4] B[4][4], the A block ABID broadcast to every block (CBSZ = 4)
-template <int LP, int ABID>
-__device__ __forceinline__ lp_f32x4 lp_mfma4_bcast(lp_x4 a, lp_x4 b, lp_f32x4 c) {
-  if constexpr (LP == 1) return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(a, b, c, 4, ABID, 0);
-  else return __builtin_amdgcn_mfma_f32_4x4x4f16(__builtin_bit_cast(lp_h16x4, a), __builtin_bit_cast(lp_h16x4, b), c, 4, ABID, 0);
-}

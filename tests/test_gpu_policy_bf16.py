@@ -1,5 +1,7 @@
-"""OFX_OPT_POLICY_BF16 - the OPT-IN reduced-precision forward (value 1: bf16, value 2: fp16 operands in conv2-4 and
-upconv3 / upconv4, fp32 sums; never the default, never the headline number).  Measured against the float64 graph like the fp32 path (tests/policy_ref64.py):
+"""OFX_OPT_POLICY_BF16 - the OPT-IN reduced-precision forward (value 1: bf16, value 2: fp16 operands in conv2-4 of the
+streaming trunk and in upconv3, fp32 sums; upconv4 and everything else stay fp32 - tests/policy_lowp_ref.py is the
+definition of what is rounded, and tests/test_gpu_policy_lowp.py holds the kernels to it at the fp32 path's bounds;
+never the default, never the headline number).  Measured HERE against the UNROUNDED float64 graph like the fp32 path (tests/policy_ref64.py):
 the error of the heat map and how often its arg-max is the float64 map's are REPORTED (gpurun_out/policy_fp64_report.json,
 bench.py --full repeats the measurement in its bf16 lines); asserted is only that the switch gives a reduced-precision version
 of the same function - act_values within 2e-2 of their scale (conv2 / conv3 of the streaming trunk run on bf16 operands
