@@ -1,5 +1,5 @@
 """float64 checker of ONE fit step of the DQN at any batch size: the training-mode graph of
-tests/test_train.py::_torch_reference (BatchNorm on batch statistics, mse / Huber on both heads) and its backward with
+tests/fit_torch_ref.py::fit_reference (BatchNorm on batch statistics, mse / Huber on both heads) and its backward with
 torch autograd, evaluated in chunks of rows so that the peak memory is set by the chunk and not by the minibatch
 (the unchunked autograd holds 0.24 GB per row in float64).
 
@@ -61,8 +61,8 @@ def fit_step(w, shapes, bits, vec8, iaction=None, px=None, py=None, y_act=None, 
 
     bits [n][2][5000] uint32 (bit k of the plane = word k / 32, bit k % 32), vec8 [n][8]; the textbook targets are
     (iaction, px, py, y_act, y_ptr): one error per head and row.  dense = (t1 [n][2], t2 [n][400][400]): whole target
-    tensors (ofx_dqn_fit_reference).  row_w [n]: Keras sample_weight (tests/per_torch_ref.py); huber_delta > 0: Keras
-    Huber(delta) in place of the squared error under the same normalisation (tests/huber_torch_ref.py).
+    tensors (ofx_dqn_fit_reference).  row_w [n]: Keras sample_weight; huber_delta > 0: Keras
+    Huber(delta) in place of the squared error under the same normalisation (both as in tests/fit_torch_ref.py).
     chunk: rows per chunk (None: the whole minibatch at once, without checkpoints).
     Two diagnostic forms, for telling apart what a float32 evaluation of this graph may do differently:
     round_stats: every BatchNorm's batch mean and variance are rounded to float32 where they are used (the gradient passes

@@ -1,0 +1,73 @@
+"""What the replay-memory tests share on the device: capture masks that leave arenas with 0, 1, 4 and 11 rows, the rows
+of a window without their maps, hand-set masses, and how many of an arena's oldest rows lost their frame.  A helper
+module (not collected)."""
+import ctypes as C
+
+import numpy as np
+
+
+def varied_masks(NG, M):
+    """arena 0 never captures (0 rows), arena 1 captures at ticks 0-1 (1 row), arena 2 with one ship (11 rows at 12
+    ticks), arena 3 one ship at ticks 0-4 (4 rows), the others every ship."""
+    def masks(t):
+        mk = np.ones((NG, M), np.uint8)
+        mk[0] = 0
+        mk[1] = 0
+        mk[1, 0] = t < 2
+        mk[2] = 0
+        mk[2, 0] = 1
+        mk[3] = 0
+        mk[3, 0] = t < 5
+        return mk
+    return masks
+
+
+def gather_rows(b, slot, n_s, batch, first, max_rows):
+    """gather_valid without the maps -> (rows DeviceBuffer, n_rows)."""
+    from ofighters_amd import DeviceBuffer, _native as nat
+    rows = DeviceBuffer(max(1, max_rows) * b.TRANSITION_DTYPE.itemsize)
+    n = C.c_int32()
+    nat.check(nat.lib().ofx_replay_gather_valid(b.handle, slot.ptr, n_s.ptr, int(batch), int(first), int(max_rows), rows.ptr,
+                                                 None, None, C.byref(n)))
+    return rows, n.value
+
+
+def all_rows_window(b):
+    """slot / n_sampled naming every row of every arena (oldest first), and those rows gathered."""
+    from ofighters_amd import DeviceBuffer
+    cnt, _ = b.replay_count()
+    Cap = b.replay_capacity
+    slot = np.full((b.N, Cap), -1, np.int32)
+    for a in range(b.N):
+        slot[a, :cnt[a]] = np.arange(cnt[a])
+    slot_d, n_d = DeviceBuffer(slot.nbytes).upload(slot), DeviceBuffer(4 * b.N).upload(cnt.astype(np.int32))
+    total = int(cnt.sum())
+    rows, got = gather_rows(b, slot_d, n_d, Cap, 0, total)
+    assert got == total
+    return slot_d, n_d, Cap, rows, total, cnt
+
+
+def set_masses(b, td_fn):
+    """Hand-set masses: one write-back over every row with td = td_fn(rows) [n][2]."""
+    from ofighters_amd import DeviceBuffer
+    slot_d, n_d, Cap, rows, total, cnt = all_rows_window(b)
+    b.sync()
+    r = rows.download(b.TRANSITION_DTYPE, (total,))
+    td = np.ascontiguousarray(td_fn(r), np.float32)
+    td_d = DeviceBuffer(td.nbytes).upload(td)
+    b.replay_update_priorities(slot_d, n_d, Cap, 0, total, rows.ptr, td_d.ptr)
+    b.sync()
+    return r, td
+
+
+def stale_rows(b, a):
+    """How many of the arena's oldest rows have lost their `state` frame (not eligible)."""
+    from ofighters_amd import OfxError
+    rows = b.replay_rows(a)
+    for k, r in enumerate(rows):
+        try:
+            b.replay_frame(a, int(r["tick_prev"]))
+            return k
+        except OfxError:
+            pass
+    return len(rows)

@@ -3,20 +3,11 @@ every symbol include/ofx.h declares, and fails loudly (no CPU fallback) when
 no HIP device is visible.  No compute call is made here."""
 import ctypes as C
 import os
-import re
 
 import pytest
 
 from ofighters_amd import _native as nat
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_symbols():
-    src = open(os.path.join(ROOT, "include", "ofx.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ofx_[a-z0-9_]+)\s*\(", src)))
-
+from tests.abi_header import ROOT, header_symbols
 
 def test_library_exports_every_declared_symbol():
     L = C.CDLL(nat.LIB_PATH)

@@ -7,6 +7,7 @@ import pytest
 from ofighters_amd import checkpoint
 from ofighters_amd.rollout import TrainingRollout
 from tests import repeat_oracle as ro
+from tests.rollout_standin import FakeEngine, FakeTrainer, fake_device_buffers
 
 
 # ------------------------------------------------------------------------------------------------- 1. the model
@@ -50,49 +51,12 @@ def test_scenario_conditions():
 
 
 # ------------------------------------------------------------------------------------------- 2. the call sequence
-class _Buf:
-    ptr = 1
-
-
-class _Eps:
-    def __init__(self): self.v, self.n = 0.5, 0
-    def get(self): return self.v
-    def next(self): self.n += 1
-
-
-class _FakeTrainer:
-    def __init__(self):
-        self.weights, self.epsilon, self.replays = _Buf(), _Eps(), []
-    def decay_epsilon(self): self.epsilon.next()
-    def replay(self):
-        self.replays.append(self.clock())
-        return (1.0, 2.0)
-    def fingerprint(self): return {}
-
-
-class _FakeEngine:
-    """Records the call order; nobody dies."""
-    def __init__(self, N=3, M=2):
-        self.N, self.M, self.W, self.H, self.arena_base = N, M, 400, 400, 0
-        self.episode, self.log, self.tick = 0, [], 0
-    def sync(self): pass
+class _Engine(FakeEngine):
+    """The stand-in with the span calls; spawn and restart are logged."""
     def spawn_random(self, seed): self.log.append("spawn")
     def restart_random(self, seed):
         self.episode += 1
         self.log.append("restart@%d" % self.tick)
-    def episode_scores(self): return np.arange(self.M + 1, dtype=np.int64)
-    def policy_pin_weights(self, p): self.log.append("pin")
-    def agents_first_done(self, mask_ptr, seen): return 0
-    def bot_actions(self, beh, seed, tick=None): self.log.append("bots")
-    def policy_forward(self, w, m): self.log.append("forward")
-    def policy_explore(self, eps, seed, tick=None, collecting=False, ship_mask_ptr=None):
-        self.log.append("explore:%d:%d" % (tick, collecting))
-    def replay_capture(self, tick, ship_mask_ptr=None): self.log.append("capture:%d" % tick)
-    def policy_actions(self, ship_mask_ptr=None): self.log.append("actions")
-    def step(self):
-        self.log.append("step")
-        self.tick += 1
-    def rasterise(self): self.log.append("raster")
     def replay_reward_source(self, ptr): self.log.append("reward_source:%r" % ptr)
     def step_repeat(self, behaviours, seed, tick0, n_ticks, hold_mask_ptr=None, actions_ptr=None, span_reward_ptr=None,
                     observe=None):
@@ -103,22 +67,11 @@ class _FakeEngine:
 
 @pytest.fixture
 def fake_buffers(monkeypatch):
-    import ofighters_amd.engine as eng
-    made = []
-
-    class _DB:
-        def __init__(self, n):
-            made.append(self)
-            self.ptr = 100 + len(made)
-        def upload(self, a):
-            self.held = np.array(a)
-            return self
-    monkeypatch.setattr(eng, "DeviceBuffer", _DB)
-    return made
+    return fake_device_buffers(monkeypatch)
 
 
 def _rollout(**kw):
-    e, t = _FakeEngine(), _FakeTrainer()
+    e, t = _Engine(), FakeTrainer()
     r = TrainingRollout(e, t, ["idle", "idle"], seed=3, policy_ships=(0,), collecting_steps=3, replay_every=5, **kw)
     t.clock = lambda: r.total_steps
     return e, t, r
@@ -174,7 +127,7 @@ def test_action_repeat_4_one_span_per_decision(fake_buffers):
                                 dict(action_repeat=3, episode_ticks=40),
                                 dict(action_repeat=4, episode_ticks=40, start_tick=6)])
 def test_action_repeat_value_errors(fake_buffers, kw):
-    e, t = _FakeEngine(), _FakeTrainer()
+    e, t = _Engine(), FakeTrainer()
     with pytest.raises(ValueError) as err:
         TrainingRollout(e, t, ["idle", "idle"], seed=3, **kw)
     assert "action_repeat" in str(err.value)

@@ -7,6 +7,7 @@ import pytest
 from ofighters_amd import checkpoint
 from ofighters_amd.rollout import TrainingRollout
 from tests import autoreset_oracle as ao
+from tests.rollout_standin import FakeEngine, FakeTrainer, fake_device_buffers
 
 
 # ------------------------------------------------------------------------------------------------- 1. the model
@@ -51,49 +52,14 @@ def test_nothing_selected_is_the_global_clock():
 
 
 # ------------------------------------------------------------------------------------------- 2. the call sequence
-class _Buf:
-    ptr = 1
-
-
-class _Eps:
-    def __init__(self): self.v, self.n = 0.5, 0
-    def get(self): return self.v
-    def next(self): self.n += 1
-
-
-class _FakeTrainer:
-    def __init__(self):
-        self.weights, self.epsilon, self.replays = _Buf(), _Eps(), []
-    def decay_epsilon(self): self.epsilon.next()
-    def replay(self):
-        self.replays.append(self.clock())
-        return (1.0, 2.0)
-    def fingerprint(self): return {}
-
-
-class _FakeEngine:
-    """Records the call order; nobody dies.  Every restart_finished banks one episode of `tick` lock-steps per arena."""
-    def __init__(self, N=3, M=2):
-        self.N, self.M, self.W, self.H, self.arena_base = N, M, 400, 400, 0
-        self.episode, self.log, self.tick = 0, [], 0
+class _Engine(FakeEngine):
+    """The stand-in with the per-arena restart; spawn, restart and sync are logged.  Every restart_finished banks one
+    episode of `tick` lock-steps per arena."""
     def sync(self): self.log.append("sync")
     def spawn_random(self, seed): self.log.append("spawn")
     def restart_random(self, seed):
         self.episode += 1
         self.log.append("restart@%d" % self.tick)
-    def episode_scores(self): return np.arange(self.M + 1, dtype=np.int64)
-    def policy_pin_weights(self, p): self.log.append("pin")
-    def agents_first_done(self, mask_ptr, seen): return 0
-    def bot_actions(self, beh, seed, tick=None): self.log.append("bots")
-    def policy_forward(self, w, m): self.log.append("forward")
-    def policy_explore(self, eps, seed, tick=None, collecting=False, ship_mask_ptr=None):
-        self.log.append("explore:%d:%d" % (tick, collecting))
-    def replay_capture(self, tick, ship_mask_ptr=None): self.log.append("capture:%d" % tick)
-    def policy_actions(self, ship_mask_ptr=None): self.log.append("actions")
-    def step(self):
-        self.log.append("step")
-        self.tick += 1
-    def rasterise(self): self.log.append("raster")
     def replay_reward_source(self, ptr): self.log.append("reward_source:%r" % ptr)
     def step_repeat(self, behaviours, seed, tick0, n_ticks, hold_mask_ptr=None, actions_ptr=None, span_reward_ptr=None,
                     observe=None):
@@ -110,26 +76,11 @@ class _FakeEngine:
 
 @pytest.fixture
 def fake_buffers(monkeypatch):
-    import ofighters_amd.engine as eng
-    made = []
-
-    class _DB:
-        def __init__(self, n):
-            made.append(self)
-            self.ptr = 100 + len(made)
-            self.uploads = 0
-        def upload(self, a):
-            self.held = np.array(a)
-            self.uploads += 1
-            return self
-        def download(self, dtype, shape):
-            return np.array(self.held, dtype).reshape(shape)
-    monkeypatch.setattr(eng, "DeviceBuffer", _DB)
-    return made
+    return fake_device_buffers(monkeypatch)
 
 
 def _rollout(**kw):
-    e, t = _FakeEngine(), _FakeTrainer()
+    e, t = _Engine(), FakeTrainer()
     r = TrainingRollout(e, t, ["idle", "idle"], seed=3, policy_ships=(0,), collecting_steps=3, replay_every=5, **kw)
     t.clock = lambda: r.total_steps
     return e, t, r
@@ -195,7 +146,7 @@ def test_auto_reset_with_action_repeat_calls_once_per_decision(fake_buffers):
 
 
 def test_auto_reset_with_the_ladder_groups(fake_buffers):
-    e, t = _FakeEngine(N=4), _FakeTrainer()
+    e, t = _Engine(N=4), FakeTrainer()
     e.policy_epsilon_ladder = lambda expo: None
     e.restart_finished = lambda seed, ship_mask_ptr=None, **kw: e.log.append(
         "rf:%r:%d:%s" % (kw["group_buf"].ptr, kw["n_groups"], kw["sums_buf"].held.shape))
@@ -210,7 +161,7 @@ def test_auto_reset_with_the_ladder_groups(fake_buffers):
 
 @pytest.mark.parametrize("value", [1, 0, None, "yes", 1.0, np.int32(1)])
 def test_auto_reset_must_be_a_bool(fake_buffers, value):
-    e, t = _FakeEngine(), _FakeTrainer()
+    e, t = _Engine(), FakeTrainer()
     with pytest.raises(ValueError) as err:
         TrainingRollout(e, t, ["idle", "idle"], seed=3, auto_reset=value)
     assert "auto_reset" in str(err.value)

@@ -1,6 +1,6 @@
 """Checkpoints without a device: ofx_replay_blob_check (host only) against blobs built by tests/ckpt_blob.py from the
 layout text of include/ofx.h, the epsilon schedules' state, and TrainingRollout.checkpoint / restore on the stand-ins
-of tests/test_learning_loop.py::test_training_rollout_schedule (copied here and extended by what a checkpoint needs)."""
+of tests/checkpoint_standin.py (those of tests/rollout_standin.py extended by what a checkpoint needs)."""
 import ctypes as C
 import json
 
@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 
 from ofighters_amd import _native as nat
-from ofighters_amd.rollout import TrainingRollout
 from tests import ckpt_blob
+from tests.checkpoint_standin import (ROLLOUT_KEYS, TRAINER_KEYS, HostBuffer as _HostBuffer, host_trainer as _trainer,
+                                       standins as _standins)
 
 W = H = 400
 WORDS = W * H // 32
@@ -182,124 +183,6 @@ def test_epsilon_state_round_trips(make):
 
 
 # ------------------------------------------------------------------- TrainingRollout.checkpoint / restore, stand-ins
-TRAINER_KEYS = ("n_floats", "learning_rate", "gamma", "batch_size", "fit_batch", "seed", "reference_quirks", "prioritized",
-                "per_alpha", "per_beta", "per_beta_steps", "per_eps", "n_step", "target_sync", "target_tau", "double_dqn",
-                "huber_delta", "clip_norm", "memory_capacity", "memory_frames")
-ROLLOUT_KEYS = ("policy_ships", "behaviours", "seed", "episode_ticks", "collecting_steps", "replay_every",
-                "replay_on_death", "is_learning")
-
-
-class _Buf:
-    ptr = 1
-
-
-class _Eps:
-    def __init__(self): self.v, self.n = 0.5, 0
-    def get(self): return self.v
-    def next(self): self.n += 1
-
-
-class _FakeTrainer:
-    def __init__(self, uploads, **fp):
-        self.weights, self.epsilon, self.replays, self.saved, self.uploads = _Buf(), _Eps(), [], [], uploads
-        self.fp = dict({k: 1 for k in TRAINER_KEYS}, learning_rate=1e-3, target_tau=None, reference_quirks=False)
-        self.fp.update(fp)
-        self.w = np.arange(5, dtype=np.float32)
-    def decay_epsilon(self): self.epsilon.next()
-    def replay(self):
-        self.replays.append(self.clock())
-        self.w = self.w + 1
-        return (1.0, 2.0)
-    def save(self, id=None, overwrite=False, folder=None):
-        self.saved.append(id)
-        return "%s/%s" % (folder, id)
-    # ---- what a checkpoint needs
-    def fingerprint(self): return dict(self.fp)
-    def state_dict(self):
-        return {"fingerprint": self.fingerprint(), "weights": self.w.copy(), "adam_m": self.w * 2, "adam_v": self.w * 3,
-                "target": None, "fit_steps": len(self.replays), "draws": len(self.replays),
-                "losses": np.array([(1.0, 2.0)] * len(self.replays)).reshape(-1, 2), "grad_norms": np.zeros(0),
-                "epsilon": {"class": "_Eps", "attrs": {"v": self.epsilon.v, "n": self.epsilon.n}}}
-    def load_state_dict(self, d):
-        self.uploads.append("trainer")
-        self.w = d["weights"].copy()
-        self.replays = list(range(d["fit_steps"]))
-        self.epsilon.v, self.epsilon.n = d["epsilon"]["attrs"]["v"], d["epsilon"]["attrs"]["n"]
-
-
-class _FakeEngine:
-    """Records the call order of one lock-step; ship 0 of arena 1 dies at tick 7 of every episode."""
-    W = H = 400
-    def __init__(self, uploads, N=3, M=2, arena_base=0):
-        self.N, self.M, self.episode, self.log, self.t, self.arena_base = N, M, 0, [], 0, arena_base
-        self.alive = np.ones((N, M), np.uint8)
-        self.seen = np.zeros((N, M), bool)
-        self.mask = np.zeros((N, M), bool); self.mask[:, 0] = True
-        self.uploads, self.fail_export = uploads, False
-        self.memory = np.zeros((N, 4), np.uint8)
-    def sync(self): pass
-    def spawn_random(self, seed): pass
-    def restart_random(self, seed):
-        self.episode += 1; self.alive[:] = 1; self.t = 0
-    def episode_scores(self): return np.arange(self.M + 1, dtype=np.int64)
-    def policy_pin_weights(self, p): self.log.append("pin")
-    def get(self, field): return self.alive.copy()
-    def agents_first_done(self, mask_ptr, seen):          # the device-side `done` latches (ofx_agents_first_done)
-        if getattr(seen, "cleared", False): self.seen, seen.cleared = np.zeros((self.N, self.M), bool), False
-        first = (self.alive == 0) & self.mask & ~self.seen
-        self.seen |= first
-        return int(first.sum())
-    def bot_actions(self, beh, seed, tick=None): self.log.append("bots")
-    def policy_forward(self, w, m): self.log.append("forward")
-    def policy_explore(self, eps, seed, tick=None, collecting=False, ship_mask_ptr=None):
-        self.log.append("explore:%d:%d" % (tick, collecting))
-    def replay_capture(self, tick, ship_mask_ptr=None):
-        self.log.append("capture:%d" % tick)
-        self.memory[:, tick % 4] = tick % 251
-    def policy_actions(self, ship_mask_ptr=None): self.log.append("actions")
-    def step(self):
-        self.log.append("step"); self.t += 1
-        if self.t == 7: self.alive[1, 0] = 0
-    def rasterise(self): self.log.append("raster")
-    # ---- what a checkpoint needs
-    def state_dict(self): return {"ship_alive": self.alive.copy(), "time": np.full(self.N, self.t, np.int32),
-                                  "episode": self.episode, "tick": self.t}
-    def load_state_dict(self, d):
-        self.uploads.append("arena")
-        self.alive, self.t, self.episode = d["ship_alive"].copy(), int(d["time"][0]), d["episode"]
-    def replay_export_bytes(self, a, n): return 4 * n
-    def replay_export(self, a, n):
-        if self.fail_export and a > 0:
-            raise RuntimeError("export interrupted")
-        return self.memory[a:a + n].reshape(-1).copy()
-    def replay_import(self, a, n, blob):
-        self.uploads.append("replay:%d:%d" % (a, n))
-        self.memory[a:a + n] = np.asarray(blob).reshape(n, 4)
-
-
-def _standins(monkeypatch, tmp_path, engine_kw=None, trainer_fp=None, **roll_kw):
-    import ofighters_amd.engine as eng
-    uploads = []
-
-    class _DB:
-        def __init__(self, n): self.ptr, self.data = 7, None
-        def upload(self, a):
-            uploads.append("buffer")
-            self.data = np.array(a, copy=True)
-            self.cleared = not np.asarray(a).any()         # TrainingRollout zeroes the latches at episode ends
-            return self
-        def download(self, dtype, shape): return np.asarray(self.data, dtype).reshape(shape).copy()
-    monkeypatch.setattr(eng, "DeviceBuffer", _DB)
-    e, t = _FakeEngine(uploads, **(engine_kw or {})), _FakeTrainer(uploads, **(trainer_fp or {}))
-    kw = dict(seed=3, policy_ships=(0,), episode_ticks=40, snapshot_every=2, snapshot_folder=str(tmp_path / "snap"),
-              collecting_steps=20, replay_every=50)
-    kw.update(roll_kw)
-    r = TrainingRollout(e, t, kw.pop("behaviours", ["idle", "idle"]), **kw)
-    t.clock = lambda: r.total_steps
-    del uploads[:]
-    return r, e, t, uploads
-
-
 def test_checkpoint_manifest_round_trips(tmp_path, monkeypatch):
     from ofighters_amd import checkpoint
     r, e, t, _ = _standins(monkeypatch, tmp_path)
@@ -414,40 +297,6 @@ def test_checkpoint_every_writes_at_episode_ends(tmp_path, monkeypatch):
 
 
 # ------------------------------------------------------------------------- DeviceTrainer's own fingerprint and state
-class _HostBuffer:
-    """DeviceBuffer stand-in holding its bytes on the host."""
-    log = []
-    def __init__(self, nbytes): self.nbytes, self.data, self.ptr = int(nbytes), np.zeros(int(nbytes), np.uint8), 1
-    def upload(self, arr):
-        _HostBuffer.log.append(self)
-        b = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
-        self.data[:b.size] = b
-        return self
-    def download(self, dtype, shape, offset=0):
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        return self.data[offset:offset + n].view(dtype).reshape(shape).copy()
-    def free(self): pass
-
-
-class _FakeBatch:
-    N, M = 2, 2
-    def sync(self): pass
-    def replay_create(self, capacity, frames=0):
-        self.replay_capacity, self.replay_frames = capacity, frames or capacity + capacity // 4 + 2
-    def replay_prioritize(self, alpha, eps): self.replay_prioritized = True
-
-
-BASE = dict(learning_rate=1e-3, batch_size=4, memory_size=16, frames=0, seed=5, fit_batch=16, prioritized=True, n_step=3,
-            target_sync=2, double_dqn=True, huber_delta=1.0, clip_norm=10.0)
-
-
-def _trainer(monkeypatch, n_floats=6, **kw):
-    import ofighters_amd.trainer as tr
-    from ofighters_amd.lib.epsilon import Epsilon_decay
-    monkeypatch.setattr(tr, "DeviceBuffer", _HostBuffer)
-    return tr.DeviceTrainer(_FakeBatch(), np.arange(n_floats, dtype=np.float32), epsilon=Epsilon_decay(), **dict(BASE, **kw))
-
-
 def test_device_trainer_state_round_trips_on_host_buffers(monkeypatch):
     a = _trainer(monkeypatch)
     assert tuple(sorted(a.fingerprint())) == tuple(sorted(TRAINER_KEYS))

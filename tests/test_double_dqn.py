@@ -15,7 +15,7 @@ F = np.float32
 # ------------------------------------------------------------------------------------------------------ CPU
 def test_ddqn_symbols_exported_declared_and_bound():
     from ofighters_amd import _native as nat
-    from tests.test_abi import header_symbols
+    from tests.abi_header import header_symbols
     L = C.CDLL(nat.LIB_PATH)
     declared = header_symbols()
     for s in DDQN_SYMBOLS:

@@ -1,6 +1,6 @@
 """The exploration ladder and evaluation arenas without a device: the host arithmetic of ofighters_amd/exploration.py, the
 inputs of the device test (how far they keep from a last-bit flip of pow), the binding's entries, and TrainingRollout's
-fingerprint / checkpoint under the options on the stand-ins of tests/test_checkpoint_format.py."""
+fingerprint / checkpoint under the options on the stand-ins of tests/checkpoint_standin.py."""
 import math
 
 import numpy as np
@@ -9,7 +9,7 @@ import pytest
 from ofighters_amd import _native as nat
 from ofighters_amd.exploration import apex_exponents, score_groups
 from tests import ladder_oracle as lo
-from tests import test_checkpoint_format as base
+from tests import checkpoint_standin as base
 
 LADDER_KEYS = ("epsilon_ladder", "eval_arenas", "total_arenas", "score_bands")
 
@@ -109,7 +109,7 @@ def test_binding_carries_the_new_entries():
 
 
 # ------------------------------------------------------------------ TrainingRollout on the stand-ins: fingerprint, checkpoint
-class _LadderEngine(base._FakeEngine):
+class _LadderEngine(base.CheckpointEngine):
     """The stand-in engine with the two calls the options add."""
     ladder = None
 
@@ -128,9 +128,8 @@ class _LadderEngine(base._FakeEngine):
 
 
 def _standins(monkeypatch, tmp_path, **kw):
-    monkeypatch.setattr(base, "_FakeEngine", _LadderEngine)
     kw.setdefault("engine_kw", {"N": 6})
-    return base._standins(monkeypatch, tmp_path, **kw)
+    return base.standins(monkeypatch, tmp_path, engine=_LadderEngine, **kw)
 
 
 ON = dict(epsilon_ladder=7.0, eval_arenas=2, score_bands=2)

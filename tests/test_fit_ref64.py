@@ -1,6 +1,6 @@
 """tests/fit_ref64.py - the chunked float64 checker of one fit step - checked on the CPU against the small references the
-suite already trusts: tests/test_train.py::_torch_reference (F.conv2d, F.batch_norm in float64), tests/per_torch_ref.py
-and tests/huber_torch_ref.py.  Random maps with 3 % of the bits set, weights synthetic(5).
+suite already trusts: tests/fit_torch_ref.py::fit_reference (F.conv2d, F.batch_norm in float64) and its options.
+Random maps with 3 % of the bits set, weights synthetic(5).
 
 The bound is 1e-10 of the layer's kernel-gradient scale on every tensor: two float64 evaluations of one graph in
 different summation orders (measured: worst 7.8e-12 unchunked, 7e-15 chunked against unchunked).
@@ -18,6 +18,7 @@ import pytest
 
 from oracle import pyoracle
 from tests import fit_ref64 as F64
+from tests.fit_torch_ref import fit_reference
 
 BOUND = 1e-10
 
@@ -33,6 +34,12 @@ def _inputs(n, seed):
              px=rs.randint(0, 400, n).astype(np.int64), py=rs.randint(0, 400, n).astype(np.int64),
              y_act=rs.uniform(-1, 2, n).astype(np.float32), y_ptr=rs.uniform(-1, 2, n).astype(np.float32))
     return w, shapes, x0.astype(np.float64), a
+
+
+def _ref(*args, **kw):
+    """fit_reference -> (l1, l2, g, stats, e1, e2)"""
+    r = fit_reference(*args, **kw)
+    return (r["l1"], r["l2"], r["g"], r["stats"]) + ((None, None) if r["e"] is None else (r["e"][:, 0], r["e"][:, 1]))
 
 
 def _agree(tag, shapes, got, ref_l, ref_g, ref_stats=None):
@@ -63,11 +70,10 @@ def _agree(tag, shapes, got, ref_l, ref_g, ref_stats=None):
 
 
 def test_unchunked_checker_equals_torch_reference_at_4_rows():
-    from tests.test_train import _torch_reference
     w, shapes, x0, a = _inputs(4, 1)
-    l1, l2, g, stats = _torch_reference(w, shapes, x0, a["vec8"], a["iaction"], a["px"], a["py"], a["y_act"], a["y_ptr"])
+    l1, l2, g, stats = _ref(w, shapes, x0, a["vec8"], a["iaction"], a["px"], a["py"], a["y_act"], a["y_ptr"])[:4]
     got = F64.fit_step(w, shapes, **a)
-    _agree("checker vs _torch_reference, 4 rows", shapes, got, (l1, l2), g, stats)
+    _agree("checker vs fit_reference, 4 rows", shapes, got, (l1, l2), g, stats)
     assert got["e"].shape == (4, 2)
     assert abs((got["e"][:, 0] ** 2).sum() / 8 - l1) <= 1e-12 * l1 and abs((got["e"][:, 1] ** 2).sum() / 640000 - l2) <= 1e-12 * l2
 
@@ -84,27 +90,24 @@ def test_chunked_equals_unchunked():
 def test_options_against_the_small_references():
     """legacy bilinear, dense targets, row weights and Huber(delta), each at 2 rows against the reference the suite
     already uses for it (the chunked form: chunk 1)"""
-    from tests.huber_torch_ref import huber_reference
-    from tests.per_torch_ref import weighted_reference
-    from tests.test_train import _torch_reference
     w, shapes, x0, a = _inputs(2, 3)
     rs = np.random.RandomState(4)
     pos = (a["vec8"], a["iaction"], a["px"], a["py"], a["y_act"], a["y_ptr"])
-    l1, l2, g, stats = _torch_reference(w, shapes, x0, *pos, legacy=True)
+    l1, l2, g, stats = _ref(w, shapes, x0, *pos, legacy=True)[:4]
     _agree("legacy", shapes, F64.fit_step(w, shapes, legacy=True, chunk=1, **a), (l1, l2), g, stats)
     dense = (rs.uniform(-1, 2, (2, 2)), rs.uniform(-1, 2, (2, 400, 400)))
-    l1, l2, g, stats = _torch_reference(w, shapes, x0, a["vec8"], None, None, None, None, None, dense=dense)
+    l1, l2, g, stats = _ref(w, shapes, x0, a["vec8"], dense=dense)[:4]
     got = F64.fit_step(w, shapes, a["bits"], a["vec8"], dense=dense, chunk=1)
     _agree("dense", shapes, got, (l1, l2), g, stats)
     assert "e" not in got
     row_w = rs.uniform(0.05, 1.0, 2)
-    l1, l2, g, e1, e2 = weighted_reference(w, shapes, x0, *pos, row_w)
+    l1, l2, g, _, e1, e2 = _ref(w, shapes, x0, *pos, row_w=row_w)
     got = F64.fit_step(w, shapes, row_w=row_w, chunk=1, **a)
     _agree("row weights", shapes, got, (l1, l2), g)
     assert np.abs(got["e"] - np.stack([e1, e2], 1)).max() <= BOUND * np.abs(e1).max()
     delta = float(np.median(np.abs(np.stack([e1, e2]))))          # errors on both sides of delta
     assert (np.abs(np.stack([e1, e2])) > delta).any() and (np.abs(np.stack([e1, e2])) < delta).any()
-    l1, l2, g, h1, h2 = huber_reference(w, shapes, x0, *pos, row_w, delta)
+    l1, l2, g, _, h1, h2 = _ref(w, shapes, x0, *pos, row_w=row_w, huber_delta=delta)
     got = F64.fit_step(w, shapes, row_w=row_w, huber_delta=delta, chunk=1, **a)
     _agree("row weights + huber", shapes, got, (l1, l2), g)
     assert np.abs(got["e"] - np.stack([h1, h2], 1)).max() <= BOUND * np.abs(h1).max()

@@ -18,7 +18,7 @@ WORDS = W * H // 32
 # ------------------------------------------------------------------------------------------------------ CPU
 def test_global_symbols_exported_declared_and_bound():
     from ofighters_amd import _native as nat
-    from tests.test_abi import header_symbols
+    from tests.abi_header import header_symbols
     L = C.CDLL(nat.LIB_PATH)
     declared = header_symbols()
     for s in GLOBAL_SYMBOLS:
@@ -134,7 +134,7 @@ def test_restatement_write_back_levels_and_the_later_entry_wins():
 
 def test_trainer_argument_checks(monkeypatch):
     from ofighters_amd.trainer import DeviceTrainer, fingerprint_diff
-    from tests.test_checkpoint_format import TRAINER_KEYS, _trainer
+    from tests.checkpoint_standin import TRAINER_KEYS, host_trainer as _trainer
     with pytest.raises(ValueError) as err:
         DeviceTrainer(None, np.zeros(4, np.float32), global_sampling=True, reference_quirks=True)
     assert "global sampling" in str(err.value)
@@ -210,7 +210,7 @@ def _dev_sample(b, seed, draw, n_rows, per=False, beta=0.0):
 
 
 def _spread_masses(b, seed):
-    from tests.test_prioritized_replay import _set_masses
+    from tests.replay_cases import set_masses as _set_masses
     rs = np.random.RandomState(seed)
     spread = 10.0 ** rs.uniform(-3, 3, b.N * b.replay_capacity)
     _set_masses(b, lambda r: np.stack([spread[:len(r)], np.zeros(len(r))], 1))
@@ -247,7 +247,7 @@ def _check_sampler(b, skip, v, n_rows_list, draws, arena_base=0):
 @pytest.mark.parametrize("frames", [0, 4])
 @pytest.mark.parametrize("N", [5, 300])
 def test_sampler_equals_restatement(N, frames, packed):
-    from tests.test_prioritized_replay import _skip, _varied_masks
+    from tests.replay_cases import stale_rows as _skip, varied_masks as _varied_masks
     M = 4
     b = _rollout(N, M, capacity=40, frames=frames, masks=_varied_masks(N, M), alpha=1.0, packed=packed)
     cnt, _ = b.replay_count()
@@ -271,7 +271,7 @@ def test_sampler_equals_restatement(N, frames, packed):
 @pytest.mark.gpu
 def test_shards_draw_different_rows_from_equal_memories():
     N, M = 5, 4
-    from tests.test_prioritized_replay import _varied_masks
+    from tests.replay_cases import varied_masks as _varied_masks
     a = _rollout(N, M, masks=_varied_masks(N, M), alpha=1.0)
     _spread_masses(a, 1)
     blob = a.replay_export(0, N)
@@ -365,7 +365,7 @@ def _gather_both(b, arena_h, slot_h, nstep, gamma=0.9):
 @pytest.mark.gpu
 @pytest.mark.parametrize("packed", [False, True])
 def test_list_gather_equals_the_window_gathers(packed):
-    from tests.test_prioritized_replay import _varied_masks
+    from tests.replay_cases import varied_masks as _varied_masks
     N, M = 5, 4
     b = _rollout(N, M, capacity=40, frames=0, masks=_varied_masks(N, M), alpha=1.0, packed=packed)
     _spread_masses(b, 2)
@@ -394,7 +394,7 @@ def test_list_gather_equals_the_window_gathers(packed):
 @pytest.mark.parametrize("packed", [False, True])
 def test_list_gather_pads_entries_that_name_no_row(packed):
     from ofighters_amd import DeviceBuffer
-    from tests.test_prioritized_replay import _varied_masks
+    from tests.replay_cases import varied_masks as _varied_masks
     N, M = 5, 4
     b = _rollout(N, M, capacity=40, frames=0, masks=_varied_masks(N, M), packed=packed)
     cnt, _ = b.replay_count()
@@ -438,7 +438,7 @@ def _both_write_backs(a, b, arena_h, slot_h, td, between=None):
     a.replay_gather_list_into(ar_d, sl_d, n, rows_a, None, None)
     tab, per, batch = _table(arena_h, slot_h, b.N)
     tab_d, per_d = DeviceBuffer(tab.nbytes).upload(tab), DeviceBuffer(per.nbytes).upload(per)
-    from tests.test_prioritized_replay import _gather_rows
+    from tests.replay_cases import gather_rows as _gather_rows
     rows_b, got = _gather_rows(b, tab_d, per_d, batch, 0, n)
     assert got == n
     a.sync(), b.sync()
@@ -455,7 +455,7 @@ def _both_write_backs(a, b, arena_h, slot_h, td, between=None):
 
 @pytest.mark.gpu
 def test_list_write_back_equals_the_per_arena_write_back():
-    from tests.test_prioritized_replay import _varied_masks
+    from tests.replay_cases import varied_masks as _varied_masks
     N, M = 16, 4
     mems = []
     for _ in range(2):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import ckpt_blob
+from tests.train_state import inspect_replay as _inspect, training_state as _state
 
 pytestmark = pytest.mark.gpu
 
@@ -89,25 +90,6 @@ def _fresh():
     b.replay_create(capacity=CAP, frames=0)
     b.replay_prioritize(ALPHA, EPS)
     return b
-
-
-def _inspect(b, ticks):
-    """What the host inspections report: counts, appended, and per arena the rows, the masses and every held frame."""
-    from ofighters_amd import OfxError
-    cnt, app = b.replay_count()
-    out = {"count": cnt, "appended": app, "rows": [], "mass": [], "frames": []}
-    for a in range(b.N):
-        out["rows"].append(b.replay_rows(a).tobytes())
-        out["mass"].append(b.replay_priorities(a).tobytes() if b.replay_prioritized else None)
-        held = {}
-        for t in range(ticks):
-            try:
-                s, l = b.replay_frame(a, t)
-                held[t] = (np.packbits(s).tobytes(), np.packbits(l).tobytes())
-            except OfxError:
-                pass
-        out["frames"].append(held)
-    return out
 
 
 def _same(x, y):
@@ -273,25 +255,6 @@ def _build(cfg, **roll_kw):
     roll = TrainingRollout(b, tr, ["random"] * M2, SEED2, policy_ships=(0, 1), episode_ticks=20, collecting_steps=5,
                            replay_every=3, **roll_kw)
     return b, tr, roll
-
-
-def _state(b, tr, roll):
-    """Everything the issue lists, in comparable form."""
-    from ofighters_amd import _native as nat
-    b.sync()
-    s = {"weights": tr.weights_host().tobytes(), "adam_m": tr.adam_m.download(np.float32, (tr.n_floats,)).tobytes(),
-         "adam_v": tr.adam_v.download(np.float32, (tr.n_floats,)).tobytes(),
-         "target": None if tr.target is None else tr.target_host().tobytes(),
-         "losses": list(tr.losses), "grad_norms": list(tr.grad_norms), "fit_steps": tr.fit_steps, "draws": tr.draws,
-         "epsilon": tr.epsilon.get(), "score_log": [x.tolist() for x in roll.score_log], "epsilons": list(roll.epsilons),
-         "roll_losses": list(roll.losses),
-         "counters": (roll.tick, roll.total_steps, roll.capture_tick, roll.episode, b.episode, b.tick)}
-    for f in range(19):
-        s["field%d" % f] = b.get(f).tobytes()
-    s["maps"] = [m.tobytes() for m in b.maps_host(nat.MAP_U8)]
-    s["replay"] = _inspect(b, roll.capture_tick)
-    s["replay"]["count"], s["replay"]["appended"] = s["replay"]["count"].tobytes(), s["replay"]["appended"].tobytes()
-    return s
 
 
 _RUN_A = {}

@@ -1,9 +1,9 @@
 """The textbook fit at 1024 rows against the chunked float64 checker (tests/fit_ref64.py on the GPU, one child for the
 module), on the two windows of tests/test_train.py::test_lean_fit_equals_plain_fit_large_batches:
 
-    window 0   rows [0, 1024) of _collect_minibatch(256) - the minibatch on which the lean form sits 4.5e-4 / 1.1e-3 /
+    window 0   rows [0, 1024) of collect_minibatch(256) - the minibatch on which the lean form sits 4.5e-4 / 1.1e-3 /
                6.8e-4 of scale away from float64 on conv1.kernel / conv1.gamma / conv2.kernel
-    control    rows [4, 1028) of _collect_minibatch(257)
+    control    rows [4, 1028) of collect_minibatch(257)
 
 The bounds are those of tests/test_gpu_fit_fp64.py, strict on every tensor, against float64 - with ONE freedom, shown
 and not assumed: a ReLU gate of dense1 / dense2 / updense1 that is a near-tie may be decided either way.  The child
@@ -32,8 +32,8 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
-from tests.test_gpu_fit_fp64 import (LR, _report, check_gradient, check_losses, check_update, fit_buffers, report_case,
-                                     reset_buffers, run_checker, tensor_errors)
+from tests.fit_fp64_cases import (LR, check_gradient, check_losses, check_update, fit_buffers, report as _report, report_case,
+                                  reset_buffers, run_checker, tensor_errors)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,13 +46,13 @@ ROWS, CHUNK = 1024, 32
 def fit_both_windows(tmp):
     """both forms on both windows, then - the handles closed - the checker on both: one child"""
     from ofighters_amd import DeviceBuffer, _native as nat
-    from tests.test_train import _collect_minibatch
+    from tests.fit_cases import collect_minibatch
     w, shapes = pyoracle.policy_init(5, trained_like=True)
     rs = np.random.RandomState(3)
     y_act, y_ptr = rs.uniform(-1, 2, ROWS).astype(np.float32), rs.uniform(-1, 2, ROWS).astype(np.float32)
     out, arrays, cases, workspace = {}, dict(y_act=y_act, y_ptr=y_ptr), [], {}
     for name, (arenas, skip) in WINDOWS.items():
-        b, n_all, rows_all, bp_all, bn_all = _collect_minibatch(arenas)
+        b, n_all, rows_all, bp_all, bn_all = collect_minibatch(arenas)
         assert n_all >= ROWS + skip
         y, y2 = DeviceBuffer(4 * ROWS).upload(y_act), DeviceBuffer(4 * ROWS).upload(y_ptr)
         bufs = fit_buffers(w)

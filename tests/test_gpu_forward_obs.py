@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 
 from tests import obs_batches as OB
-from tests.test_gpu_head_frame_argmax import CASES as FRAME_CASES, frame_weights, where
-from tests.test_gpu_policy_fp64 import TOL_ACT, TOL_HEAT, _report
+from tests.frame_cases import CASES as FRAME_CASES, frame_weights, where
+from tests.policy_fp64_cases import TOL_ACT, TOL_HEAT, report as _report
 
 pytestmark = pytest.mark.gpu
 

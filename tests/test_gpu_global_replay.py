@@ -43,7 +43,7 @@ def _record(b, names):
 
 
 def _state(b, tr, roll):
-    from tests.test_gpu_checkpoint import _state as ckpt_state
+    from tests.train_state import training_state as ckpt_state
     s = ckpt_state(b, tr, roll)                          # weights, moments, losses, counters, arenas, rows, masses, frames
     s["blob"] = b.replay_export(0, N).tobytes()          # ... and mmax, which only the blob shows
     return s

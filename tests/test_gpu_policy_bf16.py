@@ -10,7 +10,7 @@ pointer a near-maximum of the float64 map - and that the fp32 path is untouched 
 import numpy as np
 import pytest
 
-from tests.test_gpu_policy_fp64 import _report, _rollout
+from tests.policy_fp64_cases import report as _report, rollout as _rollout
 
 pytestmark = pytest.mark.gpu
 TOL_LOWP = {1: 3e-2, 2: 4e-3}   # max |heat - heat64| / max |heat64|; measured 8e-3 (bf16: 8 significant bits) / ~1e-3 (fp16: 11)

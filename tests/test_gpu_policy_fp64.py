@@ -4,42 +4,12 @@ MFMA GEMMs, split-K dense1) - are measured against a float64 evaluation of the s
 The bounds below are 4x the largest error either of them showed on the chip (r02), per output:
 act_values, heat-map interior, heat-map frame (the frame takes the zero-padding path of k_head_frames).  Parity with Keras itself
 stays UNPINNED (no keras / tensorflow / weights in the image)."""
-import json
-import os
-
 import numpy as np
 import pytest
 
+from tests.policy_fp64_cases import TOL_ACT, TOL_FRAME, TOL_HEAT, report as _report, rollout as _rollout
+
 pytestmark = pytest.mark.gpu
-
-# max |err| / max |value| of a tensor against float64.  Measured (r02, gpurun_out/policy_fp64_report.json):
-#   HIP path      act 3.6e-6 (4096 x 8, bench weights), heat interior 5.8e-7, heat frame 5.9e-7
-#   C restatement act 2.0e-6,                           heat interior 2.0e-6, heat frame 1.9e-6
-# arg-max equal to the float64 map's for 288 of 288 ships.
-TOL_ACT, TOL_HEAT, TOL_FRAME = 1.5e-5, 8e-6, 8e-6
-REPORT = os.path.join(os.path.dirname(__file__), "..", "gpurun_out", "policy_fp64_report.json")
-
-
-def _rollout(N, M, seed, ticks):
-    from ofighters_amd import ArenaBatch
-    b = ArenaBatch(N, M)
-    b.spawn_random(seed)
-    for t in range(ticks):
-        b.bot_actions(["turret"] * (M // 2) + ["random"] * (M - M // 2), seed, tick=t)
-        b.step(actions_ptr=b._actions.ptr)
-    return b
-
-
-def _report(tag, rec):
-    try:
-        os.makedirs(os.path.dirname(REPORT), exist_ok=True)
-        data = json.load(open(REPORT)) if os.path.exists(REPORT) else {}
-        data[tag] = rec
-        json.dump(data, open(REPORT, "w"), indent=1)
-    except OSError:
-        pass
-    print(tag, rec)
-
 
 @pytest.mark.parametrize("trained,legacy", [(False, False), (True, False), (True, True)])
 def test_small_batch_against_fp64(trained, legacy):

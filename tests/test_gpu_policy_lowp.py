@@ -26,9 +26,9 @@ import pytest
 
 from tests import policy_lowp_ref as L
 from tests import policy_ref64 as R
-from tests.test_gpu_policy_fp64 import TOL_ACT, TOL_HEAT, _report, _rollout
-from tests.test_policy_lowp_ref import (BORDER_TICKS, CASES, SHARE_CAP, YARD_SHARE, border_xy, case_inputs, case_reference,
-                                        case_tag, per_ship, summary, violations)
+from tests.policy_fp64_cases import TOL_ACT, TOL_HEAT, report as _report, rollout as _rollout
+from tests.policy_lowp_cases import (BORDER_TICKS, CASES, SHARE_CAP, YARD_SHARE, border_xy, case_inputs, case_reference,
+                                     case_tag, per_ship, summary, violations)
 
 pytestmark = pytest.mark.gpu
 # (tag, ship) -> allowed heat max, for a ship whose worst pixel was SHOWN to sit behind an operand within fp32 error of a

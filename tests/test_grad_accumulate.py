@@ -19,7 +19,7 @@ WORDS = 2 * 5000                                            # uint32 words of on
 def test_split_symbols_exported_declared_and_bound():
     from ofighters_amd import _native as nat
     from ofighters_amd.engine import ArenaBatch
-    from tests.test_abi import header_symbols
+    from tests.abi_header import header_symbols
     L = C.CDLL(nat.LIB_PATH)
     declared = header_symbols()
     for s in SYMBOLS:
@@ -55,7 +55,7 @@ def test_trainer_refuses_accumulate_with_reference_quirks():
 
 def test_fingerprint_carries_accumulate_only_above_one(monkeypatch):
     from ofighters_amd.trainer import fingerprint_diff
-    from tests.test_checkpoint_format import TRAINER_KEYS, _trainer
+    from tests.checkpoint_standin import TRAINER_KEYS, host_trainer as _trainer
     plain = _trainer(monkeypatch, global_sampling=True)
     one = _trainer(monkeypatch, global_sampling=True, accumulate=1)
     two = _trainer(monkeypatch, global_sampling=True, accumulate=2)
@@ -88,14 +88,14 @@ def _row_weights(n, seed=8):
 
 
 class _Case:
-    """One gathered minibatch (tests.test_train._collect_minibatch), the weights of policy_init(5), targets and row
+    """One gathered minibatch (tests.fit_cases.collect_minibatch), the weights of policy_init(5), targets and row
     weights on the device; chunk(i) addresses rows [4 i, 4 i + 4) as pointer offsets."""
 
     def __init__(self, N, form="lean"):
         from ofighters_amd import DeviceBuffer, _native as nat
         from oracle import pyoracle
-        from tests.test_train import _collect_minibatch
-        self.b, self.n, self.rows, self.bp, _ = _collect_minibatch(N)
+        from tests.fit_cases import collect_minibatch
+        self.b, self.n, self.rows, self.bp, _ = collect_minibatch(N)
         assert self.n == 4 * N
         self.b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
         self.w, self.shapes = pyoracle.policy_init(5, trained_like=True)

@@ -15,7 +15,7 @@ DELTA = 0.5
 # ------------------------------------------------------------------------------------------------------ CPU
 def test_robust_symbol_exported_declared_and_bound():
     from ofighters_amd import _native as nat
-    from tests.test_abi import header_symbols
+    from tests.abi_header import header_symbols
     L = C.CDLL(nat.LIB_PATH)
     declared = header_symbols()
     for s in SYMBOLS:
@@ -44,7 +44,7 @@ def test_trainer_refuses_reference_quirks(name):
 def test_torch_reference_huber_on_two_scalars():
     """one error in each zone, delta = 0.5: h(0.2) = 0.5 * 0.04 = 0.02 with slope 0.2; h(-2) = 0.5 * 2 - 0.125 = 0.875
     with slope -0.5"""
-    from tests.huber_torch_ref import huber
+    from tests.fit_torch_ref import huber
     e = torch.tensor([0.2, -2.0], dtype=torch.float64, requires_grad=True)
     h = huber(e, 0.5)
     h.sum().backward()
@@ -79,8 +79,8 @@ def _download(bufs, w):
 def test_both_options_off_is_the_weighted_fit(form):
     from ofighters_amd import DeviceBuffer, _native as nat
     from oracle import pyoracle
-    from tests.test_train import _collect_minibatch
-    b, n, rows_d, bp_d, _ = _collect_minibatch(1)
+    from tests.fit_cases import collect_minibatch
+    b, n, rows_d, bp_d, _ = collect_minibatch(1)
     assert n == 4
     b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
     w, _ = pyoracle.policy_init(5, trained_like=True)
@@ -114,7 +114,7 @@ def _huber_case(b, n, rows_d, bp_d):
     head 2 (y = o_ref - e_wanted, o_ref from the float64 graph with zero targets), random row weights, and the float64
     reference of that case.  Computed once: the collection is seeded, every caller gathers the same rows."""
     from oracle import pyoracle
-    from tests.huber_torch_ref import huber_reference
+    from tests.fit_torch_ref import fit_reference
     w, shapes = pyoracle.policy_init(9, trained_like=True)
     if "case" not in _REF:
         rows = rows_d.download(b.TRANSITION_DTYPE, (n,))
@@ -124,10 +124,11 @@ def _huber_case(b, n, rows_d, bp_d):
                  rows["px"].astype(np.int64), rows["py"].astype(np.int64))
         rw = _row_weights(n)
         zero = np.zeros(n)
-        _, _, _, o1, o2 = huber_reference(*fixed, zero, zero, rw, DELTA, backward=False)
+        o1, o2 = fit_reference(*fixed, zero, zero, row_w=rw, huber_delta=DELTA, backward=False)["e"].T
         want = DELTA * np.array([0.25, -0.5, 3.0, -2.0])
         y, y2 = (o1 - want).astype(np.float32), (o2 - want[[2, 0, 3, 1]]).astype(np.float32)
-        _REF["case"] = (y, y2, rw, huber_reference(*fixed, y, y2, rw, DELTA), rows.copy())
+        ref = fit_reference(*fixed, y, y2, row_w=rw, huber_delta=DELTA)
+        _REF["case"] = (y, y2, rw, (ref["l1"], ref["l2"], ref["g"], ref["e"][:, 0], ref["e"][:, 1]), rows.copy())
     y, y2, rw, ref, rows0 = _REF["case"]
     assert np.array_equal(rows_d.download(b.TRANSITION_DTYPE, (n,)), rows0)
     return w, shapes, y, y2, rw, ref
@@ -147,8 +148,8 @@ def test_huber_fit_vs_torch_autograd(form):
     """the bounds of test_weighted_fit_vs_torch_autograd; the errors sit at |e| / delta = 0.25, 0.5, 2, 3 by
     construction, so fp32 and float64 cannot disagree on a row's zone (asserted from the returned td)"""
     from ofighters_amd import DeviceBuffer, _native as nat
-    from tests.test_train import _collect_minibatch, _compare_gradients
-    b, n, rows_d, bp_d, _ = _collect_minibatch(1)
+    from tests.fit_cases import collect_minibatch, compare_gradients
+    b, n, rows_d, bp_d, _ = collect_minibatch(1)
     assert n == 4
     b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
     w, shapes, y, y2, rw, (rl1, rl2, rg, e1, e2) = _huber_case(b, n, rows_d, bp_d)
@@ -164,7 +165,7 @@ def test_huber_fit_vs_torch_autograd(form):
     _assert_zones(td, DELTA, 0.25 - 1e-3)
     _assert_zones(np.stack([e1, e2], 1), DELTA, 0.25 - 1e-3)
     assert abs(l1 - rl1) <= 1e-4 * max(1.0, abs(rl1)) and abs(l2 - rl2) <= 1e-4 * max(1e-9, abs(rl2)) + 1e-12
-    _compare_gradients(shapes, rg, g)
+    compare_gradients(shapes, rg, g)
     np.testing.assert_allclose(td[:, 0], e1, rtol=0, atol=1e-4 * max(1.0, np.abs(e1).max()))
     np.testing.assert_allclose(td[:, 1], e2, rtol=0, atol=1e-4 * max(1.0, np.abs(e2).max()))
     np.testing.assert_allclose(norm, np.sqrt((g * g).sum()), rtol=1e-6)
@@ -186,8 +187,8 @@ def test_gradient_norm_clip():
     lr * sign(g), which would hide a missing scale."""
     from ofighters_amd import DeviceBuffer
     from oracle import pyoracle
-    from tests.test_train import _collect_minibatch
-    b, n, rows_d, bp_d, _ = _collect_minibatch(1)
+    from tests.fit_cases import collect_minibatch
+    b, n, rows_d, bp_d, _ = collect_minibatch(1)
     assert n == 4
     w, _ = pyoracle.policy_init(9, trained_like=True)
     y, y2 = _fit_inputs(n)
@@ -232,8 +233,8 @@ def test_robust_lean_fit_equals_plain_fit_at_128_rows():
     targets: the nearest error sits at 1.0026 delta in both forms, 222 of the 256 errors lie beyond delta)."""
     from ofighters_amd import DeviceBuffer, _native as nat
     from oracle import pyoracle
-    from tests.test_train import _check_lean_equals_plain, _collect_minibatch
-    b, n, rows_d, bp_d, bn_d = _collect_minibatch(32)
+    from tests.fit_cases import check_lean_equals_plain, collect_minibatch
+    b, n, rows_d, bp_d, bn_d = collect_minibatch(32)
     assert n == 128
     rw = DeviceBuffer(4 * n).upload(_row_weights(n, 6))
     td_d = DeviceBuffer(8 * n)
@@ -257,7 +258,7 @@ def test_robust_lean_fit_equals_plain_fit_at_128_rows():
     plain_fit = b.dqn_fit
     b.dqn_fit = robust
     try:
-        _check_lean_equals_plain(b, n, rows_d, bp_d, bn_d)
+        check_lean_equals_plain(b, n, rows_d, bp_d, bn_d)
     finally:
         b.dqn_fit = plain_fit
     assert len(tds) == 3                                    # lean, lean again, plain
@@ -315,8 +316,8 @@ def test_training_rollout_with_huber_and_clip():
 def test_entry_refuses_negative_and_nan_options():
     from ofighters_amd import DeviceBuffer, _native as nat
     from oracle import pyoracle
-    from tests.test_train import _collect_minibatch
-    b, n, rows_d, bp_d, _ = _collect_minibatch(1)
+    from tests.fit_cases import collect_minibatch
+    b, n, rows_d, bp_d, _ = collect_minibatch(1)
     w, _ = pyoracle.policy_init(5, trained_like=True)
     y, y2 = _fit_inputs(n)
     y_d, y2_d = DeviceBuffer(4 * n).upload(y), DeviceBuffer(4 * n).upload(y2)

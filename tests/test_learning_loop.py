@@ -12,71 +12,12 @@ import numpy as np
 import pytest
 
 from ofighters_amd.rollout import TrainingRollout
-
-
-class _Buf:
-    ptr = 1
-
-
-class _Eps:
-    def __init__(self): self.v, self.n = 0.5, 0
-    def get(self): return self.v
-    def next(self): self.n += 1
-
-
-class _FakeTrainer:
-    def __init__(self):
-        self.weights, self.epsilon, self.replays, self.saved = _Buf(), _Eps(), [], []
-    def decay_epsilon(self): self.epsilon.next()
-    def replay(self):
-        self.replays.append(self.clock())
-        return (1.0, 2.0)
-    def save(self, id=None, overwrite=False, folder=None):
-        self.saved.append(id)
-        return "%s/%s" % (folder, id)
-
-
-class _FakeEngine:
-    """Records the call order of one lock-step; ship 0 of arena 1 dies at tick 7 of every episode."""
-    def __init__(self, N=3, M=2):
-        self.N, self.M, self.episode, self.log, self.t = N, M, 0, [], 0
-        self.alive = np.ones((N, M), np.uint8)
-        self.seen = np.zeros((N, M), bool)
-        self.mask = np.zeros((N, M), bool); self.mask[:, 0] = True
-    def sync(self): pass
-    def spawn_random(self, seed): pass
-    def restart_random(self, seed):
-        self.episode += 1; self.alive[:] = 1; self.t = 0
-    def episode_scores(self): return np.arange(self.M + 1, dtype=np.int64)
-    def policy_pin_weights(self, p): self.log.append("pin")
-    def get(self, field): return self.alive.copy()
-    def agents_first_done(self, mask_ptr, seen):          # the device-side `done` latches (ofx_agents_first_done)
-        if getattr(seen, "cleared", False): self.seen, seen.cleared = np.zeros((self.N, self.M), bool), False
-        first = (self.alive == 0) & self.mask & ~self.seen
-        self.seen |= first
-        return int(first.sum())
-    def bot_actions(self, beh, seed, tick=None): self.log.append("bots")
-    def policy_forward(self, w, m): self.log.append("forward")
-    def policy_explore(self, eps, seed, tick=None, collecting=False, ship_mask_ptr=None):
-        self.log.append("explore:%d:%d" % (tick, collecting))
-    def replay_capture(self, tick, ship_mask_ptr=None): self.log.append("capture:%d" % tick)
-    def policy_actions(self, ship_mask_ptr=None): self.log.append("actions")
-    def step(self):
-        self.log.append("step"); self.t += 1
-        if self.t == 7: self.alive[1, 0] = 0
-    def rasterise(self): self.log.append("raster")
+from tests.rollout_standin import FakeTrainer, MortalEngine, fake_device_buffers
 
 
 def test_training_rollout_schedule(tmp_path, monkeypatch):
-    import ofighters_amd.engine as eng
-
-    class _DB:
-        def __init__(self, n): self.ptr = 7
-        def upload(self, a):
-            self.cleared = not np.asarray(a).any()         # TrainingRollout zeroes the latches at episode ends
-            return self
-    monkeypatch.setattr(eng, "DeviceBuffer", _DB)
-    e, t = _FakeEngine(), _FakeTrainer()
+    fake_device_buffers(monkeypatch)
+    e, t = MortalEngine(), FakeTrainer()
     r = TrainingRollout(e, t, ["idle", "idle"], seed=3, policy_ships=(0,), episode_ticks=40, snapshot_every=2,
                         snapshot_folder=str(tmp_path), collecting_steps=20, replay_every=50)
     t.clock = lambda: r.total_steps

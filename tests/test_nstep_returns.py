@@ -14,7 +14,7 @@ GAMMA = 0.9
 # ------------------------------------------------------------------------------------------------------ CPU
 def test_nstep_symbols_exported_declared_and_bound():
     from ofighters_amd import _native as nat
-    from tests.test_abi import header_symbols
+    from tests.abi_header import header_symbols
     L = C.CDLL(nat.LIB_PATH)
     declared = header_symbols()
     for s in NSTEP_SYMBOLS:

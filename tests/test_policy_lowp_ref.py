@@ -22,104 +22,15 @@ case and the loop case the yardstick's worst ship had, for the seeds 5 .. 16: 0.
 depends on the trunk - and for the same reason conv4's operands left unrounded in fp16 move NO ship out of bound
 with it.  Seed 15 is the one that leaves the yardstick its room AND shows every planted defect on every ship.  The
 choice was made on these CPU figures alone, before any kernel was compared."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 from tests import policy_lowp_ref as L
 from tests import policy_ref64 as R
-from tests.test_gpu_policy_fp64 import TOL_ACT, TOL_HEAT, _report
-
-SHARE_CAP = 0.02          # of a ship's 160 000 heat pixels beyond TOL_HEAT: a condition on the kernel, not a measurement
-YARD_SHARE = SHARE_CAP / 4  # ... which the inputs have to leave room for: the fp32 yardstick stays at or below this
-MODE = {1: "bf16", 2: "fp16"}
-WEIGHT_SEED = 15
-# the three cases of tests/test_gpu_policy_lowp.py: arenas (global ids), ships per arena, seed, ticks of [turret] * (M / 2) +
-# [random] * (M - M / 2) (tests/test_gpu_policy_fp64._rollout)
-CASES = {"small": (tuple(range(4)), 4, 31, 40), "border": (tuple(range(4)), 4, 31, 40), "loop": ((0, 255, 256, 257, 299), 2, 19, 25)}
-EDGE = (0, 1, 2, 7, 8, 199, 200, 391, 392, 398, 399, 400)   # test_trunk_sparse_is_bit_identical's border coordinates
-BORDER_TICKS = 6                                             # all turrets, after the ships were placed
-
-
-def border_xy(n, m):
-    rs = np.random.RandomState(5)
-    return rs.choice(EDGE, (n, m)), rs.choice(EDGE, (n, m))
-
-
-@functools.lru_cache(maxsize=None)
-def case_inputs(case):
-    """(ship maps [n][400][400] u8, laser maps, heads [n][M][8] f64, weights) of a case, from the CPU oracle."""
-    from oracle import pyoracle
-    from ofighters_amd import _native as nat
-    ids, M, seed, ticks = CASES[case]
-    beh = np.array([nat.BEHAVIOURS[b] for b in ["turret"] * (M // 2) + ["random"] * (M - M // 2)], np.int32)
-    arenas = []
-    for g in ids:
-        a = pyoracle.Arena(n_ships=M)
-        a.spawn(pyoracle.reset_draws(a.cfg, seed, g, 0))
-        for t in range(ticks):
-            a.step(a.bot_actions(beh, seed, g, t))
-        arenas.append(a)
-    if case == "border":
-        x, y = border_xy(len(ids), M)
-        turrets = np.full(M, nat.BEHAVIOURS["turret"], np.int32)
-        for k, (g, a) in enumerate(zip(ids, arenas)):
-            pt = a.ships()["pt"]
-            for i in range(M):
-                a.set_ship(i, x[k, i], y[k, i], pt[i, 0], pt[i, 1])
-            for t in range(ticks, ticks + BORDER_TICKS):
-                a.step(a.bot_actions(turrets, seed, g, t))
-    maps = [a.rasterise() for a in arenas]
-    sm, lm = np.stack([m[0] for m in maps]), np.stack([m[1] for m in maps])
-    head = np.stack([a.obs_head()[0] for a in arenas])
-    w, _ = pyoracle.policy_init(WEIGHT_SEED, trained_like=True)
-    for v in (sm, lm, head, w):
-        v.setflags(write=False)
-    return sm, lm, head, w
-
-
-def small_inputs():
-    return case_inputs("small")
-
-
-def rounded_pair(sm, lm, head, w, lowp, legacy, trunk_lowp):
-    """Per arena the rounded graph in float64 (the reference) and in float32 (the yardstick): [(act, heat)], [(act, heat)]."""
-    torch.set_num_threads(8)
-    ref, yard = [], []
-    for g in range(len(sm)):
-        v = head[g].astype(np.float32)
-        ref.append(L.forward(sm[g], lm[g], v, w, lowp, legacy_bilinear=legacy, trunk_lowp=trunk_lowp))
-        yard.append(L.forward(sm[g], lm[g], v, w, lowp, dtype=torch.float32, legacy_bilinear=legacy, trunk_lowp=trunk_lowp))
-    return ref, yard
-
-
-def per_ship(got, ref):
-    """L.stats of every ship of [(act [K][2], heat [K][400][400])] per arena against the reference of the same shape."""
-    return [L.stats(ga[i], gh[i], ra[i], rh[i], TOL_HEAT) for (ga, gh), (ra, rh) in zip(got, ref) for i in range(len(ra))]
-
-
-def summary(st):
-    """The worst ship of a list of L.stats, figure by figure."""
-    return {k: max(s[k] for s in st) for k in st[0] if k != "worst"}
-
-
-def violations(st, act_tol=TOL_ACT, share_cap=SHARE_CAP):
-    """The section's bounds: per ship act <= TOL_ACT and at most SHARE_CAP of the heat pixels beyond TOL_HEAT."""
-    return [(i, s["act"], s["share"]) for i, s in enumerate(st) if not (s["act"] <= act_tol and s["share"] <= share_cap)]
-
-
-@functools.lru_cache(maxsize=None)
-def case_reference(case, lowp, legacy, trunk_lowp):
-    """(reference, per-ship yardstick stats) of a case; computed once, shared by the tests, never written to."""
-    sm, lm, head, w = case_inputs(case)
-    ref, yard = rounded_pair(sm, lm, head, w, lowp, legacy, trunk_lowp)
-    return ref, per_ship(yard, ref)
-
-
-def small_reference(lowp, legacy, trunk_lowp):
-    return case_reference("small", lowp, legacy, trunk_lowp)
+from tests.policy_fp64_cases import TOL_ACT, TOL_HEAT, report as _report
+from tests.policy_lowp_cases import (CASES, MODE, YARD_SHARE, case_reference, case_tag, per_ship, small_inputs,
+                                     small_reference, summary, violations)
 
 
 @pytest.mark.parametrize("legacy", [False, True])
@@ -193,10 +104,6 @@ def test_rounding_helper_is_nearest_even(lowp):
         assert not np.array_equal(L.truncate_bf16(torch.from_numpy(x)).numpy().astype(np.float64), want)
     else:
         assert np.isinf(want).sum() == 6 and (want[np.abs(x) < 2.0 ** -14] != 0).any() and (want[x != 0] == 0).any()
-
-
-def case_tag(case, lowp, legacy, trunk_lowp):
-    return "%s_%s%s_%s" % (case, MODE[lowp], "_legacy_bilinear" if legacy else "", "stream" if trunk_lowp else "unfused")
 
 
 # every form the GPU test compares: (case, lowp, legacy, trunk_lowp)

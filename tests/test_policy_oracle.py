@@ -7,36 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import pyoracle
-
-
-def torch_forward(sm, lm, vec8, w, lay, legacy=False):
-    from tests.policy_ref64 import upsample2
-    def T(name):
-        o, shp = lay[name]
-        return torch.from_numpy(w[o:o + int(np.prod(shp))].reshape(shp).copy())
-
-    def conv(x, name):                              # HWIO -> OIHW
-        return F.conv2d(x, T(name + ".kernel").permute(3, 2, 0, 1), T(name + ".bias"), padding=1)
-
-    def bn(x, name):
-        return F.batch_norm(x, T(name + ".mean"), T(name + ".var"), T(name + ".gamma"), T(name + ".beta"),
-                            training=False, eps=1e-3)
-
-    x = torch.from_numpy(np.stack([sm, lm], 0).astype(np.float32))[None]      # NCHW
-    for i in (1, 2, 3, 4):
-        x = F.max_pool2d(F.relu(bn(conv(x, "conv%d" % i), "conv%d" % i)), 2)
-    flat = x.permute(0, 2, 3, 1).reshape(1, -1)                              # Flatten (h,w,c)
-    cat = torch.cat([torch.from_numpy(vec8.astype(np.float32))[None], flat], 1)
-    d1 = F.relu(cat @ T("dense1.kernel") + T("dense1.bias"))
-    d2 = F.relu(d1 @ T("dense2.kernel") + T("dense2.bias"))
-    act = d2 @ T("output1.kernel") + T("output1.bias")
-    u = F.relu(d1 @ T("updense1.kernel") + T("updense1.bias")).reshape(1, 1, 25, 25)
-    for i in (1, 2, 3):
-        u = upsample2(u, legacy)
-        u = F.relu(bn(conv(u, "upconv%d" % i), "upconv%d" % i))
-    u = upsample2(u, legacy)
-    heat = conv(u, "upconv4")[0, 0]
-    return act[0].numpy(), heat.numpy()
+from tests import policy_ref64
 
 
 def scene(seed):
@@ -70,7 +41,8 @@ def test_oracle_matches_torch():
         w, lay = pyoracle.policy_init(seed, trained_like=trained)
         sm, lm, vec8 = scene(seed)
         act, heat, ia, ip = pyoracle.policy_forward(sm, lm, vec8, w, legacy_bilinear=legacy)
-        tact, theat = torch_forward(sm, lm, vec8, w, lay, legacy)
+        tact, theat = policy_ref64.forward(sm, lm, vec8[None], w, dtype=torch.float32, legacy_bilinear=legacy)
+        tact, theat = tact[0], theat[0]
         np.testing.assert_allclose(act, tact, rtol=0, atol=2e-5 * max(1.0, float(np.abs(tact).max())))
         np.testing.assert_allclose(heat, theat, rtol=0, atol=2e-5 * float(np.abs(theat).max()))
         assert ia == int(np.argmax(act))

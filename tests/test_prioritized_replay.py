@@ -7,6 +7,7 @@ import pytest
 from scipy import stats
 
 from tests import per_oracle
+from tests.replay_cases import gather_rows as _gather_rows, set_masses as _set_masses, stale_rows as _skip, varied_masks as _varied_masks
 
 PER_SYMBOLS = ["ofx_replay_prioritize", "ofx_replay_sample_prioritized", "ofx_replay_window_weights",
                "ofx_replay_update_priorities", "ofx_replay_priorities_host", "ofx_dqn_fit_weighted"]
@@ -15,7 +16,7 @@ PER_SYMBOLS = ["ofx_replay_prioritize", "ofx_replay_sample_prioritized", "ofx_re
 # ------------------------------------------------------------------------------------------------------ CPU
 def test_per_symbols_exported_declared_and_bound():
     from ofighters_amd import _native as nat
-    from tests.test_abi import header_symbols
+    from tests.abi_header import header_symbols
     L = C.CDLL(nat.LIB_PATH)
     declared = header_symbols()
     for s in PER_SYMBOLS:
@@ -102,73 +103,6 @@ def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_bas
         b.step(actions_ptr=b._actions.ptr)
     b.sync()
     return b
-
-
-def _varied_masks(NG, M):
-    """arena 0 never captures (0 rows), arena 1 captures at ticks 0-1 (1 row), arena 2 with one ship (11 rows at 12
-    ticks), arena 3 one ship at ticks 0-4 (4 rows), the others every ship."""
-    def masks(t):
-        mk = np.ones((NG, M), np.uint8)
-        mk[0] = 0
-        mk[1] = 0
-        mk[1, 0] = t < 2
-        mk[2] = 0
-        mk[2, 0] = 1
-        mk[3] = 0
-        mk[3, 0] = t < 5
-        return mk
-    return masks
-
-
-def _gather_rows(b, slot, n_s, batch, first, max_rows):
-    """gather_valid without the maps -> (rows DeviceBuffer, n_rows)."""
-    from ofighters_amd import DeviceBuffer, _native as nat
-    rows = DeviceBuffer(max(1, max_rows) * b.TRANSITION_DTYPE.itemsize)
-    n = C.c_int32()
-    nat.check(nat.lib().ofx_replay_gather_valid(b.handle, slot.ptr, n_s.ptr, int(batch), int(first), int(max_rows), rows.ptr,
-                                                 None, None, C.byref(n)))
-    return rows, n.value
-
-
-def _all_rows_window(b):
-    """slot / n_sampled naming every row of every arena (oldest first), and those rows gathered."""
-    from ofighters_amd import DeviceBuffer
-    cnt, _ = b.replay_count()
-    Cap = b.replay_capacity
-    slot = np.full((b.N, Cap), -1, np.int32)
-    for a in range(b.N):
-        slot[a, :cnt[a]] = np.arange(cnt[a])
-    slot_d, n_d = DeviceBuffer(slot.nbytes).upload(slot), DeviceBuffer(4 * b.N).upload(cnt.astype(np.int32))
-    total = int(cnt.sum())
-    rows, got = _gather_rows(b, slot_d, n_d, Cap, 0, total)
-    assert got == total
-    return slot_d, n_d, Cap, rows, total, cnt
-
-
-def _set_masses(b, td_fn):
-    """Hand-set masses: one write-back over every row with td = td_fn(rows) [n][2]."""
-    from ofighters_amd import DeviceBuffer
-    slot_d, n_d, Cap, rows, total, cnt = _all_rows_window(b)
-    b.sync()
-    r = rows.download(b.TRANSITION_DTYPE, (total,))
-    td = np.ascontiguousarray(td_fn(r), np.float32)
-    td_d = DeviceBuffer(td.nbytes).upload(td)
-    b.replay_update_priorities(slot_d, n_d, Cap, 0, total, rows.ptr, td_d.ptr)
-    b.sync()
-    return r, td
-
-
-def _skip(b, a):
-    """How many of the arena's oldest rows have lost their `state` frame (not eligible)."""
-    from ofighters_amd import OfxError
-    rows = b.replay_rows(a)
-    for k, r in enumerate(rows):
-        try:
-            b.replay_frame(a, int(r["tick_prev"]))
-            return k
-        except OfxError:
-            pass
-    return len(rows)
 
 
 def _device_sample(b, seed, draw, batch, beta):
@@ -368,8 +302,8 @@ def _fit_inputs(n):
 def test_weighted_fit_with_unit_weights_is_dqn_fit(form):
     from ofighters_amd import DeviceBuffer, _native as nat
     from oracle import pyoracle
-    from tests.test_train import _collect_minibatch
-    b, n, rows_d, bp_d, _ = _collect_minibatch(4)
+    from tests.fit_cases import collect_minibatch
+    b, n, rows_d, bp_d, _ = collect_minibatch(4)
     b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
     w, _ = pyoracle.policy_init(5, trained_like=True)
     y, y2 = _fit_inputs(n)
@@ -399,9 +333,9 @@ def test_weighted_fit_with_unit_weights_is_dqn_fit(form):
 def test_weighted_fit_vs_torch_autograd(form):
     from ofighters_amd import DeviceBuffer, _native as nat
     from oracle import pyoracle
-    from tests.per_torch_ref import weighted_reference
-    from tests.test_train import _collect_minibatch, _compare_gradients
-    b, n, rows_d, bp_d, _ = _collect_minibatch(1)           # 4 rows
+    from tests.fit_cases import collect_minibatch, compare_gradients
+    from tests.fit_torch_ref import fit_reference
+    b, n, rows_d, bp_d, _ = collect_minibatch(1)           # 4 rows
     assert n == 4
     b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
     w, shapes = pyoracle.policy_init(9, trained_like=True)
@@ -419,11 +353,11 @@ def test_weighted_fit_vs_torch_autograd(form):
     rows = rows_d.download(b.TRANSITION_DTYPE, (n,))
     bits = bp_d.download(np.uint32, (n, 2, 5000))
     x0 = np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(n, 2, 400, 400).astype(np.float64)
-    rl1, rl2, rg, e1, e2 = weighted_reference(w.astype(np.float64), shapes, x0, rows["head_prev"],
-                                              rows["iaction"].astype(np.int64), rows["px"].astype(np.int64),
-                                              rows["py"].astype(np.int64), y, y2, rw)
+    ref = fit_reference(w.astype(np.float64), shapes, x0, rows["head_prev"], rows["iaction"].astype(np.int64),
+                        rows["px"].astype(np.int64), rows["py"].astype(np.int64), y, y2, row_w=rw)
+    rl1, rl2, rg, (e1, e2) = ref["l1"], ref["l2"], ref["g"], ref["e"].T
     assert abs(l1 - rl1) <= 1e-4 * max(1.0, abs(rl1)) and abs(l2 - rl2) <= 1e-4 * max(1e-9, abs(rl2)) + 1e-12
-    _compare_gradients(shapes, rg, g)
+    compare_gradients(shapes, rg, g)
     np.testing.assert_allclose(td[:, 0], e1, rtol=0, atol=1e-4 * max(1.0, np.abs(e1).max()))
     np.testing.assert_allclose(td[:, 1], e2, rtol=0, atol=1e-4 * max(1.0, np.abs(e2).max()))
     b.close()
@@ -434,15 +368,15 @@ def test_weighted_lean_fit_equals_plain_fit_at_128_rows():
     """the bounds of test_lean_fit_equals_plain_fit_large_batches (its checker, reused) with random row weights in the
     textbook fit"""
     from ofighters_amd import DeviceBuffer
-    from tests.test_train import _check_lean_equals_plain, _collect_minibatch
-    b, n, rows_d, bp_d, bn_d = _collect_minibatch(32)
+    from tests.fit_cases import check_lean_equals_plain, collect_minibatch
+    b, n, rows_d, bp_d, bn_d = collect_minibatch(32)
     assert n == 128
     rw = DeviceBuffer(4 * n).upload(np.random.RandomState(6).uniform(0.05, 1.0, n).astype(np.float32))
     plain_fit = b.dqn_fit
     b.dqn_fit = lambda *a, grad_buf=None: b.dqn_fit_weighted(*a[:10], row_weight_ptr=rw.ptr,
                                                              grad_buf=grad_buf if grad_buf is not None else a[10])
     try:
-        _check_lean_equals_plain(b, n, rows_d, bp_d, bn_d)
+        check_lean_equals_plain(b, n, rows_d, bp_d, bn_d)
     finally:
         b.dqn_fit = plain_fit
     b.close()

@@ -6,91 +6,10 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
+from tests.fit_cases import batch_statistics_f64, check_lean_equals_plain, collect_minibatch, compare_gradients, fit_once
+from tests.fit_torch_ref import fit_reference
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch_reference(w, shapes, x0, vec8, iaction, px, py, y_act, y_ptr, legacy=False, dense=None, dtype=None):
-    """dense = (t1 [n][2], t2 [n][400][400]): whole target tensors (ofx_dqn_fit_reference) instead of one error per head.
-    dtype: torch.float64 (the checker) or torch.float32 (how far plain fp32 autograd lands from it)."""
-    import torch
-    import torch.nn.functional as F
-    from tests.policy_ref64 import upsample2
-    torch.set_num_threads(8)
-    f64 = torch.float64
-    dt = dtype or f64
-    P = {}
-    for name, (o, shp) in shapes.items():
-        P[name] = torch.tensor(w[o:o + int(np.prod(shp))].reshape(shp), dtype=dt, requires_grad=True)
-    n = x0.shape[0]
-    stats = {}
-
-    def block(x, name, up=False):
-        if up:
-            x = upsample2(x, legacy)
-        k = P[name + ".kernel"].permute(3, 2, 0, 1)           # HWIO -> OIHW
-        z = F.conv2d(x, k, P[name + ".bias"], padding=1)
-        stats[name] = (z.mean(dim=(0, 2, 3)).detach().cpu(), z.var(dim=(0, 2, 3), unbiased=False).detach().cpu())
-        return torch.relu(F.batch_norm(z, None, None, P[name + ".gamma"], P[name + ".beta"], training=True, eps=1e-3))
-
-    x = torch.tensor(x0, dtype=dt)
-    for i in (1, 2, 3, 4):
-        x = F.max_pool2d(block(x, "conv%d" % i), 2)
-    flat = x.permute(0, 2, 3, 1).reshape(n, 5000)
-    f = torch.cat([torch.tensor(vec8, dtype=dt), flat], dim=1)
-    d1 = torch.relu(f @ P["dense1.kernel"] + P["dense1.bias"])
-    d2 = torch.relu(d1 @ P["dense2.kernel"] + P["dense2.bias"])
-    o1 = d2 @ P["output1.kernel"] + P["output1.bias"]
-    u = torch.relu(d1 @ P["updense1.kernel"] + P["updense1.bias"]).reshape(n, 1, 25, 25)
-    for j in (1, 2, 3):
-        u = block(u, "upconv%d" % j, up=True)
-    u = upsample2(u, legacy)
-    o2 = F.conv2d(u, P["upconv4.kernel"].permute(3, 2, 0, 1), P["upconv4.bias"], padding=1)
-    idx = torch.arange(n)
-    if dense is not None:
-        e1 = o1 - torch.tensor(dense[0], dtype=dt)
-        e2 = o2[:, 0] - torch.tensor(dense[1], dtype=dt)
-    else:
-        e1 = o1[idx, torch.tensor(iaction)] - torch.tensor(y_act, dtype=dt)
-        e2 = o2[idx, 0, torch.tensor(py), torch.tensor(px)] - torch.tensor(y_ptr, dtype=dt)
-    l1, l2 = (e1 ** 2).sum() / (2 * n), (e2 ** 2).sum() / (160000 * n)
-    (l1 + l2).backward()
-    g = np.zeros_like(w, dtype=np.float64)
-    for name, (o, shp) in shapes.items():
-        if P[name].grad is not None:
-            g[o:o + int(np.prod(shp))] = P[name].grad.detach().cpu().numpy().ravel()
-    return float(l1.detach()), float(l2.detach()), g, stats
-
-
-def _compare_gradients(shapes, rg, g, loose=()):
-    """gradients tensor by tensor: fp32 kernels vs the float64 checker
-    (the bias of a convolution that feeds a BatchNorm has an exactly zero gradient: only rounding noise is left, so
-    the absolute part of the tolerance is tied to the layer's kernel gradient).
-    `loose` layers: a ReLU whose input is within fp32 rounding of zero is gated one way in fp32 and the other way in
-    float64; the gradient of that ONE activation then differs by its full value, which shows as a localised error (a few
-    cells of u0 and their neighbours through the up-sampling) in the gradients that are short sums.  For those tensors
-    the check is on the structure of the error - rms, share of outliers, a cap on the worst element - instead of max."""
-    report = []
-    for name, (o, shp) in shapes.items():
-        c = int(np.prod(shp))
-        layer, kind = name.split(".")
-        if kind in ("mean", "var"):
-            continue
-        ref, got = rg[o:o + c], g[o:o + c]
-        ko, kshp = shapes[layer + ".kernel"]
-        kscale = float(np.abs(rg[ko:ko + int(np.prod(kshp))]).max())
-        scale, err = float(np.abs(ref).max()), float(np.abs(got - ref).max())
-        if layer in loose:
-            tol = 1e-4 * scale + 5e-5 * kscale
-            rms = float(np.sqrt(((got - ref) ** 2).mean()))
-            outliers = float((np.abs(got - ref) > tol).mean())
-            ok = rms <= tol and outliers <= 0.03 and err <= 3e-3 * scale
-            report.append((name, scale, err, ok))
-            print("%-18s rms %.2e of scale, %.2f %% of the elements above 1e-4, worst %.2e" % (name, rms / scale, 100 * outliers, err / scale))
-        else:
-            report.append((name, scale, err, err <= 1e-4 * scale + 5e-5 * kscale))
-    print("\n".join("%-18s scale %.3e  err %.3e  %s" % r for r in report))
-    assert all(r[3] for r in report), [r for r in report if not r[3]]
 
 
 @pytest.mark.parametrize("form", ["lean", "plain"])
@@ -136,11 +55,11 @@ def test_dqn_fit_vs_torch_autograd(legacy, form):
 
     bits = bp_d.download(np.uint32, (n, 2, 5000))
     x0 = np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(n, 2, 400, 400).astype(np.float64)
-    rl1, rl2, rg, stats = _torch_reference(w.astype(np.float64), shapes, x0, rows["head_prev"], rows["iaction"].astype(np.int64),
-                                           rows["px"].astype(np.int64), rows["py"].astype(np.int64), y_act, y_ptr,
-                                           legacy=legacy)
+    ref = fit_reference(w.astype(np.float64), shapes, x0, rows["head_prev"], rows["iaction"].astype(np.int64),
+                        rows["px"].astype(np.int64), rows["py"].astype(np.int64), y_act, y_ptr, legacy=legacy)
+    rl1, rl2, rg, stats = ref["l1"], ref["l2"], ref["g"], ref["stats"]
     assert abs(l1 - rl1) <= 1e-4 * max(1.0, abs(rl1)) and abs(l2 - rl2) <= 1e-4 * max(1e-9, abs(rl2)) + 1e-12
-    _compare_gradients(shapes, rg, g)
+    compare_gradients(shapes, rg, g)
     # Adam step 1 from the device's own gradient, and the moving statistics
     lr_t = lr * np.sqrt(1 - 0.999) / (1 - 0.9)
     for name, (o, shp) in shapes.items():
@@ -148,7 +67,7 @@ def test_dqn_fit_vs_torch_autograd(legacy, form):
         layer, kind = name.split(".")
         if kind in ("mean", "var"):
             bm, bv = stats[layer]
-            want = 0.99 * w[o:o + c] + 0.01 * (bm if kind == "mean" else bv).numpy()
+            want = 0.99 * w[o:o + c] + 0.01 * (bm if kind == "mean" else bv)
             np.testing.assert_allclose(w_new[o:o + c], want, rtol=1e-4, atol=1e-6)
         else:
             gi = g[o:o + c]
@@ -207,14 +126,14 @@ def test_dqn_fit_reference_quirks(form):
         live = 0.0 if rows["done"][s] else 1.0
         t1[s, int(rows["iaction"][s] != 0)] = rows["reward"][s] + gamma * a_next[0].max() * live
         t2[s, rows["px"][s], rows["py"][s]] = rows["reward"][s] + gamma * h_next[0].max() * live     # [x][y]
-    rl1, rl2, rg, _ = _torch_reference(w.astype(np.float64), shapes, xn.astype(np.float64), rows["head_next"], None, None,
-                                       None, None, None, dense=(t1, t2))
+    ref = fit_reference(w.astype(np.float64), shapes, xn.astype(np.float64), rows["head_next"], dense=(t1, t2))
+    rl1, rl2, rg = ref["l1"], ref["l2"], ref["g"]
     assert abs(l1 - rl1) <= 2e-4 * max(1.0, abs(rl1)) and abs(l2 - rl2) <= 2e-4 * max(1e-9, abs(rl2)) + 1e-12, (l1, rl1, l2, rl2)
     # Every tensor inside 1e-4 of its scale except updense1 (1.25e-3).  tools/fit_precision.py (r03, on the chip)
     # attributes it: the error sits in 7 of the 625 cells of u0 (one cluster; rms 6e-5 of the scale) - one ReLU gate
     # that fp32 and float64 decide differently - not in cancellation noise as r02 guessed: torch's own fp32 autograd on
     # the CPU lands at 1.7e-6 on this minibatch (its rounding leaves that activation on the float64 side).
-    _compare_gradients(shapes, rg, g, loose=("updense1",))
+    compare_gradients(shapes, rg, g, loose=("updense1",))
     b.close()
 
 
@@ -414,7 +333,7 @@ def test_adam_recurrence_after_the_first_step(form):
     w: the allowance of the step-1 check of test_dqn_fit_vs_torch_autograd.  The moving BatchNorm statistics are not
     Adam's (excluded, as there)."""
     from ofighters_amd import DeviceBuffer, _native as nat
-    b, n, rows_d, bp_d, bn_d = _collect_minibatch(3)
+    b, n, rows_d, bp_d, bn_d = collect_minibatch(3)
     b.set_option(nat.OPT_FIT_PLAIN, int(form == "plain"))
     w0, shapes = pyoracle.policy_init(9, trained_like=True)
     rs = np.random.RandomState(5)
@@ -460,83 +379,6 @@ def test_adam_recurrence_after_the_first_step(form):
 # the weight-gradient kernels), the reductions go through their two-level ordered combines and f_bits_corr through its
 # per-block partial rows - paths the 4- and 24-row comparisons above reach with one tile per block only.
 
-def _collect_minibatch(N, M=4, batch=4, seed=0x0F160077, ticks=10):
-    from ofighters_amd import ArenaBatch, DeviceBuffer
-    b = ArenaBatch(N, M)
-    b.replay_create(16, 0)
-    b.spawn_random(seed)
-    mask = np.zeros((N, M), np.uint8)
-    mask[:, [0, 3]] = 1
-    mask_d = DeviceBuffer(mask.nbytes).upload(mask)
-    ia_d, ip_d = DeviceBuffer(4 * N * M), DeviceBuffer(8 * N * M)
-    for t in range(ticks):
-        b.bot_actions(["random"] * M, seed, tick=t)
-        b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
-        b.policy_actions(out_ptr=b._actions.ptr, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
-        b.replay_capture(t, mask_d.ptr, ia_d.ptr, ip_d.ptr)
-        b.step(actions_ptr=b._actions.ptr)
-    slot, _ = b.replay_sample(7, 0, batch)
-    rows_d, bp_d, bn_d = b.replay_gather_device(slot, batch)
-    b.sync()                                                # the gather runs on the handle's stream; raw copies do not wait for it
-    n = N * batch
-    assert (rows_d.download(b.TRANSITION_DTYPE, (n,))["ship"] >= 0).all()
-    return b, n, rows_d, bp_d, bn_d
-
-
-def _fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs):
-    w_d, m_d, v_d, g_d = bufs
-    zeros = np.zeros_like(w)
-    w_d.upload(w); m_d.upload(zeros); v_d.upload(zeros)
-    if kind == "textbook":
-        l = b.dqn_fit(w_d, m_d, v_d, 1, 1e-4, n, rows_d.ptr, bp_d.ptr, y.ptr, y2.ptr, g_d)
-    else:
-        l = b.dqn_fit_reference(w_d, m_d, v_d, 1, 1e-4, n, rows_d.ptr, bp_d.ptr, bn_d.ptr, 0.9, g_d)
-    return l, g_d.download(np.float32, w.shape), w_d.download(np.float32, w.shape)
-
-
-def _check_lean_equals_plain(b, n, rows_d, bp_d, bn_d, loose=frozenset(), loose_both=frozenset()):
-    """Both forms of the fit on one minibatch, textbook and reference targets: the per-tensor bounds of
-    test_lean_fit_equals_plain_fit, equal moved statistics, and two lean runs give the same bits."""
-    from ofighters_amd import DeviceBuffer, _native as nat
-    w, shapes = pyoracle.policy_init(5, trained_like=True)
-    rs = np.random.RandomState(3)
-    y = DeviceBuffer(4 * n).upload(rs.uniform(-1, 2, n).astype(np.float32))
-    y2 = DeviceBuffer(4 * n).upload(rs.uniform(-1, 2, n).astype(np.float32))
-    bufs = tuple(DeviceBuffer(w.nbytes) for _ in range(4))
-    for kind in ("textbook", "reference"):
-        b.set_option(nat.OPT_FIT_PLAIN, 0)
-        la, ga, wa = _fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
-        la2, ga2, wa2 = _fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
-        assert la == la2 and np.array_equal(ga, ga2) and np.array_equal(wa, wa2), "lean fit is not bit-reproducible at %d rows" % n
-        b.set_option(nat.OPT_FIT_PLAIN, 1)
-        lb, gb, wb = _fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
-        ga, gb = ga.astype(np.float64), gb.astype(np.float64)
-        assert np.isfinite(ga).all() and np.abs(ga).max() > 0
-        assert abs(la[0] - lb[0]) <= 1e-5 * max(1.0, abs(lb[0])) and abs(la[1] - lb[1]) <= 1e-5 * abs(lb[1]) + 1e-12, (kind, la, lb)
-        bad = []
-        for name, (o, shp) in shapes.items():
-            c = int(np.prod(shp))
-            layer, what = name.split(".")
-            if what in ("mean", "var"):
-                np.testing.assert_allclose(wa[o:o + c], wb[o:o + c], rtol=1e-5, atol=1e-7, err_msg="%s %s" % (kind, name))
-                continue
-            ko, kshp = shapes[layer + ".kernel"]
-            kscale = float(np.abs(gb[ko:ko + int(np.prod(kshp))]).max())
-            scale, err = float(np.abs(gb[o:o + c]).max()), float(np.abs(ga[o:o + c] - gb[o:o + c]).max())
-            print("%-10s %-18s scale %.3e  err/scale %.2e" % (kind, name, scale, err / max(scale, 1e-30)))
-            if what == "bias" and layer + ".gamma" in shapes:
-                # the bias of a convolution in front of a BatchNorm has an EXACTLY zero gradient: what either form delivers
-                # is the rounding noise of its sums (it grows with the batch) - bounded against the layer's kernel
-                # gradient, not compared element by element
-                lean_scale = float(np.abs(ga[o:o + c]).max())
-                assert max(scale, lean_scale) <= 2e-4 * kscale, (kind, name, scale, lean_scale, kscale)
-                if layer == "conv1":        # the first layer's is written as the exact zero (f_first_bwd_finish)
-                    assert lean_scale == 0.0, (kind, name)
-            elif err > (2e-3 if ((name in loose and kind == "textbook") or name in loose_both) else 1e-4) * scale + 5e-5 * kscale:
-                bad.append((name, scale, err))
-        assert not bad, (kind, n, bad)
-
-
 @pytest.mark.parametrize("rows,skip", [(128, 0), (1024, 4), (1024, 0)])
 def test_lean_fit_equals_plain_fit_large_batches(rows, skip):
     """lean == plain at 128 rows (every persistent kernel past its first tile: f_conv_fwd at 200x200 loops from 52 rows,
@@ -559,7 +401,7 @@ def test_lean_fit_equals_plain_fit_large_batches(rows, skip):
     decision inside the trunk (a ReLU gate, a max-pool arg-max) that the plain form takes as float64 does and the other two
     do not, and element-wise fp32 rounding that does not average out: no margin and no forced evaluation shows which."""
     from ofighters_amd import DeviceBuffer, _native as nat
-    b, n_all, rows_all, bp_all, bn_all = _collect_minibatch((rows + skip + 3) // 4)
+    b, n_all, rows_all, bp_all, bn_all = collect_minibatch((rows + skip + 3) // 4)
     n = rows
     assert n_all >= n + skip
 
@@ -567,7 +409,7 @@ def test_lean_fit_equals_plain_fit_large_batches(rows, skip):
         def __init__(self, buf, stride): self.ptr = buf.ptr + skip * stride
     rows_d, bp_d, bn_d = _Off(rows_all, b.TRANSITION_DTYPE.itemsize), _Off(bp_all, 40000), _Off(bn_all, 40000)
     loose = {"conv1.kernel", "conv1.gamma", "conv1.beta", "conv2.kernel", "conv2.beta"} if (rows, skip) == (1024, 0) else set()
-    _check_lean_equals_plain(b, n, rows_d, bp_d, bn_d, loose)
+    check_lean_equals_plain(b, n, rows_d, bp_d, bn_d, loose)
     b.close()
 
 
@@ -577,7 +419,7 @@ def test_lean_fit_on_maps_without_empty_windows(case):
     share from border sums of the second layer's dz.  Arena observations leave ~97 % of the windows empty; here NONE is
     (30 % of the cells set; 60 % and 50 %), one half of the plane is and the other is not (the border
     terms with both kinds of window on the frame), or only the plane's frame is set - same bounds against the plain form."""
-    b, n, rows_d, bp_d, bn_d = _collect_minibatch(3)
+    b, n, rows_d, bp_d, bn_d = collect_minibatch(3)
     rs = np.random.RandomState(11)
     for buf in (bp_d, bn_d):
         x = np.zeros((n, 2, 400, 400), bool)
@@ -597,27 +439,8 @@ def test_lean_fit_on_maps_without_empty_windows(case):
         buf.upload(np.packbits(x.reshape(n, 2, 160000), axis=-1, bitorder="little").view(np.uint32))
     # updense1: one ReLU gate of u0 that the two forms may decide differently on synthetic maps (the allowance of the float64
     # comparisons above, tools/fit_precision.py) - this test is about the trunk's first layers
-    _check_lean_equals_plain(b, n, rows_d, bp_d, bn_d, loose_both={"updense1.kernel", "updense1.bias"})
+    check_lean_equals_plain(b, n, rows_d, bp_d, bn_d, loose_both={"updense1.kernel", "updense1.bias"})
     b.close()
-
-
-def _batch_statistics_f64(tmp_path, w, shapes, bits, vec8):
-    """tests/bn_stats64.py in a process of its own: torch's HIP runtime and libofx's do not initialise side by side in
-    one process in that order (torch reports no GPU once libofx has opened the device), and the checker shares nothing
-    with the library anyway."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    names = list(shapes)
-    fin, fout = str(tmp_path / "bn_in.npz"), str(tmp_path / "bn_out.npz")
-    np.savez(fin, w=w, bits=bits, vec8=vec8, names=np.array(names), offs=np.array([shapes[k][0] for k in names]),
-             shp=np.array([list(shapes[k][1]) + [0] * (4 - len(shapes[k][1])) for k in names]))
-    p = subprocess.run([sys.executable, os.path.join(root, "tests", "bn_stats64.py"), fin, fout], capture_output=True,
-                       text=True, timeout=600)
-    assert p.returncode == 0, p.stderr[-3000:]
-    d = np.load(fout)
-    return {k[:-5]: (d[k], d[k[:-5] + ".var"]) for k in d.files if k.endswith(".mean")}
 
 
 def test_lean_fit_at_4096_rows(tmp_path):
@@ -626,7 +449,7 @@ def test_lean_fit_at_4096_rows(tmp_path):
     autocorrelation of the 1-bit maps) up to upconv3 (the last normalised layer, behind all others) - equal
     0.99 * old + 0.01 * (batch mean | biased batch variance) of a float64 evaluation of the same minibatch."""
     from ofighters_amd import DeviceBuffer, _native as nat
-    b, n, rows_d, bp_d, bn_d = _collect_minibatch(1024)
+    b, n, rows_d, bp_d, bn_d = collect_minibatch(1024)
     assert n == 4096
     w, shapes = pyoracle.policy_init(5, trained_like=True)
     rs = np.random.RandomState(3)
@@ -635,14 +458,14 @@ def test_lean_fit_at_4096_rows(tmp_path):
     bufs = tuple(DeviceBuffer(w.nbytes) for _ in range(4))
     b.set_option(nat.OPT_FIT_PLAIN, 0)
     for kind in ("textbook", "reference"):
-        la, ga, wa = _fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
-        la2, ga2, wa2 = _fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
+        la, ga, wa = fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
+        la2, ga2, wa2 = fit_once(b, kind, w, n, rows_d, bp_d, bn_d, y, y2, bufs)
         assert la == la2 and np.array_equal(ga, ga2) and np.array_equal(wa, wa2), kind
         assert np.isfinite(ga).all() and np.isfinite(wa).all() and np.isfinite(la).all() and np.abs(ga).max() > 0
         rows = rows_d.download(b.TRANSITION_DTYPE, (n,))
         bits = (bn_d if kind == "reference" else bp_d).download(np.uint32, (n, 2, 5000))     # the reference fits on next_state
         vec8 = rows["head_next" if kind == "reference" else "head_prev"]
-        stats = _batch_statistics_f64(tmp_path, w.astype(np.float64), shapes, bits, vec8)
+        stats = batch_statistics_f64(tmp_path, w.astype(np.float64), shapes, bits, vec8)
         for layer, (bm, bv) in stats.items():
             for what, batch_stat in (("mean", bm), ("var", bv)):
                 o, shp = shapes[layer + "." + what]

@@ -9,10 +9,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ofighters_amd import DeviceBuffer, _native as nat   # noqa: E402
 from oracle import pyoracle                              # noqa: E402
-from tests.test_train import _collect_minibatch          # noqa: E402
+from tests.fit_cases import collect_minibatch          # noqa: E402
 
 rows_n = int(([a for a in sys.argv[1:] if not a.startswith('--')] or [1024])[0])
-b, n, rows_d, bp_d, bn_d = _collect_minibatch(rows_n // 4)
+b, n, rows_d, bp_d, bn_d = collect_minibatch(rows_n // 4)
 w, shapes = pyoracle.policy_init(5, trained_like=True)
 rs = np.random.RandomState(3)
 y = DeviceBuffer(4 * n).upload(rs.uniform(-1, 2, n).astype(np.float32))

@@ -11,20 +11,18 @@ sys.path.insert(0, ROOT)
 
 if len(sys.argv) > 1 and sys.argv[1] == "--torch-gpu":
     import torch                                   # torch's HIP runtime first (its own copy)
-    from tests.test_train import _torch_reference
+    from tests.fit_torch_ref import fit_reference
     z = np.load(sys.argv[2], allow_pickle=False)
     shapes = {k: (int(o), tuple(int(v) for v in s.split("x") if v)) for k, o, s in zip(z["names"], z["offs"], z["shps"])}
     # run the reference on the GPU by making new tensors land there
     torch.set_default_device("cuda")
-    l1, l2, g, _ = _torch_reference(z["w"], shapes, z["xn"], z["head_next"], None, None, None, None, None,
-                                    dense=(z["t1"], z["t2"]), dtype=torch.float32)
-    np.save(sys.argv[3], g)
+    np.save(sys.argv[3], fit_reference(z["w"], shapes, z["xn"], z["head_next"], dense=(z["t1"], z["t2"]), dtype=torch.float32)["g"])
     sys.exit(0)
 
 from ofighters_amd import ArenaBatch, DeviceBuffer
 from oracle import pyoracle
 from tests import policy_ref64 as R
-from tests.test_train import _torch_reference
+from tests.fit_torch_ref import fit_reference
 
 N, M, seed, batch, lr, gamma = 2, 4, 0x0F160001, 2, 1e-4, 0.9
 b = ArenaBatch(N, M)
@@ -64,9 +62,9 @@ for s in range(n):
     t2[s, rows["px"][s], rows["py"][s]] = rows["reward"][s] + gamma * h_next[0].max() * live
 b.close()
 import torch
-args = (w.astype(np.float64), shapes, xn.astype(np.float64), rows["head_next"], None, None, None, None, None)
-_, _, g64, _ = _torch_reference(*args, dense=(t1, t2))
-_, _, g32, _ = _torch_reference(*args, dense=(t1, t2), dtype=torch.float32)
+args = (w.astype(np.float64), shapes, xn.astype(np.float64), rows["head_next"])
+g64 = fit_reference(*args, dense=(t1, t2))["g"]
+g32 = fit_reference(*args, dense=(t1, t2), dtype=torch.float32)["g"]
 ggpu = None
 with tempfile.TemporaryDirectory() as d:
     names = list(shapes)
