@@ -460,6 +460,34 @@ int ofx_policy_epsilon_ladder_host(ofx_handle *h, double *dst_host);
  * with any explicit output withdraws that again (the handle's arrays would be partly stale).  Does not synchronise.   */
 int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t *ship_mask, double epsilon, uint64_t seed,
                    uint32_t tick, int32_t collecting, float *q_sa, float *p_sp, float *v_act, float *v_ptr);
+/* Opt-in Boltzmann exploration: ofx_policy_act with both heads SAMPLED from softmax(Q / T) instead of the epsilon-greedy
+ * choice (not in the reference).  Argument checks, pinning, the OFX_OPT_* switches, the handle-kept (iaction, ipointer),
+ * the four values and the NULL-output rule are ofx_policy_act's; tau_act and tau_ptr must be finite and >= 0
+ * (OFX_ERR_INVALID otherwise, nothing changes).  Does not synchronise.
+ *   temperature  per local arena a: T_act[a] = tau_act * (float)eps_a, T_ptr[a] = tau_ptr * (float)eps_a in float32, with
+ *                eps_a the float64 rate of ofx_policy_explore: `epsilon` without a ladder and at exponent 1 (bit for
+ *                bit), pow(epsilon, expo[a]) otherwise, 0 at exponent +inf (a greedy arena).  The epsilon schedule is
+ *                the annealing schedule.
+ *   collecting   != 0: the call IS ofx_policy_act(..., collecting = 1), bit for bit in actions and values.
+ *   noise        standard Gumbel from a Philox4x32-10 word r keyed by `seed`: w = (r + 0.5) / 2^32, E = -ln(1 - w),
+ *                g = -ln(E).  Pointer: pixel (x, y) of ship i of global arena G takes word [x & 3] of counter
+ *                (G, i * (W*H/4) + (y*W + x) / 4, tick, stream 6); action k takes word [k] of (G, i, tick, stream 7).
+ *                The noise is keyed by the pixel, so the choice is a function of (seed, arena, ship, tick, heat map).
+ *   pointer      the first maximum in C order of fmaf(T_ptr[a], g, heat) in float32, heat bit for bit what
+ *                ofx_policy_forward writes into a heat-map buffer; by the Gumbel-max identity an exact sample from
+ *                softmax(heat / T).  T_ptr[a] == 0 draws no noise: the greedy pointer, bit for bit.
+ *   action       1 iff fmaf(T_act[a], g1, act_values[1]) > fmaf(T_act[a], g0, act_values[0]) (a tie gives 0).
+ *   values       q_sa = act_values[iaction], v_act = max(act_values), v_ptr = the RAW heat map's maximum (the bits
+ *                ofx_policy_act returns), p_sp = the RAW heat value at the chosen pointer.
+ * The float32 form of g never rounds 1 - w (that would quantise g by 1e-2 around g = 12, the tail that wins among
+ * 160 000 pixels); ofx_policy_gumbel runs the kernels' own function on n device words (a diagnostic).  Largest
+ * |g - float64| over the edge words (0, 1, 2^32 - 1, 2^k, 2^k +- 1) and 2^20 Philox words on the MI355X:
+ * 9.3e-6, at words just above 2^30 (the tests allow twice that, tests/boltzmann_oracle.py GUMBEL_ABS_ERR; the contract's
+ * bound is 1e-4).                                                                                                       */
+int ofx_policy_act_boltzmann(ofx_handle *h, const float *weights, const uint8_t *ship_mask, double epsilon,
+                             float tau_act, float tau_ptr, uint64_t seed, uint32_t tick, int32_t collecting,
+                             float *q_sa, float *p_sp, float *v_act, float *v_ptr);
+int ofx_policy_gumbel(ofx_handle *h, const uint32_t *words_dev, int32_t n, float *g_dev);
 /* QlearnIA.play action packing (qlearnIA_V2.py:447-454): exactly one of
  * shoot/thrust set, pointer always set.  NULL iaction / ipointer = the handle's
  * results of the last ofx_policy_forward / ofx_policy_explore.               */

@@ -122,6 +122,9 @@ SIGNATURES = {
     "ofx_policy_epsilon_ladder": (_i, [_vp, _vp]),
     "ofx_policy_epsilon_ladder_host": (_i, [_vp, _vp]),
     "ofx_policy_act": (_i, [_vp, _vp, _vp, C.c_double, _u64, _u32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ofx_policy_act_boltzmann": (_i, [_vp, _vp, _vp, C.c_double, C.c_float, C.c_float, _u64, _u32, C.c_int32, _vp, _vp, _vp,
+                                      _vp]),
+    "ofx_policy_gumbel": (_i, [_vp, _vp, C.c_int32, _vp]),
     "ofx_policy_forward_obs": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_targets": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "ofx_dqn_fit": (_i, [_vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -139,6 +139,8 @@ def rollout_fingerprint(r):
         fp["action_repeat"] = int(r.action_repeat)
     if getattr(r, "auto_reset", False):
         fp["auto_reset"] = True
+    if getattr(r, "boltzmann", None) is not None:
+        fp["boltzmann"] = [float(r.boltzmann[0]), float(r.boltzmann[1])]
     return fp
 
 

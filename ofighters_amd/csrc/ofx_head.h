@@ -33,7 +33,44 @@ struct HeadParams2 {
   int event_base;               // >= 0: ofx_event_record(event_base / event_base + 1) around k_head_stream
   int ablate;                   // diagnostics (OFX_HEAD_HOOKS builds only)
   unsigned long long *dbg;      // diagnostics: [blocks][8 waves][6] s_memtime sums
+  // ---- Boltzmann sampling of the pointer (ofx_policy_act_boltzmann): k_head_stream_sample instead of k_head_stream
+  int sample;                   // != 0: the sampling kernel; `best`, `heat` and the probe are not used
+  int M, arena_base;            // ships per arena, first global arena of the handle: the noise is keyed by (global arena, ship)
+  unsigned nk0, nk1, ntick;     // Philox key (the seed's halves) and the tick of the noise
+  const float *t_ptr;           // [S] temperature of the ship's arena (0 = greedy: no noise is drawn)
+  unsigned long long *cand_key; // [S][8] per consumer wave (2 strips x 4): (ordered perturbed value << 32) | ~index, 0 = none
+  float *cand_raw;              // [S][8] the raw heat-map value at that candidate's pixel
+  unsigned *cand_max;           // [S][8] the wave's raw maximum as an ordered word (hd_ordered_f32)
 };
+
+#define OFX_STREAM_BOLTZMANN_PTR 6u
+#define OFX_STREAM_BOLTZMANN_ACT 7u
+
+#ifdef __HIPCC__
+// Standard Gumbel noise from one Philox word r, in float32: w = (r + 0.5) / 2^32, E = -ln(1 - w), g = -ln(E).
+// Rounding 1 - w to float32 would quantise g by about 1e-2 around g = 12, the tail that wins among 160 000 pixels, so
+// E never goes through a rounded 1 - w:
+//   r <  2^30 (w < 1/4)  E = 2 atanh(s), s = w / (2 - w), as an odd series up to s^9 (truncation below 3e-10 relative)
+//   otherwise            1 - w = (2 k + 1) / 2^33 with k = ~r, so E = ln 2 (33 - log2(2 k + 1)), E >= 0.287
+// and the two logs are the hardware's (v_log_f32, 1 ulp of the base-2 logarithm: below 4e-6 at |log2| <= 33).
+// Largest |g - float64| over the edge words and 2^20 Philox words, measured on the MI355X: 9.3e-6, at words just above
+// 2^30 where E is smallest on the second route (include/ofx.h; the contract's bound is 1e-4).
+// Every multiply-add is an explicit fmaf and no product feeds a sum: the function gives the same bits in every
+// translation unit, whatever its contraction setting (k_head_stream_sample, k_policy_boltz_finish, k_head_gumbel).
+__device__ __forceinline__ float hd_gumbel(unsigned r) {
+  const float w = fmaf((float)r, 0x1p-32f, 0x1p-33f);
+  const float s = w * __builtin_amdgcn_rcpf(2.f - w), s2 = s * s;
+  float q = fmaf(s2, 1.f / 9.f, 1.f / 7.f);
+  q = fmaf(s2, q, 1.f / 5.f);
+  q = fmaf(s2, q, 1.f / 3.f);
+  q = fmaf(s2, q, 1.f);
+  const float e_lo = 2.f * s * q;
+  const float m = fmaf((float)(~r), 2.f, 1.f);
+  const float e_hi = 0.693147180559945f * (33.f - __builtin_amdgcn_logf(m));
+  const float E = r < 0x40000000u ? e_lo : e_hi;
+  return -0.693147180559945f * __builtin_amdgcn_logf(E);
+}
+#endif
 
 // bytes of the three frame buffers for S samples
 size_t ofx_head_frame_bytes(size_t S, size_t *u2fr, size_t *vfr, size_t *c4);
@@ -41,3 +78,5 @@ size_t ofx_head_frame_bytes(size_t S, size_t *u2fr, size_t *vfr, size_t *c4);
 int ofx_head_compact(ofx_handle *h, int S, const uint8_t *mask, int32_t *live);
 // k_head_frames + k_head_stream on the handle's stream
 int ofx_launch_head(ofx_handle *h, const HeadParams2 &p);
+// g[i] = hd_gumbel(words[i]) on the handle's stream (ofx_policy_gumbel)
+int ofx_head_gumbel(ofx_handle *h, const uint32_t *words, int n, float *g);

@@ -27,6 +27,7 @@
 // only on the 1-pixel frame of each layer's output.  k_head_frames computes those thin lines exactly (frame lines of
 // uprelu2 / uprelu3, correction lines of the heat map) in a small pre-pass; k_head_stream overwrites the frame cells
 // of its rings with the exact values and starts the heat-map accumulators of frame pixels at bias - correction.
+#ifndef OFX_HEAD_STREAM_BODY
 #include "ofx_head.h"
 #include "ofx_lowp.h"
 #include "ofx_diag.h"
@@ -681,8 +682,136 @@ constexpr int HS_THREADS = 64 * (HS_NB + 4);
 // 3 MFMAs of K = 16 per channel half instead of 9 of K = 4): the operands - uprelu2 values read from the fp32 ring and
 // the phase weights - are rounded on the way into the matrix instruction, the sums stay fp32.  The 1x1, the stencil,
 // rings, schedule, frame lines (exact fp32) and stage A are the fp32 kernel's.
+//
+// SAMPLE (k_head_stream_sample, ofx_policy_act_boltzmann): the consumers' arg-max runs on heat + T g with standard
+// Gumbel noise g keyed by the PIXEL - one Philox call per four horizontally adjacent pixels, counter (global arena,
+// ship * 40000 + (y * 400 + x) / 4, tick, stream 6), word x & 3 - so its winner is an exact sample from softmax(heat / T)
+// (the Gumbel-max identity) and a function of (seed, arena, ship, tick, heat map) alone, whatever lane or pass meets
+// the pixel.  T is the ship's, uniform over the workgroup: T == 0 skips the noise with a scalar branch and the pass is
+// the arg-max's.  The raw values keep a running maximum of their own (v_ptr), the snapshot stays raw, and the winning
+// pass's noise is drawn again behind the loop to find the slot.  A wave writes its candidate (no atomics: the raw
+// value at the winner is only known once all 8 waves of the ship are compared, k_policy_boltz_finish).
+// The body is ONE text, the #else part at the end of this file, which the two kernels include (this file includes itself
+// with OFX_HEAD_STREAM_BODY defined) with `p`, EXTRA, LP and SAMPLE in scope: with SAMPLE = false the sampling parts
+// vanish and the default kernels compile to the code they had before the sampling form existed.  Not a function:
+// handed the argument struct through a force-inlined template, k_head_stream<false, 0> came out with another register
+// assignment and operand order, and its schedule is pinned (tests/test_head_isa.py).
+__device__ __forceinline__ void hs_noise8(unsigned G, unsigned c1, unsigned tick, unsigned k0, unsigned k1, float g[8]) {
+#pragma unroll
+  for (int a = 0; a < 2; a++) {   // the two heat-map rows of a pass: 100 Philox blocks further
+    uint32_t r[4];
+    ofx_philox4x32_10(G, c1 + 100u * a, tick, OFX_STREAM_BOLTZMANN_PTR, k0, k1, r);
+#pragma unroll
+    for (int j = 0; j < 4; j++) g[4 * a + j] = hd_gumbel(r[j]);
+  }
+}
+
 template <bool EXTRA, int LP>
 __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
+  constexpr bool SAMPLE = false;
+#define OFX_HEAD_STREAM_BODY
+#include "ofx_head.hip"
+#undef OFX_HEAD_STREAM_BODY
+}
+
+template <int LP>
+__global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream_sample(HeadParams2 p) {
+  constexpr bool EXTRA = false, SAMPLE = true;
+#define OFX_HEAD_STREAM_BODY
+#include "ofx_head.hip"
+#undef OFX_HEAD_STREAM_BODY
+}
+
+// diagnostic (ofx_policy_gumbel): the noise function of the sampling kernels on given words
+__global__ void k_head_gumbel(const uint32_t *words, int n, float *g) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) g[i] = hd_gumbel(words[i]);
+}
+
+int ofx_head_gumbel(ofx_handle *h, const uint32_t *words, int n, float *g) {
+  hipLaunchKernelGGL(k_head_gumbel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, words, n, g);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+int ofx_head_compact(ofx_handle *h, int S, const uint8_t *mask, int32_t *live) {
+  hipLaunchKernelGGL(k_head_compact, dim3(1), dim3(1024), 0, h->stream, S, mask, live);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+size_t ofx_head_frame_bytes(size_t S, size_t *u2fr, size_t *vfr, size_t *c4) {
+  *u2fr = 4 * S * 1600;
+  *vfr = 4 * S * 7200;
+  *c4 = 4 * (S + 1) * HC4_STRIDE;   // + the block of zeros
+  return *u2fr + *vfr + *c4;
+}
+
+int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
+  HeadParams2 p = p0;
+#if OFX_HEAD_HOOKS
+  { const char *e = getenv("OFX_HEAD_ABLATE"); p.ablate = e ? atoi(e) : 0; }  // diagnostics: 1 no stage C, 2 no stage A / B
+  static unsigned long long *dbg = nullptr;
+  static int dbg_calls = 0;
+  const unsigned dbg_blocks = (unsigned)(((p.S + 7) / 8) * 16);
+  p.dbg = nullptr;
+  if (getenv("OFX_HEAD_STAMPS")) {  // s_memtime stamps per wave, printed for the 20th forward
+    if (!dbg) (void)hipMalloc(&dbg, (size_t)dbg_blocks * 6 * (HS_NB + 4) * 8);
+    if (++dbg_calls == 20) p.dbg = dbg;
+  }
+#endif
+  if (p.mask) {
+    if (!p.live) { ofx_set_error("ofx_launch_head: a mask needs the live-list scratch"); return OFX_ERR_STATE; }
+    if (!p.live_ready) hipLaunchKernelGGL(k_head_compact, dim3(1), dim3(1024), 0, h->stream, p.S, p.mask, p.live);
+  } else {
+    p.live = nullptr;
+  }
+  if (p.frames_ref) hipLaunchKernelGGL(k_head_frames_ref, dim3((unsigned)p.S), dim3(HF_THREADS), 0, h->stream, p);
+  else hipLaunchKernelGGL(k_head_frames, dim3((unsigned)((p.S + 7) & ~7)), dim3(HG_THREADS), 0, h->stream, p);
+  OFX_HIP(hipGetLastError());
+  const unsigned blocks = (unsigned)(((p.S + 7) / 8) * 16);
+  int rc;
+  if (p.event_base >= 0 && (rc = ofx_event_record(h, p.event_base))) return rc;
+  const bool extra = p.heat || p.ptr_probe;
+#define HS_LAUNCH(E, L) hipLaunchKernelGGL((k_head_stream<E, L>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p)
+#define HS_LAUNCH_SAMPLE(L) hipLaunchKernelGGL((k_head_stream_sample<L>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p)
+  if (p.sample) {
+    if (extra || !p.t_ptr || !p.cand_key || !p.cand_raw || !p.cand_max || p.M < 1) {
+      ofx_set_error("ofx_launch_head: the sampling kernel takes no heat map or probe and needs its temperature and candidate arrays");
+      return OFX_ERR_STATE;
+    }
+    if (p.bf16 == 1) HS_LAUNCH_SAMPLE(1); else if (p.bf16 == 2) HS_LAUNCH_SAMPLE(2); else HS_LAUNCH_SAMPLE(0);
+  }
+  else if (p.bf16 == 1) { if (extra) HS_LAUNCH(true, 1); else HS_LAUNCH(false, 1); }
+  else if (p.bf16 == 2) { if (extra) HS_LAUNCH(true, 2); else HS_LAUNCH(false, 2); }
+  else { if (extra) HS_LAUNCH(true, 0); else HS_LAUNCH(false, 0); }
+#undef HS_LAUNCH
+#undef HS_LAUNCH_SAMPLE
+  OFX_HIP(hipGetLastError());
+  if (p.event_base >= 0 && (rc = ofx_event_record(h, p.event_base + 1))) return rc;
+#if OFX_HEAD_HOOKS
+  if (p.dbg) {
+    (void)hipStreamSynchronize(h->stream);
+    unsigned long long *hst = (unsigned long long *)malloc((size_t)blocks * 6 * (HS_NB + 4) * 8);
+    (void)hipMemcpy(hst, p.dbg, (size_t)blocks * 6 * (HS_NB + 4) * 8, hipMemcpyDeviceToHost);
+    double sum[2][6] = {{0}};
+    for (unsigned b = 0; b < blocks; b++)
+      for (int w = 0; w < HS_NB + 4; w++)
+        for (int i = 0; i < 6; i++) sum[w >= HS_NB][i] += (double)hst[((size_t)b * (HS_NB + 4) + w) * 6 + i] / (w >= HS_NB ? 4.0 : (double)HS_NB);
+    for (int r = 0; r < 2; r++) {
+      fprintf(stderr, "head stamps %s (cycles per wave and sub-step):", r ? "C" : "B");
+      for (int i = 0; i < 6; i++) fprintf(stderr, " %.0f", sum[r][i] / ((double)blocks * HS_NS));
+      fprintf(stderr, "\n");
+    }
+    free(hst);
+  }
+#endif
+  return OFX_OK;
+}
+
+#else  // OFX_HEAD_STREAM_BODY ------------------------------------------------------------------------------------------
+// The body of k_head_stream<EXTRA, LP> and k_head_stream_sample<LP>: in scope are `p` (the kernel's HeadParams2), EXTRA,
+// LP and SAMPLE.
   constexpr bool BF16 = LP != 0;  // reduced-precision operands (1 = bf16, 2 = fp16), fp32 sums
   __shared__ __align__(16) float vr[HS_NV * HS_PL3];
   __shared__ __align__(16) float u2r[4 * HS_PL2];
@@ -1065,6 +1194,16 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
     int tst = 0;
     f32x4 snap[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // the 8 values of the pass that holds the lane's maximum
     const char *const vb = reinterpret_cast<const char *>(vr);
+    // SAMPLE: the ship's temperature and noise counter (wave-uniform), the Philox block of the lane's first pixel of
+    // heat-map row 0, and the running maximum of the raw values
+    float T = 0.f, rmax = -INFINITY;
+    unsigned nG = 0u, nc1 = 0u;
+    if constexpr (SAMPLE) {
+      const int ar = s / p.M;
+      T = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.t_ptr[s])));
+      nG = (unsigned)(p.arena_base + ar);
+      nc1 = (unsigned)(s - ar * p.M) * (unsigned)(HD_PS * HD_PS / 4) + (unsigned)(50 * side + jx);
+    }
 
     {  // prologue: uprelu2 row pairs 0 and 1, one tile per consumer wave
       float av0[6];
@@ -1179,7 +1318,20 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
         // stays) the 8 values are kept; the position inside the pass is looked up once, behind the loop
         const float m01 = hd_max_raw(hd_max_raw(o[0][0], o[0][1]), hd_max_raw(o[0][2], o[0][3]));
         const float m23 = hd_max_raw(hd_max_raw(o[1][0], o[1][1]), hd_max_raw(o[1][2], o[1][3]));
-        const float m8 = hd_max_raw(m01, m23);
+        const float m8r = hd_max_raw(m01, m23);
+        float m8s = m8r;   // SAMPLE: the maximum of the perturbed values
+        if constexpr (SAMPLE) {
+          if (ok && m8r > rmax) rmax = m8r;
+          if (T != 0.f) {   // scalar branch
+            float g[8];
+            hs_noise8(nG, nc1 + 200u * (unsigned)R, p.ntick, p.nk0, p.nk1, g);
+            float pm = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 8; i++) pm = fmaxf(pm, fmaf(T, g[i], o[(i >> 1) & 1][2 * (i >> 2) + (i & 1)]));
+            m8s = pm;
+          }
+        }
+        const float m8 = SAMPLE ? m8s : m8r;
         const bool better = ok && m8 > tv;
         if (__builtin_amdgcn_ballot_w64(better) != 0) {   // wave-uniform: most passes improve no lane's maximum
           if (better) {
@@ -1207,87 +1359,57 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
     HS_STAMP_OUT();
 
     // ---- arg-max of the strip (first maximum in C order) ----
-    int slot = 0;  // first of the 8 values, in flat order (row a, pixel, column b), that equals the maximum
+    if constexpr (!SAMPLE) {
+      int slot = 0;  // first of the 8 values, in flat order (row a, pixel, column b), that equals the maximum
 #pragma unroll
-    for (int i = 7; i >= 0; i--) {
-      const int a = i >> 2, px = (i >> 1) & 1, b = i & 1;
-      if (snap[px][2 * a + b] == tv) slot = i;
-    }
-    const int Rb = 5 * tst - 8 + r_in;
-    const int y = 2 * Rb + (slot >> 2), x = 2 * x0 + (slot & 3);
-    unsigned long long key = 0ull;
-    if (tv > -INFINITY) key = ((unsigned long long)hd_ordered_f32(tv) << 32) | (unsigned long long)(~(unsigned)(y * HD_PS + x));
+      for (int i = 7; i >= 0; i--) {
+        const int a = i >> 2, px = (i >> 1) & 1, b = i & 1;
+        if (snap[px][2 * a + b] == tv) slot = i;
+      }
+      const int Rb = 5 * tst - 8 + r_in;
+      const int y = 2 * Rb + (slot >> 2), x = 2 * x0 + (slot & 3);
+      unsigned long long key = 0ull;
+      if (tv > -INFINITY) key = ((unsigned long long)hd_ordered_f32(tv) << 32) | (unsigned long long)(~(unsigned)(y * HD_PS + x));
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long other = __shfl_xor(key, o);
-      key = other > key ? other : key;
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o);
+        key = other > key ? other : key;
+      }
+      if (lane == 0 && key) atomicMax(&p.best[s], key);
+    } else {
+      // the winning pass's noise again, through the same function and the same fmaf: the same bits as in the pass
+      const int Rb = 5 * tst - 8 + r_in;
+      float g[8];
+      if (T != 0.f) hs_noise8(nG, nc1 + 200u * (unsigned)Rb, p.ntick, p.nk0, p.nk1, g);
+      int slot = 0;      // first of the 8 perturbed values, in flat order, that equals the maximum
+      float raw = 0.f;   // the raw value there
+#pragma unroll
+      for (int i = 7; i >= 0; i--) {
+        const float v = snap[(i >> 1) & 1][2 * (i >> 2) + (i & 1)];
+        if ((T != 0.f ? fmaf(T, g[i], v) : v) == tv) { slot = i; raw = v; }
+      }
+      const int y = 2 * Rb + (slot >> 2), x = 2 * x0 + (slot & 3);
+      unsigned long long key = 0ull;
+      if (tv > -INFINITY) key = ((unsigned long long)hd_ordered_f32(tv) << 32) | (unsigned long long)(~(unsigned)(y * HD_PS + x));
+      const unsigned long long mine = key;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o);
+        key = other > key ? other : key;
+      }
+      // the wave's candidate: its best key, the raw value of the lane that holds it (keys carry the pixel: one lane at
+      // most), and the wave's raw maximum.  Every wave writes its slot in every launch.
+      unsigned om = hd_ordered_f32(rmax);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) om = max(om, (unsigned)__shfl_xor((int)om, o));
+      const unsigned long long holds = __builtin_amdgcn_ballot_w64(key != 0ull && mine == key);
+      const float wraw = __shfl(raw, holds ? (int)__builtin_ctzll(holds) : 0);
+      if (lane == 0) {
+        const size_t c = (size_t)s * 8 + 4 * side + cw;
+        p.cand_key[c] = key;
+        p.cand_raw[c] = wraw;
+        p.cand_max[c] = om;
+      }
     }
-    if (lane == 0 && key) atomicMax(&p.best[s], key);
   }
-}
-
-int ofx_head_compact(ofx_handle *h, int S, const uint8_t *mask, int32_t *live) {
-  hipLaunchKernelGGL(k_head_compact, dim3(1), dim3(1024), 0, h->stream, S, mask, live);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
-}
-
-size_t ofx_head_frame_bytes(size_t S, size_t *u2fr, size_t *vfr, size_t *c4) {
-  *u2fr = 4 * S * 1600;
-  *vfr = 4 * S * 7200;
-  *c4 = 4 * (S + 1) * HC4_STRIDE;   // + the block of zeros
-  return *u2fr + *vfr + *c4;
-}
-
-int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
-  HeadParams2 p = p0;
-#if OFX_HEAD_HOOKS
-  { const char *e = getenv("OFX_HEAD_ABLATE"); p.ablate = e ? atoi(e) : 0; }  // diagnostics: 1 no stage C, 2 no stage A / B
-  static unsigned long long *dbg = nullptr;
-  static int dbg_calls = 0;
-  const unsigned dbg_blocks = (unsigned)(((p.S + 7) / 8) * 16);
-  p.dbg = nullptr;
-  if (getenv("OFX_HEAD_STAMPS")) {  // s_memtime stamps per wave, printed for the 20th forward
-    if (!dbg) (void)hipMalloc(&dbg, (size_t)dbg_blocks * 6 * (HS_NB + 4) * 8);
-    if (++dbg_calls == 20) p.dbg = dbg;
-  }
-#endif
-  if (p.mask) {
-    if (!p.live) { ofx_set_error("ofx_launch_head: a mask needs the live-list scratch"); return OFX_ERR_STATE; }
-    if (!p.live_ready) hipLaunchKernelGGL(k_head_compact, dim3(1), dim3(1024), 0, h->stream, p.S, p.mask, p.live);
-  } else {
-    p.live = nullptr;
-  }
-  if (p.frames_ref) hipLaunchKernelGGL(k_head_frames_ref, dim3((unsigned)p.S), dim3(HF_THREADS), 0, h->stream, p);
-  else hipLaunchKernelGGL(k_head_frames, dim3((unsigned)((p.S + 7) & ~7)), dim3(HG_THREADS), 0, h->stream, p);
-  OFX_HIP(hipGetLastError());
-  const unsigned blocks = (unsigned)(((p.S + 7) / 8) * 16);
-  int rc;
-  if (p.event_base >= 0 && (rc = ofx_event_record(h, p.event_base))) return rc;
-  const bool extra = p.heat || p.ptr_probe;
-#define HS_LAUNCH(E, L) hipLaunchKernelGGL((k_head_stream<E, L>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p)
-  if (p.bf16 == 1) { if (extra) HS_LAUNCH(true, 1); else HS_LAUNCH(false, 1); }
-  else if (p.bf16 == 2) { if (extra) HS_LAUNCH(true, 2); else HS_LAUNCH(false, 2); }
-  else { if (extra) HS_LAUNCH(true, 0); else HS_LAUNCH(false, 0); }
-#undef HS_LAUNCH
-  OFX_HIP(hipGetLastError());
-  if (p.event_base >= 0 && (rc = ofx_event_record(h, p.event_base + 1))) return rc;
-#if OFX_HEAD_HOOKS
-  if (p.dbg) {
-    (void)hipStreamSynchronize(h->stream);
-    unsigned long long *hst = (unsigned long long *)malloc((size_t)blocks * 6 * (HS_NB + 4) * 8);
-    (void)hipMemcpy(hst, p.dbg, (size_t)blocks * 6 * (HS_NB + 4) * 8, hipMemcpyDeviceToHost);
-    double sum[2][6] = {{0}};
-    for (unsigned b = 0; b < blocks; b++)
-      for (int w = 0; w < HS_NB + 4; w++)
-        for (int i = 0; i < 6; i++) sum[w >= HS_NB][i] += (double)hst[((size_t)b * (HS_NB + 4) + w) * 6 + i] / (w >= HS_NB ? 4.0 : (double)HS_NB);
-    for (int r = 0; r < 2; r++) {
-      fprintf(stderr, "head stamps %s (cycles per wave and sub-step):", r ? "C" : "B");
-      for (int i = 0; i < 6; i++) fprintf(stderr, " %.0f", sum[r][i] / ((double)blocks * HS_NS));
-      fprintf(stderr, "\n");
-    }
-    free(hst);
-  }
-#endif
-  return OFX_OK;
-}
+#endif  // OFX_HEAD_STREAM_BODY

@@ -633,11 +633,83 @@ __global__ void k_policy_actions(int S, const ofx_state st, const int32_t *iacti
   out[s] = a;
 }
 
+// The exploration rate of local arena a under the ladder (`expo` null = none): epsilon itself at exponent 1 (no pow),
+// pow(epsilon, exponent) in float64 otherwise (pow(x, 0) = 1: exponent 0 always explores); *greedy at +inf.
+__device__ __forceinline__ double arena_eps(double eps, const double *expo, int a, bool *greedy) {
+  *greedy = false;
+  if (expo) {
+    const double x = expo[a];
+    if (x == (double)INFINITY) { *greedy = true; return 0.0; }
+    if (x != 1.0) eps = pow(eps, x);
+  }
+  return eps;
+}
+
+// ---- Boltzmann exploration (ofx_policy_act_boltzmann) ----------------------------------------------------------
+// what the forward needs to sample instead of taking the arg-max
+struct BoltzArgs {
+  double eps;
+  float tau_act, tau_ptr;
+  uint32_t k0, k1, tick;
+  float *q_sa, *p_sp, *v_act, *v_ptr;
+};
+
+// per ship: the temperatures of its arena, T = tau * (float)eps_a in float32 (a greedy arena: 0)
+__global__ void k_boltz_temps(int N, int M, double eps, const double *expo, float tau_act, float tau_ptr, float *t_act,
+                              float *t_ptr) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= N * M) return;
+  bool greedy;
+  const float e = (float)arena_eps(eps, expo, s / M, &greedy);
+  t_act[s] = tau_act * e;
+  t_ptr[s] = tau_ptr * e;
+}
+
+// Behind k_head_stream_sample: the ship's winner among its 8 waves' candidates (the largest key: the largest perturbed
+// value, the first pixel in C order among equals), the raw heat value there and the raw maximum; the action head
+// sampled the same way from two Gumbel words of its own stream.
+__global__ void k_policy_boltz_finish(int S, int M, int arena_base, const uint8_t *mask, const unsigned long long *cand_key,
+                                      const float *cand_raw, const unsigned *cand_max, const float *act, const float *t_act,
+                                      uint32_t k0, uint32_t k1, uint32_t tick, int32_t *iaction, int32_t *ipointer,
+                                      float *q_sa, float *p_sp, float *v_act, float *v_ptr) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S || (mask && !mask[s])) return;
+  unsigned long long key = 0ull;
+  float raw = __builtin_nanf("");
+  unsigned om = 0u;
+  for (int c = 0; c < 8; c++) {
+    const unsigned long long k = cand_key[(size_t)s * 8 + c];
+    if (k > key) { key = k; raw = cand_raw[(size_t)s * 8 + c]; }
+    om = max(om, cand_max[(size_t)s * 8 + c]);
+  }
+  // key == 0: no value ever beat -inf (a NaN or -inf map), as in k_policy_finish: pointer 0, NaN values
+  const unsigned idx = key ? ~(unsigned)(key & 0xFFFFFFFFull) : 0u;
+  ipointer[2 * s] = (int)(idx % PS);
+  ipointer[2 * s + 1] = (int)(idx / PS);
+  p_sp[s] = raw;
+  v_ptr[s] = key ? unordered_f32(om) : __builtin_nanf("");
+  const int a = s / M, i = s - a * M;
+  const float a0 = act[2 * s], a1 = act[2 * s + 1], T = t_act[s];
+  int ia = a1 > a0 ? 1 : 0;   // np.argmax: first maximum
+  if (T != 0.f) {
+    uint32_t r[4];
+    ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_BOLTZMANN_ACT, k0, k1, r);
+    ia = fmaf(T, hd_gumbel(r[1]), a1) > fmaf(T, hd_gumbel(r[0]), a0) ? 1 : 0;
+  }
+  iaction[s] = ia;
+  q_sa[s] = ia ? a1 : a0;
+  v_act[s] = fmaxf(a0, a1);
+}
+
 // ---- workspace -----------------------------------------------------------------------
 struct PolicyWs {
   float *p1, *p2, *p3, *p4, *g1, *d1, *u0, *up1, *u2fr, *vfr, *c4;
   unsigned long long *best;
   int32_t *iaction, *ipointer, *live;
+  // sampling forwards only (null otherwise): per-ship temperatures, per-wave candidates of k_head_stream_sample
+  float *t_act, *t_ptr, *cand_raw;
+  unsigned long long *cand_key;
+  unsigned *cand_max;
 };
 
 static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -647,7 +719,7 @@ constexpr int kDense1Chunks = 25;  // split-K of dense1: 5000 = 25 x 200
 // any other user of the handle's scratch block may overwrite or re-allocate it.  The (iaction, ipointer) slots only
 // take results nobody asked for (ofx_policy_forward_obs with null outputs); the results that ofx_policy_forward keeps
 // for ofx_policy_explore / ofx_policy_actions / ofx_replay_capture live in the handle (ofx_policy_results).
-static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S) {
+static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S, bool sample = false) {
   size_t f2, f3, f4;
   ofx_head_frame_bytes(S, &f2, &f3, &f4);
   // p1 (5.2 GB at 4096 arenas) exists only in the two-kernel form of the trunk
@@ -655,7 +727,10 @@ static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S) {
                        al(4ull * N * 5000),          al(4ull * N * 100 * kDense1Chunks), al(4ull * S * 100),
                        al(4ull * S * 625),           al(4ull * S * 2 * 50 * 50),   al(f2), al(f3), al(f4),
                        al(8ull * S),                 al(4ull * S),                 al(8ull * S),
-                       al(4ull * (S + 1))};
+                       al(4ull * (S + 1)),
+                       // the sampling forward's arrays stand behind everything else: the other forwards' layout is unchanged
+                       sample ? al(4ull * S) : 0,    sample ? al(4ull * S) : 0,    sample ? al(4ull * 8 * S) : 0,
+                       sample ? al(8ull * 8 * S) : 0, sample ? al(4ull * 8 * S) : 0};
   size_t total = 0;
   for (size_t b : sz) total += b;
   int rc = ofx_ensure_scratch(h, total);
@@ -664,7 +739,8 @@ static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S) {
   void **dst[] = {(void **)&ws->p1,   (void **)&ws->p2,   (void **)&ws->p3,      (void **)&ws->p4,      (void **)&ws->g1,
                   (void **)&ws->d1,   (void **)&ws->u0,   (void **)&ws->up1,     (void **)&ws->u2fr,    (void **)&ws->vfr,
                   (void **)&ws->c4,   (void **)&ws->best, (void **)&ws->iaction, (void **)&ws->ipointer,
-                  (void **)&ws->live};
+                  (void **)&ws->live, (void **)&ws->t_act, (void **)&ws->t_ptr, (void **)&ws->cand_raw,
+                  (void **)&ws->cand_key, (void **)&ws->cand_max};
   for (size_t i = 0; i < sizeof(sz) / sizeof(sz[0]); i++) { *dst[i] = base; base += sz[i]; }
   return OFX_OK;
 }
@@ -775,13 +851,14 @@ struct ForwardArgs {
   float *act_values, *heatmap, *ptr_max, *ptr_probe;
   int32_t *iaction, *ipointer;
   const int32_t *probe;
+  const BoltzArgs *boltz;          // non-null: sample both heads (k_head_stream_sample + k_policy_boltz_finish); needs act_values
 };
 
 static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   const int N = a.N, S = a.N * a.M;
   const float *weights = a.weights;
   PolicyWs ws;
-  int rc = policy_workspace(h, &ws, N, S);
+  int rc = policy_workspace(h, &ws, N, S, a.boltz != nullptr);
   if (rc) return rc;
   int32_t off[64], cnt[64];
   policy_layout(off, cnt);
@@ -843,7 +920,7 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   if (up.legacy) hipLaunchKernelGGL(k_upconv1<true>, dim3((unsigned)(live && S > 4096 ? 4096 : S)), dim3(256), 0, h->stream, up);
   else hipLaunchKernelGGL(k_upconv1<false>, dim3((unsigned)(live && S > 4096 ? 4096 : S)), dim3(256), 0, h->stream, up);
   OFX_HIP(hipGetLastError());
-  OFX_HIP(hipMemsetAsync(ws.best, 0, sizeof(unsigned long long) * S, h->stream));
+  if (!a.boltz) OFX_HIP(hipMemsetAsync(ws.best, 0, sizeof(unsigned long long) * S, h->stream));
   HeadParams2 hp2;
   memset(&hp2, 0, sizeof(hp2));
   hp2.S = S; hp2.up1 = ws.up1;
@@ -856,10 +933,28 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   hp2.bf16 = lowp;  // the rollout's forward only: targets and fit stay fp32
   hp2.mask = a.ship_mask; hp2.live = ws.live; hp2.live_ready = a.ship_mask != nullptr; hp2.best = ws.best; hp2.heat = a.heatmap;
   hp2.probe = a.probe; hp2.ptr_probe = a.probe ? a.ptr_probe : nullptr;
+  if (a.boltz) {
+    const BoltzArgs &b = *a.boltz;
+    hipLaunchKernelGGL(k_boltz_temps, dim3((S + 255) / 256), dim3(256), 0, h->stream, N, a.M, b.eps, h->eps_expo, b.tau_act,
+                       b.tau_ptr, ws.t_act, ws.t_ptr);
+    OFX_HIP(hipGetLastError());
+    hp2.sample = 1; hp2.M = a.M; hp2.arena_base = h->cfg.arena_base;
+    hp2.nk0 = b.k0; hp2.nk1 = b.k1; hp2.ntick = b.tick; hp2.t_ptr = ws.t_ptr;
+    hp2.cand_key = ws.cand_key; hp2.cand_raw = ws.cand_raw; hp2.cand_max = ws.cand_max;
+  }
   const int pb = h->prof_base;  // ofx_policy_profile: events around the dominant kernel, until the ring is full
   hp2.event_base = pb;
   if ((rc = ofx_launch_head(h, hp2))) return rc;
   if (pb >= 0) h->prof_base = pb + 3 < OFX_RING_MAX ? pb + 2 : -1;
+  if (a.boltz) {
+    const BoltzArgs &b = *a.boltz;
+    hipLaunchKernelGGL(k_policy_boltz_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, a.M, h->cfg.arena_base,
+                       a.ship_mask, ws.cand_key, ws.cand_raw, ws.cand_max, a.act_values, ws.t_act, b.k0, b.k1, b.tick,
+                       a.iaction ? a.iaction : ws.iaction, a.ipointer ? a.ipointer : ws.ipointer, b.q_sa, b.p_sp, b.v_act,
+                       b.v_ptr);
+    OFX_HIP(hipGetLastError());
+    return OFX_OK;
+  }
   hipLaunchKernelGGL(k_policy_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, a.ship_mask, ws.best,
                      a.ipointer ? a.ipointer : ws.ipointer, a.ptr_max);
   OFX_HIP(hipGetLastError());
@@ -949,11 +1044,9 @@ __device__ __forceinline__ bool explore_draw(int a, int i, int W, int H, int are
   *ia = ofx_draw_int(r[1], 1);
   *px = ofx_draw_int(r[2], W - 1);
   *py = ofx_draw_int(r[3], H - 1);
-  if (expo) {
-    const double x = expo[a];
-    if (x == (double)INFINITY) return false;
-    if (x != 1.0) eps = pow(eps, x);   // float64; pow(x, 0) = 1: exponent 0 always explores
-  }
+  bool greedy;
+  eps = arena_eps(eps, expo, a, &greedy);
+  if (greedy) return false;
   return collecting || u <= eps;
 }
 
@@ -1112,6 +1205,47 @@ extern "C" int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t
   OFX_HIP(hipGetLastError());
   h->act_called = kept;
   return OFX_OK;
+}
+
+// ---- ofx_policy_act_boltzmann: the same call with both heads sampled from softmax(Q / T) ---------------------------
+// The pointer is sampled inside the streaming kernel (Gumbel-max on per-pixel noise, ofx_head.hip), the action by the
+// finish kernel; nothing is drawn in front of the forward.  The collecting phase is ofx_policy_act's.
+extern "C" int ofx_policy_act_boltzmann(ofx_handle *h, const float *weights, const uint8_t *ship_mask, double epsilon,
+                                        float tau_act, float tau_ptr, uint64_t seed, uint32_t tick, int32_t collecting,
+                                        float *q_sa, float *p_sp, float *v_act, float *v_ptr) {
+  int rc = live_forward_check(h, weights, "ofx_policy_act_boltzmann");
+  if (rc) return rc;
+  if (epsilon < 0.0 || epsilon > 1.0) { ofx_set_error("Value must me in range [0,1]"); return OFX_ERR_INVALID; }  // epsilon.py:56
+  if (!(tau_act >= 0.f && tau_act < INFINITY && tau_ptr >= 0.f && tau_ptr < INFINITY)) {   // NaN fails the comparisons
+    ofx_set_error("ofx_policy_act_boltzmann: tau_act = %g, tau_ptr = %g; both must be finite and >= 0", (double)tau_act, (double)tau_ptr);
+    return OFX_ERR_INVALID;
+  }
+  if (collecting) return ofx_policy_act(h, weights, ship_mask, epsilon, seed, tick, 1, q_sa, p_sp, v_act, v_ptr);
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if ((rc = policy_act_block(h))) return rc;
+  const int S = h->cfg.n_arenas * h->cfg.n_ships;
+  float *f = h->act_vals;
+  const bool kept = !q_sa && !p_sp && !v_act && !v_ptr;   // as in ofx_policy_act
+  BoltzArgs b;
+  b.eps = epsilon; b.tau_act = tau_act; b.tau_ptr = tau_ptr;
+  b.k0 = (uint32_t)seed; b.k1 = (uint32_t)(seed >> 32); b.tick = tick;
+  b.q_sa = q_sa ? q_sa : f; b.p_sp = p_sp ? p_sp : f + S;
+  b.v_act = v_act ? v_act : f + 2 * (size_t)S; b.v_ptr = v_ptr ? v_ptr : f + 3 * (size_t)S;
+  ForwardArgs a{};
+  a.weights = weights; a.ship_mask = ship_mask;
+  a.act_values = f + 4 * (size_t)S;
+  a.boltz = &b;
+  h->act_called = false;
+  if ((rc = live_forward(h, a))) return rc;   // (iaction, ipointer): the handle's results
+  h->act_called = kept;
+  return OFX_OK;
+}
+
+// diagnostic: g_dev[i] = the sampling kernels' float32 Gumbel noise of Philox word words_dev[i]
+extern "C" int ofx_policy_gumbel(ofx_handle *h, const uint32_t *words_dev, int32_t n, float *g_dev) {
+  if (!h || !words_dev || !g_dev || n < 1) { ofx_set_error("ofx_policy_gumbel: bad argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  return ofx_head_gumbel(h, words_dev, n, g_dev);
 }
 
 extern "C" int ofx_policy_actions(ofx_handle *h, const int32_t *iaction, const int32_t *ipointer,

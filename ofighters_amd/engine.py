@@ -644,6 +644,27 @@ class ArenaBatch:
                                            self.tick if tick is None else tick, int(bool(collecting)), q_sa_ptr, p_sp_ptr,
                                            v_act_ptr, v_ptr_ptr))
 
+    def policy_act_boltzmann(self, weights_ptr, epsilon, tau_act, tau_ptr, seed, tick=None, collecting=False,
+                             ship_mask_ptr=None, q_sa_ptr=None, p_sp_ptr=None, v_act_ptr=None, v_ptr_ptr=None):
+        """policy_act with both heads sampled from softmax(Q / T) (opt-in Boltzmann exploration, include/ofx.h): arena a
+        plays at T = tau * eps_a, eps_a the rate policy_explore would use (ladder included; a greedy arena stays greedy),
+        on per-pixel Gumbel noise keyed by (seed, global arena, ship, tick).  `collecting`: exactly policy_act's
+        collecting phase.  Results, values and the None rule are policy_act's.  Does not synchronise."""
+        nat.check(nat.lib().ofx_policy_act_boltzmann(self._h, weights_ptr, ship_mask_ptr, float(epsilon), float(tau_act),
+                                                     float(tau_ptr), seed, self.tick if tick is None else tick,
+                                                     int(bool(collecting)), q_sa_ptr, p_sp_ptr, v_act_ptr, v_ptr_ptr))
+
+    def policy_gumbel(self, words):
+        """The sampling kernels' float32 Gumbel noise of the given Philox words (uint32 array), float32, same shape: a
+        diagnostic of its accuracy against -log(-log1p(-(r + 0.5) / 2**32)) in float64."""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        if w.size < 1:
+            raise ValueError("ArenaBatch.policy_gumbel: at least one word expected")
+        src, dst = DeviceBuffer(w.nbytes).upload(w), DeviceBuffer(4 * w.size)
+        nat.check(nat.lib().ofx_policy_gumbel(self._h, src.ptr, int(w.size), dst.ptr))
+        self.sync()
+        return dst.download(np.float32, w.shape)
+
     def replay_actor_priorities(self, gamma):
         """Enable actor-side initial priorities on a prioritized memory: replay_capture_valued then gives every new
         row the mass of its one-step TD error under `gamma` instead of the arena's running maximum."""

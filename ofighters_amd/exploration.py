@@ -21,6 +21,24 @@ def _integer(name, v, lo=None):
     return int(v)
 
 
+def boltzmann_pair(v):
+    """TrainingRollout's `boltzmann` argument: None (off) or a pair (tau_act, tau_ptr) of finite numbers >= 0, returned
+    as a tuple of floats that float32 can hold.  ValueError naming `boltzmann` for anything else."""
+    if v is None:
+        return None
+    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2:
+        raise ValueError("boltzmann must be None or a pair (tau_act, tau_ptr), got %r" % (v,))
+    out = []
+    for name, x in zip(("tau_act", "tau_ptr"), v):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError("boltzmann: %s must be a number, got %r" % (name, x))
+        x = float(x)
+        if not (0.0 <= x <= float(np.finfo(np.float32).max)):   # NaN fails both comparisons
+            raise ValueError("boltzmann: %s must be finite and >= 0, got %r" % (name, x))
+        out.append(x)
+    return tuple(out)
+
+
 def _shard(total_arenas, arena_base, n, eval_arenas):
     total = _integer("total_arenas", total_arenas, 1)
     base = _integer("arena_base", arena_base, 0)

@@ -186,6 +186,17 @@ class TrainingRollout(ShardedRollout):
     ends an episode exactly there.  The trainer does not change: n-step chains stop at the cleared previous_*.  With
     auto_reset=False none of this exists and lockstep() makes exactly the calls it always made.
 
+    Opt-in, not in the reference (Boltzmann / softmax exploration, e.g. Sutton & Barto 2018, section 2.8):
+    `boltzmann=(tau_act, tau_ptr)`, a pair of finite floats >= 0 (anything else: ValueError naming `boltzmann` before the
+    first device call).  An exploring ship of the default rule points uniformly over all 160 000 cells; with the option
+    every policy ship SAMPLES both heads from softmax(Q / T), T = tau * eps_a with eps_a the arena's exploration rate:
+    the trainer's epsilon schedule anneals the temperature, the ladder spreads it over the arenas and the evaluation
+    arenas (exponent +inf, T = 0) stay greedy.  _play then makes ONE engine.policy_act_boltzmann call
+    (ofx_policy_act_boltzmann: the pointer is sampled inside the streaming head kernel by the Gumbel-max identity, on
+    noise keyed by pixel and `capture_tick`) where forward + explore - or policy_act under actor_priorities - stood,
+    followed by the same capture.  The collecting phase is the default rule's, bit for bit.  No new state: a checkpoint
+    carries the pair in its fingerprint only.  With boltzmann=None _play makes exactly the calls it always made.
+
     engine    ArenaBatch
     trainer   DeviceTrainer built on that engine (owns weights, Adam state, epsilon, the replay memory)
     policy_ships  ship slots driven by the policy (the stock line-up has ONE, lib/ofighters.py:53); the others
@@ -195,8 +206,9 @@ class TrainingRollout(ShardedRollout):
     def __init__(self, engine, trainer, behaviours, seed, policy_ships=(0,), is_learning=True, collecting_steps=20,
                  replay_every=50, replay_on_death=True, snapshot_every=50, snapshot_folder=None, checkpoint_every=0,
                  checkpoint_folder=None, epsilon_ladder=None, eval_arenas=0, total_arenas=None, score_bands=8,
-                 action_repeat=1, auto_reset=False, **kw):
+                 action_repeat=1, auto_reset=False, boltzmann=None, **kw):
         from . import exploration
+        self.boltzmann = exploration.boltzmann_pair(boltzmann)   # every argument is checked before the first device call
         if not isinstance(auto_reset, (bool, np.bool_)):   # every argument is checked before the first device call
             raise ValueError("auto_reset must be a bool, got %r" % (auto_reset,))
         self.auto_reset = bool(auto_reset)
@@ -385,7 +397,16 @@ class TrainingRollout(ShardedRollout):
             if e.agents_first_done(lm, self._seen_done) > 0:
                 self._replay()
                 replayed = True
-        if getattr(t, "actor_priorities", False):      # (a duck-typed trainer that predates the option has none)
+        if self.boltzmann is not None:
+            # both heads sampled from softmax(Q / (tau * eps_a)) inside the forward: one call instead of forward + explore
+            # (and instead of policy_act); the evaluation arenas stay greedy through their +inf exponent
+            e.policy_act_boltzmann(t.weights.ptr, t.epsilon.get(), self.boltzmann[0], self.boltzmann[1], self.seed,
+                                   tick=self.capture_tick, collecting=collecting, ship_mask_ptr=m)
+            if getattr(t, "actor_priorities", False):
+                e.replay_capture_valued(self.capture_tick, ship_mask_ptr=lm)
+            else:
+                e.replay_capture(self.capture_tick, ship_mask_ptr=lm)
+        elif getattr(t, "actor_priorities", False):    # (a duck-typed trainer that predates the option has none)
             # the same choice in one call, with its values; the capture turns them into the new rows' priorities
             e.policy_act(t.weights.ptr, t.epsilon.get(), self.seed, tick=self.capture_tick, collecting=collecting,
                          ship_mask_ptr=m)
