@@ -58,6 +58,8 @@ struct ofx_handle {
   int ring_n;
   int prof_base;                   // ofx_policy_profile: next event pair, -1 = off
   ofx_replay *replay;              // transition memory (ofx_replay_create), null = none
+  // Hand-carved blocks (aux, fitws, fitws2, applyws, scratch under the forward): each is laid out by one function on an
+  // Arena (ofx_arena.h), run once to measure and once on the block; the buffers and their counts are stated there alone.
   void *aux;                       // temporaries of ofx_dqn_targets (grown on demand)
   size_t aux_bytes;
   void *fitws;                     // workspace of ofx_dqn_fit / ofx_dqn_fit_reference, kept between calls (a fresh 4 GB
@@ -84,7 +86,7 @@ struct ofx_handle {
   unsigned long long *trunk_stat;  // [4] device counters of the sparse trunk (allocated with value 1 of the option)
   // ofx_policy_act (one block, allocated at its first call): the four value arrays a null output stands for, then the
   // forward's results they are selected from and the pre-drawn exploration
-  float *act_vals;                 // [4][N*M] q_sa, p_sp, v_act, v_ptr, then act [N*M][2], ptr_max [N*M], ptr_probe [N*M]
+  float *act_vals;                 // one packed block: q_sa, p_sp, v_act, v_ptr [N*M] each, then ... (act_block, ofx_policy.hip)
   bool act_called;                 // the LAST ofx_policy_act wrote all four of the handle's arrays (all outputs NULL)
   double *eps_expo;                // [N] ofx_policy_epsilon_ladder: arena a explores at epsilon^eps_expo[a] (+inf: never); null = no ladder
   // ofx_restart_finished (one allocation at its first call, null before): per-arena episode counter, the ships seen

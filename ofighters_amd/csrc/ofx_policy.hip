@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "ofx_internal.h"
+#include "ofx_arena.h"
 #include "ofx_blob.h"
 #include "ofx_trunk.h"
 #include "ofx_head.h"
@@ -706,42 +707,40 @@ struct PolicyWs {
   float *p1, *p2, *p3, *p4, *g1, *d1, *u0, *up1, *u2fr, *vfr, *c4;
   unsigned long long *best;
   int32_t *iaction, *ipointer, *live;
-  // sampling forwards only (null otherwise): per-ship temperatures, per-wave candidates of k_head_stream_sample
+  // sampling forwards only: per-ship temperatures, per-wave candidates of k_head_stream_sample.  Otherwise the five have no
+  // bytes (they point at the block's end) and no kernel gets them; so p1, which points at p2, in the fused form of the trunk.
   float *t_act, *t_ptr, *cand_raw;
   unsigned long long *cand_key;
   unsigned *cand_max;
 };
 
-static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int kDense1Chunks = 25;  // split-K of dense1: 5000 = 25 x 200
 
 // N images (trunk runs), S policy samples (heads).  Everything here is transient: a later forward with other sizes or
 // any other user of the handle's scratch block may overwrite or re-allocate it.  The (iaction, ipointer) slots only
 // take results nobody asked for (ofx_policy_forward_obs with null outputs); the results that ofx_policy_forward keeps
 // for ofx_policy_explore / ofx_policy_actions / ofx_replay_capture live in the handle (ofx_policy_results).
-static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S, bool sample = false) {
+static void policy_layout_ws(Arena &A, bool fused, size_t N, size_t S, bool sample, PolicyWs &W) {
   size_t f2, f3, f4;
   ofx_head_frame_bytes(S, &f2, &f3, &f4);
-  // p1 (5.2 GB at 4096 arenas) exists only in the two-kernel form of the trunk
-  const size_t sz[] = {ofx_trunk_fused(h, N) ? 0 : al(4ull * N * 8 * 200 * 200), al(4ull * N * 8 * 100 * 100), al(4ull * N * 8 * 50 * 50),
-                       al(4ull * N * 5000),          al(4ull * N * 100 * kDense1Chunks), al(4ull * S * 100),
-                       al(4ull * S * 625),           al(4ull * S * 2 * 50 * 50),   al(f2), al(f3), al(f4),
-                       al(8ull * S),                 al(4ull * S),                 al(8ull * S),
-                       al(4ull * (S + 1)),
-                       // the sampling forward's arrays stand behind everything else: the other forwards' layout is unchanged
-                       sample ? al(4ull * S) : 0,    sample ? al(4ull * S) : 0,    sample ? al(4ull * 8 * S) : 0,
-                       sample ? al(8ull * 8 * S) : 0, sample ? al(4ull * 8 * S) : 0};
-  size_t total = 0;
-  for (size_t b : sz) total += b;
-  int rc = ofx_ensure_scratch(h, total);
+  W.p1 = A.f(fused ? 0 : N * 8 * 200 * 200);   // (5.2 GB at 4096 arenas) only in the two-kernel form of the trunk
+  W.p2 = A.f(N * 8 * 100 * 100); W.p3 = A.f(N * 8 * 50 * 50); W.p4 = A.f(N * 5000); W.g1 = A.f(N * 100 * kDense1Chunks);
+  W.d1 = A.f(S * 100); W.u0 = A.f(S * 625); W.up1 = A.f(S * 2 * 50 * 50);
+  W.u2fr = (float *)A.take(f2); W.vfr = (float *)A.take(f3); W.c4 = (float *)A.take(f4);
+  W.best = A.n<unsigned long long>(S); W.iaction = A.n<int32_t>(S); W.ipointer = A.n<int32_t>(2 * S); W.live = A.n<int32_t>(S + 1);
+  // the sampling forward's arrays stand behind everything else: the other forwards' layout is unchanged
+  const size_t Q = sample ? S : 0;
+  W.t_act = A.f(Q); W.t_ptr = A.f(Q); W.cand_raw = A.f(8 * Q); W.cand_key = A.n<unsigned long long>(8 * Q); W.cand_max = A.n<unsigned>(8 * Q);
+}
+static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S, bool sample = false) {
+  const bool fused = ofx_trunk_fused(h, N);
+  Arena measure;
+  policy_layout_ws(measure, fused, N, S, sample, *ws);
+  const int rc = ofx_ensure_scratch(h, measure.used);
   if (rc) return rc;
-  char *base = (char *)h->scratch;
-  void **dst[] = {(void **)&ws->p1,   (void **)&ws->p2,   (void **)&ws->p3,      (void **)&ws->p4,      (void **)&ws->g1,
-                  (void **)&ws->d1,   (void **)&ws->u0,   (void **)&ws->up1,     (void **)&ws->u2fr,    (void **)&ws->vfr,
-                  (void **)&ws->c4,   (void **)&ws->best, (void **)&ws->iaction, (void **)&ws->ipointer,
-                  (void **)&ws->live, (void **)&ws->t_act, (void **)&ws->t_ptr, (void **)&ws->cand_raw,
-                  (void **)&ws->cand_key, (void **)&ws->cand_max};
-  for (size_t i = 0; i < sizeof(sz) / sizeof(sz[0]); i++) { *dst[i] = base; base += sz[i]; }
+  Arena A(h->scratch, measure.used);
+  policy_layout_ws(A, fused, N, S, sample, *ws);
+  if (!A.ok()) { ofx_set_error("policy forward: internal workspace sized too small"); return OFX_ERR_STATE; }
   return OFX_OK;
 }
 
@@ -1156,20 +1155,39 @@ __global__ void k_policy_act_finish(int S, const uint8_t *mask, const uint8_t *e
   p_sp[s] = ex ? ptr_probe[s] : ptr_max[s];   // the greedy pointer is the arg-max: its value is the maximum
 }
 
-// the handle's block of ofx_policy_act: floats q_sa, p_sp, v_act, v_ptr [S] each, act [S][2], ptr_max [S], ptr_probe [S];
-// then int32 draw_ia [S], probe [S][2]; then uint8 explores [S]
-static int policy_act_block(ofx_handle *h) {
-  if (h->act_vals) return OFX_OK;
+// the handle's block of ofx_policy_act, allocated once and kept: the arrays stand back to back in this order (floats, then
+// int32, then bytes - every one aligned for its type with no rounding in between), S = N*M
+struct ActBlock {
+  float *q_sa, *p_sp, *v_act, *v_ptr;   // [S] each: what a null output of ofx_policy_act stands for
+  float *act, *ptr_max, *ptr_probe;     // [S][2], [S], [S]: the forward's results they are selected from
+  int32_t *draw_ia, *probe;             // [S], [S][2]: the pre-drawn exploration
+  uint8_t *explores;                    // [S]
+  size_t bytes;
+};
+static ActBlock act_block(const ofx_handle *h) {   // (before the block exists: null pointers, bytes alone)
   const size_t S = (size_t)h->cfg.n_arenas * h->cfg.n_ships;
-  OFX_HIP(hipMalloc((void **)&h->act_vals, S * (8 * sizeof(float) + 3 * sizeof(int32_t) + 1)));
-  OFX_HIP(hipMemsetAsync(h->act_vals, 0, S * (8 * sizeof(float) + 3 * sizeof(int32_t) + 1), h->stream));
+  ActBlock B;
+  B.bytes = 0;
+  auto put = [&](size_t bytes) { char *p = h->act_vals ? (char *)h->act_vals + B.bytes : nullptr; B.bytes += bytes; return p; };
+  B.q_sa = (float *)put(4 * S); B.p_sp = (float *)put(4 * S); B.v_act = (float *)put(4 * S); B.v_ptr = (float *)put(4 * S);
+  B.act = (float *)put(4 * 2 * S); B.ptr_max = (float *)put(4 * S); B.ptr_probe = (float *)put(4 * S);
+  B.draw_ia = (int32_t *)put(4 * S); B.probe = (int32_t *)put(4 * 2 * S); B.explores = (uint8_t *)put(S);
+  return B;
+}
+static int policy_act_block(ofx_handle *h, ActBlock *B) {
+  const size_t bytes = act_block(h).bytes;
+  if (!h->act_vals) {
+    OFX_HIP(hipMalloc((void **)&h->act_vals, bytes));
+    OFX_HIP(hipMemsetAsync(h->act_vals, 0, bytes, h->stream));
+  }
+  *B = act_block(h);
   return OFX_OK;
 }
 
 int ofx_policy_act_values(ofx_handle *h, const float **q_sa, const float **p_sp, const float **v_act, const float **v_ptr) {
   if (!h->act_called) return OFX_ERR_STATE;
-  const size_t S = (size_t)h->cfg.n_arenas * h->cfg.n_ships;
-  *q_sa = h->act_vals; *p_sp = h->act_vals + S; *v_act = h->act_vals + 2 * S; *v_ptr = h->act_vals + 3 * S;
+  const ActBlock B = act_block(h);
+  *q_sa = B.q_sa; *p_sp = B.p_sp; *v_act = B.v_act; *v_ptr = B.v_ptr;
   return OFX_OK;
 }
 
@@ -1179,29 +1197,24 @@ extern "C" int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t
   if (rc) return rc;
   if (epsilon < 0.0 || epsilon > 1.0) { ofx_set_error("Value must me in range [0,1]"); return OFX_ERR_INVALID; }  // epsilon.py:56
   OFX_HIP(hipSetDevice(h->cfg.device));
-  if ((rc = policy_act_block(h))) return rc;
+  ActBlock B;
+  if ((rc = policy_act_block(h, &B))) return rc;
   const int S = h->cfg.n_arenas * h->cfg.n_ships;
-  float *f = h->act_vals;
-  float *act = f + 4 * (size_t)S, *ptr_max = f + 6 * (size_t)S, *ptr_probe = f + 7 * (size_t)S;
-  int32_t *draw_ia = (int32_t *)(f + 8 * (size_t)S), *probe = draw_ia + S;
-  uint8_t *explores = (uint8_t *)(probe + 2 * (size_t)S);
   // the handle's four arrays stand for "the last ofx_policy_act" only when that call wrote all four of them
   const bool kept = !q_sa && !p_sp && !v_act && !v_ptr;
-  if (!q_sa) q_sa = f;
-  if (!p_sp) p_sp = f + S;
-  if (!v_act) v_act = f + 2 * (size_t)S;
-  if (!v_ptr) v_ptr = f + 3 * (size_t)S;
+  q_sa = q_sa ? q_sa : B.q_sa; p_sp = p_sp ? p_sp : B.p_sp;
+  v_act = v_act ? v_act : B.v_act; v_ptr = v_ptr ? v_ptr : B.v_ptr;
   hipLaunchKernelGGL(k_policy_predraw, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
                      h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     tick, collecting, ship_mask, explores, draw_ia, probe);
+                     tick, collecting, ship_mask, B.explores, B.draw_ia, B.probe);
   OFX_HIP(hipGetLastError());
   ForwardArgs a{};
   a.weights = weights; a.ship_mask = ship_mask;
-  a.act_values = act; a.ptr_max = ptr_max; a.probe = probe; a.ptr_probe = ptr_probe;
+  a.act_values = B.act; a.ptr_max = B.ptr_max; a.probe = B.probe; a.ptr_probe = B.ptr_probe;
   h->act_called = false;
   if ((rc = live_forward(h, a))) return rc;   // (iaction, ipointer): the handle's results
-  hipLaunchKernelGGL(k_policy_act_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, ship_mask, explores, draw_ia,
-                     probe, act, ptr_max, ptr_probe, a.iaction, a.ipointer, q_sa, p_sp, v_act, v_ptr);
+  hipLaunchKernelGGL(k_policy_act_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, ship_mask, B.explores, B.draw_ia,
+                     B.probe, B.act, B.ptr_max, B.ptr_probe, a.iaction, a.ipointer, q_sa, p_sp, v_act, v_ptr);
   OFX_HIP(hipGetLastError());
   h->act_called = kept;
   return OFX_OK;
@@ -1222,18 +1235,17 @@ extern "C" int ofx_policy_act_boltzmann(ofx_handle *h, const float *weights, con
   }
   if (collecting) return ofx_policy_act(h, weights, ship_mask, epsilon, seed, tick, 1, q_sa, p_sp, v_act, v_ptr);
   OFX_HIP(hipSetDevice(h->cfg.device));
-  if ((rc = policy_act_block(h))) return rc;
-  const int S = h->cfg.n_arenas * h->cfg.n_ships;
-  float *f = h->act_vals;
+  ActBlock B;
+  if ((rc = policy_act_block(h, &B))) return rc;
   const bool kept = !q_sa && !p_sp && !v_act && !v_ptr;   // as in ofx_policy_act
   BoltzArgs b;
   b.eps = epsilon; b.tau_act = tau_act; b.tau_ptr = tau_ptr;
   b.k0 = (uint32_t)seed; b.k1 = (uint32_t)(seed >> 32); b.tick = tick;
-  b.q_sa = q_sa ? q_sa : f; b.p_sp = p_sp ? p_sp : f + S;
-  b.v_act = v_act ? v_act : f + 2 * (size_t)S; b.v_ptr = v_ptr ? v_ptr : f + 3 * (size_t)S;
+  b.q_sa = q_sa ? q_sa : B.q_sa; b.p_sp = p_sp ? p_sp : B.p_sp;
+  b.v_act = v_act ? v_act : B.v_act; b.v_ptr = v_ptr ? v_ptr : B.v_ptr;
   ForwardArgs a{};
   a.weights = weights; a.ship_mask = ship_mask;
-  a.act_values = f + 4 * (size_t)S;
+  a.act_values = B.act;
   a.boltz = &b;
   h->act_called = false;
   if ((rc = live_forward(h, a))) return rc;   // (iaction, ipointer): the handle's results

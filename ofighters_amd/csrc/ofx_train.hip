@@ -4,7 +4,7 @@
 // Two forms of the same step.  The default is the LEAN form (dqn_fit_lean below + the kernels of ofx_fit.hip): only the
 // pre-activation tensor of every convolution is kept in HBM, the rest is recomputed inside fused tiles (9.4 MB of
 // workspace per minibatch row; 4096 rows in 42 ms, 65 ms with the reference's dense targets).  The PLAIN form (OFX_OPT_FIT_PLAIN, dqn_fit_impl) is the layer-by-layer
-// original - one fp32 VALU kernel per layer and pass, every tensor of the graph in HBM (61 MB per row) - kept as the
+// original - one fp32 VALU kernel per layer and pass, every tensor of the graph in HBM (37 MB per row) - kept as the
 // reference of the lean form.  Both: fixed-order reductions (no atomics: a fit is reproducible to the bit), the dense
 // forwards on the f32 MFMA GEMM of the forward, every gradient tensor checked against torch autograd in float64 and the
 // two forms against each other (tests/test_train.py).  Keras semantics assumed (parity unpinned: no keras in the image):
@@ -17,6 +17,7 @@
 //     next_state as input, :280-283, are stated in include/ofx.h, not reproduced);
 //   * Adam: beta1 0.9, beta2 0.999, eps 1e-7, bias-corrected step size.
 #include "ofx_internal.h"
+#include "ofx_arena.h"
 #include "ofx_blob.h"
 #include "ofx_fit.h"
 #include <float.h>
@@ -660,16 +661,10 @@ __global__ void t_adam_scaled(size_t cnt, float *w, const float *g, float *m, fl
     w[e] -= lr_t * mi / (sqrtf(vi) + eps);
   }
 }
-__global__ void t_moving(int c_n, float *mean, float *var, const float *stat) {
-  const int c = threadIdx.x;
-  if (c >= c_n) return;
-  mean[c] = 0.99f * mean[c] + 0.01f * stat[2 * c];
-  var[c] = 0.99f * var[c] + 0.01f * stat[2 * c + 1];
-}
 
 // ---- the split fit (ofx_dqn_grad / ofx_dqn_apply): the accumulator is [n_floats gradient][OFX_ACC_TAIL] (include/ofx.h) ----
 // One micro-batch into the accumulator, element by element in a fixed order: the gradient blob, the {mean, var} pairs
-// t_moving reads from the 7 stat slots, the two losses, a count of 1 and zeros.  reset: acc = value, else acc += value - a
+// t_moving_scaled reads from the 7 stat slots, the two losses, a count of 1 and zeros.  reset: acc = value, else acc += value - a
 // plain fp32 add (this file is compiled with -ffp-contract=off), no scale.
 struct AccSrc {
   const float *stat[7];   // trunk 0-3, head-2 0-2
@@ -704,7 +699,9 @@ __global__ void t_apply_factor(int count, const double *part, float clip, float 
   out[2] = norm;
   out[3] = (clip > 0.f ? fminf(1.f, clip / (norm + 1e-6f)) : 1.f) * scale;
 }
-// t_moving on scale * stat (the accumulator's summed batch statistics); a scale of exactly 1 gives t_moving's bits
+// moving = 0.99 moving + 0.01 (scale * stat): stat holds the batch statistics {mean, var} per channel - a fit's own at
+// scale 1 (the product by 1.0f is exact and nothing here is contracted: the bits of the unscaled expression), or the
+// accumulator's summed ones (ofx_dqn_apply)
 __global__ void t_moving_scaled(int c_n, float *mean, float *var, const float *stat, float scale) {
   const int c = threadIdx.x;
   if (c >= c_n) return;
@@ -715,19 +712,6 @@ __global__ void t_moving_scaled(int c_n, float *mean, float *var, const float *s
 // ---------------------------------------------------------------- host orchestration
 #define GRID(total) dim3((unsigned)(((total) + 255) / 256 > 65535 * 16 ? 65535 * 16 : ((total) + 255) / 256)), dim3(256)
 #define K(kern, total, ...) do { hipLaunchKernelGGL(kern, GRID(total), 0, st, __VA_ARGS__); OFX_HIP(hipGetLastError()); } while (0)
-
-struct Arena {  // bump allocator over one hipMalloc
-  char *base; size_t used, cap;
-  bool over = false;
-  char *take(size_t bytes) {
-    char *p = base + used;
-    used += (bytes + 255) & ~(size_t)255;
-    if (used > cap) { over = true; used = 0; p = base; }   // never hand out memory past the block; the caller checks `over`
-    return p;
-  }
-  float *f(size_t n) { return (float *)take(n * 4); }
-  double *d(size_t n) { return (double *)take(n * 8); }
-};
 
 static const int kWSlices = 128;
 
@@ -753,14 +737,13 @@ static void conv_bwd_weight(hipStream_t st, int n, int ci, int co, int H, int W,
 
 // one blockIdx.y per (sample, channel) plane of `per` elements, up to 64 blocks of 256 threads along it
 #define PLANES(per, planes) dim3((unsigned)(((per) + 255) / 256 > 64 ? 64 : ((per) + 255) / 256), (unsigned)(planes)), dim3(256)
-#define GRIDP(total) dim3((unsigned)(((total) + 255) / 256 > 65535 * 16 ? 65535 * 16 : ((total) + 255) / 256)), dim3(256)
 static int conv_fwd(hipStream_t st, int n, int ci, int co, int H, int W, const float *x, const float *w, const float *b, float *z) {
   const size_t px = (size_t)n * H * W;
   switch (co) {
-    case 8: hipLaunchKernelGGL(t_conv_fwd<8>, GRIDP(px), 0, st, n, ci, H, W, x, w, b, z); break;
-    case 4: hipLaunchKernelGGL(t_conv_fwd<4>, GRIDP(px), 0, st, n, ci, H, W, x, w, b, z); break;
-    case 2: hipLaunchKernelGGL(t_conv_fwd<2>, GRIDP(px), 0, st, n, ci, H, W, x, w, b, z); break;
-    case 1: hipLaunchKernelGGL(t_conv_fwd<1>, GRIDP(px), 0, st, n, ci, H, W, x, w, b, z); break;
+    case 8: hipLaunchKernelGGL(t_conv_fwd<8>, GRID(px), 0, st, n, ci, H, W, x, w, b, z); break;
+    case 4: hipLaunchKernelGGL(t_conv_fwd<4>, GRID(px), 0, st, n, ci, H, W, x, w, b, z); break;
+    case 2: hipLaunchKernelGGL(t_conv_fwd<2>, GRID(px), 0, st, n, ci, H, W, x, w, b, z); break;
+    case 1: hipLaunchKernelGGL(t_conv_fwd<1>, GRID(px), 0, st, n, ci, H, W, x, w, b, z); break;
     default: ofx_set_error("ofx_dqn_fit: no conv kernel for %d output channels", co); return OFX_ERR_STATE;
   }
   OFX_HIP(hipGetLastError());
@@ -769,10 +752,10 @@ static int conv_fwd(hipStream_t st, int n, int ci, int co, int H, int W, const f
 static int conv_bwd_data(hipStream_t st, int n, int ci, int co, int H, int W, const float *dz, const float *w, float *dx) {
   const size_t px = (size_t)n * H * W;
   switch (ci) {
-    case 8: hipLaunchKernelGGL(t_conv_bwd_data<8>, GRIDP(px), 0, st, n, co, H, W, dz, w, dx); break;
-    case 4: hipLaunchKernelGGL(t_conv_bwd_data<4>, GRIDP(px), 0, st, n, co, H, W, dz, w, dx); break;
-    case 2: hipLaunchKernelGGL(t_conv_bwd_data<2>, GRIDP(px), 0, st, n, co, H, W, dz, w, dx); break;
-    case 1: hipLaunchKernelGGL(t_conv_bwd_data<1>, GRIDP(px), 0, st, n, co, H, W, dz, w, dx); break;
+    case 8: hipLaunchKernelGGL(t_conv_bwd_data<8>, GRID(px), 0, st, n, co, H, W, dz, w, dx); break;
+    case 4: hipLaunchKernelGGL(t_conv_bwd_data<4>, GRID(px), 0, st, n, co, H, W, dz, w, dx); break;
+    case 2: hipLaunchKernelGGL(t_conv_bwd_data<2>, GRID(px), 0, st, n, co, H, W, dz, w, dx); break;
+    case 1: hipLaunchKernelGGL(t_conv_bwd_data<1>, GRID(px), 0, st, n, co, H, W, dz, w, dx); break;
     default: ofx_set_error("ofx_dqn_fit: no conv kernel for %d input channels", ci); return OFX_ERR_STATE;
   }
   OFX_HIP(hipGetLastError());
@@ -789,6 +772,20 @@ __global__ void t_count_pads(int n, const ofx_transition *rows, int32_t *out) {
 static int keep_workspace(ofx_handle *h, void **buf, size_t *have, size_t need) {
   if (*have / 4 > need) *have = 0;   // given back: allocated anew at `need`
   return ofx_ensure_buffer(h, buf, have, need);
+}
+
+// A workspace (ofx_arena.h): `layout`, the one statement of its buffers, measures; the handle's block is ensured (keep: under
+// keep_workspace's give-back rule); `layout` hands out the pointers; ok() is checked before the caller's first launch
+template <class Layout>
+static int carve(ofx_handle *h, void **buf, size_t *have, bool keep, const char *who, Layout layout) {
+  Arena measure;
+  layout(measure);
+  const int rc = keep ? keep_workspace(h, buf, have, measure.used) : ofx_ensure_buffer(h, buf, have, measure.used);
+  if (rc) return rc;
+  Arena A(*buf, measure.used);
+  layout(A);
+  if (!A.ok()) { ofx_set_error("%s: internal workspace sized too small", who); return OFX_ERR_STATE; }
+  return OFX_OK;
 }
 
 // padding rows (ship < 0) would enter the BatchNorm batch statistics and the loss scale: refused before any work is done
@@ -812,6 +809,17 @@ static int refuse_pads(ofx_handle *h, int n, const ofx_transition *rows, const c
 // ofx_dqn_targets_double (dbl; `weights` is the online blob): the forward on next_state runs twice - online for
 // (iaction, ipointer), then `target` probed at that pointer - and k_dqn_targets_double takes the place of k_dqn_targets.
 // What one forward hands to the next lives in the aux arena: the forward's scratch block is laid out anew by each.
+struct TargetsWs {
+  float *vec_prev, *vec_next, *act_prev, *act_next, *probe_prev, *max_next, *act_tgt, *probe_tgt;
+  int32_t *probe, *sel_action, *sel_pointer;   // sel_*, *_tgt: the double form only (null otherwise)
+};
+static void targets_layout(Arena &A, size_t n, bool dbl, TargetsWs &W) {
+  W.vec_prev = A.f(8 * n); W.vec_next = A.f(8 * n);
+  W.probe = A.n<int32_t>(2 * n);
+  W.act_prev = A.f(2 * n); W.act_next = A.f(2 * n); W.probe_prev = A.f(n); W.max_next = A.f(n);
+  W.sel_action = dbl ? A.n<int32_t>(n) : nullptr; W.sel_pointer = dbl ? A.n<int32_t>(2 * n) : nullptr;
+  W.act_tgt = dbl ? A.f(2 * n) : nullptr; W.probe_tgt = dbl ? A.f(n) : nullptr;
+}
 static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, const float *target, bool dbl, int32_t n,
                             const ofx_transition *rows, const void *bits_prev, const void *bits_next, float gamma,
                             const float *ret, const float *disc, float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
@@ -821,38 +829,30 @@ static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights
     return OFX_ERR_INVALID;
   }
   OFX_HIP(hipSetDevice(h->cfg.device));
-  const size_t nn = (size_t)n;
-  // seven arrays (four more for the double form), each rounded up to 256 bytes
-  const size_t need = 7 * 256 + 4 * nn * (8 + 8 + 2 + 2 + 2 + 1 + 1) + (dbl ? 4 * 256 + 4 * nn * (1 + 2 + 2 + 1) : 0);
-  int rc = ofx_ensure_buffer(h, &h->aux, &h->aux_bytes, need);
+  TargetsWs W;
+  int rc = carve(h, &h->aux, &h->aux_bytes, false, who, [&](Arena &A) { targets_layout(A, (size_t)n, dbl, W); });
   if (rc) return rc;
-  Arena A{(char *)h->aux, 0, need};
-  float *vec_prev = A.f(8 * nn), *vec_next = A.f(8 * nn);
-  int32_t *probe = (int32_t *)A.f(2 * nn);
-  float *act_prev = A.f(2 * nn), *act_next = A.f(2 * nn), *probe_prev = A.f(nn), *max_next = A.f(nn);
-  hipLaunchKernelGGL(k_dqn_unpack, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, vec_prev, vec_next, probe);
+  hipLaunchKernelGGL(k_dqn_unpack, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, W.vec_prev, W.vec_next, W.probe);
   OFX_HIP(hipGetLastError());
   // q_sa = p_sp = NULL: the caller only wants the targets (ofx_dqn_fit's own forward gives the current values) - the forward
   // on `state` is skipped
-  if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, vec_prev, act_prev, nullptr, nullptr, nullptr, probe, probe_prev)))
+  if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, W.vec_prev, W.act_prev, nullptr, nullptr, nullptr, W.probe, W.probe_prev)))
     return rc;
   if (dbl) {
-    int32_t *sel_action = (int32_t *)A.f(nn), *sel_pointer = (int32_t *)A.f(2 * nn);
-    float *act_tgt = A.f(2 * nn), *probe_tgt = A.f(nn);
     // online first (the pinned slot when `weights` is the pinned blob), then the target through prep_tmp
-    if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, nullptr, sel_action, sel_pointer, nullptr, nullptr, nullptr)))
+    if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, W.vec_next, nullptr, W.sel_action, W.sel_pointer, nullptr, nullptr, nullptr)))
       return rc;
-    if ((rc = ofx_policy_forward_obs(h, target, n, bits_next, vec_next, act_tgt, nullptr, nullptr, nullptr, sel_pointer, probe_tgt)))
+    if ((rc = ofx_policy_forward_obs(h, target, n, bits_next, W.vec_next, W.act_tgt, nullptr, nullptr, nullptr, W.sel_pointer, W.probe_tgt)))
       return rc;
-    hipLaunchKernelGGL(k_dqn_targets_double, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev,
-                       probe_prev, sel_action, act_tgt, probe_tgt, q_sa, p_sp, y_act, y_ptr, ret, disc);
+    hipLaunchKernelGGL(k_dqn_targets_double, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev,
+                       W.probe_prev, W.sel_action, W.act_tgt, W.probe_tgt, q_sa, p_sp, y_act, y_ptr, ret, disc);
     OFX_HIP(hipGetLastError());
     return OFX_OK;
   }
-  if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, nullptr, max_next, nullptr, nullptr)))
+  if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, W.vec_next, W.act_next, nullptr, nullptr, W.max_next, nullptr, nullptr)))
     return rc;
-  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, act_prev, probe_prev,
-                     act_next, max_next, q_sa, p_sp, y_act, y_ptr, ret, disc);
+  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev, W.probe_prev,
+                     W.act_next, W.max_next, q_sa, p_sp, y_act, y_ptr, ret, disc);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -904,85 +904,89 @@ extern "C" int ofx_policy_blend_weights(ofx_handle *h, float *dst, const float *
   return ofx_policy_weights_updated(h, dst);
 }
 
-// The tail of a fit step, after the gradients: Adam on the trained tensors, the moving BatchNorm statistics from the batch
-// statistics (tstat / ustat: trunk / head-2 layers), the loss read back (a synchronisation), a pinned blob prepared again.
-// ofx_dqn_fit_robust (R.clip_norm > 0 or R.grad_norm_host given): the gradient's global norm and the clip factor go to
-// loss[2] / loss[3] - the slot is 64 floats - so the copy that fetches the loss fetches the norm too; with a clip, Adam
-// reads the factor from there.  npart: kNormBlocks doubles.
-struct FitRobust {
-  float huber_delta = 0.f, clip_norm = 0.f;
-  float *grad_norm_host = nullptr;
+// One fit step, as the extern "C" entries hand it to the drivers.  Two forms of the targets: the sparse one of ofx_dqn_fit
+// (one error per head and sample: y_act / y_ptr, inputs = `state`) and the dense one of ofx_dqn_fit_reference (t1 [n][2] /
+// t2 [n][400][400] whole target tensors, inputs = next_state's maps + the rows' next_state head).  Everything from
+// row_weight on belongs to the sparse form and is off by default.
+struct FitCall {
+  float *weights = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+  int32_t step = 1, n = 0;
+  float lr = 0.f;
+  const ofx_transition *rows = nullptr;
+  const void *bits = nullptr;                                            // the input maps [n][2][5000] words
+  const float *y_act = nullptr, *y_ptr = nullptr, *t1 = nullptr, *t2 = nullptr;   // sparse / dense targets
+  float *grad_out = nullptr, *loss_host = nullptr;                       // either may be null
+  const float *row_weight = nullptr;                                     // per-row loss weights and the rows' errors
+  float *td_out = nullptr, *grad_norm_host = nullptr;                    // (ofx_dqn_fit_weighted); the norm's read-back
+  float huber_delta = 0.f, clip_norm = 0.f, scale = 1.f;                 // ofx_dqn_fit_robust; tail's factor
   // the split fit.  acc (ofx_dqn_grad): the drivers stop after the gradient and hand it to fit_accumulate instead of the
-  // update.  tail (ofx_dqn_apply): `grad` is an accumulator, tail its last OFX_ACC_TAIL floats, scale its factor.
+  // update.  tail (ofx_dqn_apply): the gradient is an accumulator, tail its last OFX_ACC_TAIL floats, scale its factor.
   float *acc = nullptr;
-  int acc_reset = 0;
   const float *tail = nullptr;
-  float scale = 1.f;
+  int acc_reset = 0;
   bool norm() const { return clip_norm > 0.f || grad_norm_host; }
 };
-static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, float *weights, const float *grad, float *adam_m,
-                            float *adam_v, int32_t step, float lr, const float *const *tstat, const float *const *ustat,
-                            float *loss, float *loss_host, const FitRobust &R, double *npart) {
+
+// The tail of a fit step, after the gradients: Adam on the trained tensors, the moving BatchNorm statistics from the batch
+// statistics (tstat / ustat: trunk / head-2 layers), the loss read back (a synchronisation), a pinned blob prepared again.
+// ofx_dqn_fit_robust (C.clip_norm > 0 or C.grad_norm_host given): the gradient's global norm and the clip factor go to
+// loss[2] / loss[3] - the slot is 64 floats - so the copy that fetches the loss fetches the norm too; with a clip, Adam
+// reads the factor from there.  npart: kNormBlocks doubles.
+static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, const FitCall &C, const float *grad,
+                            const float *const *tstat, const float *const *ustat, float *loss, double *npart) {
   hipStream_t st = h->stream;
+  float *weights = C.weights;
   const float b1 = 0.9f, b2 = 0.999f;
-  const float lr_t = lr * sqrtf(1.f - powf(b2, (float)step)) / (1.f - powf(b1, (float)step));
-  const bool scaled = R.clip_norm > 0.f || (R.tail && R.scale != 1.f);   // Adam reads its factor from loss[3]
-  if (R.tail) {     // the same norm pass, then the norm, the factor and the losses times scale (t_apply_factor)
-    if (R.norm()) hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
-    hipLaunchKernelGGL(t_apply_factor, dim3(1), dim3(64), 0, st, R.norm() ? kNormBlocks : 0, npart, R.clip_norm, R.scale,
-                       R.tail, loss);
+  const float lr_t = C.lr * sqrtf(1.f - powf(b2, (float)C.step)) / (1.f - powf(b1, (float)C.step));
+  const bool scaled = C.clip_norm > 0.f || (C.tail && C.scale != 1.f);   // Adam reads its factor from loss[3]
+  if (C.tail) {     // the same norm pass, then the norm, the factor and the losses times scale (t_apply_factor)
+    if (C.norm()) hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
+    hipLaunchKernelGGL(t_apply_factor, dim3(1), dim3(64), 0, st, C.norm() ? kNormBlocks : 0, npart, C.clip_norm, C.scale,
+                       C.tail, loss);
     OFX_HIP(hipGetLastError());
-  } else if (R.norm()) {   // untrained slots of the gradient blob are zero: one pass over all of it
+  } else if (C.norm()) {   // untrained slots of the gradient blob are zero: one pass over all of it
     hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
-    hipLaunchKernelGGL(t_clip_scale, dim3(1), dim3(64), 0, st, kNormBlocks, npart, R.clip_norm, loss + 2);
+    hipLaunchKernelGGL(t_clip_scale, dim3(1), dim3(64), 0, st, kNormBlocks, npart, C.clip_norm, loss + 2);
     OFX_HIP(hipGetLastError());
   }
   for (int t = 0; t < L.n_tensors; t++) {
     if (!ofx_blob_trained(t)) continue;  // moving mean / variance
     if (scaled)
       K(t_adam_scaled, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t],
-        adam_m + L.offset[t], adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f, loss + 3);
+        C.adam_m + L.offset[t], C.adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f, loss + 3);
     else
-      K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], adam_m + L.offset[t],
-        adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
+      K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], C.adam_m + L.offset[t],
+        C.adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
   }
-  if (R.tail) {
-    for (int i = 0; i < 4; i++)
-      hipLaunchKernelGGL(t_moving_scaled, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
-                         weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i], R.scale);
-    for (int j = 0; j < 3; j++)
-      hipLaunchKernelGGL(t_moving_scaled, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
-                         weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j], R.scale);
-  } else {
-    for (int i = 0; i < 4; i++)
-      hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
-                         weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i]);
-    for (int j = 0; j < 3; j++)
-      hipLaunchKernelGGL(t_moving, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
-                         weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j]);
-  }
+  // (a fit's own statistics: scale 1, the bits of the unscaled expression)
+  for (int i = 0; i < 4; i++)
+    hipLaunchKernelGGL(t_moving_scaled, dim3(1), dim3(64), 0, st, 8, weights + L.offset[ofx_t_trunk(i, OFX_T_MEAN)],
+                       weights + L.offset[ofx_t_trunk(i, OFX_T_VAR)], tstat[i], C.scale);
+  for (int j = 0; j < 3; j++)
+    hipLaunchKernelGGL(t_moving_scaled, dim3(1), dim3(64), 0, st, kUpCout[j], weights + L.offset[ofx_t_up(j, OFX_T_MEAN)],
+                       weights + L.offset[ofx_t_up(j, OFX_T_VAR)], ustat[j], C.scale);
   OFX_HIP(hipGetLastError());
   float lh[4] = {0.f, 0.f, 0.f, 0.f};   // {loss1, loss2, norm, clip factor}
-  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(float) * (R.norm() ? 4 : 2), hipMemcpyDeviceToHost, st));
+  OFX_HIP(hipMemcpyAsync(lh, loss, sizeof(float) * (C.norm() ? 4 : 2), hipMemcpyDeviceToHost, st));
   OFX_HIP(hipStreamSynchronize(st));
-  if (loss_host) { loss_host[0] = lh[0]; loss_host[1] = lh[1]; }
-  if (R.grad_norm_host) *R.grad_norm_host = lh[2];
+  if (C.loss_host) { C.loss_host[0] = lh[0]; C.loss_host[1] = lh[1]; }
+  if (C.grad_norm_host) *C.grad_norm_host = lh[2];
   return ofx_policy_weights_updated(h, weights);
 }
 
 // The tail of ofx_dqn_grad, in place of fit_apply_update: this micro-batch's gradient, batch statistics and losses into
 // the accumulator (t_accumulate).  Nothing of the weights, the Adam moments or a pinned blob's preparation is touched.
-static int fit_accumulate(ofx_handle *h, const ofx_policy_desc &L, const float *grad, const float *const *tstat,
-                          const float *const *ustat, const float *loss, float *loss_host, const FitRobust &R) {
+static int fit_accumulate(ofx_handle *h, const ofx_policy_desc &L, const FitCall &C, const float *grad,
+                          const float *const *tstat, const float *const *ustat, const float *loss) {
   hipStream_t st = h->stream;
   AccSrc S;
   for (int i = 0; i < 4; i++) { S.stat[i] = tstat[i]; S.stat_n[i] = 2 * 8; }
   for (int j = 0; j < 3; j++) { S.stat[4 + j] = ustat[j]; S.stat_n[4 + j] = 2 * kUpCout[j]; }
   S.loss = loss;
   const size_t total = (size_t)L.n_floats + OFX_ACC_TAIL;
-  K(t_accumulate, total, (size_t)L.n_floats, grad, S, R.acc, R.acc_reset);
-  if (loss_host) {
-    OFX_HIP(hipMemcpyAsync(loss_host, loss, sizeof(float) * 2, hipMemcpyDeviceToHost, st));
+  K(t_accumulate, total, (size_t)L.n_floats, grad, S, C.acc, C.acc_reset);
+  if (C.loss_host) {
+    OFX_HIP(hipMemcpyAsync(C.loss_host, loss, sizeof(float) * 2, hipMemcpyDeviceToHost, st));
     OFX_HIP(hipStreamSynchronize(st));
   }
   return OFX_OK;
@@ -990,350 +994,334 @@ static int fit_accumulate(ofx_handle *h, const ofx_policy_desc &L, const float *
 
 // The lean form of one fit step (default; ofx_fit.hip): the same graph, loss and update as dqn_fit_impl below with only
 // z of every convolution in HBM.  The dense layers, the loss and Adam are the plain form's kernels.
-static int dqn_fit_lean(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
-                        const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
-                        const float *t1, const float *t2, float *grad_out, float *loss_host, const float *row_weight,
-                        float *td_out, const FitRobust &R) {
-  const bool dense = t1 != nullptr;
+static const int tS[4] = {400, 200, 100, 50}, uS[3] = {50, 100, 200};   // map sizes of the trunk / head-2 layers
+struct LeanWs {
+  float *grad, *loss, *zero, *wtr, *lpart, *weff, *gpatch, *luts, *w1t;
+  double *part, *sums, *fpart, *pscratch, *cpart, *fpart2, *npart;
+  float *tp[3], *tz[4], *tg[4], *tstat[4], *tact[4], *uz[3], *ug[3], *ustat[3], *uact[3];
+  float *o2, *do2, *p3, *f, *d1, *d2, *o1, *u0, *gu0, *do1, *dd1, *dd2, *df, *dp3;
+};
+static void lean_layout(Arena &A, int n, size_t n_floats, LeanWs &W) {
+  const size_t N = (size_t)n;
+  W.grad = A.f(n_floats); W.loss = A.f(64); W.zero = A.f(64); W.wtr = A.f(576);   // loss, zero: adjacent, one memset clears both
+  W.lpart = A.f(2 * N + 4096); W.part = A.d(ofx_fit_part_doubles()); W.sums = A.d(32); W.weff = A.f(ofx_fit_out_floats());
+  W.fpart = A.d(ofx_fit_out_doubles(n)); W.pscratch = A.d(ofx_fit_point_doubles(n));
+  W.gpatch = A.f(N * 128);   // textbook targets: all of the last head layer's g that is not zero
+  for (int i = 0; i < 3; i++) W.tp[i] = A.f(N * 8 * tS[i + 1] * tS[i + 1]);   // pooled activation
+  for (int i = 0; i < 4; i++) {   // z, g (layer 0 has neither), stat (+ the mean's low parts), act
+    W.tz[i] = i ? A.f(N * 8 * tS[i] * tS[i]) : nullptr; W.tg[i] = i ? A.f(N * 8 * tS[i] * tS[i]) : nullptr; W.tstat[i] = A.f(32); W.tact[i] = A.f(16);
+  }
+  W.luts = A.f(ofx_fit_first_floats()); W.w1t = A.f(5008 * 100);
+  W.cpart = A.d(ofx_fit_first_doubles(n)); W.fpart2 = A.d(ofx_fit_first_part_doubles(n));   // correlation, first-layers backward
+  for (int j = 0; j < 3; j++) { W.uz[j] = A.f(N * kUpCout[j] * uS[j] * uS[j]); W.ug[j] = A.f(N * kUpCout[j] * uS[j] * uS[j]); W.ustat[j] = A.f(32); W.uact[j] = A.f(16); }
+  W.o2 = A.f(N * 160000); W.do2 = A.f(N * 160000);
+  W.p3 = A.f(N * 5000); W.f = A.f(N * 5008); W.d1 = A.f(N * 100); W.d2 = A.f(N * 50); W.o1 = A.f(N * 2); W.u0 = A.f(N * 625);
+  W.gu0 = A.f(N * 625); W.do1 = A.f(N * 2); W.dd1 = A.f(N * 100); W.dd2 = A.f(N * 50); W.df = A.f(N * 5008); W.dp3 = A.f(N * 5000);
+  W.npart = A.d(kNormBlocks);   // gradient-norm partials
+}
+static int dqn_fit_lean(ofx_handle *h, const FitCall &C) {
+  const bool dense = C.t1 != nullptr;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
   ofx_policy_desc L;
   int rc = ofx_policy_layout(h, &L);
   if (rc) return rc;
+  const int n = C.n;
+  const ofx_transition *rows = C.rows;
+  const void *bits_prev = C.bits;   // (the maps of `state`; dense targets: of next_state)
   if (!dense && (rc = refuse_pads(h, n, rows, "ofx_dqn_fit"))) return rc;   // (dense targets: ofx_dqn_fit_reference has checked)
   const size_t N = (size_t)n;
   const int legacy = h->opt_bilinear_legacy;
-  static const int tS[4] = {400, 200, 100, 50}, uS[3] = {50, 100, 200};
-  size_t need = 0;
-  auto sz = [&](size_t bytes) { need += (bytes + 255) & ~(size_t)255; };
-  for (int i = 1; i < 4; i++) { sz(4 * N * 8 * tS[i] * tS[i]); sz(4 * N * 8 * tS[i] * tS[i]); }  // z, g (layer 0 has neither)
-  sz(4 * ofx_fit_first_floats()); sz(4 * 5008 * 100);
-  sz(8 * ofx_fit_first_doubles(n)); sz(8 * ofx_fit_first_part_doubles(n));                                 // correlation, first-layers backward
-  for (int i = 0; i < 3; i++) sz(4 * N * 8 * tS[i + 1] * tS[i + 1]);                                       // pooled activation
-  for (int j = 0; j < 3; j++) { sz(4 * N * kUpCout[j] * uS[j] * uS[j]); sz(4 * N * kUpCout[j] * uS[j] * uS[j]); }
-  sz(4 * N * 160000); sz(4 * N * 160000);                                                                  // o2, do2
-  sz(4 * N * 5000); sz(4 * N * 5008); sz(4 * N * 100); sz(4 * N * 50); sz(4 * N * 2); sz(4 * N * 625);      // p3 f d1 d2 o1 u0
-  sz(4 * N * 625); sz(4 * N * 2); sz(4 * N * 100); sz(4 * N * 50); sz(4 * N * 5008); sz(4 * N * 5000);      // gu0 do1 dd1 dd2 df dp3
-  sz(4 * (size_t)L.n_floats); sz(4 * 64); sz(4 * 64); sz(4 * 576); sz(4 * (2 * N + 4096)); sz(8 * ofx_fit_part_doubles()); sz(8 * 32);
-  sz(4 * ofx_fit_out_floats()); sz(8 * ofx_fit_out_doubles(n)); sz(8 * ofx_fit_point_doubles(n)); sz(4 * N * 128);
-  sz(8 * kNormBlocks);                                                                                     // gradient-norm partials
-  for (int k = 0; k < 7; k++) { sz(4 * 32); sz(4 * 16); }   // stat (+ the mean's low parts), act
-  if ((rc = keep_workspace(h, &h->fitws, &h->fitws_bytes, need))) return rc;
-  Arena A{(char *)h->fitws, 0, need};
-  auto T = [&](int t) { return weights + L.offset[t]; };
-  float *grad = A.f(L.n_floats);
-  OFX_HIP(hipMemsetAsync(grad, 0, sizeof(float) * L.n_floats, st));
-  auto G = [&](int t) { return grad + L.offset[t]; };
-  float *loss = A.f(64), *zero = A.f(64), *wtr = A.f(576);
-  OFX_HIP(hipMemsetAsync(loss, 0, 2 * 256, st));   // loss and zero: adjacent 256-byte slots of the arena
-  float *lpart = A.f(2 * N + 4096);
-  double *part = A.d(ofx_fit_part_doubles()), *sums = A.d(32);
-  float *weff = A.f(ofx_fit_out_floats());
-  double *fpart = A.d(ofx_fit_out_doubles(n)), *pscratch = A.d(ofx_fit_point_doubles(n));
-  float *gpatch = A.f(N * 128);   // textbook targets: all of the last head layer's g that is not zero
-  float *tz[4], *tg[4], *tstat[4], *tact[4], *uz[3], *ug[3], *ustat[3], *uact[3], *tp[3];
-  for (int i = 0; i < 3; i++) tp[i] = A.f(N * 8 * tS[i + 1] * tS[i + 1]);
-  for (int i = 0; i < 4; i++) { tz[i] = i ? A.f(N * 8 * tS[i] * tS[i]) : nullptr; tg[i] = i ? A.f(N * 8 * tS[i] * tS[i]) : nullptr; tstat[i] = A.f(32); tact[i] = A.f(16); }
-  float *luts = A.f(ofx_fit_first_floats()), *w1t = A.f(5008 * 100);
-  double *cpart = A.d(ofx_fit_first_doubles(n)), *fpart2 = A.d(ofx_fit_first_part_doubles(n));
-  for (int j = 0; j < 3; j++) { uz[j] = A.f(N * kUpCout[j] * uS[j] * uS[j]); ug[j] = A.f(N * kUpCout[j] * uS[j] * uS[j]); ustat[j] = A.f(32); uact[j] = A.f(16); }
-  float *o2 = A.f(N * 160000), *do2 = A.f(N * 160000);
-  float *p3 = A.f(N * 5000), *f = A.f(N * 5008), *d1 = A.f(N * 100), *d2 = A.f(N * 50), *o1 = A.f(N * 2), *u0 = A.f(N * 625);
-  float *gu0 = A.f(N * 625), *do1 = A.f(N * 2), *dd1 = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008), *dp3 = A.f(N * 5000);
-  double *npart = A.d(kNormBlocks);
-  if (A.over) { ofx_set_error("ofx_dqn_fit: internal workspace sized too small"); return OFX_ERR_STATE; }
+  LeanWs W;
+  if ((rc = carve(h, &h->fitws, &h->fitws_bytes, true, "ofx_dqn_fit", [&](Arena &A) { lean_layout(A, n, (size_t)L.n_floats, W); })))
+    return rc;
+  auto T = [&](int t) { return C.weights + L.offset[t]; };
+  auto G = [&](int t) { return W.grad + L.offset[t]; };
+  OFX_HIP(hipMemsetAsync(W.grad, 0, sizeof(float) * L.n_floats, st));
+  OFX_HIP(hipMemsetAsync(W.loss, 0, 2 * 256, st));   // loss and zero
   int nb = 0;
   // input of trunk layer i: the forward pools the previous layer's z on the fly and KEEPS the pooled activation (a quarter
   // of z's bytes); the weight gradient reads that plane back instead of pooling z a second time
   auto trunk_src = [&](int i, bool backward) {
     if (i == 0) return ofx_fit_src{OFX_FIT_SRC_BITS, nullptr, bits_prev, nullptr, 400, 400, legacy};
-    if (backward || i == 1) return ofx_fit_src{OFX_FIT_SRC_PLANE, nullptr, tp[i - 1], zero, tS[i], tS[i], legacy};
-    return ofx_fit_src{OFX_FIT_SRC_POOL, tp[i - 1], tz[i - 1], tact[i - 1], tS[i - 1], tS[i - 1], legacy};
+    if (backward || i == 1) return ofx_fit_src{OFX_FIT_SRC_PLANE, nullptr, W.tp[i - 1], W.zero, tS[i], tS[i], legacy};
+    return ofx_fit_src{OFX_FIT_SRC_POOL, W.tp[i - 1], W.tz[i - 1], W.tact[i - 1], tS[i - 1], tS[i - 1], legacy};
   };
   auto head_src = [&](int j) {   // input of head-2 layer j (3 = the output convolution)
-    return j == 0 ? ofx_fit_src{OFX_FIT_SRC_UPRAW, nullptr, u0, nullptr, 25, 25, legacy}
-                  : ofx_fit_src{OFX_FIT_SRC_UP, nullptr, uz[j - 1], uact[j - 1], uS[j - 1], uS[j - 1], legacy};
+    return j == 0 ? ofx_fit_src{OFX_FIT_SRC_UPRAW, nullptr, W.u0, nullptr, 25, 25, legacy}
+                  : ofx_fit_src{OFX_FIT_SRC_UP, nullptr, W.uz[j - 1], W.uact[j - 1], uS[j - 1], uS[j - 1], legacy};
   };
 
   // ---- forward (training mode) ----
   // the first layer is never materialised: statistics from the autocorrelation of the bit maps, p0 through the table kernel
-  if ((rc = ofx_fit_first_fwd(h, n, bits_prev, T(ofx_t_trunk(0)), T(ofx_t_trunk(0, OFX_T_BIAS)), T(ofx_t_trunk(0, OFX_T_GAMMA)), T(ofx_t_trunk(0, OFX_T_BETA)), cpart, tstat[0], tact[0], luts, tp[0]))) return rc;
+  if ((rc = ofx_fit_first_fwd(h, n, bits_prev, T(ofx_t_trunk(0)), T(ofx_t_trunk(0, OFX_T_BIAS)), T(ofx_t_trunk(0, OFX_T_GAMMA)), T(ofx_t_trunk(0, OFX_T_BETA)), W.cpart, W.tstat[0], W.tact[0], W.luts, W.tp[0]))) return rc;
   for (int i = 1; i < 4; i++) {
     const int s = tS[i];
-    if ((rc = ofx_fit_conv_fwd(st, n, kTrunkCin[i], 8, s, s, trunk_src(i, false), T(ofx_t_trunk(i)), T(ofx_t_trunk(i, OFX_T_BIAS)), tz[i], part, &nb))) return rc;
-    if ((rc = ofx_fit_finish(st, nb, 8, (double)N * s * s, part, T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), nullptr, tstat[i], tact[i]))) return rc;
+    if ((rc = ofx_fit_conv_fwd(st, n, kTrunkCin[i], 8, s, s, trunk_src(i, false), T(ofx_t_trunk(i)), T(ofx_t_trunk(i, OFX_T_BIAS)), W.tz[i], W.part, &nb))) return rc;
+    if ((rc = ofx_fit_finish(st, nb, 8, (double)N * s * s, W.part, T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), nullptr, W.tstat[i], W.tact[i]))) return rc;
   }
-  if ((rc = ofx_fit_pool_act(st, n, 8, 50, 50, tz[3], tact[3], p3))) return rc;
-  K(t_concat_fwd, N * 5008, n, rows, p3, f, dense ? 1 : 0);
-  if ((rc = ofx_launch_gemm(h, f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), d1, 100, n, 100, 5008, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), d2, 50, n, 50, 100, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), o1, 2, n, 2, 50, 0))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), u0, 625, n, 625, 100, 1))) return rc;
+  if ((rc = ofx_fit_pool_act(st, n, 8, 50, 50, W.tz[3], W.tact[3], W.p3))) return rc;
+  K(t_concat_fwd, N * 5008, n, rows, W.p3, W.f, dense ? 1 : 0);
+  if ((rc = ofx_launch_gemm(h, W.f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), W.d1, 100, n, 100, 5008, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), W.d2, 50, n, 50, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, W.d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), W.o1, 2, n, 2, 50, 0))) return rc;
+  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), W.u0, 625, n, 625, 100, 1))) return rc;
   for (int j = 0; j < 3; j++) {
     const int s = uS[j];
-    if ((rc = ofx_fit_conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), uz[j], part, &nb))) return rc;
-    if ((rc = ofx_fit_finish(st, nb, kUpCout[j], (double)N * s * s, part, T(ofx_t_up(j, OFX_T_GAMMA)), T(ofx_t_up(j, OFX_T_BETA)), nullptr, ustat[j], uact[j]))) return rc;
+    if ((rc = ofx_fit_conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), W.uz[j], W.part, &nb))) return rc;
+    if ((rc = ofx_fit_finish(st, nb, kUpCout[j], (double)N * s * s, W.part, T(ofx_t_up(j, OFX_T_GAMMA)), T(ofx_t_up(j, OFX_T_BETA)), nullptr, W.ustat[j], W.uact[j]))) return rc;
   }
-  if (dense && (rc = ofx_fit_out_fwd(st, n, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o2, weff))) return rc;
+  if (dense && (rc = ofx_fit_out_fwd(st, n, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), W.o2, W.weff))) return rc;
 
   // ---- loss seeds ----
-  OFX_HIP(hipMemsetAsync(do1, 0, N * 2 * 4, st));
+  OFX_HIP(hipMemsetAsync(W.do1, 0, N * 2 * 4, st));
   if (!dense) {
     // one error per sample on the heat map: the output convolution at the pointer only, its gradients and the last head
     // layer's g from that one pixel (ofx_fit.hip, "the top of head 2 for the textbook targets")
-    float *o2p = o2, *d2p = o2 + N;                          // [n] each: the dense planes are not used on this path
-    if ((rc = ofx_fit_top_point(st, n, rows, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o1, y_act, y_ptr, ustat[2], o2p, do1, d2p, lpart, gpatch,
-                                pscratch, sums, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1), row_weight, td_out, R.huber_delta))) return rc;
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
+    float *o2p = W.o2, *d2p = W.o2 + N;                      // [n] each: the dense planes are not used on this path
+    if ((rc = ofx_fit_top_point(st, n, rows, head_src(3), T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), W.o1, C.y_act, C.y_ptr, W.ustat[2], o2p, W.do1, d2p, W.lpart, W.gpatch,
+                                W.pscratch, W.sums, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1), C.row_weight, C.td_out, C.huber_delta))) return rc;
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, W.lpart, W.loss);
     OFX_HIP(hipGetLastError());
-  } else if (dense) {
+  } else {
     const int nb1 = (int)((N * 2 + 255) / 256), nb2 = (int)(N * 160000 / 256 > 2048 ? 2048 : (N * 160000 + 255) / 256);
-    hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), o1, t1, do1, lpart);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, lpart, loss);
-    hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), o2, t2, do2, lpart + 2048);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, lpart + 2048, loss + 1);
+    hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), W.o1, C.t1, W.do1, W.lpart);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, W.lpart, W.loss);
+    hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), W.o2, C.t2, W.do2, W.lpart + 2048);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, W.lpart + 2048, W.loss + 1);
     OFX_HIP(hipGetLastError());
   }
 
   // ---- backward: head 2 ----
-  if (dense && (rc = ofx_fit_out_bw(st, n, head_src(3), do2, part, fpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1)))) return rc;
-  const float *dzn = do2;
+  if (dense && (rc = ofx_fit_out_bw(st, n, head_src(3), W.do2, W.part, W.fpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1)))) return rc;
+  const float *dzn = W.do2;
   for (int j = 2; j >= 0; j--) {
     const int s = uS[j];
     if (j < 2 || dense) {   // (the textbook path has the last layer's g and its sums already)
-      if ((rc = ofx_fit_b1_up(st, n, kUpCout[j], kUpCout[j + 1], s, s, 1, dzn, T(ofx_t_up(j + 1)), uz[j], ustat[j], uact[j], legacy, ug[j], part, &nb, zero, wtr))) return rc;
-      if ((rc = ofx_fit_finish(st, nb, kUpCout[j], 1.0, part, nullptr, nullptr, sums, nullptr, nullptr))) return rc;
+      if ((rc = ofx_fit_b1_up(st, n, kUpCout[j], kUpCout[j + 1], s, s, 1, dzn, T(ofx_t_up(j + 1)), W.uz[j], W.ustat[j], W.uact[j], legacy, W.ug[j], W.part, &nb, W.zero, W.wtr))) return rc;
+      if ((rc = ofx_fit_finish(st, nb, kUpCout[j], 1.0, W.part, nullptr, nullptr, W.sums, nullptr, nullptr))) return rc;
     }
     const bool patch = j == 2 && !dense;   // (g of the last layer is a 4 x 4 patch per sample there: not read, dz written)
-    if ((rc = ofx_fit_bw(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), 1, ug[j], uz[j], ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), sums, part,
-                         G(ofx_t_up(j)), G(ofx_t_up(j, OFX_T_BIAS)), G(ofx_t_up(j, OFX_T_GAMMA)), G(ofx_t_up(j, OFX_T_BETA)), patch ? gpatch : nullptr,
+    if ((rc = ofx_fit_bw(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), 1, W.ug[j], W.uz[j], W.ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), W.sums, W.part,
+                         G(ofx_t_up(j)), G(ofx_t_up(j, OFX_T_BIAS)), G(ofx_t_up(j, OFX_T_GAMMA)), G(ofx_t_up(j, OFX_T_BETA)), patch ? W.gpatch : nullptr,
                          patch ? rows : nullptr))) return rc;
-    dzn = ug[j];
+    dzn = W.ug[j];
   }
-  if ((rc = ofx_fit_b1_up(st, n, 1, 2, 25, 25, 0, dzn, T(ofx_t_up(0)), u0, nullptr, nullptr, legacy, gu0, part, &nb, zero, wtr))) return rc;
+  if ((rc = ofx_fit_b1_up(st, n, 1, 2, 25, 25, 0, dzn, T(ofx_t_up(0)), W.u0, nullptr, nullptr, legacy, W.gu0, W.part, &nb, W.zero, W.wtr))) return rc;
   // gu0 = d u0 [n][625], already behind u0's ReLU mask
-  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, gu0, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, gu0, T(OFX_T_UPDENSE), dd1, 0);
+  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, W.d1, W.gu0, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, W.gu0, T(OFX_T_UPDENSE), W.dd1, 0);
   // ---- backward: head 1 ----
-  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(OFX_T_OUT1), dd2, 0);
-  K(t_relu_mask, N * 50, N * 50, d2, dd2);
-  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(OFX_T_DENSE2), dd1, 1);
+  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, W.d2, W.do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, W.do1, T(OFX_T_OUT1), W.dd2, 0);
+  K(t_relu_mask, N * 50, N * 50, W.d2, W.dd2);
+  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, W.d1, W.dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, W.dd2, T(OFX_T_DENSE2), W.dd1, 1);
   // ---- dense1 + trunk ----
-  K(t_relu_mask, N * 100, N * 100, d1, dd1);
-  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
+  K(t_relu_mask, N * 100, N * 100, W.d1, W.dd1);
+  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, W.f, W.dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
   // d f = dd1 x W1^T on the f32 MFMA GEMM (the 5008 x 100 kernel transposed first): 2 x 5008 x 100 FLOP per row
-  hipLaunchKernelGGL(t_transpose, dim3((100 + 31) / 32, (5008 + 31) / 32), dim3(256), 0, st, 5008, 100, T(OFX_T_DENSE1), w1t);
+  hipLaunchKernelGGL(t_transpose, dim3((100 + 31) / 32, (5008 + 31) / 32), dim3(256), 0, st, 5008, 100, T(OFX_T_DENSE1), W.w1t);
   OFX_HIP(hipGetLastError());
-  if ((rc = ofx_launch_gemm(h, dd1, 100, w1t, 5008, nullptr, df, 5008, n, 5008, 100, 0))) return rc;
-  K(t_concat_bwd, N * 5000, n, df, dp3);
-  dzn = dp3;
+  if ((rc = ofx_launch_gemm(h, W.dd1, 100, W.w1t, 5008, nullptr, W.df, 5008, n, 5008, 100, 0))) return rc;
+  K(t_concat_bwd, N * 5000, n, W.df, W.dp3);
+  dzn = W.dp3;
   for (int i = 3; i >= 0; i--) {
     const int s = tS[i];
-    if ((rc = ofx_fit_b1_pool(st, n, s, s, i < 3, dzn, i < 3 ? T(ofx_t_trunk(i + 1)) : nullptr, tz[i], tstat[i], tact[i], tg[i], part, &nb, wtr, zero))) return rc;
-    if ((rc = ofx_fit_finish(st, nb, 8, 1.0, part, nullptr, nullptr, sums, nullptr, nullptr))) return rc;
+    if ((rc = ofx_fit_b1_pool(st, n, s, s, i < 3, dzn, i < 3 ? T(ofx_t_trunk(i + 1)) : nullptr, W.tz[i], W.tstat[i], W.tact[i], W.tg[i], W.part, &nb, W.wtr, W.zero))) return rc;
+    if ((rc = ofx_fit_finish(st, nb, 8, 1.0, W.part, nullptr, nullptr, W.sums, nullptr, nullptr))) return rc;
     if (i == 1) {
       // the first two layers: the first has neither z, g nor dz, the second's dz is never stored - only the windows that see
       // a set bit are visited (ofx_fit.hip, f_first_bwd)
-      if ((rc = ofx_fit_first_bwd(st, n, bits_prev, tg[1], tz[1], tstat[1], T(ofx_t_trunk(1, OFX_T_GAMMA)), sums, T(ofx_t_trunk(1)), tp[0], luts, T(ofx_t_trunk(0)), T(ofx_t_trunk(0, OFX_T_BIAS)), tstat[0],
-                                  T(ofx_t_trunk(0, OFX_T_GAMMA)), T(ofx_t_trunk(0, OFX_T_BETA)), fpart2, cpart, G(ofx_t_trunk(0)), G(ofx_t_trunk(0, OFX_T_BIAS)), G(ofx_t_trunk(0, OFX_T_GAMMA)), G(ofx_t_trunk(0, OFX_T_BETA)), G(ofx_t_trunk(1)), G(ofx_t_trunk(1, OFX_T_BIAS)), G(ofx_t_trunk(1, OFX_T_GAMMA)), G(ofx_t_trunk(1, OFX_T_BETA))))) return rc;
+      if ((rc = ofx_fit_first_bwd(st, n, bits_prev, W.tg[1], W.tz[1], W.tstat[1], T(ofx_t_trunk(1, OFX_T_GAMMA)), W.sums, T(ofx_t_trunk(1)), W.tp[0], W.luts, T(ofx_t_trunk(0)), T(ofx_t_trunk(0, OFX_T_BIAS)), W.tstat[0],
+                                  T(ofx_t_trunk(0, OFX_T_GAMMA)), T(ofx_t_trunk(0, OFX_T_BETA)), W.fpart2, W.cpart, G(ofx_t_trunk(0)), G(ofx_t_trunk(0, OFX_T_BIAS)), G(ofx_t_trunk(0, OFX_T_GAMMA)), G(ofx_t_trunk(0, OFX_T_BETA)), G(ofx_t_trunk(1)), G(ofx_t_trunk(1, OFX_T_BIAS)), G(ofx_t_trunk(1, OFX_T_GAMMA)), G(ofx_t_trunk(1, OFX_T_BETA))))) return rc;
       break;
     }
-    if ((rc = ofx_fit_bw(st, n, kTrunkCin[i], 8, s, s, trunk_src(i, true), 1, tg[i], tz[i], tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), sums, part,
+    if ((rc = ofx_fit_bw(st, n, kTrunkCin[i], 8, s, s, trunk_src(i, true), 1, W.tg[i], W.tz[i], W.tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), W.sums, W.part,
                          G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)), G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA))))) return rc;
-    dzn = tg[i];
+    dzn = W.tg[i];
   }
-  if (R.acc) return fit_accumulate(h, L, grad, tstat, ustat, loss, loss_host, R);   // ofx_dqn_grad: gradient only
-  if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
+  if (C.acc) return fit_accumulate(h, L, C, W.grad, W.tstat, W.ustat, W.loss);   // ofx_dqn_grad: gradient only
+  if (C.grad_out) OFX_HIP(hipMemcpyAsync(C.grad_out, W.grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
-  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
+  return fit_apply_update(h, L, C, W.grad, W.tstat, W.ustat, W.loss, W.npart);
 }
 
-// One fit step.  Two forms of the targets: the sparse one of ofx_dqn_fit (one error per head and sample: y_act / y_ptr,
-// inputs = `state`) and the dense one of ofx_dqn_fit_reference (t1 [n][2] / t2 [n][400][400] whole target tensors,
-// inputs = bits_in + the rows' next_state head).
-// row_weight / td_out (sparse form only, either may be null): per-row loss weights and the rows' errors (ofx_dqn_fit_weighted).
-// R (sparse form only): the Huber loss, the gradient-norm clip and the norm's read-back (ofx_dqn_fit_robust); all off by default.
-static int dqn_fit_impl(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
-                        const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
-                        const float *t1, const float *t2, float *grad_out, float *loss_host,
-                        const float *row_weight = nullptr, float *td_out = nullptr, const FitRobust &R = FitRobust()) {
-  if (!h->opt_fit_plain)
-    return dqn_fit_lean(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, t1, t2, grad_out, loss_host,
-                        row_weight, td_out, R);
-  const bool dense = t1 != nullptr;
+// The plain form of one fit step (OFX_OPT_FIT_PLAIN): every tensor of the graph in HBM, one kernel per layer and pass.
+// gA / gB: two gradient scratch planes of the largest size, reused down the backward pass (as are up4 and the
+// activations, once dead).
+struct PlainWs {
+  float *grad, *loss, *lpart;           // lpart: per-sample / per-block loss shares, summed in order
+  double *sums, *spart, *wpart, *npart; // spart: t_chan_sums partials [channel][slice][2]
+  float *x0, *tz[4], *ta[4], *tp[4], *tstat[4], *f, *d1, *d2, *o1, *u0, *uu[3], *uz[3], *ua[3], *ustat[3], *up4, *o2;
+  float *do1, *do2, *gA, *gB, *dd1, *dd2, *df;
+};
+static void plain_layout(Arena &A, size_t N, size_t n_floats, PlainWs &W) {
+  W.grad = A.f(n_floats); W.loss = A.f(64); W.lpart = A.f(2 * N + 4096);
+  W.sums = A.d(16 * 16); W.spart = A.d(16 * 64 * 2); W.wpart = A.d((size_t)kWSlices * 600);
+  W.x0 = A.f(N * 2 * 160000);
+  for (int i = 0; i < 4; i++) {   // trunk: z, activation, pooled activation, batch statistics
+    const size_t per = (size_t)tS[i] * tS[i];
+    W.tz[i] = A.f(N * 8 * per); W.ta[i] = A.f(N * 8 * per); W.tp[i] = A.f(N * 8 * per / 4); W.tstat[i] = A.f(16);
+  }
+  W.f = A.f(N * 5008); W.d1 = A.f(N * 100); W.d2 = A.f(N * 50); W.o1 = A.f(N * 2); W.u0 = A.f(N * 625);
+  for (int j = 0; j < 3; j++) {   // head 2: up-sampled input, z, activation, batch statistics
+    const size_t per = (size_t)uS[j] * uS[j];
+    W.uu[j] = A.f(N * kUpCin[j] * per); W.uz[j] = A.f(N * kUpCout[j] * per); W.ua[j] = A.f(N * kUpCout[j] * per); W.ustat[j] = A.f(16);
+  }
+  W.up4 = A.f(N * 8 * 160000); W.o2 = A.f(N * 160000); W.do1 = A.f(N * 2); W.do2 = A.f(N * 160000);
+  W.gA = A.f(N * 8 * 160000); W.gB = A.f(N * 8 * 160000);   // gradient scratch (largest tensors)
+  W.dd1 = A.f(N * 100); W.dd2 = A.f(N * 50); W.df = A.f(N * 5008); W.npart = A.d(kNormBlocks);
+}
+static int dqn_fit_impl(ofx_handle *h, const FitCall &C) {
+  if (!h->opt_fit_plain) return dqn_fit_lean(h, C);
+  const bool dense = C.t1 != nullptr;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
   ofx_policy_desc L;
   int rc = ofx_policy_layout(h, &L);
   if (rc) return rc;
+  const int n = C.n;
+  const ofx_transition *rows = C.rows;
   if (!dense && (rc = refuse_pads(h, n, rows, "ofx_dqn_fit"))) return rc;   // (dense targets: ofx_dqn_fit_reference has checked)
   const size_t N = (size_t)n;
   const int legacy = h->opt_bilinear_legacy;
-  // activations: trunk sizes 400,200,100,50 (z, a per layer + pooled), head-2 sizes 50,100,200 (+ upsampled inputs)
-  size_t need = 0;
-  auto sz = [&](size_t fl) { need += (fl * 4 + 255) & ~(size_t)255; };
-  sz(N * 2 * 160000);
-  for (int i = 0, s = 400; i < 4; i++, s /= 2) { sz(N * 8 * s * s); sz(N * 8 * s * s); sz(N * 8 * (s / 2) * (s / 2)); sz(N * 8 * s * s); sz(N * 8 * s * s); }
-  sz(N * 5008); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625);
-  for (int j = 0, s = 50; j < 3; j++, s *= 2) { sz(N * kUpCin[j] * s * s); sz(N * kUpCout[j] * s * s); sz(N * kUpCout[j] * s * s); sz(N * kUpCout[j] * s * s); sz(N * kUpCout[j] * s * s); }
-  sz(N * 8 * 160000); sz(N * 160000);               // up4, o2
-  sz(N * 8 * 160000); sz(N * 8 * 160000);           // two gradient scratch planes of the largest size
-  sz(N * 5008); sz(N * 100); sz(N * 100); sz(N * 50); sz(N * 2); sz(N * 625); sz(N * 160000);
-  sz(L.n_floats); sz(64); sz(2 * N + 4096); sz(2 * kNormBlocks);   // (the last: gradient-norm partials, doubles)
-  need += 65536 + 16 * 64 * 8 + 16 * 64 * 2 * 8 + (size_t)kWSlices * 600 * 8;
-  if ((rc = keep_workspace(h, &h->fitws, &h->fitws_bytes, need))) return rc;
-  void *raw = h->fitws;
-  Arena A{(char *)raw, 0, need};
-  auto T = [&](int t) { return weights + L.offset[t]; };
-  float *grad = A.f(L.n_floats);
-  OFX_HIP(hipMemsetAsync(grad, 0, sizeof(float) * L.n_floats, st));
-  float *loss = A.f(64);
-  OFX_HIP(hipMemsetAsync(loss, 0, 64 * sizeof(float), st));
-  float *lpart = A.f(2 * N + 4096);                   // per-sample / per-block loss shares, summed in order
-  double *sums = A.d(16 * 16);
-  double *spart = A.d(16 * 64 * 2);                  // t_chan_sums partials [channel][slice][2]
-  double *wpart = A.d((size_t)kWSlices * 600);
-  auto G = [&](int t) { return grad + L.offset[t]; };
+  PlainWs W;
+  if ((rc = carve(h, &h->fitws, &h->fitws_bytes, true, "ofx_dqn_fit", [&](Arena &A) { plain_layout(A, N, (size_t)L.n_floats, W); })))
+    return rc;
+  auto T = [&](int t) { return C.weights + L.offset[t]; };
+  auto G = [&](int t) { return W.grad + L.offset[t]; };
+  OFX_HIP(hipMemsetAsync(W.grad, 0, sizeof(float) * L.n_floats, st));
+  OFX_HIP(hipMemsetAsync(W.loss, 0, 64 * sizeof(float), st));
 
   // ---- forward (training mode) ----
-  float *x0 = A.f(N * 2 * 160000);
-  K(t_bits_to_f32, N * 2 * 160000, n, (const uint32_t *)bits_prev, x0);
-  float *tz[4], *ta[4], *tp[4], *tstat[4];
-  const float *tin = x0;
+  K(t_bits_to_f32, N * 2 * 160000, n, (const uint32_t *)C.bits, W.x0);
+  const float *tin = W.x0;
   for (int i = 0, s = 400; i < 4; i++, s /= 2) {
     const size_t per = (size_t)s * s;
-    tz[i] = A.f(N * 8 * per); ta[i] = A.f(N * 8 * per); tp[i] = A.f(N * 8 * per / 4); tstat[i] = A.f(16);
-    if ((rc = conv_fwd(st, n, kTrunkCin[i], 8, s, s, tin, T(ofx_t_trunk(i)), T(ofx_t_trunk(i, OFX_T_BIAS)), tz[i]))) return rc;
-    hipLaunchKernelGGL(t_chan_sums, dim3(8, 64), dim3(256), 0, st, n, 8, per, tz[i], (const float *)nullptr, spart);
-    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, 8, 64, spart, sums);
-    hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, 8, (double)N * (double)per, sums, tstat[i]);
-    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * 8), 0, st, 8, per, tz[i], tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), ta[i]);
-    K(t_pool_fwd, N * 8 * per / 4, n * 8, s, s, ta[i], tp[i]);
-    tin = tp[i];
+    if ((rc = conv_fwd(st, n, kTrunkCin[i], 8, s, s, tin, T(ofx_t_trunk(i)), T(ofx_t_trunk(i, OFX_T_BIAS)), W.tz[i]))) return rc;
+    hipLaunchKernelGGL(t_chan_sums, dim3(8, 64), dim3(256), 0, st, n, 8, per, W.tz[i], (const float *)nullptr, W.spart);
+    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, 8, 64, W.spart, W.sums);
+    hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, 8, (double)N * (double)per, W.sums, W.tstat[i]);
+    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * 8), 0, st, 8, per, W.tz[i], W.tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), W.ta[i]);
+    K(t_pool_fwd, N * 8 * per / 4, n * 8, s, s, W.ta[i], W.tp[i]);
+    tin = W.tp[i];
   }
-  float *f = A.f(N * 5008), *d1 = A.f(N * 100), *d2 = A.f(N * 50), *o1 = A.f(N * 2), *u0 = A.f(N * 625);
-  K(t_concat_fwd, N * 5008, n, rows, tp[3], f, dense ? 1 : 0);
+  K(t_concat_fwd, N * 5008, n, rows, W.tp[3], W.f, dense ? 1 : 0);
   // the four dense layers on the f32 MFMA (k_gemm_f32: exact fp32 products, fp32 accumulation in MFMA order)
-  if ((rc = ofx_launch_gemm(h, f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), d1, 100, n, 100, 5008, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), d2, 50, n, 50, 100, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), o1, 2, n, 2, 50, 0))) return rc;
-  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), u0, 625, n, 625, 100, 1))) return rc;
-  float *uu[3], *uz[3], *ua[3], *ustat[3];
-  const float *uin = u0;
+  if ((rc = ofx_launch_gemm(h, W.f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), W.d1, 100, n, 100, 5008, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), W.d2, 50, n, 50, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, W.d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), W.o1, 2, n, 2, 50, 0))) return rc;
+  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), W.u0, 625, n, 625, 100, 1))) return rc;
+  const float *uin = W.u0;
   for (int j = 0, s = 50; j < 3; j++, s *= 2) {
     const size_t per = (size_t)s * s;
-    uu[j] = A.f(N * kUpCin[j] * per); uz[j] = A.f(N * kUpCout[j] * per); ua[j] = A.f(N * kUpCout[j] * per); ustat[j] = A.f(16);
-    K(t_up_fwd, N * kUpCin[j] * per, n * kUpCin[j], s / 2, s / 2, uin, uu[j], legacy);
-    if ((rc = conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, uu[j], T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), uz[j]))) return rc;
-    hipLaunchKernelGGL(t_chan_sums, dim3(kUpCout[j], 64), dim3(256), 0, st, n, kUpCout[j], per, uz[j], (const float *)nullptr, spart);
-    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUpCout[j], 64, spart, sums);
-    hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, kUpCout[j], (double)N * (double)per, sums, ustat[j]);
-    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, uz[j], ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), T(ofx_t_up(j, OFX_T_BETA)), ua[j]);
-    uin = ua[j];
+    K(t_up_fwd, N * kUpCin[j] * per, n * kUpCin[j], s / 2, s / 2, uin, W.uu[j], legacy);
+    if ((rc = conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, W.uu[j], T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), W.uz[j]))) return rc;
+    hipLaunchKernelGGL(t_chan_sums, dim3(kUpCout[j], 64), dim3(256), 0, st, n, kUpCout[j], per, W.uz[j], (const float *)nullptr, W.spart);
+    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUpCout[j], 64, W.spart, W.sums);
+    hipLaunchKernelGGL(t_bn_finish_stats, dim3(1), dim3(64), 0, st, kUpCout[j], (double)N * (double)per, W.sums, W.ustat[j]);
+    hipLaunchKernelGGL(t_bn_relu_fwd, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, W.uz[j], W.ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), T(ofx_t_up(j, OFX_T_BETA)), W.ua[j]);
+    uin = W.ua[j];
   }
-  float *up4 = A.f(N * 8 * 160000), *o2 = A.f(N * 160000);
-  K(t_up_fwd, N * 8 * 160000, n * 8, 200, 200, ua[2], up4, legacy);
-  if ((rc = conv_fwd(st, n, 8, 1, 400, 400, up4, T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), o2))) return rc;
+  K(t_up_fwd, N * 8 * 160000, n * 8, 200, 200, W.ua[2], W.up4, legacy);
+  if ((rc = conv_fwd(st, n, 8, 1, 400, 400, W.up4, T(OFX_T_OUT2), T(OFX_T_OUT2 + 1), W.o2))) return rc;
 
   // ---- loss seeds ----
-  float *do1 = A.f(N * 2), *do2 = A.f(N * 160000);
-  OFX_HIP(hipMemsetAsync(do1, 0, N * 2 * 4, st));
-  OFX_HIP(hipMemsetAsync(do2, 0, N * 160000 * 4, st));
+  OFX_HIP(hipMemsetAsync(W.do1, 0, N * 2 * 4, st));
+  OFX_HIP(hipMemsetAsync(W.do2, 0, N * 160000 * 4, st));
   if (dense) {
-    {
-      const int nb1 = (int)((N * 2 + 255) / 256), nb2 = (int)(N * 160000 / 256 > 2048 ? 2048 : (N * 160000 + 255) / 256);
-      hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), o1, t1, do1, lpart);
-      hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, lpart, loss);
-      hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), o2, t2, do2, lpart + 2048);
-      hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, lpart + 2048, loss + 1);
-      OFX_HIP(hipGetLastError());
-    }
-  } else if (R.huber_delta > 0.f) {
-    K(t_loss_seed_huber, N, n, rows, o1, o2, y_act, y_ptr, do1, do2, lpart, row_weight, td_out, R.huber_delta);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
+    const int nb1 = (int)((N * 2 + 255) / 256), nb2 = (int)(N * 160000 / 256 > 2048 ? 2048 : (N * 160000 + 255) / 256);
+    hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), W.o1, C.t1, W.do1, W.lpart);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, W.lpart, W.loss);
+    hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), W.o2, C.t2, W.do2, W.lpart + 2048);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, W.lpart + 2048, W.loss + 1);
+    OFX_HIP(hipGetLastError());
+  } else if (C.huber_delta > 0.f) {
+    K(t_loss_seed_huber, N, n, rows, W.o1, W.o2, C.y_act, C.y_ptr, W.do1, W.do2, W.lpart, C.row_weight, C.td_out, C.huber_delta);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, W.lpart, W.loss);
   } else {
-    K(t_loss_seed, N, n, rows, o1, o2, y_act, y_ptr, do1, do2, lpart, row_weight, td_out);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, lpart, loss);
+    K(t_loss_seed, N, n, rows, W.o1, W.o2, C.y_act, C.y_ptr, W.do1, W.do2, W.lpart, C.row_weight, C.td_out);
+    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, W.lpart, W.loss);
   }
 
   // ---- backward: head 2 ----
-  float *gA = A.f(N * 8 * 160000), *gB = A.f(N * 8 * 160000);  // gradient scratch (largest tensors)
-  conv_bwd_weight(st, n, 8, 1, 400, 400, up4, do2, wpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1));
-  if ((rc = conv_bwd_data(st, n, 8, 1, 400, 400, do2, T(OFX_T_OUT2), gA))) return rc;   // d up4
-  float *dcur = gB;                                                          // d ua[2]
-  K(t_up_bwd, N * 8 * 40000, n * 8, 200, 200, gA, dcur, legacy);
+  conv_bwd_weight(st, n, 8, 1, 400, 400, W.up4, W.do2, W.wpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1));
+  if ((rc = conv_bwd_data(st, n, 8, 1, 400, 400, W.do2, T(OFX_T_OUT2), W.gA))) return rc;   // d up4
+  float *dcur = W.gB;                                                          // d W.ua[2]
+  K(t_up_bwd, N * 8 * 40000, n * 8, 200, 200, W.gA, dcur, legacy);
   for (int j = 2, s = 200; j >= 0; j--, s /= 2) {
     const size_t per = (size_t)s * s;
-    float *xh = gA;                                                          // reuse as xhat
-    hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, uz[j], ua[j], ustat[j], dcur, xh);
-    hipLaunchKernelGGL(t_chan_sums, dim3(kUpCout[j], 64), dim3(256), 0, st, n, kUpCout[j], per, dcur, xh, spart);
-    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUpCout[j], 64, spart, sums);
-    float *dz = ua[j];                                                       // the activation is dead now: holds dz
-    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, (double)N * (double)per, dcur, xh, ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), sums, dz, G(ofx_t_up(j, OFX_T_GAMMA)), G(ofx_t_up(j, OFX_T_BETA)));
-    conv_bwd_weight(st, n, kUpCin[j], kUpCout[j], s, s, uu[j], dz, wpart, G(ofx_t_up(j)), G(ofx_t_up(j, OFX_T_BIAS)));
-    float *duu = gA;                                                         // d (upsampled input)
+    float *xh = W.gA;                                                          // reuse as xhat
+    hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, W.uz[j], W.ua[j], W.ustat[j], dcur, xh);
+    hipLaunchKernelGGL(t_chan_sums, dim3(kUpCout[j], 64), dim3(256), 0, st, n, kUpCout[j], per, dcur, xh, W.spart);
+    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, kUpCout[j], 64, W.spart, W.sums);
+    float *dz = W.ua[j];                                                       // the activation is dead now: holds dz
+    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * kUpCout[j]), 0, st, kUpCout[j], per, (double)N * (double)per, dcur, xh, W.ustat[j], T(ofx_t_up(j, OFX_T_GAMMA)), W.sums, dz, G(ofx_t_up(j, OFX_T_GAMMA)), G(ofx_t_up(j, OFX_T_BETA)));
+    conv_bwd_weight(st, n, kUpCin[j], kUpCout[j], s, s, W.uu[j], dz, W.wpart, G(ofx_t_up(j)), G(ofx_t_up(j, OFX_T_BIAS)));
+    float *duu = W.gA;                                                         // d (upsampled input)
     if ((rc = conv_bwd_data(st, n, kUpCin[j], kUpCout[j], s, s, dz, T(ofx_t_up(j)), duu))) return rc;
-    float *dprev = gB;                                                       // d (previous activation / u0)
+    float *dprev = W.gB;                                                       // d (previous activation / u0)
     K(t_up_bwd, N * kUpCin[j] * per / 4, n * kUpCin[j], s / 2, s / 2, duu, dprev, legacy);
     dcur = dprev;
   }
   // dcur = d u0 [n][625] (pre-mask)
-  float *dd1 = A.f(N * 100), *dd2 = A.f(N * 50), *df = A.f(N * 5008);
-  double *npart = A.d(kNormBlocks);
-  K(t_relu_mask, N * 625, N * 625, u0, dcur);
-  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, dcur, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, dcur, T(OFX_T_UPDENSE), dd1, 0);
+  K(t_relu_mask, N * 625, N * 625, W.u0, dcur);
+  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, W.d1, dcur, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, dcur, T(OFX_T_UPDENSE), W.dd1, 0);
   // ---- backward: head 1 ----
-  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(OFX_T_OUT1), dd2, 0);
-  K(t_relu_mask, N * 50, N * 50, d2, dd2);
-  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(OFX_T_DENSE2), dd1, 1);
+  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, W.d2, W.do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, W.do1, T(OFX_T_OUT1), W.dd2, 0);
+  K(t_relu_mask, N * 50, N * 50, W.d2, W.dd2);
+  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, W.d1, W.dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, W.dd2, T(OFX_T_DENSE2), W.dd1, 1);
   // ---- dense1 + trunk ----
-  K(t_relu_mask, N * 100, N * 100, d1, dd1);
-  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 1252, n, 5008, 100, dd1, T(OFX_T_DENSE1), df, 0);
-  float *dp = gB;
-  K(t_concat_bwd, N * 5000, n, df, dp);                                      // d tp[3] [n][8][25][25]
+  K(t_relu_mask, N * 100, N * 100, W.d1, W.dd1);
+  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, W.f, W.dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 1252, n, 5008, 100, W.dd1, T(OFX_T_DENSE1), W.df, 0);
+  float *dp = W.gB;
+  K(t_concat_bwd, N * 5000, n, W.df, dp);                                    // d W.tp[3] [n][8][25][25]
   for (int i = 3, s = 50; i >= 0; i--, s *= 2) {
     const size_t per = (size_t)s * s, tot = N * 8 * per;
-    float *da = gA;
-    K(t_pool_bwd, tot / 4, n * 8, s, s, ta[i], dp, da);
-    float *xh = gB + N * 8 * 40000;                                          // second half of gB (>= N*8*per for s <= 200)
-    if (s == 400) xh = up4;                                                  // the 400^2 layer: up4 (8 x 400^2) is dead by now
-    hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * 8), 0, st, 8, per, tz[i], ta[i], tstat[i], da, xh);
-    hipLaunchKernelGGL(t_chan_sums, dim3(8, 64), dim3(256), 0, st, n, 8, per, da, xh, spart);
-    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, 8, 64, spart, sums);
-    float *dz = ta[i];
-    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * 8), 0, st, 8, per, (double)N * (double)per, da, xh, tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), sums, dz, G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA)));
-    const float *xin = i == 0 ? x0 : tp[i - 1];
-    conv_bwd_weight(st, n, kTrunkCin[i], 8, s, s, xin, dz, wpart, G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)));
+    float *da = W.gA;
+    K(t_pool_bwd, tot / 4, n * 8, s, s, W.ta[i], dp, da);
+    float *xh = W.gB + N * 8 * 40000;                                          // second half of W.gB (>= N*8*per for s <= 200)
+    if (s == 400) xh = W.up4;                                                // the 400^2 layer: up4 (8 x 400^2) is dead by now
+    hipLaunchKernelGGL(t_bn_relu_bwd_pre, PLANES(per, n * 8), 0, st, 8, per, W.tz[i], W.ta[i], W.tstat[i], da, xh);
+    hipLaunchKernelGGL(t_chan_sums, dim3(8, 64), dim3(256), 0, st, n, 8, per, da, xh, W.spart);
+    hipLaunchKernelGGL(t_chan_sums_finish, dim3(1), dim3(64), 0, st, 8, 64, W.spart, W.sums);
+    float *dz = W.ta[i];
+    hipLaunchKernelGGL(t_bn_bwd, PLANES(per, n * 8), 0, st, 8, per, (double)N * (double)per, da, xh, W.tstat[i], T(ofx_t_trunk(i, OFX_T_GAMMA)), W.sums, dz, G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA)));
+    const float *xin = i == 0 ? W.x0 : W.tp[i - 1];
+    conv_bwd_weight(st, n, kTrunkCin[i], 8, s, s, xin, dz, W.wpart, G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)));
     if (i > 0) {
-      dp = gB;                                                               // d tp[i-1] [n][8][s][s]
+      dp = W.gB;                                                               // d W.tp[i-1] [n][8][s][s]
       if ((rc = conv_bwd_data(st, n, 8, 8, s, s, dz, T(ofx_t_trunk(i)), dp))) return rc;
     }
   }
-  if (A.over) {  // sizing bug guard: nothing has touched the weights yet
-    ofx_set_error("ofx_dqn_fit: internal workspace sized too small");
-    return OFX_ERR_STATE;
-  }
-  if (R.acc) return fit_accumulate(h, L, grad, tstat, ustat, loss, loss_host, R);   // ofx_dqn_grad: gradient only
-  if (grad_out) OFX_HIP(hipMemcpyAsync(grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
+  if (C.acc) return fit_accumulate(h, L, C, W.grad, W.tstat, W.ustat, W.loss);   // ofx_dqn_grad: gradient only
+  if (C.grad_out) OFX_HIP(hipMemcpyAsync(C.grad_out, W.grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
 
-  return fit_apply_update(h, L, weights, grad, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
+  return fit_apply_update(h, L, C, W.grad, W.tstat, W.ustat, W.loss, W.npart);
 }
+
+// The null / range checks the five fit entries share.  `update`: the call ends in the Adam update (moments and a step
+// number are needed); `sparse`: it takes y_act / y_ptr; `own`: the entry's further pointers are all there.
+static int fit_check(const ofx_handle *h, const FitCall &C, const char *who, bool update, bool sparse, bool own = true) {
+  if (!h || !C.weights || !C.rows || !C.bits || C.n < 1 || !own || (update && (!C.adam_m || !C.adam_v || C.step < 1)) ||
+      (sparse && (!C.y_act || !C.y_ptr))) { ofx_set_error("%s: bad argument", who); return OFX_ERR_INVALID; }
+  return OFX_OK;
+}
+static bool finite_nonneg(float x) { return x >= 0.f && x <= FLT_MAX; }   // NaN fails the first comparison, infinity the second
 
 extern "C" int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                            const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
                            float *grad_out, float *loss_host) {
-  if (!h || !weights || !adam_m || !adam_v || !rows || !bits_prev || !y_act || !y_ptr || n < 1 || step < 1) {
-    ofx_set_error("ofx_dqn_fit: bad argument");
-    return OFX_ERR_INVALID;
-  }
-  return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
-                      loss_host);
+  FitCall C;
+  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.n = n; C.rows = rows;
+  C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr; C.grad_out = grad_out; C.loss_host = loss_host;
+  const int rc = fit_check(h, C, "ofx_dqn_fit", true, true);
+  return rc ? rc : dqn_fit_impl(h, C);
 }
 
 // ofx_dqn_fit with Keras sample_weight semantics (prioritized replay's importance-sampling weights): the loss is
@@ -1342,12 +1330,12 @@ extern "C" int ofx_dqn_fit_weighted(ofx_handle *h, float *weights, float *adam_m
                                     int32_t n, const ofx_transition *rows, const void *bits_prev, const float *y_act,
                                     const float *y_ptr, float *grad_out, float *loss_host, const float *row_weight,
                                     float *td_out) {
-  if (!h || !weights || !adam_m || !adam_v || !rows || !bits_prev || !y_act || !y_ptr || n < 1 || step < 1) {
-    ofx_set_error("ofx_dqn_fit_weighted: bad argument");
-    return OFX_ERR_INVALID;
-  }
-  return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
-                      loss_host, row_weight, td_out);
+  FitCall C;
+  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.n = n; C.rows = rows;
+  C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr; C.grad_out = grad_out; C.loss_host = loss_host;
+  C.row_weight = row_weight; C.td_out = td_out;
+  const int rc = fit_check(h, C, "ofx_dqn_fit_weighted", true, true);
+  return rc ? rc : dqn_fit_impl(h, C);
 }
 
 // ofx_dqn_fit_weighted with the error bounded by Huber(huber_delta) and the gradient clipped to a global norm of
@@ -1356,26 +1344,22 @@ extern "C" int ofx_dqn_fit_robust(ofx_handle *h, float *weights, float *adam_m, 
                                   int32_t n, const ofx_transition *rows, const void *bits_prev, const float *y_act,
                                   const float *y_ptr, float *grad_out, float *loss_host, const float *row_weight,
                                   float *td_out, float huber_delta, float clip_norm, float *grad_norm_host) {
-  if (!h || !weights || !adam_m || !adam_v || !rows || !bits_prev || !y_act || !y_ptr || n < 1 || step < 1) {
-    ofx_set_error("ofx_dqn_fit_robust: bad argument");
-    return OFX_ERR_INVALID;
-  }
-  // NaN fails the first comparison, infinity the second
-  if (!(huber_delta >= 0.f && huber_delta <= FLT_MAX) || !(clip_norm >= 0.f && clip_norm <= FLT_MAX)) {
+  FitCall C;
+  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.n = n; C.rows = rows;
+  C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr; C.grad_out = grad_out; C.loss_host = loss_host;
+  C.row_weight = row_weight; C.td_out = td_out; C.huber_delta = huber_delta; C.clip_norm = clip_norm; C.grad_norm_host = grad_norm_host;
+  const int rc = fit_check(h, C, "ofx_dqn_fit_robust", true, true);
+  if (rc) return rc;
+  if (!finite_nonneg(huber_delta) || !finite_nonneg(clip_norm)) {
     ofx_set_error("ofx_dqn_fit_robust: huber_delta and clip_norm must be finite and >= 0 (0 = off), got %g and %g",
                   (double)huber_delta, (double)clip_norm);
     return OFX_ERR_INVALID;
   }
-  FitRobust R;
-  R.huber_delta = huber_delta;
-  R.clip_norm = clip_norm;
-  R.grad_norm_host = grad_norm_host;
-  return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, nullptr, nullptr, grad_out,
-                      loss_host, row_weight, td_out, R);
+  return dqn_fit_impl(h, C);
 }
 
 // The split fit.  ofx_dqn_grad is ofx_dqn_fit_robust up to and including the backward pass - the same driver in its
-// gradient-only mode (R.acc) - and ofx_dqn_apply is fit_apply_update on an accumulator (R.tail): include/ofx.h.
+// gradient-only mode (C.acc) - and ofx_dqn_apply is fit_apply_update on an accumulator (C.tail): include/ofx.h.
 extern "C" int32_t ofx_dqn_acc_floats(const ofx_handle *h) {
   ofx_policy_desc L;
   if (!h || ofx_policy_layout(h, &L)) return -1;
@@ -1385,22 +1369,21 @@ extern "C" int32_t ofx_dqn_acc_floats(const ofx_handle *h) {
 extern "C" int ofx_dqn_grad(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
                             const void *bits_prev, const float *y_act, const float *y_ptr, const float *row_weight,
                             float *td_out, float huber_delta, float *acc, int32_t reset, float *loss_host) {
-  if (!h || !weights || !rows || !bits_prev || !y_act || !y_ptr || !acc || n < 1) {
-    ofx_set_error("ofx_dqn_grad: bad argument");
-    return OFX_ERR_INVALID;
-  }
-  if (!(huber_delta >= 0.f && huber_delta <= FLT_MAX)) {   // NaN fails the first comparison, infinity the second
+  FitCall C;
+  // (the drivers read the blob and hand it on to fit_apply_update alone, which this mode never reaches)
+  C.weights = const_cast<float *>(weights); C.n = n; C.rows = rows; C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr;
+  C.loss_host = loss_host; C.row_weight = row_weight; C.td_out = td_out; C.huber_delta = huber_delta; C.acc = acc; C.acc_reset = reset != 0;
+  const int rc = fit_check(h, C, "ofx_dqn_grad", false, true, acc != nullptr);
+  if (rc) return rc;
+  if (!finite_nonneg(huber_delta)) {
     ofx_set_error("ofx_dqn_grad: huber_delta must be finite and >= 0 (0 = off), got %g", (double)huber_delta);
     return OFX_ERR_INVALID;
   }
-  FitRobust R;
-  R.huber_delta = huber_delta;
-  R.acc = acc;
-  R.acc_reset = reset != 0;
-  // (the drivers read the blob and hand it on to fit_apply_update alone, which this mode never reaches)
-  return dqn_fit_impl(h, const_cast<float *>(weights), nullptr, nullptr, 1, 0.f, n, rows, bits_prev, y_act, y_ptr, nullptr,
-                      nullptr, nullptr, loss_host, row_weight, td_out, R);
+  return dqn_fit_impl(h, C);
 }
+
+struct ApplyWs { float *loss; double *npart; };   // {loss1, loss2, norm, factor} and the norm's block partials
+static void apply_layout(Arena &A, ApplyWs &W) { W.loss = A.f(64); W.npart = A.d(kNormBlocks); }
 
 extern "C" int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr,
                              const float *acc, float scale, float clip_norm, float *loss_host, float *grad_norm_host) {
@@ -1408,7 +1391,7 @@ extern "C" int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float
     ofx_set_error("ofx_dqn_apply: bad argument");
     return OFX_ERR_INVALID;
   }
-  if (!(scale > 0.f && scale <= FLT_MAX) || !(clip_norm >= 0.f && clip_norm <= FLT_MAX)) {
+  if (!(scale > 0.f && scale <= FLT_MAX) || !finite_nonneg(clip_norm)) {
     ofx_set_error("ofx_dqn_apply: scale must be finite and > 0, clip_norm finite and >= 0 (0 = off), got %g and %g",
                   (double)scale, (double)clip_norm);
     return OFX_ERR_INVALID;
@@ -1417,20 +1400,16 @@ extern "C" int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float
   ofx_policy_desc L;
   int rc = ofx_policy_layout(h, &L);
   if (rc) return rc;
-  // {loss1, loss2, norm, factor} and the norm's block partials: a block of its own, so the fit's workspace stays as the
-  // last ofx_dqn_grad sized it
-  if ((rc = ofx_ensure_buffer(h, &h->applyws, &h->applyws_bytes, 256 + sizeof(double) * kNormBlocks))) return rc;
-  float *loss = (float *)h->applyws;
-  double *npart = (double *)((char *)h->applyws + 256);
+  // a block of its own, so the fit's workspace stays as the last ofx_dqn_grad sized it
+  ApplyWs W;
+  if ((rc = carve(h, &h->applyws, &h->applyws_bytes, false, "ofx_dqn_apply", [&](Arena &A) { apply_layout(A, W); }))) return rc;
   const float *tail = acc + L.n_floats, *tstat[4], *ustat[3];
   for (int i = 0; i < 4; i++) tstat[i] = tail + OFX_ACC_STAT_FLOATS * i;
   for (int j = 0; j < 3; j++) ustat[j] = tail + OFX_ACC_STAT_FLOATS * (4 + j);
-  FitRobust R;
-  R.clip_norm = clip_norm;
-  R.grad_norm_host = grad_norm_host;
-  R.tail = tail;
-  R.scale = scale;
-  return fit_apply_update(h, L, weights, acc, adam_m, adam_v, step, lr, tstat, ustat, loss, loss_host, R, npart);
+  FitCall C;
+  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.loss_host = loss_host;
+  C.clip_norm = clip_norm; C.grad_norm_host = grad_norm_host; C.tail = tail; C.scale = scale;
+  return fit_apply_update(h, L, C, acc, tstat, ustat, W.loss, W.npart);
 }
 
 // Trainer.replay's loop body and fit exactly as written (agents/qlearnIA_V2.py:251-285), quirks included:
@@ -1443,26 +1422,29 @@ extern "C" int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float
 //   inputs1[i] = img_input (re-bound to NEXT_state's maps at :273), inputs2[i] = next_obs.vector[:8]     (:282-283)
 //   fit(x = inputs, y = [target, ptr_target]): training-mode forward on next_state against targets built from state
 // so every output element carries an error, not one per head.
+struct RefWs { float *vec_prev, *vec_next, *act_next, *max_next, *t1, *t2; };
+static void ref_layout(Arena &A, size_t N, RefWs &W) {
+  W.vec_prev = A.f(8 * N); W.vec_next = A.f(8 * N); W.act_next = A.f(2 * N); W.max_next = A.f(N);
+  W.t1 = A.f(2 * N); W.t2 = A.f(N * TPS * TPS);
+}
 extern "C" int ofx_dqn_fit_reference(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr,
                                      int32_t n, const ofx_transition *rows, const void *bits_prev, const void *bits_next,
                                      float gamma, float *grad_out, float *loss_host) {
-  if (!h || !weights || !adam_m || !adam_v || !rows || !bits_prev || !bits_next || n < 1 || step < 1) {
-    ofx_set_error("ofx_dqn_fit_reference: bad argument");
-    return OFX_ERR_INVALID;
-  }
+  FitCall C;
+  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr;
+  C.n = n; C.rows = rows; C.bits = bits_next; C.grad_out = grad_out; C.loss_host = loss_host;
+  int rc = fit_check(h, C, "ofx_dqn_fit_reference", true, false, bits_prev != nullptr);
+  if (rc) return rc;
   OFX_HIP(hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
-  int rc;
   if ((rc = refuse_pads(h, n, rows, "ofx_dqn_fit_reference"))) return rc;  // before the two predict passes
   const size_t N = (size_t)n;
-  // vec_prev [n][8], vec_next [n][8], act_next [n][2], max_next [n], t1 [n][2], t2 [n][160000]
-  if ((rc = keep_workspace(h, &h->fitws2, &h->fitws2_bytes, sizeof(float) * N * (8 + 8 + 2 + 1 + 2 + 160000)))) return rc;
-  float *buf = (float *)h->fitws2;
-  float *vec_prev = buf, *vec_next = vec_prev + 8 * N, *act_next = vec_next + 8 * N, *max_next = act_next + 2 * N;
-  float *t1 = max_next + N, *t2 = t1 + 2 * N;
-  K(k_dqn_unpack, N, n, rows, vec_prev, vec_next, (int32_t *)nullptr);   // (padding rows were refused above)
-  if ((rc = ofx_policy_predict_obs(h, weights, n, bits_prev, vec_prev, t1, t2, nullptr))) return rc;
-  if ((rc = ofx_policy_predict_obs(h, weights, n, bits_next, vec_next, act_next, nullptr, max_next))) return rc;
-  K(t_reference_targets, N, n, rows, gamma, act_next, max_next, t1, t2);
-  return dqn_fit_impl(h, weights, adam_m, adam_v, step, lr, n, rows, bits_next, nullptr, nullptr, t1, t2, grad_out, loss_host);
+  RefWs W;
+  if ((rc = carve(h, &h->fitws2, &h->fitws2_bytes, true, "ofx_dqn_fit_reference", [&](Arena &A) { ref_layout(A, N, W); }))) return rc;
+  K(k_dqn_unpack, N, n, rows, W.vec_prev, W.vec_next, (int32_t *)nullptr);   // (padding rows were refused above)
+  if ((rc = ofx_policy_predict_obs(h, weights, n, bits_prev, W.vec_prev, W.t1, W.t2, nullptr))) return rc;
+  if ((rc = ofx_policy_predict_obs(h, weights, n, bits_next, W.vec_next, W.act_next, nullptr, W.max_next))) return rc;
+  K(t_reference_targets, N, n, rows, gamma, W.act_next, W.max_next, W.t1, W.t2);
+  C.t1 = W.t1; C.t2 = W.t2;
+  return dqn_fit_impl(h, C);
 }

@@ -479,3 +479,97 @@ def test_lean_fit_at_4096_rows(tmp_path):
                 assert err <= 2e-4 * scale + 2e-5, (kind, layer, what, err, scale)
                 np.testing.assert_allclose(wa[o:o + c], want, rtol=5e-6, atol=1e-6)
     b.close()
+
+
+def test_one_handle_relays_its_blocks_for_every_form():
+    """Every hand-carved workspace is one layout run twice (ofx_arena.h): measured, then laid out on the handle's block.  A
+    block that was sized, grown, given back and laid out again for another form leaves nothing behind that a later call can
+    see.  ONE handle runs, in this order: a lean fit of 2 rows, a plain fit of 16, the lean fit again, Double-DQN targets on
+    5 rows, a sampling forward, a plain forward, the lean fit a third time.  The three lean fits start from the same weights
+    and return the same bits (losses, gradient, weights, moments); the targets and both forwards equal, bit for bit, the
+    same calls made first on a fresh handle in the same state.
+
+    The give-back rule fires on the way: by the layouts' per-row counts a lean row is 9.3 MB and a plain row 36.9 MB, so
+    the 16-row plain block holds 590 MB of rows, while the 2-row lean block is 19 MB of rows plus under 20 MB of buffers
+    that do not grow with the rows (the 9.6 MB of block partials, the correlation rows, the gradient, dense1 transposed) -
+    less than a quarter of the plain block: the second lean fit frees the block and allocates its own size anew."""
+    from ofighters_amd import ArenaBatch, DeviceBuffer, _native as nat
+    N, M, seed, batch = 2, 2, 0x0F160077, 8
+    S, n = N * M, N * batch
+    w, _ = pyoracle.policy_init(5, trained_like=True)
+    w2, _ = pyoracle.policy_init(6, trained_like=True)
+    rs = np.random.RandomState(3)
+    y_h, y2_h = rs.uniform(-1, 2, n).astype(np.float32), rs.uniform(-1, 2, n).astype(np.float32)
+    zeros = np.zeros_like(w)
+
+    class Rig:
+        def __init__(self):
+            b = self.b = ArenaBatch(N, M)
+            b.replay_create(16, 0)
+            b.spawn_random(seed)
+            mask_d = DeviceBuffer(S).upload(np.ones((N, M), np.uint8))
+            ia_d, ip_d = DeviceBuffer(4 * S), DeviceBuffer(8 * S)
+            for t in range(10):
+                b.bot_actions(["random"] * M, seed, tick=t)
+                b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+                b.policy_actions(out_ptr=b._actions.ptr, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+                b.replay_capture(t, mask_d.ptr, ia_d.ptr, ip_d.ptr)
+                b.step(actions_ptr=b._actions.ptr)
+            slot, _ = b.replay_sample(7, 0, batch)
+            self.rows_d, self.bp_d, self.bn_d = b.replay_gather_device(slot, batch)
+            b.sync()                                        # the gather runs on the handle's stream; raw copies do not wait for it
+            assert (self.rows_d.download(b.TRANSITION_DTYPE, (n,))["ship"] >= 0).all()
+            self.y, self.y2 = DeviceBuffer(4 * n).upload(y_h), DeviceBuffer(4 * n).upload(y2_h)
+            self.bufs = tuple(DeviceBuffer(w.nbytes) for _ in range(4))
+            self.online, self.target = DeviceBuffer(w.nbytes).upload(w), DeviceBuffer(w2.nbytes).upload(w2)
+
+        def fit(self, plain, rows_n):
+            w_d, m_d, v_d, g_d = self.bufs
+            self.b.set_option(nat.OPT_FIT_PLAIN, int(plain))
+            w_d.upload(w); m_d.upload(zeros); v_d.upload(zeros)
+            l = self.b.dqn_fit(w_d, m_d, v_d, 1, 1e-4, rows_n, self.rows_d.ptr, self.bp_d.ptr, self.y.ptr, self.y2.ptr, g_d)
+            return [np.array(l)] + [d.download(np.float32, w.shape) for d in (g_d, w_d, m_d, v_d)]
+
+        def targets(self):
+            outs = [DeviceBuffer(4 * 5) for _ in range(4)]    # q_sa, p_sp, y_act, y_ptr
+            self.b.dqn_targets_double_into(self.online.ptr, self.target.ptr, 5, self.rows_d.ptr, self.bp_d.ptr, self.bn_d.ptr, 0.9,
+                                           outs[2].ptr, outs[3].ptr, q_sa_ptr=outs[0].ptr, p_sp_ptr=outs[1].ptr)
+            self.b.sync()
+            return [o.download(np.float32, (5,)) for o in outs]
+
+        def boltzmann(self):
+            vals = [DeviceBuffer(4 * S) for _ in range(4)]
+            self.b.policy_act_boltzmann(self.online.ptr, 0.5, 0.7, 1.3, seed, tick=3, q_sa_ptr=vals[0].ptr, p_sp_ptr=vals[1].ptr,
+                                        v_act_ptr=vals[2].ptr, v_ptr_ptr=vals[3].ptr)
+            self.b.policy_actions()                            # the handle's kept (iaction, ipointer), as packed actions
+            acts = self.b.actions_host()
+            return [v.download(np.float32, (S,)) for v in vals] + [np.ascontiguousarray(acts[k]) for k in ("valid", "shoot", "thrust", "px", "py")]
+
+        def forward(self):
+            act_d, ia_d, ip_d, heat_d = DeviceBuffer(8 * S), DeviceBuffer(4 * S), DeviceBuffer(8 * S), DeviceBuffer(4 * S * 160000)
+            self.b.policy_forward(self.target.ptr, None, act_d.ptr, ia_d.ptr, ip_d.ptr, heat_d.ptr)
+            self.b.sync()
+            return [act_d.download(np.float32, (S, 2)), ia_d.download(np.int32, (S,)), ip_d.download(np.int32, (S, 2)),
+                    heat_d.download(np.float32, (S, 160000))]
+
+    def same(a, c):
+        return len(a) == len(c) and all(x.dtype == z.dtype and np.array_equal(x.view(np.uint8), z.view(np.uint8)) for x, z in zip(a, c))
+
+    fresh = Rig()
+    want_targets, want_boltzmann, want_forward = fresh.targets(), fresh.boltzmann(), fresh.forward()
+    fresh.b.close()
+    assert all(np.isfinite(x).all() for x in want_targets + want_forward[:1])
+
+    one = Rig()
+    lean1 = one.fit(False, 2)
+    plain = one.fit(True, 16)
+    lean2 = one.fit(False, 2)
+    got_targets, got_boltzmann, got_forward = one.targets(), one.boltzmann(), one.forward()
+    lean3 = one.fit(False, 2)
+    one.b.close()
+    assert np.isfinite(lean1[1]).all() and np.abs(lean1[1]).max() > 0 and np.isfinite(plain[1]).all()
+    assert same(lean1, lean2), "the lean fit behind a 16-row plain fit"
+    assert same(lean1, lean3), "the lean fit behind the targets and the forwards"
+    assert same(want_targets, got_targets), "ofx_dqn_targets_double behind the fits"
+    assert same(want_boltzmann, got_boltzmann), "ofx_policy_act_boltzmann behind the fits"
+    assert same(want_forward, got_forward), "ofx_policy_forward behind the fits"

@@ -1,6 +1,6 @@
 """Diagnostic (GPU box): one DeviceTrainer.replay (sample + gather + the two target forwards + the fit) per fit batch size.
 usage: python tools/fit_time.py [--plain] [--reference] [fit_batch ...]     (default 8 64 256 1024 4096)
---plain: the layer-by-layer form of the fit (OFX_OPT_FIT_PLAIN; 61 MB of workspace per row: keep it at <= 1024 rows)
+--plain: the layer-by-layer form of the fit (OFX_OPT_FIT_PLAIN; 37 MB of workspace per row: keep it at <= 1024 rows)
 --reference: Trainer.replay as written (dense targets) instead of the textbook step"""
 import os
 import sys, time
