@@ -1010,6 +1010,53 @@ int ofx_dqn_grad(ofx_handle *h, const float *weights, int32_t n, const ofx_trans
 int ofx_dqn_apply(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, const float *acc,
                   float scale, float clip_norm, float *loss_host, float *grad_norm_host);
 
+/* ---- soft and Munchausen targets (opt-in) --------------------------------
+ * Not in the reference.  Off unless these two calls are used; nothing above changes.  The hard maximum of the next
+ * state is replaced by the soft (entropy-regularised) value V_T = T ln sum_a exp(Q(a) / T) of soft Q-learning, and
+ * Munchausen-DQN (Vieillard et al. 2020) adds the scaled, clipped log-policy of the action taken to the reward.
+ *
+ * ofx_policy_forward_obs_soft is ofx_policy_forward_obs with two more per-observation outputs (device float32 [n_obs],
+ * either may be NULL) and an optional heatmap:
+ *  - ptr_mass = Z = sum over the 160 000 pixels of exp((heat - M) / tau_ptr), M = ptr_max (the term of the maximum is 1,
+ *    so Z >= 1); ptr_soft = M + tau_ptr * ln Z.  M is ptr_max bit for bit.  A map with no finite value gives NaN in
+ *    both, as in ptr_max.
+ *  - heatmap (may be NULL): float32 [n_obs][400][400], the bits ofx_policy_forward writes for the same observation.
+ *  - Every output ofx_policy_forward_obs has comes out bit for bit as from that call.
+ *  - tau_ptr must be 0, or finite in [1e-6, 1e30]; anything else is OFX_ERR_INVALID and nothing is launched.  At
+ *    tau_ptr == 0 the default kernel runs: ptr_soft has ptr_max's bits and ptr_mass is 1.
+ *  - The heat map is never formed for the sum: the streaming head kernel keeps an online (maximum, sum) per lane next to
+ *    its arg-max, merges the lanes of a wave in a fixed tree and the 8 waves of a ship in slot order (no atomics), so a
+ *    row's result is the same bits whatever n_obs is and wherever the row stands.
+ *  - Accuracy against the float64 log-sum-exp of the float32 heat map the call wrote: |ptr_mass - ref| <= 1e-4 ref and
+ *    |ptr_soft - ref| <= 1e-4 tau_ptr + 4 ulp(ref) (DESIGN.md has the derivation; measured: tests/soft_oracle.py).
+ *  - Does not synchronise.
+ *
+ * ofx_dqn_targets_soft is ofx_dqn_targets (ret == disc == NULL) / ofx_dqn_targets_nstep (both given; exactly one NULL is
+ * OFX_ERR_INVALID) with the two maxima of `weights` on next_state replaced by soft values:
+ *  - V_ptr = ptr_soft at tau_ptr;  V_act = tau_act == 0 ? max(a0, a1) : max(a0, a1) + tau_act * log1p(exp(-|a0 - a1| /
+ *    tau_act)), in float32 (expf, log1pf), every operation rounded on its own.
+ *  - One-step form: y = (float)reward + gamma * V * live;  n-step form: y = ret + disc * V (gamma ignored): the
+ *    expressions and the rounding order of ofx_dqn_targets / _nstep.  tau_act == tau_ptr == 0 with m_alpha == 0 gives
+ *    those calls' results bit for bit.
+ *  - Munchausen (m_alpha > 0; one-step form only): the forward on `state` runs with `weights` whether or not q_sa / p_sp
+ *    are asked for, with the probe at the row's pointer and the soft value;
+ *      t = (float)reward + m_alpha * clamp(q - V(state), m_clip, 0)   per head: q = act(state)[iaction] against V_act(state),
+ *                                                                      q = the probed heat value against V_ptr(state)
+ *      y = t + gamma * V(next_state) * live
+ *    (q - V is T ln pi(a | s) of the softmax policy, <= 0 up to rounding.)
+ *  - q_sa / p_sp: both NULL or both given; padding rows (ship < 0) give zeros; a pinned blob uses its preparation.
+ *  - OFX_ERR_INVALID, before anything is launched: a NULL handle, blob, rows, bits or y; n < 1; a tau that is neither 0
+ *    nor finite in [1e-6, 1e30]; m_alpha outside [0, 1] or NaN; and with m_alpha > 0: ret / disc given, a tau that is
+ *    0, m_clip not finite or > 0.
+ *  - Accuracy against a float64 evaluation of these formulas on the float32 outputs of ofx_policy_forward_obs_soft:
+ *    2e-6 * max(1, |reward| + |m_alpha * m_clip| + |V|).  Does not synchronise.                                        */
+int ofx_policy_forward_obs_soft(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits, const float *vec8,
+                                float tau_ptr, float *act_values, int32_t *iaction, int32_t *ipointer, float *ptr_max,
+                                const int32_t *probe, float *ptr_probe, float *ptr_soft, float *ptr_mass, float *heatmap);
+int ofx_dqn_targets_soft(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows, const void *bits_prev,
+                         const void *bits_next, float gamma, const float *ret, const float *disc, float tau_act,
+                         float tau_ptr, float m_alpha, float m_clip, float *q_sa, float *p_sp, float *y_act, float *y_ptr);
+
 /* ---- timing helpers (HIP events on the handle's stream) ---------------- */
 int ofx_timer_start(ofx_handle *h);
 int ofx_timer_stop(ofx_handle *h, float *ms_host); /* synchronises */

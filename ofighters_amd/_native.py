@@ -170,6 +170,9 @@ SIGNATURES = {
     "ofx_dqn_targets_nstep": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_targets_double": (_i, [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_blend_weights": (_i, [_vp, _vp, _vp, C.c_float]),
+    "ofx_policy_forward_obs_soft": (_i, [_vp, _vp, C.c_int32, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ofx_dqn_targets_soft": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, C.c_float, C.c_float, C.c_float,
+                                  C.c_float, _vp, _vp, _vp, _vp]),
     "ofx_timer_start": (_i, [_vp]),
     "ofx_timer_stop": (_i, [_vp, C.POINTER(C.c_float)]),
     "ofx_event_record": (_i, [_vp, C.c_int32]),

@@ -41,6 +41,9 @@ struct HeadParams2 {
   unsigned long long *cand_key; // [S][8] per consumer wave (2 strips x 4): (ordered perturbed value << 32) | ~index, 0 = none
   float *cand_raw;              // [S][8] the raw heat-map value at that candidate's pixel
   unsigned *cand_max;           // [S][8] the wave's raw maximum as an ordered word (hd_ordered_f32)
+  // ---- soft value of the pointer head (ofx_policy_forward_obs_soft): k_head_stream_soft instead of k_head_stream (fp32)
+  float soft_k;                 // != 0: the soft kernel; log2(e) / T, one temperature for the launch
+  float *soft_m, *soft_z;       // [S][8] per consumer wave (the slots of cand_*): its maximum and sum exp((v - m) / T)
 };
 
 #define OFX_STREAM_BOLTZMANN_PTR 6u
@@ -69,6 +72,21 @@ __device__ __forceinline__ float hd_gumbel(unsigned r) {
   const float e_hi = 0.693147180559945f * (33.f - __builtin_amdgcn_logf(m));
   const float E = r < 0x40000000u ? e_lo : e_hi;
   return -0.693147180559945f * __builtin_amdgcn_logf(E);
+}
+
+// Soft value of the pointer head (k_head_stream_soft, k_policy_soft_finish): exp((v - m) / T) as v_exp_f32((v - m) * k),
+// k = log2(e) / T.  The difference is formed first and rounded on its own (v * k - m * k would carry the rounding of
+// m * k, |m| / T ulps, into every term alike).  m >= v: the argument is <= 0 and the term in [0, 1]; v = m gives 1.
+__device__ __forceinline__ float hd_soft_w(float v, float m, float k) { return __builtin_amdgcn_exp2f((v - m) * k); }
+typedef float hd_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ hd_f32x4 hd_soft_exp4(hd_f32x4 v, float m, float k) {
+  const hd_f32x4 x = (v - (hd_f32x4){m, m, m, m}) * (hd_f32x4){k, k, k, k};
+  return (hd_f32x4){__builtin_amdgcn_exp2f(x[0]), __builtin_amdgcn_exp2f(x[1]), __builtin_amdgcn_exp2f(x[2]), __builtin_amdgcn_exp2f(x[3])};
+}
+// a partial sum z over maximum m, rescaled to the maximum M >= m of a merge; a part that holds no value (m = -inf, an
+// idle lane) weighs nothing
+__device__ __forceinline__ float hd_soft_term(float m, float z, float M, float k) {
+  return m > -INFINITY ? z * hd_soft_w(m, M, k) : 0.f;
 }
 #endif
 

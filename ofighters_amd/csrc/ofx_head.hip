@@ -691,9 +691,10 @@ constexpr int HS_THREADS = 64 * (HS_NB + 4);
 // the arg-max's.  The raw values keep a running maximum of their own (v_ptr), the snapshot stays raw, and the winning
 // pass's noise is drawn again behind the loop to find the slot.  A wave writes its candidate (no atomics: the raw
 // value at the winner is only known once all 8 waves of the ship are compared, k_policy_boltz_finish).
-// The body is ONE text, the #else part at the end of this file, which the two kernels include (this file includes itself
-// with OFX_HEAD_STREAM_BODY defined) with `p`, EXTRA, LP and SAMPLE in scope: with SAMPLE = false the sampling parts
-// vanish and the default kernels compile to the code they had before the sampling form existed.  Not a function:
+// The body is ONE text, the #else part at the end of this file, which the three kernels include (this file includes itself
+// with OFX_HEAD_STREAM_BODY defined) with `p`, EXTRA, LP, SAMPLE and SOFT (k_head_stream_soft, below) in scope: with
+// SAMPLE = false and SOFT = false their parts vanish and the default kernels compile to the code they had before those
+// forms existed.  Not a function:
 // handed the argument struct through a force-inlined template, k_head_stream<false, 0> came out with another register
 // assignment and operand order, and its schedule is pinned (tests/test_head_isa.py).
 __device__ __forceinline__ void hs_noise8(unsigned G, unsigned c1, unsigned tick, unsigned k0, unsigned k1, float g[8]) {
@@ -708,7 +709,7 @@ __device__ __forceinline__ void hs_noise8(unsigned G, unsigned c1, unsigned tick
 
 template <bool EXTRA, int LP>
 __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
-  constexpr bool SAMPLE = false;
+  constexpr bool SAMPLE = false, SOFT = false;
 #define OFX_HEAD_STREAM_BODY
 #include "ofx_head.hip"
 #undef OFX_HEAD_STREAM_BODY
@@ -716,7 +717,25 @@ __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream(HeadParams2 p) {
 
 template <int LP>
 __global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream_sample(HeadParams2 p) {
-  constexpr bool EXTRA = false, SAMPLE = true;
+  constexpr bool EXTRA = false, SAMPLE = true, SOFT = false;
+#define OFX_HEAD_STREAM_BODY
+#include "ofx_head.hip"
+#undef OFX_HEAD_STREAM_BODY
+}
+
+// SOFT (k_head_stream_soft, ofx_policy_forward_obs_soft; fp32 only: the forwards on stored observations): next to the
+// arg-max every lane keeps the online log-sum-exp of the values it has finished - the 8 per pass that the arg-max compares
+// and the heat output stores - as a pair (m, z): m the running maximum, which the arg-max keeps anyway (tv), and
+// z = sum exp((v - m) / T), multiplied by exp((m - m') / T) in the rare pass that raises m to m'.  T is one float for the
+// launch (p.soft_k = log2(e) / T: a term is one subtraction, one product and one v_exp_f32).  Behind the loop the 64
+// lanes merge over a fixed xor tree, M = max(m1, m2), Z = z1 exp((m1 - M) / T) + z2 exp((m2 - M) / T), and lane 0 writes
+// the wave's pair into its slot of [S][8] (the slot of cand_*); the ship's 8 slots are merged in slot order by
+// k_policy_soft_finish.  No floating-point atomics: the order of every sum is fixed by (lane, pass, slot), so a row's
+// result does not depend on the batch around it.  The term of a lane's maximum is exp2(0) = 1: Z >= 1.
+template <bool EXTRA>
+__global__ __launch_bounds__(HS_THREADS, 4) void k_head_stream_soft(HeadParams2 p) {
+  constexpr int LP = 0;
+  constexpr bool SAMPLE = false, SOFT = true;
 #define OFX_HEAD_STREAM_BODY
 #include "ofx_head.hip"
 #undef OFX_HEAD_STREAM_BODY
@@ -775,7 +794,15 @@ int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
   const bool extra = p.heat || p.ptr_probe;
 #define HS_LAUNCH(E, L) hipLaunchKernelGGL((k_head_stream<E, L>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p)
 #define HS_LAUNCH_SAMPLE(L) hipLaunchKernelGGL((k_head_stream_sample<L>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p)
-  if (p.sample) {
+  if (p.soft_k != 0.f) {
+    if (p.sample || p.bf16 || p.mask || !p.soft_m || !p.soft_z) {
+      ofx_set_error("ofx_launch_head: the soft kernel is fp32, takes no mask and no sampling and needs its slot arrays");
+      return OFX_ERR_STATE;
+    }
+    if (extra) hipLaunchKernelGGL((k_head_stream_soft<true>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p);
+    else hipLaunchKernelGGL((k_head_stream_soft<false>), dim3(blocks), dim3(HS_THREADS), 0, h->stream, p);
+  }
+  else if (p.sample) {
     if (extra || !p.t_ptr || !p.cand_key || !p.cand_raw || !p.cand_max || p.M < 1) {
       ofx_set_error("ofx_launch_head: the sampling kernel takes no heat map or probe and needs its temperature and candidate arrays");
       return OFX_ERR_STATE;
@@ -810,8 +837,8 @@ int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
 }
 
 #else  // OFX_HEAD_STREAM_BODY ------------------------------------------------------------------------------------------
-// The body of k_head_stream<EXTRA, LP> and k_head_stream_sample<LP>: in scope are `p` (the kernel's HeadParams2), EXTRA,
-// LP and SAMPLE.
+// The body of k_head_stream<EXTRA, LP>, k_head_stream_sample<LP> and k_head_stream_soft<EXTRA>: in scope are `p` (the
+// kernel's HeadParams2), EXTRA, LP, SAMPLE and SOFT.
   constexpr bool BF16 = LP != 0;  // reduced-precision operands (1 = bf16, 2 = fp16), fp32 sums
   __shared__ __align__(16) float vr[HS_NV * HS_PL3];
   __shared__ __align__(16) float u2r[4 * HS_PL2];
@@ -1198,6 +1225,9 @@ int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
     // heat-map row 0, and the running maximum of the raw values
     float T = 0.f, rmax = -INFINITY;
     unsigned nG = 0u, nc1 = 0u;
+    // SOFT: log2(e) / T (launch-uniform) and the lane's sum exp((v - tv) / T) over its finished values
+    const float sk = SOFT ? p.soft_k : 0.f;
+    float sz = 0.f;
     if constexpr (SAMPLE) {
       const int ar = s / p.M;
       T = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.t_ptr[s])));
@@ -1335,11 +1365,17 @@ int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
         const bool better = ok && m8 > tv;
         if (__builtin_amdgcn_ballot_w64(better) != 0) {   // wave-uniform: most passes improve no lane's maximum
           if (better) {
+            if constexpr (SOFT) sz *= hd_soft_w(tv, m8, sk);   // the maximum grows: the sum so far is rescaled to it
             tv = m8;
             tst = st;
             snap[0] = o[0];
             snap[1] = o[1];
           }
+        }
+        if constexpr (SOFT) {   // the pass's 8 terms against the lane's maximum (an `ok` lane's tv is >= each of them)
+          const f32x4 e0 = hd_soft_exp4(o[0], tv, sk), e1 = hd_soft_exp4(o[1], tv, sk);
+          const float t8 = ((e0[0] + e0[1]) + (e0[2] + e0[3])) + ((e1[0] + e1[1]) + (e1[2] + e1[3]));
+          sz += ok ? t8 : 0.f;
         }
       }
       HS_STAMP(2);
@@ -1376,6 +1412,21 @@ int ofx_launch_head(ofx_handle *h, const HeadParams2 &p0) {
         key = other > key ? other : key;
       }
       if (lane == 0 && key) atomicMax(&p.best[s], key);
+      if constexpr (SOFT) {   // the wave's (M, Z): a fixed tree over the 64 lanes, idle lanes (m = -inf) weigh nothing
+        float sm = tv;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float m2 = __shfl_xor(sm, o), z2 = __shfl_xor(sz, o);
+          const float M2 = fmaxf(sm, m2);
+          sz = hd_soft_term(sm, sz, M2, sk) + hd_soft_term(m2, z2, M2, sk);
+          sm = M2;
+        }
+        if (lane == 0) {
+          const size_t c = (size_t)s * 8 + 4 * side + cw;
+          p.soft_m[c] = sm;
+          p.soft_z[c] = sz;
+        }
+      }
     } else {
       // the winning pass's noise again, through the same function and the same fmaf: the same bits as in the pass
       const int Rb = 5 * tst - 8 + r_in;

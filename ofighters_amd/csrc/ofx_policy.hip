@@ -619,6 +619,28 @@ __global__ void k_policy_finish(int S, const uint8_t *mask, const unsigned long 
   if (ptr_max) ptr_max[s] = none ? __builtin_nanf("") : unordered_f32((unsigned)(best[s] >> 32));  // np.max(ptr_prediction)
 }
 
+// Behind k_head_stream_soft (ofx_policy_forward_obs_soft): the ship's 8 per-wave pairs (m, z) merged in slot order against
+// the ship's maximum M - the float of the `best` key, so the bits of ptr_max - into Z = sum z_c exp((m_c - M) / T) and
+// the soft value M + T ln Z (one fmaf: the same bits under either contraction setting).  k = log2(e) / T; k == 0 is
+// the call at T == 0, where the default kernel ran: the soft value is the maximum, the mass 1.  No finite value
+// (key == 0): NaN, as ptr_max.
+__global__ void k_policy_soft_finish(int S, const unsigned long long *best, const float *soft_m, const float *soft_z,
+                                     float T, float k, float *ptr_soft, float *ptr_mass) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  const bool none = best[s] == 0ull;
+  const float M = none ? __builtin_nanf("") : unordered_f32((unsigned)(best[s] >> 32));
+  float Z = 1.f, V = M;
+  if (k != 0.f) {
+    Z = 0.f;
+    for (int c = 0; c < 8; c++) Z += hd_soft_term(soft_m[(size_t)s * 8 + c], soft_z[(size_t)s * 8 + c], M, k);
+    if (none) Z = __builtin_nanf("");
+    V = fmaf(T, logf(Z), M);
+  }
+  if (ptr_soft) ptr_soft[s] = V;
+  if (ptr_mass) ptr_mass[s] = Z;
+}
+
 // QlearnIA.play packing (qlearnIA_V2.py:447-454): exactly one of shoot / thrust, pointer always set
 __global__ void k_policy_actions(int S, const ofx_state st, const int32_t *iaction, const int32_t *ipointer,
                                  const uint8_t *mask, ofx_action *out) {
@@ -712,6 +734,7 @@ struct PolicyWs {
   float *t_act, *t_ptr, *cand_raw;
   unsigned long long *cand_key;
   unsigned *cand_max;
+  float *soft_m, *soft_z;   // soft forwards only: per-wave (maximum, sum) of k_head_stream_soft; no bytes otherwise
 };
 
 constexpr int kDense1Chunks = 25;  // split-K of dense1: 5000 = 25 x 200
@@ -720,7 +743,7 @@ constexpr int kDense1Chunks = 25;  // split-K of dense1: 5000 = 25 x 200
 // any other user of the handle's scratch block may overwrite or re-allocate it.  The (iaction, ipointer) slots only
 // take results nobody asked for (ofx_policy_forward_obs with null outputs); the results that ofx_policy_forward keeps
 // for ofx_policy_explore / ofx_policy_actions / ofx_replay_capture live in the handle (ofx_policy_results).
-static void policy_layout_ws(Arena &A, bool fused, size_t N, size_t S, bool sample, PolicyWs &W) {
+static void policy_layout_ws(Arena &A, bool fused, size_t N, size_t S, bool sample, bool soft, PolicyWs &W) {
   size_t f2, f3, f4;
   ofx_head_frame_bytes(S, &f2, &f3, &f4);
   W.p1 = A.f(fused ? 0 : N * 8 * 200 * 200);   // (5.2 GB at 4096 arenas) only in the two-kernel form of the trunk
@@ -731,15 +754,18 @@ static void policy_layout_ws(Arena &A, bool fused, size_t N, size_t S, bool samp
   // the sampling forward's arrays stand behind everything else: the other forwards' layout is unchanged
   const size_t Q = sample ? S : 0;
   W.t_act = A.f(Q); W.t_ptr = A.f(Q); W.cand_raw = A.f(8 * Q); W.cand_key = A.n<unsigned long long>(8 * Q); W.cand_max = A.n<unsigned>(8 * Q);
+  // and the soft forward's behind those
+  const size_t Qs = soft ? S : 0;
+  W.soft_m = A.f(8 * Qs); W.soft_z = A.f(8 * Qs);
 }
-static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S, bool sample = false) {
+static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S, bool sample = false, bool soft = false) {
   const bool fused = ofx_trunk_fused(h, N);
   Arena measure;
-  policy_layout_ws(measure, fused, N, S, sample, *ws);
+  policy_layout_ws(measure, fused, N, S, sample, soft, *ws);
   const int rc = ofx_ensure_scratch(h, measure.used);
   if (rc) return rc;
   Arena A(h->scratch, measure.used);
-  policy_layout_ws(A, fused, N, S, sample, *ws);
+  policy_layout_ws(A, fused, N, S, sample, soft, *ws);
   if (!A.ok()) { ofx_set_error("policy forward: internal workspace sized too small"); return OFX_ERR_STATE; }
   return OFX_OK;
 }
@@ -851,13 +877,21 @@ struct ForwardArgs {
   int32_t *iaction, *ipointer;
   const int32_t *probe;
   const BoltzArgs *boltz;          // non-null: sample both heads (k_head_stream_sample + k_policy_boltz_finish); needs act_values
+  // ofx_policy_forward_obs_soft: soft != 0 asks for ptr_soft / ptr_mass [N*M] (either may be null) at temperature tau_ptr;
+  // tau_ptr == 0 runs the default kernel (k_policy_soft_finish copies the maximum)
+  int soft;
+  float tau_ptr;
+  float *ptr_soft, *ptr_mass;
 };
 
 static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   const int N = a.N, S = a.N * a.M;
   const float *weights = a.weights;
   PolicyWs ws;
-  int rc = policy_workspace(h, &ws, N, S, a.boltz != nullptr);
+  // k_head_stream_soft takes the place of k_head_stream - when an output asks for its sums
+  const bool soft = a.soft && a.tau_ptr != 0.f && (a.ptr_soft || a.ptr_mass);
+  if (a.soft && (a.boltz || a.ship_mask)) { ofx_set_error("policy forward: the soft form takes no mask and no sampling"); return OFX_ERR_STATE; }
+  int rc = policy_workspace(h, &ws, N, S, a.boltz != nullptr, soft);
   if (rc) return rc;
   int32_t off[64], cnt[64];
   policy_layout(off, cnt);
@@ -941,6 +975,8 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
     hp2.nk0 = b.k0; hp2.nk1 = b.k1; hp2.ntick = b.tick; hp2.t_ptr = ws.t_ptr;
     hp2.cand_key = ws.cand_key; hp2.cand_raw = ws.cand_raw; hp2.cand_max = ws.cand_max;
   }
+  const float soft_k = soft ? (float)(1.4426950408889634 / (double)a.tau_ptr) : 0.f;   // log2(e) / T
+  if (soft) { hp2.soft_k = soft_k; hp2.soft_m = ws.soft_m; hp2.soft_z = ws.soft_z; }
   const int pb = h->prof_base;  // ofx_policy_profile: events around the dominant kernel, until the ring is full
   hp2.event_base = pb;
   if ((rc = ofx_launch_head(h, hp2))) return rc;
@@ -957,6 +993,11 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   hipLaunchKernelGGL(k_policy_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, a.ship_mask, ws.best,
                      a.ipointer ? a.ipointer : ws.ipointer, a.ptr_max);
   OFX_HIP(hipGetLastError());
+  if (a.soft && (a.ptr_soft || a.ptr_mass)) {
+    hipLaunchKernelGGL(k_policy_soft_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, ws.best, ws.soft_m, ws.soft_z,
+                       a.tau_ptr, soft_k, a.ptr_soft, a.ptr_mass);
+    OFX_HIP(hipGetLastError());
+  }
   return OFX_OK;
 }
 
@@ -1017,6 +1058,25 @@ extern "C" int ofx_policy_forward_obs(ofx_handle *h, const float *weights, int32
   OFX_HIP(hipSetDevice(h->cfg.device));
   ForwardArgs a = obs_args(weights, n_obs, bits, vec8);
   a.act_values = act_values; a.iaction = iaction; a.ipointer = ipointer; a.ptr_max = ptr_max; a.probe = probe; a.ptr_probe = ptr_probe;
+  return policy_forward_impl(h, a);
+}
+
+// ofx_policy_forward_obs with the soft value of the pointer head (and, on request, the heat map it was reduced from)
+extern "C" int ofx_policy_forward_obs_soft(ofx_handle *h, const float *weights, int32_t n_obs, const void *bits,
+                                           const float *vec8, float tau_ptr, float *act_values, int32_t *iaction,
+                                           int32_t *ipointer, float *ptr_max, const int32_t *probe, float *ptr_probe,
+                                           float *ptr_soft, float *ptr_mass, float *heatmap) {
+  if (!h || !weights || !bits || !vec8 || n_obs < 1) { ofx_set_error("ofx_policy_forward_obs_soft: bad argument"); return OFX_ERR_INVALID; }
+  if ((probe == nullptr) != (ptr_probe == nullptr)) { ofx_set_error("ofx_policy_forward_obs_soft: pass probe and ptr_probe together"); return OFX_ERR_INVALID; }
+  if (!(tau_ptr == 0.f || (tau_ptr >= 1e-6f && tau_ptr <= 1e30f))) {   // NaN fails every comparison
+    ofx_set_error("ofx_policy_forward_obs_soft: tau_ptr = %g; it must be 0 or lie in [1e-6, 1e30]", (double)tau_ptr);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  ForwardArgs a = obs_args(weights, n_obs, bits, vec8);
+  a.act_values = act_values; a.iaction = iaction; a.ipointer = ipointer; a.ptr_max = ptr_max; a.probe = probe; a.ptr_probe = ptr_probe;
+  a.heatmap = heatmap;
+  a.soft = 1; a.tau_ptr = tau_ptr; a.ptr_soft = ptr_soft; a.ptr_mass = ptr_mass;
   return policy_forward_impl(h, a);
 }
 

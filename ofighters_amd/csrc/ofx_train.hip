@@ -805,24 +805,76 @@ static int refuse_pads(ofx_handle *h, int n, const ofx_transition *rows, const c
   return OFX_OK;
 }
 
+// ---- soft and Munchausen targets (ofx_dqn_targets_soft) ---------------------------------------------------------------
+// k_dqn_targets with the two maxima replaced by soft values: the pointer head's comes from the forward (soft_next =
+// ptr_soft of ofx_policy_forward_obs_soft), the two-action head's is formed here.  Every operation is rounded on its own
+// (this file is compiled with -ffp-contract=off), in k_dqn_targets' order: with tau_act == 0, soft_next = the maximum and
+// m_alpha == 0 the expressions below are that kernel's.
+__device__ __forceinline__ float soft_act_value(float a0, float a1, float tau) {
+  const float m = fmaxf(a0, a1);  // np.max(prediction)
+  if (tau == 0.f) return m;
+  return m + tau * log1pf(expf(-fabsf(a0 - a1) / tau));
+}
+__global__ void k_dqn_targets_soft(int n, const ofx_transition *rows, float gamma, const float *act_prev, const float *probe_prev,
+                                   const float *soft_prev, const float *act_next, const float *soft_next, float tau_act,
+                                   float m_alpha, float m_clip, float *q_sa, float *p_sp, float *y_act, float *y_ptr,
+                                   const float *ret, const float *disc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ofx_transition r = rows[i];
+  if (r.ship < 0) {
+    if (q_sa) q_sa[i] = p_sp[i] = 0.f;
+    y_act[i] = y_ptr[i] = 0.f;
+    return;
+  }
+  if (q_sa) {   // (act_prev / probe_prev: the forward on `state` was run - asked for, or Munchausen's)
+    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
+    p_sp[i] = probe_prev[i];
+  }
+  const float v_act = soft_act_value(act_next[2 * i], act_next[2 * i + 1], tau_act), v_ptr = soft_next[i];
+  if (ret) {                                                          // n-step: ret + disc * V
+    y_act[i] = ret[i] + disc[i] * v_act;
+    y_ptr[i] = ret[i] + disc[i] * v_ptr;
+    return;
+  }
+  const float live = r.done ? 0.f : 1.f;  // int(not done)
+  if (m_alpha > 0.f) {   // Munchausen: the scaled, clipped T ln pi(a | s) of the action taken joins the reward
+    const float l_act = act_prev[2 * i + (r.iaction ? 1 : 0)] - soft_act_value(act_prev[2 * i], act_prev[2 * i + 1], tau_act);
+    const float l_ptr = probe_prev[i] - soft_prev[i];
+    const float t_act = (float)r.reward + m_alpha * fminf(fmaxf(l_act, m_clip), 0.f);
+    const float t_ptr = (float)r.reward + m_alpha * fminf(fmaxf(l_ptr, m_clip), 0.f);
+    y_act[i] = t_act + gamma * v_act * live;
+    y_ptr[i] = t_ptr + gamma * v_ptr * live;
+    return;
+  }
+  y_act[i] = (float)r.reward + gamma * v_act * live;
+  y_ptr[i] = (float)r.reward + gamma * v_ptr * live;
+}
+
 // ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch.
 // ofx_dqn_targets_double (dbl; `weights` is the online blob): the forward on next_state runs twice - online for
 // (iaction, ipointer), then `target` probed at that pointer - and k_dqn_targets_double takes the place of k_dqn_targets.
+// ofx_dqn_targets_soft (soft): the forwards are ofx_policy_forward_obs_soft's - max_next then holds ptr_soft of next_state,
+// and with the Munchausen term the forward on `state` runs whether or not q_sa / p_sp are wanted and adds soft_prev - and
+// k_dqn_targets_soft takes the place of k_dqn_targets.
 // What one forward hands to the next lives in the aux arena: the forward's scratch block is laid out anew by each.
+struct SoftArgs { float tau_act, tau_ptr, m_alpha, m_clip; };   // checked by ofx_dqn_targets_soft
 struct TargetsWs {
-  float *vec_prev, *vec_next, *act_prev, *act_next, *probe_prev, *max_next, *act_tgt, *probe_tgt;
-  int32_t *probe, *sel_action, *sel_pointer;   // sel_*, *_tgt: the double form only (null otherwise)
+  float *vec_prev, *vec_next, *act_prev, *act_next, *probe_prev, *max_next, *act_tgt, *probe_tgt, *soft_prev;
+  int32_t *probe, *sel_action, *sel_pointer;   // sel_*, *_tgt: the double form only, soft_prev: the soft form only (null otherwise)
 };
-static void targets_layout(Arena &A, size_t n, bool dbl, TargetsWs &W) {
+static void targets_layout(Arena &A, size_t n, bool dbl, bool soft, TargetsWs &W) {
   W.vec_prev = A.f(8 * n); W.vec_next = A.f(8 * n);
   W.probe = A.n<int32_t>(2 * n);
   W.act_prev = A.f(2 * n); W.act_next = A.f(2 * n); W.probe_prev = A.f(n); W.max_next = A.f(n);
   W.sel_action = dbl ? A.n<int32_t>(n) : nullptr; W.sel_pointer = dbl ? A.n<int32_t>(2 * n) : nullptr;
   W.act_tgt = dbl ? A.f(2 * n) : nullptr; W.probe_tgt = dbl ? A.f(n) : nullptr;
+  W.soft_prev = soft ? A.f(n) : nullptr;
 }
 static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights, const float *target, bool dbl, int32_t n,
                             const ofx_transition *rows, const void *bits_prev, const void *bits_next, float gamma,
-                            const float *ret, const float *disc, float *q_sa, float *p_sp, float *y_act, float *y_ptr) {
+                            const float *ret, const float *disc, float *q_sa, float *p_sp, float *y_act, float *y_ptr,
+                            const SoftArgs *soft = nullptr) {
   if (!h || !weights || (dbl && !target) || !rows || !bits_prev || !bits_next || (!q_sa) != (!p_sp) || !y_act || !y_ptr ||
       n < 1) {
     ofx_set_error("%s: bad argument", who);
@@ -830,14 +882,28 @@ static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights
   }
   OFX_HIP(hipSetDevice(h->cfg.device));
   TargetsWs W;
-  int rc = carve(h, &h->aux, &h->aux_bytes, false, who, [&](Arena &A) { targets_layout(A, (size_t)n, dbl, W); });
+  int rc = carve(h, &h->aux, &h->aux_bytes, false, who, [&](Arena &A) { targets_layout(A, (size_t)n, dbl, soft != nullptr, W); });
   if (rc) return rc;
   hipLaunchKernelGGL(k_dqn_unpack, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, W.vec_prev, W.vec_next, W.probe);
   OFX_HIP(hipGetLastError());
   // q_sa = p_sp = NULL: the caller only wants the targets (ofx_dqn_fit's own forward gives the current values) - the forward
   // on `state` is skipped
-  if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, W.vec_prev, W.act_prev, nullptr, nullptr, nullptr, W.probe, W.probe_prev)))
+  if (soft && soft->m_alpha > 0.f) {   // Munchausen: always, with the soft value of `state` next to the probe
+    if ((rc = ofx_policy_forward_obs_soft(h, weights, n, bits_prev, W.vec_prev, soft->tau_ptr, W.act_prev, nullptr, nullptr, nullptr,
+                                          W.probe, W.probe_prev, W.soft_prev, nullptr, nullptr)))
+      return rc;
+  } else if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, W.vec_prev, W.act_prev, nullptr, nullptr, nullptr, W.probe, W.probe_prev)))
     return rc;
+  if (soft) {
+    if ((rc = ofx_policy_forward_obs_soft(h, weights, n, bits_next, W.vec_next, soft->tau_ptr, W.act_next, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr, W.max_next, nullptr, nullptr)))
+      return rc;
+    hipLaunchKernelGGL(k_dqn_targets_soft, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev, W.probe_prev,
+                       W.soft_prev, W.act_next, W.max_next, soft->tau_act, soft->m_alpha, soft->m_clip, q_sa, p_sp, y_act, y_ptr, ret,
+                       disc);
+    OFX_HIP(hipGetLastError());
+    return OFX_OK;
+  }
   if (dbl) {
     // online first (the pinned slot when `weights` is the pinned blob), then the target through prep_tmp
     if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, W.vec_next, nullptr, W.sel_action, W.sel_pointer, nullptr, nullptr, nullptr)))
@@ -879,6 +945,29 @@ extern "C" int ofx_dqn_targets_double(ofx_handle *h, const float *online, const 
   if ((!ret) != (!disc)) { ofx_set_error("ofx_dqn_targets_double: pass ret and disc together"); return OFX_ERR_INVALID; }
   return dqn_targets_impl(h, "ofx_dqn_targets_double", online, target, true, n, rows, bits_prev, bits_next,
                           ret ? 0.f : gamma, ret, disc, q_sa, p_sp, y_act, y_ptr);
+}
+
+static bool soft_tau_ok(float tau) { return tau == 0.f || (tau >= 1e-6f && tau <= 1e30f); }   // NaN fails every comparison
+
+extern "C" int ofx_dqn_targets_soft(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
+                                    const void *bits_prev, const void *bits_next, float gamma, const float *ret,
+                                    const float *disc, float tau_act, float tau_ptr, float m_alpha, float m_clip, float *q_sa,
+                                    float *p_sp, float *y_act, float *y_ptr) {
+  const char *who = "ofx_dqn_targets_soft";
+  if ((!ret) != (!disc)) { ofx_set_error("%s: pass ret and disc together", who); return OFX_ERR_INVALID; }
+  if (!soft_tau_ok(tau_act) || !soft_tau_ok(tau_ptr)) {
+    ofx_set_error("%s: tau_act = %g, tau_ptr = %g; each must be 0 or lie in [1e-6, 1e30]", who, (double)tau_act, (double)tau_ptr);
+    return OFX_ERR_INVALID;
+  }
+  if (!(m_alpha >= 0.f && m_alpha <= 1.f)) { ofx_set_error("%s: m_alpha = %g; it must lie in [0, 1]", who, (double)m_alpha); return OFX_ERR_INVALID; }
+  if (m_alpha > 0.f && (ret || tau_act == 0.f || tau_ptr == 0.f || !(m_clip <= 0.f && m_clip > -INFINITY))) {
+    ofx_set_error("%s: the Munchausen term (m_alpha > 0) takes the one-step form, both taus > 0 and a finite m_clip <= 0 (got %g)", who,
+                  (double)m_clip);
+    return OFX_ERR_INVALID;
+  }
+  const SoftArgs soft = {tau_act, tau_ptr, m_alpha, m_clip};
+  return dqn_targets_impl(h, who, weights, nullptr, false, n, rows, bits_prev, bits_next, ret ? 0.f : gamma, ret, disc, q_sa, p_sp,
+                          y_act, y_ptr, &soft);
 }
 
 // Soft / hard update of a target network: the whole blob, BatchNorm moving statistics included.  tau == 1 is a copy (a

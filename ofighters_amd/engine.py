@@ -846,6 +846,39 @@ class ArenaBatch:
             out["ptr_probe"] = pp.download(np.float32, (n,))
         return out
 
+    # ------------------------------------------- soft and Munchausen targets (include/ofx.h: the contract)
+    def policy_forward_obs_soft(self, weights_ptr, n_obs, bits_ptr, vec8_ptr, tau_ptr, want_probe_ptr=None, want_heat=False):
+        """policy_forward_obs plus the soft value of the pointer head at temperature tau_ptr: the host dict gains ptr_soft
+        = ptr_max + tau_ptr * ln(ptr_mass) and ptr_mass = sum exp((heat - ptr_max) / tau_ptr) (tau_ptr = 0: ptr_max and
+        1), and with want_heat `heat`, the float32 [n_obs][H][W] map the sum was taken over."""
+        n = int(n_obs)
+        act, ia, ip, pm = DeviceBuffer(8 * n), DeviceBuffer(4 * n), DeviceBuffer(8 * n), DeviceBuffer(4 * n)
+        ps, pz = DeviceBuffer(4 * n), DeviceBuffer(4 * n)
+        pp = DeviceBuffer(4 * n) if want_probe_ptr else None
+        heat = DeviceBuffer(4 * n * self.W * self.H) if want_heat else None
+        nat.check(nat.lib().ofx_policy_forward_obs_soft(self._h, weights_ptr, n, bits_ptr, vec8_ptr, float(tau_ptr), act.ptr,
+                                                         ia.ptr, ip.ptr, pm.ptr, want_probe_ptr, pp.ptr if pp else None,
+                                                         ps.ptr, pz.ptr, heat.ptr if heat else None))
+        self.sync()
+        out = {"act": act.download(np.float32, (n, 2)), "iaction": ia.download(np.int32, (n,)),
+               "ipointer": ip.download(np.int32, (n, 2)), "ptr_max": pm.download(np.float32, (n,)),
+               "ptr_soft": ps.download(np.float32, (n,)), "ptr_mass": pz.download(np.float32, (n,))}
+        if pp:
+            out["ptr_probe"] = pp.download(np.float32, (n,))
+        if heat:
+            out["heat"] = heat.download(np.float32, (n, self.H, self.W))
+        return out
+
+    def dqn_targets_soft_into(self, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr, gamma, y_act_ptr, y_ptr_ptr,
+                              tau_act, tau_ptr, m_alpha=0.0, m_clip=0.0, ret_ptr=None, disc_ptr=None, q_sa_ptr=None,
+                              p_sp_ptr=None):
+        """The soft targets into the caller's device arrays, bootstrapped from the blob at weights_ptr: dqn_targets_into
+        with the maxima of next_state replaced by the soft values at (tau_act, tau_ptr); m_alpha > 0 adds the Munchausen
+        term m_alpha * clamp(q - V(state), m_clip, 0) to the reward (one-step form only).  Does not synchronise."""
+        nat.check(nat.lib().ofx_dqn_targets_soft(self._h, weights_ptr, int(n), rows_ptr, bits_prev_ptr, bits_next_ptr,
+                                                  float(gamma), ret_ptr, disc_ptr, float(tau_act), float(tau_ptr),
+                                                  float(m_alpha), float(m_clip), q_sa_ptr, p_sp_ptr, y_act_ptr, y_ptr_ptr))
+
     def dqn_targets(self, weights_ptr, n, rows_ptr, bits_prev_ptr, bits_next_ptr, gamma=0.9, current=True):
         """Trainer.replay's targets (qlearnIA_V2.py:251-270; gamma = 0.9, :51): host arrays q_sa, p_sp, y_act, y_ptr.
         current=False: only y_act, y_ptr (the forward on `state` is skipped; q_sa / p_sp come back as None)."""

@@ -89,6 +89,21 @@ write-back replaces it with the learner's error, as before.  The actions played 
 fingerprint() carries "actor_priorities": True only when it is on; a checkpoint gains the section
 `replay_actor_values` (the ships' previous values), the replay blob keeps its format.
 
+`soft_targets=(tau_act, tau_ptr)` and `munchausen=(alpha, clip)` (opt-in, not in the reference; each None or a pair of
+finite floats: ValueError naming the argument before anything is allocated) change what the targets bootstrap from, through
+ofx_dqn_targets_soft.  soft_targets replaces the hard maximum of next_state by the soft (entropy-regularised) value of
+soft Q-learning, V_T = T ln sum_a exp(Q(a) / T) - over the two actions at tau_act, over the heat map's 160 000 pixels at
+tau_ptr, reduced inside the streaming head kernel; each tau is 0 (that head keeps its maximum) or lies in [1e-6, 1e30].
+It is the backup that matches a Boltzmann behaviour policy (TrainingRollout(boltzmann=...)), and (0.0, 0.0) fits the
+default trainer's bits.  munchausen (Vieillard et al. 2020; alpha in [0, 1], clip finite and <= 0) adds alpha * clamp(Q(s, a)
+- V_T(s), clip, 0) - the scaled, clipped log-policy of the action taken - to the reward of both heads, from one more
+forward on `state`; it needs soft_targets with both taus > 0 and n_step == 1.  Both are refused with double_dqn (a soft
+backup has no selection step) and with reference_quirks, and work with `prioritized`, a target network (the soft values
+and Munchausen's log-policy then come from the target blob), n_step (soft only), huber_delta / clip_norm, packed_memory,
+global_sampling, accumulate and actor_priorities - whose initial priority stays the HARD one-step error the actor
+forms from the maxima it plays with.  fingerprint() carries "soft_targets" / "munchausen" only when set; a
+checkpoint needs nothing new.
+
 save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
 (`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
 cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
@@ -122,6 +137,22 @@ def fingerprint_diff(have, want):
     return sorted(k for k in set(have) | set(want) if k not in have or k not in want or have[k] != want[k])
 
 
+def _float_pair(name, val):
+    """None, or `val` as a tuple of two finite floats (no bools); ValueError naming the argument otherwise."""
+    if val is None:
+        return None
+    try:
+        pair = tuple(val)
+        ok = len(pair) == 2 and all(isinstance(x, (int, float, np.integer, np.floating)) and
+                                    not isinstance(x, (bool, np.bool_)) for x in pair)
+        pair = tuple(float(x) for x in pair) if ok else None
+    except (TypeError, ValueError):
+        pair = None
+    if pair is None or not all(np.isfinite(x) for x in pair):
+        raise ValueError("DeviceTrainer: %s must be None or a pair of finite floats, got %r" % (name, val))
+    return pair
+
+
 class _At:
     """A position inside a DeviceBuffer for the engine calls that take one (they read .ptr alone); owns nothing."""
 
@@ -134,12 +165,36 @@ class DeviceTrainer:
     accumulate = 1                                           # likewise: micro-batches per fit step
     actor_priorities = False                                 # likewise: new rows enter at the actor's own TD error
     grad_hook = None                                         # hook(trainer, acc_buffer) before ofx_dqn_apply; see above
+    soft_targets = None                                      # likewise: (tau_act, tau_ptr) of the soft backup
+    munchausen = None                                        # likewise: (alpha, clip) of the Munchausen term
 
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
                  per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
                  huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0, global_sampling=False,
-                 accumulate=1, actor_priorities=False):
+                 accumulate=1, actor_priorities=False, soft_targets=None, munchausen=None):
+        soft_targets = _float_pair("soft_targets", soft_targets)
+        munchausen = _float_pair("munchausen", munchausen)
+        if soft_targets is not None:
+            for tau in soft_targets:
+                if not (tau == 0.0 or 1e-6 <= tau <= 1e30):
+                    raise ValueError("DeviceTrainer: soft_targets takes (tau_act, tau_ptr), each 0 or in [1e-6, 1e30], got %r"
+                                     % (soft_targets,))
+        if munchausen is not None:
+            if not (0.0 <= munchausen[0] <= 1.0 and munchausen[1] <= 0.0):
+                raise ValueError("DeviceTrainer: munchausen takes (alpha, clip) with alpha in [0, 1] and clip <= 0, got %r"
+                                 % (munchausen,))
+            if soft_targets is None or not (soft_targets[0] > 0.0 and soft_targets[1] > 0.0):
+                raise ValueError("DeviceTrainer: munchausen needs soft_targets with both taus > 0 (its log-policy is the "
+                                 "softmax's), got soft_targets=%r" % (soft_targets,))
+            if n_step != 1:
+                raise ValueError("DeviceTrainer: munchausen needs n_step == 1 (the term belongs to one action's reward)")
+        for name, val in (("soft_targets", soft_targets), ("munchausen", munchausen)):
+            if val is not None and double_dqn:
+                raise ValueError("DeviceTrainer: %s is refused with double_dqn (a soft backup has no selection step)" % name)
+            if val is not None and reference_quirks:
+                raise ValueError("DeviceTrainer: %s needs the textbook fit (reference_quirks=False computes its own "
+                                 "targets)" % name)
         memory_pool_pairs = check_pool_pairs("DeviceTrainer: memory_pool_pairs", packed_memory, memory_pool_pairs)
         if not isinstance(actor_priorities, (bool, np.bool_)):
             raise ValueError("DeviceTrainer: actor_priorities must be a bool, got %r" % (actor_priorities,))
@@ -221,6 +276,8 @@ class DeviceTrainer:
         self.global_sampling = bool(global_sampling)         # one minibatch of fit_batch rows from all arenas' memories
         self.accumulate = int(accumulate)                    # micro-batches of fit_batch rows per fit step
         self.actor_priorities = bool(actor_priorities)       # a new row's mass: the actor's one-step TD error
+        self.soft_targets = soft_targets                     # (tau_act, tau_ptr): soft values in place of the maxima
+        self.munchausen = munchausen                         # (alpha, clip): the clipped log-policy joins the reward
         if self.packed_memory:
             batch.replay_create(memory_size, frames, packed=True, pool_pairs=memory_pool_pairs)
         else:
@@ -285,6 +342,10 @@ class DeviceTrainer:
             fp["accumulate"] = self.accumulate
         if self.actor_priorities:
             fp["actor_priorities"] = True
+        if self.soft_targets is not None:
+            fp["soft_targets"] = list(self.soft_targets)
+        if self.munchausen is not None:
+            fp["munchausen"] = list(self.munchausen)
         return fp
 
     def state_dict(self):
@@ -477,11 +538,15 @@ class DeviceTrainer:
         """y_act / y_ptr of the gathered window.  q_sa / p_sp (the current values at the chosen action / pointer) are not
         asked for: the fit's own training-mode forward produces them, so the targets need the forward on next_state only.
         They bootstrap from the target network when there is one; with double_dqn the online blob selects what it
-        evaluates."""
+        evaluates; with soft_targets the soft values (and munchausen's log-policy) take the maxima's place."""
         w = self.target.ptr if self.target is not None else self.weights.ptr
         nstep = self.n_step > 1
         ret_p, disc_p = (self._buf["ret"].ptr, self._buf["disc"].ptr) if nstep else (None, None)
-        if self.double_dqn:
+        if self.soft_targets is not None:
+            alpha, clip = self.munchausen if self.munchausen is not None else (0.0, 0.0)
+            self.batch.dqn_targets_soft_into(w, n, rows_p, prev_p, next_p, self.gamma, y_act.ptr, y_ptr.ptr,
+                                             self.soft_targets[0], self.soft_targets[1], alpha, clip, ret_p, disc_p)
+        elif self.double_dqn:
             self.batch.dqn_targets_double_into(self.weights.ptr, w, n, rows_p, prev_p, next_p, self.gamma, y_act.ptr,
                                                y_ptr.ptr, ret_p, disc_p)
         else:
