@@ -1057,6 +1057,58 @@ int ofx_dqn_targets_soft(ofx_handle *h, const float *weights, int32_t n, const o
                          const void *bits_next, float gamma, const float *ret, const float *disc, float tau_act,
                          float tau_ptr, float m_alpha, float m_clip, float *q_sa, float *p_sp, float *y_act, float *y_ptr);
 
+/* ---- symmetry augmentation (opt-in) ---------------------------------------
+ * Not in the reference.  Off unless these two calls are used; nothing above changes.  The arena is a square with walls,
+ * ships are clamped to [0, W-1] and discs are drawn around integer centres, so an observation mirrored or rotated on
+ * the pixel grid is (up to sub-pixel effects of the step) an observation of the same game: RAD / DrQ-style
+ * augmentation of a sampled minibatch by the eight isometries of the square (the dihedral group D4).
+ *
+ * An element is g in 0 .. 7: three bits, applied IN THIS ORDER to a position (x, y):                                  */
+#define OFX_SYM_TRANSPOSE 1 /* (x, y) -> (y, x); needs width == height                                               */
+#define OFX_SYM_FLIP_X    2 /* x -> W - 1 - x                                                                        */
+#define OFX_SYM_FLIP_Y    4 /* y -> H - 1 - y                                                                        */
+/* g = 0 is the identity, 6 the half turn, 3 and 5 the two quarter turns - the only elements that are not their own
+ * inverse.  With a . b = "a first, then b":
+ *   inverse [g]    = {0, 1, 2, 5, 4, 3, 6, 7}
+ *   compose [a][b] = {{0, 1, 2, 3, 4, 5, 6, 7}, {1, 0, 3, 2, 5, 4, 7, 6}, {2, 5, 0, 7, 6, 1, 4, 3}, {3, 4, 1, 6, 7, 0, 5, 2},
+ *                     {4, 3, 6, 1, 0, 7, 2, 5}, {5, 2, 7, 0, 1, 6, 3, 4}, {6, 7, 4, 5, 2, 3, 0, 1}, {7, 6, 5, 4, 3, 2, 1, 0}}
+ * Applied to one observation:
+ *  - maps: both 1-bit maps (ship, laser; pixel p = y*W + x at bit p & 31 of word p >> 5) satisfy out[y'][x'] = in[y][x]
+ *    with (x', y') the image of (x, y).  Every word of the observation is written and nothing outside its 2 * W*H/32
+ *    words is touched; the transformation is exact and in place.
+ *  - head vec8: elements 2, 3 (pointing) and 6, 7 (position) go through the same map in float32, a flip being
+ *    (float)(W - 1) - v: exact for the integer values the engine stores.  Elements 0, 1 (reward, can_shoot) and 4, 5
+ *    (dim; invariant because a transpose needs W == H) keep their bits.
+ *  - pointer: (px, py) int32 goes through the same map.
+ *  - Nothing is clamped: the formula is computed as it stands.  A ship spawned at coordinate W (the spawn's randint is
+ *    inclusive) keeps that value until its first thrust, and a flip maps it to -1.
+ *
+ * ofx_obs_transform applies op[i] to observation i of n_obs: bits [n_obs][2][W*H/32] uint32 in place, vec8 [n_obs][8]
+ * and pointer [n_obs][2] when not NULL (all device memory).  op is device memory and cannot be checked on the host: an
+ * op[i] above 7, or one with the transpose bit while width != height, leaves observation i untouched.
+ * OFX_ERR_INVALID, before anything is launched, for a NULL handle, op or bits, n_obs < 1, width*height no multiple of
+ * 128, or a frame whose two maps (W*H/4 bytes) exceed the 64 KB of LDS the packed frame readers are held to.
+ *
+ * ofx_replay_augment draws one element per row of a gathered batch and applies it to the whole transition:
+ *  - bits_prev / bits_next [n][2][W*H/32], head_prev, head_next and (px, py) of rows[n] are transformed in place;
+ *    tick_*, frame_*, ship, iaction, reward and done keep their bits (the priority write-backs find a row's ring
+ *    position through (tick_prev, ship), which a transformed copy still carries), and so do an n-step gather's ret /
+ *    disc, which the call never sees.
+ *  - Row d uses Philox counter (arena_base, first + d, draw, stream 8), key = seed, rr = its four words: with
+ *    k = popcount(op_mask), the element is the ofx_draw_int(rr[0], k - 1)-th set bit of op_mask in ascending order.
+ *    `first` is the row's position in the draw: the chunks of one draw, first = 0, m, 2m, ..., get the operations one
+ *    call over all of them would give.
+ *  - A padding row (ship < 0) is left as it is; op_out [n] (device uint8, may be NULL) receives each row's element, 0 for
+ *    a padding row.
+ *  - op_mask == 1 (the identity alone): no kernel is launched; op_out, if given, is zeroed.
+ *  - OFX_ERR_INVALID, before anything is launched: a NULL handle, rows or bits; n < 1, first < 0 or first + n >= 2^31;
+ *    op_mask with no bit of 0xFF or with a bit above it; an odd (transposing) element allowed while width != height; and
+ *    the two frame conditions of ofx_obs_transform.
+ * One workgroup per observation, the two maps staged in LDS.  Neither call synchronises.                              */
+int ofx_obs_transform(ofx_handle *h, int32_t n_obs, const uint8_t *op, void *bits, float *vec8, int32_t *pointer);
+int ofx_replay_augment(ofx_handle *h, uint64_t seed, uint32_t draw, int32_t first, int32_t n, uint32_t op_mask,
+                       ofx_transition *rows, void *bits_prev, void *bits_next, uint8_t *op_out);
+
 /* ---- timing helpers (HIP events on the handle's stream) ---------------- */
 int ofx_timer_start(ofx_handle *h);
 int ofx_timer_stop(ofx_handle *h, float *ms_host); /* synchronises */

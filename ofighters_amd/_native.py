@@ -173,6 +173,8 @@ SIGNATURES = {
     "ofx_policy_forward_obs_soft": (_i, [_vp, _vp, C.c_int32, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_dqn_targets_soft": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_float, _vp, _vp, C.c_float, C.c_float, C.c_float,
                                   C.c_float, _vp, _vp, _vp, _vp]),
+    "ofx_obs_transform": (_i, [_vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ofx_replay_augment": (_i, [_vp, _u64, _u32, C.c_int32, C.c_int32, _u32, _vp, _vp, _vp, _vp]),
     "ofx_timer_start": (_i, [_vp]),
     "ofx_timer_stop": (_i, [_vp, C.POINTER(C.c_float)]),
     "ofx_event_record": (_i, [_vp, C.c_int32]),

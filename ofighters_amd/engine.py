@@ -96,6 +96,14 @@ def check_pool_pairs(what, packed, pool_pairs):
     return int(pool_pairs)
 
 
+# include/ofx.h, "symmetry augmentation": an element g in 0 .. 7 is three bits applied in this order to a position
+OFX_SYM_TRANSPOSE, OFX_SYM_FLIP_X, OFX_SYM_FLIP_Y = 1, 2, 4
+SYM_INVERSE = (0, 1, 2, 5, 4, 3, 6, 7)
+SYM_COMPOSE = ((0, 1, 2, 3, 4, 5, 6, 7), (1, 0, 3, 2, 5, 4, 7, 6), (2, 5, 0, 7, 6, 1, 4, 3), (3, 4, 1, 6, 7, 0, 5, 2),
+               (4, 3, 6, 1, 0, 7, 2, 5), (5, 2, 7, 0, 1, 6, 3, 4), (6, 7, 4, 5, 2, 3, 0, 1), (7, 6, 5, 4, 3, 2, 1, 0))
+"""SYM_COMPOSE[a][b]: the one element that does a first, then b."""
+
+
 class ArenaBatch:
     def __init__(self, n_arenas, n_ships=8, **cfg):
         self.cfg = nat.default_config(n_arenas=n_arenas, n_ships=n_ships, **cfg)
@@ -724,6 +732,21 @@ class ArenaBatch:
         """Priority write-back for the n rows of a gathered list from td [n][2] = (e1, e2); afterwards every arena's
         running maximum is the maximum over all arenas."""
         nat.check(nat.lib().ofx_replay_update_priorities_list(self._h, arena.ptr, slot.ptr, int(n), rows_ptr, td_ptr))
+
+    # ------------------------------------------------------------ symmetry augmentation (include/ofx.h: the contract)
+    def obs_transform(self, n_obs, op, bits, vec8=None, pointer=None):
+        """Element op[i] (device uint8 [n_obs]; 0 .. 7, OFX_SYM_* bits) on observation i, in place: bits uint32
+        [n_obs][2][W*H/32], and when given vec8 float32 [n_obs][8] and pointer int32 [n_obs][2] (DeviceBuffers).  An op
+        above 7 leaves its observation untouched.  Does not synchronise."""
+        nat.check(nat.lib().ofx_obs_transform(self._h, int(n_obs), op.ptr, bits.ptr, vec8.ptr if vec8 else None,
+                                               pointer.ptr if pointer else None))
+
+    def replay_augment_into(self, seed, draw, first, n, op_mask, rows, bits_prev, bits_next, op_out=None):
+        """One element of op_mask per row of a gathered batch (Philox counter (arena_base, first + d, draw, stream 8)) on
+        the row's two observations, heads and pointer, in place in the caller's DeviceBuffers; padding rows are left
+        alone; op_out (device uint8 [n]) receives the elements.  op_mask == 1 launches nothing.  Does not synchronise."""
+        nat.check(nat.lib().ofx_replay_augment(self._h, seed, int(draw), int(first), int(n), int(op_mask), rows.ptr,
+                                                bits_prev.ptr, bits_next.ptr, op_out.ptr if op_out else None))
 
     # ------------------------------------------------------------ checkpoint (include/ofx.h: the blob's layout)
     def replay_export_bytes(self, arena0, n):

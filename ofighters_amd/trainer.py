@@ -104,6 +104,20 @@ global_sampling, accumulate and actor_priorities - whose initial priority stays 
 forms from the maxima it plays with.  fingerprint() carries "soft_targets" / "munchausen" only when set; a
 checkpoint needs nothing new.
 
+`augment="flips"`, `"d4"` or an integer mask in 1..255 (opt-in, not in the reference; no bool; anything else: ValueError
+naming augment before anything is allocated; refused with reference_quirks) augments every gathered chunk by the
+symmetries of the square arena (RAD, Laskin et al. 2020; DrQ, Kostrikov et al. 2020): right after a chunk's gather,
+ofx_replay_augment draws one of the allowed isometries per row - bit g of the mask allows element g of include/ofx.h's
+"symmetry augmentation"; "flips" = 0x55 is the identity, the two mirrors and the half turn, "d4" = 0xFF all eight - and
+applies it in place to the row's two observations: both 1-bit maps of state and next_state, the pointing and position
+elements of both heads, and the stored pointer.  It is the row COPIES in `rows` that are transformed, never the memory:
+targets of every flavour, the fit in both forms and ofx_dqn_grad read only (rows, bits_prev, bits_next) and so see one
+consistent transformed transition - munchausen's probe reads the transformed pointer -, and the priority write-back
+still finds its ring rows through (tick_prev, ship), which the copies keep.  The element of a row is a pure function of
+(seed, the replay's draw counter, the row's position in the draw), so chunks of one draw do not repeat each other's
+operations and a checkpoint needs nothing new.  Works with every other option of the textbook fit; how symmetric the
+game itself is under each element is measured in DESIGN.md.  fingerprint() carries "augment": mask only when set.
+
 save() and a checkpoint are different things.  save() writes the online blob alone as the Keras-compatible `.npz`
 (`model.get_weights()` order): something to load into a model and play with; a run "resumed" from it starts over with a
 cold optimiser, an empty memory and epsilon at its start.  state_dict() / load_state_dict() carry what the trainer itself
@@ -137,6 +151,21 @@ def fingerprint_diff(have, want):
     return sorted(k for k in set(have) | set(want) if k not in have or k not in want or have[k] != want[k])
 
 
+AUGMENT_MASKS = {"flips": 0x55, "d4": 0xFF}                  # identity, both mirrors, half turn / the whole dihedral group
+
+
+def _augment_mask(val):
+    """None, or the element mask of `augment`: a name of AUGMENT_MASKS or an integer in 1..255 (no bool)."""
+    if val is None:
+        return None
+    if isinstance(val, str) and val in AUGMENT_MASKS:
+        return AUGMENT_MASKS[val]
+    if isinstance(val, (int, np.integer)) and not isinstance(val, (bool, np.bool_)) and 1 <= val <= 255:
+        return int(val)
+    raise ValueError("DeviceTrainer: augment must be None, %s or an integer mask in 1..255, got %r"
+                     % (", ".join(repr(k) for k in AUGMENT_MASKS), val))
+
+
 def _float_pair(name, val):
     """None, or `val` as a tuple of two finite floats (no bools); ValueError naming the argument otherwise."""
     if val is None:
@@ -167,12 +196,17 @@ class DeviceTrainer:
     grad_hook = None                                         # hook(trainer, acc_buffer) before ofx_dqn_apply; see above
     soft_targets = None                                      # likewise: (tau_act, tau_ptr) of the soft backup
     munchausen = None                                        # likewise: (alpha, clip) of the Munchausen term
+    augment = None                                           # likewise: the element mask of the symmetry augmentation
 
     def __init__(self, batch, weights, learning_rate=0.0001, epsilon=None, batch_size=8, memory_size=400, frames=0,
                  seed=0x0F160003, fit_batch=256, reference_quirks=False, prioritized=False, per_alpha=0.6, per_beta=0.4,
                  per_beta_steps=50_000, per_eps=1e-3, n_step=1, target_sync=0, target_tau=None, double_dqn=False,
                  huber_delta=None, clip_norm=None, packed_memory=False, memory_pool_pairs=0, global_sampling=False,
-                 accumulate=1, actor_priorities=False, soft_targets=None, munchausen=None):
+                 accumulate=1, actor_priorities=False, soft_targets=None, munchausen=None, augment=None):
+        augment = _augment_mask(augment)
+        if augment is not None and reference_quirks:
+            raise ValueError("DeviceTrainer: augment needs the textbook fit (reference_quirks=False is the reference's "
+                             "replay on its own memory as written)")
         soft_targets = _float_pair("soft_targets", soft_targets)
         munchausen = _float_pair("munchausen", munchausen)
         if soft_targets is not None:
@@ -278,6 +312,7 @@ class DeviceTrainer:
         self.actor_priorities = bool(actor_priorities)       # a new row's mass: the actor's one-step TD error
         self.soft_targets = soft_targets                     # (tau_act, tau_ptr): soft values in place of the maxima
         self.munchausen = munchausen                         # (alpha, clip): the clipped log-policy joins the reward
+        self.augment = augment                               # mask of the isometries a gathered row may be seen under
         if self.packed_memory:
             batch.replay_create(memory_size, frames, packed=True, pool_pairs=memory_pool_pairs)
         else:
@@ -346,6 +381,8 @@ class DeviceTrainer:
             fp["soft_targets"] = list(self.soft_targets)
         if self.munchausen is not None:
             fp["munchausen"] = list(self.munchausen)
+        if self.augment is not None:
+            fp["augment"] = self.augment
         return fp
 
     def state_dict(self):
@@ -485,6 +522,8 @@ class DeviceTrainer:
             o = i * m
             rows_i = _At(rows, o * row_bytes)
             gather(o, m, rows_i, bits_prev, bits_next, ret, disc)
+            if self.augment is not None:                     # this replay's draw has already been counted
+                b.replay_augment_into(self.seed, self.draws - 1, o, m, self.augment, rows_i, bits_prev, bits_next)
             if quirks:                                       # as written: no hook, no split, its targets inside the fit
                 loss = b.dqn_fit_reference(self.weights, self.adam_m, self.adam_v, self.fit_steps, self.learning_rate, m,
                                            rows_i.ptr, bits_prev.ptr, bits_next.ptr, self.gamma)
