@@ -340,6 +340,62 @@ int ofx_scratch_feed_obs(ofx_handle *h, const int32_t *layers_host, int32_t n_la
                          const double *weights, const double *biases, double *y,
                          int32_t *argmax);
 
+/* ---- neuroevolution of the scratch MLP (opt-in): a genome per ship --------------------------
+ * The reference's second learner: the scratch network above with a genetic algorithm around it - Neural_network.generate /
+ * evolution / mutate / reproduce / dafts (agents/neural_network.py:436-478), one network per ship
+ * (lib/battleground.py:52-76), the four-sigmoid decode of agents/brAIn.py:129-134.  A handle holds ONE population of P
+ * genomes of the topology layers_host[n_layers], resident in HBM; ofx_destroy frees it.  All sizes and element offsets
+ * are 64-bit (P x elements passes 2^31 at 746 genomes of [320008, 9, 4]).
+ * ofx_population_create refuses, each with a message (OFX_ERR_INVALID): layers[0] != 8 + 2*W*H; layers[-1] != 4 (the
+ * reference's Action.size); fewer than 2 or more than 8 layers; a layer after the input wider than 64 (a ship's
+ * activations stay in one workgroup's LDS); P < 1.  A handle that already holds a population: OFX_ERR_STATE.  An
+ * allocation that fails: OFX_ERR_HIP, the message names the bytes asked for.
+ * ELEMENTS.  ofx_population_get / _set move genome `p` in ofx_scratch_feed's layout: every W_l row-major
+ * [n_{l+1}][n_l], layer by layer, then every bias - weights_layers + biases_layers of the reference.  A genome's ELEMENT
+ * INDEX e is the position in that concatenation, weights first; every random draw below is keyed by it, and an exported
+ * genome can be handed to ofx_scratch_feed_obs unchanged.  (On the device the first layer is kept input-major: the n1
+ * weights of one input are contiguous.  DESIGN.md section 3.)  Both calls synchronise.
+ * DRAWS.  u(r_hi, r_lo) = ((r_hi >> 5) * 2^26 + (r_lo >> 6)) / 2^53 from two Philox words: numpy's 53-bit double in
+ * [0, 1), exact in float64.  Words come from Philox4x32-10 keyed by `seed` with counter (slot p, e, generation, stream);
+ * the streams are 9 (evolve: words 0, 1 the coefficient, words 2, 3 the mutation selector), 10 (the replacement value of
+ * a mutated element, words 0, 1) and 11 (a fresh genome, words 0, 1).
+ * ofx_population_init writes 2 u - 1 on stream 11 to every element of every slot: Neural_network.__init__'s U[-1, 1)
+ * (neural_network.py:108-111), the same law on the project's counter stream.  Does not synchronise.                   */
+int ofx_population_create(ofx_handle *h, const int32_t *layers_host, int32_t n_layers, int64_t P);
+int ofx_population_destroy(ofx_handle *h);
+int ofx_population_init(ofx_handle *h, uint64_t seed, uint32_t generation);
+int ofx_population_get(ofx_handle *h, int64_t p, double *weights_host, double *biases_host);
+int ofx_population_set(ofx_handle *h, int64_t p, const double *weights_host, const double *biases_host);
+/* Reproduction in place.  plan_host: HOST int32 [P], the fate of each slot:
+ *   plan[p] == p        kept, not one bit changed
+ *   plan[p] == q != p   the slot becomes a child of q, and q must itself be kept (plan[q] == q)
+ *   plan[p] == -1       a fresh genome, as in dafts: stream 11 at this `generation`
+ * The whole plan is checked before any launch; a value outside [-1, P) or a parent that is not kept returns
+ * OFX_ERR_INVALID with nothing written.  Sources are never destinations, so there is no second buffer.
+ * A child is deepcopy(parent).evolution(rate).mutate(rate) (neural_network.py:436-467), per element e of slot p with the
+ * stream-9 words r0..r3 of counter (p, e, generation, 9):
+ *   w = parent[e]
+ *   evolution_rate > 0:                                   c = (2 u(r0, r1) - 1) * evolution_rate;  w = c * w + w
+ *                                                         (three separately rounded float64 operations, no FMA)
+ *   mutation_rate > 0 and u(r2, r3) < mutation_rate:      w = 2 u(s0, s1) - 1, s = the stream-10 words of (p, e, generation)
+ * A rate <= 0 skips its step.  One kernel, one pass.  Does not synchronise (the plan is copied before the call returns). */
+int ofx_population_breed(ofx_handle *h, const int32_t *plan_host, double evolution_rate, double mutation_rate,
+                         uint64_t seed, uint32_t generation);
+/* The forward with a genome per ship.  genome_of: DEVICE int32 [N][M], -1 = this ship is not evolved; actions: DEVICE
+ * [N][M] ofx_action, updated in place; y: DEVICE float64 [N][M][4] or NULL.  Rasterises the handle's 1-bit maps as
+ * ofx_scratch_feed_obs does; then, in one launch, for every LIVE ship with 0 <= genome_of < P: Neural_network.feed with
+ * that genome on the ship's live observation vector (toVector order: the 8-scalar head of ofx_observe_head, then the two
+ * binary maps, consumed sparsely), and the reference's decode of a four-sigmoid output with the arena's size in place of
+ * 400: shoot = y0 > 0.5, thrust = y1 > 0.5, px = (int)(y2 * W), py = (int)(y3 * H), valid = 1; no clamp, as there.
+ * Entries (actions and y) of dead, unassigned or out-of-range ships are NOT written: run ofx_bot_actions first, this
+ * call overwrites the evolved ships the way ofx_policy_actions does.  Fixed summation order, no floating-point
+ * atomics: the same bits on every call.  Does not synchronise.                                                       */
+int ofx_population_act(ofx_handle *h, const int32_t *genome_of, ofx_action *actions, double *y);
+/* Fitness.  sum: DEVICE int64 [P], count: DEVICE int32 [P].  After a restart: sum[g] += OFX_F_LAST_SCORES of every
+ * (arena, ship) with genome_of == g, count[g] += 1; reset != 0 zeroes both first.  Integer atomics: exact in any order.
+ * Does not synchronise.                                                                                              */
+int ofx_population_fitness(ofx_handle *h, const int32_t *genome_of, int64_t *sum, int32_t *count, int32_t reset);
+
 /* ---- bi-head policy forward --------------------------------------------
  * Trainer.pointer_model graph + inference glue
  * (agents/qlearnIA_V2.py:123-190, 206-220).  See ofx_policy.h-style layout

@@ -115,6 +115,14 @@ SIGNATURES = {
     "ofx_scores_allreduce": (_i, [_vp, _vp, _vp]),
     "ofx_scratch_feed": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     "ofx_scratch_feed_obs": (_i, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ofx_population_create": (_i, [_vp, _vp, C.c_int32, C.c_int64]),
+    "ofx_population_destroy": (_i, [_vp]),
+    "ofx_population_init": (_i, [_vp, _u64, _u32]),
+    "ofx_population_get": (_i, [_vp, C.c_int64, _vp, _vp]),
+    "ofx_population_set": (_i, [_vp, C.c_int64, _vp, _vp]),
+    "ofx_population_breed": (_i, [_vp, _vp, C.c_double, C.c_double, _u64, _u32]),
+    "ofx_population_act": (_i, [_vp, _vp, _vp, _vp]),
+    "ofx_population_fitness": (_i, [_vp, _vp, _vp, _vp, C.c_int32]),
     "ofx_policy_layout": (_i, [_vp, C.POINTER(OfxPolicyDesc)]),
     "ofx_policy_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_actions": (_i, [_vp, _vp, _vp, _vp, _vp]),

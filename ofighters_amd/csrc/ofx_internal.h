@@ -38,6 +38,7 @@ struct ofx_state {
 };
 
 struct ofx_replay;  // ofx_replay.hip
+struct ofx_population;  // ofx_evolve.hip
 
 struct ofx_handle {
   ofx_config cfg;
@@ -94,6 +95,7 @@ struct ofx_handle {
   uint32_t *ar_episode;            // [N]
   uint8_t *ar_dead_once;           // [N][M]
   uint8_t *ar_restarted;           // [N]
+  ofx_population *population;      // genomes of the neuroevolution (ofx_population_create), null = none
 };
 #define OFX_RING_MAX 65536         /* numbered events of ofx_event_record */
 
@@ -110,6 +112,7 @@ int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer);
 // the handle's (q_sa, p_sp, v_act, v_ptr) [N*M] of ofx_policy_act; OFX_ERR_STATE unless the last one wrote all four
 int ofx_policy_act_values(ofx_handle *h, const float **q_sa, const float **p_sp, const float **v_act, const float **v_ptr);
 void ofx_replay_free(ofx_handle *h);
+void ofx_population_free(ofx_handle *h);
 int ofx_replay_episode_reset(ofx_handle *h, const uint8_t *arena_mask);
 // C[M][N] = act(A[M][K] (lda) x B[K][N] (ldb) + bias[N]) on the f32 MFMA (k_gemm_f32, ofx_policy.hip)
 int ofx_launch_gemm(ofx_handle *h, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,

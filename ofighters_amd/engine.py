@@ -1011,3 +1011,45 @@ class ArenaBatch:
         """epsilon-greedy / collecting-phase random play over the last forward's results."""
         nat.check(nat.lib().ofx_policy_explore(self._h, float(epsilon), seed, self.tick if tick is None else tick,
                                                int(bool(collecting)), ship_mask_ptr, iaction_ptr, ipointer_ptr))
+
+    # ------------------------------------------------------------ neuroevolution (include/ofx.h: the contract)
+    def population_create(self, layers, P):
+        """One population of P genomes of the scratch MLP `layers` ([8 + 2*W*H, ..., 4]) in HBM (ofx_population_create;
+        ofighters_amd.evolution.Population owns these calls)."""
+        l = np.ascontiguousarray(layers, dtype=np.int32)
+        nat.check(nat.lib().ofx_population_create(self._h, l.ctypes.data_as(C.c_void_p), len(l), int(P)))
+
+    def population_destroy(self):
+        nat.check(nat.lib().ofx_population_destroy(self._h))
+
+    def population_init(self, seed, generation=0):
+        """U[-1, 1) on the fresh-genome stream for every element of every slot.  Does not synchronise."""
+        nat.check(nat.lib().ofx_population_init(self._h, seed, int(generation)))
+
+    def population_get(self, p, n_weights, n_biases):
+        """Genome p as (weights float64 [n_weights], biases float64 [n_biases]) in the element order.  Synchronises."""
+        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
+        nat.check(nat.lib().ofx_population_get(self._h, int(p), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def population_set(self, p, weights, biases):
+        w, b = np.ascontiguousarray(weights, dtype=np.float64), np.ascontiguousarray(biases, dtype=np.float64)
+        nat.check(nat.lib().ofx_population_set(self._h, int(p), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+
+    def population_breed(self, plan, evolution_rate, mutation_rate, seed, generation):
+        """Reproduction in place on the int32 [P] plan (kept / child of a kept slot / -1 fresh); the library checks the
+        whole plan before it writes anything.  Does not synchronise."""
+        pl = np.ascontiguousarray(plan, dtype=np.int32)
+        nat.check(nat.lib().ofx_population_breed(self._h, pl.ctypes.data_as(C.c_void_p), float(evolution_rate),
+                                                 float(mutation_rate), seed, int(generation)))
+
+    def population_act(self, genome_of_ptr, out_ptr=None, y_ptr=None):
+        """The forward with a genome per ship: overwrites, in the device action array (None = the batch's own, the one
+        bot_actions wrote), the entries of the live ships whose entry of the device int32 [N][M] at genome_of_ptr names a
+        genome; y_ptr: device float64 [N][M][4] or None.  Does not synchronise."""
+        nat.check(nat.lib().ofx_population_act(self._h, genome_of_ptr, out_ptr or self._actions.ptr, y_ptr))
+
+    def population_fitness(self, genome_of_ptr, sum_buf, count_buf, reset=False):
+        """sum[g] (int64 [P]) += the score every ship flown by genome g banked at the last restart, count[g] (int32 [P])
+        += 1 per such ship; reset zeroes both first.  Does not synchronise."""
+        nat.check(nat.lib().ofx_population_fitness(self._h, genome_of_ptr, sum_buf.ptr, count_buf.ptr, int(bool(reset))))
