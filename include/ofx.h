@@ -335,7 +335,9 @@ int ofx_scratch_feed(ofx_handle *h, const int32_t *layers_host, int32_t n_layers
 /* same network fed with the live observation vector of every (arena, ship)
  * (toVector order, observation.py:119-125; needs layers[0] == 8 + 2*W*H):
  * the binary map tail is consumed as a sparse gather of W_1 columns.
- * y [N][M][layers[-1]].                                                      */
+ * y [N][M][layers[-1]].  layers[1] <= 2048: the gather keeps 32 * layers[1]
+ * bytes in LDS; a wider first layer returns OFX_ERR_INVALID with a message
+ * naming the limit, before anything is enqueued.                             */
 int ofx_scratch_feed_obs(ofx_handle *h, const int32_t *layers_host, int32_t n_layers,
                          const double *weights, const double *biases, double *y,
                          int32_t *argmax);

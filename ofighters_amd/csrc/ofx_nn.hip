@@ -12,6 +12,8 @@
 // arena's bit maps, once per arena; only the 8-scalar head is per ship.
 #include "ofx_internal.h"
 
+#define OBS_MAX_N1 2048             /* k_obs_tail's dynamic LDS is 32 * n1 bytes: at most 64 KB is asked for */
+
 __device__ inline double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -157,6 +159,12 @@ extern "C" int ofx_scratch_feed_obs(ofx_handle *h, const int32_t *layers, int32_
   const size_t cells = (size_t)c.width * c.height;
   if ((size_t)layers[0] != 8 + 2 * cells) {
     ofx_set_error("ofx_scratch_feed_obs: layers[0] must be 8 + 2*W*H = %zu (got %d)", 8 + 2 * cells, layers[0]);
+    return OFX_ERR_INVALID;
+  }
+  // k_obs_tail keeps [4 waves][n1] doubles in dynamic LDS: refused here, before anything is queued
+  if (layers[1] > OBS_MAX_N1) {
+    ofx_set_error("ofx_scratch_feed_obs: layers[1] must be <= %d, the first layer's 32 * layers[1] bytes of LDS (got %d)",
+                  OBS_MAX_N1, layers[1]);
     return OFX_ERR_INVALID;
   }
   OFX_HIP(hipSetDevice(c.device));
