@@ -73,6 +73,16 @@ void ofx_replay_free(ofx_handle *h) {
   h->replay = nullptr;
 }
 
+// The rows of one arena as every reader sees them: `count` rows, oldest first, that end in front of `head` in a ring of
+// C positions (rows and mass share the positions).  at(i) is the ring position of oldest-first row i.
+struct RowRing {
+  int C, first, count;
+  __host__ __device__ __forceinline__ int at(int i) const { return (first + i) % C; }
+};
+__host__ __device__ __forceinline__ RowRing row_ring(int C, int head, int count) {
+  return RowRing{C, ((head - count) % C + C) % C, count};
+}
+
 template <typename T>
 static int zalloc(T **p, size_t count, int fill = 0) {
   OFX_HIP(hipMalloc((void **)p, sizeof(T) * count));
@@ -348,6 +358,22 @@ __global__ __launch_bounds__(256) void k_replay_frames(int N, int F, int words, 
   for (int k = threadIdx.x; k < q; k += 256) { dst[k] = s0[k]; dst[q + k] = s1[k]; }
 }
 
+// Where a lane's nonzero words go when a wave packs 64 uint4s (w: the lane's four words) in ascending word order, which
+// is lane-major, then component: returns *run + the nonzero words of all four components in the lanes below; the lane's
+// own nonzero words follow from there.  *run moves past the wave's.  Every lane of the wave must call it.
+template <typename T>
+__device__ __forceinline__ T nonzero_place(const uint32_t w[4], int lane, T *run) {
+  const unsigned long long below = (1ull << lane) - 1ull;
+  T pos = *run;
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    const unsigned long long bal = __ballot(w[c] != 0u);
+    pos += (T)__popcll(bal & below);
+    *run += (T)__popcll(bal);
+  }
+  return pos;
+}
+
 // The packed form of k_replay_frames: one workgroup per arena that stores a frame, four waves.  A map is q = words / 4
 // uint4s = P = ceil(q / 64) passes of 64 lanes; wave w takes the passes [w * per, (w + 1) * per) of BOTH maps, so within a
 // map the waves' pairs follow each other in wave order.  Count pass (ballots of the nonzero components), the waves' counts
@@ -367,15 +393,14 @@ __global__ __launch_bounds__(256) void k_replay_frames_packed(int N, int F, int 
                          reinterpret_cast<const uint4 *>(laser_bits + (size_t)a * words)};
   const int q = words >> 2, P = (q + 63) >> 6, per = (P + 3) >> 2;
   const int p0 = min(wave * per, P), p1 = min(p0 + per, P);  // wave-uniform
-  const unsigned long long below = (1ull << lane) - 1ull;
   for (int m = 0; m < 2; m++) {
     uint32_t run = 0;
     for (int pass = p0; pass < p1; pass++) {  // wave-uniform trip count: the ballots see every lane
       const int k = pass * 64 + lane;
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
       if (k < q) v = src[m][k];
-      run += (uint32_t)__popcll(__ballot(v.x != 0u)) + (uint32_t)__popcll(__ballot(v.y != 0u)) +
-             (uint32_t)__popcll(__ballot(v.z != 0u)) + (uint32_t)__popcll(__ballot(v.w != 0u));
+      const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+      (void)nonzero_place(w4, lane, &run);
     }
     if (lane == 0) wcnt[m][wave] = run;
   }
@@ -417,13 +442,7 @@ __global__ __launch_bounds__(256) void k_replay_frames_packed(int N, int F, int 
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
       if (k < q) v = src[m][k];
       const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
-      uint32_t pos = run;
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const unsigned long long bal = __ballot(w4[c] != 0u);
-        pos += (uint32_t)__popcll(bal & below);
-        run += (uint32_t)__popcll(bal);
-      }
+      uint32_t pos = nonzero_place(w4, lane, &run);
 #pragma unroll
       for (int c = 0; c < 4; c++)
         if (w4[c] != 0u) {  // base < pool_pairs and at most 2 * words pairs follow it: one wrap at the most, then < pool_pairs
@@ -521,24 +540,28 @@ extern "C" int ofx_replay_count(ofx_handle *h, int32_t *count_host, int64_t *app
   return OFX_OK;
 }
 
-// rows of one arena, oldest first (list(memory))
-extern "C" int ofx_replay_rows_host(ofx_handle *h, int32_t arena, ofx_transition *rows_host, int32_t *n_host) {
-  if (!h || !h->replay || !rows_host || !n_host) { ofx_set_error("ofx_replay_rows_host: bad argument"); return OFX_ERR_INVALID; }
-  if (arena < 0 || arena >= h->cfg.n_arenas) { ofx_set_error("ofx_replay_rows_host: arena out of range"); return OFX_ERR_INVALID; }
+// one arena's part of a ring array (rows or mass, `size` bytes per position) to the host, oldest first; synchronises
+static int ring_to_host(ofx_handle *h, int32_t arena, const void *array, size_t size, void *dst_host, int32_t *n_host) {
   ofx_replay *r = h->replay;
   OFX_HIP(hipSetDevice(h->cfg.device));
   OFX_HIP(hipStreamSynchronize(h->stream));
   int32_t head, count;
   OFX_HIP(hipMemcpy(&head, r->head + arena, 4, hipMemcpyDeviceToHost));
   OFX_HIP(hipMemcpy(&count, r->count + arena, 4, hipMemcpyDeviceToHost));
-  const int C = r->capacity;
-  const int first = ((head - count) % C + C) % C;
-  const ofx_transition *base = r->rows + (size_t)arena * C;
-  const int n1 = min(count, C - first);
-  if (n1 > 0) OFX_HIP(hipMemcpy(rows_host, base + first, sizeof(ofx_transition) * n1, hipMemcpyDeviceToHost));
-  if (count > n1) OFX_HIP(hipMemcpy(rows_host + n1, base, sizeof(ofx_transition) * (count - n1), hipMemcpyDeviceToHost));
+  const RowRing ring = row_ring(r->capacity, head, count);
+  const uint8_t *base = (const uint8_t *)array + size * (size_t)arena * ring.C;
+  const int n1 = min(count, ring.C - ring.first);  // the rows up to the ring's end, then the ones that wrapped
+  if (n1 > 0) OFX_HIP(hipMemcpy(dst_host, base + size * ring.first, size * n1, hipMemcpyDeviceToHost));
+  if (count > n1) OFX_HIP(hipMemcpy((uint8_t *)dst_host + size * n1, base, size * (count - n1), hipMemcpyDeviceToHost));
   *n_host = count;
   return OFX_OK;
+}
+
+// rows of one arena, oldest first (list(memory))
+extern "C" int ofx_replay_rows_host(ofx_handle *h, int32_t arena, ofx_transition *rows_host, int32_t *n_host) {
+  if (!h || !h->replay || !rows_host || !n_host) { ofx_set_error("ofx_replay_rows_host: bad argument"); return OFX_ERR_INVALID; }
+  if (arena < 0 || arena >= h->cfg.n_arenas) { ofx_set_error("ofx_replay_rows_host: arena out of range"); return OFX_ERR_INVALID; }
+  return ring_to_host(h, arena, h->replay->rows, sizeof(ofx_transition), rows_host, n_host);
 }
 
 // ---- the one reader of a stored frame: slot `slot` of arena a -> out[2][words] (16-byte aligned), every word written ----
@@ -618,20 +641,37 @@ extern "C" int ofx_replay_frame_host(ofx_handle *h, int32_t arena, int32_t tick,
 // draw, stream 3).  Transitions whose `state` frame has already left the arena's frame ring are not eligible (only
 // possible when the ring is shorter than the rows need: C rows in runs of consecutive plays use C + #runs frames).  slot[a][j] indexes the arena's rows oldest-first, -1 pads.
 #define OFX_STREAM_REPLAY 3u
+
+// Eligibility: row o of arena a can be sampled while its `state` frame is still in the frame ring, i.e. the slot it
+// names still holds its lock-step.  Rows are chronological, so the expired ones are an arena's oldest.
+__device__ __forceinline__ bool state_frame_live(const ofx_replay &r, int a, int F, const ofx_transition &o) {
+  const int f = o.frame_prev;
+  return (unsigned)f < (unsigned)F && r.frame_tick[(size_t)a * F + f] == o.tick_prev;
+}
+
+// The expired oldest rows of arena a, counted by its wave: 64 rows per ballot, the first live one ends the walk.  A frame
+// ring as long as the rows need expires nothing, so the oldest row is tried first, by all lanes at one address: the
+// usual arena then costs one cache line, not the 64 of a ballot round.
+__device__ __forceinline__ int expired_rows_wave(const ofx_replay &r, int a, int F, const RowRing &ring, int lane) {
+  const ofx_transition *rows = r.rows + (size_t)a * ring.C;
+  if (ring.count && state_frame_live(r, a, F, rows[ring.at(0)])) return 0;  // wave-uniform
+  for (int base = 0; base < ring.count; base += 64) {  // wave-uniform trip count
+    const int i = base + lane;
+    const unsigned long long hit = __ballot(i < ring.count && state_frame_live(r, a, F, rows[ring.at(i)]));
+    if (hit) return base + __ffsll((long long)hit) - 1;
+  }
+  return ring.count;
+}
+
 __global__ void k_replay_sample(int N, int C, int F, int batch, int arena_base, uint32_t k0, uint32_t k1, uint32_t draw,
                                 ofx_replay r, int32_t *slot, int32_t *n_out) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= N) return;
-  const int count = r.count[a], head = r.head[a];
-  const int first = ((head - count) % C + C) % C;
+  const RowRing ring = row_ring(C, r.head[a], r.count[a]);
   const ofx_transition *rows = r.rows + (size_t)a * C;
-  int skip = 0;  // rows are chronological: the expired ones are the oldest
-  while (skip < count) {
-    const ofx_transition &o = rows[(first + skip) % C];
-    if (r.frame_tick[(size_t)a * F + o.frame_prev] == o.tick_prev) break;
-    skip++;
-  }
-  const int valid = count - skip, n = min(batch, valid);
+  int skip = 0;  // one thread per arena: the serial walk
+  while (skip < ring.count && !state_frame_live(r, a, F, rows[ring.at(skip)])) skip++;
+  const int valid = ring.count - skip, n = min(batch, valid);
   int32_t *out = slot + (size_t)a * batch;
   for (int j = 0; j < n; j++) {
     const int top = valid - n + j;  // draw t in [0, top]
@@ -665,6 +705,12 @@ struct GatherParams {
   ofx_transition *rows;      // [N][batch]
   uint32_t *bits_prev, *bits_next;  // [N][batch][2][words] or null
 };
+static GatherParams gather_params(ofx_handle *h, const int32_t *slot, int32_t batch, ofx_transition *rows, void *bits_prev,
+                                  void *bits_next) {
+  const ofx_replay *r = h->replay;
+  return GatherParams{h->cfg.n_arenas, r->capacity, r->frames, batch, r->words, *r, slot, rows, (uint32_t *)bits_prev,
+                      (uint32_t *)bits_next};
+}
 
 // n-step returns (ofx_replay_gather_nstep; include/ofx.h states the contract): chain length, discount and outputs
 struct NstepParams {
@@ -687,46 +733,6 @@ __device__ __forceinline__ void gather_pad_row(const P &p, size_t d, const Nstep
   if (NSTEP && threadIdx.x == 0) { q.ret[d] = 0.f; q.disc[d] = 0.f; }
 }
 
-// one workgroup per (arena, j): row copy + the two frames' bit maps (16-byte loads/stores)
-template <bool PACKED>
-__global__ __launch_bounds__(256) void k_replay_gather(GatherParams p) {
-  const int a = blockIdx.x / p.batch, j = blockIdx.x - a * p.batch;
-  const int s = p.slot[(size_t)a * p.batch + j];
-  ofx_transition *dst = p.rows + (size_t)a * p.batch + j;
-  if (s < 0) {
-    gather_pad_row<false>(p, (size_t)a * p.batch + j, NstepParams{});
-    return;
-  }
-  const int count = p.r.count[a], head = p.r.head[a];
-  const int first = ((head - count) % p.C + p.C) % p.C;
-  const ofx_transition *src = p.r.rows + (size_t)a * p.C + (first + s) % p.C;
-  if (threadIdx.x < sizeof(ofx_transition) / 4) ((int32_t *)dst)[threadIdx.x] = ((const int32_t *)src)[threadIdx.x];
-  const int slots[2] = {src->frame_prev, src->frame_next};
-  uint32_t *outs[2] = {p.bits_prev, p.bits_next};
-  for (int w = 0; w < 2; w++) {
-    if (!outs[w]) continue;  // block-uniform
-    frame_read<PACKED>(p.r, a, p.F, p.words, slots[w], outs[w] + ((size_t)a * p.batch + j) * 2 * p.words);
-  }
-}
-
-extern "C" int ofx_replay_gather(ofx_handle *h, const int32_t *slot, int32_t batch, ofx_transition *rows,
-                                 void *bits_prev, void *bits_next) {
-  if (!h || !h->replay || !slot || !rows || batch <= 0) { ofx_set_error("ofx_replay_gather: bad argument"); return OFX_ERR_INVALID; }
-  ofx_replay *r = h->replay;
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  GatherParams p;
-  p.N = h->cfg.n_arenas; p.C = r->capacity; p.F = r->frames; p.batch = batch; p.words = r->words;
-  p.r = *r; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
-  if (r->packed)
-    hipLaunchKernelGGL(k_replay_gather<true>, dim3((unsigned)(p.N * batch)), dim3(256), (size_t)r->words * 8, h->stream, p);
-  else
-    hipLaunchKernelGGL(k_replay_gather<false>, dim3((unsigned)(p.N * batch)), dim3(256), 0, h->stream, p);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
-}
-
-// ---- the same minibatch without padding: only the rows that exist, packed (Trainer.replay never pads: its batch is
-// min(batch_size, len(memory)) real transitions, qlearnIA_V2.py:241-243) ------------------------------------------------
 // exclusive scan of n_sampled[N] by one workgroup -> off[N], total in off[N] (int32 for the gathers' windows, 64-bit
 // sums for the checkpoint's pair offsets)
 template <typename In, typename Out>
@@ -752,23 +758,22 @@ __global__ __launch_bounds__(1024) void k_replay_scan(int N, const In *n_sampled
 // after the current one; the lowest row of the same ship is the ship's next row in append order, and it is the
 // successor iff its tick_prev is the current row's tick_next (a ship's tick_prev values increase strictly; a restart
 // in between leaves a gap).  Lane 0 writes ret / disc; returns the oldest-first index of the chain's last row.
-__device__ int nstep_chain(const ofx_transition *ring, int C, int first_row, int count, int s, int lane, int d,
-                           const NstepParams &q) {
+__device__ int nstep_chain(const ofx_transition *rows, const RowRing &ring, int s, int lane, int d, const NstepParams &q) {
   int cur = s, L = 0;
   double acc = 0.0, pw = 1.0;
   for (;;) {
-    const ofx_transition *r = ring + (first_row + cur) % C;
+    const ofx_transition *r = rows + ring.at(cur);
     const int done = r->done, ship = r->ship, tick = r->tick_next;
     acc += pw * (double)r->reward;  // -ffp-contract=off: the product and the sum round on their own
     pw *= q.gamma;
     if (done || ++L == q.nstep) break;
     int next = -1;
-    for (int base = cur + 1; base < count; base += 64) {  // wave-uniform trip count
+    for (int base = cur + 1; base < ring.count; base += 64) {  // wave-uniform trip count
       const int i = base + lane;
       bool same = false;
       int tp = 0;
-      if (i < count) {
-        const ofx_transition *c = ring + (first_row + i) % C;
+      if (i < ring.count) {
+        const ofx_transition *c = rows + ring.at(i);
         same = c->ship == ship;
         tp = c->tick_prev;
       }
@@ -784,7 +789,7 @@ __device__ int nstep_chain(const ofx_transition *ring, int C, int first_row, int
   }
   if (lane == 0) {
     q.ret[d] = (float)acc;
-    q.disc[d] = ring[(first_row + cur) % C].done ? 0.f : (float)pw;
+    q.disc[d] = rows[ring.at(cur)].done ? 0.f : (float)pw;
   }
   return cur;
 }
@@ -794,19 +799,18 @@ __device__ int nstep_chain(const ofx_transition *ring, int C, int first_row, int
 // n-step chain from it (wave 0 walks the chain first; one LDS word carries its end to the other waves).
 template <bool NSTEP, bool PACKED, typename P>
 __device__ __forceinline__ void gather_row(const P &p, int a, int s, int count, int d, const NstepParams &q) {
-  const int head = p.r.head[a];
-  const int first_row = ((head - count) % p.C + p.C) % p.C;
-  const ofx_transition *ring = p.r.rows + (size_t)a * p.C;
-  const ofx_transition *src = ring + (first_row + s) % p.C;
+  const RowRing ring = row_ring(p.C, p.r.head[a], count);
+  const ofx_transition *rows = p.r.rows + (size_t)a * p.C;
+  const ofx_transition *src = rows + ring.at(s);
   const ofx_transition *end = src;  // the row whose next state is gathered
   if constexpr (NSTEP) {
     __shared__ int end_s;
     if (threadIdx.x < 64) {
-      const int e = nstep_chain(ring, p.C, first_row, count, s, threadIdx.x, d, q);
+      const int e = nstep_chain(rows, ring, s, threadIdx.x, d, q);
       if (threadIdx.x == 0) end_s = e;
     }
     __syncthreads();
-    end = ring + (first_row + end_s) % p.C;
+    end = rows + ring.at(end_s);
   }
   ofx_transition *dst = p.rows + d;
   if (threadIdx.x < sizeof(ofx_transition) / 4) {
@@ -822,6 +826,31 @@ __device__ __forceinline__ void gather_row(const P &p, int a, int s, int count, 
   }
 }
 
+// ofx_replay_gather: one workgroup per (arena, j), row a * batch + j of the padded output
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_replay_gather(GatherParams p) {
+  const int a = blockIdx.x / p.batch;
+  const int s = p.slot[blockIdx.x];
+  if (s < 0) gather_pad_row<false>(p, (size_t)blockIdx.x, NstepParams{});  // block-uniform
+  else gather_row<false, PACKED>(p, a, s, p.r.count[a], (int)blockIdx.x, NstepParams{});
+}
+
+extern "C" int ofx_replay_gather(ofx_handle *h, const int32_t *slot, int32_t batch, ofx_transition *rows,
+                                 void *bits_prev, void *bits_next) {
+  if (!h || !h->replay || !slot || !rows || batch <= 0) { ofx_set_error("ofx_replay_gather: bad argument"); return OFX_ERR_INVALID; }
+  ofx_replay *r = h->replay;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const GatherParams p = gather_params(h, slot, batch, rows, bits_prev, bits_next);
+  if (r->packed)
+    hipLaunchKernelGGL(k_replay_gather<true>, dim3((unsigned)(p.N * batch)), dim3(256), (size_t)r->words * 8, h->stream, p);
+  else
+    hipLaunchKernelGGL(k_replay_gather<false>, dim3((unsigned)(p.N * batch)), dim3(256), 0, h->stream, p);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ---- the same minibatch without padding: only the rows that exist, packed (Trainer.replay never pads: its batch is
+// min(batch_size, len(memory)) real transitions, qlearnIA_V2.py:241-243) ------------------------------------------------
 // one workgroup per (arena, j): sampled entry j of arena a is packed row off[a] + j - first, when it falls into
 // [0, max_rows)
 template <bool NSTEP, bool PACKED>
@@ -847,9 +876,7 @@ static int gather_window(ofx_handle *h, const char *who, const int32_t *slot, co
   const int N = h->cfg.n_arenas;
   int32_t *off = r->scan_off;
   hipLaunchKernelGGL((k_replay_scan<int32_t, int32_t>), dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
-  GatherParams p;
-  p.N = N; p.C = r->capacity; p.F = r->frames; p.batch = batch; p.words = r->words;
-  p.r = *r; p.slot = slot; p.rows = rows; p.bits_prev = (uint32_t *)bits_prev; p.bits_next = (uint32_t *)bits_next;
+  const GatherParams p = gather_params(h, slot, batch, rows, bits_prev, bits_next);
   const dim3 grid((unsigned)(N * batch));
   const size_t lds = (size_t)r->words * 8;  // packed: the two maps of a frame
   if (q && r->packed)
@@ -943,35 +970,56 @@ struct PerSampleParams {
   float *is_weight;
 };
 
-// One 64-lane wave per arena.  Lane L sums chunk L; every lane then runs the same sequential chain over the 64 chunk
-// totals and keeps its own inclusive prefix.  Draw j belongs to lane j % 64: binary search for the first chunk whose
-// inclusive prefix exceeds u (the prefixes are monotone), then a sequential walk inside it that rebuilds the chunk's
-// running sum - prefix(row) = excl(chunk) + running sum, which reaches the chunk's inclusive prefix exactly at its last row.
+// The summation order of the proportional pick, by the arena's wave: lane L sums chunk L of the `valid` eligible rows
+// behind the `skip` expired ones, every lane then runs the same sequential chain over the 64 chunk totals.  Returns the
+// total, *incl = the lane's inclusive chunk prefix.
+__device__ __forceinline__ double arena_chunk_chain(const float *mass, const RowRing &ring, int skip, int valid, int lane,
+                                                    double *incl) {
+  const int cs = (valid + 63) / 64;
+  const int lo = min(lane * cs, valid), hi = min(lo + cs, valid);
+  double t = 0.0;
+  for (int i = lo; i < hi; i++) t += (double)mass[ring.at(skip + i)];
+  double total = 0.0, in = 0.0;
+  for (int k = 0; k < 64; k++) {
+    total += __shfl(t, k);
+    if (k == lane) in = total;
+  }
+  *incl = in;
+  return total;
+}
+
+// The walk inside chunk k, whose exclusive prefix is ex: it rebuilds the chunk's running sum - prefix(row) = ex + running
+// sum, which reaches the chunk's inclusive prefix exactly at its last row - and returns the first eligible row whose
+// prefix exceeds u (the chunk's last row when rounding left none).
+__device__ __forceinline__ int chunk_pick(const float *mass, const RowRing &ring, int skip, int valid, int k, double ex,
+                                          double u) {
+  const int cs = (valid + 63) / 64, r0 = k * cs, r1 = min(r0 + cs, valid);
+  double run = 0.0;
+  for (int i = r0; i < r1; i++) {
+    run += (double)mass[ring.at(skip + i)];
+    if (ex + run > u) return i;
+  }
+  return r1 - 1;
+}
+
+// raw importance-sampling weight of a row of mass m drawn from `rows` eligible rows of `total` mass: (rows * P(row))^-beta
+__device__ __forceinline__ float is_weight_raw(double rows, double m, double total, double beta) {
+  return total > 0.0 ? (float)pow(rows * m / total, -beta) : 1.f;
+}
+
+// One 64-lane wave per arena.  Every lane keeps its own inclusive chunk prefix.  Draw j belongs to lane j % 64: binary
+// search over shuffles for the first chunk whose inclusive prefix exceeds u (the prefixes are monotone), then the walk
+// inside it.  k_global_draw keeps its own chunk search: there u is wave-uniform and one ballot finds the chunk.
 __global__ __launch_bounds__(256) void k_replay_sample_per(PerSampleParams p) {
   const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (a >= p.N) return;  // wave-uniform
-  const int C = p.C;
-  const int count = p.r.count[a], head = p.r.head[a];
-  const int first = ((head - count) % C + C) % C;
-  const ofx_transition *rows = p.r.rows + (size_t)a * C;
-  int skip = 0;  // the same eligibility as k_replay_sample: the oldest rows whose `state` frame has left the ring
-  while (skip < count) {
-    const ofx_transition &o = rows[(first + skip) % C];
-    if (p.r.frame_tick[(size_t)a * p.F + o.frame_prev] == o.tick_prev) break;
-    skip++;
-  }
-  const int valid = count - skip, n = min(p.batch, valid);
-  const float *mass = p.r.mass + (size_t)a * C;
-  const int base = first + skip;  // eligible row i sits at ring position (base + i) % C
+  const RowRing ring = row_ring(p.C, p.r.head[a], p.r.count[a]);
+  const int skip = expired_rows_wave(p.r, a, p.F, ring, lane);
+  const int valid = ring.count - skip, n = min(p.batch, valid);
+  const float *mass = p.r.mass + (size_t)a * p.C;
   const int cs = (valid + 63) / 64, nchunks = cs ? (valid + cs - 1) / cs : 0;
-  const int lo = min(lane * cs, valid), hi = min(lo + cs, valid);
-  double t = 0.0;
-  for (int i = lo; i < hi; i++) t += (double)mass[(base + i) % C];
-  double total = 0.0, incl = 0.0;
-  for (int k = 0; k < 64; k++) {
-    total += __shfl(t, k);
-    if (k == lane) incl = total;
-  }
+  double incl;
+  const double total = arena_chunk_chain(mass, ring, skip, valid, lane, &incl);
   int32_t *out = p.slot + (size_t)a * p.batch;
   float *wout = p.is_weight + (size_t)a * p.batch;
   for (int j0 = 0; j0 < n; j0 += 64) {  // wave-uniform trip count: the shuffles below see every lane
@@ -995,19 +1043,10 @@ __global__ __launch_bounds__(256) void k_replay_sample_per(PerSampleParams p) {
     double ex = __shfl(incl, max(klo - 1, 0));
     if (klo == 0) ex = 0.0;
     if (j < n) {
-      int pick = valid - 1;  // rounding left no row above u: the last eligible row
-      if (klo < nchunks) {
-        const int r0 = klo * cs, r1 = min(r0 + cs, valid);
-        double run = 0.0;
-        pick = r1 - 1;
-        for (int i = r0; i < r1; i++) {
-          run += (double)mass[(base + i) % C];
-          if (ex + run > u) { pick = i; break; }
-        }
-      }
-      const double m = (double)mass[(base + pick) % C];
+      // klo == nchunks: rounding left no row above u, the last eligible row
+      const int pick = klo < nchunks ? chunk_pick(mass, ring, skip, valid, klo, ex, u) : valid - 1;
       out[j] = skip + pick;
-      wout[j] = total > 0.0 ? (float)pow((double)valid * m / total, -p.beta) : 1.f;
+      wout[j] = is_weight_raw((double)valid, (double)mass[ring.at(skip + pick)], total, p.beta);
     }
   }
   for (int j = n + lane; j < p.batch; j += 64) { out[j] = -1; wout[j] = 0.f; }
@@ -1043,21 +1082,31 @@ __global__ __launch_bounds__(256) void k_replay_window_pack(int N, int batch, co
   if (d < 0 || d >= max_rows) return;
   out[d] = is_weight[t];
 }
-// the window's weights over their maximum (the max is exact in any order)
-__global__ __launch_bounds__(1024) void k_replay_window_norm(int N, const int32_t *off, int first, int max_rows, float *out) {
+
+// the maximum of v[0 .. n) and 0 in every thread of a workgroup of 1024 (the max is exact in any order)
+__device__ __forceinline__ float block_max(const float *v, int n) {
   __shared__ float red[1024];
-  const int tid = threadIdx.x, n = min(max(off[N] - first, 0), max_rows);
+  const int tid = threadIdx.x;
   float m = 0.f;
-  for (int d = tid; d < n; d += 1024) m = fmaxf(m, out[d]);
+  for (int d = tid; d < n; d += 1024) m = fmaxf(m, v[d]);
   red[tid] = m;
   __syncthreads();
   for (int k = 512; k > 0; k >>= 1) {
     if (tid < k) red[tid] = fmaxf(red[tid], red[tid + k]);
     __syncthreads();
   }
-  const float mx = red[0];
+  return red[0];
+}
+
+// The raw weights of a minibatch over their maximum.  The minibatch is what an exclusive scan (k_replay_scan) counted,
+// from entry `first` on and `cap` entries at the most: w[0 .. n), n = min(max(*total - first, 0), cap).
+template <typename T>
+__global__ __launch_bounds__(1024) void k_replay_norm(const T *total, int first, int cap, float *w) {
+  const long long left = (long long)*total - first;
+  const int n = (int)(left < 0 ? 0 : left < cap ? left : cap);
+  const float mx = block_max(w, n);
   if (mx > 0.f)
-    for (int d = tid; d < n; d += 1024) out[d] = out[d] / mx;
+    for (int d = threadIdx.x; d < n; d += 1024) w[d] = w[d] / mx;
 }
 
 extern "C" int ofx_replay_window_weights(ofx_handle *h, const float *is_weight, const int32_t *n_sampled, int32_t batch,
@@ -1074,9 +1123,22 @@ extern "C" int ofx_replay_window_weights(ofx_handle *h, const float *is_weight, 
   hipLaunchKernelGGL((k_replay_scan<int32_t, int32_t>), dim3(1), dim3(1024), 0, h->stream, N, n_sampled, off);
   hipLaunchKernelGGL(k_replay_window_pack, dim3((unsigned)((N * batch + 255) / 256)), dim3(256), 0, h->stream, N, batch,
                      is_weight, n_sampled, (const int32_t *)off, first, max_rows, out);
-  hipLaunchKernelGGL(k_replay_window_norm, dim3(1), dim3(1024), 0, h->stream, N, (const int32_t *)off, first, max_rows, out);
+  hipLaunchKernelGGL(k_replay_norm<int32_t>, dim3(1), dim3(1024), 0, h->stream, (const int32_t *)off + N, first, max_rows, out);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
+}
+
+// Whether a write-back entry lands - oldest-first row s of arena a (whose rows are `ring`), gathered as g, with the two
+// errors e: the row is in range, the ring row still holds the gathered (tick_prev, ship), both errors are finite.
+// *pos_out = the row's position in rows / mass.
+__device__ __forceinline__ bool entry_lands(const ofx_replay &r, const RowRing &ring, int a, int s, const ofx_transition &g,
+                                            const float *e, size_t *pos_out) {
+  if (s < 0 || s >= ring.count) return false;
+  const size_t pos = (size_t)a * ring.C + ring.at(s);
+  if (r.rows[pos].tick_prev != g.tick_prev || r.rows[pos].ship != g.ship) return false;  // overwritten since sampling
+  if (!isfinite(e[0]) || !isfinite(e[1])) return false;
+  *pos_out = pos;
+  return true;
 }
 
 // one thread per arena, j in order: a duplicate row takes the later packed position's priority
@@ -1084,20 +1146,15 @@ __global__ void k_replay_update_per(int N, int C, int batch, const int32_t *slot
                                     int first, int n_rows, const ofx_transition *rows, const float *td, ofx_replay r) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= N) return;
-  const int count = r.count[a], head = r.head[a];
-  const int first_row = ((head - count) % C + C) % C;
+  const RowRing ring = row_ring(C, r.head[a], r.count[a]);
   const int j0 = max(0, first - off[a]), j1 = min(n_sampled[a], first + n_rows - off[a]);
   float mx = r.mmax[a];
   for (int j = j0; j < j1; j++) {
     const int d = off[a] + j - first;
-    const int s = slot[(size_t)a * batch + j];
-    if (s < 0 || s >= count) continue;
-    const size_t pos = (size_t)a * C + (first_row + s) % C;
-    const ofx_transition &g = rows[d];
-    if (r.rows[pos].tick_prev != g.tick_prev || r.rows[pos].ship != g.ship) continue;  // overwritten since sampling
-    const float e1 = td[2 * (size_t)d], e2 = td[2 * (size_t)d + 1];
-    if (!isfinite(e1) || !isfinite(e2)) continue;
-    const float m = per_mass(e1, e2, r.eps, r.alpha);
+    const float *e = td + 2 * (size_t)d;
+    size_t pos;
+    if (!entry_lands(r, ring, a, slot[(size_t)a * batch + j], rows[d], e, &pos)) continue;
+    const float m = per_mass(e[0], e[1], r.eps, r.alpha);
     r.mass[pos] = m;
     mx = fmaxf(mx, m);
   }
@@ -1129,20 +1186,7 @@ extern "C" int ofx_replay_priorities_host(ofx_handle *h, int32_t arena, float *m
   if ((rc = per_ready(h, "ofx_replay_priorities_host"))) return rc;
   if (!mass_host || !n_host) { ofx_set_error("ofx_replay_priorities_host: bad argument"); return OFX_ERR_INVALID; }
   if (arena < 0 || arena >= h->cfg.n_arenas) { ofx_set_error("ofx_replay_priorities_host: arena out of range"); return OFX_ERR_INVALID; }
-  ofx_replay *r = h->replay;
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  int32_t head, count;
-  OFX_HIP(hipMemcpy(&head, r->head + arena, 4, hipMemcpyDeviceToHost));
-  OFX_HIP(hipMemcpy(&count, r->count + arena, 4, hipMemcpyDeviceToHost));
-  const int C = r->capacity;
-  const int first = ((head - count) % C + C) % C;
-  const float *base = r->mass + (size_t)arena * C;
-  const int n1 = min(count, C - first);
-  if (n1 > 0) OFX_HIP(hipMemcpy(mass_host, base + first, sizeof(float) * n1, hipMemcpyDeviceToHost));
-  if (count > n1) OFX_HIP(hipMemcpy(mass_host + n1, base, sizeof(float) * (count - n1), hipMemcpyDeviceToHost));
-  *n_host = count;
-  return OFX_OK;
+  return ring_to_host(h, arena, h->replay->mass, sizeof(float), mass_host, n_host);
 }
 
 // ---- actor-side initial priorities (Horgan et al. 2018; include/ofx.h states the contract) ---------------------------
@@ -1216,47 +1260,17 @@ extern "C" int ofx_replay_set_actor_values(ofx_handle *h, const float *src_host)
 #define OFX_STREAM_GLOBAL 5u
 #define OFX_GLOBAL_GROUP 256
 
-// lane L of the wave sums chunk L of the arena's `valid` eligible rows; every lane runs the same chain over the 64 chunk
-// totals (the summation order of k_replay_sample_per).  Returns the total, *incl = the lane's inclusive chunk prefix.
-__device__ __forceinline__ double arena_chunk_chain(const float *mass, int C, int base, int valid, int lane, double *incl) {
-  const int cs = (valid + 63) / 64;
-  const int lo = min(lane * cs, valid), hi = min(lo + cs, valid);
-  double t = 0.0;
-  for (int i = lo; i < hi; i++) t += (double)mass[(base + i) % C];
-  double total = 0.0, in = 0.0;
-  for (int k = 0; k < 64; k++) {
-    total += __shfl(t, k);
-    if (k == lane) in = total;
-  }
-  *incl = in;
-  return total;
-}
-
-// One wave per arena.  The expiry walk of k_replay_sample, 64 rows per ballot: the first row whose `state` frame is
-// still in the ring ends it.  PER: T[a] by the chunk scheme.
+// One wave per arena: skip, v and, PER, T[a] by the chunk scheme.
 template <bool PER>
 __global__ __launch_bounds__(256) void k_global_arena(int N, int C, int F, ofx_replay r) {
   const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (a >= N) return;  // wave-uniform
-  const int count = r.count[a], head = r.head[a];
-  const int first = ((head - count) % C + C) % C;
-  const ofx_transition *rows = r.rows + (size_t)a * C;
-  int skip = count;
-  for (int base = 0; base < count; base += 64) {  // wave-uniform trip count
-    const int i = base + lane;
-    bool live = false;
-    if (i < count) {
-      const ofx_transition &o = rows[(first + i) % C];
-      const int f = o.frame_prev;
-      live = (unsigned)f < (unsigned)F && r.frame_tick[(size_t)a * F + f] == o.tick_prev;
-    }
-    const unsigned long long hit = __ballot(live);
-    if (hit) { skip = base + __ffsll((long long)hit) - 1; break; }
-  }
-  const int valid = count - skip;
+  const RowRing ring = row_ring(C, r.head[a], r.count[a]);
+  const int skip = expired_rows_wave(r, a, F, ring, lane);
+  const int valid = ring.count - skip;
   if constexpr (PER) {
     double incl;
-    const double total = arena_chunk_chain(r.mass + (size_t)a * C, C, first + skip, valid, lane, &incl);
+    const double total = arena_chunk_chain(r.mass + (size_t)a * C, ring, skip, valid, lane, &incl);
     if (lane == 0) r.g_T[a] = total;
   }
   if (lane == 0) { r.g_skip[a] = skip; r.g_v[a] = valid; }
@@ -1345,52 +1359,29 @@ __global__ __launch_bounds__(256) void k_global_draw(GlobalDrawParams p) {
     }
     const int a = lo < p.N ? lo : global_arena_of(p.r.g_voff, p.N, R - 1);
     const double up = u - (a ? p.r.g_G[a - 1] : 0.0);
-    const int C = p.C, count = p.r.count[a], head = p.r.head[a], skip = p.r.g_skip[a], valid = p.r.g_v[a];
-    const int base = ((head - count) % C + C) % C + skip;
-    const float *mass = p.r.mass + (size_t)a * C;
+    const RowRing ring = row_ring(p.C, p.r.head[a], p.r.count[a]);
+    const int skip = p.r.g_skip[a], valid = p.r.g_v[a];
+    const float *mass = p.r.mass + (size_t)a * p.C;
     int pick = valid - 1;  // rounding left no row above u': the arena's last eligible row
     if (valid > 0) {       // wave-uniform (an arena with G > G[a - 1] has rows; the fallback arena has one too)
       double incl;
-      arena_chunk_chain(mass, C, base, valid, lane, &incl);
+      arena_chunk_chain(mass, ring, skip, valid, lane, &incl);
       const int cs = (valid + 63) / 64, nchunks = (valid + cs - 1) / cs;
-      const unsigned long long hit = __ballot(lane < nchunks && incl > up);
+      const unsigned long long hit = __ballot(lane < nchunks && incl > up);  // u' is wave-uniform: one ballot finds the chunk
       if (hit) {
         const int k = __ffsll((long long)hit) - 1;
         double ex = __shfl(incl, max(k - 1, 0));
         if (k == 0) ex = 0.0;
-        const int r0 = k * cs, r1 = min(r0 + cs, valid);
-        double run = 0.0;
-        pick = r1 - 1;
-        for (int i = r0; i < r1; i++) {
-          run += (double)mass[(base + i) % C];
-          if (ex + run > up) { pick = i; break; }
-        }
+        pick = chunk_pick(mass, ring, skip, valid, k, ex, up);
       }
     }
     if (lane == 0) {
-      const double m = valid > 0 ? (double)mass[(base + pick) % C] : 0.0;
+      const double m = valid > 0 ? (double)mass[ring.at(skip + pick)] : 0.0;
       p.arena[j] = a;
       p.slot[j] = skip + pick;
-      p.is_weight[j] = total > 0.0 ? (float)pow((double)R * m / total, -p.beta) : 1.f;
+      p.is_weight[j] = is_weight_raw((double)R, m, total, p.beta);
     }
   }
-}
-
-// the n = min(n_rows, R) raw weights over their maximum (the max is exact in any order)
-__global__ __launch_bounds__(1024) void k_global_norm(int N, int n_rows, const long long *voff, float *w) {
-  __shared__ float red[1024];
-  const int tid = threadIdx.x, n = (int)(voff[N] < (long long)n_rows ? voff[N] : (long long)n_rows);
-  float m = 0.f;
-  for (int d = tid; d < n; d += 1024) m = fmaxf(m, w[d]);
-  red[tid] = m;
-  __syncthreads();
-  for (int k = 512; k > 0; k >>= 1) {
-    if (tid < k) red[tid] = fmaxf(red[tid], red[tid + k]);
-    __syncthreads();
-  }
-  const float mx = red[0];
-  if (mx > 0.f)
-    for (int d = tid; d < n; d += 1024) w[d] = w[d] / mx;
 }
 
 static int global_workspace(ofx_handle *h) {
@@ -1442,7 +1433,8 @@ extern "C" int ofx_replay_sample_global(ofx_handle *h, uint64_t seed, uint32_t d
                        dim3(OFX_GLOBAL_GROUP), 0, h->stream, N, *r);
     hipLaunchKernelGGL(k_global_group_chain, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, N, *r);
     hipLaunchKernelGGL(k_global_draw<true>, draws, dim3(256), 0, h->stream, p);
-    hipLaunchKernelGGL(k_global_norm, dim3(1), dim3(1024), 0, h->stream, N, n_rows, (const long long *)r->g_voff, is_weight);
+    hipLaunchKernelGGL(k_replay_norm<long long>, dim3(1), dim3(1024), 0, h->stream, (const long long *)r->g_voff + N, 0, n_rows,
+                       is_weight);
   } else {
     hipLaunchKernelGGL(k_global_draw<false>, draws, dim3(256), 0, h->stream, p);
   }
@@ -1504,51 +1496,30 @@ extern "C" int ofx_replay_gather_list(ofx_handle *h, const int32_t *arena, const
   return OFX_OK;
 }
 
-// entry j may write: in range, the ring row still holds the gathered (tick_prev, ship), both errors finite
-__device__ __forceinline__ bool list_entry_lands(const ofx_replay &r, int N, int C, int a, int s, const ofx_transition &g,
-                                                 const float *td, int j, size_t *pos_out) {
-  if (a < 0 || a >= N) return false;
-  const int count = r.count[a], head = r.head[a];
-  if (s < 0 || s >= count) return false;
-  const size_t pos = (size_t)a * C + (((head - count) % C + C) % C + s) % C;
-  if (r.rows[pos].tick_prev != g.tick_prev || r.rows[pos].ship != g.ship) return false;  // overwritten since sampling
-  if (!isfinite(td[2 * (size_t)j]) || !isfinite(td[2 * (size_t)j + 1])) return false;
-  *pos_out = pos;
-  return true;
-}
-
 // One thread per entry.  Every entry that lands raises mmax; of a run of adjacent entries naming one (arena, slot) the
-// last one that lands writes the mass (k_replay_update_per's serial walk, without the walk).
+// last one that lands writes the mass (the outcome of k_replay_update_per's serial walk, without the walk).
 __global__ __launch_bounds__(256) void k_replay_update_list(int N, int C, int n, const int32_t *arena, const int32_t *slot,
                                                             const ofx_transition *rows, const float *td, ofx_replay r) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
   const int a = arena[j], s = slot[j];
+  if (a < 0 || a >= N) return;  // the entry names no arena
+  const RowRing ring = row_ring(C, r.head[a], r.count[a]);
   size_t pos;
-  if (!list_entry_lands(r, N, C, a, s, rows[j], td, j, &pos)) return;
+  if (!entry_lands(r, ring, a, s, rows[j], td + 2 * (size_t)j, &pos)) return;
   const float m = per_mass(td[2 * (size_t)j], td[2 * (size_t)j + 1], r.eps, r.alpha);
   atomicMax(reinterpret_cast<unsigned int *>(r.mmax + a), __float_as_uint(m));  // masses are >= 0: the bit patterns order like the values
   for (int k = j + 1; k < n && arena[k] == a && slot[k] == s; k++) {
     size_t other;
-    if (list_entry_lands(r, N, C, a, s, rows[k], td, k, &other)) return;  // a later entry of the run wins
+    if (entry_lands(r, ring, a, s, rows[k], td + 2 * (size_t)k, &other)) return;  // a later entry of the run wins
   }
   r.mass[pos] = m;
 }
 
 // every arena's mmax <- the maximum over the arenas: under global competition a new row enters at the global maximum
 __global__ __launch_bounds__(1024) void k_replay_level_mmax(int N, float *mmax) {
-  __shared__ float red[1024];
-  const int tid = threadIdx.x;
-  float m = 0.f;
-  for (int a = tid; a < N; a += 1024) m = fmaxf(m, mmax[a]);
-  red[tid] = m;
-  __syncthreads();
-  for (int k = 512; k > 0; k >>= 1) {
-    if (tid < k) red[tid] = fmaxf(red[tid], red[tid + k]);
-    __syncthreads();
-  }
-  const float mx = red[0];
-  for (int a = tid; a < N; a += 1024) mmax[a] = mx;
+  const float mx = block_max(mmax, N);
+  for (int a = threadIdx.x; a < N; a += 1024) mmax[a] = mx;
 }
 
 extern "C" int ofx_replay_update_priorities_list(ofx_handle *h, const int32_t *arena, const int32_t *slot, int32_t n,
@@ -1614,8 +1585,7 @@ static void wr(uint8_t *p, T v) { memcpy(p, &v, sizeof(T)); }
 
 // One wave per map m = (arena * F + slot) * 2 + which of the chunk.  WRITE = false: counts[m] = nonzero words;
 // WRITE = true: the map's pairs at pairs[off[m] ...] in ascending word index.  Lane l of iteration k0 holds words
-// 4 (k0 + l) .. + 3, so ascending order is lane-major, then component: position = the nonzero words of all four
-// components in the lanes below + the lane's own lower components.
+// 4 (k0 + l) .. + 3: nonzero_place's order.
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_replay_pack(int n_maps, int words, const uint32_t *bits, const int32_t *frame_tick,
                                                      uint32_t *counts, const unsigned long long *off, uint2 *pairs) {
@@ -1627,7 +1597,6 @@ __global__ __launch_bounds__(256) void k_replay_pack(int n_maps, int words, cons
   }
   const uint4 *src = reinterpret_cast<const uint4 *>(bits + (size_t)m * words);
   const int q = words >> 2;
-  const unsigned long long below = (1ull << lane) - 1ull;
   unsigned long long run = 0ull;
   if constexpr (WRITE) run = off[m];
   for (int k0 = 0; k0 < q; k0 += 64) {  // wave-uniform trip count: the ballots see every lane
@@ -1635,13 +1604,7 @@ __global__ __launch_bounds__(256) void k_replay_pack(int n_maps, int words, cons
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (k < q) v = src[k];
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    unsigned long long pos = run;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const unsigned long long bal = __ballot(w[c] != 0u);
-      pos += (unsigned long long)__popcll(bal & below);
-      run += (unsigned long long)__popcll(bal);
-    }
+    unsigned long long pos = nonzero_place(w, lane, &run);
     if constexpr (WRITE) {
 #pragma unroll
       for (int c = 0; c < 4; c++)
@@ -1936,9 +1899,9 @@ extern "C" int ofx_replay_blob_check(const void *src_host, size_t bytes, int32_t
     if (count < 0 || count > d.C) BLOB_FAIL("count %d of arena %d outside [0, %d]", count, a, d.C);
     if (app < count) BLOB_FAIL("appended %lld of arena %d below its count %d", (long long)app, a, count);
     const uint8_t *rows = raw + roff[RAW_ROWS] + sizeof(ofx_transition) * (size_t)a * d.C;
-    const int first = ((head - count) % d.C + d.C) % d.C;
+    const RowRing ring = row_ring(d.C, head, count);
     for (int i = 0; i < count; i++) {  // the live rows: the sampler and the fit index with these
-      const ofx_transition t = rd<ofx_transition>(rows + sizeof(ofx_transition) * (size_t)((first + i) % d.C));
+      const ofx_transition t = rd<ofx_transition>(rows + sizeof(ofx_transition) * (size_t)ring.at(i));
       if (t.frame_prev < 0 || t.frame_prev >= d.F) BLOB_FAIL("row %d of arena %d: frame_prev %d outside [0, %d)", i, a, t.frame_prev, d.F);
       if (t.frame_next < 0 || t.frame_next >= d.F) BLOB_FAIL("row %d of arena %d: frame_next %d outside [0, %d)", i, a, t.frame_next, d.F);
       if (t.ship < 0 || t.ship >= d.M) BLOB_FAIL("row %d of arena %d: ship %d outside [0, %d)", i, a, t.ship, d.M);

@@ -1,6 +1,6 @@
-"""What the replay-memory tests share on the device: capture masks that leave arenas with 0, 1, 4 and 11 rows, the rows
-of a window without their maps, hand-set masses, and how many of an arena's oldest rows lost their frame.  A helper
-module (not collected)."""
+"""What the replay-memory tests share on the device: capture masks that leave arenas with 0, 1, 4 and 11 rows, the wide
+memory whose arenas hold more rows than the samplers have chunks, the rows of a window without their maps, hand-set
+masses, and how many of an arena's oldest rows lost their frame.  A helper module (not collected)."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +20,49 @@ def varied_masks(NG, M):
         mk[3, 0] = t < 5
         return mk
     return masks
+
+
+WIDE_N, WIDE_M, WIDE_CAPACITY, WIDE_TICKS, WIDE_RESTART, WIDE_FRAMES = 8, 8, 200, 70, 10, 24
+_WIDE_SHIPS = (0, 8, 6, 4, 3, 2, 1, 8)
+
+
+def wide_masks(NG=WIDE_N, M=WIDE_M):
+    """The memory of WIDE_CAPACITY rows the samplers are held to beyond one row per chunk: arena a captures with its
+    first _WIDE_SHIPS[a] ships (arena 0 never), the last arena only before lock-step 25, so that its frame ring stands
+    still while it holds more than 128 eligible rows.  With a new episode every WIDE_RESTART lock-steps the ships come
+    back, the busy arenas' row rings wrap within WIDE_TICKS lock-steps, and a ring of WIDE_FRAMES frames expires more
+    than 64 of their oldest rows."""
+    assert (NG, M) == (WIDE_N, WIDE_M)
+    def masks(t):
+        mk = np.zeros((NG, M), np.uint8)
+        for a, k in enumerate(_WIDE_SHIPS):
+            mk[a, :k] = 1
+        if t >= 25:
+            mk[NG - 1] = 0
+        return mk
+    return masks
+
+
+def wide_preconditions(cnt, appended, skip, frames, batch=None):
+    """What a wide memory must hold for its test to reach the code one row per chunk never reaches.  cnt / appended
+    [N] of replay_count, skip [N] expired oldest rows.  Prints the figures before it asserts."""
+    C = WIDE_CAPACITY
+    cnt, skip = np.asarray(cnt, np.int64), np.asarray(skip, np.int64)
+    valid = cnt - skip
+    first = (np.asarray(appended, np.int64) % C - cnt) % C   # head = appended % C
+    cs = -(-valid // 64)
+    print("wide memory: count %s skip %s valid %s first %s" % (cnt.tolist(), skip.tolist(), valid.tolist(), first.tolist()))
+    assert (cnt == C).any() and (appended > C).any(), "no row ring wrapped"
+    assert (valid >= 129).any(), "no arena with chunks of three rows"
+    assert ((valid >= 65) & (valid <= 128)).any(), "no arena with chunks of two rows"
+    assert ((valid > 0) & (valid % np.maximum(cs, 1) != 0)).any(), "no ragged last chunk"
+    assert ((valid > 0) & (first + skip + valid > C)).any(), "no arena whose eligible rows wrap the ring"
+    if frames:
+        assert (skip >= 65).any(), "no expiry walk of more than 64 rows"
+    else:
+        assert (skip == 0).all()
+    if batch is not None and batch > 64:
+        assert (valid >= batch).any(), "no arena draws more than 64 rows"
 
 
 def gather_rows(b, slot, n_s, batch, first, max_rows):

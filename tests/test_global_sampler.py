@@ -9,6 +9,7 @@ from scipy import stats
 
 from tests import global_sample_oracle as gso
 from tests import per_oracle
+from tests import replay_cases as _wide
 
 GLOBAL_SYMBOLS = ["ofx_replay_sample_global", "ofx_replay_gather_list", "ofx_replay_update_priorities_list"]
 W = H = 400
@@ -157,7 +158,7 @@ def test_trainer_argument_checks(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------ GPU
 def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_base=0, prioritize=True, alpha=0.6,
-             masks=None, packed=False):
+             masks=None, packed=False, restart_every=0):
     """A seeded collecting rollout with capture; masks(t) -> uint8 [N_global][M] of the capturing ships at tick t
     (tests/test_prioritized_replay.py's helper, with the choice of the frame store)."""
     from ofighters_amd import ArenaBatch, DeviceBuffer
@@ -171,6 +172,8 @@ def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_bas
     for t in range(ticks):
         mk = np.ones((N, M), np.uint8) if masks is None else masks(t)[arena_base:arena_base + N]
         b.sync()
+        if restart_every and t and t % restart_every == 0:
+            b.restart_random(seed)
         mask_d.upload(np.ascontiguousarray(mk))
         b.bot_actions(["random"] * M, seed, tick=t)
         b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
@@ -242,21 +245,33 @@ def _check_sampler(b, skip, v, n_rows_list, draws, arena_base=0):
             assert (np.diff(key) >= 0).all()
 
 
+# N == WIDE_N: the memory of tests/replay_cases.py's wide_masks - chunks of more than one row, ragged last chunks, a
+# second round of the expiry walk and eligible rows across the ring's end
 @pytest.mark.gpu
-@pytest.mark.parametrize("packed", [False, True])
-@pytest.mark.parametrize("frames", [0, 4])
-@pytest.mark.parametrize("N", [5, 300])
+@pytest.mark.parametrize("N,frames,packed", [
+    pytest.param(N, frames, packed, id="%d-%d-%s" % (N, frames, packed))
+    for packed in (False, True) for frames in (0, 4) for N in (5, 300)] + [
+    pytest.param(_wide.WIDE_N, frames, packed, id="wide-%d-%s" % (frames, packed))
+    for frames, packed in ((0, False), (_wide.WIDE_FRAMES, False), (_wide.WIDE_FRAMES, True))])
 def test_sampler_equals_restatement(N, frames, packed):
     from tests.replay_cases import stale_rows as _skip, varied_masks as _varied_masks
-    M = 4
-    b = _rollout(N, M, capacity=40, frames=frames, masks=_varied_masks(N, M), alpha=1.0, packed=packed)
-    cnt, _ = b.replay_count()
-    assert cnt[0] == 0 and cnt[1] == 1 and 0 < cnt[3] <= 4 < cnt[2] <= 11 and cnt[4] == 40 and (cnt == 40).sum() > (N - 4) // 2   # rings wrapped
+    wide = N == _wide.WIDE_N
+    if wide:
+        M = _wide.WIDE_M
+        b = _rollout(N, M, capacity=_wide.WIDE_CAPACITY, frames=frames, ticks=_wide.WIDE_TICKS, masks=_wide.wide_masks(),
+                     alpha=1.0, packed=packed, restart_every=_wide.WIDE_RESTART)
+    else:
+        M = 4
+        b = _rollout(N, M, capacity=40, frames=frames, masks=_varied_masks(N, M), alpha=1.0, packed=packed)
+        cnt, _ = b.replay_count()
+        assert cnt[0] == 0 and cnt[1] == 1 and 0 < cnt[3] <= 4 < cnt[2] <= 11 and cnt[4] == 40 and (cnt == 40).sum() > (N - 4) // 2   # rings wrapped
     _spread_masses(b, N + frames)
     allm = np.concatenate([b.replay_priorities(a) for a in range(min(N, 16))])
     assert allm.max() / allm.min() > 1e5                                           # six decades (alpha = 1)
     skip, v = _eligibility(b)
-    if N == 5:
+    if wide:
+        _wide.wide_preconditions(*b.replay_count(), skip, frames)
+    if N == 5 or wide:
         assert skip == [_skip(b, a) for a in range(N)]                             # the host inspections agree
     if frames:
         assert max(skip) > 0, "no row expired"

@@ -7,6 +7,7 @@ import pytest
 from scipy import stats
 
 from tests import per_oracle
+from tests import replay_cases as _wide
 from tests.replay_cases import gather_rows as _gather_rows, set_masses as _set_masses, stale_rows as _skip, varied_masks as _varied_masks
 
 PER_SYMBOLS = ["ofx_replay_prioritize", "ofx_replay_sample_prioritized", "ofx_replay_window_weights",
@@ -82,8 +83,9 @@ def test_restatement_never_draws_expired_rows():
 
 # ------------------------------------------------------------------------------------------------------ GPU
 def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_base=0, prioritize=True, alpha=0.6,
-             masks=None):
-    """A seeded collecting rollout with capture; masks(t) -> uint8 [N_global][M] of the capturing ships at tick t."""
+             masks=None, restart_every=0):
+    """A seeded collecting rollout with capture; masks(t) -> uint8 [N_global][M] of the capturing ships at tick t;
+    restart_every: a new episode every so many lock-steps (0 = one episode)."""
     from ofighters_amd import ArenaBatch, DeviceBuffer
     b = ArenaBatch(N, M, arena_base=arena_base)
     b.replay_create(capacity, frames)
@@ -95,6 +97,8 @@ def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_bas
     for t in range(ticks):
         mk = np.ones((N, M), np.uint8) if masks is None else masks(t)[arena_base:arena_base + N]
         b.sync()
+        if restart_every and t and t % restart_every == 0:
+            b.restart_random(seed)
         mask_d.upload(np.ascontiguousarray(mk))
         b.bot_actions(["random"] * M, seed, tick=t)
         b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
@@ -155,13 +159,26 @@ def test_capture_writes_the_running_max():
     b.close()
 
 
+# "wide": the memory of tests/replay_cases.py's wide_masks - chunks of more than one row, fewer than 64 and 64 chunks,
+# ragged last chunks, expiry walks past 64 rows, eligible rows across the ring's end and a second round of the draw loop
 @pytest.mark.gpu
-@pytest.mark.parametrize("frames,batch", [(0, 8), (0, 32), (4, 8), (4, 32)])
-def test_sampler_equals_restatement(frames, batch):
-    N, M = 64, 4
-    b = _rollout(N, M, capacity=40, frames=frames, masks=_varied_masks(N, M))
-    cnt, _ = b.replay_count()
-    assert cnt[0] == 0 and cnt[1] == 1 and 0 < cnt[3] <= 4 < cnt[2] <= 11 and (cnt == 40).sum() > 32   # rings wrapped
+@pytest.mark.parametrize("wide,frames,batch", [
+    pytest.param(False, 0, 8, id="0-8"), pytest.param(False, 0, 32, id="0-32"), pytest.param(False, 4, 8, id="4-8"),
+    pytest.param(False, 4, 32, id="4-32"), pytest.param(True, 0, 96, id="wide-0-96"),
+    pytest.param(True, _wide.WIDE_FRAMES, 96, id="wide-%d-96" % _wide.WIDE_FRAMES),
+    pytest.param(True, _wide.WIDE_FRAMES, 32, id="wide-%d-32" % _wide.WIDE_FRAMES)])
+def test_sampler_equals_restatement(wide, frames, batch):
+    if wide:
+        N, M = _wide.WIDE_N, _wide.WIDE_M
+        b = _rollout(N, M, capacity=_wide.WIDE_CAPACITY, frames=frames, ticks=_wide.WIDE_TICKS, masks=_wide.wide_masks(),
+                     restart_every=_wide.WIDE_RESTART)
+        cnt, app = b.replay_count()
+        _wide.wide_preconditions(cnt, app, [_skip(b, a) for a in range(N)], frames, batch)
+    else:
+        N, M = 64, 4
+        b = _rollout(N, M, capacity=40, frames=frames, masks=_varied_masks(N, M))
+        cnt, _ = b.replay_count()
+        assert cnt[0] == 0 and cnt[1] == 1 and 0 < cnt[3] <= 4 < cnt[2] <= 11 and (cnt == 40).sum() > 32   # rings wrapped
     rs = np.random.RandomState(frames + batch)
     spread = 10.0 ** rs.uniform(-3, 3, 400 * 64)
     _set_masses(b, lambda r: np.stack([spread[:len(r)], np.zeros(len(r))], 1))

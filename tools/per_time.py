@@ -1,11 +1,19 @@
 """Prioritized replay timing: the PER kernels at 4096 arenas x 400 rows x batch 8 (hipEvents on the handle's stream,
 after a warm-up; the uniform sampler beside them), and one 256-row DeviceTrainer.replay with PER on and off (wall time
-of the call, which ends in the fit's synchronisation).  Usage: python tools/per_time.py [reps]"""
+of the call, which ends in the fit's synchronisation).  Usage: python tools/per_time.py [reps] [--package DIR]
+--package DIR imports ofighters_amd from DIR instead of this tree (tools/global_replay_time.py's option): two builds on
+one card in one session."""
 import os
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = ROOT
+if "--package" in sys.argv:
+    at = sys.argv.index("--package")
+    PKG = os.path.abspath(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+sys.path.insert(0, PKG)
 import numpy as np
 
 from ofighters_amd import ArenaBatch, DeviceBuffer
@@ -58,7 +66,7 @@ def trainer(prioritized):
 
 
 def main():
-    out = []
+    out = ["package %s" % os.path.relpath(PKG, ROOT)]
     b, tr = trainer(True)
     cnt, _ = b.replay_count()
     out.append("arenas %d, rows per arena %d..%d, batch %d, %d reps after 5 warm-up calls" % (N, cnt.min(), cnt.max(), BATCH, REPS))
