@@ -51,10 +51,10 @@ def encode(d):
         assert a.shape == shape, (name, a.shape, shape)
         b = a.tobytes()
         raw += b + b"\0" * (-len(b) % 8)
-    counts = (maps != 0).sum(axis=1).astype("<u4")
-    mi, wi = np.nonzero(maps)                        # row-major: map order, ascending word index inside a map
-    pairs = np.empty((len(wi), 2), "<u4")
-    pairs[:, 0], pairs[:, 1] = wi, maps[mi, wi]
+    counts = np.count_nonzero(maps, axis=1).astype("<u4")
+    at = np.flatnonzero(maps)                        # row-major: map order, ascending word index inside a map
+    pairs = np.empty((len(at), 2), "<u4")
+    pairs[:, 0], pairs[:, 1] = at % words, maps.reshape(-1)[at]
     head = struct.pack("<II8i2f4Q", MAGIC, VERSION, d["W"], d["H"], d["M"], d["C"], d["F"], words, d["n"], int(d["per"]),
                        d["alpha"] if d["per"] else 0.0, d["eps"] if d["per"] else 0.0, len(raw), counts.nbytes, pairs.nbytes, 0)
     assert len(head) == HEADER
@@ -69,23 +69,45 @@ def header(blob):
     return d
 
 
+SCALARS = ("W", "H", "M", "C", "F", "per", "alpha", "eps")
+
+
+def concat(dicts):
+    """The decoded dicts of consecutive chunks of one memory -> the dict of the chunk that spans them: every raw array,
+    `maps` and (where the dicts carry them) `counts` concatenated along n; the scalars must agree."""
+    dicts = list(dicts)
+    first = dicts[0]
+    out = {k: first[k] for k in SCALARS}
+    for d in dicts[1:]:
+        for k in SCALARS:
+            same = np.float32(d[k]) == np.float32(first[k]) if k in ("alpha", "eps") else d[k] == first[k]
+            assert same, (k, d[k], first[k])
+    out["n"] = int(sum(d["n"] for d in dicts))
+    names = [name for name, _, _ in raw_arrays(first)] + ["maps"] + (["counts"] if all("counts" in d for d in dicts) else [])
+    for name in names:
+        for d in dicts:
+            assert len(d[name]) == d["n"], name
+        out[name] = np.concatenate([d[name] for d in dicts], axis=0)
+    return out
+
+
 def decode(blob):
-    buf = np.frombuffer(bytes(blob) if not isinstance(blob, np.ndarray) else blob.tobytes(), np.uint8)
-    d = header(buf.tobytes())
+    buf = (np.ascontiguousarray(blob).view(np.uint8).reshape(-1) if isinstance(blob, np.ndarray)
+           else np.frombuffer(bytes(blob), np.uint8))
+    d = header(buf[:HEADER].tobytes())
     words = d["words"]
     assert words == d["W"] * d["H"] // 32
     lay = layout(d)
     for name, dt, shape in raw_arrays(d):
         at, nb = lay[name]
-        d[name] = np.frombuffer(buf[at:at + nb].tobytes(), dt).reshape(shape).copy()
+        d[name] = buf[at:at + nb].view(dt).reshape(shape).copy()
     n_maps = d["n"] * d["F"] * 2
     assert lay["counts"] == HEADER + d["raw_bytes"] and d["count_bytes"] == 4 * n_maps
-    counts = np.frombuffer(buf[lay["counts"]:lay["pairs"]].tobytes(), "<u4")
+    counts = buf[lay["counts"]:lay["pairs"]].view("<u4")
     assert d["pair_bytes"] == 8 * int(counts.sum()) and len(buf) == lay["pairs"] + d["pair_bytes"]
-    pairs = np.frombuffer(buf[lay["pairs"]:].tobytes(), "<u4").reshape(-1, 2)
+    pairs = buf[lay["pairs"]:].view("<u4").reshape(-1, 2)
     maps = np.zeros((n_maps, words), np.uint32)
-    mi = np.repeat(np.arange(n_maps), counts)
-    maps[mi, pairs[:, 0]] = pairs[:, 1]
+    maps.reshape(-1)[np.repeat(np.arange(n_maps, dtype=np.int64) * words, counts) + pairs[:, 0]] = pairs[:, 1]
     d["counts"] = counts.reshape(d["n"], d["F"], 2).copy()
     d["maps"] = maps.reshape(d["n"], d["F"], 2, words)
     return d

@@ -1,6 +1,7 @@
-"""What the replay-memory tests share on the device: capture masks that leave arenas with 0, 1, 4 and 11 rows, the wide
-memory whose arenas hold more rows than the samplers have chunks, the rows of a window without their maps, hand-set
-masses, and how many of an arena's oldest rows lost their frame.  A helper module (not collected)."""
+"""What the replay-memory tests share on the device: the collecting rollout on any map size, capture masks that leave
+arenas with 0, 1, 4 and 11 rows, the wide memory whose arenas hold more rows than the samplers have chunks, the rows of a
+window without their maps, hand-set masses, and how many of an arena's oldest rows lost their frame.  A helper module
+(not collected)."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +21,44 @@ def varied_masks(NG, M):
         mk[3, 0] = t < 5
         return mk
     return masks
+
+
+def rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_base=0, prioritize=True, alpha=0.6,
+            masks=None, packed=False, restart_every=0, width=400, height=400, ship_radius=None, laser_radius=None,
+            pool_pairs=0, after_spawn=None):
+    """A seeded collecting rollout with capture on a width x height map; masks(t) -> uint8 [N_global][M] of the
+    capturing ships at tick t; restart_every: a new episode every so many lock-steps (0 = one episode); packed /
+    pool_pairs: the frame store; after_spawn(b) runs after the spawn and after every restart (to place ships)."""
+    from ofighters_amd import ArenaBatch, DeviceBuffer
+    cfg = dict(width=width, height=height, arena_base=arena_base)
+    if ship_radius is not None:
+        cfg["ship_radius"] = ship_radius
+    if laser_radius is not None:
+        cfg["laser_radius"] = laser_radius
+    b = ArenaBatch(N, M, **cfg)
+    b.replay_create(capacity, frames, packed=packed, pool_pairs=pool_pairs)
+    if prioritize:
+        b.replay_prioritize(alpha, 1e-3)
+    b.spawn_random(seed)
+    if after_spawn:
+        after_spawn(b)
+    ia_d, ip_d = DeviceBuffer(4 * N * M), DeviceBuffer(8 * N * M)
+    mask_d = DeviceBuffer(N * M)
+    for t in range(ticks):
+        mk = np.ones((N, M), np.uint8) if masks is None else masks(t)[arena_base:arena_base + N]
+        b.sync()
+        if restart_every and t and t % restart_every == 0:
+            b.restart_random(seed)
+            if after_spawn:
+                after_spawn(b)
+        mask_d.upload(np.ascontiguousarray(mk))
+        b.bot_actions(["random"] * M, seed, tick=t)
+        b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+        b.policy_actions(out_ptr=b._actions.ptr, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
+        b.replay_capture(t, mask_d.ptr, ia_d.ptr, ip_d.ptr)
+        b.step(actions_ptr=b._actions.ptr)
+    b.sync()
+    return b
 
 
 WIDE_N, WIDE_M, WIDE_CAPACITY, WIDE_TICKS, WIDE_RESTART, WIDE_FRAMES = 8, 8, 200, 70, 10, 24
@@ -101,6 +140,22 @@ def set_masses(b, td_fn):
     b.replay_update_priorities(slot_d, n_d, Cap, 0, total, rows.ptr, td_d.ptr)
     b.sync()
     return r, td
+
+
+def spread_masses(b, seed, heavy=()):
+    """Hand-set masses over six decades: 10^U(-3, 3) per row (seeded) as the first TD error, the second zero.  heavy:
+    arenas whose rows all sit at the top of that range, 1000, so that a stratified draw of a few thousand rows over the
+    whole memory cannot pass them by."""
+    rs = np.random.RandomState(seed)
+    spread = 10.0 ** rs.uniform(-3, 3, b.N * b.replay_capacity)
+    cnt, _ = b.replay_count()
+    top = np.isin(np.repeat(np.arange(b.N), cnt), list(heavy))
+
+    def td(r):
+        e = spread[:len(r)].copy()
+        e[top] = 1000.0
+        return np.stack([e, np.zeros(len(r))], 1)
+    return set_masses(b, td)
 
 
 def stale_rows(b, a):

@@ -161,6 +161,64 @@ def test_blob_check_reads_an_unaligned_blob(good):
     assert rc == nat.OFX_OK, nat.lib().ofx_last_error()
 
 
+# -------------------------------------------------------------------------------- stitching the dicts of chunks
+def _synthetic(n, w, h, per, seed, M=3, Cc=5, F=7):
+    """A memory of n arenas on w x h maps that no device wrote: empty slots, all-zero stored maps, full maps, the first
+    and the last word set, arenas without rows."""
+    rng = np.random.default_rng(seed)
+    words = w * h // 32
+    d = dict(W=w, H=h, M=M, C=Cc, F=F, n=n, per=per, alpha=np.float32(0.7), eps=np.float32(1e-2))
+    d["frame_tick"] = rng.integers(-1, 50, (n, F)).astype(np.int32)
+    d["frame_tick"][n // 2] = -1                                       # an arena whose ring is empty
+    d["frame_tick"][0, 0], d["frame_tick"][n - 1, F - 1] = 3, 4
+    maps = rng.integers(0, 2**32, (n, F, 2, words), dtype=np.uint64).astype(np.uint32)
+    maps[rng.random((n, F, 2, words)) < 0.6] = 0
+    maps[rng.random((n, F, 2)) < 0.2] = 0                              # all-zero stored maps
+    maps[0, 0, 0], maps[n - 1, F - 1, 1] = 0xFFFFFFFF, 0x80000001      # every word set; the last map of the chunk
+    maps[d["frame_tick"] < 0] = 0
+    d["maps"] = maps
+    rows = np.zeros((n, Cc), ckpt_blob.TRANSITION)
+    rows.view(np.uint8)[:] = rng.integers(0, 256, rows.view(np.uint8).shape, dtype=np.uint8)
+    d["rows"] = rows
+    for k in ("frame_head", "cur_slot", "head", "count"):
+        d[k] = rng.integers(0, Cc, n).astype(np.int32)
+    d["appended"] = rng.integers(0, 2**40, n).astype(np.int64)
+    d["has_prev"], d["latched"] = (rng.integers(0, 2, (n, M)).astype(np.uint8) for _ in range(2))
+    for k in ("prev_iaction", "prev_px", "prev_py", "prev_tick", "prev_slot"):
+        d[k] = rng.integers(0, 1000, (n, M)).astype(np.int32)
+    d["prev_head"] = rng.random((n, M, 8)).astype(np.float32)
+    if per:
+        d["mass"], d["mmax"] = rng.random((n, Cc)).astype(np.float32), rng.random(n).astype(np.float32)
+    return d
+
+
+def _chunk(d, lo, hi):
+    out = {k: v for k, v in d.items() if not isinstance(v, np.ndarray) or v.ndim == 0}
+    out.update({k: v[lo:hi] for k, v in d.items() if isinstance(v, np.ndarray) and v.ndim})
+    out["n"] = hi - lo
+    return out
+
+
+@pytest.mark.parametrize("per", [0, 1])
+@pytest.mark.parametrize("w,h", [(16, 8), (32, 32)])
+def test_concat_of_decoded_chunks_is_the_spanning_chunk(w, h, per):
+    """7 arenas cut into 2 + 5 and into 4 + 1 + 2: the chunks' blobs decoded, stitched and encoded are the blob of the
+    whole, byte for byte - odd array sizes, so the 8-byte padding of the raw arrays differs between chunk and whole."""
+    ab = _synthetic(7, w, h, per, seed=w + per)
+    whole = ckpt_blob.encode(ab)
+    for cuts in ((0, 2, 7), (0, 4, 5, 7)):
+        parts = [_chunk(ab, lo, hi) for lo, hi in zip(cuts, cuts[1:])]
+        blobs = [ckpt_blob.encode(p) for p in parts]
+        assert len(set(len(b) for b in blobs)) == len(blobs)           # unequal parts
+        got = ckpt_blob.concat([ckpt_blob.decode(ckpt_blob.encode(p)) for p in parts])
+        assert got["n"] == 7 and np.array_equal(got["counts"], ckpt_blob.decode(whole)["counts"])
+        assert ckpt_blob.encode(got) == whole
+    assert ckpt_blob.encode(ckpt_blob.concat([ckpt_blob.decode(whole)])) == whole
+    other = _chunk(_synthetic(7, w, h, per, seed=1, Cc=6), 0, 2)       # a chunk of another memory: refused
+    with pytest.raises(AssertionError):
+        ckpt_blob.concat([ckpt_blob.decode(ckpt_blob.encode(parts[0])), ckpt_blob.decode(ckpt_blob.encode(other))])
+
+
 # ---------------------------------------------------------------------------------------------- epsilon schedules
 @pytest.mark.parametrize("make", ["cos", "decay", "cos_set"])
 def test_epsilon_state_round_trips(make):

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import ckpt_blob
-from tests.train_state import inspect_replay as _inspect, training_state as _state
+from tests.train_state import check_decoded as _check_decoded, inspect_replay as _inspect, training_state as _state
 
 pytestmark = pytest.mark.gpu
 
@@ -95,28 +95,6 @@ def _fresh():
 def _same(x, y):
     return (np.array_equal(x["count"], y["count"]) and np.array_equal(x["appended"], y["appended"]) and x["rows"] == y["rows"]
             and x["mass"] == y["mass"] and x["frames"] == y["frames"])
-
-
-def _unpack(words):
-    return np.packbits(np.unpackbits(np.ascontiguousarray(words, "<u4").view(np.uint8), bitorder="little").reshape(H, W)).tobytes()
-
-
-def _check_decoded(d, ins, arena0):
-    """The decoded chunk says what the inspections say about arenas [arena0, arena0 + n)."""
-    for i in range(d["n"]):
-        a = arena0 + i
-        cnt, head = int(d["count"][i]), int(d["head"][i])
-        assert cnt == ins["count"][a] and d["appended"][i] == ins["appended"][a]
-        order = (head - cnt + np.arange(cnt)) % d["C"]
-        assert d["rows"][i][order].tobytes() == ins["rows"][a]
-        assert d["mass"][i][order].tobytes() == ins["mass"][a]
-        live = {int(t): s for s, t in enumerate(d["frame_tick"][i]) if t >= 0}
-        assert sorted(live) == sorted(ins["frames"][a])
-        for t, s in live.items():
-            assert (_unpack(d["maps"][i, s, 0]), _unpack(d["maps"][i, s, 1])) == ins["frames"][a][t], (a, t)
-        for s, t in enumerate(d["frame_tick"][i]):
-            if t < 0:
-                assert d["counts"][i, s].sum() == 0
 
 
 def _samples(b, draw):

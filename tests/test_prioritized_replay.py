@@ -86,27 +86,8 @@ def _rollout(N, M=4, capacity=40, frames=0, ticks=12, seed=0x0F160011, arena_bas
              masks=None, restart_every=0):
     """A seeded collecting rollout with capture; masks(t) -> uint8 [N_global][M] of the capturing ships at tick t;
     restart_every: a new episode every so many lock-steps (0 = one episode)."""
-    from ofighters_amd import ArenaBatch, DeviceBuffer
-    b = ArenaBatch(N, M, arena_base=arena_base)
-    b.replay_create(capacity, frames)
-    if prioritize:
-        b.replay_prioritize(alpha, 1e-3)
-    b.spawn_random(seed)
-    ia_d, ip_d = DeviceBuffer(4 * N * M), DeviceBuffer(8 * N * M)
-    mask_d = DeviceBuffer(N * M)
-    for t in range(ticks):
-        mk = np.ones((N, M), np.uint8) if masks is None else masks(t)[arena_base:arena_base + N]
-        b.sync()
-        if restart_every and t and t % restart_every == 0:
-            b.restart_random(seed)
-        mask_d.upload(np.ascontiguousarray(mk))
-        b.bot_actions(["random"] * M, seed, tick=t)
-        b.policy_explore(1.0, seed, tick=t, collecting=True, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
-        b.policy_actions(out_ptr=b._actions.ptr, ship_mask_ptr=mask_d.ptr, iaction_ptr=ia_d.ptr, ipointer_ptr=ip_d.ptr)
-        b.replay_capture(t, mask_d.ptr, ia_d.ptr, ip_d.ptr)
-        b.step(actions_ptr=b._actions.ptr)
-    b.sync()
-    return b
+    return _wide.rollout(N, M, capacity=capacity, frames=frames, ticks=ticks, seed=seed, arena_base=arena_base,
+                         prioritize=prioritize, alpha=alpha, masks=masks, restart_every=restart_every)
 
 
 def _device_sample(b, seed, draw, batch, beta):
