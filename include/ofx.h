@@ -475,9 +475,19 @@ int ofx_policy_pin_weights(ofx_handle *h, const float *weights);
  *      reference of the == tests.  The forwards on stored observations (ofx_policy_forward_obs, the DQN targets) run the
  *      sparse form whatever the value.
  * ofx_policy_trunk_stats: since the last call, M-tiles run / all and table passes run / all [4] (resets; synchronises);
- * all zero unless the option is 1. */
+ * all zero unless the option is 1.
+ * conv3 follows the sparse form: the streaming conv1 -> conv2 kernel leaves a bit map of the conv2 outputs that may
+ * differ from conv2's constant, and the streaming conv3 stores ITS constant for the M-tiles whose window is unmarked and
+ * off the padding (bit-identical again, tests/test_gpu_conv3_sparse.py).  The sparse conv3 runs exactly when the sparse
+ * conv1 -> conv2 made its input; value 0 gives the dense pair.
+ * ofx_policy_trunk_stats3: conv3's M-tiles run / all since ITS last call, under the same rule (zero unless the option is 1).
+ * ofx_policy_trunk_features (diagnostic): the trunk's output [n_images][5000], (h, w, c) order, of the last forward of
+ * n_images images x m samples per image on this handle, copied out of the forward's workspace - valid only right
+ * behind that forward (OFX_ERR_STATE when no workspace of that size stands). */
 #define OFX_OPT_TRUNK_SPARSE 7
 int ofx_policy_trunk_stats(ofx_handle *h, int64_t *counts_host);
+int ofx_policy_trunk_stats3(ofx_handle *h, int64_t *run_host, int64_t *total_host);
+int ofx_policy_trunk_features(ofx_handle *h, int32_t n_images, int32_t m, float *out_host);
 int ofx_set_option(ofx_handle *h, int32_t option, int32_t value);
 /* Exploration of the bi-head action space (Trainer.get_best_action epsilon branch, agents/qlearnIA_V2.py:199-204,
  * and the collecting phase :393-395): for every selected ship, with probability `epsilon` - or always when

@@ -190,6 +190,8 @@ SIGNATURES = {
     "ofx_policy_pin_weights": (_i, [_vp, _vp]),
     "ofx_set_option": (_i, [_vp, C.c_int32, C.c_int32]),
     "ofx_policy_trunk_stats": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "ofx_policy_trunk_stats3": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ofx_policy_trunk_features": (_i, [_vp, C.c_int32, C.c_int32, _vp]),
     "ofx_event_elapsed": (_i, [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
 }
 

@@ -84,7 +84,7 @@ struct ofx_handle {
   // counters.  1: the same with the counters of ofx_policy_trunk_stats.  0: the dense kernel for the live forward
   // (diagnostic, the reference of the == tests); the forwards on stored observations stay sparse.
   bool opt_trunk_dense, opt_trunk_count;
-  unsigned long long *trunk_stat;  // [4] device counters of the sparse trunk (allocated with value 1 of the option)
+  unsigned long long *trunk_stat;  // [6] device counters of the sparse trunk (allocated with value 1 of the option)
   // ofx_policy_act (one block, allocated at its first call): the four value arrays a null output stands for, then the
   // forward's results they are selected from and the pre-drawn exploration
   float *act_vals;                 // one packed block: q_sa, p_sp, v_act, v_ptr [N*M] each, then ... (act_block, ofx_policy.hip)

@@ -727,6 +727,8 @@ __global__ void k_policy_boltz_finish(int S, int M, int arena_base, const uint8_
 // ---- workspace -----------------------------------------------------------------------
 struct PolicyWs {
   float *p1, *p2, *p3, *p4, *g1, *d1, *u0, *up1, *u2fr, *vfr, *c4;
+  unsigned *nz2;            // streaming trunk only: the p2 marks k_trunk12 leaves for k_conv3_stream, 1.6 KB per image ...
+  float *k2;                // ... and conv2's constant [8]; no bytes in the per-layer form
   unsigned long long *best;
   int32_t *iaction, *ipointer, *live;
   // sampling forwards only: per-ship temperatures, per-wave candidates of k_head_stream_sample.  Otherwise the five have no
@@ -750,6 +752,7 @@ static void policy_layout_ws(Arena &A, bool fused, size_t N, size_t S, bool samp
   W.p2 = A.f(N * 8 * 100 * 100); W.p3 = A.f(N * 8 * 50 * 50); W.p4 = A.f(N * 5000); W.g1 = A.f(N * 100 * kDense1Chunks);
   W.d1 = A.f(S * 100); W.u0 = A.f(S * 625); W.up1 = A.f(S * 2 * 50 * 50);
   W.u2fr = (float *)A.take(f2); W.vfr = (float *)A.take(f3); W.c4 = (float *)A.take(f4);
+  W.nz2 = A.n<unsigned>(fused ? N * 100 * 4 : 0); W.k2 = A.f(fused ? 8 : 0);
   W.best = A.n<unsigned long long>(S); W.iaction = A.n<int32_t>(S); W.ipointer = A.n<int32_t>(2 * S); W.live = A.n<int32_t>(S + 1);
   // the sampling forward's arrays stand behind everything else: the other forwards' layout is unchanged
   const size_t Q = sample ? S : 0;
@@ -768,6 +771,16 @@ static int policy_workspace(ofx_handle *h, PolicyWs *ws, size_t N, size_t S, boo
   policy_layout_ws(A, fused, N, S, sample, soft, *ws);
   if (!A.ok()) { ofx_set_error("policy forward: internal workspace sized too small"); return OFX_ERR_STATE; }
   return OFX_OK;
+}
+
+const float *ofx_policy_ws_p4(ofx_handle *h, size_t N, size_t S) {  // ofx_trunk.h
+  PolicyWs ws;
+  Arena measure;
+  policy_layout_ws(measure, ofx_trunk_fused(h, N), N, S, false, false, ws);
+  if (!h->scratch || h->scratch_bytes < measure.used) return nullptr;
+  Arena A(h->scratch, measure.used);
+  policy_layout_ws(A, ofx_trunk_fused(h, N), N, S, false, false, ws);
+  return A.ok() ? ws.p4 : nullptr;
 }
 
 // (also the dense layers of the fit's forward, ofx_train.hip)
@@ -847,8 +860,8 @@ extern "C" int ofx_set_option(ofx_handle *h, int32_t option, int32_t value) {
     case OFX_OPT_TRUNK_SPARSE:
       if (value && !h->trunk_stat) {
         OFX_HIP(hipSetDevice(h->cfg.device));
-        OFX_HIP(hipMalloc((void **)&h->trunk_stat, 4 * sizeof(unsigned long long)));
-        OFX_HIP(hipMemsetAsync(h->trunk_stat, 0, 4 * sizeof(unsigned long long), h->stream));
+        OFX_HIP(hipMalloc((void **)&h->trunk_stat, 6 * sizeof(unsigned long long)));
+        OFX_HIP(hipMemsetAsync(h->trunk_stat, 0, 6 * sizeof(unsigned long long), h->stream));
       }
       h->opt_trunk_dense = value == 0; h->opt_trunk_count = value != 0; return OFX_OK;
     case OFX_OPT_FIT_PLAIN: h->opt_fit_plain = value != 0; return OFX_OK;
@@ -911,7 +924,7 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   for (int i = 0; i < 4; i++) { tp.tw[i] = prep + L.tw[i]; tp.tb[i] = prep + L.tb[i]; }
   for (int i = 0; i < 3; i++) tp.wbm[i] = prep + L.wbm[i];
   tp.lut1 = prep + L.lut1; tp.zero16 = prep + L.zero16;
-  tp.p1 = ws.p1; tp.p2 = ws.p2; tp.p3 = ws.p3; tp.p4 = ws.p4;
+  tp.p1 = ws.p1; tp.p2 = ws.p2; tp.p3 = ws.p3; tp.p4 = ws.p4; tp.nz2 = ws.nz2; tp.k2 = ws.k2;
   // the sparse kernel is exact, so it is the default; OFX_OPT_TRUNK_SPARSE = 0 asks for the dense one (live forward only:
   // the forwards on stored observations, i.e. the DQN targets, always take the sparse one), = 1 for the counters
   tp.lowp = lowp; tp.sparse = !h->opt_trunk_dense || a.vec8 != nullptr;

@@ -19,7 +19,11 @@ struct ConvParams {
   int legacy;                      // k_upconv1: TF1 legacy source mapping (src = dst / 2) instead of half-pixel centres
   int images;                      // k_convm: number of images (the grid is padded to a multiple of 8 of them)
   const int32_t *live;             // k_upconv1 with a mask: ordered list of the selected images (live[0] = count), else null
-  unsigned long long *stat;        // k_trunk12<0, true>: [4] M-tiles executed / all, table waves executed / all (may be null)
+  unsigned long long *stat;        // k_trunk12<., true>: [4] M-tiles executed / all, table waves executed / all;
+                                   // k_conv3_stream<., true>: [4], [5] M-tiles executed / all (may be null)
+  unsigned *marks;                 // k_trunk12<., true> writes, k_conv3_stream<., true> reads: [img][100][4] words, bit x of
+                                   // row y set <-> p2(y, x) may differ from K2 (written by an M-tile that ran)
+  float *k2;                       // likewise: [8] conv2's constant K2[co], as k_trunk12<., true> derived it
 };
 
 struct TrunkParams {
@@ -30,14 +34,19 @@ struct TrunkParams {
   float *p1, *p2, *p3, *p4;        // pooled activations [img][8][200][200] (absent in the streaming form), [8][100][100],
                                    // [8][50][50] planar, [25][25][8] (h,w,c) = Flatten order
   int lowp;                        // OFX_OPT_POLICY_BF16: 0 fp32, 1 bf16 / 2 fp16 operands (streaming form only)
-  bool sparse;                     // the streaming conv1 -> conv2 skips constant windows (exact)
-  unsigned long long *stat;        // counters of the sparse form [4] or null
+  bool sparse;                     // the streaming conv1 -> conv2 and conv3 skip constant windows (exact)
+  unsigned long long *stat;        // counters of the sparse form [6] or null
+  unsigned *nz2;                   // streaming form: the p2 marks [img][100][4] and K2 [8] (ConvParams::marks, ::k2)
+  float *k2;
 };
 
 // the streaming form (k_trunk12 + k_conv3_stream) for this many images?  Otherwise one kernel per layer, and p1 exists.
 bool ofx_trunk_fused(const ofx_handle *h, size_t images);
 // the four layers on the handle's stream: plain (OFX_OPT_TRUNK_PLAIN) / streaming / per-layer form
 int ofx_launch_trunk(ofx_handle *h, const TrunkParams &p);
+// p4 inside the handle's scratch block as the forward of N images, S samples laid it out; null when the block is smaller
+// (ofx_policy.hip, which owns the workspace layout; for ofx_policy_trunk_features)
+const float *ofx_policy_ws_p4(ofx_handle *h, size_t N, size_t S);
 // conv1 + BatchNorm + ReLU + pool of n stored observations (bits [n][2][5000]) through a caller-built table [2][512][8]
 // (channel 0 carries the bias): out [n][8][200][200].  The fit's first layer (ofx_fit.hip): its table folds the BATCH statistics.
 int ofx_launch_conv1_lut(ofx_handle *h, const void *bits, int n, const float *lut, float *out);

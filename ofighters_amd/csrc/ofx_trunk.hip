@@ -522,7 +522,7 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
                                                      const f32x4 binit, int wv, int lane,
                                                      int n16, int kq, int r, float *orow, const unsigned *nz, float k2,
                                                      bool top, bool bottom, unsigned &n_exec, unsigned &n_all,
-                                                     unsigned long long *dbg = nullptr) {
+                                                     unsigned *marks = nullptr, unsigned long long *dbg = nullptr) {
 #if OFX_TRUNK_STAMPS
   unsigned long long g_last = __builtin_amdgcn_s_memtime();
 #define TSG_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); dbg[i] += t_ - g_last; g_last = t_; } while (0)
@@ -588,9 +588,10 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
   // mask: tile T has to run.  (A first version let a wave test its own four tiles one after the other with eight lanes each
   // and appended to a shared list behind a barrier: 4 500 cycles per step for the classification alone, stamps.)
   unsigned long long run_mask;
+  bool run;
   {
     const int T = lane, P = 16 * T, rp = P / WD, x = P - rp * WD;
-    bool run = T < NT;
+    run = T < NT;
     if (run && !(x < 1 || x + 15 > WD - 2 || P + 15 >= NPX || (top && rp == 0) || (bottom && rp == RP - 1))) {
       // window = bits x - 1 .. x + 16 of tile rows 2 rp .. 2 rp + 3: two words per row
       const int w0 = (x - 1) >> 5, lo = (x - 1) & 31;
@@ -604,6 +605,25 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
       run = any != 0u;
     }
     run_mask = __builtin_amdgcn_ballot_w64(run);
+  }
+  // marks != null (k_trunk12; an LDS array): the step's OUTPUT marks for the next layer, RP pooled rows x (WD / 2 + 31) / 32
+  // words, bit x of row y set <-> the pooled pixel (y, x) was written by a tile that ran (it may differ from k2).  Tile T
+  // writes the pooled pixels 8 T .. 8 T + 7 of the step's flat RP x WD / 2 enumeration, so a word is five mask bits spread
+  // to bytes and shifted to the word's start; one lane per word of the last wave.  The caller stores them behind the
+  // step's barrier (a global pointer kept alive through this phase spilled k_trunk12<0, true>: 118 -> 128 VGPRs + scratch).
+  if (marks != nullptr && wv == 15) {
+    constexpr int W2 = WD / 2, WPR = (W2 + 31) / 32;
+    static_assert(RP * WPR <= 64, "one lane per word");
+    if (lane < RP * WPR) {
+      const int y = lane / WPR, w = lane - y * WPR;
+      const int f0 = y * W2 + 32 * w, t0 = f0 >> 3;                // flat pooled pixel of bit 0, its tile
+      const unsigned b5 = (unsigned)(run_mask >> t0);              // tiles t0 .. t0 + 4 (t0 < 64; no tile past NT is set)
+      const unsigned lo = (((b5 & 15u) * 0x00204081u) & 0x01010101u) * 0xFFu, hi = ((b5 >> 4) & 1u) * 0xFFu;  // a bit -> a byte
+      unsigned word = __funnelshift_r(lo, hi, (unsigned)(f0 & 7));
+      const int nb = W2 - 32 * w;                                  // columns of the row in this word
+      if (nb < 32) word &= (1u << nb) - 1u;
+      marks[lane] = word;
+    }
   }
   auto store_const = [&](int T) {                                          // the constant tile: the dense result, stored
     const int P = 16 * T + 4 * kq, rp = P / WD, x = P - rp * WD;
@@ -621,22 +641,23 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
     if (!((run_mask >> T) & 1ull)) store_const(T);
   if (wv == 0) { n_all += (unsigned)NT; n_exec += (unsigned)__builtin_popcountll(run_mask); }
   TSG_STAMP(0);
-  unsigned long long m = run_mask;
-  for (int i = 0; i < wv && m; i++) m &= m - 1;                             // skip the bits of the waves in front
+  // lane T knows its tile's rank among the run tiles (the set bits below it); one more ballot gives the wave ITS tiles,
+  // four at most.  (Walking the mask bit by bit to the w-th, (w + 16)-th, ... set bit was ~700 scalar instructions per wave
+  // and step with three tiles per wave, k_conv3_stream: more than the skipped tiles saved.)
+  const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(run_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)run_mask, 0u));
+  unsigned long long m = __builtin_amdgcn_ballot_w64(run && (rank & 15u) == (unsigned)wv);
 #pragma unroll 1
   while (m) {
     const int T0 = __builtin_ctzll(m);
-    unsigned long long m2 = m;
-    for (int i = 0; i < 16 && m2; i++) m2 &= m2 - 1;                        // 16 set bits further on: this wave's next tile
-    if (m2) {                                                               // two accumulator chains
-      const int T1 = __builtin_ctzll(m2);
+    m &= m - 1;
+    if (m) {                                                                // two accumulator chains
+      const int T1 = __builtin_ctzll(m);
+      m &= m - 1;
       f32x4 d0 = binit, d1 = binit;
       mm2(a_of_tile(T0), a_of_tile(T1), d0, d1);
       finish(d0, T0);
       finish(d1, T1);
-      for (int i = 0; i < 16 && m2; i++) m2 &= m2 - 1;
     } else run1(T0);
-    m = m2;
   }
   TSG_STAMP(2);
 }
@@ -711,6 +732,7 @@ constexpr int F12_TH = 10, F12_LS = 216, F12_ROWS = F12_TH + 2;
 constexpr int F12_PLS = (F12_ROWS * F12_LS + 63) / 64 * 64 + 16;  // plane stride = 16 mod 64, as k_convm
 constexpr int F12_WR = 14, F12_BR = 2 * (F12_TH + 1) + 2;         // words per staged bit row; bit rows of the first step
 constexpr int F12_THREADS = 1024;
+constexpr int C3_MW = 4;                                          // words of a p2 row's marks (100 bits): ConvParams::marks
 static_assert(F12_PLS % 64 == 16 && F12_PLS % 4 == 0 && F12_LS % 4 == 0, "tile layout");
 static_assert(2 * F12_BR * F12_WR <= F12_THREADS, "one staged word per thread");
 static_assert((F12_TH + 1) * 100 <= 2 * F12_THREADS && F12_TH * 100 <= F12_THREADS, "pixel pairs per step");
@@ -731,6 +753,7 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
   __shared__ __align__(16) float halo[2][8][2][F12_LS];  // the last two p1 rows of a step = the first two of the next
   __shared__ unsigned nz[SPARSE ? 2 : 1][F12_ROWS][8];   // SPARSE: [buffer][tile row]: bit x <-> column x may differ from K1
   __shared__ __align__(16) float k1s[8], k2s[8];         // SPARSE: the constants of an empty neighbourhood
+  __shared__ unsigned mk2[SPARSE ? (F12_TH / 2) * C3_MW : 1];  // SPARSE: the step's p2 marks for k_conv3_stream (ConvParams::marks)
   // SPARSE (fp32): the 24 B operands of a lane are re-read from here in every phase B instead of living in registers
   // through phase A - with them the loop spilled, and every spill reload is an s_waitcnt vmcnt(0), i.e. a wait for the bit
   // rows in flight and for the stores' acknowledgements (stamps: 3 400 of a step's 13 700 cycles in front of phase A's
@@ -821,7 +844,10 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
       }
       float q0 = max_raw(max_raw(d0[0], 0.f), d0[1]);
       q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-      if (r == 0 && kq == 0) k2s[co] = q0;
+      if (r == 0 && kq == 0) {
+        k2s[co] = q0;
+        if (blockIdx.x == 0 && p.k2) p.k2[co] = q0;               // for k_conv3_stream<., true>: every workgroup has the same bits
+      }
     }
     __syncthreads();
     for (int e = tid; e < 8 * PLS / 4; e += F12_THREADS) reinterpret_cast<f32x4 *>(tile)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -949,7 +975,7 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
       }
       ts_gemm_phase_sparse<200, F12_TH / 2, F12_LS, F12_PLS, LP>(abase, bwl, bwb, binit, wv, lane, n16, kq, r,
                                                                   p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2,
-                                                                  &nz[buf][0][0], k2, step == 0, last, n_exec, n_all
+                                                                  &nz[buf][0][0], k2, step == 0, last, n_exec, n_all, mk2
 #if OFX_TRUNK_STAMPS
                                                                   , st_g
 #endif
@@ -964,6 +990,8 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
                                                        p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
     if constexpr (!SPARSE) { if (more) bits_commit(buf ^ 1, na, nb, nextw); }  // the other buffer: phase A of this step is behind every wave
     __syncthreads();
+    // the step's p2 marks: 5 rows x 4 words, one plain store (the next GEMM phase, which rewrites mk2, is a barrier away)
+    if constexpr (SPARSE) { if (tid < (F12_TH / 2) * C3_MW) p.marks[((size_t)img * H2 + (R0 >> 1)) * C3_MW + tid] = mk2[tid]; }
   }
   if constexpr (SPARSE) {
 #if OFX_TRUNK_STAMPS
@@ -995,11 +1023,22 @@ constexpr int C3_PF4 = C3_ROWS * C3_F4, C3_NI = (C3_PF4 + 63) / 64;  // float4 o
 static_assert(C3_PLS % 64 == 16 && C3_W % C3_TH == 0 && C3_W / 4 + 2 == C3_F4 && 64 * C3_NI * 4 <= C3_PLS + 64 * 4, "tile layout");
 static_assert(2 * 8 * C3_PLS * 4 <= 160 * 1024, "two tiles in LDS");
 
-template <int LP>
+//
+// SPARSE (exact; runs exactly when k_trunk12<., true> made this launch's p2): most of p2 is conv2's constant K2[ci], and
+// k_trunk12 leaves a bit map of the pixels that may differ from it (ConvParams::marks, from the run mask of its own GEMM
+// phase) and K2 itself (ConvParams::k2).  The marks of a step's 22 tile rows arrive with the tile - LDS-direct, 4 bytes
+// per lane, rows of 8 words of which 4 are zeros: the nz array of ts_gemm_phase_sparse - and an M-tile whose 4 x 18
+// window is unmarked and off the zero padding stores K3[co] instead of running: K3 = this kernel's own matrix sequence
+// (the 16-bit one for LP != 0) on a tile of K2 planes, pooled, once per workgroup.  Bit-identical to the dense form.
+template <int LP, bool SPARSE = false>
 __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, const float *zero16) {
   constexpr bool BF16 = LP != 0;
   constexpr int W = C3_W, H = C3_W, H2 = C3_W / 2, PLS = C3_PLS, NK = 24, STEPS = H / C3_TH;
   __shared__ __align__(16) float tiles[2][8 * C3_PLS];
+  __shared__ __align__(16) unsigned nzs[SPARSE ? 2 : 1][SPARSE ? C3_ROWS : 1][8];  // SPARSE: [buffer][tile row]: bit x <-> column x may differ from K2
+  __shared__ float k3s[8];
+  static_assert((2 * 8 * C3_PLS + 2 * C3_ROWS * 8 + 8) * 4 <= 160 * 1024, "tiles, marks and K3 in LDS");
+  unsigned n_exec = 0, n_all = 0;                        // SPARSE: wave 0's counts of M-tiles run / all
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n16 = lane & 15, kq = lane >> 4, co = n16 >> 1, r = n16 & 1;
@@ -1018,6 +1057,18 @@ __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, cons
                                          (__attribute__((address_space(3))) void *)&tiles[buf][ci * PLS + 256 * k], 16, 0, 0);
       }
     }
+    if constexpr (SPARSE) {  // the marks of the same 22 rows: word q -> (row q / 8, word q % 8), three wave-instructions
+      constexpr int NM = (C3_ROWS * 8 + 63) / 64;
+      const int k = F12_THREADS / 64 - 1 - wv;             // the last waves take them
+      const int q = 64 * k + lane;
+      if (k < NM && q < C3_ROWS * 8) {
+        const int row = q >> 3, w = q & 7, gy = R0 - 1 + row;
+        const unsigned *src = reinterpret_cast<const unsigned *>(zero16);
+        if (w < C3_MW && gy >= 0 && gy < H) src = p.marks + ((size_t)img * H + gy) * C3_MW + w;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                         (__attribute__((address_space(3))) void *)(&nzs[buf][0][0] + 64 * k), 4, 0, 0);
+      }
+    }
   };
 
   float bw[BF16 ? 1 : NK];
@@ -1030,10 +1081,36 @@ __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, cons
   const float bias = p.b[co];
   const f32x4 binit = {bias, bias, bias, bias};
   if ((int)blockIdx.x < p.images) stage(0, (int)blockIdx.x, 0);
+  if constexpr (SPARSE) {
+    // K3 while the first tile is in flight: the first four rows of the OTHER tile's planes hold K2 (read from where
+    // k_trunk12 left it), wave 0 runs the M-tile at row pair 0, columns 16 .. 31 on them
+    for (int e = tid; e < 8 * 4 * C3_LS; e += F12_THREADS) tiles[1][(e / (4 * C3_LS)) * PLS + e % (4 * C3_LS)] = p.k2[e / (4 * C3_LS)];
+    __syncthreads();
+    if (wv == 0) {
+      const float *a0 = &tiles[1][kq * PLS + 3] + 16 + n16;
+      f32x4 d0 = binit;
+      if constexpr (BF16) {
+#pragma unroll
+        for (int J = 0; J < 6; J++) {
+          const int tap = 2 * J + (kq >> 1);
+          const float *q0 = a0 + (4 * (kq & 1) - kq) * PLS + (tap / 3) * C3_LS + tap % 3;
+          d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
+        }
+      } else {
+        auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * C3_LS + ((j >> 1) % 3); };
+#pragma unroll
+        for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[BF16 ? 0 : j], d0, 0, 0, 0);
+      }
+      float q0 = max_raw(max_raw(d0[0], 0.f), d0[1]);
+      q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
+      if (r == 0 && kq == 0) k3s[co] = q0;
+    }
+  }
   // the LDS-direct loads are published to the other waves by vmcnt(0) BEFORE the barrier: the memory model only
   // promises lgkmcnt(0) at a workgroup fence, so the wait is written out rather than left to the compiler
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   __syncthreads();
+  const float k3 = SPARSE ? k3s[co] : 0.f;
   int buf = 0;
 #pragma unroll 1
   for (int img = (int)blockIdx.x; img < p.images; img += (int)gridDim.x)
@@ -1043,7 +1120,18 @@ __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, cons
     const bool last = step + 1 == STEPS;
     const int nimg = last ? img + (int)gridDim.x : img;
     if (nimg < p.images) stage(buf ^ 1, nimg, last ? 0 : R0 + C3_TH);
-    if constexpr (BF16)
+    if constexpr (SPARSE) {
+#if OFX_TRUNK_STAMPS
+      unsigned long long st_g[3] = {0, 0, 0};
+#endif
+      ts_gemm_phase_sparse<W, C3_TH / 2, C3_LS, C3_PLS, LP>(&tiles[buf][kq * PLS + 3], bw, bwb, binit, wv, lane, n16, kq, r,
+                                                            p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2,
+                                                            &nzs[buf][0][0], k3, step == 0, last, n_exec, n_all, nullptr
+#if OFX_TRUNK_STAMPS
+                                                            , st_g
+#endif
+                                                            );
+    } else if constexpr (BF16)
       ts_gemm_phase_bf16<W, C3_TH / 2, C3_LS, C3_PLS, LP ? LP : 1>(&tiles[buf][kq * PLS + 3], bwb, binit, wv, n16, kq, r,
                                                       p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
     else
@@ -1052,6 +1140,11 @@ __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, cons
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's LDS-direct loads have landed (see above)
     __syncthreads();
     buf ^= 1;
+  }
+  if constexpr (SPARSE) {
+#if !OFX_TRUNK_STAMPS
+    if (p.stat && tid == 0) { atomicAdd(&p.stat[4], (unsigned long long)n_exec); atomicAdd(&p.stat[5], (unsigned long long)n_all); }
+#endif
   }
 }
 
@@ -1102,11 +1195,15 @@ template <int LP>
 static int trunk_streaming(ofx_handle *h, ConvParams cp, const TrunkParams &p) {
   const dim3 grid((unsigned)(p.images < h->n_cus ? p.images : h->n_cus));
   cp.w = p.tw[0]; cp.b = p.tb[1]; cp.out = p.p2; cp.wbm = p.wbm[0]; cp.stat = p.stat;
+  if (p.sparse && !(p.nz2 && p.k2)) { ofx_set_error("trunk_streaming: the sparse form needs the marks buffer"); return OFX_ERR_STATE; }
+  cp.marks = p.nz2; cp.k2 = p.k2;
   if (p.sparse) hipLaunchKernelGGL((k_trunk12<LP, true>), grid, dim3(F12_THREADS), 0, h->stream, cp, p.lut1);
   else hipLaunchKernelGGL((k_trunk12<LP, false>), grid, dim3(F12_THREADS), 0, h->stream, cp, p.lut1);
   OFX_HIP(hipGetLastError());
   trunk_layer(cp, p, 2, p.p2, p.p3);
-  hipLaunchKernelGGL(k_conv3_stream<LP>, grid, dim3(F12_THREADS), 0, h->stream, cp, p.zero16);
+  // the sparse conv3 reads the marks and K2 the sparse k_trunk12 has just written for these very images; the dense pair otherwise
+  if (p.sparse) hipLaunchKernelGGL((k_conv3_stream<LP, true>), grid, dim3(F12_THREADS), 0, h->stream, cp, p.zero16);
+  else hipLaunchKernelGGL((k_conv3_stream<LP, false>), grid, dim3(F12_THREADS), 0, h->stream, cp, p.zero16);
   OFX_HIP(hipGetLastError());
   trunk_layer(cp, p, 3, p.p3, p.p4);
   return launch_convm<8, 10, 4, 0, true, 1, LP>(h, cp, p.images, 50);
@@ -1139,6 +1236,32 @@ extern "C" int ofx_policy_trunk_stats(ofx_handle *h, int64_t *counts_host) {
   OFX_HIP(hipSetDevice(h->cfg.device));
   OFX_HIP(hipMemcpyAsync(counts_host, h->trunk_stat, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
   OFX_HIP(hipMemsetAsync(h->trunk_stat, 0, 4 * sizeof(unsigned long long), h->stream));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  return OFX_OK;
+}
+
+// conv3's M-tiles (k_conv3_stream<., true>): slots 4 and 5 of the same counters, read and reset on their own
+extern "C" int ofx_policy_trunk_stats3(ofx_handle *h, int64_t *run_host, int64_t *total_host) {
+  if (!h || !run_host || !total_host) { ofx_set_error("ofx_policy_trunk_stats3: null argument"); return OFX_ERR_INVALID; }
+  *run_host = *total_host = 0;
+  if (!h->trunk_stat) return OFX_OK;
+  unsigned long long v[2] = {0, 0};
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipMemcpyAsync(v, h->trunk_stat + 4, sizeof(v), hipMemcpyDeviceToHost, h->stream));
+  OFX_HIP(hipMemsetAsync(h->trunk_stat + 4, 0, sizeof(v), h->stream));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  *run_host = (int64_t)v[0]; *total_host = (int64_t)v[1];
+  return OFX_OK;
+}
+
+// the trunk's output of the last forward of n_images images x m ships on this handle: p4 [n_images][5000] in (h, w, c) order,
+// read out of the forward's workspace (same sizes -> same layout; valid until the next user of the scratch block)
+extern "C" int ofx_policy_trunk_features(ofx_handle *h, int32_t n_images, int32_t m, float *out_host) {
+  if (!h || !out_host || n_images <= 0 || m <= 0) { ofx_set_error("ofx_policy_trunk_features: bad argument"); return OFX_ERR_INVALID; }
+  const float *p4 = ofx_policy_ws_p4(h, (size_t)n_images, (size_t)n_images * (size_t)m);
+  if (!p4) { ofx_set_error("ofx_policy_trunk_features: no forward of these sizes has run"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipMemcpyAsync(out_host, p4, (size_t)n_images * 5000 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   OFX_HIP(hipStreamSynchronize(h->stream));
   return OFX_OK;
 }

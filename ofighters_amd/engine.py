@@ -435,6 +435,20 @@ class ArenaBatch:
         nat.check(nat.lib().ofx_policy_trunk_stats(self._h, v))
         return tuple(int(x) for x in v)
 
+    def policy_trunk_stats3(self):
+        """OPT_TRUNK_SPARSE = 1: (M-tiles run, M-tiles) of the streaming conv3 since the last call."""
+        run, total = C.c_int64(), C.c_int64()
+        nat.check(nat.lib().ofx_policy_trunk_stats3(self._h, C.byref(run), C.byref(total)))
+        return int(run.value), int(total.value)
+
+    def policy_trunk_features(self):
+        """The trunk's output [N][25][25][8] of the forward that has just run on all N arenas (diagnostic: read out of the
+        forward's workspace, valid only right behind it)."""
+        out = np.empty((self.N, 25, 25, 8), np.float32)
+        self.sync()
+        nat.check(nat.lib().ofx_policy_trunk_features(self._h, self.N, self.M, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def policy_actions(self, out_ptr=None, iaction_ptr=None, ipointer_ptr=None, ship_mask_ptr=None):
         """QlearnIA.play packing of the last forward into [N][M] ofx_action."""
         out_ptr = out_ptr or self._actions.ptr
