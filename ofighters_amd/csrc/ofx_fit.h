@@ -74,7 +74,7 @@ int ofx_fit_out_fwd(hipStream_t st, int n, const ofx_fit_src &src, const float *
 int ofx_fit_out_bw(hipStream_t st, int n, const ofx_fit_src &src, const float *d2, double *part, double *fpart, float *dw,
                    float *db);
 // the top of head 2 when d o2 has one non-zero per sample (ofx_dqn_fit's targets): see ofx_fit.hip
-// huber_delta > 0 (ofx_dqn_fit_robust): the seeds and loss shares of Huber(delta); 0 launches the squared-error seed kernel
+// huber_delta > 0 (ofx_dqn_fit_robust): the seeds and loss shares of Huber(delta); 0: of the squared error (ofx_loss_seed)
 size_t ofx_fit_point_doubles(int n);
 int ofx_fit_top_point(hipStream_t st, int n, const ofx_transition *rows, const ofx_fit_src &src, const float *w, const float *b,
                       const float *o1, const float *y_act, const float *y_ptr, const float *stat, float *o2p, float *do1,
@@ -90,4 +90,20 @@ __device__ __forceinline__ float ofx_huber(float e, float delta, float *slope) {
   if (a <= delta) { *slope = e; return 0.5f * e * e; }
   *slope = e > 0.f ? delta : -delta;
   return delta * (a - 0.5f * delta);
+}
+
+// The loss-seed rule of both forms of the fit, for one error e of a row with loss weight w over the denominator d (the
+// head's output elements times the batch size): *seed = d loss / d output, the return value the row's share of the loss.
+// delta == 0: squared error, w 2 e / d and w e e / d; delta > 0: Huber(delta), w clamp(e, -delta, delta) / d and w h(e) / d -
+// half the squared-error seed inside the quadratic zone, as in Keras.  The weight is the first factor of every term (a
+// weight of 1 gives the unweighted bits), and as in ofx_huber no product feeds a sum.
+__device__ __forceinline__ float ofx_loss_seed(float e, float w, float d, float delta, float *seed) {
+  if (delta > 0.f) {
+    float c;
+    const float h = ofx_huber(e, delta, &c);
+    *seed = w * c / d;
+    return w * h / d;
+  }
+  *seed = w * 2.f * e / d;
+  return w * e * e / d;
 }

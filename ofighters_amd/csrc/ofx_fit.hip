@@ -1688,39 +1688,18 @@ __global__ void f_top_point_fwd(int n, const ofx_transition *rows, FitSrc S, con
   o2p[s] = acc;
 }
 // seeds of both heads (t_loss_seed of ofx_train.hip with o2 at the pointer only): do1, d2p[s] = d loss / d o2 at the pointer.
-// rw (may be null = 1): per-row loss weights, the first factor of every term (a weight of 1 gives the unweighted bits);
-// td (may be null): the row's errors (e1, e2)
+// rw (may be null = 1): per-row loss weights; td (may be null): the row's raw errors (e1, e2); delta: ofx_loss_seed's
 __global__ void f_top_point_seed(int n, const ofx_transition *rows, const float *o1, const float *o2p, const float *y_act,
-                                 const float *y_ptr, float *do1, float *d2p, float *lpart, const float *rw, float *td) {
+                                 const float *y_ptr, float *do1, float *d2p, float *lpart, const float *rw, float *td,
+                                 float delta) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const ofx_transition r = rows[s];
   const int a = r.iaction ? 1 : 0;
   const float e1 = o1[2 * s + a] - y_act[s], e2 = o2p[s] - y_ptr[s];
   const float w = rw ? rw[s] : 1.f;
-  do1[2 * s + a] = w * 2.f * e1 / (2.f * n);
-  d2p[s] = w * 2.f * e2 / (160000.f * n);
-  lpart[2 * s] = w * e1 * e1 / (2.f * n);
-  lpart[2 * s + 1] = w * e2 * e2 / (160000.f * n);
-  if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
-}
-// the same under Huber(delta) (t_loss_seed_huber of ofx_train.hip): seeds w clamp(e, -delta, delta) and loss shares
-// w h(e) over the same denominators; td keeps the raw errors
-__global__ void f_top_point_seed_huber(int n, const ofx_transition *rows, const float *o1, const float *o2p, const float *y_act,
-                                       const float *y_ptr, float *do1, float *d2p, float *lpart, const float *rw, float *td,
-                                       float delta) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
-  const ofx_transition r = rows[s];
-  const int a = r.iaction ? 1 : 0;
-  const float e1 = o1[2 * s + a] - y_act[s], e2 = o2p[s] - y_ptr[s];
-  const float w = rw ? rw[s] : 1.f;
-  float c1, c2;
-  const float h1 = ofx_huber(e1, delta, &c1), h2 = ofx_huber(e2, delta, &c2);
-  do1[2 * s + a] = w * c1 / (2.f * n);
-  d2p[s] = w * c2 / (160000.f * n);
-  lpart[2 * s] = w * h1 / (2.f * n);
-  lpart[2 * s + 1] = w * h2 / (160000.f * n);
+  lpart[2 * s] = ofx_loss_seed(e1, w, 2.f * n, delta, &do1[2 * s + a]);
+  lpart[2 * s + 1] = ofx_loss_seed(e2, w, 160000.f * n, delta, &d2p[s]);
   if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
 }
 // block = sample: pw[s][73] = d U (the output convolution's weight-gradient share, then d for the bias); the 4 x 4 x 8 patch
@@ -2002,7 +1981,7 @@ size_t ofx_fit_point_doubles(int n) { return (size_t)n * (73 + 16); }
 // lpart [2 n]; weighted by row_weight [n] and the errors written to td_out [n][2] when those are not null), the output
 // convolution's dw / db, g of the last head layer as its 4 x 4 patch per sample and channel (gpatch [n][8][16], for
 // ofx_fit_bw's gpatch argument; + its BatchNorm sums in `sums`); scratch: ofx_fit_point_doubles(n) doubles;
-// huber_delta > 0: the seeds and loss shares of Huber(delta) (f_top_point_seed_huber)
+// huber_delta: ofx_loss_seed's delta (0: squared error)
 int ofx_fit_top_point(hipStream_t st, int n, const ofx_transition *rows, const ofx_fit_src &src, const float *w, const float *b,
                       const float *o1, const float *y_act, const float *y_ptr, const float *stat, float *o2p, float *do1,
                       float *d2p, float *lpart, float *gpatch, double *scratch, double *sums, float *dw, float *db,
@@ -2010,12 +1989,8 @@ int ofx_fit_top_point(hipStream_t st, int n, const ofx_transition *rows, const o
   const FitSrc S = dev_src(src);
   double *pw = scratch, *part = scratch + (size_t)n * 73;
   hipLaunchKernelGGL(f_top_point_fwd, dim3((n + 63) / 64), dim3(64), 0, st, n, rows, S, w, b, o2p);
-  if (huber_delta > 0.f)
-    hipLaunchKernelGGL(f_top_point_seed_huber, dim3((n + 255) / 256), dim3(256), 0, st, n, rows, o1, o2p, y_act, y_ptr, do1, d2p,
-                       lpart, row_weight, td_out, huber_delta);
-  else
-    hipLaunchKernelGGL(f_top_point_seed, dim3((n + 255) / 256), dim3(256), 0, st, n, rows, o1, o2p, y_act, y_ptr, do1, d2p, lpart,
-                       row_weight, td_out);
+  hipLaunchKernelGGL(f_top_point_seed, dim3((n + 255) / 256), dim3(256), 0, st, n, rows, o1, o2p, y_act, y_ptr, do1, d2p, lpart,
+                     row_weight, td_out, huber_delta);
   hipLaunchKernelGGL(f_top_point_bwd, dim3(n), dim3(128), 0, st, n, rows, S, w, d2p, stat, gpatch, pw, part);
   hipLaunchKernelGGL(f_bw_finish, dim3((73 + 15) / 16), dim3(256), 0, st, 73, 72, n, pw, dw, db, 0, (const double *)nullptr,
                      (float *)nullptr, (float *)nullptr);

@@ -441,9 +441,10 @@ __global__ void t_concat_bwd(int n, const float *df, float *dx4) {
 }
 
 // loss seeds: one non-zero error per head and sample; loss[0] += mse(out1) share, loss[1] += mse(out2) share.
-// rw (may be null = 1): per-row loss weights, the first factor of every term; td (may be null): the errors (e1, e2)
+// rw (may be null = 1): per-row loss weights; td (may be null): the raw errors (e1, e2); delta: ofx_loss_seed's - 0 the
+// squared error, > 0 Huber(delta) (ofx_dqn_fit_robust)
 __global__ void t_loss_seed(int n, const ofx_transition *rows, const float *o1, const float *o2, const float *y_act,
-                            const float *y_ptr, float *do1, float *do2, float *lpart, const float *rw, float *td) {
+                            const float *y_ptr, float *do1, float *do2, float *lpart, const float *rw, float *td, float delta) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const ofx_transition r = rows[s];
@@ -453,32 +454,8 @@ __global__ void t_loss_seed(int n, const ofx_transition *rows, const float *o1, 
   const size_t k = (size_t)s * TPS * TPS + (size_t)py * TPS + px;
   const float e2 = o2[k] - y_ptr[s];
   const float w = rw ? rw[s] : 1.f;
-  do1[2 * s + a] = w * 2.f * e1 / (2.f * n);
-  do2[k] = w * 2.f * e2 / ((float)(TPS * TPS) * n);
-  lpart[2 * s] = w * e1 * e1 / (2.f * n);      // summed in sample order by t_sum_ordered
-  lpart[2 * s + 1] = w * e2 * e2 / ((float)(TPS * TPS) * n);
-  if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
-}
-// t_loss_seed under Huber(delta) (ofx_dqn_fit_robust, delta > 0): seeds w clamp(e, -delta, delta) and loss shares w h(e)
-// over the same denominators - half the squared-error seed inside the quadratic zone, as in Keras; td keeps the raw errors
-__global__ void t_loss_seed_huber(int n, const ofx_transition *rows, const float *o1, const float *o2, const float *y_act,
-                                  const float *y_ptr, float *do1, float *do2, float *lpart, const float *rw, float *td,
-                                  float delta) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
-  const ofx_transition r = rows[s];
-  if (r.ship < 0) { lpart[2 * s] = lpart[2 * s + 1] = 0.f; return; }  // padding row: no error
-  const int a = r.iaction ? 1 : 0, px = min(max(r.px, 0), TPS - 1), py = min(max(r.py, 0), TPS - 1);
-  const float e1 = o1[2 * s + a] - y_act[s];
-  const size_t k = (size_t)s * TPS * TPS + (size_t)py * TPS + px;
-  const float e2 = o2[k] - y_ptr[s];
-  const float w = rw ? rw[s] : 1.f;
-  float c1, c2;
-  const float h1 = ofx_huber(e1, delta, &c1), h2 = ofx_huber(e2, delta, &c2);
-  do1[2 * s + a] = w * c1 / (2.f * n);
-  do2[k] = w * c2 / ((float)(TPS * TPS) * n);
-  lpart[2 * s] = w * h1 / (2.f * n);      // summed in sample order by t_sum_ordered
-  lpart[2 * s + 1] = w * h2 / ((float)(TPS * TPS) * n);
+  lpart[2 * s] = ofx_loss_seed(e1, w, 2.f * n, delta, &do1[2 * s + a]);      // summed in sample order by t_sum_ordered
+  lpart[2 * s + 1] = ofx_loss_seed(e2, w, (float)(TPS * TPS) * n, delta, &do2[k]);
   if (td) { td[2 * s] = e1; td[2 * s + 1] = e2; }
 }
 // out[j] = sum_i part[i * stride + j] for j < stride, in index order (one thread per j: tiny)
@@ -509,15 +486,22 @@ __global__ __launch_bounds__(256) void t_sqnorm_part(size_t cnt, const float *g,
   }
   if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
-// one thread, like t_sum_ordered: the block partials in index order, then out[0] = norm and out[1] = the factor of
-// torch.nn.utils.clip_grad_norm_, min(1, clip / (norm + 1e-6)) in fp32 (clip == 0: no clipping, 1)
-__global__ void t_clip_scale(int count, const double *part, float clip, float *out) {
+// one thread, like t_sum_ordered: the block partials in index order (count == 0: no norm asked for), then
+// loss[2] = scale * norm and loss[3] = the one factor Adam multiplies the gradient by, the factor of
+// torch.nn.utils.clip_grad_norm_, min(1, clip / (norm + 1e-6)) in fp32 (clip == 0: no clipping, 1), times scale - the two
+// multiplied once.  tail null (a fit's own gradient): scale is 1 - both products by 1.0f are exact - and the losses are
+// left alone; else (ofx_dqn_apply: tail = the accumulator's last OFX_ACC_TAIL floats) loss[0..1] = scale * its two losses.
+__global__ void t_clip_scale(int count, const double *part, float clip, float scale, const float *tail, float *loss) {
   if (threadIdx.x || blockIdx.x) return;
   double acc = 0.0;
   for (int i = 0; i < count; i++) acc += part[i];
-  const float norm = (float)sqrt(acc);
-  out[0] = norm;
-  out[1] = clip > 0.f ? fminf(1.f, clip / (norm + 1e-6f)) : 1.f;
+  const float sc = tail ? scale : 1.f, norm = (float)sqrt(acc) * sc;
+  if (tail) {
+    loss[0] = sc * tail[OFX_ACC_LOSS];
+    loss[1] = sc * tail[OFX_ACC_LOSS + 1];
+  }
+  loss[2] = norm;
+  loss[3] = (clip > 0.f ? fminf(1.f, clip / (norm + 1e-6f)) : 1.f) * sc;
 }
 
 // Trainer.replay as written (ofx_dqn_fit_reference): the targets are whole predictions of `state` with one entry
@@ -534,46 +518,38 @@ __global__ void t_reference_targets(int n, const ofx_transition *rows, float gam
   t2[(size_t)s * TPS * TPS + (size_t)px * TPS + py] = (float)r.reward + gamma * max_next[s] * live;
 }
 
-// ---- TD targets of Trainer.replay (agents/qlearnIA_V2.py:251-270): ofx_dqn_targets / ofx_dqn_targets_nstep below ----
+// ---- TD targets of Trainer.replay (agents/qlearnIA_V2.py:251-270): the four ofx_dqn_targets* entries below ----
 // The TD arithmetic (the forwards run in ofx_policy.hip).  It lives in this
 // -ffp-contract=off file because the n-step form must round the product and the sum on their own, and under
 // -ffp-contract=fast the backend fuses them whatever `#pragma clang fp contract` says.  The one-step form gives the
 // bits it gave there as fma(live, gamma * m, reward): live is 0 or 1, so that fma rounds once, like the add here.
-// ret / disc null: the one-step targets of Trainer.replay.
-__global__ void k_dqn_targets(int n, const ofx_transition *rows, float gamma, const float *act_prev, const float *probe_prev,
-                              const float *act_next, const float *max_next, float *q_sa, float *p_sp, float *y_act,
-                              float *y_ptr, const float *ret, const float *disc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ofx_transition r = rows[i];
-  if (r.ship < 0) {
-    if (q_sa) q_sa[i] = p_sp[i] = 0.f;
-    y_act[i] = y_ptr[i] = 0.f;
-    return;
-  }
-  if (q_sa) {   // the forward on `state` was run
-    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
-    p_sp[i] = probe_prev[i];
-  }
-  const float m_act = fmaxf(act_next[2 * i], act_next[2 * i + 1]);  // np.max(prediction)
-  if (ret) {                                                          // n-step: ret + disc * max
-    y_act[i] = ret[i] + disc[i] * m_act;
-    y_ptr[i] = ret[i] + disc[i] * max_next[i];
-    return;
-  }
-  const float live = r.done ? 0.f : 1.f;  // int(not done)
-  y_act[i] = (float)r.reward + gamma * m_act * live;
-  y_ptr[i] = (float)r.reward + gamma * max_next[i] * live;  // np.max(ptr_prediction)
-}
+//
+// The entries differ only in where the two bootstrap values of next_state come from:
+//   v_act = the value of act [n][2]: act[2 i + sel[i]] when sel is given (Double DQN: the online forward's iaction - the
+//           first maximum - picks among the target network's values), else the two-action soft value at tau_act, which
+//           at tau_act == 0 is np.max(prediction);
+//   v_ptr = ptr[i]: the heat map's maximum (max_next), the target network's map probed at the online forward's ipointer
+//           (probe_tgt), or the forward's soft value (soft_next = ptr_soft of ofx_policy_forward_obs_soft).
+struct Bootstrap {
+  const float *act;     // [n][2]
+  const int32_t *sel;   // [n] or null
+  const float *ptr;     // [n]
+  float tau_act;
+};
+// the Munchausen bonus (ofx_dqn_targets_soft, one-step form only): alpha > 0 adds the scaled, clipped T ln pi(a | s) of the
+// action taken to the reward; soft_prev [n] is ptr_soft of `state`
+struct Munchausen { float alpha, clip; const float *soft_prev; };
 
-// Double DQN (ofx_dqn_targets_double): the online network selects, the target network evaluates.  sel_action [n] is the
-// online forward's iaction on next_state (the first maximum), act_tgt [n][2] the target network's action values there
-// and probe_tgt [n] its heat map probed at the online forward's ipointer.  The TD arithmetic is k_dqn_targets' with
-// the two maxima replaced by the selected values: the same expressions, every operation rounded on its own.
-__global__ void k_dqn_targets_double(int n, const ofx_transition *rows, float gamma, const float *act_prev,
-                                     const float *probe_prev, const int32_t *sel_action, const float *act_tgt,
-                                     const float *probe_tgt, float *q_sa, float *p_sp, float *y_act, float *y_ptr,
-                                     const float *ret, const float *disc) {
+__device__ __forceinline__ float soft_act_value(float a0, float a1, float tau) {
+  const float m = fmaxf(a0, a1);  // np.max(prediction)
+  if (tau == 0.f) return m;
+  return m + tau * log1pf(expf(-fabsf(a0 - a1) / tau));
+}
+// ret / disc null: the one-step form, y = reward + gamma * v * int(not done); else n-step, y = ret + disc * v.  Every
+// operation is rounded on its own.  q_sa / p_sp (may be null): the forward on `state` was run (act_prev / probe_prev).
+__global__ void k_dqn_targets(int n, const ofx_transition *rows, float gamma, const float *act_prev, const float *probe_prev,
+                              Bootstrap B, Munchausen M, float *q_sa, float *p_sp, float *y_act, float *y_ptr,
+                              const float *ret, const float *disc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const ofx_transition r = rows[i];
@@ -582,19 +558,28 @@ __global__ void k_dqn_targets_double(int n, const ofx_transition *rows, float ga
     y_act[i] = y_ptr[i] = 0.f;
     return;
   }
-  if (q_sa) {   // the online forward on `state` was run
-    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
+  const int a = r.iaction ? 1 : 0;
+  if (q_sa) {
+    q_sa[i] = act_prev[2 * i + a];
     p_sp[i] = probe_prev[i];
   }
-  const float v_act = act_tgt[2 * i + (sel_action[i] ? 1 : 0)], v_ptr = probe_tgt[i];
-  if (ret) {                                                          // n-step: ret + disc * v
+  const float v_act = B.sel ? B.act[2 * i + (B.sel[i] ? 1 : 0)] : soft_act_value(B.act[2 * i], B.act[2 * i + 1], B.tau_act);
+  const float v_ptr = B.ptr[i];
+  if (ret) {
     y_act[i] = ret[i] + disc[i] * v_act;
     y_ptr[i] = ret[i] + disc[i] * v_ptr;
     return;
   }
   const float live = r.done ? 0.f : 1.f;  // int(not done)
-  y_act[i] = (float)r.reward + gamma * v_act * live;
-  y_ptr[i] = (float)r.reward + gamma * v_ptr * live;
+  float r_act = (float)r.reward, r_ptr = (float)r.reward;
+  if (M.alpha > 0.f) {
+    const float l_act = act_prev[2 * i + a] - soft_act_value(act_prev[2 * i], act_prev[2 * i + 1], B.tau_act);
+    const float l_ptr = probe_prev[i] - M.soft_prev[i];
+    r_act = r_act + M.alpha * fminf(fmaxf(l_act, M.clip), 0.f);
+    r_ptr = r_ptr + M.alpha * fminf(fmaxf(l_ptr, M.clip), 0.f);
+  }
+  y_act[i] = r_act + gamma * v_act * live;
+  y_ptr[i] = r_ptr + gamma * v_ptr * live;
 }
 
 // ofx_policy_blend_weights: dst = c * dst + tau * src with c = 1 - tau formed once by the caller; both products are
@@ -639,23 +624,14 @@ __global__ __launch_bounds__(256) void t_loss_dense(size_t total, float scale, c
 }
 
 // c1 = 1 - beta1 and c2 = 1 - beta2 arrive rounded from their decimal values (0.1, 0.001): formed in fp32 from the rounded
-// betas, 1.f - 0.999f is 0.000999987 - 1.3e-5 off the constant of the recurrence, 27 times what the format asks for
+// betas, 1.f - 0.999f is 0.000999987 - 1.3e-5 off the constant of the recurrence, 27 times what the format asks for.
+// scale (may be null = 1): Adam on scale[0] * g, the factor t_clip_scale left in device memory (no host round trip between
+// the gradient and the update); a factor of exactly 1 - the clip inactive - gives the bits of the null form
 __global__ void t_adam(size_t cnt, float *w, const float *g, float *m, float *v, float lr_t, float b1, float b2, float c1,
-                       float c2, float eps) {
+                       float c2, float eps, const float *scale) {
+  const float sc = scale ? scale[0] : 1.f;
   for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
-    const float gi = g[e];
-    const float mi = b1 * m[e] + c1 * gi, vi = b2 * v[e] + c2 * gi * gi;
-    m[e] = mi; v[e] = vi;
-    w[e] -= lr_t * mi / (sqrtf(vi) + eps);
-  }
-}
-// t_adam on scale[0] * g, the factor t_clip_scale left in device memory (no host round trip between the gradient and the
-// update); a factor of exactly 1 - the clip inactive - gives t_adam's bits
-__global__ void t_adam_scaled(size_t cnt, float *w, const float *g, float *m, float *v, float lr_t, float b1, float b2,
-                              float c1, float c2, float eps, const float *scale) {
-  const float sc = scale[0];
-  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < cnt; e += (size_t)gridDim.x * blockDim.x) {
-    const float gi = sc * g[e];
+    const float gi = scale ? sc * g[e] : g[e];
     const float mi = b1 * m[e] + c1 * gi, vi = b2 * v[e] + c2 * gi * gi;
     m[e] = mi; v[e] = vi;
     w[e] -= lr_t * mi / (sqrtf(vi) + eps);
@@ -685,19 +661,6 @@ __global__ void t_accumulate(size_t n_floats, const float *grad, AccSrc S, float
     }
     acc[e] = reset ? v : acc[e] + v;
   }
-}
-// ofx_dqn_apply's one thread: t_clip_scale's norm of the accumulator (count == 0: none asked for) times scale, and the
-// one factor Adam multiplies the accumulator by, min(1, clip / (norm + 1e-6)) * scale - the two multiplied once, in fp32.
-// out = {scale * loss1, scale * loss2, scaled norm, factor}; scale == 1 leaves t_clip_scale's bits in out[2] / out[3].
-__global__ void t_apply_factor(int count, const double *part, float clip, float scale, const float *tail, float *out) {
-  if (threadIdx.x || blockIdx.x) return;
-  double acc = 0.0;
-  for (int i = 0; i < count; i++) acc += part[i];
-  const float norm = (float)sqrt(acc) * scale;
-  out[0] = scale * tail[OFX_ACC_LOSS];
-  out[1] = scale * tail[OFX_ACC_LOSS + 1];
-  out[2] = norm;
-  out[3] = (clip > 0.f ? fminf(1.f, clip / (norm + 1e-6f)) : 1.f) * scale;
 }
 // moving = 0.99 moving + 0.01 (scale * stat): stat holds the batch statistics {mean, var} per channel - a fit's own at
 // scale 1 (the product by 1.0f is exact and nothing here is contracted: the bits of the unscaled expression), or the
@@ -805,58 +768,12 @@ static int refuse_pads(ofx_handle *h, int n, const ofx_transition *rows, const c
   return OFX_OK;
 }
 
-// ---- soft and Munchausen targets (ofx_dqn_targets_soft) ---------------------------------------------------------------
-// k_dqn_targets with the two maxima replaced by soft values: the pointer head's comes from the forward (soft_next =
-// ptr_soft of ofx_policy_forward_obs_soft), the two-action head's is formed here.  Every operation is rounded on its own
-// (this file is compiled with -ffp-contract=off), in k_dqn_targets' order: with tau_act == 0, soft_next = the maximum and
-// m_alpha == 0 the expressions below are that kernel's.
-__device__ __forceinline__ float soft_act_value(float a0, float a1, float tau) {
-  const float m = fmaxf(a0, a1);  // np.max(prediction)
-  if (tau == 0.f) return m;
-  return m + tau * log1pf(expf(-fabsf(a0 - a1) / tau));
-}
-__global__ void k_dqn_targets_soft(int n, const ofx_transition *rows, float gamma, const float *act_prev, const float *probe_prev,
-                                   const float *soft_prev, const float *act_next, const float *soft_next, float tau_act,
-                                   float m_alpha, float m_clip, float *q_sa, float *p_sp, float *y_act, float *y_ptr,
-                                   const float *ret, const float *disc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ofx_transition r = rows[i];
-  if (r.ship < 0) {
-    if (q_sa) q_sa[i] = p_sp[i] = 0.f;
-    y_act[i] = y_ptr[i] = 0.f;
-    return;
-  }
-  if (q_sa) {   // (act_prev / probe_prev: the forward on `state` was run - asked for, or Munchausen's)
-    q_sa[i] = act_prev[2 * i + (r.iaction ? 1 : 0)];
-    p_sp[i] = probe_prev[i];
-  }
-  const float v_act = soft_act_value(act_next[2 * i], act_next[2 * i + 1], tau_act), v_ptr = soft_next[i];
-  if (ret) {                                                          // n-step: ret + disc * V
-    y_act[i] = ret[i] + disc[i] * v_act;
-    y_ptr[i] = ret[i] + disc[i] * v_ptr;
-    return;
-  }
-  const float live = r.done ? 0.f : 1.f;  // int(not done)
-  if (m_alpha > 0.f) {   // Munchausen: the scaled, clipped T ln pi(a | s) of the action taken joins the reward
-    const float l_act = act_prev[2 * i + (r.iaction ? 1 : 0)] - soft_act_value(act_prev[2 * i], act_prev[2 * i + 1], tau_act);
-    const float l_ptr = probe_prev[i] - soft_prev[i];
-    const float t_act = (float)r.reward + m_alpha * fminf(fmaxf(l_act, m_clip), 0.f);
-    const float t_ptr = (float)r.reward + m_alpha * fminf(fmaxf(l_ptr, m_clip), 0.f);
-    y_act[i] = t_act + gamma * v_act * live;
-    y_ptr[i] = t_ptr + gamma * v_ptr * live;
-    return;
-  }
-  y_act[i] = (float)r.reward + gamma * v_act * live;
-  y_ptr[i] = (float)r.reward + gamma * v_ptr * live;
-}
-
-// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, one k_dqn_targets launch.
+// ofx_dqn_targets (ret == disc == null) and ofx_dqn_targets_nstep: the same two forwards, then the one k_dqn_targets launch
+// every form ends in.
 // ofx_dqn_targets_double (dbl; `weights` is the online blob): the forward on next_state runs twice - online for
-// (iaction, ipointer), then `target` probed at that pointer - and k_dqn_targets_double takes the place of k_dqn_targets.
+// (iaction, ipointer), then `target` probed at that pointer - and the bootstrap is the target's values at that selection.
 // ofx_dqn_targets_soft (soft): the forwards are ofx_policy_forward_obs_soft's - max_next then holds ptr_soft of next_state,
-// and with the Munchausen term the forward on `state` runs whether or not q_sa / p_sp are wanted and adds soft_prev - and
-// k_dqn_targets_soft takes the place of k_dqn_targets.
+// and with the Munchausen term the forward on `state` runs whether or not q_sa / p_sp are wanted and adds soft_prev.
 // What one forward hands to the next lives in the aux arena: the forward's scratch block is laid out anew by each.
 struct SoftArgs { float tau_act, tau_ptr, m_alpha, m_clip; };   // checked by ofx_dqn_targets_soft
 struct TargetsWs {
@@ -894,31 +811,25 @@ static int dqn_targets_impl(ofx_handle *h, const char *who, const float *weights
       return rc;
   } else if (q_sa && (rc = ofx_policy_forward_obs(h, weights, n, bits_prev, W.vec_prev, W.act_prev, nullptr, nullptr, nullptr, W.probe, W.probe_prev)))
     return rc;
+  Bootstrap B = {W.act_next, nullptr, W.max_next, 0.f};   // two-action value at tau_act, the pointer head's from the forward
+  Munchausen M = {0.f, 0.f, nullptr};
   if (soft) {
-    if ((rc = ofx_policy_forward_obs_soft(h, weights, n, bits_next, W.vec_next, soft->tau_ptr, W.act_next, nullptr, nullptr, nullptr,
-                                          nullptr, nullptr, W.max_next, nullptr, nullptr)))
-      return rc;
-    hipLaunchKernelGGL(k_dqn_targets_soft, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev, W.probe_prev,
-                       W.soft_prev, W.act_next, W.max_next, soft->tau_act, soft->m_alpha, soft->m_clip, q_sa, p_sp, y_act, y_ptr, ret,
-                       disc);
-    OFX_HIP(hipGetLastError());
-    return OFX_OK;
-  }
-  if (dbl) {
+    rc = ofx_policy_forward_obs_soft(h, weights, n, bits_next, W.vec_next, soft->tau_ptr, W.act_next, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, W.max_next, nullptr, nullptr);
+    B.tau_act = soft->tau_act;
+    M = {soft->m_alpha, soft->m_clip, W.soft_prev};
+  } else if (dbl) {
     // online first (the pinned slot when `weights` is the pinned blob), then the target through prep_tmp
     if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, W.vec_next, nullptr, W.sel_action, W.sel_pointer, nullptr, nullptr, nullptr)))
       return rc;
-    if ((rc = ofx_policy_forward_obs(h, target, n, bits_next, W.vec_next, W.act_tgt, nullptr, nullptr, nullptr, W.sel_pointer, W.probe_tgt)))
-      return rc;
-    hipLaunchKernelGGL(k_dqn_targets_double, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev,
-                       W.probe_prev, W.sel_action, W.act_tgt, W.probe_tgt, q_sa, p_sp, y_act, y_ptr, ret, disc);
-    OFX_HIP(hipGetLastError());
-    return OFX_OK;
+    rc = ofx_policy_forward_obs(h, target, n, bits_next, W.vec_next, W.act_tgt, nullptr, nullptr, nullptr, W.sel_pointer, W.probe_tgt);
+    B = {W.act_tgt, W.sel_action, W.probe_tgt, 0.f};
+  } else {
+    rc = ofx_policy_forward_obs(h, weights, n, bits_next, W.vec_next, W.act_next, nullptr, nullptr, W.max_next, nullptr, nullptr);
   }
-  if ((rc = ofx_policy_forward_obs(h, weights, n, bits_next, W.vec_next, W.act_next, nullptr, nullptr, W.max_next, nullptr, nullptr)))
-    return rc;
-  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev, W.probe_prev,
-                     W.act_next, W.max_next, q_sa, p_sp, y_act, y_ptr, ret, disc);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_dqn_targets, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, rows, gamma, W.act_prev, W.probe_prev, B, M,
+                     q_sa, p_sp, y_act, y_ptr, ret, disc);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -1028,24 +939,16 @@ static int fit_apply_update(ofx_handle *h, const ofx_policy_desc &L, const FitCa
   const float b1 = 0.9f, b2 = 0.999f;
   const float lr_t = C.lr * sqrtf(1.f - powf(b2, (float)C.step)) / (1.f - powf(b1, (float)C.step));
   const bool scaled = C.clip_norm > 0.f || (C.tail && C.scale != 1.f);   // Adam reads its factor from loss[3]
-  if (C.tail) {     // the same norm pass, then the norm, the factor and the losses times scale (t_apply_factor)
-    if (C.norm()) hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
-    hipLaunchKernelGGL(t_apply_factor, dim3(1), dim3(64), 0, st, C.norm() ? kNormBlocks : 0, npart, C.clip_norm, C.scale,
-                       C.tail, loss);
-    OFX_HIP(hipGetLastError());
-  } else if (C.norm()) {   // untrained slots of the gradient blob are zero: one pass over all of it
-    hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
-    hipLaunchKernelGGL(t_clip_scale, dim3(1), dim3(64), 0, st, kNormBlocks, npart, C.clip_norm, loss + 2);
-    OFX_HIP(hipGetLastError());
-  }
+  // the norm pass (untrained slots of the gradient blob are zero: one pass over all of it), then the norm, the factor
+  // and - an accumulator's (C.tail) - the losses times scale; neither asked for: nothing is launched
+  if (C.norm()) hipLaunchKernelGGL(t_sqnorm_part, dim3(kNormBlocks), dim3(256), 0, st, (size_t)L.n_floats, grad, npart);
+  if (C.norm() || C.tail)
+    hipLaunchKernelGGL(t_clip_scale, dim3(1), dim3(64), 0, st, C.norm() ? kNormBlocks : 0, npart, C.clip_norm, C.scale, C.tail, loss);
+  OFX_HIP(hipGetLastError());
   for (int t = 0; t < L.n_tensors; t++) {
     if (!ofx_blob_trained(t)) continue;  // moving mean / variance
-    if (scaled)
-      K(t_adam_scaled, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t],
-        C.adam_m + L.offset[t], C.adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f, loss + 3);
-    else
-      K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], C.adam_m + L.offset[t],
-        C.adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f);
+    K(t_adam, (size_t)L.count[t], (size_t)L.count[t], weights + L.offset[t], grad + L.offset[t], C.adam_m + L.offset[t],
+      C.adam_v + L.offset[t], lr_t, b1, b2, 0.1f, 0.001f, 1e-7f, scaled ? loss + 3 : (const float *)nullptr);
   }
   // (a fit's own statistics: scale 1, the bits of the unscaled expression)
   for (int i = 0; i < 4; i++)
@@ -1079,6 +982,61 @@ static int fit_accumulate(ofx_handle *h, const ofx_policy_desc &L, const FitCall
     OFX_HIP(hipStreamSynchronize(st));
   }
   return OFX_OK;
+}
+
+// ---- what the two drivers below run alike, kernel for kernel ----
+// dense forward: f = concat(head vector, flattened p3) (next_head: the rows' next_state head - the dense targets), then the
+// four dense layers on the f32 MFMA (k_gemm_f32: exact fp32 products, fp32 accumulation in MFMA order)
+static int fit_dense_fwd(ofx_handle *h, const ofx_policy_desc &L, const float *w, int n, const ofx_transition *rows, int next_head,
+                         const float *p3, float *f, float *d1, float *d2, float *o1, float *u0) {
+  hipStream_t st = h->stream;
+  auto T = [&](int t) { return w + L.offset[t]; };
+  int rc;
+  K(t_concat_fwd, (size_t)n * 5008, n, rows, p3, f, next_head);
+  if ((rc = ofx_launch_gemm(h, f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), d1, 100, n, 100, 5008, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), d2, 50, n, 50, 100, 1))) return rc;
+  if ((rc = ofx_launch_gemm(h, d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), o1, 2, n, 2, 50, 0))) return rc;
+  return ofx_launch_gemm(h, d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), u0, 625, n, 625, 100, 1);
+}
+// the loss of the dense targets (ofx_dqn_fit_reference): both heads' seeds, loss[0] / loss[1] from the block shares in lpart
+static int fit_dense_loss(hipStream_t st, int n, const float *o1, const float *o2, const float *t1, const float *t2, float *do1,
+                          float *do2, float *lpart, float *loss) {
+  const size_t N = (size_t)n;
+  const int nb1 = (int)((N * 2 + 255) / 256), nb2 = (int)(N * 160000 / 256 > 2048 ? 2048 : (N * 160000 + 255) / 256);
+  hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), o1, t1, do1, lpart);
+  hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, lpart, loss);
+  hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), o2, t2, do2, lpart + 2048);
+  hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, lpart + 2048, loss + 1);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+// backward of updense (du0 = d u0 [n][625], behind u0's ReLU mask), of head 1 from its seeds do1, and of dense2, down to
+// dense1's weight gradient; dd1 = d d1 is left behind its mask for the caller's d f.  g: the gradient blob
+static int fit_dense_bwd(hipStream_t st, const ofx_policy_desc &L, const float *w, float *g, int n, const float *du0,
+                         const float *f, const float *d1, const float *d2, const float *do1, float *dd1, float *dd2) {
+  const size_t N = (size_t)n;
+  auto T = [&](int t) { return w + L.offset[t]; };
+  auto G = [&](int t) { return g + L.offset[t]; };
+  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, d1, du0, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, du0, T(OFX_T_UPDENSE), dd1, 0);
+  // ---- head 1 ----
+  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, d2, do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, do1, T(OFX_T_OUT1), dd2, 0);
+  K(t_relu_mask, N * 50, N * 50, d2, dd2);
+  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, d1, dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
+  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, dd2, T(OFX_T_DENSE2), dd1, 1);
+  // ---- dense1 ----
+  K(t_relu_mask, N * 100, N * 100, d1, dd1);
+  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, f, dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
+  return OFX_OK;
+}
+// after the backward pass: ofx_dqn_grad (C.acc) stops at the gradient; else the gradient is copied out when asked for, then
+// the update
+static int fit_finish(ofx_handle *h, const ofx_policy_desc &L, const FitCall &C, const float *grad, const float *const *tstat,
+                      const float *const *ustat, float *loss, double *npart) {
+  if (C.acc) return fit_accumulate(h, L, C, grad, tstat, ustat, loss);
+  if (C.grad_out) OFX_HIP(hipMemcpyAsync(C.grad_out, grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, h->stream));
+  return fit_apply_update(h, L, C, grad, tstat, ustat, loss, npart);
 }
 
 // The lean form of one fit step (default; ofx_fit.hip): the same graph, loss and update as dqn_fit_impl below with only
@@ -1150,11 +1108,7 @@ static int dqn_fit_lean(ofx_handle *h, const FitCall &C) {
     if ((rc = ofx_fit_finish(st, nb, 8, (double)N * s * s, W.part, T(ofx_t_trunk(i, OFX_T_GAMMA)), T(ofx_t_trunk(i, OFX_T_BETA)), nullptr, W.tstat[i], W.tact[i]))) return rc;
   }
   if ((rc = ofx_fit_pool_act(st, n, 8, 50, 50, W.tz[3], W.tact[3], W.p3))) return rc;
-  K(t_concat_fwd, N * 5008, n, rows, W.p3, W.f, dense ? 1 : 0);
-  if ((rc = ofx_launch_gemm(h, W.f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), W.d1, 100, n, 100, 5008, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), W.d2, 50, n, 50, 100, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, W.d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), W.o1, 2, n, 2, 50, 0))) return rc;
-  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), W.u0, 625, n, 625, 100, 1))) return rc;
+  if ((rc = fit_dense_fwd(h, L, C.weights, n, rows, dense ? 1 : 0, W.p3, W.f, W.d1, W.d2, W.o1, W.u0))) return rc;
   for (int j = 0; j < 3; j++) {
     const int s = uS[j];
     if ((rc = ofx_fit_conv_fwd(st, n, kUpCin[j], kUpCout[j], s, s, head_src(j), T(ofx_t_up(j)), T(ofx_t_up(j, OFX_T_BIAS)), W.uz[j], W.part, &nb))) return rc;
@@ -1172,14 +1126,7 @@ static int dqn_fit_lean(ofx_handle *h, const FitCall &C) {
                                 W.pscratch, W.sums, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1), C.row_weight, C.td_out, C.huber_delta))) return rc;
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, W.lpart, W.loss);
     OFX_HIP(hipGetLastError());
-  } else {
-    const int nb1 = (int)((N * 2 + 255) / 256), nb2 = (int)(N * 160000 / 256 > 2048 ? 2048 : (N * 160000 + 255) / 256);
-    hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), W.o1, C.t1, W.do1, W.lpart);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, W.lpart, W.loss);
-    hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), W.o2, C.t2, W.do2, W.lpart + 2048);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, W.lpart + 2048, W.loss + 1);
-    OFX_HIP(hipGetLastError());
-  }
+  } else if ((rc = fit_dense_loss(st, n, W.o1, W.o2, C.t1, C.t2, W.do1, W.do2, W.lpart, W.loss))) return rc;
 
   // ---- backward: head 2 ----
   if (dense && (rc = ofx_fit_out_bw(st, n, head_src(3), W.do2, W.part, W.fpart, G(OFX_T_OUT2), G(OFX_T_OUT2 + 1)))) return rc;
@@ -1198,17 +1145,8 @@ static int dqn_fit_lean(ofx_handle *h, const FitCall &C) {
   }
   if ((rc = ofx_fit_b1_up(st, n, 1, 2, 25, 25, 0, dzn, T(ofx_t_up(0)), W.u0, nullptr, nullptr, legacy, W.gu0, W.part, &nb, W.zero, W.wtr))) return rc;
   // gu0 = d u0 [n][625], already behind u0's ReLU mask
-  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, W.d1, W.gu0, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, W.gu0, T(OFX_T_UPDENSE), W.dd1, 0);
-  // ---- backward: head 1 ----
-  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, W.d2, W.do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, W.do1, T(OFX_T_OUT1), W.dd2, 0);
-  K(t_relu_mask, N * 50, N * 50, W.d2, W.dd2);
-  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, W.d1, W.dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, W.dd2, T(OFX_T_DENSE2), W.dd1, 1);
-  // ---- dense1 + trunk ----
-  K(t_relu_mask, N * 100, N * 100, W.d1, W.dd1);
-  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, W.f, W.dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
+  // ---- backward: updense, head 1, dense2, dense1's weights; then d f and the trunk ----
+  if ((rc = fit_dense_bwd(st, L, C.weights, W.grad, n, W.gu0, W.f, W.d1, W.d2, W.do1, W.dd1, W.dd2))) return rc;
   // d f = dd1 x W1^T on the f32 MFMA GEMM (the 5008 x 100 kernel transposed first): 2 x 5008 x 100 FLOP per row
   hipLaunchKernelGGL(t_transpose, dim3((100 + 31) / 32, (5008 + 31) / 32), dim3(256), 0, st, 5008, 100, T(OFX_T_DENSE1), W.w1t);
   OFX_HIP(hipGetLastError());
@@ -1230,10 +1168,7 @@ static int dqn_fit_lean(ofx_handle *h, const FitCall &C) {
                          G(ofx_t_trunk(i)), G(ofx_t_trunk(i, OFX_T_BIAS)), G(ofx_t_trunk(i, OFX_T_GAMMA)), G(ofx_t_trunk(i, OFX_T_BETA))))) return rc;
     dzn = W.tg[i];
   }
-  if (C.acc) return fit_accumulate(h, L, C, W.grad, W.tstat, W.ustat, W.loss);   // ofx_dqn_grad: gradient only
-  if (C.grad_out) OFX_HIP(hipMemcpyAsync(C.grad_out, W.grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
-
-  return fit_apply_update(h, L, C, W.grad, W.tstat, W.ustat, W.loss, W.npart);
+  return fit_finish(h, L, C, W.grad, W.tstat, W.ustat, W.loss, W.npart);
 }
 
 // The plain form of one fit step (OFX_OPT_FIT_PLAIN): every tensor of the graph in HBM, one kernel per layer and pass.
@@ -1296,12 +1231,7 @@ static int dqn_fit_impl(ofx_handle *h, const FitCall &C) {
     K(t_pool_fwd, N * 8 * per / 4, n * 8, s, s, W.ta[i], W.tp[i]);
     tin = W.tp[i];
   }
-  K(t_concat_fwd, N * 5008, n, rows, W.tp[3], W.f, dense ? 1 : 0);
-  // the four dense layers on the f32 MFMA (k_gemm_f32: exact fp32 products, fp32 accumulation in MFMA order)
-  if ((rc = ofx_launch_gemm(h, W.f, 5008, T(OFX_T_DENSE1), 100, T(OFX_T_DENSE1 + 1), W.d1, 100, n, 100, 5008, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_DENSE2), 50, T(OFX_T_DENSE2 + 1), W.d2, 50, n, 50, 100, 1))) return rc;
-  if ((rc = ofx_launch_gemm(h, W.d2, 50, T(OFX_T_OUT1), 2, T(OFX_T_OUT1 + 1), W.o1, 2, n, 2, 50, 0))) return rc;
-  if ((rc = ofx_launch_gemm(h, W.d1, 100, T(OFX_T_UPDENSE), 625, T(OFX_T_UPDENSE + 1), W.u0, 625, n, 625, 100, 1))) return rc;
+  if ((rc = fit_dense_fwd(h, L, C.weights, n, rows, dense ? 1 : 0, W.tp[3], W.f, W.d1, W.d2, W.o1, W.u0))) return rc;
   const float *uin = W.u0;
   for (int j = 0, s = 50; j < 3; j++, s *= 2) {
     const size_t per = (size_t)s * s;
@@ -1320,17 +1250,9 @@ static int dqn_fit_impl(ofx_handle *h, const FitCall &C) {
   OFX_HIP(hipMemsetAsync(W.do1, 0, N * 2 * 4, st));
   OFX_HIP(hipMemsetAsync(W.do2, 0, N * 160000 * 4, st));
   if (dense) {
-    const int nb1 = (int)((N * 2 + 255) / 256), nb2 = (int)(N * 160000 / 256 > 2048 ? 2048 : (N * 160000 + 255) / 256);
-    hipLaunchKernelGGL(t_loss_dense, dim3(nb1), dim3(256), 0, st, N * 2, 1.f / (2.f * n), W.o1, C.t1, W.do1, W.lpart);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb1, 1, W.lpart, W.loss);
-    hipLaunchKernelGGL(t_loss_dense, dim3(nb2), dim3(256), 0, st, N * 160000, 1.f / (160000.f * n), W.o2, C.t2, W.do2, W.lpart + 2048);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, nb2, 1, W.lpart + 2048, W.loss + 1);
-    OFX_HIP(hipGetLastError());
-  } else if (C.huber_delta > 0.f) {
-    K(t_loss_seed_huber, N, n, rows, W.o1, W.o2, C.y_act, C.y_ptr, W.do1, W.do2, W.lpart, C.row_weight, C.td_out, C.huber_delta);
-    hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, W.lpart, W.loss);
+    if ((rc = fit_dense_loss(st, n, W.o1, W.o2, C.t1, C.t2, W.do1, W.do2, W.lpart, W.loss))) return rc;
   } else {
-    K(t_loss_seed, N, n, rows, W.o1, W.o2, C.y_act, C.y_ptr, W.do1, W.do2, W.lpart, C.row_weight, C.td_out);
+    K(t_loss_seed, N, n, rows, W.o1, W.o2, C.y_act, C.y_ptr, W.do1, W.do2, W.lpart, C.row_weight, C.td_out, C.huber_delta);
     hipLaunchKernelGGL(t_sum_ordered, dim3(1), dim3(64), 0, st, n, 2, W.lpart, W.loss);
   }
 
@@ -1356,17 +1278,8 @@ static int dqn_fit_impl(ofx_handle *h, const FitCall &C) {
   }
   // dcur = d u0 [n][625] (pre-mask)
   K(t_relu_mask, N * 625, N * 625, W.u0, dcur);
-  K(t_dense_bwd_w, (size_t)26 * 157 * 8, n, 100, 625, W.d1, dcur, G(OFX_T_UPDENSE), G(OFX_T_UPDENSE + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 625, dcur, T(OFX_T_UPDENSE), W.dd1, 0);
-  // ---- backward: head 1 ----
-  K(t_dense_bwd_w, (size_t)32 * 8, n, 50, 2, W.d2, W.do1, G(OFX_T_OUT1), G(OFX_T_OUT1 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 13, n, 50, 2, W.do1, T(OFX_T_OUT1), W.dd2, 0);
-  K(t_relu_mask, N * 50, N * 50, W.d2, W.dd2);
-  K(t_dense_bwd_w, (size_t)26 * 13 * 8 + 255, n, 100, 50, W.d1, W.dd2, G(OFX_T_DENSE2), G(OFX_T_DENSE2 + 1));
-  K(t_dense_bwd_x, ((N + 3) / 4) * 25, n, 100, 50, W.dd2, T(OFX_T_DENSE2), W.dd1, 1);
-  // ---- dense1 + trunk ----
-  K(t_relu_mask, N * 100, N * 100, W.d1, W.dd1);
-  K(t_dense_bwd_w, (size_t)1253 * 25 * 8, n, 5008, 100, W.f, W.dd1, G(OFX_T_DENSE1), G(OFX_T_DENSE1 + 1));
+  // ---- backward: updense, head 1, dense2, dense1's weights; then d f and the trunk ----
+  if ((rc = fit_dense_bwd(st, L, C.weights, W.grad, n, dcur, W.f, W.d1, W.d2, W.do1, W.dd1, W.dd2))) return rc;
   K(t_dense_bwd_x, ((N + 3) / 4) * 1252, n, 5008, 100, W.dd1, T(OFX_T_DENSE1), W.df, 0);
   float *dp = W.gB;
   K(t_concat_bwd, N * 5000, n, W.df, dp);                                    // d W.tp[3] [n][8][25][25]
@@ -1388,10 +1301,7 @@ static int dqn_fit_impl(ofx_handle *h, const FitCall &C) {
       if ((rc = conv_bwd_data(st, n, 8, 8, s, s, dz, T(ofx_t_trunk(i)), dp))) return rc;
     }
   }
-  if (C.acc) return fit_accumulate(h, L, C, W.grad, W.tstat, W.ustat, W.loss);   // ofx_dqn_grad: gradient only
-  if (C.grad_out) OFX_HIP(hipMemcpyAsync(C.grad_out, W.grad, sizeof(float) * L.n_floats, hipMemcpyDeviceToDevice, st));
-
-  return fit_apply_update(h, L, C, W.grad, W.tstat, W.ustat, W.loss, W.npart);
+  return fit_finish(h, L, C, W.grad, W.tstat, W.ustat, W.loss, W.npart);
 }
 
 // The null / range checks the five fit entries share.  `update`: the call ends in the Adam update (moments and a step
@@ -1403,12 +1313,23 @@ static int fit_check(const ofx_handle *h, const FitCall &C, const char *who, boo
 }
 static bool finite_nonneg(float x) { return x >= 0.f && x <= FLT_MAX; }   // NaN fails the first comparison, infinity the second
 
-extern "C" int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
+// The sparse-target call of ofx_dqn_fit, _weighted, _robust and ofx_dqn_grad: what the four take in common; an entry adds
+// what is its own
+static FitCall sparse_call(float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
                            const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
-                           float *grad_out, float *loss_host) {
+                           float *grad_out, float *loss_host, const float *row_weight = nullptr, float *td_out = nullptr,
+                           float huber_delta = 0.f) {
   FitCall C;
   C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.n = n; C.rows = rows;
   C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr; C.grad_out = grad_out; C.loss_host = loss_host;
+  C.row_weight = row_weight; C.td_out = td_out; C.huber_delta = huber_delta;
+  return C;
+}
+
+extern "C" int ofx_dqn_fit(ofx_handle *h, float *weights, float *adam_m, float *adam_v, int32_t step, float lr, int32_t n,
+                           const ofx_transition *rows, const void *bits_prev, const float *y_act, const float *y_ptr,
+                           float *grad_out, float *loss_host) {
+  const FitCall C = sparse_call(weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, grad_out, loss_host);
   const int rc = fit_check(h, C, "ofx_dqn_fit", true, true);
   return rc ? rc : dqn_fit_impl(h, C);
 }
@@ -1419,10 +1340,8 @@ extern "C" int ofx_dqn_fit_weighted(ofx_handle *h, float *weights, float *adam_m
                                     int32_t n, const ofx_transition *rows, const void *bits_prev, const float *y_act,
                                     const float *y_ptr, float *grad_out, float *loss_host, const float *row_weight,
                                     float *td_out) {
-  FitCall C;
-  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.n = n; C.rows = rows;
-  C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr; C.grad_out = grad_out; C.loss_host = loss_host;
-  C.row_weight = row_weight; C.td_out = td_out;
+  const FitCall C = sparse_call(weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, grad_out, loss_host,
+                                row_weight, td_out);
   const int rc = fit_check(h, C, "ofx_dqn_fit_weighted", true, true);
   return rc ? rc : dqn_fit_impl(h, C);
 }
@@ -1433,10 +1352,9 @@ extern "C" int ofx_dqn_fit_robust(ofx_handle *h, float *weights, float *adam_m, 
                                   int32_t n, const ofx_transition *rows, const void *bits_prev, const float *y_act,
                                   const float *y_ptr, float *grad_out, float *loss_host, const float *row_weight,
                                   float *td_out, float huber_delta, float clip_norm, float *grad_norm_host) {
-  FitCall C;
-  C.weights = weights; C.adam_m = adam_m; C.adam_v = adam_v; C.step = step; C.lr = lr; C.n = n; C.rows = rows;
-  C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr; C.grad_out = grad_out; C.loss_host = loss_host;
-  C.row_weight = row_weight; C.td_out = td_out; C.huber_delta = huber_delta; C.clip_norm = clip_norm; C.grad_norm_host = grad_norm_host;
+  FitCall C = sparse_call(weights, adam_m, adam_v, step, lr, n, rows, bits_prev, y_act, y_ptr, grad_out, loss_host, row_weight,
+                          td_out, huber_delta);
+  C.clip_norm = clip_norm; C.grad_norm_host = grad_norm_host;
   const int rc = fit_check(h, C, "ofx_dqn_fit_robust", true, true);
   if (rc) return rc;
   if (!finite_nonneg(huber_delta) || !finite_nonneg(clip_norm)) {
@@ -1458,10 +1376,11 @@ extern "C" int32_t ofx_dqn_acc_floats(const ofx_handle *h) {
 extern "C" int ofx_dqn_grad(ofx_handle *h, const float *weights, int32_t n, const ofx_transition *rows,
                             const void *bits_prev, const float *y_act, const float *y_ptr, const float *row_weight,
                             float *td_out, float huber_delta, float *acc, int32_t reset, float *loss_host) {
-  FitCall C;
-  // (the drivers read the blob and hand it on to fit_apply_update alone, which this mode never reaches)
-  C.weights = const_cast<float *>(weights); C.n = n; C.rows = rows; C.bits = bits_prev; C.y_act = y_act; C.y_ptr = y_ptr;
-  C.loss_host = loss_host; C.row_weight = row_weight; C.td_out = td_out; C.huber_delta = huber_delta; C.acc = acc; C.acc_reset = reset != 0;
+  // (the drivers read the blob and hand it on to fit_apply_update alone, which this mode never reaches: no moments, step
+  // and rate at FitCall's defaults)
+  FitCall C = sparse_call(const_cast<float *>(weights), nullptr, nullptr, 1, 0.f, n, rows, bits_prev, y_act, y_ptr, nullptr,
+                          loss_host, row_weight, td_out, huber_delta);
+  C.acc = acc; C.acc_reset = reset != 0;
   const int rc = fit_check(h, C, "ofx_dqn_grad", false, true, acc != nullptr);
   if (rc) return rc;
   if (!finite_nonneg(huber_delta)) {

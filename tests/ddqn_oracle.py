@@ -1,7 +1,10 @@
 """CPU restatement of the target network / Double DQN contract in include/ofx.h (ofx_dqn_targets_double,
 ofx_policy_blend_weights).  numpy float32 throughout: every numpy operation on float32 arrays rounds on its own, which is
-what ofx_train.hip computes under -ffp-contract=off, so the results must match exactly."""
+what ofx_train.hip computes under -ffp-contract=off, so the results must match exactly.  The TD arithmetic itself is
+tests/td_oracle.py's."""
 import numpy as np
+
+from tests import td_oracle
 
 _F = np.float32
 
@@ -18,21 +21,7 @@ def targets_double(rows, gamma, ret, disc, iaction_online, act_target, probe_tar
     act = np.asarray(act_target, _F).reshape(n, 2)
     sel = (np.asarray(iaction_online).reshape(n) != 0).astype(np.intp)
     v_act = act[np.arange(n), sel]                               # evaluation of the online selection
-    v_ptr = np.asarray(probe_target, _F).reshape(n)
-    if ret is None:
-        reward = rows["reward"].astype(_F)
-        live = np.where(rows["done"] != 0, _F(0), _F(1))
-        g = _F(gamma)
-        y_act = reward + (g * v_act) * live
-        y_ptr = reward + (g * v_ptr) * live
-    else:
-        ret, disc = np.asarray(ret, _F), np.asarray(disc, _F)
-        y_act = ret + disc * v_act
-        y_ptr = ret + disc * v_ptr
-    pad = rows["ship"] < 0
-    y_act, y_ptr = np.where(pad, _F(0), y_act), np.where(pad, _F(0), y_ptr)
-    assert y_act.dtype == _F and y_ptr.dtype == _F
-    return y_act, y_ptr
+    return td_oracle.targets(rows, gamma, v_act, np.asarray(probe_target, _F).reshape(n), ret, disc)
 
 
 def blend(dst, src, tau):

@@ -3,6 +3,8 @@ Plain Python floats are IEEE float64 with every operation rounded on its own, wh
 -ffp-contract=off: ret and disc must match exactly."""
 import numpy as np
 
+from tests import td_oracle
+
 # the composite row takes these fields from the chain's last row, every other one from the sampled row
 FROM_END = ("tick_next", "frame_next", "head_next", "done")
 REASONS = ("full", "done", "restart", "head")
@@ -53,7 +55,7 @@ def chain(rows, slot, nstep, gamma):
 
 
 def targets(ret, disc, act_next, ptr_max):
-    """ofx_dqn_targets_nstep's arithmetic in float32: the product rounded, then the sum.  act_next [n][2], ptr_max [n]."""
-    ret, disc = np.asarray(ret, np.float32), np.asarray(disc, np.float32)
-    m_act = np.maximum(np.asarray(act_next, np.float32)[:, 0], np.asarray(act_next, np.float32)[:, 1])
-    return ret + disc * m_act, ret + disc * np.asarray(ptr_max, np.float32)
+    """ofx_dqn_targets_nstep's arithmetic in float32 (tests/td_oracle.py): the product rounded, then the sum.
+    act_next [n][2], ptr_max [n]."""
+    act = np.asarray(act_next, np.float32)
+    return td_oracle.targets(None, None, np.maximum(act[:, 0], act[:, 1]), ptr_max, ret, disc)
