@@ -1,5 +1,5 @@
 // ofx_api.hip - C-ABI entry points of libofx.so (see include/ofx.h) and the
-// small per-(arena, ship) kernels: spawn, restart, scripted bots, obs head.
+// small per-(arena, ship) kernels: spawn, restart, obs head (the lock-step and the bots: ofx_step.hip).
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -234,7 +234,8 @@ struct ResetParams {
   const int32_t *draws;      // [N][M][2] or null -> counter RNG
   const uint8_t *mask;       // [N] or null
   uint8_t *dead_once;        // [N][M] of ofx_restart_finished or null: cleared for the arenas that restart
-  uint32_t k0, k1, episode;
+  ofx_rng_key key;
+  uint32_t episode;
 };
 
 // Battleground.__init__ -> Ship.__init__ (battleground.py:79-81, ship.py:35-58)
@@ -247,10 +248,7 @@ __global__ void k_spawn(ResetParams p) {
     dx = p.draws[2 * t];
     dy = p.draws[2 * t + 1];
   } else {
-    uint32_t r[4];
-    ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)i, p.episode, OFX_STREAM_RESET, p.k0, p.k1, r);
-    dx = ofx_draw_int(r[0], p.W);
-    dy = ofx_draw_int(r[1], p.H);
+    ofx_reset_draw(p.key, p.W, p.H, (uint32_t)(p.arena_base + a), (uint32_t)i, p.episode, &dx, &dy);
   }
   p.st.ship_x[t] = dx; p.st.ship_y[t] = dy;
   p.st.ship_px[t] = dx; p.st.ship_py[t] = dy;
@@ -297,10 +295,7 @@ __global__ void k_restart(ResetParams p) {
     dx = p.draws[2 * t];
     dy = p.draws[2 * t + 1];
   } else {
-    uint32_t r[4];
-    ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)i, p.episode, OFX_STREAM_RESET, p.k0, p.k1, r);
-    dx = ofx_draw_int(r[0], p.W);
-    dy = ofx_draw_int(r[1], p.H);
+    ofx_reset_draw(p.key, p.W, p.H, (uint32_t)(p.arena_base + a), (uint32_t)i, p.episode, &dx, &dy);
   }
   restart_ship(p.st, p.M, a, i, dx, dy, p.st.episode_sums, nullptr);
   if (p.dead_once) p.dead_once[t] = 0;
@@ -319,7 +314,7 @@ struct FinishedParams {
   uint32_t *arena_episode;   // [N]
   uint8_t *dead_once;        // [N][M]
   uint8_t *restarted;        // [N]
-  uint32_t k0, k1;
+  ofx_rng_key key;
 };
 
 __global__ __launch_bounds__(256) void k_restart_finished(FinishedParams p) {
@@ -341,14 +336,14 @@ __global__ __launch_bounds__(256) void k_restart_finished(FinishedParams p) {
   const uint32_t episode = p.arena_episode[a] + 1u;
   if (lane == 0) p.arena_episode[a] = episode;
   if (!ship) return;
-  uint32_t r[4];
-  ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)lane, episode, OFX_STREAM_RESET, p.k0, p.k1, r);
+  int dx, dy;
+  ofx_reset_draw(p.key, p.W, p.H, (uint32_t)(p.arena_base + a), (uint32_t)lane, episode, &dx, &dy);
   long long *row = nullptr;
   if (p.sums) {
     const int g = p.group ? p.group[a] : 0;
     if (g >= 0 && g < p.n_groups) row = p.sums + (size_t)g * (p.M + 2);
   }
-  restart_ship(p.st, p.M, a, lane, ofx_draw_int(r[0], p.W), ofx_draw_int(r[1], p.H), row, row ? row + p.M + 1 : nullptr);
+  restart_ship(p.st, p.M, a, lane, dx, dy, row, row ? row + p.M + 1 : nullptr);
   p.dead_once[t] = 0;
   if (p.seen) p.seen[t] = 0;
 }
@@ -359,7 +354,7 @@ static ResetParams reset_params(ofx_handle *h, const int32_t *draws, const uint8
   p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height;
   p.arena_base = h->cfg.arena_base;
   p.st = h->st; p.draws = draws; p.mask = mask; p.dead_once = h->ar_dead_once;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.episode = episode;
+  p.key = ofx_key(seed); p.episode = episode;
   return p;
 }
 
@@ -441,9 +436,8 @@ extern "C" int ofx_restart_finished(ofx_handle *h, uint64_t seed, const uint8_t 
   p.arena_base = h->cfg.arena_base; p.max_ticks = max_ticks; p.n_groups = n_groups;
   p.st = h->st; p.ship_mask = ship_mask; p.seen = seen; p.group = group; p.sums = (long long *)sums;
   p.arena_episode = h->ar_episode; p.dead_once = h->ar_dead_once; p.restarted = h->ar_restarted;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32);
-  hipLaunchKernelGGL(k_restart_finished, dim3((p.N + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK), dim3(256), 0,
-                     h->stream, p);
+  p.key = ofx_key(seed);
+  hipLaunchKernelGGL(k_restart_finished, dim3(arena_blocks(p.N)), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   return ofx_replay_episode_reset(h, h->ar_restarted);  // QlearnIA.reset of the restarted arenas' agents
 }
@@ -474,167 +468,12 @@ extern "C" int ofx_autoreset_set_state(ofx_handle *h, const uint32_t *episode_ho
   return OFX_OK;
 }
 
-// --------------------------------------------------------------------- tick
-extern "C" int ofx_step(ofx_handle *h, const ofx_action *actions) {
-  if (!h || !actions) { ofx_set_error("ofx_step: null argument"); return OFX_ERR_INVALID; }
-  if (!h->spawned) { ofx_set_error("ofx_step before ofx_spawn"); return OFX_ERR_STATE; }
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  return ofx_launch_step(h, actions);
-}
-
-// ------------------------------------------------------------- scripted bots
-struct BotParams {
-  int N, M, W, H, arena_base;
-  ofx_state st;
-  const int32_t *beh;
-  uint32_t k0, k1, tick;
-  ofx_action *out;
-};
-
-// agents/agent.py:99-155 action laws on the counter RNG; a dead ship's agent is
-// still stepped but its action is None (ship.py:260-262)
-__global__ void k_bots(BotParams p) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= p.N * p.M) return;
-  const int a = t / p.M, i = t - a * p.M;
-  uint32_t r[4];
-  ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)i, p.tick, OFX_STREAM_BOT, p.k0, p.k1, r);
-  bool shoot = false, thrust = false, repoint = false;
-  const double u0 = (double)r[0] * (1.0 / 4294967296.0), u1 = (double)r[1] * (1.0 / 4294967296.0);
-  switch (p.beh[i]) {
-    case OFX_BOT_RANDOM: {
-      const uint32_t k = (uint32_t)(((uint64_t)r[0] * 3u) >> 32);
-      shoot = k == 0; thrust = k == 1; repoint = k == 2;
-    } break;
-    case OFX_BOT_TURRET: shoot = u0 < 0.8; repoint = u1 < 0.3; break;
-    case OFX_BOT_RUNNER: thrust = u0 < 0.9; repoint = u1 < 0.1; break;
-    case OFX_BOT_THRUST: thrust = true; break;
-    case OFX_BOT_SHOOT: shoot = true; break;
-    default: break;
-  }
-  const bool alive = p.st.alive[t] != 0;
-  ofx_action act;
-  act.px = p.st.ship_px[t];
-  act.py = p.st.ship_py[t];
-  act.shoot = 0; act.thrust = 0; act.valid = alive ? 1 : 0; act._pad = 0;
-  if (alive) {
-    act.shoot = shoot; act.thrust = thrust;
-    if (repoint) { act.px = ofx_draw_int(r[2], p.W); act.py = ofx_draw_int(r[3], p.H); }
-  }
-  p.out[t] = act;
-}
-
-extern "C" int ofx_bot_actions(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick,
-                               ofx_action *actions) {
-  if (!h || !behaviours_host || !actions) { ofx_set_error("ofx_bot_actions: null argument"); return OFX_ERR_INVALID; }
-  if (!h->spawned) { ofx_set_error("ofx_bot_actions before ofx_spawn"); return OFX_ERR_STATE; }
-  for (int i = 0; i < h->cfg.n_ships; i++)
-    if (behaviours_host[i] < OFX_BOT_IDLE || behaviours_host[i] > OFX_BOT_SHOOT) {
-      // agents/agent.py:51
-      ofx_set_error("You must give a bot in parameter or select an existing behavior.");
-      return OFX_ERR_INVALID;
-    }
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipMemcpyAsync(h->bot_behaviours, behaviours_host, sizeof(int32_t) * h->cfg.n_ships,
-                         hipMemcpyHostToDevice, h->stream));
-  BotParams p;
-  p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height;
-  p.arena_base = h->cfg.arena_base; p.st = h->st; p.beh = h->bot_behaviours;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.tick = tick; p.out = actions;
-  const int T = p.N * p.M;
-  hipLaunchKernelGGL(k_bots, dim3((T + 255) / 256), dim3(256), 0, h->stream, p);
-  OFX_HIP(hipGetLastError());
-  return OFX_OK;
-}
-
-// ------------------------------------------------ headless loop: K lock-steps per host call
-// Battleground.run (lib/battleground.py:169-173: `while True: self.frame()`) for the scripted bots: request_actions,
-// generate_frame and - when observing - Observation(battleground) for n_ticks lock-steps enqueued by ONE call.
-int ofx_launch_step_bots(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks);  // ofx_step.hip
-
-extern "C" int ofx_rollout(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0, int32_t n_ticks,
-                           int32_t observe_map_type) {
-  if (!h || !behaviours_host) { ofx_set_error("ofx_rollout: null argument"); return OFX_ERR_INVALID; }
-  if (!h->spawned) { ofx_set_error("ofx_rollout before ofx_spawn"); return OFX_ERR_STATE; }
-  if (n_ticks < 0 || observe_map_type < -1 || observe_map_type > OFX_MAP_BITS) {
-    ofx_set_error("ofx_rollout: n_ticks must be >= 0 and observe_map_type -1 (none) or an OFX_MAP_* type");
-    return OFX_ERR_INVALID;
-  }
-  for (int i = 0; i < h->cfg.n_ships; i++)
-    if (behaviours_host[i] < OFX_BOT_IDLE || behaviours_host[i] > OFX_BOT_SHOOT) {
-      ofx_set_error("You must give a bot in parameter or select an existing behavior.");  // agents/agent.py:51
-      return OFX_ERR_INVALID;
-    }
-  if (n_ticks == 0) return OFX_OK;
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipMemcpyAsync(h->bot_behaviours, behaviours_host, sizeof(int32_t) * h->cfg.n_ships, hipMemcpyHostToDevice,
-                         h->stream));
-  int rc;
-  const int pb = h->prof_base;  // ofx_policy_profile: one event pair around this call's dominant kernel
-  const bool prof = pb >= 0 && pb + 1 < OFX_RING_MAX;
-  if (observe_map_type < 0) {
-    // no observer between the lock-steps: all of them inside ONE launch (an arena belongs to one wavefront)
-    if (prof && (rc = ofx_event_record(h, pb))) return rc;
-    if ((rc = ofx_launch_step_bots(h, seed, tick0, n_ticks))) return rc;
-    if (prof && (rc = ofx_event_record(h, pb + 1))) return rc;
-  } else {
-    for (int t = 0; t < n_ticks; t++) {
-      if ((rc = ofx_launch_step_bots(h, seed, tick0 + (uint32_t)t, 1))) return rc;
-      const bool last = t + 1 == n_ticks;  // the rasteriser of the last lock-step stands for the launch pair
-      if (prof && last && (rc = ofx_event_record(h, pb))) return rc;
-      if ((rc = ofx_launch_raster(h, observe_map_type, nullptr, nullptr))) return rc;
-      if (prof && last && (rc = ofx_event_record(h, pb + 1))) return rc;
-    }
-  }
-  if (pb >= 0) h->prof_base = pb + 3 < OFX_RING_MAX ? pb + 2 : -1;
-  return OFX_OK;
-}
-
-// ------------------------------------------------ action repeat: K lock-steps per decision in one launch
-// The held ships (the learning agents, say) keep the action of their last decision for the whole span while the others
-// follow the bots' law lock-step by lock-step; the span's rewards are summed per ship for the replay memory
-// (ofx_replay_reward_source) and the maps are rasterised once, for the next decision.
-int ofx_launch_step_repeat(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks, const uint8_t *hold_mask,
-                           const ofx_action *actions, int32_t *span_reward);  // ofx_step.hip
-
-extern "C" int ofx_step_repeat(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0,
-                               int32_t n_ticks, const uint8_t *hold_mask, const ofx_action *actions, int32_t *span_reward,
-                               int32_t observe_map_type) {
-  if (!h || !behaviours_host) { ofx_set_error("ofx_step_repeat: null argument"); return OFX_ERR_INVALID; }
-  if (!h->spawned) { ofx_set_error("ofx_step_repeat before ofx_spawn"); return OFX_ERR_STATE; }
-  if (n_ticks < 1 || observe_map_type < -1 || observe_map_type > OFX_MAP_BITS) {
-    ofx_set_error("ofx_step_repeat: n_ticks must be >= 1 and observe_map_type -1 (none) or an OFX_MAP_* type");
-    return OFX_ERR_INVALID;
-  }
-  if (hold_mask && !actions) { ofx_set_error("ofx_step_repeat: hold_mask given without actions"); return OFX_ERR_INVALID; }
-  for (int i = 0; i < h->cfg.n_ships; i++)
-    if (behaviours_host[i] < OFX_BOT_IDLE || behaviours_host[i] > OFX_BOT_SHOOT) {
-      ofx_set_error("You must give a bot in parameter or select an existing behavior.");  // agents/agent.py:51
-      return OFX_ERR_INVALID;
-    }
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipMemcpyAsync(h->bot_behaviours, behaviours_host, sizeof(int32_t) * h->cfg.n_ships, hipMemcpyHostToDevice,
-                         h->stream));
-  int rc;
-  if ((rc = ofx_launch_step_repeat(h, seed, tick0, n_ticks, hold_mask, actions, span_reward))) return rc;
-  if (observe_map_type >= 0 && (rc = ofx_launch_raster(h, observe_map_type, nullptr, nullptr))) return rc;
-  return OFX_OK;
-}
-
 // ------------------------------------------------------------------ obs head
 // Observation.analyse_ship + toVector head (observation.py:101-123)
 __global__ void k_obs_head(int N, int M, int W, int H, ofx_state st, double *head, uint8_t *done) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= N * M) return;
-  double *v = head + (size_t)t * 8;
-  v[0] = (double)st.reward[t];
-  v[1] = 1.0;  // can_shoot is constant 1 (ship.py:58)
-  v[2] = (double)st.ship_px[t];
-  v[3] = (double)st.ship_py[t];
-  v[4] = (double)W;
-  v[5] = (double)H;
-  v[6] = (double)st.ship_x[t];
-  v[7] = (double)st.ship_y[t];
+  ofx_obs_head(st, t, W, H, head + (size_t)t * 8);
   if (done) done[t] = st.alive[t] ? 0 : 1;
 }
 

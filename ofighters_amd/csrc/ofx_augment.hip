@@ -17,7 +17,6 @@
 #include <string.h>
 
 #define OFX_LDS_LIMIT (64 * 1024) /* the budget of the packed readers (ofx_replay.hip): a frame's two maps in LDS */
-#define OFX_STREAM_AUGMENT 8u
 
 struct AugmentParams {
   int W, H, words;
@@ -27,7 +26,8 @@ struct AugmentParams {
   int32_t *pointer;      // !DRAW: [n][2] or null
   const uint8_t *op;     // !DRAW: [n]
   uint8_t *op_out;       // DRAW: [n] or null
-  uint32_t k0, k1, draw, first, arena_base, mask;
+  ofx_rng_key key;
+  uint32_t draw, first, arena_base, mask;
   int perm_s, perm_g;    // the transposed walk's permutation (uint4s per map = perm_s * perm_g), perm_s == 0: none
 };
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void k_obs_transform(AugmentParams p) {
     g = 0;
     if (!pad) {
       uint32_t rr[4];
-      ofx_philox4x32_10(p.arena_base, p.first + (uint32_t)d, p.draw, OFX_STREAM_AUGMENT, p.k0, p.k1, rr);
+      ofx_philox4x32_10(p.arena_base, p.first + (uint32_t)d, p.draw, OFX_STREAM_AUGMENT, p.key, rr);
       int nth = ofx_draw_int(rr[0], __popc(p.mask) - 1);
       for (uint32_t m = p.mask; m; m &= m - 1u, nth--)
         if (nth == 0) { g = __ffs((int)m) - 1; break; }
@@ -211,7 +211,7 @@ extern "C" int ofx_replay_augment(ofx_handle *h, uint64_t seed, uint32_t draw, i
   AugmentParams p;
   augment_params(h, &p);
   p.bits[0] = (uint32_t *)bits_prev; p.bits[1] = (uint32_t *)bits_next; p.rows = rows; p.op_out = op_out;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.draw = draw; p.first = (uint32_t)first;
+  p.key = ofx_key(seed); p.draw = draw; p.first = (uint32_t)first;
   p.arena_base = (uint32_t)h->cfg.arena_base; p.mask = op_mask;
   hipLaunchKernelGGL(k_obs_transform<true>, dim3((unsigned)n, 2u), dim3(256), (size_t)p.words * 8, h->stream, p);
   OFX_HIP(hipGetLastError());

@@ -28,10 +28,6 @@
 #include <new>
 #include <vector>
 
-#define OFX_STREAM_EVOLVE 9u        /* evolution coefficient (words 0, 1) and mutation selector (words 2, 3) */
-#define OFX_STREAM_MUTATE 10u       /* the replacement value of a mutated element (words 0, 1)               */
-#define OFX_STREAM_FRESH 11u        /* a fresh genome: ofx_population_init and plan[p] == -1 (words 0, 1)    */
-
 #define POP_MAX_LAYERS 8
 #define POP_MAX_WIDTH 64
 #define POP_LIST 2048               /* set cells one wave lists before it gathers: a batch of 64 words holds <= 2048 */
@@ -63,7 +59,7 @@ __device__ inline uint32_t pop_element(uint32_t s, uint32_t first, uint32_t nin,
 // jobs == nullptr: job j is a fresh genome in slot j (ofx_population_init)
 __global__ __launch_bounds__(256) void k_pop_breed(double *data, const int32_t *jobs, int n_jobs, uint32_t G,
                                                    uint32_t first, uint32_t nin, uint32_t n1, double evo, double mut,
-                                                   uint32_t k0, uint32_t k1, uint32_t generation) {
+                                                   ofx_rng_key key, uint32_t generation) {
   const uint32_t s = blockIdx.x * 256u + threadIdx.x;
   if (s >= G) return;
   const uint32_t e = pop_element(s, first, nin, n1);
@@ -72,11 +68,11 @@ __global__ __launch_bounds__(256) void k_pop_breed(double *data, const int32_t *
     uint32_t r[4];
     double w;
     if (src < 0) {
-      ofx_philox4x32_10((uint32_t)dst, e, generation, OFX_STREAM_FRESH, k0, k1, r);
+      ofx_philox4x32_10((uint32_t)dst, e, generation, OFX_STREAM_FRESH, key, r);
       w = 2.0 * pop_uniform(r[0], r[1]) - 1.0;
     } else {
       w = data[(size_t)src * G + s];
-      ofx_philox4x32_10((uint32_t)dst, e, generation, OFX_STREAM_EVOLVE, k0, k1, r);
+      ofx_philox4x32_10((uint32_t)dst, e, generation, OFX_STREAM_EVOLVE, key, r);
       if (evo > 0.0) {
         const double c = (2.0 * pop_uniform(r[0], r[1]) - 1.0) * evo;
         const double cw = c * w;
@@ -84,7 +80,7 @@ __global__ __launch_bounds__(256) void k_pop_breed(double *data, const int32_t *
       }
       if (mut > 0.0 && pop_uniform(r[2], r[3]) < mut) {
         uint32_t q[4];
-        ofx_philox4x32_10((uint32_t)dst, e, generation, OFX_STREAM_MUTATE, k0, k1, q);
+        ofx_philox4x32_10((uint32_t)dst, e, generation, OFX_STREAM_MUTATE, key, q);
         w = 2.0 * pop_uniform(q[0], q[1]) - 1.0;
       }
     }
@@ -176,14 +172,11 @@ __global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state 
   __syncthreads();
   if (tid < n1) {
     // first layer of neuron tid: head in toVector order, the map cells in (wave, group) order, bias
-    double z = gen[(size_t)0 * n1 + tid] * (double)st.reward[s];
-    z += gen[(size_t)1 * n1 + tid] * 1.0;
-    z += gen[(size_t)2 * n1 + tid] * (double)st.ship_px[s];
-    z += gen[(size_t)3 * n1 + tid] * (double)st.ship_py[s];
-    z += gen[(size_t)4 * n1 + tid] * (double)W;
-    z += gen[(size_t)5 * n1 + tid] * (double)H;
-    z += gen[(size_t)6 * n1 + tid] * (double)st.ship_x[s];
-    z += gen[(size_t)7 * n1 + tid] * (double)st.ship_y[s];
+    double v[8];
+    ofx_obs_head(st, s, W, H, v);
+    double z = gen[tid] * v[0];
+#pragma unroll
+    for (int k = 1; k < 8; k++) z += gen[(size_t)k * n1 + tid] * v[k];
     for (int q = 0; q < 4; q++)
       for (int j = 0; j < groups; j++) z += part[q][j * n1 + tid];
     act[0][tid] = pop_sigmoid(z + gen[n_w + tid]);
@@ -312,8 +305,7 @@ static int launch_breed(ofx_handle *h, ofx_population *p, const int32_t *jobs, i
   if (n_jobs < 1) return OFX_OK;
   const dim3 grid((p->G + 255u) / 256u, (unsigned)(n_jobs < 65535 ? n_jobs : 65535));
   hipLaunchKernelGGL(k_pop_breed, grid, dim3(256), 0, h->stream, p->data, jobs, n_jobs, p->G, p->first,
-                     (uint32_t)p->layers[0], (uint32_t)p->layers[1], evo, mut, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     generation);
+                     (uint32_t)p->layers[0], (uint32_t)p->layers[1], evo, mut, ofx_key(seed), generation);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }

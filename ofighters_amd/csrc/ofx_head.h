@@ -46,9 +46,6 @@ struct HeadParams2 {
   float *soft_m, *soft_z;       // [S][8] per consumer wave (the slots of cand_*): its maximum and sum exp((v - m) / T)
 };
 
-#define OFX_STREAM_BOLTZMANN_PTR 6u
-#define OFX_STREAM_BOLTZMANN_ACT 7u
-
 #ifdef __HIPCC__
 // Standard Gumbel noise from one Philox word r, in float32: w = (r + 0.5) / 2^32, E = -ln(1 - w), g = -ln(E).
 // Rounding 1 - w to float32 would quantise g by about 1e-2 around g = 12, the tail that wins among 160 000 pixels, so

@@ -6,9 +6,11 @@
 #include <stdio.h>
 
 #include "../../include/ofx.h"
+#include "ofx_rng.h"
 
 #define OFX_WAVE 64
 #define OFX_ARENAS_PER_BLOCK 4 /* one 64-lane wave per arena, 256-thread blocks */
+static inline int arena_blocks(int N) { return (N + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK; }
 
 void ofx_set_error(const char *fmt, ...);
 
@@ -100,7 +102,6 @@ struct ofx_handle {
 #define OFX_RING_MAX 65536         /* numbered events of ofx_event_record */
 
 // kernels / launchers implemented in the other translation units
-int ofx_launch_step(ofx_handle *h, const ofx_action *actions);
 int ofx_launch_raster(ofx_handle *h, int map_type, void *ship_map, void *laser_map);
 int ofx_ensure_buffer(ofx_handle *h, void **buf, size_t *have, size_t bytes);  // a handle-kept block, grown on demand
 int ofx_ensure_scratch(ofx_handle *h, size_t bytes);   // h->scratch; transient: the next caller may overwrite or re-allocate it
@@ -124,24 +125,4 @@ int ofx_policy_predict_obs(ofx_handle *h, const float *weights, int32_t n_obs, c
 
 #define OFX_MAP_BITS_LSB 4 /* internal: 1 bit / cell, pixel p -> bit (p & 31) of word p >> 5 */
 
-// Philox4x32-10 counter RNG (Salmon et al. SC'11); same constants / round
-// structure as the oracle's restatement so both produce one stream.
-__host__ __device__ inline void ofx_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                                  uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-#define OFX_STREAM_BOT 0u
-#define OFX_STREAM_RESET 1u
-
-__host__ __device__ inline int32_t ofx_draw_int(uint32_t r, int32_t n_inclusive) {
-  return (int32_t)(((uint64_t)r * (uint64_t)(n_inclusive + 1)) >> 32);
-}
+#include "ofx_sim.h"  // the arena rules more than one kernel applies: bots' law, reset draw, observation head

@@ -91,14 +91,11 @@ __global__ void k_obs_first(int N, int M, int W, int H, ofx_state st, const doub
   if (t >= N * M * n1) return;
   const int o = t % n1, s = t / n1, a = s / M;
   const double *w = W1 + (size_t)o * nin;
-  double acc = w[0] * (double)st.reward[s];
-  acc += w[1] * 1.0;
-  acc += w[2] * (double)st.ship_px[s];
-  acc += w[3] * (double)st.ship_py[s];
-  acc += w[4] * (double)W;
-  acc += w[5] * (double)H;
-  acc += w[6] * (double)st.ship_x[s];
-  acc += w[7] * (double)st.ship_y[s];
+  double v[8];
+  ofx_obs_head(st, s, W, H, v);
+  double acc = w[0] * v[0];
+#pragma unroll
+  for (int k = 1; k < 8; k++) acc += w[k] * v[k];
   acc += tail[(size_t)a * n1 + o];
   y[t] = sigmoid64(acc + B1[o]);
 }

@@ -567,10 +567,7 @@ __global__ __launch_bounds__(256) void k_head_dense(HeadParams p) {
 #pragma unroll
       for (int k = 0; k < 8; k++) vec[k] = p.vec8[(size_t)s * 8 + k];
     } else {
-      vec[0] = (float)p.st.reward[s]; vec[1] = 1.f;
-      vec[2] = (float)p.st.ship_px[s]; vec[3] = (float)p.st.ship_py[s];
-      vec[4] = (float)PS; vec[5] = (float)PS;
-      vec[6] = (float)p.st.ship_x[s]; vec[7] = (float)p.st.ship_y[s];
+      ofx_obs_head(p.st, s, PS, PS, vec);
     }
     for (int o = lane; o < 100; o += 64) {
       float acc = 0.f;
@@ -673,7 +670,8 @@ __device__ __forceinline__ double arena_eps(double eps, const double *expo, int 
 struct BoltzArgs {
   double eps;
   float tau_act, tau_ptr;
-  uint32_t k0, k1, tick;
+  ofx_rng_key key;
+  uint32_t tick;
   float *q_sa, *p_sp, *v_act, *v_ptr;
 };
 
@@ -693,7 +691,7 @@ __global__ void k_boltz_temps(int N, int M, double eps, const double *expo, floa
 // sampled the same way from two Gumbel words of its own stream.
 __global__ void k_policy_boltz_finish(int S, int M, int arena_base, const uint8_t *mask, const unsigned long long *cand_key,
                                       const float *cand_raw, const unsigned *cand_max, const float *act, const float *t_act,
-                                      uint32_t k0, uint32_t k1, uint32_t tick, int32_t *iaction, int32_t *ipointer,
+                                      ofx_rng_key noise_key, uint32_t tick, int32_t *iaction, int32_t *ipointer,
                                       float *q_sa, float *p_sp, float *v_act, float *v_ptr) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S || (mask && !mask[s])) return;
@@ -716,7 +714,7 @@ __global__ void k_policy_boltz_finish(int S, int M, int arena_base, const uint8_
   int ia = a1 > a0 ? 1 : 0;   // np.argmax: first maximum
   if (T != 0.f) {
     uint32_t r[4];
-    ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_BOLTZMANN_ACT, k0, k1, r);
+    ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_BOLTZMANN_ACT, noise_key, r);
     ia = fmaf(T, hd_gumbel(r[1]), a1) > fmaf(T, hd_gumbel(r[0]), a0) ? 1 : 0;
   }
   iaction[s] = ia;
@@ -985,7 +983,7 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
                        b.tau_ptr, ws.t_act, ws.t_ptr);
     OFX_HIP(hipGetLastError());
     hp2.sample = 1; hp2.M = a.M; hp2.arena_base = h->cfg.arena_base;
-    hp2.nk0 = b.k0; hp2.nk1 = b.k1; hp2.ntick = b.tick; hp2.t_ptr = ws.t_ptr;
+    hp2.nk0 = b.key.k0; hp2.nk1 = b.key.k1; hp2.ntick = b.tick; hp2.t_ptr = ws.t_ptr;
     hp2.cand_key = ws.cand_key; hp2.cand_raw = ws.cand_raw; hp2.cand_max = ws.cand_max;
   }
   const float soft_k = soft ? (float)(1.4426950408889634 / (double)a.tau_ptr) : 0.f;   // log2(e) / T
@@ -997,7 +995,7 @@ static int policy_forward_impl(ofx_handle *h, const ForwardArgs &a) {
   if (a.boltz) {
     const BoltzArgs &b = *a.boltz;
     hipLaunchKernelGGL(k_policy_boltz_finish, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, a.M, h->cfg.arena_base,
-                       a.ship_mask, ws.cand_key, ws.cand_raw, ws.cand_max, a.act_values, ws.t_act, b.k0, b.k1, b.tick,
+                       a.ship_mask, ws.cand_key, ws.cand_raw, ws.cand_max, a.act_values, ws.t_act, b.key, b.tick,
                        a.iaction ? a.iaction : ws.iaction, a.ipointer ? a.ipointer : ws.ipointer, b.q_sa, b.p_sp, b.v_act,
                        b.v_ptr);
     OFX_HIP(hipGetLastError());
@@ -1101,18 +1099,17 @@ int ofx_policy_predict_obs(ofx_handle *h, const float *weights, int32_t n_obs, c
   return policy_forward_impl(h, a);
 }
 
-#define OFX_STREAM_EXPLORE 2u
 // The draw of ship i of arena a at `tick`: true when the ship explores, i.e. random_play() replaces its greedy choice
 // (np.random.rand() <= epsilon, qlearnIA_V2.py:201, or the collecting phase).  The Philox words exist either way, so
 // (*ia, *px, *py) is a valid random choice for every ship - ofx_policy_act probes the heat map there before it knows.
 // `expo` (ofx_policy_epsilon_ladder, null = none) changes only WHETHER the ship explores: arena a explores at
 // epsilon^expo[a]; exponent 1 leaves epsilon as it is (no pow), +inf is a greedy arena that not even `collecting` moves.
 __device__ __forceinline__ bool explore_draw(int a, int i, int W, int H, int arena_base, double eps, const double *expo,
-                                             uint32_t k0, uint32_t k1, uint32_t tick, int collecting, int32_t *ia,
+                                             ofx_rng_key key, uint32_t tick, int collecting, int32_t *ia,
                                              int32_t *px, int32_t *py) {
   uint32_t r[4];
-  ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_EXPLORE, k0, k1, r);
-  const double u = (double)r[0] * (1.0 / 4294967296.0);
+  ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)i, tick, OFX_STREAM_EXPLORE, key, r);
+  const double u = ofx_unit(r[0]);
   *ia = ofx_draw_int(r[1], 1);
   *px = ofx_draw_int(r[2], W - 1);
   *py = ofx_draw_int(r[3], H - 1);
@@ -1122,14 +1119,14 @@ __device__ __forceinline__ bool explore_draw(int a, int i, int W, int H, int are
   return collecting || u <= eps;
 }
 
-__global__ void k_policy_explore(int N, int M, int W, int H, int arena_base, double eps, const double *expo, uint32_t k0,
-                                 uint32_t k1, uint32_t tick, int collecting, const uint8_t *mask, int32_t *iaction,
+__global__ void k_policy_explore(int N, int M, int W, int H, int arena_base, double eps, const double *expo, ofx_rng_key key,
+                                 uint32_t tick, int collecting, const uint8_t *mask, int32_t *iaction,
                                  int32_t *ipointer) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N * M || (mask && !mask[s])) return;
   const int a = s / M, i = s - a * M;
   int32_t ia, px, py;
-  if (explore_draw(a, i, W, H, arena_base, eps, expo, k0, k1, tick, collecting, &ia, &px, &py)) {
+  if (explore_draw(a, i, W, H, arena_base, eps, expo, key, tick, collecting, &ia, &px, &py)) {
     iaction[s] = ia;
     ipointer[2 * s] = px;
     ipointer[2 * s + 1] = py;
@@ -1149,8 +1146,7 @@ extern "C" int ofx_policy_explore(ofx_handle *h, double epsilon, uint64_t seed, 
   if (!ipointer) ipointer = rip;
   const int S = h->cfg.n_arenas * h->cfg.n_ships;
   hipLaunchKernelGGL(k_policy_explore, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
-                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     tick, collecting, ship_mask, iaction, ipointer);
+                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, ofx_key(seed), tick, collecting, ship_mask, iaction, ipointer);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -1192,8 +1188,8 @@ extern "C" int ofx_policy_epsilon_ladder_host(ofx_handle *h, double *dst_host) {
 // kernel as its probe: the heat map's value at an exploratory pointer leaves the same pass that finds the maximum.
 // Everything is addressed by ship index s = a * M + i (a masked forward walks the compacted list, but hd_ship maps
 // every work item back to s before it reads the probe or writes a result).
-__global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, double eps, const double *expo, uint32_t k0,
-                                 uint32_t k1, uint32_t tick, int collecting, const uint8_t *mask, uint8_t *explores,
+__global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, double eps, const double *expo, ofx_rng_key key,
+                                 uint32_t tick, int collecting, const uint8_t *mask, uint8_t *explores,
                                  int32_t *draw_ia, int32_t *probe) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= N * M) return;
@@ -1203,7 +1199,7 @@ __global__ void k_policy_predraw(int N, int M, int W, int H, int arena_base, dou
   }
   const int a = s / M, i = s - a * M;
   int32_t ia, px, py;
-  explores[s] = explore_draw(a, i, W, H, arena_base, eps, expo, k0, k1, tick, collecting, &ia, &px, &py) ? 1 : 0;
+  explores[s] = explore_draw(a, i, W, H, arena_base, eps, expo, key, tick, collecting, &ia, &px, &py) ? 1 : 0;
   draw_ia[s] = ia;
   probe[2 * s] = px;
   probe[2 * s + 1] = py;
@@ -1278,8 +1274,7 @@ extern "C" int ofx_policy_act(ofx_handle *h, const float *weights, const uint8_t
   q_sa = q_sa ? q_sa : B.q_sa; p_sp = p_sp ? p_sp : B.p_sp;
   v_act = v_act ? v_act : B.v_act; v_ptr = v_ptr ? v_ptr : B.v_ptr;
   hipLaunchKernelGGL(k_policy_predraw, dim3((S + 255) / 256), dim3(256), 0, h->stream, h->cfg.n_arenas, h->cfg.n_ships,
-                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     tick, collecting, ship_mask, B.explores, B.draw_ia, B.probe);
+                     h->cfg.width, h->cfg.height, h->cfg.arena_base, epsilon, h->eps_expo, ofx_key(seed), tick, collecting, ship_mask, B.explores, B.draw_ia, B.probe);
   OFX_HIP(hipGetLastError());
   ForwardArgs a{};
   a.weights = weights; a.ship_mask = ship_mask;
@@ -1313,7 +1308,7 @@ extern "C" int ofx_policy_act_boltzmann(ofx_handle *h, const float *weights, con
   const bool kept = !q_sa && !p_sp && !v_act && !v_ptr;   // as in ofx_policy_act
   BoltzArgs b;
   b.eps = epsilon; b.tau_act = tau_act; b.tau_ptr = tau_ptr;
-  b.k0 = (uint32_t)seed; b.k1 = (uint32_t)(seed >> 32); b.tick = tick;
+  b.key = ofx_key(seed); b.tick = tick;
   b.q_sa = q_sa ? q_sa : B.q_sa; b.p_sp = p_sp ? p_sp : B.p_sp;
   b.v_act = v_act ? v_act : B.v_act; b.v_ptr = v_ptr ? v_ptr : B.v_ptr;
   ForwardArgs a{};

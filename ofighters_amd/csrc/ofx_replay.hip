@@ -254,7 +254,7 @@ __device__ __forceinline__ float per_mass(float e1, float e2, float eps, float a
 // stays the fallback for a non-finite error and is raised by one wave reduction (an arena is one wave: no atomics).
 template <bool VALUED>
 __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
-  const int a = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int a = blockIdx.x * OFX_ARENAS_PER_BLOCK + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (a >= p.N) return;  // wave-uniform
   const int t = a * p.M + lane;
   const bool ship = lane < p.M && (!p.mask || p.mask[t]);
@@ -262,14 +262,10 @@ __global__ __launch_bounds__(256) void k_replay_capture(CaptureParams p) {
   float hd[8];
   int done = 0, reward = 0;
   if (plays) {
-    reward = p.st.reward[t];  // obs.reward: sampled before Agent.step zeroes it (agent.py:73-74)
+    reward = p.st.reward[t];  // obs.reward
     done = p.st.alive[t] ? 0 : 1;
-    hd[0] = (float)reward; hd[1] = 1.f;
-    hd[2] = (float)p.st.ship_px[t]; hd[3] = (float)p.st.ship_py[t];
-    hd[4] = (float)p.W; hd[5] = (float)p.H;
-    hd[6] = (float)p.st.ship_x[t]; hd[7] = (float)p.st.ship_y[t];
-    // the row's reward (and the valued form's targets) may come from a span's sum; hd[0] above stays the state's
-    // reward, which is what the live forward feeds (ofx_policy.hip: vec[0] = st.reward)
+    ofx_obs_head(p.st, t, p.W, p.H, hd);  // the head the live forward feeds
+    // the row's reward (and the valued form's targets) may come from a span's sum; hd[0] stays the state's reward
     if (p.r.reward_src) reward = p.r.reward_src[t];
   }
   // the arena keeps this lock-step's maps iff one of its agents plays (k_replay_frames copies them afterwards)
@@ -475,8 +471,8 @@ static int replay_capture(ofx_handle *h, const char *who, uint32_t tick, const u
   p.F = r->frames;
   p.tick = (int)tick; p.st = h->st; p.mask = ship_mask; p.iaction = iaction; p.ipointer = ipointer; p.r = *r;
   p.q_sa = q_sa; p.p_sp = p_sp; p.v_act = v_act; p.v_ptr = v_ptr;
-  if (q_sa) hipLaunchKernelGGL(k_replay_capture<true>, dim3((p.N + 3) / 4), dim3(256), 0, h->stream, p);
-  else hipLaunchKernelGGL(k_replay_capture<false>, dim3((p.N + 3) / 4), dim3(256), 0, h->stream, p);
+  if (q_sa) hipLaunchKernelGGL(k_replay_capture<true>, dim3(arena_blocks(p.N)), dim3(256), 0, h->stream, p);
+  else hipLaunchKernelGGL(k_replay_capture<false>, dim3(arena_blocks(p.N)), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   if (r->packed)
     hipLaunchKernelGGL(k_replay_frames_packed, dim3((unsigned)p.N), dim3(256), 0, h->stream, p.N, r->frames, r->words,
@@ -638,9 +634,8 @@ extern "C" int ofx_replay_frame_host(ofx_handle *h, int32_t arena, int32_t tick,
 
 // ---- minibatch: random.sample(memory, min(batch, len(memory))) per arena (qlearnIA_V2.py:241-243) ----------------
 // Floyd's subset sampling (uniform over the subsets, no replacement) on Philox draws: counter (global arena, j,
-// draw, stream 3).  Transitions whose `state` frame has already left the arena's frame ring are not eligible (only
+// draw, OFX_STREAM_REPLAY).  Transitions whose `state` frame has already left the arena's frame ring are not eligible (only
 // possible when the ring is shorter than the rows need: C rows in runs of consecutive plays use C + #runs frames).  slot[a][j] indexes the arena's rows oldest-first, -1 pads.
-#define OFX_STREAM_REPLAY 3u
 
 // Eligibility: row o of arena a can be sampled while its `state` frame is still in the frame ring, i.e. the slot it
 // names still holds its lock-step.  Rows are chronological, so the expired ones are an arena's oldest.
@@ -663,7 +658,7 @@ __device__ __forceinline__ int expired_rows_wave(const ofx_replay &r, int a, int
   return ring.count;
 }
 
-__global__ void k_replay_sample(int N, int C, int F, int batch, int arena_base, uint32_t k0, uint32_t k1, uint32_t draw,
+__global__ void k_replay_sample(int N, int C, int F, int batch, int arena_base, ofx_rng_key key, uint32_t draw,
                                 ofx_replay r, int32_t *slot, int32_t *n_out) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x;
   if (a >= N) return;
@@ -676,7 +671,7 @@ __global__ void k_replay_sample(int N, int C, int F, int batch, int arena_base, 
   for (int j = 0; j < n; j++) {
     const int top = valid - n + j;  // draw t in [0, top]
     uint32_t rr[4];
-    ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)j, draw, OFX_STREAM_REPLAY, k0, k1, rr);
+    ofx_philox4x32_10((uint32_t)(arena_base + a), (uint32_t)j, draw, OFX_STREAM_REPLAY, key, rr);
     int tsel = ofx_draw_int(rr[0], top);
     for (int q = 0; q < j; q++) if (out[q] == skip + tsel) { tsel = top; break; }
     out[j] = skip + tsel;
@@ -692,7 +687,7 @@ extern "C" int ofx_replay_sample(ofx_handle *h, uint64_t seed, uint32_t draw, in
   OFX_HIP(hipSetDevice(h->cfg.device));
   const int N = h->cfg.n_arenas;
   hipLaunchKernelGGL(k_replay_sample, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, r->capacity, r->frames, batch,
-                     h->cfg.arena_base, (uint32_t)seed, (uint32_t)(seed >> 32), draw, *r, slot, n_sampled);
+                     h->cfg.arena_base, ofx_key(seed), draw, *r, slot, n_sampled);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -924,7 +919,6 @@ extern "C" int ofx_replay_gather_nstep(ofx_handle *h, const int32_t *slot, const
 // mass[a][ring position] = p^alpha beside every row; sampling is stratified proportional over the arena's eligible rows,
 // with a summation order fixed so that a CPU restatement (tests/per_oracle.py) picks the same slots: float64 sums, 64
 // chunks of ceil(valid / 64) consecutive rows each summed in row order, chunk totals chained in chunk order.
-#define OFX_STREAM_PER 4u
 __global__ void k_fill_f32(size_t count, float v, float *out) {
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i < count) out[i] = v;
@@ -963,7 +957,8 @@ static int per_ready(ofx_handle *h, const char *who) {
 
 struct PerSampleParams {
   int N, C, F, batch, arena_base;
-  uint32_t k0, k1, draw;
+  ofx_rng_key key;
+  uint32_t draw;
   double beta;
   ofx_replay r;
   int32_t *slot, *n_out;
@@ -1027,8 +1022,8 @@ __global__ __launch_bounds__(256) void k_replay_sample_per(PerSampleParams p) {
     double u = 0.0;
     if (j < n) {
       uint32_t rr[4];
-      ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)j, p.draw, OFX_STREAM_PER, p.k0, p.k1, rr);
-      const double U = (double)rr[0] * 0x1p-32;
+      ofx_philox4x32_10((uint32_t)(p.arena_base + a), (uint32_t)j, p.draw, OFX_STREAM_PER, p.key, rr);
+      const double U = ofx_unit(rr[0]);
       u = ((double)j + U) / n * total;
     }
     int klo = 0, khi = nchunks;  // first chunk with incl > u lies in [klo, khi]; khi == nchunks: none
@@ -1064,7 +1059,7 @@ extern "C" int ofx_replay_sample_prioritized(ofx_handle *h, uint64_t seed, uint3
   OFX_HIP(hipSetDevice(h->cfg.device));
   PerSampleParams p;
   p.N = h->cfg.n_arenas; p.C = h->replay->capacity; p.F = h->replay->frames; p.batch = batch;
-  p.arena_base = h->cfg.arena_base; p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.draw = draw; p.beta = beta;
+  p.arena_base = h->cfg.arena_base; p.key = ofx_key(seed); p.draw = draw; p.beta = beta;
   p.r = *h->replay; p.slot = slot; p.n_out = n_sampled; p.is_weight = is_weight;
   hipLaunchKernelGGL(k_replay_sample_per, dim3((unsigned)((p.N + 3) / 4)), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
@@ -1257,7 +1252,6 @@ extern "C" int ofx_replay_set_actor_values(ofx_handle *h, const float *src_host)
 // ---- global minibatch sampling: n rows from the union of all arenas' memories (include/ofx.h states the contract) -----
 // Per-arena pass (skip, v, T) -> integer scan of v -> float64 group scan of T (PER) -> one wave per draw -> the weights
 // over their maximum.  The list gather and the list write-back take the (arena, slot) pairs the sampler wrote.
-#define OFX_STREAM_GLOBAL 5u
 #define OFX_GLOBAL_GROUP 256
 
 // One wave per arena: skip, v and, PER, T[a] by the chunk scheme.
@@ -1303,7 +1297,8 @@ __global__ __launch_bounds__(256) void k_global_group_chain(int N, ofx_replay r)
 
 struct GlobalDrawParams {
   int N, C, n_rows, arena_base;
-  uint32_t k0, k1, draw;
+  ofx_rng_key key;
+  uint32_t draw;
   double beta;
   ofx_replay r;
   int32_t *arena, *slot;
@@ -1337,7 +1332,7 @@ __global__ __launch_bounds__(256) void k_global_draw(GlobalDrawParams p) {
     return;
   }
   uint32_t rr[4];
-  ofx_philox4x32_10((uint32_t)p.arena_base, (uint32_t)j, p.draw, OFX_STREAM_GLOBAL, p.k0, p.k1, rr);
+  ofx_philox4x32_10((uint32_t)p.arena_base, (uint32_t)j, p.draw, OFX_STREAM_GLOBAL, p.key, rr);
   if constexpr (!PER) {
     const long long lo = (long long)j * R / n, hi = ((long long)j + 1) * R / n;
     const long long idx = lo + ofx_draw_int(rr[0], (int32_t)(hi - lo - 1));
@@ -1349,7 +1344,7 @@ __global__ __launch_bounds__(256) void k_global_draw(GlobalDrawParams p) {
     }
   } else {
     const double total = p.r.g_G[p.N - 1];
-    const double U = (double)rr[0] * 0x1p-32;
+    const double U = ofx_unit(rr[0]);
     const double u = ((double)j + U) / (double)n * total;
     int lo = 0, hi = p.N;  // the first arena with G > u lies in [lo, hi]; hi == N: none
     while (lo < hi) {
@@ -1425,7 +1420,7 @@ extern "C" int ofx_replay_sample_global(ofx_handle *h, uint64_t seed, uint32_t d
                      r->g_voff);
   GlobalDrawParams p;
   p.N = N; p.C = r->capacity; p.n_rows = n_rows; p.arena_base = h->cfg.arena_base;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.draw = draw; p.beta = beta;
+  p.key = ofx_key(seed); p.draw = draw; p.beta = beta;
   p.r = *r; p.arena = arena; p.slot = slot; p.is_weight = is_weight;
   const dim3 draws((unsigned)((n_rows + 3) / 4));
   if (prioritized) {

@@ -21,7 +21,8 @@
 // in place (a chunk's stores land at or below its own load indices).
 // Three forms of the one kernel: k_step<false> (the caller's actions, one lock-step), k_step<true> (the bots' law, n
 // lock-steps per launch: ofx_rollout) and k_step<true, true> (the same loop with held actions for the ships of a mask
-// and the span's rewards summed: ofx_step_repeat).
+// and the span's rewards summed: ofx_step_repeat).  Their entry points, and ofx_bot_actions with k_bots, follow the
+// kernel; the bots' law itself is ofx_bot_action (ofx_sim.h).
 //
 // Arithmetic is fp64 with contraction off (build flag -ffp-contract=off):
 // positions are bit-identical to CPython's.  The collide test
@@ -37,10 +38,11 @@ struct StepParams {
   double hit_thresh;
   ofx_state st;
   const ofx_action *actions;   // BOTS = false: the caller's actions [N][M]
-  // BOTS = true (ofx_rollout): the scripted bots' action law evaluated in the kernel (agents/agent.py:99-155 on the
-  // counter RNG, the same draws as k_bots) for lock-steps tick0 .. tick0 + n_ticks - 1, all inside ONE launch
+  // BOTS = true (ofx_rollout): the scripted bots' action law evaluated in the kernel (ofx_bot_action, as k_bots does)
+  // for lock-steps tick0 .. tick0 + n_ticks - 1, all inside ONE launch
   const int32_t *beh;          // device [M] OFX_BOT_*
-  uint32_t k0, k1, tick0;
+  ofx_rng_key key;
+  uint32_t tick0;
   int n_ticks, arena_base;
   // HOLD = true (ofx_step_repeat): BOTS' loop in which the ships marked in hold_mask play `actions` on every lock-step
   const uint8_t *hold_mask;    // device [N][M] or null = nobody holds
@@ -59,36 +61,6 @@ __device__ inline double py_fmod_pos(double a, double b) {
 }
 
 __device__ inline int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-// The scripted bots' law for ship `i` of global arena `ga` at lock-step `tick` - the arithmetic of k_bots
-// (ofx_api.hip), evaluated by the ship's own lane: `alive` / (ptx, pty) are the ship's state when request_actions
-// runs, i.e. before this lock-step's lasers move (battleground.py:146-150).
-__device__ inline ofx_action bot_action(int beh, uint32_t ga, uint32_t i, uint32_t tick, uint32_t k0, uint32_t k1, int W,
-                                        int H, bool alive, int ptx, int pty) {
-  uint32_t r[4];
-  ofx_philox4x32_10(ga, i, tick, OFX_STREAM_BOT, k0, k1, r);
-  bool shoot = false, thrust = false, repoint = false;
-  const double u0 = (double)r[0] * (1.0 / 4294967296.0), u1 = (double)r[1] * (1.0 / 4294967296.0);
-  switch (beh) {
-    case OFX_BOT_RANDOM: {
-      const uint32_t k = (uint32_t)(((uint64_t)r[0] * 3u) >> 32);
-      shoot = k == 0; thrust = k == 1; repoint = k == 2;
-    } break;
-    case OFX_BOT_TURRET: shoot = u0 < 0.8; repoint = u1 < 0.3; break;
-    case OFX_BOT_RUNNER: thrust = u0 < 0.9; repoint = u1 < 0.1; break;
-    case OFX_BOT_THRUST: thrust = true; break;
-    case OFX_BOT_SHOOT: shoot = true; break;
-    default: break;
-  }
-  ofx_action act;
-  act.px = ptx; act.py = pty;
-  act.shoot = 0; act.thrust = 0; act.valid = alive ? 1 : 0; act._pad = 0;
-  if (alive) {
-    act.shoot = shoot; act.thrust = thrust;
-    if (repoint) { act.px = ofx_draw_int(r[2], W); act.py = ofx_draw_int(r[3], H); }
-  }
-  return act;
-}
 
 template <bool BOTS, bool HOLD = false>
 __global__ __launch_bounds__(256) void k_step(StepParams p) {
@@ -134,8 +106,8 @@ __global__ __launch_bounds__(256) void k_step(StepParams p) {
     rew = 0;
   }
   ofx_action bot_act;           // request_actions comes before generate_frame: the state the lasers have not touched yet
-  if (BOTS) bot_act = bot_action(my_beh, (uint32_t)(p.arena_base + a), (uint32_t)lane, p.tick0 + (uint32_t)tk, p.k0, p.k1,
-                                 p.W, p.H, alive, ptx, pty);
+  if (BOTS) bot_act = ofx_bot_action(my_beh, (uint32_t)(p.arena_base + a), (uint32_t)lane, p.tick0 + (uint32_t)tk, p.key,
+                                     p.W, p.H, alive, ptx, pty);
   unsigned long long alive_mask = __ballot(alive);
 
   // ---- laser phase ----
@@ -337,40 +309,138 @@ static StepParams step_params(ofx_handle *h) {
   p.r_death = c.reward_death; p.r_kill = c.reward_kill; p.r_aim = c.reward_aim; p.r_traj = c.reward_trajectory;
   p.hit_thresh = h->hit_thresh;
   p.st = h->st;
-  p.actions = nullptr; p.beh = nullptr; p.k0 = p.k1 = p.tick0 = 0; p.n_ticks = 1; p.arena_base = c.arena_base;
+  p.actions = nullptr; p.beh = nullptr; p.key = ofx_key(0); p.tick0 = 0; p.n_ticks = 1; p.arena_base = c.arena_base;
   p.hold_mask = nullptr; p.span_reward = nullptr;
   return p;
 }
 
-int ofx_launch_step(ofx_handle *h, const ofx_action *actions) {
+template <bool BOTS, bool HOLD>
+static int launch_step(ofx_handle *h, const StepParams &p) {
+  hipLaunchKernelGGL((k_step<BOTS, HOLD>), dim3(arena_blocks(p.N)), dim3(256), 0, h->stream, p);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// the bots' form: n_ticks lock-steps from tick0 in ONE launch (h->bot_behaviours already holds the behaviours)
+static StepParams bots_params(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks) {
+  StepParams p = step_params(h);
+  p.beh = h->bot_behaviours;
+  p.key = ofx_key(seed); p.tick0 = tick0; p.n_ticks = n_ticks;
+  return p;
+}
+
+extern "C" int ofx_step(ofx_handle *h, const ofx_action *actions) {
+  if (!h || !actions) { ofx_set_error("ofx_step: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_step before ofx_spawn"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
   StepParams p = step_params(h);
   p.actions = actions;
-  const int blocks = (h->cfg.n_arenas + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK;
-  hipLaunchKernelGGL(k_step<false>, dim3(blocks), dim3(256), 0, h->stream, p);
+  return launch_step<false, false>(h, p);
+}
+
+// ------------------------------------------------------------- scripted bots
+// the range check with the reference's message, then (unless the caller has nothing to launch) the upload to
+// h->bot_behaviours on the handle's stream
+static int set_behaviours(ofx_handle *h, const int32_t *behaviours_host, bool upload = true) {
+  for (int i = 0; i < h->cfg.n_ships; i++)
+    if (behaviours_host[i] < OFX_BOT_IDLE || behaviours_host[i] > OFX_BOT_SHOOT) {
+      ofx_set_error("You must give a bot in parameter or select an existing behavior.");  // agents/agent.py:51
+      return OFX_ERR_INVALID;
+    }
+  if (!upload) return OFX_OK;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipMemcpyAsync(h->bot_behaviours, behaviours_host, sizeof(int32_t) * h->cfg.n_ships, hipMemcpyHostToDevice,
+                         h->stream));
+  return OFX_OK;
+}
+
+struct BotParams {
+  int N, M, W, H, arena_base;
+  ofx_state st;
+  const int32_t *beh;
+  ofx_rng_key key;
+  uint32_t tick;
+  ofx_action *out;
+};
+
+// the bots' law as actions in memory, for a caller that steps with ofx_step
+__global__ void k_bots(BotParams p) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= p.N * p.M) return;
+  const int a = t / p.M, i = t - a * p.M;
+  p.out[t] = ofx_bot_action(p.beh[i], (uint32_t)(p.arena_base + a), (uint32_t)i, p.tick, p.key, p.W, p.H,
+                            p.st.alive[t] != 0, p.st.ship_px[t], p.st.ship_py[t]);
+}
+
+extern "C" int ofx_bot_actions(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick,
+                               ofx_action *actions) {
+  if (!h || !behaviours_host || !actions) { ofx_set_error("ofx_bot_actions: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_bot_actions before ofx_spawn"); return OFX_ERR_STATE; }
+  int rc = set_behaviours(h, behaviours_host);
+  if (rc) return rc;
+  BotParams p;
+  p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height;
+  p.arena_base = h->cfg.arena_base; p.st = h->st; p.beh = h->bot_behaviours;
+  p.key = ofx_key(seed); p.tick = tick; p.out = actions;
+  const int T = p.N * p.M;
+  hipLaunchKernelGGL(k_bots, dim3((T + 255) / 256), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
 
-// n_ticks lock-steps of bots + step in ONE launch (h->bot_behaviours already holds the behaviours)
-int ofx_launch_step_bots(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks) {
-  StepParams p = step_params(h);
-  p.beh = h->bot_behaviours;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.tick0 = tick0; p.n_ticks = n_ticks;
-  const int blocks = (h->cfg.n_arenas + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK;
-  hipLaunchKernelGGL(k_step<true>, dim3(blocks), dim3(256), 0, h->stream, p);
-  OFX_HIP(hipGetLastError());
+// ------------------------------------------------ headless loop: K lock-steps per host call
+// Battleground.run (lib/battleground.py:169-173: `while True: self.frame()`) for the scripted bots: request_actions,
+// generate_frame and - when observing - Observation(battleground) for n_ticks lock-steps enqueued by ONE call.
+extern "C" int ofx_rollout(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0, int32_t n_ticks,
+                           int32_t observe_map_type) {
+  if (!h || !behaviours_host) { ofx_set_error("ofx_rollout: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_rollout before ofx_spawn"); return OFX_ERR_STATE; }
+  if (n_ticks < 0 || observe_map_type < -1 || observe_map_type > OFX_MAP_BITS) {
+    ofx_set_error("ofx_rollout: n_ticks must be >= 0 and observe_map_type -1 (none) or an OFX_MAP_* type");
+    return OFX_ERR_INVALID;
+  }
+  int rc = set_behaviours(h, behaviours_host, n_ticks > 0);
+  if (rc || n_ticks == 0) return rc;
+  const int pb = h->prof_base;  // ofx_policy_profile: one event pair around this call's dominant kernel
+  const bool prof = pb >= 0 && pb + 1 < OFX_RING_MAX;
+  if (observe_map_type < 0) {
+    // no observer between the lock-steps: all of them inside ONE launch (an arena belongs to one wavefront)
+    if (prof && (rc = ofx_event_record(h, pb))) return rc;
+    if ((rc = launch_step<true, false>(h, bots_params(h, seed, tick0, n_ticks)))) return rc;
+    if (prof && (rc = ofx_event_record(h, pb + 1))) return rc;
+  } else {
+    for (int t = 0; t < n_ticks; t++) {
+      if ((rc = launch_step<true, false>(h, bots_params(h, seed, tick0 + (uint32_t)t, 1)))) return rc;
+      const bool last = t + 1 == n_ticks;  // the rasteriser of the last lock-step stands for the launch pair
+      if (prof && last && (rc = ofx_event_record(h, pb))) return rc;
+      if ((rc = ofx_launch_raster(h, observe_map_type, nullptr, nullptr))) return rc;
+      if (prof && last && (rc = ofx_event_record(h, pb + 1))) return rc;
+    }
+  }
+  if (pb >= 0) h->prof_base = pb + 3 < OFX_RING_MAX ? pb + 2 : -1;
   return OFX_OK;
 }
 
-// ofx_step_repeat: n_ticks lock-steps in ONE launch, the ships of hold_mask on `actions`, the others on the bots' law
-int ofx_launch_step_repeat(ofx_handle *h, uint64_t seed, uint32_t tick0, int n_ticks, const uint8_t *hold_mask,
-                           const ofx_action *actions, int32_t *span_reward) {
-  StepParams p = step_params(h);
-  p.beh = h->bot_behaviours;
-  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); p.tick0 = tick0; p.n_ticks = n_ticks;
+// ------------------------------------------------ action repeat: K lock-steps per decision in one launch
+// The held ships (the learning agents, say) keep the action of their last decision for the whole span while the others
+// follow the bots' law lock-step by lock-step; the span's rewards are summed per ship for the replay memory
+// (ofx_replay_reward_source) and the maps are rasterised once, for the next decision.
+extern "C" int ofx_step_repeat(ofx_handle *h, const int32_t *behaviours_host, uint64_t seed, uint32_t tick0,
+                               int32_t n_ticks, const uint8_t *hold_mask, const ofx_action *actions, int32_t *span_reward,
+                               int32_t observe_map_type) {
+  if (!h || !behaviours_host) { ofx_set_error("ofx_step_repeat: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_step_repeat before ofx_spawn"); return OFX_ERR_STATE; }
+  if (n_ticks < 1 || observe_map_type < -1 || observe_map_type > OFX_MAP_BITS) {
+    ofx_set_error("ofx_step_repeat: n_ticks must be >= 1 and observe_map_type -1 (none) or an OFX_MAP_* type");
+    return OFX_ERR_INVALID;
+  }
+  if (hold_mask && !actions) { ofx_set_error("ofx_step_repeat: hold_mask given without actions"); return OFX_ERR_INVALID; }
+  int rc = set_behaviours(h, behaviours_host);
+  if (rc) return rc;
+  StepParams p = bots_params(h, seed, tick0, n_ticks);
   p.hold_mask = hold_mask; p.actions = actions; p.span_reward = span_reward;
-  const int blocks = (h->cfg.n_arenas + OFX_ARENAS_PER_BLOCK - 1) / OFX_ARENAS_PER_BLOCK;
-  hipLaunchKernelGGL((k_step<true, true>), dim3(blocks), dim3(256), 0, h->stream, p);
-  OFX_HIP(hipGetLastError());
+  if ((rc = launch_step<true, true>(h, p))) return rc;
+  if (observe_map_type >= 0 && (rc = ofx_launch_raster(h, observe_map_type, nullptr, nullptr))) return rc;
   return OFX_OK;
 }
+

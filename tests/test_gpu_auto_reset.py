@@ -117,6 +117,38 @@ def test_zero_mask_is_the_global_restart():
     a.close(), b.close()
 
 
+def test_zero_mask_is_the_global_restart_on_a_non_square_map():
+    """The same scenario at 5 arenas x 3 ships on 96 x 64, where a swap of W and H in restart_finished's reset draw
+    would show: == the global restart lock-step by lock-step, and the restarted ships stand where
+    pyoracle.reset_draws puts them in episode 1 (a draw of 0 keeps the coordinate: ship.py:100-101)."""
+    from ofighters_amd import ArenaBatch, _native as nat
+    from oracle import pyoracle
+    n, m, w, h, seed, ticks = 5, 3, 96, 64, 779, 10
+    beh = ao.behaviours(m)
+    a, b = (ArenaBatch(n, m, **dict(ro.REWARDS, width=w, height=h, laser_cap=64)) for _ in range(2))
+    for x in (a, b):
+        x.spawn_random(seed)
+    au = _Auto(a, ())
+    for t in range(ticks + 3):
+        old = np.stack([a.get(nat.F_SHIP_X), a.get(nat.F_SHIP_Y)], 2)
+        au.call(seed, ticks)
+        if t == ticks:
+            b.restart_random(seed)
+            cfg = pyoracle.default_cfg(m, width=w, height=h)
+            draws = np.stack([pyoracle.reset_draws(cfg, seed, g, 1) for g in range(n)])
+            assert draws[..., 0].max() > h                        # an x draw no y draw can give
+            now = np.stack([a.get(nat.F_SHIP_X), a.get(nat.F_SHIP_Y)], 2)
+            assert np.array_equal(now, np.where(draws != 0, draws, old))
+        assert _differences(_state(a), _state(b)) == [], t
+        st = a.autoreset_state()
+        assert (st["arena_episode"] == b.episode).all() and (st["restarted"] == (1 if t == ticks else 0)).all()
+        for x in (a, b):
+            x.bot_actions(beh, seed, tick=t)
+            x.step()
+    assert b.episode == 1
+    a.close(), b.close()
+
+
 # ------------------------------------------------------------------------------------------ b. the scenarios of the model
 CASES = {
     "M8": dict(ao.SCENARIOS["M8"]),

@@ -83,14 +83,14 @@ def test_step_trace_gpu(name):
     b.close()
 
 
-def _oracle_rollout(b, oracles, behaviours, seed, ticks, episode_ticks, arena_base=0, check_every=1):
+def _oracle_rollout(b, oracles, behaviours, seed, ticks, episode_ticks, arena_base=0, check_every=1, tick0=0):
     """Advance GPU batch and per-arena CPU oracles with the device bot law and
-    compare the complete state."""
+    compare the complete state: lock-steps tick0 .. tick0 + ticks - 1."""
     from ofighters_amd import _native as nat
     from oracle import pyoracle
     N, M = b.N, b.M
     beh = np.array([nat.BEHAVIOURS[x] for x in behaviours], dtype=np.int32)
-    for t in range(ticks):
+    for t in range(tick0, tick0 + ticks):
         if t > 0 and t % episode_ticks == 0:
             b.restart_random(seed)
             for g, o in enumerate(oracles):
@@ -98,7 +98,7 @@ def _oracle_rollout(b, oracles, behaviours, seed, ticks, episode_ticks, arena_ba
         b.bot_actions(behaviours, seed, tick=t)
         acts = b.actions_host()
         b.step(actions_ptr=b._actions.ptr)
-        full = (t % check_every == 0) or t == ticks - 1
+        full = (t % check_every == 0) or t == tick0 + ticks - 1
         if full:
             X, Y, PX, PY = (b.get(f) for f in (nat.F_SHIP_X, nat.F_SHIP_Y, nat.F_SHIP_PX, nat.F_SHIP_PY))
             AL, RW, SC, KL = (b.get(f) for f in (nat.F_SHIP_ALIVE, nat.F_REWARD, nat.F_SCORE, nat.F_KILLER))
@@ -258,6 +258,50 @@ def test_rollout_k_ticks_equal_single_ticks(observe):
         assert np.array_equal(a, c)
     for a, c in zip(logs[0][1], logs[1][1]):
         assert np.array_equal(a, c)
+
+
+def test_lock_step_forms_agree_on_a_non_square_map():
+    """The three forms of the lock-step - single (ofx_bot_actions, ofx_step) calls, ofx_rollout and ofx_step_repeat
+    with nobody holding - on a 96 x 64 map: a swap of W and H in the bots' repoint draw or in the reset draw is
+    invisible on a square one.  5 arenas (the last block has idle waves), 13 ships on all six laws, 40 lock-steps as
+    1 + 7 + 32 with an episode end (restart_random) after the eighth; the single calls are held to the CPU oracle
+    lock-step by lock-step, the other two to the single calls, every field with ==."""
+    from ofighters_amd import _native as nat
+    from oracle import pyoracle
+    N, M, W, H, seed, base = 5, 13, 96, 64, 4242, 3
+    beh = (["random", "turret", "runner", "shoot", "thrust", "idle"] * 3)[:M]
+    assert {nat.BEHAVIOURS[x] for x in beh} == set(nat.BEHAVIOURS.values())
+    fields = (nat.F_SHIP_X, nat.F_SHIP_Y, nat.F_SHIP_PX, nat.F_SHIP_PY, nat.F_SHIP_ALIVE, nat.F_REWARD, nat.F_SCORE,
+              nat.F_OBS_REWARD, nat.F_KILLER, nat.F_HULL, nat.F_N_LASERS, nat.F_LASER_X, nat.F_LASER_Y, nat.F_LASER_DX,
+              nat.F_LASER_DY, nat.F_LASER_OWNER, nat.F_LASER_DEAD, nat.F_TIME, nat.F_LAST_SCORES)
+    single, roll, rep = (_batch(N, M, laser_cap=64, width=W, height=H, arena_base=base) for _ in range(3))
+    oracles = []
+    for g in range(N):
+        o = pyoracle.Arena(cfg=pyoracle.default_cfg(M, width=W, height=H))
+        o.spawn(pyoracle.reset_draws(o.cfg, seed, base + g, 0))
+        oracles.append(o)
+    for b in (single, roll, rep):
+        b.spawn_random(seed)
+    t = 0
+    for n in (1, 7, 32):
+        if t == 8:
+            for b in (single, roll, rep):
+                b.restart_random(seed)
+            for g, o in enumerate(oracles):
+                o.restart(pyoracle.reset_draws(o.cfg, seed, base + g, single.episode))
+        _oracle_rollout(single, oracles, beh, seed, ticks=n, episode_ticks=10 ** 9, arena_base=base, tick0=t)
+        roll.rollout(beh, seed, t, n)
+        rep.step_repeat(beh, seed, t, n)
+        t += n
+        for f in fields:
+            want = single.get(f)
+            assert np.array_equal(roll.get(f), want), (n, f, "rollout")
+            assert np.array_equal(rep.get(f), want), (n, f, "step_repeat")
+    assert single.episode == 1 and (single.get(nat.F_TIME) == 32).all()
+    assert int((single.get(nat.F_SHIP_ALIVE) == 0).sum()) > 0 and int(single.get(nat.F_N_LASERS).sum()) > 0
+    for b in (single, roll, rep):
+        assert b.overflow_count() == 0      # the oracle's laser list has no capacity
+        b.close()
 
 
 def test_full_size_properties():
