@@ -6,9 +6,7 @@
 #include "ofx_trunk.h"
 #include "ofx_diag.h"
 #include "ofx_lowp.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "ofx_trunk_tile.h"
 
 // ---- generic direct 3x3 convolution ------------------------------------------------
 // MODE: 0 planar f32 input, 1 two 1-bit maps
@@ -109,17 +107,6 @@ __global__ __launch_bounds__(((TH / 2) * (TW / 2) + 63) / 64 * 64) void k_conv(C
   }
 }
 
-// max without the canonicalising v_max(x, x) the compiler puts in front of fmaxf() in IEEE mode (x is an MFMA
-// result here, never a signalling NaN): med3(x, floor, +inf).  NOT inline assembly: the compiler's hazard recogniser
-// does not look inside an asm statement, so an asm v_max placed right behind the MFMA that produces x reads the
-// register before the matrix pipe has written it (seen as wrong cells under one scheduling variant).
-// The +inf comes out of an opaque scalar move: with a literal the optimiser folds med3 back into the canonicalising max.
-__device__ __forceinline__ float max_raw(float x, float floor) {
-  float pinf;
-  asm("s_mov_b32 %0, 0x7f800000" : "=s"(pinf));
-  return __builtin_amdgcn_fmed3f(x, floor, pinf);
-}
-
 // ---- trunk convolution on the matrix cores ---------------------------------------------------------------------
 // conv3x3 (zero padding) + folded BN + ReLU + 2x2 max-pool as a GEMM whose N dimension is 8 output channels x 2
 // adjacent output rows:  D[pixel x][(co, r)] = sum_k A[x][k] B[k][(co, r)],  k = (input row 0..3, dx, ci),
@@ -129,8 +116,13 @@ __device__ __forceinline__ float max_raw(float x, float floor) {
 // A[x][k] is gathered from an LDS copy of the input tile (one ds_read_b32 per lane per MFMA, immediate offsets);
 // the row pair of a column group shares one accumulator quad: lane (n = (co, r), kq) holds pixels 4 kq .. 4 kq + 3,
 // so the x-pool is in-lane and the y-pool is one DPP quad swap.
-// bf16 operand helpers of the opt-in OFX_OPT_POLICY_BF16 forms (k_convm, ts_gemm_phase_bf16)
-// the lane's six B operands from wbm [24][64] (value for MFMA j of the fp32 form, lane l: k = l >> 4 -> ci = (l >> 4) + 4 (j & 1), tap j >> 1)
+// The M-tile itself - taps, matrix sequence, pool - is stated in ofx_trunk_tile.h for every kernel below.
+// OFX_OPT_POLICY_BF16 (opt-in): the same banded GEMM on v_mfma_f32_16x16x16_bf16 / _f16 - K = 96 as 6 MFMAs of K = 16
+// instead of 24 of K = 4.  MFMA J, lane (pixel n16, k-quarter kq), element i: k <-> (tap = 2 J + (kq >> 1), ci = 4 (kq & 1) + i):
+// the A operand is the four channel planes 4 (kq & 1) .. + 3 at the tap's (row, dx) of the fp32 LDS tile, rounded to
+// 16 bits on the way in; the B operand is packed once from the same PrepLayout::wbm the fp32 kernel uses: the lane's six
+// from wbm [24][64] (value for MFMA j of the fp32 form, lane l: k = l >> 4 -> ci = (l >> 4) + 4 (j & 1), tap j >> 1).
+// fp32 accumulation, same epilogue.
 template <int LP>
 __device__ __forceinline__ void ts_bw_lp(const float *wbm, int n16, int kq, lp_x4 (&bwb)[6]) {
 #pragma unroll
@@ -140,22 +132,22 @@ __device__ __forceinline__ void ts_bw_lp(const float *wbm, int n16, int kq, lp_x
     bwb[J] = lp_pk4<LP>(q[0], q[16], q[32], q[48]);
   }
 }
-// MODE 0: planar f32 input [img][CIN][H][W] (the only mode left; conv1 reads the bit maps through k_conv1_lut).  Output: planar [img][8][H/2][W/2] or
+// Planar f32 input [img][8][H][W] (conv1 reads the bit maps through k_conv1_lut).  Output: planar [img][8][H/2][W/2] or
 // (OUT_HWC) [img][H/2][W/2][8].  TH rows x 16 NG columns per workgroup, TH even, H % TH == 0; W is masked.
 // A workgroup walks TPW consecutive tiles of one image: the weights are fetched once, the global loads of tile i+1 are
 // in flight (in registers) while tile i computes, and the grid stays small (the dispatcher needs ~5 ns per workgroup:
 // one workgroup per tile cost 1.6 ms of launch floor for conv2 alone).
-template <int CIN, int TH, int NG, int MODE, bool OUT_HWC, int TPW, int LP = 0>
+template <int TH, int NG, bool OUT_HWC, int TPW, int LP = 0>
 __global__ __launch_bounds__(256) void k_convm(ConvParams p) {
   constexpr bool BF16 = LP != 0;
-  static_assert(!BF16 || CIN == 8, "the bf16 form packs the four channels of a k-quarter");
+  constexpr int CIN = 8;
   constexpr int TW = 16 * NG, LS = TW + 8;  // LDS row: image column tx0 + c sits at index c + 4 (16-byte aligned interior),
                                             // the left / right halo columns at 3 and TW + 4
   constexpr int PLS = ((TH + 2) * LS + 63) / 64 * 64 + 16;  // plane stride = 16 mod 64: the 4 k-quarters hit different banks
   constexpr int NK = 3 * CIN;                                // MFMAs per M-tile (K = 12 CIN)
   constexpr int JOBS = NG * (TH / 2);
   constexpr int ROWS = CIN * (TH + 2);
-  constexpr bool VEC = MODE == 0 && !OUT_HWC;                // rows of W floats are 16-byte aligned (W % 4 == 0)
+  constexpr bool VEC = !OUT_HWC;                             // rows of W floats are 16-byte aligned (W % 4 == 0)
   __shared__ __align__(16) float tile[CIN * PLS];
   const unsigned bid = blockIdx.x;
   // XCD-aware order: workgroups go round-robin over the 8 XCDs (each with its own L2), so workgroup b works on image
@@ -170,29 +162,19 @@ __global__ __launch_bounds__(256) void k_convm(ConvParams p) {
   const int H = p.H, W = p.W;
   const int n16 = lane & 15, kq = lane >> 4, co = n16 >> 1, r = n16 & 1;
 
-  // B operand: the lane's column (co, r) of the banded weight matrix, rows k = 4 j + kq
-  float bw[NK];
-  int aoff[NK];  // LDS offset of A[.][4 j + kq] relative to the M-tile origin (compile-time + kq * PLS when CIN == 8)
-#pragma unroll
-  for (int j = 0; j < NK; j++) {
-    const int k = 4 * j + kq, rd = k / CIN, ci = k - rd * CIN, row = rd / 3, dx = rd - row * 3, tr = row - r;
-    if constexpr (CIN == 8) bw[j] = p.wbm[j * 64 + lane];  // pre-arranged by k_policy_prepare: one coalesced load
-    else bw[j] = (tr >= 0 && tr < 3) ? p.w[((tr * 3 + dx) * CIN + ci) * 8 + co] : 0.f;
-    aoff[j] = ci * PLS + row * LS + dx;
-  }
-  const float bias = p.b[co];
-  const f32x4 binit = {bias, bias, bias, bias};
-  // OFX_OPT_POLICY_BF16: see ts_gemm_phase_bf16 - MFMA J, element i: tap 2 J + (kq >> 1), channel 4 (kq & 1) + i
+  // B operand: the lane's column (co, r) of the banded weight matrix, rows k = 4 j + kq (16-bit: ts_bw_lp)
+  float bw[BF16 ? 1 : NK];
   lp_x4 bwb[6];
   int toff[6];
   if constexpr (BF16) {
     ts_bw_lp<LP ? LP : 1>(p.wbm, n16, kq, bwb);
+    mt_toff<LS, PLS>(kq, toff);
+  } else {
 #pragma unroll
-    for (int J = 0; J < 6; J++) {
-      const int tap = 2 * J + (kq >> 1);
-      toff[J] = (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-    }
+    for (int j = 0; j < NK; j++) bw[j] = p.wbm[j * 64 + lane];  // pre-arranged by k_policy_prepare: one coalesced load
   }
+  const float bias = p.b[co];
+  const f32x4 binit = {bias, bias, bias, bias};
   const int H2 = H >> 1, W2 = W >> 1;
 
   // ---- staging, split into fetch (global -> registers) and commit (registers -> LDS) ----
@@ -259,15 +241,7 @@ __global__ __launch_bounds__(256) void k_convm(ConvParams p) {
     }
   };
 
-  // A[.][4 j + kq]: with 8 input channels the (row, dx) of step j is a compile-time constant and the channel is
-  // 4 (j & 1) + kq, so every LDS read is base + immediate; with 2 channels the per-lane offsets live in registers
-  const float *abase = &tile[(CIN == 8 ? kq * PLS : 0) + n16 + 3];
-  auto aof = [&](int j) -> int {
-    if (CIN == 8) return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3);
-    return aoff[j];
-  };
-
-  auto lda = [&](const float *a, int j) -> float { return a[aof(j)]; };
+  const float *abase = &tile[kq * PLS + n16 + 3];  // the lane's A row of the M-tile at the tile's origin (taps: mt_aof)
   if constexpr (!VEC) {  // left halo column (image column -1): never written by the staging above
     for (int e = tid; e < CIN * (TH + 2); e += 256) tile[(e / (TH + 2)) * PLS + (e % (TH + 2)) * LS + 3] = 0.f;
   }
@@ -280,16 +254,12 @@ __global__ __launch_bounds__(256) void k_convm(ConvParams p) {
     __syncthreads();
     if (i + 1 < TPW) fetch(t + 1);
 
-    // epilogue of an M-tile: x-pool + ReLU (two v_med3), y-pool = max with the DPP quad swap [1,0,3,2] (rows r = 0 / 1
-    // sit in lanes n, n ^ 1), one 8-byte store from the r = 0 lanes
+    // epilogue of an M-tile: pool + ReLU (mt_pool), one 8-byte store from the r = 0 lanes
     float *const obase = OUT_HWC ? p.out + (((size_t)img * H2 + (ty0 >> 1)) * W2 + (tx0 >> 1) + 2 * kq) * 8 + co
                                  : p.out + (((size_t)img * 8 + co) * H2 + (ty0 >> 1)) * W2 + (tx0 >> 1) + 2 * kq;
     auto finish = [&](const f32x4 d, int g, int tt) {
-      float q0, q1;
-      q0 = max_raw(max_raw(d[0], 0.f), d[1]);  // compiler-visible reads of the MFMA result (see max_raw)
-      q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-      q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-      q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
+      const f32x2 q = mt_pool(d);
+      const float q0 = q[0], q1 = q[1];
       const int px = ((tx0 + 16 * g) >> 1) + 2 * kq;
       if (r == 0 && px < W2) {
         if (OUT_HWC) {
@@ -311,36 +281,14 @@ __global__ __launch_bounds__(256) void k_convm(ConvParams p) {
         const int g1 = job1 % NG, t1 = job1 / NG;
         const float *a1 = abase + (2 * t1) * LS + 16 * g1;
         f32x4 d0 = binit, d1 = binit;
-        if constexpr (BF16) {
 #pragma unroll
-          for (int J = 0; J < 6; J++) {
-            const float *q0 = a0 + toff[J], *q1 = a1 + toff[J];
-            const lp_x4 A0 = lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]);
-            const lp_x4 A1 = lp_pk4<LP ? LP : 1>(q1[0], q1[PLS], q1[2 * PLS], q1[3 * PLS]);
-            d0 = lp_mfma16<LP ? LP : 1>(A0, bwb[J], d0);
-            d1 = lp_mfma16<LP ? LP : 1>(A1, bwb[J], d1);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < NK; j++) {
-            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(lda(a0, j), bw[j], d0, 0, 0, 0);
-            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(lda(a1, j), bw[j], d1, 0, 0, 0);
-          }
-        }
+        for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, MtAcc{a0, d0}, MtAcc{a1, d1});
         finish(d0, g0, t0);
         finish(d1, g1, t1);
       } else {
         f32x4 d0 = binit;
-        if constexpr (BF16) {
 #pragma unroll
-          for (int J = 0; J < 6; J++) {
-            const float *q0 = a0 + toff[J];
-            d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(lda(a0, j), bw[j], d0, 0, 0, 0);
-        }
+        for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, MtAcc{a0, d0});
         finish(d0, g0, t0);
       }
     }
@@ -348,7 +296,7 @@ __global__ __launch_bounds__(256) void k_convm(ConvParams p) {
   }
 }
 
-template <int CIN, int TH, int NG, int MODE, bool OUT_HWC, int TPW, int LP = 0>
+template <int TH, int NG, bool OUT_HWC, int TPW, int LP = 0>
 static int launch_convm(ofx_handle *h, ConvParams p, int images, int H) {
   p.H = H; p.W = H;
   p.tiles_x = (H + 16 * NG - 1) / (16 * NG);
@@ -356,7 +304,7 @@ static int launch_convm(ofx_handle *h, ConvParams p, int images, int H) {
   if (p.tiles % TPW) { ofx_set_error("launch_convm: %d tiles per image not divisible by %d", p.tiles, TPW); return OFX_ERR_INVALID; }
   if (OUT_HWC && (H % 2 || H > 16 * NG)) { ofx_set_error("launch_convm: the 8-byte staging takes even rows of one tile width"); return OFX_ERR_INVALID; }
   p.images = images;
-  hipLaunchKernelGGL((k_convm<CIN, TH, NG, MODE, OUT_HWC, TPW, LP>), dim3((unsigned)((images + 7) / 8 * 8 * (p.tiles / TPW))), dim3(256), 0,
+  hipLaunchKernelGGL((k_convm<TH, NG, OUT_HWC, TPW, LP>), dim3((unsigned)((images + 7) / 8 * 8 * (p.tiles / TPW))), dim3(256), 0,
                      h->stream, p);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
@@ -371,6 +319,12 @@ static int launch_convm(ofx_handle *h, ConvParams p, int images, int H) {
 // pixel against 6 MFMAs + epilogue per 16 in the GEMM form (3.4 ms): the kernel is bound by its 5.2 GB of output.
 // Input rows are re-aligned while staging: bit x + 1 of LDS row r <-> image column x of row ty0 - 1 + r (bit 0 and
 // the bits past column W-1 are the zero padding).
+// staged bits x0 .. x0 + NB - 1 of a staged row
+template <int NB>
+__device__ __forceinline__ unsigned c1_window(const unsigned *row, int x0) {
+  const unsigned *rw = row + (x0 >> 5);
+  return __funnelshift_r(rw[0], rw[1], (unsigned)(x0 & 31)) & ((1u << NB) - 1u);
+}
 template <int TH>
 __global__ __launch_bounds__(256) void k_conv1_lut(ConvParams p, const float *lut) {
   constexpr int W = PS, H = PS, WR = 14;                       // words per staged row (402 bits)
@@ -414,10 +368,7 @@ __global__ __launch_bounds__(256) void k_conv1_lut(ConvParams p, const float *lu
 #pragma unroll
     for (int ci = 0; ci < 2; ci++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const unsigned *rw = &rows[ci][2 * py + r][x0 >> 5];
-        f[ci][r] = __funnelshift_r(rw[0], rw[1], (unsigned)(x0 & 31)) & 1023u;
-      }
+      for (int r = 0; r < 4; r++) f[ci][r] = c1_window<10>(rows[ci][2 * py + r], x0);
     f32x4 m4[8];                                                  // [channel] = the 4 pixels
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -446,43 +397,41 @@ __global__ __launch_bounds__(256) void k_conv1_lut(ConvParams p, const float *lu
   }
 }
 
-// ---- streaming trunk kernel (k_trunk12): the GEMM phase ---------------------------------------------
+// ---- streaming trunk kernels (k_trunk12, k_conv3_stream): the GEMM phase ---------------------------------------------
 // k_convm's banded GEMM over an LDS tile of RP row pairs x WD columns (planes PLS apart, rows LS apart; abase = the
-// lane's k-quarter plane at column -1 of tile row 0).  M-tiles of 16 pixels are enumerated FLAT over (row pair, column):
-// RP * WD / 16 of them, no masked columns; wave w takes tiles w, w + 16, w + 32, w + 48 as four interleaved accumulator
-// chains (a wave with three: a pair and a single).  Epilogue as k_convm: 2x2 pool + ReLU, one 8-byte store per lane to
+// lane's k-quarter plane at column -1 of tile row 0), built from ofx_trunk_tile.h: the flat M-tiles, their A rows and their
+// store (MtFlat), the matrix sequence (mt_step), the epilogue (mt_pool).  What the drivers below add is the schedule:
+//   fp32, dense:   wave w takes tiles w, w + 16, w + 32, w + 48 as four interleaved accumulator chains (a wave with
+//                  three: a pair and a single);
+//   16-bit, dense: pairs, the last tile twice when it is alone;
+//   sparse:        the tiles that have to run, dealt to the waves by one ballot, as pairs and a single.
 // orow = the lane's channel plane at the step's first pooled row (planar [.][WD/2]).
-template <int WD, int RP, int LS, int PLS>
-__device__ __forceinline__ void ts_gemm_phase(const float *abase, const float (&bw)[24], const f32x4 binit, int wv, int n16,
-                                              int kq, int r, float *orow) {
-  constexpr int NK = 24, NPX = RP * WD, NT = (NPX + 15) / 16;
-  static_assert(WD % 4 == 0 && NT <= 64, "four M-tiles per wave at most");
-  auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3); };
-  auto finish = [&](const f32x4 d, int T) {
-    float q0, q1;
-    q0 = max_raw(max_raw(d[0], 0.f), d[1]);  // compiler-visible reads of the MFMA result (see max_raw)
-    q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-    q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-    q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-    const int P = 16 * T + 4 * kq;                                 // the lane's four pixels P .. P + 3 of one row pair
-    const int rp = P / WD, x = P - rp * WD;
-    if (r == 0 && P < NPX) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(q0, q1);
-  };
-  auto a_of_tile = [&](int T) -> const float * {                   // the lane's A row: pixel 16 T + n16 (clamped past the end)
-    const int P = min(16 * T + n16, NPX - 1);
-    const int rp = P / WD, x = P - rp * WD;
-    return abase + 2 * rp * LS + x;
-  };
-  if (wv + 48 < NT) {  // all four M-tiles of the wave at once (k_trunk12: 3.0 -> 2.84 ms against two pairs)
+template <int WD, int RP, int LS, int PLS, int LP>
+__device__ __forceinline__ void ts_gemm_phase(const float *abase, const float (&bw)[LP ? 1 : 24], const lp_x4 (&bwb)[6],
+                                              const f32x4 binit, int wv, int n16, int kq, int r, float *orow) {
+  using F = MtFlat<WD, RP, LS>;
+  constexpr int NT = F::NT;
+  int toff[6];
+  if constexpr (LP != 0) mt_toff<LS, PLS>(kq, toff);  // the 16-bit taps; fp32 reads none
+  auto finish = [&](const f32x4 d, int T) { F::finish(d, orow, T, kq, r); };
+  auto a_of_tile = [&](int T) { return F::a_of_tile(abase, T, n16); };
+  if constexpr (LP != 0) {
+#pragma unroll 1
+    for (int T = wv; T < NT; T += 32) {  // two M-tiles at a time: two accumulator chains (the last tile twice when it is alone)
+      const int T1 = T + 16;
+      const bool two = T1 < NT;          // wave-uniform
+      const float *a0 = a_of_tile(T), *a1 = a_of_tile(two ? T1 : T);
+      f32x4 d0 = binit, d1 = binit;
+#pragma unroll
+      for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, MtAcc{a0, d0}, MtAcc{a1, d1});
+      finish(d0, T);
+      if (two) finish(d1, T1);
+    }
+  } else if (wv + 48 < NT) {  // all four M-tiles of the wave at once (k_trunk12: 3.0 -> 2.84 ms against two pairs)
     const float *a0 = a_of_tile(wv), *a1 = a_of_tile(wv + 16), *a2 = a_of_tile(wv + 32), *a3 = a_of_tile(wv + 48);
     f32x4 d0 = binit, d1 = binit, d2 = binit, d3 = binit;
 #pragma unroll
-    for (int j = 0; j < NK; j++) {
-      d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[j], d0, 0, 0, 0);
-      d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[aof(j)], bw[j], d1, 0, 0, 0);
-      d2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[aof(j)], bw[j], d2, 0, 0, 0);
-      d3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[aof(j)], bw[j], d3, 0, 0, 0);
-    }
+    for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, MtAcc{a0, d0}, MtAcc{a1, d1}, MtAcc{a2, d2}, MtAcc{a3, d3});
     finish(d0, wv); finish(d1, wv + 16); finish(d2, wv + 32); finish(d3, wv + 48);
   } else {
 #pragma unroll 1
@@ -493,16 +442,13 @@ __device__ __forceinline__ void ts_gemm_phase(const float *abase, const float (&
         const float *a1 = a_of_tile(T1);
         f32x4 d0 = binit, d1 = binit;
 #pragma unroll
-        for (int j = 0; j < NK; j++) {
-          d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[j], d0, 0, 0, 0);
-          d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[aof(j)], bw[j], d1, 0, 0, 0);
-        }
+        for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, MtAcc{a0, d0}, MtAcc{a1, d1});
         finish(d0, T);
         finish(d1, T1);
       } else {
         f32x4 d0 = binit;
 #pragma unroll
-        for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[j], d0, 0, 0, 0);
+        for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, MtAcc{a0, d0});
         finish(d0, T);
       }
     }
@@ -516,7 +462,7 @@ __device__ __forceinline__ void ts_gemm_phase(const float *abase, const float (&
 // <-> column x of that row is NOT known to be constant (phase A).  An M-tile that crosses from one row pair into the
 // next contains columns 199 and 0, i.e. touches the padding: only tiles inside one row pair with 1 <= x, x + 15 <= 198
 // can be constant.  top / bottom: tile row 0 / the last tile row is a padding row of the image.
-// LP != 0: the same with the 16-bit operand sequence of ts_gemm_phase_bf16 (K2 then comes from THAT sequence).
+// LP != 0: the same with the 16-bit operand sequence (K2 then comes from THAT sequence: mt_const).
 template <int WD, int RP, int LS, int PLS, int LP>
 __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const float (&bw)[LP ? 1 : 24], const lp_x4 (&bwb)[6],
                                                      const f32x4 binit, int wv, int lane,
@@ -529,61 +475,17 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
 #else
 #define TSG_STAMP(i) do { } while (0)
 #endif
-  constexpr int NK = 24, NPX = RP * WD, NT = (NPX + 15) / 16;
-  static_assert(WD % 4 == 0 && NT <= 64, "four M-tiles per wave at most");
-  auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3); };
-  int toff[6];  // LP: abase carries the fp32 form's + kq * PLS: taken out again (ts_gemm_phase_bf16)
+  using F = MtFlat<WD, RP, LS>;
+  constexpr int NPX = F::NPX, NT = F::NT;
+  int toff[6];
+  if constexpr (LP != 0) mt_toff<LS, PLS>(kq, toff);  // the 16-bit taps; fp32 reads none
+  // the M-tile's matrix sequence on one or two accumulator chains, and its epilogue
+  auto mm = [&](auto... c) {
 #pragma unroll
-  for (int J = 0; J < 6; J++) {
-    const int tap = 2 * J + (kq >> 1);
-    toff[J] = (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-  }
-  // the M-tile's matrix sequence: one or two accumulator chains
-  auto mm1 = [&](const float *a0, f32x4 &d0) {
-    if constexpr (LP != 0) {
-#pragma unroll
-      for (int J = 0; J < 6; J++) {
-        const float *q0 = a0 + toff[J];
-        d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[LP ? 0 : j], d0, 0, 0, 0);
-    }
+    for (int j = 0; j < MT_NJ<LP>; j++) mt_step<LP, LS, PLS>(j, bw, bwb, toff, c...);
   };
-  auto mm2 = [&](const float *a0, const float *a1, f32x4 &d0, f32x4 &d1) {
-    if constexpr (LP != 0) {
-#pragma unroll
-      for (int J = 0; J < 6; J++) {
-        const float *q0 = a0 + toff[J], *q1 = a1 + toff[J];
-        const lp_x4 A0 = lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]);
-        const lp_x4 A1 = lp_pk4<LP ? LP : 1>(q1[0], q1[PLS], q1[2 * PLS], q1[3 * PLS]);
-        d0 = lp_mfma16<LP ? LP : 1>(A0, bwb[J], d0);
-        d1 = lp_mfma16<LP ? LP : 1>(A1, bwb[J], d1);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < NK; j++) {
-        d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[LP ? 0 : j], d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[aof(j)], bw[LP ? 0 : j], d1, 0, 0, 0);
-      }
-    }
-  };
-  auto finish = [&](const f32x4 d, int T) {
-    float q0, q1;
-    q0 = max_raw(max_raw(d[0], 0.f), d[1]);
-    q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-    q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-    q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-    const int P = 16 * T + 4 * kq;
-    const int rp = P / WD, x = P - rp * WD;
-    if (r == 0 && P < NPX) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(q0, q1);
-  };
-  auto a_of_tile = [&](int T) -> const float * {
-    const int P = min(16 * T + n16, NPX - 1);
-    const int rp = P / WD, x = P - rp * WD;
-    return abase + 2 * rp * LS + x;
-  };
+  auto finish = [&](const f32x4 d, int T) { F::finish(d, orow, T, kq, r); };
+  auto a_of_tile = [&](int T) { return F::a_of_tile(abase, T, n16); };
   // Every wave classifies ALL the step's M-tiles by itself, lane T tile T: no list to build, no barrier.  Bit T of the
   // mask: tile T has to run.  (A first version let a wave test its own four tiles one after the other with eight lanes each
   // and appended to a shared list behind a barrier: 4 500 cycles per step for the classification alone, stamps.)
@@ -626,12 +528,11 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
     }
   }
   auto store_const = [&](int T) {                                          // the constant tile: the dense result, stored
-    const int P = 16 * T + 4 * kq, rp = P / WD, x = P - rp * WD;
-    if (r == 0) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(k2, k2);
+    F::template store<true>(orow, T, kq, r, k2, k2);
   };
   auto run1 = [&](int T0) {
     f32x4 d0 = binit;
-    mm1(a_of_tile(T0), d0);
+    mm(MtAcc{a_of_tile(T0), d0});
     finish(d0, T0);
   };
   // the wave's own four tiles: the constant ones are stored; then the RUN tiles are dealt out over all 16 waves - wave w
@@ -654,62 +555,12 @@ __device__ __forceinline__ void ts_gemm_phase_sparse(const float *abase, const f
       const int T1 = __builtin_ctzll(m);
       m &= m - 1;
       f32x4 d0 = binit, d1 = binit;
-      mm2(a_of_tile(T0), a_of_tile(T1), d0, d1);
+      mm(MtAcc{a_of_tile(T0), d0}, MtAcc{a_of_tile(T1), d1});
       finish(d0, T0);
       finish(d1, T1);
     } else run1(T0);
   }
   TSG_STAMP(2);
-}
-
-// OFX_OPT_POLICY_BF16 (opt-in): the same banded GEMM on v_mfma_f32_16x16x16_bf16 - K = 96 as 6 MFMAs of K = 16 instead
-// of 24 of K = 4.  MFMA J, lane (pixel n16, k-quarter kq), element i: k <-> (tap = 2 J + (kq >> 1), ci = 4 (kq & 1) + i):
-// the A operand is the four channel planes 4 (kq & 1) .. + 3 at the tap's (row, dx) of the fp32 LDS tile, rounded to
-// bf16 on the way in (one address per J: lane-constant tap offset, planes by immediate); the B operand is packed once
-// from the same PrepLayout::wbm the fp32 kernel uses.  fp32 accumulation, same epilogue.
-template <int WD, int RP, int LS, int PLS, int LP>
-__device__ __forceinline__ void ts_gemm_phase_bf16(const float *abase, const lp_x4 (&bwb)[6], const f32x4 binit, int wv, int n16,
-                                                   int kq, int r, float *orow) {
-  constexpr int NPX = RP * WD, NT = (NPX + 15) / 16;
-  static_assert(WD % 4 == 0 && NT <= 64, "four M-tiles per wave at most");
-  int toff[6];  // abase carries the fp32 form's + kq * PLS: taken out again
-#pragma unroll
-  for (int J = 0; J < 6; J++) {
-    const int tap = 2 * J + (kq >> 1);
-    toff[J] = (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-  }
-  auto finish = [&](const f32x4 d, int T) {
-    float q0, q1;
-    q0 = max_raw(max_raw(d[0], 0.f), d[1]);
-    q1 = max_raw(max_raw(d[2], 0.f), d[3]);
-    q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
-    q1 = max_raw(q1, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, true)));
-    const int P = 16 * T + 4 * kq;
-    const int rp = P / WD, x = P - rp * WD;
-    if (r == 0 && P < NPX) *reinterpret_cast<float2 *>(orow + rp * (WD / 2) + (x >> 1)) = make_float2(q0, q1);
-  };
-  auto a_of_tile = [&](int T) -> const float * {
-    const int P = min(16 * T + n16, NPX - 1);
-    const int rp = P / WD, x = P - rp * WD;
-    return abase + 2 * rp * LS + x;
-  };
-#pragma unroll 1
-  for (int T = wv; T < NT; T += 32) {  // two M-tiles at a time: two accumulator chains
-    const int T1 = T + 16;
-    const bool two = T1 < NT;          // wave-uniform
-    const float *a0 = a_of_tile(T), *a1 = a_of_tile(two ? T1 : T);
-    f32x4 d0 = binit, d1 = binit;
-#pragma unroll
-    for (int J = 0; J < 6; J++) {
-      const float *q0 = a0 + toff[J], *q1 = a1 + toff[J];
-      const lp_x4 A0 = lp_pk4<LP>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]);
-      const lp_x4 A1 = lp_pk4<LP>(q1[0], q1[PLS], q1[2 * PLS], q1[3 * PLS]);
-      d0 = lp_mfma16<LP>(A0, bwb[J], d0);
-      d1 = lp_mfma16<LP>(A1, bwb[J], d1);
-    }
-    finish(d0, T);
-    if (two) finish(d1, T1);
-  }
 }
 
 // ---- conv1 -> conv2 fused: the 5.2 GB pooled conv1 activation never exists -----------------------------------------
@@ -759,9 +610,9 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
   // rows in flight and for the stores' acknowledgements (stamps: 3 400 of a step's 13 700 cycles in front of phase A's
   // barrier, 5 000 behind the last M-tile)
   __shared__ float wbs[(SPARSE && !BF16) ? 24 * 64 : 1];
-  unsigned n_exec = 0, n_all = 0, t_exec = 0, t_all = 0; // SPARSE: the wave's counts (M-tiles run / all, table passes run / all)
+  [[maybe_unused]] unsigned n_exec = 0, n_all = 0, t_exec = 0, t_all = 0; // SPARSE: the wave's counts (M-tiles run / all, table passes run / all; not read out by the stamps build)
 #if OFX_TRUNK_STAMPS
-  unsigned long long st_a = 0, st_b = 0, st_last = __builtin_amdgcn_s_memtime(), st_begin = st_last, st_g[3] = {0, 0, 0};
+  unsigned long long st_a = 0, st_b = 0, st_last = __builtin_amdgcn_s_memtime(), st_g[3] = {0, 0, 0};
 #define T12_STAMP(acc) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc += t_ - st_last; st_last = t_; } while (0)
 #else
 #define T12_STAMP(acc) do { } while (0)
@@ -828,22 +679,8 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
     for (int e = tid; e < 8 * PLS; e += F12_THREADS) tile[e] = k1s[min(e / PLS, 7)];
     __syncthreads();
     if (wv == 0) {
-      const float *a0 = abase + 2 * LS + 16 + n16;                 // any interior M-tile: row pair 1, columns 16 .. 31
-      f32x4 d0 = binit;
-      if constexpr (BF16) {
-#pragma unroll
-        for (int J = 0; J < 6; J++) {
-          const int tap = 2 * J + (kq >> 1);
-          const float *q0 = a0 + (4 * (kq & 1) - kq) * PLS + (tap / 3) * LS + tap % 3;
-          d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-        }
-      } else {
-        auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * LS + ((j >> 1) % 3); };
-#pragma unroll
-        for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], wbs[(BF16 ? 0 : j) * 64 + lane], d0, 0, 0, 0);
-      }
-      float q0 = max_raw(max_raw(d0[0], 0.f), d0[1]);
-      q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
+      // any interior M-tile: row pair 1, columns 16 .. 31; fp32: the lane's B operands straight out of wbs [24][64]
+      const float q0 = mt_const<LP, LS, PLS, 64>(abase + 2 * LS + 16 + n16, wbs + lane, bwb, kq, binit);
       if (r == 0 && kq == 0) {
         k2s[co] = q0;
         if (blockIdx.x == 0 && p.k2) p.k2[co] = q0;               // for k_conv3_stream<., true>: every workgroup has the same bits
@@ -895,10 +732,7 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
 #pragma unroll
       for (int ci = 0; ci < 2; ci++)
 #pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-          const unsigned *rw = &rows[buf][ci][2 * py + rr][x0 >> 5];
-          f[ci][rr] = __funnelshift_r(rw[0], rw[1], (unsigned)(x0 & 31)) & 63u;
-        }
+        for (int rr = 0; rr < 4; rr++) f[ci][rr] = c1_window<6>(rows[buf][ci][2 * py + rr], x0);
       float m2[8][2];
       bool dense_pass = true;
       if constexpr (SPARSE) {
@@ -982,12 +816,9 @@ __global__ __launch_bounds__(F12_THREADS) void k_trunk12(ConvParams p, const flo
                                                                   );
       // the other buffer's marks are last step's: cleared for the next step (its first two rows are copied in there)
       for (int e = tid; e < F12_ROWS * 8; e += F12_THREADS) (&nz[buf ^ 1][0][0])[e] = 0u;
-    } else if constexpr (BF16)
-      ts_gemm_phase_bf16<200, F12_TH / 2, F12_LS, F12_PLS, LP ? LP : 1>(abase, bwb, binit, wv, n16, kq, r,
-                                                            p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
-    else
-      ts_gemm_phase<200, F12_TH / 2, F12_LS, F12_PLS>(abase, bw, binit, wv, n16, kq, r,
-                                                       p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
+    } else
+      ts_gemm_phase<200, F12_TH / 2, F12_LS, F12_PLS, LP>(abase, bw, bwb, binit, wv, n16, kq, r,
+                                                           p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
     if constexpr (!SPARSE) { if (more) bits_commit(buf ^ 1, na, nb, nextw); }  // the other buffer: phase A of this step is behind every wave
     __syncthreads();
     // the step's p2 marks: 5 rows x 4 words, one plain store (the next GEMM phase, which rewrites mk2, is a barrier away)
@@ -1087,22 +918,7 @@ __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, cons
     for (int e = tid; e < 8 * 4 * C3_LS; e += F12_THREADS) tiles[1][(e / (4 * C3_LS)) * PLS + e % (4 * C3_LS)] = p.k2[e / (4 * C3_LS)];
     __syncthreads();
     if (wv == 0) {
-      const float *a0 = &tiles[1][kq * PLS + 3] + 16 + n16;
-      f32x4 d0 = binit;
-      if constexpr (BF16) {
-#pragma unroll
-        for (int J = 0; J < 6; J++) {
-          const int tap = 2 * J + (kq >> 1);
-          const float *q0 = a0 + (4 * (kq & 1) - kq) * PLS + (tap / 3) * C3_LS + tap % 3;
-          d0 = lp_mfma16<LP ? LP : 1>(lp_pk4<LP ? LP : 1>(q0[0], q0[PLS], q0[2 * PLS], q0[3 * PLS]), bwb[J], d0);
-        }
-      } else {
-        auto aof = [&](int j) -> int { return (4 * (j & 1)) * PLS + ((j >> 1) / 3) * C3_LS + ((j >> 1) % 3); };
-#pragma unroll
-        for (int j = 0; j < NK; j++) d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[aof(j)], bw[BF16 ? 0 : j], d0, 0, 0, 0);
-      }
-      float q0 = max_raw(max_raw(d0[0], 0.f), d0[1]);
-      q0 = max_raw(q0, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, true)));
+      const float q0 = mt_const<LP, C3_LS, C3_PLS>(&tiles[1][kq * PLS + 3] + 16 + n16, bw, bwb, kq, binit);
       if (r == 0 && kq == 0) k3s[co] = q0;
     }
   }
@@ -1131,12 +947,9 @@ __global__ __launch_bounds__(F12_THREADS) void k_conv3_stream(ConvParams p, cons
                                                             , st_g
 #endif
                                                             );
-    } else if constexpr (BF16)
-      ts_gemm_phase_bf16<W, C3_TH / 2, C3_LS, C3_PLS, LP ? LP : 1>(&tiles[buf][kq * PLS + 3], bwb, binit, wv, n16, kq, r,
-                                                      p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
-    else
-      ts_gemm_phase<W, C3_TH / 2, C3_LS, C3_PLS>(&tiles[buf][kq * PLS + 3], bw, binit, wv, n16, kq, r,
-                                                 p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
+    } else
+      ts_gemm_phase<W, C3_TH / 2, C3_LS, C3_PLS, LP>(&tiles[buf][kq * PLS + 3], bw, bwb, binit, wv, n16, kq, r,
+                                                     p.out + (((size_t)img * 8 + co) * H2 + (R0 >> 1)) * H2);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's LDS-direct loads have landed (see above)
     __syncthreads();
     buf ^= 1;
@@ -1206,7 +1019,7 @@ static int trunk_streaming(ofx_handle *h, ConvParams cp, const TrunkParams &p) {
   else hipLaunchKernelGGL((k_conv3_stream<LP, false>), grid, dim3(F12_THREADS), 0, h->stream, cp, p.zero16);
   OFX_HIP(hipGetLastError());
   trunk_layer(cp, p, 3, p.p3, p.p4);
-  return launch_convm<8, 10, 4, 0, true, 1, LP>(h, cp, p.images, 50);
+  return launch_convm<10, 4, true, 1, LP>(h, cp, p.images, 50);
 }
 
 int ofx_launch_trunk(ofx_handle *h, const TrunkParams &p) {
@@ -1222,36 +1035,37 @@ int ofx_launch_trunk(ofx_handle *h, const TrunkParams &p) {
   trunk_layer(cp, p, 0, nullptr, p.p1);
   if ((rc = plain ? launch_conv<2, 8, 10, 100, 1, true, false>(h, cp, N, 400) : launch_conv1_lut(h, cp, p.lut1))) return rc;
   trunk_layer(cp, p, 1, p.p1, p.p2);
-  if ((rc = plain ? launch_conv<8, 8, 10, 100, 0, true, false>(h, cp, N, 200) : launch_convm<8, 2, 13, 0, false, 1>(h, cp, N, 200))) return rc;
+  if ((rc = plain ? launch_conv<8, 8, 10, 100, 0, true, false>(h, cp, N, 200) : launch_convm<2, 13, false, 1>(h, cp, N, 200))) return rc;
   trunk_layer(cp, p, 2, p.p2, p.p3);
-  if ((rc = plain ? launch_conv<8, 8, 10, 100, 0, true, false>(h, cp, N, 100) : launch_convm<8, 4, 7, 0, false, 1>(h, cp, N, 100))) return rc;
+  if ((rc = plain ? launch_conv<8, 8, 10, 100, 0, true, false>(h, cp, N, 100) : launch_convm<4, 7, false, 1>(h, cp, N, 100))) return rc;
   trunk_layer(cp, p, 3, p.p3, p.p4);  // writes (h,w,c) = Flatten order
-  return plain ? launch_conv<8, 8, 10, 50, 0, true, true>(h, cp, N, 50) : launch_convm<8, 10, 4, 0, true, 1>(h, cp, N, 50);
+  return plain ? launch_conv<8, 8, 10, 50, 0, true, true>(h, cp, N, 50) : launch_convm<10, 4, true, 1>(h, cp, N, 50);
+}
+
+// the sparse form's counters (ConvParams::stat): slots first .. first + count - 1 read into dst and reset; dst stays as it
+// is when the handle has none
+static int trunk_stat_take(ofx_handle *h, int first, int count, void *dst) {
+  if (!h->trunk_stat) return OFX_OK;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipMemcpyAsync(dst, h->trunk_stat + first, count * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  OFX_HIP(hipMemsetAsync(h->trunk_stat + first, 0, count * sizeof(unsigned long long), h->stream));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  return OFX_OK;
 }
 
 extern "C" int ofx_policy_trunk_stats(ofx_handle *h, int64_t *counts_host) {
   if (!h || !counts_host) { ofx_set_error("ofx_policy_trunk_stats: null argument"); return OFX_ERR_INVALID; }
   for (int i = 0; i < 4; i++) counts_host[i] = 0;
-  if (!h->trunk_stat) return OFX_OK;
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipMemcpyAsync(counts_host, h->trunk_stat, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-  OFX_HIP(hipMemsetAsync(h->trunk_stat, 0, 4 * sizeof(unsigned long long), h->stream));
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  return OFX_OK;
+  return trunk_stat_take(h, 0, 4, counts_host);
 }
 
 // conv3's M-tiles (k_conv3_stream<., true>): slots 4 and 5 of the same counters, read and reset on their own
 extern "C" int ofx_policy_trunk_stats3(ofx_handle *h, int64_t *run_host, int64_t *total_host) {
   if (!h || !run_host || !total_host) { ofx_set_error("ofx_policy_trunk_stats3: null argument"); return OFX_ERR_INVALID; }
-  *run_host = *total_host = 0;
-  if (!h->trunk_stat) return OFX_OK;
-  unsigned long long v[2] = {0, 0};
-  OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipMemcpyAsync(v, h->trunk_stat + 4, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-  OFX_HIP(hipMemsetAsync(h->trunk_stat + 4, 0, sizeof(v), h->stream));
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  *run_host = (int64_t)v[0]; *total_host = (int64_t)v[1];
-  return OFX_OK;
+  int64_t v[2] = {0, 0};
+  const int rc = trunk_stat_take(h, 4, 2, v);
+  *run_host = v[0]; *total_host = v[1];
+  return rc;
 }
 
 // the trunk's output of the last forward of n_images images x m ships on this handle: p4 [n_images][5000] in (h, w, c) order,

@@ -127,7 +127,7 @@ def test_small_case_against_the_rounded_graph(lowp, legacy, fuse):
 @pytest.mark.parametrize("lowp", [1, 2])
 def test_border_case_against_the_rounded_graph(lowp):
     """Ships on x, y in {0, 1, 2, 7, 8, 199, 200, 391, 392, 398, 399, 400}, then turrets firing for a few ticks: non-constant
-    operands in the halo columns, in the first and last row tiles of ts_gemm_phase_bf16 and on the strip edges of
+    operands in the halo columns, in the first and last row tiles of the 16-bit ts_gemm_phase and on the strip edges of
     tile_bf16."""
     ids, M, seed, ticks = CASES["border"]
     b = _rollout(len(ids), M, seed=seed, ticks=ticks)
