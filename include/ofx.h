@@ -397,6 +397,48 @@ int ofx_population_act(ofx_handle *h, const int32_t *genome_of, ofx_action *acti
  * (arena, ship) with genome_of == g, count[g] += 1; reset != 0 zeroes both first.  Integer atomics: exact in any order.
  * Does not synchronise.                                                                                              */
 int ofx_population_fitness(ofx_handle *h, const int32_t *genome_of, int64_t *sum, int32_t *count, int32_t reset);
+/* A learning step per genome: Neural_network.backprop (agents/neural_network.py:338-393) and the step of update_network
+ * (:241-300) / update_network_continuous (:319-334), for every genome on its own ships' observations, on the device.
+ * All pointers are DEVICE pointers.  genome_of: int32 [N][M] as in ofx_population_act; solution: float64 [N][M][4], the
+ * target output; learn_mask: uint8 [N][M] or NULL (= all ones); actions: [N][M] ofx_action or NULL; y: float64 [N][M][4]
+ * or NULL; err: float64 [N][M] or NULL.  Rasterises the handle's 1-bit maps as ofx_population_act does.
+ * SAMPLES.  A ship is a sample iff it is alive, 0 <= genome_of < P and its mask entry is nonzero.  The samples of genome
+ * g in ascending flat index a*M + i are j_1 < ... < j_n; two ships of one arena on the same genome are two samples.
+ * FORWARD OUTPUTS.  For every live assigned ship, sample or not, actions and y get what ofx_population_act would have
+ * written from the weights BEFORE this call, bit for bit (the same device code); dead, unassigned and out-of-range
+ * entries are not written.  One forward per lock-step is enough: this call stands where the acting call stood.
+ * GRADIENT.  Per sample, with the OLD weights of its genome and the forward's z_l, a_l (the same bits):
+ *   d = solution - a_L;  delta_L[o] = d[o] * (a_L[o] * (1 - a_L[o]))
+ *   l = L-1 .. 1:  delta_l[k] = (sum over o ascending of W_{l+1}[o][k] * delta_{l+1}[o]) * (a_l[k] * (1 - a_l[k]))
+ * every product and sum rounded on its own (no FMA).  The reference's sigmoid_prime(z) recomputes sigmoid(z): the same
+ * function of the same input, so a (1 - a) is the same number.  err[j] = d0^2 + d1^2 + d2^2 + d3^2, added in that
+ * order, for samples only.
+ * APPLY.  c = rate / (double)n; for j = j_1 .. j_n in that order
+ *   W_l[o][k] <- W_l[o][k] + (c * delta_{l,j}[o]) * a_{l-1,j}[k]        b_l[o] <- b_l[o] + c * delta_{l,j}[o]
+ * In the first layer a map input is 0 or 1: at a set cell the element becomes w + c * delta_1[o], at an unset cell it is
+ * NOT written (an update touches set cells x n1 doubles of a genome, not all of it); the 8 head inputs are ordinary
+ * doubles.  A genome with n = 0 keeps every bit.  rate == 0 skips the apply; the forward outputs and err are written.
+ * This is update_network's step on the average gradient scaled by `rate`: rate = 1 is update_network, n = 1 is
+ * update_network_continuous(obs, sol, rate).  ONE DIFFERENCE: the reference sums the per-sample terms, divides and adds
+ * the sum to the weight once; here each sample's term is added to the weight one after the other, which differs in the
+ * last bits only and lets the sparse first layer go without an accumulator the size of a genome.
+ * No floating-point atomics: the same state gives the same bits on every call.  Refused, each with a message and before
+ * anything is enqueued: no population (OFX_ERR_STATE); genome_of or solution NULL, rate not finite (OFX_ERR_INVALID).
+ * Two launches (every delta of a genome's samples comes from the old weights).  Does not synchronise.                */
+int ofx_population_learn(ofx_handle *h, const int32_t *genome_of, const double *solution, const uint8_t *learn_mask,
+                         double rate, ofx_action *actions, double *y, double *err);
+/* The teacher's action as a target, for every (arena, ship); teacher: DEVICE [N][M] ofx_action (what ofx_bot_actions
+ * wrote), solution: DEVICE float64 [N][M][4], mask: DEVICE uint8 [N][M].
+ *   solution = (shoot ? 1 : 0, thrust ? 1 : 0, clamp((px + 0.5) / W, 0, 1), clamp((py + 0.5) / H, 0, 1))
+ *   mask = teacher.valid != 0
+ * The inverse of ofx_population_act's decode: for 0 <= px < W the decode of the target gives px back.  OFX_ERR_INVALID
+ * for a NULL pointer.  Does not synchronise.                                                                          */
+int ofx_population_targets(ofx_handle *h, const ofx_action *teacher, double *solution, uint8_t *mask);
+/* The imitation log's reduction.  err: DEVICE float64 [N][M], acc: DEVICE float64 [2].  acc[0] += the entries of err that
+ * are >= 0, acc[1] += their number; every entry of err is then set to -1 ("no sample": ofx_population_learn writes the
+ * samples' entries only, and an err is never negative).  One workgroup, a fixed order of additions: the same bits every
+ * call.  OFX_ERR_INVALID for a NULL pointer.  Does not synchronise.                                                   */
+int ofx_population_err_reduce(ofx_handle *h, double *err, double *acc);
 
 /* ---- bi-head policy forward --------------------------------------------
  * Trainer.pointer_model graph + inference glue

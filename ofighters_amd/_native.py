@@ -123,6 +123,9 @@ SIGNATURES = {
     "ofx_population_breed": (_i, [_vp, _vp, C.c_double, C.c_double, _u64, _u32]),
     "ofx_population_act": (_i, [_vp, _vp, _vp, _vp]),
     "ofx_population_fitness": (_i, [_vp, _vp, _vp, _vp, C.c_int32]),
+    "ofx_population_learn": (_i, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "ofx_population_targets": (_i, [_vp, _vp, _vp, _vp]),
+    "ofx_population_err_reduce": (_i, [_vp, _vp, _vp]),
     "ofx_policy_layout": (_i, [_vp, C.POINTER(OfxPolicyDesc)]),
     "ofx_policy_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_actions": (_i, [_vp, _vp, _vp, _vp, _vp]),

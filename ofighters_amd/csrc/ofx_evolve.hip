@@ -22,8 +22,15 @@
 //              partial sums per neuron, are added in a fixed order: no floating-point atomics, the same bits every call.
 //              Head, bias, sigmoid, the remaining layers (activations in LDS), the decode and the stores follow in the
 //              same launch.
+// k_pop_grad / k_pop_apply  ofx_population_learn, a gradient step per genome on its own samples (include/ofx.h).  The
+//              walk (pop_walk), the forward (pop_forward) and the decode (pop_emit) are __device__ bodies shared with
+//              k_pop_act: each exists once.  Phase A (k_pop_grad, a workgroup per ship) runs the forward and leaves
+//              every layer's activations and deltas, all from the OLD weights, in a workspace; phase B (k_pop_apply,
+//              a workgroup per genome) adds its samples' terms in ascending ship order and touches, in the first layer,
+//              only the n1-double runs of the set cells.  No floating-point atomics.
 // k_pop_fitness  integer atomics only.
 #include "ofx_internal.h"
+#include "ofx_arena.h"
 
 #include <new>
 #include <vector>
@@ -31,6 +38,7 @@
 #define POP_MAX_LAYERS 8
 #define POP_MAX_WIDTH 64
 #define POP_LIST 2048               /* set cells one wave lists before it gathers: a batch of 64 words holds <= 2048 */
+#define POP_MAX_ACTS ((POP_MAX_LAYERS - 2) * POP_MAX_WIDTH + 4) /* activations of one ship behind the input: <= 6 x 64 + 4 */
 #define POP_AHEAD 16                /* batches of 64 map words a wave loads before it looks at the first              */
 
 struct ofx_population {
@@ -95,43 +103,21 @@ struct pop_net {
   int32_t layers[POP_MAX_LAYERS];
 };
 
-__global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state st, const unsigned *ship_bits,
-                                                 const unsigned *laser_bits, int words, const double *data, long long P,
-                                                 uint32_t G, uint32_t first, uint32_t n_w, pop_net net,
-                                                 const int32_t *genome_of, ofx_action *actions, double *y) {
-  __shared__ uint32_t list[4][POP_LIST];
-  __shared__ double part[4][64];
-  __shared__ double act[2][POP_MAX_WIDTH];
-  const int s = blockIdx.x, a = s / M;
-  const int32_t g = genome_of[s];
-  if (g < 0 || (long long)g >= P || !st.alive[s]) return;  // uniform over the workgroup
-  const double *gen = data + (size_t)g * G;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int n1 = net.layers[1];
-  const int groups = 64 / n1;                   // cells one wave gathers per pass
-  const int o = lane % n1, grp = lane / n1;     // this lane's neuron and its place among the pass's cells
-  const bool gathers = grp < groups;
-  const unsigned *sb = ship_bits + (size_t)a * words, *lb = laser_bits + (size_t)a * words;
-  // the two maps are one run of 2*words words (toVector: ship map, then laser map); a wave owns a quarter of it
+// The walk over one arena's set cells, stated once for the forward (k_pop_act, k_pop_grad) and the first layer's update
+// (k_pop_apply).  The two maps are one run of 2*words words (toVector: ship map, then laser map); wave wv of the four
+// owns a quarter of it, lists the set cells of its quarter in ascending order in `mine` (POP_LIST entries of its own,
+// a wave scan, no block barrier) and hands them to flush(n) - whenever the next batch would not fit, and once at the
+// end (n may be 0).  The wavefront fences order the lanes' list writes before flush's reads and those before the next
+// writes.
+template <class Flush>
+__device__ __forceinline__ void pop_walk(const unsigned *sb, const unsigned *lb, int words, int wv, int lane,
+                                         uint32_t *mine, Flush flush) {
   const int total = 2 * words, per = (total + 3) / 4;
   const int w_end = min(total, (wv + 1) * per);
-  uint32_t *mine = list[wv];
   int count = 0;                                // cells listed, uniform over the wave
-  double acc = 0.0;
-  // gather what is listed: lane (grp, o) takes cells grp, grp + groups, ... in list order
-  auto gather = [&]() {
+  auto drain = [&]() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (gathers) {
-      int i = grp;
-      for (; i + 7 * groups < count; i += 8 * groups) {
-        double t[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) t[q] = gen[(size_t)(8u + mine[i + q * groups]) * n1 + o];
-#pragma unroll
-        for (int q = 0; q < 8; q++) acc += t[q];
-      }
-      for (; i < count; i += groups) acc += gen[(size_t)(8u + mine[i]) * n1 + o];
-    }
+    flush(count);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     count = 0;
   };
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state 
         if (lane >= d) inc += up;
       }
       const int n_new = __shfl(inc, 63);
-      if (count + n_new > POP_LIST) gather();
+      if (count + n_new > POP_LIST) drain();
       const uint32_t cell0 = (uint32_t)(w0 + j * 64 + lane) * 32u;
       int at = count + inc - c;
       while (x) {
@@ -167,13 +153,49 @@ __global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state 
       count += n_new;
     }
   }
-  gather();
+  drain();
+}
+
+// Neural_network.feed of genome `gen` on ship s of arena a, by one 256-thread workgroup; returns the row of `act` that
+// holds the four outputs.  KEEP = false (k_pop_act): two rows, layer l's activations in row l & 1.  KEEP = true
+// (k_pop_grad): a row per layer, a_{l+1} in row l, and the 8-scalar head of the observation in `head`.
+template <bool KEEP>
+__device__ __forceinline__ int pop_forward(int s, int a, int W, int H, const ofx_state &st, const unsigned *ship_bits,
+                                           const unsigned *laser_bits, int words, const double *gen, uint32_t first,
+                                           uint32_t n_w, const pop_net &net, uint32_t (*list)[POP_LIST],
+                                           double (*part)[64], double (*act)[POP_MAX_WIDTH], double *head) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n1 = net.layers[1];
+  const int groups = 64 / n1;                   // cells one wave gathers per pass
+  const int o = lane % n1, grp = lane / n1;     // this lane's neuron and its place among the pass's cells
+  const bool gathers = grp < groups;
+  const unsigned *sb = ship_bits + (size_t)a * words, *lb = laser_bits + (size_t)a * words;
+  uint32_t *mine = list[wv];
+  double acc = 0.0;
+  // gather what is listed: lane (grp, o) takes cells grp, grp + groups, ... in list order
+  pop_walk(sb, lb, words, wv, lane, mine, [&](int count) {
+    if (gathers) {
+      int i = grp;
+      for (; i + 7 * groups < count; i += 8 * groups) {
+        double t[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) t[q] = gen[(size_t)(8u + mine[i + q * groups]) * n1 + o];
+#pragma unroll
+        for (int q = 0; q < 8; q++) acc += t[q];
+      }
+      for (; i < count; i += groups) acc += gen[(size_t)(8u + mine[i]) * n1 + o];
+    }
+  });
   part[wv][lane] = gathers ? acc : 0.0;
   __syncthreads();
   if (tid < n1) {
     // first layer of neuron tid: head in toVector order, the map cells in (wave, group) order, bias
     double v[8];
     ofx_obs_head(st, s, W, H, v);
+    if (KEEP && tid == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) head[k] = v[k];
+    }
     double z = gen[tid] * v[0];
 #pragma unroll
     for (int k = 1; k < 8; k++) z += gen[(size_t)k * n1 + tid] * v[k];
@@ -186,29 +208,245 @@ __global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state 
   int cur = 0;
   for (int l = 1; l + 1 < net.n_layers; l++) {
     const int nin = net.layers[l], nout = net.layers[l + 1];
+    const int nxt = KEEP ? l : cur ^ 1;
     if (tid < nout) {
       const double *w = gen + woff + (size_t)tid * nin;
       double z = 0.0;
       for (int k = 0; k < nin; k++) z += w[k] * act[cur][k];
-      act[cur ^ 1][tid] = pop_sigmoid(z + gen[boff + tid]);
+      act[nxt][tid] = pop_sigmoid(z + gen[boff + tid]);
     }
     __syncthreads();
     woff += (uint32_t)(nin * nout);
     boff += (uint32_t)nout;
-    cur ^= 1;
+    cur = nxt;
   }
+  return cur;
+}
+
+// the reference's decode of the four outputs `out` (brAIn.py:129-134, the arena's size in place of 400) and the stores
+__device__ __forceinline__ void pop_emit(int s, int W, int H, const double *out, ofx_action *actions, double *y) {
+  const int tid = threadIdx.x;
+  if (actions && tid == 0) {
+    const double y0 = out[0], y1 = out[1], y2 = out[2], y3 = out[3];
+    ofx_action act;
+    act.px = (int32_t)(y2 * (double)W);
+    act.py = (int32_t)(y3 * (double)H);
+    act.shoot = y0 > 0.5 ? 1 : 0;
+    act.thrust = y1 > 0.5 ? 1 : 0;
+    act.valid = 1;
+    act._pad = 0;
+    actions[s] = act;
+  }
+  if (y && tid < 4) y[(size_t)s * 4 + tid] = out[tid];
+}
+
+__global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state st, const unsigned *ship_bits,
+                                                 const unsigned *laser_bits, int words, const double *data, long long P,
+                                                 uint32_t G, uint32_t first, uint32_t n_w, pop_net net,
+                                                 const int32_t *genome_of, ofx_action *actions, double *y) {
+  __shared__ uint32_t list[4][POP_LIST];
+  __shared__ double part[4][64];
+  __shared__ double act[2][POP_MAX_WIDTH];
+  const int s = blockIdx.x, a = s / M;
+  const int32_t g = genome_of[s];
+  if (g < 0 || (long long)g >= P || !st.alive[s]) return;  // uniform over the workgroup
+  const int cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, data + (size_t)g * G, first, n_w, net,
+                                     list, part, act, nullptr);
+  pop_emit(s, W, H, act[cur], actions, y);
+}
+
+// What one ofx_population_learn call keeps between its two kernels (learn_layout): per ship the activations and deltas
+// of every layer packed one after the other (S = layers[1] + ... + layers[L] doubles each) and the observation's head,
+// per ship the genome it is a sample of (-1: none), per genome its number of samples.
+struct LearnWs {
+  int32_t *sample_of;  // [N*M]
+  int32_t *count;      // [P]
+  double *a, *d;       // [N*M][S]
+  double *head;        // [N*M][8]
+};
+
+// Phase A of ofx_population_learn: the forward of k_pop_act (the same bodies, the same bits), then for a sample the
+// deltas of every layer from the genome's OLD weights.  One workgroup per (arena, ship).
+__global__ __launch_bounds__(256) void k_pop_grad(int M, int W, int H, ofx_state st, const unsigned *ship_bits,
+                                                  const unsigned *laser_bits, int words, const double *data, long long P,
+                                                  uint32_t G, uint32_t first, uint32_t n_w, pop_net net, int S,
+                                                  const int32_t *genome_of, const double *solution,
+                                                  const uint8_t *learn_mask, ofx_action *actions, double *y, double *err,
+                                                  LearnWs ws) {
+  // 38 496 B: four workgroups fit a CU's 160 KB, as with k_pop_act (with the deltas in rows of their own, 42 080 B, three
+  // did, and the call's phase A took 628 us against the forward's 459 at 4096 arenas)
+  __shared__ __attribute__((aligned(16))) uint32_t list[4][POP_LIST];
+  __shared__ double part[4][64];
+  __shared__ double act[POP_MAX_LAYERS - 1][POP_MAX_WIDTH];
+  __shared__ double head[8], diff[4];
+  const int s = blockIdx.x, a = s / M;
+  const int32_t g = genome_of[s];
+  if (g < 0 || (long long)g >= P || !st.alive[s]) return;  // uniform over the workgroup
+  const double *gen = data + (size_t)g * G;
+  const int top = pop_forward<true>(s, a, W, H, st, ship_bits, laser_bits, words, gen, first, n_w, net, list, part, act,
+                                    head);
+  pop_emit(s, W, H, act[top], actions, y);
+  if (learn_mask && !learn_mask[s]) return;                // uniform over the workgroup
+  const int tid = threadIdx.x;
+  // the deltas take the cell lists' place: the forward's barriers stand behind every wave's last look at its list
+  double (*dl)[POP_MAX_WIDTH] = reinterpret_cast<double (*)[POP_MAX_WIDTH]>(&list[0][0]);
+  if (tid < 4) {
+    const double out = act[top][tid], d = solution[(size_t)s * 4 + tid];
+    const double df = d - out;
+    diff[tid] = df;
+    dl[top][tid] = df * (out * (1.0 - out));
+  }
+  __syncthreads();
   if (tid == 0) {
-    const double y0 = act[cur][0], y1 = act[cur][1], y2 = act[cur][2], y3 = act[cur][3];
-    ofx_action out;
-    out.px = (int32_t)(y2 * (double)W);
-    out.py = (int32_t)(y3 * (double)H);
-    out.shoot = y0 > 0.5 ? 1 : 0;
-    out.thrust = y1 > 0.5 ? 1 : 0;
-    out.valid = 1;
-    out._pad = 0;
-    actions[s] = out;
+    if (err) err[s] = ((diff[0] * diff[0] + diff[1] * diff[1]) + diff[2] * diff[2]) + diff[3] * diff[3];
+    ws.sample_of[s] = g;
+    atomicAdd(ws.count + g, 1);
   }
-  if (y && tid < 4) y[(size_t)s * 4 + tid] = act[cur][tid];
+  // delta_l = (W_{l+1}^T delta_{l+1}) * a_l (1 - a_l); row l holds layer l + 1, W_{l+1} is row-major behind the first layer
+  uint32_t woff = n_w;
+  for (int l = top - 1; l >= 0; l--) {
+    const int nk = net.layers[l + 1], no = net.layers[l + 2];
+    woff -= (uint32_t)(nk * no);
+    if (tid < nk) {
+      const double *w = gen + woff + tid;
+      double sum = w[0] * dl[l + 1][0];
+      for (int q = 1; q < no; q++) sum += w[(size_t)q * nk] * dl[l + 1][q];
+      const double v = act[l][tid];
+      dl[l][tid] = sum * (v * (1.0 - v));
+    }
+    __syncthreads();
+  }
+  int off = 0;
+  for (int l = 0; l <= top; l++) {
+    const int n = net.layers[l + 1];
+    if (tid < n) {
+      ws.a[(size_t)s * S + off + tid] = act[l][tid];
+      ws.d[(size_t)s * S + off + tid] = dl[l][tid];
+    }
+    off += n;
+  }
+  if (tid < 8) ws.head[(size_t)s * 8 + tid] = head[tid];
+}
+
+// Phase B of ofx_population_learn: one workgroup per genome applies its samples' terms one sample after the other, in
+// ascending flat ship index.  It finds them by scanning sample_of 256 entries at a time (a ballot per wave, the hits
+// compacted in order into `found`), and per sample: the head rows of the first layer, the later layers and every bias
+// with a thread per element, then the shared walk over the sample's arena with a read-add-write of the n1 contiguous
+// doubles of each set cell, lanes over (cell, neuron) as in the gather.  Within one sample every address is distinct;
+// two samples may meet in a cell from different waves, hence the barrier between samples.  A genome belongs to one
+// workgroup alone.
+__global__ __launch_bounds__(256) void k_pop_apply(int NM, int M, const unsigned *ship_bits, const unsigned *laser_bits,
+                                                   int words, double *data, uint32_t G, uint32_t first, uint32_t n_w,
+                                                   pop_net net, int S, LearnWs ws, double rate) {
+  __shared__ uint32_t list[4][POP_LIST];
+  __shared__ int32_t found[256];
+  __shared__ int in_wave[4];
+  __shared__ double sa[POP_MAX_ACTS], sd[POP_MAX_ACTS], sh[8];   // 40 080 B in all: four workgroups a CU
+  const int g = blockIdx.x;
+  const int n = ws.count[g];
+  if (n == 0) return;                                      // uniform over the workgroup
+  const double c = rate / (double)n;
+  double *gen = data + (size_t)g * G;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n1 = net.layers[1];
+  const int groups = 64 / n1;
+  const int o = lane % n1, grp = lane / n1;
+  const bool gathers = grp < groups;
+  uint32_t *mine = list[wv];
+  int done = 0;
+  for (int base = 0; base < NM && done < n; base += 256) {
+    const int idx = base + tid;
+    const bool hit = idx < NM && ws.sample_of[idx] == g;
+    const unsigned long long b = __ballot(hit);
+    if (lane == 0) in_wave[wv] = __popcll(b);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int q = 0; q < 4; q++) {
+      if (q < wv) before += in_wave[q];
+      total += in_wave[q];
+    }
+    if (hit) found[before + __popcll(b & ((1ull << lane) - 1ull))] = idx;
+    __syncthreads();
+    for (int j = 0; j < total; j++) {
+      const int s = found[j], a = s / M;
+      for (int t = tid; t < S; t += 256) {                 // S can pass 256: 6 x 64 + 4
+        sa[t] = ws.a[(size_t)s * S + t];
+        sd[t] = c * ws.d[(size_t)s * S + t];
+      }
+      if (tid < 8) sh[tid] = ws.head[(size_t)s * 8 + tid];
+      __syncthreads();
+      // the 8 head inputs of the first layer: storage position k * n1 + o
+      for (int e = tid; e < 8 * n1; e += 256) {
+        const int k = e / n1;
+        const double t = sd[e - k * n1] * sh[k];
+        gen[e] = gen[e] + t;
+      }
+      uint32_t woff = first;
+      int in = 0, out = n1;
+      for (int l = 1; l + 1 < net.n_layers; l++) {
+        const int nin = net.layers[l], nout = net.layers[l + 1];
+        for (int e = tid; e < nin * nout; e += 256) {
+          const int q = e / nin;
+          const double t = sd[out + q] * sa[in + (e - q * nin)];
+          gen[woff + e] = gen[woff + e] + t;
+        }
+        woff += (uint32_t)(nin * nout);
+        in = out;
+        out += nout;
+      }
+      for (int t = tid; t < S; t += 256) gen[n_w + t] = gen[n_w + t] + sd[t];
+      // the set cells: the input is 1, the element becomes w + c * delta_1[o]
+      const double cd = sd[o];
+      pop_walk(ship_bits + (size_t)a * words, laser_bits + (size_t)a * words, words, wv, lane, mine, [&](int count) {
+        if (gathers)
+          for (int i = grp; i < count; i += groups) {
+            double *w = gen + (size_t)(8u + mine[i]) * n1 + o;
+            *w = *w + cd;
+          }
+      });
+      __syncthreads();
+    }
+    done += total;
+  }
+}
+
+// the teacher's action as a target: the inverse of pop_emit's decode; one thread per (arena, ship)
+__global__ void k_pop_targets(int NM, int W, int H, const ofx_action *teacher, double *solution, uint8_t *mask) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= NM) return;
+  const ofx_action t = teacher[s];
+  const double x = ((double)t.px + 0.5) / (double)W, y = ((double)t.py + 0.5) / (double)H;
+  double *out = solution + (size_t)s * 4;
+  out[0] = t.shoot ? 1.0 : 0.0;
+  out[1] = t.thrust ? 1.0 : 0.0;
+  out[2] = x < 0.0 ? 0.0 : x > 1.0 ? 1.0 : x;
+  out[3] = y < 0.0 ? 0.0 : y > 1.0 ? 1.0 : y;
+  mask[s] = t.valid != 0;
+}
+
+// acc[0] += the err entries >= 0 (thread t adds entries t, t + 256, ... in that order, then the 256 partial sums are
+// added in thread order: the same bits every call), acc[1] += their number; every entry is then set to -1 (no sample)
+__global__ __launch_bounds__(256) void k_pop_err_reduce(int NM, double *err, double *acc) {
+  __shared__ double sum[256];
+  __shared__ int cnt[256];
+  const int tid = threadIdx.x;
+  double v = 0.0;
+  int k = 0;
+  for (int s = tid; s < NM; s += 256) {
+    const double e = err[s];
+    if (e >= 0.0) { v += e; k++; }
+    err[s] = -1.0;
+  }
+  sum[tid] = v;
+  cnt[tid] = k;
+  __syncthreads();
+  if (tid == 0) {
+    double t = sum[0];
+    int m = cnt[0];
+    for (int q = 1; q < 256; q++) { t += sum[q]; m += cnt[q]; }
+    acc[0] = acc[0] + t;
+    acc[1] = acc[1] + (double)m;
+  }
 }
 
 __global__ void k_pop_fitness(int NM, long long P, const int32_t *last_score, const int32_t *genome_of,
@@ -222,6 +460,13 @@ __global__ void k_pop_fitness(int NM, long long P, const int32_t *last_score, co
 }
 
 static ofx_population *&pop_of(ofx_handle *h) { return h->population; }
+
+static pop_net net_of(const ofx_population *p) {
+  pop_net net;
+  net.n_layers = p->n_layers;
+  for (int i = 0; i < POP_MAX_LAYERS; i++) net.layers[i] = i < p->n_layers ? p->layers[i] : 0;
+  return net;
+}
 
 void ofx_population_free(ofx_handle *h) {
   ofx_population *p = pop_of(h);
@@ -402,14 +647,78 @@ extern "C" int ofx_population_act(ofx_handle *h, const int32_t *genome_of, ofx_a
   const ofx_config &c = h->cfg;
   OFX_HIP(hipSetDevice(c.device));
   if ((rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr))) return rc;
-  pop_net net;
-  net.n_layers = p->n_layers;
-  for (int i = 0; i < POP_MAX_LAYERS; i++) net.layers[i] = i < p->n_layers ? p->layers[i] : 0;
+  const pop_net net = net_of(p);
   const int words = (int)(((size_t)c.width * c.height) >> 5);
   hipLaunchKernelGGL(k_pop_act, dim3((unsigned)(c.n_arenas * c.n_ships)), dim3(256), 0, h->stream, c.n_ships, c.width,
                      c.height, h->st, (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0],
                      (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1], words, p->data, (long long)p->P, p->G, p->first,
                      p->n_w, net, genome_of, actions, y);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// the one statement of ofx_population_learn's workspace (ofx_arena.h): NM ships, S activations per ship, P genomes
+static void learn_layout(Arena &A, size_t NM, size_t S, size_t P, LearnWs &W) {
+  W.sample_of = A.n<int32_t>(NM);
+  W.count = A.n<int32_t>(P);
+  W.a = A.d(NM * S);
+  W.d = A.d(NM * S);
+  W.head = A.d(NM * 8);
+}
+
+extern "C" int ofx_population_learn(ofx_handle *h, const int32_t *genome_of, const double *solution,
+                                    const uint8_t *learn_mask, double rate, ofx_action *actions, double *y, double *err) {
+  ofx_population *p;
+  int rc = need_population(h, "ofx_population_learn", &p);
+  if (rc) return rc;
+  if (!genome_of || !solution) { ofx_set_error("ofx_population_learn: genome_of or solution is NULL"); return OFX_ERR_INVALID; }
+  if (!(rate - rate == 0.0)) { ofx_set_error("ofx_population_learn: rate is not finite"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("You must execute analyse_battleground first."); return OFX_ERR_STATE; }
+  const ofx_config &c = h->cfg;
+  OFX_HIP(hipSetDevice(c.device));
+  const size_t NM = (size_t)c.n_arenas * c.n_ships;
+  size_t S = 0;
+  for (int i = 1; i < p->n_layers; i++) S += (size_t)p->layers[i];
+  LearnWs ws;
+  Arena measure;
+  learn_layout(measure, NM, S, (size_t)p->P, ws);
+  if ((rc = ofx_ensure_scratch(h, measure.used))) return rc;
+  Arena A(h->scratch, measure.used);
+  learn_layout(A, NM, S, (size_t)p->P, ws);
+  if (!A.ok()) { ofx_set_error("ofx_population_learn: the workspace does not fit its block of %zu bytes", measure.used); return OFX_ERR_STATE; }
+  if ((rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr))) return rc;
+  OFX_HIP(hipMemsetAsync(ws.sample_of, 0xff, NM * sizeof(int32_t), h->stream));   // -1: no sample
+  OFX_HIP(hipMemsetAsync(ws.count, 0, (size_t)p->P * sizeof(int32_t), h->stream));
+  const pop_net net = net_of(p);
+  const int words = (int)(((size_t)c.width * c.height) >> 5);
+  const unsigned *sb = (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0], *lb = (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1];
+  hipLaunchKernelGGL(k_pop_grad, dim3((unsigned)NM), dim3(256), 0, h->stream, c.n_ships, c.width, c.height, h->st, sb, lb,
+                     words, p->data, (long long)p->P, p->G, p->first, p->n_w, net, (int)S, genome_of, solution, learn_mask,
+                     actions, y, err, ws);
+  OFX_HIP(hipGetLastError());
+  if (rate == 0.0) return OFX_OK;                          // outputs and err only: no genome changes a bit
+  hipLaunchKernelGGL(k_pop_apply, dim3((unsigned)p->P), dim3(256), 0, h->stream, (int)NM, c.n_ships, sb, lb, words,
+                     p->data, p->G, p->first, p->n_w, net, (int)S, ws, rate);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+extern "C" int ofx_population_targets(ofx_handle *h, const ofx_action *teacher, double *solution, uint8_t *mask) {
+  if (!h || !teacher || !solution || !mask) { ofx_set_error("ofx_population_targets: null argument"); return OFX_ERR_INVALID; }
+  const ofx_config &c = h->cfg;
+  OFX_HIP(hipSetDevice(c.device));
+  const int NM = c.n_arenas * c.n_ships;
+  hipLaunchKernelGGL(k_pop_targets, dim3((NM + 255) / 256), dim3(256), 0, h->stream, NM, c.width, c.height, teacher,
+                     solution, mask);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+extern "C" int ofx_population_err_reduce(ofx_handle *h, double *err, double *acc) {
+  if (!h || !err || !acc) { ofx_set_error("ofx_population_err_reduce: null argument"); return OFX_ERR_INVALID; }
+  const ofx_config &c = h->cfg;
+  OFX_HIP(hipSetDevice(c.device));
+  hipLaunchKernelGGL(k_pop_err_reduce, dim3(1), dim3(256), 0, h->stream, c.n_arenas * c.n_ships, err, acc);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }

@@ -1063,6 +1063,27 @@ class ArenaBatch:
         genome; y_ptr: device float64 [N][M][4] or None.  Does not synchronise."""
         nat.check(nat.lib().ofx_population_act(self._h, genome_of_ptr, out_ptr or self._actions.ptr, y_ptr))
 
+    def population_learn(self, genome_of_ptr, solution_ptr, rate, mask_ptr=None, out_ptr=None, y_ptr=None, err_ptr=None,
+                         actions=True):
+        """A gradient step per genome on its own ships (ofx_population_learn): the forward outputs of population_act
+        from the weights before the call (actions into the batch's own array, or out_ptr; actions=False: none), then
+        every genome's weights move by rate / n times its samples' gradients toward the device float64 [N][M][4] at
+        solution_ptr.  mask_ptr: device uint8 [N][M] or None; err_ptr: device float64 [N][M] or None.  Does not
+        synchronise."""
+        out = (out_ptr or self._actions.ptr) if actions else None
+        nat.check(nat.lib().ofx_population_learn(self._h, genome_of_ptr, solution_ptr, mask_ptr, float(rate), out, y_ptr,
+                                                 err_ptr))
+
+    def population_targets(self, solution_ptr, mask_ptr, teacher_ptr=None):
+        """The teacher's actions (None = the batch's own array, as bot_actions wrote it) as targets float64 [N][M][4] and
+        a mask uint8 [N][M] (ofx_population_targets).  Does not synchronise."""
+        nat.check(nat.lib().ofx_population_targets(self._h, teacher_ptr or self._actions.ptr, solution_ptr, mask_ptr))
+
+    def population_err_reduce(self, err_ptr, acc_ptr):
+        """acc (device float64 [2]) += (sum, count) of the entries >= 0 of err (device float64 [N][M]), which are then
+        set to -1 (ofx_population_err_reduce).  Does not synchronise."""
+        nat.check(nat.lib().ofx_population_err_reduce(self._h, err_ptr, acc_ptr))
+
     def population_fitness(self, genome_of_ptr, sum_buf, count_buf, reset=False):
         """sum[g] (int64 [P]) += the score every ship flown by genome g banked at the last restart, count[g] (int32 [P])
         += 1 per such ship; reset zeroes both first.  Does not synchronise."""
