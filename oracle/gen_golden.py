@@ -5,6 +5,8 @@ Imports the *live* reference from /root/reference (read-only) under
 /opt/conda/bin/python3.9 (numpy 1.26.4, scikit-image 0.18.3) and records small
 input/output fixtures for the hot path into tests/golden/*.npz:
 
+  step_const_<tag>.npz  the same traces recorded at CHANGED game constants (ship radius, both speeds, the four
+                    rewards), set on the reference's objects from outside; see const_traces()
   step_<name>.npz   per-tick traces of Battleground.frame()  (battleground.py:163-166)
                     with the GUI laser clean-up of ofighters.py:619-625,702-707
                     emulated between ticks and Battleground.restart() between
@@ -119,9 +121,33 @@ def pack(m):
     return np.packbits(np.asarray(m) != 0)
 
 
+def apply_consts(bg, consts):
+    """Harness-side: the game constants of every ship, set on the live objects (ship.py:43,50,86 are plain
+    attributes; Ship.reset leaves them alone, they are set again after a restart all the same)."""
+    for s in bg.ships:
+        s.body.radius = consts["ship_radius"]
+        s.max_speed = consts["ship_speed"]
+        s.laser_speed = consts["laser_speed"]
+
+
 def run_trace(name, ships, seed, episodes, ticks=EPISODE_TICKS, map_every=1,
-              init=None, scripts=None, box=None, lmax=None, setup=None, clock=None, extra=None):
-    """Drive the reference exactly as the GUI does and dump a trace."""
+              init=None, scripts=None, box=None, lmax=None, setup=None, clock=None, extra=None, consts=None):
+    """Drive the reference exactly as the GUI does and dump a trace.  consts: ship_radius, ship_speed, laser_speed
+    and the four reward_* values to run at instead of the reference's own; they are stored in the trace as const_*."""
+    if consts is not None:
+        import ofighters.agents.qlearnIA_V2 as ql
+        saved = dict(ql.REWARDS)            # ship.py:22 and laser.py:11 hold this very dict: change its entries
+        for k in ("death", "kill", "aim", "trajectory"):
+            ql.REWARDS[k] = consts["reward_" + k]
+        try:
+            return _run_trace(name, ships, seed, episodes, ticks, map_every, init, scripts, box, lmax, setup, clock,
+                              extra, consts)
+        finally:
+            ql.REWARDS.update(saved)
+    return _run_trace(name, ships, seed, episodes, ticks, map_every, init, scripts, box, lmax, setup, clock, extra, None)
+
+
+def _run_trace(name, ships, seed, episodes, ticks, map_every, init, scripts, box, lmax, setup, clock, extra, consts):
     random.seed(seed)
     TAP.log = []
     TAP.box = box
@@ -135,6 +161,9 @@ def run_trace(name, ships, seed, episodes, ticks=EPISODE_TICKS, map_every=1,
         for s, (x, y, px, py) in zip(bg.ships, init):
             s.body.x, s.body.y = x, y
             s.pointing = Point(px, py)
+    if consts is not None:
+        apply_consts(bg, consts)
+    if init is not None or consts is not None:
         with contextlib.redirect_stdout(_sink):
             bg.absolute_state = Observation(battleground=bg)
     if scripts is not None:
@@ -201,6 +230,9 @@ def run_trace(name, ships, seed, episodes, ticks=EPISODE_TICKS, map_every=1,
             bg.lasers = [l for l in bg.lasers if l.state != "destroyed"]
             TAP.log = []
             bg.restart()
+            if consts is not None:
+                apply_consts(bg, consts)
+                bg.absolute_state = Observation(battleground=bg)
             reset_draws[ep] = np.array(TAP.log, dtype=np.int32).reshape(M, 2)
             for i, s in enumerate(bg.ships):
                 reset_state[ep, i] = (s.body.x, s.body.y, s.pointing.x, s.pointing.y)
@@ -225,6 +257,7 @@ def run_trace(name, ships, seed, episodes, ticks=EPISODE_TICKS, map_every=1,
         map_ticks=np.array(map_ticks, dtype=np.int32),
         ship_maps=np.array(ship_maps), laser_maps=np.array(laser_maps),
         reset_draws=reset_draws, reset_state=reset_state, ep_scores=ep_scores,
+        **{"const_" + k: np.int32(v) for k, v in (consts or {}).items()},
         **(extra() if extra is not None else {}))
     kills = int((ship_alive[ticks - 1::ticks] == 0).sum())
     print("step_%-22s M=%d T=%d maxL=%d deaths=%d reward_sum=%d" % (
@@ -323,6 +356,20 @@ def crafted_traces():
     # 8. reset quirks (ship.py:99-101): pointing = OLD position, `x or old`
     #    keeps the coordinate when the draw is 0 -> confine draws to {0,1}
     run_trace("craft_reset_zero", {"random": 4}, 2, 4, ticks=5, box=(0, 1))
+
+
+def const_traces():
+    """Brawls at changed constants: the first three constant sets of tests/step_constant_cases.py (the reference
+    hard-codes the laser's radius 2 - laser.py:23, ship.py:135,147 - so laser_radius stays 2 and R = ship_radius + 2
+    is 5, 13 and 25) with the rewards death -7, kill 11, aim 3, trajectory 5.  The map stays the reference's 400 x 400."""
+    rewards = dict(reward_death=-7, reward_kill=11, reward_aim=3, reward_trajectory=5)
+    for tag, r, ss, ls, seed, box in (("r5", 3, 5, 5, 51, (180, 215)), ("r13", 11, 13, 26, 52, (0, 50)),
+                                      ("r25", 23, 0, 0, 53, (340, 400))):
+        rs = np.random.RandomState(seed)
+        eps, ticks, M = 3, 20, 6
+        scripts = brawl_script(rs, M, eps * ticks, box)
+        run_trace("const_" + tag, {"idle": M}, seed, episodes=eps, ticks=ticks, map_every=7, scripts=scripts, box=box,
+                  consts=dict(ship_radius=r, laser_radius=2, ship_speed=ss, laser_speed=ls, **rewards))
 
 
 # --------------------------------------------------------------------------
@@ -507,6 +554,10 @@ def epsilon_cases():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) > 2 and sys.argv[2] == "const":     # only the changed-constant traces
+        const_traces()
+        sys.exit(0)
+    const_traces()
     random_traces()
     brawl_traces()
     crafted_traces()

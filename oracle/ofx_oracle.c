@@ -125,6 +125,27 @@ void orc_set_ship(orc_arena *a, int i, long x, long y, long px, long py) {
   a->ships[i].py = py;
 }
 
+/* crafted laser lists used by the tests: the n given lasers replace the list.
+ * (dx, dy) is the integer direction pointing - fired that Laser.move turns
+ * into the per-lock-step velocity by its own arithmetic (laser.py:39-48);
+ * (0, 0) is the zero-velocity laser of laser.py:43.                         */
+static void push_laser(orc_arena *a, const orc_laser *l);
+void orc_set_lasers(orc_arena *a, int n, const double *x, const double *y, const int32_t *dx, const int32_t *dy,
+                    const int32_t *owner, const uint8_t *destroyed) {
+  a->n_lasers = 0;
+  for (int j = 0; j < n; j++) {
+    orc_laser l;
+    memset(&l, 0, sizeof(l));
+    l.x = x[j];
+    l.y = y[j];
+    l.tx = dx[j]; /* fired = (0, 0), pointing = (dx, dy) */
+    l.ty = dy[j];
+    l.owner = owner[j];
+    l.destroyed = destroyed[j] != 0;
+    push_laser(a, &l);
+  }
+}
+
 /* Battleground.restart -> Ship.reset -> Agent.reset
  * battleground.py:108-117, ship.py:92-106, agent.py:59-64                   */
 void orc_restart(orc_arena *a, const int32_t *draws) {

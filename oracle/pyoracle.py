@@ -45,6 +45,7 @@ def lib():
         L.orc_destroy.argtypes = [vp]
         L.orc_spawn.argtypes = [vp, i32p]
         L.orc_set_ship.argtypes = [vp, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long]
+        L.orc_set_lasers.argtypes = [vp, C.c_int, f64p, f64p, i32p, i32p, i32p, u8p]
         L.orc_restart.argtypes = [vp, i32p]
         L.orc_step.argtypes = [vp, i32p]
         L.orc_n_lasers.argtypes = [vp]
@@ -94,6 +95,20 @@ class Arena:
 
     def set_ship(self, i, x, y, px, py):
         lib().orc_set_ship(self._h, i, int(x), int(y), int(px), int(py))
+
+    def set_lasers(self, x, y, dx, dy, owner, destroyed):
+        """Replace the laser list (crafted starts, like set_ship).  x, y: float64 centres; dx, dy: the INTEGER direction
+        pointing - fired, from which Laser.move derives the velocity d * laser_speed / |d| itself (laser.py:39-48;
+        (0, 0) = a laser that never moves); owner: ship index; destroyed: 1 = leaves the list at the next lock-step."""
+        x, y = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (x, y))
+        dx, dy, owner = (np.ascontiguousarray(v, dtype=np.int32).ravel() for v in (dx, dy, owner))
+        destroyed = np.ascontiguousarray(destroyed, dtype=np.uint8).ravel()
+        n = len(x)
+        if not all(len(v) == n for v in (y, dx, dy, owner, destroyed)):
+            raise ValueError("set_lasers: all six arrays need one entry per laser")
+        if n and (owner.min() < 0 or owner.max() >= self.M):
+            raise ValueError("set_lasers: owner outside 0 .. n_ships - 1")
+        lib().orc_set_lasers(self._h, n, _p(x), _p(y), _p(dx), _p(dy), _p(owner), _p(destroyed))
 
     def restart(self, draws):
         d = np.ascontiguousarray(draws, dtype=np.int32).reshape(self.M, 2)

@@ -12,7 +12,7 @@ failure (none is expected)."""
 import numpy as np
 import pytest
 
-from tests.trace_util import load_trace, step_traces, unpack_map
+from tests.trace_util import load_trace, step_traces, trace_constants, unpack_map
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +30,7 @@ def test_step_trace_gpu(name):
     z = load_trace(name)
     M = z["init_state"].shape[0]
     ticks, episodes = int(z["ticks"]), int(z["episodes"])
-    b = _batch(REP, M, laser_cap=256)
+    b = _batch(REP, M, laser_cap=256, **trace_constants(z))   # the step_const_* traces carry their own constants
     rep = lambda a: np.broadcast_to(a, (REP,) + a.shape)
     b.spawn(rep(z["spawn_draws"]))
     ini = z["init_state"]

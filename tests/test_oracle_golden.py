@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle
-from tests.trace_util import load_trace, step_traces, unpack_map, GOLDEN
+from tests.trace_util import load_trace, step_traces, trace_constants, unpack_map, GOLDEN
 
 
 @pytest.mark.parametrize("name", step_traces())
@@ -14,7 +14,7 @@ def test_step_trace(name):
     z = load_trace(name)
     M = z["init_state"].shape[0]
     ticks, episodes = int(z["ticks"]), int(z["episodes"])
-    a = pyoracle.Arena(n_ships=M)
+    a = pyoracle.Arena(cfg=pyoracle.default_cfg(M, **trace_constants(z)))
     a.spawn(z["spawn_draws"])
     for i, (x, y, px, py) in enumerate(z["init_state"]):
         a.set_ship(i, x, y, px, py)
@@ -109,3 +109,15 @@ def test_scratch_nn():
             got = pyoracle.nn_feed(layers, W, B, x)
             np.testing.assert_allclose(got, y, rtol=1e-12, atol=0)
             assert int(np.argmax(got)) == int(am)
+
+
+def test_const_traces_change_every_constant():
+    """The step_const_* traces are recorded at other constants than the reference's own, every one of the seven that
+    can be set from outside the reference; the laser's radius is hard-coded there (laser.py:23) and stays 2."""
+    names = [n for n in step_traces() if n.startswith("const_")]
+    assert sorted(names) == ["const_r13", "const_r25", "const_r5"]
+    d = pyoracle.default_cfg()
+    for n in names:
+        k = trace_constants(load_trace(n))
+        assert k["laser_radius"] == 2
+        assert len(k) == 8 and all(v != getattr(d, f) for f, v in k.items() if f != "laser_radius"), (n, k)

@@ -19,3 +19,13 @@ def load_trace(name):
 
 def unpack_map(bits, w=400, h=400):
     return np.unpackbits(bits)[: w * h].reshape(w, h)
+
+
+CONSTANTS = ("ship_radius", "laser_radius", "ship_speed", "laser_speed",
+             "reward_death", "reward_kill", "reward_aim", "reward_trajectory")
+
+
+def trace_constants(z):
+    """The game constants a trace was recorded at, as config keywords: the const_* entries of the step_const_* traces
+    (oracle/gen_golden.py const_traces); empty for the traces recorded at the reference's own numbers."""
+    return {k: int(z["const_" + k]) for k in CONSTANTS if "const_" + k in z}
