@@ -440,6 +440,62 @@ int ofx_population_targets(ofx_handle *h, const ofx_action *teacher, double *sol
  * call.  OFX_ERR_INVALID for a NULL pointer.  Does not synchronise.                                                   */
 int ofx_population_err_reduce(ofx_handle *h, double *err, double *acc);
 
+/* ---- evolution strategies (opt-in): a population that is never stored ------------------------
+ * Not in the reference.  Salimans, Ho, Chen, Sidor, Sutskever 2017, "Evolution Strategies as a Scalable Alternative to
+ * Reinforcement Learning" (OpenAI-ES) with mirrored sampling: ONE centre genome theta, and every member of the population
+ * is theta +- sigma * eps with eps a pure function of (seed, pair, element, generation).  Nothing of a member is stored:
+ * the forward regenerates the noise of the rows it gathers, the generation step is one pass over theta, and a population
+ * of any P costs one genome of HBM.  Selection and breeding become a rank-weighted gradient step.
+ * STATE.  A handle may hold one ES centre, independent of its population (both may exist at once): one genome of G
+ * float64 of the topology layers_host[n_layers], in the storage layout of the neuroevolution section (first layer
+ * input-major); ofx_destroy frees it.  ofx_es_create refuses what ofx_population_create refuses, with the same messages
+ * (there is no P here); a handle that already holds a centre: OFX_ERR_STATE.
+ * ELEMENTS.  The element index e is exactly that of the neuroevolution section: an exported centre or member can be
+ * handed to ofx_population_set and ofx_scratch_feed_obs unchanged.
+ * NOISE.  r0..r3 = the Philox4x32-10 words of counter (pair i, e, generation, 12), keyed by `seed` (stream 12,
+ * OFX_ES_STREAM).  S = r0 + r1 + r2 + r3 as an integer, and
+ *   eps(i, e) = (double)(S - (2^33 - 2)) * 2^-32
+ * an Irwin-Hall sum of four uniforms: bell-shaped, bounded to (-2, 2), and EXACTLY symmetric - complementing the four
+ * words negates eps.  Every step is exact in float64 (|S - (2^33 - 2)| < 2^34), so device and numpy agree to the bit
+ * with no libm in play.  Its variance is (1 - 2^-64) / 3: sigma and the learning rate are in units of THIS eps, not of
+ * a unit normal (a unit-variance sigma is sigma * sqrt(3) here).
+ * MEMBERS.  P = 2 * n_pairs.  Member m = 2 i + b has sign s = +1 for b = 0 and -1 for b = 1, and its element is
+ *   w_m[e] = theta[e] + (s * sigma) * eps(i, e)
+ * the product rounded, then the sum rounded, no FMA.  Member index P is the centre itself, w = theta[e] (evaluation).
+ * Every layer and every bias is perturbed.
+ * REFUSALS, each with a message and before anything is enqueued: no centre (OFX_ERR_STATE); P odd or < 2; sigma not
+ * finite or <= 0; scale or any d[i] not finite; a NULL pointer; member outside [0, P] (OFX_ERR_INVALID).            */
+int ofx_es_create(ofx_handle *h, const int32_t *layers_host, int32_t n_layers);
+int ofx_es_destroy(ofx_handle *h);
+/* The centre becomes the fresh genome of slot 0: stream 11, the law (and the kernel) of ofx_population_init.  Does not
+ * synchronise.                                                                                                       */
+int ofx_es_init(ofx_handle *h, uint64_t seed, uint32_t generation);
+/* The centre in the element order, as ofx_population_get / _set move a slot.  Both synchronise.                       */
+int ofx_es_get(ofx_handle *h, double *weights_host, double *biases_host);
+int ofx_es_set(ofx_handle *h, const double *weights_host, const double *biases_host);
+/* Member `member` of P (P: the centre), materialised on the device and copied out in the element order.  Synchronises. */
+int ofx_es_member(ofx_handle *h, int64_t member, int64_t P, double sigma, uint64_t seed, uint32_t generation,
+                  double *weights_host, double *biases_host);
+/* ofx_population_act with a member per ship.  member_of: DEVICE int32 [N][M] with values in [-1, P]: -1 = not evolved,
+ * P = the centre.  Rasterises the same way, then ONE forward launch; entries of dead, unassigned (-1) and out-of-range
+ * ships are not written.  The device code is ofx_population_act's with another way to read a weight - the same lanes,
+ * the same list order, the same order of every sum - so y and the actions equal, BIT FOR BIT, those of
+ * ofx_population_act on a stored genome that holds the member's elements.  The centre takes a path without any Philox
+ * evaluation.  Does not synchronise.                                                                                 */
+int ofx_es_act(ofx_handle *h, const int32_t *member_of, int64_t P, double sigma, uint64_t seed, uint32_t generation,
+               ofx_action *actions, double *y);
+/* ofx_population_fitness over members.  sum: DEVICE int64 [P + 1], count: DEVICE int32 [P + 1]; slot P is the centre.
+ * Integer atomics.  Does not synchronise.                                                                            */
+int ofx_es_fitness(ofx_handle *h, const int32_t *member_of, int64_t P, int64_t *sum, int32_t *count, int32_t reset);
+/* The generation step.  d_host: HOST float64 [n_pairs], the weight of each pair (ofighters_amd.es.pair_weights).  Per
+ * element e:
+ *   g = 0.0;   for i = 0 .. n_pairs - 1 ascending:  g = g + d[i] * eps(i, e);   theta[e] = theta[e] + scale * g
+ * every product and every sum rounded on its own, no FMA, no floating-point atomics: the same bits on every call.  (A
+ * pair with d[i] == 0 adds +-0 to a sum that is never -0.0; the library leaves such pairs out, which changes no bit.)
+ * `generation` is the one the members flew with.  One kernel, one pass over theta.  Does not wait for the update (d is
+ * copied before the call returns, after the work already on the handle's stream).                                    */
+int ofx_es_update(ofx_handle *h, const double *d_host, int64_t n_pairs, double scale, uint64_t seed, uint32_t generation);
+
 /* ---- bi-head policy forward --------------------------------------------
  * Trainer.pointer_model graph + inference glue
  * (agents/qlearnIA_V2.py:123-190, 206-220).  See ofx_policy.h-style layout

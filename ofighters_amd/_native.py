@@ -126,6 +126,15 @@ SIGNATURES = {
     "ofx_population_learn": (_i, [_vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "ofx_population_targets": (_i, [_vp, _vp, _vp, _vp]),
     "ofx_population_err_reduce": (_i, [_vp, _vp, _vp]),
+    "ofx_es_create": (_i, [_vp, _vp, C.c_int32]),
+    "ofx_es_destroy": (_i, [_vp]),
+    "ofx_es_init": (_i, [_vp, _u64, _u32]),
+    "ofx_es_get": (_i, [_vp, _vp, _vp]),
+    "ofx_es_set": (_i, [_vp, _vp, _vp]),
+    "ofx_es_member": (_i, [_vp, C.c_int64, C.c_int64, C.c_double, _u64, _u32, _vp, _vp]),
+    "ofx_es_act": (_i, [_vp, _vp, C.c_int64, C.c_double, _u64, _u32, _vp, _vp]),
+    "ofx_es_fitness": (_i, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int32]),
+    "ofx_es_update": (_i, [_vp, _vp, C.c_int64, C.c_double, _u64, _u32]),
     "ofx_policy_layout": (_i, [_vp, C.POINTER(OfxPolicyDesc)]),
     "ofx_policy_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_actions": (_i, [_vp, _vp, _vp, _vp, _vp]),

@@ -163,6 +163,7 @@ extern "C" int ofx_destroy(ofx_handle *h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   ofx_replay_free(h);
   ofx_population_free(h);
+  ofx_es_free(h);
   ofx_state &s = h->st;
   void *ptrs[] = {s.ship_x, s.ship_y, s.ship_px, s.ship_py, s.hull, s.reward, s.score, s.obs_reward, s.last_score,
                   s.alive, s.killer, s.time, s.n_lasers, s.laser_x, s.laser_y, s.laser_dx, s.laser_dy,

@@ -29,6 +29,8 @@
 //              a workgroup per genome) adds its samples' terms in ascending ship order and touches, in the first layer,
 //              only the n1-double runs of the set cells.  No floating-point atomics.
 // k_pop_fitness  integer atomics only.
+// k_es_act / k_es_update / k_es_member  seeded evolution strategies, at the end of this file: one centre genome, the
+//              members' noise regenerated where it is read; k_es_act is pop_forward with another weight reader.
 #include "ofx_internal.h"
 #include "ofx_arena.h"
 
@@ -156,12 +158,21 @@ __device__ __forceinline__ void pop_walk(const unsigned *sb, const unsigned *lb,
   drain();
 }
 
-// Neural_network.feed of genome `gen` on ship s of arena a, by one 256-thread workgroup; returns the row of `act` that
-// holds the four outputs.  KEEP = false (k_pop_act): two rows, layer l's activations in row l & 1.  KEEP = true
-// (k_pop_grad): a row per layer, a_{l+1} in row l, and the 8-scalar head of the observation in `head`.
-template <bool KEEP>
+// How pop_forward reads a weight, stated per caller: first(k, o) is W_1[o][k] at storage position k * n1 + o, at(s) the
+// storage position s behind the first layer (there s is the element index).  pop_stored reads the genome as it lies in
+// HBM (k_pop_act, k_pop_grad, the centre in k_es_act); es_member, further down, adds the member's noise to it.
+struct pop_stored {
+  const double *gen;
+  __device__ __forceinline__ double first(size_t k, int o, int n1) const { return gen[k * n1 + o]; }
+  __device__ __forceinline__ double at(size_t s) const { return gen[s]; }
+};
+
+// Neural_network.feed of the genome `rd` reads on ship s of arena a, by one 256-thread workgroup; returns the row of
+// `act` that holds the four outputs.  KEEP = false (k_pop_act, k_es_act): two rows, layer l's activations in row l & 1.
+// KEEP = true (k_pop_grad): a row per layer, a_{l+1} in row l, and the 8-scalar head of the observation in `head`.
+template <bool KEEP, class Read>
 __device__ __forceinline__ int pop_forward(int s, int a, int W, int H, const ofx_state &st, const unsigned *ship_bits,
-                                           const unsigned *laser_bits, int words, const double *gen, uint32_t first,
+                                           const unsigned *laser_bits, int words, const Read &rd, uint32_t first,
                                            uint32_t n_w, const pop_net &net, uint32_t (*list)[POP_LIST],
                                            double (*part)[64], double (*act)[POP_MAX_WIDTH], double *head) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -179,11 +190,11 @@ __device__ __forceinline__ int pop_forward(int s, int a, int W, int H, const ofx
       for (; i + 7 * groups < count; i += 8 * groups) {
         double t[8];
 #pragma unroll
-        for (int q = 0; q < 8; q++) t[q] = gen[(size_t)(8u + mine[i + q * groups]) * n1 + o];
+        for (int q = 0; q < 8; q++) t[q] = rd.first(8u + mine[i + q * groups], o, n1);
 #pragma unroll
         for (int q = 0; q < 8; q++) acc += t[q];
       }
-      for (; i < count; i += groups) acc += gen[(size_t)(8u + mine[i]) * n1 + o];
+      for (; i < count; i += groups) acc += rd.first(8u + mine[i], o, n1);
     }
   });
   part[wv][lane] = gathers ? acc : 0.0;
@@ -196,12 +207,12 @@ __device__ __forceinline__ int pop_forward(int s, int a, int W, int H, const ofx
 #pragma unroll
       for (int k = 0; k < 8; k++) head[k] = v[k];
     }
-    double z = gen[tid] * v[0];
+    double z = rd.first(0, tid, n1) * v[0];
 #pragma unroll
-    for (int k = 1; k < 8; k++) z += gen[(size_t)k * n1 + tid] * v[k];
+    for (int k = 1; k < 8; k++) z += rd.first(k, tid, n1) * v[k];
     for (int q = 0; q < 4; q++)
       for (int j = 0; j < groups; j++) z += part[q][j * n1 + tid];
-    act[0][tid] = pop_sigmoid(z + gen[n_w + tid]);
+    act[0][tid] = pop_sigmoid(z + rd.at(n_w + tid));
   }
   __syncthreads();
   uint32_t woff = first, boff = n_w + (uint32_t)n1;
@@ -210,10 +221,10 @@ __device__ __forceinline__ int pop_forward(int s, int a, int W, int H, const ofx
     const int nin = net.layers[l], nout = net.layers[l + 1];
     const int nxt = KEEP ? l : cur ^ 1;
     if (tid < nout) {
-      const double *w = gen + woff + (size_t)tid * nin;
+      const size_t w = woff + (size_t)tid * nin;
       double z = 0.0;
-      for (int k = 0; k < nin; k++) z += w[k] * act[cur][k];
-      act[nxt][tid] = pop_sigmoid(z + gen[boff + tid]);
+      for (int k = 0; k < nin; k++) z += rd.at(w + k) * act[cur][k];
+      act[nxt][tid] = pop_sigmoid(z + rd.at(boff + tid));
     }
     __syncthreads();
     woff += (uint32_t)(nin * nout);
@@ -250,8 +261,9 @@ __global__ __launch_bounds__(256) void k_pop_act(int M, int W, int H, ofx_state 
   const int s = blockIdx.x, a = s / M;
   const int32_t g = genome_of[s];
   if (g < 0 || (long long)g >= P || !st.alive[s]) return;  // uniform over the workgroup
-  const int cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, data + (size_t)g * G, first, n_w, net,
-                                     list, part, act, nullptr);
+  const pop_stored rd = {data + (size_t)g * G};
+  const int cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, rd, first, n_w, net, list, part, act,
+                                     nullptr);
   pop_emit(s, W, H, act[cur], actions, y);
 }
 
@@ -283,7 +295,8 @@ __global__ __launch_bounds__(256) void k_pop_grad(int M, int W, int H, ofx_state
   const int32_t g = genome_of[s];
   if (g < 0 || (long long)g >= P || !st.alive[s]) return;  // uniform over the workgroup
   const double *gen = data + (size_t)g * G;
-  const int top = pop_forward<true>(s, a, W, H, st, ship_bits, laser_bits, words, gen, first, n_w, net, list, part, act,
+  const pop_stored rd = {gen};
+  const int top = pop_forward<true>(s, a, W, H, st, ship_bits, laser_bits, words, rd, first, n_w, net, list, part, act,
                                     head);
   pop_emit(s, W, H, act[top], actions, y);
   if (learn_mask && !learn_mask[s]) return;                // uniform over the workgroup
@@ -484,33 +497,44 @@ static int need_population(ofx_handle *h, const char *who, ofx_population **out)
   return OFX_OK;
 }
 
-extern "C" int ofx_population_create(ofx_handle *h, const int32_t *layers, int32_t n_layers, int64_t P) {
-  if (!h || !layers) { ofx_set_error("ofx_population_create: null argument"); return OFX_ERR_INVALID; }
-  if (pop_of(h)) { ofx_set_error("ofx_population_create: the handle already holds a population (ofx_population_destroy)"); return OFX_ERR_STATE; }
+// the topologies a genome can have on this handle, stated once for ofx_population_create and ofx_es_create (`who`);
+// n_w, n_b: the weights and biases of one genome
+static int check_topology(ofx_handle *h, const char *who, const int32_t *layers, int32_t n_layers,
+                          unsigned long long *n_w, unsigned long long *n_b) {
   if (n_layers < 2 || n_layers > POP_MAX_LAYERS) {
-    ofx_set_error("ofx_population_create: need 2..%d layers (got %d)", POP_MAX_LAYERS, n_layers);
+    ofx_set_error("%s: need 2..%d layers (got %d)", who, POP_MAX_LAYERS, n_layers);
     return OFX_ERR_INVALID;
   }
   const ofx_config &c = h->cfg;
   const long long nin = 8 + 2ll * c.width * c.height;
   if (layers[0] != nin) {
-    ofx_set_error("ofx_population_create: layers[0] must be 8 + 2*W*H = %lld (got %d)", nin, layers[0]);
+    ofx_set_error("%s: layers[0] must be 8 + 2*W*H = %lld (got %d)", who, nin, layers[0]);
     return OFX_ERR_INVALID;
   }
   if (layers[n_layers - 1] != 4) {
-    ofx_set_error("ofx_population_create: the last layer must have 4 outputs, the reference's Action.size (got %d)",
+    ofx_set_error("%s: the last layer must have 4 outputs, the reference's Action.size (got %d)", who,
                   layers[n_layers - 1]);
     return OFX_ERR_INVALID;
   }
   for (int i = 1; i < n_layers; i++)
     if (layers[i] < 1 || layers[i] > POP_MAX_WIDTH) {
-      ofx_set_error("ofx_population_create: layer %d must be 1..%d wide (got %d)", i, POP_MAX_WIDTH, layers[i]);
+      ofx_set_error("%s: layer %d must be 1..%d wide (got %d)", who, i, POP_MAX_WIDTH, layers[i]);
       return OFX_ERR_INVALID;
     }
+  *n_w = *n_b = 0;
+  for (int i = 0; i + 1 < n_layers; i++) { *n_w += (unsigned long long)layers[i] * layers[i + 1]; *n_b += layers[i + 1]; }
+  if (*n_w + *n_b >= (1ull << 32)) { ofx_set_error("%s: a genome of %llu elements", who, *n_w + *n_b); return OFX_ERR_INVALID; }
+  return OFX_OK;
+}
+
+extern "C" int ofx_population_create(ofx_handle *h, const int32_t *layers, int32_t n_layers, int64_t P) {
+  if (!h || !layers) { ofx_set_error("ofx_population_create: null argument"); return OFX_ERR_INVALID; }
+  if (pop_of(h)) { ofx_set_error("ofx_population_create: the handle already holds a population (ofx_population_destroy)"); return OFX_ERR_STATE; }
+  unsigned long long n_w, n_b;
+  const int rc = check_topology(h, "ofx_population_create", layers, n_layers, &n_w, &n_b);
+  if (rc) return rc;
   if (P < 1 || P > 0x7fffffffll) { ofx_set_error("ofx_population_create: P must be in [1, 2^31) (got %lld)", (long long)P); return OFX_ERR_INVALID; }
-  unsigned long long n_w = 0, n_b = 0;
-  for (int i = 0; i + 1 < n_layers; i++) { n_w += (unsigned long long)layers[i] * layers[i + 1]; n_b += layers[i + 1]; }
-  if (n_w + n_b >= (1ull << 32)) { ofx_set_error("ofx_population_create: a genome of %llu elements", n_w + n_b); return OFX_ERR_INVALID; }
+  const ofx_config &c = h->cfg;
   OFX_HIP(hipSetDevice(c.device));
   ofx_population *p = new (std::nothrow) ofx_population();
   if (!p) { ofx_set_error("ofx_population_create: out of host memory"); return OFX_ERR_INVALID; }
@@ -545,12 +569,13 @@ extern "C" int ofx_population_destroy(ofx_handle *h) {
   return OFX_OK;
 }
 
-static int launch_breed(ofx_handle *h, ofx_population *p, const int32_t *jobs, int n_jobs, double evo, double mut,
-                        uint64_t seed, uint32_t generation) {
+// k_pop_breed on the genomes at `data`, each G elements of the topology `layers` (the population's, or the ES centre)
+static int launch_breed(ofx_handle *h, double *data, uint32_t G, uint32_t first, const int32_t *layers,
+                        const int32_t *jobs, int n_jobs, double evo, double mut, uint64_t seed, uint32_t generation) {
   if (n_jobs < 1) return OFX_OK;
-  const dim3 grid((p->G + 255u) / 256u, (unsigned)(n_jobs < 65535 ? n_jobs : 65535));
-  hipLaunchKernelGGL(k_pop_breed, grid, dim3(256), 0, h->stream, p->data, jobs, n_jobs, p->G, p->first,
-                     (uint32_t)p->layers[0], (uint32_t)p->layers[1], evo, mut, ofx_key(seed), generation);
+  const dim3 grid((G + 255u) / 256u, (unsigned)(n_jobs < 65535 ? n_jobs : 65535));
+  hipLaunchKernelGGL(k_pop_breed, grid, dim3(256), 0, h->stream, data, jobs, n_jobs, G, first, (uint32_t)layers[0],
+                     (uint32_t)layers[1], evo, mut, ofx_key(seed), generation);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }
@@ -560,7 +585,7 @@ extern "C" int ofx_population_init(ofx_handle *h, uint64_t seed, uint32_t genera
   int rc = need_population(h, "ofx_population_init", &p);
   if (rc) return rc;
   OFX_HIP(hipSetDevice(h->cfg.device));
-  return launch_breed(h, p, nullptr, (int)p->P, 0.0, 0.0, seed, generation);
+  return launch_breed(h, p->data, p->G, p->first, p->layers, nullptr, (int)p->P, 0.0, 0.0, seed, generation);
 }
 
 // host <-> storage order of one genome: the first layer is transposed, the rest is the element order
@@ -570,21 +595,40 @@ static int check_slot(ofx_population *p, const char *who, int64_t slot, const vo
   return OFX_OK;
 }
 
+// one genome in storage order at `src` -> the element order on the host (weights, then biases), and back; both wait
+// for the handle's stream.  Stated once for the population's slots and the ES centre and members.
+static int genome_to_host(ofx_handle *h, const double *src, const int32_t *layers, uint32_t first, uint32_t n_w,
+                          uint32_t G, double *weights_host, double *biases_host) {
+  std::vector<double> tmp(first);
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  OFX_HIP(hipMemcpy(tmp.data(), src, (size_t)first * sizeof(double), hipMemcpyDeviceToHost));
+  OFX_HIP(hipMemcpy(weights_host + first, src + first, (size_t)(n_w - first) * sizeof(double), hipMemcpyDeviceToHost));
+  OFX_HIP(hipMemcpy(biases_host, src + n_w, (size_t)(G - n_w) * sizeof(double), hipMemcpyDeviceToHost));
+  const size_t nin = (size_t)layers[0], n1 = (size_t)layers[1];
+  for (size_t k = 0; k < nin; k++)
+    for (size_t o = 0; o < n1; o++) weights_host[o * nin + k] = tmp[k * n1 + o];
+  return OFX_OK;
+}
+
+static int genome_from_host(ofx_handle *h, double *dst, const int32_t *layers, uint32_t first, uint32_t n_w, uint32_t G,
+                            const double *weights_host, const double *biases_host) {
+  std::vector<double> tmp(first);
+  const size_t nin = (size_t)layers[0], n1 = (size_t)layers[1];
+  for (size_t k = 0; k < nin; k++)
+    for (size_t o = 0; o < n1; o++) tmp[k * n1 + o] = weights_host[o * nin + k];
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  OFX_HIP(hipMemcpy(dst, tmp.data(), (size_t)first * sizeof(double), hipMemcpyHostToDevice));
+  OFX_HIP(hipMemcpy(dst + first, weights_host + first, (size_t)(n_w - first) * sizeof(double), hipMemcpyHostToDevice));
+  OFX_HIP(hipMemcpy(dst + n_w, biases_host, (size_t)(G - n_w) * sizeof(double), hipMemcpyHostToDevice));
+  return OFX_OK;
+}
+
 extern "C" int ofx_population_get(ofx_handle *h, int64_t slot, double *weights_host, double *biases_host) {
   ofx_population *p;
   int rc = need_population(h, "ofx_population_get", &p);
   if (rc || (rc = check_slot(p, "ofx_population_get", slot, weights_host, biases_host))) return rc;
   OFX_HIP(hipSetDevice(h->cfg.device));
-  std::vector<double> tmp(p->first);
-  const double *src = p->data + (size_t)slot * p->G;
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  OFX_HIP(hipMemcpy(tmp.data(), src, (size_t)p->first * sizeof(double), hipMemcpyDeviceToHost));
-  OFX_HIP(hipMemcpy(weights_host + p->first, src + p->first, (size_t)(p->n_w - p->first) * sizeof(double), hipMemcpyDeviceToHost));
-  OFX_HIP(hipMemcpy(biases_host, src + p->n_w, (size_t)(p->G - p->n_w) * sizeof(double), hipMemcpyDeviceToHost));
-  const size_t nin = (size_t)p->layers[0], n1 = (size_t)p->layers[1];
-  for (size_t k = 0; k < nin; k++)
-    for (size_t o = 0; o < n1; o++) weights_host[o * nin + k] = tmp[k * n1 + o];
-  return OFX_OK;
+  return genome_to_host(h, p->data + (size_t)slot * p->G, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
 }
 
 extern "C" int ofx_population_set(ofx_handle *h, int64_t slot, const double *weights_host, const double *biases_host) {
@@ -592,16 +636,7 @@ extern "C" int ofx_population_set(ofx_handle *h, int64_t slot, const double *wei
   int rc = need_population(h, "ofx_population_set", &p);
   if (rc || (rc = check_slot(p, "ofx_population_set", slot, weights_host, biases_host))) return rc;
   OFX_HIP(hipSetDevice(h->cfg.device));
-  std::vector<double> tmp(p->first);
-  const size_t nin = (size_t)p->layers[0], n1 = (size_t)p->layers[1];
-  for (size_t k = 0; k < nin; k++)
-    for (size_t o = 0; o < n1; o++) tmp[k * n1 + o] = weights_host[o * nin + k];
-  double *dst = p->data + (size_t)slot * p->G;
-  OFX_HIP(hipStreamSynchronize(h->stream));
-  OFX_HIP(hipMemcpy(dst, tmp.data(), (size_t)p->first * sizeof(double), hipMemcpyHostToDevice));
-  OFX_HIP(hipMemcpy(dst + p->first, weights_host + p->first, (size_t)(p->n_w - p->first) * sizeof(double), hipMemcpyHostToDevice));
-  OFX_HIP(hipMemcpy(dst + p->n_w, biases_host, (size_t)(p->G - p->n_w) * sizeof(double), hipMemcpyHostToDevice));
-  return OFX_OK;
+  return genome_from_host(h, p->data + (size_t)slot * p->G, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
 }
 
 extern "C" int ofx_population_breed(ofx_handle *h, const int32_t *plan_host, double evolution_rate, double mutation_rate,
@@ -635,7 +670,8 @@ extern "C" int ofx_population_breed(ofx_handle *h, const int32_t *plan_host, dou
   OFX_HIP(hipSetDevice(h->cfg.device));
   OFX_HIP(hipStreamSynchronize(h->stream));  // the last breed may still read the job list
   OFX_HIP(hipMemcpy(p->jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  return launch_breed(h, p, p->jobs, (int)(jobs.size() / 2), evolution_rate, mutation_rate, seed, generation);
+  return launch_breed(h, p->data, p->G, p->first, p->layers, p->jobs, (int)(jobs.size() / 2), evolution_rate,
+                      mutation_rate, seed, generation);
 }
 
 extern "C" int ofx_population_act(ofx_handle *h, const int32_t *genome_of, ofx_action *actions, double *y) {
@@ -738,6 +774,329 @@ extern "C" int ofx_population_fitness(ofx_handle *h, const int32_t *genome_of, i
   const int NM = h->cfg.n_arenas * h->cfg.n_ships;
   hipLaunchKernelGGL(k_pop_fitness, dim3((NM + 255) / 256), dim3(256), 0, h->stream, NM, (long long)p->P,
                      h->st.last_score, genome_of, (unsigned long long *)sum, count);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ---- evolution strategies: a population that is never stored (include/ofx.h, "evolution strategies") ----------------
+// One centre genome theta of G doubles in the storage layout above.  Member m = 2i + b of P = 2 n_pairs is
+// theta + (+-sigma) * eps(i, e), eps a pure function of (seed, pair, element, generation) on stream 12; member P is
+// theta itself.  Nothing of a member is ever kept: the forward regenerates the noise of the rows it gathers, the
+// generation step is one pass over theta.
+//
+// k_es_act     k_pop_act's launch shape and bodies (pop_walk, pop_forward, pop_emit: each still exists once) with the
+//              es_member reader: one Philox evaluation per weight read, set cells x n1 + 8 n1 + the later layers per ship.
+//              Lane layout, list order and the order of every sum are pop_forward's, so a member's y has the bits
+//              k_pop_act gives on a stored genome holding the member's elements.  The centre (member P) goes through
+//              pop_stored: no Philox on that path.
+// k_es_update  one thread per storage position, the loop over the pairs inside: coalesced reads and writes of theta,
+//              (pair, d) read wave-uniformly, the sum in ascending pair order in a register.  No floating-point atomics.
+//              Compute-bound on Philox by design: G x n_pairs evaluations against 16 G bytes.
+// k_es_member  a member materialised into a G-double buffer, for ofx_es_member.
+struct ofx_es {
+  int n_layers;
+  int32_t layers[POP_MAX_LAYERS];
+  uint32_t G, first, n_w;   // as in ofx_population
+  double *theta;            // [G] the centre
+  double *member;           // [G] ofx_es_member's buffer, allocated at its first call
+  double *d;                // [d_cap] the nonzero pair weights of the running ofx_es_update, ascending pair order
+  uint32_t *d_pair;         // [d_cap] their pairs
+  size_t d_cap;
+};
+
+// eps(i, e): the four stream-12 words of (pair, element, generation) summed, centred and scaled to (-2, 2).  The words
+// are below 2^32 and their sum below 2^34, so the float64 sum IS the integer sum, and so are the difference from
+// 2^33 - 2 and the scaling by 2^-32: every step is exact, no rounding and no libm between here and the oracle.
+__host__ __device__ inline double es_eps(uint32_t pair, uint32_t e, uint32_t generation, ofx_rng_key key) {
+  uint32_t r[4];
+  ofx_philox4x32_10(pair, e, generation, OFX_ES_STREAM, key, r);
+  const double S = ((double)r[0] + (double)r[1]) + ((double)r[2] + (double)r[3]);
+  return (S - 8589934590.0) * 0x1p-32;
+}
+
+// pop_forward's reader for member 2 * pair + b of the centre `theta`: w = theta + (ss * eps), ss = +sigma or -sigma, the
+// product rounded, then the sum (the library is built with -ffp-contract=off).  In the first layer storage position
+// k * n1 + o is element o * nin + k; behind it the position is the element.
+struct es_member {
+  const double *theta;
+  uint32_t nin, pair, generation;
+  ofx_rng_key key;
+  double ss;
+  __device__ __forceinline__ double noisy(double w, uint32_t e) const {
+    const double t = ss * es_eps(pair, e, generation, key);
+    return w + t;
+  }
+  __device__ __forceinline__ double first(size_t k, int o, int n1) const {
+    return noisy(theta[k * n1 + o], (uint32_t)o * nin + (uint32_t)k);
+  }
+  __device__ __forceinline__ double at(size_t s) const { return noisy(theta[s], (uint32_t)s); }
+};
+
+__global__ __launch_bounds__(256) void k_es_act(int M, int W, int H, ofx_state st, const unsigned *ship_bits,
+                                                const unsigned *laser_bits, int words, const double *theta, int P,
+                                                uint32_t first, uint32_t n_w, pop_net net, double sigma, ofx_rng_key key,
+                                                uint32_t generation, const int32_t *member_of, ofx_action *actions,
+                                                double *y) {
+  __shared__ uint32_t list[4][POP_LIST];
+  __shared__ double part[4][64];
+  __shared__ double act[2][POP_MAX_WIDTH];
+  const int s = blockIdx.x, a = s / M;
+  const int32_t m = member_of[s];
+  if (m < 0 || m > P || !st.alive[s]) return;              // uniform over the workgroup
+  int cur;
+  if (m == P) {                                            // the centre: the stored-genome path, no Philox
+    const pop_stored rd = {theta};
+    cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, rd, first, n_w, net, list, part, act, nullptr);
+  } else {
+    const es_member rd = {theta, (uint32_t)net.layers[0], (uint32_t)m >> 1, generation, key, (m & 1) ? -sigma : sigma};
+    cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, rd, first, n_w, net, list, part, act, nullptr);
+  }
+  pop_emit(s, W, H, act[cur], actions, y);
+}
+
+// out[s] = member `m` of P at storage position s (m == P: the centre)
+__global__ __launch_bounds__(256) void k_es_member(const double *theta, double *out, uint32_t G, uint32_t first,
+                                                   uint32_t nin, uint32_t n1, int m, int P, double sigma,
+                                                   ofx_rng_key key, uint32_t generation) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= G) return;
+  double w = theta[s];
+  if (m != P) {
+    const double ss = (m & 1) ? -sigma : sigma;
+    const double t = ss * es_eps((uint32_t)m >> 1, pop_element(s, first, nin, n1), generation, key);
+    w = w + t;
+  }
+  out[s] = w;
+}
+
+// theta[e] += scale * (sum over the listed pairs, in list order, of d * eps(pair, e)): every product and sum rounded on
+// its own, the sum kept in a register.  The list holds the pairs with d != 0 in ascending order (ofx_es_update).
+__global__ __launch_bounds__(256) void k_es_update(double *theta, const double *__restrict__ d,
+                                                   const uint32_t *__restrict__ d_pair, int n, uint32_t G,
+                                                   uint32_t first, uint32_t nin, uint32_t n1, double scale,
+                                                   ofx_rng_key key, uint32_t generation) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= G) return;
+  const uint32_t e = pop_element(s, first, nin, n1);
+  double g = 0.0;
+#pragma unroll 4
+  for (int j = 0; j < n; j++) {                            // d[j], d_pair[j]: the same address in every lane
+    const double t = d[j] * es_eps(d_pair[j], e, generation, key);
+    g = g + t;
+  }
+  const double step = scale * g;
+  theta[s] = theta[s] + step;
+}
+
+static ofx_es *&es_of(ofx_handle *h) { return h->es; }
+
+static pop_net net_of(const ofx_es *p) {
+  pop_net net;
+  net.n_layers = p->n_layers;
+  for (int i = 0; i < POP_MAX_LAYERS; i++) net.layers[i] = i < p->n_layers ? p->layers[i] : 0;
+  return net;
+}
+
+void ofx_es_free(ofx_handle *h) {
+  ofx_es *p = es_of(h);
+  if (!p) return;
+  if (p->theta) (void)hipFree(p->theta);
+  if (p->member) (void)hipFree(p->member);
+  if (p->d) (void)hipFree(p->d);
+  if (p->d_pair) (void)hipFree(p->d_pair);
+  delete p;
+  es_of(h) = nullptr;
+}
+
+static int need_es(ofx_handle *h, const char *who, ofx_es **out) {
+  if (!h) { ofx_set_error("%s: null handle", who); return OFX_ERR_INVALID; }
+  if (!es_of(h)) { ofx_set_error("%s: the handle holds no ES centre (ofx_es_create)", who); return OFX_ERR_STATE; }
+  *out = es_of(h);
+  return OFX_OK;
+}
+
+// P = 2 n_pairs members and their noise scale
+static int check_members(const char *who, int64_t P, double sigma) {
+  if (P < 2 || (P & 1) || P > 0x7ffffffell) {
+    ofx_set_error("%s: P must be even and in [2, 2^31 - 2], two members per pair (got %lld)", who, (long long)P);
+    return OFX_ERR_INVALID;
+  }
+  if (!(sigma - sigma == 0.0) || !(sigma > 0.0)) {
+    ofx_set_error("%s: sigma must be finite and > 0 (got %g)", who, sigma);
+    return OFX_ERR_INVALID;
+  }
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_create(ofx_handle *h, const int32_t *layers, int32_t n_layers) {
+  if (!h || !layers) { ofx_set_error("ofx_es_create: null argument"); return OFX_ERR_INVALID; }
+  if (es_of(h)) { ofx_set_error("ofx_es_create: the handle already holds an ES centre (ofx_es_destroy)"); return OFX_ERR_STATE; }
+  unsigned long long n_w, n_b;
+  const int rc = check_topology(h, "ofx_es_create", layers, n_layers, &n_w, &n_b);
+  if (rc) return rc;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  ofx_es *p = new (std::nothrow) ofx_es();
+  if (!p) { ofx_set_error("ofx_es_create: out of host memory"); return OFX_ERR_INVALID; }
+  p->n_layers = n_layers;
+  for (int i = 0; i < n_layers; i++) p->layers[i] = layers[i];
+  p->G = (uint32_t)(n_w + n_b);
+  p->first = (uint32_t)((unsigned long long)layers[0] * layers[1]);
+  p->n_w = (uint32_t)n_w;
+  p->theta = p->member = p->d = nullptr;
+  p->d_pair = nullptr;
+  p->d_cap = 0;
+  const size_t bytes = (size_t)p->G * sizeof(double);
+  const hipError_t e = hipMalloc((void **)&p->theta, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ofx_set_error("ofx_es_create: allocating %zu bytes for a centre of %u elements failed: %s", bytes, p->G,
+                  hipGetErrorString(e));
+    delete p;
+    return OFX_ERR_HIP;
+  }
+  es_of(h) = p;
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_destroy(ofx_handle *h) {
+  if (!h) { ofx_set_error("ofx_es_destroy: null handle"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  ofx_es_free(h);
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_init(ofx_handle *h, uint64_t seed, uint32_t generation) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_init", &p);
+  if (rc) return rc;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  // the fresh genome of slot 0: k_pop_breed with one job and no job list, as ofx_population_init runs it
+  return launch_breed(h, p->theta, p->G, p->first, p->layers, nullptr, 1, 0.0, 0.0, seed, generation);
+}
+
+extern "C" int ofx_es_get(ofx_handle *h, double *weights_host, double *biases_host) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_get", &p);
+  if (rc) return rc;
+  if (!weights_host || !biases_host) { ofx_set_error("ofx_es_get: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  return genome_to_host(h, p->theta, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
+}
+
+extern "C" int ofx_es_set(ofx_handle *h, const double *weights_host, const double *biases_host) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_set", &p);
+  if (rc) return rc;
+  if (!weights_host || !biases_host) { ofx_set_error("ofx_es_set: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  return genome_from_host(h, p->theta, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
+}
+
+extern "C" int ofx_es_member(ofx_handle *h, int64_t member, int64_t P, double sigma, uint64_t seed, uint32_t generation,
+                             double *weights_host, double *biases_host) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_member", &p);
+  if (rc || (rc = check_members("ofx_es_member", P, sigma))) return rc;
+  if (!weights_host || !biases_host) { ofx_set_error("ofx_es_member: null argument"); return OFX_ERR_INVALID; }
+  if (member < 0 || member > P) {
+    ofx_set_error("ofx_es_member: member %lld outside [0, %lld] (P is the centre)", (long long)member, (long long)P);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if (!p->member) {
+    const hipError_t e = hipMalloc((void **)&p->member, (size_t)p->G * sizeof(double));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      p->member = nullptr;
+      ofx_set_error("ofx_es_member: allocating %zu bytes failed: %s", (size_t)p->G * sizeof(double), hipGetErrorString(e));
+      return OFX_ERR_HIP;
+    }
+  }
+  hipLaunchKernelGGL(k_es_member, dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta, p->member, p->G, p->first,
+                     (uint32_t)p->layers[0], (uint32_t)p->layers[1], (int)member, (int)P, sigma, ofx_key(seed), generation);
+  OFX_HIP(hipGetLastError());
+  return genome_to_host(h, p->member, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
+}
+
+extern "C" int ofx_es_act(ofx_handle *h, const int32_t *member_of, int64_t P, double sigma, uint64_t seed,
+                          uint32_t generation, ofx_action *actions, double *y) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_act", &p);
+  if (rc || (rc = check_members("ofx_es_act", P, sigma))) return rc;
+  if (!member_of || !actions) { ofx_set_error("ofx_es_act: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("You must execute analyse_battleground first."); return OFX_ERR_STATE; }
+  const ofx_config &c = h->cfg;
+  OFX_HIP(hipSetDevice(c.device));
+  if ((rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr))) return rc;
+  const pop_net net = net_of(p);
+  const int words = (int)(((size_t)c.width * c.height) >> 5);
+  hipLaunchKernelGGL(k_es_act, dim3((unsigned)(c.n_arenas * c.n_ships)), dim3(256), 0, h->stream, c.n_ships, c.width,
+                     c.height, h->st, (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0],
+                     (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1], words, p->theta, (int)P, p->first, p->n_w, net, sigma,
+                     ofx_key(seed), generation, member_of, actions, y);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_fitness(ofx_handle *h, const int32_t *member_of, int64_t P, int64_t *sum, int32_t *count,
+                              int32_t reset) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_fitness", &p);
+  if (rc || (rc = check_members("ofx_es_fitness", P, 1.0))) return rc;
+  if (!member_of || !sum || !count) { ofx_set_error("ofx_es_fitness: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_es_fitness before ofx_spawn"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const size_t slots = (size_t)P + 1;                      // slot P: the centre
+  if (reset) {
+    OFX_HIP(hipMemsetAsync(sum, 0, slots * sizeof(int64_t), h->stream));
+    OFX_HIP(hipMemsetAsync(count, 0, slots * sizeof(int32_t), h->stream));
+  }
+  const int NM = h->cfg.n_arenas * h->cfg.n_ships;
+  hipLaunchKernelGGL(k_pop_fitness, dim3((NM + 255) / 256), dim3(256), 0, h->stream, NM, (long long)slots,
+                     h->st.last_score, member_of, (unsigned long long *)sum, count);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_update(ofx_handle *h, const double *d_host, int64_t n_pairs, double scale, uint64_t seed,
+                             uint32_t generation) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_update", &p);
+  if (rc) return rc;
+  if (!d_host) { ofx_set_error("ofx_es_update: null argument"); return OFX_ERR_INVALID; }
+  if (n_pairs < 1 || n_pairs > 0x3fffffffll) {
+    ofx_set_error("ofx_es_update: n_pairs must be in [1, 2^30) (got %lld)", (long long)n_pairs);
+    return OFX_ERR_INVALID;
+  }
+  if (!(scale - scale == 0.0)) { ofx_set_error("ofx_es_update: scale is not finite"); return OFX_ERR_INVALID; }
+  // A pair with d == 0 adds +-0 to a sum that starts at +0.0 and can never be -0.0 (x + (-x) rounds to +0), so leaving
+  // it out changes no bit: ties and incomplete pairs, the common case, cost nothing.
+  std::vector<double> d;
+  std::vector<uint32_t> pair;
+  for (int64_t i = 0; i < n_pairs; i++) {
+    if (!(d_host[i] - d_host[i] == 0.0)) { ofx_set_error("ofx_es_update: d[%lld] is not finite", (long long)i); return OFX_ERR_INVALID; }
+    if (d_host[i] != 0.0) { d.push_back(d_host[i]); pair.push_back((uint32_t)i); }
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));  // the last update may still read the list
+  if (d.size() > p->d_cap) {
+    if (p->d) (void)hipFree(p->d);
+    if (p->d_pair) (void)hipFree(p->d_pair);
+    p->d = nullptr;
+    p->d_pair = nullptr;
+    p->d_cap = 0;
+    OFX_HIP(hipMalloc((void **)&p->d, d.size() * sizeof(double)));
+    OFX_HIP(hipMalloc((void **)&p->d_pair, d.size() * sizeof(uint32_t)));
+    p->d_cap = d.size();
+  }
+  if (!d.empty()) {
+    OFX_HIP(hipMemcpy(p->d, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
+    OFX_HIP(hipMemcpy(p->d_pair, pair.data(), pair.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(k_es_update, dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta, p->d, p->d_pair,
+                     (int)d.size(), p->G, p->first, (uint32_t)p->layers[0], (uint32_t)p->layers[1], scale, ofx_key(seed),
+                     generation);
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }

@@ -41,6 +41,7 @@ struct ofx_state {
 
 struct ofx_replay;  // ofx_replay.hip
 struct ofx_population;  // ofx_evolve.hip
+struct ofx_es;          // ofx_evolve.hip
 
 struct ofx_handle {
   ofx_config cfg;
@@ -98,6 +99,7 @@ struct ofx_handle {
   uint8_t *ar_dead_once;           // [N][M]
   uint8_t *ar_restarted;           // [N]
   ofx_population *population;      // genomes of the neuroevolution (ofx_population_create), null = none
+  ofx_es *es;                      // centre of the evolution strategy (ofx_es_create), null = none
 };
 #define OFX_RING_MAX 65536         /* numbered events of ofx_event_record */
 
@@ -114,6 +116,7 @@ int ofx_policy_results(ofx_handle *h, int32_t **iaction, int32_t **ipointer);
 int ofx_policy_act_values(ofx_handle *h, const float **q_sa, const float **p_sp, const float **v_act, const float **v_ptr);
 void ofx_replay_free(ofx_handle *h);
 void ofx_population_free(ofx_handle *h);
+void ofx_es_free(ofx_handle *h);
 int ofx_replay_episode_reset(ofx_handle *h, const uint8_t *arena_mask);
 // C[M][N] = act(A[M][K] (lda) x B[K][N] (ldb) + bias[N]) on the f32 MFMA (k_gemm_f32, ofx_policy.hip)
 int ofx_launch_gemm(ofx_handle *h, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc,

@@ -20,6 +20,12 @@ enum : uint32_t {
   OFX_STREAM_MUTATE = 10,        // (slot, element, generation): 0, 1 the replacement value of a mutated element
   OFX_STREAM_FRESH = 11,         // (slot, element, generation): 0, 1 a fresh genome's element (ofx_population_init, plan[p] == -1)
 };
+// The evolution strategy's stream, id 12, stated here beside the others and like them nowhere else.  It stands outside
+// the enum above and carries another prefix because tests/test_rng_streams.py holds that enum to exactly the twelve
+// names and ids 0 .. 11; tests/test_es.py holds this id to be 12, distinct from all of those, and defined once.
+enum : uint32_t {
+  OFX_ES_STREAM = 12,            // (pair, element, generation): 0..3 summed, the noise of an ES member's element (ofx_es_act, ofx_es_update)
+};
 
 // Philox4x32-10 (Salmon et al. SC'11); same constants / round structure as the oracle's restatement so both produce
 // one stream.

@@ -1088,3 +1088,53 @@ class ArenaBatch:
         """sum[g] (int64 [P]) += the score every ship flown by genome g banked at the last restart, count[g] (int32 [P])
         += 1 per such ship; reset zeroes both first.  Does not synchronise."""
         nat.check(nat.lib().ofx_population_fitness(self._h, genome_of_ptr, sum_buf.ptr, count_buf.ptr, int(bool(reset))))
+
+    # ------------------------------------------------------------ evolution strategies (include/ofx.h: the contract)
+    def es_create(self, layers):
+        """One ES centre of the scratch MLP `layers` in HBM, beside any population (ofx_es_create; ofighters_amd.es.ES
+        owns these calls)."""
+        l = np.ascontiguousarray(layers, dtype=np.int32)
+        nat.check(nat.lib().ofx_es_create(self._h, l.ctypes.data_as(C.c_void_p), len(l)))
+
+    def es_destroy(self):
+        nat.check(nat.lib().ofx_es_destroy(self._h))
+
+    def es_init(self, seed, generation=0):
+        """The centre becomes the fresh genome of slot 0 (stream 11).  Does not synchronise."""
+        nat.check(nat.lib().ofx_es_init(self._h, seed, int(generation)))
+
+    def es_get(self, n_weights, n_biases):
+        """The centre as (weights float64 [n_weights], biases float64 [n_biases]) in the element order.  Synchronises."""
+        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
+        nat.check(nat.lib().ofx_es_get(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def es_set(self, weights, biases):
+        w, b = np.ascontiguousarray(weights, dtype=np.float64), np.ascontiguousarray(biases, dtype=np.float64)
+        nat.check(nat.lib().ofx_es_set(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+
+    def es_member(self, member, P, sigma, seed, generation, n_weights, n_biases):
+        """Member `member` of P (P: the centre) at `generation`, materialised on the device, as (weights, biases) in the
+        element order.  Synchronises."""
+        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
+        nat.check(nat.lib().ofx_es_member(self._h, int(member), int(P), float(sigma), seed, int(generation),
+                                          w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def es_act(self, member_of_ptr, P, sigma, seed, generation, out_ptr=None, y_ptr=None):
+        """population_act with a member of the ES population per ship: the device int32 [N][M] at member_of_ptr holds
+        values in [-1, P], P = the centre; the noise is regenerated in the kernel.  Does not synchronise."""
+        nat.check(nat.lib().ofx_es_act(self._h, member_of_ptr, int(P), float(sigma), seed, int(generation),
+                                       out_ptr or self._actions.ptr, y_ptr))
+
+    def es_fitness(self, member_of_ptr, P, sum_buf, count_buf, reset=False):
+        """population_fitness over members: sum int64 [P + 1], count int32 [P + 1], slot P the centre.  Does not
+        synchronise."""
+        nat.check(nat.lib().ofx_es_fitness(self._h, member_of_ptr, int(P), sum_buf.ptr, count_buf.ptr, int(bool(reset))))
+
+    def es_update(self, d, scale, seed, generation):
+        """theta[e] += scale * sum_i d[i] * eps(i, e) in ascending pair order (ofx_es_update); d: float64 [P / 2].  Does
+        not wait for the update."""
+        a = np.ascontiguousarray(d, dtype=np.float64)
+        nat.check(nat.lib().ofx_es_update(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], float(scale), seed,
+                                          int(generation)))

@@ -1,0 +1,334 @@
+"""Seeded evolution strategies on the scratch MLP: a population that is never stored (include/ofx.h, "evolution
+strategies").
+
+Not in the reference.  Salimans et al. 2017 (OpenAI-ES) with mirrored sampling: one centre genome theta lives in HBM,
+member m = 2 i + b of the population is theta +- sigma * eps(i, .) with eps a pure function of (seed, pair, element,
+generation) on the project's counter RNG, and a generation ends in a rank-weighted gradient step on theta.  The forward
+regenerates the noise of the rows it gathers inside the kernel, so a population of any P costs one genome of memory.
+
+    pair_weights  fitness sums -> the weight of every mirrored pair (centred average ranks): pure numpy, no randomness
+    ES            owns the ofx_es_* calls of one ArenaBatch
+    ESRollout     the generational loop around ShardedRollout's lock-step
+
+eps has variance 1/3 (an Irwin-Hall sum of four uniforms in (-2, 2)): sigma and lr are in units of that eps.  Whether
+the fitness rises is an observation (tools/es_time.py records it), not a property any test holds the code to.
+"""
+import math
+
+import numpy as np
+
+from .evolution import genome_sizes, join_genome, sidecar_path, split_genome
+from .rollout import ShardedRollout
+
+
+def check_members(P, sigma=None):
+    """P = 2 n_pairs >= 2 members and, when given, a finite sigma > 0: the library's refusals, checked before it is
+    called.  ValueError otherwise; returns int(P)."""
+    if int(P) != P or int(P) < 2 or int(P) % 2:
+        raise ValueError("P must be even and >= 2 (two members per pair), got %r" % (P,))
+    if sigma is not None and not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be finite and > 0, got %r" % (sigma,))
+    return int(P)
+
+
+def check_member_assignment(member_of, N, M, P):
+    """member_of as an int32 [N][M] with every value in [-1, P] (-1: the ship is not evolved, P: the centre);
+    ValueError otherwise."""
+    a = np.asarray(member_of)
+    if a.shape != (int(N), int(M)) or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("member_of is an integer array [%d][%d], got %s %s" % (N, M, a.dtype, a.shape))
+    bad = np.argwhere((a < -1) | (a > P))
+    if bad.size:
+        i, j = bad[0]
+        raise ValueError("member_of[%d][%d] = %d is outside [-1, %d]" % (i, j, a[i, j], P))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def pair_weights(sum, count):
+    """The weight d_i of every mirrored pair from the device's fitness sums: (d float64 [P/2], n_c).
+
+    sum, count: [P] or [P + 1] (slot P, the centre, is ignored).  A pair is COMPLETE when both its members were flown
+    (count > 0); n_c is the number of members of complete pairs.  Those members are ranked by mean fitness sum / count,
+    ascending from 0, with AVERAGE ranks for ties (scores are small integers: ties are the common case), then
+        u_m = r_m / (n_c - 1) - 0.5        d_i = u_{2i} - u_{2i+1}
+    so a tied pair weighs exactly 0, the weights lie in [-1, 1] and swapping a pair's fitness negates its weight.
+    Incomplete pairs get 0; n_c < 2 or all means equal gives all zeros.  Pure numpy, no randomness."""
+    s, c = np.asarray(sum, np.int64), np.asarray(count, np.int64)
+    if s.ndim != 1 or s.shape != c.shape or s.shape[0] < 2:
+        raise ValueError("sum and count are [P] or [P + 1] arrays, got %s and %s" % (s.shape, c.shape))
+    n_pairs = s.shape[0] // 2
+    s, c = s[:2 * n_pairs].reshape(n_pairs, 2), c[:2 * n_pairs].reshape(n_pairs, 2)
+    complete = (c > 0).all(axis=1)
+    n_c = 2 * int(complete.sum())
+    d = np.zeros(n_pairs, np.float64)
+    if n_c < 2:
+        return d, n_c
+    mean = (s[complete] / c[complete]).ravel()
+    values, inverse, counts = np.unique(mean, return_inverse=True, return_counts=True)
+    if values.size == 1:
+        return d, n_c
+    below = np.cumsum(counts) - counts                     # members ranked strictly below each distinct mean
+    rank = (below + (counts - 1) / 2.0)[inverse]           # the average of the ranks a tied group covers
+    u = (rank / (n_c - 1) - 0.5).reshape(-1, 2)
+    d[complete] = u[:, 0] - u[:, 1]
+    return d, n_c
+
+
+def es_meta(layers, seed):
+    return {"layers": [int(v) for v in layers], "seed": int(seed)}
+
+
+def check_es_meta(meta, shape, dtype, layers, seed, path="the checkpoint"):
+    """ES.load's refusals, before the centre is touched: ValueError naming the first field of the sidecar `meta` (or of
+    the array: its shape, its dtype) that differs from this ES's - evolution.check_population_meta without P."""
+    want = es_meta(layers, seed)
+    for field in ("layers", "seed"):
+        if field not in meta:
+            raise ValueError("%s: the sidecar has no field %r" % (path, field))
+        got = [int(v) for v in meta[field]] if field == "layers" else int(meta[field])
+        if got != want[field]:
+            raise ValueError("%s: %s is %r, this ES's is %r" % (path, field, got, want[field]))
+    elements = sum(genome_sizes(layers))
+    if tuple(shape) != (elements,):
+        raise ValueError("%s: shape is %r, a centre of %d elements is %r" % (path, tuple(shape), elements, (elements,)))
+    if np.dtype(dtype) != np.float64:
+        raise ValueError("%s: dtype is %s, a centre is float64" % (path, np.dtype(dtype)))
+
+
+class ES:
+    """One ES centre of the scratch MLP `layers` on the device of `batch` (an ArenaBatch), beside any Population the
+    batch holds; initialised to the fresh genome of slot 0 from `seed` (the law of Population's init).
+
+    Every member's noise is keyed by (seed, pair, element, generation): a run is reproducible, and no member is stored."""
+
+    def __init__(self, batch, layers, seed, init=True):
+        from .engine import DeviceBuffer
+        self.b = batch
+        self.layers = [int(v) for v in layers]
+        self.seed = int(seed)
+        self.n_weights, self.n_biases = genome_sizes(self.layers)
+        batch.es_create(self.layers)
+        self._member_of = DeviceBuffer(batch.N * batch.M * 4)
+        self.P, self.member_of = None, None
+        self._sum = self._count = None
+        if init:
+            self.init()
+
+    def close(self):
+        if self.b is not None:
+            self.b.es_destroy()
+            self.b = None
+
+    # ---------------------------------------------------------------- the centre and its members
+    def init(self, generation=0):
+        self.b.es_init(self.seed, generation)
+
+    def centre(self):
+        """(weights_layers, biases_layers) of the centre: lists of numpy arrays in the reference's shapes."""
+        return split_genome(self.layers, *self.b.es_get(self.n_weights, self.n_biases))
+
+    def set_centre(self, weights_layers, biases_layers):
+        self.b.es_set(*join_genome(self.layers, weights_layers, biases_layers))
+
+    def member(self, m, P, sigma, generation):
+        """(weights_layers, biases_layers) of member m of P at `generation` (m == P: the centre), materialised on the
+        device: what Population.set_genome takes."""
+        P = check_members(P, sigma)
+        if not (0 <= int(m) <= P):
+            raise ValueError("member %d outside [0, %d]" % (m, P))
+        return split_genome(self.layers, *self.b.es_member(m, P, sigma, self.seed, generation, self.n_weights,
+                                                           self.n_biases))
+
+    # ------------------------------------------------------------ the device calls
+    def assign(self, member_of, P):
+        """Which member flies which ship: numpy int [N][M], values in [-1, P] (P: the centre), checked before the upload.
+        The fitness buffers are sized for P + 1 slots; a new P starts them at zero."""
+        from .engine import DeviceBuffer
+        P = check_members(P)
+        a = check_member_assignment(member_of, self.b.N, self.b.M, P)
+        self.b.sync()
+        if P != self.P:
+            self._sum = DeviceBuffer(8 * (P + 1)).upload(np.zeros(P + 1, np.int64))
+            self._count = DeviceBuffer(4 * (P + 1)).upload(np.zeros(P + 1, np.int32))
+            self.P = P
+        self._member_of.upload(a)
+        self.member_of = a
+
+    def _assigned(self):
+        if self.P is None:
+            raise ValueError("no assignment yet: call assign(member_of, P) first")
+
+    def act(self, sigma, generation, y_ptr=None):
+        """Overwrite the evolved ships' entries of the batch's action array (after bot_actions, before step)."""
+        self._assigned()
+        check_members(self.P, sigma)
+        self.b.es_act(self._member_of.ptr, self.P, sigma, self.seed, generation, y_ptr=y_ptr)
+
+    def fitness(self, reset=False):
+        """After a restart: add what every assigned ship banked to its member's sum and count (slot P: the centre)."""
+        self._assigned()
+        self.b.es_fitness(self._member_of.ptr, self.P, self._sum, self._count, reset)
+
+    def fitness_host(self):
+        """(sum int64 [P + 1], count int32 [P + 1]) - what a generation brings to the host.  Synchronises."""
+        self._assigned()
+        self.b.sync()
+        return self._sum.download(np.int64, (self.P + 1,)), self._count.download(np.int32, (self.P + 1,))
+
+    def load_fitness(self, sum, count):
+        """Put back what fitness_host returned (a resumed run)."""
+        self._assigned()
+        s, c = np.asarray(sum, np.int64), np.asarray(count, np.int32)
+        if s.shape != (self.P + 1,) or c.shape != (self.P + 1,):
+            raise ValueError("sum and count are [%d] arrays, got %s and %s" % (self.P + 1, s.shape, c.shape))
+        self.b.sync()
+        self._sum.upload(s)
+        self._count.upload(c)
+
+    def update(self, d, lr, sigma, n_c, generation):
+        """The generation step theta += lr / (n_c sigma) * sum_i d_i eps(i, .) on the noise of `generation`, the one the
+        members flew with; (d, n_c) from pair_weights.  The scale is computed in Python floats, in that order."""
+        d = np.asarray(d, np.float64)
+        if d.ndim != 1 or d.shape[0] < 1 or not np.isfinite(d).all():
+            raise ValueError("d is a finite float64 [P / 2], got %s" % (d.shape,))
+        check_members(2 * d.shape[0], sigma)
+        if int(n_c) < 2 or not math.isfinite(lr):
+            raise ValueError("update needs n_c >= 2 and a finite lr, got n_c = %r, lr = %r" % (n_c, lr))
+        scale = float(lr) / (int(n_c) * float(sigma))
+        self.b.es_update(d, scale, self.seed, generation)
+
+    # ------------------------------------------------------------ checkpoint of the centre
+    def save(self, path):
+        """The centre as ONE .npy at `path`, float64 [n_weights + n_biases] in the element order, and the sidecar
+        `path + ".json"` with layers and seed.  Returns path."""
+        import json
+        w, b = self.b.es_get(self.n_weights, self.n_biases)
+        with open(path, "wb") as f:
+            np.save(f, np.concatenate([w, b]))
+        with open(sidecar_path(path), "w") as f:
+            json.dump(es_meta(self.layers, self.seed), f)
+        return path
+
+    def load(self, path):
+        """The centre `save` wrote, into this ES.  ValueError naming the field, with the centre untouched, when the
+        checkpoint's layers or seed (or the array's shape or dtype) differ from this ES's."""
+        import json
+        with open(sidecar_path(path)) as f:
+            meta = json.load(f)
+        arr = np.load(path)
+        check_es_meta(meta, arr.shape, arr.dtype, self.layers, self.seed, path)
+        self.b.es_set(arr[:self.n_weights], arr[self.n_weights:])
+
+
+class ESRollout(ShardedRollout):
+    """The generational loop of the evolution strategy: every ship of `ships` in every arena is flown by a member of the
+    population of `P` around the centre of `es`, the others by `behaviours`; at each episode end the restart banks the
+    scores and the fitness call adds them per member; every `episodes_per_generation` episodes, in this order: the
+    2 x (P + 1) fitness numbers come to the host, (best, mean) is appended to `fitness_log`, pair_weights turns them into
+    (d, n_c) - kept in `weight_log` - the centre takes its step on the noise of the generation that just flew,
+    generation += 1 and the ships are reassigned.  A generation with fewer than two flown members of complete pairs has
+    nothing to learn from and leaves the centre as it is.
+
+    member_of[a][ships[k]] = ((arena_base + a) * len(ships) + k + generation) % P, as EvolutionRollout assigns genomes;
+    the last `eval_arenas` arenas fly the centre (member P) instead, and their mean banked score per generation goes to
+    `centre_log`.  Runs with observe=False; its policy hook is es.act.  Single GPU: with `dist` set it refuses.
+
+    es  an ES on `engine` (or anything with its assign, act, fitness, fitness_host, update; for state_dict also
+        load_fitness)
+    """
+
+    def __init__(self, engine, es, behaviours, seed, P, sigma, lr, ships=(0,), episodes_per_generation=1, eval_arenas=0,
+                 **kw):
+        if kw.get("dist") is not None:
+            raise ValueError("ESRollout runs on one GPU: `dist` must be None")
+        if kw.get("policy") is not None or kw.get("observe"):
+            raise ValueError("ESRollout sets `policy` and runs with observe=False")
+        self.ships = [int(i) for i in ships]
+        if not self.ships or len(set(self.ships)) != len(self.ships) or not all(0 <= i < engine.M for i in self.ships):
+            raise ValueError("ships must be distinct ship slots in [0, %d), got %r" % (engine.M, list(ships)))
+        self.P = check_members(P, sigma)
+        if not math.isfinite(lr):
+            raise ValueError("lr must be finite, got %r" % (lr,))
+        if int(episodes_per_generation) < 1:
+            raise ValueError("episodes_per_generation must be >= 1, got %r" % (episodes_per_generation,))
+        if int(eval_arenas) != eval_arenas or not (0 <= int(eval_arenas) < engine.N):
+            raise ValueError("eval_arenas must be in [0, %d): an arena must be left to learn from, got %r"
+                             % (engine.N, eval_arenas))
+        kw["observe"] = False
+        super().__init__(engine, behaviours, seed, **kw)
+        self.es = es
+        self.sigma, self.lr = float(sigma), float(lr)
+        self.episodes_per_generation, self.eval_arenas = int(episodes_per_generation), int(eval_arenas)
+        self.generation = 0
+        self.episodes = 0                 # finished episodes of the current generation
+        self.fitness_log = []             # (best mean fitness of a member, mean fitness per evolved ship) per generation
+        self.centre_log = []              # mean banked score of a centre-flown ship per generation (eval_arenas > 0)
+        self.weight_log = []              # (d, n_c) each generation stepped on
+        self.policy = self._fly
+        self._assign()
+
+    def _fly(self, engine):
+        self.es.act(self.sigma, self.generation)
+
+    def assignment(self, generation):
+        """member_of (int32 [N][M]) of `generation` by the formula; the last eval_arenas arenas fly the centre."""
+        e, K = self.e, len(self.ships)
+        g = np.full((e.N, e.M), -1, np.int32)
+        arena = np.arange(e.arena_base, e.arena_base + e.N, dtype=np.int64)
+        for k, ship in enumerate(self.ships):
+            g[:, ship] = (arena * K + k + generation) % self.P
+            if self.eval_arenas:
+                g[e.N - self.eval_arenas:, ship] = self.P
+        return g
+
+    def _assign(self):
+        self.es.assign(self.assignment(self.generation), self.P)
+
+    def _episode_end(self):
+        total = super()._episode_end()
+        self.es.fitness(reset=self.episodes == 0)
+        self.episodes += 1
+        if self.episodes == self.episodes_per_generation:
+            s, c = self.es.fitness_host()
+            ms, mc = s[:self.P], c[:self.P]
+            flown = mc > 0
+            mean = ms[flown] / mc[flown]
+            self.fitness_log.append((float(mean.max()) if flown.any() else float("nan"),
+                                     float(ms.sum()) / float(max(int(mc.sum()), 1))))
+            if self.eval_arenas:
+                self.centre_log.append(float(s[self.P]) / float(c[self.P]) if c[self.P] else float("nan"))
+            d, n_c = pair_weights(s, c)
+            if n_c >= 2:
+                self.es.update(d, self.lr, self.sigma, n_c, self.generation)
+            self.weight_log.append((d, n_c))
+            self.generation += 1
+            self.episodes = 0
+            self._assign()
+        return total
+
+    # ------------------------------------------------------------ stop and go on
+    def state_dict(self):
+        """What a run stopped between two lock-steps needs, beside the centre (ES.save), to go on bit for bit in fresh
+        handles: the generation and episode counters, the logs, the fitness sums and counts of the running generation,
+        the tick and ArenaBatch.state_dict()."""
+        s, c = self.es.fitness_host()
+        return {"generation": self.generation, "episodes": self.episodes, "tick": self.tick,
+                "fitness_log": list(self.fitness_log), "centre_log": list(self.centre_log),
+                "weight_log": [(np.array(d), int(n)) for d, n in self.weight_log],
+                "score_log": [np.array(t) for t in self.score_log], "fitness_sum": s, "fitness_count": c,
+                "engine": self.e.state_dict()}
+
+    def load_state_dict(self, d):
+        """Continue the run state_dict() described, on a freshly constructed ESRollout with the same arguments whose ES
+        already holds the centre (ES.load)."""
+        missing = [k for k in ("generation", "episodes", "tick", "fitness_log", "centre_log", "weight_log", "score_log",
+                               "fitness_sum", "fitness_count", "engine") if k not in d]
+        if missing:
+            raise ValueError("ESRollout.load_state_dict: field %r is missing" % missing[0])
+        self.e.load_state_dict(d["engine"])
+        self.generation, self.episodes, self.tick = int(d["generation"]), int(d["episodes"]), int(d["tick"])
+        self.fitness_log, self.centre_log = list(d["fitness_log"]), list(d["centre_log"])
+        self.weight_log = [(np.array(w), int(n)) for w, n in d["weight_log"]]
+        self.score_log = [np.array(t) for t in d["score_log"]]
+        self._assign()
+        self.es.load_fitness(d["fitness_sum"], d["fitness_count"])

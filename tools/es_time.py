@@ -1,0 +1,174 @@
+"""Seeded evolution strategies at the training size (profiles/r29_es.txt): `--arenas` (4096) arenas x 8 ships, ship 0 of
+every arena flown by a member of the ES population around one centre of the reference's [320008, 9, 4], the seven others
+by `random` bots.
+
+kernels  HIP events on the handle's stream (ofx_event_record / ofx_event_elapsed), one event pair per call, ONE handle
+         that holds the ES centre AND a stored population of `--stored` (512) genomes, on the scene of
+         tools/evolution_time.py (same seed, 40 lock-steps of the bots, lasers in flight).  `--repeats` (3) times,
+         alternating: a block of `--calls` (50) calls of
+           (a) ofx_es_act with member_of[a][0] = a % P at P = `--small` (4096) and at P = `--large` (32768: one member
+               per arena and no member twice), and with every evolved ship on the centre (member P: the path without
+               Philox);
+           (b) ofx_population_act on the stored population, genome_of[a][0] = a % 512: the yardstick;
+         (each call = the 1-bit rasteriser and the one forward launch), then (c) one ofx_es_update per P with a weight on
+         EVERY pair (the worst case: ties and incomplete pairs are left out by the library).  Reported: us per call
+         (mean of each block), the ratio es_act / population_act, the Philox evaluations one es_act makes (per live
+         evolved ship: set cells x n1 + 8 n1 + the later layers and biases), ms per update and the Philox evaluations
+         per second it reaches (elements x pairs / time).
+loop     ESRollout at P = `--small`, sigma 0.05, lr 0.1, `--eval-arenas` (64) arenas on the centre, `--generations` (5)
+         generations of one 200-lock-step episode each; a host clock around every generation (its lock-steps, the
+         restart, the fitness download, pair_weights and the update), ending in a synchronise.  Reported: ms per
+         lock-step and arena-steps/s per generation, fitness_log and centre_log.  Whether they rise is an observation of
+         this run, not something any test holds the code to.
+Each mode prints one JSON line and, with `--out FILE`, appends it to that file.
+Usage: python tools/es_time.py kernels|loop [--arenas 4096] [--small 4096] [--large 32768] [--stored 512] [--calls 50]
+                               [--repeats 3] [--generations 5] [--eval-arenas 64] [--out FILE]
+
+One GPU step per process, each under its own time limit, chained so that a failure ends the chain:
+    timeout -k 10 400 python tools/es_time.py kernels --out profiles/r29_es.txt \\
+    && timeout -k 10 400 python tools/es_time.py loop --out profiles/r29_es.txt"""
+import json
+import os
+import sys
+import time
+
+
+def _arg(name, default):
+    return type(default)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+
+from ofighters_amd import ArenaBatch, DeviceBuffer, _native as nat
+from ofighters_amd.es import ES, ESRollout
+from ofighters_amd.evolution import Population
+
+M, SEED = 8, 0x0F160123
+ARENAS = _arg("--arenas", 4096)
+LAYERS = [320008, 9, 4]
+SIGMA, LR = 0.05, 0.1
+G = sum(LAYERS[i] * LAYERS[i + 1] + LAYERS[i + 1] for i in range(len(LAYERS) - 1))
+_POPCOUNT = np.array([bin(v).count("1") for v in range(256)], np.uint8)
+
+
+class _Timer:
+    def __init__(self, b):
+        self.b, self.next_event = b, 0
+
+    def __call__(self, fn, calls):
+        """Mean us per call of `calls` calls of fn, one event pair each."""
+        e0 = self.next_event
+        for j in range(calls):
+            self.b.event_record(e0 + 2 * j)
+            fn()
+            self.b.event_record(e0 + 2 * j + 1)
+        self.b.sync()
+        self.next_event = e0 + 2 * calls
+        return float(np.mean([self.b.event_elapsed(e0 + 2 * j, e0 + 2 * j + 1) for j in range(calls)])) * 1e3
+
+
+def _assignment(P, centre=False):
+    g = np.full((ARENAS, M), -1, np.int32)
+    g[:, 0] = P if centre else np.arange(ARENAS) % P
+    return DeviceBuffer(g.nbytes).upload(g)
+
+
+def kernels():
+    calls, repeats = _arg("--calls", 50), _arg("--repeats", 3)
+    sizes = [_arg("--small", 4096), _arg("--large", 32768)]
+    stored = _arg("--stored", 512)
+    b = ArenaBatch(ARENAS, M)
+    b.spawn_random(SEED)
+    b.rollout(["random"] * M, SEED, 0, 40)
+    es = ES(b, LAYERS, SEED)
+    pop = Population(b, LAYERS, stored, SEED)
+    g = np.full((ARENAS, M), -1, np.int32)
+    g[:, 0] = np.arange(ARENAS) % stored
+    pop.assign(g)
+    b.bot_actions(["random"] * M, SEED, tick=40)
+    b.sync()
+    members = {P: _assignment(P) for P in sizes}
+    centre = _assignment(sizes[0], centre=True)
+    timed = _Timer(b)
+
+    def es_act(buf, P):
+        return lambda: b.es_act(buf.ptr, P, SIGMA, SEED, 1)
+
+    for P in sizes:                                             # warm-up: the first calls allocate the maps
+        timed(es_act(members[P], P), 5)
+    timed(es_act(centre, sizes[0]), 5)
+    timed(pop.act, 5)
+    act_us, centre_us, pop_us = {P: [] for P in sizes}, [], []
+    update_ms = {P: [] for P in sizes}
+    rs = np.random.RandomState(0)
+    generation = 1
+    for _ in range(repeats):
+        for P in sizes:
+            act_us[P].append(round(timed(es_act(members[P], P), calls), 2))
+        centre_us.append(round(timed(es_act(centre, sizes[0]), calls), 2))
+        pop_us.append(round(timed(pop.act, calls), 2))
+        for P in sizes:
+            d = rs.uniform(0.01, 1.0, P // 2) * rs.choice([-1.0, 1.0], P // 2)     # a weight on every pair
+            gen = generation
+            update_ms[P].append(round(timed(lambda: b.es_update(d, LR / (P * SIGMA), SEED, gen), 1) / 1e3, 3))
+            generation += 1
+    alive = b.get(nat.F_SHIP_ALIVE)[:, 0] != 0
+    sm, lm = b.maps_host(nat.MAP_BITS)
+    cells = _POPCOUNT[sm].sum(axis=1, dtype=np.int64) + _POPCOUNT[lm].sum(axis=1, dtype=np.int64)
+    later = G - LAYERS[0] * LAYERS[1]
+    philox_per_act = int((cells[alive] * LAYERS[1]).sum() + int(alive.sum()) * (8 * LAYERS[1] + later))
+    pop_mean = float(np.mean(pop_us))
+    out = {"what": "kernels", "arenas": ARENAS, "ships": M, "layers": LAYERS, "elements": G, "calls_per_block": calls,
+           "sigma": SIGMA, "stored_population": stored, "population_act_us": pop_us, "es_act_centre_us": centre_us,
+           "es_act_centre_over_population_act": round(float(np.mean(centre_us)) / pop_mean, 3),
+           "evolved_live_ships": int(alive.sum()), "mean_set_cells_per_arena": round(float(cells.mean()), 1),
+           "es_act_philox_evaluations": philox_per_act, "sizes": []}
+    for P in sizes:
+        act_s, upd_s = float(np.mean(act_us[P])) * 1e-6, float(np.mean(update_ms[P])) * 1e-3
+        out["sizes"].append({
+            "P": P, "es_act_us": act_us[P], "es_act_over_population_act": round(float(np.mean(act_us[P])) / pop_mean, 3),
+            "es_act_philox_per_s": round(philox_per_act / act_s, 1),
+            "update_ms": update_ms[P], "update_pairs": P // 2, "update_philox_evaluations": G * (P // 2),
+            "update_philox_per_s": round(G * (P // 2) / upd_s, 1)})
+    b.close()
+    return out
+
+
+def loop():
+    P, generations, eval_arenas = _arg("--small", 4096), _arg("--generations", 5), _arg("--eval-arenas", 64)
+    b = ArenaBatch(ARENAS, M)
+    es = ES(b, LAYERS, SEED)
+    T = b.cfg.episode_ticks
+    roll = ESRollout(b, es, ["random"] * M, SEED, P, SIGMA, LR, ships=(0,), eval_arenas=eval_arenas, episode_ticks=T)
+    roll.run(1)                                                # the episode-end check stands at the head of a lock-step
+    ms = []
+    for _ in range(generations):
+        b.sync()
+        t0 = time.perf_counter()
+        roll.run(T)
+        b.sync()
+        ms.append((time.perf_counter() - t0) * 1e3 / T)
+    out = {"what": "loop", "arenas": ARENAS, "ships": M, "layers": LAYERS, "P": P, "sigma": SIGMA, "lr": LR,
+           "eval_arenas": eval_arenas, "episode_ticks": T, "generations": roll.generation,
+           "ms_per_lock_step": [round(x, 4) for x in ms], "mean_ms_per_lock_step": round(float(np.mean(ms)), 4),
+           "arena_steps_per_s": round(ARENAS / (float(np.mean(ms)) * 1e-3), 1),
+           "complete_pair_members": [n for _, n in roll.weight_log],
+           "nonzero_pair_weights": [int(np.count_nonzero(d)) for d, _ in roll.weight_log],
+           "fitness_log_best": [round(f[0], 3) for f in roll.fitness_log],
+           "fitness_log_mean": [round(f[1], 3) for f in roll.fitness_log],
+           "centre_log": [round(c, 3) for c in roll.centre_log]}
+    b.close()
+    return out
+
+
+if __name__ == "__main__":
+    what = [x for x in sys.argv[1:] if x in ("kernels", "loop")]
+    if len(what) != 1:
+        raise SystemExit(__doc__)
+    line = json.dumps(kernels() if what[0] == "kernels" else loop())
+    print(line, flush=True)
+    if "--out" in sys.argv:
+        with open(_arg("--out", ""), "a") as f:
+            f.write(line + "\n")
