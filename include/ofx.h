@@ -495,6 +495,52 @@ int ofx_es_fitness(ofx_handle *h, const int32_t *member_of, int64_t P, int64_t *
  * `generation` is the one the members flew with.  One kernel, one pass over theta.  Does not wait for the update (d is
  * copied before the call returns, after the work already on the handle's stream).                                    */
 int ofx_es_update(ofx_handle *h, const double *d_host, int64_t n_pairs, double scale, uint64_t seed, uint32_t generation);
+/* The optimiser of the centre (opt-in): momentum or Adam on the rank-weighted estimate minus an L2 term, as Salimans et
+ * al.'s published implementation steps (there: Adam or SGD with momentum, l2coeff 0.005).  The estimate
+ * G_e = sum_i d_i eps(i, e) exists only in the registers of the generation step, so the optimiser is a kernel of its own
+ * that keeps the single pass over theta.
+ * STATE.  ofx_es_opt_create gives the centre two more buffers of G float64, m and v, zeroed, in theta's storage layout
+ * (first layer input-major): the centre then costs 3 G doubles of HBM, still at any P.  ofx_es_opt_destroy frees them;
+ * ofx_es_destroy and ofx_destroy free them too.  No centre, state already present (create) or absent (every other
+ * call): OFX_ERR_STATE.  An allocation that fails: OFX_ERR_HIP, the message naming the bytes.  The library holds only m
+ * and v: the step count and every scalar derived from it are the caller's.
+ * ofx_es_opt_get / _set move m and v in the element order, each as (weights, biases), the way ofx_es_get / _set move
+ * theta (the same host path).  Both synchronise.  OFX_ERR_INVALID for a NULL pointer.                                 */
+int ofx_es_opt_create(ofx_handle *h);
+int ofx_es_opt_destroy(ofx_handle *h);
+int ofx_es_opt_get(ofx_handle *h, double *m_weights, double *m_biases, double *v_weights, double *v_biases);
+int ofx_es_opt_set(ofx_handle *h, const double *m_weights, const double *m_biases, const double *v_weights,
+                   const double *v_biases);
+#define OFX_ES_RULE_MOMENTUM 1
+#define OFX_ES_RULE_ADAM 2
+/* The generation step through the optimiser.  d_host, n_pairs, seed, generation: as in ofx_es_update.  stats: DEVICE
+ * float64 [3] or NULL.  Per element e, G_e is exactly ofx_es_update's register sum (g = 0.0; g = g + d[i] * eps(i, e),
+ * ascending over the pairs with d != 0), and every line below is ONE separately rounded float64 operation, no FMA:
+ *   ghat = gscale * G_e
+ *   wd   = decay * theta
+ *   q    = ghat - wd
+ *   t1 = c1 * m;  t2 = k1 * q;  m' = t1 + t2
+ *   MOMENTUM:  step = alpha * m';                                            theta' = theta + step
+ *   ADAM:      qq = q * q;  t3 = c2 * v;  t4 = k2 * qq;  v' = t3 + t4
+ *              r = sqrt(v');  den = r + eps;  quo = m' / den;  step = alpha * quo;  theta' = theta + step
+ * Ascent on fitness - (decay / 2) |theta|^2.  c1 = 0, k1 = 1 is plain SGD with decay.  Under MOMENTUM v is neither read
+ * nor written.  sqrt and / are IEEE 754's correctly rounded operations (the library is built without fast-math), so
+ * theta', m' and v' are specified to the bit.  With Adam's bias correction folded into the step size, the caller passes
+ * k1 = 1 - beta1, k2 = 1 - beta2, alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t) at step t (ofighters_amd.es.ES.update).
+ * One kernel, one pass: theta, m (and v) read once and written once, coalesced.
+ * STATS.  When stats is not NULL: stats[0] = sum over e of q * q, stats[1] = sum of step * step, stats[2] = sum of
+ * theta' * theta', each in this fixed order.  A workgroup holds 256 consecutive STORAGE positions (a position past G
+ * holds +0.0) and adds its terms as a pairwise tree over the position within the workgroup: for stride = 128, 64, .. 1,
+ * x[t] = x[t] + x[t + stride] for t < stride.  The workgroup sums lie in a buffer the handle owns; one workgroup then
+ * adds them: thread t adds the sums of workgroups t, t + 256, ... in that order starting from 0.0, and the 256 thread
+ * sums are added in thread order.  No floating-point atomics: the same state gives the same bits on every call.  With
+ * stats == NULL the kernel carries none of this and theta', m', v' are the same bits.
+ * REFUSALS, each with a message and before anything is enqueued or written: no optimiser state (OFX_ERR_STATE); NULL
+ * d_host; n_pairs outside [1, 2^30); a rule other than the two; any scalar or any d[i] not finite; decay < 0; under
+ * ADAM eps <= 0 (OFX_ERR_INVALID).  Does not wait for the step (d is copied before the call returns).               */
+int ofx_es_step(ofx_handle *h, const double *d_host, int64_t n_pairs, int32_t rule, double gscale, double decay,
+                double alpha, double c1, double k1, double c2, double k2, double eps, uint64_t seed, uint32_t generation,
+                double *stats);
 
 /* ---- bi-head policy forward --------------------------------------------
  * Trainer.pointer_model graph + inference glue

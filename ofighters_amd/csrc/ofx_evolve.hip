@@ -29,8 +29,9 @@
 //              a workgroup per genome) adds its samples' terms in ascending ship order and touches, in the first layer,
 //              only the n1-double runs of the set cells.  No floating-point atomics.
 // k_pop_fitness  integer atomics only.
-// k_es_act / k_es_update / k_es_member  seeded evolution strategies, at the end of this file: one centre genome, the
-//              members' noise regenerated where it is read; k_es_act is pop_forward with another weight reader.
+// k_es_act / k_es_update / k_es_step / k_es_member  seeded evolution strategies, at the end of this file: one centre
+//              genome, the members' noise regenerated where it is read; k_es_act is pop_forward with another weight
+//              reader, k_es_step is k_es_update with momentum or Adam state beside the centre.
 #include "ofx_internal.h"
 #include "ofx_arena.h"
 
@@ -792,6 +793,9 @@ extern "C" int ofx_population_fitness(ofx_handle *h, const int32_t *genome_of, i
 // k_es_update  one thread per storage position, the loop over the pairs inside: coalesced reads and writes of theta,
 //              (pair, d) read wave-uniformly, the sum in ascending pair order in a register.  No floating-point atomics.
 //              Compute-bound on Philox by design: G x n_pairs evaluations against 16 G bytes.
+// k_es_step    k_es_update's pass with the moments m (and, under Adam, v) read and written at theta's position: the
+//              same G x n_pairs evaluations against 32 or 48 G bytes.  With stats, a
+//              fixed-order sum per workgroup and k_es_stats over the workgroups; no floating-point atomics.
 // k_es_member  a member materialised into a G-double buffer, for ofx_es_member.
 struct ofx_es {
   int n_layers;
@@ -802,6 +806,8 @@ struct ofx_es {
   double *d;                // [d_cap] the nonzero pair weights of the running ofx_es_update, ascending pair order
   uint32_t *d_pair;         // [d_cap] their pairs
   size_t d_cap;
+  double *m, *v;            // [G] each, theta's layout: the optimiser's moments (ofx_es_opt_create), null = none
+  double *part;             // [3][ceil(G / 256)] k_es_step's per-workgroup sums of q^2, step^2, theta'^2
 };
 
 // eps(i, e): the four stream-12 words of (pair, element, generation) summed, centred and scaled to (-2, 2).  The words
@@ -888,6 +894,99 @@ __global__ __launch_bounds__(256) void k_es_update(double *theta, const double *
   theta[s] = theta[s] + step;
 }
 
+// the scalars of ofx_es_step's law (include/ofx.h), all the caller's
+struct es_law {
+  double gscale, decay, alpha, c1, k1, c2, k2, eps;
+};
+
+// ofx_es_step: k_es_update's shape - one thread per storage position, the element by pop_element, the pair loop inside -
+// with the moments m and v at the same position as theta (coalesced, one read and one write each; momentum never
+// touches v).  Every line of the law is one rounded float64 operation; sqrt and / are the correctly rounded ones.
+// STATS: the workgroup's sums of q^2, step^2 and theta'^2 go to part[k][blockIdx.x], added as a pairwise tree over the
+// thread index (stride 128, 64, .. 1: x[t] = x[t] + x[t + stride]; a position past G adds +0.0); k_es_stats adds the
+// workgroups'.  Without STATS none of that is compiled in.
+template <bool ADAM, bool STATS>
+__global__ __launch_bounds__(256) void k_es_step(double *theta, double *m, double *v, const double *__restrict__ d,
+                                                 const uint32_t *__restrict__ d_pair, int n, uint32_t G, uint32_t first,
+                                                 uint32_t nin, uint32_t n1, es_law c, ofx_rng_key key,
+                                                 uint32_t generation, double *part) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  double sq0 = 0.0, sq1 = 0.0, sq2 = 0.0;
+  if (s < G) {
+    const uint32_t e = pop_element(s, first, nin, n1);
+    // k_es_update's sum, term for term.  es_eps is stated once; the loop stands in both kernels, because one shared
+    // body changed k_es_update's instruction stream (an inverted loop branch, a commuted final add)
+    double g = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < n; j++) {
+      const double t = d[j] * es_eps(d_pair[j], e, generation, key);
+      g = g + t;
+    }
+    const double w = theta[s];
+    const double ghat = c.gscale * g;
+    const double wd = c.decay * w;
+    const double q = ghat - wd;
+    const double t1 = c.c1 * m[s];
+    const double t2 = c.k1 * q;
+    const double mn = t1 + t2;
+    double quo = mn;
+    if (ADAM) {
+      const double qq = q * q;
+      const double t3 = c.c2 * v[s];
+      const double t4 = c.k2 * qq;
+      const double vn = t3 + t4;
+      const double r = sqrt(vn);
+      const double den = r + c.eps;
+      quo = mn / den;
+      v[s] = vn;
+    }
+    const double step = c.alpha * quo;
+    const double wn = w + step;
+    m[s] = mn;
+    theta[s] = wn;
+    if (STATS) {
+      sq0 = q * q;
+      sq1 = step * step;
+      sq2 = wn * wn;
+    }
+  }
+  if (STATS) {
+    __shared__ double red[3][256];
+    const int tid = threadIdx.x;
+    red[0][tid] = sq0;
+    red[1][tid] = sq1;
+    red[2][tid] = sq2;
+    __syncthreads();
+    for (int stride = 128; stride > 0; stride >>= 1) {
+      if (tid < stride) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) red[k][tid] = red[k][tid] + red[k][tid + stride];
+      }
+      __syncthreads();
+    }
+    if (tid < 3) part[(size_t)tid * gridDim.x + blockIdx.x] = red[tid][0];
+  }
+}
+
+// stats[k] = the nb workgroup sums part[k][0 .. nb): thread t adds entries t, t + 256, ... in that order from 0.0, then
+// thread k adds the 256 thread sums in thread order.  One workgroup: the same bits every call.
+__global__ __launch_bounds__(256) void k_es_stats(const double *part, int nb, double *stats) {
+  __shared__ double sum[3][256];
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    double a = 0.0;
+    for (int j = tid; j < nb; j += 256) a = a + part[(size_t)k * nb + j];
+    sum[k][tid] = a;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    double t = sum[tid][0];
+    for (int q = 1; q < 256; q++) t = t + sum[tid][q];
+    stats[tid] = t;
+  }
+}
+
 static ofx_es *&es_of(ofx_handle *h) { return h->es; }
 
 static pop_net net_of(const ofx_es *p) {
@@ -897,6 +996,13 @@ static pop_net net_of(const ofx_es *p) {
   return net;
 }
 
+static void es_opt_free(ofx_es *p) {
+  if (p->m) (void)hipFree(p->m);
+  if (p->v) (void)hipFree(p->v);
+  if (p->part) (void)hipFree(p->part);
+  p->m = p->v = p->part = nullptr;
+}
+
 void ofx_es_free(ofx_handle *h) {
   ofx_es *p = es_of(h);
   if (!p) return;
@@ -904,6 +1010,7 @@ void ofx_es_free(ofx_handle *h) {
   if (p->member) (void)hipFree(p->member);
   if (p->d) (void)hipFree(p->d);
   if (p->d_pair) (void)hipFree(p->d_pair);
+  es_opt_free(p);
   delete p;
   es_of(h) = nullptr;
 }
@@ -943,6 +1050,7 @@ extern "C" int ofx_es_create(ofx_handle *h, const int32_t *layers, int32_t n_lay
   p->first = (uint32_t)((unsigned long long)layers[0] * layers[1]);
   p->n_w = (uint32_t)n_w;
   p->theta = p->member = p->d = nullptr;
+  p->m = p->v = p->part = nullptr;
   p->d_pair = nullptr;
   p->d_cap = 0;
   const size_t bytes = (size_t)p->G * sizeof(double);
@@ -1059,27 +1167,31 @@ extern "C" int ofx_es_fitness(ofx_handle *h, const int32_t *member_of, int64_t P
   return OFX_OK;
 }
 
-extern "C" int ofx_es_update(ofx_handle *h, const double *d_host, int64_t n_pairs, double scale, uint64_t seed,
-                             uint32_t generation) {
-  ofx_es *p;
-  int rc = need_es(h, "ofx_es_update", &p);
-  if (rc) return rc;
-  if (!d_host) { ofx_set_error("ofx_es_update: null argument"); return OFX_ERR_INVALID; }
+// d_host[n_pairs] as the generation steps take it (`who`): not NULL, n_pairs in range
+static int check_pairs(const char *who, const double *d_host, int64_t n_pairs) {
+  if (!d_host) { ofx_set_error("%s: null argument", who); return OFX_ERR_INVALID; }
   if (n_pairs < 1 || n_pairs > 0x3fffffffll) {
-    ofx_set_error("ofx_es_update: n_pairs must be in [1, 2^30) (got %lld)", (long long)n_pairs);
+    ofx_set_error("%s: n_pairs must be in [1, 2^30) (got %lld)", who, (long long)n_pairs);
     return OFX_ERR_INVALID;
   }
-  if (!(scale - scale == 0.0)) { ofx_set_error("ofx_es_update: scale is not finite"); return OFX_ERR_INVALID; }
-  // A pair with d == 0 adds +-0 to a sum that starts at +0.0 and can never be -0.0 (x + (-x) rounds to +0), so leaving
-  // it out changes no bit: ties and incomplete pairs, the common case, cost nothing.
-  std::vector<double> d;
-  std::vector<uint32_t> pair;
+  return OFX_OK;
+}
+
+// The pairs with a weight, ascending.  A pair with d == 0 adds +-0 to a sum that starts at +0.0 and can never be -0.0
+// (x + (-x) rounds to +0), so leaving it out changes no bit: ties and incomplete pairs, the common case, cost nothing.
+static int nonzero_pairs(const char *who, const double *d_host, int64_t n_pairs, std::vector<double> &d,
+                         std::vector<uint32_t> &pair) {
   for (int64_t i = 0; i < n_pairs; i++) {
-    if (!(d_host[i] - d_host[i] == 0.0)) { ofx_set_error("ofx_es_update: d[%lld] is not finite", (long long)i); return OFX_ERR_INVALID; }
+    if (!(d_host[i] - d_host[i] == 0.0)) { ofx_set_error("%s: d[%lld] is not finite", who, (long long)i); return OFX_ERR_INVALID; }
     if (d_host[i] != 0.0) { d.push_back(d_host[i]); pair.push_back((uint32_t)i); }
   }
+  return OFX_OK;
+}
+
+// the list into the centre's device copy, after the work already on the handle's stream
+static int upload_pairs(ofx_handle *h, ofx_es *p, const std::vector<double> &d, const std::vector<uint32_t> &pair) {
   OFX_HIP(hipSetDevice(h->cfg.device));
-  OFX_HIP(hipStreamSynchronize(h->stream));  // the last update may still read the list
+  OFX_HIP(hipStreamSynchronize(h->stream));  // the last step may still read the list
   if (d.size() > p->d_cap) {
     if (p->d) (void)hipFree(p->d);
     if (p->d_pair) (void)hipFree(p->d_pair);
@@ -1094,9 +1206,131 @@ extern "C" int ofx_es_update(ofx_handle *h, const double *d_host, int64_t n_pair
     OFX_HIP(hipMemcpy(p->d, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice));
     OFX_HIP(hipMemcpy(p->d_pair, pair.data(), pair.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_update(ofx_handle *h, const double *d_host, int64_t n_pairs, double scale, uint64_t seed,
+                             uint32_t generation) {
+  ofx_es *p;
+  int rc = need_es(h, "ofx_es_update", &p);
+  if (rc || (rc = check_pairs("ofx_es_update", d_host, n_pairs))) return rc;
+  if (!(scale - scale == 0.0)) { ofx_set_error("ofx_es_update: scale is not finite"); return OFX_ERR_INVALID; }
+  std::vector<double> d;
+  std::vector<uint32_t> pair;
+  if ((rc = nonzero_pairs("ofx_es_update", d_host, n_pairs, d, pair)) || (rc = upload_pairs(h, p, d, pair))) return rc;
   hipLaunchKernelGGL(k_es_update, dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta, p->d, p->d_pair,
                      (int)d.size(), p->G, p->first, (uint32_t)p->layers[0], (uint32_t)p->layers[1], scale, ofx_key(seed),
                      generation);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ---- the optimiser of the centre (include/ofx.h: ofx_es_opt_*, ofx_es_step) ----
+static int need_opt(ofx_handle *h, const char *who, ofx_es **out) {
+  const int rc = need_es(h, who, out);
+  if (rc) return rc;
+  if (!(*out)->m) { ofx_set_error("%s: the centre has no optimiser state (ofx_es_opt_create)", who); return OFX_ERR_STATE; }
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_opt_create(ofx_handle *h) {
+  ofx_es *p;
+  const int rc = need_es(h, "ofx_es_opt_create", &p);
+  if (rc) return rc;
+  if (p->m) { ofx_set_error("ofx_es_opt_create: the centre already has optimiser state (ofx_es_opt_destroy)"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const size_t bytes = (size_t)p->G * sizeof(double), nb = (p->G + 255u) / 256u;
+  hipError_t e = hipMalloc((void **)&p->m, bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->v, bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->part, 3 * nb * sizeof(double));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ofx_set_error("ofx_es_opt_create: allocating 2 x %zu bytes for the moments of %u elements failed: %s", bytes, p->G,
+                  hipGetErrorString(e));
+    es_opt_free(p);
+    return OFX_ERR_HIP;
+  }
+  e = hipMemsetAsync(p->m, 0, bytes, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(p->v, 0, bytes, h->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ofx_set_error("ofx_es_opt_create: zeroing the moments failed: %s", hipGetErrorString(e));
+    (void)hipStreamSynchronize(h->stream);
+    es_opt_free(p);
+    return OFX_ERR_HIP;
+  }
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_opt_destroy(ofx_handle *h) {
+  ofx_es *p;
+  const int rc = need_opt(h, "ofx_es_opt_destroy", &p);
+  if (rc) return rc;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  es_opt_free(p);
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_opt_get(ofx_handle *h, double *m_weights, double *m_biases, double *v_weights, double *v_biases) {
+  ofx_es *p;
+  int rc = need_opt(h, "ofx_es_opt_get", &p);
+  if (rc) return rc;
+  if (!m_weights || !m_biases || !v_weights || !v_biases) { ofx_set_error("ofx_es_opt_get: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if ((rc = genome_to_host(h, p->m, p->layers, p->first, p->n_w, p->G, m_weights, m_biases))) return rc;
+  return genome_to_host(h, p->v, p->layers, p->first, p->n_w, p->G, v_weights, v_biases);
+}
+
+extern "C" int ofx_es_opt_set(ofx_handle *h, const double *m_weights, const double *m_biases, const double *v_weights,
+                              const double *v_biases) {
+  ofx_es *p;
+  int rc = need_opt(h, "ofx_es_opt_set", &p);
+  if (rc) return rc;
+  if (!m_weights || !m_biases || !v_weights || !v_biases) { ofx_set_error("ofx_es_opt_set: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if ((rc = genome_from_host(h, p->m, p->layers, p->first, p->n_w, p->G, m_weights, m_biases))) return rc;
+  return genome_from_host(h, p->v, p->layers, p->first, p->n_w, p->G, v_weights, v_biases);
+}
+
+template <bool ADAM, bool STATS>
+static void launch_step(ofx_handle *h, ofx_es *p, int n, const es_law &law, uint64_t seed, uint32_t generation) {
+  hipLaunchKernelGGL((k_es_step<ADAM, STATS>), dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta, p->m, p->v,
+                     p->d, p->d_pair, n, p->G, p->first, (uint32_t)p->layers[0], (uint32_t)p->layers[1], law,
+                     ofx_key(seed), generation, p->part);
+}
+
+extern "C" int ofx_es_step(ofx_handle *h, const double *d_host, int64_t n_pairs, int32_t rule, double gscale,
+                           double decay, double alpha, double c1, double k1, double c2, double k2, double eps,
+                           uint64_t seed, uint32_t generation, double *stats) {
+  ofx_es *p;
+  int rc = need_opt(h, "ofx_es_step", &p);
+  if (rc || (rc = check_pairs("ofx_es_step", d_host, n_pairs))) return rc;
+  if (rule != OFX_ES_RULE_MOMENTUM && rule != OFX_ES_RULE_ADAM) {
+    ofx_set_error("ofx_es_step: rule must be OFX_ES_RULE_MOMENTUM (1) or OFX_ES_RULE_ADAM (2) (got %d)", rule);
+    return OFX_ERR_INVALID;
+  }
+  const es_law law = {gscale, decay, alpha, c1, k1, c2, k2, eps};
+  const double scalars[8] = {gscale, decay, alpha, c1, k1, c2, k2, eps};
+  static const char *const names[8] = {"gscale", "decay", "alpha", "c1", "k1", "c2", "k2", "eps"};
+  for (int i = 0; i < 8; i++)
+    if (!(scalars[i] - scalars[i] == 0.0)) { ofx_set_error("ofx_es_step: %s is not finite", names[i]); return OFX_ERR_INVALID; }
+  if (decay < 0.0) { ofx_set_error("ofx_es_step: decay must be >= 0 (got %g)", decay); return OFX_ERR_INVALID; }
+  if (rule == OFX_ES_RULE_ADAM && !(eps > 0.0)) { ofx_set_error("ofx_es_step: eps must be > 0 under Adam (got %g)", eps); return OFX_ERR_INVALID; }
+  std::vector<double> d;
+  std::vector<uint32_t> pair;
+  if ((rc = nonzero_pairs("ofx_es_step", d_host, n_pairs, d, pair)) || (rc = upload_pairs(h, p, d, pair))) return rc;
+  const int n = (int)d.size();
+  const bool adam = rule == OFX_ES_RULE_ADAM;
+  if (stats) {
+    if (adam) launch_step<true, true>(h, p, n, law, seed, generation);
+    else launch_step<false, true>(h, p, n, law, seed, generation);
+    OFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_es_stats, dim3(1), dim3(256), 0, h->stream, p->part, (int)((p->G + 255u) / 256u), stats);
+  } else {
+    if (adam) launch_step<true, false>(h, p, n, law, seed, generation);
+    else launch_step<false, false>(h, p, n, law, seed, generation);
+  }
   OFX_HIP(hipGetLastError());
   return OFX_OK;
 }

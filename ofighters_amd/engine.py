@@ -1138,3 +1138,28 @@ class ArenaBatch:
         a = np.ascontiguousarray(d, dtype=np.float64)
         nat.check(nat.lib().ofx_es_update(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], float(scale), seed,
                                           int(generation)))
+
+    def es_opt_create(self):
+        """The centre's optimiser state: the moments m and v, zeroed, in theta's layout (ofx_es_opt_create)."""
+        nat.check(nat.lib().ofx_es_opt_create(self._h))
+
+    def es_opt_destroy(self):
+        nat.check(nat.lib().ofx_es_opt_destroy(self._h))
+
+    def es_opt_get(self, n_weights, n_biases):
+        """The moments as ((m weights, m biases), (v weights, v biases)) in the element order.  Synchronises."""
+        out = [np.empty(int(n), np.float64) for n in (n_weights, n_biases, n_weights, n_biases)]
+        nat.check(nat.lib().ofx_es_opt_get(self._h, *[a.ctypes.data_as(C.c_void_p) for a in out]))
+        return (out[0], out[1]), (out[2], out[3])
+
+    def es_opt_set(self, m_weights, m_biases, v_weights, v_biases):
+        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (m_weights, m_biases, v_weights, v_biases)]
+        nat.check(nat.lib().ofx_es_opt_set(self._h, *[x.ctypes.data_as(C.c_void_p) for x in a]))
+
+    def es_step(self, d, rule, gscale, decay, alpha, c1, k1, c2, k2, eps, seed, generation, stats_ptr=None):
+        """The generation step through the optimiser (ofx_es_step: the law, line by line); d: float64 [P / 2], rule:
+        nat.ES_RULE_MOMENTUM or nat.ES_RULE_ADAM, stats_ptr: device float64 [3] or None.  Does not wait for the step."""
+        a = np.ascontiguousarray(d, dtype=np.float64)
+        nat.check(nat.lib().ofx_es_step(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(rule), float(gscale),
+                                        float(decay), float(alpha), float(c1), float(k1), float(c2), float(k2),
+                                        float(eps), seed, int(generation), stats_ptr))

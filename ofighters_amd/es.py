@@ -7,7 +7,7 @@ generation) on the project's counter RNG, and a generation ends in a rank-weight
 regenerates the noise of the rows it gathers inside the kernel, so a population of any P costs one genome of memory.
 
     pair_weights  fitness sums -> the weight of every mirrored pair (centred average ranks): pure numpy, no randomness
-    ES            owns the ofx_es_* calls of one ArenaBatch
+    ES            owns the ofx_es_* calls of one ArenaBatch; opt-in momentum / Adam and weight decay for the centre
     ESRollout     the generational loop around ShardedRollout's lock-step
 
 eps has variance 1/3 (an Irwin-Hall sum of four uniforms in (-2, 2)): sigma and lr are in units of that eps.  Whether
@@ -95,19 +95,100 @@ def check_es_meta(meta, shape, dtype, layers, seed, path="the checkpoint"):
         raise ValueError("%s: dtype is %s, a centre is float64" % (path, np.dtype(dtype)))
 
 
+OPTIMIZERS = ("momentum", "adam")
+
+
+def check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay):
+    """ES's optimiser arguments, checked before the library is touched: ValueError naming the argument."""
+    if optimizer is not None and optimizer not in OPTIMIZERS:
+        raise ValueError("optimizer must be None, 'momentum' or 'adam', got %r" % (optimizer,))
+    for name, beta in (("beta1", beta1), ("beta2", beta2)):
+        if not (math.isfinite(beta) and 0.0 <= beta < 1.0):
+            raise ValueError("%s must be in [0, 1), got %r" % (name, beta))
+    if not (math.isfinite(adam_eps) and adam_eps > 0):
+        raise ValueError("adam_eps must be finite and > 0, got %r" % (adam_eps,))
+    if not (math.isfinite(weight_decay) and weight_decay >= 0):
+        raise ValueError("weight_decay must be finite and >= 0, got %r" % (weight_decay,))
+    if weight_decay != 0 and optimizer is None:
+        raise ValueError("weight_decay needs an optimizer: the bare update has no decay term")
+
+
+def step_scalars(optimizer, lr, sigma, n_c, t, beta1, beta2):
+    """(gscale, alpha, c1, k1, c2, k2) of ofx_es_step at step t (1-based), in Python floats and in this order; Adam's
+    bias correction is folded into the step size."""
+    gscale = 1.0 / (int(n_c) * float(sigma))
+    k1 = 1.0 - beta1
+    k2 = 1.0 - beta2
+    alpha = float(lr) if optimizer == "momentum" else float(lr) * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    return gscale, alpha, float(beta1), k1, float(beta2), k2
+
+
+def es_opt_meta(optimizer, beta1, beta2, adam_eps, weight_decay, steps):
+    return {"rule": optimizer, "beta1": float(beta1), "beta2": float(beta2), "eps": float(adam_eps),
+            "weight_decay": float(weight_decay), "steps": int(steps)}
+
+
+def check_es_opt_meta(meta, want, shape=None, dtype=None, elements=None, path="the checkpoint"):
+    """ES.load's refusals about the optimiser, before anything is touched: ValueError naming the first field that
+    differs.  `meta` is the sidecar, `want` this ES's es_opt_meta (None: no optimiser).  The block must be there exactly
+    when this ES has an optimiser, and equal `want` in everything but `steps`; shape / dtype, when given, are those of
+    the moments' array, float64 [2][elements].  Returns the checkpoint's step count (0 without an optimiser)."""
+    block = meta.get("optimizer")
+    if want is None:
+        if block is not None:
+            raise ValueError("%s: the sidecar has an optimizer block, this ES has no optimizer" % path)
+        return 0
+    if block is None:
+        raise ValueError("%s: the sidecar has no optimizer block, this ES's optimizer is %r" % (path, want["rule"]))
+    for field in ("rule", "beta1", "beta2", "eps", "weight_decay"):
+        if field not in block:
+            raise ValueError("%s: the optimizer block has no field %r" % (path, field))
+        got = block[field] if field == "rule" else float(block[field])
+        if got != want[field]:
+            raise ValueError("%s: optimizer %s is %r, this ES's is %r" % (path, field, got, want[field]))
+    steps = block.get("steps")
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise ValueError("%s: the optimizer block's steps must be an integer >= 0, got %r" % (path, steps))
+    if shape is not None and tuple(shape) != (2, elements):
+        raise ValueError("%s: the moments' shape is %r, m and v of %d elements are %r" % (path, tuple(shape), elements,
+                                                                                         (2, elements)))
+    if dtype is not None and np.dtype(dtype) != np.float64:
+        raise ValueError("%s: the moments' dtype is %s, they are float64" % (path, np.dtype(dtype)))
+    return steps
+
+
+def moments_path(path):
+    return path + ".opt.npy"
+
+
 class ES:
     """One ES centre of the scratch MLP `layers` on the device of `batch` (an ArenaBatch), beside any Population the
     batch holds; initialised to the fresh genome of slot 0 from `seed` (the law of Population's init).
 
-    Every member's noise is keyed by (seed, pair, element, generation): a run is reproducible, and no member is stored."""
+    Every member's noise is keyed by (seed, pair, element, generation): a run is reproducible, and no member is stored.
 
-    def __init__(self, batch, layers, seed, init=True):
+    optimizer  None (default): `update` is the bare step theta += lr / (n_c sigma) * sum_i d_i eps(i, .), call for call
+               what it always was.  "momentum" or "adam": the centre gets the moments m and v in HBM (3 genomes instead
+               of 1, still at any P) and `update` feeds the estimate minus weight_decay * theta through ofx_es_step
+               (include/ofx.h states the law); `opt_steps` counts the steps, 1-based, and is the t of Adam's bias
+               correction.  beta1 is the momentum (both rules), beta2 and adam_eps are Adam's."""
+
+    def __init__(self, batch, layers, seed, optimizer=None, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
+                 init=True):
         from .engine import DeviceBuffer
+        check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay)
         self.b = batch
         self.layers = [int(v) for v in layers]
         self.seed = int(seed)
         self.n_weights, self.n_biases = genome_sizes(self.layers)
+        self.optimizer = optimizer
+        self.beta1, self.beta2, self.adam_eps = float(beta1), float(beta2), float(adam_eps)
+        self.weight_decay = float(weight_decay)
+        self.opt_steps = 0
         batch.es_create(self.layers)
+        if optimizer is not None:
+            batch.es_opt_create()
+            self._stats = DeviceBuffer(3 * 8).upload(np.zeros(3, np.float64))
         self._member_of = DeviceBuffer(batch.N * batch.M * 4)
         self.P, self.member_of = None, None
         self._sum = self._count = None
@@ -129,6 +210,21 @@ class ES:
 
     def set_centre(self, weights_layers, biases_layers):
         self.b.es_set(*join_genome(self.layers, weights_layers, biases_layers))
+
+    def moments(self):
+        """(m, v) of the optimiser, each (weights_layers, biases_layers) in the shapes of centre().  Synchronises."""
+        self._has_optimizer()
+        m, v = self.b.es_opt_get(self.n_weights, self.n_biases)
+        return split_genome(self.layers, *m), split_genome(self.layers, *v)
+
+    def set_moments(self, m, v):
+        """Put back what moments() returned."""
+        self._has_optimizer()
+        self.b.es_opt_set(*(join_genome(self.layers, *m) + join_genome(self.layers, *v)))
+
+    def _has_optimizer(self):
+        if self.optimizer is None:
+            raise ValueError("this ES has no optimizer: construct it with optimizer='momentum' or 'adam'")
 
     def member(self, m, P, sigma, generation):
         """(weights_layers, biases_layers) of member m of P at `generation` (m == P: the centre), materialised on the
@@ -187,37 +283,79 @@ class ES:
 
     def update(self, d, lr, sigma, n_c, generation):
         """The generation step theta += lr / (n_c sigma) * sum_i d_i eps(i, .) on the noise of `generation`, the one the
-        members flew with; (d, n_c) from pair_weights.  The scale is computed in Python floats, in that order."""
+        members flew with; (d, n_c) from pair_weights.  The scale is computed in Python floats, in that order.
+
+        With an optimizer: opt_steps += 1 and the step goes through ofx_es_step with the scalars of step_scalars; its
+        three sums wait in the ES's stats buffer for step_stats()."""
         d = np.asarray(d, np.float64)
         if d.ndim != 1 or d.shape[0] < 1 or not np.isfinite(d).all():
             raise ValueError("d is a finite float64 [P / 2], got %s" % (d.shape,))
         check_members(2 * d.shape[0], sigma)
         if int(n_c) < 2 or not math.isfinite(lr):
             raise ValueError("update needs n_c >= 2 and a finite lr, got n_c = %r, lr = %r" % (n_c, lr))
-        scale = float(lr) / (int(n_c) * float(sigma))
-        self.b.es_update(d, scale, self.seed, generation)
+        if self.optimizer is None:
+            scale = float(lr) / (int(n_c) * float(sigma))
+            self.b.es_update(d, scale, self.seed, generation)
+            return
+        from . import _native as nat
+        self.opt_steps += 1
+        gscale, alpha, c1, k1, c2, k2 = step_scalars(self.optimizer, lr, sigma, n_c, self.opt_steps, self.beta1, self.beta2)
+        rule = nat.ES_RULE_MOMENTUM if self.optimizer == "momentum" else nat.ES_RULE_ADAM
+        self.b.es_step(d, rule, gscale, self.weight_decay, alpha, c1, k1, c2, k2, self.adam_eps, self.seed, generation,
+                       stats_ptr=self._stats.ptr)
+
+    def step_stats(self):
+        """(grad_sq, step_sq, centre_sq) of the last optimiser step: the sums over the genome of q^2 (the estimate minus
+        the decay term), of step^2 and of theta'^2, zeros before the first step.  Synchronises."""
+        self._has_optimizer()
+        self.b.sync()
+        return tuple(float(x) for x in self._stats.download(np.float64, (3,)))
 
     # ------------------------------------------------------------ checkpoint of the centre
     def save(self, path):
         """The centre as ONE .npy at `path`, float64 [n_weights + n_biases] in the element order, and the sidecar
-        `path + ".json"` with layers and seed.  Returns path."""
+        `path + ".json"` with layers and seed.  With an optimizer also `path + ".opt.npy"`, float64 [2][elements], m
+        then v in the element order, and the sidecar's "optimizer" block (rule, betas, eps, weight_decay, steps).
+        Returns path."""
         import json
         w, b = self.b.es_get(self.n_weights, self.n_biases)
+        meta = es_meta(self.layers, self.seed)
+        if self.optimizer is not None:
+            m, v = self.b.es_opt_get(self.n_weights, self.n_biases)
+            with open(moments_path(path), "wb") as f:
+                np.save(f, np.stack([np.concatenate(m), np.concatenate(v)]))
+            meta["optimizer"] = self._opt_meta()
         with open(path, "wb") as f:
             np.save(f, np.concatenate([w, b]))
         with open(sidecar_path(path), "w") as f:
-            json.dump(es_meta(self.layers, self.seed), f)
+            json.dump(meta, f)
         return path
+
+    def _opt_meta(self):
+        if self.optimizer is None:
+            return None
+        return es_opt_meta(self.optimizer, self.beta1, self.beta2, self.adam_eps, self.weight_decay, self.opt_steps)
 
     def load(self, path):
         """The centre `save` wrote, into this ES.  ValueError naming the field, with the centre untouched, when the
-        checkpoint's layers or seed (or the array's shape or dtype) differ from this ES's."""
+        checkpoint's layers or seed (or the array's shape or dtype) differ from this ES's - or when its optimizer block
+        is missing, unwanted or differs in anything but `steps` (check_es_opt_meta).  With an optimizer the moments and
+        opt_steps come back too: the next update is the one the saved run would have made."""
         import json
         with open(sidecar_path(path)) as f:
             meta = json.load(f)
         arr = np.load(path)
         check_es_meta(meta, arr.shape, arr.dtype, self.layers, self.seed, path)
+        want = self._opt_meta()
+        steps = check_es_opt_meta(meta, want, path=path)       # the sidecar first: no moments file is opened for a refusal
+        if want is not None:
+            mom = np.load(moments_path(path))
+            check_es_opt_meta(meta, want, mom.shape, mom.dtype, arr.shape[0], path)
         self.b.es_set(arr[:self.n_weights], arr[self.n_weights:])
+        if want is not None:
+            nw = self.n_weights
+            self.b.es_opt_set(mom[0, :nw], mom[0, nw:], mom[1, :nw], mom[1, nw:])
+            self.opt_steps = steps
 
 
 class ESRollout(ShardedRollout):
@@ -234,11 +372,14 @@ class ESRollout(ShardedRollout):
     `centre_log`.  Runs with observe=False; its policy hook is es.act.  Single GPU: with `dist` set it refuses.
 
     es  an ES on `engine` (or anything with its assign, act, fitness, fitness_host, update; for state_dict also
-        load_fitness)
+        load_fitness; for log_steps also step_stats)
+    log_steps  opt-in, for an ES with an optimizer: after each generation's update, es.step_stats() - the sums of
+        squares of the estimate, the step and the centre - is appended to `step_log` (one download of three doubles per
+        stepped generation).
     """
 
     def __init__(self, engine, es, behaviours, seed, P, sigma, lr, ships=(0,), episodes_per_generation=1, eval_arenas=0,
-                 **kw):
+                 log_steps=False, **kw):
         if kw.get("dist") is not None:
             raise ValueError("ESRollout runs on one GPU: `dist` must be None")
         if kw.get("policy") is not None or kw.get("observe"):
@@ -264,6 +405,8 @@ class ESRollout(ShardedRollout):
         self.fitness_log = []             # (best mean fitness of a member, mean fitness per evolved ship) per generation
         self.centre_log = []              # mean banked score of a centre-flown ship per generation (eval_arenas > 0)
         self.weight_log = []              # (d, n_c) each generation stepped on
+        self.log_steps = bool(log_steps)
+        self.step_log = []                # (grad_sq, step_sq, centre_sq) per stepped generation (log_steps)
         self.policy = self._fly
         self._assign()
 
@@ -300,6 +443,8 @@ class ESRollout(ShardedRollout):
             d, n_c = pair_weights(s, c)
             if n_c >= 2:
                 self.es.update(d, self.lr, self.sigma, n_c, self.generation)
+                if self.log_steps:
+                    self.step_log.append(tuple(self.es.step_stats()))
             self.weight_log.append((d, n_c))
             self.generation += 1
             self.episodes = 0
@@ -308,15 +453,19 @@ class ESRollout(ShardedRollout):
 
     # ------------------------------------------------------------ stop and go on
     def state_dict(self):
-        """What a run stopped between two lock-steps needs, beside the centre (ES.save), to go on bit for bit in fresh
-        handles: the generation and episode counters, the logs, the fitness sums and counts of the running generation,
-        the tick and ArenaBatch.state_dict()."""
+        """What a run stopped between two lock-steps needs, beside the centre (ES.save: with an optimizer also its
+        moments and step count), to go on bit for bit in fresh handles: the generation and episode counters, the logs
+        (step_log only with log_steps), the fitness sums and counts of the running generation, the tick and
+        ArenaBatch.state_dict()."""
         s, c = self.es.fitness_host()
-        return {"generation": self.generation, "episodes": self.episodes, "tick": self.tick,
-                "fitness_log": list(self.fitness_log), "centre_log": list(self.centre_log),
-                "weight_log": [(np.array(d), int(n)) for d, n in self.weight_log],
-                "score_log": [np.array(t) for t in self.score_log], "fitness_sum": s, "fitness_count": c,
-                "engine": self.e.state_dict()}
+        d = {"generation": self.generation, "episodes": self.episodes, "tick": self.tick,
+             "fitness_log": list(self.fitness_log), "centre_log": list(self.centre_log),
+             "weight_log": [(np.array(d), int(n)) for d, n in self.weight_log],
+             "score_log": [np.array(t) for t in self.score_log], "fitness_sum": s, "fitness_count": c,
+             "engine": self.e.state_dict()}
+        if self.log_steps:
+            d["step_log"] = list(self.step_log)
+        return d
 
     def load_state_dict(self, d):
         """Continue the run state_dict() described, on a freshly constructed ESRollout with the same arguments whose ES
@@ -330,5 +479,7 @@ class ESRollout(ShardedRollout):
         self.fitness_log, self.centre_log = list(d["fitness_log"]), list(d["centre_log"])
         self.weight_log = [(np.array(w), int(n)) for w, n in d["weight_log"]]
         self.score_log = [np.array(t) for t in d["score_log"]]
+        if "step_log" in d:
+            self.step_log = [tuple(t) for t in d["step_log"]]
         self._assign()
         self.es.load_fitness(d["fitness_sum"], d["fitness_count"])

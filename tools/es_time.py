@@ -1,4 +1,4 @@
-"""Seeded evolution strategies at the training size (profiles/r29_es.txt): `--arenas` (4096) arenas x 8 ships, ship 0 of
+"""Seeded evolution strategies at the training size (profiles/r29_es.txt, profiles/r30_es_optimizer.txt): `--arenas` (4096) arenas x 8 ships, ship 0 of
 every arena flown by a member of the ES population around one centre of the reference's [320008, 9, 4], the seven others
 by `random` bots.
 
@@ -14,15 +14,23 @@ kernels  HIP events on the handle's stream (ofx_event_record / ofx_event_elapsed
          EVERY pair (the worst case: ties and incomplete pairs are left out by the library).  Reported: us per call
          (mean of each block), the ratio es_act / population_act, the Philox evaluations one es_act makes (per live
          evolved ship: set cells x n1 + 8 n1 + the later layers and biases), ms per update and the Philox evaluations
-         per second it reaches (elements x pairs / time).
-loop     ESRollout at P = `--small`, sigma 0.05, lr 0.1, `--eval-arenas` (64) arenas on the centre, `--generations` (5)
-         generations of one 200-lock-step episode each; a host clock around every generation (its lock-steps, the
+         per second it reaches (elements x pairs / time).  Beside every ofx_es_update, on the same handle, with the
+         same d and in the same block: (d) one ofx_es_step per rule (momentum, Adam) without and with the statistics -
+         the same Philox evaluations, 32 / 48 bytes per element instead of 16 - then the update once more and the four steps in
+         reverse order (the first call of a block follows the host's work on d, and position in the block shows);
+         reported as ms per call and as the ratio to the block's
+         first ofx_es_update.
+loop     ESRollout at P = `--small`, `--sigma` (0.05), `--lr` (0.1), `--optimizer` (none; momentum or adam) with
+         `--weight-decay` (0), `--eval-arenas` (64) arenas on the centre, `--generations` (5) generations of one
+         200-lock-step episode each; a host clock around every generation (its lock-steps, the
          restart, the fitness download, pair_weights and the update), ending in a synchronise.  Reported: ms per
-         lock-step and arena-steps/s per generation, fitness_log and centre_log.  Whether they rise is an observation of
-         this run, not something any test holds the code to.
+         lock-step and arena-steps/s per generation, fitness_log and centre_log, and with an optimizer step_log (the
+         sums of squares of the estimate, the step and the centre per generation).  Whether they rise is an observation
+         of this run, not something any test holds the code to.
 Each mode prints one JSON line and, with `--out FILE`, appends it to that file.
 Usage: python tools/es_time.py kernels|loop [--arenas 4096] [--small 4096] [--large 32768] [--stored 512] [--calls 50]
-                               [--repeats 3] [--generations 5] [--eval-arenas 64] [--out FILE]
+                               [--repeats 3] [--generations 5] [--eval-arenas 64] [--optimizer adam|momentum]
+                               [--weight-decay 0.005] [--lr 0.1] [--sigma 0.05] [--out FILE]
 
 One GPU step per process, each under its own time limit, chained so that a failure ends the chain:
     timeout -k 10 400 python tools/es_time.py kernels --out profiles/r29_es.txt \\
@@ -48,7 +56,9 @@ from ofighters_amd.evolution import Population
 M, SEED = 8, 0x0F160123
 ARENAS = _arg("--arenas", 4096)
 LAYERS = [320008, 9, 4]
-SIGMA, LR = 0.05, 0.1
+SIGMA, LR = _arg("--sigma", 0.05), _arg("--lr", 0.1)
+STEP_KINDS = [("momentum", nat.ES_RULE_MOMENTUM, False), ("momentum_stats", nat.ES_RULE_MOMENTUM, True),
+              ("adam", nat.ES_RULE_ADAM, False), ("adam_stats", nat.ES_RULE_ADAM, True)]
 G = sum(LAYERS[i] * LAYERS[i + 1] + LAYERS[i + 1] for i in range(len(LAYERS) - 1))
 _POPCOUNT = np.array([bin(v).count("1") for v in range(256)], np.uint8)
 
@@ -83,6 +93,8 @@ def kernels():
     b.spawn_random(SEED)
     b.rollout(["random"] * M, SEED, 0, 40)
     es = ES(b, LAYERS, SEED)
+    b.es_opt_create()                                           # the moments, for ofx_es_step beside ofx_es_update
+    stats = DeviceBuffer(24)
     pop = Population(b, LAYERS, stored, SEED)
     g = np.full((ARENAS, M), -1, np.int32)
     g[:, 0] = np.arange(ARENAS) % stored
@@ -102,6 +114,9 @@ def kernels():
     timed(pop.act, 5)
     act_us, centre_us, pop_us = {P: [] for P in sizes}, [], []
     update_ms = {P: [] for P in sizes}
+    step_ms = {P: {kind: [] for kind, _, _ in STEP_KINDS} for P in sizes}
+    update_again_ms = {P: [] for P in sizes}                    # the update once more behind the steps,
+    step_again_ms = {P: {kind: [] for kind, _, _ in STEP_KINDS} for P in sizes}   # then the steps in reverse order
     rs = np.random.RandomState(0)
     generation = 1
     for _ in range(repeats):
@@ -113,6 +128,13 @@ def kernels():
             d = rs.uniform(0.01, 1.0, P // 2) * rs.choice([-1.0, 1.0], P // 2)     # a weight on every pair
             gen = generation
             update_ms[P].append(round(timed(lambda: b.es_update(d, LR / (P * SIGMA), SEED, gen), 1) / 1e3, 3))
+            for into, kinds in ((step_ms, STEP_KINDS), (step_again_ms, STEP_KINDS[::-1])):
+                for kind, rule, with_stats in kinds:
+                    step = lambda: b.es_step(d, rule, 1.0 / (P * SIGMA), 0.005, LR, 0.9, 1.0 - 0.9, 0.999, 1.0 - 0.999, 1e-8,
+                                             SEED, gen, stats_ptr=stats.ptr if with_stats else None)
+                    into[P][kind].append(round(timed(step, 1) / 1e3, 3))
+                if into is step_ms:
+                    update_again_ms[P].append(round(timed(lambda: b.es_update(d, LR / (P * SIGMA), SEED, gen), 1) / 1e3, 3))
             generation += 1
     alive = b.get(nat.F_SHIP_ALIVE)[:, 0] != 0
     sm, lm = b.maps_host(nat.MAP_BITS)
@@ -131,17 +153,22 @@ def kernels():
             "P": P, "es_act_us": act_us[P], "es_act_over_population_act": round(float(np.mean(act_us[P])) / pop_mean, 3),
             "es_act_philox_per_s": round(philox_per_act / act_s, 1),
             "update_ms": update_ms[P], "update_pairs": P // 2, "update_philox_evaluations": G * (P // 2),
-            "update_philox_per_s": round(G * (P // 2) / upd_s, 1)})
+            "update_philox_per_s": round(G * (P // 2) / upd_s, 1), "step_ms": step_ms[P],
+            "update_again_ms": update_again_ms[P], "step_again_ms": step_again_ms[P],
+            "step_over_update": {kind: round(float(np.mean(step_ms[P][kind])) / float(np.mean(update_ms[P])), 4)
+                                 for kind, _, _ in STEP_KINDS}})
     b.close()
     return out
 
 
 def loop():
     P, generations, eval_arenas = _arg("--small", 4096), _arg("--generations", 5), _arg("--eval-arenas", 64)
+    optimizer, weight_decay = _arg("--optimizer", "") or None, _arg("--weight-decay", 0.0)
     b = ArenaBatch(ARENAS, M)
-    es = ES(b, LAYERS, SEED)
+    es = ES(b, LAYERS, SEED, optimizer=optimizer, weight_decay=weight_decay)
     T = b.cfg.episode_ticks
-    roll = ESRollout(b, es, ["random"] * M, SEED, P, SIGMA, LR, ships=(0,), eval_arenas=eval_arenas, episode_ticks=T)
+    roll = ESRollout(b, es, ["random"] * M, SEED, P, SIGMA, LR, ships=(0,), eval_arenas=eval_arenas, episode_ticks=T,
+                     log_steps=optimizer is not None)
     roll.run(1)                                                # the episode-end check stands at the head of a lock-step
     ms = []
     for _ in range(generations):
@@ -151,14 +178,16 @@ def loop():
         b.sync()
         ms.append((time.perf_counter() - t0) * 1e3 / T)
     out = {"what": "loop", "arenas": ARENAS, "ships": M, "layers": LAYERS, "P": P, "sigma": SIGMA, "lr": LR,
-           "eval_arenas": eval_arenas, "episode_ticks": T, "generations": roll.generation,
+           "optimizer": optimizer, "weight_decay": weight_decay, "eval_arenas": eval_arenas, "episode_ticks": T,
+           "generations": roll.generation,
            "ms_per_lock_step": [round(x, 4) for x in ms], "mean_ms_per_lock_step": round(float(np.mean(ms)), 4),
            "arena_steps_per_s": round(ARENAS / (float(np.mean(ms)) * 1e-3), 1),
            "complete_pair_members": [n for _, n in roll.weight_log],
            "nonzero_pair_weights": [int(np.count_nonzero(d)) for d, _ in roll.weight_log],
            "fitness_log_best": [round(f[0], 3) for f in roll.fitness_log],
            "fitness_log_mean": [round(f[1], 3) for f in roll.fitness_log],
-           "centre_log": [round(c, 3) for c in roll.centre_log]}
+           "centre_log": [round(c, 3) for c in roll.centre_log],
+           "step_log": [[float("%.6g" % x) for x in t] for t in roll.step_log]}
     b.close()
     return out
 
