@@ -541,6 +541,75 @@ int ofx_es_opt_set(ofx_handle *h, const double *m_weights, const double *m_biase
 int ofx_es_step(ofx_handle *h, const double *d_host, int64_t n_pairs, int32_t rule, double gscale, double decay,
                 double alpha, double c1, double k1, double c2, double k2, double eps, uint64_t seed, uint32_t generation,
                 double *stats);
+/* Per-element adaptive sigma (opt-in): parameter-exploring policy gradients with symmetric sampling (Sehnke, Osendorfer,
+ * Rueckstiess, Graves, Peters, Schmidhuber 2010; the separable case of natural evolution strategies).  The mirrored
+ * pairs are already the population, and both sums the method needs come from the same eps(i, e): the centre's
+ * sum d_i eps and sigma's sum s_i (eps^2 - 1/3).  The generation step is bound by its G x n_pairs Philox evaluations,
+ * so sigma is learned in the pass that steps the centre: a kernel of its own, one more genome of HBM, still at any P.
+ * STATE.  ofx_es_sigma_create gives the centre one more buffer of G float64, sigma, in theta's storage layout (first
+ * layer input-major), every element sigma0.  ofx_es_sigma_destroy frees it; ofx_es_destroy and ofx_destroy free it too.
+ * ofx_es_sigma_get / _set move it in the element order as (weights, biases), on the host path of ofx_es_get / _set; both
+ * synchronise.  ofx_es_update and ofx_es_step neither read nor write it.
+ * REFUSALS, each with a message and before anything is enqueued or written: no centre, a vector that is already there
+ * (create), no vector (every other call): OFX_ERR_STATE.  sigma0, or any element given to _set, not finite or <= 0;
+ * a NULL pointer; P odd or < 2; member outside [0, P]: OFX_ERR_INVALID.  An allocation that fails: OFX_ERR_HIP, the
+ * message naming the bytes.
+ * MEMBERS.  Member m = 2 i + b of P is
+ *   w_m[e] = theta[e] + (s * sigma[e]) * eps(i, e)
+ * s = +1 (b = 0) or -1 (b = 1): the sign is exact, the product is rounded, then the sum, no FMA.  Member P is the centre.
+ * With every sigma[e] equal to one value this is ofx_es_member's and ofx_es_act's law bit for bit.
+ * ofx_es_sigma_member is ofx_es_member and ofx_es_sigma_act is ofx_es_act under this law: the forward's device code is
+ * ofx_es_act's with a reader that reads sigma at the storage position where it reads theta - the same lanes, the same
+ * list order, the same order of every sum - and the centre takes the stored-genome path.                             */
+int ofx_es_sigma_create(ofx_handle *h, double sigma0);
+int ofx_es_sigma_destroy(ofx_handle *h);
+int ofx_es_sigma_get(ofx_handle *h, double *weights_host, double *biases_host);
+int ofx_es_sigma_set(ofx_handle *h, const double *weights_host, const double *biases_host);
+int ofx_es_sigma_member(ofx_handle *h, int64_t member, int64_t P, uint64_t seed, uint32_t generation,
+                        double *weights_host, double *biases_host);
+int ofx_es_sigma_act(ofx_handle *h, const int32_t *member_of, int64_t P, uint64_t seed, uint32_t generation,
+                     ofx_action *actions, double *y);
+#define OFX_ES_RULE_PLAIN 0
+/* The generation step of the centre AND of sigma.  d_host, s_host: HOST float64 [n_pairs], the pair's weight for the
+ * centre (u_{2i} - u_{2i+1}) and for sigma (u_{2i} + u_{2i+1}; ofighters_amd.es.pair_utilities).  The library lists the
+ * pairs with d[i] != 0 OR s[i] != 0, ascending: leaving out a pair whose two weights are both zero changes no bit, and a
+ * listed pair whose d or whose s is zero adds +-0 to a sum that is never -0.0 - so g is exactly ofx_es_update's register
+ * sum.  Per element e, with THIRD = 0x1.5555555555555p-2 (eps's variance to the last bit but 2^-64), every line ONE
+ * separately rounded float64 operation, no FMA:
+ *   g = 0.0;  qs = 0.0
+ *   for each listed pair j, ascending:
+ *       x = eps(pair_j, e)
+ *       t = d[j] * x;   g = g + t
+ *       xx = x * x;  c = xx - THIRD;  u = s[j] * c;  qs = qs + u
+ *   sg   = sigma * g
+ *   ghat = gscale * sg
+ *   wd   = decay * theta
+ *   q    = ghat - wd
+ *   PLAIN:     step = alpha * q
+ *   MOMENTUM:  t1 = c1 * m;  t2 = k1 * q;  m' = t1 + t2;  step = alpha * m'
+ *   ADAM:      t1 = c1 * m;  t2 = k1 * q;  m' = t1 + t2;  qq = q * q;  t3 = c2 * v;  t4 = k2 * qq;  v' = t3 + t4
+ *              r = sqrt(v');  den = r + eps;  quo = m' / den;  step = alpha * quo
+ *   theta' = theta + step
+ *   r  = srate * qs
+ *   f  = 1.0 + r
+ *   sn = sigma * f
+ *   if sn < smin: sn = smin
+ *   if sn > smax: sn = smax
+ *   sigma' = sn
+ * The sigma read is the one the members flew with.  sigma[e] stands inside the law, so the caller's gscale is 1 / n_c
+ * (PEPG's form), not ofx_es_step's 1 / (n_c sigma).  PLAIN needs no moments; MOMENTUM and ADAM need ofx_es_opt_create's
+ * state (else OFX_ERR_STATE), MOMENTUM leaves v alone.  One kernel, one pass: theta, sigma, m, v are each read once and
+ * written once, coalesced; no floating-point atomics.
+ * STATS.  stats: DEVICE float64 [5] or NULL.  stats[0] = sum of q * q, stats[1] = sum of step * step, stats[2] = sum of
+ * theta' * theta', stats[3] = sum of sigma' * sigma', stats[4] = the number of elements a clamp changed (1.0 each), in
+ * ofx_es_step's summation order: the pairwise tree over the 256 positions of a workgroup, then one workgroup over the
+ * workgroup sums.  NULL compiles none of it and gives the same state bits.
+ * REFUSALS beyond those above (OFX_ERR_INVALID): NULL d_host or s_host; n_pairs outside [1, 2^30); a rule outside the
+ * three; any scalar, d[i] or s[i] not finite; decay < 0; eps <= 0 under ADAM; smin <= 0 or smax < smin.  Does not wait
+ * for the step (d and s are copied before the call returns).                                                          */
+int ofx_es_sigma_step(ofx_handle *h, const double *d_host, const double *s_host, int64_t n_pairs, int32_t rule,
+                      double gscale, double decay, double alpha, double c1, double k1, double c2, double k2, double eps,
+                      double srate, double smin, double smax, uint64_t seed, uint32_t generation, double *stats);
 
 /* ---- bi-head policy forward --------------------------------------------
  * Trainer.pointer_model graph + inference glue

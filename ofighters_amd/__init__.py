@@ -8,7 +8,7 @@ Battleground / Observation / Action / Agent interface.
 from . import _native
 from ._native import OfxError, BEHAVIOURS
 from .engine import ArenaBatch, DeviceBuffer, pack_actions, ACTION_DTYPE
-from .es import ES, ESRollout, pair_weights
+from .es import ES, ESRollout, pair_utilities, pair_weights
 
 __all__ = ["ArenaBatch", "DeviceBuffer", "pack_actions", "ACTION_DTYPE", "OfxError", "BEHAVIOURS", "_native",
-           "ES", "ESRollout", "pair_weights"]
+           "ES", "ESRollout", "pair_utilities", "pair_weights"]

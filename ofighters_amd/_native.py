@@ -30,6 +30,7 @@ BEHAVIOURS = {None: BOT_IDLE, "idle": BOT_IDLE, "random": BOT_RANDOM, "turret": 
 
 MAP_U8, MAP_F32, MAP_F64, MAP_BITS = range(4)
 ES_RULE_MOMENTUM, ES_RULE_ADAM = 1, 2        # ofx_es_step
+ES_RULE_PLAIN = 0                            # ofx_es_sigma_step takes all three
 OPT_TRUNK_PLAIN, OPT_FRAMES_REF, OPT_BILINEAR_LEGACY, OPT_TRUNK_FUSE, OPT_POLICY_BF16, OPT_FIT_PLAIN, OPT_TRUNK_SPARSE = 1, 2, 3, 4, 5, 6, 7   # ofx_set_option
 
 
@@ -141,6 +142,13 @@ SIGNATURES = {
     "ofx_es_opt_get": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ofx_es_opt_set": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ofx_es_step": (_i, [_vp, _vp, C.c_int64, C.c_int32] + [C.c_double] * 8 + [_u64, _u32, _vp]),
+    "ofx_es_sigma_create": (_i, [_vp, C.c_double]),
+    "ofx_es_sigma_destroy": (_i, [_vp]),
+    "ofx_es_sigma_get": (_i, [_vp, _vp, _vp]),
+    "ofx_es_sigma_set": (_i, [_vp, _vp, _vp]),
+    "ofx_es_sigma_member": (_i, [_vp, C.c_int64, C.c_int64, _u64, _u32, _vp, _vp]),
+    "ofx_es_sigma_act": (_i, [_vp, _vp, C.c_int64, _u64, _u32, _vp, _vp]),
+    "ofx_es_sigma_step": (_i, [_vp, _vp, _vp, C.c_int64, C.c_int32] + [C.c_double] * 11 + [_u64, _u32, _vp]),
     "ofx_policy_layout": (_i, [_vp, C.POINTER(OfxPolicyDesc)]),
     "ofx_policy_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ofx_policy_actions": (_i, [_vp, _vp, _vp, _vp, _vp]),

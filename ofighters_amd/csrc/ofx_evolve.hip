@@ -32,6 +32,8 @@
 // k_es_act / k_es_update / k_es_step / k_es_member  seeded evolution strategies, at the end of this file: one centre
 //              genome, the members' noise regenerated where it is read; k_es_act is pop_forward with another weight
 //              reader, k_es_step is k_es_update with momentum or Adam state beside the centre.
+// k_es_sigma_act / k_es_sigma_member / k_es_sigma_step  the same with a per-element exploration width sigma[e] beside
+//              the centre, learned in the pass that steps the centre (PEPG with symmetric sampling).
 #include "ofx_internal.h"
 #include "ofx_arena.h"
 
@@ -808,6 +810,10 @@ struct ofx_es {
   size_t d_cap;
   double *m, *v;            // [G] each, theta's layout: the optimiser's moments (ofx_es_opt_create), null = none
   double *part;             // [3][ceil(G / 256)] k_es_step's per-workgroup sums of q^2, step^2, theta'^2
+  double *sigma;            // [G] theta's layout: the per-element exploration width (ofx_es_sigma_create), null = none
+  double *s;                // [s_cap] the listed pairs' sigma weights of the running ofx_es_sigma_step, beside d / d_pair
+  size_t s_cap;
+  double *sigma_part;       // [5][ceil(G / 256)] k_es_sigma_step's per-workgroup sums, allocated with sigma
 };
 
 // eps(i, e): the four stream-12 words of (pair, element, generation) summed, centred and scaled to (-2, 2).  The words
@@ -969,21 +975,187 @@ __global__ __launch_bounds__(256) void k_es_step(double *theta, double *m, doubl
 }
 
 // stats[k] = the nb workgroup sums part[k][0 .. nb): thread t adds entries t, t + 256, ... in that order from 0.0, then
-// thread k adds the 256 thread sums in thread order.  One workgroup: the same bits every call.
+// thread k adds the 256 thread sums in thread order.  One workgroup: the same bits every call.  R rows: 3 for
+// ofx_es_step, 5 for ofx_es_sigma_step.
+template <int R>
 __global__ __launch_bounds__(256) void k_es_stats(const double *part, int nb, double *stats) {
-  __shared__ double sum[3][256];
+  __shared__ double sum[R][256];
   const int tid = threadIdx.x;
 #pragma unroll
-  for (int k = 0; k < 3; k++) {
+  for (int k = 0; k < R; k++) {
     double a = 0.0;
     for (int j = tid; j < nb; j += 256) a = a + part[(size_t)k * nb + j];
     sum[k][tid] = a;
   }
   __syncthreads();
-  if (tid < 3) {
+  if (tid < R) {
     double t = sum[tid][0];
     for (int q = 1; q < 256; q++) t = t + sum[tid][q];
     stats[tid] = t;
+  }
+}
+
+// ---- per-element adaptive sigma (include/ofx.h: ofx_es_sigma_*) ----
+// pop_forward's reader for member 2 * pair + b with a width per element: w = theta + ((sgn * sigma) * eps), sgn = +1 or
+// -1 (the sign is exact), the product rounded, then the sum.  sigma is read at the storage position theta is read at.
+struct es_sigma_member {
+  const double *theta, *sigma;
+  uint32_t nin, pair, generation;
+  ofx_rng_key key;
+  double sgn;
+  __device__ __forceinline__ double noisy(double w, double sg, uint32_t e) const {
+    const double ss = sgn * sg;
+    const double t = ss * es_eps(pair, e, generation, key);
+    return w + t;
+  }
+  __device__ __forceinline__ double first(size_t k, int o, int n1) const {
+    const size_t s = k * n1 + o;
+    return noisy(theta[s], sigma[s], (uint32_t)o * nin + (uint32_t)k);
+  }
+  __device__ __forceinline__ double at(size_t s) const { return noisy(theta[s], sigma[s], (uint32_t)s); }
+};
+
+// k_es_act with the es_sigma_member reader; the centre still goes through pop_stored
+__global__ __launch_bounds__(256) void k_es_sigma_act(int M, int W, int H, ofx_state st, const unsigned *ship_bits,
+                                                      const unsigned *laser_bits, int words, const double *theta,
+                                                      const double *sigma, int P, uint32_t first, uint32_t n_w,
+                                                      pop_net net, ofx_rng_key key, uint32_t generation,
+                                                      const int32_t *member_of, ofx_action *actions, double *y) {
+  __shared__ uint32_t list[4][POP_LIST];
+  __shared__ double part[4][64];
+  __shared__ double act[2][POP_MAX_WIDTH];
+  const int s = blockIdx.x, a = s / M;
+  const int32_t m = member_of[s];
+  if (m < 0 || m > P || !st.alive[s]) return;              // uniform over the workgroup
+  int cur;
+  if (m == P) {
+    const pop_stored rd = {theta};
+    cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, rd, first, n_w, net, list, part, act, nullptr);
+  } else {
+    const es_sigma_member rd = {theta, sigma, (uint32_t)net.layers[0], (uint32_t)m >> 1, generation, key,
+                                (m & 1) ? -1.0 : 1.0};
+    cur = pop_forward<false>(s, a, W, H, st, ship_bits, laser_bits, words, rd, first, n_w, net, list, part, act, nullptr);
+  }
+  pop_emit(s, W, H, act[cur], actions, y);
+}
+
+// out[s] = member `m` of P at storage position s under sigma[s] (m == P: the centre)
+__global__ __launch_bounds__(256) void k_es_sigma_member(const double *theta, const double *sigma, double *out,
+                                                         uint32_t G, uint32_t first, uint32_t nin, uint32_t n1, int m,
+                                                         int P, ofx_rng_key key, uint32_t generation) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= G) return;
+  double w = theta[s];
+  if (m != P) {
+    const double sgn = (m & 1) ? -1.0 : 1.0;
+    const double ss = sgn * sigma[s];
+    const double t = ss * es_eps((uint32_t)m >> 1, pop_element(s, first, nin, n1), generation, key);
+    w = w + t;
+  }
+  out[s] = w;
+}
+
+__global__ __launch_bounds__(256) void k_es_fill(double *out, uint32_t G, double value) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s < G) out[s] = value;
+}
+
+// the scalars ofx_es_sigma_step's law adds to es_law
+struct es_sigma_law {
+  double srate, smin, smax;
+};
+
+#define ES_SIGMA_THIRD 0x1.5555555555555p-2               /* eps's variance to the last bit but 2^-64 */
+
+// ofx_es_sigma_step: k_es_step's shape - one thread per storage position, the element by pop_element, the pair loop
+// inside - with a second register sum beside g: qs = sum s[j] * (eps^2 - 1/3), from the SAME eps evaluation, so the
+// G x n Philox evaluations of the step are not repeated for sigma.  theta, sigma, m and v lie at the same position:
+// each read once and written once, coalesced (PLAIN touches neither moment, MOMENTUM not v).  Every line is one rounded
+// float64 operation.  The optimiser's lines are restated from k_es_step, not shared with it, for the reason given at
+// its loop.  STATS: five workgroup sums - q^2, step^2, theta'^2, sigma'^2, clamped elements - in k_es_step's tree.
+template <int RULE, bool STATS>
+__global__ __launch_bounds__(256) void k_es_sigma_step(double *theta, double *sigma, double *m, double *v,
+                                                       const double *__restrict__ d, const double *__restrict__ sw,
+                                                       const uint32_t *__restrict__ d_pair, int n, uint32_t G,
+                                                       uint32_t first, uint32_t nin, uint32_t n1, es_law c,
+                                                       es_sigma_law z, ofx_rng_key key, uint32_t generation,
+                                                       double *part) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  double sq0 = 0.0, sq1 = 0.0, sq2 = 0.0, sq3 = 0.0, sq4 = 0.0;
+  if (s < G) {
+    const uint32_t e = pop_element(s, first, nin, n1);
+    double g = 0.0, qs = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < n; j++) {                          // d[j], sw[j], d_pair[j]: the same address in every lane
+      const double x = es_eps(d_pair[j], e, generation, key);
+      const double t = d[j] * x;
+      g = g + t;
+      const double xx = x * x;
+      const double cc = xx - ES_SIGMA_THIRD;
+      const double u = sw[j] * cc;
+      qs = qs + u;
+    }
+    const double w = theta[s];
+    const double sg = sigma[s];
+    const double sgg = sg * g;
+    const double ghat = c.gscale * sgg;
+    const double wd = c.decay * w;
+    const double q = ghat - wd;
+    double step;
+    if (RULE == OFX_ES_RULE_PLAIN) {
+      step = c.alpha * q;
+    } else {
+      const double t1 = c.c1 * m[s];
+      const double t2 = c.k1 * q;
+      const double mn = t1 + t2;
+      double quo = mn;
+      if (RULE == OFX_ES_RULE_ADAM) {
+        const double qq = q * q;
+        const double t3 = c.c2 * v[s];
+        const double t4 = c.k2 * qq;
+        const double vn = t3 + t4;
+        const double r = sqrt(vn);
+        const double den = r + c.eps;
+        quo = mn / den;
+        v[s] = vn;
+      }
+      step = c.alpha * quo;
+      m[s] = mn;
+    }
+    const double wn = w + step;
+    theta[s] = wn;
+    const double r = z.srate * qs;
+    const double f = 1.0 + r;
+    double sn = sg * f;
+    bool clamped = false;
+    if (sn < z.smin) { sn = z.smin; clamped = true; }
+    if (sn > z.smax) { sn = z.smax; clamped = true; }
+    sigma[s] = sn;
+    if (STATS) {
+      sq0 = q * q;
+      sq1 = step * step;
+      sq2 = wn * wn;
+      sq3 = sn * sn;
+      sq4 = clamped ? 1.0 : 0.0;
+    }
+  }
+  if (STATS) {
+    __shared__ double red[5][256];
+    const int tid = threadIdx.x;
+    red[0][tid] = sq0;
+    red[1][tid] = sq1;
+    red[2][tid] = sq2;
+    red[3][tid] = sq3;
+    red[4][tid] = sq4;
+    __syncthreads();
+    for (int stride = 128; stride > 0; stride >>= 1) {
+      if (tid < stride) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) red[k][tid] = red[k][tid] + red[k][tid + stride];
+      }
+      __syncthreads();
+    }
+    if (tid < 5) part[(size_t)tid * gridDim.x + blockIdx.x] = red[tid][0];
   }
 }
 
@@ -994,6 +1166,14 @@ static pop_net net_of(const ofx_es *p) {
   net.n_layers = p->n_layers;
   for (int i = 0; i < POP_MAX_LAYERS; i++) net.layers[i] = i < p->n_layers ? p->layers[i] : 0;
   return net;
+}
+
+static void es_sigma_free(ofx_es *p) {
+  if (p->sigma) (void)hipFree(p->sigma);
+  if (p->s) (void)hipFree(p->s);
+  if (p->sigma_part) (void)hipFree(p->sigma_part);
+  p->sigma = p->s = p->sigma_part = nullptr;
+  p->s_cap = 0;
 }
 
 static void es_opt_free(ofx_es *p) {
@@ -1011,6 +1191,7 @@ void ofx_es_free(ofx_handle *h) {
   if (p->d) (void)hipFree(p->d);
   if (p->d_pair) (void)hipFree(p->d_pair);
   es_opt_free(p);
+  es_sigma_free(p);
   delete p;
   es_of(h) = nullptr;
 }
@@ -1053,6 +1234,8 @@ extern "C" int ofx_es_create(ofx_handle *h, const int32_t *layers, int32_t n_lay
   p->m = p->v = p->part = nullptr;
   p->d_pair = nullptr;
   p->d_cap = 0;
+  p->sigma = p->s = p->sigma_part = nullptr;
+  p->s_cap = 0;
   const size_t bytes = (size_t)p->G * sizeof(double);
   const hipError_t e = hipMalloc((void **)&p->theta, bytes);
   if (e != hipSuccess) {
@@ -1101,6 +1284,19 @@ extern "C" int ofx_es_set(ofx_handle *h, const double *weights_host, const doubl
   return genome_from_host(h, p->theta, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
 }
 
+// the G-double buffer a member is materialised into, allocated at the first call that needs it (`who`)
+static int member_buffer(ofx_es *p, const char *who) {
+  if (p->member) return OFX_OK;
+  const hipError_t e = hipMalloc((void **)&p->member, (size_t)p->G * sizeof(double));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    p->member = nullptr;
+    ofx_set_error("%s: allocating %zu bytes failed: %s", who, (size_t)p->G * sizeof(double), hipGetErrorString(e));
+    return OFX_ERR_HIP;
+  }
+  return OFX_OK;
+}
+
 extern "C" int ofx_es_member(ofx_handle *h, int64_t member, int64_t P, double sigma, uint64_t seed, uint32_t generation,
                              double *weights_host, double *biases_host) {
   ofx_es *p;
@@ -1112,15 +1308,7 @@ extern "C" int ofx_es_member(ofx_handle *h, int64_t member, int64_t P, double si
     return OFX_ERR_INVALID;
   }
   OFX_HIP(hipSetDevice(h->cfg.device));
-  if (!p->member) {
-    const hipError_t e = hipMalloc((void **)&p->member, (size_t)p->G * sizeof(double));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p->member = nullptr;
-      ofx_set_error("ofx_es_member: allocating %zu bytes failed: %s", (size_t)p->G * sizeof(double), hipGetErrorString(e));
-      return OFX_ERR_HIP;
-    }
-  }
+  if ((rc = member_buffer(p, "ofx_es_member"))) return rc;
   hipLaunchKernelGGL(k_es_member, dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta, p->member, p->G, p->first,
                      (uint32_t)p->layers[0], (uint32_t)p->layers[1], (int)member, (int)P, sigma, ofx_key(seed), generation);
   OFX_HIP(hipGetLastError());
@@ -1326,10 +1514,195 @@ extern "C" int ofx_es_step(ofx_handle *h, const double *d_host, int64_t n_pairs,
     if (adam) launch_step<true, true>(h, p, n, law, seed, generation);
     else launch_step<false, true>(h, p, n, law, seed, generation);
     OFX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_es_stats, dim3(1), dim3(256), 0, h->stream, p->part, (int)((p->G + 255u) / 256u), stats);
+    hipLaunchKernelGGL(k_es_stats<3>, dim3(1), dim3(256), 0, h->stream, p->part, (int)((p->G + 255u) / 256u), stats);
   } else {
     if (adam) launch_step<true, false>(h, p, n, law, seed, generation);
     else launch_step<false, false>(h, p, n, law, seed, generation);
+  }
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// ---- per-element adaptive sigma (include/ofx.h: ofx_es_sigma_*) ----
+static int need_sigma(ofx_handle *h, const char *who, ofx_es **out) {
+  const int rc = need_es(h, who, out);
+  if (rc) return rc;
+  if (!(*out)->sigma) { ofx_set_error("%s: the centre has no sigma vector (ofx_es_sigma_create)", who); return OFX_ERR_STATE; }
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_sigma_create(ofx_handle *h, double sigma0) {
+  ofx_es *p;
+  const int rc = need_es(h, "ofx_es_sigma_create", &p);
+  if (rc) return rc;
+  if (p->sigma) { ofx_set_error("ofx_es_sigma_create: the centre already has a sigma vector (ofx_es_sigma_destroy)"); return OFX_ERR_STATE; }
+  if (!(sigma0 - sigma0 == 0.0) || !(sigma0 > 0.0)) {
+    ofx_set_error("ofx_es_sigma_create: sigma0 must be finite and > 0 (got %g)", sigma0);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const size_t bytes = (size_t)p->G * sizeof(double), nb = (p->G + 255u) / 256u;
+  hipError_t e = hipMalloc((void **)&p->sigma, bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&p->sigma_part, 5 * nb * sizeof(double));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    ofx_set_error("ofx_es_sigma_create: allocating %zu bytes for the sigma of %u elements failed: %s", bytes, p->G,
+                  hipGetErrorString(e));
+    es_sigma_free(p);
+    return OFX_ERR_HIP;
+  }
+  hipLaunchKernelGGL(k_es_fill, dim3((unsigned)nb), dim3(256), 0, h->stream, p->sigma, p->G, sigma0);
+  e = hipGetLastError();
+  if (e != hipSuccess) {
+    ofx_set_error("ofx_es_sigma_create: filling the vector failed: %s", hipGetErrorString(e));
+    (void)hipStreamSynchronize(h->stream);
+    es_sigma_free(p);
+    return OFX_ERR_HIP;
+  }
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_sigma_destroy(ofx_handle *h) {
+  ofx_es *p;
+  const int rc = need_sigma(h, "ofx_es_sigma_destroy", &p);
+  if (rc) return rc;
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  OFX_HIP(hipStreamSynchronize(h->stream));
+  es_sigma_free(p);
+  return OFX_OK;
+}
+
+extern "C" int ofx_es_sigma_get(ofx_handle *h, double *weights_host, double *biases_host) {
+  ofx_es *p;
+  int rc = need_sigma(h, "ofx_es_sigma_get", &p);
+  if (rc) return rc;
+  if (!weights_host || !biases_host) { ofx_set_error("ofx_es_sigma_get: null argument"); return OFX_ERR_INVALID; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  return genome_to_host(h, p->sigma, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
+}
+
+extern "C" int ofx_es_sigma_set(ofx_handle *h, const double *weights_host, const double *biases_host) {
+  ofx_es *p;
+  int rc = need_sigma(h, "ofx_es_sigma_set", &p);
+  if (rc) return rc;
+  if (!weights_host || !biases_host) { ofx_set_error("ofx_es_sigma_set: null argument"); return OFX_ERR_INVALID; }
+  for (uint32_t i = 0; i < p->G; i++) {
+    const double x = i < p->n_w ? weights_host[i] : biases_host[i - p->n_w];
+    if (!(x - x == 0.0) || !(x > 0.0)) {
+      ofx_set_error("ofx_es_sigma_set: sigma[%u] must be finite and > 0 (got %g)", i, x);
+      return OFX_ERR_INVALID;
+    }
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  return genome_from_host(h, p->sigma, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
+}
+
+extern "C" int ofx_es_sigma_member(ofx_handle *h, int64_t member, int64_t P, uint64_t seed, uint32_t generation,
+                                   double *weights_host, double *biases_host) {
+  ofx_es *p;
+  int rc = need_sigma(h, "ofx_es_sigma_member", &p);
+  if (rc || (rc = check_members("ofx_es_sigma_member", P, 1.0))) return rc;
+  if (!weights_host || !biases_host) { ofx_set_error("ofx_es_sigma_member: null argument"); return OFX_ERR_INVALID; }
+  if (member < 0 || member > P) {
+    ofx_set_error("ofx_es_sigma_member: member %lld outside [0, %lld] (P is the centre)", (long long)member, (long long)P);
+    return OFX_ERR_INVALID;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  if ((rc = member_buffer(p, "ofx_es_sigma_member"))) return rc;
+  hipLaunchKernelGGL(k_es_sigma_member, dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta, p->sigma, p->member,
+                     p->G, p->first, (uint32_t)p->layers[0], (uint32_t)p->layers[1], (int)member, (int)P, ofx_key(seed),
+                     generation);
+  OFX_HIP(hipGetLastError());
+  return genome_to_host(h, p->member, p->layers, p->first, p->n_w, p->G, weights_host, biases_host);
+}
+
+extern "C" int ofx_es_sigma_act(ofx_handle *h, const int32_t *member_of, int64_t P, uint64_t seed, uint32_t generation,
+                                ofx_action *actions, double *y) {
+  ofx_es *p;
+  int rc = need_sigma(h, "ofx_es_sigma_act", &p);
+  if (rc || (rc = check_members("ofx_es_sigma_act", P, 1.0))) return rc;
+  if (!member_of || !actions) { ofx_set_error("ofx_es_sigma_act: null argument"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("You must execute analyse_battleground first."); return OFX_ERR_STATE; }
+  const ofx_config &c = h->cfg;
+  OFX_HIP(hipSetDevice(c.device));
+  if ((rc = ofx_launch_raster(h, OFX_MAP_BITS_LSB, nullptr, nullptr))) return rc;
+  const pop_net net = net_of(p);
+  const int words = (int)(((size_t)c.width * c.height) >> 5);
+  hipLaunchKernelGGL(k_es_sigma_act, dim3((unsigned)(c.n_arenas * c.n_ships)), dim3(256), 0, h->stream, c.n_ships,
+                     c.width, c.height, h->st, (const unsigned *)h->maps[OFX_MAP_BITS_LSB][0],
+                     (const unsigned *)h->maps[OFX_MAP_BITS_LSB][1], words, p->theta, p->sigma, (int)P, p->first, p->n_w,
+                     net, ofx_key(seed), generation, member_of, actions, y);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
+}
+
+// the listed pairs' sigma weights into the centre's device copy, after upload_pairs (which has synchronised)
+static int upload_sigma_weights(ofx_es *p, const std::vector<double> &s) {
+  if (s.size() > p->s_cap) {
+    if (p->s) (void)hipFree(p->s);
+    p->s = nullptr;
+    p->s_cap = 0;
+    OFX_HIP(hipMalloc((void **)&p->s, s.size() * sizeof(double)));
+    p->s_cap = s.size();
+  }
+  if (!s.empty()) OFX_HIP(hipMemcpy(p->s, s.data(), s.size() * sizeof(double), hipMemcpyHostToDevice));
+  return OFX_OK;
+}
+
+template <int RULE, bool STATS>
+static void launch_sigma_step(ofx_handle *h, ofx_es *p, int n, const es_law &law, const es_sigma_law &z, uint64_t seed,
+                              uint32_t generation) {
+  hipLaunchKernelGGL((k_es_sigma_step<RULE, STATS>), dim3((p->G + 255u) / 256u), dim3(256), 0, h->stream, p->theta,
+                     p->sigma, p->m, p->v, p->d, p->s, p->d_pair, n, p->G, p->first, (uint32_t)p->layers[0],
+                     (uint32_t)p->layers[1], law, z, ofx_key(seed), generation, p->sigma_part);
+}
+
+extern "C" int ofx_es_sigma_step(ofx_handle *h, const double *d_host, const double *s_host, int64_t n_pairs, int32_t rule,
+                                 double gscale, double decay, double alpha, double c1, double k1, double c2, double k2,
+                                 double eps, double srate, double smin, double smax, uint64_t seed, uint32_t generation,
+                                 double *stats) {
+  ofx_es *p;
+  int rc = need_sigma(h, "ofx_es_sigma_step", &p);
+  if (rc || (rc = check_pairs("ofx_es_sigma_step", d_host, n_pairs))) return rc;
+  if (!s_host) { ofx_set_error("ofx_es_sigma_step: null argument"); return OFX_ERR_INVALID; }
+  if (rule != OFX_ES_RULE_PLAIN && rule != OFX_ES_RULE_MOMENTUM && rule != OFX_ES_RULE_ADAM) {
+    ofx_set_error("ofx_es_sigma_step: rule must be OFX_ES_RULE_PLAIN (0), _MOMENTUM (1) or _ADAM (2) (got %d)", rule);
+    return OFX_ERR_INVALID;
+  }
+  const es_law law = {gscale, decay, alpha, c1, k1, c2, k2, eps};
+  const es_sigma_law z = {srate, smin, smax};
+  const double scalars[11] = {gscale, decay, alpha, c1, k1, c2, k2, eps, srate, smin, smax};
+  static const char *const names[11] = {"gscale", "decay", "alpha", "c1", "k1", "c2", "k2", "eps", "srate", "smin", "smax"};
+  for (int i = 0; i < 11; i++)
+    if (!(scalars[i] - scalars[i] == 0.0)) { ofx_set_error("ofx_es_sigma_step: %s is not finite", names[i]); return OFX_ERR_INVALID; }
+  if (decay < 0.0) { ofx_set_error("ofx_es_sigma_step: decay must be >= 0 (got %g)", decay); return OFX_ERR_INVALID; }
+  if (rule == OFX_ES_RULE_ADAM && !(eps > 0.0)) { ofx_set_error("ofx_es_sigma_step: eps must be > 0 under Adam (got %g)", eps); return OFX_ERR_INVALID; }
+  if (!(smin > 0.0)) { ofx_set_error("ofx_es_sigma_step: smin must be > 0 (got %g)", smin); return OFX_ERR_INVALID; }
+  if (smax < smin) { ofx_set_error("ofx_es_sigma_step: smax must be >= smin (got smax %g, smin %g)", smax, smin); return OFX_ERR_INVALID; }
+  if (rule != OFX_ES_RULE_PLAIN && !p->m) {
+    ofx_set_error("ofx_es_sigma_step: the centre has no optimiser state (ofx_es_opt_create), which rule %d needs", rule);
+    return OFX_ERR_STATE;
+  }
+  // the pairs with either weight, ascending: a pair with both zero adds +-0 to two sums that are never -0.0
+  std::vector<double> d, s;
+  std::vector<uint32_t> pair;
+  for (int64_t i = 0; i < n_pairs; i++) {
+    if (!(d_host[i] - d_host[i] == 0.0)) { ofx_set_error("ofx_es_sigma_step: d[%lld] is not finite", (long long)i); return OFX_ERR_INVALID; }
+    if (!(s_host[i] - s_host[i] == 0.0)) { ofx_set_error("ofx_es_sigma_step: s[%lld] is not finite", (long long)i); return OFX_ERR_INVALID; }
+    if (d_host[i] != 0.0 || s_host[i] != 0.0) { d.push_back(d_host[i]); s.push_back(s_host[i]); pair.push_back((uint32_t)i); }
+  }
+  if ((rc = upload_pairs(h, p, d, pair)) || (rc = upload_sigma_weights(p, s))) return rc;
+  const int n = (int)d.size();
+  if (stats) {
+    if (rule == OFX_ES_RULE_ADAM) launch_sigma_step<OFX_ES_RULE_ADAM, true>(h, p, n, law, z, seed, generation);
+    else if (rule == OFX_ES_RULE_MOMENTUM) launch_sigma_step<OFX_ES_RULE_MOMENTUM, true>(h, p, n, law, z, seed, generation);
+    else launch_sigma_step<OFX_ES_RULE_PLAIN, true>(h, p, n, law, z, seed, generation);
+    OFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_es_stats<5>, dim3(1), dim3(256), 0, h->stream, p->sigma_part, (int)((p->G + 255u) / 256u), stats);
+  } else {
+    if (rule == OFX_ES_RULE_ADAM) launch_sigma_step<OFX_ES_RULE_ADAM, false>(h, p, n, law, z, seed, generation);
+    else if (rule == OFX_ES_RULE_MOMENTUM) launch_sigma_step<OFX_ES_RULE_MOMENTUM, false>(h, p, n, law, z, seed, generation);
+    else launch_sigma_step<OFX_ES_RULE_PLAIN, false>(h, p, n, law, z, seed, generation);
   }
   OFX_HIP(hipGetLastError());
   return OFX_OK;

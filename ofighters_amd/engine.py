@@ -1163,3 +1163,46 @@ class ArenaBatch:
         nat.check(nat.lib().ofx_es_step(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(rule), float(gscale),
                                         float(decay), float(alpha), float(c1), float(k1), float(c2), float(k2),
                                         float(eps), seed, int(generation), stats_ptr))
+
+    # ------------------------------------------------------------ per-element adaptive sigma (ofx_es_sigma_*)
+    def es_sigma_create(self, sigma0):
+        """The centre's exploration width per element, every element sigma0, in theta's layout (ofx_es_sigma_create)."""
+        nat.check(nat.lib().ofx_es_sigma_create(self._h, float(sigma0)))
+
+    def es_sigma_destroy(self):
+        nat.check(nat.lib().ofx_es_sigma_destroy(self._h))
+
+    def es_sigma_get(self, n_weights, n_biases):
+        """sigma as (weights float64 [n_weights], biases float64 [n_biases]) in the element order.  Synchronises."""
+        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
+        nat.check(nat.lib().ofx_es_sigma_get(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def es_sigma_set(self, weights, biases):
+        w, b = np.ascontiguousarray(weights, dtype=np.float64), np.ascontiguousarray(biases, dtype=np.float64)
+        nat.check(nat.lib().ofx_es_sigma_set(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+
+    def es_sigma_member(self, member, P, seed, generation, n_weights, n_biases):
+        """es_member under the sigma vector: theta[e] + (+-sigma[e]) * eps(i, e).  Synchronises."""
+        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
+        nat.check(nat.lib().ofx_es_sigma_member(self._h, int(member), int(P), seed, int(generation),
+                                                w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return w, b
+
+    def es_sigma_act(self, member_of_ptr, P, seed, generation, out_ptr=None, y_ptr=None):
+        """es_act under the sigma vector.  Does not synchronise."""
+        nat.check(nat.lib().ofx_es_sigma_act(self._h, member_of_ptr, int(P), seed, int(generation),
+                                             out_ptr or self._actions.ptr, y_ptr))
+
+    def es_sigma_step(self, d, s, rule, gscale, decay, alpha, c1, k1, c2, k2, eps, srate, smin, smax, seed, generation,
+                      stats_ptr=None):
+        """The generation step of the centre and of sigma in one pass (ofx_es_sigma_step: the law, line by line); d, s:
+        float64 [P / 2], rule: nat.ES_RULE_PLAIN, _MOMENTUM or _ADAM, stats_ptr: device float64 [5] or None.  Does not
+        wait for the step."""
+        a, w = np.ascontiguousarray(d, dtype=np.float64), np.ascontiguousarray(s, dtype=np.float64)
+        if a.ndim != 1 or a.shape != w.shape:
+            raise ValueError("d and s are float64 [P / 2] arrays of one length, got %s and %s" % (a.shape, w.shape))
+        nat.check(nat.lib().ofx_es_sigma_step(self._h, a.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                              a.shape[0], int(rule), float(gscale), float(decay), float(alpha), float(c1),
+                                              float(k1), float(c2), float(k2), float(eps), float(srate), float(smin),
+                                              float(smax), seed, int(generation), stats_ptr))

@@ -7,11 +7,23 @@ generation) on the project's counter RNG, and a generation ends in a rank-weight
 regenerates the noise of the rows it gathers inside the kernel, so a population of any P costs one genome of memory.
 
     pair_weights  fitness sums -> the weight of every mirrored pair (centred average ranks): pure numpy, no randomness
-    ES            owns the ofx_es_* calls of one ArenaBatch; opt-in momentum / Adam and weight decay for the centre
+    pair_utilities  the same ranks -> (d, s): the pair's weight for the centre and for sigma (adaptive mode)
+    ES            owns the ofx_es_* calls of one ArenaBatch; opt-in momentum / Adam and weight decay for the centre,
+                  opt-in per-element adaptive sigma
     ESRollout     the generational loop around ShardedRollout's lock-step
 
 eps has variance 1/3 (an Irwin-Hall sum of four uniforms in (-2, 2)): sigma and lr are in units of that eps.  Whether
 the fitness rises is an observation (tools/es_time.py records it), not a property any test holds the code to.
+
+Adaptive mode (ES(..., sigma_init=...)) is parameter-exploring policy gradients with symmetric sampling (Sehnke et al.
+2010; the separable case of NES): every element e has its own exploration width sigma[e] in HBM beside the centre, member
+m = 2 i + b is theta[e] +- sigma[e] * eps(i, e), and ONE kernel steps both from the same noise - the centre on
+sum_i d_i eps, sigma on sum_i s_i (eps^2 - 1/3) with s_i = u_{2i} + u_{2i+1}, the pair's utility against the baseline 0
+of the centred ranks.  In this mode `lr` multiplies sigma[e] * sum_i d_i eps(i, e) / n_c, which is PEPG's form (the step
+of an element is proportional to its own width); the scalar path's estimate is sum_i d_i eps(i, e) / (n_c sigma), OpenAI-ES's
+(inversely proportional to the one width).  At equal sigma the two differ by the factor sigma^2: an `lr` tuned for one
+mode is not the other's.  sigma[e] itself moves by sigma *= 1 + sigma_lr / n_c * sum_i s_i (eps^2 - 1/3), clamped to
+[sigma_min, sigma_max].
 """
 import math
 
@@ -74,6 +86,35 @@ def pair_weights(sum, count):
     return d, n_c
 
 
+def pair_utilities(sum, count):
+    """(d float64 [P/2], s float64 [P/2], n_c) for the adaptive step: d and n_c exactly pair_weights', and
+        s_i = u_{2i} + u_{2i+1}
+    for complete pairs - the pair's mean utility against the baseline, which is 0 because the ranks are centred (the u
+    of the n_c members sum to 0).  A pair both of whose members beat the median has s > 0 and widens sigma where its
+    noise was large; swapping a pair's fitness leaves s and negates d.  Incomplete pairs get 0; n_c < 2 or all means
+    equal gives all zeros.  Pure numpy, no randomness."""
+    s, c = np.asarray(sum, np.int64), np.asarray(count, np.int64)
+    if s.ndim != 1 or s.shape != c.shape or s.shape[0] < 2:
+        raise ValueError("sum and count are [P] or [P + 1] arrays, got %s and %s" % (s.shape, c.shape))
+    n_pairs = s.shape[0] // 2
+    s, c = s[:2 * n_pairs].reshape(n_pairs, 2), c[:2 * n_pairs].reshape(n_pairs, 2)
+    complete = (c > 0).all(axis=1)
+    n_c = 2 * int(complete.sum())
+    d, w = np.zeros(n_pairs, np.float64), np.zeros(n_pairs, np.float64)
+    if n_c < 2:
+        return d, w, n_c
+    mean = (s[complete] / c[complete]).ravel()
+    values, inverse, counts = np.unique(mean, return_inverse=True, return_counts=True)
+    if values.size == 1:
+        return d, w, n_c
+    below = np.cumsum(counts) - counts                     # as in pair_weights, operation for operation
+    rank = (below + (counts - 1) / 2.0)[inverse]
+    u = (rank / (n_c - 1) - 0.5).reshape(-1, 2)
+    d[complete] = u[:, 0] - u[:, 1]
+    w[complete] = u[:, 0] + u[:, 1]
+    return d, w, n_c
+
+
 def es_meta(layers, seed):
     return {"layers": [int(v) for v in layers], "seed": int(seed)}
 
@@ -98,8 +139,9 @@ def check_es_meta(meta, shape, dtype, layers, seed, path="the checkpoint"):
 OPTIMIZERS = ("momentum", "adam")
 
 
-def check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay):
-    """ES's optimiser arguments, checked before the library is touched: ValueError naming the argument."""
+def check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay, adaptive=False):
+    """ES's optimiser arguments, checked before the library is touched: ValueError naming the argument.  `adaptive`: the
+    step is ofx_es_sigma_step's, whose PLAIN rule has a decay term."""
     if optimizer is not None and optimizer not in OPTIMIZERS:
         raise ValueError("optimizer must be None, 'momentum' or 'adam', got %r" % (optimizer,))
     for name, beta in (("beta1", beta1), ("beta2", beta2)):
@@ -109,7 +151,7 @@ def check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay):
         raise ValueError("adam_eps must be finite and > 0, got %r" % (adam_eps,))
     if not (math.isfinite(weight_decay) and weight_decay >= 0):
         raise ValueError("weight_decay must be finite and >= 0, got %r" % (weight_decay,))
-    if weight_decay != 0 and optimizer is None:
+    if weight_decay != 0 and optimizer is None and not adaptive:
         raise ValueError("weight_decay needs an optimizer: the bare update has no decay term")
 
 
@@ -161,6 +203,61 @@ def moments_path(path):
     return path + ".opt.npy"
 
 
+def check_sigma_args(sigma_init, sigma_lr, sigma_min, sigma_max):
+    """ES's adaptive-sigma arguments, checked before the library is touched: ValueError naming the argument.  Returns
+    None when sigma_init is None (no adaptation), else (sigma_init, sigma_lr, sigma_min, sigma_max) as floats with the
+    defaults sigma_min = sigma_init / 64 and sigma_max = sigma_init * 4 filled in."""
+    if sigma_init is None:
+        if sigma_min is not None or sigma_max is not None:
+            raise ValueError("sigma_min and sigma_max need sigma_init: without it sigma is not adapted")
+        return None
+    if not (math.isfinite(sigma_init) and sigma_init > 0):
+        raise ValueError("sigma_init must be finite and > 0, got %r" % (sigma_init,))
+    if not (math.isfinite(sigma_lr) and sigma_lr >= 0):
+        raise ValueError("sigma_lr must be finite and >= 0, got %r" % (sigma_lr,))
+    lo = float(sigma_init) / 64 if sigma_min is None else sigma_min
+    hi = float(sigma_init) * 4 if sigma_max is None else sigma_max
+    if not (math.isfinite(lo) and lo > 0):
+        raise ValueError("sigma_min must be finite and > 0, got %r" % (sigma_min,))
+    if not (math.isfinite(hi) and hi >= lo):
+        raise ValueError("sigma_max must be finite and >= sigma_min, got %r (sigma_min %r)" % (sigma_max, lo))
+    if not (lo <= sigma_init <= hi):
+        raise ValueError("sigma_init must lie in [sigma_min, sigma_max] = [%r, %r], got %r" % (lo, hi, sigma_init))
+    return float(sigma_init), float(sigma_lr), float(lo), float(hi)
+
+
+def es_sigma_meta(sigma_lr, sigma_min, sigma_max):
+    return {"lr": float(sigma_lr), "min": float(sigma_min), "max": float(sigma_max)}
+
+
+def check_es_sigma_meta(meta, want, shape=None, dtype=None, elements=None, path="the checkpoint"):
+    """ES.load's refusals about the sigma vector, before anything is touched: ValueError naming the first field that
+    differs.  `meta` is the sidecar, `want` this ES's es_sigma_meta (None: not adaptive).  The "sigma" block must be
+    there exactly when this ES is adaptive, and equal `want`; shape / dtype, when given, are those of the sigma array,
+    float64 [elements]."""
+    block = meta.get("sigma")
+    if want is None:
+        if block is not None:
+            raise ValueError("%s: the sidecar has a sigma block, this ES does not adapt sigma" % path)
+        return
+    if block is None:
+        raise ValueError("%s: the sidecar has no sigma block, this ES adapts sigma" % path)
+    for field in ("lr", "min", "max"):
+        if field not in block:
+            raise ValueError("%s: the sigma block has no field %r" % (path, field))
+        if float(block[field]) != want[field]:
+            raise ValueError("%s: sigma %s is %r, this ES's is %r" % (path, field, float(block[field]), want[field]))
+    if shape is not None and tuple(shape) != (elements,):
+        raise ValueError("%s: the sigma array's shape is %r, a sigma of %d elements is %r" % (path, tuple(shape), elements,
+                                                                                           (elements,)))
+    if dtype is not None and np.dtype(dtype) != np.float64:
+        raise ValueError("%s: the sigma array's dtype is %s, it is float64" % (path, np.dtype(dtype)))
+
+
+def sigma_path(path):
+    return path + ".sigma.npy"
+
+
 class ES:
     """One ES centre of the scratch MLP `layers` on the device of `batch` (an ArenaBatch), beside any Population the
     batch holds; initialised to the fresh genome of slot 0 from `seed` (the law of Population's init).
@@ -171,12 +268,20 @@ class ES:
                what it always was.  "momentum" or "adam": the centre gets the moments m and v in HBM (3 genomes instead
                of 1, still at any P) and `update` feeds the estimate minus weight_decay * theta through ofx_es_step
                (include/ofx.h states the law); `opt_steps` counts the steps, 1-based, and is the t of Adam's bias
-               correction.  beta1 is the momentum (both rules), beta2 and adam_eps are Adam's."""
+               correction.  beta1 is the momentum (both rules), beta2 and adam_eps are Adam's.
+    sigma_init  None (default): one scalar sigma, the caller's, at every call.  A number turns ADAPTATION on
+               (`adaptive`): the centre gets a width per element in HBM (one more genome), every element sigma_init, and
+               act / member / update take sigma=None and go to the ofx_es_sigma_* calls; `update` needs the pair
+               utilities `s` beside `d` (pair_utilities) and steps theta and sigma in one kernel (include/ofx.h states
+               the law; the module docstring what `lr` multiplies here).  sigma_lr is the rate of the sigma step,
+               sigma_min / sigma_max its clamp (defaults sigma_init / 64 and sigma_init * 4).  Works with optimizer=None
+               (the PLAIN rule, which then also takes weight_decay), "momentum" and "adam"."""
 
     def __init__(self, batch, layers, seed, optimizer=None, beta1=0.9, beta2=0.999, adam_eps=1e-8, weight_decay=0.0,
-                 init=True):
+                 init=True, sigma_init=None, sigma_lr=0.2, sigma_min=None, sigma_max=None):
         from .engine import DeviceBuffer
-        check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay)
+        adapt = check_sigma_args(sigma_init, sigma_lr, sigma_min, sigma_max)
+        check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay, adaptive=adapt is not None)
         self.b = batch
         self.layers = [int(v) for v in layers]
         self.seed = int(seed)
@@ -186,8 +291,14 @@ class ES:
         self.weight_decay = float(weight_decay)
         self.opt_steps = 0
         batch.es_create(self.layers)
+        self.adaptive = adapt is not None
         if optimizer is not None:
             batch.es_opt_create()
+        if self.adaptive:
+            self.sigma_init, self.sigma_lr, self.sigma_min, self.sigma_max = adapt
+            batch.es_sigma_create(self.sigma_init)
+            self._stats = DeviceBuffer(5 * 8).upload(np.zeros(5, np.float64))
+        elif optimizer is not None:
             self._stats = DeviceBuffer(3 * 8).upload(np.zeros(3, np.float64))
         self._member_of = DeviceBuffer(batch.N * batch.M * 4)
         self.P, self.member_of = None, None
@@ -226,12 +337,37 @@ class ES:
         if self.optimizer is None:
             raise ValueError("this ES has no optimizer: construct it with optimizer='momentum' or 'adam'")
 
+    def sigmas(self):
+        """(weights_layers, biases_layers) of the sigma vector, in the shapes of centre().  Synchronises."""
+        self._is_adaptive()
+        return split_genome(self.layers, *self.b.es_sigma_get(self.n_weights, self.n_biases))
+
+    def set_sigmas(self, weights_layers, biases_layers):
+        """Put back what sigmas() returned; every element finite and > 0."""
+        self._is_adaptive()
+        self.b.es_sigma_set(*join_genome(self.layers, weights_layers, biases_layers))
+
+    def _is_adaptive(self):
+        if not self.adaptive:
+            raise ValueError("this ES does not adapt sigma: construct it with sigma_init")
+
+    def _check_sigma(self, sigma):
+        """sigma is the caller's number, or None exactly when this ES adapts its own: nothing is silently ignored."""
+        if self.adaptive and sigma is not None:
+            raise ValueError("sigma must be None: this ES adapts sigma per element (sigma_init), got %r" % (sigma,))
+        if not self.adaptive and sigma is None:
+            raise ValueError("sigma must be a number: this ES does not adapt sigma (no sigma_init)")
+
     def member(self, m, P, sigma, generation):
         """(weights_layers, biases_layers) of member m of P at `generation` (m == P: the centre), materialised on the
-        device: what Population.set_genome takes."""
+        device: what Population.set_genome takes.  Adaptive: sigma is None."""
+        self._check_sigma(sigma)
         P = check_members(P, sigma)
         if not (0 <= int(m) <= P):
             raise ValueError("member %d outside [0, %d]" % (m, P))
+        if self.adaptive:
+            return split_genome(self.layers, *self.b.es_sigma_member(m, P, self.seed, generation, self.n_weights,
+                                                                     self.n_biases))
         return split_genome(self.layers, *self.b.es_member(m, P, sigma, self.seed, generation, self.n_weights,
                                                            self.n_biases))
 
@@ -255,9 +391,14 @@ class ES:
             raise ValueError("no assignment yet: call assign(member_of, P) first")
 
     def act(self, sigma, generation, y_ptr=None):
-        """Overwrite the evolved ships' entries of the batch's action array (after bot_actions, before step)."""
+        """Overwrite the evolved ships' entries of the batch's action array (after bot_actions, before step).  Adaptive:
+        sigma is None."""
+        self._check_sigma(sigma)
         self._assigned()
         check_members(self.P, sigma)
+        if self.adaptive:
+            self.b.es_sigma_act(self._member_of.ptr, self.P, self.seed, generation, y_ptr=y_ptr)
+            return
         self.b.es_act(self._member_of.ptr, self.P, sigma, self.seed, generation, y_ptr=y_ptr)
 
     def fitness(self, reset=False):
@@ -281,18 +422,43 @@ class ES:
         self._sum.upload(s)
         self._count.upload(c)
 
-    def update(self, d, lr, sigma, n_c, generation):
+    def update(self, d, lr, sigma, n_c, generation, s=None):
         """The generation step theta += lr / (n_c sigma) * sum_i d_i eps(i, .) on the noise of `generation`, the one the
         members flew with; (d, n_c) from pair_weights.  The scale is computed in Python floats, in that order.
 
         With an optimizer: opt_steps += 1 and the step goes through ofx_es_step with the scalars of step_scalars; its
-        three sums wait in the ES's stats buffer for step_stats()."""
+        three sums wait in the ES's stats buffer for step_stats().
+
+        Adaptive: sigma is None and `s` (pair_utilities) is required; theta and sigma[e] step in one kernel
+        (ofx_es_sigma_step) with gscale = 1.0 / n_c - sigma[e] is inside the law - srate = sigma_lr / n_c, alpha as
+        step_scalars computes it (lr itself for the PLAIN rule); opt_steps counts as before (with an optimizer) and
+        the five sums wait for step_stats()."""
+        self._check_sigma(sigma)
+        if self.adaptive and s is None:
+            raise ValueError("s is required: the adaptive step needs the pair utilities (pair_utilities)")
+        if not self.adaptive and s is not None:
+            raise ValueError("s must be None: this ES does not adapt sigma (no sigma_init)")
         d = np.asarray(d, np.float64)
         if d.ndim != 1 or d.shape[0] < 1 or not np.isfinite(d).all():
             raise ValueError("d is a finite float64 [P / 2], got %s" % (d.shape,))
         check_members(2 * d.shape[0], sigma)
         if int(n_c) < 2 or not math.isfinite(lr):
             raise ValueError("update needs n_c >= 2 and a finite lr, got n_c = %r, lr = %r" % (n_c, lr))
+        if self.adaptive:
+            from . import _native as nat
+            s = np.asarray(s, np.float64)
+            if s.shape != d.shape or not np.isfinite(s).all():
+                raise ValueError("s is a finite float64 [P / 2] like d, got %s" % (s.shape,))
+            alpha, c1, k1, c2, k2 = float(lr), 0.0, 1.0, 0.0, 1.0
+            rule = nat.ES_RULE_PLAIN
+            if self.optimizer is not None:
+                self.opt_steps += 1
+                _, alpha, c1, k1, c2, k2 = step_scalars(self.optimizer, lr, 1.0, n_c, self.opt_steps, self.beta1, self.beta2)
+                rule = nat.ES_RULE_MOMENTUM if self.optimizer == "momentum" else nat.ES_RULE_ADAM
+            self.b.es_sigma_step(d, s, rule, 1.0 / int(n_c), self.weight_decay, alpha, c1, k1, c2, k2, self.adam_eps,
+                                 self.sigma_lr / int(n_c), self.sigma_min, self.sigma_max, self.seed, generation,
+                                 stats_ptr=self._stats.ptr)
+            return
         if self.optimizer is None:
             scale = float(lr) / (int(n_c) * float(sigma))
             self.b.es_update(d, scale, self.seed, generation)
@@ -306,7 +472,11 @@ class ES:
 
     def step_stats(self):
         """(grad_sq, step_sq, centre_sq) of the last optimiser step: the sums over the genome of q^2 (the estimate minus
-        the decay term), of step^2 and of theta'^2, zeros before the first step.  Synchronises."""
+        the decay term), of step^2 and of theta'^2, zeros before the first step.  Adaptive: five numbers - those three, the
+        sum of sigma'^2 and the number of elements a clamp changed.  Synchronises."""
+        if self.adaptive:
+            self.b.sync()
+            return tuple(float(x) for x in self._stats.download(np.float64, (5,)))
         self._has_optimizer()
         self.b.sync()
         return tuple(float(x) for x in self._stats.download(np.float64, (3,)))
@@ -316,7 +486,8 @@ class ES:
         """The centre as ONE .npy at `path`, float64 [n_weights + n_biases] in the element order, and the sidecar
         `path + ".json"` with layers and seed.  With an optimizer also `path + ".opt.npy"`, float64 [2][elements], m
         then v in the element order, and the sidecar's "optimizer" block (rule, betas, eps, weight_decay, steps).
-        Returns path."""
+        Adaptive: also `path + ".sigma.npy"`, float64 [elements] in the element order, and the sidecar's "sigma" block
+        (lr, min, max).  Returns path."""
         import json
         w, b = self.b.es_get(self.n_weights, self.n_biases)
         meta = es_meta(self.layers, self.seed)
@@ -325,6 +496,10 @@ class ES:
             with open(moments_path(path), "wb") as f:
                 np.save(f, np.stack([np.concatenate(m), np.concatenate(v)]))
             meta["optimizer"] = self._opt_meta()
+        if self.adaptive:
+            with open(sigma_path(path), "wb") as f:
+                np.save(f, np.concatenate(self.b.es_sigma_get(self.n_weights, self.n_biases)))
+            meta["sigma"] = self._sigma_meta()
         with open(path, "wb") as f:
             np.save(f, np.concatenate([w, b]))
         with open(sidecar_path(path), "w") as f:
@@ -336,11 +511,15 @@ class ES:
             return None
         return es_opt_meta(self.optimizer, self.beta1, self.beta2, self.adam_eps, self.weight_decay, self.opt_steps)
 
+    def _sigma_meta(self):
+        return es_sigma_meta(self.sigma_lr, self.sigma_min, self.sigma_max) if self.adaptive else None
+
     def load(self, path):
         """The centre `save` wrote, into this ES.  ValueError naming the field, with the centre untouched, when the
         checkpoint's layers or seed (or the array's shape or dtype) differ from this ES's - or when its optimizer block
         is missing, unwanted or differs in anything but `steps` (check_es_opt_meta).  With an optimizer the moments and
-        opt_steps come back too: the next update is the one the saved run would have made."""
+        opt_steps come back too: the next update is the one the saved run would have made.  The same for the "sigma"
+        block and the sigma array (check_es_sigma_meta): every refusal comes before anything is written."""
         import json
         with open(sidecar_path(path)) as f:
             meta = json.load(f)
@@ -348,14 +527,23 @@ class ES:
         check_es_meta(meta, arr.shape, arr.dtype, self.layers, self.seed, path)
         want = self._opt_meta()
         steps = check_es_opt_meta(meta, want, path=path)       # the sidecar first: no moments file is opened for a refusal
+        want_sigma = self._sigma_meta()
+        check_es_sigma_meta(meta, want_sigma, path=path)
         if want is not None:
             mom = np.load(moments_path(path))
             check_es_opt_meta(meta, want, mom.shape, mom.dtype, arr.shape[0], path)
+        if want_sigma is not None:
+            sig = np.load(sigma_path(path))
+            check_es_sigma_meta(meta, want_sigma, sig.shape, sig.dtype, arr.shape[0], path)
+            if not (np.isfinite(sig).all() and (sig > 0).all()):
+                raise ValueError("%s: the sigma array holds a value that is not finite and > 0" % path)
         self.b.es_set(arr[:self.n_weights], arr[self.n_weights:])
         if want is not None:
             nw = self.n_weights
             self.b.es_opt_set(mom[0, :nw], mom[0, nw:], mom[1, :nw], mom[1, nw:])
             self.opt_steps = steps
+        if want_sigma is not None:
+            self.b.es_sigma_set(sig[:self.n_weights], sig[self.n_weights:])
 
 
 class ESRollout(ShardedRollout):
@@ -376,6 +564,9 @@ class ESRollout(ShardedRollout):
     log_steps  opt-in, for an ES with an optimizer: after each generation's update, es.step_stats() - the sums of
         squares of the estimate, the step and the centre - is appended to `step_log` (one download of three doubles per
         stepped generation).
+    sigma  a number, or None exactly when es.adaptive: the members then fly with the ES's own sigma per element, the
+        generation end uses pair_utilities, `weight_log` keeps (d, s, n_c), es.update gets s=s and, with log_steps,
+        `step_log` holds five-tuples (ES.step_stats).
     """
 
     def __init__(self, engine, es, behaviours, seed, P, sigma, lr, ships=(0,), episodes_per_generation=1, eval_arenas=0,
@@ -387,6 +578,11 @@ class ESRollout(ShardedRollout):
         self.ships = [int(i) for i in ships]
         if not self.ships or len(set(self.ships)) != len(self.ships) or not all(0 <= i < engine.M for i in self.ships):
             raise ValueError("ships must be distinct ship slots in [0, %d), got %r" % (engine.M, list(ships)))
+        self.adaptive = bool(getattr(es, "adaptive", False))
+        if self.adaptive and sigma is not None:
+            raise ValueError("sigma must be None: the ES adapts sigma per element, got %r" % (sigma,))
+        if not self.adaptive and sigma is None:
+            raise ValueError("sigma must be a number: the ES does not adapt sigma")
         self.P = check_members(P, sigma)
         if not math.isfinite(lr):
             raise ValueError("lr must be finite, got %r" % (lr,))
@@ -398,13 +594,13 @@ class ESRollout(ShardedRollout):
         kw["observe"] = False
         super().__init__(engine, behaviours, seed, **kw)
         self.es = es
-        self.sigma, self.lr = float(sigma), float(lr)
+        self.sigma, self.lr = (None if sigma is None else float(sigma)), float(lr)
         self.episodes_per_generation, self.eval_arenas = int(episodes_per_generation), int(eval_arenas)
         self.generation = 0
         self.episodes = 0                 # finished episodes of the current generation
         self.fitness_log = []             # (best mean fitness of a member, mean fitness per evolved ship) per generation
         self.centre_log = []              # mean banked score of a centre-flown ship per generation (eval_arenas > 0)
-        self.weight_log = []              # (d, n_c) each generation stepped on
+        self.weight_log = []              # (d, n_c) each generation stepped on; adaptive: (d, s, n_c)
         self.log_steps = bool(log_steps)
         self.step_log = []                # (grad_sq, step_sq, centre_sq) per stepped generation (log_steps)
         self.policy = self._fly
@@ -440,12 +636,18 @@ class ESRollout(ShardedRollout):
                                      float(ms.sum()) / float(max(int(mc.sum()), 1))))
             if self.eval_arenas:
                 self.centre_log.append(float(s[self.P]) / float(c[self.P]) if c[self.P] else float("nan"))
-            d, n_c = pair_weights(s, c)
+            if self.adaptive:
+                d, w, n_c = pair_utilities(s, c)
+            else:
+                d, n_c = pair_weights(s, c)
             if n_c >= 2:
-                self.es.update(d, self.lr, self.sigma, n_c, self.generation)
+                if self.adaptive:
+                    self.es.update(d, self.lr, None, n_c, self.generation, s=w)
+                else:
+                    self.es.update(d, self.lr, self.sigma, n_c, self.generation)
                 if self.log_steps:
                     self.step_log.append(tuple(self.es.step_stats()))
-            self.weight_log.append((d, n_c))
+            self.weight_log.append((d, w, n_c) if self.adaptive else (d, n_c))
             self.generation += 1
             self.episodes = 0
             self._assign()
@@ -460,7 +662,7 @@ class ESRollout(ShardedRollout):
         s, c = self.es.fitness_host()
         d = {"generation": self.generation, "episodes": self.episodes, "tick": self.tick,
              "fitness_log": list(self.fitness_log), "centre_log": list(self.centre_log),
-             "weight_log": [(np.array(d), int(n)) for d, n in self.weight_log],
+             "weight_log": [tuple(np.array(x) for x in w[:-1]) + (int(w[-1]),) for w in self.weight_log],
              "score_log": [np.array(t) for t in self.score_log], "fitness_sum": s, "fitness_count": c,
              "engine": self.e.state_dict()}
         if self.log_steps:
@@ -477,7 +679,7 @@ class ESRollout(ShardedRollout):
         self.e.load_state_dict(d["engine"])
         self.generation, self.episodes, self.tick = int(d["generation"]), int(d["episodes"]), int(d["tick"])
         self.fitness_log, self.centre_log = list(d["fitness_log"]), list(d["centre_log"])
-        self.weight_log = [(np.array(w), int(n)) for w, n in d["weight_log"]]
+        self.weight_log = [tuple(np.array(x) for x in w[:-1]) + (int(w[-1]),) for w in d["weight_log"]]
         self.score_log = [np.array(t) for t in d["score_log"]]
         if "step_log" in d:
             self.step_log = [tuple(t) for t in d["step_log"]]

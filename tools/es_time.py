@@ -27,10 +27,20 @@ loop     ESRollout at P = `--small`, `--sigma` (0.05), `--lr` (0.1), `--optimize
          lock-step and arena-steps/s per generation, fitness_log and centre_log, and with an optimizer step_log (the
          sums of squares of the estimate, the step and the centre per generation).  Whether they rise is an observation
          of this run, not something any test holds the code to.
+sigma    per-element adaptive sigma against the scalar calls (profiles/r31_es_sigma.txt): one handle with an Adam centre
+         and its sigma vector, ship 0 of every arena on member a % P.  Per P (`--small`, `--large`) ONE warmed-up timing
+         block, `--repeats` (3) rounds of: `--calls` (50) calls of ofx_es_act, the same of ofx_es_sigma_act, then one
+         ofx_es_step (Adam, no statistics), one ofx_es_sigma_step (Adam, no statistics, a d and an s on EVERY pair), and
+         the two steps once more in reverse order.  Reported: us per forward, ms per step and the ratios sigma / scalar
+         within the block.  `--no-sigma` leaves the two sigma calls out and creates no vector: the same blocks of
+         ofx_es_act and ofx_es_step alone, which is what an older build of the library can run (for a comparison of
+         these two kernels across builds, and an A/A run of one build for its noise).
+         `loop` takes `--adaptive`: ES(sigma_init=`--sigma`, sigma_lr=`--sigma-lr` (0.2)), ESRollout(sigma=None).
 Each mode prints one JSON line and, with `--out FILE`, appends it to that file.
-Usage: python tools/es_time.py kernels|loop [--arenas 4096] [--small 4096] [--large 32768] [--stored 512] [--calls 50]
+Usage: python tools/es_time.py kernels|loop|sigma [--arenas 4096] [--small 4096] [--large 32768] [--stored 512] [--calls 50]
                                [--repeats 3] [--generations 5] [--eval-arenas 64] [--optimizer adam|momentum]
-                               [--weight-decay 0.005] [--lr 0.1] [--sigma 0.05] [--out FILE]
+                               [--weight-decay 0.005] [--lr 0.1] [--sigma 0.05] [--adaptive] [--sigma-lr 0.2]
+                               [--no-sigma] [--out FILE]
 
 One GPU step per process, each under its own time limit, chained so that a failure ends the chain:
     timeout -k 10 400 python tools/es_time.py kernels --out profiles/r29_es.txt \\
@@ -161,14 +171,66 @@ def kernels():
     return out
 
 
+def sigma():
+    calls, repeats = _arg("--calls", 50), _arg("--repeats", 3)
+    sizes = [_arg("--small", 4096), _arg("--large", 32768)]
+    adaptive = "--no-sigma" not in sys.argv
+    b = ArenaBatch(ARENAS, M)
+    b.spawn_random(SEED)
+    b.rollout(["random"] * M, SEED, 0, 40)
+    ES(b, LAYERS, SEED)
+    b.es_opt_create()
+    if adaptive:
+        b.es_sigma_create(SIGMA)
+    b.bot_actions(["random"] * M, SEED, tick=40)
+    b.sync()
+    timed = _Timer(b)
+    rs = np.random.RandomState(0)
+    adam = (0.005, LR, 0.9, 1.0 - 0.9, 0.999, 1.0 - 0.999, 1e-8)
+    out = {"what": "sigma", "adaptive": adaptive, "arenas": ARENAS, "ships": M, "layers": LAYERS, "elements": G,
+           "calls_per_block": calls, "sigma": SIGMA, "sizes": []}
+    for P in sizes:
+        buf = _assignment(P)
+        d = rs.uniform(0.01, 1.0, P // 2) * rs.choice([-1.0, 1.0], P // 2)         # a weight on every pair
+        s = rs.uniform(0.01, 1.0, P // 2) * rs.choice([-1.0, 1.0], P // 2)
+        kinds = {"es_act": lambda: b.es_act(buf.ptr, P, SIGMA, SEED, 1),
+                 "es_step": lambda: b.es_step(d, nat.ES_RULE_ADAM, 1.0 / (P * SIGMA), *adam, SEED, 1)}
+        if adaptive:
+            kinds["es_sigma_act"] = lambda: b.es_sigma_act(buf.ptr, P, SEED, 1)
+            kinds["es_sigma_step"] = lambda: b.es_sigma_step(d, s, nat.ES_RULE_ADAM, 1.0 / P, *adam, 0.2 / P, SIGMA / 64,
+                                                             SIGMA * 4, SEED, 1)
+        acts = [k for k in ("es_act", "es_sigma_act") if k in kinds]
+        steps = [k for k in ("es_step", "es_sigma_step") if k in kinds]
+        for k in acts:                                              # warm-up: maps, the pair list's buffers, the clocks
+            timed(kinds[k], 5)
+        for k in steps:
+            timed(kinds[k], 1)
+        res = {k: [] for k in kinds}
+        for _ in range(repeats):
+            for k in acts:
+                res[k].append(round(timed(kinds[k], calls), 2))                     # us per forward
+            for k in steps + steps[::-1]:
+                res[k].append(round(timed(kinds[k], 1) / 1e3, 3))                   # ms per step
+        entry = {"P": P, "es_act_us": res["es_act"], "es_step_adam_ms": res["es_step"]}
+        if adaptive:
+            entry.update({"es_sigma_act_us": res["es_sigma_act"], "es_sigma_step_adam_ms": res["es_sigma_step"],
+                          "sigma_act_over_act": round(float(np.mean(res["es_sigma_act"])) / float(np.mean(res["es_act"])), 4),
+                          "sigma_step_over_step": round(float(np.mean(res["es_sigma_step"])) / float(np.mean(res["es_step"])), 4)})
+        out["sizes"].append(entry)
+    b.close()
+    return out
+
+
 def loop():
     P, generations, eval_arenas = _arg("--small", 4096), _arg("--generations", 5), _arg("--eval-arenas", 64)
     optimizer, weight_decay = _arg("--optimizer", "") or None, _arg("--weight-decay", 0.0)
+    adaptive = "--adaptive" in sys.argv
     b = ArenaBatch(ARENAS, M)
-    es = ES(b, LAYERS, SEED, optimizer=optimizer, weight_decay=weight_decay)
+    kw = dict(sigma_init=SIGMA, sigma_lr=_arg("--sigma-lr", 0.2)) if adaptive else {}
+    es = ES(b, LAYERS, SEED, optimizer=optimizer, weight_decay=weight_decay, **kw)
     T = b.cfg.episode_ticks
-    roll = ESRollout(b, es, ["random"] * M, SEED, P, SIGMA, LR, ships=(0,), eval_arenas=eval_arenas, episode_ticks=T,
-                     log_steps=optimizer is not None)
+    roll = ESRollout(b, es, ["random"] * M, SEED, P, None if adaptive else SIGMA, LR, ships=(0,), eval_arenas=eval_arenas,
+                     episode_ticks=T, log_steps=optimizer is not None or adaptive)
     roll.run(1)                                                # the episode-end check stands at the head of a lock-step
     ms = []
     for _ in range(generations):
@@ -178,12 +240,13 @@ def loop():
         b.sync()
         ms.append((time.perf_counter() - t0) * 1e3 / T)
     out = {"what": "loop", "arenas": ARENAS, "ships": M, "layers": LAYERS, "P": P, "sigma": SIGMA, "lr": LR,
-           "optimizer": optimizer, "weight_decay": weight_decay, "eval_arenas": eval_arenas, "episode_ticks": T,
+           "optimizer": optimizer, "weight_decay": weight_decay, "adaptive": adaptive, "eval_arenas": eval_arenas,
+           "episode_ticks": T,
            "generations": roll.generation,
            "ms_per_lock_step": [round(x, 4) for x in ms], "mean_ms_per_lock_step": round(float(np.mean(ms)), 4),
            "arena_steps_per_s": round(ARENAS / (float(np.mean(ms)) * 1e-3), 1),
-           "complete_pair_members": [n for _, n in roll.weight_log],
-           "nonzero_pair_weights": [int(np.count_nonzero(d)) for d, _ in roll.weight_log],
+           "complete_pair_members": [w[-1] for w in roll.weight_log],
+           "nonzero_pair_weights": [int(np.count_nonzero(w[0])) for w in roll.weight_log],
            "fitness_log_best": [round(f[0], 3) for f in roll.fitness_log],
            "fitness_log_mean": [round(f[1], 3) for f in roll.fitness_log],
            "centre_log": [round(c, 3) for c in roll.centre_log],
@@ -193,10 +256,10 @@ def loop():
 
 
 if __name__ == "__main__":
-    what = [x for x in sys.argv[1:] if x in ("kernels", "loop")]
+    what = [x for x in sys.argv[1:] if x in ("kernels", "loop", "sigma")]
     if len(what) != 1:
         raise SystemExit(__doc__)
-    line = json.dumps(kernels() if what[0] == "kernels" else loop())
+    line = json.dumps({"kernels": kernels, "loop": loop, "sigma": sigma}[what[0]]())
     print(line, flush=True)
     if "--out" in sys.argv:
         with open(_arg("--out", ""), "a") as f:
