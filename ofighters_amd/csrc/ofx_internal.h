@@ -40,8 +40,8 @@ struct ofx_state {
 };
 
 struct ofx_replay;  // ofx_replay.hip
-struct ofx_population;  // ofx_evolve.hip
-struct ofx_es;          // ofx_evolve.hip
+struct ofx_population;  // ofx_evolve.hip: the stored population
+struct ofx_es;          // ofx_es.hip: the centre of the evolution strategy
 
 struct ofx_handle {
   ofx_config cfg;

@@ -86,6 +86,19 @@ def pack_actions(valid, shoot, thrust, px, py):
     return a
 
 
+def _f64_out(*sizes):
+    """(arrays, pointers): fresh float64 arrays of `sizes` for the library to fill - a genome's (weights, biases)."""
+    arrays = [np.empty(int(n), np.float64) for n in sizes]
+    return arrays, [a.ctypes.data_as(C.c_void_p) for a in arrays]
+
+
+def _f64_in(*values):
+    """(arrays, pointers): `values` as contiguous float64 for the library to read; the arrays live as long as the
+    caller holds them."""
+    arrays = [np.ascontiguousarray(v, dtype=np.float64) for v in values]
+    return arrays, [a.ctypes.data_as(C.c_void_p) for a in arrays]
+
+
 def check_pool_pairs(what, packed, pool_pairs):
     """The size argument of the packed frame store (replay_create's pool_pairs, DeviceTrainer's memory_pool_pairs): an
     integer >= 0 and no bool, and 0 unless the packed store is asked for.  ValueError otherwise; returns it as int."""
@@ -1042,13 +1055,13 @@ class ArenaBatch:
 
     def population_get(self, p, n_weights, n_biases):
         """Genome p as (weights float64 [n_weights], biases float64 [n_biases]) in the element order.  Synchronises."""
-        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
-        nat.check(nat.lib().ofx_population_get(self._h, int(p), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        (w, b), ptrs = _f64_out(n_weights, n_biases)
+        nat.check(nat.lib().ofx_population_get(self._h, int(p), *ptrs))
         return w, b
 
     def population_set(self, p, weights, biases):
-        w, b = np.ascontiguousarray(weights, dtype=np.float64), np.ascontiguousarray(biases, dtype=np.float64)
-        nat.check(nat.lib().ofx_population_set(self._h, int(p), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        _keep, ptrs = _f64_in(weights, biases)
+        nat.check(nat.lib().ofx_population_set(self._h, int(p), *ptrs))
 
     def population_breed(self, plan, evolution_rate, mutation_rate, seed, generation):
         """Reproduction in place on the int32 [P] plan (kept / child of a kept slot / -1 fresh); the library checks the
@@ -1105,20 +1118,19 @@ class ArenaBatch:
 
     def es_get(self, n_weights, n_biases):
         """The centre as (weights float64 [n_weights], biases float64 [n_biases]) in the element order.  Synchronises."""
-        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
-        nat.check(nat.lib().ofx_es_get(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        (w, b), ptrs = _f64_out(n_weights, n_biases)
+        nat.check(nat.lib().ofx_es_get(self._h, *ptrs))
         return w, b
 
     def es_set(self, weights, biases):
-        w, b = np.ascontiguousarray(weights, dtype=np.float64), np.ascontiguousarray(biases, dtype=np.float64)
-        nat.check(nat.lib().ofx_es_set(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        _keep, ptrs = _f64_in(weights, biases)
+        nat.check(nat.lib().ofx_es_set(self._h, *ptrs))
 
     def es_member(self, member, P, sigma, seed, generation, n_weights, n_biases):
         """Member `member` of P (P: the centre) at `generation`, materialised on the device, as (weights, biases) in the
         element order.  Synchronises."""
-        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
-        nat.check(nat.lib().ofx_es_member(self._h, int(member), int(P), float(sigma), seed, int(generation),
-                                          w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        (w, b), ptrs = _f64_out(n_weights, n_biases)
+        nat.check(nat.lib().ofx_es_member(self._h, int(member), int(P), float(sigma), seed, int(generation), *ptrs))
         return w, b
 
     def es_act(self, member_of_ptr, P, sigma, seed, generation, out_ptr=None, y_ptr=None):
@@ -1135,9 +1147,8 @@ class ArenaBatch:
     def es_update(self, d, scale, seed, generation):
         """theta[e] += scale * sum_i d[i] * eps(i, e) in ascending pair order (ofx_es_update); d: float64 [P / 2].  Does
         not wait for the update."""
-        a = np.ascontiguousarray(d, dtype=np.float64)
-        nat.check(nat.lib().ofx_es_update(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], float(scale), seed,
-                                          int(generation)))
+        (a,), (ptr,) = _f64_in(d)
+        nat.check(nat.lib().ofx_es_update(self._h, ptr, a.shape[0], float(scale), seed, int(generation)))
 
     def es_opt_create(self):
         """The centre's optimiser state: the moments m and v, zeroed, in theta's layout (ofx_es_opt_create)."""
@@ -1148,19 +1159,19 @@ class ArenaBatch:
 
     def es_opt_get(self, n_weights, n_biases):
         """The moments as ((m weights, m biases), (v weights, v biases)) in the element order.  Synchronises."""
-        out = [np.empty(int(n), np.float64) for n in (n_weights, n_biases, n_weights, n_biases)]
-        nat.check(nat.lib().ofx_es_opt_get(self._h, *[a.ctypes.data_as(C.c_void_p) for a in out]))
+        out, ptrs = _f64_out(n_weights, n_biases, n_weights, n_biases)
+        nat.check(nat.lib().ofx_es_opt_get(self._h, *ptrs))
         return (out[0], out[1]), (out[2], out[3])
 
     def es_opt_set(self, m_weights, m_biases, v_weights, v_biases):
-        a = [np.ascontiguousarray(x, dtype=np.float64) for x in (m_weights, m_biases, v_weights, v_biases)]
-        nat.check(nat.lib().ofx_es_opt_set(self._h, *[x.ctypes.data_as(C.c_void_p) for x in a]))
+        _keep, ptrs = _f64_in(m_weights, m_biases, v_weights, v_biases)
+        nat.check(nat.lib().ofx_es_opt_set(self._h, *ptrs))
 
     def es_step(self, d, rule, gscale, decay, alpha, c1, k1, c2, k2, eps, seed, generation, stats_ptr=None):
         """The generation step through the optimiser (ofx_es_step: the law, line by line); d: float64 [P / 2], rule:
         nat.ES_RULE_MOMENTUM or nat.ES_RULE_ADAM, stats_ptr: device float64 [3] or None.  Does not wait for the step."""
-        a = np.ascontiguousarray(d, dtype=np.float64)
-        nat.check(nat.lib().ofx_es_step(self._h, a.ctypes.data_as(C.c_void_p), a.shape[0], int(rule), float(gscale),
+        (a,), (ptr,) = _f64_in(d)
+        nat.check(nat.lib().ofx_es_step(self._h, ptr, a.shape[0], int(rule), float(gscale),
                                         float(decay), float(alpha), float(c1), float(k1), float(c2), float(k2),
                                         float(eps), seed, int(generation), stats_ptr))
 
@@ -1174,19 +1185,18 @@ class ArenaBatch:
 
     def es_sigma_get(self, n_weights, n_biases):
         """sigma as (weights float64 [n_weights], biases float64 [n_biases]) in the element order.  Synchronises."""
-        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
-        nat.check(nat.lib().ofx_es_sigma_get(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        (w, b), ptrs = _f64_out(n_weights, n_biases)
+        nat.check(nat.lib().ofx_es_sigma_get(self._h, *ptrs))
         return w, b
 
     def es_sigma_set(self, weights, biases):
-        w, b = np.ascontiguousarray(weights, dtype=np.float64), np.ascontiguousarray(biases, dtype=np.float64)
-        nat.check(nat.lib().ofx_es_sigma_set(self._h, w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        _keep, ptrs = _f64_in(weights, biases)
+        nat.check(nat.lib().ofx_es_sigma_set(self._h, *ptrs))
 
     def es_sigma_member(self, member, P, seed, generation, n_weights, n_biases):
         """es_member under the sigma vector: theta[e] + (+-sigma[e]) * eps(i, e).  Synchronises."""
-        w, b = np.empty(int(n_weights), np.float64), np.empty(int(n_biases), np.float64)
-        nat.check(nat.lib().ofx_es_sigma_member(self._h, int(member), int(P), seed, int(generation),
-                                                w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        (w, b), ptrs = _f64_out(n_weights, n_biases)
+        nat.check(nat.lib().ofx_es_sigma_member(self._h, int(member), int(P), seed, int(generation), *ptrs))
         return w, b
 
     def es_sigma_act(self, member_of_ptr, P, seed, generation, out_ptr=None, y_ptr=None):
@@ -1199,10 +1209,10 @@ class ArenaBatch:
         """The generation step of the centre and of sigma in one pass (ofx_es_sigma_step: the law, line by line); d, s:
         float64 [P / 2], rule: nat.ES_RULE_PLAIN, _MOMENTUM or _ADAM, stats_ptr: device float64 [5] or None.  Does not
         wait for the step."""
-        a, w = np.ascontiguousarray(d, dtype=np.float64), np.ascontiguousarray(s, dtype=np.float64)
+        (a, w), ptrs = _f64_in(d, s)
         if a.ndim != 1 or a.shape != w.shape:
             raise ValueError("d and s are float64 [P / 2] arrays of one length, got %s and %s" % (a.shape, w.shape))
-        nat.check(nat.lib().ofx_es_sigma_step(self._h, a.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+        nat.check(nat.lib().ofx_es_sigma_step(self._h, *ptrs,
                                               a.shape[0], int(rule), float(gscale), float(decay), float(alpha), float(c1),
                                               float(k1), float(c2), float(k2), float(eps), float(srate), float(smin),
                                               float(smax), seed, int(generation), stats_ptr))

@@ -56,6 +56,27 @@ def check_member_assignment(member_of, N, M, P):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _ranked_pairs(sum, count):
+    """(complete bool [P/2], u, n_c) behind pair_weights and pair_utilities: the centred average ranks u float64
+    [n_c/2][2] of the complete pairs' members, None when there is nothing to rank (n_c < 2 or all means equal)."""
+    s, c = np.asarray(sum, np.int64), np.asarray(count, np.int64)
+    if s.ndim != 1 or s.shape != c.shape or s.shape[0] < 2:
+        raise ValueError("sum and count are [P] or [P + 1] arrays, got %s and %s" % (s.shape, c.shape))
+    n_pairs = s.shape[0] // 2
+    s, c = s[:2 * n_pairs].reshape(n_pairs, 2), c[:2 * n_pairs].reshape(n_pairs, 2)
+    complete = (c > 0).all(axis=1)
+    n_c = 2 * int(complete.sum())
+    if n_c < 2:
+        return complete, None, n_c
+    mean = (s[complete] / c[complete]).ravel()
+    values, inverse, counts = np.unique(mean, return_inverse=True, return_counts=True)
+    if values.size == 1:
+        return complete, None, n_c
+    below = np.cumsum(counts) - counts                     # members ranked strictly below each distinct mean
+    rank = (below + (counts - 1) / 2.0)[inverse]           # the average of the ranks a tied group covers
+    return complete, (rank / (n_c - 1) - 0.5).reshape(-1, 2), n_c
+
+
 def pair_weights(sum, count):
     """The weight d_i of every mirrored pair from the device's fitness sums: (d float64 [P/2], n_c).
 
@@ -65,24 +86,10 @@ def pair_weights(sum, count):
         u_m = r_m / (n_c - 1) - 0.5        d_i = u_{2i} - u_{2i+1}
     so a tied pair weighs exactly 0, the weights lie in [-1, 1] and swapping a pair's fitness negates its weight.
     Incomplete pairs get 0; n_c < 2 or all means equal gives all zeros.  Pure numpy, no randomness."""
-    s, c = np.asarray(sum, np.int64), np.asarray(count, np.int64)
-    if s.ndim != 1 or s.shape != c.shape or s.shape[0] < 2:
-        raise ValueError("sum and count are [P] or [P + 1] arrays, got %s and %s" % (s.shape, c.shape))
-    n_pairs = s.shape[0] // 2
-    s, c = s[:2 * n_pairs].reshape(n_pairs, 2), c[:2 * n_pairs].reshape(n_pairs, 2)
-    complete = (c > 0).all(axis=1)
-    n_c = 2 * int(complete.sum())
-    d = np.zeros(n_pairs, np.float64)
-    if n_c < 2:
-        return d, n_c
-    mean = (s[complete] / c[complete]).ravel()
-    values, inverse, counts = np.unique(mean, return_inverse=True, return_counts=True)
-    if values.size == 1:
-        return d, n_c
-    below = np.cumsum(counts) - counts                     # members ranked strictly below each distinct mean
-    rank = (below + (counts - 1) / 2.0)[inverse]           # the average of the ranks a tied group covers
-    u = (rank / (n_c - 1) - 0.5).reshape(-1, 2)
-    d[complete] = u[:, 0] - u[:, 1]
+    complete, u, n_c = _ranked_pairs(sum, count)
+    d = np.zeros(complete.shape[0], np.float64)
+    if u is not None:
+        d[complete] = u[:, 0] - u[:, 1]
     return d, n_c
 
 
@@ -93,25 +100,11 @@ def pair_utilities(sum, count):
     of the n_c members sum to 0).  A pair both of whose members beat the median has s > 0 and widens sigma where its
     noise was large; swapping a pair's fitness leaves s and negates d.  Incomplete pairs get 0; n_c < 2 or all means
     equal gives all zeros.  Pure numpy, no randomness."""
-    s, c = np.asarray(sum, np.int64), np.asarray(count, np.int64)
-    if s.ndim != 1 or s.shape != c.shape or s.shape[0] < 2:
-        raise ValueError("sum and count are [P] or [P + 1] arrays, got %s and %s" % (s.shape, c.shape))
-    n_pairs = s.shape[0] // 2
-    s, c = s[:2 * n_pairs].reshape(n_pairs, 2), c[:2 * n_pairs].reshape(n_pairs, 2)
-    complete = (c > 0).all(axis=1)
-    n_c = 2 * int(complete.sum())
-    d, w = np.zeros(n_pairs, np.float64), np.zeros(n_pairs, np.float64)
-    if n_c < 2:
-        return d, w, n_c
-    mean = (s[complete] / c[complete]).ravel()
-    values, inverse, counts = np.unique(mean, return_inverse=True, return_counts=True)
-    if values.size == 1:
-        return d, w, n_c
-    below = np.cumsum(counts) - counts                     # as in pair_weights, operation for operation
-    rank = (below + (counts - 1) / 2.0)[inverse]
-    u = (rank / (n_c - 1) - 0.5).reshape(-1, 2)
-    d[complete] = u[:, 0] - u[:, 1]
-    w[complete] = u[:, 0] + u[:, 1]
+    complete, u, n_c = _ranked_pairs(sum, count)
+    d, w = np.zeros(complete.shape[0], np.float64), np.zeros(complete.shape[0], np.float64)
+    if u is not None:
+        d[complete] = u[:, 0] - u[:, 1]
+        w[complete] = u[:, 0] + u[:, 1]
     return d, w, n_c
 
 
@@ -158,11 +151,20 @@ def check_optimizer(optimizer, beta1, beta2, adam_eps, weight_decay, adaptive=Fa
 def step_scalars(optimizer, lr, sigma, n_c, t, beta1, beta2):
     """(gscale, alpha, c1, k1, c2, k2) of ofx_es_step at step t (1-based), in Python floats and in this order; Adam's
     bias correction is folded into the step size."""
-    gscale = 1.0 / (int(n_c) * float(sigma))
-    k1 = 1.0 - beta1
-    k2 = 1.0 - beta2
-    alpha = float(lr) if optimizer == "momentum" else float(lr) * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
-    return gscale, alpha, float(beta1), k1, float(beta2), k2
+    return (1.0 / (int(n_c) * float(sigma)),) + step_law(optimizer, lr, t, beta1, beta2)[1:]
+
+
+def step_law(optimizer, lr, t, beta1, beta2):
+    """(rule, alpha, c1, k1, c2, k2): the library's rule constant of `optimizer` and the scalars of its law at step t
+    (1-based), in Python floats.  None is the PLAIN rule of ofx_es_sigma_step: the step is lr times the estimate."""
+    from . import _native as nat
+    if optimizer is None:
+        return nat.ES_RULE_PLAIN, float(lr), 0.0, 1.0, 0.0, 1.0
+    k1, k2 = 1.0 - beta1, 1.0 - beta2
+    if optimizer == "momentum":
+        return nat.ES_RULE_MOMENTUM, float(lr), float(beta1), k1, float(beta2), k2
+    alpha = float(lr) * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    return nat.ES_RULE_ADAM, alpha, float(beta1), k1, float(beta2), k2
 
 
 def es_opt_meta(optimizer, beta1, beta2, adam_eps, weight_decay, steps):
@@ -175,28 +177,44 @@ def check_es_opt_meta(meta, want, shape=None, dtype=None, elements=None, path="t
     differs.  `meta` is the sidecar, `want` this ES's es_opt_meta (None: no optimiser).  The block must be there exactly
     when this ES has an optimiser, and equal `want` in everything but `steps`; shape / dtype, when given, are those of
     the moments' array, float64 [2][elements].  Returns the checkpoint's step count (0 without an optimiser)."""
-    block = meta.get("optimizer")
-    if want is None:
-        if block is not None:
-            raise ValueError("%s: the sidecar has an optimizer block, this ES has no optimizer" % path)
-        return 0
+    block = _check_block(meta, "optimizer", want, ("rule", "beta1", "beta2", "eps", "weight_decay"),
+                         "an optimizer block, this ES has no optimizer",
+                         want and "this ES's optimizer is %r" % (want["rule"],), path)
     if block is None:
-        raise ValueError("%s: the sidecar has no optimizer block, this ES's optimizer is %r" % (path, want["rule"]))
-    for field in ("rule", "beta1", "beta2", "eps", "weight_decay"):
-        if field not in block:
-            raise ValueError("%s: the optimizer block has no field %r" % (path, field))
-        got = block[field] if field == "rule" else float(block[field])
-        if got != want[field]:
-            raise ValueError("%s: optimizer %s is %r, this ES's is %r" % (path, field, got, want[field]))
+        return 0
     steps = block.get("steps")
     if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
         raise ValueError("%s: the optimizer block's steps must be an integer >= 0, got %r" % (path, steps))
-    if shape is not None and tuple(shape) != (2, elements):
-        raise ValueError("%s: the moments' shape is %r, m and v of %d elements are %r" % (path, tuple(shape), elements,
-                                                                                         (2, elements)))
-    if dtype is not None and np.dtype(dtype) != np.float64:
-        raise ValueError("%s: the moments' dtype is %s, they are float64" % (path, np.dtype(dtype)))
+    _check_array(shape, dtype, (2, elements), "the moments'", "m and v of %d elements are" % (elements or 0),
+                 "they are", path)
     return steps
+
+
+def _check_block(meta, name, want, fields, unwanted, missing, path):
+    """The sidecar's block `name` against this ES's `want` (None: no such state): there exactly when wanted, and equal
+    in every one of `fields` (a string as it is, a number as a float).  Returns the block, None when none is wanted."""
+    block = meta.get(name)
+    if want is None:
+        if block is not None:
+            raise ValueError("%s: the sidecar has %s" % (path, unwanted))
+        return None
+    if block is None:
+        raise ValueError("%s: the sidecar has no %s block, %s" % (path, name, missing))
+    for field in fields:
+        if field not in block:
+            raise ValueError("%s: the %s block has no field %r" % (path, name, field))
+        got = block[field] if isinstance(want[field], str) else float(block[field])
+        if got != want[field]:
+            raise ValueError("%s: %s %s is %r, this ES's is %r" % (path, name, field, got, want[field]))
+    return block
+
+
+def _check_array(shape, dtype, want_shape, whose, of, it_is, path):
+    """shape / dtype, when given, of the array a block comes with: float64 `want_shape`."""
+    if shape is not None and tuple(shape) != want_shape:
+        raise ValueError("%s: %s shape is %r, %s %r" % (path, whose, tuple(shape), of, want_shape))
+    if dtype is not None and np.dtype(dtype) != np.float64:
+        raise ValueError("%s: %s dtype is %s, %s float64" % (path, whose, np.dtype(dtype), it_is))
 
 
 def moments_path(path):
@@ -235,27 +253,22 @@ def check_es_sigma_meta(meta, want, shape=None, dtype=None, elements=None, path=
     differs.  `meta` is the sidecar, `want` this ES's es_sigma_meta (None: not adaptive).  The "sigma" block must be
     there exactly when this ES is adaptive, and equal `want`; shape / dtype, when given, are those of the sigma array,
     float64 [elements]."""
-    block = meta.get("sigma")
-    if want is None:
-        if block is not None:
-            raise ValueError("%s: the sidecar has a sigma block, this ES does not adapt sigma" % path)
-        return
-    if block is None:
-        raise ValueError("%s: the sidecar has no sigma block, this ES adapts sigma" % path)
-    for field in ("lr", "min", "max"):
-        if field not in block:
-            raise ValueError("%s: the sigma block has no field %r" % (path, field))
-        if float(block[field]) != want[field]:
-            raise ValueError("%s: sigma %s is %r, this ES's is %r" % (path, field, float(block[field]), want[field]))
-    if shape is not None and tuple(shape) != (elements,):
-        raise ValueError("%s: the sigma array's shape is %r, a sigma of %d elements is %r" % (path, tuple(shape), elements,
-                                                                                           (elements,)))
-    if dtype is not None and np.dtype(dtype) != np.float64:
-        raise ValueError("%s: the sigma array's dtype is %s, it is float64" % (path, np.dtype(dtype)))
+    if _check_block(meta, "sigma", want, ("lr", "min", "max"), "a sigma block, this ES does not adapt sigma",
+                    "this ES adapts sigma", path) is not None:
+        _check_array(shape, dtype, (elements,), "the sigma array's", "a sigma of %d elements is" % (elements or 0),
+                     "it is", path)
 
 
 def sigma_path(path):
     return path + ".sigma.npy"
+
+
+def check_sigma_mode(adaptive, sigma, es="the ES", how="", how_not=""):
+    """sigma is the caller's number, or None exactly when the ES adapts its own: nothing is silently ignored."""
+    if adaptive and sigma is not None:
+        raise ValueError("sigma must be None: %s adapts sigma per element%s, got %r" % (es, how, sigma))
+    if not adaptive and sigma is None:
+        raise ValueError("sigma must be a number: %s does not adapt sigma%s" % (es, how_not))
 
 
 class ES:
@@ -297,9 +310,9 @@ class ES:
         if self.adaptive:
             self.sigma_init, self.sigma_lr, self.sigma_min, self.sigma_max = adapt
             batch.es_sigma_create(self.sigma_init)
-            self._stats = DeviceBuffer(5 * 8).upload(np.zeros(5, np.float64))
-        elif optimizer is not None:
-            self._stats = DeviceBuffer(3 * 8).upload(np.zeros(3, np.float64))
+        self.n_stats = 5 if self.adaptive else 3 if optimizer is not None else 0   # the sums a step leaves (step_stats)
+        if self.n_stats:
+            self._stats = DeviceBuffer(self.n_stats * 8).upload(np.zeros(self.n_stats, np.float64))
         self._member_of = DeviceBuffer(batch.N * batch.M * 4)
         self.P, self.member_of = None, None
         self._sum = self._count = None
@@ -352,11 +365,7 @@ class ES:
             raise ValueError("this ES does not adapt sigma: construct it with sigma_init")
 
     def _check_sigma(self, sigma):
-        """sigma is the caller's number, or None exactly when this ES adapts its own: nothing is silently ignored."""
-        if self.adaptive and sigma is not None:
-            raise ValueError("sigma must be None: this ES adapts sigma per element (sigma_init), got %r" % (sigma,))
-        if not self.adaptive and sigma is None:
-            raise ValueError("sigma must be a number: this ES does not adapt sigma (no sigma_init)")
+        check_sigma_mode(self.adaptive, sigma, "this ES", " (sigma_init)", " (no sigma_init)")
 
     def member(self, m, P, sigma, generation):
         """(weights_layers, biases_layers) of member m of P at `generation` (m == P: the centre), materialised on the
@@ -445,41 +454,32 @@ class ES:
         if int(n_c) < 2 or not math.isfinite(lr):
             raise ValueError("update needs n_c >= 2 and a finite lr, got n_c = %r, lr = %r" % (n_c, lr))
         if self.adaptive:
-            from . import _native as nat
             s = np.asarray(s, np.float64)
             if s.shape != d.shape or not np.isfinite(s).all():
                 raise ValueError("s is a finite float64 [P / 2] like d, got %s" % (s.shape,))
-            alpha, c1, k1, c2, k2 = float(lr), 0.0, 1.0, 0.0, 1.0
-            rule = nat.ES_RULE_PLAIN
-            if self.optimizer is not None:
-                self.opt_steps += 1
-                _, alpha, c1, k1, c2, k2 = step_scalars(self.optimizer, lr, 1.0, n_c, self.opt_steps, self.beta1, self.beta2)
-                rule = nat.ES_RULE_MOMENTUM if self.optimizer == "momentum" else nat.ES_RULE_ADAM
-            self.b.es_sigma_step(d, s, rule, 1.0 / int(n_c), self.weight_decay, alpha, c1, k1, c2, k2, self.adam_eps,
-                                 self.sigma_lr / int(n_c), self.sigma_min, self.sigma_max, self.seed, generation,
-                                 stats_ptr=self._stats.ptr)
-            return
-        if self.optimizer is None:
+        elif self.optimizer is None:
             scale = float(lr) / (int(n_c) * float(sigma))
             self.b.es_update(d, scale, self.seed, generation)
             return
-        from . import _native as nat
-        self.opt_steps += 1
-        gscale, alpha, c1, k1, c2, k2 = step_scalars(self.optimizer, lr, sigma, n_c, self.opt_steps, self.beta1, self.beta2)
-        rule = nat.ES_RULE_MOMENTUM if self.optimizer == "momentum" else nat.ES_RULE_ADAM
-        self.b.es_step(d, rule, gscale, self.weight_decay, alpha, c1, k1, c2, k2, self.adam_eps, self.seed, generation,
-                       stats_ptr=self._stats.ptr)
+        if self.optimizer is not None:
+            self.opt_steps += 1
+        rule, alpha, c1, k1, c2, k2 = step_law(self.optimizer, lr, self.opt_steps, self.beta1, self.beta2)
+        if self.adaptive:
+            self.b.es_sigma_step(d, s, rule, 1.0 / int(n_c), self.weight_decay, alpha, c1, k1, c2, k2, self.adam_eps,
+                                 self.sigma_lr / int(n_c), self.sigma_min, self.sigma_max, self.seed, generation,
+                                 stats_ptr=self._stats.ptr)
+        else:
+            self.b.es_step(d, rule, 1.0 / (int(n_c) * float(sigma)), self.weight_decay, alpha, c1, k1, c2, k2,
+                           self.adam_eps, self.seed, generation, stats_ptr=self._stats.ptr)
 
     def step_stats(self):
         """(grad_sq, step_sq, centre_sq) of the last optimiser step: the sums over the genome of q^2 (the estimate minus
         the decay term), of step^2 and of theta'^2, zeros before the first step.  Adaptive: five numbers - those three, the
         sum of sigma'^2 and the number of elements a clamp changed.  Synchronises."""
-        if self.adaptive:
-            self.b.sync()
-            return tuple(float(x) for x in self._stats.download(np.float64, (5,)))
-        self._has_optimizer()
+        if not self.adaptive:
+            self._has_optimizer()
         self.b.sync()
-        return tuple(float(x) for x in self._stats.download(np.float64, (3,)))
+        return tuple(float(x) for x in self._stats.download(np.float64, (self.n_stats,)))
 
     # ------------------------------------------------------------ checkpoint of the centre
     def save(self, path):
@@ -491,15 +491,12 @@ class ES:
         import json
         w, b = self.b.es_get(self.n_weights, self.n_biases)
         meta = es_meta(self.layers, self.seed)
-        if self.optimizer is not None:
-            m, v = self.b.es_opt_get(self.n_weights, self.n_biases)
-            with open(moments_path(path), "wb") as f:
-                np.save(f, np.stack([np.concatenate(m), np.concatenate(v)]))
-            meta["optimizer"] = self._opt_meta()
-        if self.adaptive:
-            with open(sigma_path(path), "wb") as f:
-                np.save(f, np.concatenate(self.b.es_sigma_get(self.n_weights, self.n_biases)))
-            meta["sigma"] = self._sigma_meta()
+        for block, want, file_of, _, get, _ in self._vectors():
+            if want is not None:
+                a = get()
+                with open(file_of(path), "wb") as f:
+                    np.save(f, a)
+                meta[block] = want
         with open(path, "wb") as f:
             np.save(f, np.concatenate([w, b]))
         with open(sidecar_path(path), "w") as f:
@@ -507,12 +504,22 @@ class ES:
         return path
 
     def _opt_meta(self):
-        if self.optimizer is None:
-            return None
-        return es_opt_meta(self.optimizer, self.beta1, self.beta2, self.adam_eps, self.weight_decay, self.opt_steps)
+        return None if self.optimizer is None else es_opt_meta(self.optimizer, self.beta1, self.beta2, self.adam_eps,
+                                                               self.weight_decay, self.opt_steps)
 
     def _sigma_meta(self):
         return es_sigma_meta(self.sigma_lr, self.sigma_min, self.sigma_max) if self.adaptive else None
+
+    def _vectors(self):
+        """What a checkpoint may hold beside the centre, in the order save and load take it: (the sidecar's block, this
+        ES's meta for it or None, the array's file, the checker, the array from the device, the array to the device)."""
+        b, nw, nb = self.b, self.n_weights, self.n_biases
+        return (("optimizer", self._opt_meta(), moments_path, check_es_opt_meta,
+                 lambda: np.stack([np.concatenate(x) for x in b.es_opt_get(nw, nb)]),
+                 lambda a: b.es_opt_set(a[0, :nw], a[0, nw:], a[1, :nw], a[1, nw:])),
+                ("sigma", self._sigma_meta(), sigma_path, check_es_sigma_meta,
+                 lambda: np.concatenate(b.es_sigma_get(nw, nb)),
+                 lambda a: b.es_sigma_set(a[:nw], a[nw:])))
 
     def load(self, path):
         """The centre `save` wrote, into this ES.  ValueError naming the field, with the centre untouched, when the
@@ -525,25 +532,22 @@ class ES:
             meta = json.load(f)
         arr = np.load(path)
         check_es_meta(meta, arr.shape, arr.dtype, self.layers, self.seed, path)
-        want = self._opt_meta()
-        steps = check_es_opt_meta(meta, want, path=path)       # the sidecar first: no moments file is opened for a refusal
-        want_sigma = self._sigma_meta()
-        check_es_sigma_meta(meta, want_sigma, path=path)
-        if want is not None:
-            mom = np.load(moments_path(path))
-            check_es_opt_meta(meta, want, mom.shape, mom.dtype, arr.shape[0], path)
-        if want_sigma is not None:
-            sig = np.load(sigma_path(path))
-            check_es_sigma_meta(meta, want_sigma, sig.shape, sig.dtype, arr.shape[0], path)
-            if not (np.isfinite(sig).all() and (sig > 0).all()):
-                raise ValueError("%s: the sigma array holds a value that is not finite and > 0" % path)
+        vectors = self._vectors()
+        # the sidecar first: no array's file is opened for a refusal the sidecar alone decides
+        steps = [check(meta, want, path=path) for _, want, _, check, _, _ in vectors][0]
+        arrays = []
+        for block, want, file_of, check, _, put in vectors:
+            if want is not None:
+                a = np.load(file_of(path))
+                check(meta, want, a.shape, a.dtype, arr.shape[0], path)
+                if block == "sigma" and not (np.isfinite(a).all() and (a > 0).all()):
+                    raise ValueError("%s: the sigma array holds a value that is not finite and > 0" % path)
+                arrays.append((put, a))
         self.b.es_set(arr[:self.n_weights], arr[self.n_weights:])
-        if want is not None:
-            nw = self.n_weights
-            self.b.es_opt_set(mom[0, :nw], mom[0, nw:], mom[1, :nw], mom[1, nw:])
+        for put, a in arrays:
+            put(a)
+        if self.optimizer is not None:
             self.opt_steps = steps
-        if want_sigma is not None:
-            self.b.es_sigma_set(sig[:self.n_weights], sig[self.n_weights:])
 
 
 class ESRollout(ShardedRollout):
@@ -579,10 +583,7 @@ class ESRollout(ShardedRollout):
         if not self.ships or len(set(self.ships)) != len(self.ships) or not all(0 <= i < engine.M for i in self.ships):
             raise ValueError("ships must be distinct ship slots in [0, %d), got %r" % (engine.M, list(ships)))
         self.adaptive = bool(getattr(es, "adaptive", False))
-        if self.adaptive and sigma is not None:
-            raise ValueError("sigma must be None: the ES adapts sigma per element, got %r" % (sigma,))
-        if not self.adaptive and sigma is None:
-            raise ValueError("sigma must be a number: the ES does not adapt sigma")
+        check_sigma_mode(self.adaptive, sigma)
         self.P = check_members(P, sigma)
         if not math.isfinite(lr):
             raise ValueError("lr must be finite, got %r" % (lr,))
@@ -636,15 +637,10 @@ class ESRollout(ShardedRollout):
                                      float(ms.sum()) / float(max(int(mc.sum()), 1))))
             if self.eval_arenas:
                 self.centre_log.append(float(s[self.P]) / float(c[self.P]) if c[self.P] else float("nan"))
-            if self.adaptive:
-                d, w, n_c = pair_utilities(s, c)
-            else:
-                d, n_c = pair_weights(s, c)
+            d, w, n_c = pair_utilities(s, c)                   # d and n_c are pair_weights'
             if n_c >= 2:
-                if self.adaptive:
-                    self.es.update(d, self.lr, None, n_c, self.generation, s=w)
-                else:
-                    self.es.update(d, self.lr, self.sigma, n_c, self.generation)
+                # self.sigma is None exactly when adaptive; a scalar ES, or a stand-in for one, takes no s=
+                self.es.update(d, self.lr, self.sigma, n_c, self.generation, **({"s": w} if self.adaptive else {}))
                 if self.log_steps:
                     self.step_log.append(tuple(self.es.step_stats()))
             self.weight_log.append((d, w, n_c) if self.adaptive else (d, n_c))

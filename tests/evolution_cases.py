@@ -2,15 +2,15 @@
 tolerance and its power) and tests/test_gpu_evolution_edges.py (GPU: the same cases on the device).  A helper module
 (not collected).
 
-The cases aim at the branches of ofx_evolve.hip's k_pop_act that a sparse, even-sized map never takes: the mid-walk
-flush of a wave's cell list, the ship/laser boundary inside one wave's span, and the lane layouts n1 = 1 .. 64."""
+The cases aim at the branches of k_pop_act (ofx_evolve.hip; its walk and forward are ofx_genome.h's) that a sparse,
+even-sized map never takes: the mid-walk flush of a wave's cell list, the ship/laser boundary inside one wave's span, and the lane layouts n1 = 1 .. 64."""
 import math
 
 import numpy as np
 
 from tests import evolution_oracle as eo
 
-POP_LIST = 2048                      # ofx_evolve.hip: set cells one wave lists before it gathers
+POP_LIST = 2048                      # ofx_genome.h: set cells one wave lists before it gathers
 BEHAVIOURS = ("shoot", "turret")     # the bots of a scene with ticks > 0, dealt round-robin over the ships
 P = 5                                # genomes of a forward case
 RTOL = 1e-12                         # the project's figure for this kernel family; test_evolution_edges.py shows per
@@ -108,7 +108,7 @@ def quarter_counts(ship_map, laser_map):
     """Set cells in each quarter [q * per, min(total, (q + 1) * per)) of the run of total = 2 * words 32-cell words,
     per = ceil(total / 4).
 
-    This mirrors k_pop_act's split of the two bit maps over its four waves (ofx_evolve.hip: `per = (total + 3) / 4`)
+    This mirrors k_pop_act's split of the two bit maps over its four waves (pop_walk in ofx_genome.h: `per = (total + 3) / 4`)
     and is read against POP_LIST, a copy of that file's constant: it must move with them."""
     cells = np.asarray(ship_map).size
     assert cells % 32 == 0

@@ -16,13 +16,10 @@ from tests import es_opt_oracle as oo
 from tests import es_oracle as so
 from tests import evolution_oracle as eo
 from tests.abi_header import ROOT, header_symbols
+from tests.es_cases import bits as _bits
 
 LAYERS = [8 + 2 * 48 * 40, 9, 4]
 SEED = 0x0E512345
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def test_entry_points_declared_bound_and_exported():

@@ -18,15 +18,12 @@ from tests import es_oracle as so
 from tests import es_sigma_oracle as sg
 from tests import evolution_oracle as eo
 from tests.abi_header import ROOT, header_symbols
+from tests.es_cases import bits as _bits
 from tests.test_es_optimizer import _FakeBatch as _OptFakeBatch, _FakeBuffer
 
 LAYERS = [8 + 2 * 48 * 40, 9, 4]
 SEED = 0x0E512345
 ELEMENTS = np.array([0, 1, 77, 3848 * 9 - 1, 3848 * 9, 34680], np.int64)   # both sides of the first layer's end
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def test_entry_points_declared_bound_and_exported():
@@ -103,6 +100,27 @@ def test_pair_utilities_properties_and_the_oracle():
         pair_utilities(np.zeros(1, np.int64), np.zeros(1, np.int32))
     with pytest.raises(ValueError):
         pair_utilities(np.zeros(4, np.int64), np.zeros(5, np.int32))
+
+
+def test_pair_weights_is_pair_utilities_on_every_bit():
+    """pair_weights(s, c) == (pair_utilities(s, c)[0], [2]) - one ranking behind both - at P = 2, 4, 6 with and without
+    the centre's slot: ties, an incomplete pair, all means equal, fewer than two flown members."""
+    cases = {2: [([3, 1], [1, 1]), ([2, 2], [1, 1]), ([3, 1], [1, 0]), ([0, 0], [0, 0])],
+             4: [([6, 1, 4, 2], [2, 1, 2, 1]), ([5, 5, 1, 0], [1, 1, 1, 1]), ([9, 0, 4, 3], [1, 1, 0, 1]),
+                 ([4, 2, 2, 6], [2, 1, 1, 3]), ([5, 1, 0, 0], [1, 0, 0, 1])],
+             6: [([6, 1, 4, 2, 0, 5], [2, 1, 2, 1, 1, 1]), ([1, 1, 1, 2, 2, 2], [1, 1, 1, 1, 1, 1]),
+                 ([7, -3, 4, 4, 0, 5], [1, 1, 1, 1, 0, 2]), ([3, 3, 6, 6, 9, 9], [1, 1, 2, 2, 3, 3]),
+                 ([5, 1, 0, 0, 2, 2], [1, 0, 0, 1, 0, 0])]}
+    for P, rows in cases.items():
+        for s, c in rows:
+            for extra in ((), (99,)):                          # [P], then [P + 1] with the centre flown
+                sv, cv = np.array(list(s) + list(extra), np.int64), np.array(list(c) + [7] * len(extra), np.int32)
+                assert sv.shape == (P + len(extra),)
+                d, n_c = es.pair_weights(sv, cv)
+                ud, uw, un = pair_utilities(sv, cv)
+                assert n_c == un and type(n_c) is type(un), (s, c)
+                assert d.dtype == ud.dtype == np.float64 and d.shape == ud.shape == (P // 2,)
+                assert np.array_equal(_bits(d), _bits(ud)), (s, c)
 
 
 # ---------------------------------------------------------------- the oracle against the oracles it degenerates to

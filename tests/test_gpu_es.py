@@ -1,25 +1,14 @@
 """Seeded evolution strategies on the GPU: members, the forward against the stored-genome forward, the generation step,
 fitness and the loop, each against tests/es_oracle.py (numpy float64, the contract of include/ofx.h).  Every comparison
 is == on bits unless it says otherwise."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from tests import es_oracle as so
 from tests import evolution_oracle as eo
+from tests.es_cases import SEED, bits as _bits, vp as _vp
 
 pytestmark = pytest.mark.gpu
-
-SEED = 0x0E5090FF
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def _centre(es):

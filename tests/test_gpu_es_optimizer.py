@@ -2,57 +2,18 @@
 checkpoint and the loop, each against tests/es_opt_oracle.py (numpy float64, the contract of include/ofx.h).  theta, m and
 v are compared with == on bits everywhere; the three statistics, whose summation order is the library's own, to the worst
 case of any order."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from tests import es_opt_oracle as oo
 from tests import es_oracle as so
 from tests import evolution_oracle as eo
+from tests.es_cases import H, HIDDEN, NIN, SEED, W, bits as _bits, make as _make, same as _same, set_state as _set_state, \
+    state as _state, vp as _vp
 
 pytestmark = pytest.mark.gpu
 
-SEED = 0x0E5090FF
-W, H = 48, 40
-NIN = 8 + 2 * W * H
-HIDDEN = [(9,), (13, 7)]
 ADAM_SC = dict(gscale=1.0 / (6 * 0.05), alpha=0.03, c1=0.9, k1=1.0 - 0.9, c2=0.999, k2=1.0 - 0.999, eps=1e-8)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def _state(es):
-    """(theta, m, v) of an ES as element vectors, through ofx_es_get and ofx_es_opt_get."""
-    m, v = es.b.es_opt_get(es.n_weights, es.n_biases)
-    return np.concatenate(es.b.es_get(es.n_weights, es.n_biases)), np.concatenate(m), np.concatenate(v)
-
-
-def _set_state(es, theta, m, v):
-    nw = es.n_weights
-    es.b.es_set(theta[:nw], theta[nw:])
-    es.b.es_opt_set(m[:nw], m[nw:], v[:nw], v[nw:])
-
-
-def _same(got, want, what):
-    for g, w, name in zip(got, want, ("theta", "m", "v")):
-        diff = int((_bits(g) != _bits(w)).sum())
-        assert diff == 0, "%s: %s differs in %d of %d elements (max |diff| %.3e)" % (what, name, diff, g.size,
-                                                                                    float(np.max(np.abs(g - w))))
-
-
-def _make(hidden, optimizer, **kw):
-    from ofighters_amd import ArenaBatch
-    from ofighters_amd.es import ES
-    layers = [NIN] + list(hidden) + [4]
-    b = ArenaBatch(1, 1, width=W, height=H)
-    return b, ES(b, layers, SEED, optimizer=optimizer, **kw), layers
 
 
 def _random_moments(G, seed):

@@ -2,66 +2,26 @@
 generation step of centre and sigma, its statistics, the refusals, the lifetime and the loop, each against
 tests/es_sigma_oracle.py (numpy float64, the contract of include/ofx.h).  Every comparison of state - theta, sigma, m, v,
 y, the five statistics - is == on bits; only the numpy forward is compared at rtol 1e-12."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from tests import es_opt_oracle as oo
 from tests import es_oracle as so
 from tests import es_sigma_oracle as sg
+from tests import es_cases
 from tests import evolution_oracle as eo
+from tests.es_cases import H, HIDDEN, NIN, SEED, W, bits as _bits, same as _same, set_state as _set_state, \
+    state as _state, vp as _vp
 from tests.test_gpu_es import _assignment, _scaled_genome, _scene
 
 pytestmark = pytest.mark.gpu
 
-SEED = 0x0E5090FF
-W, H = 48, 40
-NIN = 8 + 2 * W * H
-HIDDEN = [(9,), (13, 7)]
 OPTIMIZERS = [None, "momentum", "adam"]
 
 
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def _state(es):
-    """(theta, sigma, m, v) of an ES as element vectors; m and v are None without optimiser state."""
-    b, nw, nb = es.b, es.n_weights, es.n_biases
-    m = v = None
-    if es.optimizer is not None:
-        m, v = (np.concatenate(x) for x in b.es_opt_get(nw, nb))
-    return np.concatenate(b.es_get(nw, nb)), np.concatenate(b.es_sigma_get(nw, nb)), m, v
-
-
-def _set_state(es, theta, sigma, m=None, v=None):
-    nw = es.n_weights
-    es.b.es_set(theta[:nw], theta[nw:])
-    es.b.es_sigma_set(sigma[:nw], sigma[nw:])
-    if m is not None:
-        es.b.es_opt_set(m[:nw], m[nw:], v[:nw], v[nw:])
-
-
-def _same(got, want, what):
-    for g, w, name in zip(got, want, ("theta", "sigma", "m", "v")):
-        if g is None and w is None:
-            continue
-        diff = int((_bits(g) != _bits(w)).sum())
-        assert diff == 0, "%s: %s differs in %d of %d elements (max |diff| %.3e)" % (what, name, diff, g.size,
-                                                                                    float(np.max(np.abs(g - w))))
-
-
-def _make(hidden, optimizer=None, sigma_init=0.05, N=1, M=1, **kw):
-    from ofighters_amd import ArenaBatch
-    from ofighters_amd.es import ES
-    layers = [NIN] + list(hidden) + [4]
-    b = ArenaBatch(N, M, width=W, height=H)
-    return b, ES(b, layers, SEED, optimizer=optimizer, sigma_init=sigma_init, **kw), layers
+def _make(hidden, optimizer=None, sigma_init=0.05, **kw):
+    """es_cases.make with adaptation on"""
+    return es_cases.make(hidden, optimizer, sigma_init=sigma_init, **kw)
 
 
 def _distinct_sigma(G):
