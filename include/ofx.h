@@ -194,6 +194,15 @@ int ofx_restart_finished(ofx_handle *h, uint64_t seed, const uint8_t *ship_mask,
                          const int32_t *group, int32_t n_groups, int64_t *sums);
 int ofx_autoreset_state_host(ofx_handle *h, uint32_t *episode_host, uint8_t *dead_once_host, uint8_t *restarted_host);
 int ofx_autoreset_set_state(ofx_handle *h, const uint32_t *episode_host, const uint8_t *dead_once_host);
+/* The restart of ofx_restart_finished, decided by the caller: every arena with arena_mask[a] != 0 (DEVICE uint8 [N],
+ * NULL = all) restarts, whatever its ships and its clock say.  For such an arena arena_episode[a] += 1, every ship gets
+ * ofx_restart's treatment, quirks included, on the draws of counter (global arena, ship, arena_episode[a]), and
+ * dead_once[a][*] = 0; nothing is summed and there is no `seen`.  restarted[a] = (arena_mask[a] != 0) is written for
+ * EVERY arena; an arena that is not selected changes in nothing else.  Allocates the state above like
+ * ofx_restart_finished, and like it ends by making the restarted arenas' agents forget previous_* while a replay memory
+ * exists.  One kernel of ofx_restart_finished's shape; does not synchronise.
+ * OFX_ERR_INVALID: NULL handle; OFX_ERR_STATE before ofx_spawn.                                                       */
+int ofx_restart_arenas(ofx_handle *h, uint64_t seed, const uint8_t *arena_mask);
 
 /* ---- the tick ----------------------------------------------------------
  * ofx_step = Agent.step bookkeeping for every ship, dead included
@@ -487,6 +496,34 @@ int ofx_es_act(ofx_handle *h, const int32_t *member_of, int64_t P, double sigma,
 /* ofx_population_fitness over members.  sum: DEVICE int64 [P + 1], count: DEVICE int32 [P + 1]; slot P is the centre.
  * Integer atomics.  Does not synchronise.                                                                            */
 int ofx_es_fitness(ofx_handle *h, const int32_t *member_of, int64_t P, int64_t *sum, int32_t *count, int32_t reset);
+/* THE MEMBER QUEUE (opt-in): with per-arena episodes (ofx_restart_finished, ofx_restart_arenas) the ships of an arena
+ * that restarts bank the score of the episode to the member they flew and take the next member from a queue on the
+ * device, so P no longer depends on the number of arenas.  All pointers are DEVICE pointers: member_of int32 [N][M],
+ * queue_mask uint8 [N][M] (the ships that draw from the queue), queue int64 [2] = (next, completed), sum int64 [P + 1],
+ * count int32 [P + 1].  The call reads the handle's restarted[N] as the last ofx_restart_finished / ofx_restart_arenas
+ * left it, and OFX_F_LAST_SCORES.  queue[0] >= 0 is the caller's to keep (a queue starts at (0, 0) and the call only
+ * counts up).  The law:
+ *   next = queue[0];  completed = queue[1]
+ *   for a = 0 .. N-1 ascending, if restarted[a] != 0:
+ *     for i = 0 .. M-1 ascending:
+ *       m = member_of[a][i]
+ *       if bank != 0 and 0 <= m <= P:
+ *           sum[m] += last_score[a][i];  count[m] += 1;  if m < P: completed += 1
+ *       if queue_mask[a][i] != 0:
+ *           if next < total:  member_of[a][i] = (int32)(next % P);  next += 1
+ *           else:             member_of[a][i] = -1
+ *   queue[0] = next;  queue[1] = completed
+ * Ticket t is member t % P: total = E * P flies every member exactly E times, and the two signs of a pair hold adjacent
+ * tickets.  A ship outside the queue mask keeps its member - an evaluation arena's centre, member P, banks to slot P on
+ * its own restarts.  A value of member_of outside [-1, P] is never banked; an arena with restarted[a] == 0 is not
+ * touched.  Two kernels: a wave per arena banks (integer atomics: exact in any order) and counts the tickets the arena
+ * asks for; one 256-thread workgroup scans the N counts and hands the tickets out.  A ticket is the RANK of its ship
+ * among the asking ships in ascending (a, i) order, from a prefix count - never the order atomics land in: the same
+ * state gives the same bits on every call.  Does not synchronise.
+ * Refusals, each with a message and before anything is enqueued: OFX_ERR_STATE while the handle has no per-arena
+ * episode state; OFX_ERR_INVALID for a NULL pointer, P odd or < 2, total < 0.                                          */
+int ofx_es_requeue(ofx_handle *h, int32_t *member_of, const uint8_t *queue_mask, int64_t P, int64_t total,
+                   int64_t *queue, int64_t *sum, int32_t *count, int32_t bank);
 /* The generation step.  d_host: HOST float64 [n_pairs], the weight of each pair (ofighters_amd.es.pair_weights).  Per
  * element e:
  *   g = 0.0;   for i = 0 .. n_pairs - 1 ascending:  g = g + d[i] * eps(i, e);   theta[e] = theta[e] + scale * g

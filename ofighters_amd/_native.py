@@ -96,6 +96,7 @@ SIGNATURES = {
     "ofx_spawn_random": (_i, [_vp, _u64]),
     "ofx_restart_random": (_i, [_vp, _u64, _u32]),
     "ofx_restart_finished": (_i, [_vp, _u64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp]),
+    "ofx_restart_arenas": (_i, [_vp, _u64, _vp]),
     "ofx_autoreset_state_host": (_i, [_vp, _vp, _vp, _vp]),
     "ofx_autoreset_set_state": (_i, [_vp, _vp, _vp]),
     "ofx_step": (_i, [_vp, _vp]),
@@ -136,6 +137,7 @@ SIGNATURES = {
     "ofx_es_member": (_i, [_vp, C.c_int64, C.c_int64, C.c_double, _u64, _u32, _vp, _vp]),
     "ofx_es_act": (_i, [_vp, _vp, C.c_int64, C.c_double, _u64, _u32, _vp, _vp]),
     "ofx_es_fitness": (_i, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int32]),
+    "ofx_es_requeue": (_i, [_vp, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp, _vp, C.c_int32]),
     "ofx_es_update": (_i, [_vp, _vp, C.c_int64, C.c_double, _u64, _u32]),
     "ofx_es_opt_create": (_i, [_vp]),
     "ofx_es_opt_destroy": (_i, [_vp]),

@@ -168,7 +168,7 @@ extern "C" int ofx_destroy(ofx_handle *h) {
   void *ptrs[] = {s.ship_x, s.ship_y, s.ship_px, s.ship_py, s.hull, s.reward, s.score, s.obs_reward, s.last_score,
                   s.alive, s.killer, s.time, s.n_lasers, s.laser_x, s.laser_y, s.laser_dx, s.laser_dy,
                   s.laser_owner, s.laser_dead, s.overflow, s.episode_sums, h->bot_behaviours, h->scratch, h->aux, h->prep, h->prep_tmp, h->counter, h->res_iaction, h->fitws, h->fitws2, h->applyws, h->trunk_stat, h->act_vals, h->eps_expo,
-                  h->ar_episode, h->ar_dead_once, h->ar_restarted};
+                  h->ar_episode, h->ar_dead_once, h->ar_restarted, h->ar_want};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   for (int t = 0; t < 5; t++) for (int w = 0; w < 2; w++) if (h->maps[t][w]) (void)hipFree(h->maps[t][w]);
   if (h->events) { (void)hipEventDestroy(h->ev0); (void)hipEventDestroy(h->ev1); }
@@ -349,6 +349,34 @@ __global__ __launch_bounds__(256) void k_restart_finished(FinishedParams p) {
   if (p.seen) p.seen[t] = 0;
 }
 
+// ofx_restart_arenas: k_restart_finished's restart branch for the arenas of `arena_mask` (null = all), decided by the
+// caller.  The same launch shape - wave per arena, lane = ship, every branch wave-uniform, no block barrier - and no
+// sums, no `seen`.
+struct ArenasParams {
+  int N, M, W, H, arena_base;
+  ofx_state st;
+  const uint8_t *arena_mask; // [N] or null = every arena
+  uint32_t *arena_episode;   // [N]
+  uint8_t *dead_once;        // [N][M]
+  uint8_t *restarted;        // [N]
+  ofx_rng_key key;
+};
+
+__global__ __launch_bounds__(256) void k_restart_arenas(ArenasParams p) {
+  const int a = blockIdx.x * OFX_ARENAS_PER_BLOCK + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (a >= p.N) return;  // wave-uniform
+  const bool go = !p.arena_mask || p.arena_mask[a] != 0;
+  if (lane == 0) p.restarted[a] = go ? 1 : 0;
+  if (!go) return;  // wave-uniform
+  const uint32_t episode = p.arena_episode[a] + 1u;
+  if (lane == 0) p.arena_episode[a] = episode;
+  if (lane >= p.M) return;
+  int dx, dy;
+  ofx_reset_draw(p.key, p.W, p.H, (uint32_t)(p.arena_base + a), (uint32_t)lane, episode, &dx, &dy);
+  restart_ship(p.st, p.M, a, lane, dx, dy, nullptr, nullptr);
+  p.dead_once[a * p.M + lane] = 0;
+}
+
 static ResetParams reset_params(ofx_handle *h, const int32_t *draws, const uint8_t *mask, uint64_t seed,
                                 uint32_t episode) {
   ResetParams p;
@@ -441,6 +469,23 @@ extern "C" int ofx_restart_finished(ofx_handle *h, uint64_t seed, const uint8_t 
   hipLaunchKernelGGL(k_restart_finished, dim3(arena_blocks(p.N)), dim3(256), 0, h->stream, p);
   OFX_HIP(hipGetLastError());
   return ofx_replay_episode_reset(h, h->ar_restarted);  // QlearnIA.reset of the restarted arenas' agents
+}
+
+extern "C" int ofx_restart_arenas(ofx_handle *h, uint64_t seed, const uint8_t *arena_mask) {
+  if (!h) { ofx_set_error("null handle"); return OFX_ERR_INVALID; }
+  if (!h->spawned) { ofx_set_error("ofx_restart_arenas before ofx_spawn"); return OFX_ERR_STATE; }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  int rc = autoreset_alloc(h);
+  if (rc) return rc;
+  ArenasParams p;
+  p.N = h->cfg.n_arenas; p.M = h->cfg.n_ships; p.W = h->cfg.width; p.H = h->cfg.height;
+  p.arena_base = h->cfg.arena_base;
+  p.st = h->st; p.arena_mask = arena_mask;
+  p.arena_episode = h->ar_episode; p.dead_once = h->ar_dead_once; p.restarted = h->ar_restarted;
+  p.key = ofx_key(seed);
+  hipLaunchKernelGGL(k_restart_arenas, dim3(arena_blocks(p.N)), dim3(256), 0, h->stream, p);
+  OFX_HIP(hipGetLastError());
+  return ofx_replay_episode_reset(h, h->ar_restarted);
 }
 
 extern "C" int ofx_autoreset_state_host(ofx_handle *h, uint32_t *episode_host, uint8_t *dead_once_host,

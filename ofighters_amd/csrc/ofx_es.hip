@@ -18,6 +18,9 @@
 // k_es_member  a member materialised into a G-double buffer, for ofx_es_member.
 // k_es_sigma_act / k_es_sigma_member / k_es_sigma_step  the same with a per-element exploration width sigma[e] beside
 //              the centre, learned in the pass that steps the centre (PEPG with symmetric sampling).
+// k_es_requeue_bank / k_es_requeue_assign  ofx_es_requeue: the ships of restarted arenas bank to the member they flew
+//              (integer atomics) and take the next members of a device-side queue; tickets are ranks from a prefix count
+//              over the arenas, never the order atomics land in.
 #include "ofx_genome.h"
 
 #include <new>
@@ -377,6 +380,82 @@ __global__ __launch_bounds__(256) void k_es_sigma_step(double *theta, double *si
 }
 
 // ---- host side ----
+// ofx_es_requeue, pass 1 (include/ofx.h has the law).  One 64-lane wave per arena, lane = ship, four arenas per block as
+// in k_restart_finished; an arena that did not restart costs its wave one byte read and one store.  Banking is integer
+// atomics (exact in any order); what the arena wants from the queue is a ballot.  No block barrier.
+__global__ __launch_bounds__(256) void k_es_requeue_bank(int N, int M, long long P, int bank, const uint8_t *restarted,
+                                                         const int32_t *last_score, const int32_t *member_of,
+                                                         const uint8_t *queue_mask, unsigned long long *sum, int *count,
+                                                         int32_t *want, unsigned long long *completed) {
+  const int a = blockIdx.x * OFX_ARENAS_PER_BLOCK + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (a >= N) return;  // wave-uniform
+  if (!restarted[a]) {  // wave-uniform
+    if (lane == 0) want[a] = 0;
+    return;
+  }
+  const bool ship = lane < M;
+  const size_t t = (size_t)a * M + lane;  // used under `ship` only
+  const long long m = ship ? (long long)member_of[t] : -1;
+  const bool banked = bank && m >= 0 && m <= P;
+  if (banked) {
+    atomicAdd(sum + m, (unsigned long long)(long long)last_score[t]);
+    atomicAdd(count + m, 1);
+  }
+  const unsigned long long done = __ballot(banked && m < P), asks = __ballot(ship && queue_mask[t] != 0);
+  if (lane == 0) {
+    want[a] = __popcll(asks);
+    if (done) atomicAdd(completed, (unsigned long long)__popcll(done));
+  }
+}
+
+// Pass 2: ONE 256-thread workgroup.  Thread t owns the contiguous run of `run` = ceil(N / 256) arenas from t * run; the
+// exclusive prefix of the runs' wants - a shuffle scan inside each wave, the four wave totals through LDS - is the rank of
+// the run's first ticket, so tickets go out in ascending (arena, ship) order whatever order anything executes in.  A
+// thread then walks only the arenas of its run that want tickets (want > 0 implies restarted).
+__global__ __launch_bounds__(256) void k_es_requeue_assign(int N, int M, int run, long long P, long long total,
+                                                           const int32_t *want, const uint8_t *queue_mask,
+                                                           int32_t *member_of, long long *queue) {
+  __shared__ int wave_sum[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int first = min(tid * run, N), last = min(first + run, N);  // (run <= 2^23: tid * run fits)
+  int mine = 0;
+  for (int a = first; a < last; a++) mine += want[a];
+  int incl = mine;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int up = __shfl_up(incl, d);
+    if (lane >= d) incl += up;
+  }
+  if (lane == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  int base = incl - mine, all = 0;
+  for (int w = 0; w < 4; w++) {
+    if (w < wave) base += wave_sum[w];
+    all += wave_sum[w];
+  }
+  const long long next = queue[0];
+  const long long left = total > next ? total - next : 0;   // tickets still in the queue
+  if (mine > 0) {
+    long long rank = base;
+    long long m = rank < left ? (next + rank) % P : 0;       // one division per thread; then m walks round P
+    for (int a = first; a < last; a++) {
+      if (want[a] == 0) continue;
+      const size_t row = (size_t)a * M;
+      for (int i = 0; i < M; i++) {
+        if (!queue_mask[row + i]) continue;
+        if (rank < left) {
+          member_of[row + i] = (int32_t)m;
+          if (++m == P) m = 0;
+        } else {
+          member_of[row + i] = -1;
+        }
+        rank++;
+      }
+    }
+  }
+  __syncthreads();  // every thread has read queue[0]
+  if (tid == 0) queue[0] = next + (all < left ? (long long)all : left);
+}
+
 static ofx_es *&es_of(ofx_handle *h) { return h->es; }
 static unsigned es_blocks(const ofx_es *p) { return p->shape.blocks(); }   // one thread per storage position
 
@@ -577,6 +656,33 @@ extern "C" int ofx_es_fitness(ofx_handle *h, const int32_t *member_of, int64_t P
   if (!member_of || !sum || !count) { ofx_set_error("ofx_es_fitness: null argument"); return OFX_ERR_INVALID; }
   if (!h->spawned) { ofx_set_error("ofx_es_fitness before ofx_spawn"); return OFX_ERR_STATE; }
   return launch_fitness(h, (size_t)P + 1, member_of, sum, count, reset);   // slot P: the centre
+}
+
+extern "C" int ofx_es_requeue(ofx_handle *h, int32_t *member_of, const uint8_t *queue_mask, int64_t P, int64_t total,
+                              int64_t *queue, int64_t *sum, int32_t *count, int32_t bank) {
+  if (!h) { ofx_set_error("ofx_es_requeue: null handle"); return OFX_ERR_INVALID; }
+  if (!member_of || !queue_mask || !queue || !sum || !count) {
+    ofx_set_error("ofx_es_requeue: null argument");
+    return OFX_ERR_INVALID;
+  }
+  const int rc = check_members("ofx_es_requeue", P, 1.0);
+  if (rc) return rc;
+  if (total < 0) { ofx_set_error("ofx_es_requeue: total must be >= 0 (got %lld)", (long long)total); return OFX_ERR_INVALID; }
+  if (!h->ar_restarted) {
+    ofx_set_error("ofx_es_requeue: no arena has its own episodes yet (ofx_restart_finished or ofx_restart_arenas first)");
+    return OFX_ERR_STATE;
+  }
+  OFX_HIP(hipSetDevice(h->cfg.device));
+  const int N = h->cfg.n_arenas, M = h->cfg.n_ships;
+  if (!h->ar_want) OFX_HIP(hipMalloc((void **)&h->ar_want, (size_t)N * sizeof(int32_t)));  // pass 1 writes all of it
+  hipLaunchKernelGGL(k_es_requeue_bank, dim3(arena_blocks(N)), dim3(256), 0, h->stream, N, M, (long long)P, (int)(bank != 0),
+                     h->ar_restarted, h->st.last_score, member_of, queue_mask, (unsigned long long *)sum, count, h->ar_want,
+                     (unsigned long long *)(queue + 1));
+  OFX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_es_requeue_assign, dim3(1), dim3(256), 0, h->stream, N, M, (N + 255) / 256, (long long)P,
+                     (long long)total, h->ar_want, queue_mask, member_of, (long long *)queue);
+  OFX_HIP(hipGetLastError());
+  return OFX_OK;
 }
 
 // d_host[n_pairs] as the generation steps take it (`who`): not NULL, n_pairs in range

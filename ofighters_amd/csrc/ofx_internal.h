@@ -98,6 +98,7 @@ struct ofx_handle {
   uint32_t *ar_episode;            // [N]
   uint8_t *ar_dead_once;           // [N][M]
   uint8_t *ar_restarted;           // [N]
+  int32_t *ar_want;                // [N] ofx_es_requeue: the tickets each arena asks for (allocated at its first call)
   ofx_population *population;      // genomes of the neuroevolution (ofx_population_create), null = none
   ofx_es *es;                      // centre of the evolution strategy (ofx_es_create), null = none
 };

@@ -198,6 +198,12 @@ class ArenaBatch:
                                                  group_buf.ptr if group_buf is not None else None, int(n_groups),
                                                  sums_buf.ptr if sums_buf is not None else None))
 
+    def restart_arenas(self, seed, mask_buf=None):
+        """Restart, on the device, the arenas the caller names (ofx_restart_arenas): mask_buf is a DeviceBuffer of uint8
+        [N], None = every arena.  restart_finished's restart without its decision, its sums and its `seen`; `restarted`
+        of autoreset_state() becomes the mask.  `episode` is not advanced.  Does not synchronise."""
+        nat.check(nat.lib().ofx_restart_arenas(self._h, seed, mask_buf.ptr if mask_buf is not None else None))
+
     def autoreset_state(self):
         """restart_finished's state on the host: arena_episode uint32 [N], dead_once uint8 [N][M] and restarted uint8
         [N], the arenas the last call restarted.  OfxError (OFX_ERR_STATE) before the first call.  Synchronises."""
@@ -1143,6 +1149,14 @@ class ArenaBatch:
         """population_fitness over members: sum int64 [P + 1], count int32 [P + 1], slot P the centre.  Does not
         synchronise."""
         nat.check(nat.lib().ofx_es_fitness(self._h, member_of_ptr, int(P), sum_buf.ptr, count_buf.ptr, int(bool(reset))))
+
+    def es_requeue(self, member_of_ptr, queue_mask_ptr, P, total, queue_buf, sum_buf, count_buf, bank=True):
+        """The member queue (ofx_es_requeue: the law, line by line): the ships of the arenas the last restart_finished /
+        restart_arenas restarted bank to the member they flew (bank) and those under the device uint8 [N][M] at
+        queue_mask_ptr take the next tickets of queue_buf (int64 [2]: next, completed), member = ticket % P, -1 once
+        `total` tickets are out.  Rewrites the device int32 [N][M] at member_of_ptr.  Does not synchronise."""
+        nat.check(nat.lib().ofx_es_requeue(self._h, member_of_ptr, queue_mask_ptr, int(P), int(total), queue_buf.ptr,
+                                           sum_buf.ptr, count_buf.ptr, int(bool(bank))))
 
     def es_update(self, d, scale, seed, generation):
         """theta[e] += scale * sum_i d[i] * eps(i, e) in ascending pair order (ofx_es_update); d: float64 [P / 2].  Does

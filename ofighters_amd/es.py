@@ -316,6 +316,8 @@ class ES:
         self._member_of = DeviceBuffer(batch.N * batch.M * 4)
         self.P, self.member_of = None, None
         self._sum = self._count = None
+        self._queue = self._queue_mask = None     # the member queue's (next, completed) and its ships (queue_begin)
+        self.queue_total = None
         if init:
             self.init()
 
@@ -430,6 +432,72 @@ class ES:
         self.b.sync()
         self._sum.upload(s)
         self._count.upload(c)
+
+    # ------------------------------------------------------------ the member queue (ofx_es_requeue)
+    def queue_begin(self, queue_mask, P, total):
+        """Start a queue of `total` tickets over the assignment made by assign(member_of, P): ticket t is member t % P,
+        so total = E * P flies every member E times.  queue_mask: numpy [N][M], nonzero where a ship draws from the
+        queue; it is uploaded, member_of becomes -1 on those ships (the other entries of the caller's assignment stay),
+        and sum, count and the queue's (next, completed) start at zero.  Synchronises."""
+        from .engine import DeviceBuffer
+        self._assigned()
+        if check_members(P) != self.P:
+            raise ValueError("P is %d, the assignment was made for %d: call assign first" % (P, self.P))
+        if int(total) != total or int(total) < 0:
+            raise ValueError("total must be an integer >= 0, got %r" % (total,))
+        q = np.asarray(queue_mask)
+        if q.shape != (self.b.N, self.b.M):
+            raise ValueError("queue_mask is an array [%d][%d], got %s" % (self.b.N, self.b.M, q.shape))
+        q = np.ascontiguousarray(q != 0, dtype=np.uint8)
+        a = self.member_of.copy()
+        a[q != 0] = -1
+        self.b.sync()
+        if self._queue is None:
+            self._queue_mask, self._queue = DeviceBuffer(q.nbytes), DeviceBuffer(16)
+        self._queue_mask.upload(q)
+        self._member_of.upload(a)
+        self._sum.upload(np.zeros(self.P + 1, np.int64))
+        self._count.upload(np.zeros(self.P + 1, np.int32))
+        self._queue.upload(np.zeros(2, np.int64))
+        self.queue_total = int(total)
+
+    def _queued(self):
+        if self._queue is None:
+            raise ValueError("no queue yet: call queue_begin(queue_mask, P, total) first")
+
+    def requeue(self, bank=True):
+        """After restart_finished / restart_arenas: the ships of the restarted arenas bank what they scored to the member
+        they flew (bank) and the queue's ships take the next tickets, -1 when none is left.  Does not synchronise."""
+        self._queued()
+        self.b.es_requeue(self._member_of.ptr, self._queue_mask.ptr, self.P, self.queue_total, self._queue, self._sum,
+                          self._count, bank)
+
+    def queue_host(self):
+        """(next, completed): the tickets handed out and the member evaluations banked so far.  Synchronises."""
+        self._queued()
+        self.b.sync()
+        nxt, completed = self._queue.download(np.int64, (2,))
+        return int(nxt), int(completed)
+
+    def member_of_host(self):
+        """member_of as the device holds it now (requeue rewrites it), int32 [N][M].  Synchronises."""
+        self._assigned()
+        self.b.sync()
+        return self._member_of.download(np.int32, (self.b.N, self.b.M))
+
+    def load_queue(self, member_of, queue):
+        """Put back what member_of_host and queue_host returned (a resumed run), after queue_begin.  The queue must
+        satisfy 0 <= completed <= next <= total.  The host copy `member_of` stays the assignment assign() was given:
+        under the queue only the device holds who flies what (member_of_host)."""
+        self._queued()
+        a = check_member_assignment(member_of, self.b.N, self.b.M, self.P)
+        q = np.asarray([int(v) for v in queue], np.int64)
+        if q.shape != (2,) or not (0 <= q[1] <= q[0] <= self.queue_total):
+            raise ValueError("queue is (next, completed) with 0 <= completed <= next <= total = %d, got %r"
+                             % (self.queue_total, queue))
+        self.b.sync()
+        self._member_of.upload(a)
+        self._queue.upload(q)
 
     def update(self, d, lr, sigma, n_c, generation, s=None):
         """The generation step theta += lr / (n_c sigma) * sum_i d_i eps(i, .) on the noise of `generation`, the one the
@@ -571,10 +639,32 @@ class ESRollout(ShardedRollout):
     sigma  a number, or None exactly when es.adaptive: the members then fly with the ES's own sigma per element, the
         generation end uses pair_utilities, `weight_log` keeps (d, s, n_c), es.update gets s=s and, with log_steps,
         `step_log` holds five-tuples (ES.step_stats).
+    auto_reset  opt-in (a bool; False: lockstep() makes exactly the calls it always made).  True gives every arena its
+        own episodes and takes the members from a queue on the device (include/ofx.h, "the member queue"), so P may
+        exceed N * len(ships) and no lock-step is spent on a finished evaluation except in a generation's tail.
+        episodes_per_generation is then E, the evaluations per member, and a generation is total = E * P tickets, ticket
+        t = member t % P.  The queue mask is `ships` in the first N - eval_arenas arenas, the restart mask `ships` in
+        every arena; the evaluation arenas hold member P throughout and bank to slot P on their own restarts.
+        A generation BEGINS - at construction after the spawn, and after every update - with es.queue_begin,
+        engine.restart_arenas(seed) on all arenas and es.requeue(bank=False): a centre episode cut by the forced restart
+        is discarded, centre_log[g] holds only episodes flown wholly by centre g.  Every lockstep() STARTS with
+        engine.restart_finished(seed, restart mask, max_ticks=episode_ticks) and es.requeue(bank=True); when tick > 0 and
+        tick % poll_every == 0 the two queue counters come to the host (the one synchronisation), and
+        completed == total ends the generation: fitness to the host, fitness_log (centre_log), pair_utilities, update,
+        step_log, weight_log, generation += 1, then the next generation begins; then the lock-step goes on as ever.  A
+        ship whose tickets ran out (member -1) flies its `behaviours` entry until the generation ends.  The global
+        episode end never runs: score_log stays empty and engine.episode 0.  `generation_log` holds per generation
+        (lock-steps it took, member evaluations banked, centre episodes banked).
+    poll_every  an integer >= 1: how often, in lock-steps, auto_reset looks at the queue.
     """
 
     def __init__(self, engine, es, behaviours, seed, P, sigma, lr, ships=(0,), episodes_per_generation=1, eval_arenas=0,
-                 log_steps=False, **kw):
+                 log_steps=False, auto_reset=False, poll_every=8, **kw):
+        if not isinstance(auto_reset, (bool, np.bool_)):   # every argument is checked before the first device call
+            raise ValueError("auto_reset must be a bool, got %r" % (auto_reset,))
+        if isinstance(poll_every, bool) or not isinstance(poll_every, (int, np.integer)) or poll_every < 1:
+            raise ValueError("poll_every must be an integer >= 1, got %r" % (poll_every,))
+        self.auto_reset, self.poll_every = bool(auto_reset), int(poll_every)
         if kw.get("dist") is not None:
             raise ValueError("ESRollout runs on one GPU: `dist` must be None")
         if kw.get("policy") is not None or kw.get("observe"):
@@ -605,10 +695,48 @@ class ESRollout(ShardedRollout):
         self.log_steps = bool(log_steps)
         self.step_log = []                # (grad_sq, step_sq, centre_sq) per stepped generation (log_steps)
         self.policy = self._fly
-        self._assign()
+        self.generation_log = []          # auto_reset: (lock-steps, member evaluations banked, centre episodes banked)
+        if not self.auto_reset:
+            self._assign()
+            return
+        from .engine import DeviceBuffer
+        self.total = self.episodes_per_generation * self.P    # tickets of a generation: every member flown E times
+        restart = np.zeros((engine.N, engine.M), np.uint8)
+        restart[:, self.ships] = 1
+        self.queue_mask = restart.copy()
+        self.queue_mask[engine.N - self.eval_arenas:] = 0     # the evaluation arenas hold member P throughout
+        held = np.full((engine.N, engine.M), -1, np.int32)
+        held[restart != self.queue_mask] = self.P
+        engine.sync()
+        self._restart_mask = DeviceBuffer(restart.nbytes).upload(restart)
+        self.es.assign(held, self.P)
+        self._generation_begin()
 
     def _fly(self, engine):
         self.es.act(self.sigma, self.generation)
+
+    # ------------------------------------------------------------ auto_reset: per-arena episodes, members from a queue
+    def _generation_begin(self):
+        """Every arena starts an episode of its own on fresh tickets; a centre episode cut here is discarded."""
+        self.es.queue_begin(self.queue_mask, self.P, self.total)
+        self.e.restart_arenas(self.seed)
+        self.es.requeue(bank=False)
+        self._generation_tick = self.tick
+
+    def lockstep(self):
+        if not self.auto_reset:
+            return super().lockstep()
+        self.e.restart_finished(self.seed, self._restart_mask.ptr, max_ticks=self.episode_ticks)
+        self.es.requeue(bank=True)
+        if self.tick > 0 and self.tick % self.poll_every == 0:
+            if self.es.queue_host()[1] == self.total:
+                self._generation_end()
+        self._fly_and_step()
+
+    def _generation_end(self):
+        s, c = self._learn()
+        self.generation_log.append((self.tick - self._generation_tick, int(c[:self.P].sum()), int(c[self.P])))
+        self._generation_begin()
 
     def assignment(self, generation):
         """member_of (int32 [N][M]) of `generation` by the formula; the last eval_arenas arenas fly the centre."""
@@ -629,32 +757,41 @@ class ESRollout(ShardedRollout):
         self.es.fitness(reset=self.episodes == 0)
         self.episodes += 1
         if self.episodes == self.episodes_per_generation:
-            s, c = self.es.fitness_host()
-            ms, mc = s[:self.P], c[:self.P]
-            flown = mc > 0
-            mean = ms[flown] / mc[flown]
-            self.fitness_log.append((float(mean.max()) if flown.any() else float("nan"),
-                                     float(ms.sum()) / float(max(int(mc.sum()), 1))))
-            if self.eval_arenas:
-                self.centre_log.append(float(s[self.P]) / float(c[self.P]) if c[self.P] else float("nan"))
-            d, w, n_c = pair_utilities(s, c)                   # d and n_c are pair_weights'
-            if n_c >= 2:
-                # self.sigma is None exactly when adaptive; a scalar ES, or a stand-in for one, takes no s=
-                self.es.update(d, self.lr, self.sigma, n_c, self.generation, **({"s": w} if self.adaptive else {}))
-                if self.log_steps:
-                    self.step_log.append(tuple(self.es.step_stats()))
-            self.weight_log.append((d, w, n_c) if self.adaptive else (d, n_c))
-            self.generation += 1
+            self._learn()
             self.episodes = 0
             self._assign()
         return total
+
+    def _learn(self):
+        """The end of a generation up to generation += 1: the fitness comes to the host, the logs, the centre's step.
+        Returns the (sum, count) it learned from."""
+        s, c = self.es.fitness_host()
+        ms, mc = s[:self.P], c[:self.P]
+        flown = mc > 0
+        mean = ms[flown] / mc[flown]
+        self.fitness_log.append((float(mean.max()) if flown.any() else float("nan"),
+                                 float(ms.sum()) / float(max(int(mc.sum()), 1))))
+        if self.eval_arenas:
+            self.centre_log.append(float(s[self.P]) / float(c[self.P]) if c[self.P] else float("nan"))
+        d, w, n_c = pair_utilities(s, c)                   # d and n_c are pair_weights'
+        if n_c >= 2:
+            # self.sigma is None exactly when adaptive; a scalar ES, or a stand-in for one, takes no s=
+            self.es.update(d, self.lr, self.sigma, n_c, self.generation, **({"s": w} if self.adaptive else {}))
+            if self.log_steps:
+                self.step_log.append(tuple(self.es.step_stats()))
+        self.weight_log.append((d, w, n_c) if self.adaptive else (d, n_c))
+        self.generation += 1
+        return s, c
 
     # ------------------------------------------------------------ stop and go on
     def state_dict(self):
         """What a run stopped between two lock-steps needs, beside the centre (ES.save: with an optimizer also its
         moments and step count), to go on bit for bit in fresh handles: the generation and episode counters, the logs
         (step_log only with log_steps), the fitness sums and counts of the running generation, the tick and
-        ArenaBatch.state_dict()."""
+        ArenaBatch.state_dict().  Under auto_reset it also carries auto_reset and poll_every (load_state_dict refuses a
+        rollout whose own differ, by field, before anything is touched; a state without them was written with the
+        option off), member_of as the queue left it, the queue's (next, completed), the arenas' episode counters and
+        dead_once marks, generation_log and the tick the running generation began at."""
         s, c = self.es.fitness_host()
         d = {"generation": self.generation, "episodes": self.episodes, "tick": self.tick,
              "fitness_log": list(self.fitness_log), "centre_log": list(self.centre_log),
@@ -663,6 +800,12 @@ class ESRollout(ShardedRollout):
              "engine": self.e.state_dict()}
         if self.log_steps:
             d["step_log"] = list(self.step_log)
+        if self.auto_reset:
+            # what the queue has handed out, and every arena's own episode (the engine's counters, not in its state_dict)
+            auto = self.e.autoreset_state()
+            d.update(auto_reset=True, poll_every=self.poll_every, member_of=self.es.member_of_host(), queue=self.es.queue_host(),
+                     arena_episode=auto["arena_episode"], dead_once=auto["dead_once"],
+                     generation_log=list(self.generation_log), generation_tick=self._generation_tick)
         return d
 
     def load_state_dict(self, d):
@@ -672,6 +815,16 @@ class ESRollout(ShardedRollout):
                                "fitness_sum", "fitness_count", "engine") if k not in d]
         if missing:
             raise ValueError("ESRollout.load_state_dict: field %r is missing" % missing[0])
+        # a state written with the option off has neither field (poll_every means nothing there)
+        for field, mine in (("auto_reset", self.auto_reset), ("poll_every", self.poll_every)):
+            saved = d.get(field, False if field == "auto_reset" else mine)
+            if saved != mine and (field == "auto_reset" or self.auto_reset):
+                raise ValueError("ESRollout.load_state_dict: %s is %r, this rollout's is %r" % (field, saved, mine))
+        if self.auto_reset:
+            missing = [k for k in ("member_of", "queue", "arena_episode", "dead_once", "generation_log",
+                                   "generation_tick") if k not in d]
+            if missing:
+                raise ValueError("ESRollout.load_state_dict: field %r is missing" % missing[0])
         self.e.load_state_dict(d["engine"])
         self.generation, self.episodes, self.tick = int(d["generation"]), int(d["episodes"]), int(d["tick"])
         self.fitness_log, self.centre_log = list(d["fitness_log"]), list(d["centre_log"])
@@ -679,5 +832,12 @@ class ESRollout(ShardedRollout):
         self.score_log = [np.array(t) for t in d["score_log"]]
         if "step_log" in d:
             self.step_log = [tuple(t) for t in d["step_log"]]
-        self._assign()
+        if self.auto_reset:
+            # the construction began a generation of its own: the saved one's tickets and counters replace it
+            self.e.load_autoreset_state({"arena_episode": d["arena_episode"], "dead_once": d["dead_once"]})
+            self.es.load_queue(d["member_of"], d["queue"])
+            self.generation_log = [tuple(int(v) for v in t) for t in d["generation_log"]]
+            self._generation_tick = int(d["generation_tick"])
+        else:
+            self._assign()
         self.es.load_fitness(d["fitness_sum"], d["fitness_count"])

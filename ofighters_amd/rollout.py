@@ -65,6 +65,10 @@ class ShardedRollout:
     def lockstep(self):
         if self.tick > 0 and self.tick % self.episode_ticks == 0:
             self._episode_end()
+        self._fly_and_step()
+
+    def _fly_and_step(self):
+        """A lock-step behind its episode-end check: the bots, the policy hook, the step, the observation."""
         self.e.bot_actions(self.behaviours, self.seed, tick=self.tick)
         if self.policy is not None:
             self.policy(self.e)

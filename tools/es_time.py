@@ -36,8 +36,11 @@ sigma    per-element adaptive sigma against the scalar calls (profiles/r31_es_si
          ofx_es_act and ofx_es_step alone, which is what an older build of the library can run (for a comparison of
          these two kernels across builds, and an A/A run of one build for its noise).
          `loop` takes `--adaptive`: ES(sigma_init=`--sigma`, sigma_lr=`--sigma-lr` (0.2)), ESRollout(sigma=None).
+queue    the generational loop against ESRollout(auto_reset=True) - per-arena episodes, members from the device-side
+         queue (profiles/r32_es_queue.txt): queue()'s docstring has the protocol.  [--members 4096] [--evaluations 1]
+         [--poll-every 8] [--sample-every 10] [--event-steps 200]
 Each mode prints one JSON line and, with `--out FILE`, appends it to that file.
-Usage: python tools/es_time.py kernels|loop|sigma [--arenas 4096] [--small 4096] [--large 32768] [--stored 512] [--calls 50]
+Usage: python tools/es_time.py kernels|loop|sigma|queue [--arenas 4096] [--small 4096] [--large 32768] [--stored 512] [--calls 50]
                                [--repeats 3] [--generations 5] [--eval-arenas 64] [--optimizer adam|momentum]
                                [--weight-decay 0.005] [--lr 0.1] [--sigma 0.05] [--adaptive] [--sigma-lr 0.2]
                                [--no-sigma] [--out FILE]
@@ -255,11 +258,93 @@ def loop():
     return out
 
 
+def _queue_loop(P, E, generations, eval_arenas, auto_reset, poll_every, sample_every, event_steps):
+    """One ESRollout to `generations` generations under a host clock that stops for the samples; see queue()."""
+    b = ArenaBatch(ARENAS, M)
+    es = ES(b, LAYERS, SEED)
+    T = b.cfg.episode_ticks
+    roll = ESRollout(b, es, ["random"] * M, SEED, P, SIGMA, LR, ships=(0,), eval_arenas=eval_arenas, episode_ticks=T,
+                     episodes_per_generation=E, **(dict(auto_reset=True, poll_every=poll_every) if auto_reset else {}))
+    learn = ARENAS - eval_arenas
+    alive, flying, seconds, steps = [], [], 0.0, 0
+    b.sync()
+    t0 = time.perf_counter()
+    while roll.generation < generations:
+        roll.lockstep()
+        steps += 1
+        if steps % sample_every == 0:                           # the clock stops for the sample
+            b.sync()
+            seconds += time.perf_counter() - t0
+            a = b.get(nat.F_SHIP_ALIVE)[:learn, 0] != 0
+            if auto_reset:                                      # an idle ship (member -1, the tail) evaluates nothing
+                held = es.member_of_host()[:learn, 0] >= 0
+                a &= held
+                flying.append(float(held.mean()))
+            alive.append(float(a.mean()))
+            t0 = time.perf_counter()
+    b.sync()
+    seconds += time.perf_counter() - t0
+    if auto_reset:
+        evaluations = sum(g[1] for g in roll.generation_log)
+        per_generation = [g[0] for g in roll.generation_log]
+    else:
+        evaluations = generations * E * learn                   # every learning arena's ship banks once per episode
+        per_generation = [E * T] * generations
+    out = {"auto_reset": auto_reset, "P": P, "E": E, "generations": roll.generation, "lock_steps": steps,
+           "lock_steps_per_generation": per_generation, "seconds": round(seconds, 4),
+           "ms_per_lock_step": round(seconds * 1e3 / steps, 4), "member_evaluations": int(evaluations),
+           "member_evaluations_per_s": round(evaluations / seconds, 1),
+           "members_of_complete_pairs": [w[-1] for w in roll.weight_log],
+           "share_evaluating_at_forward": round(float(np.mean(alive)), 4), "samples": len(alive),
+           "fitness_log_mean": [round(f[1], 3) for f in roll.fitness_log],
+           "centre_log": [round(c, 3) for c in roll.centre_log]}
+    if auto_reset:
+        out["share_holding_a_ticket"] = round(float(np.mean(flying)), 4)
+        out["centre_episodes_per_generation"] = [g[2] for g in roll.generation_log]
+        # restart_finished + requeue at the head of `event_steps` more lock-steps, one event pair each
+        e, rf, rq, j = roll.e, roll.e.restart_finished, es.requeue, [0]
+
+        def restart_finished(*a, **k):
+            e.event_record(2 * j[0])
+            return rf(*a, **k)
+
+        def requeue(bank=True):
+            rq(bank)
+            if bank:
+                e.event_record(2 * j[0] + 1)
+                j[0] += 1
+        e.restart_finished, es.requeue = restart_finished, requeue
+        g0 = roll.generation
+        while j[0] < event_steps and roll.generation == g0:
+            roll.lockstep()
+        e.restart_finished, es.requeue = rf, rq
+        b.sync()
+        us = [b.event_elapsed(2 * i, 2 * i + 1) * 1e3 for i in range(j[0])]
+        out["restart_finished_plus_requeue_us"] = {"lock_steps": j[0], "mean": round(float(np.mean(us)), 2),
+                                                   "median": round(float(np.median(us)), 2),
+                                                   "max": round(float(np.max(us)), 2)}
+    b.close()
+    return out
+
+
+def queue():
+    """`queue`: the old generational loop against ESRollout(auto_reset=True) (profiles/r32_es_queue.txt) at P =
+    `--members` (4096), E = `--evaluations` (1), `--generations` (3), `--eval-arenas` (64), `--poll-every` (8).  A host
+    clock around the lock-steps of each loop, ending in a synchronise and stopped for the samples: every
+    `--sample-every` (10) lock-steps, the share of the learning arenas' evolved ships that are alive and fly a member.
+    Then, with the option on, `--event-steps` (200) lock-steps with one event pair around restart_finished + requeue."""
+    P, E, generations = _arg("--members", 4096), _arg("--evaluations", 1), _arg("--generations", 3)
+    args = (P, E, generations, _arg("--eval-arenas", 64))
+    rest = (_arg("--poll-every", 8), _arg("--sample-every", 10), _arg("--event-steps", 200))
+    return {"what": "queue", "arenas": ARENAS, "ships": M, "layers": LAYERS, "sigma": SIGMA, "lr": LR,
+            "old": _queue_loop(*args, False, *rest), "new": _queue_loop(*args, True, *rest)}
+
+
 if __name__ == "__main__":
-    what = [x for x in sys.argv[1:] if x in ("kernels", "loop", "sigma")]
+    what = [x for x in sys.argv[1:] if x in ("kernels", "loop", "sigma", "queue")]
     if len(what) != 1:
         raise SystemExit(__doc__)
-    line = json.dumps({"kernels": kernels, "loop": loop, "sigma": sigma}[what[0]]())
+    line = json.dumps({"kernels": kernels, "loop": loop, "sigma": sigma, "queue": queue}[what[0]]())
     print(line, flush=True)
     if "--out" in sys.argv:
         with open(_arg("--out", ""), "a") as f:
